@@ -11,10 +11,19 @@ A "step" is one pass of the whole per-query hot path (seed -> chain -> refine ->
 PAF text) over THE WHOLE WORKLOAD the metric is quoted on: all 20 000 proteins, as 5 mini-batches of 4 000.  The K timed steps are
 K x 5 mini-batches handed to mpa_map_batches() as one stream (what miniprot's own batch loop, map.c:273-345, would call):
 pipeline fill and drain are inside the timed region (about 3 % of it at the driver's K = 20; `ms_per_mini_batch` is the old
-per-mini-batch figure).  Every output line of every timed step is compared with the reference's output for the same proteins
-(`paf_identical`).
+per-mini-batch figure).  With --full every output line of every timed step is compared with the reference's output for the same
+proteins (`paf_identical`).
+
+A plain run sets up, warms up, times the steps and prints the line.  --full adds what the headline figure does not need: the
+reference binary on the host cores (CPU baseline, `paf_identical`), the relinked command line end to end, and at N=1 the
+config-2, config-5 and 8 000-protein mini-batch records.  --dump-outputs DIR writes what the last timed step computed: its PAF
+lines (one pass over the protein set, rank 0) as DIR/paf_fields.npy -- float64, one row per line, the columns of PAF_COLUMNS,
+-1 where a line has no value -- and DIR/paf_line_md5.npy, float64, the first 48 bits of each whole line's md5 (CIGAR and the
+other string fields included).  Inputs are generated from fixed seeds, so two builds given the same arguments can be compared
+output for output.
 
     python bench.py                                    # N=1, config 3, 16 steps (16 passes over the 20 000 proteins)
+    python bench.py --full                             # ... and everything besides the headline figure
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N
 
 N>1 (BASELINE.json configs[3]).  `--scaling weak` (default, what the task's contract asks of a path that shards without a
@@ -23,11 +32,11 @@ proteins x K passes over 1/2/4/8 GPUs): the job is K passes whatever N is.  Eith
 distinct mini-batch j mod 5) are shared by the N ranks -- one process per GPU, index replicated, no collective on
 the data path.  The deal is dynamic: every rank's pipeline claims the next unclaimed batch of the job from a shared counter whenever
 it has room for one (mpa_map_batches_claim + miniprot_amd/dist.py; the work stealing of map.c:264-271, between processes); the
-output is gathered to rank 0 over RCCL in job order and every line of it is compared with the reference's (`paf_identical`, at any
-N).  `value` = aligned residues of all N x K batches / elapsed.  Rank 0 builds genome and index once; the other ranks restore the
+output is gathered to rank 0 over RCCL in job order and, with --full, every line of it is compared with the reference's
+(`paf_identical`, at any N).  `value` = aligned residues of all N x K batches / elapsed.  Rank 0 builds genome and index once; the other ranks restore the
 .mpi from /dev/shm.
-`--config 2` / `--config 5` run the 50 Mbp x 1k and the long-intron (-G 500k) workloads instead; at N=1 they are also
-recorded as extra keys of the config-3 line unless --no-extra.  Prints ONE JSON line on rank 0.
+`--config 2` / `--config 5` run the 50 Mbp x 1k and the long-intron (-G 500k) workloads instead; at N=1 with --full they are
+also recorded as extra keys of the config-3 line unless --no-extra.  Prints ONE JSON line on rank 0.
 """
 import argparse
 import hashlib
@@ -66,6 +75,40 @@ CONFIGS = {
 }
 
 
+# --dump-outputs: the numeric columns of a PAF line (PAF columns 2-4 and 6-12, the strand as +1/-1, the query as its index in
+# the protein set and the target as its contig index) followed by the integer tags miniprot writes
+PAF_COLUMNS = ("query", "qlen", "qstart", "qend", "strand", "target", "tlen", "tstart", "tend", "n_match", "block_len", "mapq",
+               "AS", "ms", "np", "fs", "st", "da", "do")
+
+
+def dump_outputs(out_dir, text, names):
+    """DIR/paf_fields.npy and DIR/paf_line_md5.npy of the PAF text of one step (see the module docstring)"""
+    qidx = {n.encode(): i for i, n in enumerate(names)}
+    tags = {t.encode(): PAF_COLUMNS.index(t) for t in PAF_COLUMNS[12:]}
+    lines = [l for l in text.split(b"\n") if l]
+    fields = np.full((len(lines), len(PAF_COLUMNS)), -1.0)
+    md5 = np.empty(len(lines))
+    for i, line in enumerate(lines):
+        f = line.split(b"\t")
+        row = fields[i]
+        row[0] = qidx.get(f[0], -1)
+        for c in (1, 2, 3, 6, 7, 8, 9, 10, 11):             # (PAF_COLUMNS follows the PAF's own column numbers up to mapq)
+            if len(f) > c and f[c].lstrip(b"-").isdigit():
+                row[c] = int(f[c])
+        if len(f) > 4:
+            row[4] = {b"+": 1.0, b"-": -1.0}.get(f[4], 0.0)
+        if len(f) > 5 and f[5].startswith(b"chr") and f[5][3:].isdigit():
+            row[5] = int(f[5][3:]) - 1
+        for t in f[12:]:
+            k = tags.get(t[:2])
+            if k is not None and t[2:5] == b":i:":
+                row[k] = int(t[5:])
+        md5[i] = int.from_bytes(hashlib.md5(line).digest()[:6], "big")
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "paf_fields.npy"), fields)
+    np.save(os.path.join(out_dir, "paf_line_md5.npy"), md5)
+
+
 def aligned_residues(paf):
     n = 0
     for line in paf.split(b"\n"):
@@ -93,7 +136,7 @@ class Workload:
     """Genome index + protein mini-batches of one config.  Rank 0 generates and indexes; with several ranks the index and the
     proteins travel through a directory in /dev/shm (mpa_idx_dump / mpa_idx_restore), so the host work is done once."""
 
-    def __init__(self, mpa, cfg, rank, world, barrier, share_dir, n_threads, scale=1.0, ctx=None):
+    def __init__(self, mpa, cfg, rank, world, barrier, share_dir, n_threads, scale=1.0, ctx=None, keep_files=True):
         from miniprot_amd import synth
         self.cfg, self.mpa = cfg, mpa
         t0 = time.time()
@@ -110,8 +153,9 @@ class Workload:
             # the k-mer table: scan + one radix sort on the GPU (mpa_idx_build_kmers_device), on the host cores if that declines
             self.index_built_on = self.idx.build_kmers(max(2, n_threads), ctx)
             self.t_index = time.time() - t1
-            synth.write_fasta_aa(faa, prots, names)
-            self.idx.dump(mpi)                                # for the other ranks and for the reference binary
+            if keep_files:                                    # for the other ranks, the reference binary and --workload-cache
+                synth.write_fasta_aa(faa, prots, names)
+                self.idx.dump(mpi)
         barrier()
         if rank != 0 or cached:
             self.idx = mpa.Index.restore(mpi)
@@ -342,10 +386,10 @@ def roofline_record(st, elapsed, world):
 
 
 def cli_end_to_end(wl, n_threads, cpu):
-    """The drop-in as a user runs it, cold: the reference's own main.c relinked against libmpamd.so (examples/_relink/miniprot)
+    """The drop-in as a user runs it, cold: the reference's own main.c relinked against libmpamd.so (oracle/_ref/relink/miniprot)
     on the same .mpi and protein file as the reference binary -- whole wall clock including index restore, upload to HBM, pool
     growth and pipeline fill (main.c:189-217, index.c:204-237) -- next to oracle/_ref/miniprot's whole wall clock, bytes compared."""
-    exe = os.path.join(ROOT, "examples", "_relink", "miniprot")
+    exe = os.path.join(ROOT, "oracle", "_ref", "relink", "miniprot")
     if not os.path.exists(exe) or cpu is None:
         return None
     env = dict(os.environ)
@@ -380,6 +424,10 @@ def main():
     ap.add_argument("--no-cli", action="store_true", help="skip the end-to-end run of the relinked miniprot command line (cli_end_to_end)")
     ap.add_argument("--debug-shared-gpu", action="store_true", help="(debug) all ranks on cuda:0 with the gloo backend: exercises the N>1 code path on a "
                     "one-GPU box; the line is NOT a scaling measurement")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: CPU baseline and output "
+                    "identity against the reference binary, the relinked command line, and (N=1, config 3) the config-2/config-5/8 000-protein records")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the PAF lines of the last timed step as DIR/paf_fields.npy and "
+                    "DIR/paf_line_md5.npy (float64; see the module docstring)")
     a = ap.parse_args()
 
     # --gpus N is a promise about the line's n_gpus.  Started plainly (no RANK in the environment) with N > 1 the script launches
@@ -454,7 +502,7 @@ def main():
     base = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else "/tmp"
     share_root = os.path.join(base, "mpa_bench_%s" % os.environ.get("MASTER_PORT", str(os.getpid())))
 
-    def run_config(cid, steps, warmup, with_cpu, batch=0, keep_share=False):
+    def run_config(cid, steps, warmup, with_cpu, batch=0, keep_share=False, dump=""):
         cfg = dict(CONFIGS[cid])
         if batch > 0:
             cfg["batch"] = batch
@@ -465,7 +513,7 @@ def main():
             os.makedirs(share, exist_ok=True)
         barrier()
         ctx = mpa.Context(local_rank)
-        wl = Workload(mpa, cfg, rank, world, barrier, share, n_threads, a.scale, ctx)
+        wl = Workload(mpa, cfg, rank, world, barrier, share, n_threads, a.scale, ctx, keep_files=a.full or world > 1 or bool(a.workload_cache))
         wl.idx.to_device(ctx)
         weak = a.scaling == "weak"
         elapsed, texts, st = measure(mpa, mdist, wl, ctx, steps, warmup, n_threads, rank, world, device, sync, weak)
@@ -488,6 +536,8 @@ def main():
                     res_of[k % nb] = aligned_residues(t)
                 residues += res_of[k % nb]
             one_pass = b"".join(texts[k] for k in range(min(nb, len(texts))))
+            if dump:
+                dump_outputs(dump, b"".join(texts[-nb:]), wl.names)
             cpu, identical, ident = None, None, None
             if with_cpu and not a.no_cpu_baseline:
                 # the reference itself on this box's host cores, outside the timed region: every output line of every timed step of
@@ -545,8 +595,8 @@ def main():
             shutil.rmtree(share, ignore_errors=True)
         return rec
 
-    want_extra = world == 1 and a.config == 3 and not a.no_extra and a.scale == 1.0
-    main_rec = run_config(a.config, a.steps, a.warmup, with_cpu=True, keep_share=want_extra and a.batch == 0)
+    want_extra = a.full and world == 1 and a.config == 3 and not a.no_extra and a.scale == 1.0
+    main_rec = run_config(a.config, a.steps, a.warmup, with_cpu=a.full, keep_share=want_extra and a.batch == 0, dump=a.dump_outputs)
     extra = {}
     if want_extra and a.batch == 0:
         # the same workload (index and proteins of the headline run, restored from its share directory) with 8 000 proteins per

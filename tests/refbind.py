@@ -16,9 +16,8 @@ ORA_SO = os.path.join(ORACLE_DIR, "libmporacle.so")
 
 
 def build_oracle():
-    subprocess.run(["make", "-s", "-C", ORACLE_DIR, "oracle"], check=True)
-    if os.path.isdir("/root/reference"):
-        subprocess.run(["make", "-s", "-C", ORACLE_DIR, "ref"], check=True)
+    # (`ref` builds the reference where its sources are, and keeps the prebuilt oracle/_ref/ elsewhere: oracle/Makefile)
+    subprocess.run(["make", "-s", "-C", ORACLE_DIR, "oracle", "ref"], check=True)
 
 
 def have_ref():

@@ -1,6 +1,6 @@
 """The reference's own interface (include/miniprot.h, include/nasw.h) as exported by libmpamd.so: record layouts,
-tables, and the reference's own programs -- example.c and main.c, compiled UNCHANGED from /root/reference by
-examples/Makefile -- relinked against this library.  CPU part: layouts, genetic codes, index files.  GPU part: the
+tables, and the reference's own programs -- example.c and main.c, compiled UNCHANGED from the reference's sources by
+oracle/Makefile (oracle/_ref/relink/) -- relinked against this library.  CPU part: layouts, genetic codes, index files.  GPU part: the
 relinked programs and ns_global_gs16b() produce the reference's bytes."""
 import ctypes as C
 import hashlib
@@ -14,7 +14,7 @@ import golden
 import gen_synth
 
 ROOT = refbind.ROOT
-RELINK = os.path.join(ROOT, "examples", "_relink")
+RELINK = os.path.join(ROOT, "oracle", "_ref", "relink")
 CLI, LITE = os.path.join(RELINK, "miniprot"), os.path.join(RELINK, "miniprot-lite")
 REF_LITE = os.path.join(ROOT, "oracle", "_ref", "miniprot-lite")
 
@@ -49,13 +49,13 @@ def _layout(tmp_path, incdirs, tag):
 
 def test_reference_records_have_the_reference_layout(tmp_path):
     """include/miniprot.h + include/nasw.h compile as plain C99 and describe the reference's ABI: the sizes SURVEY.md 8(b)
-    measured on the reference (104/48/56/656/96/32/20) and, where /root/reference is present, every probed offset"""
+    measured on the reference (104/48/56/656/96/32/20) and every probed offset of the reference's own headers
+    (tests/golden/ref_layout.txt, the same probe compiled against them by tools/make_golden.py)"""
     ours = _layout(tmp_path, [os.path.join(ROOT, "include")], "ours")
     d = dict(l.rsplit(" ", 1) for l in ours.splitlines() if not l.startswith("flags"))
     assert (d["mp_reg1_t"], d["mp_extra_t"], d["mp_feat_t"], d["mp_mapopt_t"], d["ns_opt_t"], d["ns_rst_t"], d["mp_idxopt_t"]) == \
         ("104", "48", "56", "656", "96", "32", "20")
-    if os.path.isdir("/root/reference"):
-        assert ours == _layout(tmp_path, ["/root/reference"], "ref")
+    assert ours == open(golden.path("ref_layout.txt")).read()
 
 
 @pytest.mark.skipif(not refbind.have_ref(), reason="compiled reference not available")
@@ -129,7 +129,7 @@ def _run(cmd):
 
 @pytest.mark.gpu
 def test_relinked_example_prints_the_reference_lines():
-    """/root/reference/example.c, unchanged, compiled against include/miniprot.h and linked with -lmpamd: mp_idx_load +
+    """the reference's example.c, unchanged, compiled against include/miniprot.h and linked with -lmpamd: mp_idx_load +
     mp_map per query + the caller freeing ->p -- same lines as the reference's miniprot-lite on DPP3"""
     args = [golden.path("DPP3-hs.gen.fa.gz"), golden.path("DPP3-mm.pep.fa.gz")]
     assert _run([LITE] + args) == _run([REF_LITE] + args)

@@ -44,11 +44,11 @@ def test_two_pipelines_of_one_process_equal_one_pipeline():
 
 
 def test_relinked_reference_cli_maps_on_a_device_list(tmp_path):
-    """The reference's own main.c, relinked (examples/_relink/miniprot), with MPA_DEVICES=0,0: mp_map_file() runs two pipelines and
+    """The reference's own main.c, relinked (oracle/_ref/relink/miniprot), with MPA_DEVICES=0,0: mp_map_file() runs two pipelines and
     prints the bytes of the one-pipeline run."""
-    exe = os.path.join(refbind.ROOT, "examples", "_relink", "miniprot")
+    exe = os.path.join(refbind.ROOT, "oracle", "_ref", "relink", "miniprot")
     if not os.path.exists(exe):
-        pytest.skip("examples/_relink/miniprot is built where /root/reference exists")
+        pytest.skip("oracle/_ref/relink/miniprot is built where the reference's sources exist")
     mpa, golden, case, idx, batches, prots, names = _job()
     mpi = str(tmp_path / "g.mpi")
     faa = str(tmp_path / "p.faa")
@@ -81,9 +81,9 @@ def test_eight_pipelines_on_one_device(tmp_path):
     the one-pipeline run and of the reference, and the host CPU the eight pipelines take (recorded, not asserted)."""
     import time
     import resource
-    exe = os.path.join(refbind.ROOT, "examples", "_relink", "miniprot")
+    exe = os.path.join(refbind.ROOT, "oracle", "_ref", "relink", "miniprot")
     if not os.path.exists(exe):
-        pytest.skip("examples/_relink/miniprot is built where /root/reference exists")
+        pytest.skip("oracle/_ref/relink/miniprot is built where the reference's sources exist")
     mpa, golden, case, idx, batches, prots, names = _job()
     mpi = str(tmp_path / "g.mpi")
     faa = str(tmp_path / "p.faa")

@@ -7,6 +7,8 @@ oracle/Makefile).  Run in the authoring container only; the outputs are committe
   * dp_vectors.npz: random DP calls with the reference's ns_global_gs16b() answers (all three modes)
   * gs32_vectors.npz: calls of the 32-bit operator (ns_global_gs32b, -msse4.1 build of the reference): `make_golden.py gs32` makes only these
   * chain_vectors.npz / sketch vectors: anchor sets with the reference's mp_chain() output
+  * ref_layout.txt: sizes and offsets of the reference's records as its own headers declare them (tests/test_compat.py):
+    `make_golden.py layout <reference source dir>` makes only this
 """
 import os
 import shutil
@@ -52,7 +54,22 @@ def make_gs32_vectors():
     print("gs32_vectors", len(flags), "calls,", sum(1 for x in scores if x > 32767), "with scores beyond int16")
 
 
+def make_layout(ref_dir):
+    """tests/golden/ref_layout.txt: what test_compat's layout probe prints when compiled against the reference's own headers"""
+    import test_compat
+    with tempfile.TemporaryDirectory() as tmp:
+        src, exe = os.path.join(tmp, "layout.c"), os.path.join(tmp, "layout")
+        open(src, "w").write(test_compat.LAYOUT_PROG)
+        subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + ref_dir, src, "-o", exe], check=True)
+        out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout
+    open(golden.path("ref_layout.txt"), "w").write(out)
+    print("ref_layout", out.count("\n"), "lines")
+
+
 def main():
+    if len(sys.argv) > 2 and sys.argv[1] == "layout":
+        make_layout(sys.argv[2])
+        return
     refbind.build_oracle()
     if len(sys.argv) > 1 and sys.argv[1] == "gs32":
         make_gs32_vectors()

@@ -8,13 +8,13 @@ export TMPDIR=/tmp
 OUT=${1:-gpurun_out/r05_final}
 mkdir -p $OUT
 WL=/dev/shm/mpa_wl
-(time python bench.py --steps 20 --warmup 5 --workload-cache $WL) > $OUT/bench.json 2> $OUT/bench.err; python tools/bench_line.py $OUT/bench.json "bench (driver settings)"
+(time python bench.py --steps 20 --warmup 5 --full --workload-cache $WL) > $OUT/bench.json 2> $OUT/bench.err; python tools/bench_line.py $OUT/bench.json "bench (driver settings)"
 (time python -m pytest tests -m gpu -q) > $OUT/pytest_gpu.log 2>&1; grep -h "passed\|failed" $OUT/pytest_gpu.log | tail -2
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log | cut -c1-100
 # cold start of the drop-in, with the library's timing notes (index restore, uploads, pool growth, first batches)
-if [ -x examples/_relink/miniprot ] && [ -f $WL/c3/g.mpi ]; then
-  ( export LD_LIBRARY_PATH=$PWD/miniprot_amd:$LD_LIBRARY_PATH; /usr/bin/time -v env MPA_TIMING=1 examples/_relink/miniprot -t16 -I -u $WL/c3/g.mpi $WL/c3/p.faa > /tmp/cli.paf ) 2> $OUT/cli_cold_timing.err
-  { echo "# examples/_relink/miniprot -t16 -I -u g.mpi p.faa (config 3, 20 000 proteins), cold, MPA_TIMING=1: the reference's own progress lines carry wall clock @ CPU share"; grep -E "^\[M::|index upload|pool growth|Elapsed|Maximum resident" $OUT/cli_cold_timing.err | head -60; python tools/timing_agg.py < $OUT/cli_cold_timing.err 2>/dev/null | grep -E "index upload|pool growth|seeding on the GPU|mpa_dp_run|stage A" ; md5sum /tmp/cli.paf; } > $OUT/cli_cold_start.txt 2>&1
+if [ -x oracle/_ref/relink/miniprot ] && [ -f $WL/c3/g.mpi ]; then
+  ( export LD_LIBRARY_PATH=$PWD/miniprot_amd:$LD_LIBRARY_PATH; /usr/bin/time -v env MPA_TIMING=1 oracle/_ref/relink/miniprot -t16 -I -u $WL/c3/g.mpi $WL/c3/p.faa > /tmp/cli.paf ) 2> $OUT/cli_cold_timing.err
+  { echo "# oracle/_ref/relink/miniprot -t16 -I -u g.mpi p.faa (config 3, 20 000 proteins), cold, MPA_TIMING=1: the reference's own progress lines carry wall clock @ CPU share"; grep -E "^\[M::|index upload|pool growth|Elapsed|Maximum resident" $OUT/cli_cold_timing.err | head -60; python tools/timing_agg.py < $OUT/cli_cold_timing.err 2>/dev/null | grep -E "index upload|pool growth|seeding on the GPU|mpa_dp_run|stage A" ; md5sum /tmp/cli.paf; } > $OUT/cli_cold_start.txt 2>&1
   tail -5 $OUT/cli_cold_start.txt
 fi
 # kernel trace of the bench command (shorter job)
@@ -56,7 +56,7 @@ except Exception as e: print("pmc summary:", repr(e)[:200])
 PY
 # the N = 2 code path with both ranks on this one GPU (gloo; NOT a scaling number): identity at N > 1, dynamic deal, both scaling modes
 for SC in weak strong; do
-  ( HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29655 bench.py --gpus 2 --debug-shared-gpu --scaling $SC --batch 1000 --steps 1 --warmup 1 --no-extra --no-cli --threads 8 --workload-cache $WL ) > $OUT/bench_n2_shared_gpu_debug_$SC.json 2> $OUT/n2_$SC.err
+  ( HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29655 bench.py --gpus 2 --debug-shared-gpu --full --scaling $SC --batch 1000 --steps 1 --warmup 1 --no-extra --no-cli --threads 8 --workload-cache $WL ) > $OUT/bench_n2_shared_gpu_debug_$SC.json 2> $OUT/n2_$SC.err
   python tools/bench_line.py $OUT/bench_n2_shared_gpu_debug_$SC.json "N=2 shared GPU (debug, $SC)"
   tail -2 $OUT/n2_$SC.err | cut -c1-200
 done

@@ -11,7 +11,7 @@ mkdir -p $OUT
 WL=/dev/shm/mpa_wl
 has() { [[ " $WHAT " == *" $1 "* ]]; }
 if has bench; then
-  (time python bench.py --gpus 1 --steps 20 --warmup 5 --workload-cache $WL) > $OUT/bench.json 2> $OUT/bench.err; python tools/bench_line.py $OUT/bench.json "bench (driver settings)"
+  (time python bench.py --gpus 1 --steps 20 --warmup 5 --full --workload-cache $WL) > $OUT/bench.json 2> $OUT/bench.err; python tools/bench_line.py $OUT/bench.json "bench (driver settings)"
 else
   python bench.py --no-extra --no-cpu-baseline --no-cli --steps 1 --warmup 1 --workload-cache $WL > /dev/null 2>&1
 fi
@@ -64,7 +64,7 @@ fi
 if has cold; then bash tools/r05_cold.sh $OUT/cold > /dev/null 2>&1; cp $OUT/cold/cli_cold_start.txt $OUT/cli_cold_start.txt; tail -12 $OUT/cli_cold_start.txt; fi
 if has n2; then
   for SC in weak strong; do
-    ( HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python bench.py --gpus 2 --debug-shared-gpu --scaling $SC --batch 1000 --steps 1 --warmup 1 --no-extra --no-cli --threads 8 --workload-cache $WL ) > $OUT/bench_n2_shared_gpu_debug_$SC.json 2> $OUT/n2_$SC.err
+    ( HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python bench.py --gpus 2 --debug-shared-gpu --full --scaling $SC --batch 1000 --steps 1 --warmup 1 --no-extra --no-cli --threads 8 --workload-cache $WL ) > $OUT/bench_n2_shared_gpu_debug_$SC.json 2> $OUT/n2_$SC.err
     python tools/bench_line.py $OUT/bench_n2_shared_gpu_debug_$SC.json "N=2 shared GPU (debug, $SC; bench.py spawned its own ranks)"
     tail -2 $OUT/n2_$SC.err | cut -c1-200
   done

@@ -15,12 +15,12 @@ for kv in sys.argv[2:]:
     k, v = kv.split("=", 1); env[k] = v
 wl = "/dev/shm/mpa_wl/c3"
 t = time.time()
-p = subprocess.run(["examples/_relink/miniprot", "-t16", "-I", "-u", wl + "/g.mpi", wl + "/p.faa"], stdout=subprocess.PIPE, stderr=open(err, "w"), env=env)
+p = subprocess.run(["oracle/_ref/relink/miniprot", "-t16", "-I", "-u", wl + "/g.mpi", wl + "/p.faa"], stdout=subprocess.PIPE, stderr=open(err, "w"), env=env)
 print("   whole process %.2f s, rc %d, md5 %s" % (time.time() - t, p.returncode, hashlib.md5(p.stdout).hexdigest()))
 PY
 }
 {
-echo "# examples/_relink/miniprot -t16 -I -u g.mpi p.faa (config 3: 3 Gbp, 20 000 proteins = 4 mini-batches of the reference's default -K 2M), one MI355X"
+echo "# oracle/_ref/relink/miniprot -t16 -I -u g.mpi p.faa (config 3: 3 Gbp, 20 000 proteins = 4 mini-batches of the reference's default -K 2M), one MI355X"
 for spec in "plain:" "plain_again:" "timing:MPA_TIMING=1" "fast_exit:MPA_FAST_EXIT=1" "fast_exit_again:MPA_FAST_EXIT=1"; do
   name=${spec%%:*}; vars=${spec#*:}
   echo "## $name $vars"

@@ -1,10 +1,11 @@
 #!/bin/bash
 cd "${GRAFT_REPO_ROOT:-.}"
-mkdir -p gpurun_out/r06_wide /tmp/wl
-python bench.py --gpus 1 --steps 20 --warmup 5 --workload-cache /tmp/wl > gpurun_out/r06_wide/bench.json 2> gpurun_out/r06_wide/bench.err; tail -3 gpurun_out/r06_wide/bench.err
+export OUT=${OUT:?set OUT to the directory for this run's files}
+mkdir -p $OUT /tmp/wl
+python bench.py --gpus 1 --steps 20 --warmup 5 --full --workload-cache /tmp/wl > $OUT/bench.json 2> $OUT/bench.err; tail -3 $OUT/bench.err
 python - <<'PY'
-import json
-d=json.loads(open('gpurun_out/r06_wide/bench.json').read().strip().splitlines()[-1])
+import json, os
+d=json.loads(open(os.path.join(os.environ['OUT'], 'bench.json')).read().strip().splitlines()[-1])
 print(d['value'], d['ms_per_step'], d['paf_identical'], d['hbm_resident_gb'], d['cli_end_to_end']['wall_s'], d['config5']['value'], d['config5']['paf_identical'], d['config2']['value'])
 print(d['roofline']['avg_launch_ms'], d['roofline']['frac'], d['rounds_in_flight_avg'], d['dp_wall_ms_per_batch'], d['seeding_wall_ms_per_batch'])
 PY
