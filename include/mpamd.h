@@ -181,7 +181,7 @@ typedef struct {
 	double ms_round_union;                       /* worker pool: time during which at least one worker launch of the DEVICE was running
 	                                              * (the union of the launches' intervals; the stream's rounds overlap) -- what one
 	                                              * persistent kernel's duration would be.  0 unless MPA_DP_POOL=1. */
-	/* checkpointed traceback (traceback calls of <= 64 columns and >= MPA_DP_LITE_MIN rows): calls and padded cells swept by the
+	/* checkpointed traceback (traceback calls of <= 128 columns and >= MPA_DP_LITE_MIN rows): calls and padded cells swept by the
 	 * packed sweep, and the blocks of 96 rows whose traceback words the walk recomputed */
 	int64_t n_ckpt, cells_ckpt, walk_blocks;
 } mpa_dp_stats_t;

@@ -165,6 +165,7 @@ struct mpa_ctx_s {
 	mpa_dp_stats_t stats = {};
 	mpa_dp_stats_t total = {};
 	size_t tb_budget = (size_t)8 << 30;       // bytes of traceback matrix per k_glob launch
+	int lite_min = 384;                       // rows from which a traceback call of <= 128 columns is checkpointed (MPA_DP_LITE_MIN; 0: never)
 	std::vector<mpa_ctx_s*> siblings;         // extra contexts on the same device for concurrent sub-batches (owned)
 	SeedBufs seed;                            // buffers of the GPU seeding stage (seed_exec.hip)
 	hipEvent_t wait_ev = nullptr;             // blocking-sync event: a host thread that waits for the device SLEEPS (wait_stream)
@@ -441,6 +442,7 @@ mpa_ctx_t *mpa_ctx_create(int device)
 		return nullptr;
 	}
 	if (const char *s = getenv("MPA_TB_BUDGET_MB")) ctx->tb_budget = (size_t)atoll(s) << 20;
+	if (const char *s = getenv("MPA_DP_LITE_MIN")) ctx->lite_min = atoi(s);
 	return ctx;
 }
 
@@ -495,6 +497,7 @@ mpa_ctx_t *ctx_sibling(mpa_ctx_t *ctx, int k)
 		mpa_ctx_t *sb = mpa_ctx_create(ctx->device);
 		if (!sb) return nullptr;
 		sb->tb_budget = ctx->tb_budget;
+		sb->lite_min = ctx->lite_min;
 		sb->root = ctx;
 		ctx->siblings.push_back(sb);
 	}
@@ -1536,16 +1539,16 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 		// have their own bound, may_saturate)
 		const bool seg_overflow = (int64_t)t.ncol * opt->ge >= (1 << 19);
 		const bool is_ext = (x.flag & (MPA_F_EXT_LEFT | MPA_F_EXT_RIGHT)) != 0;
+		// The packed int16 kernels run their gap scan on h + j*ge with saturating adds and hold go + j*ge in int16, which is only the
+		// reference's value while nothing can reach the int16 limits.  Calls that could -- with BLOSUM62 and ge = 1 more than ~2900
+		// columns, always of the "huge" class; with a large -E or -O already at a few dozen columns -- go to the int32 sweeps, which
+		// clamp every operation like the reference does: k_ext_huge for extension calls, the plain traceback sweep for the others.
+		const bool may_saturate = (int64_t)x.al * max_mat + (int64_t)t.ncol * opt->ge + std::max(0, opt->end_bonus) > 32000 || opt->go + (int64_t)t.ncol * opt->ge > 32000;
 		if (is_ext) {
 			int cls = ext_class_of(t.ncol);                        // -1: wider than k_ext_wide<16> covers -> k_ext_huge (class 7)
 			if (ctx->no_split && cls >= 5) cls = -1;               // repeated round: no inter-workgroup hand-off (see mpa_dp_run)
-			if (wide_ge) cls = -1;
+			if (wide_ge || may_saturate) cls = -1;
 			if (cls < 0 && seg_overflow) { set_error("DP call " + std::to_string(k) + ": too wide for this gap-extension penalty (columns x ge must stay below 2^19 in the int32 sweeps)"); return MPA_ERR_UNSUPPORTED; }
-			// The packed kernels run their gap scan on h + j*ge with saturating adds, which is only the reference's value while
-			// nothing can reach the int16 limits; calls that could (more than ~2900 columns with BLOSUM62, hence always of the
-			// "huge" class) are swept by k_ext_huge, whose int32 arithmetic clamps every operation like the reference does.
-			const bool may_saturate = (int64_t)x.al * max_mat + (int64_t)t.ncol * opt->ge + std::max(0, opt->end_bonus) > 32000 || opt->go + (int64_t)t.ncol * opt->ge > 32000;
-			if (may_saturate && cls >= 0) { set_error("extension call could saturate int16 in the packed kernels; not supported with these scores"); return MPA_ERR_UNSUPPORTED; }
 			t.pw = cls >= 0 ? kExtClasses[cls].G * kExtClasses[cls].NB : t.ncol;
 			t.pad_ = cls >= 0 ? cls : 7;
 			// 65..128 columns: one wave per call, column c + 64 in the high half of lane c (ext_narrow<64, false, true>, class 8), instead
@@ -1559,12 +1562,12 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 			if (seg_overflow) { set_error("DP call " + std::to_string(k) + ": too wide for this gap-extension penalty (columns x ge must stay below 2^19 in the int32 sweeps)"); return MPA_ERR_UNSUPPORTED; }
 			t.pw = t.ncol;
 			t.pad_ = t.ncol <= 16 ? 0 : t.ncol <= 32 ? 1 : t.ncol <= 64 ? 2 : t.ncol <= 128 ? 3 : t.ncol <= 256 ? 4 : t.ncol <= 512 ? 5 : t.ncol <= 1024 ? 6 : 7;
-			// Checkpointed traceback (dp_device.h): a call of up to 64 columns and many rows -- the gap fills across introns and the spans
+			// Checkpointed traceback (dp_device.h): a call of up to 128 columns and many rows -- the gap fills across introns and the spans
 			// of accepted extensions, where nearly every row lies inside an intron -- is swept by the packed sweep (classes 8, 9, 10: 16,
-			// 32, 64 lanes per call, two calls per lane) and walked by k_walk.  Short calls stay on the plain traceback sweep: the walk
-			// would recompute all of their rows anyway.  MPA_DP_LITE_MIN (rows; 0: never).
-			static const int lite_min = [] { const char *e = getenv("MPA_DP_LITE_MIN"); return e ? atoi(e) : 384; }();
-			if (lite_min > 0 && !wide_ge && t.ncol <= 128 && x.nl >= lite_min && x.nl >= 3) t.pad_ += 8, t.pw = 16 << (t.pad_ - 8);   // (class 11: 65..128 columns, one call per wave)
+			// 32, 64 lanes per call, two calls per lane; class 11: one call per wave) and walked by k_walk.  Short calls stay on the plain
+			// traceback sweep: the walk would recompute all of their rows anyway.  MPA_DP_LITE_MIN (rows; 0: never), read when the context
+			// is created.  The packed sweep is an int16 one: calls that may saturate stay on the plain sweep too.
+			if (ctx->lite_min > 0 && !wide_ge && !may_saturate && t.ncol <= 128 && x.nl >= ctx->lite_min && x.nl >= 3) t.pad_ += 8, t.pw = 16 << (t.pad_ - 8);   // (class 11: 65..128 columns, one call per wave)
 			glob_ids.push_back((int32_t)k);
 		}
 	}

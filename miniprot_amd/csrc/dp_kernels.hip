@@ -840,7 +840,7 @@ __device__ __forceinline__ void ext_narrow(const ExtArgs &a, const ExtWave *wvp,
 	//     H_w >= Gs - xdrop + pen - eb (and 32767 - pen >= Gs - xdrop) proves m >= cand_w >= Gs - xdrop.
 	// Whenever a bound does not fit int16 (absurd ie_coef / x-drop: never with the reference's defaults), or a call has no witness
 	// yet, the thresholds are set so that EVERY row votes: lo = 32767, hi = -32768 makes the clamp return 32767 in every lane,
-	// and H stays below 32 000 in the packed kernels (dp_exec.hip refuses calls that could saturate).
+	// and H stays below 32 000 in the packed kernels (dp_exec.hip sends calls that could saturate to the int32 sweeps).
 	auto repack = [&](const ExtCall (&e)[2], const int col_) {
 		int32_t gl[2], tl[2];
 		bool force = false, any = false;

@@ -92,3 +92,60 @@ def make_ss(rng, nl, density=0.02):
     acc = rng.integers(0, 2, len(idx))
     ss[idx] = ((sc + 64) << 1 | acc).astype(np.uint8)
     return bytes(ss)
+
+
+# Scoring points between miniprot's defaults and the limits mpa_dp_run() accepts (dp_exec.hip: go, io, xdrop <= 32000, ge, fs <= 16000,
+# end_bonus <= 1000; the reference's command line takes any -O/-E/-J/-B/--xdrop, main.c:132-150): one parameter at a time, then
+# combinations.  Keyword arguments of refbind.DpParams; a point with fs also needs refbind.mapping_matrix(min(fs, 127)).
+PENALTY_POINTS = [
+    dict(ge=4), dict(ge=40), dict(ge=120), dict(ge=200), dict(ge=255),
+    dict(go=200), dict(go=2000), dict(go=20000), dict(go=32000),
+    dict(io=200), dict(io=5000), dict(io=32000),
+    dict(xdrop=0), dict(xdrop=1), dict(xdrop=2000), dict(xdrop=32000),
+    dict(end_bonus=100), dict(end_bonus=1000),
+    dict(fs=60), dict(fs=255),
+    dict(sp=(40, 60, 80, 100, 12, 12), ie_coef=1.0),
+    dict(go=20000, ge=100), dict(ge=250, io=5000, xdrop=32000, end_bonus=1000), dict(io=32000, ge=200),
+]
+
+# al on both sides of every lane-class boundary of the DP kernels (extension: 16 / 32 / 64 lanes, 65..128 in one wave, 2 / 4 / 8 / 16
+# blocks of 64 columns, then k_ext_huge)
+CLASS_EDGES = (8, 16, 17, 32, 33, 64, 65, 128, 129, 256, 257, 512, 513, 1024, 1025)
+
+# Calls at the int16 bound of the packed kernels (dp_exec.hip, may_saturate: al * max_mat + ncol * ge + max(0, end_bonus) > 32000 or
+# go + ncol * ge > 32000, with ncol = 8 * ceil(al / 8)).  (al, parameters, the parameter to raise by one): with BLOSUM62 (max_mat 11)
+# the larger of the two sums is exactly 32000 for a call of al columns, and 32001 once `key` is raised by one.  The score sum decides
+# the first five, go + ncol * ge the others; the al cover every extension class and every lane class of the checkpointed sweep, with
+# and without padded lanes.
+BOUND_CASES = [
+    (128, dict(ge=239, end_bonus=0), "end_bonus"),
+    (136, dict(ge=224, end_bonus=40), "end_bonus"),
+    (256, dict(ge=114, end_bonus=0), "end_bonus"),
+    (512, dict(ge=51, end_bonus=256), "end_bonus"),
+    (1024, dict(ge=20, end_bonus=256), "end_bonus"),
+    (16, dict(go=31952, ge=3), "go"),
+    (24, dict(go=29600, ge=100), "go"),
+    (40, dict(go=31800, ge=5), "go"),
+    (64, dict(go=31360, ge=10), "go"),
+    (72, dict(go=31424, ge=8), "go"),
+    (128, dict(go=31744, ge=2), "go"),
+    (300, dict(go=31392, ge=2), "go"),
+    (520, dict(go=16400, ge=30), "go"),
+    (1024, dict(go=30976, ge=1), "go"),
+]
+
+
+def bound_params(case, over):
+    """keyword arguments of BOUND_CASES[k] with the decisive sum at 32000 + over"""
+    al, kw, key = case
+    kw = dict(kw)
+    kw[key] += over
+    return kw
+
+
+def long_window(rng, al, p_indel=0.02):
+    """a traceback-shaped call of al residues whose window has at least 384 rows (introns and flanks)"""
+    while True:
+        nt, aa = make_task(rng, al=al, max_intron=1000, flank=400, p_intron=0.05, p_indel=p_indel)
+        if len(nt) >= 384:
+            return nt, aa

@@ -153,7 +153,7 @@ def test_relinked_cli_is_a_drop_in(tmp_path):
     # records' byte; -F is held to an int8 by the reference itself, options.c:26, so a frameshift penalty above 255 can only arrive
     # through the operator, ns_opt_t: tests/test_dp_gpu.py)
     for flags in (["-u"], ["-u", "-I", "--gtf"], ["-u", "--gff", "--outs=0.5", "-N", "50", "-K", "3k"], ["-u", "-S"], ["-u", "-T", "4", "--aln", "--trans"],
-                  ["-u", "-E", "300"], ["-u", "-E", "260", "-O", "9"]):     # (with -F 60..100 next to -E 260 the reference aborts in its own mp_extra_cal assertion -- and so does this)
+                  ["-u", "-E", "300"], ["-u", "-E", "260", "-O", "9"], ["-u", "-E", "120", "-O", "30"], ["-u", "--xdrop", "20000", "-B", "500"]):     # (with -F 60..100 next to -E 260 the reference aborts in its own mp_extra_cal assertion -- and so does this)
         src = [fa] if "-T" in flags else [mpi]                      # (-T changes the index: build it from the FASTA)
         assert _run([CLI, "-t8"] + flags + src + [faa]) == _run([refbind.REF_BIN, "-t8"] + flags + src + [faa]), " ".join(flags)
 

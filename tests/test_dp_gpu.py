@@ -238,9 +238,11 @@ def test_checkpointed_traceback(oracle_built, monkeypatch):
     traceback words of a block only where the path needs them.  CIGARs and scores against the oracle for every lane class (16 /
     32 / 64 lanes per call, full and partly filled waves; 65..128 columns: one call per wave, column c + 64 in the high half of lane c), paths that change state right at block boundaries (several block
     phases through the flank), introns of all phases, frameshifts, indels, N runs; and with the row threshold lowered so that
-    calls of a single block and of two blocks go the same way."""
+    calls of a single block and of two blocks go the same way.  The threshold is read when a context is created: every context
+    here counts exactly the calls of at least that many rows as checkpointed, and with "0" none."""
     P = refbind.DpParams(refbind.mapping_matrix(23))
-    for lite_min, seed in (("384", 31), ("3", 32), ("100", 33)):
+    n_ckpt = {}
+    for lite_min, seed in (("384", 31), ("3", 32), ("100", 33), ("0", 35)):
         monkeypatch.setenv("MPA_DP_LITE_MIN", lite_min)
         rng = np.random.default_rng(seed)
         pairs = []
@@ -250,9 +252,15 @@ def test_checkpointed_traceback(oracle_built, monkeypatch):
         pairs += [make_task(rng, max_intron=2500, flank=400, p_fs=0.05, p_indel=0.06, p_n=0.01) for _ in range(150)]
         pairs += [make_task(rng, al=int(rng.integers(1, 129)), max_intron=20000, flank=50, p_intron=0.1) for _ in range(16)]
         pairs += [make_task(rng, al=int(rng.integers(65, 129)), max_intron=2500, flank=400, p_fs=0.05, p_indel=0.06, p_n=0.01) for _ in range(60)]
+        if lite_min == "0":
+            pairs = pairs[::4]
         c2 = mpa.Context(0)
         run_case(c2, pairs, P, rng, modes=("cigar",))
+        n_ckpt[lite_min] = c2.dp_stats()["n_ckpt"]
         c2.close()
+        lm = int(lite_min)
+        assert n_ckpt[lite_min] == sum(lm > 0 and len(nt) >= max(lm, 3) and len(aa) <= 128 for nt, aa in pairs), (lite_min, n_ckpt[lite_min])
+    assert n_ckpt["0"] == 0 and n_ckpt["3"] > n_ckpt["384"] > 0, n_ckpt
     # other scoring: the bits follow the penalties (gap extension 2, intron open 40, mammalian splice model)
     monkeypatch.setenv("MPA_DP_LITE_MIN", "200")
     rng = np.random.default_rng(34)

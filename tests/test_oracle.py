@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import refbind
 import golden
-from dpgen import make_task, make_ss
+from dpgen import make_task, make_ss, long_window, PENALTY_POINTS, BOUND_CASES, CLASS_EDGES, bound_params
 
 
 def test_dp_oracle_matches_golden_vectors(oracle_built):
@@ -26,6 +26,28 @@ def test_dp_oracle_matches_golden_vectors(oracle_built):
         assert got == want, "vector %d flag %d" % (k, z["flag"][k])
 
 
+def _penalty_params(kw):
+    return refbind.DpParams(refbind.mapping_matrix(min(kw.get("fs", 23), 127)), **kw)
+
+
+def test_dp_oracle_matches_golden_vectors_across_the_penalty_range(oracle_built):
+    """the reference's answers (tools/make_golden.py penalties) at every point of dpgen.PENALTY_POINTS and on both sides of every
+    int16 bound case: the pin of the oracle where the GPU tests of those scores use it, without the compiled reference"""
+    z = np.load(golden.path("dp_vectors_penalties.npz"))
+    nt_off, aa_off, ss_off, cg_off = (np.concatenate([[0], np.cumsum(z[k])]) for k in ("nt_len", "aa_len", "ss_len", "cig_len"))
+    n = len(z["flag"])
+    assert n >= 250
+    for k in range(n):
+        go, ge, io, fs, xdrop, eb = (int(x) for x in z["par"][k][:6])
+        P = refbind.DpParams(z["mat"][k], go=go, ge=ge, io=io, fs=fs, xdrop=xdrop, end_bonus=eb, sp=[int(x) for x in z["par"][k][6:12]],
+                             ie_coef=float(z["ie_coef"][k]))
+        i = int(z["pair"][k])
+        ss = bytes(z["ss"][ss_off[i]:ss_off[i + 1]]) if z["ss_len"][i] else None
+        got = refbind.ora_nasw(bytes(z["nt"][nt_off[i]:nt_off[i + 1]]), bytes(z["aa"][aa_off[i]:aa_off[i + 1]]), P, int(z["flag"][k]), ss)
+        want = (int(z["res"][k][0]), int(z["res"][k][1]), int(z["res"][k][2]), [int(x) for x in z["cig"][cg_off[k]:cg_off[k + 1]]])
+        assert got == want, "vector %d flag %d par %s" % (k, z["flag"][k], list(z["par"][k]))
+
+
 needs_ref = pytest.mark.skipif(not refbind.have_ref(), reason="compiled reference (oracle/_ref) not present")
 
 
@@ -42,6 +64,27 @@ def test_dp_oracle_vs_reference_fuzz(oracle_built):
         ss = make_ss(rng, len(nt)) if rng.random() < 0.2 else None
         for flag in (1, 2, 4, 0):
             assert refbind.ref_nasw(nt, aa, P, flag, ss) == refbind.ora_nasw(nt, aa, P, flag, ss), (it, flag)
+
+
+@needs_ref
+def test_dp_oracle_vs_reference_across_the_penalty_range(oracle_built):
+    """go, ge, io, fs, x-drop and end bonus from miniprot's defaults up to the limits mpa_dp_run() accepts (dpgen.PENALTY_POINTS), and
+    both sides of the int16 bound of the packed kernels (dpgen.BOUND_CASES): al on both sides of every kernel class boundary,
+    windows of 384 rows and more, splice scores on some calls, all four modes"""
+    rng = np.random.default_rng(303)
+    points = [kw for kw in PENALTY_POINTS] + [bound_params(c, over) for c in BOUND_CASES for over in (0, 1)]
+    n = 0
+    for kw in points:
+        P = _penalty_params(kw)
+        als = [al for al in CLASS_EDGES if al <= 257] + [int(rng.choice(CLASS_EDGES[-4:]))]
+        calls = [make_task(rng, al=al, p_intron=0.02, max_intron=300, flank=200) for al in als]
+        calls += [long_window(rng, int(rng.integers(1, 129))) for _ in range(2)]
+        for nt, aa in calls:
+            ss = make_ss(rng, len(nt)) if rng.random() < 0.2 else None
+            for flag in (1, 2, 4, 0):
+                assert refbind.ref_nasw(nt, aa, P, flag, ss) == refbind.ora_nasw(nt, aa, P, flag, ss), (kw, len(nt), len(aa), flag)
+                n += 1
+    assert n > 2500
 
 
 @needs_ref

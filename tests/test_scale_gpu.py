@@ -2,7 +2,7 @@
 with the repo).  These are the regimes the small golden cases never reach: `-I` at hundreds of Mbp with N runs and tandem
 paralogs, mini-batches big enough that the library switches GPU seeding and the GPU refinement scan on BY ITSELF (thresholds of
 host_map.cpp left at their defaults), `-G 500000` with 250 000-row extension windows, and the widest extension classes
-(k_ext_wide<8>, k_ext_wide<16>).  About two minutes in total."""
+(k_ext_wide<8>, k_ext_wide<16>), and wide extensions under large penalties.  About two minutes in total."""
 import ctypes as C
 import os
 import subprocess
@@ -14,7 +14,7 @@ import golden  # noqa: F401  (puts tools/ on sys.path)
 import gen_synth
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not os.path.exists(refbind.REF_BIN), reason="oracle/_ref/miniprot not present")]
-NCPU = os.cpu_count() or 4
+NCPU = min(16, os.cpu_count() or 4)                  # (a command on a shared machine may use 16 of its CPUs)
 
 
 @pytest.fixture(scope="module")
@@ -103,6 +103,37 @@ def test_long_introns_and_the_widest_extension_classes(ctx, tmp_path):
     assert st["n_ext"] > 100 and st["cells_ext"] > 1.5e9           # the long windows were really swept
     ref = _reference(tmp_path, idx, prots, names, ["-G", "500000", "-u"])
     assert ours[0] == ref, _first_difference(ours[0], ref)
+    idx.close()
+
+
+# (flags, MapOpt fields they set: main.c's -E -> ge, -O -> go, -J -> io, --xdrop -> xdrop, -B -> end_bonus)
+_PENALTY_RUNS = [(["-u", "-E", "40"], dict(ge=40)), (["-u", "-E", "120", "-O", "30"], dict(ge=120, go=30)), (["-u", "-J", "2000"], dict(io=2000)),
+                 (["-u", "--xdrop", "20000", "-B", "500"], dict(xdrop=20000, end_bonus=500))]
+
+
+@pytest.mark.parametrize("flags,fields", _PENALTY_RUNS, ids=lambda x: " ".join(x) if isinstance(x, list) else "")
+def test_extensions_under_large_penalties(ctx, tmp_path, flags, fields):
+    """The whole path with scores far from the defaults: proteins seeded at one end only (a planted protein's end + a random tail of
+    300, 800 or 1000 residues), so that the extension call at the other end is that wide -- with -E 40 or -E 120 such calls could
+    saturate int16 in the packed kernels and go to the int32 sweep instead; -J 2000 and --xdrop 20000 -B 500 change what the
+    extension keeps.  Every output byte equals the reference's, run live with the same flags."""
+    contigs, prots, names, planted = gen_synth.generate(20_000_000, 1, 30, 23, imax=20000, return_planted=True)
+    rng = np.random.default_rng(230)
+    chim = _chimeras(rng, planted, [300, 800, 1000, 300, 800, 1000])
+    prots = list(prots) + chim
+    names = list(names) + ["chim%02d" % k for k in range(len(chim))]
+    idx = mpa.Index.from_nt4(contigs, ["chr1"])
+    del contigs
+    mpa._check(mpa.lib().mpa_idx_build_kmers(idx.h, min(32, NCPU)))
+    idx.to_device(ctx)
+    mo = mpa.default_mapopt()
+    mo.flag |= 4
+    for k, v in fields.items():
+        setattr(mo, k, v)
+    ours = mpa.map_batches(ctx, idx, mo, [mpa.Queries(prots, names)], min(32, NCPU))[0]
+    ref = _reference(tmp_path, idx, prots, names, flags)
+    assert ours == ref, _first_difference(ours, ref)
+    assert sum(l.startswith(b"chim") for l in ours.split(b"\n")) >= len(chim)
     idx.close()
 
 

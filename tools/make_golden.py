@@ -5,6 +5,8 @@ oracle/Makefile).  Run in the authoring container only; the outputs are committe
   * DPP3 fixture (the reference's own test data) and the reference's PAF for it (config 1)
   * reference PAF for the synthetic cases of tests/golden.py (inputs are regenerated from their seeds)
   * dp_vectors.npz: random DP calls with the reference's ns_global_gs16b() answers (all three modes)
+  * dp_vectors_penalties.npz: DP calls at the scores of tests/dpgen.py's PENALTY_POINTS and BOUND_CASES (defaults up to the limits
+    mpa_dp_run() accepts) with the reference's ns_global_gs16b() answers: `make_golden.py penalties` makes only these
   * gs32_vectors.npz: calls of the 32-bit operator (ns_global_gs32b, -msse4.1 build of the reference): `make_golden.py gs32` makes only these
   * chain_vectors.npz / sketch vectors: anchor sets with the reference's mp_chain() output
   * ref_layout.txt: sizes and offsets of the reference's records as its own headers declare them (tests/test_compat.py):
@@ -24,7 +26,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import refbind  # noqa: E402
 import golden  # noqa: E402
 import gen_synth  # noqa: E402
-from dpgen import make_task  # noqa: E402
+from dpgen import make_task, make_ss, PENALTY_POINTS, BOUND_CASES, CLASS_EDGES, bound_params  # noqa: E402
 
 GOLD = golden.GOLD
 os.makedirs(GOLD, exist_ok=True)
@@ -54,6 +56,36 @@ def make_gs32_vectors():
     print("gs32_vectors", len(flags), "calls,", sum(1 for x in scores if x > 32767), "with scores beyond int16")
 
 
+def make_penalty_vectors():
+    """tests/golden/dp_vectors_penalties.npz: per scoring point (PENALTY_POINTS, then both sides of every BOUND_CASES entry) two calls at
+    kernel class edges (for a bound case one call at the bound's own al) in all three modes and a window of >= 384 rows in global mode,
+    some with ss[]"""
+    rng = np.random.default_rng(3131)
+    points = [(kw, None) for kw in PENALTY_POINTS] + [(bound_params(c, over), c[0]) for c in BOUND_CASES for over in (0, 1)]
+    nts, aas, sss, pair, flags, pars, coefs, mats, res, cigs = [], [], [], [], [], [], [], [], [], []
+    for kw, al in points:
+        P = refbind.DpParams(refbind.mapping_matrix(min(kw.get("fs", 23), 127)), **kw)
+        edges = [al] if al else [int(rng.choice(CLASS_EDGES[:11])) for _ in range(2)]
+        calls = [(make_task(rng, al=a, p_intron=0.02, max_intron=200, flank=100, p_indel=0.0), (1, 2, 4)) for a in edges]
+        while True:                                        # (a window of 384..480 rows: long enough for the checkpointed sweep, and small)
+            lw = make_task(rng, al=int(rng.integers(1, 129)), max_intron=300, flank=250, p_intron=0.05)
+            if 384 <= len(lw[0]) <= 480:
+                break
+        for (nt, aa), modes in calls + [(lw, (1,))]:
+            ss = make_ss(rng, len(nt)) if rng.random() < 0.25 else None
+            nts.append(np.frombuffer(nt, np.uint8)), aas.append(np.frombuffer(aa, np.uint8))
+            sss.append(np.frombuffer(ss, np.uint8) if ss is not None else np.zeros(0, np.uint8))
+            for fl in modes:
+                r = refbind.ref_nasw(nt, aa, P, fl, ss)
+                pair.append(len(nts) - 1), flags.append(fl), pars.append([P.go, P.ge, P.io, P.fs, P.xdrop, P.end_bonus] + list(P.sp)), coefs.append(P.ie_coef), mats.append(P.mat.copy())
+                res.append(r[:3]), cigs.append(np.array(r[3], np.uint32))
+    np.savez_compressed(golden.path("dp_vectors_penalties.npz"), nt=np.concatenate(nts), nt_len=np.array([len(x) for x in nts]),
+                        aa=np.concatenate(aas), aa_len=np.array([len(x) for x in aas]), ss=np.concatenate(sss), ss_len=np.array([len(x) for x in sss]),
+                        pair=np.array(pair), flag=np.array(flags), par=np.array(pars, np.int64), ie_coef=np.array(coefs, np.float32), mat=np.array(mats, np.int8),
+                        res=np.array(res, np.int64), cig=np.concatenate(cigs), cig_len=np.array([len(x) for x in cigs]))
+    print("dp_vectors_penalties", len(flags), "calls")
+
+
 def make_layout(ref_dir):
     """tests/golden/ref_layout.txt: what test_compat's layout probe prints when compiled against the reference's own headers"""
     import test_compat
@@ -73,6 +105,9 @@ def main():
     refbind.build_oracle()
     if len(sys.argv) > 1 and sys.argv[1] == "gs32":
         make_gs32_vectors()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "penalties":
+        make_penalty_vectors()
         return
     # config 1
     for f in ("DPP3-hs.gen.fa.gz", "DPP3-mm.pep.fa.gz"):
@@ -106,6 +141,7 @@ def main():
                         res=np.array(res, np.int64), cig=np.concatenate(cigs), cig_len=np.array([len(x) for x in cigs]), mat=P.mat)
     print("dp_vectors", len(flags))
     make_gs32_vectors()
+    make_penalty_vectors()
 
 
 if __name__ == "__main__":
