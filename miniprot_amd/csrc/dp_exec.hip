@@ -1109,7 +1109,8 @@ int dev_refine_scan(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_aa_
 	out.first.assign((size_t)n_win + 1, 0);
 	out.hits.clear();
 	if (n_win == 0) return MPA_OK;
-	if (kmer < 1 || kmer > 7 || min_aa_len > (REFINE_HALO - 3 * kmer) / 3 + kmer) { set_error("refinement scan: parameters outside the device kernel's range"); return MPA_ERR_UNSUPPORTED; }
+	static_assert(REFINE_HALO == kRefineHaloBases, "dev_refine_in_range() states the halo of the scan kernels");
+	if (!dev_refine_in_range(kmer, min_aa_len)) { set_error("refinement scan: parameters outside the device kernel's range"); return MPA_ERR_UNSUPPORTED; }
 	int64_t max_words = 0;
 	for (int32_t q = 0; q < n_query; ++q) max_words = std::max(max_words, qw_first[q + 1] - qw_first[q]);
 	int hs_log2 = 10;
@@ -1185,7 +1186,7 @@ int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_a
 	out.u_first.assign((size_t)n_win + 1, 0), out.a_first.assign((size_t)n_win + 1, 0);
 	out.U = out.A = nullptr;
 	if (n_win == 0) return MPA_OK;
-	if (kmer < 1 || kmer > 7 || min_aa_len > (REFINE_HALO - 3 * kmer) / 3 + kmer || cp.bbit != 0) { set_error("device refinement: parameters outside the kernels' range"); return MPA_ERR_UNSUPPORTED; }
+	if (!dev_refine_in_range(kmer, min_aa_len) || cp.bbit != 0) { set_error("device refinement: parameters outside the kernels' range"); return MPA_ERR_UNSUPPORTED; }
 	if (n_win >= (1 << 20)) { set_error("device refinement: more than 2^20 windows in a batch"); return MPA_ERR_UNSUPPORTED; }
 	int64_t max_groups = 0;
 	for (int32_t q = 0; q < n_query; ++q) max_groups = std::max(max_groups, G.qg_first[(size_t)q + 1] - G.qg_first[(size_t)q]);

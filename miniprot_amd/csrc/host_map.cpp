@@ -1011,7 +1011,8 @@ static void batch_plan_phase(mpa_batch_s *b, mpa_ctx_t *rctx)
 	RefineChains rchains;
 	bool on_device = false, chains_on_device = false;
 	const int mode = gpu_refine_mode();
-	if (rctx && mode != 0 && b->opt.kmer2 <= 6) {
+	// (outside the kernels' range -- dev_refine_in_range(): -l above 7, -L above 37 -- the host refines; the device is not asked)
+	if (rctx && mode != 0 && dev_refine_in_range(b->opt.kmer2, b->mi->opt.min_aa_len)) {
 		static thread_local std::vector<RefineWindow> wins;
 		static thread_local std::vector<int64_t> qw_first;
 		static thread_local std::vector<uint32_t> qwords;
@@ -1052,8 +1053,9 @@ static void batch_plan_phase(mpa_batch_s *b, mpa_ctx_t *rctx)
 			const double t1 = now_ms();
 			const int rc = dev_refine_chains(rctx, const_cast<mpa_idx_s*>(b->mi), b->opt.kmer2, b->mi->opt.min_aa_len, b->opt.max_ava, refine_chain_params(b->opt), (int32_t)n_q, G,
 			                                 (int64_t)wins.size(), wins.data(), rchains);
-			timing_note("  refinement on the GPU (scan + pairs + chains)", now_ms() - t1);
 			chains_on_device = rc == MPA_OK;                   // anything else: the scan alone below, or the host
+			if (chains_on_device) timing_note("  refinement on the GPU (scan + pairs + chains)", now_ms() - t1);
+			else if (timing_on()) fprintf(stderr, "[mpa-timing]   device refinement declined (%s)\n", mpa_last_error());
 		}
 		if (!chains_on_device && !wins.empty() && (mode == 1 || n_bases >= kDeviceRefineMinBases)) {
 			std::vector<uint32_t> w;
@@ -1066,8 +1068,9 @@ static void batch_plan_phase(mpa_batch_s *b, mpa_ctx_t *rctx)
 			const double t1 = now_ms();
 			const int rc = dev_refine_scan(rctx, const_cast<mpa_idx_s*>(b->mi), b->opt.kmer2, b->mi->opt.min_aa_len, (int32_t)n_q, qw_first.data(), qwords.data(),
 			                               (int64_t)wins.size(), wins.data(), rh);
-			timing_note("  refinement scan on the GPU", now_ms() - t1);
 			on_device = rc == MPA_OK;                         // anything else: scan on the host
+			if (on_device) timing_note("  refinement scan on the GPU", now_ms() - t1);
+			else if (timing_on()) fprintf(stderr, "[mpa-timing]   device refinement scan declined (%s): refinement on the host\n", mpa_last_error());
 		}
 	}
 	const RefineHits *rhp = on_device ? &rh : nullptr;
@@ -1123,7 +1126,14 @@ int64_t mpa_dbg_refine_hits(mpa_ctx_t *ctx, const mpa_idx_t *mi, int32_t kmer, c
 		for (int32_t k = 0; k < n_win; ++k) {
 			nt.resize((size_t)std::max(len[k], 1));
 			fetch_nt(mi, vid[k], as[k], as[k] + len[k], nt.data());
-			refine_seed_pairs(nt.data(), len[k], mi->opt.min_aa_len, kmer, rq.qk, rq.filter->data(), INT32_MAX, per[k], a);
+			if (rq.filter) { refine_seed_pairs(nt.data(), len[k], mi->opt.min_aa_len, kmer, rq.qk, rq.filter->data(), INT32_MAX, per[k], a); continue; }
+			// large k (no bitmap of the query's words, as in refine_region_pairs): the reference's own sketch of the window, and of it
+			// the k-mers whose hash the query has
+			sketch_nt4(nt.data(), len[k], mi->opt.min_aa_len, kmer, 0, 0, 0, a, false);
+			for (uint64_t x : a) {
+				const auto it = std::lower_bound(rq.qk.begin(), rq.qk.end(), x >> 32 << 32);
+				if (it != rq.qk.end() && *it >> 32 == x >> 32) per[k].push_back(x);
+			}
 		}
 	}
 	first[0] = 0;

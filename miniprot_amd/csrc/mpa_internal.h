@@ -134,6 +134,16 @@ struct PrechainSparse {              // result for a mini-batch: the chained anc
 	std::vector<int64_t> u_first, a_first;   // [n_query + 1]
 	const uint64_t *U = nullptr, *A = nullptr;   // pinned buffers of the context, valid until its next call
 };
+// What the device refinement takes (k_refine_scan, k_refine_scan_map), stated once for the callers' gate (host_map.cpp) and the
+// guards of dev_refine_scan / dev_refine_chains: k-mers of 1..7 residues (4 bits each in a 32-bit word whose all-ones value marks
+// an empty slot of the LDS table) and a minimum ORF length that the walk into the chunk's halo can decide -- from a k-mer at the
+// chunk's first position the walk sees (halo - 3 k) / 3 whole codons before it: 37 codons in all for every k of 3..7.
+static const int32_t kRefineHaloBases = 112;
+static const int32_t kRefineMaxKmer = 7;
+static inline bool dev_refine_in_range(int32_t kmer, int32_t min_aa_len)
+{
+	return kmer >= 1 && kmer <= kRefineMaxKmer && min_aa_len <= (kRefineHaloBases - 3 * kmer) / 3 + kmer;
+}
 struct RefineWindow { int64_t as; int32_t qid, vid, len; };    // strand-local window [as, as + len) on vid, refined for query qid
 struct RefineHits { std::vector<int64_t> first; std::vector<uint64_t> hits; };
 int dev_refine_scan(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_aa_len, int32_t n_query, const int64_t *qw_first, const uint32_t *qwords,

@@ -164,6 +164,52 @@ def test_synthetic_paf_identical(oracle_built, case, tmp_path):
     assert paf == ref
 
 
+@pytest.mark.parametrize("case", golden.OPTION_CASES, ids=[c["name"] for c in golden.OPTION_CASES])
+def test_option_cases_paf_identical(oracle_built, case, tmp_path):
+    """The host stages + oracle executor away from the default index and seeding / chaining options (-k -M -b -L, -c -l -g -w -n -m
+    --max-skip --no-pre-chain -G): the bytes of the reference, which built its own index with the same flags.  The GPU tests of
+    tests/test_seed_options_gpu.py lean on the host stages at these points."""
+    import seedopts
+    contigs, prots, names = golden.synth_inputs(case)
+    idx = mpa.Index.read_fasta(seedopts.write_genome(tmp_path, contigs), case["idx"])
+    assert idx.build_kmers(4) == "host"
+    paf = map_batch(idx, golden.mapopt_for(case), mpa.Queries(prots, names), oracle_executor, n_threads=4)
+    ref = open(golden.path(case["name"] + ".ref.paf"), "rb").read()
+    if paf != ref:
+        for x, y in zip(paf.split(b"\n"), ref.split(b"\n")):
+            if x != y:
+                raise AssertionError("first differing line\n ours %r\n ref  %r" % (x[:300], y[:300]))
+    assert paf == ref
+    idx.close()
+
+
+def test_option_cases_name_the_index_their_flags_build():
+    """the "idx" tuple of every option case is what its -b -L -k -M flags say over mp_idxopt_init's 8, 30, 6, 1 (several of these
+    cases print the same bytes, -L37 and -L38 among them: a wrong tuple would put a GPU test on the other side of a guard unseen),
+    and every seedopts point translates into the fields it names"""
+    import seedopts
+    for case in golden.OPTION_CASES:
+        want = {"-b": 8, "-L": 30, "-k": 6, "-M": 1}
+        fl = case["flags"]
+        for i, f in enumerate(fl):
+            if f in want:
+                want[f] = int(fl[i + 1])
+        assert tuple(case["idx"]) == (want["-b"], want["-L"], want["-k"], want["-M"]), case["name"]
+        assert os.path.getsize(golden.path(case["name"] + ".ref.paf")) < 100000
+    d = mpa.default_mapopt()
+    got = {p.name: p.apply(mpa.default_mapopt()) for p in seedopts.CHAIN_POINTS + seedopts.REFINE_POINTS}
+    m = got["skip2-w0.2-g200"]
+    assert (m.max_chn_max_skip, round(m.chn_coef_log, 4), m.max_gap) == (2, 0.2, 200)
+    m = got["n6-m40-c50"]
+    assert (m.min_chn_cnt, m.min_chn_sc, m.max_occ) == (6, 40, 50)
+    assert (got["G2000"].max_intron, got["G2000"].bw) == (2000, 2000)
+    assert (got["iter20-skip0"].max_chn_iter, got["iter20-skip0"].max_chn_max_skip) == (20, 0)
+    assert got["no-pre-chain"].flag & 0x40 and got["no-splice"].flag & 0x1 and not got["default"].flag & 0x41
+    assert [got["l%d" % k].kmer2 for k in seedopts.REFINE_KMERS] == seedopts.REFINE_KMERS and d.kmer2 == 5
+    assert [got["ava%d" % v].max_ava for v in seedopts.MAX_AVA] == seedopts.MAX_AVA and d.max_ava == 1000
+    assert (d.max_chn_max_skip, d.max_chn_iter, d.min_chn_cnt, d.min_chn_sc, d.max_occ, d.max_gap) == (25, 1000000, 3, 0, 20000, 1000)
+
+
 def test_threads_do_not_change_output(oracle_built):
     case = golden.SYNTH_CASES[0]
     contigs, prots, names = golden.synth_inputs(case)

@@ -9,6 +9,8 @@ oracle/Makefile).  Run in the authoring container only; the outputs are committe
     mpa_dp_run() accepts) with the reference's ns_global_gs16b() answers: `make_golden.py penalties` makes only these
   * gs32_vectors.npz: calls of the 32-bit operator (ns_global_gs32b, -msse4.1 build of the reference): `make_golden.py gs32` makes only these
   * chain_vectors.npz / sketch vectors: anchor sets with the reference's mp_chain() output
+  * opt_<name>.ref.paf: reference PAF for golden.OPTION_CASES (one genome, index and seeding / chaining options away from the
+    defaults; the index flags go to the reference with the FASTA): `make_golden.py options` makes only these
   * ref_layout.txt: sizes and offsets of the reference's records as its own headers declare them (tests/test_compat.py):
     `make_golden.py layout <reference source dir>` makes only this
 """
@@ -98,7 +100,23 @@ def make_layout(ref_dir):
     print("ref_layout", out.count("\n"), "lines")
 
 
+def make_option_cases():
+    """tests/golden/opt_<name>.ref.paf: the reference's output for golden.OPTION_CASES"""
+    with tempfile.TemporaryDirectory() as tmp:
+        for case in golden.OPTION_CASES:
+            contigs, prots, names = golden.synth_inputs(case)
+            fa, faa = os.path.join(tmp, "g.fa"), os.path.join(tmp, "p.fa")
+            gen_synth.write_fasta_nt(fa, contigs)
+            gen_synth.write_fasta_aa(faa, prots, names)
+            out = run_ref(case["flags"] + [fa, faa])
+            open(golden.path(case["name"] + ".ref.paf"), "wb").write(out)
+            print(case["name"], len(out), "bytes", out.count(b"\n"), "lines,", sum(1 for l in out.split(b"\n") if l and l.split(b"\t")[5] != b"*"), "mapped")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "options":
+        make_option_cases()
+        return
     if len(sys.argv) > 2 and sys.argv[1] == "layout":
         make_layout(sys.argv[2])
         return
@@ -142,6 +160,7 @@ def main():
     print("dp_vectors", len(flags))
     make_gs32_vectors()
     make_penalty_vectors()
+    make_option_cases()
 
 
 if __name__ == "__main__":
