@@ -331,6 +331,14 @@ int32_t mpa_dbg_gs32_model(int32_t nl, int32_t al, const uint32_t *rec, const in
 void mpa_dbg_antidiag(mpa_ctx_t *ctx, int on);
 int64_t mpa_dbg_main_chains(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads, int64_t *off_u, uint64_t **out_u,
                             int64_t *off_a, uint64_t **out_a);
+/* the kept seeds of every query (map.c:152-170: sketch, bucket lookup, occurrence cut-off) as (query position, bucket, occurrences)
+ * int32 triples in ascending query position, and the cut-off in force per query; from the host stage (ctx == NULL) or from the
+ * device stage (MPA_GPU_SKETCH's kernels: a download of the seed jobs they leave for the sift).  off [n_seq + 1] counts triples,
+ * max_occ [n_seq], *out (mpa_free).  Returns how many queries the device handed to the host, or a negative error code. */
+int64_t mpa_dbg_seed_jobs(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads, int64_t *off, int32_t *max_occ,
+                          int32_t **out);
+/* cnt[i] = entries of bucket[i] in the index's k-mer table (what the occurrence cut-off is computed from).  Host only. */
+int mpa_idx_bucket_counts(const mpa_idx_t *mi, int64_t n, const uint32_t *bucket, int64_t *cnt);
 
 #ifdef __cplusplus
 }

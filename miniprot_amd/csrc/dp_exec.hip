@@ -31,6 +31,7 @@ static_assert(EXT_WIDE_LDS(2) % 16 == 0 && EXT_WIDE_LDS(4) % 16 == 0 && (2 * 64 
 static_assert(EXT_WIDE_RING % 12 == 0 && EXT_WIDE_XIN % 48 == 0 && EXT_WIDE_KROWS % 12 == 0 && EXT_WIDE_KROWS >= 64 + 12 + 12 + 3, "rings in whole 12-row blocks; the key ring holds a flush of 64 rows, a block, and the first wave's lead");
 #include "dp_antidiag.hip"
 #include "seed_exec.hip"
+#include "sketch_exec.hip"
 
 namespace mpa {
 
@@ -105,6 +106,8 @@ struct DeviceIndex {
 	int64_t *ctg_off = nullptr, *ctg_len = nullptr;
 	uint32_t *kb = nullptr;                   // k-mer occurrence lists (block ids), uploaded on first GPU seeding call
 	size_t kb_bytes = 0;
+	int64_t *ki = nullptr;                    // bucket offsets of the k-mer table, uploaded on the first device sketch (dev_sketch_jobs)
+	size_t ki_bytes = 0;
 	uint8_t *spsc = nullptr;                  // splice-score track (--spsc), uploaded with the genome when the index has one
 	size_t seq_bytes = 0, spsc_bytes = 0;     // bytes counted into g_dev_bytes for the genome and the track
 };
@@ -139,6 +142,8 @@ struct SeedBufs {
 	DevBuf pf_qfirst2, val64[2];                                            // first kept anchor of every query; the kept anchors' values
 	DevBuf s_meta, s_cur, s_cur2, s_kept, s_base, s_out, s_flag, dkey;      // k_seed_sift: segments + per-query tables, list cursors, per-segment results, dense keys
 	HostPinned h_meta, h_back;                                             // ... their staging (up) and qfirst2 / flags / cfirst (down)
+	DevBuf k_in, k_cnt, k_bkt, k_q;                                         // device sketch (sketch_exec.hip): residue table + q_off + protein text; count and bucket per position; per-query counts, prefixes, cut-offs, flags
+	HostPinned h_kin, h_kout;                                              // ... its staging (up) and qfirst / jfirst / cut-offs / flags (down)
 	DevBuf x_all;                                                          // device chaining: views, extraction scratch, survivors, main-chain state, chains (carved up per call)
 	DevBuf rx_all, rx_keys;                                                // device refinement: pairing tables, pair keys (two buffers), chain state (carved up per call)
 	HostPinned h_xoff;                                                     // ... offsets of the chains of every query (down)
@@ -208,7 +213,7 @@ template<typename F> static void ctx_each_devbuf(mpa_ctx_s *ctx, F f)
 	                  &B.c_a, &B.c_f, &B.c_pred, &B.c_mark, &B.c_flag, &B.c_first, &B.c_long,
 	                  &B.pf_qfirst2, &B.val64[0], &B.val64[1],
 	                  &B.s_meta, &B.s_cur, &B.s_cur2, &B.s_kept, &B.s_base, &B.s_out, &B.s_flag, &B.dkey, &B.x_all, &B.rx_all, &B.rx_keys,
-	                  &ctx->lite, &ctx->ckpt, &ctx->wlist };
+	                  &ctx->lite, &ctx->ckpt, &ctx->wlist, &B.k_in, &B.k_cnt, &B.k_bkt, &B.k_q };
 	int k = 0;
 	for (DevBuf *b : all) f(*b, k++);
 }
@@ -321,6 +326,7 @@ void dev_free_index(mpa_idx_s *mi)
 		(void)hipFree(d->seq); (void)hipFree(d->ctg_off); (void)hipFree(d->ctg_len);
 		g_dev_bytes -= (long long)(d->seq_bytes + d->spsc_bytes);
 		if (d->kb) { (void)hipFree(d->kb); g_dev_bytes -= (long long)d->kb_bytes; }
+		if (d->ki) { (void)hipFree(d->ki); g_dev_bytes -= (long long)d->ki_bytes; }
 		if (d->spsc) (void)hipFree(d->spsc);
 		delete d;
 		d = nullptr;
@@ -462,7 +468,7 @@ void mpa_ctx_destroy(mpa_ctx_t *ctx)
 	ctx->dp_trace.release();
 	SeedBufs &B = ctx->seed;
 	ctx_each_devbuf(ctx, [](DevBuf &b, int) { b.release(); });
-	for (HostPinned *h : { &B.h_jobs, &B.h_rhits, &B.hc_a, &B.hc_f, &B.hc_pred, &B.h_meta, &B.h_back, &B.h_xoff, &ctx->h_up, &ctx->h_down, &ctx->h_pool }) h->release();
+	for (HostPinned *h : { &B.h_jobs, &B.h_rhits, &B.hc_a, &B.hc_f, &B.hc_pred, &B.h_meta, &B.h_back, &B.h_xoff, &B.h_kin, &B.h_kout, &ctx->h_up, &ctx->h_down, &ctx->h_pool }) h->release();
 	auto drop_hold = [](SeedHold &H) { for (HostPinned *h : { &H.h_pos, &H.h_f, &H.h_pred, &H.h_a, &H.h_U, &H.h_A }) h->release(); };
 	drop_hold(B.own);
 	for (SeedHold *H : ctx->holds) { drop_hold(*H); delete H; }
@@ -570,7 +576,8 @@ static int dev_chains_on_device(mpa_ctx_t *ctx, int32_t n_query, int64_t m, int6
                                 const int32_t *h_flag, const ChainParams &pre, const ChainParams &mainp, PrechainSparse &out, SeedHold &H);
 
 static int dev_prechain_forward_sift(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_block, const PreParams &pp, int nb, int32_t n_query, const int64_t *qfirst,
-                                     const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, double t_begin, const ChainParams *pre_cp, const ChainParams *main_cp, SeedHold &H)
+                                     const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, double t_begin, const ChainParams *pre_cp, const ChainParams *main_cp, SeedHold &H,
+                                     const int64_t *jfirst_in = nullptr)
 {
 	SeedBufs &B = ctx->seed;
 	hipStream_t s = ctx->seed_stream;
@@ -586,8 +593,11 @@ static int dev_prechain_forward_sift(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_
 	jfirst.assign((size_t)n_query + 1, 0), qseg.assign((size_t)n_query + 1, 0), sfirst.assign((size_t)n_query + 1, 0);
 	for (int32_t q = 0; q < n_query; ++q) sfirst[(size_t)q + 1] = sfirst[(size_t)q] + sift_stage_slots(qfirst[q + 1] - qfirst[q]);
 	const int64_t n_stage = sfirst[(size_t)n_query];
-	for (int64_t j = 0; j < n_jobs; ++j) ++jfirst[(size_t)jobs[j].qid + 1];
-	for (int32_t q = 0; q < n_query; ++q) jfirst[(size_t)q + 1] += jfirst[(size_t)q];
+	if (jfirst_in) jfirst.assign(jfirst_in, jfirst_in + n_query + 1);      // (the jobs were made on the device: dev_sketch_jobs counted them)
+	else {
+		for (int64_t j = 0; j < n_jobs; ++j) ++jfirst[(size_t)jobs[j].qid + 1];
+		for (int32_t q = 0; q < n_query; ++q) jfirst[(size_t)q + 1] += jfirst[(size_t)q];
+	}
 	for (int32_t q = 0; q < n_query; ++q) {
 		const int64_t na = qfirst[q + 1] - qfirst[q];
 		qseg[(size_t)q] = (int32_t)segs.size();
@@ -867,7 +877,7 @@ static int dev_chains_on_device(mpa_ctx_t *ctx, int32_t n_query, int64_t m, int6
 // offset); qfirst[n_query + 1]: first anchor of every query.  out: per query a sparse ChainView's arrays
 // (pred = index into the query's part of the view, -1 for none).
 int dev_prechain_forward(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams &pre, int32_t n_query, const int64_t *qfirst,
-                         const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, const ChainParams *main, SeedHold *hold)
+                         const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, const ChainParams *main, SeedHold *hold, const int64_t *jfirst_dev)
 {
 	const int64_t n = qfirst[n_query];
 	out.cfirst.assign((size_t)n_query + 1, 0);
@@ -912,19 +922,121 @@ int dev_prechain_forward(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams &pre, 
 	ensure_seed_stream(ctx);
 	hipStream_t s = ctx->seed_stream;
 	const double t_begin = now_ms();
-	// ---- upload the seed jobs
-	if (B.h_jobs.ensure((size_t)n_jobs * sizeof(SeedJobDev)) != MPA_OK) return MPA_ERR_HIP;
-	SeedJobDev *hj = B.h_jobs.as<SeedJobDev>();
-	for (int64_t i = 0; i < n_jobs; ++i) hj[i] = SeedJobDev{ jobs[i].kb_off, jobs[i].dst, jobs[i].cnt, jobs[i].qpos, jobs[i].qid, 0 };
-	if (B.jobs.ensure((size_t)n_jobs * sizeof(SeedJobDev)) != MPA_OK) return MPA_ERR_HIP;
-	HIP_TRY(hipMemcpyAsync(B.jobs.p, hj, (size_t)n_jobs * sizeof(SeedJobDev), hipMemcpyHostToDevice, s));
+	// ---- upload the seed jobs (jfirst_dev: dev_sketch_jobs of this context has left them in B.jobs)
+	if (!jfirst_dev) {
+		if (B.h_jobs.ensure((size_t)n_jobs * sizeof(SeedJobDev)) != MPA_OK) return MPA_ERR_HIP;
+		SeedJobDev *hj = B.h_jobs.as<SeedJobDev>();
+		for (int64_t i = 0; i < n_jobs; ++i) hj[i] = SeedJobDev{ jobs[i].kb_off, jobs[i].dst, jobs[i].cnt, jobs[i].qpos, jobs[i].qid, 0 };
+		if (B.jobs.ensure((size_t)n_jobs * sizeof(SeedJobDev)) != MPA_OK) return MPA_ERR_HIP;
+		HIP_TRY(hipMemcpyAsync(B.jobs.p, hj, (size_t)n_jobs * sizeof(SeedJobDev), hipMemcpyHostToDevice, s));
+	}
 	// merge the occurrence lists per query in block order, keep what has a neighbour (k_seed_sift, seed_exec.hip)
 	tl_alloc_failed = false;
-	const int rc = dev_prechain_forward_sift(ctx, d, mi->n_block, pp, nb, n_query, qfirst, jobs, n_jobs, out, t_begin, &pre, main, hold ? *hold : B.own);
+	const int rc = dev_prechain_forward_sift(ctx, d, mi->n_block, pp, nb, n_query, qfirst, jobs, n_jobs, out, t_begin, &pre, main, hold ? *hold : B.own, jfirst_dev);
 	// a pool that could not grow (the admission check above is an estimate): the batch is seeded on the host, as for any batch
 	// that does not fit -- nothing has been handed to the caller yet
 	if (rc == MPA_ERR_HIP && tl_alloc_failed) { (void)hipStreamSynchronize(s); return MPA_ERR_UNSUPPORTED; }
 	return rc;
+}
+
+// ki[] next to kb[] in HBM, on the first device sketch of a device.  The host array may be a misaligned view into a mapped .mpi:
+// it is only ever copied byte-wise.  No device memory for it: the caller sketches on the host.
+static int ensure_dev_ki(mpa_ctx_t *ctx, mpa_idx_s *mi, DeviceIndex *d)
+{
+	if (d->ki) return MPA_OK;
+	static std::mutex mu[mpa_idx_s::kMaxDevices];            // (per device, like dev_upload_index)
+	std::lock_guard<std::mutex> g(mu[ctx->device]);
+	if (d->ki) return MPA_OK;
+	int64_t *p = nullptr;
+	const size_t bytes = mi->ki.size() * 8;
+	if (hipMalloc((void**)&p, bytes + 16) != hipSuccess) { (void)hipGetLastError(); set_error("GPU sketch: no device memory for the bucket offsets"); return MPA_ERR_UNSUPPORTED; }
+	const double t0 = now_ms();
+	const hipError_t e = upload_large(p, (const void*)mi->ki.data(), bytes, ctx->stream);
+	if (e != hipSuccess) { (void)hipFree(p); set_error(std::string("GPU sketch: uploading the bucket offsets: ") + hipGetErrorString(e)); return MPA_ERR_HIP; }
+	timing_note("index upload: bucket offsets", now_ms() - t0);
+	d->ki = p, d->ki_bytes = bytes + 16;
+	g_dev_bytes += (long long)d->ki_bytes;
+	return MPA_OK;
+}
+
+static int dev_sketch_jobs_impl(mpa_ctx_t *ctx, mpa_idx_s *mi, DeviceIndex *d, int32_t max_occ, const mpa_qbatch_t *q, SketchResult &out)
+{
+	SeedBufs &B = ctx->seed;
+	hipStream_t s = ctx->seed_stream;
+	const int32_t n_query = q->n_seq;
+	const int64_t base = q->q_off[0], L = q->q_off[n_query] - base;
+	const size_t NQ = (size_t)n_query, mq = (NQ + 1) * 8, fq = (NQ * 4 + 15) & ~(size_t)15;
+	// one pinned block up: residue table | q_off (from 0) | protein text
+	const size_t off_qo = 256, off_tx = off_qo + mq, up_bytes = off_tx + (size_t)L + 16;
+	int rc;
+	if ((rc = B.h_kin.ensure(up_bytes)) || (rc = B.k_in.ensure(up_bytes)) || (rc = B.k_cnt.ensure((size_t)L * 4 + 16)) || (rc = B.k_bkt.ensure((size_t)L * 4 + 16)) ||
+	    (rc = B.k_q.ensure(4 * mq + 2 * fq)) || (rc = B.h_kout.ensure(2 * mq + 2 * fq)) || (rc = B.jobs.ensure(((size_t)L + 1) * sizeof(SeedJobDev)))) return rc;   // (a position ends at most one seed)
+	char *hu = B.h_kin.as<char>();
+	memcpy(hu, tab_aa13(), 256);
+	{ int64_t *qo = (int64_t*)(hu + off_qo); for (int32_t i = 0; i <= n_query; ++i) qo[i] = q->q_off[i] - base; }
+	if (L > 0) memcpy(hu + off_tx, q->seqs + base, (size_t)L);
+	HIP_TRY(hipMemcpyAsync(B.k_in.p, hu, off_tx + (size_t)L, hipMemcpyHostToDevice, s));
+	const char *din = B.k_in.as<char>();
+	char *dq = B.k_q.as<char>();
+	int64_t *d_na = (int64_t*)dq, *d_nk = (int64_t*)(dq + mq), *d_qfirst = (int64_t*)(dq + 2 * mq), *d_jfirst = (int64_t*)(dq + 3 * mq);
+	int32_t *d_mo = (int32_t*)(dq + 4 * mq), *d_flag = (int32_t*)(dq + 4 * mq + fq);
+	SketchParams sp;
+	sp.n_bucket = (int64_t)mi->ki.size(), sp.n_kb = mi->n_kb, sp.kmer = mi->opt.kmer, sp.mod_bit = mi->opt.mod_bit, sp.max_occ = max_occ, sp.pad = 0;
+	const unsigned nwg = (unsigned)((n_query + SKETCH_WAVES - 1) / SKETCH_WAVES);
+	hipLaunchKernelGGL(k_sketch_count, dim3(nwg), dim3(64 * SKETCH_WAVES), 0, s, (const uint8_t*)(din + off_tx), (const int64_t*)(din + off_qo), n_query, (const uint8_t*)din,
+	                   (const int64_t*)d->ki, sp, B.k_cnt.as<int32_t>(), B.k_bkt.as<uint32_t>(), d_na, d_nk, d_mo, d_flag);
+	hipLaunchKernelGGL(k_offsets2, dim3(1), dim3(256), 0, s, (const int64_t*)d_na, (const int64_t*)d_nk, n_query, d_qfirst, d_jfirst);
+	hipLaunchKernelGGL(k_sketch_emit, dim3(nwg), dim3(64 * SKETCH_WAVES), 0, s, (const int64_t*)(din + off_qo), n_query, (const int64_t*)d->ki, B.k_cnt.as<int32_t>(),
+	                   B.k_bkt.as<uint32_t>(), (const int64_t*)d_qfirst, (const int64_t*)d_jfirst, (const int32_t*)d_mo, (const int32_t*)d_flag, B.jobs.as<SeedJobDev>());
+	HIP_TRY(hipGetLastError());
+	// qfirst | jfirst | cut-offs | flags: contiguous on the device, one copy, one wait
+	char *hd = B.h_kout.as<char>();
+	HIP_TRY(hipMemcpyAsync(hd, dq + 2 * mq, 2 * mq + 2 * fq, hipMemcpyDeviceToHost, s));
+	HIP_TRY(wait_stream(ctx, s));
+	out.qfirst = (const int64_t*)hd, out.jfirst = (const int64_t*)(hd + mq), out.max_occ = (const int32_t*)(hd + 2 * mq), out.flag = (const int32_t*)(hd + 2 * mq + fq);
+	out.n_anchor = out.qfirst[n_query], out.n_jobs = out.jfirst[n_query];
+	for (int32_t i = 0; i < n_query; ++i) out.n_flagged += out.flag[i] != 0;
+	return MPA_OK;
+}
+
+// The sketch stage of a mini-batch on the device (sketch_exec.hip): protein text up, the seed jobs of every query left in the
+// seeder context's B.jobs for dev_prechain_forward(jfirst_dev), the two prefix arrays, cut-offs and flags back.  out points into
+// pinned memory of the context, valid until its next sketch.  MPA_ERR_UNSUPPORTED: the caller runs the host stage.
+int dev_sketch_jobs(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t max_occ, const mpa_qbatch_t *q, SketchResult &out)
+{
+	out = SketchResult();
+	const mpa_idxopt_t &io = mi->opt;
+	if (q->n_seq <= 0) { set_error("GPU sketch: an empty batch"); return MPA_ERR_UNSUPPORTED; }
+	if (io.kmer < 1 || io.kmer > 7) { set_error("GPU sketch: k-mers of 1..7 residues only"); return MPA_ERR_UNSUPPORTED; }
+	if (io.mod_bit < 0 || io.mod_bit >= 4 * io.kmer || mi->ki.size() != (size_t)1 << (4 * io.kmer - io.mod_bit)) { set_error("GPU sketch: the index has no k-mer table of 2^(4k - M) buckets"); return MPA_ERR_UNSUPPORTED; }
+	if (q->q_off[q->n_seq] - q->q_off[0] >= (int64_t)INT32_MAX) { set_error("GPU sketch: too many seeds in a batch for 32-bit job indices"); return MPA_ERR_UNSUPPORTED; }
+	HIP_TRY(hipSetDevice(ctx->device));
+	if (dev_upload_index(ctx, mi) != MPA_OK) return MPA_ERR_HIP;
+	DeviceIndex *d = mi->dev[ctx->device];
+	int rc = ensure_dev_ki(ctx, mi, d);
+	if (rc != MPA_OK) return rc;
+	ensure_seed_stream(ctx);
+	tl_alloc_failed = false;
+	rc = dev_sketch_jobs_impl(ctx, mi, d, max_occ, q, out);
+	if (rc == MPA_ERR_HIP && tl_alloc_failed) { (void)hipStreamSynchronize(ctx->seed_stream); out = SketchResult(); return MPA_ERR_UNSUPPORTED; }   // (a pool could not grow: host stage)
+	return rc;
+}
+
+// test hook (mpa_dbg_seed_jobs): the first n_jobs records of B.jobs, and the bucket that rides in their pad field
+int dev_sketch_fetch(mpa_ctx_t *ctx, int64_t n_jobs, SeedJob *jobs, int32_t *bucket)
+{
+	if (n_jobs <= 0) return MPA_OK;
+	SeedBufs &B = ctx->seed;
+	if ((size_t)n_jobs * sizeof(SeedJobDev) > B.jobs.cap) { set_error("dev_sketch_fetch: more jobs than the context holds"); return MPA_ERR_ARG; }
+	HIP_TRY(hipSetDevice(ctx->device));
+	std::vector<SeedJobDev> h((size_t)n_jobs);
+	HIP_TRY(hipMemcpyAsync(h.data(), B.jobs.p, (size_t)n_jobs * sizeof(SeedJobDev), hipMemcpyDeviceToHost, ctx->seed_stream));
+	HIP_TRY(wait_stream(ctx, ctx->seed_stream));
+	for (int64_t i = 0; i < n_jobs; ++i) {
+		const SeedJobDev &j = h[(size_t)i];
+		jobs[i] = SeedJob{ j.kb_off, j.dst, j.cnt, j.qpos, j.qid }, bucket[i] = j.pad;
+	}
+	return MPA_OK;
 }
 } // namespace mpa
 
@@ -1036,6 +1148,7 @@ int dev_index_build(mpa_ctx_t *ctx, mpa_idx_s *mi)
 	HIP_TRY(wait_stream(ctx, s));
 	mi->ki.swap(ki_new), mi->kb.swap(kb_new), mi->n_kb = n_kb;
 	if (d->kb) { (void)hipFree(d->kb); g_dev_bytes -= (long long)d->kb_bytes; }
+	if (d->ki) { (void)hipFree(d->ki); g_dev_bytes -= (long long)d->ki_bytes; d->ki = nullptr, d->ki_bytes = 0; }   // (the new table's offsets go up with the first device sketch)
 	d->kb = d_kb, d->kb_bytes = (size_t)n_kb * 4 + 16;     // stays resident for the seeding kernels
 	g_dev_bytes += (long long)d->kb_bytes;
 	d_kb = nullptr;                                        // (ownership moved: the guard lets go)

@@ -25,6 +25,7 @@
 #include <mutex>
 #include <condition_variable>
 #include <functional>
+#include <memory>
 #include "host_core.h"
 
 namespace mpa {
@@ -59,6 +60,8 @@ struct QueryState {
 	std::vector<uint64_t> ext_refine;    // per region: window extension limits of the refinement (between the planning sub-stages)
 	int64_t win0 = 0;                    // first refinement window of this query in the batch's list (device refinement)
 	int64_t n_anchor = 0;                // anchors those seeds expand to
+	bool seeds_ready = false;            // seeds / n_anchor / max_occ are the host's (stage_seeds has run); false after a device sketch: built when the host anchor stage asks
+	int32_t max_occ = 0;                 // the occurrence cut-off in force for this query (stage_seeds)
 	std::vector<mpa_dp_task_t> local1;   // this query's round-1 DP tasks (plan fields index into it)
 	int64_t base1 = 0;                   // where local1 starts in the batch's round-1 task array
 };
@@ -90,6 +93,7 @@ struct mpa_batch_s {
 	// query as occurrence lists (one job per seed) and the first anchor of every query; empty = the batch is seeded on the host
 	std::vector<SeedJob> seed_jobs;
 	std::vector<int64_t> seed_qfirst;
+	bool dev_sketch = false;         // MPA_GPU_SKETCH: the sketch phase built the shell only, the seeder runs the sketch on the device first
 };
 
 namespace mpa {
@@ -521,7 +525,7 @@ static void stage_seeds(mpa_batch_s *b, QueryState &qs)
 	int32_t max_occ = opt.max_occ;
 	if (sd.size() >= 8) max_occ = std::min(max_occ, occurrence_cutoff(mi, sd));
 	// kept in ascending query position so that the anchor sort only has to look at the block ids
-	qs.seeds.clear(), qs.n_anchor = 0;
+	qs.seeds.clear(), qs.n_anchor = 0, qs.max_occ = max_occ, qs.seeds_ready = true;
 	for (uint64_t s : sd) {
 		const int64_t bkt = (int64_t)(s >> 32), st = mi->ki[bkt], en = bkt + 1 < n_bucket ? mi->ki[bkt + 1] : mi->n_kb;
 		if (en - st <= max_occ && en > st) qs.n_anchor += en - st, qs.seeds.push_back((uint64_t)(uint32_t)s << 32 | (uint64_t)bkt);
@@ -544,6 +548,7 @@ static void stage_anchors_host(mpa_batch_s *b, QueryState &qs, std::vector<uint6
 	const int64_t n_bucket = (int64_t)mi->ki.size();
 	static thread_local std::vector<uint64_t> u;
 	a.clear();
+	if (!qs.seeds_ready) stage_seeds(b, qs);                   // (the batch was sketched on the device, and this query comes back to the host)
 	{
 		AccTimer tm(0);
 		a.reserve((size_t)qs.n_anchor);
@@ -863,9 +868,14 @@ struct SeedModeScope { int keep; explicit SeedModeScope(int m) : keep(tl_seed_mo
 // busy with DP rounds (measured: 2.7 M anchors at config 2 -> host, 25 M at 600 Mbp and 240 M at config 3 -> device).
 static const int64_t kDeviceSeedingMinAnchors = 8000000;
 
-// Phase 1a of a batch, host only: the seeds of every query (sketch, bucket lookup, occurrence cut-off: map.c:126-177 up to the
-// anchor loop) and, if the batch is worth seeding on the device, its seed jobs.  In the stream pipeline this is a stage of its own.
-static mpa_batch_t *batch_sketch_phase(bool have_device, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads)
+// MPA_GPU_SKETCH: 1 = the sketch stage runs on the device wherever device seeding does (sketch_exec.hip); 0 / unset = on the host
+static int gpu_sketch_mode()
+{
+	const char *e = getenv("MPA_GPU_SKETCH");           // (read per call: the tests flip it)
+	return e && atoi(e) != 0 ? 1 : 0;
+}
+
+static mpa_batch_s *batch_shell(const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads)
 {
 	if (mi->kb.empty() && mi->n_kb == 0) { set_error("the index has no k-mer table (genome-only index): cannot map"); return nullptr; }
 	mpa_batch_s *b = new mpa_batch_s();
@@ -875,16 +885,38 @@ static mpa_batch_t *batch_sketch_phase(bool have_device, const mpa_idx_t *mi, co
 	for (int32_t i = 0; i < q->n_seq; ++i) {
 		b->qs[i].qid = i, b->qs[i].seq = q->seqs + q->q_off[i], b->qs[i].qlen = (int32_t)(q->q_off[i + 1] - q->q_off[i]);
 	}
+	return b;
+}
+
+// Phase 1a of a batch, host only: the seeds of every query (sketch, bucket lookup, occurrence cut-off: map.c:126-177 up to the
+// anchor loop) and, if the batch is worth seeding on the device, its seed jobs.  In the stream pipeline this is a stage of its own.
+static void batch_host_seeds(mpa_batch_s *b, bool have_device);
+static mpa_batch_t *batch_sketch_phase(bool have_device, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads)
+{
+	mpa_batch_s *b = batch_shell(mi, opt, q, n_threads);
+	if (!b) return nullptr;
+	// with MPA_GPU_SKETCH the stage runs where its result is consumed: the seeder sketches on the device (batch_device_seed_phase)
+	if (have_device && gpu_sketch_mode() && gpu_seeding_mode() != 0 && prechain_enabled(*opt) && mi->opt.bbit > 0 && q->n_seq > 0) { b->dev_sketch = true; return b; }
+	batch_host_seeds(b, have_device);
+	return b;
+}
+
+// the host's sketch stage: seeds of every query and, if the batch is worth seeding on the device, its seed jobs
+static void batch_host_seeds(mpa_batch_s *b, bool have_device)
+{
+	const mpa_idx_t *mi = b->mi;
+	const mpa_mapopt_t *opt = &b->opt;
+	const mpa_qbatch_t *q = &b->q;
 	const double t0 = now_ms();
 	parallel_for(b->n_threads, q->n_seq, [&](int64_t i) { stage_seeds(b, b->qs[i]); });
 	timing_note("  A1: seeds of all queries", now_ms() - t0);
 	const int mode = gpu_seeding_mode();
-	if (!have_device || mode == 0 || !prechain_enabled(*opt) || mi->opt.bbit <= 0 || q->n_seq == 0) return b;
+	if (!have_device || mode == 0 || !prechain_enabled(*opt) || mi->opt.bbit <= 0 || q->n_seq == 0) return;
 	std::vector<int64_t> &qfirst = b->seed_qfirst;
 	std::vector<size_t> jfirst((size_t)q->n_seq + 1, 0);
 	qfirst.assign((size_t)q->n_seq + 1, 0);
 	for (int32_t i = 0; i < q->n_seq; ++i) qfirst[i + 1] = qfirst[i] + b->qs[i].n_anchor, jfirst[i + 1] = jfirst[i] + b->qs[i].seeds.size();
-	if ((mode < 0 && qfirst[q->n_seq] < kDeviceSeedingMinAnchors) || jfirst[q->n_seq] == 0) { qfirst.clear(); return b; }
+	if ((mode < 0 && qfirst[q->n_seq] < kDeviceSeedingMinAnchors) || jfirst[q->n_seq] == 0) { qfirst.clear(); return; }
 	b->seed_jobs.resize(jfirst[q->n_seq]);
 	const int64_t n_bucket = (int64_t)mi->ki.size();
 	SeedJob *const jobs_p = b->seed_jobs.data();
@@ -900,19 +932,44 @@ static mpa_batch_t *batch_sketch_phase(bool have_device, const mpa_idx_t *mi, co
 		}
 	});
 	timing_note("  A1: seed jobs", now_ms() - t0);
-	return b;
 }
 
 // Phase 1b: the anchors of the seed jobs, the pre-chain and the main chain on the device (seed_exec.hip).  false = error.
-static bool batch_device_seed_phase(mpa_ctx_t *seed_ctx, mpa_batch_s *b, bool want_chains, SeedHold *hold)
+// sketch_ms: receives the wall time of the sketch stage where it ran in this phase (MPA_GPU_SKETCH), else 0
+static bool batch_device_seed_phase(mpa_ctx_t *seed_ctx, mpa_batch_s *b, bool want_chains, SeedHold *hold, double *sketch_ms = nullptr)
 {
-	if (!seed_ctx || b->seed_jobs.empty()) return true;
-	const double t1 = now_ms();
+	if (sketch_ms) *sketch_ms = 0;
+	if (!seed_ctx) return true;
 	const mpa_idx_t *mi = b->mi;
+	SketchResult sk;
+	bool jobs_on_device = false;
+	if (b->dev_sketch) {
+		// the sketch stage on the device: its jobs stay in the seeder context's HBM, the prefix arrays and flags come back
+		b->dev_sketch = false;
+		const double t0 = now_ms();
+		const int rc = dev_sketch_jobs(seed_ctx, const_cast<mpa_idx_s*>(mi), b->opt.max_occ, &b->q, sk);
+		if (rc == MPA_ERR_UNSUPPORTED) {                // (no device memory for ki, k > 7, a batch beyond 32-bit job indices)
+			if (timing_on()) fprintf(stderr, "[mpa-timing]   device sketch declined (%s): sketch on the host\n", mpa_last_error());
+			batch_host_seeds(b, true);
+		} else if (rc != MPA_OK) return false;
+		else {
+			timing_note("  sketch on the GPU (sketch + lookup + cut-off + seed jobs)", now_ms() - t0);
+			for (int32_t i = 0; i < b->q.n_seq; ++i) b->qs[i].n_anchor = sk.qfirst[i + 1] - sk.qfirst[i];   // (0 for a query handed back: stage_seeds counts it)
+			// MPA_GPU_SEED unset keeps its meaning: a batch under the threshold is seeded on the host, from seeds built when asked for
+			jobs_on_device = !((gpu_seeding_mode() < 0 && sk.n_anchor < kDeviceSeedingMinAnchors) || sk.n_jobs == 0);
+		}
+		if (sketch_ms) *sketch_ms = now_ms() - t0;
+		if (rc == MPA_OK && !jobs_on_device) return true;
+	}
+	if (!jobs_on_device && b->seed_jobs.empty()) return true;
+	const double t1 = now_ms();
 	// (with the main chain's parameters the device carries on through both chaining rounds, unless the caller only wants the pre-chain)
 	const ChainParams main_cp = main_chain_params(mi, b->opt);
-	const int rc = dev_prechain_forward(seed_ctx, const_cast<mpa_idx_s*>(mi), prechain_params(mi, b->opt), b->q.n_seq, b->seed_qfirst.data(), b->seed_jobs.data(),
-	                                    (int64_t)b->seed_jobs.size(), b->sparse, want_chains ? &main_cp : nullptr, hold);
+	const int rc = jobs_on_device
+		? dev_prechain_forward(seed_ctx, const_cast<mpa_idx_s*>(mi), prechain_params(mi, b->opt), b->q.n_seq, sk.qfirst, nullptr, sk.n_jobs, b->sparse,
+		                       want_chains ? &main_cp : nullptr, hold, sk.jfirst)
+		: dev_prechain_forward(seed_ctx, const_cast<mpa_idx_s*>(mi), prechain_params(mi, b->opt), b->q.n_seq, b->seed_qfirst.data(), b->seed_jobs.data(),
+		                       (int64_t)b->seed_jobs.size(), b->sparse, want_chains ? &main_cp : nullptr, hold);
 	std::vector<SeedJob>().swap(b->seed_jobs);
 	std::vector<int64_t>().swap(b->seed_qfirst);
 	if (rc == MPA_ERR_UNSUPPORTED) {                    // e.g. the batch does not fit the device: seed on the host
@@ -921,6 +978,10 @@ static bool batch_device_seed_phase(mpa_ctx_t *seed_ctx, mpa_batch_s *b, bool wa
 	}
 	if (rc != MPA_OK) return false;
 	b->seeded_on_device = true;
+	if (jobs_on_device && sk.n_flagged) {               // queries the sketch kernel handed back have no jobs on the device: the host seeds them
+		if (b->sparse.on_host.empty()) b->sparse.on_host.assign((size_t)b->q.n_seq, 0);
+		for (int32_t i = 0; i < b->q.n_seq; ++i) if (sk.flag[i]) b->sparse.on_host[(size_t)i] = 1;
+	}
 	timing_note("  seeding on the GPU (sift + pre-chain + both chaining rounds)", now_ms() - t1);
 	return true;
 }
@@ -1167,6 +1228,77 @@ int64_t mpa_dbg_anchors(const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_
 	const int64_t n = off[q->n_seq];
 	delete b;
 	return n;
+}
+
+// Test hook: the kept seeds of every query (map.c:152-170) as (query position, bucket, occurrences) triples in job order and the
+// occurrence cut-off in force per query, from the host stage (ctx == NULL: stage_seeds) or from the device stage (sketch_exec.hip:
+// a download of the jobs it left for k_seed_sift, whose kb_off / dst / qid fields are checked here against ki[] and the prefix
+// arrays).  off[n_seq + 1]: triples before every query; max_occ[n_seq]; *out malloc'd (mpa_free).  Returns the number of queries the
+// device handed to the host (their triples are the host's), or a negative error code.
+int64_t mpa_dbg_seed_jobs(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads, int64_t *off, int32_t *max_occ, int32_t **out)
+{
+	*out = nullptr;
+	return mpa::guarded<int64_t>((int64_t)MPA_ERR_HIP, [&]() -> int64_t {
+		mpa_batch_s *b = batch_shell(mi, opt, q, n_threads);
+		if (!b) return MPA_ERR_ARG;
+		std::unique_ptr<mpa_batch_s> own(b);
+		const int32_t n = q->n_seq;
+		const int64_t n_bucket = (int64_t)mi->ki.size();
+		SketchResult sk;
+		std::vector<SeedJob> jobs;
+		std::vector<int32_t> bucket;
+		if (ctx && n > 0) {
+			int rc = dev_sketch_jobs(ctx, const_cast<mpa_idx_s*>(mi), opt->max_occ, q, sk);
+			if (rc != MPA_OK) return rc;
+			jobs.resize((size_t)sk.n_jobs), bucket.resize((size_t)sk.n_jobs);
+			if ((rc = dev_sketch_fetch(ctx, sk.n_jobs, jobs.data(), bucket.data())) != MPA_OK) return rc;
+		}
+		parallel_for(b->n_threads, n, [&](int64_t i) { if (!ctx || sk.flag[i]) stage_seeds(b, b->qs[i]); });
+		off[0] = 0;
+		for (int32_t i = 0; i < n; ++i) off[i + 1] = off[i] + (b->qs[i].seeds_ready ? (int64_t)b->qs[i].seeds.size() : sk.jfirst[i + 1] - sk.jfirst[i]);
+		int32_t *o = (int32_t*)malloc((size_t)std::max<int64_t>(off[n], 1) * 12);
+		if (!o) { set_error("out of host memory"); return MPA_ERR_ARG; }
+		for (int32_t i = 0; i < n; ++i) {
+			int32_t *t = o + 3 * off[i];
+			const QueryState &qs = b->qs[i];
+			if (qs.seeds_ready) {
+				max_occ[i] = qs.max_occ;
+				for (uint64_t kq : qs.seeds) {
+					const int64_t bkt = (int64_t)(uint32_t)kq, st = mi->ki[bkt], en = bkt + 1 < n_bucket ? mi->ki[bkt + 1] : mi->n_kb;
+					*t++ = (int32_t)(kq >> 32), *t++ = (int32_t)bkt, *t++ = (int32_t)(en - st);
+				}
+				continue;
+			}
+			max_occ[i] = sk.max_occ[i];
+			int64_t dst = sk.qfirst[i];
+			for (int64_t j = sk.jfirst[i]; j < sk.jfirst[i + 1]; ++j) {
+				const SeedJob &s = jobs[(size_t)j];
+				const int64_t bkt = (int64_t)(uint32_t)bucket[(size_t)j];
+				if (bkt >= n_bucket || s.kb_off != mi->ki[bkt] || s.dst != dst || s.qid != i) {
+					free(o);
+					set_error("device seed job " + std::to_string(j) + " of query " + std::to_string(i) + ": kb_off / dst / qid differ from the index and the prefix arrays");
+					return MPA_ERR_ARG;
+				}
+				*t++ = s.qpos, *t++ = (int32_t)bkt, *t++ = s.cnt;
+				dst += s.cnt;
+			}
+			if (dst != sk.qfirst[i + 1]) { free(o); set_error("device seed jobs of query " + std::to_string(i) + ": their counts do not add up to qfirst"); return MPA_ERR_ARG; }
+		}
+		*out = o;
+		return ctx ? (int64_t)sk.n_flagged : 0;
+	});
+}
+
+// cnt[i] = occurrences of bucket[i] in the index's k-mer table (ki[b + 1] - ki[b]; n_kb closes the last bucket).  Host only.
+int mpa_idx_bucket_counts(const mpa_idx_t *mi, int64_t n, const uint32_t *bucket, int64_t *cnt)
+{
+	const int64_t n_bucket = (int64_t)mi->ki.size();
+	for (int64_t i = 0; i < n; ++i) {
+		const int64_t b = (int64_t)bucket[i];
+		if (b >= n_bucket) { set_error("mpa_idx_bucket_counts: bucket " + std::to_string(b) + " beyond the table"); return MPA_ERR_ARG; }
+		cnt[i] = (b + 1 < n_bucket ? mi->ki[b + 1] : mi->n_kb) - mi->ki[b];
+	}
+	return MPA_OK;
 }
 
 int64_t mpa_dbg_prechain_survivors(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads, int64_t *off, uint64_t **out)
@@ -1510,7 +1642,10 @@ static int mpa_map_batches_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_m
 			}
 			trace(kSeedName[sd], k, "begin");
 			bool ok;
-			{ StageClock sc(0); ok = batch_device_seed_phase(seed_dev[sd], slot[k].b, true, hold[k % n_seed_ctx]); }
+			double sketch_ms = 0;
+			{ StageClock sc(0); ok = batch_device_seed_phase(seed_dev[sd], slot[k].b, true, hold[k % n_seed_ctx], &sketch_ms); }
+			// (clock [4] is the sketch stage wherever it ran: with MPA_GPU_SKETCH its time inside this phase moves over from clock [0])
+			if (sketch_ms > 0) g_stage_us[4] += (int64_t)(sketch_ms * 1000.0), g_stage_us[0] -= (int64_t)(sketch_ms * 1000.0);
 			trace(kSeedName[sd], k, "end");
 			if (!ok) { fail(MPA_ERR_HIP, mpa_last_error()); return; }
 			std::lock_guard<std::mutex> g(mu);

@@ -170,6 +170,19 @@ int dev_chain_forward(mpa_ctx_t *ctx, const ChainParams &p, int32_t n_prob, cons
 struct SeedHold;
 SeedHold *ctx_seed_hold(mpa_ctx_t *ctx, int k);   // k-th result holder of a context (created on first use, owned by it)
 int dev_prechain_forward(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams &pre, int32_t n_query, const int64_t *qfirst,
-                         const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, const ChainParams *main = nullptr, SeedHold *hold = nullptr);
+                         const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, const ChainParams *main = nullptr, SeedHold *hold = nullptr,
+                         const int64_t *jfirst_dev = nullptr);
+// The sketch stage (map.c:126-170) of a mini-batch on the device, sketch_exec.hip: the kept seeds of every query as the sift's
+// jobs, left in the context's device memory -- dev_prechain_forward(jobs = nullptr, jfirst_dev = jfirst) then runs on them.  What
+// comes back (pinned memory of the context, valid until its next sketch): first anchor / first job of every query, the cut-off in
+// force, and flag[q] = 1 where the device hands the query to the host (no jobs, no anchors counted for it).
+struct SketchResult {
+	const int64_t *qfirst = nullptr, *jfirst = nullptr;   // [n_query + 1]
+	const int32_t *max_occ = nullptr, *flag = nullptr;    // [n_query]
+	int64_t n_anchor = 0, n_jobs = 0;
+	int32_t n_flagged = 0;
+};
+int dev_sketch_jobs(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t max_occ, const mpa_qbatch_t *q, SketchResult &out);
+int dev_sketch_fetch(mpa_ctx_t *ctx, int64_t n_jobs, SeedJob *jobs, int32_t *bucket);   // test hook: the jobs the last sketch left, and their buckets
 
 } // namespace mpa
