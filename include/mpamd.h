@@ -311,6 +311,14 @@ const char *mpa_version(void);
  * first[n_win + 1] the boundaries.  Returns the number of hits or a negative error code. */
 int64_t mpa_dbg_refine_hits(mpa_ctx_t *ctx, const mpa_idx_t *mi, int32_t kmer, const char *aa, int32_t l_aa, int32_t n_win, const int32_t *vid, const int64_t *as,
                             const int32_t *len, int64_t *first, uint64_t **out);
+/* the refinement chains (what mp_chain() returns at map.c:88) of n_win windows [as, as+len) on vid, window k refined for query
+ * qid[k] of the batch: u = score << 32 | anchors of each chain, a = the chains' anchors (window position << 32 | query position);
+ * off_u / off_a [n_win + 1], *out_u / *out_a (mpa_free).  ctx != NULL: the device refinement (window scan with the query's k-mer
+ * map in LDS or, for a long query, in device memory; pairing; sort; chaining); ctx == NULL: the host stage on the same windows.
+ * host_flag[n_win]: 1 = the device handed this window back to the host (2^22 bases or more, or a query of more than 2^22
+ * residues) and returned no chains for it.  Returns the number of anchors or a negative error code. */
+int64_t mpa_dbg_refine_chains(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int32_t n_win, const int32_t *qid, const int32_t *vid,
+                              const int64_t *as, const int32_t *len, int64_t *off_u, uint64_t **out_u, int64_t *off_a, uint64_t **out_a, uint8_t *host_flag);
 /* forward pass of mp_chain (chain.c:181-209) of n_prob problems (sorted anchors back to back in a[], first[n_prob + 1]): f and
  * pred (index inside the problem, -1 = none) of every anchor, from the device kernel (ctx != NULL) or the host pass (ctx == NULL) */
 int mpa_dbg_chain_forward(mpa_ctx_t *ctx, int32_t max_dist_x, int32_t max_dist_y, int32_t bw, int32_t max_skip, int32_t max_iter, float coef_log,

@@ -147,6 +147,8 @@ def lib():
             ("mpa_result_n_output", C.c_int64, [C.POINTER(MapOpt), C.POINTER(QBatch), C.c_void_p]),
             ("mpa_format_paf", C.c_int64, [C.c_void_p, C.POINTER(MapOpt), C.POINTER(QBatch), C.POINTER(C.c_char_p),
                                            C.c_void_p, C.POINTER(C.c_void_p)]),
+            ("mpa_dbg_refine_chains", C.c_int64, [C.c_void_p, C.c_void_p, C.POINTER(MapOpt), C.POINTER(QBatch), C.c_int32, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
         ]:
             if hasattr(L, name):
                 f = getattr(L, name)
@@ -396,6 +398,27 @@ def map_batch(ctx, idx, mo, queries, n_threads=1):
     res = C.c_void_p()
     _check(lib().mpa_map_batch(ctx.h, idx.h, C.byref(mo), C.byref(queries.c), n_threads, C.byref(res)))
     return Result(res.value)
+
+
+def refine_chains(ctx, idx, mo, queries, wins):
+    """mpa_dbg_refine_chains(): the refinement chains of the windows `wins` = [(query, vid, start, length), ...] -- from the device
+    refinement (ctx) or from the host stage (ctx = None).  Returns (off_u, u, off_a, a, host_flag): u = score << 32 | anchors of each
+    chain and a = the chains' anchors, window k's in [off[k], off[k + 1]); host_flag[k] = 1 where the device handed the window back."""
+    n = len(wins)
+    qid = np.array([w[0] for w in wins], np.int32)
+    vid = np.array([w[1] for w in wins], np.int32)
+    as_ = np.array([w[2] for w in wins], np.int64)
+    ln_ = np.array([w[3] for w in wins], np.int32)
+    off_u, off_a, flag = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64), np.zeros(max(n, 1), np.uint8)
+    pu, pa = C.c_void_p(), C.c_void_p()
+    rc = lib().mpa_dbg_refine_chains(ctx.h if ctx else None, idx.h, C.byref(mo), C.byref(queries.c), n, qid.ctypes.data, vid.ctypes.data, as_.ctypes.data,
+                                     ln_.ctypes.data, off_u.ctypes.data, C.byref(pu), off_a.ctypes.data, C.byref(pa), flag.ctypes.data)
+    if rc < 0:
+        raise MpaError("libmpamd error %d: %s" % (rc, last_error()))
+    u = np.ctypeslib.as_array(C.cast(pu, C.POINTER(C.c_uint64)), (max(int(off_u[n]), 1),))[:int(off_u[n])].copy()
+    a = np.ctypeslib.as_array(C.cast(pa, C.POINTER(C.c_uint64)), (max(int(off_a[n]), 1),))[:int(off_a[n])].copy()
+    lib().mpa_free(pu), lib().mpa_free(pa)
+    return off_u, u, off_a, a, flag[:n]
 
 
 CLAIM_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p)

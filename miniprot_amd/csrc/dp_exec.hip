@@ -138,6 +138,7 @@ struct SeedBufs {
 	HostPinned h_jobs;
 	SeedHold own;                                                          // results of a call without a holder of its own (blocking path, refinement)
 	DevBuf r_win, r_chunk, r_words, r_hits, r_count;      // refinement scan
+	DevBuf r_gmap;                                        // ... the k-mer tables of long queries (k_refine_gmap_build), grow-only
 	HostPinned h_rhits;
 	DevBuf pf_qfirst2, val64[2];                                            // first kept anchor of every query; the kept anchors' values
 	DevBuf s_meta, s_cur, s_cur2, s_kept, s_base, s_out, s_flag, dkey;      // k_seed_sift: segments + per-query tables, list cursors, per-segment results, dense keys
@@ -213,7 +214,7 @@ template<typename F> static void ctx_each_devbuf(mpa_ctx_s *ctx, F f)
 	                  &B.c_a, &B.c_f, &B.c_pred, &B.c_mark, &B.c_flag, &B.c_first, &B.c_long,
 	                  &B.pf_qfirst2, &B.val64[0], &B.val64[1],
 	                  &B.s_meta, &B.s_cur, &B.s_cur2, &B.s_kept, &B.s_base, &B.s_out, &B.s_flag, &B.dkey, &B.x_all, &B.rx_all, &B.rx_keys,
-	                  &ctx->lite, &ctx->ckpt, &ctx->wlist, &B.k_in, &B.k_cnt, &B.k_bkt, &B.k_q };
+	                  &ctx->lite, &ctx->ckpt, &ctx->wlist, &B.k_in, &B.k_cnt, &B.k_bkt, &B.k_q, &B.r_gmap };
 	int k = 0;
 	for (DevBuf *b : all) f(*b, k++);
 }
@@ -1213,9 +1214,45 @@ int dev_chain_forward(mpa_ctx_t *ctx, const ChainParams &cp, int32_t n_prob, con
 } // namespace mpa
 
 namespace mpa {
-// Refinement scan of a mini-batch's region windows on the device (k_refine_scan).  qw_first/qwords: the distinct k-mer words
+// MPA_REFINE_GMAP_MIN: from how many entries (groups in dev_refine_chains, k-mers in dev_refine_scan) a query's k-mer table lives in
+// device memory instead of LDS.  Unset = lds_max + 1, the first size the LDS classes do not take; a smaller number sends more
+// queries there (1 = every query: the tests); "off" = none, and a batch with a longer query is declined.  Read on every call.
+// Returns the threshold, or -1 for "off".
+static int64_t refine_gmap_min(int64_t lds_max)
+{
+	const char *e = getenv("MPA_REFINE_GMAP_MIN");
+	if (!e || !*e) return lds_max + 1;
+	if (!strcmp(e, "off")) return -1;
+	const long long v = atoll(e);
+	return v < 1 ? lds_max + 1 : std::min<int64_t>(v, lds_max + 1);
+}
+// The tables of a call's long queries: slots per query (power of two >= 2 x entries, at least 1 024), their places in the pool.
+struct GmapPlan {
+	std::vector<int32_t> long_q;          // the queries that get a table
+	std::vector<int64_t> desc;            // [n_query] first slot << 8 | log2 slots (0 for the others)
+	int64_t n_slots = 0, max_entries = 0;
+	void add(int32_t q, int64_t entries) {
+		int lg = 10;
+		while ((1LL << lg) < 2 * entries) ++lg;
+		long_q.push_back(q), desc[(size_t)q] = n_slots << 8 | lg;
+		n_slots += 1LL << lg, max_entries = std::max(max_entries, entries);
+	}
+};
+// memset + build of the tables on stream s: d_first / d_words = the entries of every query on the device, d_long / d_desc = the plan
+static int gmap_build(SeedBufs &B, hipStream_t s, const GmapPlan &gp, const int64_t *d_first, const uint32_t *d_words, const int32_t *d_long, const int64_t *d_desc)
+{
+	HIP_TRY(hipMemsetAsync(B.r_gmap.p, 0xff, (size_t)gp.n_slots * 8, s));
+	const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(64, (gp.max_entries + 255) / 256));
+	for (size_t k = 0; k < gp.long_q.size(); k += 65535)            // (gridDim.y)
+		hipLaunchKernelGGL(k_refine_gmap_build, dim3(gx, (unsigned)std::min<size_t>(65535, gp.long_q.size() - k)), dim3(256), 0, s, d_first, d_words, d_long + k, d_desc, B.r_gmap.as<uint32_t>());
+	HIP_TRY(hipGetLastError());
+	return MPA_OK;
+}
+
+// Refinement scan of a mini-batch's region windows on the device (k_refine_scan).  qw_first/qwords: the k-mer words
 // of every query.  out.first[w] .. out.first[w+1]: the hits (hash << 32 | window position) of window w, unsorted.
-// MPA_ERR_UNSUPPORTED (the caller scans on the host): a query with more words than the LDS hash set takes, k too large.
+// Windows of a query with more than 4 096 k-mers (MPA_REFINE_GMAP_MIN) go to a second launch that probes the query's table in
+// device memory (k_refine_scan_gset).  MPA_ERR_UNSUPPORTED (the caller scans on the host): k too large.
 int dev_refine_scan(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_aa_len, int32_t n_query, const int64_t *qw_first, const uint32_t *qwords,
                     int64_t n_win, const RefineWindow *wins, RefineHits &out)
 {
@@ -1224,11 +1261,21 @@ int dev_refine_scan(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_aa_
 	if (n_win == 0) return MPA_OK;
 	static_assert(REFINE_HALO == kRefineHaloBases, "dev_refine_in_range() states the halo of the scan kernels");
 	if (!dev_refine_in_range(kmer, min_aa_len)) { set_error("refinement scan: parameters outside the device kernel's range"); return MPA_ERR_UNSUPPORTED; }
-	int64_t max_words = 0;
-	for (int32_t q = 0; q < n_query; ++q) max_words = std::max(max_words, qw_first[q + 1] - qw_first[q]);
+	const int64_t gmin = refine_gmap_min(4096);
+	GmapPlan gp;
+	gp.desc.assign((size_t)n_query, 0);
+	std::vector<uint8_t> q_used((size_t)n_query, 0);
+	for (int64_t k = 0; k < n_win; ++k) if (wins[k].len > 0) q_used[(size_t)wins[k].qid] = 1;
+	int64_t max_words = 0;                                     // ... of the queries whose set goes to LDS
+	for (int32_t q = 0; q < n_query; ++q) {
+		const int64_t nw = qw_first[q + 1] - qw_first[q];
+		if (gmin > 0 && nw >= gmin) { if (q_used[(size_t)q]) gp.add(q, nw); }
+		else max_words = std::max(max_words, nw);
+	}
 	int hs_log2 = 10;
 	while ((1LL << hs_log2) < 2 * max_words) ++hs_log2;
 	if (hs_log2 > 13) { set_error("refinement scan: query too long for the LDS k-mer set"); return MPA_ERR_UNSUPPORTED; }
+	const size_t n_long = gp.long_q.size();
 	HIP_TRY(hipSetDevice(ctx->device));
 	if (dev_upload_index(ctx, mi) != MPA_OK) return MPA_ERR_HIP;
 	SeedBufs &B = ctx->seed;
@@ -1243,21 +1290,29 @@ int dev_refine_scan(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_aa_
 	const int64_t n_words = qw_first[n_query];
 	auto al64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
 	const size_t o_win = 0, o_chunk = al64((size_t)n_win * sizeof(RefineWindowDev)), o_qf = o_chunk + al64((size_t)n_chunk * sizeof(RefineChunk)),
-	             o_words = o_qf + al64(((size_t)n_query + 1) * 8), up_bytes = o_words + al64((size_t)n_words * 4 + 16);
+	             o_words = o_qf + al64(((size_t)n_query + 1) * 8), o_gd = o_words + al64((size_t)n_words * 4 + 16), o_lq = o_gd + al64((size_t)n_query * 8 + 8),
+	             up_bytes = o_lq + al64(n_long * 4 + 4);
 	int rc;
 	if ((rc = B.h_meta.ensure(up_bytes + 64)) || (rc = B.r_win.ensure(up_bytes)) || (rc = B.r_hits.ensure((size_t)cap * 16)) || (rc = B.r_count.ensure(16)) ||
-	    (rc = B.h_back.ensure(64))) return rc;
+	    (rc = B.h_back.ensure(64)) || (n_long && (rc = B.r_gmap.ensure((size_t)gp.n_slots * 8)))) return rc;
 	char *hm = B.h_meta.as<char>();
+	int64_t c_lds = 0;                                         // the chunks of the LDS launch come first, then those of the long queries' windows
 	{
 		RefineWindowDev *dw = (RefineWindowDev*)(hm + o_win);
 		RefineChunk *ch = (RefineChunk*)(hm + o_chunk);
 		int64_t c = 0;
-		for (int64_t k = 0; k < n_win; ++k) {
-			dw[k] = RefineWindowDev{ wins[k].as, wins[k].qid, wins[k].vid, wins[k].len, 0 };
-			for (int32_t st = 0; st < wins[k].len; st += REFINE_CHUNK) ch[c++] = RefineChunk{ (int32_t)k, st };
+		for (int pass = 0; pass < 2; ++pass) {
+			for (int64_t k = 0; k < n_win; ++k) {
+				if (pass == 0) dw[k] = RefineWindowDev{ wins[k].as, wins[k].qid, wins[k].vid, wins[k].len, 0 };
+				if ((gp.desc[(size_t)wins[k].qid] != 0) != (pass == 1)) continue;
+				for (int32_t st = 0; st < wins[k].len; st += REFINE_CHUNK) ch[c++] = RefineChunk{ (int32_t)k, st };
+			}
+			if (pass == 0) c_lds = c;
 		}
 		memcpy(hm + o_qf, qw_first, ((size_t)n_query + 1) * 8);
 		memcpy(hm + o_words, qwords, (size_t)n_words * 4);
+		memcpy(hm + o_gd, gp.desc.data(), (size_t)n_query * 8);
+		if (n_long) memcpy(hm + o_lq, gp.long_q.data(), n_long * 4);
 	}
 	HIP_TRY(hipMemcpyAsync(B.r_win.p, hm, up_bytes, hipMemcpyHostToDevice, s));
 	HIP_TRY(hipMemsetAsync(B.r_count.p, 0, 16, s));
@@ -1266,8 +1321,16 @@ int dev_refine_scan(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_aa_
 	DevGenome dg{ mi->dev[ctx->device]->seq, mi->dev[ctx->device]->ctg_off, mi->dev[ctx->device]->ctg_len, nullptr, mi->l_seq };
 	const size_t lds = ((size_t)4 << hs_log2) + REFINE_CHUNK + 2 * REFINE_HALO;
 	const char *dm = B.r_win.as<char>();
-	hipLaunchKernelGGL(k_refine_scan, dim3((unsigned)n_chunk), dim3(256), lds, s, dg, (const RefineWindowDev*)(dm + o_win), (const RefineChunk*)(dm + o_chunk),
-	                   (const int64_t*)(dm + o_qf), (const uint32_t*)(dm + o_words), rt, kmer, min_aa_len, hs_log2, B.r_hits.as<uint4>(), B.r_count.as<unsigned long long>(), cap);
+	if (c_lds > 0)
+		hipLaunchKernelGGL(k_refine_scan, dim3((unsigned)c_lds), dim3(256), lds, s, dg, (const RefineWindowDev*)(dm + o_win), (const RefineChunk*)(dm + o_chunk),
+		                   (const int64_t*)(dm + o_qf), (const uint32_t*)(dm + o_words), rt, kmer, min_aa_len, hs_log2, B.r_hits.as<uint4>(), B.r_count.as<unsigned long long>(), cap);
+	if (n_chunk > c_lds) {
+		if ((rc = gmap_build(B, s, gp, (const int64_t*)(dm + o_qf), (const uint32_t*)(dm + o_words), (const int32_t*)(dm + o_lq), (const int64_t*)(dm + o_gd)))) return rc;
+		hipLaunchKernelGGL(k_refine_scan_gset, dim3((unsigned)(n_chunk - c_lds)), dim3(256), REFINE_CHUNK + 2 * REFINE_HALO, s, dg, (const RefineWindowDev*)(dm + o_win),
+		                   (const RefineChunk*)(dm + o_chunk) + c_lds, rt, kmer, min_aa_len, B.r_hits.as<uint4>(), B.r_count.as<unsigned long long>(), cap,
+		                   RefineGmap{ B.r_gmap.as<uint2>(), (const int64_t*)(dm + o_gd) });
+		if (timing_on()) fprintf(stderr, "[mpa-timing]     refine scan: global-set launch (%zu queries, %lld chunks)\n", n_long, (long long)(n_chunk - c_lds));
+	}
 	HIP_TRY(hipGetLastError());
 	unsigned long long *h_n = B.h_back.as<unsigned long long>();
 	HIP_TRY(hipMemcpyAsync(h_n, B.r_count.p, 8, hipMemcpyDeviceToHost, s));
@@ -1292,21 +1355,42 @@ int dev_refine_scan(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_aa_
 namespace mpa {
 // mp_refine_reg (map.c:32-96) for all windows of a mini-batch on the device: see the kernels in seed_exec.hip ("Refinement
 // pairing on the device") and k_chain_fwd / k_chain_fwd_wave / k_chain_extract.  MPA_ERR_UNSUPPORTED: outside the kernels' range
-// (the caller refines on the host).
+// (the caller refines on the host).  out.on_host[w] = 1: this window alone is the host's (2^22 bases or more, or a query with a
+// position of 2^22 or more -- the sort key window << 44 | position << 22 | query position holds neither); its chains come back empty.
+// A query with more groups than the largest LDS map takes (MPA_REFINE_GMAP_MIN) gets its map in device memory: a fourth launch.
 int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_aa_len, int32_t max_ava, const ChainParams &cp, int32_t n_query, const RefineGroupsHost &G,
                       int64_t n_win, const RefineWindow *wins, RefineChains &out)
 {
 	out.u_first.assign((size_t)n_win + 1, 0), out.a_first.assign((size_t)n_win + 1, 0);
 	out.U = out.A = nullptr;
+	out.on_host.assign((size_t)n_win, 0);
 	if (n_win == 0) return MPA_OK;
 	if (!dev_refine_in_range(kmer, min_aa_len) || cp.bbit != 0) { set_error("device refinement: parameters outside the kernels' range"); return MPA_ERR_UNSUPPORTED; }
 	if (n_win >= (1 << 20)) { set_error("device refinement: more than 2^20 windows in a batch"); return MPA_ERR_UNSUPPORTED; }
-	int64_t max_groups = 0;
-	for (int32_t q = 0; q < n_query; ++q) max_groups = std::max(max_groups, G.qg_first[(size_t)q + 1] - G.qg_first[(size_t)q]);
-	int hs_log2 = 10;
-	while ((1LL << hs_log2) < 2 * max_groups) ++hs_log2;
-	if (hs_log2 > 12) { set_error("device refinement: query too long for the LDS k-mer map"); return MPA_ERR_UNSUPPORTED; }
-	for (uint32_t p : G.qpos) if (p >= (1u << 22)) { set_error("device refinement: a query longer than 2^22 residues"); return MPA_ERR_UNSUPPORTED; }
+	const int64_t gmin = refine_gmap_min(2048);
+	// which windows the device takes, and the size class of every query that has one: 0..2 = LDS map of 1 024 / 2 048 / 4 096 slots, 3 = map in device memory
+	std::vector<uint8_t> q_far((size_t)n_query, 0);
+	std::vector<int8_t> q_cls((size_t)n_query, -1);
+	for (int32_t q = 0; q < n_query; ++q) {
+		const int64_t g0 = G.qg_first[(size_t)q], g1 = G.qg_first[(size_t)q + 1];
+		const size_t p0 = g0 < g1 ? G.gfirst[(size_t)g0] : 0, p1 = g0 < g1 ? (size_t)G.gfirst[(size_t)g1 - 1] + G.gcount[(size_t)g1 - 1] : 0;
+		for (size_t k = p0; k < p1; ++k) if (G.qpos[k] >= (1u << 22)) { q_far[(size_t)q] = 1; break; }
+	}
+	GmapPlan gp;
+	gp.desc.assign((size_t)n_query, 0);
+	int64_t n_long_win = 0;
+	for (int64_t k = 0; k < n_win; ++k) {
+		const size_t q = (size_t)wins[k].qid;
+		if (wins[k].len >= (1 << 22) || q_far[q]) { out.on_host[(size_t)k] = 1; continue; }
+		if (q_cls[q] < 0) {
+			const int64_t ng = G.qg_first[q + 1] - G.qg_first[q];
+			if (gmin > 0 && ng >= gmin) q_cls[q] = 3, gp.add((int32_t)q, ng);
+			else if (2 * ng > 4096) { set_error("device refinement: query too long for the LDS k-mer map"); return MPA_ERR_UNSUPPORTED; }
+			else q_cls[q] = 2 * ng <= 1024 ? 0 : 2 * ng <= 2048 ? 1 : 2;
+		}
+		n_long_win += q_cls[q] == 3;
+	}
+	const size_t n_long = gp.long_q.size();
 	HIP_TRY(hipSetDevice(ctx->device));
 	if (dev_upload_index(ctx, mi) != MPA_OK) return MPA_ERR_HIP;
 	SeedBufs &B = ctx->seed;
@@ -1317,7 +1401,7 @@ int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_a
 	static const int n_super = [] { const char *e = getenv("MPA_REFINE_SUPER"); const int v = e ? atoi(e) : REFINE_SUPER; return v < 1 ? 1 : v > 16 ? 16 : v; }();
 	int64_t n_pos = 0, n_chunk = 0, wg_total = 0;
 	for (int64_t k = 0; k < n_win; ++k) {
-		if (wins[k].len >= (1 << 22)) { set_error("device refinement: a window longer than 2^22 bases"); return MPA_ERR_UNSUPPORTED; }
+		if (out.on_host[(size_t)k]) continue;
 		n_pos += wins[k].len, n_chunk += (wins[k].len + n_super * REFINE_CHUNK - 1) / (n_super * REFINE_CHUNK);   // (a workgroup sweeps n_super chunks of its window)
 	}
 	if (n_chunk == 0) return MPA_OK;
@@ -1326,11 +1410,11 @@ int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_a
 	auto al64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
 	const size_t o_win = 0, o_chunk = al64(NW * sizeof(RefineWindowDev)), o_wg = o_chunk + al64((size_t)n_chunk * sizeof(RefineChunk)), o_qg = o_wg + al64((NW + 1) * 8),
 	             o_gw = o_qg + al64((NQ + 1) * 8), o_gf = o_gw + al64(n_group * 4 + 4), o_gc = o_gf + al64(n_group * 4 + 4), o_qp = o_gc + al64(n_group * 4 + 4),
-	             up_bytes = o_qp + al64(n_qpos * 4 + 4);
+	             o_gd = o_qp + al64(n_qpos * 4 + 4), o_lq = o_gd + al64(NQ * 8 + 8), up_bytes = o_lq + al64(n_long * 4 + 4);
 	int rc;
-	int64_t cls_end[3] = { 0, 0, 0 };                          // chunks of the windows whose query's map has 1 024 / 2 048 / 4 096 slots end here
+	int64_t cls_end[4] = { 0, 0, 0, 0 };                       // chunks of the windows whose query's map has 1 024 / 2 048 / 4 096 LDS slots, or lives in device memory, end here
 	if ((rc = B.h_meta.ensure(up_bytes + 64)) || (rc = B.r_win.ensure(up_bytes)) || (rc = B.r_hits.ensure((size_t)cap * 16)) || (rc = B.r_count.ensure(16)) ||
-	    (rc = B.h_back.ensure(256))) return rc;
+	    (rc = B.h_back.ensure(256)) || (n_long && (rc = B.r_gmap.ensure((size_t)gp.n_slots * 8)))) return rc;
 	char *hm = B.h_meta.as<char>();
 	{
 		RefineWindowDev *dw = (RefineWindowDev*)(hm + o_win);
@@ -1339,17 +1423,16 @@ int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_a
 		for (int64_t k = 0; k < n_win; ++k) {
 			dw[k] = RefineWindowDev{ wins[k].as, wins[k].qid, wins[k].vid, wins[k].len, 0 };
 			wg[k] = wg_total;
-			wg_total += G.qg_first[(size_t)wins[k].qid + 1] - G.qg_first[(size_t)wins[k].qid];
+			if (!out.on_host[(size_t)k]) wg_total += G.qg_first[(size_t)wins[k].qid + 1] - G.qg_first[(size_t)wins[k].qid];   // (a window of the host has no workgroup, no hits, no pairs: an empty problem)
 		}
 		wg[n_win] = wg_total;
-		// the workgroups of a window, grouped by the size of its query's k-mer map (1 024 / 2 048 / 4 096 slots): one launch per size, so
-		// that the windows of ordinary proteins take 13 KB of LDS per workgroup and not the 37 KB the batch's longest protein needs
+		// the workgroups of a window, grouped by the size of its query's k-mer map (1 024 / 2 048 / 4 096 slots, or a table in device
+		// memory): one launch per size, so that the windows of ordinary proteins take 13 KB of LDS per workgroup and not the 37 KB the
+		// longest protein of the LDS classes needs
 		int64_t c = 0;
-		for (int cls = 0; cls < 3; ++cls) {
+		for (int cls = 0; cls < 4; ++cls) {
 			for (int64_t k = 0; k < n_win; ++k) {
-				const int64_t ng = G.qg_first[(size_t)wins[k].qid + 1] - G.qg_first[(size_t)wins[k].qid];
-				const int kc = 2 * ng <= 1024 ? 0 : 2 * ng <= 2048 ? 1 : 2;
-				if (kc != cls) continue;
+				if (out.on_host[(size_t)k] || q_cls[(size_t)wins[k].qid] != cls) continue;
 				for (int32_t st = 0; st < wins[k].len; st += n_super * REFINE_CHUNK) ch[c++] = RefineChunk{ (int32_t)k, st };
 			}
 			cls_end[cls] = c;
@@ -1357,6 +1440,8 @@ int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_a
 		memcpy(hm + o_qg, G.qg_first.data(), (NQ + 1) * 8);
 		if (n_group) memcpy(hm + o_gw, G.gword.data(), n_group * 4), memcpy(hm + o_gf, G.gfirst.data(), n_group * 4), memcpy(hm + o_gc, G.gcount.data(), n_group * 4);
 		if (n_qpos) memcpy(hm + o_qp, G.qpos.data(), n_qpos * 4);
+		memcpy(hm + o_gd, gp.desc.data(), NQ * 8);
+		if (n_long) memcpy(hm + o_lq, gp.long_q.data(), n_long * 4);
 	}
 	// device tables: per (window, group) hit counts and per-window pair counts, zeroed
 	size_t at = 0;
@@ -1384,6 +1469,13 @@ int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_a
 		const size_t lds = ((size_t)8 << hs) + 2 * (REFINE_CHUNK + 2 * REFINE_HALO);   // k-mer map, bases, codons
 		hipLaunchKernelGGL(k_refine_scan_map, dim3((unsigned)c_n), dim3(256), lds, s, dg, (const RefineWindowDev*)(dm + o_win), (const RefineChunk*)(dm + o_chunk) + c_first, gr, d_wg, rt,
 		                   kmer, min_aa_len, hs, B.r_hits.as<uint4>(), B.r_count.as<unsigned long long>(), cap, d_wcnt, (int32_t)n_super);
+	}
+	if (cls_end[3] > cls_end[2]) {                             // the long queries: their tables once per batch, then the scan that probes them (LDS: bases + codons)
+		if ((rc = gmap_build(B, s, gp, gr.qg_first, gr.gword, (const int32_t*)(dm + o_lq), (const int64_t*)(dm + o_gd)))) return rc;
+		hipLaunchKernelGGL(k_refine_scan_gmap, dim3((unsigned)(cls_end[3] - cls_end[2])), dim3(256), 2 * (REFINE_CHUNK + 2 * REFINE_HALO), s, dg, (const RefineWindowDev*)(dm + o_win),
+		                   (const RefineChunk*)(dm + o_chunk) + cls_end[2], gr, d_wg, rt, kmer, min_aa_len, B.r_hits.as<uint4>(), B.r_count.as<unsigned long long>(), cap, d_wcnt, (int32_t)n_super,
+		                   RefineGmap{ B.r_gmap.as<uint2>(), (const int64_t*)(dm + o_gd) });
+		if (timing_on()) fprintf(stderr, "[mpa-timing]     refine: global-map class (%zu queries, %lld windows)\n", n_long, (long long)n_long_win);
 	}
 	HIP_TRY(hipGetLastError());
 	unsigned long long *h_n = B.h_back.as<unsigned long long>();

@@ -639,10 +639,16 @@ static void stage_refine_to_plan(mpa_batch_s *b, QueryState &qs, const RefineHit
 		AccTimer tm(5);
 		std::vector<Region> kept;
 		if (rc) {
+			std::unique_ptr<RefineQuery> rq;                         // (only for a window the device handed back: rc->on_host)
 			for (size_t i = 0; i < regs.size(); ++i) {
 				const size_t w = (size_t)qs.win0 + i;
-				g_acc[13] += 1000000LL;
-				refine_region_from_chains(mi, opt, regs[i], (int32_t)(ext[i] >> 32), rc->U + rc->u_first[w], rc->u_first[w + 1] - rc->u_first[w], rc->A + rc->a_first[w]);
+				if (!rc->on_host.empty() && rc->on_host[w]) {
+					if (!rq) rq.reset(new RefineQuery(qs.seq, qs.qlen, opt.kmer2));
+					refine_region(mi, opt, *rq, regs[i], (int32_t)(ext[i] >> 32), (int32_t)ext[i]);
+				} else {
+					g_acc[13] += 1000000LL;
+					refine_region_from_chains(mi, opt, regs[i], (int32_t)(ext[i] >> 32), rc->U + rc->u_first[w], rc->u_first[w + 1] - rc->u_first[w], rc->A + rc->a_first[w]);
+				}
 				if (regs[i].cnt > 0) kept.push_back(std::move(regs[i]));
 			}
 		} else {
@@ -1045,6 +1051,24 @@ static void query_groups(const char *aa, int32_t l_aa, int32_t k, QueryGroups &o
 	}
 }
 
+// the groups of all queries of a batch, back to back (what dev_refine_chains takes)
+static void gather_query_groups(const QueryGroups *per, int64_t n_q, RefineGroupsHost &G)
+{
+	G.qg_first.assign((size_t)n_q + 1, 0);
+	size_t n_kmer = 0;
+	for (int64_t i = 0; i < n_q; ++i) G.qg_first[(size_t)i + 1] = G.qg_first[(size_t)i] + (int64_t)per[(size_t)i].gword.size(), n_kmer += per[(size_t)i].qpos.size();
+	G.gword.resize((size_t)G.qg_first[(size_t)n_q]), G.gcount.resize(G.gword.size()), G.gfirst.resize(G.gword.size()), G.qpos.resize(n_kmer);
+	size_t at = 0;
+	for (int64_t i = 0; i < n_q; ++i) {
+		const QueryGroups &p = per[(size_t)i];
+		const size_t g0 = (size_t)G.qg_first[(size_t)i];
+		size_t k0 = at;
+		for (size_t g = 0; g < p.gword.size(); ++g) G.gword[g0 + g] = p.gword[g], G.gcount[g0 + g] = p.gcount[g], G.gfirst[g0 + g] = (uint32_t)k0, k0 += p.gcount[g];
+		if (!p.qpos.empty()) memcpy(&G.qpos[at], p.qpos.data(), p.qpos.size() * 4);
+		at += p.qpos.size();
+	}
+}
+
 static void batch_plan_phase(mpa_batch_s *b, mpa_ctx_t *rctx)
 {
 	const double t0 = now_ms();
@@ -1096,21 +1120,7 @@ static void batch_plan_phase(mpa_batch_s *b, mpa_ctx_t *rctx)
 			per.resize((size_t)n_q);
 			QueryGroups *perp = per.data();
 			parallel_for(b->n_threads, n_q, [&, perp](int64_t i) { query_groups(b->qs[i].seq, b->qs[i].qlen, b->opt.kmer2, perp[i]); });
-			G.qg_first.assign((size_t)n_q + 1, 0);
-			size_t n_kmer = 0;
-			for (int64_t i = 0; i < n_q; ++i) G.qg_first[(size_t)i + 1] = G.qg_first[(size_t)i] + (int64_t)per[(size_t)i].gword.size(), n_kmer += per[(size_t)i].qpos.size();
-			G.gword.resize((size_t)G.qg_first[(size_t)n_q]), G.gcount.resize(G.gword.size()), G.gfirst.resize(G.gword.size()), G.qpos.resize(n_kmer);
-			{
-				size_t at = 0;
-				for (int64_t i = 0; i < n_q; ++i) {
-					const QueryGroups &p = per[(size_t)i];
-					const size_t g0 = (size_t)G.qg_first[(size_t)i];
-					size_t k0 = at;
-					for (size_t g = 0; g < p.gword.size(); ++g) G.gword[g0 + g] = p.gword[g], G.gcount[g0 + g] = p.gcount[g], G.gfirst[g0 + g] = (uint32_t)k0, k0 += p.gcount[g];
-					if (!p.qpos.empty()) memcpy(&G.qpos[at], p.qpos.data(), p.qpos.size() * 4);
-					at += p.qpos.size();
-				}
-			}
+			gather_query_groups(perp, n_q, G);
 			const double t1 = now_ms();
 			const int rc = dev_refine_chains(rctx, const_cast<mpa_idx_s*>(b->mi), b->opt.kmer2, b->mi->opt.min_aa_len, b->opt.max_ava, refine_chain_params(b->opt), (int32_t)n_q, G,
 			                                 (int64_t)wins.size(), wins.data(), rchains);
@@ -1203,6 +1213,60 @@ int64_t mpa_dbg_refine_hits(mpa_ctx_t *ctx, const mpa_idx_t *mi, int32_t kmer, c
 	for (int32_t k = 0; k < n_win; ++k) memcpy(o + first[k], per[k].data(), per[k].size() * 8);
 	*out = o;
 	return first[n_win];
+}
+
+// Operator-level entry point of the refinement chains: what mp_chain() returns at map.c:88 for n_win windows [as, as + len) on vid,
+// each refined for query qid of the batch -- u = score << 32 | anchors per chain and the chains' anchors (window position << 32 |
+// query position), off_u / off_a [n_win + 1] -- from dev_refine_chains (ctx != NULL) or from the host's refine_region_pairs +
+// chain_anchors (ctx == NULL).  host_flag[n_win]: 1 = the device handed the window back (its chains are then empty here).
+int64_t mpa_dbg_refine_chains(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int32_t n_win, const int32_t *qid, const int32_t *vid,
+                              const int64_t *as, const int32_t *len, int64_t *off_u, uint64_t **out_u, int64_t *off_a, uint64_t **out_a, uint8_t *host_flag)
+{
+	*out_u = *out_a = nullptr;
+	for (int32_t k = 0; k < n_win; ++k) {
+		if (qid[k] < 0 || qid[k] >= q->n_seq || vid[k] < 0 || vid[k] >= 2 * (int32_t)mi->ctg.size() || len[k] < 0 || as[k] < 0 || as[k] + len[k] > mi->ctg[vid[k] >> 1].len) {
+			set_error("mpa_dbg_refine_chains: window " + std::to_string(k) + " is outside its contig or names no query");
+			return MPA_ERR_ARG;
+		}
+		host_flag[k] = 0;
+	}
+	const ChainParams cp = refine_chain_params(*opt);
+	std::vector<std::vector<uint64_t>> us((size_t)n_win), aa((size_t)n_win);
+	if (ctx) {
+		std::vector<QueryGroups> per((size_t)q->n_seq);
+		for (int32_t i = 0; i < q->n_seq; ++i) query_groups(q->seqs + q->q_off[i], (int32_t)(q->q_off[i + 1] - q->q_off[i]), opt->kmer2, per[(size_t)i]);
+		RefineGroupsHost G;
+		gather_query_groups(per.data(), q->n_seq, G);
+		std::vector<RefineWindow> wins((size_t)n_win);
+		for (int32_t k = 0; k < n_win; ++k) wins[(size_t)k] = RefineWindow{ as[k], qid[k], vid[k], len[k] };
+		RefineChains rc;
+		const int r = dev_refine_chains(ctx, const_cast<mpa_idx_s*>(mi), opt->kmer2, mi->opt.min_aa_len, opt->max_ava, cp, q->n_seq, G, n_win, wins.data(), rc);
+		if (r != MPA_OK) return r;
+		for (int32_t k = 0; k < n_win; ++k) {
+			host_flag[k] = rc.on_host[(size_t)k];
+			if (rc.U) us[(size_t)k].assign(rc.U + rc.u_first[(size_t)k], rc.U + rc.u_first[(size_t)k + 1]);
+			if (rc.A) aa[(size_t)k].assign(rc.A + rc.a_first[(size_t)k], rc.A + rc.a_first[(size_t)k + 1]);
+		}
+	} else {
+		for (int32_t k = 0; k < n_win; ++k) {
+			if (len[k] == 0) continue;
+			// (one RefineQuery at a time: a thread has ONE bitmap of k-mer words, which the query that owns it clears when it goes)
+			RefineQuery one(q->seqs + q->q_off[qid[k]], (int32_t)(q->q_off[qid[k] + 1] - q->q_off[qid[k]]), opt->kmer2);
+			Region r;
+			r.vid = (uint32_t)vid[k], r.vs = as[k], r.ve = as[k] + len[k];
+			refine_region_pairs(mi, *opt, one, r, 0, 0, nullptr, 0, aa[(size_t)k]);
+			chain_anchors(cp, aa[(size_t)k], us[(size_t)k]);
+		}
+	}
+	off_u[0] = off_a[0] = 0;
+	for (int32_t k = 0; k < n_win; ++k) off_u[k + 1] = off_u[k] + (int64_t)us[(size_t)k].size(), off_a[k + 1] = off_a[k] + (int64_t)aa[(size_t)k].size();
+	uint64_t *ou = (uint64_t*)malloc((size_t)std::max<int64_t>(off_u[n_win], 1) * 8), *oa = (uint64_t*)malloc((size_t)std::max<int64_t>(off_a[n_win], 1) * 8);
+	for (int32_t k = 0; k < n_win; ++k) {
+		if (!us[(size_t)k].empty()) memcpy(ou + off_u[k], us[(size_t)k].data(), us[(size_t)k].size() * 8);
+		if (!aa[(size_t)k].empty()) memcpy(oa + off_a[k], aa[(size_t)k].data(), aa[(size_t)k].size() * 8);
+	}
+	*out_u = ou, *out_a = oa;
+	return off_a[n_win];
 }
 
 // Test hook (not in include/mpamd.h): the anchors that survive the pre-chain (map.c:163-192), query by query, computed on the

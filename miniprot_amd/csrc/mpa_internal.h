@@ -158,6 +158,7 @@ struct RefineGroupsHost {
 struct RefineChains {
 	std::vector<int64_t> u_first, a_first;   // [n_win + 1]
 	const uint64_t *U = nullptr, *A = nullptr;   // pinned buffers of the context, valid until its next call
+	std::vector<uint8_t> on_host;            // [n_win] 1 = the device left this window out (2^22 bases or more, or its query has a position >= 2^22): refine it on the host
 };
 int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_aa_len, int32_t max_ava, const ChainParams &cp, int32_t n_query, const RefineGroupsHost &groups,
                       int64_t n_win, const RefineWindow *wins, RefineChains &out);

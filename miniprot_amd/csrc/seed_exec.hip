@@ -941,12 +941,54 @@ __device__ __forceinline__ uint32_t d_hash32_mask(uint32_t key, uint32_t mask)  
 	return key;
 }
 
-__global__ __launch_bounds__(256) void k_refine_scan(DevGenome g, const RefineWindowDev *wins, const RefineChunk *chunks, const int64_t *qw_first, const uint32_t *qwords,
-                                                     RefineTab rt, int32_t kmer, int32_t min_aa_len, int32_t hs_log2, uint4 *hits, unsigned long long *n_hits, unsigned long long cap)
+// The k-mer maps of LONG queries live in device memory instead of LDS (past 4 096 LDS slots a workgroup's map would take the CU's
+// LDS from the DP): one open-addressing table per long query in a pool, 8 bytes per slot = (k-mer word, group), so that ONE load
+// answers a probe; same hash as the LDS maps, slots = the power of two >= 2 x entries (at least 1 024), empty = all ones.  The
+// tables of a batch are built once per batch (k_refine_gmap_build, behind one memset of the pool) and stay in L2 for the scan:
+// 1 MB for a 36 000-residue protein against 4 MiB of L2 per XCD.
+struct RefineGmap {
+	const uint2 *slots;          // the pool
+	const int64_t *desc;         // [n_query] first slot << 8 | log2(slots) of the query's table (meaningless for a query that has none)
+};
+__device__ __forceinline__ uint32_t gmap_probe(const uint2 *tab, int32_t log2, uint32_t word)     // the group of `word`, 0xffffffff = not in the table
+{
+	const uint32_t m = (1u << log2) - 1;
+	for (uint32_t slot = (word * 2654435761u) >> (32 - log2);; slot = (slot + 1) & m) {
+		const uint2 kv = tab[slot];
+		if (kv.x == word) return kv.y;
+		if (kv.x == 0xffffffffu) return 0xffffffffu;              // (at most half of the slots are taken: the walk ends)
+	}
+}
+// one workgroup column per long query (blockIdx.y); words[first[q] .. first[q + 1]) are its entries, equal words share a slot
+__global__ __launch_bounds__(256) void k_refine_gmap_build(const int64_t *first, const uint32_t *words, const int32_t *long_q, const int64_t *desc, uint32_t *pool)
+{
+	MPA_SHORT_KERNEL();
+	const int32_t q = long_q[blockIdx.y];
+	const int64_t d = desc[q], k0 = first[q], k1 = first[q + 1];
+	const int32_t log2 = (int32_t)(d & 255);
+	const uint32_t m = (1u << log2) - 1;
+	uint32_t *tab = pool + 2 * (d >> 8);                          // slot s = tab[2 s] (word), tab[2 s + 1] (entry)
+	for (int64_t k = k0 + (int64_t)blockIdx.x * 256 + threadIdx.x; k < k1; k += (int64_t)gridDim.x * 256) {
+		const uint32_t word = words[k];
+		uint32_t slot = (word * 2654435761u) >> (32 - log2);
+		for (;;) {
+			const uint32_t old = atomicCAS(&tab[2 * slot], 0xffffffffu, word);
+			if (old == 0xffffffffu) { tab[2 * slot + 1] = (uint32_t)(k - k0); break; }
+			if (old == word) break;
+			slot = (slot + 1) & m;
+		}
+	}
+}
+
+// GSET: the query's k-mer set is its table in device memory (RefineGmap), not an LDS set filled by the workgroup
+template <bool GSET>
+__device__ __forceinline__ void refine_scan_body(DevGenome g, const RefineWindowDev *wins, const RefineChunk *chunks, const int64_t *qw_first, const uint32_t *qwords,
+                                                 const RefineTab &rt, int32_t kmer, int32_t min_aa_len, int32_t hs_log2, uint4 *hits, unsigned long long *n_hits, unsigned long long cap,
+                                                 const RefineGmap gm)
 {
 	MPA_SHORT_KERNEL();
 	extern __shared__ uint32_t lds_refine[];
-	const int32_t HS = 1 << hs_log2;
+	const int32_t HS = GSET ? 0 : 1 << hs_log2;
 	uint32_t *table = lds_refine;                                   // [HS] open addressing, 0xffffffff = empty
 	uint8_t *base = (uint8_t*)(table + HS);                         // [REFINE_CHUNK + 2 * REFINE_HALO] nt4 codes, 15 = outside the window
 	__shared__ uint8_t tab[64];                                    // codon -> reduced residue, 0xff = stop
@@ -961,7 +1003,7 @@ __global__ __launch_bounds__(256) void k_refine_scan(DevGenome g, const RefineWi
 		base[k] = (p < 0 || p >= w.len) ? 15 : (uint8_t)strand_base(g.seq, off, clen, rev, w.as + p);
 	}
 	__syncthreads();
-	for (int64_t k = qw_first[w.qid] + threadIdx.x; k < qw_first[w.qid + 1]; k += 256) {
+	if (!GSET) for (int64_t k = qw_first[w.qid] + threadIdx.x; k < qw_first[w.qid + 1]; k += 256) {
 		const uint32_t word = qwords[k];
 		uint32_t slot = (word * 2654435761u) >> (32 - hs_log2);
 		for (;;) {
@@ -971,6 +1013,8 @@ __global__ __launch_bounds__(256) void k_refine_scan(DevGenome g, const RefineWi
 		}
 	}
 	__syncthreads();
+	const int64_t gd = GSET ? gm.desc[w.qid] : 0;
+	const uint2 *gtab = GSET ? gm.slots + (gd >> 8) : nullptr;
 	const uint32_t mask = (1u << (4 * kmer)) - 1;
 	auto codon_at = [&](int e) -> uint32_t {                          // reduced residue of the codon whose last base is LDS index e; 0xff if none
 		const uint32_t b0 = base[e - 2], b1 = base[e - 1], b2 = base[e];
@@ -991,7 +1035,8 @@ __global__ __launch_bounds__(256) void k_refine_scan(DevGenome g, const RefineWi
 		if (!ok) continue;
 		word &= mask;
 		bool found = false;
-		for (uint32_t slot = (word * 2654435761u) >> (32 - hs_log2);; slot = (slot + 1) & (HS - 1)) {
+		if (GSET) found = gmap_probe(gtab, (int32_t)(gd & 255), word) != 0xffffffffu;
+		else for (uint32_t slot = (word * 2654435761u) >> (32 - hs_log2);; slot = (slot + 1) & (HS - 1)) {
 			const uint32_t v = table[slot];
 			if (v == word) { found = true; break; }
 			if (v == 0xffffffffu) break;
@@ -1005,6 +1050,17 @@ __global__ __launch_bounds__(256) void k_refine_scan(DevGenome g, const RefineWi
 		const unsigned long long at = atomicAdd(n_hits, 1ULL);
 		if (at < cap) hits[at] = make_uint4((uint32_t)ch.win, (uint32_t)pos, d_hash32_mask(word, mask), 0u);
 	}
+}
+__global__ __launch_bounds__(256) void k_refine_scan(DevGenome g, const RefineWindowDev *wins, const RefineChunk *chunks, const int64_t *qw_first, const uint32_t *qwords,
+                                                     RefineTab rt, int32_t kmer, int32_t min_aa_len, int32_t hs_log2, uint4 *hits, unsigned long long *n_hits, unsigned long long cap)
+{
+	refine_scan_body<false>(g, wins, chunks, qw_first, qwords, rt, kmer, min_aa_len, hs_log2, hits, n_hits, cap, RefineGmap{ nullptr, nullptr });
+}
+// the same scan for the windows of long queries: the k-mer set is the query's table in device memory; LDS holds the bases only
+__global__ __launch_bounds__(256) void k_refine_scan_gset(DevGenome g, const RefineWindowDev *wins, const RefineChunk *chunks, RefineTab rt, int32_t kmer, int32_t min_aa_len,
+                                                          uint4 *hits, unsigned long long *n_hits, unsigned long long cap, RefineGmap gm)
+{
+	refine_scan_body<true>(g, wins, chunks, nullptr, nullptr, rt, kmer, min_aa_len, 0, hits, n_hits, cap, gm);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1027,13 +1083,16 @@ struct RefineGroups {
 	const uint32_t *qpos;        // query positions (index of the k-mer's last residue), group by group, ascending inside a group
 };
 
-__global__ __launch_bounds__(256) void k_refine_scan_map(DevGenome g, const RefineWindowDev *wins, const RefineChunk *chunks, RefineGroups gr, const int64_t *wg_first, RefineTab rt,
-                                                         int32_t kmer, int32_t min_aa_len, int32_t hs_log2, uint4 *hits, unsigned long long *n_hits, unsigned long long cap, uint32_t *wcnt,
-                                                         const int32_t n_super)
+// GMAP: the map word -> group is the query's table in device memory (RefineGmap, built by k_refine_gmap_build), not an LDS map that
+// the workgroup fills; LDS then holds bases, codons and the hit buffer only
+template <bool GMAP>
+__device__ __forceinline__ void refine_scan_map_body(DevGenome g, const RefineWindowDev *wins, const RefineChunk *chunks, RefineGroups gr, const int64_t *wg_first, const RefineTab &rt,
+                                                     int32_t kmer, int32_t min_aa_len, int32_t hs_log2, uint4 *hits, unsigned long long *n_hits, unsigned long long cap, uint32_t *wcnt,
+                                                     const int32_t n_super, const RefineGmap gm)
 {
 	MPA_SHORT_KERNEL();
 	extern __shared__ uint32_t lds_refine[];
-	const int32_t HS = 1 << hs_log2;
+	const int32_t HS = GMAP ? 0 : 1 << hs_log2;
 	uint32_t *tkey = lds_refine, *tval = tkey + HS;               // open addressing: word -> group (0xffffffff = empty)
 	uint8_t *base = (uint8_t*)(tval + HS);                          // [REFINE_CHUNK + 2 * REFINE_HALO] nt4 codes, 15 = outside the window
 	uint8_t *cod = base + REFINE_CHUNK + 2 * REFINE_HALO;           // [same] reduced-alphabet code of the codon ENDING at each position, 0xff = none
@@ -1055,7 +1114,9 @@ __global__ __launch_bounds__(256) void k_refine_scan_map(DevGenome g, const Refi
 	__syncthreads();
 	// the query's k-mer map, once per workgroup; a workgroup sweeps REFINE_SUPER consecutive chunks of its window
 	const int64_t G0 = gr.qg_first[w.qid], G1 = gr.qg_first[w.qid + 1];
-	for (int64_t k = G0 + threadIdx.x; k < G1; k += 256) {
+	const int64_t gd = GMAP ? gm.desc[w.qid] : 0;
+	const uint2 *gtab = GMAP ? gm.slots + (gd >> 8) : nullptr;
+	if (!GMAP) for (int64_t k = G0 + threadIdx.x; k < G1; k += 256) {
 		const uint32_t word = gr.gword[k];
 		uint32_t slot = (word * 2654435761u) >> (32 - hs_log2);
 		for (;;) {
@@ -1109,7 +1170,8 @@ __global__ __launch_bounds__(256) void k_refine_scan_map(DevGenome g, const Refi
 	constexpr int PER = REFINE_CHUNK / 256;
 	auto try_hit = [&](const int32_t pos, const int e, const uint32_t word) {
 		uint32_t grp = 0xffffffffu;
-		for (uint32_t slot = (word * 2654435761u) >> (32 - hs_log2);; slot = (slot + 1) & (HS - 1)) {
+		if (GMAP) grp = gmap_probe(gtab, (int32_t)(gd & 255), word);
+		else for (uint32_t slot = (word * 2654435761u) >> (32 - hs_log2);; slot = (slot + 1) & (HS - 1)) {
 			const uint32_t v = tkey[slot];
 			if (v == word) { grp = tval[slot]; break; }
 			if (v == 0xffffffffu) break;
@@ -1173,6 +1235,19 @@ __global__ __launch_bounds__(256) void k_refine_scan_map(DevGenome g, const Refi
 		if (threadIdx.x == 0) l_n = 0;
 	}
 	}
+}
+__global__ __launch_bounds__(256) void k_refine_scan_map(DevGenome g, const RefineWindowDev *wins, const RefineChunk *chunks, RefineGroups gr, const int64_t *wg_first, RefineTab rt,
+                                                         int32_t kmer, int32_t min_aa_len, int32_t hs_log2, uint4 *hits, unsigned long long *n_hits, unsigned long long cap, uint32_t *wcnt,
+                                                         const int32_t n_super)
+{
+	refine_scan_map_body<false>(g, wins, chunks, gr, wg_first, rt, kmer, min_aa_len, hs_log2, hits, n_hits, cap, wcnt, n_super, RefineGmap{ nullptr, nullptr });
+}
+// the fourth size class ("long": more groups than the largest LDS map takes)
+__global__ __launch_bounds__(256) void k_refine_scan_gmap(DevGenome g, const RefineWindowDev *wins, const RefineChunk *chunks, RefineGroups gr, const int64_t *wg_first, RefineTab rt,
+                                                          int32_t kmer, int32_t min_aa_len, uint4 *hits, unsigned long long *n_hits, unsigned long long cap, uint32_t *wcnt,
+                                                          const int32_t n_super, RefineGmap gm)
+{
+	refine_scan_map_body<true>(g, wins, chunks, gr, wg_first, rt, kmer, min_aa_len, 0, hits, n_hits, cap, wcnt, n_super, gm);
 }
 
 __global__ __launch_bounds__(256) void k_refine_pair_count(const uint4 *hits, int64_t n_hits, const int64_t *wg_first, const uint32_t *wcnt, const uint32_t *gcount, int32_t max_ava,

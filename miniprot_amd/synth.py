@@ -232,13 +232,16 @@ def draw_background(rng, n_ctg, ctg_len, pool):
 
 
 def generate(genome_len, n_ctg, n_prot, seed, mu=7.5, sigma=1.5, imin=70, imax=50000, n_frac=0.0, min_exons=1, mean_len=400, sd_len=160, return_planted=False,
-             paralog_frac=0.0):
+             paralog_frac=0.0, long_frac=0.0, long_len=3000):
+    """long_frac > 0: that share of the proteins is drawn at mean length long_len (sd 40 % of it) instead of mean_len -- which ones, and
+    how long, comes from a generator of its own, so that everything else is drawn as without them"""
     with ThreadPoolExecutor(max_workers=max(1, min(16, os.cpu_count() or 1))) as pool:
-        return _generate(pool, genome_len, n_ctg, n_prot, seed, mu, sigma, imin, imax, n_frac, min_exons, mean_len, sd_len, return_planted, paralog_frac)
+        return _generate(pool, genome_len, n_ctg, n_prot, seed, mu, sigma, imin, imax, n_frac, min_exons, mean_len, sd_len, return_planted, paralog_frac, long_frac, long_len)
 
 
-def _generate(pool, genome_len, n_ctg, n_prot, seed, mu, sigma, imin, imax, n_frac, min_exons, mean_len, sd_len, return_planted, paralog_frac):
+def _generate(pool, genome_len, n_ctg, n_prot, seed, mu, sigma, imin, imax, n_frac, min_exons, mean_len, sd_len, return_planted, paralog_frac, long_frac=0.0, long_len=3000):
     rng = np.random.default_rng(seed)
+    rng_long = np.random.default_rng([seed, 0x10f6]) if long_frac > 0 else None
     ctg_len = genome_len // n_ctg
     # the background fills on the pool's threads while this thread draws the genes; a contig is waited for (and gets its N runs)
     # before the first gene is written into it
@@ -266,6 +269,8 @@ def _generate(pool, genome_len, n_ctg, n_prot, seed, mu, sigma, imin, imax, n_fr
             if k >= n_prot:
                 break
             length = int(max(60, rng.normal(mean_len, sd_len)))
+            if rng_long is not None and rng_long.random() < long_frac:
+                length = int(max(mean_len, rng_long.normal(long_len, 0.4 * long_len)))
             prot, gene = make_gene(rng, length, mu, sigma, imin, imax, min_exons)
             if len(gene) + 2000 > slot:       # too long for its slot: shrink introns by regenerating single-exon
                 prot, gene = make_gene(rng, length, mu, 0.1, imin, min(imax, max(imin + 1, (slot - 3 * length - 2100) // max(1, length // 60))), 1)
@@ -321,9 +326,11 @@ if __name__ == "__main__":
     ap.add_argument("--n-frac", type=float, default=0.0)
     ap.add_argument("--min-exons", type=int, default=1)
     ap.add_argument("--paralog-frac", type=float, default=0.0, help="fraction of the genome that is tandem pseudo-paralogs of planted genes")
+    ap.add_argument("--long-frac", type=float, default=0.0, help="share of the proteins drawn at mean length --long-len")
+    ap.add_argument("--long-len", type=int, default=3000)
     ap.add_argument("--out-prefix", required=True)
     a = ap.parse_args()
     contigs, prots, names = generate(int(a.genome_mb * 1e6), a.n_ctg, a.n_prot, a.seed, a.intron_mu, a.intron_sigma, a.intron_min,
-                                     a.intron_max, a.n_frac, a.min_exons, paralog_frac=a.paralog_frac)
+                                     a.intron_max, a.n_frac, a.min_exons, paralog_frac=a.paralog_frac, long_frac=a.long_frac, long_len=a.long_len)
     write_fasta_nt(a.out_prefix + ".genome.fa", contigs)
     write_fasta_aa(a.out_prefix + ".prot.fa", prots, names)

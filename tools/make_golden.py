@@ -11,6 +11,8 @@ oracle/Makefile).  Run in the authoring container only; the outputs are committe
   * chain_vectors.npz / sketch vectors: anchor sets with the reference's mp_chain() output
   * opt_<name>.ref.paf: reference PAF for golden.OPTION_CASES (one genome, index and seeding / chaining options away from the
     defaults; the index flags go to the reference with the FASTA): `make_golden.py options` makes only these
+  * long_u.ref.paf: reference PAF for the long-protein case of tests/longprot.py (device refinement past the LDS k-mer map):
+    `make_golden.py long` makes only this
   * ref_layout.txt: sizes and offsets of the reference's records as its own headers declare them (tests/test_compat.py):
     `make_golden.py layout <reference source dir>` makes only this
 """
@@ -113,9 +115,25 @@ def make_option_cases():
             print(case["name"], len(out), "bytes", out.count(b"\n"), "lines,", sum(1 for l in out.split(b"\n") if l and l.split(b"\t")[5] != b"*"), "mapped")
 
 
+def make_long_case():
+    """tests/golden/long_u.ref.paf: the reference's output for tests/longprot.py's case"""
+    import longprot
+    c = longprot.case()
+    with tempfile.TemporaryDirectory() as tmp:
+        fa, faa = os.path.join(tmp, "g.fa"), os.path.join(tmp, "p.fa")
+        gen_synth.write_fasta_nt(fa, c["contigs"])
+        gen_synth.write_fasta_aa(faa, c["prots"], c["names"])
+        out = run_ref(longprot.FLAGS + [fa, faa])
+    open(golden.path("long_u.ref.paf"), "wb").write(out)
+    print("long_u", len(out), "bytes", out.count(b"\n"), "lines")
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "options":
         make_option_cases()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "long":
+        make_long_case()
         return
     if len(sys.argv) > 2 and sys.argv[1] == "layout":
         make_layout(sys.argv[2])
@@ -161,6 +179,7 @@ def main():
     make_gs32_vectors()
     make_penalty_vectors()
     make_option_cases()
+    make_long_case()
 
 
 if __name__ == "__main__":

@@ -39,6 +39,10 @@ def main():
     ap.add_argument("--sigma", type=float, default=1.5)
     ap.add_argument("--imax", type=int, default=50000)
     ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--long-frac", type=float, default=0.0, help="share of the proteins drawn at mean length --long-len (long proteins: the global-map class of the device refinement)")
+    ap.add_argument("--long-len", type=int, default=3000)
+    ap.add_argument("--ab", default="", metavar="NAME=A,B", help="interleaved passes with the environment variable NAME (a knob the library reads per call) set to A and to B "
+                    "('-' = unset): --passes pairs, seconds, residues/s and busy host cores (process CPU time / wall) of every pass; with --ref both legs are compared")
     ap.add_argument("--passes", type=int, default=2, help="timed passes over the whole protein set (best is reported)")
     ap.add_argument("--ref", action="store_true", help="also run oracle/_ref/miniprot on the same .mpi and compare bytes")
     ap.add_argument("--no-gpu", action="store_true", help="(debug) skip our mapper")
@@ -57,7 +61,8 @@ def main():
         t1 = t2 = time.time()
         contigs = None
     else:
-      contigs, prots, names = gen_synth.generate(int(a.genome_mb * 1e6), a.n_ctg, a.n_prot, a.seed, mu=a.mu, sigma=a.sigma, imin=a.imin, imax=a.imax, n_frac=a.n_frac, min_exons=a.min_exons, paralog_frac=a.paralog_frac)
+      contigs, prots, names = gen_synth.generate(int(a.genome_mb * 1e6), a.n_ctg, a.n_prot, a.seed, mu=a.mu, sigma=a.sigma, imin=a.imin, imax=a.imax, n_frac=a.n_frac, min_exons=a.min_exons, paralog_frac=a.paralog_frac,
+                                                   long_frac=a.long_frac, long_len=a.long_len)
       t1 = time.time()
       idx = mpa.Index.from_nt4(contigs, ["chr%d" % (i + 1) for i in range(a.n_ctg)])
       mpa._check(mpa.lib().mpa_idx_build_kmers(idx.h, max(8, thr)))
@@ -79,15 +84,36 @@ def main():
         ctx = mpa.Context(0)
         tu = time.time(); idx.to_device(ctx); print("index upload %.1fs" % (time.time() - tu), file=sys.stderr)
         best = 1e30
-        for p in range(a.passes):
+        ab_texts = {}
+        if a.ab:
+            knob, vals = a.ab.split("=")
+            mpa.map_batches(ctx, idx, mo, batches, thr)                       # warm-up: pools, pinned memory
+            for p in range(a.passes):
+                for v in vals.split(","):
+                    os.environ.pop(knob, None) if v == "-" else os.environ.__setitem__(knob, v)
+                    mpa.Context.stage_clocks(reset=True)
+                    tp, cp = time.time(), time.process_time()
+                    ab_texts[v] = b"".join(mpa.map_batches(ctx, idx, mo, batches, thr))
+                    dt, dc = time.time() - tp, time.process_time() - cp
+                    clk = mpa.Context.stage_clocks()
+                    print("AB    pair %d %s=%s: %.3f s -> %.2f M aligned residues/s, %.1f host cores busy, planning %.1f ms per mini-batch (md5 %s)" %
+                          (p, knob, v, dt, aligned_residues(ab_texts[v]) / dt / 1e6, dc / dt, clk["planning"][0] / max(clk["planning"][1], 1), hashlib.md5(ab_texts[v]).hexdigest()))
+            for v in vals.split(","):                                         # one more pass per leg with the library's timing notes on stderr
+                os.environ.pop(knob, None) if v == "-" else os.environ.__setitem__(knob, v)
+                print("==== timing notes, %s=%s" % (knob, v), file=sys.stderr, flush=True)
+                os.environ["MPA_TIMING"] = "1"
+                mpa.map_batches(ctx, idx, mo, batches, thr)
+                os.environ.pop("MPA_TIMING")
+            os.environ.pop(knob, None)
+        for p in range(0 if a.ab else a.passes):
             tp = time.time()
             texts = mpa.map_batches(ctx, idx, mo, batches, thr)
             dt = time.time() - tp
             best = min(best, dt)
             print("pass %d: %.3f s" % (p, dt), file=sys.stderr)
-        ours = b"".join(texts)
+        ours = b"".join(texts) if not a.ab else list(ab_texts.values())[-1]
         res = aligned_residues(ours)
-        print("OURS  %d proteins in %d mini-batches: %.3f s -> %.2f M aligned residues/s (%d residues; md5 %s)" %
+        if not a.ab: print("OURS  %d proteins in %d mini-batches: %.3f s -> %.2f M aligned residues/s (%d residues; md5 %s)" %
               (len(prots), len(batches), best, res / best / 1e6, res, hashlib.md5(ours).hexdigest()))
     if a.ref:
         os.makedirs(a.tmp, exist_ok=True)
@@ -111,6 +137,8 @@ def main():
               (ncpu, t_all, t_load, res / max(t_all - t_load, 1e-9) / 1e6, hashlib.md5(ref).hexdigest()))
         if ours is not None:
             print("BYTES IDENTICAL" if ours == ref else "OUTPUT DIFFERS (ours %d bytes, ref %d bytes)" % (len(ours), len(ref)))
+            for v, t in ab_texts.items():
+                print("AB    %s: %s" % (v, "BYTES IDENTICAL" if t == ref else "OUTPUT DIFFERS"))
         for f in (mpi, faa):
             os.remove(f)
 
