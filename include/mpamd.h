@@ -182,8 +182,10 @@ typedef struct {
 	                                              * (the union of the launches' intervals; the stream's rounds overlap) -- what one
 	                                              * persistent kernel's duration would be.  0 unless MPA_DP_POOL=1. */
 	/* checkpointed traceback (traceback calls of <= 128 columns and >= MPA_DP_LITE_MIN rows): calls and padded cells swept by the
-	 * packed sweep, and the blocks of 96 rows whose traceback words the walk recomputed */
+	 * packed sweep, and the blocks of 96 rows whose traceback words the walk recomputed (walk_blocks: of every checkpointed class) */
 	int64_t n_ckpt, cells_ckpt, walk_blocks;
+	/* ... the same for calls of 129..256 columns (MPA_DP_LITE_WIDE=1, four waves per pair of calls); not part of n_ckpt / cells_ckpt */
+	int64_t n_ckpt_wide, cells_ckpt_wide;
 } mpa_dp_stats_t;
 void mpa_dp_last_stats(const mpa_ctx_t *ctx, mpa_dp_stats_t *st);
 /* sums over every mpa_dp_run() of this context since the last reset */

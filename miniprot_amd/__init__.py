@@ -61,7 +61,8 @@ class DpStats(C.Structure):
                 ("ms_backtrack", C.c_double), ("ms_total", C.c_double), ("launches_ext", C.c_int32),
                 ("launches_glob", C.c_int32), ("cells_ext_round", C.c_int64), ("cells_glob_round", C.c_int64),
                 ("ms_round", C.c_double), ("launches_round", C.c_int32), ("pad_", C.c_int32), ("ms_round_union", C.c_double),
-                ("n_ckpt", C.c_int64), ("cells_ckpt", C.c_int64), ("walk_blocks", C.c_int64)]
+                ("n_ckpt", C.c_int64), ("cells_ckpt", C.c_int64), ("walk_blocks", C.c_int64),
+                ("n_ckpt_wide", C.c_int64), ("cells_ckpt_wide", C.c_int64)]
 
 
 def build(verbose=False):

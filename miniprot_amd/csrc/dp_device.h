@@ -59,18 +59,50 @@ struct ExtWave {
 	int64_t ck_off;
 };
 
-// Checkpointed traceback (round 6).  A traceback call of up to 64 columns and many rows is swept by the PACKED row sweep of the
-// extension kernel (two calls per lane, ~27 VALU instructions per call and row instead of ~105), which keeps, per cell, only the
+// Checkpointed traceback (round 6).  A traceback call of up to 256 columns and many rows is swept by a PACKED row sweep of the
+// extension kernels (two calls per lane, ~27 VALU instructions per call and row instead of ~105), which keeps, per cell, only the
 // four "extension" bits that the walk follows through deletion and intron runs (bits 5..8 of the reference's traceback word:
 // D, A, B, C carried rather than opened, nasw-sse.c:455-485), and the DP state at the top of every block of MPA_TB_BLOCK rows.
 // The walk (k_walk) follows those runs on the bits alone and recomputes the full traceback words of a block -- with the exact
 // traceback sweep (glob_narrow), restarted from the block's checkpoint -- only when it stands in a block in any other state.
+// Up to 128 columns (classes 8..11: one wave per 1..8 calls, ext_narrow<G, true>):
 //   bits:        one dword per lane and three rows at lite_off + ((i - 2) / 3) * 64 + lane: row i's nibble at bit 4 * (2 - (i - 2) % 3)
-//                of the call's half (call slot s of the wave: half s / (64/G), lanes (s % (64/G)) * G + column); nibble = D | A << 1 | B << 2 | C << 3
+//                of the call's half (call slot s of the wave: half s / (64/G), lanes (s % (64/G)) * G + column; class 11, one call of
+//                65..128 columns per wave: column c + 64 in the high half of lane c); nibble = D | A << 1 | B << 2 | C << 3
 //   checkpoints: block k >= 1 (first row 2 + k * MPA_TB_BLOCK) at ck_off + (k - 1) * 9 * 64: nine dwords per lane, packed like the
 //                sweep's registers: H of rows i-1, i-2, i-3; D of rows i-1, i-2, i-3; A; B; C
+// 129..256 columns (class 12: a group of four waves per PAIR of calls, lite_wide_body; call slot s = int16 half s of every lane, wave w
+// owns the columns [64 w, 64 w + 64)): the same words with the wave index added -- see the lite_wide_* functions below, which the
+// sweep, the walk and the executor's pool sizing all call.
 #define MPA_TB_BLOCK 96
 #define MPA_LITE_SLOT_SHIFT 8        /* DTask::flag bits 8..11: the call's slot in its wave */
+#define MPA_LITE_WIDE_WAVES 4        /* waves of a class-12 group: 256 columns */
+
+// ---- class 12: the one definition of where a group's extension bits and checkpoints lie (dword offsets from the group's lite_off / ck_off)
+// bits: one dword per lane, wave and three rows
+__host__ __device__ static inline int64_t lite_wide_bits_dwords(int32_t max_nl)       // reserved per group whose longest call has max_nl rows
+{
+	return ((int64_t)max_nl / 3 + 2) * (MPA_LITE_WIDE_WAVES * 64);
+}
+// (row 2 <= i, column 0 <= j < 256, call slot 0 / 1) -> dword offset; *shift = position of the cell's nibble in that dword
+__host__ __device__ static inline int64_t lite_wide_bit_at(int32_t i, int32_t j, int32_t slot, int32_t *shift)
+{
+	const uint32_t r = (uint32_t)(i - 2);
+	*shift = 16 * slot + 4 * (2 - (int32_t)(r % 3));
+	return (int64_t)(r / 3) * (MPA_LITE_WIDE_WAVES * 64) + j;                        // (j = 64 * wave + lane)
+}
+// checkpoints: nine dwords (64 apart) per lane and wave at the top of every block k >= 1, the four waves of a block one after the other
+__host__ __device__ static inline int64_t lite_wide_ckpt_dwords(int32_t max_nl)
+{
+	const int32_t nb = max_nl > 3 ? (max_nl - 3) / MPA_TB_BLOCK : 0;                 // blocks with a first row 2 + k * MPA_TB_BLOCK <= max_nl - 1, k >= 1
+	return (int64_t)nb * 9 * (MPA_LITE_WIDE_WAVES * 64);
+}
+// (block k >= 1, column, call slot) -> dword offset of the first of the nine values (value q at + 64 q); *shift = 16 * slot
+__host__ __device__ static inline int64_t lite_wide_ckpt_at(int32_t k, int32_t j, int32_t slot, int32_t *shift)
+{
+	*shift = 16 * slot;
+	return ((int64_t)(k - 1) * MPA_LITE_WIDE_WAVES + (j >> 6)) * (9 * 64) + (j & 63);
+}
 
 struct ExtOut { int32_t nt_len, aa_len, score, flags; };
 
@@ -96,7 +128,10 @@ enum DpUnitKind : int32_t {
 	U_GLOB_W2, U_GLOB_W4,               // two two-wave / one four-wave traceback group(s)
 	U_LITE16, U_LITE32, U_LITE64,       // up to four independent waves of the checkpointed traceback's packed sweep (ExtWave descriptors)
 	U_LITE128,                          // ... one call of 65..128 columns per wave (column c + 64 in the high half of lane c)
-	U_EXT128                            // up to four independent extension waves of one 65..128-column call each (same layout)
+	U_EXT128,                           // up to four independent extension waves of one 65..128-column call each (same layout)
+	U_LITE_W4,                          // one four-wave group of the checkpointed traceback's packed sweep for a pair of 129..256-column calls: swept by
+	                                    // k_lite_wide next to the round (k_dp_round and k_dp_worker do not take it); the kind names it in the MPA_DP_TOP listing
+	U_KIND_COUNT
 };
 struct DpUnit { int32_t kind, first, count, blk, n_blk, sgroup, xg_first, pad_; };
 

@@ -171,7 +171,8 @@ struct mpa_ctx_s {
 	mpa_dp_stats_t stats = {};
 	mpa_dp_stats_t total = {};
 	size_t tb_budget = (size_t)8 << 30;       // bytes of traceback matrix per k_glob launch
-	int lite_min = 384;                       // rows from which a traceback call of <= 128 columns is checkpointed (MPA_DP_LITE_MIN; 0: never)
+	int lite_min = 384;                       // rows from which a traceback call of <= 256 columns is checkpointed (MPA_DP_LITE_MIN; 0: never)
+	int lite_wide = 0;                        // ... 129..256 columns included (MPA_DP_LITE_WIDE; 0, the default until it has been measured: those keep the plain sweep)
 	std::vector<mpa_ctx_s*> siblings;         // extra contexts on the same device for concurrent sub-batches (owned)
 	SeedBufs seed;                            // buffers of the GPU seeding stage (seed_exec.hip)
 	hipEvent_t wait_ev = nullptr;             // blocking-sync event: a host thread that waits for the device SLEEPS (wait_stream)
@@ -450,6 +451,7 @@ mpa_ctx_t *mpa_ctx_create(int device)
 	}
 	if (const char *s = getenv("MPA_TB_BUDGET_MB")) ctx->tb_budget = (size_t)atoll(s) << 20;
 	if (const char *s = getenv("MPA_DP_LITE_MIN")) ctx->lite_min = atoi(s);
+	if (const char *s = getenv("MPA_DP_LITE_WIDE")) ctx->lite_wide = atoi(s) != 0;
 	return ctx;
 }
 
@@ -505,6 +507,7 @@ mpa_ctx_t *ctx_sibling(mpa_ctx_t *ctx, int k)
 		if (!sb) return nullptr;
 		sb->tb_budget = ctx->tb_budget;
 		sb->lite_min = ctx->lite_min;
+		sb->lite_wide = ctx->lite_wide;
 		sb->root = ctx;
 		ctx->siblings.push_back(sb);
 	}
@@ -563,6 +566,7 @@ void ctx_absorb_sibling_stats(mpa_ctx_t *ctx)
 		t.ms_prep += u.ms_prep, t.ms_ext += u.ms_ext, t.ms_glob += u.ms_glob, t.ms_backtrack += u.ms_backtrack, t.ms_total += u.ms_total;
 		t.launches_ext += u.launches_ext, t.launches_glob += u.launches_glob;
 		t.cells_ext_round += u.cells_ext_round, t.cells_glob_round += u.cells_glob_round, t.ms_round += u.ms_round, t.launches_round += u.launches_round;
+		t.n_ckpt_wide += u.n_ckpt_wide, t.cells_ckpt_wide += u.cells_ckpt_wide;
 		u = mpa_dp_stats_t();
 		ctx->handoff_retries += sb->handoff_retries, sb->handoff_retries = 0;
 	}
@@ -1725,6 +1729,7 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 	std::vector<DTask> T(n);
 	std::vector<int32_t> ext_ids, glob_ids;
 	int32_t max_nl_ext = 0;
+	const bool pool_on = dp_pool_enabled();
 	for (int64_t k = 0; k < n; ++k) {
 		const mpa_dp_task_t &x = in[k];
 		DTask &t = T[k];
@@ -1774,6 +1779,11 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 			// traceback sweep: the walk would recompute all of their rows anyway.  MPA_DP_LITE_MIN (rows; 0: never), read when the context
 			// is created.  The packed sweep is an int16 one: calls that may saturate stay on the plain sweep too.
 			if (ctx->lite_min > 0 && !wide_ge && !may_saturate && t.ncol <= 128 && x.nl >= ctx->lite_min && x.nl >= 3) t.pad_ += 8, t.pw = 16 << (t.pad_ - 8);   // (class 11: 65..128 columns, one call per wave)
+			// Class 12: 129..256 columns under the same predicate, a four-wave group per pair of calls (lite_wide_body, a launch of its
+			// own next to the round), with MPA_DP_LITE_WIDE=1.  The default, 0, keeps them on the plain sweep (no A/B has
+			// been measured yet); so does the worker pool (MPA_DP_POOL=1), whose workers do not know the class.
+			else if (ctx->lite_min > 0 && ctx->lite_wide && !pool_on && !wide_ge && !may_saturate && t.ncol > 128 && t.ncol <= 256 && x.nl >= ctx->lite_min && x.nl >= 3)
+				t.pad_ = 12, t.pw = 256;
 			glob_ids.push_back((int32_t)k);
 		}
 	}
@@ -1871,6 +1881,29 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 			lwave_cnt[cls] = (int)ewaves.size() - lwave_first[cls];
 		}
 	}
+	// ---- four-wave groups of the 129..256-column class (12: sorts behind class 11), two calls each; pools sized by the group's longest call
+	const int l12_first = (int)ewaves.size();
+	{
+		size_t p = n_reg_glob;
+		while (p < glob_ids.size() && T[glob_ids[p]].pad_ < 12) ++p;
+		while (p < glob_ids.size()) {
+			ExtWave w;
+			memset(&w, 0, sizeof(w));
+			for (int k = 0; k < 8; ++k) w.task[k] = -1;
+			w.rec_base = T[glob_ids[p]].rec_off;
+			const size_t p0 = p;
+			for (int k = 0; k < 2 && p < glob_ids.size(); ++k, ++p) {
+				w.task[k] = glob_ids[p];
+				w.max_nl = std::max(w.max_nl, T[glob_ids[p]].nl);
+				T[glob_ids[p]].flag |= k << MPA_LITE_SLOT_SHIFT;
+			}
+			w.lite_off = lite_total, lite_total += lite_wide_bits_dwords(w.max_nl);
+			w.ck_off = ck_total, ck_total += lite_wide_ckpt_dwords(w.max_nl);
+			for (size_t q2 = p0; q2 < p; ++q2) T[glob_ids[q2]].tb_off = w.lite_off, T[glob_ids[q2]].bnd_off = w.ck_off;
+			ewaves.push_back(w);
+		}
+	}
+	const int l12_cnt = (int)ewaves.size() - l12_first;
 	const size_t n_lite = glob_ids.size() - n_reg_glob;
 	// per-row keys of the wide extension kernels: [group][2 halves][key_stride]
 	int64_t key_stride = 0, n_wide_groups = 0;
@@ -2075,12 +2108,17 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 		std::stable_sort(cu.begin(), cu.end(), [](const Cost &x, const Cost &y) { return x.cost > y.cost; });   // (stable: the workgroups of a split group stay adjacent, in column order)
 		static const bool show_top = [] { const char *e = getenv("MPA_DP_TOP"); return e && atoi(e) != 0; }();
 		if (show_top) {                                       // (measurement) what bounds the round: the costliest units by kind
-			int64_t by_kind[16] = { 0 }, n_kind[16] = { 0 };
-			for (const Cost &c : cu) by_kind[c.u.kind & 15] += c.cost, ++n_kind[c.u.kind & 15];
-			fprintf(stderr, "[mpa-dp-top] units %zu; longest:", cu.size());
-			for (size_t k = 0; k < cu.size() && k < 6; ++k) fprintf(stderr, " kind %d %.1f ms;", cu[k].u.kind, cu[k].cost * 1e-6);
+			// (the four-wave groups of the 129..256-column checkpointed class run next to the round, in k_lite_wide: listed here by
+			// the same cost model, as kind U_LITE_W4, so that the longest unit of the traceback round is seen whichever kernel sweeps it)
+			std::vector<Cost> shown = cu;
+			for (int k = 0; k < l12_cnt; ++k) shown.push_back(Cost{ (int64_t)ewaves[l12_first + k].max_nl * 280, DpUnit{ U_LITE_W4, l12_first + k, 1, 0, 1, 0, 0, 0 } });
+			std::stable_sort(shown.begin(), shown.end(), [](const Cost &x, const Cost &y) { return x.cost > y.cost; });
+			int64_t by_kind[U_KIND_COUNT] = { 0 }, n_kind[U_KIND_COUNT] = { 0 };
+			for (const Cost &c : shown) by_kind[c.u.kind] += c.cost, ++n_kind[c.u.kind];
+			fprintf(stderr, "[mpa-dp-top] units %zu; longest:", shown.size());
+			for (size_t k = 0; k < shown.size() && k < 6; ++k) fprintf(stderr, " kind %d %.1f ms;", shown[k].u.kind, shown[k].cost * 1e-6);
 			fprintf(stderr, " | wave-ms by kind:");
-			for (int k = 0; k < 16; ++k) if (n_kind[k]) fprintf(stderr, " %d: %ld units %.0f ms;", k, (long)n_kind[k], by_kind[k] * 1e-6);
+			for (int k = 0; k < U_KIND_COUNT; ++k) if (n_kind[k]) fprintf(stderr, " %d: %ld units %.0f ms;", k, (long)n_kind[k], by_kind[k] * 1e-6);
 			fprintf(stderr, "\n");
 		}
 		// worker pool: the units that take a whole workgroup first (queue 0), then the one-wave units (queue 1), each longest first;
@@ -2230,6 +2268,18 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 		ctx->stats.launches_ext++;
 	}
 
+	// the packed sweep of the 129..256-column checkpointed class (unit kind U_LITE_W4): a 256-thread launch of its own next to the
+	// round, on a side stream (at most two are taken at this point, by the launches above); the walk below waits for it
+	int l12_side = -1;
+	if (l12_cnt > 0) {
+		ea.waves = ctx->waves.as<ExtWave>();
+		hipStream_t st = begin_side(false);
+		hipLaunchKernelGGL(k_lite_wide, dim3((unsigned)l12_cnt), dim3(MPA_LITE_WIDE_WAVES * 64), 0, st, ea, l12_first);
+		HIP_TRY(hipGetLastError());
+		end_side(), l12_side = launches.back().side;
+		ctx->stats.launches_glob++;
+	}
+
 	// ---- K2 + traceback walk
 	float ms_glob = 0, ms_bt = 0;
 	bool glob_timed = false;
@@ -2337,12 +2387,16 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 		HIP_TRY(hipMemsetAsync(wk.n_blocks, 0, 8, s));
 		// (the list is sorted by class: one launch per class, with the LDS that class's block of direction words needs)
 		size_t at = 0;
-		for (int cls = 0; cls < 4; ++cls) {
+		for (int cls = 0; cls < 5; ++cls) {
 			size_t n_c = 0;
 			while (at + n_c < n_lite && T[glob_ids[n_reg_glob + at + n_c]].pad_ == 8 + cls) ++n_c;
 			if (n_c == 0) continue;
 			wk.list = ctx->wlist.as<int32_t>() + at, wk.n_list = (int32_t)n_c;
-			hipLaunchKernelGGL(k_walk, dim3((unsigned)n_c), dim3(64), cls == 0 ? WALK_LDS(16) : cls == 1 ? WALK_LDS(32) : cls == 2 ? WALK_LDS(64) : WALK_LDS(128), s, wk);
+			if (cls == 4) {                                                    // 129..256 columns: behind their own sweep; more LDS than a launch gets unasked
+				if (l12_side >= 0) (void)hipStreamWaitEvent(s, ctx->lev[2 * l12_side + 1], 0);
+				HIP_TRY(ensure_dynamic_lds((const void*)k_walk, ctx->device, WALK_LDS(256)));
+			}
+			hipLaunchKernelGGL(k_walk, dim3((unsigned)n_c), dim3(64), cls == 0 ? WALK_LDS(16) : cls == 1 ? WALK_LDS(32) : cls == 2 ? WALK_LDS(64) : cls == 3 ? WALK_LDS(128) : WALK_LDS(256), s, wk);
 			at += n_c;
 		}
 		HIP_TRY(hipGetLastError());
@@ -2383,6 +2437,7 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 		float ms = 0;
 		(void)hipEventElapsedTime(&ms, ctx->lev[2 * l.side], ctx->lev[2 * l.side + 1]);
 		if (l.is_ext) ms_ext_sum += ms;
+		else if (l.side == l12_side) ms_glob += ms;                      // (the 129..256-column packed sweep: a traceback sweep like the chunks')
 	}
 
 	// a boundary hand-off that never arrived (bounded spin in the kernel): the producer workgroup was running (it drew its
@@ -2452,7 +2507,7 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 		// (the first traceback chunk rides in the round's launch, except the 512/1024-thread classes)
 		if (round_launched && ((!rounds.empty() && gi < rounds[0].last && t.pad_ != 5 && t.pad_ != 6) || gi >= n_reg_glob)) st.cells_glob_round += cells;
 		st.n_glob++, st.cells_glob += cells;
-		if (gi >= n_reg_glob) st.n_ckpt++, st.cells_ckpt += cells;
+		if (gi >= n_reg_glob) { if (t.pad_ == 12) st.n_ckpt_wide++, st.cells_ckpt_wide += cells; else st.n_ckpt++, st.cells_ckpt += cells; }
 		st.alg_bytes_glob += (t.nl + 1) / 2 + t.al + 12 + 2 * cells + 2 * ((int64_t)t.nl + t.al) + 4 * (int64_t)nc[id];
 	}
 	st.rows_prep = rec_total;
@@ -2470,6 +2525,7 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 		t.n_ext += st.n_ext, t.n_glob += st.n_glob, t.cells_ext += st.cells_ext, t.cells_glob += st.cells_glob, t.rows_prep += st.rows_prep;
 		t.alg_bytes_ext += st.alg_bytes_ext, t.alg_bytes_glob += st.alg_bytes_glob;
 		t.n_ckpt += st.n_ckpt, t.cells_ckpt += st.cells_ckpt, t.walk_blocks += st.walk_blocks;
+		t.n_ckpt_wide += st.n_ckpt_wide, t.cells_ckpt_wide += st.cells_ckpt_wide;
 		t.ms_prep += st.ms_prep, t.ms_ext += st.ms_ext, t.ms_glob += st.ms_glob, t.ms_backtrack += st.ms_backtrack, t.ms_total += st.ms_total;
 		t.launches_ext += st.launches_ext, t.launches_glob += st.launches_glob;
 		t.cells_ext_round += st.cells_ext_round, t.cells_glob_round += st.cells_glob_round, t.ms_round += st.ms_round, t.launches_round += st.launches_round;

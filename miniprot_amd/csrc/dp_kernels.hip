@@ -1626,6 +1626,270 @@ __device__ __forceinline__ void ext_wide_body(const ExtWideArgs &a, const int gr
 
 
 // ------------------------------------------------------------------------------------------------
+// The packed sweep of the checkpointed traceback for calls of 129..256 columns (class 12, dp_device.h): one workgroup of four
+// waves per PAIR of calls (the two int16 halves), one column per lane, wave w three rows behind wave w - 1 and the hand-over of
+// {scan carry, H of the wave's last column} through lane 0 and the LDS exchange slots, one barrier per step of three rows --
+// ext_wide_body<4, false> without the per-row keys and the x-drop replay (a global alignment sweeps every row), with the rows
+// of ext_narrow<G, true>: the four differences whose signs are the extension bits, the three-row nibble word and the checkpoints.
+// The two calls may differ in rows: the group iterates max_nl, a call past its end only produces bits and checkpoints nobody
+// reads; its score H(nl - 1, al - 1) is taken from the wave and lane that own column al - 1 behind the step that holds row nl - 1.
+// ------------------------------------------------------------------------------------------------
+#define LITE_WIDE_LDS ((size_t)MPA_LITE_WIDE_WAVES * 2 * 64 * PROF_COL_STRIDE + (EXT_WIDE_RING + 1) * 16 + 256 + 32 + (64 * 8 + 32))   /* bytes per group; a multiple of 16 */
+#define MPA_ROW_TAIL_WL(Hr2, Hs2, Dr2, Hs3, M3, CX, CH) \
+	asm volatile( \
+		"v_pk_max_i16 %[x], %[x], %[cx]\n\t" \
+		MPA_SCAN4_L \
+		"v_mov_b32 %[t2], 0x80008000\n\t" \
+		"v_mov_b32 %[ke], %[cx]\n\t" \
+		"v_mov_b32_dpp %[t2], %[x] row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
+		"v_pk_max_i16 %[x], %[x], %[t2]\n\t" \
+		"v_mov_b32 %[t2], 0x80008000\n\t" \
+		"v_mov_b32 %[hs3], %[ch]\n\t" \
+		"v_mov_b32_dpp %[t2], %[x] row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" \
+		"v_pk_max_i16 %[x], %[x], %[t2]\n\t" \
+		"s_nop 1\n\t" \
+		"v_mov_b32_dpp %[ke], %[x] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
+		"v_pk_sub_i16 %[t2], %[ke], %[gojge] clamp\n\t" \
+		"v_pk_max_i16 %[h], %[h], %[t2]\n\t" \
+		"s_nop 1\n\t" \
+		"v_mov_b32_dpp %[hs3], %[h] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
+		"v_pk_max_i16 %[m3], %[h], %[hs3]" \
+		: [x] "+v"(x), [h] "+v"(h), [k0] "+v"(k0), [k1] "+v"(k1), [k2] "+v"(k2), [k3] "+v"(k3), [ke] "+v"(ke), [hs3] "+v"(Hs3), \
+		  [t2] "=&v"(tA_), [hDn] "=&v"(hDn), [a0] "=&v"(a0), [a1] "=&v"(a1), [m3] "=&v"(M3), [drn] "=&v"(drn), [dDn] "=&v"(dDn) \
+		: [hr2] "v"(Hr2), [dr2] "v"(Dr2), [gei] "v"(rnext.z), [s0] "v"(sraw0), [s1] "v"(sraw1), [hs2] "v"(Hs2), [pb0] "v"(pb0), [pb1] "v"(pb1), [aw] "v"(rnn.w), \
+		  [gojge] "v"(gojge), [cx] "v"(CX), [ch] "v"(CH), [go] "s"(goP), [sel] "s"(sel_lo))
+__device__ __forceinline__ void lite_wide_body(const ExtArgs &a, const int group_idx, const WavePos wp)
+{
+	constexpr int NW = MPA_LITE_WIDE_WAVES, RING = EXT_WIDE_RING;
+	// per wave: profile of its 64 columns for both halves [2][64 columns][23] int16; then the record ring, the exchange slots
+	// [2 step parities][NW waves][3 rows] of {scan, H of the wave's last column}, 32 bytes of -inf and the dump area
+	char *lds_prof = wp.lds;
+	uint4 *ring = (uint4*)(lds_prof + NW * 2 * 64 * PROF_COL_STRIDE);  // [RING + 1] decoded records of both halves
+	uint2 *xch = (uint2*)(ring + RING + 1);                          // [2][16] slots: parity * 16 + 3 w + k
+	uint2 *xneg = xch + 32;                                          // [4] {-inf, -inf}
+	uint2 *xdump = xneg + 4;                                         // [64 + 4]
+	const int lane = wp.lane, w = wp.w;                              // w: wave index inside the group, scalar
+	const ExtWave *wvp = &a.waves[group_idx];
+	const DpConst c = a.c;
+	const uint32_t *recbase = a.rec + wvp->rec_base;
+
+	int32_t tid[2], end_row[2], al[2];
+	uint32_t roff[2];
+#pragma unroll
+	for (int h = 0; h < 2; ++h) {
+		tid[h] = __builtin_amdgcn_readfirstlane(wvp->task[h]);
+		if (tid[h] >= 0) {
+			const DTask *t = &a.tasks[tid[h]];
+			end_row[h] = __builtin_amdgcn_readfirstlane(t->nl) - 1, al[h] = t->al, roff[h] = (uint32_t)(t->rec_off - wvp->rec_base);
+		} else end_row[h] = -1, al[h] = 1, roff[h] = 0;
+	}
+	// profile columns of this wave: global [22][pw] int16 -> LDS [column][amino acid]
+	for (int h = 0; h < 2; ++h) {
+		char *dst = lds_prof + (size_t)(w * 2 + h) * 64 * PROF_COL_STRIDE;
+		if (tid[h] < 0) {   // (an empty half scores zero everywhere; nobody reads what it produces)
+			for (int k = lane; k < 64 * PROF_COL_STRIDE / 2; k += 64) ((uint16_t*)dst)[k] = 0;
+			continue;
+		}
+		const DTask *t = &a.tasks[tid[h]];
+		const int16_t *src = a.prof + t->prof_off;
+		for (int k = lane; k < 22 * 64; k += 64) {
+			const int aidx = k >> 6, cc = k & 63, gcc = w * 64 + cc;
+			*(int16_t*)(dst + cc * PROF_COL_STRIDE + aidx * PROF_AA_STRIDE) = gcc < t->pw ? src[aidx * t->pw + gcc] : (int16_t)NEG16;
+		}
+	}
+	if (wp.tg < 36) xch[wp.tg] = make_uint2(NEGP, NEGP);           // the exchange slots and, behind them, the slots of -inf
+	// record ring, filled by the leading wave (ext_wide_body's scheme): row r in slot (r + 44) % 48
+	const bool loader = w == 0 && lane < 12;
+	uint2 pf = make_uint2(0, 0);
+	if (w == 0 && lane < 16) {
+		const uint4 e = ring_entry(recbase[roff[0] + lane], recbase[roff[1] + lane]);
+		ring[lane < 4 ? lane + 44 : lane - 4] = e;
+		if (lane == 4) ring[RING] = e;
+	}
+	if (loader) pf = make_uint2(recbase[roff[0] + 16 + lane], recbase[roff[1] + 16 + lane]);
+	__syncthreads();
+
+	const int gc = w * 64 + lane;
+	const uint32_t jge = splat16(gc * c.ge), gojge = splat16(c.go + gc * c.ge);
+	const uint32_t goP = __builtin_amdgcn_readfirstlane(splat16(c.go)), fsP = __builtin_amdgcn_readfirstlane(splat16(c.fs));
+	const uint32_t ioP = pack16(tid[0] >= 0 ? a.tasks[tid[0]].io : 0, tid[1] >= 0 ? a.tasks[tid[1]].io : 0);
+	const uint32_t sel_lo = __builtin_amdgcn_readfirstlane(0x05040100u);
+	const uint32_t nb1 = __builtin_amdgcn_readfirstlane(0x00010001u), nb2 = __builtin_amdgcn_readfirstlane(0x00020002u),
+	               nb4 = __builtin_amdgcn_readfirstlane(0x00040004u), nb8 = __builtin_amdgcn_readfirstlane(0x00080008u);
+	// absolute LDS addresses: this lane's two profile columns; the exchange slot it reads / writes in a step of parity 0
+	const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)wp.lds;
+	const uint32_t pb0 = lds0 + (uint32_t)(((w * 2 + 0) * 64 + lane) * PROF_COL_STRIDE), pb1 = pb0 + 64 * PROF_COL_STRIDE;
+	const uint32_t xch0 = lds0 + (uint32_t)((char*)xch - wp.lds), xneg0 = lds0 + (uint32_t)((char*)xneg - wp.lds), xdump0 = lds0 + (uint32_t)((char*)xdump - wp.lds);
+	const uint32_t xwr_even = lane == 63 ? xch0 + (uint32_t)(3 * w) * 8 : xdump0 + (uint32_t)lane * 8;
+	const uint32_t xwr_flip = lane == 63 ? 128u : 0u;              // (the other parity's slots: + 16 slots)
+	const bool takes_left = lane == 0 && w > 0;
+
+	uint32_t Hr[3], Hs[3], Dr[3], dn[3], ac[3], M[3], A = NEGP, B = NEGP, C = NEGP;
+#pragma unroll
+	for (int k = 0; k < 3; ++k) Hr[k] = Hs[k] = Dr[k] = M[k] = NEGP;
+	uint32_t k0 = NEGP, k1 = NEGP, k2 = NEGP, k3 = NEGP, ke = NEGP;    // fill registers of the asm rows' scan: only ever written by DPP moves
+	if (gc == 0) Hs[2] = 0u, Hs[1] = splat16(-c.fs), Hs[0] = splat16(-c.fs);
+	{
+		const uint4 q0 = ring[44], q1 = ring[45];
+		dn[1] = q0.x, dn[0] = q1.x, ac[1] = q0.y, ac[0] = q1.y, dn[2] = ac[2] = 0;
+	}
+	const int32_t max_nl = __builtin_amdgcn_readfirstlane(wvp->max_nl);
+	uint4 rcur = ring[46], rnext = ring[47];                           // records of rows i and i + 1
+	uint32_t S = prof2s(pb0 + (rcur.w & 0xffff), pb1 + (rcur.w >> 16));   // profile scores of row i (generic rows)
+	bool have_hD = false;                                              // hD already holds row i's max(diagonal, D) (behind the asm rows)
+	uint32_t hD = NEGP;
+	// the three-row accumulator of nibbles, the difference that holds row i's D bit, the D state the precomputation for row i replaced
+	// (what a checkpoint wants), this wave's slice of the group's bit words and checkpoints (dp_device.h)
+	uint32_t acc = 0, dDc = 0, Dold = NEGP;
+	int32_t sh_;
+	uint32_t *lite_p = a.lite + wvp->lite_off + lite_wide_bit_at(2, gc, 0, &sh_);
+	const int64_t lite_step = lite_wide_bit_at(5, gc, 0, &sh_) - lite_wide_bit_at(2, gc, 0, &sh_);
+	auto checkpoint = [&](const int32_t i, const uint32_t d3) {        // top of row i = 2 + k * MPA_TB_BLOCK: slots 0, 1, 2 hold rows i-1, i-2, i-3
+		uint32_t *p = a.ckpt + wvp->ck_off + lite_wide_ckpt_at((i - 2) / MPA_TB_BLOCK, gc, 0, &sh_);
+		p[0] = Hr[0], p[64] = Hr[1], p[128] = Hr[2], p[192] = Dr[0], p[256] = Dr[1], p[320] = d3, p[384] = A, p[448] = B, p[512] = C;
+	};
+	// the score of a call whose last row is among the rows [i, i + 3) just swept: h0, h1, h2 = their H rows (slots 2, 1, 0; passed by
+	// value: a choice among the elements of Hr[] by a run-time index would move the array out of the registers)
+	auto scores = [&](const int32_t i, const uint32_t h0, const uint32_t h1, const uint32_t h2) {
+#pragma unroll
+		for (int h = 0; h < 2; ++h) {
+			const int32_t k = end_row[h] - i;
+			uint32_t v = h2;
+			v = k == 1 ? h1 : v, v = k == 0 ? h0 : v;
+			if (tid[h] >= 0 && (uint32_t)k < 3u && gc == al[h] - 1) a.score[tid[h]] = half16(v, h);
+		}
+	};
+	auto refill = [&](const int32_t i, const int rs) {                 // the leading wave, every twelfth row
+		if (loader) {
+			const uint4 e = ring_entry(pf.x, pf.y);
+			const int at = (rs + 12) % RING + lane;
+			ring[at] = e;
+			if (at == 0) ring[RING] = e;                                       // slot 0 again behind slot 47
+			pf = make_uint2(recbase[roff[0] + (uint32_t)i + 26 + lane], recbase[roff[1] + (uint32_t)i + 26 + lane]);
+		}
+	};
+	v2u cv[3];
+	uint32_t xwr = 0;
+	auto step_begin = [&](const int par) {                             // what the wave to the left produced for the step's three rows, in the previous step
+		uint32_t at = xneg0;
+		if (takes_left) at = xch0 + (uint32_t)(((par ^ 1) * 16 + 3 * (w - 1)) * 8);
+#pragma unroll
+		for (int k = 0; k < 3; ++k) cv[k] = *(lds_u2p)(uintptr_t)(at + 8 * k);
+		xwr = xwr_even + (par ? xwr_flip : 0u);
+	};
+	// the generic row (plain C++): the first twelve rows and what the blocks of asm rows leave over
+	auto row = [&](auto kc, const int32_t i, const int rs) {
+		constexpr int K = decltype(kc)::value;
+		constexpr int R1 = (3 - K) % 3, R2 = (4 - K) % 3, R3 = (5 - K) % 3;
+		if (K == 0 && i > 2 && (uint32_t)(i - 2) % MPA_TB_BLOCK == 0) checkpoint(i, have_hD ? Dold : Dr[R3]);
+		const uint32_t Snext = prof2s(pb0 + (rnext.w & 0xffff), pb1 + (rnext.w >> 16));
+		const uint4 rnn = ring[rs + K];                                    // record of row i + 2
+		dn[R3] = rcur.x, ac[R3] = rcur.y;                                  // donor[i+1], acceptor[i]
+		uint32_t h, t, u, dA, dB, dC;
+		if (have_hD) h = hD;
+		else {
+			h = p_adds(Hs[R3], S);
+			u = p_subs(Hr[R3], goP); dDc = p_subs(u, Dr[R3]); t = p_max(u, Dr[R3]);
+			t = p_subs(t, rcur.z); Dr[R3] = t; h = p_max(h, t);
+		}
+		u = p_subs(Hr[R1], ioP); t = p_subs(u, dn[R2]); dA = p_subs(t, A);
+		t = p_max(t, A); A = t; h = p_max(h, p_subs(t, ac[R3]));
+		u = p_subs(Hs[R1], ioP); t = p_subs(u, dn[R1]); dB = p_subs(t, B);
+		t = p_max(t, B); B = t; h = p_max(h, p_subs(t, ac[R2]));
+		t = p_subs(u, dn[R3]); dC = p_subs(t, C);
+		t = p_max(t, C); C = t; h = p_max(h, p_subs(t, ac[R1]));
+		{
+			const uint32_t nib = (dDc >> 15 & 0x00010001u) | (dA >> 14 & 0x00020002u) | (dB >> 13 & 0x00040004u) | (dC >> 12 & 0x00080008u);
+			acc = K == 0 ? nib : (acc << 4 | nib);
+			if (K == 2) *lite_p = acc, lite_p += lite_step;
+		}
+		t = p_max(p_max(Hr[R1], Hr[R2]), p_max(Hs[R1], Hs[R2]));
+		h = p_max(h, p_subs(t, fsP));
+		const uint32_t y = scan_max_pk<64>(p_max(p_adds(h, jge), cv[K].x));   // (the incoming carry through lane 0)
+		const uint32_t ex = shift1<64>(y, cv[K].x, lane);
+		h = p_max(h, p_subs(ex, gojge));
+		Hr[R3] = h, Hs[R3] = shift1<64>(h, cv[K].y, lane);
+		*(lds_u2p)(uintptr_t)(xwr + 8 * K) = v2u{ y, h };
+		if (i == 2 && gc == 0) Hs[R1] = NEGP, Hs[R2] = NEGP;
+		S = Snext;
+		rcur = rnext, rnext = rnn, have_hD = false;
+	};
+
+	// Wave w runs 3 w rows behind wave 0: one barrier per step of three rows, w barriers of delay first and NW-1-w at the end so
+	// that every wave passes the same number.  Step parity = (step + w) & 1.
+	for (int k = 0; k < w; ++k) lds_barrier();
+	{
+		int par = w & 1;
+		int32_t i = 2;
+		int rs = 0, rs12 = 0;                                              // (i - 2) % 48, % 12 at the top of a step
+		auto generic_step = [&](const int n_rows) {
+			if (w == 0 && rs12 == 0) refill(i, rs);
+			step_begin(par);
+			row(std::integral_constant<int, 0>(), i, rs);
+			if (n_rows > 1) row(std::integral_constant<int, 1>(), i + 1, rs);
+			if (n_rows > 2) row(std::integral_constant<int, 2>(), i + 2, rs);
+			if (n_rows < 3) *lite_p = acc << (4 * (3 - n_rows));               // (the sweep ends inside a word)
+			if ((uint32_t)(end_row[0] - i) < 3u || (uint32_t)(end_row[1] - i) < 3u) scores(i, Hr[2], Hr[1], Hr[0]);
+			lds_barrier();
+			i += 3, par ^= 1, rs = rs == RING - 3 ? 0 : rs + 3, rs12 = rs12 == 9 ? 0 : rs12 + 3;
+		};
+		while (i < 14 && i + 3 <= max_nl) generic_step(3);
+		// ---- the asm rows, in blocks of four steps (i = 2 + 12 k: the record ring is refilled and checkpoints are written at block starts only)
+		if (i + 12 <= max_nl) {
+			uint32_t tA_, tB_, tC_, h, x, hDn, a0, a1, dA, dB, dC, drn, dDn;
+			v2s sraw0, sraw1;                                              // (.x = a profile score; .y is never set: v_perm_b32 takes the low halves)
+			M[0] = p_max(Hr[0], Hs[0]), M[1] = p_max(Hr[1], Hs[1]);
+			{                                                              // row i's diagonal term and D state (slot R3 = 2)
+				const uint32_t u = p_subs(Hr[2], goP), t = p_max(u, Dr[2]);
+				dDc = p_subs(u, Dr[2]), Dold = Dr[2];
+				Dr[2] = p_subs(t, rcur.z);
+				hD = p_max(p_adds(Hs[2], S), Dr[2]);
+			}
+			sraw0.x = *(lds_s16p)(uintptr_t)(pb0 + (rnext.w & 0xffff)), sraw1.x = *(lds_s16p)(uintptr_t)(pb1 + (rnext.w >> 16));
+			uint4 rnn = ring[rs];                                          // record of row i + 2; from here on fetched a row before it is needed
+			do {
+				if (w == 0) refill(i, rs);
+				if ((uint32_t)(i - 2) % MPA_TB_BLOCK == 0) checkpoint(i, Dold);
+				const uint4 *rb = ring + rs;
+#pragma unroll 1
+				for (int st = 0; st < 4; ++st, rb += 3) {
+					step_begin(par);
+#define MPA_LW_ROW(K, R1, R2, R3, NIB) { \
+					MPA_ROW_HEAD_L(Hr[R1], Hs[R1], dn[R1], dn[R2], rcur.x, ac[R1], ac[R2], rcur.y, M[R1], M[R2]); \
+					dn[R3] = rcur.x, ac[R3] = rcur.y; \
+					MPA_ROW_TAIL_WL(Hr[R2], Hs[R2], Dr[R2], Hs[R3], M[R3], cv[K].x, cv[K].y); \
+					MPA_NIBBLE(NIB); \
+					Dold = Dr[R2], Dr[R2] = drn, dDc = dDn; \
+					if (K == 2) *lite_p = acc, lite_p += lite_step; \
+					{ v2s f0, f1; f0.x = *(lds_s16p)(uintptr_t)a0, f1.x = *(lds_s16p)(uintptr_t)a1; sraw0 = f0, sraw1 = f1; } \
+					rcur = rnext, rnext = rnn, rnn = rb[K + 1]; \
+					Hr[R3] = h, hD = hDn; \
+					*(lds_u2p)(uintptr_t)(xwr + 8 * K) = v2u{ x, h }; }
+					MPA_LW_ROW(0, 0, 1, 2, MPA_NIB_FIRST)
+					MPA_LW_ROW(1, 2, 0, 1, MPA_NIB_NEXT)
+					MPA_LW_ROW(2, 1, 2, 0, MPA_NIB_NEXT)
+#undef MPA_LW_ROW
+					if ((uint32_t)(end_row[0] - i) < 3u || (uint32_t)(end_row[1] - i) < 3u) scores(i, Hr[2], Hr[1], Hr[0]);
+					lds_barrier();
+					i += 3, par ^= 1;
+				}
+				rs = rs == RING - 12 ? 0 : rs + 12;
+			} while (i + 12 <= max_nl);
+			have_hD = true;
+		}
+		while (i + 3 <= max_nl) generic_step(3);
+		if (i < max_nl) generic_step(max_nl - i);
+	}
+	for (int k = w; k < NW - 1; ++k) lds_barrier();
+}
+// (a launch of its own on a side stream of the round, like the 512/1024-thread traceback classes: k_dp_round stays what it is)
+__global__ __launch_bounds__(MPA_LITE_WIDE_WAVES * 64) void k_lite_wide(ExtArgs a, int first_group)
+{
+	__shared__ __attribute__((aligned(16))) char lds[LITE_WIDE_LDS];
+	lite_wide_body(a, first_group + (int)blockIdx.x, whole_block(lds));
+}
+
+// ------------------------------------------------------------------------------------------------
 // K2: global alignment with traceback.  int32 arithmetic, one column per lane, one call per group of
 // G lanes; matrices wider than 64 columns are swept in column blocks (block-major), each block leaving
 // a 16-byte boundary record per row for its right neighbour.
@@ -1710,15 +1974,20 @@ __device__ __forceinline__ int32_t glob_cands(GlobState &s, const uint32_t rcur,
 // One block of rows of a call swept again from a checkpoint of the packed sweep (the checkpointed traceback, dp_device.h; k_walk):
 // the sweep's row 2 is the call's row row_off + 2, the state comes from the checkpoint (nullptr: the call's first block, standard
 // start), the traceback words go to tb[(row - 2) * ncol + column] in LDS.  One call, in lane group 0.
+template<int NCB>                  // 64-column blocks the call may span: 1, 2 (65..128 columns) or 4 (129..256), so that a narrow walk carries one pair only
 struct GlobResume {
 	int32_t row_off, n_rows;
-	const uint32_t *ck;
-	int32_t ck_lane0, half;      // (block-major sweep of a 65..128-column call: lanes from 0, the column block is the half)
+	// where the checkpoint of each 64-column block of the call lies: the first of its nine dwords for the block's first column
+	// (nullptr: the call's first block of rows, standard start) and the position of the call's int16 half in those dwords.  One
+	// block for the classes of up to 64 columns; the two halves of the same lanes for a 65..128-column call; the four waves of a
+	// 129..256-column group (dp_device.h).
+	const uint32_t *ck[NCB];
+	int32_t sh[NCB];
 	uint16_t *tb;
 	int4 *bnd;                   // block-major sweep: the boundary records of the block's rows, [n_rows + 2]
 };
-template<int G, bool MB, bool EXT = false, bool WIDE = false>
-__device__ __forceinline__ void glob_narrow(const GlobArgs &a, const GlobWave &wv, const WavePos wp, const GlobResume *rz = nullptr)
+template<int G, bool MB, bool EXT = false, bool WIDE = false, int NCB = 1>
+__device__ __forceinline__ void glob_narrow(const GlobArgs &a, const GlobWave &wv, const WavePos wp, const GlobResume<NCB> *rz = nullptr)
 {
 	constexpr int NG = 64 / G;
 	int16_t *lds_prof = (int16_t*)wp.lds;            // [NG][22][G] for the current column block
@@ -1769,19 +2038,26 @@ __device__ __forceinline__ void glob_narrow(const GlobArgs &a, const GlobWave &w
 		const bool first_blk = !MB || blk == 0, last_blk = !MB || blk == nblk - 1;
 
 		GlobState gs;
-		glob_state_init(gs, ring[0], ring[1], first_blk && col == 0 && !(rz && rz->ck), fs);
-		if (rz && rz->ck) {
+		glob_state_init(gs, ring[0], ring[1], first_blk && col == 0 && !(rz && rz->ck[0]), fs);
+		if (rz && rz->ck[0]) {
 			// the packed sweep's registers at the top of this row: H and D of rows i-1, i-2, i-3 (this sweep's slots 1, 0, 2), A, B, C;
 			// H shifted by one column follows (column -1 is -inf behind row 2)
-			const uint32_t *p = rz->ck + rz->ck_lane0 + (gc < ncol ? col : 0);
-			const int sh = (MB ? blk : rz->half) * 16;
+			const int cb = MB ? blk : 0, lb = cb > 0 ? cb - 1 : 0;          // this column block's checkpoint and the one to its left
+			const uint32_t *p = rz->ck[0], *pl = rz->ck[0];
+			int sh = rz->sh[0], shl = rz->sh[0];
+#pragma unroll
+			for (int k = 1; k < NCB; ++k) {                                 // (constant indices: the pairs stay in registers)
+				if (cb == k) p = rz->ck[k], sh = rz->sh[k];
+				if (lb == k) pl = rz->ck[k], shl = rz->sh[k];
+			}
+			p += gc < ncol ? col : 0;
 			auto half_splat = [&](const uint32_t x) { return spl((int32_t)(x >> sh)); };
 			gs.H[1] = half_splat(p[0]), gs.H[0] = half_splat(p[64]), gs.H[2] = half_splat(p[128]);
 			gs.D[1] = half_splat(p[192]), gs.D[0] = half_splat(p[256]), gs.D[2] = half_splat(p[320]);
 			gs.A = half_splat(p[384]), gs.B = half_splat(p[448]), gs.C = half_splat(p[512]);
 			if (!live) { for (int k = 0; k < 3; ++k) gs.H[k] = gs.D[k] = NEGP; gs.A = gs.B = gs.C = NEGP; }
-			// (block-major: the left neighbour of a later block's first column is the last column of the block before, lane 63's lower half)
-			for (int k = 0; k < 3; ++k) gs.Hs[k] = shift1<G>(gs.H[k], MB && blk > 0 ? spl((int32_t)(rz->ck[(k == 0 ? 64 : k == 1 ? 0 : 128) + 63] >> ((blk - 1) * 16))) : NEGP, lane);
+			// (block-major: the left neighbour of a later block's first column is the last column of the block before: lane 63 of its checkpoint)
+			for (int k = 0; k < 3; ++k) gs.Hs[k] = shift1<G>(gs.H[k], MB && blk > 0 ? spl((int32_t)(pl[(k == 0 ? 64 : k == 1 ? 0 : 128) + 63] >> shl)) : NEGP, lane);
 		}
 		const uint32_t go_s = splat16(go), io_s = splat16(io), fs_s = splat16(fs), ge_s = splat16(ge);
 		const char *profb = (const char*)myprof;                // + byte0(record) * G = this lane's score for the row's amino acid
@@ -2443,38 +2719,54 @@ struct WalkArgs {
 	int32_t *n_cigar;
 	unsigned long long *n_blocks; // (statistics) blocks recomputed
 };
-// (per class of the packed sweep -- 16 / 32 / 64 / 128 columns at most: 8 / 11 / 17 / 29 KB; one launch per class, so that the narrow calls'
-// walks, most of them, take LDS for their own block of direction words and not for a 128-column one)
+// (per class of the packed sweep -- 16 / 32 / 64 / 128 / 256 columns at most: 8 / 11 / 17 / 29 / 53 KB; one launch per class, so that the narrow
+// calls' walks, most of them, take LDS for their own block of direction words and not for a 256-column one)
 #define WALK_LDS(NC) (GLOB_NARROW_LDS + (size_t)MPA_TB_BLOCK * (NC) * 2 + (size_t)(MPA_TB_BLOCK + 2) * 16)
 // DUAL: a call of 65..128 columns, swept with column c + 64 in the high half of lane c (ext_narrow<64, true, true>) and recomputed
 // by the block-major traceback sweep (two blocks of 64 columns, boundary records in LDS)
-template<int G, bool DUAL = false>
+// WIDE4: a call of 129..256 columns, swept by a four-wave group (lite_wide_body; the call is int16 half `slot` of every lane) and
+// recomputed by the same block-major sweep over up to four blocks of 64 columns, each from the checkpoint of the wave that swept it
+template<int G, bool DUAL = false, bool WIDE4 = false>
 __device__ __forceinline__ void walk_call(const WalkArgs &wa, const DTask &t, const int32_t tid, char *lds, const int lane)
 {
+	static_assert(!(DUAL || WIDE4) || G == 64, "the block-major classes are swept in blocks of 64 columns");
 	constexpr int NG = 64 / G;
-	const int slot = DUAL ? 0 : (t.flag >> MPA_LITE_SLOT_SHIFT) & 15, half = slot / NG, lane0 = (slot % NG) * G;
+	const int slot = DUAL ? 0 : (t.flag >> MPA_LITE_SLOT_SHIFT) & 15, half = WIDE4 ? slot : slot / NG, lane0 = WIDE4 ? 0 : (slot % NG) * G;
 	const uint32_t *lite = wa.lite + t.tb_off + lane0;
 	uint16_t *tbs = (uint16_t*)(lds + GLOB_NARROW_LDS);            // [MPA_TB_BLOCK][ncol] words of the block that is materialised
-	int4 *bnds = (int4*)(lds + GLOB_NARROW_LDS + (size_t)MPA_TB_BLOCK * (DUAL ? 128 : G) * 2);
+	int4 *bnds = (int4*)(lds + GLOB_NARROW_LDS + (size_t)MPA_TB_BLOCK * (WIDE4 ? 256 : DUAL ? 128 : G) * 2);
 	uint32_t *cig = wa.cig + t.cig_off;
 	const int32_t ncol = t.ncol, cap = t.cig_cap;
 	int32_t blk = -1, blk_lo = 0, blk_hi = 0;                      // the materialised block and its rows [blk_lo, blk_hi)
 	auto ensure = [&](const int32_t row) {
 		if (blk >= 0 && row >= blk_lo && row < blk_hi) return;
 		const int32_t b = (row - 2) / MPA_TB_BLOCK;
-		GlobResume rz;
+		constexpr int NCB = WIDE4 ? 4 : DUAL ? 2 : 1;
+		GlobResume<NCB> rz;
 		rz.row_off = b * MPA_TB_BLOCK, rz.n_rows = t.nl - 2 - rz.row_off < MPA_TB_BLOCK ? t.nl - 2 - rz.row_off : MPA_TB_BLOCK;
-		rz.ck = b ? wa.ckpt + t.bnd_off + (int64_t)(b - 1) * 9 * 64 : nullptr, rz.ck_lane0 = lane0, rz.half = half, rz.tb = tbs, rz.bnd = bnds;
+#pragma unroll
+		for (int cb = 0; cb < NCB; ++cb) {
+			rz.ck[cb] = nullptr, rz.sh[cb] = 0;
+			if (b == 0) continue;
+			if (WIDE4) rz.ck[cb] = wa.ckpt + t.bnd_off + lite_wide_ckpt_at(b, 64 * cb, half, &rz.sh[cb]);
+			else rz.ck[cb] = wa.ckpt + t.bnd_off + (int64_t)(b - 1) * 9 * 64 + lane0, rz.sh[cb] = 16 * (DUAL ? cb : half);
+		}
+		rz.tb = tbs, rz.bnd = bnds;
 		GlobWave gw;
 		gw.task[0] = tid, gw.task[1] = gw.task[2] = gw.task[3] = -1, gw.max_nl = rz.n_rows + 2;
 		wave_sync();
-		glob_narrow<G, DUAL, false, false>(wa.ga, gw, WavePos{ lds, lane, 0, lane }, &rz);
+		glob_narrow<G, DUAL || WIDE4, false, false, NCB>(wa.ga, gw, WavePos{ lds, lane, 0, lane }, &rz);
 		wave_sync();
 		blk = b, blk_lo = 2 + rz.row_off, blk_hi = blk_lo + rz.n_rows;
 		if (lane == 0) atomicAdd(wa.n_blocks, 1ULL);
 	};
 	auto full = [&](const int32_t ii, const int32_t jj) -> int32_t { return tbs[(ii - blk_lo) * ncol + jj]; };
 	auto nibble = [&](const int32_t ii, const int32_t jj) -> int32_t {
+		if (WIDE4) {
+			int32_t sh;
+			const int64_t at = lite_wide_bit_at(ii, jj, half, &sh);
+			return (int32_t)(lite[at] >> sh) & 0xf;
+		}
 		const uint32_t r = (uint32_t)(ii - 2);
 		return (int32_t)(lite[(int64_t)(r / 3) * 64 + (DUAL ? jj & 63 : jj)] >> (16 * (DUAL ? jj >> 6 : half) + 4 * (2 - r % 3))) & 0xf;
 	};
@@ -2552,7 +2844,9 @@ __global__ __launch_bounds__(64) void k_walk(WalkArgs wa)
 	case 8: walk_call<16>(wa, t, tid, (char*)lds_raw, lane); break;
 	case 9: walk_call<32>(wa, t, tid, (char*)lds_raw, lane); break;
 	case 10: walk_call<64>(wa, t, tid, (char*)lds_raw, lane); break;
-	default: walk_call<64, true>(wa, t, tid, (char*)lds_raw, lane); break;   // 11: 65..128 columns
+	case 11: walk_call<64, true>(wa, t, tid, (char*)lds_raw, lane); break;   // 65..128 columns, one call per wave
+	case 12: walk_call<64, false, true>(wa, t, tid, (char*)lds_raw, lane); break;   // 129..256 columns, a four-wave group per pair of calls
+	default: break;
 	}
 }
 

@@ -1,5 +1,5 @@
 """Randomised parity of mpa_dp_run() against the oracle: python tools/fuzz_dp.py [seconds] [first seed].  Every call class of the
-round kernel (asm extension rows, the 128-column one-call-per-wave classes, the checkpointed traceback at several row thresholds;
+round kernel (asm extension rows, the 128-column one-call-per-wave classes, the checkpointed traceback at several row thresholds, its 129..256-column class included;
 third argument "wide": the multi-wave extension classes of 129..1024 columns)."""
 import sys, os, time
 sys.path.insert(0, "tests"); sys.path.insert(0, ".")
@@ -9,11 +9,12 @@ from dputil import build_workload, oracle_eval, dpopt_from_params, compare
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
 wide = len(sys.argv) > 3 and sys.argv[3] == "wide"     # the multi-wave extension classes: 129..1024 columns, pairs of calls, split groups
+os.environ.setdefault("MPA_DP_LITE_WIDE", "1")            # the 129..256-column checkpointed class is off by default: the fuzz run covers it
 t0 = time.time()
 n_calls = n_bad = 0
 while time.time() - t0 < budget:
     rng = np.random.default_rng(seed)
-    os.environ["MPA_DP_LITE_MIN"] = str(int(rng.choice([3, 50, 100, 384, 384, 1000])))
+    os.environ["MPA_DP_LITE_MIN"] = os.environ.get("FUZZ_LITE_MIN") or str(int(rng.choice([3, 50, 100, 384, 384, 1000])))   # (FUZZ_LITE_MIN: one threshold for the whole run)
     fs = int(rng.choice([23, 23, 17, 10]))
     P = refbind.DpParams(refbind.mapping_matrix(fs), go=int(rng.choice([11, 11, 5, 13])), ge=int(rng.choice([1, 1, 2, 3])), io=int(rng.choice([29, 29, 40, 19])), fs=fs,
                          xdrop=int(rng.choice([100, 100, 30, 300])), end_bonus=int(rng.choice([5, 0, 11])), sp=tuple(rng.choice([0, 1], 1)) and ((8, 15, 21, 30, 0, 0) if rng.random() < 0.6 else (8, 15, 21, 30, 4, 4)),
@@ -32,7 +33,7 @@ while time.time() - t0 < budget:
     bad, msg = compare(rst, cig, oracle_eval(pairs, meta, P), meta, pairs)
     idx.close(); ctx.close()
     n_calls += len(tasks); n_bad += len(bad)
-    print("seed %d lite_min %s go %d ge %d io %d fs %d xdrop %d: %d calls (%d checkpointed, %d blocks recomputed), %d differ" % (seed, os.environ["MPA_DP_LITE_MIN"], P.go, P.ge, P.io, P.fs, P.xdrop, len(tasks), st["n_ckpt"], st["walk_blocks"], len(bad)), flush=True)
+    print("seed %d lite_min %s go %d ge %d io %d fs %d xdrop %d: %d calls (%d + %d wide checkpointed, %d blocks recomputed), %d differ" % (seed, os.environ["MPA_DP_LITE_MIN"], P.go, P.ge, P.io, P.fs, P.xdrop, len(tasks), st["n_ckpt"], st["n_ckpt_wide"], st["walk_blocks"], len(bad)), flush=True)
     if bad:
         print(msg[:2000])
     seed += 1

@@ -31,4 +31,4 @@ for it in range(3):
     tot = ctx.dp_stats(total=True, reset=True)
     if tot["ms_round"] > 0:                        # worker pool (default): the round is a k_dp_worker launch on the worker stream
         ms = tot["ms_round"]
-    print("al %d nl %d x %d flag %d%s: %.2f ms -> %.1f ns/row (backtrack %.2f ms)" % (al, nl, n, flag, " ANTIDIAG" if antidiag else "", ms, ms * 1e6 / nl, st["ms_backtrack"]))
+    print("al %d nl %d x %d flag %d%s: %.2f ms -> %.1f ns/row (backtrack %.2f ms; batch on the device %.2f ms; %d + %d checkpointed, %d blocks walked)" % (al, nl, n, flag, " ANTIDIAG" if antidiag else "", ms, ms * 1e6 / nl, st["ms_backtrack"], st["ms_total"], st["n_ckpt"], st["n_ckpt_wide"], st["walk_blocks"]))
