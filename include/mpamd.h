@@ -101,6 +101,17 @@ int mpa_idx_build_kmers(mpa_idx_t *mi, int n_threads);
 /* the same table built on the GPU (scan kernel + one radix sort of all k-mer keys): same ki/kb, and kb stays resident for the
  * seeding kernels.  MPA_ERR_UNSUPPORTED when the parameters or the genome do not fit the device path (build on the host then). */
 int mpa_idx_build_kmers_device(mpa_ctx_t *ctx, mpa_idx_t *mi);
+/* When the keys of the genome (44 bytes each while they are sorted) exceed the build's budget -- 7/8 of the free device memory less
+ * the two bucket tables, capped by MPA_IDX_BUILD_MB (megabytes, read on every call) -- the device build runs in PASSES over
+ * contiguous ranges of buckets, planned from a histogram of the keys over the top min(bucket bits, 12) bits of the bucket: same
+ * ki/kb, byte for byte.  It declines (MPA_ERR_UNSUPPORTED) only when a single bin of that histogram exceeds the budget.
+ * What the last device build on this context did: n_pass (1 and hist_bits = max_bin_keys = 0 when no histogram was taken; 0 when
+ * the plan failed), keys before de-duplication in all, in the fullest pass and in the fullest bin, and the budget in force. */
+typedef struct {
+	int32_t n_pass, hist_bits;
+	int64_t n_keys, max_pass_keys, max_bin_keys, budget_bytes;
+} mpa_idx_build_stats_t;
+void mpa_idx_build_last_stats(const mpa_ctx_t *ctx, mpa_idx_build_stats_t *st);
 /* genome-only index of a FASTA file with the given parameters (mp_ntseq_read, ntseq.c:29-75); build the table with either of the above */
 mpa_idx_t *mpa_idx_read_fasta(const char *fasta_fn, const mpa_idxopt_t *io);
 int mpa_idx_dump(const char *fn, const mpa_idx_t *mi);          /* mp_idx_dump, index.c:189: byte-identical file */
@@ -347,6 +358,16 @@ int64_t mpa_dbg_main_chains(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapop
  * max_occ [n_seq], *out (mpa_free).  Returns how many queries the device handed to the host, or a negative error code. */
 int64_t mpa_dbg_seed_jobs(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads, int64_t *off, int32_t *max_occ,
                           int32_t **out);
+/* (tests) an exact budget in bytes for the keys of the device index build on this context; 0 restores the default */
+void mpa_dbg_idx_build_budget(mpa_ctx_t *ctx, int64_t bytes);
+/* the pass planner of the device index build, host only: hist[n_bins] keys per bin, at most budget_keys keys per pass.  Greedy over
+ * ascending bins (a new pass starts where the next bin would take the pass over the budget), which gives the fewest contiguous
+ * passes.  Pass p covers the bins [first_bin[p], first_bin[p + 1]); first_bin has room for n_bins + 1 entries.  Returns the number
+ * of passes, or -1 when a bin alone exceeds the budget (or an argument is out of range). */
+int32_t mpa_dbg_idx_plan_passes(const int64_t *hist, int32_t n_bins, int64_t budget_keys, int32_t *first_bin);
+/* the histogram the last multi-pass build on this context planned from: copies min(cap, bins) counts, returns the number of bins
+ * (0 after a one-pass build) */
+int32_t mpa_dbg_idx_build_hist(const mpa_ctx_t *ctx, int64_t *hist, int32_t cap);
 /* cnt[i] = entries of bucket[i] in the index's k-mer table (what the occurrence cut-off is computed from).  Host only. */
 int mpa_idx_bucket_counts(const mpa_idx_t *mi, int64_t n, const uint32_t *bucket, int64_t *cnt);
 

@@ -65,6 +65,11 @@ class DpStats(C.Structure):
                 ("n_ckpt_wide", C.c_int64), ("cells_ckpt_wide", C.c_int64)]
 
 
+class IdxBuildStats(C.Structure):
+    _fields_ = [("n_pass", C.c_int32), ("hist_bits", C.c_int32), ("n_keys", C.c_int64), ("max_pass_keys", C.c_int64),
+                ("max_bin_keys", C.c_int64), ("budget_bytes", C.c_int64)]
+
+
 def build(verbose=False):
     """Compile libmpamd.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
     r = subprocess.run(["make", "-C", os.path.join(_HERE, "csrc"), "-j4"], capture_output=not verbose, text=True)
@@ -94,6 +99,15 @@ def lib():
         L.mpa_idx_dump.argtypes = [C.c_char_p, C.c_void_p]
         L.mpa_idx_build_kmers.argtypes = [C.c_void_p, C.c_int]
         L.mpa_idx_build_kmers_device.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "mpa_idx_build_last_stats"):                    # (absent from older builds loaded through MPA_LIB_PATH)
+            L.mpa_idx_build_last_stats.argtypes = [C.c_void_p, C.POINTER(IdxBuildStats)]
+            L.mpa_idx_build_last_stats.restype = None
+            L.mpa_dbg_idx_build_budget.argtypes = [C.c_void_p, C.c_int64]
+            L.mpa_dbg_idx_build_budget.restype = None
+            L.mpa_dbg_idx_plan_passes.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]
+            L.mpa_dbg_idx_plan_passes.restype = C.c_int32
+            L.mpa_dbg_idx_build_hist.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+            L.mpa_dbg_idx_build_hist.restype = C.c_int32
         L.mpa_idx_read_fasta.restype = C.c_void_p
         L.mpa_idx_read_fasta.argtypes = [C.c_char_p, C.c_void_p]
         L.mpa_idx_destroy.argtypes = [C.c_void_p]
@@ -191,6 +205,25 @@ class Context:
         else:
             lib().mpa_dp_last_stats(self.h, C.byref(st))
         return {k: getattr(st, k) for k, _ in DpStats._fields_}
+
+    def idx_build_stats(self):
+        """what the last device index build on this context did (mpa_idx_build_last_stats): passes, histogram bits, keys in all /
+        in the fullest pass / in the fullest bin, and the budget in bytes"""
+        st = IdxBuildStats()
+        lib().mpa_idx_build_last_stats(self.h, C.byref(st))
+        return {k: int(getattr(st, k)) for k, _ in IdxBuildStats._fields_}
+
+    def idx_build_budget(self, nbytes):
+        """(tests) an exact budget in bytes for the keys of the device index build; 0 restores the default"""
+        lib().mpa_dbg_idx_build_budget(self.h, int(nbytes))
+
+    def idx_build_hist(self):
+        """the key histogram the last multi-pass index build planned from (int64 array; empty after a one-pass build)"""
+        n = lib().mpa_dbg_idx_build_hist(self.h, None, 0)
+        hist = np.zeros(n, dtype=np.int64)
+        if n:
+            lib().mpa_dbg_idx_build_hist(self.h, hist.ctypes.data, n)
+        return hist
 
     def handoff_retries(self):
         """DP rounds repeated because a workgroup hand-off of a split extension call timed out (mpa_dp_handoff_retries)."""
@@ -342,6 +375,16 @@ class Queries:
         self.off = np.zeros(len(self.seqs) + 1, dtype=np.int64)
         np.cumsum([len(s) for s in self.seqs], out=self.off[1:])
         self.c = QBatch(len(self.seqs), self.buf, self.off.ctypes.data_as(C.POINTER(C.c_int64)))
+
+
+def idx_plan_passes(hist, budget_keys):
+    """The pass planner of the device index build (mpa_dbg_idx_plan_passes; no device needed): hist = keys per bin, at most
+    budget_keys keys per pass.  Returns the list first_bin[0 .. n_pass] (pass p = bins [first_bin[p], first_bin[p + 1])), or -1
+    when a bin alone exceeds the budget."""
+    hist = np.ascontiguousarray(hist, dtype=np.int64)
+    first = np.zeros(len(hist) + 1, dtype=np.int32)
+    n = lib().mpa_dbg_idx_plan_passes(hist.ctypes.data, len(hist), int(budget_keys), first.ctypes.data)
+    return -1 if n < 0 else [int(x) for x in first[:n + 1]]
 
 
 def default_mapopt():

@@ -92,6 +92,25 @@ int64_t fetch_nt(const mpa_idx_s *mi, int32_t vid, int64_t st, int64_t en, uint8
 
 template<typename T> static bool rd(FILE *fp, T *dst, size_t n) { return fread(dst, sizeof(T), n, fp) == n; }
 
+// The bucket ranges of a multi-pass device build (dev_index_build): hist[b] keys in bin b, at most budget_keys keys per pass.
+// Greedy over ascending bins -- a pass is closed where the next bin would take it over the budget -- which gives the fewest
+// contiguous passes: any plan's first pass ends no later than the greedy one's, and so on by induction.  Empty bins ride with
+// the pass in front of them.  first_bin[0 .. n_pass]; -1: a bin alone exceeds the budget.
+int32_t idx_plan_passes(const int64_t *hist, int32_t n_bins, int64_t budget_keys, int32_t *first_bin)
+{
+	if (!hist || !first_bin || n_bins < 1 || budget_keys < 0) return -1;
+	int32_t n_pass = 0;
+	int64_t in_pass = 0;
+	first_bin[0] = 0;
+	for (int32_t b = 0; b < n_bins; ++b) {
+		if (hist[b] < 0 || hist[b] > budget_keys) return -1;
+		if (hist[b] > budget_keys - in_pass) first_bin[++n_pass] = b, in_pass = 0;
+		in_pass += hist[b];
+	}
+	first_bin[++n_pass] = n_bins;
+	return n_pass;
+}
+
 } // namespace mpa
 
 using namespace mpa;
@@ -293,6 +312,11 @@ static int mpa_idx_build_kmers_impl(mpa_idx_t *mi, int n_threads)
 int mpa_idx_build_kmers(mpa_idx_t *mi, int n_threads)
 {
 	return mpa::guarded<int>(MPA_ERR_HIP, [&] { return mpa_idx_build_kmers_impl(mi, n_threads); });
+}
+
+int32_t mpa_dbg_idx_plan_passes(const int64_t *hist, int32_t n_bins, int64_t budget_keys, int32_t *first_bin)
+{
+	return idx_plan_passes(hist, n_bins, budget_keys, first_bin);
 }
 
 void mpa_idx_destroy(mpa_idx_t *mi)
