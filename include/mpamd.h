@@ -368,6 +368,18 @@ int32_t mpa_dbg_idx_plan_passes(const int64_t *hist, int32_t n_bins, int64_t bud
 /* the histogram the last multi-pass build on this context planned from: copies min(cap, bins) counts, returns the number of bins
  * (0 after a one-pass build) */
 int32_t mpa_dbg_idx_build_hist(const mpa_ctx_t *ctx, int64_t *hist, int32_t cap);
+/* the planner of a DP round, host only (dp_plan.cpp; no context, no device): what mpa_dp_run() would upload and launch for the n calls of
+ * `tasks` on contigs of ctg_len[n_ctg] and queries at q_off[n_seq + 1], serialised into buf.  knobs[8] = lite_min, lite_wide, no_split,
+ * antidiag, pool, ext_dual, unit_prio, tb_budget (bytes): the values the executor takes from its context and the environment.
+ * Layout, all little-endian: an int64 header -- counts, pool totals, first/count of every wave class, bytes asked of every device pool,
+ * offsets of the staging and download sections, the statistics that follow from the plan (the fields are named in tests/dpplan.py) --
+ * then (offset, bytes) of each section, then the sections, 8-byte aligned, in upload order: DTask[n], PrepChunk[], ExtWave[], PenTable,
+ * the traceback chunks (int64 rows: first, last, tb_words, waves, first and count per class), their call lists and their GlobWave[]
+ * one chunk after the other, DpUnit[], the walk list, its calls per class, the huge calls' GlobWave[] and list.
+ * Returns the bytes the plan takes (written when buf holds cap >= that many), or the error code mpa_dp_run() would return
+ * (message via mpa_last_error). */
+int64_t mpa_dbg_dp_plan(const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, int32_t n_seq, const int64_t *q_off, int64_t n, const mpa_dp_task_t *tasks,
+                        const int64_t *knobs, void *buf, int64_t cap);
 /* cnt[i] = entries of bucket[i] in the index's k-mer table (what the occurrence cut-off is computed from).  Host only. */
 int mpa_idx_bucket_counts(const mpa_idx_t *mi, int64_t n, const uint32_t *bucket, int64_t *cnt);
 

@@ -387,6 +387,26 @@ def idx_plan_passes(hist, budget_keys):
     return -1 if n < 0 else [int(x) for x in first[:n + 1]]
 
 
+def dbg_dp_plan(dpopt, ctg_len, q_off, tasks, knobs):
+    """The plan of one mpa_dp_run() call (mpa_dbg_dp_plan; no device needed) for a task table: contig lengths, query offsets (n_seq + 1),
+    DP_TASK array, and the executor's knobs as a dict (lite_min, lite_wide, no_split, antidiag, pool, ext_dual, unit_prio, tb_budget).
+    Returns the serialised plan as bytes (layout: mpamd.h), or (code, message) when the planner refuses the table."""
+    tasks = np.ascontiguousarray(tasks, dtype=DP_TASK)
+    ctg_len = np.ascontiguousarray(ctg_len, dtype=np.int64)
+    q_off = np.ascontiguousarray(q_off, dtype=np.int64)
+    kn = np.array([knobs[k] for k in ("lite_min", "lite_wide", "no_split", "antidiag", "pool", "ext_dual", "unit_prio", "tb_budget")], dtype=np.int64)
+    f = lib().mpa_dbg_dp_plan
+    f.restype = C.c_int64
+    f.argtypes = [C.POINTER(DpOpt), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    args = (C.byref(dpopt), len(ctg_len), ctg_len.ctypes.data, len(q_off) - 1, q_off.ctypes.data, len(tasks), tasks.ctypes.data, kn.ctypes.data)
+    need = f(*args, None, 0)
+    if need < 0:
+        return int(need), last_error()
+    buf = np.zeros(need, dtype=np.uint8)
+    assert f(*args, buf.ctypes.data, need) == need
+    return buf.tobytes()
+
+
 def default_mapopt():
     mo = MapOpt()
     lib().mpa_mapopt_init(C.byref(mo))

@@ -30,8 +30,28 @@ struct DTask {
 	int32_t pw;          // profile row width (columns, multiple of the lane-group width)
 	int32_t cig_cap;
 	int32_t out_idx;     // index into the caller's task array
-	int32_t pad_;
+	int32_t cls;         // DpClass: which sweep takes the call (set by the planner, dp_plan.cpp)
 };
+
+// The values of DTask::cls.  Extension calls and traceback calls are numbered separately (the two never share a list):
+// the number says how the call's columns are spread over lanes and waves.
+enum DpClass : int32_t {
+	// extension calls (score only)
+	X_16 = 0, X_32, X_64,        // 16 / 32 / 64 lanes per call, two calls per lane: 8 / 4 / 2 calls per wave
+	X_W2, X_W4,                  // a group of two / four waves per pair of calls: up to 128 / 256 columns
+	X_SPLIT2, X_SPLIT4,          // up to 512 / 1024 columns: two / four workgroups of four waves per pair of calls, boundaries handed over in HBM
+	X_HUGE,                      // the block-major one-wave int32 sweep (k_ext_huge): wider calls, and whatever the packed int16 sweeps may not take
+	X_128,                       // 65..128 columns, one call per wave (column c + 64 in the high half of lane c)
+	// traceback calls (CIGAR): the plain sweep that writes the traceback matrix ...
+	T_16 = 0, T_32, T_64,        // 4 / 2 / 1 call(s) per wave
+	T_W2, T_W4, T_W8, T_W16,     // one call per group of 2 / 4 / 8 / 16 waves: up to 128 / 256 / 512 / 1024 columns
+	T_MB,                        // block-major, one wave: more than 1024 columns
+	// ... and the checkpointed traceback (below): packed sweep + walk
+	T_LITE16 = 8, T_LITE32, T_LITE64,   // 8 / 4 / 2 calls per wave
+	T_LITE128,                   // 65..128 columns, one call per wave
+	T_LITE_W4                    // 129..256 columns, a four-wave group per pair of calls (k_lite_wide)
+};
+static inline bool is_checkpointed(int32_t tb_cls) { return tb_cls >= T_LITE16; }
 
 // Per-row record produced by the prep kernel, one uint32 per window row i:
 //   byte0 2*nas[i]      nas = amino acid (aa20 code) of the codon ending at row i, 21 when undefined; stored
@@ -47,6 +67,7 @@ __host__ __device__ static inline uint32_t make_rec(uint32_t nas, int32_t donor_
 
 // rows of one call that one workgroup of k_prep_rows turns into records (256 threads, four rows each)
 #define MPA_PREP_CHUNK_ROWS 1024
+struct PrepChunk { int32_t task; int32_t row0; };
 
 // A wave of the extension kernel works on up to 8 calls at once: lanes are split in 64/G groups of G
 // columns, and each 32-bit lane register carries two independent calls in its int16 halves.
@@ -133,7 +154,7 @@ enum DpUnitKind : int32_t {
 	                                    // k_lite_wide next to the round (k_dp_round and k_dp_worker do not take it); the kind names it in the MPA_DP_TOP listing
 	U_KIND_COUNT
 };
-struct DpUnit { int32_t kind, first, count, blk, n_blk, sgroup, xg_first, pad_; };
+struct DpUnit { int32_t kind, first, count, blk, n_blk, sgroup, xg_first, prio; };   // prio: issue priority 0..3 by expected duration (dp_plan.cpp, plan_units)
 
 // The device-resident unit queues of the DP worker pool (k_dp_worker, dp_kernels.hip): one slot per DP lane of the stream
 // pipeline (a batch in its DP round), all slots of a device in ONE block of device memory that every lane's workers see.

@@ -1,15 +1,18 @@
 // dp_exec.hip -- host-side executor of the batched spliced DP: the implementation of mpa_dp_run().
 //
-// A batch of ns_global_gs16b() calls (nasw.h:135; call sites align.c:73,288,293,322,327) is turned into
-//   1. one k_prep_rows / k_prep_prof launch (per-row records + query profiles, written once to HBM),
-//   2. one k_ext_narrow launch (16/32/64 lanes per call, up to 8 calls packed per wavefront) and one k_ext_wide<NW>
-//      launch per wide shape class for the score-only extension calls, calls sorted by window length so that
-//      co-resident calls finish together (k_ext_huge + k_ext_replay for calls wider than 1024 columns),
-//   3. k_glob_narrow / k_glob_wide<NW> launches for the calls that need a CIGAR, chunked by traceback memory, each
-//      followed by k_backtrack,
-// every launch on its own HIP stream of the context, bracketed by HIP events (mpa_dp_last_stats feeds bench.py's
-// roofline record).  The seeding-stage drivers (dev_prechain_forward, dev_refine_scan; kernels in seed_exec.hip) live
-// here too.  There is no CPU fallback here by design.
+// A batch of ns_global_gs16b() calls (nasw.h:135; call sites align.c:73,288,293,322,327) is planned on the host (dp_plan.cpp: classes,
+// order, pool layout, waves, traceback chunks, the round's unit list -- nothing of it needs the device) and then enqueued as
+//   1. one upload from a pinned staging block, k_prep_rows / k_prep_prof (per-row records + query profiles, written once to HBM),
+//   2. ONE k_dp_round launch for every DP unit of the round: the extension calls of every class up to 1024 columns, the packed
+//      sweeps of the checkpointed traceback and the plain traceback sweeps of the first traceback chunk, costliest unit first
+//      (MPA_DP_POOL=1: the units go to the resident workers of the device's pool, k_dp_worker, instead),
+//   3. next to it on side streams: k_ext_huge + k_ext_replay (wider calls, and whatever the int16 sweeps may not take), k_lite_wide
+//      (129..256-column checkpointed calls), the 512/1024-thread traceback classes, the anti-diagonal prototype,
+//   4. k_backtrack per traceback chunk (chunks after the first: stand-alone k_glob_* launches, serial), k_walk for the
+//      checkpointed calls, one download, one host wait, k_cigar_gather,
+// bracketed by HIP events (mpa_dp_last_stats feeds bench.py's roofline record).  mpa_dp_run_impl is that list of phases.  The
+// seeding-stage drivers (dev_prechain_forward, dev_refine_scan; kernels in seed_exec.hip) live here too.  There is no CPU
+// fallback here by design.
 #include <hip/hip_runtime.h>
 #include <time.h>
 #include <algorithm>
@@ -24,11 +27,9 @@
 #include "mpa_internal.h"
 #include "host_core.h"
 #include "dp_device.h"
+#include "dp_plan.h"
 #include "chain_core.h"
 #include "dp_kernels.hip"
-// (layout invariants of ext_wide_body, checked here so that the kernel source's md5 -- what profiles/*_pmc_summary.json is tied to -- stays put)
-static_assert(EXT_WIDE_LDS(2) % 16 == 0 && EXT_WIDE_LDS(4) % 16 == 0 && (2 * 64 * PROF_COL_STRIDE) % 16 == 0, "the groups of a workgroup and the record ring behind the profiles start on 16 bytes");
-static_assert(EXT_WIDE_RING % 12 == 0 && EXT_WIDE_XIN % 48 == 0 && EXT_WIDE_KROWS % 12 == 0 && EXT_WIDE_KROWS >= 64 + 12 + 12 + 3, "rings in whole 12-row blocks; the key ring holds a flush of 64 rows, a block, and the first wave's lead");
 #include "dp_antidiag.hip"
 #include "seed_exec.hip"
 #include "sketch_exec.hip"
@@ -338,35 +339,6 @@ void dev_free_index(mpa_idx_s *mi)
 	}
 }
 
-// ns_log2 (nasw-sse.c:330-338) and the extension-length penalty of nasw-sse.c:426 tabulated as a step
-// function.  Evaluated on the host with the same float operations as the reference (no FMA contraction),
-// so the kernel needs no floating point at all.
-static float log2_poly(float x)
-{
-	union { float f; uint32_t i; } z = { x };
-	float r = (float)((int32_t)((z.i >> 23) & 255) - 128);
-	z.i &= ~(255u << 23);
-	z.i += 127u << 23;
-	r += (-0.34484843f * z.f + 2.02466578f) * z.f - 0.67487759f;
-	return r;
-}
-
-static int build_pen_table(float coef, int32_t max_x, PenTable *pt)
-{
-	int32_t n = 0, cur = 0;
-	pt->x[n] = INT32_MIN, pt->val[n] = 0, ++n;
-	for (int32_t x = 2; x <= max_x; ++x) {
-		int32_t v = (int32_t)(coef * log2_poly((float)x) + .5f);
-		if (v != cur) {
-			if (n >= MPA_PEN_MAX - 1) return -1;
-			pt->x[n] = x, pt->val[n] = v, ++n, cur = v;
-		}
-	}
-	pt->n = n;
-	for (int32_t k = n; k < MPA_PEN_MAX; ++k) pt->x[k] = INT32_MAX, pt->val[k] = cur;
-	return 0;
-}
-
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device: remember it per (kernel, device), under a lock -- several
 // DP lanes and seeders get here at once, and a process may hold contexts on several devices
 static hipError_t ensure_dynamic_lds(const void *fn, int device, size_t bytes)
@@ -378,18 +350,6 @@ static hipError_t ensure_dynamic_lds(const void *fn, int device, size_t bytes)
 	const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 	if (e == hipSuccess) done.emplace_back(fn, device);
 	return e;
-}
-
-struct ExtClass { int G, NB; };
-// classes 0..2: k_ext_narrow, several calls per wave.  classes 3..6: k_ext_wide<NW>, NW waves per pair of calls.
-static const ExtClass kExtClasses[] = { {16, 1}, {32, 1}, {64, 1}, {64, 2}, {64, 4}, {64, 8}, {64, 16} };
-static const int kNumExtClasses = 7;
-
-static int ext_class_of(int32_t ncol)
-{
-	for (int k = 0; k < kNumExtClasses; ++k)
-		if (ncol <= kExtClasses[k].G * kExtClasses[k].NB) return k;
-	return -1;
 }
 
 template<int NW> static hipError_t launch_glob_wide(const GlobArgs &a, int n_groups, hipStream_t s, bool wide_ge = false)
@@ -404,13 +364,13 @@ template<int NW> static hipError_t launch_glob_wide(const GlobArgs &a, int n_gro
 
 extern "C" {
 
-// traceback classes 0,1,2 (16/32/64 lanes) and 7 (block-major, > 1024 columns) in one launch; a.waves = whole array
+// traceback classes T_16, T_32, T_64 (16/32/64 lanes) and T_MB (block-major, > 1024 columns) in one launch; a.waves = whole array
 // (the traceback chunks after the first, which do not ride in the round's launch)
 static hipError_t launch_glob_narrow(const GlobArgs &a, const int *first, const int *cnt, hipStream_t s, bool wide_ge = false)
 {
 	const size_t lds = (size_t)22 * 64 * 2 + (size_t)4 * 32 * 4;
 	NarrowMap m{};
-	const int cls[4] = { 0, 1, 2, 7 };
+	const int cls[4] = { T_16, T_32, T_64, T_MB };
 	int total = 0;
 	for (int k = 0; k < 4; ++k) m.first[k] = first[cls[k]], m.cnt[k] = cnt[cls[k]], total += cnt[cls[k]];
 	if (wide_ge) hipLaunchKernelGGL(k_glob_narrow<true>, dim3((unsigned)total), dim3(64), lds, s, a, m);
@@ -1769,10 +1729,6 @@ int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_a
 }
 } // namespace mpa
 
-extern "C" {
-
-} // extern "C" (reopened below)
-
 namespace mpa {
 // ---- DP worker pool: host side (the kernels and the protocol are in dp_kernels.hip, "The DP worker pool")
 // MPA_DP_POOL=1 selects the pool; the default is one k_dp_round launch per round.  Measured (profiles/r05_experiments.txt): with
@@ -1850,6 +1806,83 @@ void pool_harvest(mpa_ctx_t *ctx, bool wait)
 	(void)hipGetLastError();
 	ctx->wl_busy.resize(keep);
 }
+// A round for the pool: the round's arguments (ha: pinned) and units into the lane's slot of the device's pool, the slot armed in
+// stream order behind everything the round reads, the lane's workers launched (a worker takes any lane's units: their stream is
+// never waited for by a round -- a round is complete when its last unit says so in pinned memory).  The unit list is in
+// ctx->units already: whole-workgroup units [0, n_group), then the one-wave units.  *gen: what pool_wait_round waits for.
+static int pool_launch_round(mpa_ctx_t *ctx, hipStream_t s, const ExtArgs &ea, const ExtWideArgs &wa, const GlobArgs &ga, DpRoundArgs *ha,
+                             size_t n_units, size_t n_group, size_t round_lds, unsigned int *gen)
+{
+	int rc;
+	if ((rc = pool_attach(ctx))) return rc;
+	mpa_ctx_s *root = ctx->root ? ctx->root : ctx;
+	DpPool *pool = root->dp_pool;
+	int n_slots;
+	{ std::lock_guard<std::mutex> g(root->pool_mu); n_slots = root->pool_slots; }
+	ha->ea = ea, ha->wa = wa, ha->ga = ga, ha->units = ctx->units.as<DpUnit>(), ha->n_group = (int32_t)n_group, ha->pad_ = 0;
+	HIP_TRY(hipMemcpyAsync(&pool->args[ctx->dp_slot], ha, sizeof(DpRoundArgs), hipMemcpyHostToDevice, s));
+	long long *d_trace = nullptr;
+	if (dp_trace_path()) {
+		if ((rc = ctx->dp_trace.ensure(n_units * 16))) return rc;
+		HIP_TRY(hipMemsetAsync(ctx->dp_trace.p, 0, n_units * 16, s));
+		d_trace = ctx->dp_trace.as<long long>();
+	}
+	*gen = ++ctx->dp_gen;
+	hipLaunchKernelGGL(k_dp_arm, dim3(1), dim3(1), 0, s, pool, ctx->dp_slot, (int)n_group, (int)(n_units - n_group), *gen, ctx->dp_done, d_trace);
+	HIP_TRY(hipGetLastError());
+	// The workers go out on the lane's own stream (what follows the round on that stream then also waits for this launch's
+	// workers to run out of units of ANY lane; measured level with a stream of their own, 19.6 against 19.7 M residues/s).
+	// MPA_DP_WORKER_STREAM=1: a worker stream per lane -- one more stream per lane for HIP to deal hardware queues to, and
+	// when that stream lands on a queue another context's long kernels use, every round waits for them (the evidence run of
+	// round 5 measured 6.5 M residues/s that way: profiles/r05_experiments.txt).
+	static const bool own_stream = [] { const char *e = getenv("MPA_DP_WORKER_STREAM"); return e && atoi(e) != 0; }();
+	hipStream_t ws = own_stream ? ctx->worker_stream : s;
+	if (own_stream) {
+		HIP_TRY(hipEventRecord(ctx->arm_ev, s));
+		HIP_TRY(hipStreamWaitEvent(ws, ctx->arm_ev, 0));
+	}
+	mpa_ctx_s::WorkerLaunch wl;
+	if (!ctx->wl_free.empty()) wl = ctx->wl_free.back(), ctx->wl_free.pop_back();
+	else { HIP_TRY(hipEventCreate(&wl.e0)); HIP_TRY(hipEventCreate(&wl.e1)); }
+	HIP_TRY(ensure_dynamic_lds((const void*)k_dp_worker, ctx->device, round_lds));
+	static const int launch_cap = [] { const char *e = getenv("MPA_DP_LAUNCH_WORKERS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : dp_pool_budget(); }();
+	// a workgroup serves one workgroup unit at a time, or four one-wave units side by side
+	const unsigned grid = (unsigned)std::min<size_t>(n_group + (n_units - n_group + 3) / 4, (size_t)launch_cap);
+	HIP_TRY(hipEventRecord(wl.e0, ws));
+	hipLaunchKernelGGL(k_dp_worker, dim3(grid), dim3(256), round_lds, ws, pool, ctx->dp_slot, n_slots);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipEventRecord(wl.e1, ws));
+	ctx->wl_busy.push_back(wl);
+	return MPA_OK;
+}
+// the round is complete when the last of its units has stored the round's generation into the lane's pinned word
+static int pool_wait_round(mpa_ctx_t *ctx, hipStream_t s, unsigned int gen, const DpUnit *units, size_t n_units)
+{
+	volatile int32_t *d = ctx->dp_done;
+	const double t0 = now_ms();
+	for (int polls = 0; (unsigned int)*d != gen; ++polls) {
+		if (polls >= 8) { struct timespec ts = { 0, 100000L }; nanosleep(&ts, nullptr); }
+		if ((polls & 1023) == 1023) {
+			if (now_ms() - t0 > 120000.0) { set_error("DP worker pool: a round did not complete within two minutes"); return MPA_ERR_HIP; }
+			const hipError_t e = hipStreamQuery(s);                            // (a fault in a worker kernel shows up here, not in the word)
+			if (e != hipSuccess && e != hipErrorNotReady) { set_error(std::string("DP worker launch: ") + hipGetErrorString(e)); return MPA_ERR_HIP; }
+		}
+	}
+	hipLaunchKernelGGL(k_l2_writeback, dim3(128), dim3(64), 0, s);       // the units' results out of the L2s, before anything enqueued behind reads them
+	HIP_TRY(hipGetLastError());
+	if (const char *path = dp_trace_path()) {                             // (debug) one line per unit: who ran when
+		std::vector<long long> tr(2 * n_units);
+		HIP_TRY(hipMemcpy(tr.data(), ctx->dp_trace.p, n_units * 16, hipMemcpyDeviceToHost));
+		static std::mutex tmu;
+		std::lock_guard<std::mutex> g(tmu);
+		if (FILE *f = fopen(path, "a")) {
+			for (size_t k = 0; k < n_units; ++k)
+				fprintf(f, "%d\t%u\t%zu\t%d\t%d\t%lld\t%lld\n", ctx->dp_slot, gen, k, units[k].kind, units[k].prio, tr[2 * k], tr[2 * k + 1]);
+			fclose(f);
+		}
+	}
+	return MPA_OK;
+}
 // time during which at least one worker launch of the device was running
 static double pool_union_ms(mpa_ctx_s *root, bool reset)
 {
@@ -1881,6 +1914,495 @@ void mpa_dp_total_stats(mpa_ctx_t *ctx, mpa_dp_stats_t *st, int reset)
 }
 
 #define MPA_RETRY_NO_SPLIT (-100)   /* internal: repeat the round without split extension calls */
+
+// What the phases of one mpa_dp_run() call share: the plan, the staging blocks, the kernels' argument structs, which side streams
+// carry what, and the event times collected so far.
+struct DpRun {
+	mpa_ctx_t *ctx;
+	hipStream_t s;
+	DpPlan &plan;
+	DpPlanKnobs kn;
+	char *hup = nullptr, *hdn = nullptr;        // pinned staging: host -> device (plan.up), device -> host (plan.dn)
+	DpConst dc;
+	ExtArgs ea;
+	ExtWideArgs wa;
+	GlobArgs ga;
+	GlobWave *d_hw = nullptr;                   // the huge calls' waves and list, behind their keys
+	int32_t *d_hlist = nullptr;
+	struct Launch { int side; bool is_ext; };
+	std::vector<Launch> launches;               // side-stream launches so far (side = index of the stream and of its event pair)
+	int l12_side = -1;                          // ... the one of the T_LITE_W4 sweep
+	bool round_launched = false;
+	bool pool_pending = false;                  // (worker pool) a round is armed and not yet known to be complete ...
+	unsigned int pool_gen = 0;                  // ... its generation
+	int64_t pool_n = 0;                         // words of the dense CIGAR pool
+	float ms_glob = 0, ms_bt = 0;
+	bool glob_timed = false;                    // ev[3..5] hold a chunk's sweep and walk not yet added to ms_glob / ms_bt
+	double t_mark = 0;
+	void mark(const char *what) { const double t = now_ms(); timing_note(what, t - t_mark); t_mark = t; }   // (MPA_TIMING: wall clock between marks)
+	hipEvent_t ev_round(int k) const { return ctx->lev[2 * (mpa_ctx_s::kSide - 1) + k]; }                    // the last event pair times the round's launch
+	hipStream_t side_stream(int k) const { hipStream_t st = ctx->side[(k + ctx->side_off) % mpa_ctx_s::kSide]; return st ? st : s; }
+	void add_chunk_times() { float a = 0, b = 0; (void)hipEventElapsedTime(&a, ctx->ev[3], ctx->ev[4]); (void)hipEventElapsedTime(&b, ctx->ev[4], ctx->ev[5]); ms_glob += a, ms_bt += b; }
+};
+
+// fork: the next side stream (created when first used), waiting for fork_ev, its start event recorded
+static hipStream_t begin_side(DpRun &R, bool is_ext)
+{
+	mpa_ctx_t *ctx = R.ctx;
+	const int k = (int)R.launches.size();
+	// (side streams are created when first used: HIP deals hardware queues to streams in creation order, and sixteen idle side
+	// streams per context pushed the main streams of later contexts onto queues that other contexts' long kernels were using)
+	hipStream_t &slot = ctx->side[(k + ctx->side_off) % mpa_ctx_s::kSide];
+	if (!slot && hipStreamCreateWithFlags(&slot, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); slot = nullptr; }
+	hipStream_t st = R.side_stream(k);
+	(void)hipStreamWaitEvent(st, ctx->fork_ev, 0);
+	(void)hipEventRecord(ctx->lev[2 * k], st);
+	R.launches.push_back(DpRun::Launch{ k, is_ext });
+	return st;
+}
+static void end_side(DpRun &R) { const int k = R.launches.back().side; (void)hipEventRecord(R.ctx->lev[2 * k + 1], R.side_stream(k)); }
+
+// ---- 2. pools and staging at the sizes the plan asks for
+static int dp_size_pools(DpRun &R)
+{
+	mpa_ctx_t *ctx = R.ctx;
+	const DpPlan::Pools &z = R.plan.sz;
+	int rc;
+	if ((rc = ctx->tasks.ensure(z.tasks)) || (rc = ctx->chunks.ensure(z.chunks)) || (rc = ctx->qseq.ensure(z.qseq)) || (rc = ctx->rec.ensure(z.rec)) || (rc = ctx->prof.ensure(z.prof)) ||
+	    (rc = ctx->waves.ensure(z.waves)) || (rc = ctx->extout.ensure(z.extout)) || (rc = ctx->tb.ensure(z.tb)) || (rc = ctx->cig.ensure(z.cig)) || (rc = ctx->ncig.ensure(z.ncig)) ||
+	    (rc = ctx->lite.ensure(z.lite)) || (rc = ctx->ckpt.ensure(z.ckpt)) || (rc = ctx->wlist.ensure(z.wlist)) || (rc = ctx->score.ensure(z.score)) || (rc = ctx->rowkey.ensure(z.rowkey)) ||
+	    (rc = ctx->bnd.ensure(z.bnd)) || (rc = ctx->hkey.ensure(z.hkey)) || (rc = ctx->list.ensure(z.list)))
+		return rc;
+	// Everything the device needs from the host goes through ONE pinned staging buffer (plan.up), so that no copy is
+	// staged by the runtime and the host never waits for one: a DP round is enqueued in one go and waited for once.
+	if ((rc = ctx->h_up.ensure(R.plan.up.end + 256))) return rc;
+	R.hup = ctx->h_up.as<char>();
+	return MPA_OK;
+}
+
+// ---- 3. staging filled; uploads, memsets and the prep kernels enqueued
+static int dp_upload_and_prep(DpRun &R, const mpa_idx_t *mi, const mpa_dpopt_t *opt, const mpa_qbatch_t *q)
+{
+	mpa_ctx_t *ctx = R.ctx;
+	DpPlan &P = R.plan;
+	hipStream_t s = R.s;
+	char *hup = R.hup;
+	const size_t b_tasks = sizeof(DTask) * P.tasks.size(), b_chunks = sizeof(PrepChunk) * P.prep.size(), b_waves = sizeof(ExtWave) * P.ewaves.size();
+	memcpy(hup + P.up.tasks, P.tasks.data(), b_tasks);
+	memcpy(hup + P.up.chunks, P.prep.data(), b_chunks);
+	memcpy(hup + P.up.q, q->seqs + q->q_off[0], (size_t)P.q_bytes);
+	memcpy(hup + P.up.waves, P.ewaves.data(), b_waves);
+	R.mark("    dp: buffers");
+	HIP_TRY(hipMemcpyAsync(ctx->tasks.p, hup + P.up.tasks, b_tasks, hipMemcpyHostToDevice, s));
+	HIP_TRY(hipMemcpyAsync(ctx->chunks.p, hup + P.up.chunks, b_chunks, hipMemcpyHostToDevice, s));
+	HIP_TRY(hipMemcpyAsync(ctx->qseq.p, hup + P.up.q, P.q_bytes, hipMemcpyHostToDevice, s));
+	if (!P.ewaves.empty()) HIP_TRY(hipMemcpyAsync(ctx->waves.p, hup + P.up.waves, b_waves, hipMemcpyHostToDevice, s));
+	// (k_prep_rows writes every row of every call; only the padding the kernels prefetch behind the last call is cleared)
+	HIP_TRY(hipMemsetAsync((char*)ctx->rec.p + (size_t)(P.rec_total - P.rec_pad) * 4, 0, (size_t)P.rec_pad * 4, s));
+	if (P.n_wide_groups) HIP_TRY(hipMemsetAsync(ctx->rowkey.p, 0, (size_t)(P.n_wide_groups * 2 * P.key_stride * 4), s));
+	// split classes: boundary granules, then the per-group completion counters and the error flag; all zero before the launch (a granule's tag is row + 1)
+	if (P.n_split) {
+		int rc;
+		if ((rc = ctx->xg.ensure(P.sz.xg))) return rc;
+		HIP_TRY(hipMemsetAsync(ctx->xg.p, 0, P.xg_bytes + P.xg_tail, s));
+	}
+	// extension calls wider than 1024 columns: keys (zeroed), then one GlobWave and one list entry per call
+	if (!P.huge_ids.empty()) {
+		const size_t n_huge = P.huge_ids.size();
+		HIP_TRY(hipMemsetAsync(ctx->hkey.p, 0, (size_t)P.hkey_total * 8, s));
+		R.d_hw = (GlobWave*)((char*)ctx->hkey.p + (((size_t)P.hkey_total * 8 + 15) & ~(size_t)15));
+		R.d_hlist = (int32_t*)(R.d_hw + n_huge);
+		HIP_TRY(hipMemcpyAsync(R.d_hw, P.huge_waves.data(), sizeof(GlobWave) * n_huge, hipMemcpyHostToDevice, s));
+		HIP_TRY(hipMemcpyAsync(R.d_hlist, P.huge_ids.data(), 4 * n_huge, hipMemcpyHostToDevice, s));
+		HIP_TRY(wait_stream(ctx, s));                  // (pageable sources; the calls are rare)
+	}
+
+	DevTables tabs;
+	memcpy(tabs.aa20, tab_aa20(), 256);
+	memcpy(tabs.codon, tab_codon(), 64);
+	memcpy(tabs.mat, opt->mat, 484);
+	DpConst &dc = R.dc;
+	dc.go = opt->go, dc.ge = opt->ge, dc.fs = opt->fs, dc.xdrop = opt->xdrop, dc.end_bonus = opt->end_bonus;
+	for (int k = 0; k < 6; ++k) dc.sp[k] = opt->sp[k];
+	dc.sp_null_bonus = opt->sp_null_bonus;
+	dc.wide_ge = P.wide_ge ? 1 : 0;
+	DevGenome dg{ mi->dev[ctx->device]->seq, mi->dev[ctx->device]->ctg_off, mi->dev[ctx->device]->ctg_len, mi->dev[ctx->device]->spsc, mi->l_seq };
+
+	// per-row records and profiles
+	// (measured, round 4: putting these two on a high-priority stream of their own gives every DP lane a second active hardware
+	// queue, and with ten more queues in use the round kernels are time-sliced: 41 -> 72 ms per launch.  They stay in the lane's
+	// own queue; MPA_SHORT_KERNEL raises their wave priority instead.)
+	HIP_TRY(hipEventRecord(ctx->ev[0], s));
+	if (!P.prep.empty())
+		hipLaunchKernelGGL(k_prep_rows, dim3((unsigned)P.prep.size()), dim3(256), 0, s, dg, ctx->tasks.as<DTask>(), ctx->chunks.as<PrepChunk>(), ctx->rec.as<uint32_t>(), dc, tabs);
+	hipLaunchKernelGGL(k_prep_prof, dim3((unsigned)P.tasks.size()), dim3(256), 0, s, ctx->tasks.as<DTask>(), ctx->qseq.as<char>(), ctx->prof.as<int16_t>(), tabs);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipEventRecord(ctx->ev[1], s));
+	R.mark("    dp: uploads + prep enqueued");
+
+	// the kernels' arguments
+	ExtArgs &ea = R.ea;
+	ea.tasks = ctx->tasks.as<DTask>(), ea.rec = ctx->rec.as<uint32_t>(), ea.prof = ctx->prof.as<int16_t>(), ea.out = ctx->extout.as<ExtOut>();
+	ea.c = dc, ea.pen = P.pen;
+	ea.lite = ctx->lite.as<uint32_t>(), ea.ckpt = ctx->ckpt.as<uint32_t>(), ea.score = ctx->score.as<int32_t>();
+	ea.waves = ctx->waves.as<ExtWave>();
+	ExtWideArgs &wa = R.wa;
+	wa.tasks = ea.tasks, wa.rec = ea.rec, wa.prof = ea.prof, wa.out = ea.out, wa.c = dc, wa.pen = P.pen, wa.key_stride = P.key_stride;
+	wa.xg = P.n_split ? ctx->xg.as<unsigned long long>() : nullptr;
+	wa.done = P.n_split ? (int32_t*)((char*)ctx->xg.p + P.xg_bytes) : nullptr;
+	wa.ticket = P.n_split ? wa.done + P.n_split : nullptr;
+	wa.err = P.n_split ? wa.ticket + P.n_split : nullptr;
+	wa.waves = ctx->waves.as<ExtWave>();                // absolute descriptor indices: the rowkey slot of group g is g - first wide group
+	wa.rowkey = ctx->rowkey.as<uint32_t>() - (int64_t)P.ext[X_W2].first * 2 * P.key_stride;
+	GlobArgs &ga = R.ga;
+	ga.tasks = ctx->tasks.as<DTask>(), ga.rec = ctx->rec.as<uint32_t>(), ga.prof = ctx->prof.as<int16_t>();
+	ga.tb = ctx->tb.as<uint16_t>(), ga.bnd = ctx->bnd.as<int4>(), ga.score = ctx->score.as<int32_t>(), ga.c = dc, ga.rowkey64 = nullptr, ga.waves = nullptr;
+	return MPA_OK;
+}
+
+// ---- 4. what runs next to the round on side streams: the anti-diagonal prototype, the huge calls, the T_LITE_W4 sweep
+static int dp_side_launches(DpRun &R)
+{
+	mpa_ctx_t *ctx = R.ctx;
+	DpPlan &P = R.plan;
+	// fork: every side launch waits for the prep kernels, so the long single-wave tails overlap instead of adding up
+	HIP_TRY(hipEventRecord(ctx->fork_ev, R.s));
+	if (ctx->antidiag && P.ext[X_32].cnt > 0) {                        // (measurement) the 32-column class on the anti-diagonal prototype, one wave per block
+		hipStream_t st = begin_side(R, true);
+		hipLaunchKernelGGL(k_ext_antidiag, dim3((unsigned)P.ext[X_32].cnt), dim3(64), EXT_ANTIDIAG_LDS, st, R.ea, P.ext[X_32].first);
+		HIP_TRY(hipGetLastError());
+		end_side(R);
+		ctx->stats.launches_ext++;
+	}
+	if (!P.huge_ids.empty()) {                                         // block-major sweep with the traceback kernel's arithmetic, then the replay
+		const unsigned n_huge = (unsigned)P.huge_ids.size();
+		GlobArgs ha;
+		ha.tasks = ctx->tasks.as<DTask>(), ha.waves = R.d_hw, ha.rec = ctx->rec.as<uint32_t>(), ha.prof = ctx->prof.as<int16_t>();
+		ha.tb = nullptr, ha.bnd = ctx->bnd.as<int4>(), ha.score = nullptr, ha.c = R.dc, ha.rowkey64 = ctx->hkey.as<unsigned long long>();
+		hipStream_t st = begin_side(R, true);
+		if (P.wide_ge) hipLaunchKernelGGL(k_ext_huge<true>, dim3(n_huge), dim3(64), (size_t)22 * 64 * 2 + 4 * 32 * 4, st, ha);
+		else hipLaunchKernelGGL(k_ext_huge<false>, dim3(n_huge), dim3(64), (size_t)22 * 64 * 2 + 4 * 32 * 4, st, ha);
+		HIP_TRY(hipGetLastError());
+		hipLaunchKernelGGL(k_ext_replay, dim3(n_huge), dim3(64), 0, st, ctx->tasks.as<DTask>(), R.d_hlist, (int32_t)n_huge,
+		                   ctx->hkey.as<unsigned long long>(), ctx->extout.as<ExtOut>(), R.dc, P.pen);
+		HIP_TRY(hipGetLastError());
+		end_side(R);
+		ctx->stats.launches_ext++;
+	}
+	// the packed sweep of the 129..256-column checkpointed class (unit kind U_LITE_W4): a 256-thread launch of its own next to the
+	// round, on a side stream (at most two are taken at this point, by the launches above); the walk waits for it
+	if (P.lite_w4.cnt > 0) {
+		hipStream_t st = begin_side(R, false);
+		hipLaunchKernelGGL(k_lite_wide, dim3((unsigned)P.lite_w4.cnt), dim3(MPA_LITE_WIDE_WAVES * 64), 0, st, R.ea, P.lite_w4.first);
+		HIP_TRY(hipGetLastError());
+		end_side(R), R.l12_side = R.launches.back().side;
+		ctx->stats.launches_glob++;
+	}
+	return MPA_OK;
+}
+
+// Workgroups of the round kernel per CU, enforced through the LDS it asks for (MPA_DP_WG_PER_CU, default 3).  Round 6: the
+// kernel takes 124 VGPRs (the asm rows of ext_narrow keep the whole DP state of eight calls in registers and nothing is
+// spilled), so three workgroups hold 372 of each SIMD's 512 registers -- what four workgroups of the 95-register kernel of
+// rounds 4-5 held (384) -- and the seeding kernels of the next batches stay co-resident.  One more workgroup than wanted must
+// NOT fit; what is left of the LDS stays free for the seeding kernels.
+static size_t dp_round_lds()
+{
+	static const size_t round_lds = [] {
+		const char *e = getenv("MPA_DP_WG_PER_CU");
+		int want = e ? atoi(e) : 3;
+		if (want < 1) want = 1;
+		if (want > 4) want = 4;
+		const size_t pad = (((size_t)160 * 1024 / (want + 1)) + 256) & ~(size_t)255;
+		return pad > DP_ROUND_LDS ? pad : DP_ROUND_LDS;
+	}();
+	return round_lds;
+}
+
+// every DP unit of the round (dp_plan_units, built straight into the staging block) in ONE k_dp_round launch on the context's main stream -- or handed to the worker pool;
+// d_gw: the first traceback chunk's waves when they ride in the round
+static int dp_launch_round(DpRun &R, GlobWave *d_gw)
+{
+	mpa_ctx_t *ctx = R.ctx;
+	DpPlan &P = R.plan;
+	hipStream_t s = R.s;
+	DpUnit *units = (DpUnit*)(R.hup + P.up.units);          // (pinned: the copy below needs no wait)
+	int rc;
+	if ((rc = dp_plan_units(P, R.kn, units))) { set_error(P.err); return rc; }
+	const size_t n_units = P.n_units;
+	if (n_units == 0) return MPA_OK;
+	static const bool show_top = [] { const char *e = getenv("MPA_DP_TOP"); return e && atoi(e) != 0; }();
+	if (show_top) fputs(dp_plan_top(P, R.kn).c_str(), stderr);
+	if ((rc = ctx->units.ensure(P.sz.units))) return rc;
+	HIP_TRY(hipMemcpyAsync(ctx->units.p, units, P.sz.units, hipMemcpyHostToDevice, s));
+	R.ga.waves = d_gw;
+	const size_t round_lds = dp_round_lds();
+	if (dp_pool_enabled()) {
+		if ((rc = pool_launch_round(ctx, s, R.ea, R.wa, R.ga, (DpRoundArgs*)(R.hup + P.up.args), n_units, P.n_group, round_lds, &R.pool_gen))) return rc;
+		R.pool_pending = true;
+	} else {
+		if (round_lds > 48 * 1024) HIP_TRY(ensure_dynamic_lds((const void*)k_dp_round, ctx->device, round_lds));
+		HIP_TRY(hipEventRecord(R.ev_round(0), s));
+		hipLaunchKernelGGL(k_dp_round, dim3((unsigned)n_units), dim3(256), round_lds, s, R.ea, R.wa, R.ga, ctx->units.as<DpUnit>());
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipEventRecord(R.ev_round(1), s));
+	}
+	R.round_launched = true;
+	ctx->stats.launches_ext++;
+	return MPA_OK;
+}
+
+// launch, then (worker pool) wait until the round's units are done
+static int dp_round(DpRun &R, GlobWave *d_gw, const char *what)
+{
+	int rc;
+	if ((rc = dp_launch_round(R, d_gw)) != MPA_OK) return rc;
+	R.mark(what);
+	if (R.pool_pending) {
+		if ((rc = pool_wait_round(R.ctx, R.s, R.pool_gen, (const DpUnit*)(R.hup + R.plan.up.units), R.plan.n_units)) != MPA_OK) return rc;
+		R.pool_pending = false;
+	}
+	if (dp_pool_enabled()) R.mark("    dp: round (units done)");
+	return MPA_OK;
+}
+
+// one stand-alone launch of a chunk's plain traceback sweep: T_16, T_32, T_64 and T_MB share one ("narrow", cls < 0), every wide class has its own
+static hipError_t launch_glob_class(DpRun &R, const DpTbChunk &r, GlobWave *d_gw, int cls, hipStream_t st)
+{
+	GlobArgs &ga = R.ga;
+	const bool wide_ge = R.plan.wide_ge;
+	if (cls < 0) {
+		int first[8], cnt[8];
+		for (int c = 0; c < 8; ++c) first[c] = r.cls[c].first, cnt[c] = r.cls[c].cnt;
+		ga.waves = d_gw;
+		return launch_glob_narrow(ga, first, cnt, st, wide_ge);
+	}
+	ga.waves = d_gw + r.cls[cls].first;
+	switch (cls) {
+	case T_W2: return launch_glob_wide<2>(ga, r.cls[cls].cnt, st, wide_ge);
+	case T_W4: return launch_glob_wide<4>(ga, r.cls[cls].cnt, st, wide_ge);
+	case T_W8: return launch_glob_wide<8>(ga, r.cls[cls].cnt, st, wide_ge);
+	default: return launch_glob_wide<16>(ga, r.cls[cls].cnt, st, wide_ge);
+	}
+}
+
+// ---- 5. the chunks of the plain traceback sweep, each followed by k_backtrack; the round's launch rides with the first
+static int dp_tb_chunks(DpRun &R)
+{
+	mpa_ctx_t *ctx = R.ctx;
+	DpPlan &P = R.plan;
+	hipStream_t s = R.s;
+	char *hup = R.hup;
+	int rc;
+	for (size_t ri = 0; ri < P.chunks.size(); ++ri) {
+		dp_plan_chunk_waves(P, ri);
+		const DpTbChunk &r = P.chunks[ri];
+		if (ri > 0) {                                                    // later chunks reuse the traceback buffer (and its staging): join everything first
+			for (auto &l : R.launches) (void)hipStreamWaitEvent(s, ctx->lev[2 * l.side + 1], 0);
+			HIP_TRY(wait_stream(ctx, s));
+			R.add_chunk_times();                                           // (the previous chunk's sweep and walk)
+		}
+		int32_t *d_list = ctx->list.as<int32_t>();
+		GlobWave *d_gw = (GlobWave*)((char*)ctx->list.p + ((P.tasks.size() * 4 + 63) & ~(size_t)63));
+		memcpy(hup + P.up.list, r.list.data(), r.list.size() * 4);
+		memcpy(hup + P.up.gw, r.waves.data(), r.waves.size() * sizeof(GlobWave));
+		HIP_TRY(hipMemcpyAsync(d_list, hup + P.up.list, r.list.size() * 4, hipMemcpyHostToDevice, s));
+		HIP_TRY(hipMemcpyAsync(d_gw, hup + P.up.gw, r.waves.size() * sizeof(GlobWave), hipMemcpyHostToDevice, s));
+		R.mark("    dp: traceback lists enqueued");
+		R.ga.tb = ctx->tb.as<uint16_t>();
+		HIP_TRY(hipEventRecord(ctx->ev[3], s));
+		// every launch on its own stream (next to the extension classes in the first chunk); the walk needs them all
+		HIP_TRY(hipEventRecord(ctx->fork_ev, s));
+		const size_t first_glob_launch = R.launches.size();
+		const bool in_round = ri == 0 && P.round_has_glob;
+		const int order[5] = { T_W16, T_W8, T_W4, T_W2, -1 };
+		for (int cls : order) {
+			if (in_round && cls < T_W8) continue;                            // (only the 512/1024-thread traceback classes keep their own launch)
+			if (cls >= 0 ? !r.cls[cls].cnt : !(r.cls[T_16].cnt + r.cls[T_32].cnt + r.cls[T_64].cnt + r.cls[T_MB].cnt)) continue;
+			if ((int)R.launches.size() >= mpa_ctx_s::kSide - 1) {            // out of side streams (the last event pair times the round's launch): main stream
+				HIP_TRY(launch_glob_class(R, r, d_gw, cls, s));
+			} else {
+				hipStream_t st = begin_side(R, false);
+				HIP_TRY(launch_glob_class(R, r, d_gw, cls, st));
+				end_side(R);
+			}
+			ctx->stats.launches_glob++;
+		}
+		if (in_round) {                                        // (behind the 512/1024-thread classes' own launches: with the worker pool the host waits here)
+			ctx->stats.launches_glob++;
+			if ((rc = dp_round(R, d_gw, "    dp: units up, round launched")) != MPA_OK) return rc;
+		}
+		for (size_t k = first_glob_launch; k < R.launches.size(); ++k) (void)hipStreamWaitEvent(s, ctx->lev[2 * R.launches[k].side + 1], 0);
+		HIP_TRY(hipEventRecord(ctx->ev[4], s));
+		hipLaunchKernelGGL(k_backtrack, dim3((unsigned)r.list.size()), dim3(64), 0, s, ctx->tasks.as<DTask>(), d_list, (int32_t)r.list.size(),
+		                   ctx->tb.as<uint16_t>(), ctx->cig.as<uint32_t>(), ctx->ncig.as<int32_t>());
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipEventRecord(ctx->ev[5], s));
+		R.glob_timed = true;                                              // (ev[3..5] are read after the next wait)
+	}
+	if (!R.round_launched && (rc = dp_round(R, nullptr, "    dp: (round without traceback launched)")) != MPA_OK) return rc;
+	return MPA_OK;
+}
+
+// ---- 6. the walk of the checkpointed traceback: behind the round that swept its calls
+static int dp_walk(DpRun &R)
+{
+	mpa_ctx_t *ctx = R.ctx;
+	DpPlan &P = R.plan;
+	hipStream_t s = R.s;
+	if (!P.n_lite) return MPA_OK;
+	memcpy(R.hup + P.up.wl, P.glob_ids.data() + P.n_reg_glob, 4 * P.n_lite);
+	HIP_TRY(hipMemcpyAsync(ctx->wlist.p, R.hup + P.up.wl, 4 * P.n_lite, hipMemcpyHostToDevice, s));
+	WalkArgs wk;
+	wk.ga = R.ga, wk.ga.waves = nullptr, wk.list = ctx->wlist.as<int32_t>(), wk.n_list = (int32_t)P.n_lite;
+	wk.lite = ctx->lite.as<uint32_t>(), wk.ckpt = ctx->ckpt.as<uint32_t>(), wk.cig = ctx->cig.as<uint32_t>(), wk.n_cigar = ctx->ncig.as<int32_t>();
+	wk.n_blocks = (unsigned long long*)((char*)ctx->wlist.p + ((P.n_lite * 4 + 63) & ~(size_t)63));
+	HIP_TRY(hipMemsetAsync(wk.n_blocks, 0, 8, s));
+	// (the list is sorted by class: one launch per class, with the LDS that class's block of direction words needs)
+	size_t at = 0;
+	for (int cls = T_LITE16; cls <= T_LITE_W4; ++cls) {
+		const size_t n_c = (size_t)P.walk_cnt[cls - T_LITE16];
+		if (n_c == 0) continue;
+		wk.list = ctx->wlist.as<int32_t>() + at, wk.n_list = (int32_t)n_c;
+		if (cls == T_LITE_W4) {                                            // behind their own sweep; more LDS than a launch gets unasked
+			if (R.l12_side >= 0) (void)hipStreamWaitEvent(s, ctx->lev[2 * R.l12_side + 1], 0);
+			HIP_TRY(ensure_dynamic_lds((const void*)k_walk, ctx->device, WALK_LDS(256)));
+		}
+		hipLaunchKernelGGL(k_walk, dim3((unsigned)n_c), dim3(64), WALK_LDS(lite_columns(cls)), s, wk);
+		at += n_c;
+	}
+	HIP_TRY(hipGetLastError());
+	ctx->stats.launches_glob++;
+	return MPA_OK;
+}
+
+// ---- 7. join the side streams; results into pinned memory behind the last kernel (extension outputs, traceback scores and
+// CIGAR lengths, hand-off error flag, the walk's block count); the one wait of the round; kernel times
+static int dp_join_and_download(DpRun &R)
+{
+	mpa_ctx_t *ctx = R.ctx;
+	DpPlan &P = R.plan;
+	hipStream_t s = R.s;
+	const size_t n = P.tasks.size();
+	for (auto &l : R.launches) (void)hipStreamWaitEvent(s, ctx->lev[2 * l.side + 1], 0);
+	HIP_TRY(hipEventRecord(ctx->ev[2], s));
+	int rc;
+	if ((rc = ctx->h_down.ensure(P.dn.end))) return rc;
+	char *hdn = R.hdn = ctx->h_down.as<char>();
+	*(int32_t*)(hdn + P.dn.err) = 0;
+	if (!P.ext_ids.empty()) HIP_TRY(hipMemcpyAsync(hdn + P.dn.eo, ctx->extout.p, sizeof(ExtOut) * n, hipMemcpyDeviceToHost, s));
+	if (!P.glob_ids.empty()) {
+		HIP_TRY(hipMemcpyAsync(hdn + P.dn.sc, ctx->score.p, n * 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(hdn + P.dn.nc, ctx->ncig.p, n * 4, hipMemcpyDeviceToHost, s));
+	}
+	if (P.n_split) HIP_TRY(hipMemcpyAsync(hdn + P.dn.err, R.wa.err, 4, hipMemcpyDeviceToHost, s));
+	*(unsigned long long*)(hdn + P.dn.wb) = 0;
+	if (P.n_lite) HIP_TRY(hipMemcpyAsync(hdn + P.dn.wb, (char*)ctx->wlist.p + ((P.n_lite * 4 + 63) & ~(size_t)63), 8, hipMemcpyDeviceToHost, s));
+	R.mark("    dp: round enqueued");
+	HIP_TRY(wait_stream(ctx, s));
+	R.mark("    dp: round (wait)");
+	if (R.glob_timed) R.add_chunk_times();
+	float ms_ext_sum = 0;                                                 // sum of the per-launch durations of the extension kernels
+	if (R.round_launched && !dp_pool_enabled()) {
+		(void)hipEventElapsedTime(&ms_ext_sum, R.ev_round(0), R.ev_round(1));
+		ctx->stats.ms_round = ms_ext_sum, ctx->stats.launches_round = 1;
+	}
+	if (dp_pool_enabled()) pool_harvest(ctx, false);                    // (worker launches that have ended: into the context's totals)
+	for (auto &l : R.launches) {
+		float ms = 0;
+		(void)hipEventElapsedTime(&ms, ctx->lev[2 * l.side], ctx->lev[2 * l.side + 1]);
+		if (l.is_ext) ms_ext_sum += ms;
+		else if (l.side == R.l12_side) R.ms_glob += ms;                  // (the 129..256-column packed sweep: a traceback sweep like the chunks')
+	}
+	ctx->stats.ms_ext = ms_ext_sum;
+	return MPA_OK;
+}
+
+// ---- 8. the real CIGARs gathered into a dense pool on the device (the slots were sized for the worst case, nl+al+4 words each:
+// only that goes over PCIe); the caller's result records
+static int dp_assemble(DpRun &R, mpa_dp_rst_t *rst, uint32_t **cigar_pool, int64_t *n_pool)
+{
+	mpa_ctx_t *ctx = R.ctx;
+	DpPlan &P = R.plan;
+	hipStream_t s = R.s;
+	const size_t n_glob = P.glob_ids.size();
+	const ExtOut *eo = (const ExtOut*)(R.hdn + P.dn.eo);
+	const int32_t *sc = (const int32_t*)(R.hdn + P.dn.sc), *nc = (const int32_t*)(R.hdn + P.dn.nc);
+	int64_t &pool_n = R.pool_n;
+	int64_t *dense_off = (int64_t*)(R.hup + P.up.off);                    // (the staging buffer's earlier sections have been consumed)
+	for (size_t g = 0; g < n_glob; ++g) dense_off[g] = pool_n, pool_n += nc[P.glob_ids[g]];
+	uint32_t *pool = (uint32_t*)malloc((size_t)(pool_n > 0 ? pool_n : 1) * 4);
+	if (pool_n > 0) {
+		int rc;
+		if ((rc = ctx->cigd.ensure((size_t)pool_n * 4)) || (rc = ctx->cigoff.ensure(n_glob * 12 + 64)) || (rc = ctx->h_pool.ensure((size_t)pool_n * 4))) { free(pool); return rc; }
+		int64_t *d_off = ctx->cigoff.as<int64_t>();
+		int32_t *d_ids = (int32_t*)(d_off + n_glob);
+		memcpy(R.hup + P.up.ids, P.glob_ids.data(), n_glob * 4);
+		HIP_TRY(hipMemcpyAsync(d_off, dense_off, n_glob * 8, hipMemcpyHostToDevice, s));
+		HIP_TRY(hipMemcpyAsync(d_ids, R.hup + P.up.ids, n_glob * 4, hipMemcpyHostToDevice, s));
+		hipLaunchKernelGGL(k_cigar_gather, dim3((unsigned)n_glob), dim3(64), 0, s, ctx->tasks.as<DTask>(), d_ids, d_off, (int32_t)n_glob,
+		                   ctx->ncig.as<int32_t>(), ctx->cig.as<uint32_t>(), ctx->cigd.as<uint32_t>());
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(ctx->h_pool.p, ctx->cigd.p, (size_t)pool_n * 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(wait_stream(ctx, s));
+		memcpy(pool, ctx->h_pool.p, (size_t)pool_n * 4);
+	}
+	std::vector<int64_t> off_of(P.tasks.size(), 0);
+	for (size_t k = 0; k < n_glob; ++k) off_of[P.glob_ids[k]] = dense_off[k];
+	for (size_t k = 0; k < P.tasks.size(); ++k) {
+		const DTask &t = P.tasks[k];
+		mpa_dp_rst_t &o = rst[k];
+		if (t.flag & (MPA_F_EXT_LEFT | MPA_F_EXT_RIGHT)) {
+			o.nt_len = eo[k].nt_len, o.aa_len = eo[k].aa_len, o.score = eo[k].score, o.n_cigar = 0, o.cigar_off = 0;
+		} else {
+			o.nt_len = t.nl, o.aa_len = t.al, o.score = sc[k], o.n_cigar = nc[k], o.cigar_off = off_of[k];
+		}
+	}
+	if (cigar_pool) *cigar_pool = pool; else free(pool);
+	if (n_pool) *n_pool = pool_n;
+	return MPA_OK;
+}
+
+// ---- 9. statistics: the plan's counts, cells and bytes, the event times, the context's totals
+static void dp_statistics(DpRun &R)
+{
+	mpa_ctx_t *ctx = R.ctx;
+	mpa_dp_stats_t &st = ctx->stats;
+	dp_plan_stats(R.plan);
+	const mpa_dp_stats_t &ps = R.plan.stats;
+	st.n_ext = ps.n_ext, st.n_glob = ps.n_glob, st.cells_ext = ps.cells_ext, st.cells_glob = ps.cells_glob, st.rows_prep = ps.rows_prep;
+	st.alg_bytes_ext = ps.alg_bytes_ext, st.alg_bytes_glob = ps.alg_bytes_glob + 4 * R.pool_n;   // (+ the CIGARs' own words)
+	st.n_ckpt = ps.n_ckpt, st.cells_ckpt = ps.cells_ckpt, st.n_ckpt_wide = ps.n_ckpt_wide, st.cells_ckpt_wide = ps.cells_ckpt_wide;
+	st.cells_ext_round = ps.cells_ext_round, st.cells_glob_round = ps.cells_glob_round;
+	st.walk_blocks = (int64_t)*(const unsigned long long*)(R.hdn + R.plan.dn.wb);
+	float ms = 0;
+	(void)hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); st.ms_prep = ms;
+	st.ms_glob = R.ms_glob, st.ms_backtrack = R.ms_bt;
+	timing_note("    dp: GPU prep kernels", st.ms_prep);
+	timing_note("    dp: GPU round kernel", st.ms_round);
+	timing_note("    dp: GPU walk", R.ms_bt);
+	{ float w = 0; (void)hipEventElapsedTime(&w, ctx->ev[0], ctx->ev[2]); st.ms_total = w; }   // wall time of the whole batch on the device
+	mpa_dp_stats_t &t = ctx->total;
+	t.n_ext += st.n_ext, t.n_glob += st.n_glob, t.cells_ext += st.cells_ext, t.cells_glob += st.cells_glob, t.rows_prep += st.rows_prep;
+	t.alg_bytes_ext += st.alg_bytes_ext, t.alg_bytes_glob += st.alg_bytes_glob;
+	t.n_ckpt += st.n_ckpt, t.cells_ckpt += st.cells_ckpt, t.walk_blocks += st.walk_blocks;
+	t.n_ckpt_wide += st.n_ckpt_wide, t.cells_ckpt_wide += st.cells_ckpt_wide;
+	t.ms_prep += st.ms_prep, t.ms_ext += st.ms_ext, t.ms_glob += st.ms_glob, t.ms_backtrack += st.ms_backtrack, t.ms_total += st.ms_total;
+	t.launches_ext += st.launches_ext, t.launches_glob += st.launches_glob;
+	t.cells_ext_round += st.cells_ext_round, t.cells_glob_round += st.cells_glob_round, t.ms_round += st.ms_round, t.launches_round += st.launches_round;
+}
+
+// the executor's knobs as the planner takes them (the environment: read when the context was created, or once per process)
+static DpPlanKnobs dp_plan_knobs(const mpa_ctx_t *ctx)
+{
+	static const bool ext_dual = [] { const char *e = getenv("MPA_DP_EXT_DUAL"); return !e || atoi(e) != 0; }();
+	static const bool unit_prio = [] { const char *e = getenv("MPA_DP_PRIO"); return !e || atoi(e) != 0; }();   // (MPA_DP_PRIO=0: measurement)
+	DpPlanKnobs kn;
+	kn.lite_min = ctx->lite_min, kn.lite_wide = ctx->lite_wide, kn.no_split = ctx->no_split, kn.antidiag = ctx->antidiag, kn.pool = dp_pool_enabled();
+	kn.ext_dual = ext_dual, kn.unit_prio = unit_prio, kn.tb_budget = (int64_t)ctx->tb_budget;
+	return kn;
+}
+
 static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *opt, const mpa_qbatch_t *q,
                int64_t n, const mpa_dp_task_t *in, mpa_dp_rst_t *rst, uint32_t **cigar_pool, int64_t *n_pool)
 {
@@ -1891,827 +2413,34 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 	ctx->stats = mpa_dp_stats_t();
 	if (n <= 0) return MPA_OK;
 	HIP_TRY(hipSetDevice(ctx->device));
-	hipStream_t s = ctx->stream;
 	const double t_begin = now_ms();
-
-	// ---- parameter guards: outside these the packed-int16 kernels would not be bit-exact
-	int32_t max_mat = 0;
-	for (int k = 0; k < 484; ++k) max_mat = std::max<int32_t>(max_mat, opt->mat[k]);
-	if (opt->go < 0 || opt->go > 32000 || opt->ge < 0 || opt->ge > 16000 || opt->fs < 0 || opt->fs > 16000 || opt->xdrop < 0 || opt->xdrop > 32000 ||
-	    opt->end_bonus < 0 || opt->end_bonus > 1000 || (opt->ge > 255 && opt->go + opt->ge > 32000)) {
-		set_error("DP parameters outside the supported range (go <= 32000, ge, fs <= 16000, 0 <= xdrop <= 32000, 0 <= end_bonus <= 1000)"); return MPA_ERR_UNSUPPORTED;
-	}
-	// Gap-extension / frameshift penalties above 255 (-E / -F of the reference's command line, main.c:133,136) do not fit the byte
-	// the row records give them.  Such a run keeps the records' layout -- the byte then flags a stop codon -- and sweeps every call
-	// with the kernels that read it that way (glob_cands<K, true>): the stand-alone traceback kernels and, for extension calls,
-	// the block-major one-wave sweep (k_ext_huge); the packed round kernel is not used.  Slow, exact, and nobody's default.
-	const bool wide_ge = opt->ge > 255 || opt->fs > 255;
-
-	// ---- classify, order and lay out the calls
-	std::vector<DTask> T(n);
-	std::vector<int32_t> ext_ids, glob_ids;
-	int32_t max_nl_ext = 0;
-	const bool pool_on = dp_pool_enabled();
-	for (int64_t k = 0; k < n; ++k) {
-		const mpa_dp_task_t &x = in[k];
-		DTask &t = T[k];
-		memset(&t, 0, sizeof(t));
-		if (x.nl < 0 || x.al <= 0 || x.qid < 0 || x.qid >= q->n_seq || x.io < 0 || x.io > 32000) { set_error("malformed DP task"); return MPA_ERR_ARG; }
-		// the kernels address the resident genome and the query buffer with these: a window or a protein slice that leaves its
-		// contig / its query would read foreign memory (or fault the context), so it is refused here
-		if (x.vid < 0 || x.vid >= 2 * (int32_t)mi->ctg.size() || x.nt_off < 0 || x.nt_off + (int64_t)x.nl > mi->ctg[x.vid >> 1].len ||
-		    x.aa_off < 0 || (int64_t)x.aa_off + x.al > q->q_off[x.qid + 1] - q->q_off[x.qid]) {
-			set_error("DP task " + std::to_string(k) + " reaches outside its contig or its query"); return MPA_ERR_ARG;
-		}
-		t.nt_off = x.nt_off, t.vid = x.vid, t.nl = x.nl, t.al = x.al, t.flag = x.flag, t.io = x.io;
-		t.q_off = q->q_off[x.qid] + x.aa_off - q->q_off[0];     // relative to the slice uploaded below
-		t.ncol = (x.al + 7) / 8 * 8;
-		t.out_idx = (int32_t)k;
-		// (the int32 sweeps keep the striped reference's lane segments apart by offsets of 2^20 in their scans: column * ge must stay below)
-		// (checked below where it matters: the traceback sweeps and the block-major extension sweep; the packed extension kernels
-		// have their own bound, may_saturate)
-		const bool seg_overflow = (int64_t)t.ncol * opt->ge >= (1 << 19);
-		const bool is_ext = (x.flag & (MPA_F_EXT_LEFT | MPA_F_EXT_RIGHT)) != 0;
-		// The packed int16 kernels run their gap scan on h + j*ge with saturating adds and hold go + j*ge in int16, which is only the
-		// reference's value while nothing can reach the int16 limits.  Calls that could -- with BLOSUM62 and ge = 1 more than ~2900
-		// columns, always of the "huge" class; with a large -E or -O already at a few dozen columns -- go to the int32 sweeps, which
-		// clamp every operation like the reference does: k_ext_huge for extension calls, the plain traceback sweep for the others.
-		const bool may_saturate = (int64_t)x.al * max_mat + (int64_t)t.ncol * opt->ge + std::max(0, opt->end_bonus) > 32000 || opt->go + (int64_t)t.ncol * opt->ge > 32000;
-		if (is_ext) {
-			int cls = ext_class_of(t.ncol);                        // -1: wider than k_ext_wide<16> covers -> k_ext_huge (class 7)
-			if (ctx->no_split && cls >= 5) cls = -1;               // repeated round: no inter-workgroup hand-off (see mpa_dp_run)
-			if (wide_ge || may_saturate) cls = -1;
-			if (cls < 0 && seg_overflow) { set_error("DP call " + std::to_string(k) + ": too wide for this gap-extension penalty (columns x ge must stay below 2^19 in the int32 sweeps)"); return MPA_ERR_UNSUPPORTED; }
-			t.pw = cls >= 0 ? kExtClasses[cls].G * kExtClasses[cls].NB : t.ncol;
-			t.pad_ = cls >= 0 ? cls : 7;
-			// 65..128 columns: one wave per call, column c + 64 in the high half of lane c (ext_narrow<64, false, true>, class 8), instead
-			// of a two-wave group per pair of calls (MPA_DP_EXT_DUAL=0: the two-wave groups of rounds 2-5)
-			static const bool ext_dual = [] { const char *e = getenv("MPA_DP_EXT_DUAL"); return !e || atoi(e) != 0; }();
-			if (cls == 3 && ext_dual && !ctx->antidiag) t.pad_ = 8;
-			ext_ids.push_back((int32_t)k);
-			max_nl_ext = std::max(max_nl_ext, x.nl);
-		} else {
-			if (!(x.flag & MPA_F_CIGAR)) { set_error("global DP without CIGAR is not part of miniprot's path"); return MPA_ERR_UNSUPPORTED; }
-			if (seg_overflow) { set_error("DP call " + std::to_string(k) + ": too wide for this gap-extension penalty (columns x ge must stay below 2^19 in the int32 sweeps)"); return MPA_ERR_UNSUPPORTED; }
-			t.pw = t.ncol;
-			t.pad_ = t.ncol <= 16 ? 0 : t.ncol <= 32 ? 1 : t.ncol <= 64 ? 2 : t.ncol <= 128 ? 3 : t.ncol <= 256 ? 4 : t.ncol <= 512 ? 5 : t.ncol <= 1024 ? 6 : 7;
-			// Checkpointed traceback (dp_device.h): a call of up to 128 columns and many rows -- the gap fills across introns and the spans
-			// of accepted extensions, where nearly every row lies inside an intron -- is swept by the packed sweep (classes 8, 9, 10: 16,
-			// 32, 64 lanes per call, two calls per lane; class 11: one call per wave) and walked by k_walk.  Short calls stay on the plain
-			// traceback sweep: the walk would recompute all of their rows anyway.  MPA_DP_LITE_MIN (rows; 0: never), read when the context
-			// is created.  The packed sweep is an int16 one: calls that may saturate stay on the plain sweep too.
-			if (ctx->lite_min > 0 && !wide_ge && !may_saturate && t.ncol <= 128 && x.nl >= ctx->lite_min && x.nl >= 3) t.pad_ += 8, t.pw = 16 << (t.pad_ - 8);   // (class 11: 65..128 columns, one call per wave)
-			// Class 12: 129..256 columns under the same predicate, a four-wave group per pair of calls (lite_wide_body, a launch of its
-			// own next to the round), with MPA_DP_LITE_WIDE=1.  The default, 0, keeps them on the plain sweep (no A/B has
-			// been measured yet); so does the worker pool (MPA_DP_POOL=1), whose workers do not know the class.
-			else if (ctx->lite_min > 0 && ctx->lite_wide && !pool_on && !wide_ge && !may_saturate && t.ncol > 128 && t.ncol <= 256 && x.nl >= ctx->lite_min && x.nl >= 3)
-				t.pad_ = 12, t.pw = 256;
-			glob_ids.push_back((int32_t)k);
-		}
-	}
-	auto by_class_then_len = [&](int32_t a, int32_t b) {
-		if (T[a].pad_ != T[b].pad_) return T[a].pad_ < T[b].pad_;
-		if (T[a].nl != T[b].nl) return T[a].nl > T[b].nl;
-		return a < b;
-	};
-	std::sort(ext_ids.begin(), ext_ids.end(), by_class_then_len);
-	std::sort(glob_ids.begin(), glob_ids.end(), by_class_then_len);
-	int64_t rec_total = 0, prof_total = 0, cig_total = 0, bnd_total = 0;
-	int32_t max_nl = 0;
-	std::vector<PrepChunk> chunks;
-	auto layout = [&](int32_t id) {
-		DTask &t = T[id];
-		t.rec_off = rec_total, rec_total += t.nl;
-		t.prof_off = prof_total, prof_total += (int64_t)22 * t.pw;
-		max_nl = std::max(max_nl, t.nl);
-		for (int32_t r = 0; r < t.nl; r += MPA_PREP_CHUNK_ROWS) chunks.push_back(PrepChunk{ id, r });
-	};
-	int64_t hkey_total = 0;                                 // per-row keys (8 B) of the extension calls wider than 1024 columns
-	std::vector<int32_t> huge_ids;
-	for (int32_t id : ext_ids) {
-		layout(id);
-		DTask &t = T[id];
-		if (t.pad_ == 7) t.bnd_off = bnd_total, bnd_total += t.nl, t.tb_off = hkey_total, hkey_total += t.nl, huge_ids.push_back(id);
-	}
-	for (int32_t id : glob_ids) {
-		layout(id);
-		DTask &t = T[id];
-		t.cig_cap = t.nl + t.al + 4;
-		t.cig_off = cig_total, cig_total += t.cig_cap;
-		if (t.pad_ == 7) t.bnd_off = bnd_total, bnd_total += t.nl;
-	}
-	rec_total += max_nl + 96 + (ctx->antidiag ? 64 : 0);    // kernels prefetch records up to 48 rows past a call's end (the anti-diagonal prototype: 128)
-
-	// ---- waves of the extension kernel
-	std::vector<ExtWave> ewaves;
-	std::vector<int> ewave_cnt(kNumExtClasses, 0), ewave_first(kNumExtClasses, 0);
-	{
-		size_t p = 0;
-		for (int cls = 0; cls < kNumExtClasses; ++cls) {
-			const int slots = 2 * (64 / kExtClasses[cls].G);
-			ewave_first[cls] = (int)ewaves.size();
-			while (p < ext_ids.size() && T[ext_ids[p]].pad_ == cls) {
-				ExtWave w;
-				memset(&w, 0, sizeof(w));
-				for (int k = 0; k < 8; ++k) w.task[k] = -1;
-				w.rec_base = T[ext_ids[p]].rec_off;
-				for (int k = 0; k < slots && p < ext_ids.size() && T[ext_ids[p]].pad_ == cls; ++k, ++p) {
-					w.task[k] = ext_ids[p];
-					w.max_nl = std::max(w.max_nl, T[ext_ids[p]].nl);
-				}
-				ewaves.push_back(w);
-			}
-			ewave_cnt[cls] = (int)ewaves.size() - ewave_first[cls];
-		}
-	}
-	// ---- one-call waves of the 65..128-column extension class (8: sorts behind the huge class 7)
-	int dwave_first = (int)ewaves.size(), dwave_cnt = 0;
-	for (size_t p = 0; p < ext_ids.size(); ++p) {
-		if (T[ext_ids[p]].pad_ != 8) continue;
-		ExtWave w;
-		memset(&w, 0, sizeof(w));
-		for (int k = 0; k < 8; ++k) w.task[k] = -1;
-		w.task[0] = ext_ids[p], w.rec_base = T[ext_ids[p]].rec_off, w.max_nl = T[ext_ids[p]].nl;
-		ewaves.push_back(w), ++dwave_cnt;
-	}
-	// ---- waves of the checkpointed traceback's packed sweep (classes 8, 9, 10 sort behind every other traceback call)
-	size_t n_reg_glob = 0;
-	while (n_reg_glob < glob_ids.size() && T[glob_ids[n_reg_glob]].pad_ < 8) ++n_reg_glob;
-	int lwave_first[4] = { 0, 0, 0, 0 }, lwave_cnt[4] = { 0, 0, 0, 0 };
-	int64_t lite_total = 0, ck_total = 0;
-	{
-		size_t p = n_reg_glob;
-		for (int cls = 0; cls < 4; ++cls) {
-			const int slots = cls == 3 ? 1 : 2 * (64 / (16 << cls));
-			lwave_first[cls] = (int)ewaves.size();
-			while (p < glob_ids.size() && T[glob_ids[p]].pad_ == 8 + cls) {
-				ExtWave w;
-				memset(&w, 0, sizeof(w));
-				for (int k = 0; k < 8; ++k) w.task[k] = -1;
-				w.rec_base = T[glob_ids[p]].rec_off;
-				const size_t p0 = p;
-				for (int k = 0; k < slots && p < glob_ids.size() && T[glob_ids[p]].pad_ == 8 + cls; ++k, ++p) {
-					w.task[k] = glob_ids[p];
-					w.max_nl = std::max(w.max_nl, T[glob_ids[p]].nl);
-					T[glob_ids[p]].flag |= k << MPA_LITE_SLOT_SHIFT;
-				}
-				w.lite_off = lite_total, lite_total += ((int64_t)w.max_nl / 3 + 2) * 64;
-				w.ck_off = ck_total, ck_total += (int64_t)std::max(0, (w.max_nl - 3) / MPA_TB_BLOCK) * 9 * 64;
-				for (size_t q2 = p0; q2 < p; ++q2) T[glob_ids[q2]].tb_off = w.lite_off, T[glob_ids[q2]].bnd_off = w.ck_off;
-				ewaves.push_back(w);
-			}
-			lwave_cnt[cls] = (int)ewaves.size() - lwave_first[cls];
-		}
-	}
-	// ---- four-wave groups of the 129..256-column class (12: sorts behind class 11), two calls each; pools sized by the group's longest call
-	const int l12_first = (int)ewaves.size();
-	{
-		size_t p = n_reg_glob;
-		while (p < glob_ids.size() && T[glob_ids[p]].pad_ < 12) ++p;
-		while (p < glob_ids.size()) {
-			ExtWave w;
-			memset(&w, 0, sizeof(w));
-			for (int k = 0; k < 8; ++k) w.task[k] = -1;
-			w.rec_base = T[glob_ids[p]].rec_off;
-			const size_t p0 = p;
-			for (int k = 0; k < 2 && p < glob_ids.size(); ++k, ++p) {
-				w.task[k] = glob_ids[p];
-				w.max_nl = std::max(w.max_nl, T[glob_ids[p]].nl);
-				T[glob_ids[p]].flag |= k << MPA_LITE_SLOT_SHIFT;
-			}
-			w.lite_off = lite_total, lite_total += lite_wide_bits_dwords(w.max_nl);
-			w.ck_off = ck_total, ck_total += lite_wide_ckpt_dwords(w.max_nl);
-			for (size_t q2 = p0; q2 < p; ++q2) T[glob_ids[q2]].tb_off = w.lite_off, T[glob_ids[q2]].bnd_off = w.ck_off;
-			ewaves.push_back(w);
-		}
-	}
-	const int l12_cnt = (int)ewaves.size() - l12_first;
-	const size_t n_lite = glob_ids.size() - n_reg_glob;
-	// per-row keys of the wide extension kernels: [group][2 halves][key_stride]
-	int64_t key_stride = 0, n_wide_groups = 0;
-	for (int cls = 3; cls < kNumExtClasses; ++cls)
-		for (int k = 0; k < ewave_cnt[cls]; ++k) key_stride = std::max<int64_t>(key_stride, ewaves[ewave_first[cls] + k].max_nl), ++n_wide_groups;
-	key_stride = (key_stride + 64) & ~(int64_t)63;
-	PenTable pen;
-	if (build_pen_table(opt->ie_coef, std::max(max_nl_ext, 2), &pen) < 0) { set_error("ie_coef produces too many penalty steps"); return MPA_ERR_UNSUPPORTED; }
-
-	// ---- rounds of the traceback kernel, bounded by traceback memory
-	struct GlobRound { size_t first, last; int64_t tb_words; };
-	std::vector<GlobRound> rounds;
-	{
-		size_t p = 0;
-		while (p < n_reg_glob) {
-			GlobRound r{ p, p, 0 };
-			while (r.last < n_reg_glob) {
-				DTask &t = T[glob_ids[r.last]];
-				int64_t wds = (int64_t)t.nl * t.ncol;
-				if (r.last > r.first && (size_t)(r.tb_words + wds) * 2 > ctx->tb_budget) break;
-				t.tb_off = r.tb_words, r.tb_words += wds, ++r.last;
-			}
-			rounds.push_back(r);
-			p = r.last;
-		}
-	}
-	int64_t tb_max = 0;
-	for (auto &r : rounds) tb_max = std::max(tb_max, r.tb_words);
-
-	timing_note("  dp: classify/sort/layout", now_ms() - t_begin);
-	double t_mark = now_ms();
-	auto mark = [&](const char *what) { const double t = now_ms(); timing_note(what, t - t_mark); t_mark = t; };   // (MPA_TIMING: wall clock between marks)
-	// ---- device memory
-	const int64_t q_bytes = q->q_off[q->n_seq] - q->q_off[0];
 	int rc;
-	if ((rc = ctx->tasks.ensure(sizeof(DTask) * n)) || (rc = ctx->chunks.ensure(sizeof(PrepChunk) * (chunks.size() + 1))) ||
-	    (rc = ctx->qseq.ensure(q_bytes + 16)) || (rc = ctx->rec.ensure((size_t)rec_total * 4)) || (rc = ctx->prof.ensure((size_t)prof_total * 2 + 16)) ||
-	    (rc = ctx->waves.ensure(sizeof(ExtWave) * (ewaves.size() + 1))) || (rc = ctx->extout.ensure(sizeof(ExtOut) * n)) ||
-	    (rc = ctx->tb.ensure((size_t)tb_max * 2 + 16)) || (rc = ctx->cig.ensure((size_t)cig_total * 4 + 16)) || (rc = ctx->ncig.ensure(n * 4)) ||
-	    (rc = ctx->lite.ensure((size_t)lite_total * 4 + 256)) || (rc = ctx->ckpt.ensure((size_t)ck_total * 4 + 256)) || (rc = ctx->wlist.ensure(n_lite * 4 + 128)) ||
-	    (rc = ctx->score.ensure(n * 4)) || (rc = ctx->rowkey.ensure((size_t)(n_wide_groups * 2 * key_stride * 4 + 64))) || (rc = ctx->bnd.ensure((size_t)bnd_total * 16 + 16)) || (rc = ctx->hkey.ensure((size_t)hkey_total * 8 + 16 + (sizeof(GlobWave) + 4) * (huge_ids.size() + 1))) || (rc = ctx->list.ensure(n * 4 + 128 + sizeof(GlobWave) * (glob_ids.size() + 1))))
+	// 1. plan
+	DpPlan plan;
+	const DpPlanKnobs kn = dp_plan_knobs(ctx);
+	if ((rc = dp_plan(in, n, mi->ctg.empty() ? nullptr : &mi->ctg[0].len, sizeof(mi->ctg[0]), (int32_t)mi->ctg.size(), q, opt, kn, sizeof(DpRoundArgs), plan))) { set_error(plan.err); return rc; }
+	timing_note("  dp: classify/sort/layout", now_ms() - t_begin);
+	DpRun R{ ctx, ctx->stream, plan, kn };
+	R.t_mark = now_ms();
+	if ((rc = dp_size_pools(R)) ||                             // 2. pools and staging
+	    (rc = dp_upload_and_prep(R, mi, opt, q)) ||            // 3. uploads, memsets, prep
+	    (rc = dp_side_launches(R)) ||                          // 4. next to the round: anti-diagonal, huge, T_LITE_W4 sweep
+	    (rc = dp_tb_chunks(R)) ||                              // 5. traceback chunks with the round's launch
+	    (rc = dp_walk(R)) ||                                   // 6. walk
+	    (rc = dp_join_and_download(R)))                        // 7. join, download, the one wait
 		return rc;
-	// Everything the device needs from the host goes through ONE pinned staging buffer (sections below), so that no copy is
-	// staged by the runtime and the host never waits for one: a DP round is enqueued in one go and waited for once.
-	auto al256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
-	const size_t up_tasks = 0, up_chunks = up_tasks + al256(sizeof(DTask) * n), up_q = up_chunks + al256(sizeof(PrepChunk) * chunks.size()),
-	             up_waves = up_q + al256((size_t)q_bytes), up_list = up_waves + al256(sizeof(ExtWave) * ewaves.size()),
-	             up_gw = up_list + al256(4 * glob_ids.size()), up_units = up_gw + al256(sizeof(GlobWave) * (glob_ids.size() + 8)),
-	             up_off = up_units + al256(sizeof(DpUnit) * (4 * ewaves.size() + glob_ids.size() + 64)),
-	             up_ids = up_off + al256(8 * glob_ids.size()), up_args = up_ids + al256(4 * glob_ids.size()), up_wl = up_args + al256(sizeof(DpRoundArgs)),
-	             up_end = up_wl + al256(4 * n_lite);
-	if ((rc = ctx->h_up.ensure(up_end + 256))) return rc;
-	char *hup = ctx->h_up.as<char>();
-	memcpy(hup + up_tasks, T.data(), sizeof(DTask) * n);
-	memcpy(hup + up_chunks, chunks.data(), sizeof(PrepChunk) * chunks.size());
-	memcpy(hup + up_q, q->seqs + q->q_off[0], (size_t)q_bytes);
-	memcpy(hup + up_waves, ewaves.data(), sizeof(ExtWave) * ewaves.size());
-	mark("    dp: buffers");
-	HIP_TRY(hipMemcpyAsync(ctx->tasks.p, hup + up_tasks, sizeof(DTask) * n, hipMemcpyHostToDevice, s));
-	HIP_TRY(hipMemcpyAsync(ctx->chunks.p, hup + up_chunks, sizeof(PrepChunk) * chunks.size(), hipMemcpyHostToDevice, s));
-	HIP_TRY(hipMemcpyAsync(ctx->qseq.p, hup + up_q, q_bytes, hipMemcpyHostToDevice, s));
-	if (!ewaves.empty()) HIP_TRY(hipMemcpyAsync(ctx->waves.p, hup + up_waves, sizeof(ExtWave) * ewaves.size(), hipMemcpyHostToDevice, s));
-	// (k_prep_rows writes every row of every call; only the padding the kernels prefetch behind the last call is cleared)
-	{ const int64_t pad = max_nl + 96 + (ctx->antidiag ? 64 : 0); HIP_TRY(hipMemsetAsync((char*)ctx->rec.p + (size_t)(rec_total - pad) * 4, 0, (size_t)pad * 4, s)); }
-	if (n_wide_groups) HIP_TRY(hipMemsetAsync(ctx->rowkey.p, 0, (size_t)(n_wide_groups * 2 * key_stride * 4), s));
-	// split classes: boundary granules (16 B per row and boundary: 3 boundaries per 1024-column group, 1 per 512-column group),
-	// then the per-group completion counters and the error flag; all zero before the launch (a granule's tag is row + 1)
-	const int64_t n_split = ewave_cnt[5] + ewave_cnt[6], n_bound = 3 * (int64_t)ewave_cnt[6] + ewave_cnt[5];
-	const size_t xg_bytes = (size_t)n_bound * key_stride * 16, xg_tail = (2 * (size_t)n_split + 1) * 4;   // + done[n_split], ticket[n_split], err
-	if (n_split) {
-		if ((rc = ctx->xg.ensure(xg_bytes + xg_tail + 64))) return rc;
-		HIP_TRY(hipMemsetAsync(ctx->xg.p, 0, xg_bytes + xg_tail, s));
-	}
-	// extension calls wider than 1024 columns: keys (zeroed), then one GlobWave and one list entry per call
-	GlobWave *d_hw = nullptr;
-	int32_t *d_hlist = nullptr;
-	if (!huge_ids.empty()) {
-		HIP_TRY(hipMemsetAsync(ctx->hkey.p, 0, (size_t)hkey_total * 8, s));
-		d_hw = (GlobWave*)((char*)ctx->hkey.p + (((size_t)hkey_total * 8 + 15) & ~(size_t)15));
-		d_hlist = (int32_t*)(d_hw + huge_ids.size());
-		std::vector<GlobWave> hw(huge_ids.size());
-		for (size_t k = 0; k < huge_ids.size(); ++k) {
-			memset(&hw[k], 0, sizeof(GlobWave));
-			hw[k].task[0] = huge_ids[k], hw[k].task[1] = hw[k].task[2] = hw[k].task[3] = -1, hw[k].max_nl = T[huge_ids[k]].nl;
-		}
-		HIP_TRY(hipMemcpyAsync(d_hw, hw.data(), sizeof(GlobWave) * hw.size(), hipMemcpyHostToDevice, s));
-		HIP_TRY(hipMemcpyAsync(d_hlist, huge_ids.data(), 4 * huge_ids.size(), hipMemcpyHostToDevice, s));
-		HIP_TRY(wait_stream(ctx, s));                  // (hw is a local; the calls are rare)
-	}
-
-	DevTables tabs;
-	memcpy(tabs.aa20, tab_aa20(), 256);
-	memcpy(tabs.codon, tab_codon(), 64);
-	memcpy(tabs.mat, opt->mat, 484);
-	DpConst dc;
-	dc.go = opt->go, dc.ge = opt->ge, dc.fs = opt->fs, dc.xdrop = opt->xdrop, dc.end_bonus = opt->end_bonus;
-	for (int k = 0; k < 6; ++k) dc.sp[k] = opt->sp[k];
-	dc.sp_null_bonus = opt->sp_null_bonus;
-	dc.wide_ge = wide_ge ? 1 : 0;
-	DevGenome dg{ mi->dev[ctx->device]->seq, mi->dev[ctx->device]->ctg_off, mi->dev[ctx->device]->ctg_len, mi->dev[ctx->device]->spsc, mi->l_seq };
-
-	// ---- K3: per-row records and profiles
-	// (measured, round 4: putting these two on a high-priority stream of their own gives every DP lane a second active hardware
-	// queue, and with ten more queues in use the round kernels are time-sliced: 41 -> 72 ms per launch.  They stay in the lane's
-	// own queue; MPA_SHORT_KERNEL raises their wave priority instead.)
-	HIP_TRY(hipEventRecord(ctx->ev[0], s));
-	if (!chunks.empty())
-		hipLaunchKernelGGL(k_prep_rows, dim3((unsigned)chunks.size()), dim3(256), 0, s, dg, ctx->tasks.as<DTask>(), ctx->chunks.as<PrepChunk>(), ctx->rec.as<uint32_t>(), dc, tabs);
-	hipLaunchKernelGGL(k_prep_prof, dim3((unsigned)n), dim3(256), 0, s, ctx->tasks.as<DTask>(), ctx->qseq.as<char>(), ctx->prof.as<int16_t>(), tabs);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(ctx->ev[1], s));
-	mark("    dp: uploads + prep enqueued");
-	// ---- fork: every kernel class (extension classes and the traceback classes of the first round) gets its
-	// own stream, so the long single-wave tails of the classes overlap instead of adding up
-	HIP_TRY(hipEventRecord(ctx->fork_ev, s));
-	int n_side = 0;
-	struct Launch { int side; bool is_ext; };
-	std::vector<Launch> launches;
-	const int n_streams = mpa_ctx_s::kSide;
-	auto begin_side = [&](bool is_ext) -> hipStream_t {
-		const int k = n_side++;
-		// (side streams are created when first used: HIP deals hardware queues to streams in creation order, and sixteen idle side
-		// streams per context pushed the main streams of later contexts onto queues that other contexts' long kernels were using)
-		hipStream_t &slot = ctx->side[(k + ctx->side_off) % n_streams];
-		if (!slot && hipStreamCreateWithFlags(&slot, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); slot = nullptr; }
-		hipStream_t st = slot ? slot : s;
-		(void)hipStreamWaitEvent(st, ctx->fork_ev, 0);
-		(void)hipEventRecord(ctx->lev[2 * k], st);
-		launches.push_back(Launch{ k, is_ext });
-		return st;
-	};
-	auto end_side = [&]() { const int k = launches.back().side; hipStream_t st = ctx->side[(k + ctx->side_off) % n_streams]; (void)hipEventRecord(ctx->lev[2 * k + 1], st ? st : s); };
-
-	// ---- K1: extension calls
-	ExtArgs ea;
-	ea.tasks = ctx->tasks.as<DTask>(), ea.rec = ctx->rec.as<uint32_t>(), ea.prof = ctx->prof.as<int16_t>(), ea.out = ctx->extout.as<ExtOut>();
-	ea.c = dc, ea.pen = pen;
-	ea.lite = ctx->lite.as<uint32_t>(), ea.ckpt = ctx->ckpt.as<uint32_t>(), ea.score = ctx->score.as<int32_t>();
-	ExtWideArgs wa;
-	wa.tasks = ea.tasks, wa.rec = ea.rec, wa.prof = ea.prof, wa.out = ea.out, wa.c = dc, wa.pen = pen, wa.key_stride = key_stride;
-	wa.xg = n_split ? ctx->xg.as<unsigned long long>() : nullptr;
-	wa.done = n_split ? (int32_t*)((char*)ctx->xg.p + xg_bytes) : nullptr;
-	wa.ticket = n_split ? wa.done + n_split : nullptr;
-	wa.err = n_split ? wa.ticket + n_split : nullptr;
-	// rowkey slots follow the order of the wave descriptors (classes 3, 4, 5, 6)
-	int64_t rk_first[kNumExtClasses] = { 0 };
-	{ int64_t at = 0; for (int cls = 3; cls < kNumExtClasses; ++cls) rk_first[cls] = at, at += ewave_cnt[cls]; }
-	// every DP unit of the round goes out in ONE k_dp_round launch on the context's main stream
-	GlobArgs ga;
-	ga.tasks = ctx->tasks.as<DTask>(), ga.rec = ctx->rec.as<uint32_t>(), ga.prof = ctx->prof.as<int16_t>();
-	ga.tb = ctx->tb.as<uint16_t>(), ga.bnd = ctx->bnd.as<int4>(), ga.score = ctx->score.as<int32_t>(), ga.c = dc, ga.rowkey64 = nullptr, ga.waves = nullptr;
-	hipEvent_t ev_round0 = ctx->lev[2 * (mpa_ctx_s::kSide - 1)], ev_round1 = ctx->lev[2 * (mpa_ctx_s::kSide - 1) + 1];
-	bool round_launched = false;
-	const bool use_pool = dp_pool_enabled();
-	bool round_pending = false;                              // (worker pool) a round is armed and not yet known to be complete
-	hipStream_t round_ws = s;                                // ... and the stream its workers were launched on
-	unsigned int round_gen = 0;
-	size_t round_units = 0;
-	const DpUnit *round_unit_list = nullptr;
-	// units of the round: the extension waves/groups of every class, plus (gw_first/gw_cnt != nullptr) the traceback waves of
-	// the first traceback chunk; longest first
-	auto launch_round = [&](const int *gw_first, const int *gw_cnt, const std::vector<GlobWave> *gwv, GlobWave *d_gw) -> int {
-		struct Cost { int64_t cost; DpUnit u; };
-		std::vector<Cost> cu;
-		auto add = [&](int kind, int first, int count, int64_t cost, int blk = 0, int n_blk = 1, int sgroup = 0, int xg_first = 0) {
-			cu.push_back(Cost{ cost, DpUnit{ kind, first, count, blk, n_blk, sgroup, xg_first, 0 } });
-		};
-		// (worker pool: the one-wave kinds are units of ONE wave descriptor each, taken by single waves; without the pool a
-		// workgroup's four waves take four neighbours of the sorted list)
-		const int per_narrow = use_pool ? 1 : 4;
-		for (int cls = 0; cls < 3; ++cls)
-			for (int k = 0; k < ewave_cnt[cls] && !(cls == 1 && ctx->antidiag); k += per_narrow)
-				add(U_EXT16 + cls, ewave_first[cls] + k, std::min(per_narrow, ewave_cnt[cls] - k), (int64_t)ewaves[ewave_first[cls] + k].max_nl * 160);
-		// (worker pool: a workgroup goes on to its next unit, so all four waves must leave a unit through the same barriers -- a
-		// 65..128-column group then takes a whole workgroup on the four-wave body, its waves 2 and 3 on dead columns)
-		if (use_pool) for (int k = 0; k < ewave_cnt[3]; ++k) add(U_EXT_W4, ewave_first[3] + k, 1, (int64_t)ewaves[ewave_first[3] + k].max_nl * 270);
-		else for (int k = 0; k < ewave_cnt[3]; k += 2) add(U_EXT_W2, ewave_first[3] + k, std::min(2, ewave_cnt[3] - k), (int64_t)ewaves[ewave_first[3] + k].max_nl * 270);
-		for (int k = 0; k < ewave_cnt[4]; ++k) add(U_EXT_W4, ewave_first[4] + k, 1, (int64_t)ewaves[ewave_first[4] + k].max_nl * 270);
-		for (int k = 0; k < ewave_cnt[6]; ++k)
-			for (int b = 0; b < 4; ++b) add(U_EXT_SPLIT, ewave_first[6] + k, 1, (int64_t)ewaves[ewave_first[6] + k].max_nl * 310, b, 4, k, 3 * k);
-		for (int k = 0; k < ewave_cnt[5]; ++k)
-			for (int b = 0; b < 2; ++b) add(U_EXT_SPLIT, ewave_first[5] + k, 1, (int64_t)ewaves[ewave_first[5] + k].max_nl * 310, b, 2, ewave_cnt[6] + k, 3 * ewave_cnt[6] + k);
-		for (int k = 0; k < dwave_cnt; k += per_narrow)              // 65..128-column extension calls, one per wave
-			add(U_EXT128, dwave_first + k, std::min(per_narrow, dwave_cnt - k), (int64_t)ewaves[dwave_first + k].max_nl * 200);
-		for (int cls = 0; cls < 4; ++cls)                            // the packed sweeps of the checkpointed traceback
-			for (int k = 0; k < lwave_cnt[cls]; k += per_narrow)
-				add(U_LITE16 + cls, lwave_first[cls] + k, std::min(per_narrow, lwave_cnt[cls] - k), (int64_t)ewaves[lwave_first[cls] + k].max_nl * (cls == 3 ? 200 : 170));
-		if (gw_first) {
-			static const int kind_of[8] = { U_GLOB16, U_GLOB32, U_GLOB64, U_GLOB_W2, U_GLOB_W4, -1, -1, U_GLOB_MB };
-			for (int cls = 0; cls < 8; ++cls) {
-				if (kind_of[cls] < 0) continue;
-				const int per = cls == 3 ? (use_pool ? 1 : 2) : cls == 4 ? 1 : per_narrow;
-				for (int k = 0; k < gw_cnt[cls]; k += per) {
-					const GlobWave &g = (*gwv)[gw_first[cls] + k];
-					int64_t cost = (int64_t)g.max_nl * (cls >= 3 && cls <= 4 ? 510 : 430);
-					if (cls == 7) cost *= (T[g.task[0]].ncol + 63) / 64;
-					add(cls == 3 && use_pool ? (int)U_GLOB_W4 : kind_of[cls], gw_first[cls] + k, std::min(per, gw_cnt[cls] - k), cost);
-				}
-			}
-		}
-		if (cu.empty()) return MPA_OK;
-		std::stable_sort(cu.begin(), cu.end(), [](const Cost &x, const Cost &y) { return x.cost > y.cost; });   // (stable: the workgroups of a split group stay adjacent, in column order)
-		static const bool show_top = [] { const char *e = getenv("MPA_DP_TOP"); return e && atoi(e) != 0; }();
-		if (show_top) {                                       // (measurement) what bounds the round: the costliest units by kind
-			// (the four-wave groups of the 129..256-column checkpointed class run next to the round, in k_lite_wide: listed here by
-			// the same cost model, as kind U_LITE_W4, so that the longest unit of the traceback round is seen whichever kernel sweeps it)
-			std::vector<Cost> shown = cu;
-			for (int k = 0; k < l12_cnt; ++k) shown.push_back(Cost{ (int64_t)ewaves[l12_first + k].max_nl * 280, DpUnit{ U_LITE_W4, l12_first + k, 1, 0, 1, 0, 0, 0 } });
-			std::stable_sort(shown.begin(), shown.end(), [](const Cost &x, const Cost &y) { return x.cost > y.cost; });
-			int64_t by_kind[U_KIND_COUNT] = { 0 }, n_kind[U_KIND_COUNT] = { 0 };
-			for (const Cost &c : shown) by_kind[c.u.kind] += c.cost, ++n_kind[c.u.kind];
-			fprintf(stderr, "[mpa-dp-top] units %zu; longest:", shown.size());
-			for (size_t k = 0; k < shown.size() && k < 6; ++k) fprintf(stderr, " kind %d %.1f ms;", shown[k].u.kind, shown[k].cost * 1e-6);
-			fprintf(stderr, " | wave-ms by kind:");
-			for (int k = 0; k < U_KIND_COUNT; ++k) if (n_kind[k]) fprintf(stderr, " %d: %ld units %.0f ms;", k, (long)n_kind[k], by_kind[k] * 1e-6);
-			fprintf(stderr, "\n");
-		}
-		// worker pool: the units that take a whole workgroup first (queue 0), then the one-wave units (queue 1), each longest first;
-		// priorities stay relative to the round's longest unit of either kind
-		const int64_t cost_max = cu[0].cost;
-		size_t n_group_units = 0;
-		if (use_pool) {
-			auto is_group = [](const Cost &c) { return c.u.kind == U_EXT_W4 || c.u.kind == U_EXT_SPLIT || c.u.kind == U_GLOB_W4; };
-			std::stable_partition(cu.begin(), cu.end(), is_group);
-			for (const Cost &c : cu) n_group_units += is_group(c);
-		}
-		DpUnit *units = (DpUnit*)(hup + up_units);          // (pinned: the copy below needs no wait)
-		const size_t n_units = cu.size();
-		if (sizeof(DpUnit) * n_units > up_off - up_units) { set_error("internal: more DP units than the staging buffer holds"); return MPA_ERR_HIP; }
-		// the units that bound the round's duration issue ahead of the short ones they share a SIMD with (s_setprio in k_dp_round)
-		for (size_t k = 0; k < cu.size(); ++k) {
-			units[k] = cu[k].u;
-			units[k].pad_ = cu[k].cost * 2 >= cost_max ? 3 : cu[k].cost * 4 >= cost_max ? 2 : cu[k].cost * 10 >= cost_max ? 1 : 0;
-			static const bool unit_prio = [] { const char *e = getenv("MPA_DP_PRIO"); return !e || atoi(e) != 0; }();   // (MPA_DP_PRIO=0: measurement)
-			if (!unit_prio) units[k].pad_ = 0;
-		}
-		int rc2;
-		if ((rc2 = ctx->units.ensure(n_units * sizeof(DpUnit)))) return rc2;
-		HIP_TRY(hipMemcpyAsync(ctx->units.p, units, n_units * sizeof(DpUnit), hipMemcpyHostToDevice, s));
-		ea.waves = ctx->waves.as<ExtWave>();
-		wa.waves = ctx->waves.as<ExtWave>();                // absolute descriptor indices: the rowkey slot of group g is g - first wide group
-		wa.rowkey = ctx->rowkey.as<uint32_t>() - (int64_t)ewave_first[3] * 2 * key_stride;
-		ga.waves = d_gw;
-		// Workgroups of the round kernel per CU, enforced through the LDS it asks for (MPA_DP_WG_PER_CU, default 3).  Round 6: the
-		// kernel takes 124 VGPRs (the asm rows of ext_narrow keep the whole DP state of eight calls in registers and nothing is
-		// spilled), so three workgroups hold 372 of each SIMD's 512 registers -- what four workgroups of the 95-register kernel of
-		// rounds 4-5 held (384) -- and the seeding kernels of the next batches stay co-resident.  One more workgroup than wanted must
-		// NOT fit; what is left of the LDS stays free for the seeding kernels.
-		static const size_t round_lds = [] {
-			const char *e = getenv("MPA_DP_WG_PER_CU");
-			int want = e ? atoi(e) : 3;
-			if (want < 1) want = 1;
-			if (want > 4) want = 4;
-			const size_t pad = (((size_t)160 * 1024 / (want + 1)) + 256) & ~(size_t)255;
-			return pad > DP_ROUND_LDS ? pad : DP_ROUND_LDS;
-		}();
-		if (use_pool) {
-			// the round's arguments and units into the lane's slot of the device's pool, the slot armed in stream order behind
-			// everything the round reads, the lane's workers on the worker stream (a worker takes any lane's units: this stream is
-			// never waited for by a round -- a round is complete when its last unit says so in pinned memory)
-			if ((rc2 = pool_attach(ctx))) return rc2;
-			mpa_ctx_s *root = ctx->root ? ctx->root : ctx;
-			DpPool *pool = root->dp_pool;
-			int n_slots;
-			{ std::lock_guard<std::mutex> g(root->pool_mu); n_slots = root->pool_slots; }
-			DpRoundArgs *ha = (DpRoundArgs*)(hup + up_args);
-			ha->ea = ea, ha->wa = wa, ha->ga = ga, ha->units = ctx->units.as<DpUnit>(), ha->n_group = (int32_t)n_group_units, ha->pad_ = 0;
-			HIP_TRY(hipMemcpyAsync(&pool->args[ctx->dp_slot], ha, sizeof(DpRoundArgs), hipMemcpyHostToDevice, s));
-			long long *d_trace = nullptr;
-			if (dp_trace_path()) {
-				if ((rc2 = ctx->dp_trace.ensure(n_units * 16))) return rc2;
-				HIP_TRY(hipMemsetAsync(ctx->dp_trace.p, 0, n_units * 16, s));
-				d_trace = ctx->dp_trace.as<long long>();
-			}
-			round_gen = ++ctx->dp_gen;
-			hipLaunchKernelGGL(k_dp_arm, dim3(1), dim3(1), 0, s, pool, ctx->dp_slot, (int)n_group_units, (int)(n_units - n_group_units), round_gen, ctx->dp_done, d_trace);
-			HIP_TRY(hipGetLastError());
-			// The workers go out on the lane's own stream (what follows the round on that stream then also waits for this launch's
-			// workers to run out of units of ANY lane; measured level with a stream of their own, 19.6 against 19.7 M residues/s).
-			// MPA_DP_WORKER_STREAM=1: a worker stream per lane -- one more stream per lane for HIP to deal hardware queues to, and
-			// when that stream lands on a queue another context's long kernels use, every round waits for them (the evidence run of
-			// round 5 measured 6.5 M residues/s that way: profiles/r05_experiments.txt).
-			static const bool own_stream = [] { const char *e = getenv("MPA_DP_WORKER_STREAM"); return e && atoi(e) != 0; }();
-			hipStream_t ws = own_stream ? ctx->worker_stream : s;
-			if (own_stream) {
-				HIP_TRY(hipEventRecord(ctx->arm_ev, s));
-				HIP_TRY(hipStreamWaitEvent(ws, ctx->arm_ev, 0));
-			}
-			mpa_ctx_s::WorkerLaunch wl;
-			if (!ctx->wl_free.empty()) wl = ctx->wl_free.back(), ctx->wl_free.pop_back();
-			else { HIP_TRY(hipEventCreate(&wl.e0)); HIP_TRY(hipEventCreate(&wl.e1)); }
-			HIP_TRY(ensure_dynamic_lds((const void*)k_dp_worker, ctx->device, round_lds));
-			static const int launch_cap = [] { const char *e = getenv("MPA_DP_LAUNCH_WORKERS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : dp_pool_budget(); }();
-			// a workgroup serves one workgroup unit at a time, or four one-wave units side by side
-			const unsigned grid = (unsigned)std::min<size_t>(n_group_units + (n_units - n_group_units + 3) / 4, (size_t)launch_cap);
-			HIP_TRY(hipEventRecord(wl.e0, ws));
-			hipLaunchKernelGGL(k_dp_worker, dim3(grid), dim3(256), round_lds, ws, pool, ctx->dp_slot, n_slots);
-			HIP_TRY(hipGetLastError());
-			HIP_TRY(hipEventRecord(wl.e1, ws));
-			ctx->wl_busy.push_back(wl);
-			round_pending = true, round_units = n_units, round_unit_list = units;
-		} else {
-			if (round_lds > 48 * 1024) HIP_TRY(ensure_dynamic_lds((const void*)k_dp_round, ctx->device, round_lds));
-			HIP_TRY(hipEventRecord(ev_round0, s));
-			hipLaunchKernelGGL(k_dp_round, dim3((unsigned)n_units), dim3(256), round_lds, s, ea, wa, ga, ctx->units.as<DpUnit>());
-			HIP_TRY(hipGetLastError());
-			HIP_TRY(hipEventRecord(ev_round1, s));
-		}
-		round_launched = true;
-		ctx->stats.launches_ext++;
-		return MPA_OK;
-	};
-	// worker pool: the round is complete when the last of its units has stored the round's generation into the lane's pinned word
-	auto wait_round = [&]() -> int {
-		if (!round_pending) return MPA_OK;
-		volatile int32_t *d = ctx->dp_done;
-		const double t0 = now_ms();
-		for (int polls = 0; (unsigned int)*d != round_gen; ++polls) {
-			if (polls >= 8) { struct timespec ts = { 0, 100000L }; nanosleep(&ts, nullptr); }
-			if ((polls & 1023) == 1023) {
-				if (now_ms() - t0 > 120000.0) { set_error("DP worker pool: a round did not complete within two minutes"); return MPA_ERR_HIP; }
-				const hipError_t e = hipStreamQuery(round_ws);                     // (a fault in a worker kernel shows up here, not in the word)
-				if (e != hipSuccess && e != hipErrorNotReady) { set_error(std::string("DP worker launch: ") + hipGetErrorString(e)); return MPA_ERR_HIP; }
-			}
-		}
-		round_pending = false;
-		hipLaunchKernelGGL(k_l2_writeback, dim3(128), dim3(64), 0, s);       // the units' results out of the L2s, before anything enqueued behind reads them
-		HIP_TRY(hipGetLastError());
-		if (const char *path = dp_trace_path()) {                             // (debug) one line per unit: who ran when
-			std::vector<long long> tr(2 * round_units);
-			HIP_TRY(hipMemcpy(tr.data(), ctx->dp_trace.p, round_units * 16, hipMemcpyDeviceToHost));
-			static std::mutex tmu;
-			std::lock_guard<std::mutex> g(tmu);
-			if (FILE *f = fopen(path, "a")) {
-				for (size_t k = 0; k < round_units; ++k)
-					fprintf(f, "%d\t%u\t%zu\t%d\t%d\t%lld\t%lld\n", ctx->dp_slot, round_gen, k, round_unit_list[k].kind, round_unit_list[k].pad_, tr[2 * k], tr[2 * k + 1]);
-				fclose(f);
-			}
-		}
-		return MPA_OK;
-	};
-	if (ctx->antidiag && ewave_cnt[1] > 0) {                           // (measurement) the 32-column class on the anti-diagonal prototype, one wave per block
-		ea.waves = ctx->waves.as<ExtWave>();
-		hipStream_t st = begin_side(true);
-		hipLaunchKernelGGL(k_ext_antidiag, dim3((unsigned)ewave_cnt[1]), dim3(64), EXT_ANTIDIAG_LDS, st, ea, ewave_first[1]);
-		HIP_TRY(hipGetLastError());
-		end_side();
-		ctx->stats.launches_ext++;
-	}
-	if (!huge_ids.empty()) {                                           // block-major sweep with the traceback kernel's arithmetic, then the replay
-		GlobArgs ha;
-		ha.tasks = ctx->tasks.as<DTask>(), ha.waves = d_hw, ha.rec = ctx->rec.as<uint32_t>(), ha.prof = ctx->prof.as<int16_t>();
-		ha.tb = nullptr, ha.bnd = ctx->bnd.as<int4>(), ha.score = nullptr, ha.c = dc, ha.rowkey64 = ctx->hkey.as<unsigned long long>();
-		hipStream_t st = begin_side(true);
-		if (wide_ge) hipLaunchKernelGGL(k_ext_huge<true>, dim3((unsigned)huge_ids.size()), dim3(64), (size_t)22 * 64 * 2 + 4 * 32 * 4, st, ha);
-		else hipLaunchKernelGGL(k_ext_huge<false>, dim3((unsigned)huge_ids.size()), dim3(64), (size_t)22 * 64 * 2 + 4 * 32 * 4, st, ha);
-		HIP_TRY(hipGetLastError());
-		hipLaunchKernelGGL(k_ext_replay, dim3((unsigned)huge_ids.size()), dim3(64), 0, st, ctx->tasks.as<DTask>(), d_hlist, (int32_t)huge_ids.size(),
-		                   ctx->hkey.as<unsigned long long>(), ctx->extout.as<ExtOut>(), dc, pen);
-		HIP_TRY(hipGetLastError());
-		end_side();
-		ctx->stats.launches_ext++;
-	}
-
-	// the packed sweep of the 129..256-column checkpointed class (unit kind U_LITE_W4): a 256-thread launch of its own next to the
-	// round, on a side stream (at most two are taken at this point, by the launches above); the walk below waits for it
-	int l12_side = -1;
-	if (l12_cnt > 0) {
-		ea.waves = ctx->waves.as<ExtWave>();
-		hipStream_t st = begin_side(false);
-		hipLaunchKernelGGL(k_lite_wide, dim3((unsigned)l12_cnt), dim3(MPA_LITE_WIDE_WAVES * 64), 0, st, ea, l12_first);
-		HIP_TRY(hipGetLastError());
-		end_side(), l12_side = launches.back().side;
-		ctx->stats.launches_glob++;
-	}
-
-	// ---- K2 + traceback walk
-	float ms_glob = 0, ms_bt = 0;
-	bool glob_timed = false;
-	std::vector<GlobWave> gwaves;
-	std::vector<int32_t> glist;
-	for (size_t ri = 0; ri < rounds.size(); ++ri) {
-		auto &r = rounds[ri];
-		if (r.last == r.first) continue;
-		const bool concurrent = ri == 0;                                  // later rounds reuse the traceback buffer: serial
-		gwaves.clear(), glist.clear();
-		const int kNumGlobClasses = 8;
-		int cnt[kNumGlobClasses] = { 0 }, first[kNumGlobClasses] = { 0 };
-		size_t p = r.first;
-		for (int cls = 0; cls < kNumGlobClasses; ++cls) {
-			const int per = cls == 0 ? 4 : cls == 1 ? 2 : 1;
-			first[cls] = (int)gwaves.size();
-			while (p < r.last && T[glob_ids[p]].pad_ == cls) {
-				GlobWave w;
-				memset(&w, 0, sizeof(w));
-				for (int k = 0; k < 4; ++k) w.task[k] = -1;
-				for (int k = 0; k < per && p < r.last && T[glob_ids[p]].pad_ == cls; ++k, ++p) {
-					w.task[k] = glob_ids[p];
-					w.max_nl = std::max(w.max_nl, T[glob_ids[p]].nl);
-					glist.push_back(glob_ids[p]);
-				}
-				gwaves.push_back(w);
-			}
-			cnt[cls] = (int)gwaves.size() - first[cls];
-		}
-		if (!concurrent) {                                                // join everything before the buffers (and their staging) are reused
-			for (auto &l : launches) (void)hipStreamWaitEvent(s, ctx->lev[2 * l.side + 1], 0);
-			HIP_TRY(wait_stream(ctx, s));
-			float a = 0, b = 0;                                              // (the previous chunk's sweep and walk)
-			(void)hipEventElapsedTime(&a, ctx->ev[3], ctx->ev[4]);
-			(void)hipEventElapsedTime(&b, ctx->ev[4], ctx->ev[5]);
-			ms_glob += a, ms_bt += b;
-		}
-		int32_t *d_list = ctx->list.as<int32_t>();
-		GlobWave *d_gw = (GlobWave*)((char*)ctx->list.p + (((size_t)n * 4 + 63) & ~(size_t)63));
-		memcpy(hup + up_list, glist.data(), glist.size() * 4);
-		memcpy(hup + up_gw, gwaves.data(), gwaves.size() * sizeof(GlobWave));
-		HIP_TRY(hipMemcpyAsync(d_list, hup + up_list, glist.size() * 4, hipMemcpyHostToDevice, s));
-		HIP_TRY(hipMemcpyAsync(d_gw, hup + up_gw, gwaves.size() * sizeof(GlobWave), hipMemcpyHostToDevice, s));
-		mark("    dp: traceback lists enqueued");
-		ga.tb = ctx->tb.as<uint16_t>();
-		// classes 0,1,2,7 share one launch ("narrow"); every wide class has its own
-		auto launch_glob_class = [&](int cls, hipStream_t st) -> hipError_t {
-			if (cls < 0) { ga.waves = d_gw; return launch_glob_narrow(ga, first, cnt, st, wide_ge); }
-			ga.waves = d_gw + first[cls];
-			switch (cls) {
-			case 3: return launch_glob_wide<2>(ga, cnt[cls], st, wide_ge);
-			case 4: return launch_glob_wide<4>(ga, cnt[cls], st, wide_ge);
-			case 5: return launch_glob_wide<8>(ga, cnt[cls], st, wide_ge);
-			default: return launch_glob_wide<16>(ga, cnt[cls], st, wide_ge);
-			}
-		};
-		HIP_TRY(hipEventRecord(ctx->ev[3], s));
-		// every launch on its own stream (next to the extension classes in the first round); the walk needs them all
-		HIP_TRY(hipEventRecord(ctx->fork_ev, s));
-		const size_t first_glob_launch = launches.size();
-		const bool in_round = ri == 0 && !wide_ge;           // the first chunk's calls ride in the round's one launch
-		const int order[5] = { 6, 5, 4, 3, -1 };
-		for (int oi = 0; oi < 5; ++oi) {
-			const int cls = order[oi];
-			if (in_round && cls < 5) continue;                               // (only the 512/1024-thread traceback classes keep their own launch)
-			if (cls >= 0 ? !cnt[cls] : !(cnt[0] + cnt[1] + cnt[2] + cnt[7])) continue;
-			if (n_side >= mpa_ctx_s::kSide - 1) {                            // out of side streams (the last event pair times the round's launch): main stream
-				HIP_TRY(launch_glob_class(cls, s));
-			} else {
-				hipStream_t st = begin_side(false);
-				HIP_TRY(launch_glob_class(cls, st));
-				end_side();
-			}
-			ctx->stats.launches_glob++;
-		}
-		if (in_round) {                                        // (behind the 512/1024-thread classes' own launches: with the worker pool the host waits here)
-			if ((rc = launch_round(first, cnt, &gwaves, d_gw)) != MPA_OK) return rc;
-			ctx->stats.launches_glob++;
-			mark("    dp: units up, round launched");
-			if ((rc = wait_round()) != MPA_OK) return rc;
-			if (use_pool) mark("    dp: round (units done)");
-		}
-		for (size_t k = first_glob_launch; k < launches.size(); ++k) (void)hipStreamWaitEvent(s, ctx->lev[2 * launches[k].side + 1], 0);
-		HIP_TRY(hipEventRecord(ctx->ev[4], s));
-		hipLaunchKernelGGL(k_backtrack, dim3((unsigned)glist.size()), dim3(64), 0, s, ctx->tasks.as<DTask>(), d_list, (int32_t)glist.size(),
-		                   ctx->tb.as<uint16_t>(), ctx->cig.as<uint32_t>(), ctx->ncig.as<int32_t>());
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipEventRecord(ctx->ev[5], s));
-		glob_timed = true;                                                // (ev[3..5] are read after the next wait)
-	}
-	if (!round_launched) {
-		if ((rc = launch_round(nullptr, nullptr, nullptr, nullptr)) != MPA_OK) return rc;
-		mark("    dp: (round without traceback launched)");
-		if ((rc = wait_round()) != MPA_OK) return rc;
-		if (use_pool) mark("    dp: round (units done)");
-	}
-	// ---- the walk of the checkpointed traceback: behind the round that swept its calls
-	if (n_lite) {
-		memcpy(hup + up_wl, glob_ids.data() + n_reg_glob, 4 * n_lite);
-		HIP_TRY(hipMemcpyAsync(ctx->wlist.p, hup + up_wl, 4 * n_lite, hipMemcpyHostToDevice, s));
-		WalkArgs wk;
-		wk.ga = ga, wk.ga.waves = nullptr, wk.list = ctx->wlist.as<int32_t>(), wk.n_list = (int32_t)n_lite;
-		wk.lite = ctx->lite.as<uint32_t>(), wk.ckpt = ctx->ckpt.as<uint32_t>(), wk.cig = ctx->cig.as<uint32_t>(), wk.n_cigar = ctx->ncig.as<int32_t>();
-		wk.n_blocks = (unsigned long long*)((char*)ctx->wlist.p + ((n_lite * 4 + 63) & ~(size_t)63));
-		HIP_TRY(hipMemsetAsync(wk.n_blocks, 0, 8, s));
-		// (the list is sorted by class: one launch per class, with the LDS that class's block of direction words needs)
-		size_t at = 0;
-		for (int cls = 0; cls < 5; ++cls) {
-			size_t n_c = 0;
-			while (at + n_c < n_lite && T[glob_ids[n_reg_glob + at + n_c]].pad_ == 8 + cls) ++n_c;
-			if (n_c == 0) continue;
-			wk.list = ctx->wlist.as<int32_t>() + at, wk.n_list = (int32_t)n_c;
-			if (cls == 4) {                                                    // 129..256 columns: behind their own sweep; more LDS than a launch gets unasked
-				if (l12_side >= 0) (void)hipStreamWaitEvent(s, ctx->lev[2 * l12_side + 1], 0);
-				HIP_TRY(ensure_dynamic_lds((const void*)k_walk, ctx->device, WALK_LDS(256)));
-			}
-			hipLaunchKernelGGL(k_walk, dim3((unsigned)n_c), dim3(64), cls == 0 ? WALK_LDS(16) : cls == 1 ? WALK_LDS(32) : cls == 2 ? WALK_LDS(64) : cls == 3 ? WALK_LDS(128) : WALK_LDS(256), s, wk);
-			at += n_c;
-		}
-		HIP_TRY(hipGetLastError());
-		ctx->stats.launches_glob++;
-	}
-	// ---- join
-	for (auto &l : launches) (void)hipStreamWaitEvent(s, ctx->lev[2 * l.side + 1], 0);
-	HIP_TRY(hipEventRecord(ctx->ev[2], s));
-	// results into pinned memory behind the last kernel: extension outputs, traceback scores and CIGAR lengths, hand-off error flag
-	const size_t dn_eo = 0, dn_sc = dn_eo + al256(sizeof(ExtOut) * n), dn_nc = dn_sc + al256(4 * n), dn_err = dn_nc + al256(4 * n), dn_wb = dn_err + 256, dn_end = dn_wb + 256;
-	if ((rc = ctx->h_down.ensure(dn_end))) return rc;
-	char *hdn = ctx->h_down.as<char>();
-	*(int32_t*)(hdn + dn_err) = 0;
-	if (!ext_ids.empty()) HIP_TRY(hipMemcpyAsync(hdn + dn_eo, ctx->extout.p, sizeof(ExtOut) * n, hipMemcpyDeviceToHost, s));
-	if (!glob_ids.empty()) {
-		HIP_TRY(hipMemcpyAsync(hdn + dn_sc, ctx->score.p, n * 4, hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipMemcpyAsync(hdn + dn_nc, ctx->ncig.p, n * 4, hipMemcpyDeviceToHost, s));
-	}
-	if (n_split) HIP_TRY(hipMemcpyAsync(hdn + dn_err, wa.err, 4, hipMemcpyDeviceToHost, s));
-	*(unsigned long long*)(hdn + dn_wb) = 0;
-	if (n_lite) HIP_TRY(hipMemcpyAsync(hdn + dn_wb, (char*)ctx->wlist.p + ((n_lite * 4 + 63) & ~(size_t)63), 8, hipMemcpyDeviceToHost, s));
-	mark("    dp: round enqueued");
-	HIP_TRY(wait_stream(ctx, s));
-	mark("    dp: round (wait)");
-	if (glob_timed) {
-		float a = 0, b = 0;
-		(void)hipEventElapsedTime(&a, ctx->ev[3], ctx->ev[4]);
-		(void)hipEventElapsedTime(&b, ctx->ev[4], ctx->ev[5]);
-		ms_glob += a, ms_bt += b;
-	}
-	float ms_ext_sum = 0;                                                 // sum of the per-launch durations of the extension kernels
-	if (round_launched && !use_pool) {
-		(void)hipEventElapsedTime(&ms_ext_sum, ev_round0, ev_round1);
-		ctx->stats.ms_round = ms_ext_sum, ctx->stats.launches_round = 1;
-	}
-	if (use_pool) pool_harvest(ctx, false);                             // (worker launches that have ended: into the context's totals)
-	for (auto &l : launches) {
-		float ms = 0;
-		(void)hipEventElapsedTime(&ms, ctx->lev[2 * l.side], ctx->lev[2 * l.side + 1]);
-		if (l.is_ext) ms_ext_sum += ms;
-		else if (l.side == l12_side) ms_glob += ms;                      // (the 129..256-column packed sweep: a traceback sweep like the chunks')
-	}
-
 	// a boundary hand-off that never arrived (bounded spin in the kernel): the producer workgroup was running (it drew its
 	// ticket first) but made no progress for seconds -- a stalled hardware queue under oversubscription.  Nothing of this round
 	// has been handed to the caller yet: mpa_dp_run() repeats it with those calls on the one-wave path (k_ext_huge, same bits).
 	static const bool test_fail = [] { const char *e = getenv("MPA_TEST_HANDOFF_FAIL"); return e && atoi(e) != 0; }();
-	if (*(const int32_t*)(hdn + dn_err) || (test_fail && n_split && !ctx->no_split)) {
+	if (*(const int32_t*)(R.hdn + plan.dn.err) || (test_fail && plan.n_split && !ctx->no_split)) {
 		set_error("k_ext_wide_split: a column-block hand-off between workgroups timed out"); return MPA_RETRY_NO_SPLIT;
 	}
 	timing_note("  dp: upload+kernels (wall)", now_ms() - t_begin);
 	const double t_res = now_ms();
-	// ---- results
-	const ExtOut *eo = (const ExtOut*)(hdn + dn_eo);
-	const int32_t *sc = (const int32_t*)(hdn + dn_sc), *nc = (const int32_t*)(hdn + dn_nc);
-	int64_t pool_n = 0;
-	int64_t *dense_off = (int64_t*)(hup + up_off);                        // (the staging buffer's earlier sections have been consumed)
-	for (size_t g = 0; g < glob_ids.size(); ++g) dense_off[g] = pool_n, pool_n += nc[glob_ids[g]];
-	uint32_t *pool = (uint32_t*)malloc((size_t)(pool_n > 0 ? pool_n : 1) * 4);
-	if (pool_n > 0) {
-		// the slots were sized for the worst case (nl+al+4 words each): gather the real CIGARs into a dense pool on the
-		// device and copy only that over PCIe
-		int rc2;
-		if ((rc2 = ctx->cigd.ensure((size_t)pool_n * 4)) || (rc2 = ctx->cigoff.ensure(glob_ids.size() * 12 + 64)) || (rc2 = ctx->h_pool.ensure((size_t)pool_n * 4))) { free(pool); return rc2; }
-		int64_t *d_off = ctx->cigoff.as<int64_t>();
-		int32_t *d_ids = (int32_t*)(d_off + glob_ids.size());
-		memcpy(hup + up_ids, glob_ids.data(), glob_ids.size() * 4);
-		HIP_TRY(hipMemcpyAsync(d_off, dense_off, glob_ids.size() * 8, hipMemcpyHostToDevice, s));
-		HIP_TRY(hipMemcpyAsync(d_ids, hup + up_ids, glob_ids.size() * 4, hipMemcpyHostToDevice, s));
-		hipLaunchKernelGGL(k_cigar_gather, dim3((unsigned)glob_ids.size()), dim3(64), 0, s, ctx->tasks.as<DTask>(), d_ids, d_off, (int32_t)glob_ids.size(),
-		                   ctx->ncig.as<int32_t>(), ctx->cig.as<uint32_t>(), ctx->cigd.as<uint32_t>());
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(ctx->h_pool.p, ctx->cigd.p, (size_t)pool_n * 4, hipMemcpyDeviceToHost, s));
-		HIP_TRY(wait_stream(ctx, s));
-		memcpy(pool, ctx->h_pool.p, (size_t)pool_n * 4);
-	}
-	{
-		size_t g = 0;
-		std::vector<int64_t> off_of(n, 0);
-		for (size_t k = 0; k < glob_ids.size(); ++k) off_of[glob_ids[k]] = dense_off[k];
-		(void)g;
-		for (int64_t k = 0; k < n; ++k) {
-			const DTask &t = T[k];
-			mpa_dp_rst_t &o = rst[k];
-			if (t.flag & (MPA_F_EXT_LEFT | MPA_F_EXT_RIGHT)) {
-				o.nt_len = eo[k].nt_len, o.aa_len = eo[k].aa_len, o.score = eo[k].score, o.n_cigar = 0, o.cigar_off = 0;
-			} else {
-				o.nt_len = t.nl, o.aa_len = t.al, o.score = sc[k], o.n_cigar = nc[k], o.cigar_off = off_of[k];
-			}
-		}
-	}
+	if ((rc = dp_assemble(R, rst, cigar_pool, n_pool))) return rc;   // 8. CIGAR gather, results
 	timing_note("  dp: download+assemble", now_ms() - t_res);
-	if (cigar_pool) *cigar_pool = pool; else free(pool);
-	if (n_pool) *n_pool = pool_n;
-
-	// ---- statistics (cells = (nl-2) * 8*ceil(al/8); algorithmic bytes per call)
-	mpa_dp_stats_t &st = ctx->stats;
-	for (int32_t id : ext_ids) {
-		const DTask &t = T[id];
-		if (round_launched && t.pad_ != 7) st.cells_ext_round += (int64_t)std::max(0, t.nl - 2) * t.ncol;
-		st.n_ext++, st.cells_ext += (int64_t)std::max(0, t.nl - 2) * t.ncol;
-		st.alg_bytes_ext += (t.nl + 1) / 2 + t.al + 12;
-	}
-	for (size_t gi = 0; gi < glob_ids.size(); ++gi) {
-		const int32_t id = glob_ids[gi];
-		const DTask &t = T[id];
-		const int64_t cells = (int64_t)std::max(0, t.nl - 2) * t.ncol;
-		// (the first traceback chunk rides in the round's launch, except the 512/1024-thread classes)
-		if (round_launched && ((!rounds.empty() && gi < rounds[0].last && t.pad_ != 5 && t.pad_ != 6) || gi >= n_reg_glob)) st.cells_glob_round += cells;
-		st.n_glob++, st.cells_glob += cells;
-		if (gi >= n_reg_glob) { if (t.pad_ == 12) st.n_ckpt_wide++, st.cells_ckpt_wide += cells; else st.n_ckpt++, st.cells_ckpt += cells; }
-		st.alg_bytes_glob += (t.nl + 1) / 2 + t.al + 12 + 2 * cells + 2 * ((int64_t)t.nl + t.al) + 4 * (int64_t)nc[id];
-	}
-	st.rows_prep = rec_total;
-	st.walk_blocks = (int64_t)*(const unsigned long long*)(hdn + dn_wb);
-	float ms = 0;
-	(void)hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); st.ms_prep = ms;
-	st.ms_ext = ms_ext_sum;
-	st.ms_glob = ms_glob, st.ms_backtrack = ms_bt;
-	timing_note("    dp: GPU prep kernels", st.ms_prep);
-	timing_note("    dp: GPU round kernel", ctx->stats.ms_round);
-	timing_note("    dp: GPU walk", ms_bt);
-	{ float w = 0; (void)hipEventElapsedTime(&w, ctx->ev[0], ctx->ev[2]); st.ms_total = w; }   // wall time of the whole batch on the device
-	{
-		mpa_dp_stats_t &t = ctx->total;
-		t.n_ext += st.n_ext, t.n_glob += st.n_glob, t.cells_ext += st.cells_ext, t.cells_glob += st.cells_glob, t.rows_prep += st.rows_prep;
-		t.alg_bytes_ext += st.alg_bytes_ext, t.alg_bytes_glob += st.alg_bytes_glob;
-		t.n_ckpt += st.n_ckpt, t.cells_ckpt += st.cells_ckpt, t.walk_blocks += st.walk_blocks;
-		t.n_ckpt_wide += st.n_ckpt_wide, t.cells_ckpt_wide += st.cells_ckpt_wide;
-		t.ms_prep += st.ms_prep, t.ms_ext += st.ms_ext, t.ms_glob += st.ms_glob, t.ms_backtrack += st.ms_backtrack, t.ms_total += st.ms_total;
-		t.launches_ext += st.launches_ext, t.launches_glob += st.launches_glob;
-		t.cells_ext_round += st.cells_ext_round, t.cells_glob_round += st.cells_glob_round, t.ms_round += st.ms_round, t.launches_round += st.launches_round;
-	}
+	dp_statistics(R);                                           // 9.
 	return MPA_OK;
 }
 
@@ -2732,6 +2461,21 @@ int mpa_dp_run(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *opt, cons
 
 int64_t mpa_dp_handoff_retries(const mpa_ctx_t *ctx) { return ctx ? ctx->handoff_retries : 0; }
 void mpa_dbg_antidiag(mpa_ctx_t *ctx, int on) { if (ctx) ctx->antidiag = on != 0; }
+int64_t mpa_dbg_dp_plan(const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, int32_t n_seq, const int64_t *q_off, int64_t n, const mpa_dp_task_t *tasks,
+                        const int64_t *knobs, void *buf, int64_t cap)
+{
+	return mpa::guarded<int64_t>(MPA_ERR_HIP, [&]() -> int64_t {
+		DpPlanKnobs kn;
+		kn.lite_min = (int32_t)knobs[0], kn.lite_wide = (int32_t)knobs[1], kn.no_split = (int32_t)knobs[2], kn.antidiag = (int32_t)knobs[3], kn.pool = (int32_t)knobs[4];
+		kn.ext_dual = (int32_t)knobs[5], kn.unit_prio = (int32_t)knobs[6], kn.tb_budget = knobs[7];
+		const mpa_qbatch_t q{ n_seq, nullptr, q_off };
+		DpPlan plan;
+		int64_t r = dp_plan(tasks, n, ctg_len, sizeof(int64_t), n_ctg, &q, opt, kn, sizeof(DpRoundArgs), plan);
+		if (r == MPA_OK) r = dp_plan_serialize(plan, kn, buf, cap);
+		if (r < 0) set_error(plan.err);
+		return r;
+	});
+}
 void mpa_idx_build_last_stats(const mpa_ctx_t *ctx, mpa_idx_build_stats_t *st) { if (st) *st = ctx ? ctx->idx_stats : mpa_idx_build_stats_t{}; }
 void mpa_dbg_idx_build_budget(mpa_ctx_t *ctx, int64_t bytes) { if (ctx) ctx->idx_budget_dbg = bytes > 0 ? bytes : 0; }
 int32_t mpa_dbg_idx_build_hist(const mpa_ctx_t *ctx, int64_t *hist, int32_t cap)

@@ -203,7 +203,6 @@ __device__ __forceinline__ int32_t s_add(int32_t a, int32_t b) { return sat16(a 
 // ------------------------------------------------------------------------------------------------
 // K3: per-row records and query profiles
 // ------------------------------------------------------------------------------------------------
-struct PrepChunk { int32_t task; int32_t row0; };
 #define PROF_AA_STRIDE_REC 2   /* byte0 of a record = amino acid * 2 = byte offset into an int16 profile column (k_ext) */
 
 // base of the strand-oriented contig at strand-local position x (ntseq.c:89-106 folded into addressing; the scans of seed_exec.hip)
@@ -1224,6 +1223,8 @@ __device__ __forceinline__ unsigned long long granule_get(const unsigned long lo
 #define EXT_WIDE_XIN 96                        /* rows of incoming boundary values kept in LDS (two fetches of 48) */
 #define EXT_WIDE_KROWS 96                      /* rows of the key ring: 64 per flush + the lead of the first wave over the last; a multiple of 3 like the other two */
 #define EXT_WIDE_LDS(NW) ((size_t)(NW) * 2 * 64 * PROF_COL_STRIDE + (EXT_WIDE_RING + 1) * 16 + 256 + 32 + (64 * 8 + 32) + EXT_WIDE_XIN * 8 + EXT_WIDE_KROWS * 2 * (NW) * 4)   /* bytes per group; a multiple of 16 */
+static_assert(EXT_WIDE_LDS(2) % 16 == 0 && EXT_WIDE_LDS(4) % 16 == 0 && (2 * 64 * PROF_COL_STRIDE) % 16 == 0, "the groups of a workgroup and the record ring behind the profiles start on 16 bytes");
+static_assert(EXT_WIDE_RING % 12 == 0 && EXT_WIDE_XIN % 48 == 0 && EXT_WIDE_KROWS % 12 == 0 && EXT_WIDE_KROWS >= 64 + 12 + 12 + 3, "rings in whole 12-row blocks; the key ring holds a flush of 64 rows, a block, and the first wave's lead");
 typedef uint32_t v2u __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) v2u *lds_u2p;
 #define MPA_ROW_TAIL_W(Hr2, Hs2, Dr2, Hs3, M3, CX, CH) \
@@ -2353,7 +2354,7 @@ template<bool WG_ONLY>
 __device__ __forceinline__ void dp_run_unit(const DpUnit &u, const ExtArgs &ea, const ExtWideArgs &wa, const GlobArgs &ga, char *lds, const int tid)
 {
 	const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-	switch (u.pad_) {                                             // issue priority by expected duration (dp_exec.hip, launch_round)
+	switch (u.prio) {                                             // issue priority by expected duration (dp_plan.cpp, plan_units)
 	case 3: __builtin_amdgcn_s_setprio(3); break;
 	case 2: __builtin_amdgcn_s_setprio(2); break;
 	case 1: __builtin_amdgcn_s_setprio(1); break;
@@ -2504,7 +2505,7 @@ __device__ __forceinline__ DpUnit dp_load_unit(const DpUnit *up)
 	DpUnit u;
 	u.kind = __builtin_amdgcn_readfirstlane(up->kind), u.first = __builtin_amdgcn_readfirstlane(up->first), u.count = __builtin_amdgcn_readfirstlane(up->count);
 	u.blk = __builtin_amdgcn_readfirstlane(up->blk), u.n_blk = __builtin_amdgcn_readfirstlane(up->n_blk), u.sgroup = __builtin_amdgcn_readfirstlane(up->sgroup);
-	u.xg_first = __builtin_amdgcn_readfirstlane(up->xg_first), u.pad_ = __builtin_amdgcn_readfirstlane(up->pad_);
+	u.xg_first = __builtin_amdgcn_readfirstlane(up->xg_first), u.prio = __builtin_amdgcn_readfirstlane(up->prio);
 	return u;
 }
 
@@ -2584,7 +2585,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 		const DpUnit u = dp_load_unit(ra.units + uidx);
 		long long *trace = pool->slot[s].trace;
 		const long long t0 = trace ? wall_clock64() : 0;
-		switch (u.pad_) {                                             // issue priority by expected duration (dp_exec.hip, launch_round)
+		switch (u.prio) {                                             // issue priority by expected duration (dp_plan.cpp, plan_units)
 		case 3: __builtin_amdgcn_s_setprio(3); break;
 		case 2: __builtin_amdgcn_s_setprio(2); break;
 		case 1: __builtin_amdgcn_s_setprio(1); break;
@@ -2840,12 +2841,12 @@ __global__ __launch_bounds__(64) void k_walk(WalkArgs wa)
 	const int32_t tid = wa.list[blockIdx.x];
 	const DTask t = wa.ga.tasks[tid];
 	const int lane = (int)threadIdx.x;
-	switch (t.pad_) {                                            // (class of the call's packed sweep: 8 + {16, 32, 64 lanes per call})
-	case 8: walk_call<16>(wa, t, tid, (char*)lds_raw, lane); break;
-	case 9: walk_call<32>(wa, t, tid, (char*)lds_raw, lane); break;
-	case 10: walk_call<64>(wa, t, tid, (char*)lds_raw, lane); break;
-	case 11: walk_call<64, true>(wa, t, tid, (char*)lds_raw, lane); break;   // 65..128 columns, one call per wave
-	case 12: walk_call<64, false, true>(wa, t, tid, (char*)lds_raw, lane); break;   // 129..256 columns, a four-wave group per pair of calls
+	switch (t.cls) {                                             // (class of the call's packed sweep)
+	case T_LITE16: walk_call<16>(wa, t, tid, (char*)lds_raw, lane); break;
+	case T_LITE32: walk_call<32>(wa, t, tid, (char*)lds_raw, lane); break;
+	case T_LITE64: walk_call<64>(wa, t, tid, (char*)lds_raw, lane); break;
+	case T_LITE128: walk_call<64, true>(wa, t, tid, (char*)lds_raw, lane); break;   // 65..128 columns, one call per wave
+	case T_LITE_W4: walk_call<64, false, true>(wa, t, tid, (char*)lds_raw, lane); break;   // 129..256 columns, a four-wave group per pair of calls
 	default: break;
 	}
 }
