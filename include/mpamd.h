@@ -352,6 +352,13 @@ int32_t mpa_dbg_gs32_model(int32_t nl, int32_t al, const uint32_t *rec, const in
 void mpa_dbg_antidiag(mpa_ctx_t *ctx, int on);
 int64_t mpa_dbg_main_chains(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads, int64_t *off_u, uint64_t **out_u,
                             int64_t *off_a, uint64_t **out_a);
+/* what the sift of a run WITHOUT a pre-chain keeps (-S, --no-pre-chain with MPA_GPU_SEED_NOPRE=1): the anchors of every query, in
+ * sorted order, that have another anchor of the query at most reach = max(max_intron, bw) >> bbit blocks before or behind them --
+ * every anchor when reach > 15; from the device's sift (k_seed_sift<4096, true>) or, ctx == NULL, from a plain host restatement of
+ * the rule.  off [n_seq + 1], *out (mpa_free), flag [n_seq] (1 = the device's sift handed the query back to the host), *reach.
+ * Returns the total, or MPA_ERR_UNSUPPORTED where that route does not apply (knob unset, a run with a pre-chain, -n 1). */
+int64_t mpa_dbg_sift_kept(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads, int64_t *off, uint64_t **out, int32_t *flag,
+                          int32_t *reach);
 /* the kept seeds of every query (map.c:152-170: sketch, bucket lookup, occurrence cut-off) as (query position, bucket, occurrences)
  * int32 triples in ascending query position, and the cut-off in force per query; from the host stage (ctx == NULL) or from the
  * device stage (MPA_GPU_SKETCH's kernels: a download of the seed jobs they leave for the sift).  off [n_seq + 1] counts triples,

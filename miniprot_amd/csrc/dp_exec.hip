@@ -543,9 +543,22 @@ namespace mpa {
 static int dev_chains_on_device(mpa_ctx_t *ctx, int32_t n_query, int64_t m, int64_t n2, int nb, const uint64_t *key, const uint64_t *val, const int64_t *d_qfirst,
                                 const int32_t *h_flag, const ChainParams &pre, const ChainParams &mainp, PrechainSparse &out, SeedHold &H);
 
-static int dev_prechain_forward_sift(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_block, const PreParams &pp, int nb, int32_t n_query, const int64_t *qfirst,
-                                     const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, double t_begin, const ChainParams *pre_cp, const ChainParams *main_cp, SeedHold &H,
-                                     const int64_t *jfirst_in = nullptr)
+// The sift of a batch up to the host's first look at it: segments, k_seed_sift, k_sift_offsets, the per-query first kept anchor
+// and the hand-back flags down (one wait).  reach < 0: the pre-chain's keep rule (same or adjacent block, halved staging for large
+// queries); reach >= 0: the main chain's reach, full staging (k_seed_sift<4096, true>).  n_seg == 0 / n2 == 0: nothing (kept).
+struct SiftFront {
+	int32_t n_seg = 0;
+	int64_t n2 = 0;                                          // kept anchors of the batch
+	const SiftSeg *d_segs = nullptr;
+	const int64_t *d_qfirst = nullptr;
+	uint64_t *stage0 = nullptr, *stage1 = nullptr;
+	int64_t *h_qfirst2 = nullptr, *h_cfirst = nullptr;       // pinned: first kept anchor of every query; room for one more prefix array
+	int32_t *h_flag = nullptr;                               // pinned: the sift's hand-back flags
+	size_t meta_q = 0;
+	double t_sift = 0;
+};
+static int dev_sift_front(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_block, int nb, int32_t n_query, const int64_t *qfirst, const SeedJob *jobs, int64_t n_jobs,
+                          PrechainSparse &out, double t_begin, const int64_t *jfirst_in, int32_t reach, SiftFront &F)
 {
 	SeedBufs &B = ctx->seed;
 	hipStream_t s = ctx->seed_stream;
@@ -559,7 +572,7 @@ static int dev_prechain_forward_sift(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_
 	int64_t n_cur = 0;                                         // cursors: one per (segment, list of its query)
 	static thread_local std::vector<int64_t> sfirst;          // first staging slot of every query (sift_stage_slots)
 	jfirst.assign((size_t)n_query + 1, 0), qseg.assign((size_t)n_query + 1, 0), sfirst.assign((size_t)n_query + 1, 0);
-	for (int32_t q = 0; q < n_query; ++q) sfirst[(size_t)q + 1] = sfirst[(size_t)q] + sift_stage_slots(qfirst[q + 1] - qfirst[q]);
+	for (int32_t q = 0; q < n_query; ++q) sfirst[(size_t)q + 1] = sfirst[(size_t)q] + (reach >= 0 ? qfirst[q + 1] - qfirst[q] : sift_stage_slots(qfirst[q + 1] - qfirst[q]));
 	const int64_t n_stage = sfirst[(size_t)n_query];
 	if (jfirst_in) jfirst.assign(jfirst_in, jfirst_in + n_query + 1);      // (the jobs were made on the device: dev_sketch_jobs counted them)
 	else {
@@ -585,7 +598,7 @@ static int dev_prechain_forward_sift(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_
 	}
 	qseg[(size_t)n_query] = (int32_t)segs.size();
 	const int32_t n_seg = (int32_t)segs.size();
-	if (n_seg == 0) return MPA_OK;
+	if (n_seg == 0) return MPA_OK;                             // (F.n_seg stays 0)
 	// one pinned block up: qfirst | jfirst | sfirst | segments | qseg
 	const size_t meta_q = ((size_t)n_query + 1) * 8, seg_bytes = (size_t)n_seg * sizeof(SiftSeg);
 	const size_t off_jf = meta_q, off_sf = 2 * meta_q, off_seg = 3 * meta_q, off_qs = off_seg + seg_bytes, meta_bytes = off_qs + ((size_t)n_query + 1) * 4;
@@ -610,7 +623,11 @@ static int dev_prechain_forward_sift(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_
 	// (MPA_SIFT_CAP=2048, measurement: ranges of half the size need 18 KB of LDS instead of 37 KB -- a workgroup then fits next to
 	// four DP workgroups on a CU -- and touch the lists twice as often)
 	static const int sift_cap = [] { const char *e = getenv("MPA_SIFT_CAP"); return e ? atoi(e) : 4096; }();
-	if (sift_cap == 2048)
+	if (reach >= 0)
+		hipLaunchKernelGGL((k_seed_sift<4096, true, uint32_t>), dim3((unsigned)n_seg), dim3(SIFT_THREADS), 0, s, d_segs, B.jobs.as<SeedJobDev>(), d_jfirst, d_qfirst, d_sfirst, d->kb, n_block, nb,
+		                   B.s_cur.as<int32_t>(), B.s_cur2.as<int32_t>(), stage0, stage1, B.s_kept.as<uint32_t>(), B.s_base.as<int64_t>(),
+		                   B.s_flag.as<int32_t>(), (uint32_t)reach);
+	else if (sift_cap == 2048)
 		hipLaunchKernelGGL(k_seed_sift<2048>, dim3((unsigned)n_seg), dim3(SIFT_THREADS), 0, s, d_segs, B.jobs.as<SeedJobDev>(), d_jfirst, d_qfirst, d_sfirst, d->kb, n_block, nb,
 		                   B.s_cur.as<int32_t>(), B.s_cur2.as<int32_t>(), stage0, stage1, B.s_kept.as<uint32_t>(), B.s_base.as<int64_t>(),
 		                   B.s_flag.as<int32_t>());
@@ -634,8 +651,29 @@ static int dev_prechain_forward_sift(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_
 		out.on_host.assign((size_t)n_query, 0);
 		for (int32_t q = 0; q < n_query; ++q) out.on_host[(size_t)q] = h_flag[q] != 0;
 	}
-	const int64_t n2 = h_qfirst2[n_query];
-	if (n2 == 0) return MPA_OK;
+	F.n_seg = n_seg, F.n2 = h_qfirst2[n_query], F.d_segs = d_segs, F.d_qfirst = d_qfirst, F.stage0 = stage0, F.stage1 = stage1;
+	F.h_qfirst2 = h_qfirst2, F.h_cfirst = h_cfirst, F.h_flag = h_flag, F.meta_q = meta_q, F.t_sift = t_sift;
+	return MPA_OK;
+}
+
+static int dev_prechain_forward_sift(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_block, const PreParams &pp, int nb, int32_t n_query, const int64_t *qfirst,
+                                     const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, double t_begin, const ChainParams *pre_cp, const ChainParams *main_cp, SeedHold &H,
+                                     const int64_t *jfirst_in = nullptr)
+{
+	SeedBufs &B = ctx->seed;
+	hipStream_t s = ctx->seed_stream;
+	SiftFront F;
+	int rc = dev_sift_front(ctx, d, n_block, nb, n_query, qfirst, jobs, n_jobs, out, t_begin, jfirst_in, -1, F);
+	if (rc != MPA_OK || F.n_seg == 0 || F.n2 == 0) return rc;
+	const int32_t n_seg = F.n_seg;
+	const int64_t n2 = F.n2;
+	const SiftSeg *d_segs = F.d_segs;
+	const int64_t *d_qfirst = F.d_qfirst;
+	uint64_t *const stage0 = F.stage0, *const stage1 = F.stage1;
+	int64_t *h_cfirst = F.h_cfirst;
+	const int32_t *h_flag = F.h_flag;
+	const size_t meta_q = F.meta_q;
+	const double t_sift = F.t_sift;
 	if ((rc = B.dkey.ensure((size_t)n2 * 8)) || (rc = B.val64[0].ensure((size_t)n2 * 8)) || (rc = B.f.ensure((size_t)n2 * 4)) || (rc = B.pred.ensure((size_t)n2 * 4)) ||
 	    (rc = B.mark.ensure((size_t)n2 * 4)) || (rc = B.flag.ensure((size_t)n2 * 4)) || (rc = B.idx.ensure((size_t)n2 * 4))) return rc;
 	const unsigned nblk = (unsigned)((n2 + 255) / 256);
@@ -840,19 +878,128 @@ static int dev_chains_on_device(mpa_ctx_t *ctx, int32_t n_query, int64_t m, int6
 	return MPA_OK;
 }
 
+// Seeding without a pre-chain (map.c:186 skips it with -S and --no-pre-chain), on the seeding stream:
+//   k_seed_sift<4096, true>   the anchors of every query in sorted order, those kept that have another one within the main chain's reach
+//   k_sift_offsets, k_sift_copy   ... densely; k_sift_anchors: block << 32 | query position, and the rank the sift carried
+//   k_chain_fwd + k_chain_fwd_wave   forward pass of the MAIN chain over the kept anchors (the kernels of dev_chains_on_device, unchanged)
+//   k_chain_extract     main-chain extraction from a SPARSE view: every kept anchor at its rank in the query's full list (set_only = 0)
+//   k_offsets2 + k_chain_pack   the chains of all queries, densely, into pinned host memory
+// The view holds ALL kept anchors, not only those the pass linked: a kept anchor without a link is a root like an absent one, the
+// extraction steps over both alike, and a second compaction would cost a scan and a pass over the view to save part of one.
+// Exact because a dropped anchor has no anchor of its query within max_dist_x: it has no predecessor, is nobody's predecessor and
+// lies in no window that a kept anchor's max_skip / max_iter walk visits -- what a sparse view may leave out (chain_core.h).
+// pm: the main chain's parameters as the forward pass takes them (pm.max_dblock = the sift's reach).
+static int dev_seed_direct_impl(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_block, const PreParams &pm, int nb, int32_t n_query, const int64_t *qfirst, const SeedJob *jobs,
+                                int64_t n_jobs, PrechainSparse &out, double t_begin, const ChainParams &mainp, SeedHold &H, const int64_t *jfirst_in, SiftKept *kept)
+{
+	SeedBufs &B = ctx->seed;
+	hipStream_t s = ctx->seed_stream;
+	SiftFront F;
+	int rc = dev_sift_front(ctx, d, n_block, nb, n_query, qfirst, jobs, n_jobs, out, t_begin, jfirst_in, pm.max_dblock, F);
+	if (rc != MPA_OK || F.n_seg == 0) return rc;
+	if (kept) for (int32_t q = 0; q < n_query; ++q) kept->flag[(size_t)q] = F.h_flag[q] != 0;
+	if (F.n2 == 0) return MPA_OK;
+	const int64_t n2 = F.n2;
+	const size_t M = (size_t)n2, NQ = (size_t)n_query;
+	if ((rc = B.dkey.ensure(M * 8)) || (rc = B.val64[0].ensure(M * 8))) return rc;
+	hipLaunchKernelGGL(k_sift_copy, dim3((unsigned)F.n_seg), dim3(256), 0, s, F.d_segs, B.s_flag.as<int32_t>(), B.s_kept.as<uint32_t>(), B.s_base.as<int64_t>(), B.s_out.as<int64_t>(),
+	                   F.stage0, F.stage1, B.dkey.as<uint64_t>(), B.val64[0].as<uint64_t>());
+	HIP_TRY(hipGetLastError());
+	if (kept) {                                                // (test hook: the kept anchors of every query, as the chain would take them)
+		std::vector<uint64_t> hk(M), hv(M);
+		HIP_TRY(hipMemcpyAsync(hk.data(), B.dkey.p, M * 8, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(hv.data(), B.val64[0].p, M * 8, hipMemcpyDeviceToHost, s));
+		HIP_TRY(wait_stream(ctx, s));
+		kept->first.assign(F.h_qfirst2, F.h_qfirst2 + n_query + 1), kept->a.resize(M);
+		for (size_t i = 0; i < M; ++i) kept->a[i] = (hk[i] & ((1ULL << nb) - 1)) << 32 | (uint32_t)hv[i];
+		return MPA_OK;
+	}
+	// ---- one allocation, carved up, as in dev_chains_on_device: the view (= the forward pass's own arrays), the extraction's scratch, the chains
+	size_t at = 0;
+	auto carve = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; };
+	const size_t o_vpos = carve(M * 4), o_vf = carve(M * 4), o_vpred = carve(M * 4), o_va = carve(M * 8), o_fmark = carve(M * 4);
+	const size_t o_mark = carve(M * 4), o_order = carve(M * 4), o_ends = carve((M + 64 * NQ + 64) * sizeof(Pair64)), o_tail8 = carve(M * sizeof(Pair64)),
+	             o_items = carve(M * sizeof(SparseItem)), o_moved = carve(M * sizeof(SparseItem)), o_merged = carve(M * sizeof(SparseItem)),
+	             o_kept = carve(M), o_stack = carve((M / 64 + 6 * NQ + 16) * sizeof(SortRange)), o_status = carve(NQ * 4 + 16);
+	const int32_t kSerialRun = 48;                          // longer runs get a wavefront each (k_chain_fwd_wave)
+	const size_t long_cap = M / (size_t)(kSerialRun + 1) + 16, o_long = carve(long_cap * sizeof(LongRun)), o_nlong = carve(64);
+	const size_t o_out_a = carve(M * 8), o_out_u = carve(M * 8), o_na = carve(NQ * 8 + 8), o_nu = carve(NQ * 8 + 8), o_offa = carve(NQ * 8 + 16), o_offu = carve(NQ * 8 + 16);
+	// (the sift's staging sits at the front of this block: if the block has to move, k_sift_copy must have read it first)
+	if (at > B.x_all.cap) HIP_TRY(wait_stream(ctx, s));
+	if ((rc = B.x_all.ensure(at))) return rc;
+	char *X = B.x_all.as<char>();
+	const unsigned nblk = (unsigned)((n2 + 255) / 256);
+	const int64_t *d_first = B.pf_qfirst2.as<int64_t>();       // first kept anchor of every query (k_sift_offsets)
+	HIP_TRY(hipMemsetAsync(X + o_status, 0, NQ * 4 + 16, s));
+	HIP_TRY(hipMemsetAsync(X + o_nlong, 0, 64, s));
+	hipLaunchKernelGGL(k_sift_anchors, dim3(nblk), dim3(256), 0, s, B.dkey.as<uint64_t>(), B.val64[0].as<uint64_t>(), n2, nb, (uint64_t*)(X + o_va), (int32_t*)(X + o_vpos));
+	hipLaunchKernelGGL(k_seed_fill, dim3(nblk), dim3(256), 0, s, n2, pm.kmer, (int32_t*)(X + o_vf), (int32_t*)(X + o_vpred), (int32_t*)(X + o_fmark), (uint32_t*)(X + o_mark));
+	hipLaunchKernelGGL(k_chain_fwd, dim3(nblk), dim3(256), 0, s, (const uint64_t*)(X + o_va), n2, d_first, (const int64_t*)nullptr, n_query, pm,
+	                   (int32_t*)(X + o_vf), (int32_t*)(X + o_vpred), (int32_t*)(X + o_fmark), kSerialRun, (LongRun*)(X + o_long), (unsigned int*)(X + o_nlong), (unsigned int)long_cap);
+	hipLaunchKernelGGL(k_chain_fwd_wave, dim3((unsigned)std::min<size_t>(long_cap, 65536)), dim3(64), 0, s, (const uint64_t*)(X + o_va), (const LongRun*)(X + o_long),
+	                   (const unsigned int*)(X + o_nlong), (unsigned int)long_cap, pm, (int32_t*)(X + o_vf), (int32_t*)(X + o_vpred), (int32_t*)(X + o_fmark));
+	HIP_TRY(hipGetLastError());
+	ExtractArgs xa;
+	xa.first = d_first, xa.cnt = nullptr, xa.ntot_first = F.d_qfirst;
+	xa.v_pos = (const int32_t*)(X + o_vpos), xa.v_f = (const int32_t*)(X + o_vf), xa.v_pred = (const int32_t*)(X + o_vpred), xa.v_a = (const uint64_t*)(X + o_va);
+	xa.mark = (int32_t*)(X + o_mark), xa.order = (int32_t*)(X + o_order), xa.ends = (Pair64*)(X + o_ends), xa.tail8 = (Pair64*)(X + o_tail8);
+	xa.items = (SparseItem*)(X + o_items), xa.moved = (SparseItem*)(X + o_moved), xa.merged = (SparseItem*)(X + o_merged);
+	xa.kept = (uint8_t*)(X + o_kept), xa.stack = (SortRange*)(X + o_stack);
+	xa.a_out = (uint64_t*)(X + o_out_a), xa.u_out = (uint64_t*)(X + o_out_u), xa.n_a = (int64_t*)(X + o_na), xa.n_u = (int64_t*)(X + o_nu);
+	xa.status = (int32_t*)(X + o_status), xa.p = mainp, xa.set_only = 0;
+	hipLaunchKernelGGL(k_chain_extract, dim3((unsigned)n_query), dim3(64), EXTRACT_LDS_BYTES, s, xa, n_query);
+	hipLaunchKernelGGL(k_offsets2, dim3(1), dim3(256), 0, s, (const int64_t*)(X + o_na), (const int64_t*)(X + o_nu), n_query, (int64_t*)(X + o_offa), (int64_t*)(X + o_offu));
+	HIP_TRY(hipGetLastError());
+	// offsets + status down, then the chains themselves straight into pinned memory
+	const size_t offb = (NQ + 1) * 8;
+	if ((rc = B.h_xoff.ensure(2 * offb + NQ * 4 + 64))) return rc;
+	int64_t *h_offa = B.h_xoff.as<int64_t>(), *h_offu = h_offa + (NQ + 1);
+	int32_t *h_status = (int32_t*)(h_offu + (NQ + 1));
+	HIP_TRY(hipMemcpyAsync(h_offa, X + o_offa, offb, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h_offu, X + o_offu, offb, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h_status, X + o_status, NQ * 4, hipMemcpyDeviceToHost, s));
+	HIP_TRY(wait_stream(ctx, s));
+	const int64_t tot_a = h_offa[n_query], tot_u = h_offu[n_query];
+	if ((rc = H.h_A.ensure((size_t)tot_a * 8 + 64)) || (rc = H.h_U.ensure((size_t)tot_u * 8 + 64))) return rc;
+	if (tot_a > 0 || tot_u > 0) {
+		hipLaunchKernelGGL(k_chain_pack, dim3((unsigned)n_query), dim3(256), 0, s, d_first, (const int64_t*)(X + o_na), (const int64_t*)(X + o_nu),
+		                   (const int64_t*)(X + o_offa), (const int64_t*)(X + o_offu), (const uint64_t*)(X + o_out_a), (const uint64_t*)(X + o_out_u),
+		                   H.h_A.as<uint64_t>(), H.h_U.as<uint64_t>());
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(wait_stream(ctx, s));
+	}
+	out.a_first.assign(h_offa, h_offa + n_query + 1), out.u_first.assign(h_offu, h_offu + n_query + 1);
+	out.A = H.h_A.as<uint64_t>(), out.U = H.h_U.as<uint64_t>();
+	out.has_chains = true;
+	bool any = !out.on_host.empty();                           // (the sift's hand-backs are in there already: dev_sift_front)
+	for (int32_t q = 0; q < n_query && !any; ++q) any = h_status[q] != 0;
+	if (any) {
+		if (out.on_host.empty()) out.on_host.assign(NQ, 0);
+		for (int32_t q = 0; q < n_query; ++q) if (h_status[q] || F.h_flag[q]) out.on_host[(size_t)q] = 1;
+	}
+	timing_note("    seed: copy + main chain on the device", now_ms() - F.t_sift);
+	return MPA_OK;
+}
+
 // GPU seeding for one mini-batch: anchors -> sort -> forward pass of the pre-chain -> the anchors that have a neighbour.
 // jobs: the kept seeds of all queries (qid ascending, within a query ascending query position, dst = running anchor
 // offset); qfirst[n_query + 1]: first anchor of every query.  out: per query a sparse ChainView's arrays
 // (pred = index into the query's part of the view, -1 for none).
-int dev_prechain_forward(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams &pre, int32_t n_query, const int64_t *qfirst,
-                         const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, const ChainParams *main, SeedHold *hold, const int64_t *jfirst_dev)
+// pre_p == nullptr: the direct route (dev_seed_direct) -- no pre-chain, the sift keeps by the reach of the main chain *main
+static int dev_seed_entry(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams *pre_p, int32_t n_query, const int64_t *qfirst,
+                          const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, const ChainParams *main, SeedHold *hold, const int64_t *jfirst_dev, SiftKept *kept)
 {
 	const int64_t n = qfirst[n_query];
 	out.cfirst.assign((size_t)n_query + 1, 0);
 	out.pos = out.f = out.pred = nullptr, out.a = nullptr, out.m = 0, out.on_host.clear();
 	out.has_chains = false, out.U = out.A = nullptr, out.u_first.clear(), out.a_first.clear();
+	if (!pre_p) {                                              // (no anchors: no chains -- the planners take that from the device's result like any other)
+		out.has_chains = !kept, out.u_first.assign((size_t)n_query + 1, 0), out.a_first.assign((size_t)n_query + 1, 0);
+		if (kept) kept->first.assign((size_t)n_query + 1, 0), kept->a.clear(), kept->flag.assign((size_t)n_query, 0);
+	}
 	if (n == 0 || n_jobs == 0) return MPA_OK;
-	if (pre.bbit <= 0) { set_error("GPU pre-chain needs block anchors (bbit > 0)"); return MPA_ERR_UNSUPPORTED; }
+	const ChainParams &pre = pre_p ? *pre_p : *main;
+	if (pre.bbit <= 0) { set_error("GPU seeding needs block anchors (bbit > 0)"); return MPA_ERR_UNSUPPORTED; }
 	HIP_TRY(hipSetDevice(ctx->device));
 	if (dev_upload_index(ctx, mi) != MPA_OK) return MPA_ERR_HIP;
 	DeviceIndex *d = mi->dev[ctx->device];
@@ -871,19 +1018,20 @@ int dev_prechain_forward(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams &pre, 
 	pp.max_dist_x = std::max(pre.max_dist_x, pre.bw), pp.max_dist_y = pre.max_dist_y;
 	if (pp.max_dist_y < pre.bw && !pre.is_spliced) pp.max_dist_y = pre.bw;
 	pp.bw = pre.bw, pp.max_skip = pre.max_skip, pp.max_iter = pre.max_iter, pp.kmer = pre.kmer, pp.bbit = pre.bbit;
-	pp.is_spliced = pre.is_spliced, pp.coef_log = pre.coef_log, pp.max_dblock = pp.max_dist_x >> pre.bbit;
+	pp.is_spliced = pre.is_spliced, pp.coef_log = pre.coef_log, pp.max_dblock = pp.max_dist_x >> pre.bbit;   // (direct route: the main chain's parameters, as dev_chains_on_device derives them)
 	int nb = 1, qb = 1;
 	while ((1ULL << nb) < (uint64_t)mi->n_block + (uint64_t)pp.max_dblock + 2) ++nb;
 	while ((1LL << qb) < n_query) ++qb;
 	if (nb + qb > 64) { set_error("GPU pre-chain: too many queries x blocks for a 64-bit key"); return MPA_ERR_UNSUPPORTED; }
-	if (pp.max_dblock != 1) { set_error("GPU seeding: the sift assumes a pre-chain that reaches one block"); return MPA_ERR_UNSUPPORTED; }
+	if (pre_p && pp.max_dblock != 1) { set_error("GPU seeding: the sift assumes a pre-chain that reaches one block"); return MPA_ERR_UNSUPPORTED; }
 	{	// the working set is ~60 bytes per anchor (sift: 16 of staging, the rest sized by the kept ones); a batch that does not fit
-		// stays on the host (the caller falls back)
+		// stays on the host (the caller falls back).  Direct route: the staging is full -- 16 B per anchor where the halved one takes 8 --
+		// and the rule keeps every second anchor or more, 36 B each, before the chaining block is carved: 56 B per anchor
 		size_t free_b = 0, total_b = 0;
 		if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
 			const SeedBufs &Bc = ctx->seed;
 			const size_t have = Bc.f.cap + Bc.pred.cap + Bc.mark.cap + Bc.flag.cap + Bc.idx.cap + Bc.tmp.cap + Bc.x_all.cap + Bc.dkey.cap + Bc.val64[0].cap;
-			if ((size_t)n * 40 > have + free_b - (free_b >> 3)) { set_error("GPU seeding: batch too large for device memory"); return MPA_ERR_UNSUPPORTED; }
+			if ((size_t)n * (pre_p ? 40 : 56) > have + free_b - (free_b >> 3)) { set_error("GPU seeding: batch too large for device memory"); return MPA_ERR_UNSUPPORTED; }
 		}
 	}
 	SeedBufs &B = ctx->seed;
@@ -900,11 +1048,25 @@ int dev_prechain_forward(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams &pre, 
 	}
 	// merge the occurrence lists per query in block order, keep what has a neighbour (k_seed_sift, seed_exec.hip)
 	tl_alloc_failed = false;
-	const int rc = dev_prechain_forward_sift(ctx, d, mi->n_block, pp, nb, n_query, qfirst, jobs, n_jobs, out, t_begin, &pre, main, hold ? *hold : B.own, jfirst_dev);
+	const int rc = pre_p ? dev_prechain_forward_sift(ctx, d, mi->n_block, pp, nb, n_query, qfirst, jobs, n_jobs, out, t_begin, &pre, main, hold ? *hold : B.own, jfirst_dev)
+	                     : dev_seed_direct_impl(ctx, d, mi->n_block, pp, nb, n_query, qfirst, jobs, n_jobs, out, t_begin, *main, hold ? *hold : B.own, jfirst_dev, kept);
 	// a pool that could not grow (the admission check above is an estimate): the batch is seeded on the host, as for any batch
 	// that does not fit -- nothing has been handed to the caller yet
 	if (rc == MPA_ERR_HIP && tl_alloc_failed) { (void)hipStreamSynchronize(s); return MPA_ERR_UNSUPPORTED; }
 	return rc;
+}
+int dev_prechain_forward(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams &pre, int32_t n_query, const int64_t *qfirst,
+                         const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, const ChainParams *main, SeedHold *hold, const int64_t *jfirst_dev)
+{
+	return dev_seed_entry(ctx, mi, &pre, n_query, qfirst, jobs, n_jobs, out, main, hold, jfirst_dev, nullptr);
+}
+// Seeding without a pre-chain (-S, --no-pre-chain; MPA_GPU_SEED_NOPRE): sift by the main chain's reach, then the main chain itself
+// (dev_seed_direct_impl).  Same contract as dev_prechain_forward(main != nullptr): out.has_chains, out.on_host.  kept != nullptr
+// (test hook): stop behind the sift and hand out the kept anchors instead.
+int dev_seed_direct(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams &mainp, int32_t n_query, const int64_t *qfirst, const SeedJob *jobs, int64_t n_jobs,
+                    PrechainSparse &out, SeedHold *hold, const int64_t *jfirst_dev, SiftKept *kept)
+{
+	return dev_seed_entry(ctx, mi, nullptr, n_query, qfirst, jobs, n_jobs, out, &mainp, hold, jfirst_dev, kept);
 }
 
 // ki[] next to kb[] in HBM, on the first device sketch of a device.  The host array may be a misaligned view into a mapped .mpi:

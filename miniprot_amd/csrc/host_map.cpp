@@ -881,6 +881,29 @@ static int gpu_sketch_mode()
 	return e && atoi(e) != 0 ? 1 : 0;
 }
 
+// MPA_GPU_SEED_NOPRE: 1 = a run without a pre-chain (-S, --no-pre-chain) is seeded and chained on the device too, where MPA_GPU_SEED
+// allows device seeding at all (the direct route: dev_seed_direct); 0 / unset = such a run keeps the host stages
+static int gpu_seed_nopre_mode()
+{
+	const char *e = getenv("MPA_GPU_SEED_NOPRE");       // (read per call: the tests flip it)
+	return e && atoi(e) != 0 ? 1 : 0;
+}
+// Which way a batch is seeded, from the options alone (whether the device takes a batch of an eligible route is then a matter of
+// MPA_GPU_SEED and its size).  SEED_PRECHAIN: sift -> pre-chain -> main chain (map.c:186 runs the pre-chain).  SEED_DIRECT: sift by
+// the main chain's reach -> main chain; its extraction reads a sparse view, which is only valid with min_chn_cnt > 1 (chain_core.h)
+// -- a run whose options the extraction would hand back wholesale (chain_ends_sparse_possible) makes no device pass at all.
+enum SeedRoute { SEED_ON_HOST = 0, SEED_PRECHAIN, SEED_DIRECT };
+static SeedRoute seed_route(const mpa_mapopt_t &opt, const mpa_idxopt_t &io)
+{
+	if (io.bbit <= 0) return SEED_ON_HOST;
+	if (prechain_enabled(opt)) return SEED_PRECHAIN;
+	if (!gpu_seed_nopre_mode()) return SEED_ON_HOST;
+	ChainParams p = ChainParams();
+	p.min_cnt = opt.min_chn_cnt, p.min_sc = opt.min_chn_sc, p.kmer = io.kmer;
+	const ChainView large{ 65, 0, nullptr, nullptr, nullptr, nullptr };      // (a query of 64 anchors or fewer builds the full list whatever the options: it fits)
+	return chain_ends_sparse_possible(p, large) ? SEED_DIRECT : SEED_ON_HOST;
+}
+
 static mpa_batch_s *batch_shell(const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads)
 {
 	if (mi->kb.empty() && mi->n_kb == 0) { set_error("the index has no k-mer table (genome-only index): cannot map"); return nullptr; }
@@ -902,7 +925,7 @@ static mpa_batch_t *batch_sketch_phase(bool have_device, const mpa_idx_t *mi, co
 	mpa_batch_s *b = batch_shell(mi, opt, q, n_threads);
 	if (!b) return nullptr;
 	// with MPA_GPU_SKETCH the stage runs where its result is consumed: the seeder sketches on the device (batch_device_seed_phase)
-	if (have_device && gpu_sketch_mode() && gpu_seeding_mode() != 0 && prechain_enabled(*opt) && mi->opt.bbit > 0 && q->n_seq > 0) { b->dev_sketch = true; return b; }
+	if (have_device && gpu_sketch_mode() && gpu_seeding_mode() != 0 && seed_route(*opt, mi->opt) != SEED_ON_HOST && q->n_seq > 0) { b->dev_sketch = true; return b; }
 	batch_host_seeds(b, have_device);
 	return b;
 }
@@ -917,7 +940,7 @@ static void batch_host_seeds(mpa_batch_s *b, bool have_device)
 	parallel_for(b->n_threads, q->n_seq, [&](int64_t i) { stage_seeds(b, b->qs[i]); });
 	timing_note("  A1: seeds of all queries", now_ms() - t0);
 	const int mode = gpu_seeding_mode();
-	if (!have_device || mode == 0 || !prechain_enabled(*opt) || mi->opt.bbit <= 0 || q->n_seq == 0) return;
+	if (!have_device || mode == 0 || seed_route(*opt, mi->opt) == SEED_ON_HOST || q->n_seq == 0) return;
 	std::vector<int64_t> &qfirst = b->seed_qfirst;
 	std::vector<size_t> jfirst((size_t)q->n_seq + 1, 0);
 	qfirst.assign((size_t)q->n_seq + 1, 0);
@@ -947,6 +970,13 @@ static bool batch_device_seed_phase(mpa_ctx_t *seed_ctx, mpa_batch_s *b, bool wa
 	if (sketch_ms) *sketch_ms = 0;
 	if (!seed_ctx) return true;
 	const mpa_idx_t *mi = b->mi;
+	const SeedRoute route = seed_route(b->opt, mi->opt);
+	if (route == SEED_DIRECT && !want_chains) {          // (there is no pre-chain whose survivors the device could return: the host stages)
+		if (b->dev_sketch) { b->dev_sketch = false; batch_host_seeds(b, false); }
+		std::vector<SeedJob>().swap(b->seed_jobs);
+		std::vector<int64_t>().swap(b->seed_qfirst);
+		return true;
+	}
 	SketchResult sk;
 	bool jobs_on_device = false;
 	if (b->dev_sketch) {
@@ -971,7 +1001,10 @@ static bool batch_device_seed_phase(mpa_ctx_t *seed_ctx, mpa_batch_s *b, bool wa
 	const double t1 = now_ms();
 	// (with the main chain's parameters the device carries on through both chaining rounds, unless the caller only wants the pre-chain)
 	const ChainParams main_cp = main_chain_params(mi, b->opt);
-	const int rc = jobs_on_device
+	const int rc = route == SEED_DIRECT
+		? (jobs_on_device ? dev_seed_direct(seed_ctx, const_cast<mpa_idx_s*>(mi), main_cp, b->q.n_seq, sk.qfirst, nullptr, sk.n_jobs, b->sparse, hold, sk.jfirst)
+		                  : dev_seed_direct(seed_ctx, const_cast<mpa_idx_s*>(mi), main_cp, b->q.n_seq, b->seed_qfirst.data(), b->seed_jobs.data(), (int64_t)b->seed_jobs.size(), b->sparse, hold))
+		: jobs_on_device
 		? dev_prechain_forward(seed_ctx, const_cast<mpa_idx_s*>(mi), prechain_params(mi, b->opt), b->q.n_seq, sk.qfirst, nullptr, sk.n_jobs, b->sparse,
 		                       want_chains ? &main_cp : nullptr, hold, sk.jfirst)
 		: dev_prechain_forward(seed_ctx, const_cast<mpa_idx_s*>(mi), prechain_params(mi, b->opt), b->q.n_seq, b->seed_qfirst.data(), b->seed_jobs.data(),
@@ -988,7 +1021,8 @@ static bool batch_device_seed_phase(mpa_ctx_t *seed_ctx, mpa_batch_s *b, bool wa
 		if (b->sparse.on_host.empty()) b->sparse.on_host.assign((size_t)b->q.n_seq, 0);
 		for (int32_t i = 0; i < b->q.n_seq; ++i) if (sk.flag[i]) b->sparse.on_host[(size_t)i] = 1;
 	}
-	timing_note("  seeding on the GPU (sift + pre-chain + both chaining rounds)", now_ms() - t1);
+	timing_note(route == SEED_DIRECT ? "  seeding on the GPU (direct route: sift by the main chain's reach + main chain, no pre-chain)"
+	                                 : "  seeding on the GPU (sift + pre-chain + both chaining rounds)", now_ms() - t1);
 	return true;
 }
 
@@ -1371,7 +1405,7 @@ int64_t mpa_dbg_prechain_survivors(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mp
 	mpa_batch_t *b;
 	{ SeedModeScope forced(ctx ? 1 : 0); b = batch_seed_phase(ctx, mi, opt, q, n_threads, false); }
 	if (!b) return MPA_ERR_ARG;
-	if (ctx && !b->seeded_on_device && q->n_seq > 0 && prechain_enabled(*opt)) { delete b; set_error("device seeding was not used"); return MPA_ERR_UNSUPPORTED; }
+	if (ctx && !b->seeded_on_device && q->n_seq > 0 && seed_route(*opt, mi->opt) == SEED_PRECHAIN) { delete b; set_error("device seeding was not used"); return MPA_ERR_UNSUPPORTED; }
 	std::vector<std::vector<uint64_t>> per((size_t)q->n_seq);
 	parallel_for(b->n_threads, q->n_seq, [&](int64_t i) {
 		if (b->seeded_on_device) stage_anchors_from_device(b, b->qs[i], b->sparse, per[i]);
@@ -1398,7 +1432,7 @@ int64_t mpa_dbg_main_chains(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapop
 	mpa_batch_t *b;
 	{ SeedModeScope forced(ctx ? 1 : 0); b = batch_seed_phase(ctx, mi, opt, q, n_threads, true); }
 	if (!b) return MPA_ERR_ARG;
-	if (ctx && q->n_seq > 0 && prechain_enabled(*opt) && !(b->seeded_on_device && b->sparse.has_chains)) { delete b; set_error("the device did not chain"); return MPA_ERR_UNSUPPORTED; }
+	if (ctx && q->n_seq > 0 && seed_route(*opt, mi->opt) != SEED_ON_HOST && !(b->seeded_on_device && b->sparse.has_chains)) { delete b; set_error("the device did not chain"); return MPA_ERR_UNSUPPORTED; }
 	std::vector<std::vector<uint64_t>> us((size_t)q->n_seq), as((size_t)q->n_seq);
 	const ChainParams cp = main_chain_params(mi, *opt);
 	int64_t n_back = 0;
@@ -1423,6 +1457,63 @@ int64_t mpa_dbg_main_chains(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapop
 	*out_u = ou, *out_a = oa;
 	delete b;
 	return n_back;
+}
+
+// Test hook: what the sift of the direct route (SEED_DIRECT: k_seed_sift<4096, true>) keeps -- the anchors of every query that have
+// another one of the query within reach = max(max_intron, bw) >> bbit blocks before or behind them in sorted order, all of them when
+// reach > kSiftReachMax (15) -- in sorted order.  ctx == NULL: a plain host restatement of that rule over mpa_dbg_anchors().  off[n_seq + 1]; *out
+// malloc'd (mpa_free); flag[n_seq]: 1 = the device's sift handed the query back (its anchors are not in *out); *reach: the reach in
+// force.  Returns the total, or MPA_ERR_UNSUPPORTED where the direct route does not apply (MPA_GPU_SEED_NOPRE unset, a run with a
+// pre-chain, options that rule out a sparse view).
+int64_t mpa_dbg_sift_kept(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads, int64_t *off, uint64_t **out, int32_t *flag, int32_t *reach)
+{
+	*out = nullptr;
+	if (seed_route(*opt, mi->opt) != SEED_DIRECT) { set_error("mpa_dbg_sift_kept: the direct seeding route does not apply to this run"); return MPA_ERR_UNSUPPORTED; }
+	const ChainParams cp = main_chain_params(mi, *opt);
+	const int64_t D = std::max(cp.max_dist_x, cp.bw) >> cp.bbit;
+	*reach = (int32_t)D;
+	const int32_t n = q->n_seq;
+	for (int32_t i = 0; i < n; ++i) flag[i] = 0;
+	if (!ctx) {
+		uint64_t *a = nullptr;
+		std::vector<int64_t> a_off((size_t)n + 1, 0);
+		const int64_t n_a = mpa_dbg_anchors(mi, opt, q, n_threads, a_off.data(), &a);
+		if (n_a < 0) return n_a;
+		uint64_t *o = (uint64_t*)malloc((size_t)std::max<int64_t>(n_a, 1) * 8);
+		if (!o) { free(a); set_error("out of host memory"); return MPA_ERR_ARG; }
+		int64_t k = 0;
+		for (int32_t i = 0; i < n; ++i) {
+			off[i] = k;
+			for (int64_t j = a_off[(size_t)i]; j < a_off[(size_t)i + 1]; ++j) {
+				const int64_t blk = (int64_t)(a[j] >> 32);
+				const bool left = j > a_off[(size_t)i] && blk - (int64_t)(a[j - 1] >> 32) <= D, right = j + 1 < a_off[(size_t)i + 1] && (int64_t)(a[j + 1] >> 32) - blk <= D;
+				if (D > kSiftReachMax || left || right) o[k++] = a[j];
+			}
+		}
+		off[n] = k;
+		free(a);
+		*out = o;
+		return k;
+	}
+	return mpa::guarded<int64_t>((int64_t)MPA_ERR_HIP, [&]() -> int64_t {
+		mpa_batch_s *b = batch_shell(mi, opt, q, n_threads);
+		if (!b) return MPA_ERR_ARG;
+		std::unique_ptr<mpa_batch_s> own(b);
+		{ SeedModeScope forced(1); batch_host_seeds(b, true); }
+		SiftKept kept;
+		kept.first.assign((size_t)n + 1, 0), kept.flag.assign((size_t)n, 0);
+		if (!b->seed_jobs.empty()) {
+			const int rc = dev_seed_direct(ctx, const_cast<mpa_idx_s*>(mi), cp, n, b->seed_qfirst.data(), b->seed_jobs.data(), (int64_t)b->seed_jobs.size(), b->sparse, nullptr, nullptr, &kept);
+			if (rc != MPA_OK) return rc;
+		}
+		uint64_t *o = (uint64_t*)malloc(std::max<size_t>(kept.a.size(), 1) * 8);
+		if (!o) { set_error("out of host memory"); return MPA_ERR_ARG; }
+		if (!kept.a.empty()) memcpy(o, kept.a.data(), kept.a.size() * 8);
+		for (int32_t i = 0; i <= n; ++i) off[i] = kept.first[(size_t)i];
+		for (int32_t i = 0; i < n; ++i) flag[i] = kept.flag[(size_t)i];
+		*out = o;
+		return (int64_t)kept.a.size();
+	});
 }
 
 // Test hook: the forward pass of mp_chain (chain.c:181-209) for n_prob chaining problems whose sorted anchors lie back to back

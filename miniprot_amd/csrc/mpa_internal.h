@@ -174,6 +174,14 @@ SeedHold *ctx_seed_hold(mpa_ctx_t *ctx, int k);   // k-th result holder of a con
 int dev_prechain_forward(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams &pre, int32_t n_query, const int64_t *qfirst,
                          const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, const ChainParams *main = nullptr, SeedHold *hold = nullptr,
                          const int64_t *jfirst_dev = nullptr);
+// Seeding where map.c:186 runs no pre-chain (-S, --no-pre-chain): the sift keeps the anchors that have another one within the main
+// chain's reach, and the main chain runs over them directly.  out as from dev_prechain_forward(main != nullptr): has_chains, on_host.
+// kept != nullptr (mpa_dbg_sift_kept): stop behind the sift; the kept anchors (block << 32 | query position) of every query in
+// sorted order, and the sift's hand-back flags.
+static const int32_t kSiftReachMax = 15;   // widest reach the sift filters by; beyond it every anchor is kept
+struct SiftKept { std::vector<int64_t> first; std::vector<uint64_t> a; std::vector<uint8_t> flag; };
+int dev_seed_direct(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams &mainp, int32_t n_query, const int64_t *qfirst, const SeedJob *jobs, int64_t n_jobs,
+                    PrechainSparse &out, SeedHold *hold = nullptr, const int64_t *jfirst_dev = nullptr, SiftKept *kept = nullptr);
 // The sketch stage (map.c:126-170) of a mini-batch on the device, sketch_exec.hip: the kept seeds of every query as the sift's
 // jobs, left in the context's device memory -- dev_prechain_forward(jobs = nullptr, jfirst_dev = jfirst) then runs on them.  What
 // comes back (pinned memory of the context, valid until its next sketch): first anchor / first job of every query, the cut-off in

@@ -550,6 +550,17 @@ __device__ __forceinline__ uint32_t sift_block_sum(uint32_t v, volatile uint32_t
 	__syncthreads();
 	return scr[0] + scr[1] + scr[2] + scr[3];
 }
+// maximum over the workgroup (4 waves); scr = 4 words of LDS
+__device__ __forceinline__ uint32_t sift_block_max(uint32_t v, volatile uint32_t *scr)
+{
+#pragma unroll
+	for (int o = 32; o > 0; o >>= 1) { const uint32_t w = __shfl_xor(v, o); v = w > v ? w : v; }
+	__syncthreads();                                        // (scr may still be read from the previous call)
+	if ((threadIdx.x & 63) == 0) scr[threadIdx.x >> 6] = v;
+	__syncthreads();
+	const uint32_t a = scr[0] > scr[1] ? scr[0] : scr[1], b = scr[2] > scr[3] ? scr[2] : scr[3];
+	return a > b ? a : b;
+}
 // exclusive prefix of v over the workgroup's threads; scr = 4 words of LDS
 __device__ __forceinline__ uint32_t sift_block_scan(uint32_t v, volatile uint32_t *scr)
 {
@@ -584,8 +595,10 @@ __device__ __forceinline__ void sift_fetch(uint32_t (&v)[W], const uint32_t *lis
 #pragma unroll
 	for (int k = 0; k < W; ++k) v[k] = list[c + (k < m ? k : m - 1)];
 }
-template<int W>
-__device__ __forceinline__ int32_t sift_place(const uint32_t (&v)[W], int32_t c, int32_t cnt, uint32_t lo, uint32_t hi, int LB, uint32_t l, uint32_t *keys, uint32_t *fill, uint32_t cap)
+// (REACH: block lo takes the local number doff instead of 1)
+template<int W, bool REACH = false>
+__device__ __forceinline__ int32_t sift_place(const uint32_t (&v)[W], int32_t c, int32_t cnt, uint32_t lo, uint32_t hi, int LB, uint32_t l, uint32_t *keys, uint32_t *fill, uint32_t cap,
+                                              uint32_t doff = 1u)
 {
 	const int32_t m = cnt - c < W ? cnt - c : W;
 	int32_t below = 0;
@@ -595,25 +608,41 @@ __device__ __forceinline__ int32_t sift_place(const uint32_t (&v)[W], int32_t c,
 		const uint32_t slot = atomicAdd(fill, (uint32_t)below);
 #pragma unroll
 		for (int k = 0; k < W; ++k)
-			if (k < below && slot + k < cap) keys[slot + k] = ((v[k] - lo + 1u) << LB) | l;
+			if (k < below && slot + k < cap) keys[slot + k] = REACH ? ((v[k] - lo + doff) << LB) | l : ((v[k] - lo + 1u) << LB) | l;
 	}
 	return below;
 }
-template<int W>
-__device__ __forceinline__ int32_t sift_take(const uint32_t *list, int32_t c, int32_t cnt, uint32_t lo, uint32_t hi, int LB, uint32_t l, uint32_t *keys, uint32_t *fill, uint32_t cap)
+template<int W, bool REACH = false>
+__device__ __forceinline__ int32_t sift_take(const uint32_t *list, int32_t c, int32_t cnt, uint32_t lo, uint32_t hi, int LB, uint32_t l, uint32_t *keys, uint32_t *fill, uint32_t cap,
+                                             uint32_t doff = 1u)
 {
 	uint32_t v[W];
 	sift_fetch<W>(v, list, c, cnt);
-	return sift_place<W>(v, c, cnt, lo, hi, LB, l, keys, fill, cap);
+	return sift_place<W, REACH>(v, c, cnt, lo, hi, LB, l, keys, fill, cap, doff);
 }
-template<int SIFT_CAP>
+// REACH (the run without a pre-chain, -S / --no-pre-chain: the kept anchors go straight to the main chain): the keep rule is the main
+// chain's own reach instead of "same or adjacent block" -- an anchor is kept iff its predecessor or its successor in the query's
+// sorted list lies at most `reach` blocks away (reach = max(max_intron, bw) >> bbit; 0 = only anchors that share a block), i.e. iff
+// it is not a run of one under the run rule of k_chain_fwd.  Local block numbers start at `reach` so that a carry spanning the last
+// `reach` blocks of the range before fits below them; the segment-edge probes look `reach` blocks to either side; every query owns
+// one staging slot per anchor (this rule keeps 45-100 % of them).  reach > SIFT_REACH_MAX: every anchor is kept at its rank -- the
+// kernel then is the merge alone: no carry, no probes.  The reach is one more kernel argument, which only the REACH instantiation
+// has (R = uint32_t; the two others keep the argument list, and with it the code, they had before there was a REACH).
+#define SIFT_REACH_MAX ((uint32_t)kSiftReachMax)       /* (mpa_internal.h) */
+__device__ __forceinline__ uint32_t sift_reach_arg() { return 1u; }
+__device__ __forceinline__ uint32_t sift_reach_arg(uint32_t reach) { return reach; }
+template<int SIFT_CAP, bool REACH = false, typename... R>
 // (round 6 measured the kernel with dynamic LDS and a budget of 96 / 80 registers -- 16 / 31 spilled --: the stream is level with all three,
 // profiles/r06_experiments.txt section 10; the 128 registers and the static arrays stay)
 __global__ __launch_bounds__(SIFT_THREADS) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_seed_sift(const SiftSeg *segs, const SeedJobDev *jobs, const int64_t *jfirst, const int64_t *qfirst, const int64_t *sfirst, const uint32_t *kb,
                                                             uint32_t n_block, int nb, int32_t *cur, int32_t *cur2, uint64_t *skey, uint64_t *sval, uint32_t *seg_kept,
-                                                            int64_t *seg_base, int32_t *qflag)
+                                                            int64_t *seg_base, int32_t *qflag, R... reach_arg)
 {
+	static_assert(sizeof...(R) == (REACH ? 1 : 0), "the reach is an argument of the REACH instantiation alone");
 	MPA_SHORT_KERNEL();
+	const uint32_t reach = sift_reach_arg(reach_arg...);
+	const bool keep_all = REACH && reach > SIFT_REACH_MAX;
+	const uint32_t D = REACH ? (keep_all ? 0u : reach) : 1u;    // blocks the keep rule looks to either side = width of the carry = local number of block lo
 	constexpr uint32_t SIFT_TARGET = (uint32_t)SIFT_CAP * 5u / 8u;      // anchors a range is sized for
 	constexpr int SIFT_NBK_LOG2 = SIFT_CAP >= 4096 ? 10 : 9, SIFT_NBK = 1 << SIFT_NBK_LOG2;
 	__shared__ uint32_t keys[SIFT_CAP], kbuf[SIFT_CAP];        // a range's anchors; the same in bucket order
@@ -631,12 +660,13 @@ __global__ __launch_bounds__(SIFT_THREADS) __attribute__((amdgpu_waves_per_eu(4,
 	int LB = 1;
 	while ((1 << LB) < nl) ++LB;
 	const uint32_t lmask = (1u << LB) - 1u;
-	const uint32_t w_max = (LB >= 31 ? 1u : (1u << (32 - LB))) - 2u;           // widest range whose local block numbers fit next to LB list bits
+	const uint32_t w_max = REACH ? (1u << (32 - LB)) - 1u - D                    // (LB <= 20: the driver turns queries with more seeds away)
+	                             : (LB >= 31 ? 1u : (1u << (32 - LB))) - 2u;    // widest range whose local block numbers fit next to LB list bits
 	const uint32_t lo0 = sg.lo, hi0 = sg.hi;
 	const int64_t c0s = sg.cur_off;                            // this segment's cursors: segments of one query run side by side
 
 	// ---- cursors at the segment's first block; rank base; is there an anchor in block lo0 - 1?
-	const bool half_stage = n_anchor > SIFT_FULL_STAGE;      // (see sift_stage_slots)
+	const bool half_stage = REACH ? false : n_anchor > SIFT_FULL_STAGE;      // (see sift_stage_slots)
 	// The first 256 lists (all of them for most queries) live in their threads' registers: the job, the cursor, and the NEXT eight
 	// entries, fetched as soon as the cursor is known -- a list sits at a random place of a multi-GB array, and the round trip of
 	// its first touch in a range (TLB miss included) then runs behind the sort and the output of the range before.
@@ -651,6 +681,9 @@ __global__ __launch_bounds__(SIFT_THREADS) __attribute__((amdgpu_waves_per_eu(4,
 		int32_t c = 0;
 		if (lo0 > 0) {
 			c = d_lower_bound(list, s.cnt, (uint64_t)lo0);
+			if (REACH) {                                          // the highest block with an anchor in [lo0 - D, lo0), + 1
+				if (c > 0 && (uint64_t)list[c - 1] + D >= (uint64_t)lo0 && list[c - 1] + 1u > left_nb) left_nb = list[c - 1] + 1u;
+			} else
 			if (c > 0 && list[c - 1] == lo0 - 1) left_nb = 1;
 		}
 		cur[c0s + l] = c;
@@ -659,7 +692,8 @@ __global__ __launch_bounds__(SIFT_THREADS) __attribute__((amdgpu_waves_per_eu(4,
 		if (half_stage) inside += (uint32_t)((hi0 < n_block ? d_lower_bound(list, s.cnt, (uint64_t)hi0) : s.cnt) - c);
 	}
 	const uint32_t pos_base = sift_block_sum(below, scr);
-	left_nb = sift_block_sum(left_nb, scr) ? 1u : 0u;
+	if (REACH) left_nb = D ? sift_block_max(left_nb, scr) : 0u;
+	else left_nb = sift_block_sum(left_nb, scr) ? 1u : 0u;
 	// where this segment's kept anchors start in the staging arrays, and how many of them fit there
 	uint32_t stage_cap = 0xffffffffu;
 	int64_t out0 = sfirst[q] + (int64_t)pos_base;
@@ -671,7 +705,7 @@ __global__ __launch_bounds__(SIFT_THREADS) __attribute__((amdgpu_waves_per_eu(4,
 
 	if (c_reg < s0.cnt) sift_fetch<8>(pre, kb + s0.kb_off, c_reg, s0.cnt);
 	uint32_t lo = lo0, n_carry = 0, kept_total = 0, emitted = pos_base;
-	uint32_t prev_blk = left_nb ? lo0 - 1 : 0xffffffffu;      // block of the last anchor below the buffer (0xffffffff: none that matters)
+	uint32_t prev_blk = left_nb ? (REACH ? left_nb - 1u : lo0 - 1) : 0xffffffffu;      // block of the last anchor below the buffer (0xffffffff: none that matters)
 	// width of the first range: SIFT_TARGET anchors if the query's anchors were spread evenly over the genome
 	uint32_t width;
 	{
@@ -705,11 +739,11 @@ __global__ __launch_bounds__(SIFT_THREADS) __attribute__((amdgpu_waves_per_eu(4,
 #pragma unroll
 						for (int k = 0; k < 8; ++k) v[k] = pre[k];
 					} else sift_fetch<8>(v, list, c, s.cnt);
-					int32_t b = sift_place<8>(v, c, s.cnt, lo, hi, LB, (uint32_t)l, keys, &fill, SIFT_CAP);
+					int32_t b = sift_place<8, REACH>(v, c, s.cnt, lo, hi, LB, (uint32_t)l, keys, &fill, SIFT_CAP, D);
 					c += b;
 					if (b == 8)
 						while (c < s.cnt) {
-							b = sift_take<16>(list, c, s.cnt, lo, hi, LB, (uint32_t)l, keys, &fill, SIFT_CAP);
+							b = sift_take<16, REACH>(list, c, s.cnt, lo, hi, LB, (uint32_t)l, keys, &fill, SIFT_CAP, D);
 							c += b;
 							if (b < 16) break;
 						}
@@ -734,7 +768,8 @@ __global__ __launch_bounds__(SIFT_THREADS) __attribute__((amdgpu_waves_per_eu(4,
 		// ---- sort keys[0, n): into buckets by the leading bits (in arrival order), then every key counts the smaller keys of its
 		// bucket -- a dozen instructions per key where a bitonic network spends a few hundred (keys are unique: no ties)
 		{
-			int sh = 32 - __clz((int)(((hi - lo + 1u) << LB) - 1u)) - SIFT_NBK_LOG2;      // every key is below (hi - lo + 1) << LB
+			int sh = REACH ? 32 - __clz((int)(((hi - lo + D) << LB) - 1u)) - SIFT_NBK_LOG2      // every key is below (hi - lo + D) << LB (D = 1 without REACH)
+			               : 32 - __clz((int)(((hi - lo + 1u) << LB) - 1u)) - SIFT_NBK_LOG2;
 			if (sh < 0) sh = 0;
 			constexpr int BPT = SIFT_NBK / SIFT_THREADS;           // counters a thread owns in the scan
 #pragma unroll
@@ -781,9 +816,19 @@ __global__ __launch_bounds__(SIFT_THREADS) __attribute__((amdgpu_waves_per_eu(4,
 					}
 			}
 		}
-		// ---- which anchors are decided now: all of them in the segment's last range, else all below block hi - 1
+		// ---- which anchors are decided now: all of them in the segment's last range, else all below block hi - D
 		const bool last = hi == hi0;
 		uint32_t right_nb = 0;
+		if (REACH) {
+			if (last && hi0 < n_block && D > 0u) {               // the lowest block with an anchor in [hi0, hi0 + D) (the next segment's), complemented
+				for (int32_t l = t; l < nl; l += SIFT_THREADS) {
+					const SeedJobDev s = jobs[j0 + l];
+					const int32_t c = cur[c0s + l];
+					if (c < s.cnt) { const uint32_t b = kb[s.kb_off + c]; if (b - hi0 < D && ~b > right_nb) right_nb = ~b; }
+				}
+				right_nb = sift_block_max(right_nb, scr);
+			}
+		} else
 		if (last && hi0 < n_block) {                            // is there an anchor in block hi0 (it belongs to the next segment)?
 			for (int32_t l = t; l < nl; l += SIFT_THREADS) {
 				const SeedJobDev s = jobs[j0 + l];
@@ -793,7 +838,7 @@ __global__ __launch_bounds__(SIFT_THREADS) __attribute__((amdgpu_waves_per_eu(4,
 			right_nb = sift_block_sum(right_nb, scr) ? 1u : 0u;
 		}
 		uint32_t n_emit = n;
-		if (!last) {                                             // first key with local block hi - lo (= block hi - 1)
+		if (!last) {                                             // first key with local block hi - lo (= block hi - D; with D = 0 there is none)
 			const uint32_t bound = (hi - lo) << LB;
 			uint32_t a = 0, b = n;
 			while (a < b) { const uint32_t mid = (a + b) >> 1; if (keys[mid] < bound) a = mid + 1; else b = mid; }
@@ -803,8 +848,8 @@ __global__ __launch_bounds__(SIFT_THREADS) __attribute__((amdgpu_waves_per_eu(4,
 			if (t == 0) { atomicExch(&qflag[q], 1); seg_kept[blockIdx.x] = 0; seg_base[blockIdx.x] = out0; }
 			return;
 		}
-		const int64_t left0 = prev_blk == 0xffffffffu ? -(int64_t)(1 << 30) : (int64_t)prev_blk - (int64_t)lo + 1;   // local block of the anchor below the buffer
-		const int64_t right_end = last && right_nb ? (int64_t)(hi0 - lo) + 1 : ((int64_t)1 << 40);                      // ... of the one above it
+		const int64_t left0 = prev_blk == 0xffffffffu ? -(int64_t)(1 << 30) : REACH ? (int64_t)prev_blk - (int64_t)lo + (int64_t)D : (int64_t)prev_blk - (int64_t)lo + 1;   // local block of the anchor below the buffer
+		const int64_t right_end = last && right_nb ? (REACH ? (int64_t)(~right_nb - lo) + (int64_t)D : (int64_t)(hi0 - lo) + 1) : ((int64_t)1 << 40);   // ... of the one above it
 		// keep flags of the thread's keys (one per chunk of 256), the chunks' per-wave counts, one scan of those (each wave does
 		// it for itself), then the writes: two barriers per range
 		constexpr int ECH = SIFT_CAP / SIFT_THREADS;
@@ -819,7 +864,7 @@ __global__ __launch_bounds__(SIFT_THREADS) __attribute__((amdgpu_waves_per_eu(4,
 				const int64_t b = (int64_t)(keys[i] >> LB);
 				const int64_t lf = i > 0 ? (int64_t)(keys[i - 1] >> LB) : left0;
 				const int64_t rt = i + 1 < n ? (int64_t)(keys[i + 1] >> LB) : right_end;
-				keep = b - lf <= 1 || rt - b <= 1;
+				keep = REACH ? (keep_all || b - lf <= (int64_t)D || rt - b <= (int64_t)D) : (b - lf <= 1 || rt - b <= 1);
 			}
 			keepbits |= (keep ? 1u : 0u) << k;
 			const unsigned long long bal = __ballot(keep);
@@ -847,18 +892,18 @@ __global__ __launch_bounds__(SIFT_THREADS) __attribute__((amdgpu_waves_per_eu(4,
 			if (keep) {
 				const uint32_t i = (uint32_t)k * SIFT_THREADS + t, key = keys[i], l = key & lmask;
 				const uint32_t off = kept_total + first + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-				skey[out0 + off] = ((uint64_t)(uint32_t)q << nb) | (uint64_t)(lo + (key >> LB) - 1u);
+				skey[out0 + off] = ((uint64_t)(uint32_t)q << nb) | (uint64_t)(REACH ? lo + (key >> LB) - D : lo + (key >> LB) - 1u);
 				sval[out0 + off] = ((uint64_t)(emitted + i) << 32) | (uint32_t)jobs[j0 + l].qpos;
 			}
 		}
 		kept_total += n_keep;
 		// ---- the carry moves to the front (local block 0 of the next range); the range is done
-		if (n_emit > 0) prev_blk = lo + (keys[n_emit - 1] >> LB) - 1u;
+		if (n_emit > 0) prev_blk = REACH ? lo + (keys[n_emit - 1] >> LB) - D : lo + (keys[n_emit - 1] >> LB) - 1u;
 		uint32_t cv[SIFT_CARRY_MAX / SIFT_THREADS];
 #pragma unroll
 		for (int k = 0; k < SIFT_CARRY_MAX / SIFT_THREADS; ++k) {
 			const uint32_t i = n_emit + t + k * SIFT_THREADS;
-			cv[k] = i < n ? keys[i] & lmask : 0u;
+			cv[k] = i < n ? (REACH ? keys[i] - ((hi - lo) << LB) : keys[i] & lmask) : 0u;       // (block numbers relative to the next range: hi - D is its local block 0)
 		}
 		__syncthreads();
 #pragma unroll
@@ -913,6 +958,17 @@ __global__ __launch_bounds__(256) void k_sift_copy(const SiftSeg *segs, const in
 	const uint32_t n = seg_kept[sgi];
 	const int64_t from = seg_base[sgi], to = seg_out[sgi];
 	for (uint32_t i = threadIdx.x; i < n; i += 256) key[to + i] = skey[from + i], val[to + i] = sval[from + i];
+}
+// the kept anchors as mp_chain() takes them (block << 32 | query position), and their ranks in the query's full sorted list: the
+// anchors and positions of a sparse view whose forward pass runs over the kept anchors themselves (no pre-chain in between)
+__global__ __launch_bounds__(256) void k_sift_anchors(const uint64_t *key, const uint64_t *val, int64_t n, int nb, uint64_t *a, int32_t *pos)
+{
+	MPA_SHORT_KERNEL();
+	const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const uint64_t v = val[i];
+	a[i] = (key[i] & ((1ULL << nb) - 1)) << 32 | qpos_of(v);
+	if (pos) pos[i] = dropped_below(v);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("-I", dest="set_I", action="store_true")
     ap.add_argument("-G", dest="set_G", type=int, default=0, help="max intron size (miniprot -G: max_intron = bw = G)")
+    ap.add_argument("-S", dest="set_S", action="store_true", help="no splicing (miniprot -S: bw = max_intron = max_ext = 1000, io = io_end = 10000; no pre-chain)")
+    ap.add_argument("--no-pre-chain", dest="no_pre_chain", action="store_true", help="miniprot --no-pre-chain")
     ap.add_argument("--min-exons", type=int, default=1)
     ap.add_argument("--imin", type=int, default=70)
     ap.add_argument("--n-frac", type=float, default=0.0)
@@ -77,6 +79,12 @@ def main():
         mpa.lib().mpa_mapopt_set_max_intron(C.byref(mo), idx.genome_len())
     if a.set_G:
         mo.max_intron = mo.bw = a.set_G
+    if a.set_S:                                                               # (main.c:130)
+        mo.flag |= 0x1
+        mo.bw = mo.max_intron = mo.max_ext = 1000
+        mo.io = mo.io_end = 10000
+    if a.no_pre_chain:
+        mo.flag |= 0x40
     print("generate %.1fs, index build %.1fs (%d threads), genome %d bp, max_intron %d" % (t1 - t0, t2 - t1, thr, idx.genome_len(), mo.max_intron), file=sys.stderr)
     batches = [mpa.Queries(prots[i:i + a.batch], names[i:i + a.batch]) for i in range(0, len(prots), a.batch)]
     ours = None
@@ -96,8 +104,9 @@ def main():
                     ab_texts[v] = b"".join(mpa.map_batches(ctx, idx, mo, batches, thr))
                     dt, dc = time.time() - tp, time.process_time() - cp
                     clk = mpa.Context.stage_clocks()
-                    print("AB    pair %d %s=%s: %.3f s -> %.2f M aligned residues/s, %.1f host cores busy, planning %.1f ms per mini-batch (md5 %s)" %
-                          (p, knob, v, dt, aligned_residues(ab_texts[v]) / dt / 1e6, dc / dt, clk["planning"][0] / max(clk["planning"][1], 1), hashlib.md5(ab_texts[v]).hexdigest()))
+                    print("AB    pair %d %s=%s: %.3f s -> %.2f M aligned residues/s, %.1f host cores busy, planning %.1f ms per mini-batch, stage clocks [0] seeding %.1f ms [4] sketch %.1f ms per mini-batch (md5 %s)" %
+                          (p, knob, v, dt, aligned_residues(ab_texts[v]) / dt / 1e6, dc / dt, clk["planning"][0] / max(clk["planning"][1], 1), clk["seeding"][0] / max(clk["seeding"][1], 1),
+                           clk["sketch"][0] / max(clk["sketch"][1], 1), hashlib.md5(ab_texts[v]).hexdigest()))
             for v in vals.split(","):                                         # one more pass per leg with the library's timing notes on stderr
                 os.environ.pop(knob, None) if v == "-" else os.environ.__setitem__(knob, v)
                 print("==== timing notes, %s=%s" % (knob, v), file=sys.stderr, flush=True)
@@ -124,7 +133,7 @@ def main():
                 f.write(">%s\n%s\n" % (n, s if isinstance(s, str) else s.decode()))
         open(os.path.join(a.tmp, "empty.faa"), "w").close()
         exe = os.path.join(ROOT, "oracle", "_ref", "miniprot")
-        flags = ["-u"] + (["-I"] if a.set_I else []) + (["-G", str(a.set_G)] if a.set_G else [])
+        flags = ["-u"] + (["-I"] if a.set_I else []) + (["-G", str(a.set_G)] if a.set_G else []) + (["-S"] if a.set_S else []) + (["--no-pre-chain"] if a.no_pre_chain else [])
         def run(q):
             t = time.time()
             out = subprocess.run([exe, "-t%d" % ncpu] + flags + [mpi, q], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, check=True).stdout
