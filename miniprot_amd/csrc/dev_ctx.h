@@ -1,0 +1,213 @@
+// dev_ctx.h -- the HOST side that the device units of the library share (dev_ctx.hip, seed_run.hip, refine_run.hip, index_run.hip,
+// dp_exec.hip): the device context with its memory pools, what dev_ctx.hip offers the stage drivers, and the chain tail of
+// seed_run.hip that the refinement uses too.  Each unit compiles its own kernels; a kernel is launched only by the unit that
+// defines it, everything across units goes through the host functions declared here and in mpa_internal.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <time.h>
+#include <algorithm>
+#include <functional>
+#include <mutex>
+#include <thread>
+#include <atomic>
+#include <cstring>
+#include <cstdlib>
+#include <string>
+#include <vector>
+#include "mpa_internal.h"
+#include "host_core.h"
+#include "dp_device.h"
+#include "dp_plan.h"
+#include "chain_core.h"
+#include "dev_common.h"
+
+namespace mpa {
+
+struct DpPool;                            // the DP worker pool's block of device memory (dp_kernels.hip): the context only holds the pointer
+
+#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
+	set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); return MPA_ERR_HIP; } } while (0)
+
+// bytes of HBM this process holds through the pools below and the resident index, and how often a pool had to grow
+// (mpa_device_bytes / mpa_pool_growths: bench.py's hbm_resident_gb and pool_growth_events).  Process-wide, defined ONCE in dev_ctx.hip
+extern std::atomic<long long> g_dev_bytes, g_pool_growths;
+extern thread_local bool tl_alloc_failed;                 // the last pool request of this thread could not be met (device seeding then declines instead of failing)
+
+struct DevBuf {
+	void *p = nullptr;
+	size_t cap = 0;
+	// high-water mark of this pool over all contexts that play the same part in the stream pipeline (DP lane, seeder, planner):
+	// the batches of a job are alike, so what one lane needed for its pool the others will need too -- a context that has to
+	// (re)allocate sizes the pool for the largest request any of them has seen, and the first batches of a stream do the growing
+	// once for everybody instead of once per context (a growth is a hipFree: it waits for the whole device)
+	std::atomic<size_t> *hint = nullptr;
+	int ensure(size_t bytes);                // (dev_ctx.hip) at least `bytes`, with slack and the siblings' hint
+	int ensure_exact(size_t bytes);          // exactly `bytes` (the caller has added its own slack)
+	void release() { if (p) { (void)hipFree(p); g_dev_bytes -= (long long)cap; } p = nullptr, cap = 0; }
+	template<typename T> T *as() { return (T*)p; }
+};
+
+struct DeviceIndex {
+	int device = -1;
+	uint8_t *seq = nullptr;
+	int64_t *ctg_off = nullptr, *ctg_len = nullptr;
+	uint32_t *kb = nullptr;                   // k-mer occurrence lists (block ids), uploaded on first GPU seeding call
+	size_t kb_bytes = 0;
+	int64_t *ki = nullptr;                    // bucket offsets of the k-mer table, uploaded on the first device sketch (dev_sketch_jobs)
+	size_t ki_bytes = 0;
+	uint8_t *spsc = nullptr;                  // splice-score track (--spsc), uploaded with the genome when the index has one
+	size_t seq_bytes = 0, spsc_bytes = 0;     // bytes counted into g_dev_bytes for the genome and the track
+};
+
+struct HostPinned {
+	void *p = nullptr;
+	size_t cap = 0;
+	int ensure(size_t bytes) {
+		if (bytes <= cap) return MPA_OK;
+		if (p) (void)hipHostFree(p);
+		p = nullptr, cap = 0;
+		const size_t want = bytes * 3 / 2 + 4096;   // (re-pinning host memory is slow: grow in big steps)
+		if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc failed"); return MPA_ERR_HIP; }
+		cap = want;
+		return MPA_OK;
+	}
+	void release() { if (p) (void)hipHostFree(p); p = nullptr, cap = 0; }
+	template<typename T> T *as() { return (T*)p; }
+};
+
+// What a seeding call leaves for the planning stage: pinned host memory only.  In the stream pipeline the device pools belong to
+// the SEEDER (two of them), the results to the batch (one holder per batch between the start of its seeding and the end of its
+// planning), so that a batch waiting to be planned does not pin down a full set of device pools.
+struct SeedHold { HostPinned h_pos, h_f, h_pred, h_a, h_U, h_A; };
+
+struct SeedBufs {
+	DevBuf jobs, f, pred, mark, flag, idx, tmp, cfirst;
+	HostPinned h_jobs;
+	SeedHold own;                                                          // results of a call without a holder of its own (blocking path, refinement)
+	DevBuf r_win, r_chunk, r_words, r_hits, r_count;      // refinement scan
+	DevBuf r_gmap;                                        // ... the k-mer tables of long queries (k_refine_gmap_build), grow-only
+	HostPinned h_rhits;
+	DevBuf pf_qfirst2, val64[2];                                            // first kept anchor of every query; the kept anchors' values
+	DevBuf s_meta, s_cur, s_cur2, s_kept, s_base, s_out, s_flag, dkey;      // k_seed_sift: segments + per-query tables, list cursors, per-segment results, dense keys
+	HostPinned h_meta, h_back;                                             // ... their staging (up) and qfirst2 / flags / cfirst (down)
+	DevBuf k_in, k_cnt, k_bkt, k_q;                                         // device sketch (sketch_exec.hip): residue table + q_off + protein text; count and bucket per position; per-query counts, prefixes, cut-offs, flags
+	HostPinned h_kin, h_kout;                                              // ... its staging (up) and qfirst / jfirst / cut-offs / flags (down)
+	DevBuf x_all;                                                          // device chaining: views, extraction scratch, survivors, main-chain state, chains (carved up per call)
+	DevBuf rx_all, rx_keys;                                                // device refinement: pairing tables, pair keys (two buffers), chain state (carved up per call)
+	HostPinned h_xoff;                                                     // ... offsets of the chains of every query (down)
+	DevBuf c_a, c_f, c_pred, c_mark, c_flag, c_first, c_long;        // chain forward pass (k_chain_fwd, k_chain_fwd_wave: list of long runs + its counter)
+	HostPinned hc_a, hc_f, hc_pred;
+};
+
+
+} // namespace mpa
+
+using namespace mpa;
+
+struct mpa_ctx_s {
+	int device = 0;
+	hipStream_t stream = nullptr;
+	static const int kSide = 16;              // side streams: every kernel class of a batch runs concurrently
+	hipStream_t side[kSide] = {};
+	hipEvent_t ev[6] = {};
+	hipEvent_t fork_ev = nullptr;
+	hipEvent_t lev[2 * kSide] = {};           // start/stop pair per side-stream launch
+	DevBuf tasks, waves, chunks, qseq, rec, prof, tb, cig, ncig, score, extout, bnd, list, rowkey, cigd, cigoff, hkey, xg, units;
+	DevBuf lite, ckpt, wlist;                 // checkpointed traceback (dp_device.h): extension-bit words, checkpoints, the calls the walk takes
+	HostPinned h_up, h_down, h_pool;          // staging of a DP round's descriptors (host -> device) and of its results: no pageable copies, one wait
+	mpa_dp_stats_t stats = {};
+	mpa_dp_stats_t total = {};
+	size_t tb_budget = (size_t)8 << 30;       // bytes of traceback matrix per k_glob launch
+	int lite_min = 384;                       // rows from which a traceback call of <= 256 columns is checkpointed (MPA_DP_LITE_MIN; 0: never)
+	int lite_wide = 0;                        // ... 129..256 columns included (MPA_DP_LITE_WIDE; 0, the default until it has been measured: those keep the plain sweep)
+	std::vector<mpa_ctx_s*> siblings;         // extra contexts on the same device for concurrent sub-batches (owned)
+	SeedBufs seed;                            // buffers of the GPU seeding stage (seed_exec.hip)
+	hipEvent_t wait_ev = nullptr;             // blocking-sync event: a host thread that waits for the device SLEEPS (wait_stream)
+	int side_off = 0;                         // first side stream a round uses (lets the DP lanes of a stream of batches sit on different hardware queues)
+	hipStream_t seed_stream = nullptr;        // high-priority stream of the seeding kernels: short, and must not queue behind DP tails
+	bool no_split = false;                    // this mpa_dp_run() repeats a round whose workgroup hand-off timed out: 512/1024-column calls go to k_ext_huge
+	int64_t handoff_retries = 0;              // how often that has happened on this context (mpa_dp_handoff_retries)
+	std::vector<SeedHold*> holds;             // result holders of the stream pipeline's batches (owned; ctx_seed_hold)
+	struct PoolHints { std::atomic<size_t> dev[3][96]; };
+	PoolHints *hints = nullptr;               // (root context only, owned) high-water marks per pipeline role and pool
+	mpa_idx_build_stats_t idx_stats = {};     // what the last device index build on this context did (mpa_idx_build_last_stats)
+	std::vector<int64_t> idx_hist;            // ... and the histogram it planned its passes from (empty: one pass)
+	int64_t idx_budget_dbg = 0;               // (tests) exact key budget of the device index build in bytes, 0 = the default (mpa_dbg_idx_build_budget)
+	bool antidiag = false;                    // (measurement) the 32-column extension class runs on the anti-diagonal prototype, k_ext_antidiag (mpa_dbg_antidiag)
+	// ---- DP worker pool (dp_kernels.hip, k_dp_worker).  The pool itself belongs to the ROOT context of a device ...
+	mpa_ctx_s *root = nullptr;                // the context this one is a sibling of (nullptr: a root)
+	DpPool *dp_pool = nullptr;                // (root) slots + arguments of every lane, one block of device memory
+	std::mutex pool_mu;                       // (root) guards pool creation, slot numbers and the interval list
+	int pool_slots = 0;                       // (root) slots handed out
+	hipEvent_t pool_base = nullptr;           // (root) time zero of the worker launches' intervals
+	std::vector<std::pair<float, float>> pool_iv;   // (root) [start, end) of every finished worker launch of the device, ms since pool_base
+	// ... a slot, a generation counter, a word of pinned host memory and a worker stream belong to every context that runs DP rounds
+	int dp_slot = -1;
+	unsigned int dp_gen = 0;
+	int32_t *dp_done = nullptr;               // pinned: receives the generation of a round when its last unit has finished
+	hipStream_t worker_stream = nullptr;      // the lane's worker launches (never waited for by a round: its workers may be busy with other lanes' units)
+	hipEvent_t arm_ev = nullptr;
+	struct WorkerLaunch { hipEvent_t e0, e1; };
+	std::vector<WorkerLaunch> wl_busy, wl_free;   // event pairs of worker launches not yet harvested / free for reuse
+	DevBuf dp_trace;                          // (MPA_DP_TRACE) per-unit start/end ticks of the current round
+};
+
+namespace mpa {
+
+// every device pool of a context, in a fixed order (the index is the pool's identity across contexts)
+template<typename F> static void ctx_each_devbuf(mpa_ctx_s *ctx, F f)
+{
+	SeedBufs &B = ctx->seed;
+	DevBuf *all[] = { &ctx->tasks, &ctx->waves, &ctx->chunks, &ctx->qseq, &ctx->rec, &ctx->prof, &ctx->tb, &ctx->cig, &ctx->ncig,
+	                  &ctx->score, &ctx->extout, &ctx->bnd, &ctx->list, &ctx->rowkey, &ctx->cigd, &ctx->cigoff, &ctx->hkey, &ctx->xg, &ctx->units,
+	                  &B.jobs, &B.f, &B.pred, &B.mark, &B.flag, &B.idx, &B.tmp, &B.cfirst,
+	                  &B.r_win, &B.r_chunk, &B.r_words, &B.r_hits, &B.r_count,
+	                  &B.c_a, &B.c_f, &B.c_pred, &B.c_mark, &B.c_flag, &B.c_first, &B.c_long,
+	                  &B.pf_qfirst2, &B.val64[0], &B.val64[1],
+	                  &B.s_meta, &B.s_cur, &B.s_cur2, &B.s_kept, &B.s_base, &B.s_out, &B.s_flag, &B.dkey, &B.x_all, &B.rx_all, &B.rx_keys,
+	                  &ctx->lite, &ctx->ckpt, &ctx->wlist, &B.k_in, &B.k_cnt, &B.k_bkt, &B.k_q, &B.r_gmap };
+	int k = 0;
+	for (DevBuf *b : all) f(*b, k++);
+}
+
+// ---- dev_ctx.hip, for the stage drivers
+hipError_t wait_stream(mpa_ctx_t *ctx, hipStream_t s);                                   // wait for a stream, asleep
+hipError_t upload_large(void *dst, const void *src, size_t bytes, hipStream_t s);       // a large host array into device memory through pinned slices
+void ensure_seed_stream(mpa_ctx_t *ctx);                                                 // ctx->seed_stream, created on first use
+hipError_t ensure_dynamic_lds(const void *fn, int device, size_t bytes);                 // hipFuncSetAttribute(MaxDynamicSharedMemorySize), once per (kernel, device)
+void ctx_pool_report(mpa_ctx_t *root);
+void pool_harvest(mpa_ctx_t *ctx, bool wait);                                            // (dp_exec.hip) the finished worker launches of a context's DP pool
+
+// ---- the chain tail (seed_run.hip): what the three device chaining routes -- behind the pre-chain (dev_chains_on_device), without one
+// (dev_seed_direct) and the refinement (dev_refine_chains) -- do alike, and the forward pass dev_chain_forward shares with them
+PreParams pre_params(const ChainParams &cp);              // mp_chain's parameters as the forward-pass kernels take them
+// one allocation (x_all), carved up: every piece starts on a 256-byte boundary
+struct Carve {
+	size_t at = 0;
+	size_t operator()(size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; }
+};
+// k_seed_fill -> k_chain_fwd -> k_chain_fwd_wave on stream s over the n anchors `a` of n_prob problems (first / cnt as k_chain_fwd
+// takes them).  Runs longer than serial_run get a wavefront each, through the list `runs` (long_cap entries) and its counter n_runs,
+// which the caller has zeroed on s; flag is only initialised.
+struct ChainFwdBufs { int32_t *f, *pred, *mark; uint32_t *flag; LongRun *runs; unsigned int *n_runs; size_t long_cap; };
+int chain_fwd_launch(hipStream_t s, const uint64_t *a, int64_t n, const int64_t *first, const int64_t *cnt, int32_t n_prob, const PreParams &pp, int32_t serial_run,
+                     const ChainFwdBufs &b);
+// Offsets into x_all of what one extraction works in and leaves: scratch indexed like the views (m entries; `ends` and `stack` have
+// extras per problem), the per-problem status, the chains (out_a, out_u: m words each), their counts and the counts' prefixes.
+struct ExtractCarve { size_t mark, order, ends, tail8, items, moved, merged, kept, stack, status, out_a, out_u, na, nu, offa, offu; };
+ExtractCarve carve_extract_scratch(Carve &carve, size_t m, size_t n_prob);                // mark .. status; the caller zeroes status
+void carve_extract_counts(Carve &carve, size_t n_prob, ExtractCarve &c);                  // na, nu, offa, offu
+// the views of all problems on the device (ExtractArgs, seed_exec.hip): sparse (v_pos, ntot_first) or dense (both null)
+struct ChainViewDev { const int64_t *first, *cnt, *ntot_first; const int32_t *v_pos, *v_f, *v_pred; const uint64_t *v_a; };
+// k_chain_extract for n_prob problems on stream s, X = x_all.  prof_label != nullptr: with MPA_TIMING=2 the launch is profiled per phase
+// and reported under that label.
+int chain_extract_launch(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCarve &c, const ChainViewDev &v, const ChainParams &p, int32_t n_prob, int32_t set_only,
+                         const char *prof_label);
+// chain_extract_launch (chains, not the set) -> k_offsets2 -> offsets and status down (one wait) -> the chains of all problems, densely,
+// into the pinned memory of H (k_chain_pack).  status_error != nullptr: a problem that needs the host ends the call with that error
+// (MPA_ERR_UNSUPPORTED) before anything is packed; otherwise *h_status (pinned, valid until the context's next chain tail) tells the caller.
+struct ChainTailOut { std::vector<int64_t> &a_first, &u_first; const uint64_t *&A, *&U; };
+int chain_extract_pack(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCarve &c, const ChainViewDev &v, const ChainParams &p, int32_t n_prob, SeedHold &H,
+                       const char *prof_label, const char *status_error, ChainTailOut out, const int32_t **h_status);
+
+} // namespace mpa

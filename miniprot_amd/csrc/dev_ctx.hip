@@ -1,0 +1,339 @@
+// dev_ctx.hip -- the device context of the library (dev_ctx.h): creation and destruction, its memory pools and the process-wide
+// counters behind them, the sleeping stream wait, the upload of the index, the sibling contexts of a stream pipeline and their shared
+// pool hints.  No kernels: the stages are seed_run.hip, refine_run.hip, index_run.hip and dp_exec.hip.
+#include "dev_ctx.h"
+
+namespace mpa {
+
+std::atomic<long long> g_dev_bytes{0}, g_pool_growths{0};
+thread_local bool tl_alloc_failed = false;
+
+int DevBuf::ensure(size_t bytes)
+{
+	const size_t asked = bytes;
+	if (hint) {
+		size_t h = hint->load(std::memory_order_relaxed);
+		while (bytes > h && !hint->compare_exchange_weak(h, bytes, std::memory_order_relaxed)) {}
+		if (bytes <= cap) return MPA_OK;
+		// (the siblings' high-water mark is a guess about batches to come, not a need: it is taken only while it stays within
+		// twice the request -- one outlier batch on one lane must not make every lane's pool that large for the rest of the job)
+		if (h > bytes && h <= 2 * bytes) bytes = h;
+	}
+	if (bytes <= cap) return MPA_OK;
+	const double t0 = now_ms();
+	// (free, then allocate: measured -- round 3, call 18 -- a pool that keeps its old block until the stream is over and only
+	// hipMalloc()s pays 25 ms per growth instead of 6: the allocator hands the block just freed straight back, a fresh one is
+	// mapped)
+	if (p) { (void)hipFree(p); g_dev_bytes -= (long long)cap; ++g_pool_growths; }
+	p = nullptr, cap = 0;
+	// (round 5 tried an arena -- a few 8-GB chunks carved up on the host instead of ~180 hipMallocs in a cold run's first second:
+	// no gain, the cost of a cold start is the VOLUME of device memory the driver maps, ~100 GB in ~2.5 s, however it is asked for:
+	// profiles/r05_cli_cold_start.txt)
+	// (generous: growing a pool is a hipFree, which waits for the whole device and stalls every pipeline stage; the batches of a
+	// job are alike, so a third of slack makes the first allocation of a pool its last in nearly all cases -- but slack and hint
+	// are wishes: when the device cannot give that much, the bare request is tried before the call fails)
+	size_t want = bytes;
+	want += std::max<size_t>(want / 8, std::min<size_t>(want / 3, (size_t)256 << 20)) + 4096;   // a third of slack up to 256 MB, an eighth beyond (round 4: every pool carried a third: 100 GB per rank)
+	size_t free_b = 0, total_b = 0;
+	if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && want > free_b - (free_b >> 4)) want = asked + 4096;
+	hipError_t e = hipMalloc(&p, want);
+	if (e != hipSuccess && want > asked + 4096) { (void)hipGetLastError(); want = asked + 4096; e = hipMalloc(&p, want); }
+	if (e != hipSuccess) { (void)hipGetLastError(); p = nullptr, tl_alloc_failed = true; set_error(std::string("hipMalloc(") + std::to_string(want) + "): " + hipGetErrorString(e)); return MPA_ERR_HIP; }
+	cap = want;
+	g_dev_bytes += (long long)cap;
+	timing_note("    pool growth (device)", now_ms() - t0);
+	return MPA_OK;
+}
+
+int DevBuf::ensure_exact(size_t bytes)
+{
+	if (bytes <= cap) return MPA_OK;
+	if (p) { (void)hipFree(p); g_dev_bytes -= (long long)cap; ++g_pool_growths; }
+	p = nullptr, cap = 0;
+	if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); p = nullptr, tl_alloc_failed = true; set_error("hipMalloc(" + std::to_string(bytes) + ") failed"); return MPA_ERR_HIP; }
+	cap = bytes;
+	g_dev_bytes += (long long)cap;
+	return MPA_OK;
+}
+
+// Wait for everything enqueued on a stream -- asleep.  hipStreamSynchronize() spins on the completion signal by default; a
+// pipeline keeps eight or nine host threads waiting for the device at any time (DP lanes, seeders, planners), and on a host
+// that gives the process a CPU quota (16 cores per GPU on the boxes this was measured on) spinning waiters eat the very cores
+// the host stages need.  An event created with hipEventBlockingSync makes the runtime block on the signal instead.
+// Measured (round 3): even the "blocking" hipEventSynchronize costs a waiting thread about half a core, so the wait polls the
+// event and SLEEPS 100 us between polls after a short burst of immediate ones.
+hipError_t wait_stream(mpa_ctx_t *ctx, hipStream_t s)
+{
+	if (!ctx->wait_ev) return hipStreamSynchronize(s);
+	hipError_t e = hipEventRecord(ctx->wait_ev, s);
+	if (e != hipSuccess) return e;
+	for (int polls = 0;; ++polls) {
+		e = hipEventQuery(ctx->wait_ev);
+		if (e != hipErrorNotReady) return e;
+		if (polls >= 8) {
+			static const long nap_ns = [] { const char *e = getenv("MPA_POLL_US"); const long v = e ? atol(e) : 100; return (v < 1 ? 1 : v > 5000 ? 5000 : v) * 1000L; }();
+			struct timespec ts = { 0, nap_ns };
+			nanosleep(&ts, nullptr);
+		}
+	}
+}
+
+// A large host array into device memory.  The index arrays are views into the mapped .mpi (page cache) or pageable vectors: a
+// plain hipMemcpy stages them through the runtime's own bounce buffer on ONE thread (measured, round 4: the 7.6 GB of a 3 Gbp
+// index cost most of the 4.3 s a cold command-line run spends before it maps anything).  Here four host threads copy 32-MB slices
+// into two pinned buffers in turn while the DMA engine drains the other one.
+hipError_t upload_large(void *dst, const void *src, size_t bytes, hipStream_t s)
+{
+	const size_t kSlice = (size_t)32 << 20;
+	if (bytes < 4 * kSlice) return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
+	void *pin[2] = { nullptr, nullptr };
+	hipEvent_t done[2] = { nullptr, nullptr };
+	hipError_t e = hipSuccess;
+	for (int k = 0; k < 2 && e == hipSuccess; ++k) { e = hipHostMalloc(&pin[k], kSlice, hipHostMallocDefault); if (e == hipSuccess) e = hipEventCreateWithFlags(&done[k], hipEventDisableTiming); }
+	if (e == hipSuccess) {
+		const int kThreads = 4;
+		size_t at = 0;
+		for (int k = 0; at < bytes && e == hipSuccess; ++k, at += kSlice) {
+			const int b = k & 1;
+			const size_t n = std::min(kSlice, bytes - at);
+			if (k >= 2) e = hipEventSynchronize(done[b]);              // the copy that last used this buffer has left it
+			if (e != hipSuccess) break;
+			std::thread th[kThreads];
+			const size_t part = (n + kThreads - 1) / kThreads;
+			for (int t = 0; t < kThreads; ++t)
+				th[t] = std::thread([=] { const size_t o = (size_t)t * part; if (o < n) memcpy((char*)pin[b] + o, (const char*)src + at + o, std::min(part, n - o)); });
+			for (auto &t : th) t.join();
+			e = hipMemcpyAsync((char*)dst + at, pin[b], n, hipMemcpyHostToDevice, s);
+			if (e == hipSuccess) e = hipEventRecord(done[b], s);
+		}
+		if (e == hipSuccess) e = hipStreamSynchronize(s);
+	}
+	for (int k = 0; k < 2; ++k) { if (done[k]) (void)hipEventDestroy(done[k]); if (pin[k]) (void)hipHostFree(pin[k]); }
+	if (e != hipSuccess) { (void)hipGetLastError(); return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); }   // (no pinned memory to be had: the plain copy)
+	return hipSuccess;
+}
+
+// The seeding / refinement kernels of a context run on a stream of their own, created with the device's highest priority: they are
+// short and a pipeline stage waits for each of them (MPA_PRIO_SEED=0: normal priority; MPA_PRIO_MAIN=1: the contexts' main streams
+// -- the DP lanes' prep kernels, walks and copies -- get the high priority too).
+void ensure_seed_stream(mpa_ctx_t *ctx)
+{
+	if (ctx->seed_stream) return;
+	static const bool high = [] { const char *e = getenv("MPA_PRIO_SEED"); return !e || atoi(e) != 0; }();
+	int least = 0, greatest = 0;
+	(void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+	if (hipStreamCreateWithPriority(&ctx->seed_stream, hipStreamNonBlocking, high ? greatest : least) != hipSuccess) ctx->seed_stream = ctx->stream;
+}
+
+int dev_upload_index(mpa_ctx_t *ctx, mpa_idx_s *mi)
+{
+	if (ctx->device < 0 || ctx->device >= mpa_idx_s::kMaxDevices) { set_error("device number beyond what an index keeps copies for"); return MPA_ERR_UNSUPPORTED; }
+	static std::mutex mu[mpa_idx_s::kMaxDevices];             // one per device: the pipelines of several devices upload side by side
+	std::lock_guard<std::mutex> g(mu[ctx->device]);
+	if (mi->dev[ctx->device]) return MPA_OK;
+	HIP_TRY(hipSetDevice(ctx->device));
+	DeviceIndex *d = new DeviceIndex();
+	d->device = ctx->device;
+	// (an upload that fails half-way gives everything back: the caller may retry, e.g. on the host path, and must not leak HBM)
+	struct Undo { DeviceIndex *d; ~Undo() { if (!d) return; (void)hipFree(d->seq); (void)hipFree(d->ctg_off); (void)hipFree(d->ctg_len); (void)hipFree(d->spsc); delete d; } } undo{ d };
+	const size_t n = mi->ctg.size();
+	std::vector<int64_t> off(n), len(n);
+	for (size_t i = 0; i < n; ++i) off[i] = mi->ctg[i].off, len[i] = mi->ctg[i].len;
+	HIP_TRY(hipMalloc((void**)&d->seq, mi->seq.size() + 16));
+	HIP_TRY(hipMalloc((void**)&d->ctg_off, n * 8 + 8));
+	HIP_TRY(hipMalloc((void**)&d->ctg_len, n * 8 + 8));
+	{ const double t0 = now_ms(); HIP_TRY(upload_large(d->seq, mi->seq.data(), mi->seq.size(), ctx->stream)); timing_note("index upload: packed genome", now_ms() - t0); }
+	HIP_TRY(hipMemcpy(d->ctg_off, off.data(), n * 8, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(d->ctg_len, len.data(), n * 8, hipMemcpyHostToDevice));
+	if (!mi->spsc.empty()) {
+		HIP_TRY(hipMalloc((void**)&d->spsc, mi->spsc.size() + 16));
+		HIP_TRY(hipMemcpy(d->spsc, mi->spsc.data(), mi->spsc.size(), hipMemcpyHostToDevice));
+	}
+	d->seq_bytes = mi->seq.size() + 16, d->spsc_bytes = mi->spsc.empty() ? 0 : mi->spsc.size() + 16;   // (what was added is what dev_free_index takes off again)
+	mi->dev[ctx->device] = d;
+	undo.d = nullptr;
+	g_dev_bytes += (long long)(d->seq_bytes + d->spsc_bytes);
+	return MPA_OK;
+}
+
+void dev_free_index(mpa_idx_s *mi)
+{
+	for (DeviceIndex *&d : mi->dev) {
+		if (!d) continue;
+		(void)hipSetDevice(d->device);
+		(void)hipFree(d->seq); (void)hipFree(d->ctg_off); (void)hipFree(d->ctg_len);
+		g_dev_bytes -= (long long)(d->seq_bytes + d->spsc_bytes);
+		if (d->kb) { (void)hipFree(d->kb); g_dev_bytes -= (long long)d->kb_bytes; }
+		if (d->ki) { (void)hipFree(d->ki); g_dev_bytes -= (long long)d->ki_bytes; }
+		if (d->spsc) (void)hipFree(d->spsc);
+		delete d;
+		d = nullptr;
+	}
+}
+
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device: remember it per (kernel, device), under a lock -- several
+// DP lanes and seeders get here at once, and a process may hold contexts on several devices
+hipError_t ensure_dynamic_lds(const void *fn, int device, size_t bytes)
+{
+	static std::mutex mu;
+	static std::vector<std::pair<const void*, int>> done;
+	std::lock_guard<std::mutex> g(mu);
+	for (auto &d : done) if (d.first == fn && d.second == device) return hipSuccess;
+	const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+	if (e == hipSuccess) done.emplace_back(fn, device);
+	return e;
+}
+
+} // namespace mpa
+
+extern "C" {
+
+int mpa_device_count(void)
+{
+	int n = 0;
+	if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+	return n;
+}
+
+mpa_ctx_t *mpa_ctx_create(int device)
+{
+	int n = mpa_device_count();
+	if (n <= 0 || device < 0 || device >= n) {
+		set_error("no usable HIP device (the MI355X DP kernels have no CPU fallback)");
+		return nullptr;
+	}
+	if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice failed"); return nullptr; }
+	mpa_ctx_s *ctx = new mpa_ctx_s();
+	ctx->device = device;
+	static const bool main_high = [] { const char *e = getenv("MPA_PRIO_MAIN"); return e && atoi(e) != 0; }();
+	int least = 0, greatest = 0;
+	(void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+	bool ok = (main_high ? hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, greatest) : hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) == hipSuccess;
+	for (auto &e : ctx->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+	for (auto &e : ctx->lev) ok = ok && hipEventCreate(&e) == hipSuccess;
+	ok = ok && hipEventCreate(&ctx->fork_ev) == hipSuccess;
+	ok = ok && hipEventCreateWithFlags(&ctx->wait_ev, hipEventBlockingSync | hipEventDisableTiming) == hipSuccess;
+	if (!ok) {                                            // a null handle would silently alias the legacy default stream
+		set_error("creating the context's HIP streams/events failed");
+		mpa_ctx_destroy(ctx);
+		return nullptr;
+	}
+	if (const char *s = getenv("MPA_TB_BUDGET_MB")) ctx->tb_budget = (size_t)atoll(s) << 20;
+	if (const char *s = getenv("MPA_DP_LITE_MIN")) ctx->lite_min = atoi(s);
+	if (const char *s = getenv("MPA_DP_LITE_WIDE")) ctx->lite_wide = atoi(s) != 0;
+	return ctx;
+}
+
+void mpa_ctx_destroy(mpa_ctx_t *ctx)
+{
+	if (!ctx) return;
+	for (mpa_ctx_s *sb : ctx->siblings) mpa_ctx_destroy(sb);
+	ctx->siblings.clear();
+	(void)hipSetDevice(ctx->device);
+	if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+	if (ctx->worker_stream) { (void)hipStreamSynchronize(ctx->worker_stream); (void)hipStreamDestroy(ctx->worker_stream); }   // (workers exit by themselves once no slot has a unit left)
+	for (auto *v : { &ctx->wl_busy, &ctx->wl_free }) { for (auto &w : *v) { (void)hipEventDestroy(w.e0); (void)hipEventDestroy(w.e1); } v->clear(); }
+	if (ctx->arm_ev) (void)hipEventDestroy(ctx->arm_ev);
+	if (ctx->dp_done) (void)hipHostFree(ctx->dp_done);
+	if (ctx->pool_base) (void)hipEventDestroy(ctx->pool_base);
+	if (ctx->dp_pool) (void)hipFree(ctx->dp_pool);
+	ctx->dp_trace.release();
+	SeedBufs &B = ctx->seed;
+	ctx_each_devbuf(ctx, [](DevBuf &b, int) { b.release(); });
+	for (HostPinned *h : { &B.h_jobs, &B.h_rhits, &B.hc_a, &B.hc_f, &B.hc_pred, &B.h_meta, &B.h_back, &B.h_xoff, &B.h_kin, &B.h_kout, &ctx->h_up, &ctx->h_down, &ctx->h_pool }) h->release();
+	auto drop_hold = [](SeedHold &H) { for (HostPinned *h : { &H.h_pos, &H.h_f, &H.h_pred, &H.h_a, &H.h_U, &H.h_A }) h->release(); };
+	drop_hold(B.own);
+	for (SeedHold *H : ctx->holds) { drop_hold(*H); delete H; }
+	ctx->holds.clear();
+	delete ctx->hints, ctx->hints = nullptr;
+	for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
+	for (auto &e : ctx->lev) if (e) (void)hipEventDestroy(e);
+	if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
+	if (ctx->wait_ev) (void)hipEventDestroy(ctx->wait_ev);
+	for (auto &st : ctx->side) if (st) (void)hipStreamDestroy(st);
+	if (ctx->seed_stream && ctx->seed_stream != ctx->stream) (void)hipStreamDestroy(ctx->seed_stream);
+	if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+	delete ctx;
+}
+
+int mpa_idx_to_device(mpa_ctx_t *ctx, mpa_idx_t *mi) { return dev_upload_index(ctx, mi); }
+
+int64_t mpa_device_bytes(void) { return (int64_t)g_dev_bytes.load(); }
+int64_t mpa_pool_growths(void) { return (int64_t)g_pool_growths.load(); }
+
+} // extern "C"
+
+namespace mpa {
+// k-th sibling of a context: same device, own streams and buffers, created on first use
+mpa_ctx_t *ctx_sibling(mpa_ctx_t *ctx, int k)
+{
+	if (k <= 0) return ctx;
+	while ((int)ctx->siblings.size() < k) {
+		mpa_ctx_t *sb = mpa_ctx_create(ctx->device);
+		if (!sb) return nullptr;
+		sb->tb_budget = ctx->tb_budget;
+		sb->lite_min = ctx->lite_min;
+		sb->lite_wide = ctx->lite_wide;
+		sb->root = ctx;
+		ctx->siblings.push_back(sb);
+	}
+	return ctx->siblings[k - 1];
+}
+void ctx_set_side_offset(mpa_ctx_t *ctx, int off) { ctx->side_off = off; }
+// `ctx` (the root itself or one of its siblings) plays part `role` of the root's stream pipeline: 0 DP lane, 1 seeder, 2 planner
+void ctx_set_role(mpa_ctx_t *root, mpa_ctx_t *ctx, int role)
+{
+	if (!root->hints) {
+		root->hints = new mpa_ctx_s::PoolHints();
+		for (auto &r : root->hints->dev) for (auto &h : r) h.store(0);
+	}
+	mpa_ctx_s::PoolHints *H = root->hints;
+	ctx_each_devbuf(ctx, [&](DevBuf &b, int k) { b.hint = k < 96 ? &H->dev[role][k] : nullptr; });
+}
+SeedHold *ctx_seed_hold(mpa_ctx_t *ctx, int k)
+{
+	while ((int)ctx->holds.size() <= k) ctx->holds.push_back(new SeedHold());
+	return ctx->holds[(size_t)k];
+}
+
+// (MPA_TIMING) the device pools of a root context and its siblings, largest first: where the HBM of a pipeline goes
+void ctx_pool_report(mpa_ctx_t *root)
+{
+	static const char *const kName[] = { "tasks", "waves", "chunks", "qseq", "rec", "prof", "tb", "cig", "ncig", "score", "extout", "bnd", "list", "rowkey", "cigd", "cigoff", "hkey", "xg", "units",
+		"s.jobs", "s.f", "s.pred", "s.mark", "s.flag", "s.idx", "s.tmp", "s.cfirst", "s.r_win", "s.r_chunk", "s.r_words", "s.r_hits", "s.r_count",
+		"s.c_a", "s.c_f", "s.c_pred", "s.c_mark", "s.c_flag", "s.c_first", "s.c_long", "s.pf_qfirst2", "s.val64_0", "s.val64_1",
+		"s.s_meta", "s.s_cur", "s.s_cur2", "s.s_kept", "s.s_base", "s.s_out", "s.s_flag", "s.dkey", "s.x_all", "s.rx_all", "s.rx_keys", "lite", "ckpt", "wlist" };
+	std::vector<mpa_ctx_t*> all{ root };
+	for (mpa_ctx_t *sb : root->siblings) all.push_back(sb);
+	size_t grand = 0;
+	for (size_t c = 0; c < all.size(); ++c) {
+		size_t tot = 0;
+		std::vector<std::pair<size_t, int>> big;
+		ctx_each_devbuf(all[c], [&](DevBuf &b, int k) { tot += b.cap; if (b.cap >= ((size_t)64 << 20)) big.push_back({ b.cap, k }); });
+		std::sort(big.rbegin(), big.rend());
+		fprintf(stderr, "[mpa-pools] context %zu: %.2f GB;", c, tot / 1e9);
+		for (auto &x : big) fprintf(stderr, " %s %.2f", x.second < (int)(sizeof(kName) / sizeof(kName[0])) ? kName[x.second] : "?", x.first / 1e9);
+		fprintf(stderr, "\n");
+		grand += tot;
+	}
+	fprintf(stderr, "[mpa-pools] all contexts of the pipeline: %.2f GB of pools (+ the resident index)\n", grand / 1e9);
+}
+
+void ctx_absorb_sibling_stats(mpa_ctx_t *ctx)
+{
+	if (timing_on()) ctx_pool_report(ctx->root ? ctx->root : ctx);
+	pool_harvest(ctx, true);
+	for (mpa_ctx_s *sb : ctx->siblings) {
+		pool_harvest(sb, true);
+		mpa_dp_stats_t &t = ctx->total, &u = sb->total;
+		t.n_ext += u.n_ext, t.n_glob += u.n_glob, t.cells_ext += u.cells_ext, t.cells_glob += u.cells_glob, t.rows_prep += u.rows_prep;
+		t.alg_bytes_ext += u.alg_bytes_ext, t.alg_bytes_glob += u.alg_bytes_glob;
+		t.ms_prep += u.ms_prep, t.ms_ext += u.ms_ext, t.ms_glob += u.ms_glob, t.ms_backtrack += u.ms_backtrack, t.ms_total += u.ms_total;
+		t.launches_ext += u.launches_ext, t.launches_glob += u.launches_glob;
+		t.cells_ext_round += u.cells_ext_round, t.cells_glob_round += u.cells_glob_round, t.ms_round += u.ms_round, t.launches_round += u.launches_round;
+		t.n_ckpt_wide += u.n_ckpt_wide, t.cells_ckpt_wide += u.cells_ckpt_wide;
+		u = mpa_dp_stats_t();
+		ctx->handoff_retries += sb->handoff_retries, sb->handoff_retries = 0;
+	}
+}
+} // namespace mpa

@@ -1,5 +1,5 @@
 // gs32_exec.hip -- ns_global_gs32b on the device (included by dp_exec.hip).  One wavefront per call runs gs32_core.h's sweep
-// (policy CoopWave); the per-row records, the query profile and the traceback walk are the int16 path's own kernels
+// (policy CoopWave, dev_common.h); the per-row records, the query profile and the traceback walk are the int16 path's own kernels
 // (k_prep_rows, k_prep_prof, k_backtrack: the record and traceback-word formats are the same).  Not a throughput path: nothing
 // in miniprot calls the 32-bit operator (see gs32_core.h); a batch of calls still runs one wave per call side by side.
 #include "gs32_core.h"

@@ -1,4 +1,4 @@
-// mpa_internal.h -- internal declarations shared by the host pipeline and the HIP executor.
+// mpa_internal.h -- internal declarations shared by the host pipeline and the device units (dev_ctx.h lists those).
 // Not part of the C ABI (that is include/mpamd.h).
 #pragma once
 #include <cstdint>
@@ -51,7 +51,7 @@ struct CpuSpan {                                          // CPU time of the cal
 // ---- index (index.cpp) ---------------------------------------------------------------------------
 struct Contig { int64_t off, len; std::string name; };
 
-struct DeviceIndex;                  // opaque, owned by dp executor (mpa_dp.hip)
+struct DeviceIndex;                  // opaque to the host pipeline, owned by the device context (dev_ctx.h, dev_ctx.hip)
 
 // The big arrays of an index (packed genome, bucket offsets, occurrence lists): either owned (an index that was built or read
 // into memory) or a VIEW into a read-only mapping of the .mpi file (mpa_idx_restore), so that the processes of a multi-GPU job --
@@ -110,7 +110,7 @@ int64_t fetch_nt(const mpa_idx_s *mi, int32_t vid, int64_t st, int64_t en, uint8
 int32_t block2vid(const mpa_idx_s *mi, uint32_t blk);        // mp_idx_block2pos (index.c:28-44)
 int64_t idx_read_spsc(mpa_idx_s *mi, const char *fn, int32_t max_sc);   // mp_ntseq_read_spsc (ntseq.c:234-296)
 
-// ---- device executor (mpa_dp.hip) ----------------------------------------------------------------
+// ---- device context and index (dev_ctx.hip, index_run.hip) --------------------------------------
 int dev_upload_index(mpa_ctx_t *ctx, mpa_idx_s *mi);
 int dev_index_build(mpa_ctx_t *ctx, mpa_idx_s *mi);           // k-mer table of a genome-only index on the device (index.c:52-136)
 int32_t idx_plan_passes(const int64_t *hist, int32_t n_bins, int64_t budget_keys, int32_t *first_bin);   // bucket ranges of a multi-pass build (index.cpp; mpa_dbg_idx_plan_passes)
@@ -120,7 +120,7 @@ void ctx_absorb_sibling_stats(mpa_ctx_t *ctx);
 void ctx_set_side_offset(mpa_ctx_t *ctx, int off);   // which of its side streams a DP round starts with
 void ctx_set_role(mpa_ctx_t *root, mpa_ctx_t *ctx, int role);   // ctx's pools share their high-water marks with the root's other contexts of that role (0 DP lane, 1 seeder, 2 planner)
 
-// ---- GPU seeding (seed_exec.hip + the driver in dp_exec.hip) --------------------------------------
+// ---- GPU seeding, chaining and refinement (drivers: seed_run.hip, refine_run.hip) -----------------
 struct SeedJob { int64_t kb_off, dst; int32_t cnt, qpos, qid; };   // one kept seed: its occurrence list and where its anchors go
 struct PrechainSparse {              // result for a mini-batch: the chained anchors (with a predecessor, or being one), query by query
 	std::vector<int64_t> cfirst;     // [n_query + 1] offsets into the arrays below
@@ -163,7 +163,7 @@ struct RefineChains {
 };
 int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_aa_len, int32_t max_ava, const ChainParams &cp, int32_t n_query, const RefineGroupsHost &groups,
                       int64_t n_win, const RefineWindow *wins, RefineChains &out);
-// forward pass of mp_chain (chain.c:181-209) for a batch of problems on the device; see dp_exec.hip
+// forward pass of mp_chain (chain.c:181-209) for a batch of problems on the device; see seed_run.hip
 struct ChainIO { uint64_t *a = nullptr; int32_t *f = nullptr, *pred = nullptr; };   // pinned buffers of the context, valid until its next chain call
 int dev_chain_buffers(mpa_ctx_t *ctx, int64_t n, ChainIO &io);
 int dev_chain_forward(mpa_ctx_t *ctx, const ChainParams &p, int32_t n_prob, const int64_t *first, const ChainIO &io);

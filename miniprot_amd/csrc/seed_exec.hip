@@ -1,6 +1,7 @@
-// seed_exec.hip -- GPU side of the seeding stage, included by dp_exec.hip.
+// seed_exec.hip -- the sift and chain kernels of the seeding stage, included by seed_run.hip (which
+// includes dev_common.h first).  The refinement kernels are in refine_kernels.hip, the index-build kernels in index_kernels.hip.
 //
-// For a whole mini-batch at once (drivers in dp_exec.hip):
+// For a whole mini-batch at once (drivers in seed_run.hip):
 //   k_seed_sift     the anchors of a query merged from its occurrence lists in (block, seed) order -- the order of
 //                   radix_sort_mp64 over block << 32 | query position, map.c:163-178 -- and filtered in LDS: only anchors with
 //                   another one in the same or an adjacent block survive (the only ones the pre-chain can link)
@@ -17,13 +18,7 @@
 
 namespace mpa {
 
-struct U32ToU64 { __host__ __device__ uint64_t operator()(uint32_t x) const { return (uint64_t)x; } };   // scan inputs of 32-bit counts as 64-bit sums
-
 struct SeedJobDev { int64_t kb_off, dst; int32_t cnt, qpos, qid, pad; };
-
-
-
-struct PreParams { int32_t max_dist_x, max_dist_y, bw, max_skip, max_iter, kmer, bbit, is_spliced, max_dblock; float coef_log; };
 
 __device__ __forceinline__ float d_log2_poly(float x)          // mp_log2 (mppriv.h:91-99)
 {
@@ -163,7 +158,6 @@ __device__ __forceinline__ int32_t d_link_score_a(uint64_t cur, uint64_t prev, c
 // cnt != nullptr: problem q holds cnt[q] anchors from first[q] on (the slots up to first[q + 1] are unused).
 // long_runs != nullptr: a run of more than max_serial anchors is not walked here but handed to k_chain_fwd_wave (a wavefront
 // per run): one thread walking a gene locus of a few hundred anchors, window by window, is what the kernel used to wait for.
-struct LongRun { int64_t s, e, q0; };
 __global__ __launch_bounds__(256) void k_chain_fwd(const uint64_t *a, int64_t n, const int64_t *first, const int64_t *cnt, int32_t n_prob, PreParams p,
                                                    int32_t *f, int32_t *pred, int32_t *mark, int32_t max_serial = 0x7fffffff, LongRun *long_runs = nullptr,
                                                    unsigned int *n_long = nullptr, unsigned int long_cap = 0)
@@ -255,74 +249,9 @@ struct ExtractArgs {
 };
 
 // MPA_TIMING=2: wall-clock stamps of k_chain_extract's phases, 8 per problem (start, chain ends sorted, trees, extraction, end)
+// (declared in dev_common.h, where CoopWave -- the team of chain_core.h on the device, with its 2 KB of LDS scratch -- now lives)
 __device__ long long *g_extract_prof = nullptr;
 __device__ int g_extract_prof_n = 0;         // problems the buffer has room for (launches of other contexts may have more)
-
-// the team's fast scratch memory: 2 KB of LDS per wavefront (k_chain_extract is one wavefront per workgroup).  Round 6: 8 KB -> 2 KB.
-// With the 5 KB of digit tables a wave then takes 7.2 KB, so that LDS allows the five waves per SIMD the 85 VGPRs do (8 KB: three), all
-// 4 000 problems of a launch are resident at once and a wave's footprint next to the DP round's workgroups is half of what it was:
-// lone launch 11.9 -> 10.6 ms, stream +5 % (3 of 3 interleaved repeats; 512 words: the same; profiles/r06_experiments.txt).  Buckets
-// that do not fit are walked in place, as before.
-#ifndef EXTRACT_STAGE_WORDS
-#define EXTRACT_STAGE_WORDS 256
-#endif
-// (DYNAMIC LDS: with a static array the compiler knows that LDS allows three waves per SIMD and lets the registers grow to 512 / 3 --
-// 166 VGPRs, a wave that fits next to no DP workgroup's waves; with the size hidden, amdgpu_waves_per_eu below is what it allocates for)
-#define EXTRACT_LDS_BYTES (EXTRACT_STAGE_WORDS * 8 + 1280 * 4)
-__device__ __forceinline__ uint64_t *g_extract_stage()
-{
-	extern __shared__ __attribute__((aligned(16))) uint64_t mpa_extract_lds[];
-	return mpa_extract_lds;
-}
-
-// the team of chain_core.h on the device: the 64 lanes of one wavefront
-struct CoopWave {
-	static __device__ __forceinline__ int lane() { return (int)(threadIdx.x & 63); }
-	static __device__ __forceinline__ int width() { return 64; }
-	// lanes of one wave share their L1: ordering their global / LDS accesses needs no cache action, only completion + a barrier
-	static __device__ __forceinline__ void sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-	static __device__ __forceinline__ uint64_t ballot(bool p) { return __ballot(p); }
-	static __device__ __forceinline__ int rank(uint64_t m) { return __popcll(m & ((1ull << lane()) - 1ull)); }
-	static __device__ __forceinline__ int popc(uint64_t m) { return __popcll(m); }
-	static __device__ __forceinline__ int32_t reduce_max(int32_t v)
-	{
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1) { const int32_t w = __shfl_xor(v, o); v = w > v ? w : v; }
-		return v;
-	}
-	static __device__ __forceinline__ bool any(bool p) { return __ballot(p) != 0; }
-	static __device__ __forceinline__ void count(uint32_t *slot) { atomicAdd(slot, 1u); }
-	static __device__ __forceinline__ void atomic_min(int32_t *slot, int32_t v) { atomicMin(slot, v); }
-	static __device__ __forceinline__ int64_t scan_excl(int64_t v, int64_t *total)
-	{
-		int64_t inc = v;
-#pragma unroll
-		for (int o = 1; o < 64; o <<= 1) { const int64_t w = __shfl_up(inc, o); if (lane() >= o) inc += w; }
-		*total = __shfl(inc, 63);
-		return inc - v;
-	}
-	static __device__ __forceinline__ int64_t scan_max_excl(int64_t v, int64_t *total)
-	{
-		int64_t inc = v;
-#pragma unroll
-		for (int o = 1; o < 64; o <<= 1) { const int64_t w = __shfl_up(inc, o); if (lane() >= o && w > inc) inc = w; }
-		*total = __shfl(inc, 63);
-		const int64_t below = __shfl_up(inc, 1);
-		return lane() ? below : INT64_MIN;
-	}
-	static __device__ __forceinline__ void digit_rank(int d, bool have, int *rank, int *cnt)
-	{
-		unsigned long long eq = __ballot(have);                  // lanes that take part and hold the same 8-bit digit: eight ballots
-#pragma unroll
-		for (int b = 0; b < 8; ++b) { const unsigned long long m = __ballot((d >> b) & 1); eq &= ((d >> b) & 1) ? m : ~m; }
-		*rank = __popcll(eq & ((1ull << lane()) - 1ull)), *cnt = __popcll(eq);
-	}
-	static __device__ __forceinline__ int first_unset(uint64_t m) { return m == ~0ull ? 64 : __ffsll((long long)~m) - 1; }
-	static __device__ __forceinline__ int lowest(uint64_t m) { return __ffsll((long long)m) - 1; }
-	static __device__ __forceinline__ uint64_t *scratch(int64_t *cap) { *cap = EXTRACT_STAGE_WORDS; return g_extract_stage(); }
-	static __device__ __forceinline__ void mark_time(int k) { if (g_extract_prof && (int)blockIdx.x < g_extract_prof_n && lane() == 0) g_extract_prof[(int64_t)blockIdx.x * 16 + k] = (long long)wall_clock64(); }
-	static __device__ __forceinline__ void note(int k, int64_t v) { if (g_extract_prof && (int)blockIdx.x < g_extract_prof_n && lane() == 0) g_extract_prof[(int64_t)blockIdx.x * 16 + 8 + k] = (long long)v; }
-};
 
 // (8 waves per SIMD = a budget of 64 VGPRs: the compiler gets there with 2 spilled registers, where it takes 85 when asked for 4..5 waves and
 // 166 when the LDS is static.  The walk is serial and waits for memory 84 % of its time: it does not miss the registers, and everything
@@ -969,494 +898,6 @@ __global__ __launch_bounds__(256) void k_sift_anchors(const uint64_t *key, const
 	const uint64_t v = val[i];
 	a[i] = (key[i] & ((1ULL << nb) - 1)) << 32 | qpos_of(v);
 	if (pos) pos[i] = dropped_below(v);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Refinement scan (map.c:97-111 = mp_sketch_nt4 + mp_sketch_clean_orf at k = kmer2, every k-mer, base resolution): which
-// positions of a region's window end a k-mer that the query also has?  One workgroup per 2048-position chunk of a window;
-// the query's k-mer words sit in an LDS hash set, the chunk's bases (with a halo wide enough to decide the minimum ORF
-// length) in LDS as well.  A thread forms the k-mer that ENDS at its position directly from five codons -- no rolling
-// state, so chunks are independent.  Hits go to one global list (window, position, hash); the host groups and pairs them.
-// ------------------------------------------------------------------------------------------------
-struct RefineWindowDev { int64_t as; int32_t qid, vid, len, pad; };
-struct RefineChunk { int32_t win, start; };
-struct RefineTab { uint8_t t[64]; };                  // codon -> reduced residue (ns_tab_codon13), 0xff for a stop codon
-#define REFINE_CHUNK 2048
-#define REFINE_HALO 112
-#define REFINE_LCAP 384                                     /* hits a workgroup of k_refine_scan_map collects in LDS per chunk before it asks for room in the global list */
-#define REFINE_SUPER 4                                      /* chunks of one window a workgroup of k_refine_scan_map sweeps (round 5, one atomic per hit: 8 chunks measured 10.9 ms against 9.0 alone; round 6, hits collected per workgroup: see profiles/r06_experiments.txt) */
-
-__device__ __forceinline__ uint32_t d_hash32_mask(uint32_t key, uint32_t mask)     // mp_hash32_mask (sketch.c:7-16)
-{
-	key = (key + ~(key << 15)) & mask;
-	key ^= key >> 10;
-	key = (key + (key << 3)) & mask;
-	key ^= key >> 6;
-	key = (key + ~(key << 11)) & mask;
-	key ^= key >> 16;
-	return key;
-}
-
-// The k-mer maps of LONG queries live in device memory instead of LDS (past 4 096 LDS slots a workgroup's map would take the CU's
-// LDS from the DP): one open-addressing table per long query in a pool, 8 bytes per slot = (k-mer word, group), so that ONE load
-// answers a probe; same hash as the LDS maps, slots = the power of two >= 2 x entries (at least 1 024), empty = all ones.  The
-// tables of a batch are built once per batch (k_refine_gmap_build, behind one memset of the pool) and stay in L2 for the scan:
-// 1 MB for a 36 000-residue protein against 4 MiB of L2 per XCD.
-struct RefineGmap {
-	const uint2 *slots;          // the pool
-	const int64_t *desc;         // [n_query] first slot << 8 | log2(slots) of the query's table (meaningless for a query that has none)
-};
-__device__ __forceinline__ uint32_t gmap_probe(const uint2 *tab, int32_t log2, uint32_t word)     // the group of `word`, 0xffffffff = not in the table
-{
-	const uint32_t m = (1u << log2) - 1;
-	for (uint32_t slot = (word * 2654435761u) >> (32 - log2);; slot = (slot + 1) & m) {
-		const uint2 kv = tab[slot];
-		if (kv.x == word) return kv.y;
-		if (kv.x == 0xffffffffu) return 0xffffffffu;              // (at most half of the slots are taken: the walk ends)
-	}
-}
-// one workgroup column per long query (blockIdx.y); words[first[q] .. first[q + 1]) are its entries, equal words share a slot
-__global__ __launch_bounds__(256) void k_refine_gmap_build(const int64_t *first, const uint32_t *words, const int32_t *long_q, const int64_t *desc, uint32_t *pool)
-{
-	MPA_SHORT_KERNEL();
-	const int32_t q = long_q[blockIdx.y];
-	const int64_t d = desc[q], k0 = first[q], k1 = first[q + 1];
-	const int32_t log2 = (int32_t)(d & 255);
-	const uint32_t m = (1u << log2) - 1;
-	uint32_t *tab = pool + 2 * (d >> 8);                          // slot s = tab[2 s] (word), tab[2 s + 1] (entry)
-	for (int64_t k = k0 + (int64_t)blockIdx.x * 256 + threadIdx.x; k < k1; k += (int64_t)gridDim.x * 256) {
-		const uint32_t word = words[k];
-		uint32_t slot = (word * 2654435761u) >> (32 - log2);
-		for (;;) {
-			const uint32_t old = atomicCAS(&tab[2 * slot], 0xffffffffu, word);
-			if (old == 0xffffffffu) { tab[2 * slot + 1] = (uint32_t)(k - k0); break; }
-			if (old == word) break;
-			slot = (slot + 1) & m;
-		}
-	}
-}
-
-// GSET: the query's k-mer set is its table in device memory (RefineGmap), not an LDS set filled by the workgroup
-template <bool GSET>
-__device__ __forceinline__ void refine_scan_body(DevGenome g, const RefineWindowDev *wins, const RefineChunk *chunks, const int64_t *qw_first, const uint32_t *qwords,
-                                                 const RefineTab &rt, int32_t kmer, int32_t min_aa_len, int32_t hs_log2, uint4 *hits, unsigned long long *n_hits, unsigned long long cap,
-                                                 const RefineGmap gm)
-{
-	MPA_SHORT_KERNEL();
-	extern __shared__ uint32_t lds_refine[];
-	const int32_t HS = GSET ? 0 : 1 << hs_log2;
-	uint32_t *table = lds_refine;                                   // [HS] open addressing, 0xffffffff = empty
-	uint8_t *base = (uint8_t*)(table + HS);                         // [REFINE_CHUNK + 2 * REFINE_HALO] nt4 codes, 15 = outside the window
-	__shared__ uint8_t tab[64];                                    // codon -> reduced residue, 0xff = stop
-	const RefineChunk ch = chunks[blockIdx.x];
-	const RefineWindowDev w = wins[ch.win];
-	const int cid = w.vid >> 1, rev = w.vid & 1;
-	const int64_t off = g.ctg_off[cid], clen = g.ctg_len[cid];
-	if (threadIdx.x < 64) tab[threadIdx.x] = rt.t[threadIdx.x];
-	for (int k = threadIdx.x; k < HS; k += 256) table[k] = 0xffffffffu;
-	for (int k = threadIdx.x; k < REFINE_CHUNK + 2 * REFINE_HALO; k += 256) {
-		const int64_t p = (int64_t)ch.start - REFINE_HALO + k;        // window-local
-		base[k] = (p < 0 || p >= w.len) ? 15 : (uint8_t)strand_base(g.seq, off, clen, rev, w.as + p);
-	}
-	__syncthreads();
-	if (!GSET) for (int64_t k = qw_first[w.qid] + threadIdx.x; k < qw_first[w.qid + 1]; k += 256) {
-		const uint32_t word = qwords[k];
-		uint32_t slot = (word * 2654435761u) >> (32 - hs_log2);
-		for (;;) {
-			const uint32_t old = atomicCAS(&table[slot], 0xffffffffu, word);
-			if (old == 0xffffffffu || old == word) break;
-			slot = (slot + 1) & (HS - 1);
-		}
-	}
-	__syncthreads();
-	const int64_t gd = GSET ? gm.desc[w.qid] : 0;
-	const uint2 *gtab = GSET ? gm.slots + (gd >> 8) : nullptr;
-	const uint32_t mask = (1u << (4 * kmer)) - 1;
-	auto codon_at = [&](int e) -> uint32_t {                          // reduced residue of the codon whose last base is LDS index e; 0xff if none
-		const uint32_t b0 = base[e - 2], b1 = base[e - 1], b2 = base[e];
-		if ((b0 | b1 | b2) > 3) return 0xffu;
-		return tab[b0 << 4 | b1 << 2 | b2];
-	};
-	for (int t = 0; t < REFINE_CHUNK / 256; ++t) {
-		const int32_t pos = ch.start + t * 256 + (int32_t)threadIdx.x;   // window-local position of the k-mer's last base
-		if (pos >= w.len) continue;
-		const int e = pos - ch.start + REFINE_HALO;
-		uint32_t word = 0;
-		bool ok = true;
-		for (int c = kmer - 1; c >= 0; --c) {
-			const uint32_t r = codon_at(e - 3 * c);
-			if (r == 0xffu) { ok = false; break; }
-			word = word << 4 | r;
-		}
-		if (!ok) continue;
-		word &= mask;
-		bool found = false;
-		if (GSET) found = gmap_probe(gtab, (int32_t)(gd & 255), word) != 0xffffffffu;
-		else for (uint32_t slot = (word * 2654435761u) >> (32 - hs_log2);; slot = (slot + 1) & (HS - 1)) {
-			const uint32_t v = table[slot];
-			if (v == word) { found = true; break; }
-			if (v == 0xffffffffu) break;
-		}
-		if (!found) continue;
-		// the open reading frame around the k-mer must be at least min_aa_len codons long (sketch.c:64-100)
-		int32_t n = kmer;
-		for (int q = e - 3 * kmer; n < min_aa_len && q >= 2 && codon_at(q) != 0xffu; q -= 3) ++n;
-		for (int q = e + 3; n < min_aa_len && q < REFINE_CHUNK + 2 * REFINE_HALO && codon_at(q) != 0xffu; q += 3) ++n;
-		if (n < min_aa_len) continue;
-		const unsigned long long at = atomicAdd(n_hits, 1ULL);
-		if (at < cap) hits[at] = make_uint4((uint32_t)ch.win, (uint32_t)pos, d_hash32_mask(word, mask), 0u);
-	}
-}
-__global__ __launch_bounds__(256) void k_refine_scan(DevGenome g, const RefineWindowDev *wins, const RefineChunk *chunks, const int64_t *qw_first, const uint32_t *qwords,
-                                                     RefineTab rt, int32_t kmer, int32_t min_aa_len, int32_t hs_log2, uint4 *hits, unsigned long long *n_hits, unsigned long long cap)
-{
-	refine_scan_body<false>(g, wins, chunks, qw_first, qwords, rt, kmer, min_aa_len, hs_log2, hits, n_hits, cap, RefineGmap{ nullptr, nullptr });
-}
-// the same scan for the windows of long queries: the k-mer set is the query's table in device memory; LDS holds the bases only
-__global__ __launch_bounds__(256) void k_refine_scan_gset(DevGenome g, const RefineWindowDev *wins, const RefineChunk *chunks, RefineTab rt, int32_t kmer, int32_t min_aa_len,
-                                                          uint4 *hits, unsigned long long *n_hits, unsigned long long cap, RefineGmap gm)
-{
-	refine_scan_body<true>(g, wins, chunks, nullptr, nullptr, rt, kmer, min_aa_len, 0, hits, n_hits, cap, gm);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Refinement pairing on the device (mp_refine_reg, map.c:53-79): the window positions and the query positions that carry the
-// same k-mer, all pairs per k-mer unless there are too many.
-//   k_refine_scan_map   the refinement scan again, but the query's DISTINCT k-mers ("groups") sit in an LDS map word -> group, and
-//                       every hit also counts itself in wcnt[window][group]: n1 of map.c:66 needs no sort
-//   k_refine_pair_count n2 = the group's query positions; the pairs of a hit are n2 if n1 * n2 <= max_ava (32-bit product, as the
-//                       reference computes it), else none
-//   (exclusive scan)    where each hit's pairs go
-//   k_refine_pair_emit  window << 44 | window position << 22 | query position -- one radix sort of these keys is the reference's
-//                       sort of every window's pair list (map.c:80), and the window boundaries fall out of per-window counts
-//   k_refine_pair_decode  position << 32 | query position: the anchors mp_chain() takes (bbit = 0)
-// ------------------------------------------------------------------------------------------------
-struct RefineGroups {
-	const int64_t *qg_first;     // [n_query + 1] first group of every query
-	const uint32_t *gword;       // [n_group] the packed k-mer word of the group
-	const uint32_t *gfirst;      // [n_group] its first entry in qpos
-	const uint32_t *gcount;      // [n_group] how many query positions carry it
-	const uint32_t *qpos;        // query positions (index of the k-mer's last residue), group by group, ascending inside a group
-};
-
-// GMAP: the map word -> group is the query's table in device memory (RefineGmap, built by k_refine_gmap_build), not an LDS map that
-// the workgroup fills; LDS then holds bases, codons and the hit buffer only
-template <bool GMAP>
-__device__ __forceinline__ void refine_scan_map_body(DevGenome g, const RefineWindowDev *wins, const RefineChunk *chunks, RefineGroups gr, const int64_t *wg_first, const RefineTab &rt,
-                                                     int32_t kmer, int32_t min_aa_len, int32_t hs_log2, uint4 *hits, unsigned long long *n_hits, unsigned long long cap, uint32_t *wcnt,
-                                                     const int32_t n_super, const RefineGmap gm)
-{
-	MPA_SHORT_KERNEL();
-	extern __shared__ uint32_t lds_refine[];
-	const int32_t HS = GMAP ? 0 : 1 << hs_log2;
-	uint32_t *tkey = lds_refine, *tval = tkey + HS;               // open addressing: word -> group (0xffffffff = empty)
-	uint8_t *base = (uint8_t*)(tval + HS);                          // [REFINE_CHUNK + 2 * REFINE_HALO] nt4 codes, 15 = outside the window
-	uint8_t *cod = base + REFINE_CHUNK + 2 * REFINE_HALO;           // [same] reduced-alphabet code of the codon ENDING at each position, 0xff = none
-	__shared__ uint8_t tab[64];
-	// The hits of a chunk are collected in LDS and get their places in the global list with ONE returning atomic per workgroup and
-	// chunk that has any (round 5: one per hit -- 3.5 M returning atomics on one address per launch, which IS the 8 ms the kernel
-	// took: profiles/r05_pmc_summary.json, 72 % of the wave cycles waiting).  A hit beyond REFINE_LCAP takes its place directly, as
-	// before.  The order of the list means nothing: its consumers index it (k_refine_pair_count / _emit) and sort what they emit.
-	__shared__ uint4 l_hit[REFINE_LCAP];
-	__shared__ uint32_t l_n;
-	__shared__ unsigned long long l_base;
-	if (threadIdx.x == 0) l_n = 0;
-	const RefineChunk ch = chunks[blockIdx.x];
-	const RefineWindowDev w = wins[ch.win];
-	const int cid = w.vid >> 1, rev = w.vid & 1;
-	const int64_t off = g.ctg_off[cid], clen = g.ctg_len[cid];
-	if (threadIdx.x < 64) tab[threadIdx.x] = rt.t[threadIdx.x];
-	for (int k = threadIdx.x; k < HS; k += 256) tkey[k] = 0xffffffffu;
-	__syncthreads();
-	// the query's k-mer map, once per workgroup; a workgroup sweeps REFINE_SUPER consecutive chunks of its window
-	const int64_t G0 = gr.qg_first[w.qid], G1 = gr.qg_first[w.qid + 1];
-	const int64_t gd = GMAP ? gm.desc[w.qid] : 0;
-	const uint2 *gtab = GMAP ? gm.slots + (gd >> 8) : nullptr;
-	if (!GMAP) for (int64_t k = G0 + threadIdx.x; k < G1; k += 256) {
-		const uint32_t word = gr.gword[k];
-		uint32_t slot = (word * 2654435761u) >> (32 - hs_log2);
-		for (;;) {
-			const uint32_t old = atomicCAS(&tkey[slot], 0xffffffffu, word);
-			if (old == 0xffffffffu) { tval[slot] = (uint32_t)(k - G0); break; }     // (the groups' words are distinct)
-			slot = (slot + 1) & (HS - 1);
-		}
-	}
-	__syncthreads();
-	const uint32_t mask = (1u << (4 * kmer)) - 1;
-	auto codon_at = [&](int e) -> uint32_t { return cod[e]; };
-	const int64_t wc0 = wg_first[ch.win];
-	for (int32_t cstart = ch.start; cstart < w.len && cstart < ch.start + n_super * REFINE_CHUNK; cstart += REFINE_CHUNK) {
-	if (cstart != ch.start) __syncthreads();                    // (the scan of the chunk before has finished with base[] and cod[])
-	// the chunk's bases and its halo, sixteen per thread from three aligned words of the packed genome (a byte load per base before)
-	static_assert((REFINE_CHUNK + 2 * REFINE_HALO) % 16 == 0, "chunk + halo must be a multiple of 16");
-	for (int k = threadIdx.x * 16; k < REFINE_CHUNK + 2 * REFINE_HALO; k += 256 * 16) {
-		const int64_t p = (int64_t)cstart - REFINE_HALO + k;         // window position of base[k]
-		const int64_t x = w.as + p;                                    // strand position
-		const uint64_t nib = packed_window16(g.seq, g.l_seq, rev ? off + clen - 1 - x : off + x, rev ? -1 : 1, rev);
-		uint32_t o[4];
-#pragma unroll
-		for (int q = 0; q < 4; ++q) {
-			uint32_t v = 0;
-#pragma unroll
-			for (int j = 0; j < 4; ++j) {
-				const int64_t pj = p + 4 * q + j;
-				const uint32_t bb = (pj < 0 || pj >= w.len) ? 15u : (uint32_t)(nib >> (4 * (4 * q + j))) & 15u;
-				v |= bb << (8 * j);
-			}
-			o[q] = v;
-		}
-		uint32_t *dst = (uint32_t*)(base + k);                       // (k is a multiple of 16, base of 4)
-		dst[0] = o[0], dst[1] = o[1], dst[2] = o[2], dst[3] = o[3];
-	}
-	__syncthreads();
-	// the codon ending at every position, once (every k-mer and every reading-frame walk below reads these instead of three bases
-	// and the table per codon)
-	for (int e = threadIdx.x; e < REFINE_CHUNK + 2 * REFINE_HALO; e += 256) {
-		uint32_t c = 0xffu;
-		if (e >= 2) {
-			const uint32_t b0 = base[e - 2], b1 = base[e - 1], b2 = base[e];
-			if ((b0 | b1 | b2) <= 3) c = tab[b0 << 4 | b1 << 2 | b2];
-		}
-		cod[e] = (uint8_t)c;
-	}
-	__syncthreads();
-	// Who scans what: thread 3q + r (q < 85) takes the PER positions 3 PER q + r, + 3, + 6, ... -- one reading frame of a stretch of 3 PER
-	// bases -- so that the k-mer word ROLLS: one codon read per position instead of kmer (round 5: thread t took positions t, t + 256,
-	// ...: five LDS byte reads per k-mer).  Thread 255 takes the chunk's last PER positions the old way.  `run` = valid codons in a row.
-	constexpr int PER = REFINE_CHUNK / 256;
-	auto try_hit = [&](const int32_t pos, const int e, const uint32_t word) {
-		uint32_t grp = 0xffffffffu;
-		if (GMAP) grp = gmap_probe(gtab, (int32_t)(gd & 255), word);
-		else for (uint32_t slot = (word * 2654435761u) >> (32 - hs_log2);; slot = (slot + 1) & (HS - 1)) {
-			const uint32_t v = tkey[slot];
-			if (v == word) { grp = tval[slot]; break; }
-			if (v == 0xffffffffu) break;
-		}
-		if (grp == 0xffffffffu) return;
-		int32_t n = kmer;
-		for (int q = e - 3 * kmer; n < min_aa_len && q >= 2 && codon_at(q) != 0xffu; q -= 3) ++n;
-		for (int q = e + 3; n < min_aa_len && q < REFINE_CHUNK + 2 * REFINE_HALO && codon_at(q) != 0xffu; q += 3) ++n;
-		if (n < min_aa_len) return;
-		const uint4 hit = make_uint4((uint32_t)ch.win, (uint32_t)pos, (uint32_t)(G0 + grp), grp);
-		const uint32_t li = atomicAdd(&l_n, 1u);
-		if (li < REFINE_LCAP) l_hit[li] = hit;
-		else {
-			const unsigned long long at = atomicAdd(n_hits, 1ULL);
-			if (at < cap) hits[at] = hit;
-		}
-		atomicAdd(&wcnt[wc0 + grp], 1u);
-	};
-	if (threadIdx.x < 255) {
-		const int q3 = (int)threadIdx.x / 3, fr = (int)threadIdx.x - 3 * q3;
-		const int e0 = REFINE_HALO + 3 * PER * q3 + fr;              // LDS index of the last base of the thread's first k-mer
-		uint32_t word = 0;
-		int run = 0;
-		for (int c = kmer - 1; c >= 1; --c) {                         // the kmer - 1 codons before it
-			const uint32_t r = codon_at(e0 - 3 * c);
-			if (r == 0xffu) run = 0, word = 0; else word = word << 4 | r, ++run;
-		}
-#pragma unroll
-		for (int j = 0; j < PER; ++j) {
-			const int e = e0 + 3 * j;
-			const uint32_t r = codon_at(e);
-			if (r == 0xffu) { run = 0, word = 0; continue; }
-			word = (word << 4 | r) & mask, ++run;
-			const int32_t pos = cstart + e - REFINE_HALO;
-			if (run >= kmer && pos < w.len) try_hit(pos, e, word);
-		}
-	} else {
-		for (int j = 0; j < PER; ++j) {
-			const int e = REFINE_HALO + 3 * PER * 85 + j;
-			const int32_t pos = cstart + e - REFINE_HALO;
-			if (pos >= w.len) continue;
-			uint32_t word = 0;
-			bool ok = true;
-			for (int c = kmer - 1; c >= 0; --c) {
-				const uint32_t r = codon_at(e - 3 * c);
-				if (r == 0xffu) { ok = false; break; }
-				word = word << 4 | r;
-			}
-			if (ok) try_hit(pos, e, word & mask);
-		}
-	}
-	__syncthreads();
-	// (the buffer is emptied when a chunk leaves it more than half full, and behind the workgroup's last chunk)
-	const bool last_chunk = cstart + REFINE_CHUNK >= w.len || cstart + REFINE_CHUNK >= ch.start + n_super * REFINE_CHUNK;
-	const uint32_t ln = (l_n >= REFINE_LCAP / 2 || last_chunk) ? (l_n < REFINE_LCAP ? l_n : REFINE_LCAP) : 0u;
-	if (ln) {                                                   // (uniform: every thread sees the same count behind the barrier)
-		if (threadIdx.x == 0) l_base = atomicAdd(n_hits, (unsigned long long)ln);
-		__syncthreads();
-		for (uint32_t k = threadIdx.x; k < ln; k += 256) { const unsigned long long at = l_base + k; if (at < cap) hits[at] = l_hit[k]; }
-		__syncthreads();
-		if (threadIdx.x == 0) l_n = 0;
-	}
-	}
-}
-__global__ __launch_bounds__(256) void k_refine_scan_map(DevGenome g, const RefineWindowDev *wins, const RefineChunk *chunks, RefineGroups gr, const int64_t *wg_first, RefineTab rt,
-                                                         int32_t kmer, int32_t min_aa_len, int32_t hs_log2, uint4 *hits, unsigned long long *n_hits, unsigned long long cap, uint32_t *wcnt,
-                                                         const int32_t n_super)
-{
-	refine_scan_map_body<false>(g, wins, chunks, gr, wg_first, rt, kmer, min_aa_len, hs_log2, hits, n_hits, cap, wcnt, n_super, RefineGmap{ nullptr, nullptr });
-}
-// the fourth size class ("long": more groups than the largest LDS map takes)
-__global__ __launch_bounds__(256) void k_refine_scan_gmap(DevGenome g, const RefineWindowDev *wins, const RefineChunk *chunks, RefineGroups gr, const int64_t *wg_first, RefineTab rt,
-                                                          int32_t kmer, int32_t min_aa_len, uint4 *hits, unsigned long long *n_hits, unsigned long long cap, uint32_t *wcnt,
-                                                          const int32_t n_super, RefineGmap gm)
-{
-	refine_scan_map_body<true>(g, wins, chunks, gr, wg_first, rt, kmer, min_aa_len, 0, hits, n_hits, cap, wcnt, n_super, gm);
-}
-
-__global__ __launch_bounds__(256) void k_refine_pair_count(const uint4 *hits, int64_t n_hits, const int64_t *wg_first, const uint32_t *wcnt, const uint32_t *gcount, int32_t max_ava,
-                                                           uint32_t *pc, uint32_t *wpairs)
-{
-	MPA_SHORT_KERNEL();
-	const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-	if (i >= n_hits) return;
-	const uint4 h = hits[i];
-	const int32_t n1 = (int32_t)wcnt[wg_first[h.x] + h.w], n2 = (int32_t)gcount[h.z];
-	const uint32_t c = (n2 > 0 && (int32_t)((uint32_t)n1 * (uint32_t)n2) <= max_ava) ? (uint32_t)n2 : 0u;   // (the reference's 32-bit product, wrap-around and all)
-	pc[i] = c;
-	if (c) atomicAdd(&wpairs[h.x], c);
-}
-
-__global__ __launch_bounds__(256) void k_refine_pair_emit(const uint4 *hits, int64_t n_hits, const uint32_t *pc, const uint64_t *po, RefineGroups gr, uint64_t *keys)
-{
-	MPA_SHORT_KERNEL();
-	const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-	if (i >= n_hits) return;
-	const uint32_t c = pc[i];
-	if (!c) return;
-	const uint4 h = hits[i];
-	const uint64_t hi = (uint64_t)h.x << 44 | (uint64_t)h.y << 22;
-	const uint32_t *qp = gr.qpos + gr.gfirst[h.z];
-	uint64_t *dst = keys + po[i];
-	for (uint32_t j = 0; j < c; ++j) dst[j] = hi | qp[j];
-}
-
-__global__ __launch_bounds__(256) void k_refine_pair_decode(const uint64_t *keys, int64_t n, uint64_t *a)
-{
-	MPA_SHORT_KERNEL();
-	const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-	if (i < n) { const uint64_t k = keys[i]; a[i] = ((k >> 22) & 0x3fffffULL) << 32 | (k & 0x3fffffULL); }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Index build on the device (mp_idx_build: build_worker + build_bidx, index.c:52-136; mp_sketch_nt4 + mp_sketch_clean_orf,
-// sketch.c:40-100): every selected k-mer of every reading frame of both strands of every contig as (bucket << 32 | global
-// block id); sorted and de-duplicated these keys ARE the index -- kb[] is their low words (inside a bucket ascending global
-// block id = contig/strand order, then position, which is the reference's layout) and ki[] the bucket boundaries.
-// k_index_scan: one workgroup per 2 048 positions of a strand (bases + halo in LDS); a thread forms the k-mer that ends at
-// its position from `kmer` codons, hashes it, applies the modimizer test, and checks that the open reading frame around it
-// has at least min_aa_len codons by walking its frame both ways (an ORF ends at a stop codon, an ambiguous base or the
-// contig end).  Two passes over the genome: count per chunk, exclusive scan, then emit at exact offsets.
-// ------------------------------------------------------------------------------------------------
-struct IndexScanArgs {
-	DevGenome g;
-	const int64_t *chunk_first;     // [2 n_ctg + 1] first chunk of every strand
-	const uint32_t *bo;             // [2 n_ctg] block offset of every strand
-	int32_t n_strand, kmer, mod_bit, bbit, min_aa_len, halo;
-	RefineTab rt;
-};
-
-// One kernel, three modes.  INDEX_COUNT / INDEX_EMIT are the two passes above; INDEX_HIST adds the keys to a coarse histogram of
-// their buckets (bin = bucket >> hist_shift, n_bin = at most 4 096 counters in LDS behind the chunk's bases) -- what the multi-pass
-// build plans its bucket ranges from: a workgroup walks its share of the chunks (chunk, chunk + gridDim.x, ...) with its counters
-// in LDS and adds its non-zero bins to the global histogram once, one 64-bit atomic each: integers, so the sums are exact in any
-// order.  RANGED: a key whose bin lies outside [bin_lo, bin_hi) is neither counted nor written, so that a pass builds the slice of
-// the table that belongs to a contiguous range of buckets.  The one-pass build launches <INDEX_COUNT, false> and <INDEX_EMIT, false>,
-// which use nothing of IndexPassArgs.
-enum { INDEX_COUNT = 0, INDEX_EMIT = 1, INDEX_HIST = 2 };
-struct IndexPassArgs {
-	int64_t n_chunk;                // INDEX_HIST: chunks of the genome
-	unsigned long long *hist;       // INDEX_HIST: [n_bin] global histogram
-	int32_t hist_shift, n_bin;
-	uint32_t bin_lo, bin_hi;        // RANGED
-};
-
-template<int MODE, bool RANGED>
-__global__ __launch_bounds__(256) void k_index_scan(IndexScanArgs a, uint32_t *count, const uint64_t *offset, uint64_t *keys, IndexPassArgs r)
-{
-	extern __shared__ uint32_t lds_index[];
-	uint8_t *base = (uint8_t*)lds_index;                            // [REFINE_CHUNK + 2 halo] nt4 codes, 15 = outside the contig
-	__shared__ uint8_t tab[64];
-	__shared__ uint32_t n_here;
-	int64_t chunk = blockIdx.x;
-	if (MODE == INDEX_HIST)
-		for (int b = threadIdx.x; b < r.n_bin; b += 256) lds_index[(REFINE_CHUNK + 2 * a.halo) / 4 + b] = 0;   // (the halo is a multiple of 16 bases)
-	do {
-		int32_t lo = 0, hi = a.n_strand - 1;
-		while (lo < hi) { const int32_t mid = (lo + hi + 1) >> 1; if (a.chunk_first[mid] <= chunk) lo = mid; else hi = mid - 1; }
-		const int32_t strand = lo, cid = strand >> 1, rev = strand & 1;
-		const int64_t off = a.g.ctg_off[cid], clen = a.g.ctg_len[cid];
-		const int64_t start = (chunk - a.chunk_first[strand]) * REFINE_CHUNK;
-		const int32_t halo = a.halo, span = REFINE_CHUNK + 2 * halo;
-		if (threadIdx.x < 64) tab[threadIdx.x] = a.rt.t[threadIdx.x];
-		if (threadIdx.x == 0) n_here = 0;
-		for (int k = threadIdx.x; k < span; k += 256) {
-			const int64_t p = start - halo + k;
-			base[k] = (p < 0 || p >= clen) ? 15 : (uint8_t)strand_base(a.g.seq, off, clen, rev, p);
-		}
-		__syncthreads();
-		const uint32_t mask = (1u << (4 * a.kmer)) - 1, mask_mod = (1u << a.mod_bit) - 1;
-		auto codon_at = [&](int e) -> uint32_t {                      // reduced residue of the codon whose last base is LDS index e; 0xff if none
-			const uint32_t b0 = base[e - 2], b1 = base[e - 1], b2 = base[e];
-			if ((b0 | b1 | b2) > 3) return 0xffu;
-			return tab[b0 << 4 | b1 << 2 | b2];
-		};
-		const uint64_t out0 = MODE == INDEX_EMIT ? offset[chunk] : 0;
-		for (int t = 0; t < REFINE_CHUNK / 256; ++t) {
-			const int64_t pos = start + t * 256 + (int64_t)threadIdx.x; // strand-local position of the k-mer's last base
-			if (pos >= clen) continue;
-			const int e = (int)(pos - start) + halo;
-			uint32_t word = 0;
-			bool ok = true;
-			for (int c = a.kmer - 1; c >= 0; --c) {
-				const uint32_t r1 = codon_at(e - 3 * c);
-				if (r1 == 0xffu) { ok = false; break; }
-				word = word << 4 | r1;
-			}
-			if (!ok) continue;
-			const uint32_t h = d_hash32_mask(word & mask, mask);
-			if (h & mask_mod) continue;
-			if (RANGED) { const uint32_t bin = (h >> a.mod_bit) >> r.hist_shift; if (bin < r.bin_lo || bin >= r.bin_hi) continue; }
-			int32_t n = a.kmer;
-			for (int q = e - 3 * a.kmer; n < a.min_aa_len && q >= 2 && codon_at(q) != 0xffu; q -= 3) ++n;
-			for (int q = e + 3; n < a.min_aa_len && q < span && codon_at(q) != 0xffu; q += 3) ++n;
-			if (n < a.min_aa_len) continue;
-			if (MODE == INDEX_HIST) { atomicAdd(&lds_index[span / 4 + ((h >> a.mod_bit) >> r.hist_shift)], 1u); continue; }
-			const uint32_t slot = atomicAdd(&n_here, 1u);
-			if (MODE == INDEX_EMIT) keys[out0 + slot] = (uint64_t)(h >> a.mod_bit) << 32 | (uint64_t)((uint32_t)(pos >> a.bbit) + a.bo[strand]);
-		}
-		if (MODE != INDEX_HIST) break;
-		__syncthreads();                                            // (the next chunk's bases overwrite this one's)
-		chunk += gridDim.x;
-	} while (chunk < r.n_chunk);
-	if (MODE == INDEX_COUNT) {
-		__syncthreads();
-		if (threadIdx.x == 0) count[chunk] = n_here;
-	}
-	if (MODE == INDEX_HIST)
-		for (int b = threadIdx.x; b < r.n_bin; b += 256) {
-			const uint32_t v = lds_index[(REFINE_CHUNK + 2 * a.halo) / 4 + b];
-			if (v) atomicAdd(&r.hist[b], (unsigned long long)v);
-		}
-}
-
-// flag[i] = 1 where sorted key i differs from key i - 1
-__global__ __launch_bounds__(256) void k_index_flag(const uint64_t *keys, int64_t n, uint32_t *flag)
-{
-	MPA_SHORT_KERNEL();
-	const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-	if (i < n) flag[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
-}
-// the distinct keys: kb[] = their block ids, cnt[bucket] = how many per bucket
-__global__ __launch_bounds__(256) void k_index_compact(const uint64_t *keys, int64_t n, const uint32_t *flag, const uint64_t *idx, uint32_t *kb, unsigned long long *cnt)
-{
-	MPA_SHORT_KERNEL();
-	const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-	if (i >= n || !flag[i]) return;
-	kb[idx[i]] = (uint32_t)keys[i];
-	atomicAdd(&cnt[keys[i] >> 32], 1ULL);
 }
 
 } // namespace mpa

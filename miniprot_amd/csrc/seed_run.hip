@@ -1,0 +1,706 @@
+// seed_run.hip -- host drivers of the seeding stage on the device: the sketch (dev_sketch_jobs; kernels in sketch_exec.hip), the sift
+// and both chaining rounds behind the pre-chain (dev_prechain_forward) or without one (dev_seed_direct), the forward pass of mp_chain
+// for the host's chains (dev_chain_forward), and the chain tail that these routes and the refinement (refine_run.hip) share.  The
+// unit of the sift and chain kernels (seed_exec.hip): nothing else launches them.
+#include "dev_ctx.h"
+#include "seed_exec.hip"
+#include "sketch_exec.hip"
+
+namespace mpa {
+// ---- the chain tail (declared in dev_ctx.h): the forward pass of mp_chain, the extraction and the packed download, as every
+// device chaining route runs them
+PreParams pre_params(const ChainParams &cp)
+{
+	PreParams pp;
+	pp.max_dist_x = std::max(cp.max_dist_x, cp.bw), pp.max_dist_y = cp.max_dist_y;
+	if (pp.max_dist_y < cp.bw && !cp.is_spliced) pp.max_dist_y = cp.bw;
+	pp.bw = cp.bw, pp.max_skip = cp.max_skip, pp.max_iter = cp.max_iter, pp.kmer = cp.kmer, pp.bbit = cp.bbit;
+	pp.is_spliced = cp.is_spliced, pp.coef_log = cp.coef_log, pp.max_dblock = pp.max_dist_x >> cp.bbit;
+	return pp;
+}
+
+int chain_fwd_launch(hipStream_t s, const uint64_t *a, int64_t n, const int64_t *first, const int64_t *cnt, int32_t n_prob, const PreParams &pp, int32_t serial_run,
+                     const ChainFwdBufs &b)
+{
+	const unsigned nblk = (unsigned)((n + 255) / 256);
+	hipLaunchKernelGGL(k_seed_fill, dim3(nblk), dim3(256), 0, s, n, pp.kmer, b.f, b.pred, b.mark, b.flag);
+	hipLaunchKernelGGL(k_chain_fwd, dim3(nblk), dim3(256), 0, s, a, n, first, cnt, n_prob, pp, b.f, b.pred, b.mark, serial_run, b.runs, b.n_runs, (unsigned int)b.long_cap);
+	hipLaunchKernelGGL(k_chain_fwd_wave, dim3((unsigned)std::min<size_t>(b.long_cap, 65536)), dim3(64), 0, s, a, (const LongRun*)b.runs, (const unsigned int*)b.n_runs,
+	                   (unsigned int)b.long_cap, pp, b.f, b.pred, b.mark);
+	HIP_TRY(hipGetLastError());
+	return MPA_OK;
+}
+
+ExtractCarve carve_extract_scratch(Carve &carve, size_t m, size_t n_prob)
+{
+	ExtractCarve c{};
+	c.mark = carve(m * 4), c.order = carve(m * 4), c.ends = carve((m + 64 * n_prob + 64) * sizeof(Pair64)), c.tail8 = carve(m * sizeof(Pair64));
+	// (the chain layout's scratch -- packed anchors, sorted u, first positions -- is only live after the sort replay and the
+	// extraction: k_chain_extract puts it into the problem's own `moved` and `merged` lists)
+	c.items = carve(m * sizeof(SparseItem)), c.moved = carve(m * sizeof(SparseItem)), c.merged = carve(m * sizeof(SparseItem));
+	c.kept = carve(m), c.stack = carve((m / 64 + 6 * n_prob + 16) * sizeof(SortRange)), c.status = carve(n_prob * 4 + 16);
+	return c;
+}
+void carve_extract_counts(Carve &carve, size_t n_prob, ExtractCarve &c)
+{
+	c.na = carve(n_prob * 8 + 8), c.nu = carve(n_prob * 8 + 8), c.offa = carve(n_prob * 8 + 16), c.offu = carve(n_prob * 8 + 16);
+}
+
+// MPA_TIMING=2 (debug): per-phase wall clock of the extraction kernel, averaged over the problems of the launch
+static bool extract_prof_on()
+{
+	static const bool prof = [] { const char *e = getenv("MPA_TIMING"); return e && atoi(e) >= 2; }();
+	return prof;
+}
+static int extract_prof_begin(hipStream_t s, size_t NQ, long long *&d_prof)
+{
+	HIP_TRY(hipMalloc((void**)&d_prof, NQ * 128 + 64));
+	HIP_TRY(hipMemsetAsync(d_prof, 0, NQ * 128, s));
+	const int n_prof = (int)NQ;
+	HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_extract_prof_n), &n_prof, sizeof(n_prof), 0, hipMemcpyHostToDevice, s));
+	HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_extract_prof), &d_prof, sizeof(d_prof), 0, hipMemcpyHostToDevice, s));
+	return MPA_OK;
+}
+static int extract_prof_end(mpa_ctx_t *ctx, hipStream_t s, size_t NQ, long long *&d_prof, const char *what)
+{
+	std::vector<long long> h(NQ * 16);
+	HIP_TRY(hipMemcpyAsync(h.data(), d_prof, NQ * 128, hipMemcpyDeviceToHost, s));
+	HIP_TRY(wait_stream(ctx, s));
+	double sum[4] = { 0, 0, 0, 0 }, sub[4] = { 0, 0, 0, 0 }, mx = 0;
+	int64_t cnt = 0, cnt2 = 0;
+	std::vector<std::pair<double, size_t>> by_time;
+	for (size_t q = 0; q < NQ; ++q) {
+		const long long *t = &h[q * 16];
+		if (!t[4] || !t[0]) continue;
+		for (int k = 0; k < 4; ++k) sum[k] += (double)(t[k + 1] - t[k]) * 1e-5;   // 100 MHz ticks -> ms
+		mx = std::max(mx, (double)(t[4] - t[0]) * 1e-5), ++cnt;
+		by_time.emplace_back((double)(t[4] - t[0]) * 1e-5, q);
+		if (t[5] && t[6] && t[7]) {                            // the two-level sort replay: its parts (stamps 5-7 lie between 0 and 1)
+			sub[0] += (double)(t[5] - t[0]) * 1e-5, sub[1] += (double)(t[6] - t[5]) * 1e-5;
+			sub[2] += (double)(t[7] - t[6]) * 1e-5, sub[3] += (double)(t[1] - t[7]) * 1e-5, ++cnt2;
+		}
+	}
+	fprintf(stderr, "[mpa-extract-prof] %s: %lld problems; mean ms: sort replay %.2f, trees %.2f, extraction %.2f, output %.2f; slowest problem %.2f ms\n", what, (long long)cnt,
+	        sum[0] / std::max<int64_t>(cnt, 1), sum[1] / std::max<int64_t>(cnt, 1), sum[2] / std::max<int64_t>(cnt, 1), sum[3] / std::max<int64_t>(cnt, 1), mx);
+	if (cnt2) fprintf(stderr, "[mpa-extract-prof]   two-level replay (%lld problems): level-1 placement %.2f, level-1 walk %.2f, merge %.2f, level 2 %.2f ms\n", (long long)cnt2,
+	                  sub[0] / cnt2, sub[1] / cnt2, sub[2] / cnt2, sub[3] / cnt2);
+	if (!by_time.empty()) {                                   // the distribution, and what the slowest problems look like
+		std::sort(by_time.begin(), by_time.end());
+		const size_t n = by_time.size();
+		fprintf(stderr, "[mpa-extract-prof]   problem ms: p50 %.2f p90 %.2f p99 %.2f max %.2f\n", by_time[n / 2].first, by_time[n * 9 / 10].first, by_time[n * 99 / 100].first, by_time[n - 1].first);
+		for (size_t k = 0; k < std::min<size_t>(n, 6); ++k) {
+			const size_t q = by_time[n - 1 - k].second;
+			const long long *t = &h[q * 16];
+			fprintf(stderr, "[mpa-extract-prof]   slow #%zu: %.2f ms (replay %.2f [lvl2 %.2f] trees %.2f extraction %.2f output %.2f); view %lld, non-roots %lld, high scores %lld, largest level-2 bucket %lld, merged %lld\n", k,
+			        by_time[n - 1 - k].first, (double)(t[1] - t[0]) * 1e-5, t[7] ? (double)(t[1] - t[7]) * 1e-5 : 0.0, (double)(t[2] - t[1]) * 1e-5, (double)(t[3] - t[2]) * 1e-5, (double)(t[4] - t[3]) * 1e-5,
+			        t[8], t[9], t[10], t[11], t[12]);
+		}
+		const size_t q = by_time[n / 2].second;
+		const long long *t = &h[q * 16];
+		fprintf(stderr, "[mpa-extract-prof]   median problem: view %lld, non-roots %lld, high scores %lld, largest level-2 bucket %lld, merged %lld\n", t[8], t[9], t[10], t[11], t[12]);
+	}
+	long long *none = nullptr;
+	HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_extract_prof), &none, sizeof(none), 0, hipMemcpyHostToDevice, s));
+	HIP_TRY(wait_stream(ctx, s));
+	HIP_TRY(hipDeviceSynchronize());                   // (debug facility: an extraction launched by another context may still be stamping into the buffer)
+	(void)hipFree(d_prof), d_prof = nullptr;
+	return MPA_OK;
+}
+
+int chain_extract_launch(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCarve &c, const ChainViewDev &v, const ChainParams &p, int32_t n_prob, int32_t set_only,
+                         const char *prof_label)
+{
+	ExtractArgs xa;
+	xa.first = v.first, xa.cnt = v.cnt, xa.ntot_first = v.ntot_first;
+	xa.v_pos = v.v_pos, xa.v_f = v.v_f, xa.v_pred = v.v_pred, xa.v_a = v.v_a;
+	xa.mark = (int32_t*)(X + c.mark), xa.order = (int32_t*)(X + c.order), xa.ends = (Pair64*)(X + c.ends), xa.tail8 = (Pair64*)(X + c.tail8);
+	xa.items = (SparseItem*)(X + c.items), xa.moved = (SparseItem*)(X + c.moved), xa.merged = (SparseItem*)(X + c.merged);
+	xa.kept = (uint8_t*)(X + c.kept), xa.stack = (SortRange*)(X + c.stack);
+	xa.a_out = (uint64_t*)(X + c.out_a), xa.u_out = (uint64_t*)(X + c.out_u), xa.n_a = (int64_t*)(X + c.na), xa.n_u = (int64_t*)(X + c.nu);
+	xa.status = (int32_t*)(X + c.status), xa.p = p, xa.set_only = set_only;
+	const bool prof = prof_label && extract_prof_on();
+	long long *d_prof = nullptr;
+	int rc;
+	if (prof && (rc = extract_prof_begin(s, (size_t)n_prob, d_prof))) return rc;
+	hipLaunchKernelGGL(k_chain_extract, dim3((unsigned)n_prob), dim3(64), EXTRACT_LDS_BYTES, s, xa, n_prob);
+	HIP_TRY(hipGetLastError());
+	if (prof && (rc = extract_prof_end(ctx, s, (size_t)n_prob, d_prof, prof_label))) return rc;
+	return MPA_OK;
+}
+
+int chain_extract_pack(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCarve &c, const ChainViewDev &v, const ChainParams &p, int32_t n_prob, SeedHold &H,
+                       const char *prof_label, const char *status_error, ChainTailOut out, const int32_t **h_status_out)
+{
+	SeedBufs &B = ctx->seed;
+	const size_t NP = (size_t)n_prob;
+	int rc;
+	if ((rc = chain_extract_launch(ctx, s, X, c, v, p, n_prob, 0, prof_label))) return rc;
+	hipLaunchKernelGGL(k_offsets2, dim3(1), dim3(256), 0, s, (const int64_t*)(X + c.na), (const int64_t*)(X + c.nu), n_prob, (int64_t*)(X + c.offa), (int64_t*)(X + c.offu));
+	HIP_TRY(hipGetLastError());
+	// offsets + status down, then the chains themselves straight into pinned memory
+	const size_t offb = (NP + 1) * 8;
+	if ((rc = B.h_xoff.ensure(2 * offb + NP * 4 + 64))) return rc;
+	int64_t *h_offa = B.h_xoff.as<int64_t>(), *h_offu = h_offa + (NP + 1);
+	int32_t *h_status = (int32_t*)(h_offu + (NP + 1));
+	HIP_TRY(hipMemcpyAsync(h_offa, X + c.offa, offb, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h_offu, X + c.offu, offb, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h_status, X + c.status, NP * 4, hipMemcpyDeviceToHost, s));
+	HIP_TRY(wait_stream(ctx, s));
+	if (status_error)
+		for (size_t w = 0; w < NP; ++w) if (h_status[w]) { set_error(status_error); return MPA_ERR_UNSUPPORTED; }
+	const int64_t tot_a = h_offa[n_prob], tot_u = h_offu[n_prob];
+	if ((rc = H.h_A.ensure((size_t)tot_a * 8 + 64)) || (rc = H.h_U.ensure((size_t)tot_u * 8 + 64))) return rc;
+	if (tot_a > 0 || tot_u > 0) {
+		hipLaunchKernelGGL(k_chain_pack, dim3((unsigned)n_prob), dim3(256), 0, s, v.first, (const int64_t*)(X + c.na), (const int64_t*)(X + c.nu),
+		                   (const int64_t*)(X + c.offa), (const int64_t*)(X + c.offu), (const uint64_t*)(X + c.out_a), (const uint64_t*)(X + c.out_u),
+		                   H.h_A.as<uint64_t>(), H.h_U.as<uint64_t>());
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(wait_stream(ctx, s));
+	}
+	out.a_first.assign(h_offa, h_offa + n_prob + 1), out.u_first.assign(h_offu, h_offu + n_prob + 1);
+	out.A = H.h_A.as<uint64_t>(), out.U = H.h_U.as<uint64_t>();
+	if (h_status_out) *h_status_out = h_status;
+	return MPA_OK;
+}
+
+// the queries the host takes over: those an extraction declined (h_status) on top of the sift's hand-backs (h_flag, may be null)
+static void seed_mark_on_host(PrechainSparse &out, int32_t n_query, const int32_t *h_status, const int32_t *h_flag)
+{
+	bool any = !out.on_host.empty();
+	for (int32_t q = 0; q < n_query && !any; ++q) any = h_status[q] != 0;
+	if (any) {
+		if (out.on_host.empty()) out.on_host.assign((size_t)n_query, 0);
+		for (int32_t q = 0; q < n_query; ++q) if (h_status[q] || (h_flag && h_flag[q])) out.on_host[(size_t)q] = 1;
+	}
+}
+} // namespace mpa
+
+namespace mpa {
+// dev_prechain_forward() with k_seed_sift (the default).  The caller has uploaded the jobs.  Per-anchor memory: 16 bytes of
+// staging; everything behind the sift is sized by the kept anchors.  The result arrays are written by k_seed_compact straight
+// into pinned host memory (no copy kernels, no second pass over HBM).
+static int dev_chains_on_device(mpa_ctx_t *ctx, int32_t n_query, int64_t m, int64_t n2, int nb, const uint64_t *key, const uint64_t *val, const int64_t *d_qfirst,
+                                const int32_t *h_flag, const ChainParams &pre, const ChainParams &mainp, PrechainSparse &out, SeedHold &H);
+
+// The sift of a batch up to the host's first look at it: segments, k_seed_sift, k_sift_offsets, the per-query first kept anchor
+// and the hand-back flags down (one wait).  reach < 0: the pre-chain's keep rule (same or adjacent block, halved staging for large
+// queries); reach >= 0: the main chain's reach, full staging (k_seed_sift<4096, true>).  n_seg == 0 / n2 == 0: nothing (kept).
+struct SiftFront {
+	int32_t n_seg = 0;
+	int64_t n2 = 0;                                          // kept anchors of the batch
+	const SiftSeg *d_segs = nullptr;
+	const int64_t *d_qfirst = nullptr;
+	uint64_t *stage0 = nullptr, *stage1 = nullptr;
+	int64_t *h_qfirst2 = nullptr, *h_cfirst = nullptr;       // pinned: first kept anchor of every query; room for one more prefix array
+	int32_t *h_flag = nullptr;                               // pinned: the sift's hand-back flags
+	size_t meta_q = 0;
+	double t_sift = 0;
+};
+static int dev_sift_front(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_block, int nb, int32_t n_query, const int64_t *qfirst, const SeedJob *jobs, int64_t n_jobs,
+                          PrechainSparse &out, double t_begin, const int64_t *jfirst_in, int32_t reach, SiftFront &F)
+{
+	SeedBufs &B = ctx->seed;
+	hipStream_t s = ctx->seed_stream;
+	if (n_block >= 0x7fffffffu) { set_error("GPU seeding: more than 2^31 blocks"); return MPA_ERR_UNSUPPORTED; }
+	// ---- segments: a query's block space in pieces of ~seg_target anchors (evenly, the kernel adapts inside a segment)
+	const int64_t seg_target = [] { const char *e = getenv("MPA_SIFT_SEG"); const int64_t v = e ? atoll(e) : 49152; return v < 256 ? (int64_t)256 : v; }();   // (read per call: the tests flip it)
+	static thread_local std::vector<SiftSeg> segs;
+	static thread_local std::vector<int64_t> jfirst;
+	static thread_local std::vector<int32_t> qseg;
+	segs.clear();
+	int64_t n_cur = 0;                                         // cursors: one per (segment, list of its query)
+	static thread_local std::vector<int64_t> sfirst;          // first staging slot of every query (sift_stage_slots)
+	jfirst.assign((size_t)n_query + 1, 0), qseg.assign((size_t)n_query + 1, 0), sfirst.assign((size_t)n_query + 1, 0);
+	for (int32_t q = 0; q < n_query; ++q) sfirst[(size_t)q + 1] = sfirst[(size_t)q] + (reach >= 0 ? qfirst[q + 1] - qfirst[q] : sift_stage_slots(qfirst[q + 1] - qfirst[q]));
+	const int64_t n_stage = sfirst[(size_t)n_query];
+	if (jfirst_in) jfirst.assign(jfirst_in, jfirst_in + n_query + 1);      // (the jobs were made on the device: dev_sketch_jobs counted them)
+	else {
+		for (int64_t j = 0; j < n_jobs; ++j) ++jfirst[(size_t)jobs[j].qid + 1];
+		for (int32_t q = 0; q < n_query; ++q) jfirst[(size_t)q + 1] += jfirst[(size_t)q];
+	}
+	for (int32_t q = 0; q < n_query; ++q) {
+		const int64_t na = qfirst[q + 1] - qfirst[q];
+		qseg[(size_t)q] = (int32_t)segs.size();
+		if (na == 0) continue;
+		if (na >= (int64_t)1 << 31) { set_error("GPU seeding: a query with more than 2^31 anchors"); return MPA_ERR_UNSUPPORTED; }
+		const int64_t nl_q = jfirst[(size_t)q + 1] - jfirst[(size_t)q];
+		if (nl_q > (1 << 20)) { set_error("GPU seeding: a query with more than 2^20 seeds"); return MPA_ERR_UNSUPPORTED; }
+		const int64_t ns = std::min<int64_t>((na + seg_target - 1) / seg_target, n_block);
+		for (int64_t k = 0; k < ns; ++k) {
+			const uint32_t lo = (uint32_t)((uint64_t)n_block * (uint64_t)k / (uint64_t)ns), hi = (uint32_t)((uint64_t)n_block * (uint64_t)(k + 1) / (uint64_t)ns);
+			if (hi > lo) {
+				if (n_cur > INT32_MAX - nl_q) { set_error("GPU seeding: too many (segment, seed) cursors in one batch"); return MPA_ERR_UNSUPPORTED; }
+				segs.push_back(SiftSeg{ q, lo, hi, (int32_t)n_cur });
+				n_cur += nl_q;
+			}
+		}
+	}
+	qseg[(size_t)n_query] = (int32_t)segs.size();
+	const int32_t n_seg = (int32_t)segs.size();
+	if (n_seg == 0) return MPA_OK;                             // (F.n_seg stays 0)
+	// one pinned block up: qfirst | jfirst | sfirst | segments | qseg
+	const size_t meta_q = ((size_t)n_query + 1) * 8, seg_bytes = (size_t)n_seg * sizeof(SiftSeg);
+	const size_t off_jf = meta_q, off_sf = 2 * meta_q, off_seg = 3 * meta_q, off_qs = off_seg + seg_bytes, meta_bytes = off_qs + ((size_t)n_query + 1) * 4;
+	int rc;
+	// (round 6: the two staging arrays of the sift -- 8 B per staging slot each, dead once k_sift_copy has packed the kept anchors --
+	// live at the front of the chaining block, which is carved up only behind that copy: 4.4 GB less per seeder at genome scale)
+	const size_t stage_bytes = ((size_t)n_stage * 8 + 64 + 255) & ~(size_t)255;
+	if ((rc = B.h_meta.ensure(meta_bytes))) return rc;
+	char *hm = B.h_meta.as<char>();
+	memcpy(hm, qfirst, meta_q), memcpy(hm + off_jf, jfirst.data(), meta_q), memcpy(hm + off_sf, sfirst.data(), meta_q), memcpy(hm + off_seg, segs.data(), seg_bytes), memcpy(hm + off_qs, qseg.data(), ((size_t)n_query + 1) * 4);
+	if ((rc = B.s_meta.ensure(meta_bytes)) || (rc = B.s_cur.ensure((size_t)n_cur * 4 + 16)) || (rc = B.s_cur2.ensure((size_t)n_cur * 4 + 16)) ||
+	    (rc = B.s_kept.ensure((size_t)n_seg * 4)) || (rc = B.s_base.ensure((size_t)n_seg * 8)) || (rc = B.s_out.ensure(((size_t)n_seg + 1) * 8)) ||
+	    (rc = B.s_flag.ensure((size_t)n_query * 4 + 16)) || (rc = B.pf_qfirst2.ensure(meta_q)) || (rc = B.cfirst.ensure(meta_q)) ||
+	    (rc = B.x_all.ensure(2 * stage_bytes)) || (rc = B.h_back.ensure(2 * meta_q + (size_t)n_query * 4 + 64))) return rc;
+	uint64_t *const stage0 = B.x_all.as<uint64_t>(), *const stage1 = (uint64_t*)(B.x_all.as<char>() + stage_bytes);
+	HIP_TRY(hipMemcpyAsync(B.s_meta.p, hm, meta_bytes, hipMemcpyHostToDevice, s));
+	HIP_TRY(hipMemsetAsync(B.s_flag.p, 0, (size_t)n_query * 4 + 16, s));
+	const char *dm = B.s_meta.as<char>();
+	const int64_t *d_qfirst = (const int64_t*)dm, *d_jfirst = (const int64_t*)(dm + off_jf), *d_sfirst = (const int64_t*)(dm + off_sf);
+	const SiftSeg *d_segs = (const SiftSeg*)(dm + off_seg);
+	const int32_t *d_qseg = (const int32_t*)(dm + off_qs);
+	// (MPA_SIFT_CAP=2048, measurement: ranges of half the size need 18 KB of LDS instead of 37 KB -- a workgroup then fits next to
+	// four DP workgroups on a CU -- and touch the lists twice as often)
+	static const int sift_cap = [] { const char *e = getenv("MPA_SIFT_CAP"); return e ? atoi(e) : 4096; }();
+	if (reach >= 0)
+		hipLaunchKernelGGL((k_seed_sift<4096, true, uint32_t>), dim3((unsigned)n_seg), dim3(SIFT_THREADS), 0, s, d_segs, B.jobs.as<SeedJobDev>(), d_jfirst, d_qfirst, d_sfirst, d->kb, n_block, nb,
+		                   B.s_cur.as<int32_t>(), B.s_cur2.as<int32_t>(), stage0, stage1, B.s_kept.as<uint32_t>(), B.s_base.as<int64_t>(),
+		                   B.s_flag.as<int32_t>(), (uint32_t)reach);
+	else if (sift_cap == 2048)
+		hipLaunchKernelGGL(k_seed_sift<2048>, dim3((unsigned)n_seg), dim3(SIFT_THREADS), 0, s, d_segs, B.jobs.as<SeedJobDev>(), d_jfirst, d_qfirst, d_sfirst, d->kb, n_block, nb,
+		                   B.s_cur.as<int32_t>(), B.s_cur2.as<int32_t>(), stage0, stage1, B.s_kept.as<uint32_t>(), B.s_base.as<int64_t>(),
+		                   B.s_flag.as<int32_t>());
+	else
+	hipLaunchKernelGGL(k_seed_sift<4096>, dim3((unsigned)n_seg), dim3(SIFT_THREADS), 0, s, d_segs, B.jobs.as<SeedJobDev>(), d_jfirst, d_qfirst, d_sfirst, d->kb, n_block, nb,
+	                   B.s_cur.as<int32_t>(), B.s_cur2.as<int32_t>(), stage0, stage1, B.s_kept.as<uint32_t>(), B.s_base.as<int64_t>(),
+	                   B.s_flag.as<int32_t>());
+	hipLaunchKernelGGL(k_sift_offsets, dim3(1), dim3(256), 0, s, d_segs, n_seg, n_query, d_qseg, B.s_flag.as<int32_t>(), B.s_kept.as<uint32_t>(), B.s_out.as<int64_t>(),
+	                   B.pf_qfirst2.as<int64_t>());
+	HIP_TRY(hipGetLastError());
+	int64_t *h_qfirst2 = B.h_back.as<int64_t>(), *h_cfirst = h_qfirst2 + (n_query + 1);
+	int32_t *h_flag = (int32_t*)(h_cfirst + (n_query + 1));
+	HIP_TRY(hipMemcpyAsync(h_qfirst2, B.pf_qfirst2.p, meta_q, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h_flag, B.s_flag.p, (size_t)n_query * 4, hipMemcpyDeviceToHost, s));
+	HIP_TRY(wait_stream(ctx, s));
+	const double t_sift = now_ms();
+	timing_note("    seed: segments + sift (wait)", t_sift - t_begin);
+	int32_t n_declined = 0;
+	for (int32_t q = 0; q < n_query; ++q) n_declined += h_flag[q] != 0;
+	if (n_declined) {
+		out.on_host.assign((size_t)n_query, 0);
+		for (int32_t q = 0; q < n_query; ++q) out.on_host[(size_t)q] = h_flag[q] != 0;
+	}
+	F.n_seg = n_seg, F.n2 = h_qfirst2[n_query], F.d_segs = d_segs, F.d_qfirst = d_qfirst, F.stage0 = stage0, F.stage1 = stage1;
+	F.h_qfirst2 = h_qfirst2, F.h_cfirst = h_cfirst, F.h_flag = h_flag, F.meta_q = meta_q, F.t_sift = t_sift;
+	return MPA_OK;
+}
+
+static int dev_prechain_forward_sift(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_block, const PreParams &pp, int nb, int32_t n_query, const int64_t *qfirst,
+                                     const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, double t_begin, const ChainParams *pre_cp, const ChainParams *main_cp, SeedHold &H,
+                                     const int64_t *jfirst_in = nullptr)
+{
+	SeedBufs &B = ctx->seed;
+	hipStream_t s = ctx->seed_stream;
+	SiftFront F;
+	int rc = dev_sift_front(ctx, d, n_block, nb, n_query, qfirst, jobs, n_jobs, out, t_begin, jfirst_in, -1, F);
+	if (rc != MPA_OK || F.n_seg == 0 || F.n2 == 0) return rc;
+	const int32_t n_seg = F.n_seg;
+	const int64_t n2 = F.n2;
+	const SiftSeg *d_segs = F.d_segs;
+	const int64_t *d_qfirst = F.d_qfirst;
+	uint64_t *const stage0 = F.stage0, *const stage1 = F.stage1;
+	int64_t *h_cfirst = F.h_cfirst;
+	const int32_t *h_flag = F.h_flag;
+	const size_t meta_q = F.meta_q;
+	const double t_sift = F.t_sift;
+	if ((rc = B.dkey.ensure((size_t)n2 * 8)) || (rc = B.val64[0].ensure((size_t)n2 * 8)) || (rc = B.f.ensure((size_t)n2 * 4)) || (rc = B.pred.ensure((size_t)n2 * 4)) ||
+	    (rc = B.mark.ensure((size_t)n2 * 4)) || (rc = B.flag.ensure((size_t)n2 * 4)) || (rc = B.idx.ensure((size_t)n2 * 4))) return rc;
+	const unsigned nblk = (unsigned)((n2 + 255) / 256);
+	const uint64_t *key = B.dkey.as<uint64_t>();
+	const uint64_t *val = B.val64[0].as<uint64_t>();
+	hipLaunchKernelGGL(k_sift_copy, dim3((unsigned)n_seg), dim3(256), 0, s, d_segs, B.s_flag.as<int32_t>(), B.s_kept.as<uint32_t>(), B.s_base.as<int64_t>(), B.s_out.as<int64_t>(),
+	                   stage0, stage1, B.dkey.as<uint64_t>(), B.val64[0].as<uint64_t>());
+	hipLaunchKernelGGL(k_seed_fill, dim3(nblk), dim3(256), 0, s, n2, pp.kmer, B.f.as<int32_t>(), B.pred.as<int32_t>(), B.mark.as<int32_t>(), B.flag.as<uint32_t>());
+	hipLaunchKernelGGL(k_prechain_fwd<uint64_t>, dim3(nblk), dim3(256), 0, s, key, val, n2, nb, B.pf_qfirst2.as<int64_t>(), pp, B.f.as<int32_t>(), B.pred.as<int32_t>(),
+	                   B.mark.as<int32_t>(), B.flag.as<uint32_t>());
+	HIP_TRY(hipGetLastError());
+	size_t scan_bytes = 0;
+	HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, B.flag.as<uint32_t>(), B.idx.as<uint32_t>(), 0u, (size_t)n2, rocprim::plus<uint32_t>(), s));
+	if ((rc = B.tmp.ensure(scan_bytes + 256))) return rc;
+	HIP_TRY(rocprim::exclusive_scan(B.tmp.p, scan_bytes, B.flag.as<uint32_t>(), B.idx.as<uint32_t>(), 0u, (size_t)n2, rocprim::plus<uint32_t>(), s));
+	hipLaunchKernelGGL(k_seed_bounds, dim3((unsigned)(n_query / 256 + 1)), dim3(256), 0, s, B.pf_qfirst2.as<int64_t>(), n_query, n2, B.idx.as<uint32_t>(), B.flag.as<uint32_t>(),
+	                   B.cfirst.as<int64_t>());
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(h_cfirst, B.cfirst.p, meta_q, hipMemcpyDeviceToHost, s));
+	HIP_TRY(wait_stream(ctx, s));
+	const double t_kernels = now_ms();
+	memcpy(out.cfirst.data(), h_cfirst, meta_q);
+	const int64_t m = out.cfirst[n_query];
+	out.m = m;
+	timing_note("    seed: copy + pre-chain + scan (wait)", t_kernels - t_sift);
+	if (m == 0) return MPA_OK;
+	// both chaining rounds on the device (main_cp == nullptr: the caller wants the pre-chain's linked anchors, as rounds 1-2 did)
+	{
+		if (main_cp && pre_cp) {
+			rc = dev_chains_on_device(ctx, n_query, m, n2, nb, key, val, d_qfirst, h_flag, *pre_cp, *main_cp, out, H);
+			if (rc != MPA_ERR_UNSUPPORTED) { timing_note("    seed: chains on the device", now_ms() - t_kernels); return rc; }
+		}
+	}
+	if ((rc = H.h_pos.ensure((size_t)m * 4)) || (rc = H.h_f.ensure((size_t)m * 4)) || (rc = H.h_pred.ensure((size_t)m * 4)) || (rc = H.h_a.ensure((size_t)m * 8))) return rc;
+	hipLaunchKernelGGL((k_seed_compact<uint64_t, true>), dim3(nblk), dim3(256), 0, s, key, val, n2, nb, B.pf_qfirst2.as<int64_t>(), B.flag.as<uint32_t>(), B.idx.as<uint32_t>(),
+	                   B.f.as<int32_t>(), B.pred.as<int32_t>(), H.h_pos.as<int32_t>(), H.h_f.as<int32_t>(), H.h_pred.as<int32_t>(), H.h_a.as<uint64_t>());
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(wait_stream(ctx, s));
+	out.pos = H.h_pos.as<int32_t>(), out.f = H.h_f.as<int32_t>(), out.pred = H.h_pred.as<int32_t>(), out.a = H.h_a.as<uint64_t>();
+	timing_note("    seed: compact into pinned memory", now_ms() - t_kernels);
+	return MPA_OK;
+}
+
+// Both chaining rounds of every query on the device, behind the forward pass of the pre-chain (map.c:186-196):
+//   k_seed_compact      the linked anchors of every query as a sparse view (position in the full list, f, pred, anchor), in HBM
+//   k_chain_extract     pre-chain extraction (set): the survivors of every query, ascending
+//   k_chain_fwd         forward pass of the main chain over them (block anchors, max_dist_x = max_intron)
+//   k_chain_extract     main-chain extraction: chains (score, count) and their anchors, sorted by first target position
+//   k_offsets2 + k_chain_pack   the chains of all queries, densely, into pinned host memory
+// What travels back is what mp_reg_gen_from_block() consumes (a few hundred anchors per query) instead of every linked anchor
+// (~11 000 per query at 3 Gbp), and the host no longer spends a core-second per mini-batch on chaining.
+// key/val: the kept anchors (dense, sorted), with B.f / B.pred / B.flag / B.idx / B.cfirst from the pre-chain's forward pass.
+static int dev_chains_on_device(mpa_ctx_t *ctx, int32_t n_query, int64_t m, int64_t n2, int nb, const uint64_t *key, const uint64_t *val, const int64_t *d_qfirst,
+                                const int32_t *h_flag, const ChainParams &pre, const ChainParams &mainp, PrechainSparse &out, SeedHold &H)
+{
+	SeedBufs &B = ctx->seed;
+	hipStream_t s = ctx->seed_stream;
+	if (mainp.bbit != pre.bbit || mainp.kmer != pre.kmer) { set_error("device chains: pre-chain and main chain disagree on the anchors"); return MPA_ERR_UNSUPPORTED; }
+	// ---- one allocation, carved up: everything is indexed like the view (m entries), `ends` and `stack` have extras per problem
+	const size_t M = (size_t)m, NQ = (size_t)n_query;
+	Carve carve;
+	const size_t o_vpos = carve(M * 8), o_vf = o_vpos + M * 4, o_vpred = carve(M * 4), o_va = carve(M * 8);
+	ExtractCarve xc = carve_extract_scratch(carve, M, NQ);
+	const size_t o_pre_a = carve(M * 8), o_pre_u = carve(M * 8), o_pre_na = carve(NQ * 8 + 8), o_pre_nu = carve(NQ * 8 + 8);
+	const size_t o_mf = carve(M * 4), o_mpred = carve(M * 4), o_mmark = carve(M * 4);
+	const int32_t kSerialRun = 48;                          // longer runs of the main chain get a wavefront each (k_chain_fwd_wave)
+	const size_t long_cap = M / (size_t)(kSerialRun + 1) + 16, o_long = carve(long_cap * sizeof(LongRun)), o_nlong = carve(64);
+	// (the main chains go where the pre-chain's view was: it is dead once the pre-chain has been extracted)
+	xc.out_a = o_va, xc.out_u = o_vpos;
+	carve_extract_counts(carve, NQ, xc);
+	int rc;
+	if ((rc = B.x_all.ensure(carve.at))) return rc;         // (ensure() adds a third of slack: a re-allocation is a hipFree, which waits for the whole device)
+	char *X = B.x_all.as<char>();
+	HIP_TRY(hipMemsetAsync(X + xc.status, 0, NQ * 4 + 16, s));
+	const unsigned nblk2 = (unsigned)((n2 + 255) / 256);
+	// the sparse view of the pre-chain's forward pass
+	hipLaunchKernelGGL((k_seed_compact<uint64_t, true>), dim3(nblk2), dim3(256), 0, s, key, val, n2, nb, B.pf_qfirst2.as<int64_t>(), B.flag.as<uint32_t>(), B.idx.as<uint32_t>(),
+	                   B.f.as<int32_t>(), B.pred.as<int32_t>(), (int32_t*)(X + o_vpos), (int32_t*)(X + o_vf), (int32_t*)(X + o_vpred), (uint64_t*)(X + o_va));
+	// pre-chain extraction (the survivors as a set): into the pre_* arrays, over the scratch the main chain's extraction uses again
+	ExtractCarve pc = xc;
+	pc.out_a = o_pre_a, pc.out_u = o_pre_u, pc.na = o_pre_na, pc.nu = o_pre_nu;
+	const ChainViewDev pre_view{ B.cfirst.as<int64_t>(), nullptr, d_qfirst, (const int32_t*)(X + o_vpos), (const int32_t*)(X + o_vf), (const int32_t*)(X + o_vpred), (const uint64_t*)(X + o_va) };
+	if ((rc = chain_extract_launch(ctx, s, X, pc, pre_view, pre, n_query, 1, "pre-chain"))) return rc;
+	// the main chain over the survivors: forward pass ...
+	const PreParams pm = pre_params(mainp);
+	HIP_TRY(hipMemsetAsync(X + o_nlong, 0, 64, s));
+	if ((rc = chain_fwd_launch(s, (const uint64_t*)(X + o_pre_a), m, B.cfirst.as<int64_t>(), (const int64_t*)(X + o_pre_na), n_query, pm, kSerialRun,
+	                           ChainFwdBufs{ (int32_t*)(X + o_mf), (int32_t*)(X + o_mpred), (int32_t*)(X + o_mmark), (uint32_t*)(X + xc.mark), (LongRun*)(X + o_long), (unsigned int*)(X + o_nlong), long_cap }))) return rc;
+	// ... and extraction: dense views over the survivors; the chains of all queries into pinned memory
+	const ChainViewDev main_view{ B.cfirst.as<int64_t>(), (const int64_t*)(X + o_pre_na), nullptr, nullptr, (const int32_t*)(X + o_mf), (const int32_t*)(X + o_mpred), (const uint64_t*)(X + o_pre_a) };
+	const int32_t *h_status = nullptr;
+	if ((rc = chain_extract_pack(ctx, s, X, xc, main_view, mainp, n_query, H, "main chain", nullptr, ChainTailOut{ out.a_first, out.u_first, out.A, out.U }, &h_status))) return rc;
+	out.has_chains = true;
+	seed_mark_on_host(out, n_query, h_status, h_flag);
+	return MPA_OK;
+}
+
+// Seeding without a pre-chain (map.c:186 skips it with -S and --no-pre-chain), on the seeding stream:
+//   k_seed_sift<4096, true>   the anchors of every query in sorted order, those kept that have another one within the main chain's reach
+//   k_sift_offsets, k_sift_copy   ... densely; k_sift_anchors: block << 32 | query position, and the rank the sift carried
+//   k_chain_fwd + k_chain_fwd_wave   forward pass of the MAIN chain over the kept anchors (the kernels of dev_chains_on_device, unchanged)
+//   k_chain_extract     main-chain extraction from a SPARSE view: every kept anchor at its rank in the query's full list (set_only = 0)
+//   k_offsets2 + k_chain_pack   the chains of all queries, densely, into pinned host memory
+// The view holds ALL kept anchors, not only those the pass linked: a kept anchor without a link is a root like an absent one, the
+// extraction steps over both alike, and a second compaction would cost a scan and a pass over the view to save part of one.
+// Exact because a dropped anchor has no anchor of its query within max_dist_x: it has no predecessor, is nobody's predecessor and
+// lies in no window that a kept anchor's max_skip / max_iter walk visits -- what a sparse view may leave out (chain_core.h).
+// pm: the main chain's parameters as the forward pass takes them (pm.max_dblock = the sift's reach).
+static int dev_seed_direct_impl(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_block, const PreParams &pm, int nb, int32_t n_query, const int64_t *qfirst, const SeedJob *jobs,
+                                int64_t n_jobs, PrechainSparse &out, double t_begin, const ChainParams &mainp, SeedHold &H, const int64_t *jfirst_in, SiftKept *kept)
+{
+	SeedBufs &B = ctx->seed;
+	hipStream_t s = ctx->seed_stream;
+	SiftFront F;
+	int rc = dev_sift_front(ctx, d, n_block, nb, n_query, qfirst, jobs, n_jobs, out, t_begin, jfirst_in, pm.max_dblock, F);
+	if (rc != MPA_OK || F.n_seg == 0) return rc;
+	if (kept) for (int32_t q = 0; q < n_query; ++q) kept->flag[(size_t)q] = F.h_flag[q] != 0;
+	if (F.n2 == 0) return MPA_OK;
+	const int64_t n2 = F.n2;
+	const size_t M = (size_t)n2, NQ = (size_t)n_query;
+	if ((rc = B.dkey.ensure(M * 8)) || (rc = B.val64[0].ensure(M * 8))) return rc;
+	hipLaunchKernelGGL(k_sift_copy, dim3((unsigned)F.n_seg), dim3(256), 0, s, F.d_segs, B.s_flag.as<int32_t>(), B.s_kept.as<uint32_t>(), B.s_base.as<int64_t>(), B.s_out.as<int64_t>(),
+	                   F.stage0, F.stage1, B.dkey.as<uint64_t>(), B.val64[0].as<uint64_t>());
+	HIP_TRY(hipGetLastError());
+	if (kept) {                                                // (test hook: the kept anchors of every query, as the chain would take them)
+		std::vector<uint64_t> hk(M), hv(M);
+		HIP_TRY(hipMemcpyAsync(hk.data(), B.dkey.p, M * 8, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(hv.data(), B.val64[0].p, M * 8, hipMemcpyDeviceToHost, s));
+		HIP_TRY(wait_stream(ctx, s));
+		kept->first.assign(F.h_qfirst2, F.h_qfirst2 + n_query + 1), kept->a.resize(M);
+		for (size_t i = 0; i < M; ++i) kept->a[i] = (hk[i] & ((1ULL << nb) - 1)) << 32 | (uint32_t)hv[i];
+		return MPA_OK;
+	}
+	// ---- one allocation, carved up, as in dev_chains_on_device: the view (= the forward pass's own arrays), the extraction's scratch, the chains
+	Carve carve;
+	const size_t o_vpos = carve(M * 4), o_vf = carve(M * 4), o_vpred = carve(M * 4), o_va = carve(M * 8), o_fmark = carve(M * 4);
+	ExtractCarve xc = carve_extract_scratch(carve, M, NQ);
+	const int32_t kSerialRun = 48;                          // longer runs get a wavefront each (k_chain_fwd_wave)
+	const size_t long_cap = M / (size_t)(kSerialRun + 1) + 16, o_long = carve(long_cap * sizeof(LongRun)), o_nlong = carve(64);
+	xc.out_a = carve(M * 8), xc.out_u = carve(M * 8);
+	carve_extract_counts(carve, NQ, xc);
+	// (the sift's staging sits at the front of this block: if the block has to move, k_sift_copy must have read it first)
+	if (carve.at > B.x_all.cap) HIP_TRY(wait_stream(ctx, s));
+	if ((rc = B.x_all.ensure(carve.at))) return rc;
+	char *X = B.x_all.as<char>();
+	const unsigned nblk = (unsigned)((n2 + 255) / 256);
+	const int64_t *d_first = B.pf_qfirst2.as<int64_t>();       // first kept anchor of every query (k_sift_offsets)
+	HIP_TRY(hipMemsetAsync(X + xc.status, 0, NQ * 4 + 16, s));
+	HIP_TRY(hipMemsetAsync(X + o_nlong, 0, 64, s));
+	hipLaunchKernelGGL(k_sift_anchors, dim3(nblk), dim3(256), 0, s, B.dkey.as<uint64_t>(), B.val64[0].as<uint64_t>(), n2, nb, (uint64_t*)(X + o_va), (int32_t*)(X + o_vpos));
+	if ((rc = chain_fwd_launch(s, (const uint64_t*)(X + o_va), n2, d_first, nullptr, n_query, pm, kSerialRun,
+	                           ChainFwdBufs{ (int32_t*)(X + o_vf), (int32_t*)(X + o_vpred), (int32_t*)(X + o_fmark), (uint32_t*)(X + xc.mark), (LongRun*)(X + o_long), (unsigned int*)(X + o_nlong), long_cap }))) return rc;
+	const ChainViewDev view{ d_first, nullptr, F.d_qfirst, (const int32_t*)(X + o_vpos), (const int32_t*)(X + o_vf), (const int32_t*)(X + o_vpred), (const uint64_t*)(X + o_va) };
+	const int32_t *h_status = nullptr;
+	if ((rc = chain_extract_pack(ctx, s, X, xc, view, mainp, n_query, H, nullptr, nullptr, ChainTailOut{ out.a_first, out.u_first, out.A, out.U }, &h_status))) return rc;
+	out.has_chains = true;
+	seed_mark_on_host(out, n_query, h_status, F.h_flag);       // (the sift's hand-backs are in out.on_host already: dev_sift_front)
+	timing_note("    seed: copy + main chain on the device", now_ms() - F.t_sift);
+	return MPA_OK;
+}
+
+// GPU seeding for one mini-batch: anchors -> sort -> forward pass of the pre-chain -> the anchors that have a neighbour.
+// jobs: the kept seeds of all queries (qid ascending, within a query ascending query position, dst = running anchor
+// offset); qfirst[n_query + 1]: first anchor of every query.  out: per query a sparse ChainView's arrays
+// (pred = index into the query's part of the view, -1 for none).
+// pre_p == nullptr: the direct route (dev_seed_direct) -- no pre-chain, the sift keeps by the reach of the main chain *main
+static int dev_seed_entry(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams *pre_p, int32_t n_query, const int64_t *qfirst,
+                          const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, const ChainParams *main, SeedHold *hold, const int64_t *jfirst_dev, SiftKept *kept)
+{
+	const int64_t n = qfirst[n_query];
+	out.cfirst.assign((size_t)n_query + 1, 0);
+	out.pos = out.f = out.pred = nullptr, out.a = nullptr, out.m = 0, out.on_host.clear();
+	out.has_chains = false, out.U = out.A = nullptr, out.u_first.clear(), out.a_first.clear();
+	if (!pre_p) {                                              // (no anchors: no chains -- the planners take that from the device's result like any other)
+		out.has_chains = !kept, out.u_first.assign((size_t)n_query + 1, 0), out.a_first.assign((size_t)n_query + 1, 0);
+		if (kept) kept->first.assign((size_t)n_query + 1, 0), kept->a.clear(), kept->flag.assign((size_t)n_query, 0);
+	}
+	if (n == 0 || n_jobs == 0) return MPA_OK;
+	const ChainParams &pre = pre_p ? *pre_p : *main;
+	if (pre.bbit <= 0) { set_error("GPU seeding needs block anchors (bbit > 0)"); return MPA_ERR_UNSUPPORTED; }
+	HIP_TRY(hipSetDevice(ctx->device));
+	if (dev_upload_index(ctx, mi) != MPA_OK) return MPA_ERR_HIP;
+	DeviceIndex *d = mi->dev[ctx->device];
+	if (!d->kb) {
+		static std::mutex mu[mpa_idx_s::kMaxDevices];            // (per device, like dev_upload_index)
+		std::lock_guard<std::mutex> g(mu[ctx->device]);
+		if (!d->kb) {
+			uint32_t *p = nullptr;
+			HIP_TRY(hipMalloc((void**)&p, mi->kb.size() * 4 + 16));
+			{ const double t0 = now_ms(); HIP_TRY(upload_large(p, mi->kb.data(), mi->kb.size() * 4, ctx->stream)); timing_note("index upload: occurrence lists", now_ms() - t0); }
+			d->kb = p, d->kb_bytes = mi->kb.size() * 4 + 16;
+			g_dev_bytes += (long long)d->kb_bytes;
+		}
+	}
+	const PreParams pp = pre_params(pre);                      // (direct route: the main chain's parameters, as dev_chains_on_device derives them)
+	int nb = 1, qb = 1;
+	while ((1ULL << nb) < (uint64_t)mi->n_block + (uint64_t)pp.max_dblock + 2) ++nb;
+	while ((1LL << qb) < n_query) ++qb;
+	if (nb + qb > 64) { set_error("GPU pre-chain: too many queries x blocks for a 64-bit key"); return MPA_ERR_UNSUPPORTED; }
+	if (pre_p && pp.max_dblock != 1) { set_error("GPU seeding: the sift assumes a pre-chain that reaches one block"); return MPA_ERR_UNSUPPORTED; }
+	{	// the working set is ~60 bytes per anchor (sift: 16 of staging, the rest sized by the kept ones); a batch that does not fit
+		// stays on the host (the caller falls back).  Direct route: the staging is full -- 16 B per anchor where the halved one takes 8 --
+		// and the rule keeps every second anchor or more, 36 B each, before the chaining block is carved: 56 B per anchor
+		size_t free_b = 0, total_b = 0;
+		if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+			const SeedBufs &Bc = ctx->seed;
+			const size_t have = Bc.f.cap + Bc.pred.cap + Bc.mark.cap + Bc.flag.cap + Bc.idx.cap + Bc.tmp.cap + Bc.x_all.cap + Bc.dkey.cap + Bc.val64[0].cap;
+			if ((size_t)n * (pre_p ? 40 : 56) > have + free_b - (free_b >> 3)) { set_error("GPU seeding: batch too large for device memory"); return MPA_ERR_UNSUPPORTED; }
+		}
+	}
+	SeedBufs &B = ctx->seed;
+	ensure_seed_stream(ctx);
+	hipStream_t s = ctx->seed_stream;
+	const double t_begin = now_ms();
+	// ---- upload the seed jobs (jfirst_dev: dev_sketch_jobs of this context has left them in B.jobs)
+	if (!jfirst_dev) {
+		if (B.h_jobs.ensure((size_t)n_jobs * sizeof(SeedJobDev)) != MPA_OK) return MPA_ERR_HIP;
+		SeedJobDev *hj = B.h_jobs.as<SeedJobDev>();
+		for (int64_t i = 0; i < n_jobs; ++i) hj[i] = SeedJobDev{ jobs[i].kb_off, jobs[i].dst, jobs[i].cnt, jobs[i].qpos, jobs[i].qid, 0 };
+		if (B.jobs.ensure((size_t)n_jobs * sizeof(SeedJobDev)) != MPA_OK) return MPA_ERR_HIP;
+		HIP_TRY(hipMemcpyAsync(B.jobs.p, hj, (size_t)n_jobs * sizeof(SeedJobDev), hipMemcpyHostToDevice, s));
+	}
+	// merge the occurrence lists per query in block order, keep what has a neighbour (k_seed_sift, seed_exec.hip)
+	tl_alloc_failed = false;
+	const int rc = pre_p ? dev_prechain_forward_sift(ctx, d, mi->n_block, pp, nb, n_query, qfirst, jobs, n_jobs, out, t_begin, &pre, main, hold ? *hold : B.own, jfirst_dev)
+	                     : dev_seed_direct_impl(ctx, d, mi->n_block, pp, nb, n_query, qfirst, jobs, n_jobs, out, t_begin, *main, hold ? *hold : B.own, jfirst_dev, kept);
+	// a pool that could not grow (the admission check above is an estimate): the batch is seeded on the host, as for any batch
+	// that does not fit -- nothing has been handed to the caller yet
+	if (rc == MPA_ERR_HIP && tl_alloc_failed) { (void)hipStreamSynchronize(s); return MPA_ERR_UNSUPPORTED; }
+	return rc;
+}
+int dev_prechain_forward(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams &pre, int32_t n_query, const int64_t *qfirst,
+                         const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, const ChainParams *main, SeedHold *hold, const int64_t *jfirst_dev)
+{
+	return dev_seed_entry(ctx, mi, &pre, n_query, qfirst, jobs, n_jobs, out, main, hold, jfirst_dev, nullptr);
+}
+// Seeding without a pre-chain (-S, --no-pre-chain; MPA_GPU_SEED_NOPRE): sift by the main chain's reach, then the main chain itself
+// (dev_seed_direct_impl).  Same contract as dev_prechain_forward(main != nullptr): out.has_chains, out.on_host.  kept != nullptr
+// (test hook): stop behind the sift and hand out the kept anchors instead.
+int dev_seed_direct(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams &mainp, int32_t n_query, const int64_t *qfirst, const SeedJob *jobs, int64_t n_jobs,
+                    PrechainSparse &out, SeedHold *hold, const int64_t *jfirst_dev, SiftKept *kept)
+{
+	return dev_seed_entry(ctx, mi, nullptr, n_query, qfirst, jobs, n_jobs, out, &mainp, hold, jfirst_dev, kept);
+}
+
+// ki[] next to kb[] in HBM, on the first device sketch of a device.  The host array may be a misaligned view into a mapped .mpi:
+// it is only ever copied byte-wise.  No device memory for it: the caller sketches on the host.
+static int ensure_dev_ki(mpa_ctx_t *ctx, mpa_idx_s *mi, DeviceIndex *d)
+{
+	if (d->ki) return MPA_OK;
+	static std::mutex mu[mpa_idx_s::kMaxDevices];            // (per device, like dev_upload_index)
+	std::lock_guard<std::mutex> g(mu[ctx->device]);
+	if (d->ki) return MPA_OK;
+	int64_t *p = nullptr;
+	const size_t bytes = mi->ki.size() * 8;
+	if (hipMalloc((void**)&p, bytes + 16) != hipSuccess) { (void)hipGetLastError(); set_error("GPU sketch: no device memory for the bucket offsets"); return MPA_ERR_UNSUPPORTED; }
+	const double t0 = now_ms();
+	const hipError_t e = upload_large(p, (const void*)mi->ki.data(), bytes, ctx->stream);
+	if (e != hipSuccess) { (void)hipFree(p); set_error(std::string("GPU sketch: uploading the bucket offsets: ") + hipGetErrorString(e)); return MPA_ERR_HIP; }
+	timing_note("index upload: bucket offsets", now_ms() - t0);
+	d->ki = p, d->ki_bytes = bytes + 16;
+	g_dev_bytes += (long long)d->ki_bytes;
+	return MPA_OK;
+}
+
+static int dev_sketch_jobs_impl(mpa_ctx_t *ctx, mpa_idx_s *mi, DeviceIndex *d, int32_t max_occ, const mpa_qbatch_t *q, SketchResult &out)
+{
+	SeedBufs &B = ctx->seed;
+	hipStream_t s = ctx->seed_stream;
+	const int32_t n_query = q->n_seq;
+	const int64_t base = q->q_off[0], L = q->q_off[n_query] - base;
+	const size_t NQ = (size_t)n_query, mq = (NQ + 1) * 8, fq = (NQ * 4 + 15) & ~(size_t)15;
+	// one pinned block up: residue table | q_off (from 0) | protein text
+	const size_t off_qo = 256, off_tx = off_qo + mq, up_bytes = off_tx + (size_t)L + 16;
+	int rc;
+	if ((rc = B.h_kin.ensure(up_bytes)) || (rc = B.k_in.ensure(up_bytes)) || (rc = B.k_cnt.ensure((size_t)L * 4 + 16)) || (rc = B.k_bkt.ensure((size_t)L * 4 + 16)) ||
+	    (rc = B.k_q.ensure(4 * mq + 2 * fq)) || (rc = B.h_kout.ensure(2 * mq + 2 * fq)) || (rc = B.jobs.ensure(((size_t)L + 1) * sizeof(SeedJobDev)))) return rc;   // (a position ends at most one seed)
+	char *hu = B.h_kin.as<char>();
+	memcpy(hu, tab_aa13(), 256);
+	{ int64_t *qo = (int64_t*)(hu + off_qo); for (int32_t i = 0; i <= n_query; ++i) qo[i] = q->q_off[i] - base; }
+	if (L > 0) memcpy(hu + off_tx, q->seqs + base, (size_t)L);
+	HIP_TRY(hipMemcpyAsync(B.k_in.p, hu, off_tx + (size_t)L, hipMemcpyHostToDevice, s));
+	const char *din = B.k_in.as<char>();
+	char *dq = B.k_q.as<char>();
+	int64_t *d_na = (int64_t*)dq, *d_nk = (int64_t*)(dq + mq), *d_qfirst = (int64_t*)(dq + 2 * mq), *d_jfirst = (int64_t*)(dq + 3 * mq);
+	int32_t *d_mo = (int32_t*)(dq + 4 * mq), *d_flag = (int32_t*)(dq + 4 * mq + fq);
+	SketchParams sp;
+	sp.n_bucket = (int64_t)mi->ki.size(), sp.n_kb = mi->n_kb, sp.kmer = mi->opt.kmer, sp.mod_bit = mi->opt.mod_bit, sp.max_occ = max_occ, sp.pad = 0;
+	const unsigned nwg = (unsigned)((n_query + SKETCH_WAVES - 1) / SKETCH_WAVES);
+	hipLaunchKernelGGL(k_sketch_count, dim3(nwg), dim3(64 * SKETCH_WAVES), 0, s, (const uint8_t*)(din + off_tx), (const int64_t*)(din + off_qo), n_query, (const uint8_t*)din,
+	                   (const int64_t*)d->ki, sp, B.k_cnt.as<int32_t>(), B.k_bkt.as<uint32_t>(), d_na, d_nk, d_mo, d_flag);
+	hipLaunchKernelGGL(k_offsets2, dim3(1), dim3(256), 0, s, (const int64_t*)d_na, (const int64_t*)d_nk, n_query, d_qfirst, d_jfirst);
+	hipLaunchKernelGGL(k_sketch_emit, dim3(nwg), dim3(64 * SKETCH_WAVES), 0, s, (const int64_t*)(din + off_qo), n_query, (const int64_t*)d->ki, B.k_cnt.as<int32_t>(),
+	                   B.k_bkt.as<uint32_t>(), (const int64_t*)d_qfirst, (const int64_t*)d_jfirst, (const int32_t*)d_mo, (const int32_t*)d_flag, B.jobs.as<SeedJobDev>());
+	HIP_TRY(hipGetLastError());
+	// qfirst | jfirst | cut-offs | flags: contiguous on the device, one copy, one wait
+	char *hd = B.h_kout.as<char>();
+	HIP_TRY(hipMemcpyAsync(hd, dq + 2 * mq, 2 * mq + 2 * fq, hipMemcpyDeviceToHost, s));
+	HIP_TRY(wait_stream(ctx, s));
+	out.qfirst = (const int64_t*)hd, out.jfirst = (const int64_t*)(hd + mq), out.max_occ = (const int32_t*)(hd + 2 * mq), out.flag = (const int32_t*)(hd + 2 * mq + fq);
+	out.n_anchor = out.qfirst[n_query], out.n_jobs = out.jfirst[n_query];
+	for (int32_t i = 0; i < n_query; ++i) out.n_flagged += out.flag[i] != 0;
+	return MPA_OK;
+}
+
+// The sketch stage of a mini-batch on the device (sketch_exec.hip): protein text up, the seed jobs of every query left in the
+// seeder context's B.jobs for dev_prechain_forward(jfirst_dev), the two prefix arrays, cut-offs and flags back.  out points into
+// pinned memory of the context, valid until its next sketch.  MPA_ERR_UNSUPPORTED: the caller runs the host stage.
+int dev_sketch_jobs(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t max_occ, const mpa_qbatch_t *q, SketchResult &out)
+{
+	out = SketchResult();
+	const mpa_idxopt_t &io = mi->opt;
+	if (q->n_seq <= 0) { set_error("GPU sketch: an empty batch"); return MPA_ERR_UNSUPPORTED; }
+	if (io.kmer < 1 || io.kmer > 7) { set_error("GPU sketch: k-mers of 1..7 residues only"); return MPA_ERR_UNSUPPORTED; }
+	if (io.mod_bit < 0 || io.mod_bit >= 4 * io.kmer || mi->ki.size() != (size_t)1 << (4 * io.kmer - io.mod_bit)) { set_error("GPU sketch: the index has no k-mer table of 2^(4k - M) buckets"); return MPA_ERR_UNSUPPORTED; }
+	if (q->q_off[q->n_seq] - q->q_off[0] >= (int64_t)INT32_MAX) { set_error("GPU sketch: too many seeds in a batch for 32-bit job indices"); return MPA_ERR_UNSUPPORTED; }
+	HIP_TRY(hipSetDevice(ctx->device));
+	if (dev_upload_index(ctx, mi) != MPA_OK) return MPA_ERR_HIP;
+	DeviceIndex *d = mi->dev[ctx->device];
+	int rc = ensure_dev_ki(ctx, mi, d);
+	if (rc != MPA_OK) return rc;
+	ensure_seed_stream(ctx);
+	tl_alloc_failed = false;
+	rc = dev_sketch_jobs_impl(ctx, mi, d, max_occ, q, out);
+	if (rc == MPA_ERR_HIP && tl_alloc_failed) { (void)hipStreamSynchronize(ctx->seed_stream); out = SketchResult(); return MPA_ERR_UNSUPPORTED; }   // (a pool could not grow: host stage)
+	return rc;
+}
+
+// test hook (mpa_dbg_seed_jobs): the first n_jobs records of B.jobs, and the bucket that rides in their pad field
+int dev_sketch_fetch(mpa_ctx_t *ctx, int64_t n_jobs, SeedJob *jobs, int32_t *bucket)
+{
+	if (n_jobs <= 0) return MPA_OK;
+	SeedBufs &B = ctx->seed;
+	if ((size_t)n_jobs * sizeof(SeedJobDev) > B.jobs.cap) { set_error("dev_sketch_fetch: more jobs than the context holds"); return MPA_ERR_ARG; }
+	HIP_TRY(hipSetDevice(ctx->device));
+	std::vector<SeedJobDev> h((size_t)n_jobs);
+	HIP_TRY(hipMemcpyAsync(h.data(), B.jobs.p, (size_t)n_jobs * sizeof(SeedJobDev), hipMemcpyDeviceToHost, ctx->seed_stream));
+	HIP_TRY(wait_stream(ctx, ctx->seed_stream));
+	for (int64_t i = 0; i < n_jobs; ++i) {
+		const SeedJobDev &j = h[(size_t)i];
+		jobs[i] = SeedJob{ j.kb_off, j.dst, j.cnt, j.qpos, j.qid }, bucket[i] = j.pad;
+	}
+	return MPA_OK;
+}
+} // namespace mpa
+
+namespace mpa {
+// Forward pass of mp_chain for a batch of chaining problems on the device (k_chain_fwd): the main chain of every query of a
+// mini-batch, or the refinement chains of its regions.  The caller writes the sorted anchors of all problems, back to back,
+// into io.a (pinned memory of the context) and finds f / pred (index inside the problem) in io.f / io.pred afterwards.
+int dev_chain_buffers(mpa_ctx_t *ctx, int64_t n, ChainIO &io)
+{
+	SeedBufs &B = ctx->seed;
+	int rc;
+	if ((rc = B.hc_a.ensure((size_t)n * 8 + 64)) || (rc = B.hc_f.ensure((size_t)n * 4 + 64)) || (rc = B.hc_pred.ensure((size_t)n * 4 + 64))) return rc;
+	io.a = B.hc_a.as<uint64_t>(), io.f = B.hc_f.as<int32_t>(), io.pred = B.hc_pred.as<int32_t>();
+	return MPA_OK;
+}
+
+int dev_chain_forward(mpa_ctx_t *ctx, const ChainParams &cp, int32_t n_prob, const int64_t *first, const ChainIO &io)
+{
+	const int64_t n = first[n_prob];
+	if (n == 0 || n_prob == 0) return MPA_OK;
+	if (n_prob > (1 << 30) || cp.kmer < 0) { set_error("chain forward pass: parameters outside the device kernel's range"); return MPA_ERR_UNSUPPORTED; }
+	for (int32_t q = 0; q < n_prob; ++q)
+		if (first[q + 1] - first[q] > INT32_MAX - 2) { set_error("chain forward pass: a problem has too many anchors"); return MPA_ERR_UNSUPPORTED; }
+	HIP_TRY(hipSetDevice(ctx->device));
+	SeedBufs &B = ctx->seed;
+	ensure_seed_stream(ctx);
+	hipStream_t s = ctx->seed_stream;
+	const PreParams pp = pre_params(cp);
+	int rc;
+	if ((rc = B.c_a.ensure((size_t)n * 8)) || (rc = B.c_f.ensure((size_t)n * 4)) || (rc = B.c_pred.ensure((size_t)n * 4)) || (rc = B.c_mark.ensure((size_t)n * 4)) ||
+	    (rc = B.c_flag.ensure((size_t)n * 4)) || (rc = B.c_first.ensure(((size_t)n_prob + 1) * 8))) return rc;
+	// runs longer than this get a wavefront each (k_chain_fwd_wave); MPA_CHAIN_SERIAL_RUN overrides (tests: 4 = almost every run)
+	const int32_t serial_run = [] { const char *e = getenv("MPA_CHAIN_SERIAL_RUN"); return e ? std::max(1, atoi(e)) : 48; }();
+	const size_t long_cap = (size_t)n / (size_t)(serial_run + 1) + 16;
+	if ((rc = B.c_long.ensure(64 + long_cap * sizeof(LongRun)))) return rc;
+	unsigned int *d_nlong = B.c_long.as<unsigned int>();
+	LongRun *d_long = (LongRun*)(B.c_long.as<char>() + 64);
+	HIP_TRY(hipMemsetAsync(d_nlong, 0, 64, s));
+	HIP_TRY(hipMemcpyAsync(B.c_a.p, io.a, (size_t)n * 8, hipMemcpyHostToDevice, s));
+	HIP_TRY(hipMemcpyAsync(B.c_first.p, first, ((size_t)n_prob + 1) * 8, hipMemcpyHostToDevice, s));
+	if ((rc = chain_fwd_launch(s, B.c_a.as<uint64_t>(), n, B.c_first.as<int64_t>(), nullptr, n_prob, pp, serial_run,
+	                           ChainFwdBufs{ B.c_f.as<int32_t>(), B.c_pred.as<int32_t>(), B.c_mark.as<int32_t>(), B.c_flag.as<uint32_t>(), d_long, d_nlong, long_cap }))) return rc;
+	HIP_TRY(hipMemcpyAsync(io.f, B.c_f.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(io.pred, B.c_pred.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+	HIP_TRY(wait_stream(ctx, s));                       // (first[] may be pageable memory of the caller: it is consumed by now)
+	return MPA_OK;
+}
+} // namespace mpa

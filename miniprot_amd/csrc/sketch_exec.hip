@@ -1,5 +1,5 @@
 // sketch_exec.hip -- the first stage of mp_map() on the device (SURVEY.md kernel K5; map.c:126-170, sketch.c:18-38), included by
-// dp_exec.hip behind seed_exec.hip.  For a whole mini-batch (driver: dev_sketch_jobs in dp_exec.hip):
+// seed_run.hip behind seed_exec.hip.  For a whole mini-batch (driver: dev_sketch_jobs in seed_run.hip):
 //   k_sketch_count   per query: the protein sketch (modimizers of the reduced-alphabet k-mers), the occurrence count of every
 //                    sketched seed (ki[b + 1] - ki[b], empty buckets included), the boxplot cut-off of mp_cal_max_occ from the
 //                    25 % / 75 % order statistics of those counts, and how many seeds / anchors the cut-off keeps

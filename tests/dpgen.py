@@ -94,7 +94,7 @@ def make_ss(rng, nl, density=0.02):
     return bytes(ss)
 
 
-# Scoring points between miniprot's defaults and the limits mpa_dp_run() accepts (dp_exec.hip: go, io, xdrop <= 32000, ge, fs <= 16000,
+# Scoring points between miniprot's defaults and the limits mpa_dp_run() accepts (dp_plan.cpp: go, io, xdrop <= 32000, ge, fs <= 16000,
 # end_bonus <= 1000; the reference's command line takes any -O/-E/-J/-B/--xdrop, main.c:132-150): one parameter at a time, then
 # combinations.  Keyword arguments of refbind.DpParams; a point with fs also needs refbind.mapping_matrix(min(fs, 127)).
 PENALTY_POINTS = [
@@ -112,7 +112,7 @@ PENALTY_POINTS = [
 # blocks of 64 columns, then k_ext_huge)
 CLASS_EDGES = (8, 16, 17, 32, 33, 64, 65, 128, 129, 256, 257, 512, 513, 1024, 1025)
 
-# Calls at the int16 bound of the packed kernels (dp_exec.hip, may_saturate: al * max_mat + ncol * ge + max(0, end_bonus) > 32000 or
+# Calls at the int16 bound of the packed kernels (dp_plan.cpp, may_saturate: al * max_mat + ncol * ge + max(0, end_bonus) > 32000 or
 # go + ncol * ge > 32000, with ncol = 8 * ceil(al / 8)).  (al, parameters, the parameter to raise by one): with BLOSUM62 (max_mat 11)
 # the larger of the two sums is exactly 32000 for a call of al columns, and 32001 once `key` is raised by one.  The score sum decides
 # the first five, go + ncol * ge the others; the al cover every extension class and every lane class of the checkpointed sweep, with

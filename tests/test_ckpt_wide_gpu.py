@@ -25,7 +25,7 @@ def _may_saturate(P, al):
 
 
 def _packed(P, nl, al, lite_min):
-    """the predicate every checkpointed class shares (a restatement of dp_exec.hip's routing)"""
+    """the predicate every checkpointed class shares (a restatement of dp_plan.cpp's routing)"""
     return lite_min > 0 and P.ge <= 255 and P.fs <= 255 and not _may_saturate(P, al) and nl >= max(lite_min, 3)
 
 

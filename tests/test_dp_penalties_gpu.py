@@ -29,7 +29,7 @@ def _params(kw):
 
 
 def _may_saturate(P, al):
-    """dp_exec.hip's predicate: the call goes to the int32 sweeps"""
+    """dp_plan.cpp's predicate: the call goes to the int32 sweeps"""
     ncol = (al + 7) // 8 * 8
     return al * int(P.mat.max()) + ncol * P.ge + max(0, P.end_bonus) > 32000 or P.go + ncol * P.ge > 32000
 

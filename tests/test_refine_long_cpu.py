@@ -74,7 +74,7 @@ def test_host_leg_chains_every_long_locus():
 
 
 def test_model_of_the_global_map():
-    """CPU model of the long queries' k-mer table (k_refine_gmap_build / gmap_probe, seed_exec.hip): open addressing with the hash
+    """CPU model of the long queries' k-mer table (k_refine_gmap_build / gmap_probe, refine_kernels.hip): open addressing with the hash
     (word * 2654435761) >> (32 - log2 slots), slots = the power of two >= 2 x groups (at least 1 024), linear probing -- in ANY insertion
     order (the kernel's is not defined) every group is found with its own index, a word the query does not have ends at an empty slot,
     and with the table at most half full the walks stay short"""

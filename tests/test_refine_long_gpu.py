@@ -14,7 +14,7 @@ import seedopts
 pytestmark = pytest.mark.gpu
 
 REFINE_NOTE, REFINE_SCAN_NOTE, GMAP_NOTE = "refinement on the GPU", "refinement scan on the GPU", "refine: global-map class"
-REFINE_SUPER = 4                                                # chunks of 2 048 positions that one workgroup of the scan sweeps (seed_exec.hip)
+REFINE_SUPER = 4                                                # chunks of 2 048 positions that one workgroup of the scan sweeps (refine_kernels.hip)
 LONG_NAMES = [n for n, _, _ in longprot.LONG]
 
 

@@ -1,4 +1,4 @@
-"""CPU model of k_refine_scan_map's hit collection (miniprot_amd/csrc/seed_exec.hip), written BEFORE the kernel was changed (the
+"""CPU model of k_refine_scan_map's hit collection (miniprot_amd/csrc/refine_kernels.hip), written BEFORE the kernel was changed (the
 round-5 attempt at aggregating the hit list's atomics went to the GPU without one and produced a difference nobody could explain).
 
 What the kernel computes (mp_refine_reg, map.c:53-79, with mp_sketch_nt4 / mp_sketch_clean_orf, sketch.c:40-100, as its source of

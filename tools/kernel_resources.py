@@ -1,14 +1,20 @@
 """Static resources of every kernel of the library from the code-object metadata of `hipcc -S` (VGPRs, SGPRs, static LDS, scratch, threads per
 workgroup) and the waves per SIMD the registers allow (512 VGPRs per SIMD lane, granule 8, at most 8 waves).
-python tools/kernel_resources.py > profiles/rNN_kernel_resources.txt   (compiles miniprot_amd/csrc/dp_exec.hip for gfx950: about a minute)"""
+python tools/kernel_resources.py > profiles/rNN_kernel_resources.txt   (compiles the device units of miniprot_amd/csrc for gfx950: about a minute)"""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = os.path.join(ROOT, "miniprot_amd", "csrc", "dp_exec.hip")
+UNITS = ("seed_run.hip", "refine_run.hip", "index_run.hip", "dp_exec.hip")     # (dev_ctx.hip has no kernels)
+text = ""
 with tempfile.TemporaryDirectory() as d:
-    out = os.path.join(d, "dp_exec.s")
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only", "-o", out, src],
-                   check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    text = open(out).read()
+    jobs = []
+    for u in UNITS:
+        out = os.path.join(d, u + ".s")
+        jobs.append((out, subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only", "-o", out,
+                                            os.path.join(ROOT, "miniprot_amd", "csrc", u)], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)))
+    for out, p in jobs:
+        if p.wait() != 0:
+            sys.exit("hipcc failed on " + out)
+        text += open(out).read()
 rows = []
 for blk in text.split("  - .agpr_count:")[1:]:
     f = {k: v for k, v in re.findall(r"\.(name|vgpr_count|sgpr_count|group_segment_fixed_size|private_segment_fixed_size|max_flat_workgroup_size|vgpr_spill_count):\s+(\S+)", blk)}
