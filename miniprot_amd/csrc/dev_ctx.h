@@ -1,5 +1,5 @@
 // dev_ctx.h -- the HOST side that the device units of the library share (dev_ctx.hip, seed_run.hip, refine_run.hip, index_run.hip,
-// dp_exec.hip): the device context with its memory pools, what dev_ctx.hip offers the stage drivers, and the chain tail of
+// dp_exec.hip, stats_run.hip): the device context with its memory pools, what dev_ctx.hip offers the stage drivers, and the chain tail of
 // seed_run.hip that the refinement uses too.  Each unit compiles its own kernels; a kernel is launched only by the unit that
 // defines it, everything across units goes through the host functions declared here and in mpa_internal.h.
 #pragma once
@@ -150,6 +150,9 @@ struct mpa_ctx_s {
 	struct WorkerLaunch { hipEvent_t e0, e1; };
 	std::vector<WorkerLaunch> wl_busy, wl_free;   // event pairs of worker launches not yet harvested / free for reuse
 	DevBuf dp_trace;                          // (MPA_DP_TRACE) per-unit start/end ticks of the current round
+	// ---- alignment statistics (stats_run.hip, MPA_GPU_STATS=1): grow-only, allocated by the first call that asks for them
+	DevBuf st_in, st_out;                     // tables | jobs | CIGAR words | protein text; per-alignment records | features
+	HostPinned h_stats_up, h_stats_down;      // ... their staging: one block up, one block down
 };
 
 namespace mpa {
@@ -165,7 +168,7 @@ template<typename F> static void ctx_each_devbuf(mpa_ctx_s *ctx, F f)
 	                  &B.c_a, &B.c_f, &B.c_pred, &B.c_mark, &B.c_flag, &B.c_first, &B.c_long,
 	                  &B.pf_qfirst2, &B.val64[0], &B.val64[1],
 	                  &B.s_meta, &B.s_cur, &B.s_cur2, &B.s_kept, &B.s_base, &B.s_out, &B.s_flag, &B.dkey, &B.x_all, &B.rx_all, &B.rx_keys,
-	                  &ctx->lite, &ctx->ckpt, &ctx->wlist, &B.k_in, &B.k_cnt, &B.k_bkt, &B.k_q, &B.r_gmap };
+	                  &ctx->lite, &ctx->ckpt, &ctx->wlist, &B.k_in, &B.k_cnt, &B.k_bkt, &B.k_q, &B.r_gmap, &ctx->st_in, &ctx->st_out };
 	int k = 0;
 	for (DevBuf *b : all) f(*b, k++);
 }
@@ -177,6 +180,7 @@ void ensure_seed_stream(mpa_ctx_t *ctx);                                        
 hipError_t ensure_dynamic_lds(const void *fn, int device, size_t bytes);                 // hipFuncSetAttribute(MaxDynamicSharedMemorySize), once per (kernel, device)
 void ctx_pool_report(mpa_ctx_t *root);
 void pool_harvest(mpa_ctx_t *ctx, bool wait);                                            // (dp_exec.hip) the finished worker launches of a context's DP pool
+// (stats_run.hip: dev_aln_stats_stage / dev_aln_stats are declared in mpa_internal.h, where the host pipeline that calls them sees them)
 
 // ---- the chain tail (seed_run.hip): what the three device chaining routes -- behind the pre-chain (dev_chains_on_device), without one
 // (dev_seed_direct) and the refinement (dev_refine_chains) -- do alike, and the forward pass dev_chain_forward shares with them

@@ -1,6 +1,6 @@
 // dev_ctx.hip -- the device context of the library (dev_ctx.h): creation and destruction, its memory pools and the process-wide
 // counters behind them, the sleeping stream wait, the upload of the index, the sibling contexts of a stream pipeline and their shared
-// pool hints.  No kernels: the stages are seed_run.hip, refine_run.hip, index_run.hip and dp_exec.hip.
+// pool hints.  No kernels: the stages are seed_run.hip, refine_run.hip, index_run.hip, dp_exec.hip and stats_run.hip.
 #include "dev_ctx.h"
 
 namespace mpa {
@@ -240,7 +240,7 @@ void mpa_ctx_destroy(mpa_ctx_t *ctx)
 	ctx->dp_trace.release();
 	SeedBufs &B = ctx->seed;
 	ctx_each_devbuf(ctx, [](DevBuf &b, int) { b.release(); });
-	for (HostPinned *h : { &B.h_jobs, &B.h_rhits, &B.hc_a, &B.hc_f, &B.hc_pred, &B.h_meta, &B.h_back, &B.h_xoff, &B.h_kin, &B.h_kout, &ctx->h_up, &ctx->h_down, &ctx->h_pool }) h->release();
+	for (HostPinned *h : { &B.h_jobs, &B.h_rhits, &B.hc_a, &B.hc_f, &B.hc_pred, &B.h_meta, &B.h_back, &B.h_xoff, &B.h_kin, &B.h_kout, &ctx->h_up, &ctx->h_down, &ctx->h_pool, &ctx->h_stats_up, &ctx->h_stats_down }) h->release();
 	auto drop_hold = [](SeedHold &H) { for (HostPinned *h : { &H.h_pos, &H.h_f, &H.h_pred, &H.h_a, &H.h_U, &H.h_A }) h->release(); };
 	drop_hold(B.own);
 	for (SeedHold *H : ctx->holds) { drop_hold(*H); delete H; }
@@ -302,7 +302,7 @@ void ctx_pool_report(mpa_ctx_t *root)
 	static const char *const kName[] = { "tasks", "waves", "chunks", "qseq", "rec", "prof", "tb", "cig", "ncig", "score", "extout", "bnd", "list", "rowkey", "cigd", "cigoff", "hkey", "xg", "units",
 		"s.jobs", "s.f", "s.pred", "s.mark", "s.flag", "s.idx", "s.tmp", "s.cfirst", "s.r_win", "s.r_chunk", "s.r_words", "s.r_hits", "s.r_count",
 		"s.c_a", "s.c_f", "s.c_pred", "s.c_mark", "s.c_flag", "s.c_first", "s.c_long", "s.pf_qfirst2", "s.val64_0", "s.val64_1",
-		"s.s_meta", "s.s_cur", "s.s_cur2", "s.s_kept", "s.s_base", "s.s_out", "s.s_flag", "s.dkey", "s.x_all", "s.rx_all", "s.rx_keys", "lite", "ckpt", "wlist" };
+		"s.s_meta", "s.s_cur", "s.s_cur2", "s.s_kept", "s.s_base", "s.s_out", "s.s_flag", "s.dkey", "s.x_all", "s.rx_all", "s.rx_keys", "lite", "ckpt", "wlist", "s.k_in", "s.k_cnt", "s.k_bkt", "s.k_q", "s.r_gmap", "st_in", "st_out" };
 	std::vector<mpa_ctx_t*> all{ root };
 	for (mpa_ctx_t *sb : root->siblings) all.push_back(sb);
 	size_t grand = 0;

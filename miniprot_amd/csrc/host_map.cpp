@@ -94,6 +94,7 @@ struct mpa_batch_s {
 	std::vector<SeedJob> seed_jobs;
 	std::vector<int64_t> seed_qfirst;
 	bool dev_sketch = false;         // MPA_GPU_SKETCH: the sketch phase built the shell only, the seeder runs the sketch on the device first
+	mpa_ctx_t *dp_ctx = nullptr;     // the context that runs this batch's DP rounds (run_dp_rounds), null for a caller that drives the stage machine itself
 };
 
 namespace mpa {
@@ -825,33 +826,198 @@ static void take_round1_emit_round2(mpa_batch_s *b, const mpa_dp_rst_t *rst, con
 	b->tasks.swap(next);
 }
 
-static void take_round3(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint32_t *pool)
+// ---- take_round3: (a) results in, CIGAR and n_exon of every region; (b) the statistics pass; (c) stage_finish ----
+// (a) the accepted spans' results and the region's CIGAR, end coordinates and DP score (align.c:302-338)
+static void assemble_alignment(AlignPlan &pl, Region &r, const mpa_dp_rst_t *rst, const uint32_t *pool)
 {
+	int32_t score = 0;
+	r.cigar.clear();
+	if (pl.has_left_span) store_result(pl.left_span, rst, pool);
+	if (pl.has_right_span) store_result(pl.right_span, rst, pool);
+	auto add = [&](const Segment &s) {
+		for (uint32_t c : s.cigar) append_cigar(r.cigar, c & 0xf, (int32_t)(c >> 4));
+		score += s.score;
+	};
+	if (pl.has_left_span) add(pl.left_span);
+	for (const Segment &g : pl.gaps) add(g);
+	if (pl.has_right_span) add(pl.right_span);
+	r.ve = pl.mid_ve, r.qe = pl.mid_qe;
+	if (pl.has_right && pl.r_nt > 0 && pl.r_aa > 0) r.ve += pl.r_nt, r.qe += pl.r_aa;
+	r.aligned = true;
+	r.dp_score = score, r.dp_max2 = 0;
+}
+
+// (b) on the host, as the reference walks it
+static void stats_on_host(const mpa_batch_s *b, const QueryState &qs, const AlignPlan &pl, Region &r)
+{
+	r.dist_stop = dist_to_stop(b->mi, r, pl.ae);
+	r.dist_start = dist_to_start(b->mi, r, pl.as, pl.ae);
+	summarize_alignment(b->mi, b->opt, r, qs.seq, qs.qlen, pl.ae);
+}
+
+// MPA_GPU_STATS: 0 / unset = the statistics pass on the host (the functions above); 1 = on the device, on the context that ran the
+// batch's DP rounds (stats_run.hip); model = the host instance of the device's code with a team of one (aln_stats_core.h: the CPU tests)
+enum StatsMode { STATS_HOST = 0, STATS_DEVICE, STATS_MODEL };
+static StatsMode aln_stats_mode()
+{
+	const char *e = getenv("MPA_GPU_STATS");            // (read per call: the tests flip it)
+	if (!e || !*e) return STATS_HOST;
+	if (!strcmp(e, "model")) return STATS_MODEL;
+	return atoi(e) != 0 ? STATS_DEVICE : STATS_HOST;
+}
+
+// the packed genome as aln_stats_core.h reads it on the host: strand_base() of dev_common.h in plain C++
+struct StatsGenomeHost {
+	const uint8_t *seq;
+	int64_t off, len;
+	int rev;
+	uint32_t base(int64_t x) const
+	{
+		if (x < 0 || x >= len) return 4;
+		const int64_t p = rev ? off + len - 1 - x : off + x;
+		const uint32_t c = (seq[p >> 1] >> ((p & 1) * 4)) & 0xf;
+		return rev && c < 4 ? 3 - c : c;
+	}
+};
+
+static int32_t count_exons(const Region &r)
+{
+	int32_t n_intron = 0;
+	for (uint32_t c : r.cigar) { const uint32_t op = c & 0xf; n_intron += (op == 3 || op == 12 || op == 13); }
+	return n_intron + 1;
+}
+
+static AlnStatsJob stats_job(const QueryState &qs, const AlignPlan &pl, const Region &r, int64_t q_off, int64_t cig_off, int64_t feat_off)
+{
+	AlnStatsJob J;
+	J.vs = r.vs, J.ve = r.ve, J.as = pl.as, J.ae = pl.ae, J.q_off = q_off, J.cig_off = cig_off, J.feat_off = feat_off;
+	J.vid = (int32_t)r.vid, J.qs = r.qs, J.qe = r.qe, J.qlen = qs.qlen, J.n_cigar = (int32_t)r.cigar.size(), J.pad = 0;
+	return J;
+}
+
+// what the shared core computed for a region, into the region (n_exon is the host's: count_exons)
+static void stats_apply(Region &r, const AlnStatsOut &o, const AlnFeat *f)
+{
+	assert(!o.bad);                                      // (the walk ends at (ve - vs, qe - qs): summarize_alignment's own check)
+	r.dist_stop = o.dist_stop, r.dist_start = o.dist_start;
+	r.dp_max = o.dp_max, r.blen = o.blen, r.n_iden = o.n_iden, r.n_plus = o.n_plus, r.n_fs = o.n_fs, r.n_stop = o.n_stop;
+	r.feat.assign((size_t)o.n_feat, Feat());
+	for (int32_t k = 0; k < o.n_feat; ++k) {
+		Feat &d = r.feat[(size_t)k];
+		const AlnFeat &s = f[k];
+		d.vs = s.vs, d.ve = s.ve, d.qs = s.qs, d.qe = s.qe, d.type = s.type, d.phase = s.phase;
+		d.n_fs = s.n_fs, d.n_stop = s.n_stop, d.score = s.score, d.n_iden = s.n_iden, d.blen = s.blen;
+		memcpy(d.donor, s.donor, 2), memcpy(d.acceptor, s.acceptor, 2);
+	}
+}
+
+static AlnStatsParams stats_params(const mpa_mapopt_t &opt) { return AlnStatsParams{ opt.go, opt.ge, opt.fs, opt.asize }; }
+
+// (b) through the shared core on the host: a team of one per region
+static void stats_model(mpa_batch_s *b)
+{
+	uint8_t tab[ALN_TAB_BYTES];
+	memcpy(tab + ALN_TAB_CODON, tab_codon(), 64), memcpy(tab + ALN_TAB_AA20, tab_aa20(), 256), memcpy(tab + ALN_TAB_MAT, b->opt.mat, 484);
+	const AlnStatsParams p = stats_params(b->opt);
 	parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
+		QueryState &qs = b->qs[qi];
+		std::vector<AlnFeat> feat;
+		for (AlignPlan &pl : qs.plans) {
+			Region &r = qs.regs[pl.reg];
+			const Contig &c = b->mi->ctg[r.vid >> 1];
+			const StatsGenomeHost g{ b->mi->seq.data(), c.off, c.len, (int)(r.vid & 1) };
+			feat.assign((size_t)r.n_exon + 1, AlnFeat());
+			const AlnStatsOut o = aln_stats_core<StatsSerial>(stats_job(qs, pl, r, 0, 0, 0), p, tab, (const uint8_t*)qs.seq, r.cigar.data(), g, feat.data());
+			stats_apply(r, o, feat.data());
+		}
+	});
+}
+
+// (b) on the device.  MPA_OK: done (*ran: there was something to do); MPA_ERR_UNSUPPORTED: the device declined (last error says why)
+// and nothing was changed; anything else is an error of the call
+static int stats_on_device(mpa_batch_s *b, mpa_ctx_t *ctx, bool *ran)
+{
+	// jobs in query order: where each query's jobs, CIGAR words and feature slots start
+	const size_t nq = b->qs.size();
+	std::vector<int64_t> job0(nq + 1, 0), cig0(nq + 1, 0), feat0(nq + 1, 0);
+	for (size_t qi = 0; qi < nq; ++qi) {
+		const QueryState &qs = b->qs[qi];
+		int64_t nc = 0, nf = 0;
+		for (const AlignPlan &pl : qs.plans) { const Region &r = qs.regs[pl.reg]; nc += (int64_t)r.cigar.size(), nf += (int64_t)r.n_exon + 1; }
+		job0[qi + 1] = job0[qi] + (int64_t)qs.plans.size(), cig0[qi + 1] = cig0[qi] + nc, feat0[qi + 1] = feat0[qi] + nf;
+	}
+	const int64_t n_jobs = job0[nq], n_cigar = cig0[nq], n_feat = feat0[nq];
+	*ran = n_jobs > 0;
+	if (n_jobs == 0) return MPA_OK;
+	const int64_t t0 = b->q.q_off[0], text_bytes = b->q.q_off[b->q.n_seq] - t0;
+	AlnStatsIO io;
+	int rc = dev_aln_stats_stage(ctx, n_jobs, n_cigar, text_bytes, n_feat, io);
+	if (rc != MPA_OK) return rc;
+	if (text_bytes > 0) memcpy(io.text, b->q.seqs + t0, (size_t)text_bytes);
+	parallel_for(b->n_threads, (int64_t)nq, [&](int64_t qi) {
+		const QueryState &qs = b->qs[qi];
+		int64_t j = job0[qi], c = cig0[qi], f = feat0[qi];
+		for (const AlignPlan &pl : qs.plans) {
+			const Region &r = qs.regs[pl.reg];
+			io.jobs[j++] = stats_job(qs, pl, r, (qs.seq - b->q.seqs) - t0, c, f);
+			if (!r.cigar.empty()) memcpy(io.cigar + c, r.cigar.data(), r.cigar.size() * 4);
+			c += (int64_t)r.cigar.size(), f += (int64_t)r.n_exon + 1;
+		}
+	});
+	rc = dev_aln_stats(ctx, const_cast<mpa_idx_s*>(b->mi), stats_params(b->opt), b->opt.mat, n_jobs, n_cigar, text_bytes, n_feat, io);
+	if (rc != MPA_OK) return rc;
+	parallel_for(b->n_threads, (int64_t)nq, [&](int64_t qi) {
+		QueryState &qs = b->qs[qi];
+		int64_t j = job0[qi];
+		for (AlignPlan &pl : qs.plans) { stats_apply(qs.regs[pl.reg], io.out[j], io.feat + io.jobs[j].feat_off); ++j; }
+	});
+	return MPA_OK;
+}
+
+// MPA_OK, or the error of a device statistics call that failed (a call that merely declines leaves the batch to the host walk)
+static int take_round3(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint32_t *pool)
+{
+	StatsMode mode = aln_stats_mode();
+	if (mode == STATS_DEVICE && !b->dp_ctx) mode = STATS_HOST;            // (the stage machine without a context: mpa_batch_begin)
+	if (mode == STATS_HOST) {                                             // the three steps in one pass over the queries
+		parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
+			QueryState &qs = b->qs[qi];
+			for (AlignPlan &pl : qs.plans) {
+				Region &r = qs.regs[pl.reg];
+				assemble_alignment(pl, r, rst, pool);
+				stats_on_host(b, qs, pl, r);
+			}
+			stage_finish(b, qs);
+		});
+		return MPA_OK;
+	}
+	parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {      // (a)
 		QueryState &qs = b->qs[qi];
 		for (AlignPlan &pl : qs.plans) {
 			Region &r = qs.regs[pl.reg];
-			int32_t score = 0;
-			r.cigar.clear();
-			if (pl.has_left_span) store_result(pl.left_span, rst, pool);
-			if (pl.has_right_span) store_result(pl.right_span, rst, pool);
-			auto add = [&](const Segment &s) {
-				for (uint32_t c : s.cigar) append_cigar(r.cigar, c & 0xf, (int32_t)(c >> 4));
-				score += s.score;
-			};
-			if (pl.has_left_span) add(pl.left_span);
-			for (const Segment &g : pl.gaps) add(g);
-			if (pl.has_right_span) add(pl.right_span);
-			r.ve = pl.mid_ve, r.qe = pl.mid_qe;
-			if (pl.has_right && pl.r_nt > 0 && pl.r_aa > 0) r.ve += pl.r_nt, r.qe += pl.r_aa;
-			r.aligned = true;
-			r.dp_score = score, r.dp_max2 = 0;
-			r.dist_stop = dist_to_stop(b->mi, r, pl.ae);
-			r.dist_start = dist_to_start(b->mi, r, pl.as, pl.ae);
-			summarize_alignment(b->mi, b->opt, r, qs.seq, qs.qlen, pl.ae);
+			assemble_alignment(pl, r, rst, pool);
+			r.n_exon = count_exons(r);
 		}
-		stage_finish(b, qs);
 	});
+	const double t0 = now_ms();                                            // (b)
+	if (mode == STATS_MODEL) {
+		stats_model(b);
+		timing_note("alignment statistics: shared core", now_ms() - t0);
+	} else {
+		bool ran = false;
+		const int rc = stats_on_device(b, b->dp_ctx, &ran);
+		if (rc != MPA_OK && rc != MPA_ERR_UNSUPPORTED) return rc;
+		if (rc == MPA_OK && ran) timing_note("alignment statistics on the GPU", now_ms() - t0);
+		if (rc == MPA_ERR_UNSUPPORTED) {
+			if (timing_on()) fprintf(stderr, "[mpa-timing]   device alignment statistics declined (%s): statistics on the host\n", mpa_last_error());
+			parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
+				QueryState &qs = b->qs[qi];
+				for (AlignPlan &pl : qs.plans) stats_on_host(b, qs, pl, qs.regs[pl.reg]);
+			});
+		}
+	}
+	parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) { stage_finish(b, b->qs[qi]); });   // (c)
+	return MPA_OK;
 }
 
 } // namespace mpa
@@ -1196,7 +1362,7 @@ static void batch_plan_phase(mpa_batch_s *b, mpa_ctx_t *rctx)
 	emit_round1(b);
 	timing_note("emit round 1", now_ms() - t1);
 	b->round = 1;
-	if (b->tasks.empty()) { take_round3(b, nullptr, nullptr); b->round = 4; }   // nothing to align at all
+	if (b->tasks.empty()) { (void)take_round3(b, nullptr, nullptr); b->round = 4; }   // nothing to align at all (and no context yet: the host walk)
 }
 
 static mpa_batch_t *batch_begin_impl(mpa_ctx_t *seed_ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads)
@@ -1550,15 +1716,16 @@ mpa_batch_t *mpa_batch_begin(const mpa_idx_t *mi, const mpa_mapopt_t *opt, const
 int64_t mpa_batch_dp_tasks(mpa_batch_t *b, const mpa_dp_task_t **tasks, mpa_dpopt_t *opt)
 {
 	if (opt) *opt = b->dpopt;
+	*tasks = nullptr;
 	if (b->round == 0) {
 		double t0 = now_ms();
 		emit_round1(b);
 		timing_note("emit round 1", now_ms() - t0);
 		b->round = 1;
-		if (b->tasks.empty()) { take_round3(b, nullptr, nullptr); b->round = 4; }   // nothing to align at all
+		if (b->tasks.empty()) { const int rc = take_round3(b, nullptr, nullptr); if (rc != MPA_OK) return rc; b->round = 4; }   // nothing to align at all
 	}
 	// (round 2 without tasks: every accepted span took the ungapped shortcut)
-	if (b->round == 2 && b->tasks.empty()) { take_round3(b, nullptr, nullptr); b->round = 4; }
+	if (b->round == 2 && b->tasks.empty()) { const int rc = take_round3(b, nullptr, nullptr); if (rc != MPA_OK) return rc; b->round = 4; }
 	if (b->round >= 4) { *tasks = nullptr; return 0; }
 	*tasks = b->tasks.data();
 	return (int64_t)b->tasks.size();
@@ -1568,7 +1735,11 @@ static int mpa_batch_dp_results_impl(mpa_batch_t *b, const mpa_dp_rst_t *rst, co
 {
 	double t0 = now_ms();
 	if (b->round == 1) { take_round1_emit_round2(b, rst, cigar_pool); b->round = 2; timing_note("take 1 / emit 2", now_ms() - t0); }
-	else if (b->round == 2) { take_round3(b, rst, cigar_pool); b->round = 4; b->tasks.clear(); timing_note("take 2 + finish", now_ms() - t0); }
+	else if (b->round == 2) {
+		const int rc = take_round3(b, rst, cigar_pool);
+		if (rc != MPA_OK) return rc;
+		b->round = 4; b->tasks.clear(); timing_note("take 2 + finish", now_ms() - t0);
+	}
 	else { set_error("mpa_batch_dp_results called out of sequence"); return MPA_ERR_ARG; }
 	return MPA_OK;
 }
@@ -1635,7 +1806,9 @@ static int run_dp_rounds(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_qbatch_t
 	mpa_dpopt_t dpopt;
 	int64_t n;
 	std::vector<mpa_dp_rst_t> rst;
-	while ((n = mpa_batch_dp_tasks(b, &tasks, &dpopt)) > 0) {
+	b->dp_ctx = ctx;                 // (MPA_GPU_STATS=1: the statistics pass behind the last round runs there too)
+	while ((n = mpa_batch_dp_tasks(b, &tasks, &dpopt)) != 0) {
+		if (n < 0) return (int)n;                // (a device statistics call behind a round without tasks failed)
 		uint32_t *pool = nullptr;
 		int64_t n_pool = 0;
 		rst.resize((size_t)n);

@@ -10,6 +10,7 @@
 #include <cstring>
 #include "../../include/mpamd.h"
 #include "chain_core.h"
+#include "aln_stats_core.h"
 
 namespace mpa {
 
@@ -194,5 +195,14 @@ struct SketchResult {
 };
 int dev_sketch_jobs(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t max_occ, const mpa_qbatch_t *q, SketchResult &out);
 int dev_sketch_fetch(mpa_ctx_t *ctx, int64_t n_jobs, SeedJob *jobs, int32_t *bucket);   // test hook: the jobs the last sketch left, and their buckets
+
+// ---- alignment statistics on the device (driver: stats_run.hip; code: aln_stats_core.h) -----------
+// dev_aln_stats_stage sizes the context's pinned block for a call and hands out where the caller writes its jobs, CIGAR words and
+// protein text; dev_aln_stats runs them and leaves out[n_jobs] / feat[n_feat] in pinned memory of the context (valid until its next
+// call).  MPA_ERR_UNSUPPORTED from either: the device declines (a pool could not grow) and the caller keeps the host stage.
+struct AlnStatsIO { AlnStatsJob *jobs = nullptr; uint32_t *cigar = nullptr; char *text = nullptr; const AlnStatsOut *out = nullptr; const AlnFeat *feat = nullptr; };
+int dev_aln_stats_stage(mpa_ctx_t *ctx, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat, AlnStatsIO &io);
+int dev_aln_stats(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const int8_t *mat, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat,
+                  AlnStatsIO &io);
 
 } // namespace mpa

@@ -1,0 +1,51 @@
+// stats_kernels.hip -- the statistics pass over the finished alignments of a mini-batch on the device (row a16 of DESIGN.md section 1;
+// DESIGN.md section 4.5), included by stats_run.hip.  The code itself is aln_stats_core.h, the one source the host model runs too;
+// this file is its device team, its genome reader and the kernel around them.
+//   k_aln_stats   one wavefront per alignment, four alignments per workgroup: dist_stop / dist_start, the statistics of the CIGAR
+//                 walk and the exon / stop-codon features, written where the host's download finds them
+// The tables (codon table, aa20, substitution matrix: 804 bytes) are the workgroup's only LDS.  No capacity: the CIGAR is read 64
+// words at a time, runs of any length are strided over the lanes, features go straight to their slots in global memory.
+
+namespace mpa {
+
+#define STATS_WAVES 4                                     /* alignments per workgroup */
+
+struct StatsWave : CoopWave {                             // the team of aln_stats_core.h on the device: one wavefront
+	static __device__ __forceinline__ int32_t sum(int32_t v)
+	{
+#pragma unroll
+		for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+		return __builtin_amdgcn_readfirstlane(v);                     // (the same on every lane: a scalar from here on)
+	}
+	static __device__ __forceinline__ uint32_t bcast(uint32_t v, int k) { return (uint32_t)__builtin_amdgcn_readlane((int)v, k); }   // (k is wave-uniform)
+};
+
+// the strand of one alignment in the resident 4-bit genome; outside the contig a position reads as N
+struct StatsGenome {
+	const uint8_t *seq;
+	int64_t off, len;
+	int rev;
+	__device__ __forceinline__ uint32_t base(int64_t x) const { return x < 0 || x >= len ? 4u : strand_base(seq, off, len, rev, x); }
+};
+
+// (64 registers, no scratch, 804 bytes of LDS: next to three resident k_dp_round workgroups a SIMD has 128 registers left,
+// DESIGN.md section 5 (3))
+__global__ __launch_bounds__(64 * STATS_WAVES) __attribute__((amdgpu_waves_per_eu(8))) void k_aln_stats(const AlnStatsJob *jobs, int32_t n_jobs, const uint8_t *tabs,
+                                                                                                       AlnStatsParams p, const uint8_t *text, const uint32_t *cig,
+                                                                                                       const uint8_t *seq, const int64_t *ctg_off, const int64_t *ctg_len,
+                                                                                                       AlnStatsOut *out, AlnFeat *feat)
+{
+	MPA_SHORT_KERNEL();
+	__shared__ uint8_t tab[(ALN_TAB_BYTES + 15) & ~15];
+	for (int i = (int)threadIdx.x; i < ALN_TAB_BYTES; i += 64 * STATS_WAVES) tab[i] = tabs[i];
+	__syncthreads();
+	// (the wave's number through readfirstlane: the job record, the contig and everything the walk derives from them stay scalar)
+	const int32_t j = (int32_t)blockIdx.x * STATS_WAVES + __builtin_amdgcn_readfirstlane((int32_t)(threadIdx.x >> 6));
+	if (j >= n_jobs) return;
+	const AlnStatsJob J = jobs[j];
+	const StatsGenome g{ seq, ctg_off[J.vid >> 1], ctg_len[J.vid >> 1], J.vid & 1 };
+	const AlnStatsOut o = aln_stats_core<StatsWave>(J, p, tab, text, cig, g, feat);
+	if ((threadIdx.x & 63) == 0) out[j] = o;
+}
+
+} // namespace mpa

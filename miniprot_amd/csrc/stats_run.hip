@@ -1,0 +1,75 @@
+// stats_run.hip -- the device unit of the alignment statistics (MPA_GPU_STATS=1; kernel: stats_kernels.hip, code: aln_stats_core.h).
+// take_round3() of host_map.cpp fills one pinned block (tables | jobs | CIGAR words | the batch's protein text) through
+// dev_aln_stats_stage(), dev_aln_stats() sends it up, launches k_aln_stats on the context that ran the batch's DP rounds, takes one
+// pinned block down (per-alignment records | features) and waits once.  The pools (st_in, st_out and their staging) are grow-only and
+// allocated on first use: a run that never sets the knob holds none of them.
+#include "dev_ctx.h"
+#include "stats_kernels.hip"
+
+namespace mpa {
+
+namespace {
+struct StatsLayout {
+	size_t off_jobs, off_cig, off_text, up_bytes, off_feat, down_bytes;
+	StatsLayout(int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat)
+	{
+		auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+		off_jobs = 1024;                                                   // (the tables take ALN_TAB_BYTES of the first KB)
+		off_cig = off_jobs + up16((size_t)n_jobs * sizeof(AlnStatsJob));
+		off_text = off_cig + up16((size_t)n_cigar * 4);
+		up_bytes = off_text + up16((size_t)text_bytes) + 16;
+		off_feat = up16((size_t)n_jobs * sizeof(AlnStatsOut));
+		down_bytes = off_feat + (size_t)n_feat * sizeof(AlnFeat) + 16;
+	}
+};
+static_assert(ALN_TAB_BYTES <= 1024, "the tables share the first KB of the staging block");
+}
+
+// the pinned block of a call, for the caller to fill: jobs, CIGAR words and text.  MPA_ERR_UNSUPPORTED: no memory for it
+int dev_aln_stats_stage(mpa_ctx_t *ctx, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat, AlnStatsIO &io)
+{
+	io = AlnStatsIO();
+	if (n_jobs <= 0 || n_jobs > (int64_t)1 << 28) { set_error("GPU alignment statistics: no alignments, or too many for one launch"); return MPA_ERR_UNSUPPORTED; }
+	if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return MPA_ERR_HIP; }
+	const StatsLayout L(n_jobs, n_cigar, text_bytes, n_feat);
+	if (ctx->h_stats_up.ensure(L.up_bytes) != MPA_OK || ctx->h_stats_down.ensure(L.down_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
+	char *hu = ctx->h_stats_up.as<char>();
+	io.jobs = (AlnStatsJob*)(hu + L.off_jobs), io.cigar = (uint32_t*)(hu + L.off_cig), io.text = hu + L.off_text;
+	return MPA_OK;
+}
+
+// The statistics and features of the n_jobs alignments staged in io, on ctx.  io.out / io.feat point into pinned memory of the
+// context afterwards, valid until its next call.  MPA_ERR_UNSUPPORTED: a pool could not grow -- the caller runs the host stage.
+int dev_aln_stats(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const int8_t *mat, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat,
+                  AlnStatsIO &io)
+{
+	if (p.asize < 1 || p.asize * p.asize > 484) { set_error("GPU alignment statistics: a substitution matrix of more than 22 x 22"); return MPA_ERR_UNSUPPORTED; }
+	HIP_TRY(hipSetDevice(ctx->device));
+	if (dev_upload_index(ctx, mi) != MPA_OK) return MPA_ERR_HIP;
+	const DeviceIndex *d = mi->dev[ctx->device];
+	const StatsLayout L(n_jobs, n_cigar, text_bytes, n_feat);
+	if (L.up_bytes > ctx->h_stats_up.cap || L.down_bytes > ctx->h_stats_down.cap) { set_error("dev_aln_stats: the staging block was not sized for this call"); return MPA_ERR_ARG; }
+	tl_alloc_failed = false;
+	if (ctx->st_in.ensure(L.up_bytes) != MPA_OK || ctx->st_out.ensure(L.down_bytes) != MPA_OK) return tl_alloc_failed ? MPA_ERR_UNSUPPORTED : MPA_ERR_HIP;
+	hipStream_t s = ctx->stream;
+	char *hu = ctx->h_stats_up.as<char>();
+	memcpy(hu + ALN_TAB_CODON, tab_codon(), 64);
+	memcpy(hu + ALN_TAB_AA20, tab_aa20(), 256);
+	memset(hu + ALN_TAB_MAT, 0, 484);
+	memcpy(hu + ALN_TAB_MAT, mat, (size_t)(p.asize * p.asize));
+	HIP_TRY(hipMemcpyAsync(ctx->st_in.p, hu, L.up_bytes - 16, hipMemcpyHostToDevice, s));
+	const char *din = ctx->st_in.as<char>();
+	char *dout = ctx->st_out.as<char>();
+	const unsigned nwg = (unsigned)((n_jobs + STATS_WAVES - 1) / STATS_WAVES);
+	hipLaunchKernelGGL(k_aln_stats, dim3(nwg), dim3(64 * STATS_WAVES), 0, s, (const AlnStatsJob*)(din + L.off_jobs), (int32_t)n_jobs, (const uint8_t*)din, p,
+	                   (const uint8_t*)(din + L.off_text), (const uint32_t*)(din + L.off_cig), (const uint8_t*)d->seq, (const int64_t*)d->ctg_off, (const int64_t*)d->ctg_len,
+	                   (AlnStatsOut*)dout, (AlnFeat*)(dout + L.off_feat));
+	HIP_TRY(hipGetLastError());
+	char *hd = ctx->h_stats_down.as<char>();
+	HIP_TRY(hipMemcpyAsync(hd, dout, L.down_bytes - 16, hipMemcpyDeviceToHost, s));
+	HIP_TRY(wait_stream(ctx, s));
+	io.out = (const AlnStatsOut*)hd, io.feat = (const AlnFeat*)(hd + L.off_feat);
+	return MPA_OK;
+}
+
+} // namespace mpa

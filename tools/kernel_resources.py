@@ -3,7 +3,7 @@ workgroup) and the waves per SIMD the registers allow (512 VGPRs per SIMD lane, 
 python tools/kernel_resources.py > profiles/rNN_kernel_resources.txt   (compiles the device units of miniprot_amd/csrc for gfx950: about a minute)"""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-UNITS = ("seed_run.hip", "refine_run.hip", "index_run.hip", "dp_exec.hip")     # (dev_ctx.hip has no kernels)
+UNITS = ("seed_run.hip", "refine_run.hip", "index_run.hip", "dp_exec.hip", "stats_run.hip")     # (dev_ctx.hip has no kernels)
 text = ""
 with tempfile.TemporaryDirectory() as d:
     jobs = []
