@@ -55,6 +55,8 @@ struct DeviceIndex {
 	size_t kb_bytes = 0;
 	int64_t *ki = nullptr;                    // bucket offsets of the k-mer table, uploaded on the first device sketch (dev_sketch_jobs)
 	size_t ki_bytes = 0;
+	uint32_t *bo = nullptr;                   // block offset of every (contig, strand), uploaded on the first device regions call (k_regions)
+	size_t bo_bytes = 0;
 	uint8_t *spsc = nullptr;                  // splice-score track (--spsc), uploaded with the genome when the index has one
 	size_t seq_bytes = 0, spsc_bytes = 0;     // bytes counted into g_dev_bytes for the genome and the track
 };
@@ -78,7 +80,7 @@ struct HostPinned {
 // What a seeding call leaves for the planning stage: pinned host memory only.  In the stream pipeline the device pools belong to
 // the SEEDER (two of them), the results to the batch (one holder per batch between the start of its seeding and the end of its
 // planning), so that a batch waiting to be planned does not pin down a full set of device pools.
-struct SeedHold { HostPinned h_pos, h_f, h_pred, h_a, h_U, h_A; };
+struct SeedHold { HostPinned h_pos, h_f, h_pred, h_a, h_U, h_A, h_R; };   // h_R (MPA_GPU_REGIONS=1): region records | refinement limits | regions per query
 
 struct SeedBufs {
 	DevBuf jobs, f, pred, mark, flag, idx, tmp, cfirst;
@@ -92,6 +94,7 @@ struct SeedBufs {
 	HostPinned h_meta, h_back;                                             // ... their staging (up) and qfirst2 / flags / cfirst (down)
 	DevBuf k_in, k_cnt, k_bkt, k_q;                                         // device sketch (sketch_exec.hip): residue table + q_off + protein text; count and bucket per position; per-query counts, prefixes, cut-offs, flags
 	HostPinned h_kin, h_kout;                                              // ... its staging (up) and qfirst / jfirst / cut-offs / flags (down)
+	DevBuf rg;                                                             // device regions (k_regions): records, limits and per-query scratch, carved up per call
 	DevBuf x_all;                                                          // device chaining: views, extraction scratch, survivors, main-chain state, chains (carved up per call)
 	DevBuf rx_all, rx_keys;                                                // device refinement: pairing tables, pair keys (two buffers), chain state (carved up per call)
 	HostPinned h_xoff;                                                     // ... offsets of the chains of every query (down)
@@ -168,7 +171,7 @@ template<typename F> static void ctx_each_devbuf(mpa_ctx_s *ctx, F f)
 	                  &B.c_a, &B.c_f, &B.c_pred, &B.c_mark, &B.c_flag, &B.c_first, &B.c_long,
 	                  &B.pf_qfirst2, &B.val64[0], &B.val64[1],
 	                  &B.s_meta, &B.s_cur, &B.s_cur2, &B.s_kept, &B.s_base, &B.s_out, &B.s_flag, &B.dkey, &B.x_all, &B.rx_all, &B.rx_keys,
-	                  &ctx->lite, &ctx->ckpt, &ctx->wlist, &B.k_in, &B.k_cnt, &B.k_bkt, &B.k_q, &B.r_gmap, &ctx->st_in, &ctx->st_out };
+	                  &ctx->lite, &ctx->ckpt, &ctx->wlist, &B.k_in, &B.k_cnt, &B.k_bkt, &B.k_q, &B.r_gmap, &ctx->st_in, &ctx->st_out, &B.rg };
 	int k = 0;
 	for (DevBuf *b : all) f(*b, k++);
 }
@@ -210,8 +213,13 @@ int chain_extract_launch(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCa
 // chain_extract_launch (chains, not the set) -> k_offsets2 -> offsets and status down (one wait) -> the chains of all problems, densely,
 // into the pinned memory of H (k_chain_pack).  status_error != nullptr: a problem that needs the host ends the call with that error
 // (MPA_ERR_UNSUPPORTED) before anything is packed; otherwise *h_status (pinned, valid until the context's next chain tail) tells the caller.
+// regions != nullptr (MPA_GPU_REGIONS=1, the main round of a seeding route): k_regions + k_region_pack take k_chain_pack's place -- the
+// regions of every problem (records, refinement limits, their number: RegionsTail) come down instead of its chains, out.A / out.U stay
+// null, a_first / u_first still count what was left on the device.  A pool or pinned block that cannot grow: `done` stays false and
+// the chains are packed as without it.
 struct ChainTailOut { std::vector<int64_t> &a_first, &u_first; const uint64_t *&A, *&U; };
+struct RegionsTail { RegionsParams p; const uint32_t *d_bo; bool done; const RegionRec *R; const uint64_t *E; const int32_t *n_reg; };
 int chain_extract_pack(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCarve &c, const ChainViewDev &v, const ChainParams &p, int32_t n_prob, SeedHold &H,
-                       const char *prof_label, const char *status_error, ChainTailOut out, const int32_t **h_status);
+                       const char *prof_label, const char *status_error, ChainTailOut out, const int32_t **h_status, RegionsTail *regions = nullptr);
 
 } // namespace mpa

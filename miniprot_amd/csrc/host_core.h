@@ -55,6 +55,7 @@ struct Feat {
 struct Region {
 	int32_t off = 0, cnt = 0, id = 0, parent = 0, n_sub = 0, subsc = 0;
 	int32_t n_exon = 0, chn_sc = 0, chn_sc_ungap = 0;
+	int32_t split = 0;                // regions_from_chains: the chain spanned two strands / contigs (1: its head was kept, 2: its tail)
 	uint32_t hash = 0, vid = 0;
 	int32_t qs = 0, qe = 0;
 	int64_t vs = 0, ve = 0;

@@ -58,6 +58,7 @@ struct QueryState {
 	std::vector<AlignPlan> plans;
 	std::vector<uint64_t> seeds;         // kept seeds (query position << 32 | index bucket), ascending; only between the seeding sub-stages
 	std::vector<uint64_t> ext_refine;    // per region: window extension limits of the refinement (between the planning sub-stages)
+	int32_t n_chains = 0;                // main chains of the query before the selection (MPA_REGIONS_DUMP)
 	int64_t win0 = 0;                    // first refinement window of this query in the batch's list (device refinement)
 	int64_t n_anchor = 0;                // anchors those seeds expand to
 	bool seeds_ready = false;            // seeds / n_anchor / max_occ are the host's (stage_seeds has run); false after a device sketch: built when the host anchor stage asks
@@ -591,6 +592,53 @@ static inline ChainParams main_chain_params(const mpa_idx_s *mi, const mpa_mapop
 }
 
 static void stage_windows_from_chains(mpa_batch_s *b, QueryState &qs, const std::vector<uint64_t> &u, const std::vector<uint64_t> &a);
+
+// MPA_GPU_REGIONS: 0 / unset = main chains to refinement windows on the host (host_regions.cpp); 1 = on the device wherever device
+// seeding ran both chaining rounds (k_regions, region_kernels.hip): the regions come back instead of the chains; model = the host
+// instance of the device's code with a team of one (regions_core.h: the CPU tests), from host or device chains alike
+enum RegionsMode { REGIONS_HOST = 0, REGIONS_DEVICE, REGIONS_MODEL };
+static RegionsMode regions_mode()
+{
+	const char *e = getenv("MPA_GPU_REGIONS");          // (read per call: the tests flip it)
+	if (!e || !*e) return REGIONS_HOST;
+	if (!strcmp(e, "model")) return REGIONS_MODEL;
+	return atoi(e) != 0 ? REGIONS_DEVICE : REGIONS_HOST;
+}
+static RegionsParams regions_params(const mpa_idx_s *mi, const mpa_mapopt_t &opt)
+{
+	RegionsParams p;
+	p.n_vid = (int32_t)mi->bo.size() - 1, p.bbit = mi->opt.bbit, p.kmer = mi->opt.kmer, p.mask_len = opt.mask_len, p.best_n = opt.best_n;
+	p.max_ext = opt.max_ext, p.min_ext = 100, p.min_diff = mi->opt.kmer * 2, p.mask_level = opt.mask_level, p.pri_ratio = opt.pri_ratio * opt.pri_ratio;
+	return p;
+}
+// what the shared core left for a query (on the host or on the device), into its state
+static void regions_apply(QueryState &qs, int32_t n_chains, const RegionRec *r, const uint64_t *ext, int32_t n)
+{
+	qs.n_chains = n_chains;
+	qs.regs.clear(), qs.regs.resize((size_t)n);
+	for (int32_t i = 0; i < n; ++i) {
+		Region &x = qs.regs[(size_t)i];
+		const RegionRec &y = r[i];
+		x.off = y.off, x.cnt = y.cnt, x.id = y.id, x.parent = y.parent, x.n_sub = y.n_sub, x.subsc = y.subsc, x.chn_sc = y.chn_sc, x.chn_sc_ungap = y.chn_sc_ungap;
+		x.vid = y.vid, x.qs = y.qs, x.qe = y.qe, x.vs = y.vs, x.ve = y.ve, x.split = y.split;
+	}
+	qs.ext_refine.assign(ext, ext + n);
+}
+// MPA_GPU_REGIONS=model: the shared core with a team of one
+static void regions_model(mpa_batch_s *b, QueryState &qs, const uint64_t *u, int32_t n, const uint64_t *a)
+{
+	static thread_local std::vector<RegionRec> tmp, out;
+	static thread_local std::vector<Pair64> key;
+	static thread_local std::vector<SortRange> stack;
+	static thread_local std::vector<uint32_t> hist;
+	static thread_local std::vector<int32_t> prim;
+	static thread_local std::vector<uint64_t> cov, ext;
+	const size_t N = (size_t)n;
+	tmp.resize(N), out.resize(N), key.resize(N), stack.resize(N / 64 + 4), hist.resize(768), prim.resize(N + 2), cov.resize(N), ext.resize(N);
+	const RegionsScratch S{ tmp.data(), key.data(), stack.data(), hist.data(), prim.data(), cov.data(), prim.data() + N };
+	const int32_t k = regions_core<RegionsSerial>(regions_params(b->mi, b->opt), b->mi->bo.data(), u, n, a, S, out.data(), ext.data());
+	regions_apply(qs, n, out.data(), ext.data(), k);
+}
 static void stage_chain_to_windows(mpa_batch_s *b, QueryState &qs, std::vector<uint64_t> &a)
 {
 	const mpa_idx_s *mi = b->mi;
@@ -611,6 +659,8 @@ static void stage_windows_from_chains(mpa_batch_s *b, QueryState &qs, const std:
 	const mpa_mapopt_t &opt = b->opt;
 	std::vector<Region> &regs = qs.regs;
 	AccTimer tm(4);
+	if (regions_mode() == REGIONS_MODEL) { regions_model(b, qs, u.data(), (int32_t)u.size(), a.data()); return; }
+	qs.n_chains = (int32_t)u.size();
 	regions_from_chains(mi, u, a, regs);
 	sort_regions(regs);
 	assign_parents(opt.mask_level, opt.mask_len, regs, mi->opt.kmer);
@@ -1131,7 +1181,7 @@ static void batch_host_seeds(mpa_batch_s *b, bool have_device)
 
 // Phase 1b: the anchors of the seed jobs, the pre-chain and the main chain on the device (seed_exec.hip).  false = error.
 // sketch_ms: receives the wall time of the sketch stage where it ran in this phase (MPA_GPU_SKETCH), else 0
-static bool batch_device_seed_phase(mpa_ctx_t *seed_ctx, mpa_batch_s *b, bool want_chains, SeedHold *hold, double *sketch_ms = nullptr)
+static bool batch_device_seed_phase(mpa_ctx_t *seed_ctx, mpa_batch_s *b, bool want_chains, SeedHold *hold, double *sketch_ms = nullptr, bool for_planner = false)
 {
 	if (sketch_ms) *sketch_ms = 0;
 	if (!seed_ctx) return true;
@@ -1167,14 +1217,18 @@ static bool batch_device_seed_phase(mpa_ctx_t *seed_ctx, mpa_batch_s *b, bool wa
 	const double t1 = now_ms();
 	// (with the main chain's parameters the device carries on through both chaining rounds, unless the caller only wants the pre-chain)
 	const ChainParams main_cp = main_chain_params(mi, b->opt);
+	// (MPA_GPU_REGIONS=1 and the caller is the planner, which wants windows, not chains: the main round ends in k_regions)
+	const RegionsParams reg_p = regions_params(mi, b->opt);
+	const RegionsParams *rp = for_planner && want_chains && regions_mode() == REGIONS_DEVICE ? &reg_p : nullptr;
 	const int rc = route == SEED_DIRECT
-		? (jobs_on_device ? dev_seed_direct(seed_ctx, const_cast<mpa_idx_s*>(mi), main_cp, b->q.n_seq, sk.qfirst, nullptr, sk.n_jobs, b->sparse, hold, sk.jfirst)
-		                  : dev_seed_direct(seed_ctx, const_cast<mpa_idx_s*>(mi), main_cp, b->q.n_seq, b->seed_qfirst.data(), b->seed_jobs.data(), (int64_t)b->seed_jobs.size(), b->sparse, hold))
+		? (jobs_on_device ? dev_seed_direct(seed_ctx, const_cast<mpa_idx_s*>(mi), main_cp, b->q.n_seq, sk.qfirst, nullptr, sk.n_jobs, b->sparse, hold, sk.jfirst, nullptr, rp)
+		                  : dev_seed_direct(seed_ctx, const_cast<mpa_idx_s*>(mi), main_cp, b->q.n_seq, b->seed_qfirst.data(), b->seed_jobs.data(), (int64_t)b->seed_jobs.size(), b->sparse, hold,
+		                                    nullptr, nullptr, rp))
 		: jobs_on_device
 		? dev_prechain_forward(seed_ctx, const_cast<mpa_idx_s*>(mi), prechain_params(mi, b->opt), b->q.n_seq, sk.qfirst, nullptr, sk.n_jobs, b->sparse,
-		                       want_chains ? &main_cp : nullptr, hold, sk.jfirst)
+		                       want_chains ? &main_cp : nullptr, hold, sk.jfirst, rp)
 		: dev_prechain_forward(seed_ctx, const_cast<mpa_idx_s*>(mi), prechain_params(mi, b->opt), b->q.n_seq, b->seed_qfirst.data(), b->seed_jobs.data(),
-		                       (int64_t)b->seed_jobs.size(), b->sparse, want_chains ? &main_cp : nullptr, hold);
+		                       (int64_t)b->seed_jobs.size(), b->sparse, want_chains ? &main_cp : nullptr, hold, nullptr, rp);
 	std::vector<SeedJob>().swap(b->seed_jobs);
 	std::vector<int64_t>().swap(b->seed_qfirst);
 	if (rc == MPA_ERR_UNSUPPORTED) {                    // e.g. the batch does not fit the device: seed on the host
@@ -1194,10 +1248,11 @@ static bool batch_device_seed_phase(mpa_ctx_t *seed_ctx, mpa_batch_s *b, bool wa
 
 // Phase 1 of a batch: seeds of every query; with a device context and a batch that is worth it, also the anchors, the pre-chain
 // and the main chain on the device.
-static mpa_batch_t *batch_seed_phase(mpa_ctx_t *seed_ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads, bool want_chains = true, SeedHold *hold = nullptr)
+static mpa_batch_t *batch_seed_phase(mpa_ctx_t *seed_ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads, bool want_chains = true, SeedHold *hold = nullptr,
+                                     bool for_planner = false)
 {
 	mpa_batch_t *b = batch_sketch_phase(seed_ctx != nullptr, mi, opt, q, n_threads);
-	if (b && !batch_device_seed_phase(seed_ctx, b, want_chains, hold)) { delete b; return nullptr; }
+	if (b && !batch_device_seed_phase(seed_ctx, b, want_chains, hold, nullptr, for_planner)) { delete b; return nullptr; }
 	return b;
 }
 
@@ -1269,6 +1324,32 @@ static void gather_query_groups(const QueryGroups *per, int64_t n_q, RefineGroup
 	}
 }
 
+// MPA_REGIONS_DUMP=<file> (diagnostics; the tests' view of the stage): what the first planning step left for every query of the
+// batch, appended in query order, whichever path produced it.  Per query: int32 qid, chains before the selection, n; n records of
+// 64 bytes (int32 cnt, id, parent, n_sub, subsc, chn_sc, chn_sc_ungap; uint32 vid; int32 qs, qe; int64 vs, ve; int32 split flag,
+// int32 0); n refinement limits (uint64: left << 32 | right).  Layout and parser: tests/regionsdump.py
+static void regions_dump(const mpa_batch_s *b)
+{
+	const char *fn = getenv("MPA_REGIONS_DUMP");
+	if (!fn || !*fn) return;
+	static std::mutex mu;                                // (batches of a stream are planned side by side: one writer at a time)
+	std::lock_guard<std::mutex> g(mu);
+	FILE *fp = fopen(fn, "ab");
+	if (!fp) return;
+	for (const QueryState &qs : b->qs) {
+		const int32_t head[3] = { qs.qid, qs.n_chains, (int32_t)qs.regs.size() };
+		fwrite(head, 4, 3, fp);
+		for (const Region &r : qs.regs) {
+			const int32_t w[10] = { r.cnt, r.id, r.parent, r.n_sub, r.subsc, r.chn_sc, r.chn_sc_ungap, (int32_t)r.vid, r.qs, r.qe };
+			const int64_t v[2] = { r.vs, r.ve };
+			const int32_t t[2] = { r.split, 0 };
+			fwrite(w, 4, 10, fp), fwrite(v, 8, 2, fp), fwrite(t, 4, 2, fp);
+		}
+		if (!qs.regs.empty()) fwrite(qs.ext_refine.data(), 8, qs.regs.size(), fp);
+	}
+	fclose(fp);
+}
+
 static void batch_plan_phase(mpa_batch_s *b, mpa_ctx_t *rctx)
 {
 	const double t0 = now_ms();
@@ -1279,6 +1360,12 @@ static void batch_plan_phase(mpa_batch_s *b, mpa_ctx_t *rctx)
 		if (b->seeded_on_device && ps.has_chains && !(!ps.on_host.empty() && ps.on_host[(size_t)i])) {
 			// both chaining rounds ran on the device: its chains are what mp_chain() returns for this query (map.c:195)
 			g_acc[14] += b->qs[i].n_anchor * 1000;
+			if (ps.has_regions) {                              // ... and k_regions has made the windows from them: nothing to do but take them
+				AccTimer tm(4);
+				const int64_t u0 = ps.u_first[(size_t)i];
+				regions_apply(b->qs[i], (int32_t)(ps.u_first[(size_t)i + 1] - u0), ps.R + u0, ps.E + u0, ps.n_reg[i]);
+				return;
+			}
 			u.assign(ps.U + ps.u_first[(size_t)i], ps.U + ps.u_first[(size_t)i + 1]);
 			a.assign(ps.A + ps.a_first[(size_t)i], ps.A + ps.a_first[(size_t)i + 1]);
 			stage_windows_from_chains(b, b->qs[i], u, a);
@@ -1288,7 +1375,18 @@ static void batch_plan_phase(mpa_batch_s *b, mpa_ctx_t *rctx)
 		else stage_anchors_host(b, b->qs[i], a);
 		stage_chain_to_windows(b, b->qs[i], a);
 	});
+	if (timing_on()) {
+		const PrechainSparse &ps = b->sparse;
+		if (b->seeded_on_device && ps.has_regions) {
+			int64_t n_rec = 0;
+			for (int64_t i = 0; i < n_q; ++i) n_rec += ps.n_reg[i];
+			fprintf(stderr, "[mpa-timing]   regions on the GPU: %lld queries, records downloaded %lld B, anchors downloaded 0 B, anchors and chains not downloaded %lld B\n", (long long)n_q,
+			        (long long)(n_rec * (int64_t)(sizeof(RegionRec) + 8) + n_q * 4), (long long)((ps.a_first[(size_t)n_q] + ps.u_first[(size_t)n_q]) * 8));
+		}
+		if (regions_mode() == REGIONS_MODEL) timing_note("  regions: shared core", now_ms() - t0);
+	}
 	b->sparse = PrechainSparse();
+	regions_dump(b);
 	timing_note("  plan: anchors..windows (wall)", now_ms() - t0);
 	const double t_a = now_ms();
 	// the refinement scan of all windows on the device, if the batch is worth the round trip
@@ -1367,7 +1465,7 @@ static void batch_plan_phase(mpa_batch_s *b, mpa_ctx_t *rctx)
 
 static mpa_batch_t *batch_begin_impl(mpa_ctx_t *seed_ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads)
 {
-	mpa_batch_t *b = batch_seed_phase(seed_ctx, mi, opt, q, n_threads);
+	mpa_batch_t *b = batch_seed_phase(seed_ctx, mi, opt, q, n_threads, true, nullptr, true);
 	if (b) batch_plan_phase(b, seed_ctx);
 	return b;
 }
@@ -1971,7 +2069,7 @@ static int mpa_map_batches_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_m
 			trace(kSeedName[sd], k, "begin");
 			bool ok;
 			double sketch_ms = 0;
-			{ StageClock sc(0); ok = batch_device_seed_phase(seed_dev[sd], slot[k].b, true, hold[k % n_seed_ctx], &sketch_ms); }
+			{ StageClock sc(0); ok = batch_device_seed_phase(seed_dev[sd], slot[k].b, true, hold[k % n_seed_ctx], &sketch_ms, true); }
 			// (clock [4] is the sketch stage wherever it ran: with MPA_GPU_SKETCH its time inside this phase moves over from clock [0])
 			if (sketch_ms > 0) g_stage_us[4] += (int64_t)(sketch_ms * 1000.0), g_stage_us[0] -= (int64_t)(sketch_ms * 1000.0);
 			trace(kSeedName[sd], k, "end");

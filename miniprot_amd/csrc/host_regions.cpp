@@ -54,8 +54,8 @@ void regions_from_chains(const mpa_idx_s *mi, const std::vector<uint64_t> &u, co
 			head_end = j;
 			for (j = k + n - 1; j >= head_end; --j) if ((a[j] >> 32) < mi->bo[v_last]) break;
 			tail_beg = j + 1;
-			if (head_end - k > k + n - tail_beg) r.vid = (uint32_t)v_first, last = head_end - 1;
-			else r.vid = (uint32_t)v_last, first = tail_beg;
+			if (head_end - k > k + n - tail_beg) r.vid = (uint32_t)v_first, last = head_end - 1, r.split = 1;
+			else r.vid = (uint32_t)v_last, first = tail_beg, r.split = 2;
 		}
 		r.vs = (int64_t)((a[first] >> 32) - mi->bo[r.vid]) << bbit;
 		r.ve = (int64_t)((a[last] >> 32) - mi->bo[r.vid] + 1) << bbit;

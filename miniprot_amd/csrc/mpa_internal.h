@@ -11,6 +11,7 @@
 #include "../../include/mpamd.h"
 #include "chain_core.h"
 #include "aln_stats_core.h"
+#include "regions_core.h"
 
 namespace mpa {
 
@@ -135,6 +136,13 @@ struct PrechainSparse {              // result for a mini-batch: the chained anc
 	bool has_chains = false;
 	std::vector<int64_t> u_first, a_first;   // [n_query + 1]
 	const uint64_t *U = nullptr, *A = nullptr;   // pinned buffers of the context, valid until its next call
+	// has_regions (MPA_GPU_REGIONS=1, on top of has_chains): the main round ended in k_regions instead of k_chain_pack.  U and A stay
+	// null; u_first / a_first still count the chains and anchors of every query (what was NOT downloaded), and the selected regions
+	// of query q -- n_reg[q] fixed-size records and their refinement limits -- lie at R / E + u_first[q]
+	bool has_regions = false;
+	const RegionRec *R = nullptr;
+	const uint64_t *E = nullptr;
+	const int32_t *n_reg = nullptr;
 };
 // What the device refinement takes (k_refine_scan, k_refine_scan_map), stated once for the callers' gate (host_map.cpp) and the
 // guards of dev_refine_scan / dev_refine_chains: k-mers of 1..7 residues (4 bits each in a 32-bit word whose all-ones value marks
@@ -172,9 +180,11 @@ int dev_chain_forward(mpa_ctx_t *ctx, const ChainParams &p, int32_t n_prob, cons
 // hold != nullptr: the pinned result buffers live there (valid until the holder's next use) instead of in the context
 struct SeedHold;
 SeedHold *ctx_seed_hold(mpa_ctx_t *ctx, int k);   // k-th result holder of a context (created on first use, owned by it)
+// regions != nullptr (with main): the main round ends in the regions of every query instead of its chains (out.has_regions), unless a
+// pool or pinned block cannot grow -- then the chains come back as without it
 int dev_prechain_forward(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams &pre, int32_t n_query, const int64_t *qfirst,
                          const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, const ChainParams *main = nullptr, SeedHold *hold = nullptr,
-                         const int64_t *jfirst_dev = nullptr);
+                         const int64_t *jfirst_dev = nullptr, const RegionsParams *regions = nullptr);
 // Seeding where map.c:186 runs no pre-chain (-S, --no-pre-chain): the sift keeps the anchors that have another one within the main
 // chain's reach, and the main chain runs over them directly.  out as from dev_prechain_forward(main != nullptr): has_chains, on_host.
 // kept != nullptr (mpa_dbg_sift_kept): stop behind the sift; the kept anchors (block << 32 | query position) of every query in
@@ -182,7 +192,7 @@ int dev_prechain_forward(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams &pre, 
 static const int32_t kSiftReachMax = 15;   // widest reach the sift filters by; beyond it every anchor is kept
 struct SiftKept { std::vector<int64_t> first; std::vector<uint64_t> a; std::vector<uint8_t> flag; };
 int dev_seed_direct(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams &mainp, int32_t n_query, const int64_t *qfirst, const SeedJob *jobs, int64_t n_jobs,
-                    PrechainSparse &out, SeedHold *hold = nullptr, const int64_t *jfirst_dev = nullptr, SiftKept *kept = nullptr);
+                    PrechainSparse &out, SeedHold *hold = nullptr, const int64_t *jfirst_dev = nullptr, SiftKept *kept = nullptr, const RegionsParams *regions = nullptr);
 // The sketch stage (map.c:126-170) of a mini-batch on the device, sketch_exec.hip: the kept seeds of every query as the sift's
 // jobs, left in the context's device memory -- dev_prechain_forward(jobs = nullptr, jfirst_dev = jfirst) then runs on them.  What
 // comes back (pinned memory of the context, valid until its next sketch): first anchor / first job of every query, the cut-off in

@@ -5,6 +5,7 @@
 #include "dev_ctx.h"
 #include "seed_exec.hip"
 #include "sketch_exec.hip"
+#include "region_kernels.hip"
 
 namespace mpa {
 // ---- the chain tail (declared in dev_ctx.h): the forward pass of mp_chain, the extraction and the packed download, as every
@@ -128,8 +129,44 @@ int chain_extract_launch(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCa
 	return MPA_OK;
 }
 
+// The regions of every problem behind its main-chain extraction (MPA_GPU_REGIONS=1): k_regions reads the chains where the extraction
+// left them in X, k_region_pack puts records, limits and counts into the holder's pinned block.  Everything is laid out by the prefix
+// of the chain counts (h_offu, on the device at c.offu), which the caller has just downloaded: a query keeps at most as many regions
+// as it has chains.  MPA_ERR_UNSUPPORTED: a pool or the pinned block could not grow -- nothing was launched, the caller packs the chains.
+static int regions_tail(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCarve &c, const ChainViewDev &v, int32_t n_prob, SeedHold &H, int64_t tot_u, RegionsTail &rt)
+{
+	SeedBufs &B = ctx->seed;
+	const size_t T = (size_t)tot_u, NP = (size_t)n_prob;
+	const double t0 = now_ms();
+	Carve cv;
+	const size_t o_tmp = cv(T * sizeof(RegionRec)), o_out = cv(T * sizeof(RegionRec)), o_ext = cv(T * 8), o_cov = cv(T * 8), o_key = cv(T * sizeof(Pair64));
+	const size_t o_stack = cv((T / 64 + 5 * NP + 8) * sizeof(SortRange)), o_hist = cv(NP * 768 * 4), o_prim = cv(T * 4), o_ctl = cv(NP * 8), o_nreg = cv(NP * 4);
+	const size_t h_ext = T * sizeof(RegionRec), h_nreg = h_ext + T * 8;
+	if (B.rg.ensure(cv.at + 256) != MPA_OK || H.h_R.ensure(h_nreg + NP * 4 + 64) != MPA_OK) {
+		tl_alloc_failed = false;
+		if (timing_on()) fprintf(stderr, "[mpa-timing]   device regions declined (%s): chains to the host\n", mpa_last_error());
+		return MPA_ERR_UNSUPPORTED;
+	}
+	char *G = B.rg.as<char>(), *P = H.h_R.as<char>();
+	rt.R = (const RegionRec*)P, rt.E = (const uint64_t*)(P + h_ext), rt.n_reg = (const int32_t*)(P + h_nreg);
+	if (tot_u == 0) { memset(P + h_nreg, 0, NP * 4); rt.done = true; return MPA_OK; }
+	RegionsArgs ra;
+	ra.first = v.first, ra.a = (const uint64_t*)(X + c.out_a), ra.u = (const uint64_t*)(X + c.out_u), ra.nu = (const int64_t*)(X + c.nu), ra.offu = (const int64_t*)(X + c.offu);
+	ra.bo = rt.d_bo, ra.p = rt.p;
+	ra.tmp = (RegionRec*)(G + o_tmp), ra.out = (RegionRec*)(G + o_out), ra.ext = (uint64_t*)(G + o_ext), ra.cov = (uint64_t*)(G + o_cov), ra.key = (Pair64*)(G + o_key);
+	ra.stack = (SortRange*)(G + o_stack), ra.hist = (uint32_t*)(G + o_hist), ra.prim = (int32_t*)(G + o_prim), ra.ctl = (int32_t*)(G + o_ctl), ra.n_reg = (int32_t*)(G + o_nreg);
+	hipLaunchKernelGGL(k_regions, dim3((unsigned)((n_prob + REGIONS_WAVES - 1) / REGIONS_WAVES)), dim3(64 * REGIONS_WAVES), 0, s, ra, n_prob);
+	hipLaunchKernelGGL(k_region_pack, dim3((unsigned)n_prob), dim3(256), 0, s, ra.offu, (const int32_t*)ra.n_reg, (const RegionRec*)ra.out, (const uint64_t*)ra.ext,
+	                   (RegionRec*)P, (uint64_t*)(P + h_ext), (int32_t*)(P + h_nreg));
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(wait_stream(ctx, s));
+	rt.done = true;
+	timing_note("    seed: regions + pack (wait)", now_ms() - t0);
+	return MPA_OK;
+}
+
 int chain_extract_pack(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCarve &c, const ChainViewDev &v, const ChainParams &p, int32_t n_prob, SeedHold &H,
-                       const char *prof_label, const char *status_error, ChainTailOut out, const int32_t **h_status_out)
+                       const char *prof_label, const char *status_error, ChainTailOut out, const int32_t **h_status_out, RegionsTail *regions)
 {
 	SeedBufs &B = ctx->seed;
 	const size_t NP = (size_t)n_prob;
@@ -149,6 +186,17 @@ int chain_extract_pack(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCarv
 	if (status_error)
 		for (size_t w = 0; w < NP; ++w) if (h_status[w]) { set_error(status_error); return MPA_ERR_UNSUPPORTED; }
 	const int64_t tot_a = h_offa[n_prob], tot_u = h_offu[n_prob];
+	if (regions) {                                            // the regions instead of the chains; declined: the chains, as without it
+		regions->done = false;
+		rc = regions_tail(ctx, s, X, c, v, n_prob, H, tot_u, *regions);
+		if (rc == MPA_OK) {
+			out.a_first.assign(h_offa, h_offa + n_prob + 1), out.u_first.assign(h_offu, h_offu + n_prob + 1);
+			out.A = out.U = nullptr;
+			if (h_status_out) *h_status_out = h_status;
+			return MPA_OK;
+		}
+		if (rc != MPA_ERR_UNSUPPORTED) return rc;
+	}
 	if ((rc = H.h_A.ensure((size_t)tot_a * 8 + 64)) || (rc = H.h_U.ensure((size_t)tot_u * 8 + 64))) return rc;
 	if (tot_a > 0 || tot_u > 0) {
 		hipLaunchKernelGGL(k_chain_pack, dim3((unsigned)n_prob), dim3(256), 0, s, v.first, (const int64_t*)(X + c.na), (const int64_t*)(X + c.nu),
@@ -173,6 +221,41 @@ static void seed_mark_on_host(PrechainSparse &out, int32_t n_query, const int32_
 		for (int32_t q = 0; q < n_query; ++q) if (h_status[q] || (h_flag && h_flag[q])) out.on_host[(size_t)q] = 1;
 	}
 }
+
+// bo[] next to kb[] in HBM, on the first device regions call of a device (like ki[] for the device sketch).  No device memory for it:
+// nullptr, and the caller keeps the chains' route.
+static const uint32_t *ensure_dev_bo(mpa_ctx_t *ctx, mpa_idx_s *mi)
+{
+	DeviceIndex *d = mi->dev[ctx->device];
+	if (d->bo) return d->bo;
+	static std::mutex mu[mpa_idx_s::kMaxDevices];            // (per device, like dev_upload_index)
+	std::lock_guard<std::mutex> g(mu[ctx->device]);
+	if (d->bo) return d->bo;
+	uint32_t *p = nullptr;
+	const size_t bytes = mi->bo.size() * 4;
+	if (hipMalloc((void**)&p, bytes + 16) != hipSuccess) { (void)hipGetLastError(); set_error("device regions: no device memory for the block offsets"); return nullptr; }
+	if (hipMemcpy(p, mi->bo.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(p); set_error("device regions: uploading the block offsets"); return nullptr; }
+	d->bo_bytes = bytes + 16, g_dev_bytes += (long long)d->bo_bytes;
+	d->bo = p;
+	return d->bo;
+}
+// what a seeding route hands the chain tail for MPA_GPU_REGIONS=1 (nullptr: the chains), and what it takes from it afterwards
+static RegionsTail *regions_tail_begin(mpa_ctx_t *ctx, mpa_idx_s *mi, const RegionsParams *rp, RegionsTail &rt)
+{
+	if (!rp) return nullptr;
+	const uint32_t *d_bo = ensure_dev_bo(ctx, mi);
+	if (!d_bo) {
+		if (timing_on()) fprintf(stderr, "[mpa-timing]   device regions declined (%s): chains to the host\n", mpa_last_error());
+		return nullptr;
+	}
+	rt = RegionsTail{ *rp, d_bo, false, nullptr, nullptr, nullptr };
+	return &rt;
+}
+static void regions_tail_end(const RegionsTail *rt, PrechainSparse &out)
+{
+	out.has_regions = rt && rt->done;
+	if (out.has_regions) out.R = rt->R, out.E = rt->E, out.n_reg = rt->n_reg;
+}
 } // namespace mpa
 
 namespace mpa {
@@ -180,7 +263,7 @@ namespace mpa {
 // staging; everything behind the sift is sized by the kept anchors.  The result arrays are written by k_seed_compact straight
 // into pinned host memory (no copy kernels, no second pass over HBM).
 static int dev_chains_on_device(mpa_ctx_t *ctx, int32_t n_query, int64_t m, int64_t n2, int nb, const uint64_t *key, const uint64_t *val, const int64_t *d_qfirst,
-                                const int32_t *h_flag, const ChainParams &pre, const ChainParams &mainp, PrechainSparse &out, SeedHold &H);
+                                const int32_t *h_flag, const ChainParams &pre, const ChainParams &mainp, PrechainSparse &out, SeedHold &H, RegionsTail *regions);
 
 // The sift of a batch up to the host's first look at it: segments, k_seed_sift, k_sift_offsets, the per-query first kept anchor
 // and the hand-back flags down (one wait).  reach < 0: the pre-chain's keep rule (same or adjacent block, halved staging for large
@@ -297,7 +380,7 @@ static int dev_sift_front(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_block, int 
 
 static int dev_prechain_forward_sift(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_block, const PreParams &pp, int nb, int32_t n_query, const int64_t *qfirst,
                                      const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, double t_begin, const ChainParams *pre_cp, const ChainParams *main_cp, SeedHold &H,
-                                     const int64_t *jfirst_in = nullptr)
+                                     const int64_t *jfirst_in = nullptr, RegionsTail *regions = nullptr)
 {
 	SeedBufs &B = ctx->seed;
 	hipStream_t s = ctx->seed_stream;
@@ -342,7 +425,7 @@ static int dev_prechain_forward_sift(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_
 	// both chaining rounds on the device (main_cp == nullptr: the caller wants the pre-chain's linked anchors, as rounds 1-2 did)
 	{
 		if (main_cp && pre_cp) {
-			rc = dev_chains_on_device(ctx, n_query, m, n2, nb, key, val, d_qfirst, h_flag, *pre_cp, *main_cp, out, H);
+			rc = dev_chains_on_device(ctx, n_query, m, n2, nb, key, val, d_qfirst, h_flag, *pre_cp, *main_cp, out, H, regions);
 			if (rc != MPA_ERR_UNSUPPORTED) { timing_note("    seed: chains on the device", now_ms() - t_kernels); return rc; }
 		}
 	}
@@ -366,7 +449,7 @@ static int dev_prechain_forward_sift(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_
 // (~11 000 per query at 3 Gbp), and the host no longer spends a core-second per mini-batch on chaining.
 // key/val: the kept anchors (dense, sorted), with B.f / B.pred / B.flag / B.idx / B.cfirst from the pre-chain's forward pass.
 static int dev_chains_on_device(mpa_ctx_t *ctx, int32_t n_query, int64_t m, int64_t n2, int nb, const uint64_t *key, const uint64_t *val, const int64_t *d_qfirst,
-                                const int32_t *h_flag, const ChainParams &pre, const ChainParams &mainp, PrechainSparse &out, SeedHold &H)
+                                const int32_t *h_flag, const ChainParams &pre, const ChainParams &mainp, PrechainSparse &out, SeedHold &H, RegionsTail *regions)
 {
 	SeedBufs &B = ctx->seed;
 	hipStream_t s = ctx->seed_stream;
@@ -404,7 +487,7 @@ static int dev_chains_on_device(mpa_ctx_t *ctx, int32_t n_query, int64_t m, int6
 	// ... and extraction: dense views over the survivors; the chains of all queries into pinned memory
 	const ChainViewDev main_view{ B.cfirst.as<int64_t>(), (const int64_t*)(X + o_pre_na), nullptr, nullptr, (const int32_t*)(X + o_mf), (const int32_t*)(X + o_mpred), (const uint64_t*)(X + o_pre_a) };
 	const int32_t *h_status = nullptr;
-	if ((rc = chain_extract_pack(ctx, s, X, xc, main_view, mainp, n_query, H, "main chain", nullptr, ChainTailOut{ out.a_first, out.u_first, out.A, out.U }, &h_status))) return rc;
+	if ((rc = chain_extract_pack(ctx, s, X, xc, main_view, mainp, n_query, H, "main chain", nullptr, ChainTailOut{ out.a_first, out.u_first, out.A, out.U }, &h_status, regions))) return rc;
 	out.has_chains = true;
 	seed_mark_on_host(out, n_query, h_status, h_flag);
 	return MPA_OK;
@@ -422,7 +505,7 @@ static int dev_chains_on_device(mpa_ctx_t *ctx, int32_t n_query, int64_t m, int6
 // lies in no window that a kept anchor's max_skip / max_iter walk visits -- what a sparse view may leave out (chain_core.h).
 // pm: the main chain's parameters as the forward pass takes them (pm.max_dblock = the sift's reach).
 static int dev_seed_direct_impl(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_block, const PreParams &pm, int nb, int32_t n_query, const int64_t *qfirst, const SeedJob *jobs,
-                                int64_t n_jobs, PrechainSparse &out, double t_begin, const ChainParams &mainp, SeedHold &H, const int64_t *jfirst_in, SiftKept *kept)
+                                int64_t n_jobs, PrechainSparse &out, double t_begin, const ChainParams &mainp, SeedHold &H, const int64_t *jfirst_in, SiftKept *kept, RegionsTail *regions)
 {
 	SeedBufs &B = ctx->seed;
 	hipStream_t s = ctx->seed_stream;
@@ -467,7 +550,7 @@ static int dev_seed_direct_impl(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_block
 	                           ChainFwdBufs{ (int32_t*)(X + o_vf), (int32_t*)(X + o_vpred), (int32_t*)(X + o_fmark), (uint32_t*)(X + xc.mark), (LongRun*)(X + o_long), (unsigned int*)(X + o_nlong), long_cap }))) return rc;
 	const ChainViewDev view{ d_first, nullptr, F.d_qfirst, (const int32_t*)(X + o_vpos), (const int32_t*)(X + o_vf), (const int32_t*)(X + o_vpred), (const uint64_t*)(X + o_va) };
 	const int32_t *h_status = nullptr;
-	if ((rc = chain_extract_pack(ctx, s, X, xc, view, mainp, n_query, H, nullptr, nullptr, ChainTailOut{ out.a_first, out.u_first, out.A, out.U }, &h_status))) return rc;
+	if ((rc = chain_extract_pack(ctx, s, X, xc, view, mainp, n_query, H, nullptr, nullptr, ChainTailOut{ out.a_first, out.u_first, out.A, out.U }, &h_status, regions))) return rc;
 	out.has_chains = true;
 	seed_mark_on_host(out, n_query, h_status, F.h_flag);       // (the sift's hand-backs are in out.on_host already: dev_sift_front)
 	timing_note("    seed: copy + main chain on the device", now_ms() - F.t_sift);
@@ -480,12 +563,14 @@ static int dev_seed_direct_impl(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_block
 // (pred = index into the query's part of the view, -1 for none).
 // pre_p == nullptr: the direct route (dev_seed_direct) -- no pre-chain, the sift keeps by the reach of the main chain *main
 static int dev_seed_entry(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams *pre_p, int32_t n_query, const int64_t *qfirst,
-                          const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, const ChainParams *main, SeedHold *hold, const int64_t *jfirst_dev, SiftKept *kept)
+                          const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, const ChainParams *main, SeedHold *hold, const int64_t *jfirst_dev, SiftKept *kept,
+                          const RegionsParams *regions)
 {
 	const int64_t n = qfirst[n_query];
 	out.cfirst.assign((size_t)n_query + 1, 0);
 	out.pos = out.f = out.pred = nullptr, out.a = nullptr, out.m = 0, out.on_host.clear();
 	out.has_chains = false, out.U = out.A = nullptr, out.u_first.clear(), out.a_first.clear();
+	out.has_regions = false, out.R = nullptr, out.E = nullptr, out.n_reg = nullptr;
 	if (!pre_p) {                                              // (no anchors: no chains -- the planners take that from the device's result like any other)
 		out.has_chains = !kept, out.u_first.assign((size_t)n_query + 1, 0), out.a_first.assign((size_t)n_query + 1, 0);
 		if (kept) kept->first.assign((size_t)n_query + 1, 0), kept->a.clear(), kept->flag.assign((size_t)n_query, 0);
@@ -537,25 +622,28 @@ static int dev_seed_entry(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams *pre_
 	}
 	// merge the occurrence lists per query in block order, keep what has a neighbour (k_seed_sift, seed_exec.hip)
 	tl_alloc_failed = false;
-	const int rc = pre_p ? dev_prechain_forward_sift(ctx, d, mi->n_block, pp, nb, n_query, qfirst, jobs, n_jobs, out, t_begin, &pre, main, hold ? *hold : B.own, jfirst_dev)
-	                     : dev_seed_direct_impl(ctx, d, mi->n_block, pp, nb, n_query, qfirst, jobs, n_jobs, out, t_begin, *main, hold ? *hold : B.own, jfirst_dev, kept);
+	RegionsTail rtail;
+	RegionsTail *const rt = regions_tail_begin(ctx, mi, main && !kept ? regions : nullptr, rtail);
+	const int rc = pre_p ? dev_prechain_forward_sift(ctx, d, mi->n_block, pp, nb, n_query, qfirst, jobs, n_jobs, out, t_begin, &pre, main, hold ? *hold : B.own, jfirst_dev, rt)
+	                     : dev_seed_direct_impl(ctx, d, mi->n_block, pp, nb, n_query, qfirst, jobs, n_jobs, out, t_begin, *main, hold ? *hold : B.own, jfirst_dev, kept, rt);
+	if (rc == MPA_OK) regions_tail_end(rt, out);
 	// a pool that could not grow (the admission check above is an estimate): the batch is seeded on the host, as for any batch
 	// that does not fit -- nothing has been handed to the caller yet
 	if (rc == MPA_ERR_HIP && tl_alloc_failed) { (void)hipStreamSynchronize(s); return MPA_ERR_UNSUPPORTED; }
 	return rc;
 }
 int dev_prechain_forward(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams &pre, int32_t n_query, const int64_t *qfirst,
-                         const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, const ChainParams *main, SeedHold *hold, const int64_t *jfirst_dev)
+                         const SeedJob *jobs, int64_t n_jobs, PrechainSparse &out, const ChainParams *main, SeedHold *hold, const int64_t *jfirst_dev, const RegionsParams *regions)
 {
-	return dev_seed_entry(ctx, mi, &pre, n_query, qfirst, jobs, n_jobs, out, main, hold, jfirst_dev, nullptr);
+	return dev_seed_entry(ctx, mi, &pre, n_query, qfirst, jobs, n_jobs, out, main, hold, jfirst_dev, nullptr, regions);
 }
 // Seeding without a pre-chain (-S, --no-pre-chain; MPA_GPU_SEED_NOPRE): sift by the main chain's reach, then the main chain itself
 // (dev_seed_direct_impl).  Same contract as dev_prechain_forward(main != nullptr): out.has_chains, out.on_host.  kept != nullptr
 // (test hook): stop behind the sift and hand out the kept anchors instead.
 int dev_seed_direct(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams &mainp, int32_t n_query, const int64_t *qfirst, const SeedJob *jobs, int64_t n_jobs,
-                    PrechainSparse &out, SeedHold *hold, const int64_t *jfirst_dev, SiftKept *kept)
+                    PrechainSparse &out, SeedHold *hold, const int64_t *jfirst_dev, SiftKept *kept, const RegionsParams *regions)
 {
-	return dev_seed_entry(ctx, mi, nullptr, n_query, qfirst, jobs, n_jobs, out, &mainp, hold, jfirst_dev, kept);
+	return dev_seed_entry(ctx, mi, nullptr, n_query, qfirst, jobs, n_jobs, out, &mainp, hold, jfirst_dev, kept, regions);
 }
 
 // ki[] next to kb[] in HBM, on the first device sketch of a device.  The host array may be a misaligned view into a mapped .mpi:

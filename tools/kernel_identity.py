@@ -6,7 +6,7 @@ local labels (.LBB<n>_, .Lfunc_begin<n>, .Ltmp<n>: they count functions of the u
 Exit status 1 if a kernel differs or the two sets of kernels differ."""
 import os, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
-UNITS = ("dev_ctx.hip", "seed_run.hip", "refine_run.hip", "index_run.hip", "dp_exec.hip")
+UNITS = ("dev_ctx.hip", "seed_run.hip", "refine_run.hip", "index_run.hip", "dp_exec.hip", "stats_run.hip")
 
 def kernels_of(tree):
     csrc = os.path.join(tree, "miniprot_amd", "csrc")

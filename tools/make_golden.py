@@ -13,6 +13,8 @@ oracle/Makefile).  Run in the authoring container only; the outputs are committe
     defaults; the index flags go to the reference with the FASTA): `make_golden.py options` makes only these
   * long_u.ref.paf: reference PAF for the long-protein case of tests/longprot.py (device refinement past the LDS k-mer map):
     `make_golden.py long` makes only this
+  * regions_edge.ref.paf: reference PAF for the edge genome of tests/regioncases.py (chains across strand and contig boundaries, more
+    than 64 chains of one score): `make_golden.py regions` makes only this, after checking that the host path shows all three
   * ref_layout.txt: sizes and offsets of the reference's records as its own headers declare them (tests/test_compat.py):
     `make_golden.py layout <reference source dir>` makes only this
 """
@@ -128,7 +130,37 @@ def make_long_case():
     print("long_u", len(out), "bytes", out.count(b"\n"), "lines")
 
 
+def make_regions_edge():
+    """tests/golden/regions_edge.ref.paf: the reference's output for the edge genome of tests/regioncases.py.  The genome is only
+    worth a fixture if the host path meets on it what the tests assert first: the split flag in both directions, a query with more
+    than 64 chains before the selection, and more than 64 kept regions of one chn_sc"""
+    import miniprot_amd as mpa
+    import regioncases
+    import regionsdump
+    from hostpipe import map_batch_result, oracle_executor
+    contigs, prots, names, mo = regioncases.edge_genome()
+    with tempfile.TemporaryDirectory() as tmp:
+        dump = os.path.join(tmp, "regions.dump")
+        os.environ.pop("MPA_GPU_REGIONS", None)
+        os.environ["MPA_REGIONS_DUMP"] = dump
+        idx, q = regioncases.edge_index(contigs), mpa.Queries(prots, names)
+        ours = mpa.format_output(idx, mo, q, map_batch_result(idx, mo, q, oracle_executor, 4))[0]
+        del os.environ["MPA_REGIONS_DUMP"]
+        flags, most, ties = regioncases.edge_findings(regionsdump.read(dump))
+        assert flags == {1, 2} and most > 64 and ties > 64, (flags, most, ties)
+        fa, faa = os.path.join(tmp, "g.fa"), os.path.join(tmp, "p.fa")
+        gen_synth.write_fasta_nt(fa, contigs)
+        gen_synth.write_fasta_aa(faa, prots, names)
+        out = run_ref(regioncases.EDGE_FLAGS + [fa, faa])
+    assert ours == out, "the host path with the oracle executor does not print the reference's bytes for the edge genome"
+    open(golden.path(regioncases.EDGE_REF), "wb").write(out)
+    print("regions_edge", len(out), "bytes", out.count(b"\n"), "lines; split flags", sorted(flags), "chains", most, "equal scores", ties)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "regions":
+        make_regions_edge()
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "options":
         make_option_cases()
         return
@@ -180,6 +212,7 @@ def main():
     make_penalty_vectors()
     make_option_cases()
     make_long_case()
+    make_regions_edge()
 
 
 if __name__ == "__main__":
