@@ -80,7 +80,8 @@ struct HostPinned {
 // What a seeding call leaves for the planning stage: pinned host memory only.  In the stream pipeline the device pools belong to
 // the SEEDER (two of them), the results to the batch (one holder per batch between the start of its seeding and the end of its
 // planning), so that a batch waiting to be planned does not pin down a full set of device pools.
-struct SeedHold { HostPinned h_pos, h_f, h_pred, h_a, h_U, h_A, h_R; };   // h_R (MPA_GPU_REGIONS=1): region records | refinement limits | regions per query
+struct SeedHold { HostPinned h_pos, h_f, h_pred, h_a, h_U, h_A, h_R, h_P; };   // h_R (MPA_GPU_REGIONS=1): region records | refinement limits | regions per query
+                                                                                // h_P (MPA_GPU_PLANS=1): regions | plans | round-1 tasks | gap segments | counts per query
 
 struct SeedBufs {
 	DevBuf jobs, f, pred, mark, flag, idx, tmp, cfirst;
@@ -95,6 +96,7 @@ struct SeedBufs {
 	DevBuf k_in, k_cnt, k_bkt, k_q;                                         // device sketch (sketch_exec.hip): residue table + q_off + protein text; count and bucket per position; per-query counts, prefixes, cut-offs, flags
 	HostPinned h_kin, h_kout;                                              // ... its staging (up) and qfirst / jfirst / cut-offs / flags (down)
 	DevBuf rg;                                                             // device regions (k_regions): records, limits and per-query scratch, carved up per call
+	DevBuf pl;                                                             // device plans (k_plans): records and per-query scratch, carved up per call
 	DevBuf x_all;                                                          // device chaining: views, extraction scratch, survivors, main-chain state, chains (carved up per call)
 	DevBuf rx_all, rx_keys;                                                // device refinement: pairing tables, pair keys (two buffers), chain state (carved up per call)
 	HostPinned h_xoff;                                                     // ... offsets of the chains of every query (down)
@@ -171,7 +173,7 @@ template<typename F> static void ctx_each_devbuf(mpa_ctx_s *ctx, F f)
 	                  &B.c_a, &B.c_f, &B.c_pred, &B.c_mark, &B.c_flag, &B.c_first, &B.c_long,
 	                  &B.pf_qfirst2, &B.val64[0], &B.val64[1],
 	                  &B.s_meta, &B.s_cur, &B.s_cur2, &B.s_kept, &B.s_base, &B.s_out, &B.s_flag, &B.dkey, &B.x_all, &B.rx_all, &B.rx_keys,
-	                  &ctx->lite, &ctx->ckpt, &ctx->wlist, &B.k_in, &B.k_cnt, &B.k_bkt, &B.k_q, &B.r_gmap, &ctx->st_in, &ctx->st_out, &B.rg };
+	                  &ctx->lite, &ctx->ckpt, &ctx->wlist, &B.k_in, &B.k_cnt, &B.k_bkt, &B.k_q, &B.r_gmap, &ctx->st_in, &ctx->st_out, &B.rg, &B.pl };
 	int k = 0;
 	for (DevBuf *b : all) f(*b, k++);
 }
@@ -217,9 +219,24 @@ int chain_extract_launch(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCa
 // regions of every problem (records, refinement limits, their number: RegionsTail) come down instead of its chains, out.A / out.U stay
 // null, a_first / u_first still count what was left on the device.  A pool or pinned block that cannot grow: `done` stays false and
 // the chains are packed as without it.
+// plans != nullptr (MPA_GPU_PLANS=1, the refinement): k_plans + k_plan_pack take k_chain_pack's place -- the problems are the
+// refinement windows of n_query queries (window w of query q: h_win0[q] <= w < h_win0[q + 1]), and what comes down are every query's
+// regions, plans, round-1 tasks and gap segments (PlansTail).  The caller has uploaded what the d_ pointers name.  Declined as the
+// regions are: `done` stays false and the chains are packed.
 struct ChainTailOut { std::vector<int64_t> &a_first, &u_first; const uint64_t *&A, *&U; };
+struct PlansTail {
+	PlansParams p;
+	int32_t n_query;
+	const PlansWindow *d_win;            // [n_prob]
+	const int64_t *d_win0, *d_qoff;      // [n_query + 1] first window; first residue in d_text
+	const uint8_t *d_text, *d_tabs;      // the protein text; codon table | aa20 | matrix (ALN_TAB_BYTES)
+	const uint8_t *d_seq;                // the resident genome and its contig table
+	const int64_t *d_ctg_off, *d_ctg_len;
+	bool done;
+	const RegionRec *R; const PlanRec *P; const mpa_dp_task_t *T; const SegRec *S; const PlansCounts *N;   // pinned (H.h_P): see RefineChains
+};
 struct RegionsTail { RegionsParams p; const uint32_t *d_bo; bool done; const RegionRec *R; const uint64_t *E; const int32_t *n_reg; };
 int chain_extract_pack(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCarve &c, const ChainViewDev &v, const ChainParams &p, int32_t n_prob, SeedHold &H,
-                       const char *prof_label, const char *status_error, ChainTailOut out, const int32_t **h_status, RegionsTail *regions = nullptr);
+                       const char *prof_label, const char *status_error, ChainTailOut out, const int32_t **h_status, RegionsTail *regions = nullptr, PlansTail *plans = nullptr);
 
 } // namespace mpa

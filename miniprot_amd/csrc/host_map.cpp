@@ -1350,6 +1350,166 @@ static void regions_dump(const mpa_batch_s *b)
 	fclose(fp);
 }
 
+// MPA_GPU_PLANS: 0 / unset = refinement chains to regions, plans, round-1 tasks and gap segments on the host (stage_refine_to_plan,
+// plan_round1); 1 = on the device wherever dev_refine_chains ran (k_plans, plan_kernels.hip): the records come back instead of the
+// refinement chains; model = the host instance of the device's code with a team of one (plans_core.h: the CPU tests), from the
+// device's chains or the host refinement's alike
+enum PlansMode { PLANS_HOST = 0, PLANS_DEVICE, PLANS_MODEL };
+static PlansMode plans_mode()
+{
+	const char *e = getenv("MPA_GPU_PLANS");            // (read per call: the tests flip it)
+	if (!e || !*e) return PLANS_HOST;
+	if (!strcmp(e, "model")) return PLANS_MODEL;
+	return atoi(e) != 0 ? PLANS_DEVICE : PLANS_HOST;
+}
+static PlansParams plans_params(const mpa_idx_s *mi, const mpa_mapopt_t &opt)
+{
+	PlansParams p;
+	p.kmer2 = opt.kmer2, p.kmer = mi->opt.kmer, p.mask_len = opt.mask_len, p.best_n = opt.best_n, p.max_ext = opt.max_ext, p.max_intron = opt.max_intron;
+	p.io = opt.io, p.io_end = opt.io_end, p.no_align = (opt.flag & MPA_MF_NO_ALIGN) ? 1 : 0, p.asize = opt.asize;
+	p.mask_level = opt.mask_level, p.pri_ratio = opt.pri_ratio * opt.pri_ratio;
+	return p;
+}
+static inline PlansWindow plans_window(const mpa_idx_s *mi, const Region &r, uint64_t ext)
+{
+	int64_t as, ae;
+	refine_window(mi, r, ext, &as, &ae);
+	return PlansWindow{ as, r.vid, r.n_sub, r.subsc, r.split };
+}
+// the genome as plans_core.h reads it on the host
+struct PlansGenomeHost {
+	const mpa_idx_s *mi;
+	int64_t off(int32_t c) const { return mi->ctg[(size_t)c].off; }
+	int64_t len(int32_t c) const { return mi->ctg[(size_t)c].len; }
+	StatsGenomeHost strand(uint32_t vid) const { const Contig &c = mi->ctg[vid >> 1]; return StatsGenomeHost{ mi->seq.data(), c.off, c.len, (int)(vid & 1) }; }
+};
+// what the shared core left for a query (on the host or on the device), into its state.  Region::a stays empty: nothing reads it
+// behind plan_round1
+static void plans_apply(QueryState &qs, const PlansCounts &n, const RegionRec *r, const PlanRec *pl, const mpa_dp_task_t *t, const SegRec *sg)
+{
+	qs.regs.clear(), qs.regs.resize((size_t)n.n_reg);
+	for (int32_t i = 0; i < n.n_reg; ++i) {
+		Region &x = qs.regs[(size_t)i];
+		const RegionRec &y = r[i];
+		x.off = y.off, x.cnt = y.cnt, x.id = y.id, x.parent = y.parent, x.n_sub = y.n_sub, x.subsc = y.subsc, x.chn_sc = y.chn_sc, x.chn_sc_ungap = y.chn_sc_ungap;
+		x.vid = y.vid, x.qs = y.qs, x.qe = y.qe, x.vs = y.vs, x.ve = y.ve, x.split = y.split;
+	}
+	qs.plans.clear(), qs.plans.resize((size_t)n.n_plan);
+	for (int32_t i = 0; i < n.n_plan; ++i) {
+		AlignPlan &x = qs.plans[(size_t)i];
+		const PlanRec &y = pl[i];
+		x.reg = y.reg, x.as = y.as, x.ae = y.ae, x.vs0 = y.vs0, x.vs1 = y.vs1, x.as1 = y.as1, x.mid_ve = y.mid_ve, x.mid_qe = y.mid_qe, x.has_right = y.has_right != 0;
+		x.t_left = y.t_left, x.t_left2 = y.t_left2, x.t_right = y.t_right, x.t_right2 = y.t_right2;
+		x.gaps.resize((size_t)y.n_gap);
+		for (int32_t g = 0; g < y.n_gap; ++g) {
+			Segment &s = x.gaps[(size_t)g];
+			const SegRec &z = sg[y.gap0 + g];
+			s.ne0 = z.ne0, s.ne1 = z.ne1, s.ae0 = z.ae0, s.ae1 = z.ae1, s.task = z.task, s.score = z.score;
+			if (z.task < 0) s.cigar.assign(1, (uint32_t)(z.ae1 - z.ae0) << 4);
+		}
+	}
+	qs.local1.assign(t, t + n.n_task);
+}
+// MPA_GPU_PLANS=model: the chains of every refinement window of the query -- the device's (rc), or the host refinement's own,
+// collected instead of consumed region by region -- through the shared core with a team of one
+static void plans_model(mpa_batch_s *b, QueryState &qs, const RefineHits *rh, const RefineChains *rc)
+{
+	const mpa_idx_s *mi = b->mi;
+	const mpa_mapopt_t &opt = b->opt;
+	static thread_local std::vector<uint64_t> U, A, pa, pu, cov, ext;
+	static thread_local std::vector<int64_t> cu, ca, nu, aoff;
+	static thread_local std::vector<PlansWindow> win;
+	static thread_local std::vector<RegionRec> tmp, reg;
+	static thread_local std::vector<PlanRec> plan;
+	static thread_local std::vector<mpa_dp_task_t> task;
+	static thread_local std::vector<SegRec> seg;
+	static thread_local std::vector<Pair64> key;
+	static thread_local std::vector<SortRange> stack;
+	static thread_local std::vector<uint32_t> hist;
+	static thread_local std::vector<int32_t> prim, flag, list;
+	const size_t n = qs.regs.size();
+	U.clear(), A.clear(), cu.assign(n, 0), ca.assign(n, 0), nu.assign(n, 0), win.resize(n);
+	{
+		AccTimer tm(5);
+		std::unique_ptr<RefineQuery> rq;
+		const ChainParams cp = refine_chain_params(opt);
+		for (size_t i = 0; i < n; ++i) {
+			const size_t w = (size_t)qs.win0 + i;
+			win[i] = plans_window(mi, qs.regs[i], qs.ext_refine[i]);
+			cu[i] = (int64_t)U.size(), ca[i] = (int64_t)A.size();
+			if (rc && !(!rc->on_host.empty() && rc->on_host[w])) {
+				g_acc[13] += 1000000LL;
+				U.insert(U.end(), rc->U + rc->u_first[w], rc->U + rc->u_first[w + 1]);
+				A.insert(A.end(), rc->A + rc->a_first[w], rc->A + rc->a_first[w + 1]);
+			} else {
+				if (!rq) rq.reset(new RefineQuery(qs.seq, qs.qlen, opt.kmer2, rc != nullptr || rh == nullptr));
+				const int32_t extl = (int32_t)(qs.ext_refine[i] >> 32), extr = (int32_t)qs.ext_refine[i];
+				if (rh && !rc) refine_region_pairs(mi, opt, *rq, qs.regs[i], extl, extr, rh->hits.data() + rh->first[w], rh->first[w + 1] - rh->first[w], pa);
+				else refine_region_pairs(mi, opt, *rq, qs.regs[i], extl, extr, nullptr, 0, pa);
+				{ AccTimer tm12(12); chain_anchors(cp, pa, pu); }
+				U.insert(U.end(), pu.begin(), pu.end());
+				size_t na = 0;
+				for (uint64_t x : pu) na += (uint32_t)x;
+				A.insert(A.end(), pa.begin(), pa.begin() + na);
+			}
+			nu[i] = (int64_t)U.size() - cu[i];
+		}
+	}
+	AccTimer tm6(6);
+	const size_t m = A.size();
+	tmp.resize(n), reg.resize(n), plan.resize(n), task.resize(4 * n + m), seg.resize(m + 1), key.resize(n), stack.resize(n / 64 + 4), hist.resize(768), prim.resize(n + 2);
+	cov.resize(n), ext.resize(n), aoff.resize(n), flag.resize(m + 1), list.resize(m + 1);
+	uint8_t tab[ALN_TAB_BYTES];
+	memcpy(tab + ALN_TAB_CODON, tab_codon(), 64), memcpy(tab + ALN_TAB_AA20, tab_aa20(), 256), memcpy(tab + ALN_TAB_MAT, opt.mat, 484);
+	const PlansQuery Q{ (int32_t)n, qs.qid, qs.qlen, win.data(), cu.data(), ca.data(), nu.data(), U.data(), A.data(), (const uint8_t*)qs.seq };
+	const PlansScratch S{ tmp.data(), key.data(), stack.data(), hist.data(), prim.data(), cov.data(), ext.data(), aoff.data(), flag.data(), list.data(), prim.data() + n };
+	const PlansCounts c = plans_core<PlansSerial>(plans_params(mi, opt), Q, PlansGenomeHost{ mi }, tab, S, reg.data(), plan.data(), task.data(), seg.data());
+	plans_apply(qs, c, reg.data(), plan.data(), task.data(), seg.data());
+}
+
+// MPA_PLANS_DUMP=<file> (diagnostics; the tests' view of the step): what the step from the refinement chains to the round-1 tasks left
+// in every query's state, appended in query order, whichever path produced it.  Per query: int32 qid, regions, plans, tasks, gap
+// segments; the regions (64 bytes: as MPA_REGIONS_DUMP, with off where that has 0); the plans (80 bytes: int64 as, ae, vs0, vs1,
+// mid_ve; int32 reg, as1, mid_qe, has_right, t_left, t_left2, t_right, t_right2, first gap, gaps); the tasks (mpa_dp_task_t, 40
+// bytes); the segments (24 bytes: int32 ne0, ne1, ae0, ae1, task, score).  Layout and parser: tests/plansdump.py
+static void plans_dump(const mpa_batch_s *b)
+{
+	const char *fn = getenv("MPA_PLANS_DUMP");
+	if (!fn || !*fn) return;
+	static std::mutex mu;                                // (batches of a stream are planned side by side: one writer at a time)
+	std::lock_guard<std::mutex> g(mu);
+	FILE *fp = fopen(fn, "ab");
+	if (!fp) return;
+	for (const QueryState &qs : b->qs) {
+		int32_t n_seg = 0;
+		for (const AlignPlan &pl : qs.plans) n_seg += (int32_t)pl.gaps.size();
+		const int32_t head[5] = { qs.qid, (int32_t)qs.regs.size(), (int32_t)qs.plans.size(), (int32_t)qs.local1.size(), n_seg };
+		fwrite(head, 4, 5, fp);
+		for (const Region &r : qs.regs) {
+			const int32_t w[10] = { r.cnt, r.id, r.parent, r.n_sub, r.subsc, r.chn_sc, r.chn_sc_ungap, (int32_t)r.vid, r.qs, r.qe };
+			const int64_t v[2] = { r.vs, r.ve };
+			const int32_t t[2] = { r.split, r.off };
+			fwrite(w, 4, 10, fp), fwrite(v, 8, 2, fp), fwrite(t, 4, 2, fp);
+		}
+		int32_t gap0 = 0;
+		for (const AlignPlan &pl : qs.plans) {
+			const int64_t v[5] = { pl.as, pl.ae, pl.vs0, pl.vs1, pl.mid_ve };
+			const int32_t w[10] = { pl.reg, pl.as1, pl.mid_qe, pl.has_right ? 1 : 0, pl.t_left, pl.t_left2, pl.t_right, pl.t_right2, gap0, (int32_t)pl.gaps.size() };
+			fwrite(v, 8, 5, fp), fwrite(w, 4, 10, fp);
+			gap0 += (int32_t)pl.gaps.size();
+		}
+		if (!qs.local1.empty()) fwrite(qs.local1.data(), sizeof(mpa_dp_task_t), qs.local1.size(), fp);
+		for (const AlignPlan &pl : qs.plans)
+			for (const Segment &s : pl.gaps) {
+				// (a shortcut segment carries its one-word cigar alen << 4 on every path; one that does not shows as the impossible score)
+				const bool bare = s.task < 0 && !(s.cigar.size() == 1 && s.cigar[0] == (uint32_t)(s.ae1 - s.ae0) << 4);
+				const int32_t w[6] = { s.ne0, s.ne1, s.ae0, s.ae1, s.task, bare ? INT32_MIN : s.score };
+				fwrite(w, 4, 6, fp);
+			}
+	}
+	fclose(fp);
+}
+
 static void batch_plan_phase(mpa_batch_s *b, mpa_ctx_t *rctx)
 {
 	const double t0 = now_ms();
@@ -1394,6 +1554,7 @@ static void batch_plan_phase(mpa_batch_s *b, mpa_ctx_t *rctx)
 	RefineChains rchains;
 	bool on_device = false, chains_on_device = false;
 	const int mode = gpu_refine_mode();
+	const PlansMode pmode = plans_mode();
 	// (outside the kernels' range -- dev_refine_in_range(): -l above 7, -L above 37 -- the host refines; the device is not asked)
 	if (rctx && mode != 0 && dev_refine_in_range(b->opt.kmer2, b->mi->opt.min_aa_len)) {
 		static thread_local std::vector<RefineWindow> wins;
@@ -1419,9 +1580,24 @@ static void batch_plan_phase(mpa_batch_s *b, mpa_ctx_t *rctx)
 			QueryGroups *perp = per.data();
 			parallel_for(b->n_threads, n_q, [&, perp](int64_t i) { query_groups(b->qs[i].seq, b->qs[i].qlen, b->opt.kmer2, perp[i]); });
 			gather_query_groups(perp, n_q, G);
+			// MPA_GPU_PLANS=1: the call carries on to the plans; what it needs of the windows' regions and of the queries
+			static thread_local std::vector<PlansWindow> pwin;
+			static thread_local std::vector<int64_t> pwin0;
+			PlansRequest preq;
+			const bool want_plans = pmode == PLANS_DEVICE;
+			if (want_plans) {
+				pwin.clear(), pwin0.assign((size_t)n_q + 1, 0);
+				for (int64_t i = 0; i < n_q; ++i) {
+					const QueryState &qs = b->qs[i];
+					pwin0[(size_t)i] = qs.win0;
+					for (size_t r = 0; r < qs.regs.size(); ++r) pwin.push_back(plans_window(b->mi, qs.regs[r], qs.ext_refine[r]));
+				}
+				pwin0[(size_t)n_q] = (int64_t)wins.size();
+				preq = PlansRequest{ plans_params(b->mi, b->opt), pwin.data(), pwin0.data(), b->q.seqs, b->q.q_off, b->opt.mat };
+			}
 			const double t1 = now_ms();
 			const int rc = dev_refine_chains(rctx, const_cast<mpa_idx_s*>(b->mi), b->opt.kmer2, b->mi->opt.min_aa_len, b->opt.max_ava, refine_chain_params(b->opt), (int32_t)n_q, G,
-			                                 (int64_t)wins.size(), wins.data(), rchains);
+			                                 (int64_t)wins.size(), wins.data(), rchains, want_plans ? &preq : nullptr);
 			chains_on_device = rc == MPA_OK;                   // anything else: the scan alone below, or the host
 			if (chains_on_device) timing_note("  refinement on the GPU (scan + pairs + chains)", now_ms() - t1);
 			else if (timing_on()) fprintf(stderr, "[mpa-timing]   device refinement declined (%s)\n", mpa_last_error());
@@ -1446,11 +1622,33 @@ static void batch_plan_phase(mpa_batch_s *b, mpa_ctx_t *rctx)
 	timing_note("  plan: windows + scan (wall)", now_ms() - t_a);
 	const double t_b = now_ms();
 	const RefineChains *rcp = chains_on_device ? &rchains : nullptr;
+	const bool plans_on_device = chains_on_device && rchains.has_plans;
 	parallel_for(b->n_threads, n_q, [&, rhp, rcp](int64_t i) {
-		stage_refine_to_plan(b, b->qs[i], rhp, rcp);
+		QueryState &qs = b->qs[i];
+		if (plans_on_device) {                                 // k_plans has made regions, plans, tasks and segments: nothing to do but take them
+			AccTimer tm(6);
+			const int64_t w0 = qs.win0, a0 = rcp->a_first[(size_t)w0];
+			plans_apply(qs, rcp->PN[i], rcp->PR + w0, rcp->PP + w0, rcp->PT + 4 * w0 + a0, rcp->PS + a0);
+			return;
+		}
+		if (pmode == PLANS_MODEL) { plans_model(b, qs, rhp, rcp); return; }
+		stage_refine_to_plan(b, qs, rhp, rcp);
 		AccTimer tm(7);
-		plan_round1(b, b->qs[i]);
+		plan_round1(b, qs);
 	});
+	if (timing_on()) {
+		if (plans_on_device) {
+			int64_t bytes = n_q * (int64_t)sizeof(PlansCounts);
+			for (int64_t i = 0; i < n_q; ++i) {
+				const PlansCounts &c = rchains.PN[i];
+				bytes += (int64_t)c.n_reg * (int64_t)sizeof(RegionRec) + (int64_t)c.n_plan * (int64_t)sizeof(PlanRec) + (int64_t)c.n_task * (int64_t)sizeof(mpa_dp_task_t) + (int64_t)c.n_seg * (int64_t)sizeof(SegRec);
+			}
+			fprintf(stderr, "[mpa-timing]   plans on the GPU: %lld queries, records downloaded %lld B, refinement anchors downloaded 0 B, anchors and chains not downloaded %lld B\n",
+			        (long long)n_q, (long long)bytes, (long long)((rchains.a_first.back() + rchains.u_first.back()) * 8));
+		}
+		if (pmode == PLANS_MODEL) timing_note("  plans: shared core", now_ms() - t_b);
+	}
+	plans_dump(b);
 	timing_note("  plan: refine..plans (wall)", now_ms() - t_b);
 	timing_note("stage A (seed..plan)", now_ms() - t0);
 	if (timing_on()) for (int k = 0; k < 16; ++k) { timing_note(kAccName[k], (double)g_acc[k].exchange(0) / 1e6); }   // thread CPU ms summed over the workers (13-15: counts)

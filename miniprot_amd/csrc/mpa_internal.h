@@ -12,6 +12,7 @@
 #include "chain_core.h"
 #include "aln_stats_core.h"
 #include "regions_core.h"
+#include "plans_core.h"
 
 namespace mpa {
 
@@ -169,9 +170,30 @@ struct RefineChains {
 	std::vector<int64_t> u_first, a_first;   // [n_win + 1]
 	const uint64_t *U = nullptr, *A = nullptr;   // pinned buffers of the context, valid until its next call
 	std::vector<uint8_t> on_host;            // [n_win] 1 = the device left this window out (2^22 bases or more, or its query has a position >= 2^22): refine it on the host
+	// has_plans (MPA_GPU_PLANS=1): the call ended in k_plans instead of k_chain_pack.  U and A stay null; u_first / a_first still count
+	// what was NOT downloaded.  Query q with first window w0: counts PN[q]; its regions and plans at PR / PP + w0, its gap segments at
+	// PS + a_first[w0], its round-1 tasks at PT + 4 w0 + a_first[w0] (pinned, valid until the context's next call)
+	bool has_plans = false;
+	const RegionRec *PR = nullptr;
+	const PlanRec *PP = nullptr;
+	const mpa_dp_task_t *PT = nullptr;
+	const SegRec *PS = nullptr;
+	const PlansCounts *PN = nullptr;
 };
+// what dev_refine_chains needs on top of the windows to carry on to the plans (plans_core.h): the step's parameters, what every
+// window's region carries over from the first region pass, and the queries themselves
+struct PlansRequest {
+	PlansParams p;
+	const PlansWindow *win;                  // [n_win]
+	const int64_t *win0;                     // [n_query + 1] first window of every query
+	const char *text;                        // the batch's protein text: query q = text[q_off[q] .. q_off[q + 1])
+	const int64_t *q_off;                    // [n_query + 1]
+	const int8_t *mat;                       // [484]
+};
+// plans != nullptr: the call ends in the regions, plans, round-1 tasks and gap segments of every query (out.has_plans) instead of the
+// chains, unless a window is the host's or a pool or pinned block cannot grow -- then the chains come back as without it
 int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_aa_len, int32_t max_ava, const ChainParams &cp, int32_t n_query, const RefineGroupsHost &groups,
-                      int64_t n_win, const RefineWindow *wins, RefineChains &out);
+                      int64_t n_win, const RefineWindow *wins, RefineChains &out, const PlansRequest *plans = nullptr);
 // forward pass of mp_chain (chain.c:181-209) for a batch of problems on the device; see seed_run.hip
 struct ChainIO { uint64_t *a = nullptr; int32_t *f = nullptr, *pred = nullptr; };   // pinned buffers of the context, valid until its next chain call
 int dev_chain_buffers(mpa_ctx_t *ctx, int64_t n, ChainIO &io);

@@ -153,8 +153,9 @@ namespace mpa {
 // position of 2^22 or more -- the sort key window << 44 | position << 22 | query position holds neither); its chains come back empty.
 // A query with more groups than the largest LDS map takes (MPA_REFINE_GMAP_MIN) gets its map in device memory: a fourth launch.
 int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_aa_len, int32_t max_ava, const ChainParams &cp, int32_t n_query, const RefineGroupsHost &G,
-                      int64_t n_win, const RefineWindow *wins, RefineChains &out)
+                      int64_t n_win, const RefineWindow *wins, RefineChains &out, const PlansRequest *plans)
 {
+	out.has_plans = false;
 	out.u_first.assign((size_t)n_win + 1, 0), out.a_first.assign((size_t)n_win + 1, 0);
 	out.U = out.A = nullptr;
 	out.on_host.assign((size_t)n_win, 0);
@@ -185,13 +186,22 @@ int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_a
 		n_long_win += q_cls[q] == 3;
 	}
 	const size_t n_long = gp.long_q.size();
+	// MPA_GPU_PLANS=1: the call carries on to the plans unless a window is the host's -- its region would come from another path
+	if (plans)
+		for (int64_t k = 0; k < n_win; ++k)
+			if (out.on_host[(size_t)k]) {
+				if (timing_on()) fprintf(stderr, "[mpa-timing]   device plans declined (a refinement window is the host's): chains to the host\n");
+				plans = nullptr;
+				break;
+			}
 	HIP_TRY(hipSetDevice(ctx->device));
 	if (dev_upload_index(ctx, mi) != MPA_OK) return MPA_ERR_HIP;
 	SeedBufs &B = ctx->seed;
 	ensure_seed_stream(ctx);
 	hipStream_t s = ctx->seed_stream;
 	const double t0 = now_ms();
-	// ---- one pinned block up: windows | chunks | wg_first | qg_first | gword | gfirst | gcount | qpos
+	// ---- one pinned block up: windows | chunks | wg_first | qg_first | gword | gfirst | gcount | qpos (| with plans: what k_plans
+	// reads of the windows' regions and of the queries: PlansWindow records | first window and first residue of every query | tables | text)
 	static const int n_super = [] { const char *e = getenv("MPA_REFINE_SUPER"); const int v = e ? atoi(e) : REFINE_SUPER; return v < 1 ? 1 : v > 16 ? 16 : v; }();
 	int64_t n_pos = 0, n_chunk = 0, wg_total = 0;
 	for (int64_t k = 0; k < n_win; ++k) {
@@ -204,7 +214,10 @@ int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_a
 	auto al64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
 	const size_t o_win = 0, o_chunk = al64(NW * sizeof(RefineWindowDev)), o_wg = o_chunk + al64((size_t)n_chunk * sizeof(RefineChunk)), o_qg = o_wg + al64((NW + 1) * 8),
 	             o_gw = o_qg + al64((NQ + 1) * 8), o_gf = o_gw + al64(n_group * 4 + 4), o_gc = o_gf + al64(n_group * 4 + 4), o_qp = o_gc + al64(n_group * 4 + 4),
-	             o_gd = o_qp + al64(n_qpos * 4 + 4), o_lq = o_gd + al64(NQ * 8 + 8), up_bytes = o_lq + al64(n_long * 4 + 4);
+	             o_gd = o_qp + al64(n_qpos * 4 + 4), o_lq = o_gd + al64(NQ * 8 + 8), o_pw = o_lq + al64(n_long * 4 + 4);
+	const int64_t text0 = plans ? plans->q_off[0] : 0, text_bytes = plans ? plans->q_off[n_query] - text0 : 0;
+	const size_t o_w0 = o_pw + (plans ? al64(NW * sizeof(PlansWindow)) : 0), o_qo = o_w0 + (plans ? al64((NQ + 1) * 8) : 0), o_tab = o_qo + (plans ? al64((NQ + 1) * 8) : 0),
+	             o_txt = o_tab + (plans ? al64(ALN_TAB_BYTES) : 0), up_bytes = o_txt + (plans ? al64((size_t)text_bytes + 16) : 0);
 	int rc;
 	int64_t cls_end[4] = { 0, 0, 0, 0 };                       // chunks of the windows whose query's map has 1 024 / 2 048 / 4 096 LDS slots, or lives in device memory, end here
 	if ((rc = B.h_meta.ensure(up_bytes + 64)) || (rc = B.r_win.ensure(up_bytes)) || (rc = B.r_hits.ensure((size_t)cap * 16)) || (rc = B.r_count.ensure(16)) ||
@@ -236,6 +249,15 @@ int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_a
 		if (n_qpos) memcpy(hm + o_qp, G.qpos.data(), n_qpos * 4);
 		memcpy(hm + o_gd, gp.desc.data(), NQ * 8);
 		if (n_long) memcpy(hm + o_lq, gp.long_q.data(), n_long * 4);
+		if (plans) {
+			memcpy(hm + o_pw, plans->win, NW * sizeof(PlansWindow));
+			memcpy(hm + o_w0, plans->win0, (NQ + 1) * 8);
+			int64_t *qo = (int64_t*)(hm + o_qo);
+			for (size_t q = 0; q <= NQ; ++q) qo[q] = plans->q_off[q] - text0;
+			char *tab = hm + o_tab;
+			memcpy(tab + ALN_TAB_CODON, tab_codon(), 64), memcpy(tab + ALN_TAB_AA20, tab_aa20(), 256), memcpy(tab + ALN_TAB_MAT, plans->mat, 484);
+			if (text_bytes > 0) memcpy(hm + o_txt, plans->text + text0, (size_t)text_bytes);
+		}
 	}
 	// device tables: per (window, group) hit counts and per-window pair counts, zeroed
 	size_t at = 0;
@@ -334,8 +356,15 @@ int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_a
 	if ((rc = chain_fwd_launch(s, (const uint64_t*)d_a, np, (const int64_t*)d_first, nullptr, (int32_t)n_win, pm, kSerialRun,
 	                           ChainFwdBufs{ (int32_t*)(X + x_f), (int32_t*)(X + x_pred), (int32_t*)(X + x_fm), (uint32_t*)(X + xc.mark), (LongRun*)(X + x_long), (unsigned int*)(X + x_nlong), long_cap }))) return rc;
 	const ChainViewDev view{ d_first, nullptr, nullptr, nullptr, (const int32_t*)(X + x_f), (const int32_t*)(X + x_pred), (const uint64_t*)d_a };
+	PlansTail ptail;
+	if (plans) {
+		const DeviceIndex *d = mi->dev[ctx->device];
+		ptail = PlansTail{ plans->p, n_query, (const PlansWindow*)(dm + o_pw), (const int64_t*)(dm + o_w0), (const int64_t*)(dm + o_qo), (const uint8_t*)(dm + o_txt),
+		                   (const uint8_t*)(dm + o_tab), (const uint8_t*)d->seq, (const int64_t*)d->ctg_off, (const int64_t*)d->ctg_len, false, nullptr, nullptr, nullptr, nullptr, nullptr };
+	}
 	if ((rc = chain_extract_pack(ctx, s, X, xc, view, cp, (int32_t)n_win, B.own, nullptr, "device refinement: a chain extraction needs the host",   // (dense views never do)
-	                             ChainTailOut{ out.a_first, out.u_first, out.A, out.U }, nullptr))) return rc;
+	                             ChainTailOut{ out.a_first, out.u_first, out.A, out.U }, nullptr, nullptr, plans ? &ptail : nullptr))) return rc;
+	if (plans && ptail.done) out.has_plans = true, out.PR = ptail.R, out.PP = ptail.P, out.PT = ptail.T, out.PS = ptail.S, out.PN = ptail.N;
 	timing_note("    refine: pairs + chains (wait)", now_ms() - t1);
 	return MPA_OK;
 }

@@ -6,6 +6,7 @@
 #include "seed_exec.hip"
 #include "sketch_exec.hip"
 #include "region_kernels.hip"
+#include "plan_kernels.hip"
 
 namespace mpa {
 // ---- the chain tail (declared in dev_ctx.h): the forward pass of mp_chain, the extraction and the packed download, as every
@@ -165,8 +166,49 @@ static int regions_tail(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCar
 	return MPA_OK;
 }
 
+// The plans of every query behind the extraction of its refinement windows' chains (MPA_GPU_PLANS=1): k_plans reads the chains where
+// the extraction left them in X, k_plan_pack puts the kept records and the counts into the holder's pinned block.  Everything is
+// laid out by the windows and by the prefix of their extracted anchors (h_offa, on the device at c.offa), which the caller has just
+// downloaded: a query has at most a region and a plan per window, a gap segment per anchor and four tasks per window on top of
+// those.  MPA_ERR_UNSUPPORTED: a pool or the pinned block could not grow -- nothing was launched, the caller packs the chains.
+static int plans_tail(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCarve &c, const ChainViewDev &v, int32_t n_prob, SeedHold &H, int64_t tot_a, PlansTail &pt)
+{
+	SeedBufs &B = ctx->seed;
+	const size_t T = (size_t)tot_a, NW = (size_t)n_prob, NQ = (size_t)pt.n_query;
+	const double t0 = now_ms();
+	Carve cv;
+	const size_t o_tmp = cv(NW * sizeof(RegionRec)), o_key = cv(NW * sizeof(Pair64)), o_stack = cv((NW / 64 + 5 * NQ + 8) * sizeof(SortRange)), o_hist = cv(NQ * 768 * 4);
+	const size_t o_prim = cv(NW * 4), o_cov = cv(NW * 8), o_ext = cv(NW * 8), o_aoff = cv(NW * 8), o_flag = cv(T * 4 + 4), o_list = cv(T * 4 + 4), o_ctl = cv(NQ * 8);
+	const size_t o_reg = cv(NW * sizeof(RegionRec)), o_plan = cv(NW * sizeof(PlanRec)), o_task = cv((4 * NW + T) * sizeof(mpa_dp_task_t)), o_seg = cv(T * sizeof(SegRec) + 8);
+	const size_t o_cnt = cv(NQ * sizeof(PlansCounts));
+	const size_t h_plan = NW * sizeof(RegionRec), h_task = h_plan + NW * sizeof(PlanRec), h_seg = h_task + (4 * NW + T) * sizeof(mpa_dp_task_t), h_cnt = h_seg + T * sizeof(SegRec);
+	if (B.pl.ensure(cv.at + 256) != MPA_OK || H.h_P.ensure(h_cnt + NQ * sizeof(PlansCounts) + 64) != MPA_OK) {
+		tl_alloc_failed = false;
+		if (timing_on()) fprintf(stderr, "[mpa-timing]   device plans declined (%s): chains to the host\n", mpa_last_error());
+		return MPA_ERR_UNSUPPORTED;
+	}
+	char *G = B.pl.as<char>(), *P = H.h_P.as<char>();
+	pt.R = (const RegionRec*)P, pt.P = (const PlanRec*)(P + h_plan), pt.T = (const mpa_dp_task_t*)(P + h_task), pt.S = (const SegRec*)(P + h_seg), pt.N = (const PlansCounts*)(P + h_cnt);
+	PlansArgs pa{};
+	pa.first = v.first, pa.nu = (const int64_t*)(X + c.nu), pa.offa = (const int64_t*)(X + c.offa), pa.u = (const uint64_t*)(X + c.out_u), pa.a = (uint64_t*)(X + c.out_a);
+	pa.win = pt.d_win, pa.win0 = pt.d_win0, pa.q_off = pt.d_qoff, pa.text = pt.d_text, pa.tabs = pt.d_tabs;
+	pa.g = PlansGenome{ pt.d_seq, pt.d_ctg_off, pt.d_ctg_len }, pa.p = pt.p;
+	pa.tmp = (RegionRec*)(G + o_tmp), pa.key = (Pair64*)(G + o_key), pa.stack = (SortRange*)(G + o_stack), pa.hist = (uint32_t*)(G + o_hist), pa.prim = (int32_t*)(G + o_prim);
+	pa.flag = (int32_t*)(G + o_flag), pa.list = (int32_t*)(G + o_list), pa.ctl = (int32_t*)(G + o_ctl), pa.cov = (uint64_t*)(G + o_cov), pa.ext = (uint64_t*)(G + o_ext);
+	pa.aoff = (int64_t*)(G + o_aoff), pa.reg = (RegionRec*)(G + o_reg), pa.plan = (PlanRec*)(G + o_plan), pa.task = (mpa_dp_task_t*)(G + o_task), pa.seg = (SegRec*)(G + o_seg);
+	pa.cnt = (PlansCounts*)(G + o_cnt);
+	hipLaunchKernelGGL(k_plans, dim3((unsigned)((pt.n_query + PLANS_WAVES - 1) / PLANS_WAVES)), dim3(64 * PLANS_WAVES), 0, s, pa, pt.n_query);
+	hipLaunchKernelGGL(k_plan_pack, dim3((unsigned)pt.n_query), dim3(256), 0, s, pa.win0, pa.offa, (const PlansCounts*)pa.cnt, (const RegionRec*)pa.reg, (const PlanRec*)pa.plan,
+	                   (const mpa_dp_task_t*)pa.task, (const SegRec*)pa.seg, (RegionRec*)P, (PlanRec*)(P + h_plan), (mpa_dp_task_t*)(P + h_task), (SegRec*)(P + h_seg), (PlansCounts*)(P + h_cnt));
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(wait_stream(ctx, s));
+	pt.done = true;
+	timing_note("    refine: plans + pack (wait)", now_ms() - t0);
+	return MPA_OK;
+}
+
 int chain_extract_pack(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCarve &c, const ChainViewDev &v, const ChainParams &p, int32_t n_prob, SeedHold &H,
-                       const char *prof_label, const char *status_error, ChainTailOut out, const int32_t **h_status_out, RegionsTail *regions)
+                       const char *prof_label, const char *status_error, ChainTailOut out, const int32_t **h_status_out, RegionsTail *regions, PlansTail *plans)
 {
 	SeedBufs &B = ctx->seed;
 	const size_t NP = (size_t)n_prob;
@@ -189,6 +231,17 @@ int chain_extract_pack(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCarv
 	if (regions) {                                            // the regions instead of the chains; declined: the chains, as without it
 		regions->done = false;
 		rc = regions_tail(ctx, s, X, c, v, n_prob, H, tot_u, *regions);
+		if (rc == MPA_OK) {
+			out.a_first.assign(h_offa, h_offa + n_prob + 1), out.u_first.assign(h_offu, h_offu + n_prob + 1);
+			out.A = out.U = nullptr;
+			if (h_status_out) *h_status_out = h_status;
+			return MPA_OK;
+		}
+		if (rc != MPA_ERR_UNSUPPORTED) return rc;
+	}
+	if (plans) {                                              // the plans instead of the chains; declined: the chains, as without it
+		plans->done = false;
+		rc = plans_tail(ctx, s, X, c, v, n_prob, H, tot_a, *plans);
 		if (rc == MPA_OK) {
 			out.a_first.assign(h_offa, h_offa + n_prob + 1), out.u_first.assign(h_offu, h_offu + n_prob + 1);
 			out.A = out.U = nullptr;
