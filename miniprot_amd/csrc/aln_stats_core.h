@@ -43,6 +43,7 @@ struct AlnFeat {                         // Feat (host_core.h), field by field
 struct StatsSerial : CoopSerial {        // a team of one: the host
 	static MPA_HD int32_t sum(int32_t v) { return v; }                    // over the team, the same on every lane
 	static MPA_HD uint32_t bcast(uint32_t v, int) { return v; }           // lane k's value (k the same on every lane)
+	static MPA_HD int32_t scan32(int32_t v, int32_t *total) { *total = v; return 0; }   // sum of v over the lanes below this one; the team's total (aln_cs_core.h)
 };
 
 // codon at strand-local position j -> aa20 code, 21 for a codon with an ambiguous base (ns_tab_codon through the nt4 codes)

@@ -65,6 +65,9 @@ struct Region {
 	int32_t dp_score = 0, dp_max = 0, dp_max2 = 0, blen = 0, n_fs = 0, n_stop = 0, dist_stop = 0, dist_start = 0, n_iden = 0, n_plus = 0;
 	std::vector<uint32_t> cigar;
 	std::vector<Feat> feat;
+	// the body of its cs:Z: string when take_round3() built it (MPA_GPU_CS; src 1: the shared core on the host, 2: the device)
+	std::string cs;
+	int8_t cs_src = 0;                // 0: none carried, the formatter builds it
 };
 
 int32_t chain_score_ungapped(const uint64_t *a, int32_t n, int32_t kmer);                  // hit.c:18-30

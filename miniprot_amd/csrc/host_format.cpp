@@ -30,16 +30,16 @@ static inline uint8_t codon_aa3(const uint8_t *nt)
 }
 
 // the cs:Z: difference string (format.c:102-187)
-static void put_cs(std::string &s, const mpa_idx_s *mi, const char *aa, const mpa_hit_t &h, const uint32_t *cig)
+// (the body alone: what follows "cs:Z:" -- also what MPA_CS_DUMP records for a region that carries none, host_map.cpp)
+void put_cs_body(std::string &s, const mpa_idx_s *mi, const char *aa, int32_t vid, int64_t vs, int64_t ve, const uint32_t *cig, int32_t n_cigar)
 {
 	static const char lc[] = "acgtn";
 	const uint8_t *aa20 = tab_aa20();
-	std::vector<uint8_t> ntv((size_t)std::max<int64_t>(h.ve - h.vs, 1));
-	fetch_nt(mi, (int32_t)h.vid, h.vs, h.ve, ntv.data());
+	std::vector<uint8_t> ntv((size_t)std::max<int64_t>(ve - vs, 1));
+	fetch_nt(mi, vid, vs, ve, ntv.data());
 	const uint8_t *nt = ntv.data();
 	int32_t nl = 0, al = 0;
-	s += "cs:Z:";
-	for (int32_t k = 0; k < h.n_cigar; ++k) {
+	for (int32_t k = 0; k < n_cigar; ++k) {
 		const int32_t op = cig[k] & 0xf, len = (int32_t)(cig[k] >> 4);
 		if (op == 0) {
 			int32_t run = 0;
@@ -87,8 +87,15 @@ static void put_cs(std::string &s, const mpa_idx_s *mi, const char *aa, const mp
 	}
 }
 
+static void put_cs(std::string &s, const mpa_idx_s *mi, const char *aa, const mpa_hit_t &h, const uint32_t *cig)
+{
+	s += "cs:Z:";
+	put_cs_body(s, mi, aa, (int32_t)h.vid, h.vs, h.ve, cig, h.n_cigar);
+}
+
+// carried: the cs body that came with the hit (MPA_GPU_CS), pasted in; null: put_cs() builds it.  n_cs[0] / n_cs[1] count the two
 static void put_paf(std::string &s, const mpa_idx_s *mi, const mpa_mapopt_t &opt, const char *name, const char *seq, int32_t qlen,
-                    const mpa_hit_t *h, const uint32_t *cig_pool)
+                    const mpa_hit_t *h, const uint32_t *cig_pool, const char *carried = nullptr, int32_t carried_len = 0, int64_t *n_cs = nullptr)
 {
 	static const char ops[] = "MIDNSHP=XBFGUVE";
 	if (opt.flag & (MPA_MF_GFF | MPA_MF_GTF)) s += "##PAF\t";
@@ -107,7 +114,12 @@ static void put_paf(std::string &s, const mpa_idx_s *mi, const mpa_mapopt_t &opt
 		s += "\tst:i:", put_int(s, h->n_stop), s += "\tda:i:", put_int(s, h->dist_start), s += "\tdo:i:", put_int(s, h->dist_stop);
 		s += "\tcg:Z:";
 		for (int32_t k = 0; k < h->n_cigar; ++k) put_int(s, cig[k] >> 4), s.push_back(ops[cig[k] & 0xf]);
-		if (!(opt.flag & MPA_MF_NO_CS)) s.push_back('\t'), put_cs(s, mi, seq + h->qs, *h, cig);
+		if (!(opt.flag & MPA_MF_NO_CS)) {
+			s.push_back('\t');
+			if (carried) s += "cs:Z:", s.append(carried, (size_t)carried_len);
+			else put_cs(s, mi, seq + h->qs, *h, cig);
+			if (n_cs) ++n_cs[carried ? 0 : 1];
+		}
 	} else {
 		put_int(s, h->chn_sc), s.push_back('\t'), put_int(s, h->chn_sc_ungap), s.push_back('\t'), put_int(s, h->cnt);
 		if (!(opt.flag & MPA_MF_NO_CS)) s.push_back('\t');     // mp_write_cs() returns at once when there is no alignment
@@ -312,6 +324,7 @@ static int64_t format_batch(const mpa_idx_t *mi, const mpa_mapopt_t *opt, const 
 	}
 	const int64_t id0 = id_io ? *id_io : 0;
 	std::vector<std::string> part((size_t)n_seq);
+	std::atomic<int64_t> cs_carried(0), cs_built(0);         // cs strings pasted from the result / built here
 	auto one = [&](int32_t i) {
 		std::string &s = part[i];
 		const char *seq = q->seqs + q->q_off[i];
@@ -320,21 +333,28 @@ static int64_t format_batch(const mpa_idx_t *mi, const mpa_mapopt_t *opt, const 
 		const mpa_hit_t *h = hits + off[i];
 		int32_t best_sc = -1;
 		int64_t id = id0 + id_base[i];
+		int64_t n_cs[2] = { 0, 0 };
+		auto paf = [&](int64_t j) {                              // the hit's PAF line, with the cs body it carries when it carries one
+			const mpa_result_s::CsRef *c = r->cs.empty() ? nullptr : &r->cs[(size_t)(off[i] + j)];
+			const bool have = c && c->present;
+			put_paf(s, mi, *opt, names[i], seq, qlen, &h[j], cig, have ? r->cs_text.data() + c->off : nullptr, have ? c->len : 0, n_cs);
+		};
 		if (n_reg > 0) best_sc = h[0].has_aln ? h[0].dp_max : h[0].chn_sc;
 		for (int64_t j = 0; j < n_reg && j < opt->out_n; ++j) {
 			if (!passes(i, j, best_sc)) continue;
 			++id;
 			const bool residues = (opt->flag & (MPA_MF_SHOW_RESIDUE | MPA_MF_SHOW_TRANS)) != 0;
 			if (opt->flag & MPA_MF_GTF) {
-				if (residues) put_paf(s, mi, *opt, names[i], seq, qlen, &h[j], cig), put_residues(s, mi, *opt, seq, h[j], cig + h[j].cigar_off);
+				if (residues) paf(j), put_residues(s, mi, *opt, seq, h[j], cig + h[j].cigar_off);
 				put_gtf(s, mi, *opt, qlen, h[j], feats + h[j].feat_off, id);
 			} else {
-				if (!(opt->flag & MPA_MF_NO_PAF)) put_paf(s, mi, *opt, names[i], seq, qlen, &h[j], cig);
+				if (!(opt->flag & MPA_MF_NO_PAF)) paf(j);
 				if (residues) put_residues(s, mi, *opt, seq, h[j], cig + h[j].cigar_off);
 				if (opt->flag & MPA_MF_GFF) put_gff(s, mi, *opt, names[i], qlen, h[j], feats + h[j].feat_off, id, (int32_t)j + 1);
 			}
 		}
 		if (id_base[i + 1] == id_base[i] && (opt->flag & MPA_MF_SHOW_UNMAP)) put_paf(s, mi, *opt, names[i], seq, qlen, nullptr, cig);
+		cs_carried += n_cs[0], cs_built += n_cs[1];
 	};
 	{
 		unsigned hw = std::thread::hardware_concurrency();
@@ -352,7 +372,8 @@ static int64_t format_batch(const mpa_idx_t *mi, const mpa_mapopt_t *opt, const 
 	std::string s;
 	s.reserve(total);
 	for (const std::string &x : part) s += x;
-	timing_note("format output", now_ms() - t0);
+	// (the counts behind the time: tools/timing_agg.py still sees one label)
+	if (timing_on()) fprintf(stderr, "[mpa-timing] %-28s %9.3f ms  cs carried %lld, built %lld\n", "format output", now_ms() - t0, (long long)cs_carried.load(), (long long)cs_built.load());
 	char *buf = (char*)malloc(s.size() + 1);
 	memcpy(buf, s.data(), s.size());
 	buf[s.size()] = 0;

@@ -71,14 +71,6 @@ struct QueryState {
 
 using namespace mpa;
 
-struct mpa_result_s {
-	int32_t n_seq = 0;
-	std::vector<mpa_hit_t> hits;
-	std::vector<int64_t> hit_off;
-	std::vector<uint32_t> cigars;
-	std::vector<mpa_feat_t> feats;
-};
-
 struct mpa_batch_s {
 	const mpa_idx_s *mi = nullptr;
 	mpa_mapopt_t opt;
@@ -1024,12 +1016,152 @@ static int stats_on_device(mpa_batch_s *b, mpa_ctx_t *ctx, bool *ran)
 	return MPA_OK;
 }
 
-// MPA_OK, or the error of a device statistics call that failed (a call that merely declines leaves the batch to the host walk)
+// ---- (b') MPA_GPU_CS: the cs:Z: body of every aligned region, carried in the region to the result ----
+// 0 / unset = the formatter builds it (put_cs_body, host_format.cpp); 1 = on the device behind the last DP round (k_aln_cs), on the
+// batch's DP context; model = the host instance of the device's code with a team of one (aln_cs_core.h: the CPU tests)
+static StatsMode aln_cs_mode()
+{
+	const char *e = getenv("MPA_GPU_CS");               // (read per call: the tests flip it)
+	if (!e || !*e) return STATS_HOST;
+	if (!strcmp(e, "model")) return STATS_MODEL;
+	return atoi(e) != 0 ? STATS_DEVICE : STATS_HOST;
+}
+
+// does the formatter print a cs string for these options at all?  (format_batch: the PAF line is printed unless MPA_MF_NO_PAF is set,
+// and with --gtf only next to the residue rows of --aln / --trans)
+static bool cs_printed(const mpa_mapopt_t &opt)
+{
+	if (opt.flag & (MPA_MF_NO_CS | MPA_MF_NO_ALIGN)) return false;
+	if (opt.flag & MPA_MF_GTF) return (opt.flag & (MPA_MF_SHOW_RESIDUE | MPA_MF_SHOW_TRANS)) != 0;
+	return !(opt.flag & MPA_MF_NO_PAF);
+}
+
+static void cs_apply(Region &r, const AlnCsOut &o, const char *body, int64_t bound, int8_t src)
+{
+	assert(!o.bad && o.len <= bound);                    // (the walk ends at (ve - vs, qe - qs), inside its slot)
+	(void)bound;
+	r.cs.assign(body, (size_t)o.len), r.cs_src = src;
+}
+
+// through the shared core on the host: a team of one per region
+static void cs_model(mpa_batch_s *b)
+{
+	uint8_t tab[ALN_TAB_BYTES];
+	memcpy(tab + ALN_TAB_CODON, tab_codon(), 64), memcpy(tab + ALN_TAB_AA20, tab_aa20(), 256), memcpy(tab + ALN_TAB_MAT, b->opt.mat, 484);
+	parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
+		QueryState &qs = b->qs[qi];
+		std::vector<char> slot;
+		for (AlignPlan &pl : qs.plans) {
+			Region &r = qs.regs[pl.reg];
+			const Contig &c = b->mi->ctg[r.vid >> 1];
+			const StatsGenomeHost g{ b->mi->seq.data(), c.off, c.len, (int)(r.vid & 1) };
+			const int64_t bound = aln_cs_bound(r.cigar.data(), (int32_t)r.cigar.size());
+			slot.resize((size_t)bound + 1);
+			const AlnCsOut o = aln_cs_core<StatsSerial>(stats_job(qs, pl, r, 0, 0, 0), tab, (const uint8_t*)qs.seq, r.cigar.data(), g, slot.data());
+			cs_apply(r, o, slot.data(), bound, 1);
+		}
+	});
+}
+
+// The cs strings on the device, and with `stats` the statistics in the same call (one upload, two launches, one wait).  MPA_OK: done
+// (*ran: there was something to do); MPA_ERR_UNSUPPORTED: the device declined and nothing was changed; anything else is an error
+static int cs_on_device(mpa_batch_s *b, mpa_ctx_t *ctx, bool stats, bool *ran)
+{
+	const size_t nq = b->qs.size();
+	std::vector<int64_t> job0(nq + 1, 0), cig0(nq + 1, 0), feat0(nq + 1, 0), slot0(nq + 1, 0);
+	parallel_for(b->n_threads, (int64_t)nq, [&](int64_t qi) {                // (the bound walks every CIGAR: per query, then the prefix)
+		const QueryState &qs = b->qs[qi];
+		int64_t nc = 0, nf = 0, nb = 0;
+		for (const AlignPlan &pl : qs.plans) {
+			const Region &r = qs.regs[pl.reg];
+			nc += (int64_t)r.cigar.size(), nf += (int64_t)r.n_exon + 1, nb += aln_cs_bound(r.cigar.data(), (int32_t)r.cigar.size());
+		}
+		job0[qi + 1] = (int64_t)qs.plans.size(), cig0[qi + 1] = nc, feat0[qi + 1] = nf, slot0[qi + 1] = nb;
+	});
+	for (size_t qi = 0; qi < nq; ++qi) job0[qi + 1] += job0[qi], cig0[qi + 1] += cig0[qi], feat0[qi + 1] += feat0[qi], slot0[qi + 1] += slot0[qi];
+	const int64_t n_jobs = job0[nq], n_cigar = cig0[nq], n_feat = stats ? feat0[nq] : -1, slot_bytes = slot0[nq];
+	*ran = n_jobs > 0;
+	if (n_jobs == 0) return MPA_OK;
+	const int64_t t0 = b->q.q_off[0], text_bytes = b->q.q_off[b->q.n_seq] - t0;
+	AlnStatsIO io;
+	AlnCsIO cs;
+	int rc = dev_aln_cs_stage(ctx, n_jobs, n_cigar, text_bytes, n_feat, slot_bytes, io, cs);
+	if (rc != MPA_OK) return rc;
+	if (text_bytes > 0) memcpy(io.text, b->q.seqs + t0, (size_t)text_bytes);
+	cs.slot_off[n_jobs] = slot_bytes;
+	parallel_for(b->n_threads, (int64_t)nq, [&](int64_t qi) {
+		const QueryState &qs = b->qs[qi];
+		int64_t j = job0[qi], c = cig0[qi], f = feat0[qi], s = slot0[qi];
+		for (const AlignPlan &pl : qs.plans) {
+			const Region &r = qs.regs[pl.reg];
+			cs.slot_off[j] = s;
+			io.jobs[j++] = stats_job(qs, pl, r, (qs.seq - b->q.seqs) - t0, c, f);
+			if (!r.cigar.empty()) memcpy(io.cigar + c, r.cigar.data(), r.cigar.size() * 4);
+			c += (int64_t)r.cigar.size(), f += (int64_t)r.n_exon + 1, s += aln_cs_bound(r.cigar.data(), (int32_t)r.cigar.size());
+		}
+	});
+	rc = dev_aln_cs(ctx, const_cast<mpa_idx_s*>(b->mi), stats_params(b->opt), b->opt.mat, n_jobs, n_cigar, text_bytes, n_feat, slot_bytes, io, cs);
+	if (rc != MPA_OK) return rc;
+	if (timing_on()) {                                   // what came down against what it held (the bounded slots: DESIGN.md section 4.8)
+		int64_t used = 0;
+		for (int64_t j = 0; j < n_jobs; ++j) used += cs.out[j].len;
+		fprintf(stderr, "[mpa-timing]   cs slots: %lld alignments, %lld bytes down, %lld bytes of strings\n", (long long)n_jobs, (long long)slot_bytes, (long long)used);
+	}
+	parallel_for(b->n_threads, (int64_t)nq, [&](int64_t qi) {
+		QueryState &qs = b->qs[qi];
+		int64_t j = job0[qi];
+		for (AlignPlan &pl : qs.plans) {
+			Region &r = qs.regs[pl.reg];
+			if (stats) stats_apply(r, io.out[j], io.feat + io.jobs[j].feat_off);
+			cs_apply(r, cs.out[j], cs.body + cs.slot_off[j], cs.slot_off[j + 1] - cs.slot_off[j], 2);
+			++j;
+		}
+	});
+	return MPA_OK;
+}
+
+// MPA_CS_DUMP=<file> (diagnostics; the tests' view of the step): behind stage_finish, one record per aligned region in query and region
+// order, whichever path produced the body (a region that carries none gets the formatter's, put_cs_body).  Per record: int32 query
+// number, vid; int64 vs, ve; int32 qs, qe, source (0 host, 1 shared core, 2 device), length; the body.  Layout and parser: tests/csdump.py
+static void cs_dump(const mpa_batch_s *b)
+{
+	const char *fn = getenv("MPA_CS_DUMP");
+	if (!fn || !*fn) return;
+	static std::mutex mu;                                // (batches of a stream finish side by side: one writer at a time)
+	std::lock_guard<std::mutex> g(mu);
+	FILE *fp = fopen(fn, "ab");
+	if (!fp) return;
+	std::string body;
+	for (const QueryState &qs : b->qs)
+		for (const Region &r : qs.regs) {
+			if (!r.aligned) continue;
+			const std::string *s = &r.cs;
+			if (!r.cs_src) body.clear(), put_cs_body(body, b->mi, qs.seq + r.qs, (int32_t)r.vid, r.vs, r.ve, r.cigar.data(), (int32_t)r.cigar.size()), s = &body;
+			const int32_t a[2] = { qs.qid, (int32_t)r.vid };
+			const int64_t v[2] = { r.vs, r.ve };
+			const int32_t w[4] = { r.qs, r.qe, r.cs_src, (int32_t)s->size() };
+			fwrite(a, 4, 2, fp), fwrite(v, 8, 2, fp), fwrite(w, 4, 4, fp);
+			if (!s->empty()) fwrite(s->data(), 1, s->size(), fp);
+		}
+	fclose(fp);
+}
+
+static int take_round3_steps(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint32_t *pool);
+// MPA_OK, or the error of a device call that failed (a call that merely declines leaves the batch to the host walk)
 static int take_round3(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint32_t *pool)
+{
+	const int rc = take_round3_steps(b, rst, pool);
+	if (rc == MPA_OK) cs_dump(b);
+	return rc;
+}
+
+static int take_round3_steps(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint32_t *pool)
 {
 	StatsMode mode = aln_stats_mode();
 	if (mode == STATS_DEVICE && !b->dp_ctx) mode = STATS_HOST;            // (the stage machine without a context: mpa_batch_begin)
-	if (mode == STATS_HOST) {                                             // the three steps in one pass over the queries
+	StatsMode cs = cs_printed(b->opt) ? aln_cs_mode() : STATS_HOST;
+	if (cs == STATS_DEVICE && !b->dp_ctx) cs = STATS_HOST;
+	if (mode == STATS_HOST && cs == STATS_HOST) {                         // the three steps in one pass over the queries
 		parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
 			QueryState &qs = b->qs[qi];
 			for (AlignPlan &pl : qs.plans) {
@@ -1050,20 +1182,46 @@ static int take_round3(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint32_t *
 		}
 	});
 	const double t0 = now_ms();                                            // (b)
+	auto stats_host_all = [&]() {
+		parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
+			QueryState &qs = b->qs[qi];
+			for (AlignPlan &pl : qs.plans) stats_on_host(b, qs, pl, qs.regs[pl.reg]);
+		});
+	};
+	bool cs_done = false;
 	if (mode == STATS_MODEL) {
 		stats_model(b);
 		timing_note("alignment statistics: shared core", now_ms() - t0);
+	} else if (mode == STATS_HOST) {
+		stats_host_all();
 	} else {
+		// with MPA_GPU_CS=1 as well, the two kernels share the upload of jobs, CIGAR words and text, and the wait
+		const bool both = cs == STATS_DEVICE;
 		bool ran = false;
-		const int rc = stats_on_device(b, b->dp_ctx, &ran);
+		const int rc = both ? cs_on_device(b, b->dp_ctx, true, &ran) : stats_on_device(b, b->dp_ctx, &ran);
 		if (rc != MPA_OK && rc != MPA_ERR_UNSUPPORTED) return rc;
-		if (rc == MPA_OK && ran) timing_note("alignment statistics on the GPU", now_ms() - t0);
+		if (rc == MPA_OK && ran) {
+			timing_note("alignment statistics on the GPU", now_ms() - t0);
+			if (both) timing_note("cs strings on the GPU", now_ms() - t0);   // (one call: the same span)
+		}
 		if (rc == MPA_ERR_UNSUPPORTED) {
 			if (timing_on()) fprintf(stderr, "[mpa-timing]   device alignment statistics declined (%s): statistics on the host\n", mpa_last_error());
-			parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
-				QueryState &qs = b->qs[qi];
-				for (AlignPlan &pl : qs.plans) stats_on_host(b, qs, pl, qs.regs[pl.reg]);
-			});
+			if (both && timing_on()) fprintf(stderr, "[mpa-timing]   device cs strings declined with them: the formatter builds them\n");
+			stats_host_all();
+		}
+		cs_done = both;
+	}
+	if (cs != STATS_HOST && !cs_done) {                                    // (b')
+		const double t1 = now_ms();
+		if (cs == STATS_MODEL) {
+			cs_model(b);
+			timing_note("cs strings: shared core", now_ms() - t1);
+		} else {
+			bool ran = false;
+			const int rc = cs_on_device(b, b->dp_ctx, false, &ran);
+			if (rc != MPA_OK && rc != MPA_ERR_UNSUPPORTED) return rc;
+			if (rc == MPA_OK && ran) timing_note("cs strings on the GPU", now_ms() - t1);
+			if (rc == MPA_ERR_UNSUPPORTED && timing_on()) fprintf(stderr, "[mpa-timing]   device cs strings declined (%s): the formatter builds them\n", mpa_last_error());
 		}
 	}
 	parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) { stage_finish(b, b->qs[qi]); });   // (c)
@@ -2073,9 +2231,15 @@ static mpa_result_t *mpa_batch_finish_impl(mpa_batch_t *b)
 				memcpy(o.donor, f.donor, 2), memcpy(o.acceptor, f.acceptor, 2);
 				res->feats.push_back(o);
 			}
+			if (r.cs_src) {                                    // the cs body that came with the region (MPA_GPU_CS): one entry per hit from here on
+				res->cs.resize(res->hits.size(), mpa_result_s::CsRef{ 0, 0, 0 });
+				res->cs.push_back(mpa_result_s::CsRef{ (int64_t)res->cs_text.size(), (int32_t)r.cs.size(), 1 });
+				res->cs_text += r.cs;
+			}
 			res->hits.push_back(h);
 		}
 	}
+	if (!res->cs.empty()) res->cs.resize(res->hits.size(), mpa_result_s::CsRef{ 0, 0, 0 });
 	res->hit_off[b->qs.size()] = (int64_t)res->hits.size();
 	parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t i) { b->qs[i] = QueryState(); });   // free per-query state in parallel
 	delete b;

@@ -11,6 +11,7 @@
 #include "../../include/mpamd.h"
 #include "chain_core.h"
 #include "aln_stats_core.h"
+#include "aln_cs_core.h"
 #include "regions_core.h"
 #include "plans_core.h"
 
@@ -105,11 +106,26 @@ struct mpa_idx_s {
 	size_t map_len = 0;
 };
 
+// the result of a batch (mpa_batch_finish; read through the mpa_result_* accessors of the C ABI, and by the formatter directly)
+struct mpa_result_s {
+	int32_t n_seq = 0;
+	std::vector<mpa_hit_t> hits;
+	std::vector<int64_t> hit_off;
+	std::vector<uint32_t> cigars;
+	std::vector<mpa_feat_t> feats;
+	// cs:Z: bodies that came with the hits (MPA_GPU_CS): one entry per hit when any hit carries one, none at all otherwise
+	struct CsRef { int64_t off; int32_t len, present; };
+	std::vector<CsRef> cs;
+	std::string cs_text;
+};
+
 namespace mpa {
 
 inline uint8_t nt_at(const mpa_idx_s *mi, int64_t p) { return mi->seq[p >> 1] >> ((p & 1) * 4) & 0xf; }
 // strand-local window fetch; same contract as mp_ntseq_get_by_v (ntseq.c:108-114)
 int64_t fetch_nt(const mpa_idx_s *mi, int32_t vid, int64_t st, int64_t en, uint8_t *out);
+// the body of a cs:Z: string as the formatter builds it (host_format.cpp: mp_write_cs, format.c:102-187); aa = the query at qs
+void put_cs_body(std::string &s, const mpa_idx_s *mi, const char *aa, int32_t vid, int64_t vs, int64_t ve, const uint32_t *cig, int32_t n_cigar);
 int32_t block2vid(const mpa_idx_s *mi, uint32_t blk);        // mp_idx_block2pos (index.c:28-44)
 int64_t idx_read_spsc(mpa_idx_s *mi, const char *fn, int32_t max_sc);   // mp_ntseq_read_spsc (ntseq.c:234-296)
 
@@ -236,5 +252,13 @@ struct AlnStatsIO { AlnStatsJob *jobs = nullptr; uint32_t *cigar = nullptr; char
 int dev_aln_stats_stage(mpa_ctx_t *ctx, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat, AlnStatsIO &io);
 int dev_aln_stats(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const int8_t *mat, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat,
                   AlnStatsIO &io);
+// ---- cs:Z: difference strings on the device (MPA_GPU_CS=1; driver: stats_run.hip; code: aln_cs_core.h) ----
+// The same two steps with a slot per alignment: slot_bytes = the sum of aln_cs_bound() over the staged alignments, slot_off[n_jobs + 1]
+// is filled next to the jobs, and body + slot_off[j] holds out[j].len bytes afterwards (pinned, valid until the context's next call).
+// n_feat >= 0: the statistics run in the same call (io.out / io.feat as from dev_aln_stats); n_feat < 0: the cs strings alone.
+struct AlnCsIO { int64_t *slot_off = nullptr; const AlnCsOut *out = nullptr; const char *body = nullptr; };
+int dev_aln_cs_stage(mpa_ctx_t *ctx, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat, int64_t slot_bytes, AlnStatsIO &io, AlnCsIO &cs);
+int dev_aln_cs(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const int8_t *mat, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat,
+               int64_t slot_bytes, AlnStatsIO &io, AlnCsIO &cs);
 
 } // namespace mpa
