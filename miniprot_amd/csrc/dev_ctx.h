@@ -161,6 +161,9 @@ struct mpa_ctx_s {
 	// ---- cs strings (stats_run.hip, MPA_GPU_CS=1): what goes up shares st_in / h_stats_up; grow-only, allocated by the first call
 	DevBuf cs_out;                            // lengths | slots
 	HostPinned h_cs_down;
+	// ---- residue rows (stats_run.hip, MPA_GPU_ROWS=1): the same again
+	DevBuf rows_out;                          // records | slots
+	HostPinned h_rows_down;
 };
 
 namespace mpa {
@@ -176,7 +179,7 @@ template<typename F> static void ctx_each_devbuf(mpa_ctx_s *ctx, F f)
 	                  &B.c_a, &B.c_f, &B.c_pred, &B.c_mark, &B.c_flag, &B.c_first, &B.c_long,
 	                  &B.pf_qfirst2, &B.val64[0], &B.val64[1],
 	                  &B.s_meta, &B.s_cur, &B.s_cur2, &B.s_kept, &B.s_base, &B.s_out, &B.s_flag, &B.dkey, &B.x_all, &B.rx_all, &B.rx_keys,
-	                  &ctx->lite, &ctx->ckpt, &ctx->wlist, &B.k_in, &B.k_cnt, &B.k_bkt, &B.k_q, &B.r_gmap, &ctx->st_in, &ctx->st_out, &B.rg, &B.pl, &ctx->cs_out };
+	                  &ctx->lite, &ctx->ckpt, &ctx->wlist, &B.k_in, &B.k_cnt, &B.k_bkt, &B.k_q, &B.r_gmap, &ctx->st_in, &ctx->st_out, &B.rg, &B.pl, &ctx->cs_out, &ctx->rows_out };
 	int k = 0;
 	for (DevBuf *b : all) f(*b, k++);
 }

@@ -68,6 +68,11 @@ struct Region {
 	// the body of its cs:Z: string when take_round3() built it (MPA_GPU_CS; src 1: the shared core on the host, 2: the device)
 	std::string cs;
 	int8_t cs_src = 0;                // 0: none carried, the formatter builds it
+	// its --aln / --trans residue rows the same way (MPA_GPU_ROWS): four rows of rows_w bytes (none without --aln), then rows_sta STA
+	// bytes (none without --trans)
+	std::string rows;
+	int32_t rows_w = 0, rows_sta = 0;
+	int8_t rows_src = 0;              // 0: none carried, put_residues() walks
 };
 
 int32_t chain_score_ungapped(const uint64_t *a, int32_t n, int32_t kmer);                  // hit.c:18-30

@@ -130,9 +130,20 @@ static void put_paf(std::string &s, const mpa_idx_s *mi, const mpa_mapopt_t &opt
 // --aln / --trans (format.c:189-331): the alignment as four parallel rows -- target nucleotides (##ATN), their
 // translation (##ATA), the match line (##AAS) and the query residues (##AQA) -- and the translated target alone (##STA).
 // One text column per nucleotide; introns in lower case, abridged to max_intron_flank bases on either side when long.
-static void put_residues(std::string &s, const mpa_idx_s *mi, const mpa_mapopt_t &opt, const char *aa, const mpa_hit_t &h, const uint32_t *cig)
+// carried: the rows that came with the hit (MPA_GPU_ROWS; text = the four rows of carried->width bytes, then the STA bytes), pasted in
+// behind the five prefixes; null: the walk below builds them.  n_rows[0] / n_rows[1] count the two
+static void put_residues(std::string &s, const mpa_idx_s *mi, const mpa_mapopt_t &opt, const char *aa, const mpa_hit_t &h, const uint32_t *cig,
+                         const mpa_result_s::RowsRef *carried = nullptr, const char *text = nullptr, int64_t *n_rows = nullptr)
 {
 	if (!h.has_aln) return;
+	if (n_rows) ++n_rows[carried ? 0 : 1];
+	if (carried) {
+		static const char *const prefix[4] = { "##ATN\t", "##ATA\t", "##AAS\t", "##AQA\t" };
+		if (opt.flag & MPA_MF_SHOW_RESIDUE)
+			for (int k = 0; k < 4; ++k) s += prefix[k], s.append(text + (int64_t)k * carried->width, (size_t)carried->width), s += '\n';
+		if (opt.flag & MPA_MF_SHOW_TRANS) s += "##STA\t", s.append(text + 4 * (int64_t)carried->width, (size_t)carried->n_sta), s += '\n';
+		return;
+	}
 	static const char UC[] = "ACGTN", LC[] = "acgtn";
 	const char *i2c = "ARNDCQEGHILKMFPSTWYV*X";
 	const uint8_t *aa20 = tab_aa20();
@@ -325,6 +336,7 @@ static int64_t format_batch(const mpa_idx_t *mi, const mpa_mapopt_t *opt, const 
 	const int64_t id0 = id_io ? *id_io : 0;
 	std::vector<std::string> part((size_t)n_seq);
 	std::atomic<int64_t> cs_carried(0), cs_built(0);         // cs strings pasted from the result / built here
+	std::atomic<int64_t> rows_carried(0), rows_built(0);     // residue row sets, the same
 	auto one = [&](int32_t i) {
 		std::string &s = part[i];
 		const char *seq = q->seqs + q->q_off[i];
@@ -333,7 +345,12 @@ static int64_t format_batch(const mpa_idx_t *mi, const mpa_mapopt_t *opt, const 
 		const mpa_hit_t *h = hits + off[i];
 		int32_t best_sc = -1;
 		int64_t id = id0 + id_base[i];
-		int64_t n_cs[2] = { 0, 0 };
+		int64_t n_cs[2] = { 0, 0 }, n_rows[2] = { 0, 0 };
+		auto residue_rows = [&](int64_t j) {                     // the hit's residue rows, pasted in when it carries them
+			const mpa_result_s::RowsRef *c = r->rows.empty() ? nullptr : &r->rows[(size_t)(off[i] + j)];
+			const bool have = c && c->present;
+			put_residues(s, mi, *opt, seq, h[j], cig + h[j].cigar_off, have ? c : nullptr, have ? r->rows_text.data() + c->off : nullptr, n_rows);
+		};
 		auto paf = [&](int64_t j) {                              // the hit's PAF line, with the cs body it carries when it carries one
 			const mpa_result_s::CsRef *c = r->cs.empty() ? nullptr : &r->cs[(size_t)(off[i] + j)];
 			const bool have = c && c->present;
@@ -345,16 +362,17 @@ static int64_t format_batch(const mpa_idx_t *mi, const mpa_mapopt_t *opt, const 
 			++id;
 			const bool residues = (opt->flag & (MPA_MF_SHOW_RESIDUE | MPA_MF_SHOW_TRANS)) != 0;
 			if (opt->flag & MPA_MF_GTF) {
-				if (residues) paf(j), put_residues(s, mi, *opt, seq, h[j], cig + h[j].cigar_off);
+				if (residues) paf(j), residue_rows(j);
 				put_gtf(s, mi, *opt, qlen, h[j], feats + h[j].feat_off, id);
 			} else {
 				if (!(opt->flag & MPA_MF_NO_PAF)) paf(j);
-				if (residues) put_residues(s, mi, *opt, seq, h[j], cig + h[j].cigar_off);
+				if (residues) residue_rows(j);
 				if (opt->flag & MPA_MF_GFF) put_gff(s, mi, *opt, names[i], qlen, h[j], feats + h[j].feat_off, id, (int32_t)j + 1);
 			}
 		}
 		if (id_base[i + 1] == id_base[i] && (opt->flag & MPA_MF_SHOW_UNMAP)) put_paf(s, mi, *opt, names[i], seq, qlen, nullptr, cig);
 		cs_carried += n_cs[0], cs_built += n_cs[1];
+		rows_carried += n_rows[0], rows_built += n_rows[1];
 	};
 	{
 		unsigned hw = std::thread::hardware_concurrency();
@@ -373,7 +391,11 @@ static int64_t format_batch(const mpa_idx_t *mi, const mpa_mapopt_t *opt, const 
 	s.reserve(total);
 	for (const std::string &x : part) s += x;
 	// (the counts behind the time: tools/timing_agg.py still sees one label)
-	if (timing_on()) fprintf(stderr, "[mpa-timing] %-28s %9.3f ms  cs carried %lld, built %lld\n", "format output", now_ms() - t0, (long long)cs_carried.load(), (long long)cs_built.load());
+	if (timing_on()) {
+		fprintf(stderr, "[mpa-timing] %-28s %9.3f ms  cs carried %lld, built %lld", "format output", now_ms() - t0, (long long)cs_carried.load(), (long long)cs_built.load());
+		if (opt->flag & (MPA_MF_SHOW_RESIDUE | MPA_MF_SHOW_TRANS)) fprintf(stderr, "; rows carried %lld, built %lld", (long long)rows_carried.load(), (long long)rows_built.load());
+		fputc('\n', stderr);
+	}
 	char *buf = (char*)malloc(s.size() + 1);
 	memcpy(buf, s.data(), s.size());
 	buf[s.size()] = 0;

@@ -1063,49 +1063,124 @@ static void cs_model(mpa_batch_s *b)
 	});
 }
 
-// The cs strings on the device, and with `stats` the statistics in the same call (one upload, two launches, one wait).  MPA_OK: done
-// (*ran: there was something to do); MPA_ERR_UNSUPPORTED: the device declined and nothing was changed; anything else is an error
-static int cs_on_device(mpa_batch_s *b, mpa_ctx_t *ctx, bool stats, bool *ran)
+// ---- (b'') MPA_GPU_ROWS: the residue rows of --aln / --trans of every aligned region, carried in the region to the result (DESIGN.md
+// section 4.9) ----  0 / unset = put_residues() of the formatter walks; 1 = on the device (k_aln_rows); model = the shared core on the
+// host with a team of one
+static StatsMode aln_rows_mode()
+{
+	const char *e = getenv("MPA_GPU_ROWS");             // (read per call: the tests flip it)
+	if (!e || !*e) return STATS_HOST;
+	if (!strcmp(e, "model")) return STATS_MODEL;
+	return atoi(e) != 0 ? STATS_DEVICE : STATS_HOST;
+}
+
+// does the formatter print residue rows for these options at all?
+static bool rows_printed(const mpa_mapopt_t &opt)
+{
+	return !(opt.flag & MPA_MF_NO_ALIGN) && (opt.flag & (MPA_MF_SHOW_RESIDUE | MPA_MF_SHOW_TRANS)) != 0;
+}
+
+static AlnRowsParams rows_params(const mpa_mapopt_t &opt)
+{
+	return AlnRowsParams{ opt.asize, opt.max_intron_flank, (opt.flag & MPA_MF_SHOW_RESIDUE) != 0, (opt.flag & MPA_MF_SHOW_TRANS) != 0 };
+}
+
+// a slot as the shared core left it, into the region: the four rows closed up to their width, the STA bytes behind them
+static void rows_apply(Region &r, const AlnRowsParams &p, const AlnRowsOut &o, const char *slot, int64_t slot_bytes, int8_t src)
+{
+	const int64_t stride = p.show_aln ? aln_rows_cols(r.cigar.data(), (int32_t)r.cigar.size(), p.flank) + 3 : 0;
+	const int32_t n_sta = p.show_trans ? o.n_sta : 0;
+	assert(!o.bad && o.width <= stride && 4 * stride + n_sta <= slot_bytes);   // (the walk ends at (ve - vs, qe - qs), inside its slot)
+	(void)slot_bytes;
+	r.rows.clear(), r.rows.reserve((size_t)(4 * (int64_t)o.width + n_sta));
+	for (int k = 0; k < 4 && p.show_aln; ++k) r.rows.append(slot + k * stride, (size_t)o.width);
+	r.rows.append(slot + 4 * stride, (size_t)n_sta);
+	r.rows_w = o.width, r.rows_sta = n_sta, r.rows_src = src;
+}
+
+// through the shared core on the host: a team of one per region
+static void rows_model(mpa_batch_s *b)
+{
+	uint8_t tab[ALN_TAB_BYTES];
+	memcpy(tab + ALN_TAB_CODON, tab_codon(), 64), memcpy(tab + ALN_TAB_AA20, tab_aa20(), 256), memcpy(tab + ALN_TAB_MAT, b->opt.mat, 484);
+	const AlnRowsParams p = rows_params(b->opt);
+	parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
+		QueryState &qs = b->qs[qi];
+		std::vector<char> slot;
+		for (AlignPlan &pl : qs.plans) {
+			Region &r = qs.regs[pl.reg];
+			const Contig &c = b->mi->ctg[r.vid >> 1];
+			const StatsGenomeHost g{ b->mi->seq.data(), c.off, c.len, (int)(r.vid & 1) };
+			const int64_t bytes = aln_rows_slot(r.cigar.data(), (int32_t)r.cigar.size(), p);
+			slot.resize((size_t)bytes + 1);
+			const AlnRowsOut o = aln_rows_core<StatsSerial>(stats_job(qs, pl, r, 0, 0, 0), p, tab, (const uint8_t*)qs.seq, r.cigar.data(), g, slot.data());
+			rows_apply(r, p, o, slot.data(), bytes, 1);
+		}
+	});
+}
+
+// The walks over the finished alignments on the device in one call: the cs strings (`cs`), the residue rows (`rows`), and with `stats`
+// the statistics (one upload, a launch each, one wait).  MPA_OK: done (*ran: there was something to do); MPA_ERR_UNSUPPORTED: the
+// device declined and nothing was changed; anything else is an error
+static int walks_on_device(mpa_batch_s *b, mpa_ctx_t *ctx, bool stats, bool cs_on, bool rows_on, bool *ran)
 {
 	const size_t nq = b->qs.size();
-	std::vector<int64_t> job0(nq + 1, 0), cig0(nq + 1, 0), feat0(nq + 1, 0), slot0(nq + 1, 0);
-	parallel_for(b->n_threads, (int64_t)nq, [&](int64_t qi) {                // (the bound walks every CIGAR: per query, then the prefix)
+	const AlnRowsParams rp = rows_params(b->opt);
+	std::vector<int64_t> job0(nq + 1, 0), cig0(nq + 1, 0), feat0(nq + 1, 0), slot0(nq + 1, 0), rslot0(nq + 1, 0);
+	std::atomic<bool> too_wide(false);
+	parallel_for(b->n_threads, (int64_t)nq, [&](int64_t qi) {                // (the bounds walk every CIGAR: per query, then the prefix)
 		const QueryState &qs = b->qs[qi];
-		int64_t nc = 0, nf = 0, nb = 0;
+		int64_t nc = 0, nf = 0, nb = 0, nr = 0;
 		for (const AlignPlan &pl : qs.plans) {
 			const Region &r = qs.regs[pl.reg];
-			nc += (int64_t)r.cigar.size(), nf += (int64_t)r.n_exon + 1, nb += aln_cs_bound(r.cigar.data(), (int32_t)r.cigar.size());
+			nc += (int64_t)r.cigar.size(), nf += (int64_t)r.n_exon + 1;
+			if (cs_on) nb += aln_cs_bound(r.cigar.data(), (int32_t)r.cigar.size());
+			if (rows_on) {
+				const int64_t bytes = aln_rows_slot(r.cigar.data(), (int32_t)r.cigar.size(), rp);
+				if (bytes > (int64_t)1 << 30) too_wide = true;           // (the core counts columns in 32 bits)
+				nr += bytes;
+			}
 		}
-		job0[qi + 1] = (int64_t)qs.plans.size(), cig0[qi + 1] = nc, feat0[qi + 1] = nf, slot0[qi + 1] = nb;
+		job0[qi + 1] = (int64_t)qs.plans.size(), cig0[qi + 1] = nc, feat0[qi + 1] = nf, slot0[qi + 1] = nb, rslot0[qi + 1] = nr;
 	});
-	for (size_t qi = 0; qi < nq; ++qi) job0[qi + 1] += job0[qi], cig0[qi + 1] += cig0[qi], feat0[qi + 1] += feat0[qi], slot0[qi + 1] += slot0[qi];
-	const int64_t n_jobs = job0[nq], n_cigar = cig0[nq], n_feat = stats ? feat0[nq] : -1, slot_bytes = slot0[nq];
+	for (size_t qi = 0; qi < nq; ++qi)
+		job0[qi + 1] += job0[qi], cig0[qi + 1] += cig0[qi], feat0[qi + 1] += feat0[qi], slot0[qi + 1] += slot0[qi], rslot0[qi + 1] += rslot0[qi];
+	const int64_t n_jobs = job0[nq], n_cigar = cig0[nq], n_feat = stats ? feat0[nq] : -1, slot_bytes = cs_on ? slot0[nq] : -1, rows_bytes = rows_on ? rslot0[nq] : -1;
 	*ran = n_jobs > 0;
 	if (n_jobs == 0) return MPA_OK;
+	if (too_wide) { set_error("GPU residue rows: an alignment of more than 2^30 bytes of rows"); return MPA_ERR_UNSUPPORTED; }
 	const int64_t t0 = b->q.q_off[0], text_bytes = b->q.q_off[b->q.n_seq] - t0;
 	AlnStatsIO io;
 	AlnCsIO cs;
-	int rc = dev_aln_cs_stage(ctx, n_jobs, n_cigar, text_bytes, n_feat, slot_bytes, io, cs);
+	AlnRowsIO rows;
+	int rc = dev_aln_walks_stage(ctx, n_jobs, n_cigar, text_bytes, n_feat, slot_bytes, rows_bytes, io, cs, rows);
 	if (rc != MPA_OK) return rc;
 	if (text_bytes > 0) memcpy(io.text, b->q.seqs + t0, (size_t)text_bytes);
-	cs.slot_off[n_jobs] = slot_bytes;
+	if (cs_on) cs.slot_off[n_jobs] = slot_bytes;
+	if (rows_on) rows.slot_off[n_jobs] = rows_bytes;
 	parallel_for(b->n_threads, (int64_t)nq, [&](int64_t qi) {
 		const QueryState &qs = b->qs[qi];
-		int64_t j = job0[qi], c = cig0[qi], f = feat0[qi], s = slot0[qi];
+		int64_t j = job0[qi], c = cig0[qi], f = feat0[qi], s = slot0[qi], rs = rslot0[qi];
 		for (const AlignPlan &pl : qs.plans) {
 			const Region &r = qs.regs[pl.reg];
-			cs.slot_off[j] = s;
+			if (cs_on) cs.slot_off[j] = s, s += aln_cs_bound(r.cigar.data(), (int32_t)r.cigar.size());
+			if (rows_on) rows.slot_off[j] = rs, rs += aln_rows_slot(r.cigar.data(), (int32_t)r.cigar.size(), rp);
 			io.jobs[j++] = stats_job(qs, pl, r, (qs.seq - b->q.seqs) - t0, c, f);
 			if (!r.cigar.empty()) memcpy(io.cigar + c, r.cigar.data(), r.cigar.size() * 4);
-			c += (int64_t)r.cigar.size(), f += (int64_t)r.n_exon + 1, s += aln_cs_bound(r.cigar.data(), (int32_t)r.cigar.size());
+			c += (int64_t)r.cigar.size(), f += (int64_t)r.n_exon + 1;
 		}
 	});
-	rc = dev_aln_cs(ctx, const_cast<mpa_idx_s*>(b->mi), stats_params(b->opt), b->opt.mat, n_jobs, n_cigar, text_bytes, n_feat, slot_bytes, io, cs);
+	rc = dev_aln_walks(ctx, const_cast<mpa_idx_s*>(b->mi), stats_params(b->opt), rp, b->opt.mat, n_jobs, n_cigar, text_bytes, n_feat, slot_bytes, rows_bytes, io, cs, rows);
 	if (rc != MPA_OK) return rc;
-	if (timing_on()) {                                   // what came down against what it held (the bounded slots: DESIGN.md section 4.8)
+	if (timing_on() && cs_on) {                          // what came down against what it held (the bounded slots: DESIGN.md section 4.8)
 		int64_t used = 0;
 		for (int64_t j = 0; j < n_jobs; ++j) used += cs.out[j].len;
 		fprintf(stderr, "[mpa-timing]   cs slots: %lld alignments, %lld bytes down, %lld bytes of strings\n", (long long)n_jobs, (long long)slot_bytes, (long long)used);
+	}
+	if (timing_on() && rows_on) {                        // (exact slots but for the trailing codon: DESIGN.md section 4.9)
+		int64_t used = 0;
+		for (int64_t j = 0; j < n_jobs; ++j) used += 4 * (int64_t)rows.out[j].width + (rp.show_trans ? rows.out[j].n_sta : 0);
+		fprintf(stderr, "[mpa-timing]   rows slots: %lld alignments, %lld bytes down, %lld bytes of rows\n", (long long)n_jobs, (long long)rows_bytes, (long long)used);
 	}
 	parallel_for(b->n_threads, (int64_t)nq, [&](int64_t qi) {
 		QueryState &qs = b->qs[qi];
@@ -1113,7 +1188,8 @@ static int cs_on_device(mpa_batch_s *b, mpa_ctx_t *ctx, bool stats, bool *ran)
 		for (AlignPlan &pl : qs.plans) {
 			Region &r = qs.regs[pl.reg];
 			if (stats) stats_apply(r, io.out[j], io.feat + io.jobs[j].feat_off);
-			cs_apply(r, cs.out[j], cs.body + cs.slot_off[j], cs.slot_off[j + 1] - cs.slot_off[j], 2);
+			if (cs_on) cs_apply(r, cs.out[j], cs.body + cs.slot_off[j], cs.slot_off[j + 1] - cs.slot_off[j], 2);
+			if (rows_on) rows_apply(r, rp, rows.out[j], rows.body + rows.slot_off[j], rows.slot_off[j + 1] - rows.slot_off[j], 2);
 			++j;
 		}
 	});
@@ -1161,7 +1237,9 @@ static int take_round3_steps(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint
 	if (mode == STATS_DEVICE && !b->dp_ctx) mode = STATS_HOST;            // (the stage machine without a context: mpa_batch_begin)
 	StatsMode cs = cs_printed(b->opt) ? aln_cs_mode() : STATS_HOST;
 	if (cs == STATS_DEVICE && !b->dp_ctx) cs = STATS_HOST;
-	if (mode == STATS_HOST && cs == STATS_HOST) {                         // the three steps in one pass over the queries
+	StatsMode rows = rows_printed(b->opt) ? aln_rows_mode() : STATS_HOST;
+	if (rows == STATS_DEVICE && !b->dp_ctx) rows = STATS_HOST;
+	if (mode == STATS_HOST && cs == STATS_HOST && rows == STATS_HOST) {   // the three steps in one pass over the queries
 		parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
 			QueryState &qs = b->qs[qi];
 			for (AlignPlan &pl : qs.plans) {
@@ -1188,40 +1266,54 @@ static int take_round3_steps(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint
 			for (AlignPlan &pl : qs.plans) stats_on_host(b, qs, pl, qs.regs[pl.reg]);
 		});
 	};
-	bool cs_done = false;
+	const bool cs_dev = cs == STATS_DEVICE, rows_dev = rows == STATS_DEVICE;
+	bool walks_done = false;                                               // the device's cs strings and rows went with the statistics
 	if (mode == STATS_MODEL) {
 		stats_model(b);
 		timing_note("alignment statistics: shared core", now_ms() - t0);
 	} else if (mode == STATS_HOST) {
 		stats_host_all();
 	} else {
-		// with MPA_GPU_CS=1 as well, the two kernels share the upload of jobs, CIGAR words and text, and the wait
-		const bool both = cs == STATS_DEVICE;
+		// with MPA_GPU_CS=1 / MPA_GPU_ROWS=1 as well, the kernels share the upload of jobs, CIGAR words and text, and the wait
+		const bool more = cs_dev || rows_dev;
 		bool ran = false;
-		const int rc = both ? cs_on_device(b, b->dp_ctx, true, &ran) : stats_on_device(b, b->dp_ctx, &ran);
+		const int rc = more ? walks_on_device(b, b->dp_ctx, true, cs_dev, rows_dev, &ran) : stats_on_device(b, b->dp_ctx, &ran);
 		if (rc != MPA_OK && rc != MPA_ERR_UNSUPPORTED) return rc;
 		if (rc == MPA_OK && ran) {
 			timing_note("alignment statistics on the GPU", now_ms() - t0);
-			if (both) timing_note("cs strings on the GPU", now_ms() - t0);   // (one call: the same span)
+			if (cs_dev) timing_note("cs strings on the GPU", now_ms() - t0);      // (one call: the same span)
+			if (rows_dev) timing_note("residue rows on the GPU", now_ms() - t0);
 		}
 		if (rc == MPA_ERR_UNSUPPORTED) {
 			if (timing_on()) fprintf(stderr, "[mpa-timing]   device alignment statistics declined (%s): statistics on the host\n", mpa_last_error());
-			if (both && timing_on()) fprintf(stderr, "[mpa-timing]   device cs strings declined with them: the formatter builds them\n");
+			if (cs_dev && timing_on()) fprintf(stderr, "[mpa-timing]   device cs strings declined with them: the formatter builds them\n");
+			if (rows_dev && timing_on()) fprintf(stderr, "[mpa-timing]   device residue rows declined with them: the formatter builds them\n");
 			stats_host_all();
 		}
-		cs_done = both;
+		walks_done = more;
 	}
-	if (cs != STATS_HOST && !cs_done) {                                    // (b')
+	if (cs == STATS_MODEL) {                                               // (b')
 		const double t1 = now_ms();
-		if (cs == STATS_MODEL) {
-			cs_model(b);
-			timing_note("cs strings: shared core", now_ms() - t1);
-		} else {
-			bool ran = false;
-			const int rc = cs_on_device(b, b->dp_ctx, false, &ran);
-			if (rc != MPA_OK && rc != MPA_ERR_UNSUPPORTED) return rc;
-			if (rc == MPA_OK && ran) timing_note("cs strings on the GPU", now_ms() - t1);
-			if (rc == MPA_ERR_UNSUPPORTED && timing_on()) fprintf(stderr, "[mpa-timing]   device cs strings declined (%s): the formatter builds them\n", mpa_last_error());
+		cs_model(b);
+		timing_note("cs strings: shared core", now_ms() - t1);
+	}
+	if (rows == STATS_MODEL) {                                             // (b'')
+		const double t1 = now_ms();
+		rows_model(b);
+		timing_note("residue rows: shared core", now_ms() - t1);
+	}
+	if ((cs_dev || rows_dev) && !walks_done) {                             // (b') / (b'') on the device: one call for both
+		const double t1 = now_ms();
+		bool ran = false;
+		const int rc = walks_on_device(b, b->dp_ctx, false, cs_dev, rows_dev, &ran);
+		if (rc != MPA_OK && rc != MPA_ERR_UNSUPPORTED) return rc;
+		if (rc == MPA_OK && ran) {
+			if (cs_dev) timing_note("cs strings on the GPU", now_ms() - t1);
+			if (rows_dev) timing_note("residue rows on the GPU", now_ms() - t1);
+		}
+		if (rc == MPA_ERR_UNSUPPORTED && timing_on()) {
+			if (cs_dev) fprintf(stderr, "[mpa-timing]   device cs strings declined (%s): the formatter builds them\n", mpa_last_error());
+			if (rows_dev) fprintf(stderr, "[mpa-timing]   device residue rows declined (%s): the formatter builds them\n", mpa_last_error());
 		}
 	}
 	parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) { stage_finish(b, b->qs[qi]); });   // (c)
@@ -2236,10 +2328,16 @@ static mpa_result_t *mpa_batch_finish_impl(mpa_batch_t *b)
 				res->cs.push_back(mpa_result_s::CsRef{ (int64_t)res->cs_text.size(), (int32_t)r.cs.size(), 1 });
 				res->cs_text += r.cs;
 			}
+			if (r.rows_src) {                                  // its residue rows the same way (MPA_GPU_ROWS)
+				res->rows.resize(res->hits.size(), mpa_result_s::RowsRef{ 0, 0, 0, 0 });
+				res->rows.push_back(mpa_result_s::RowsRef{ (int64_t)res->rows_text.size(), r.rows_w, r.rows_sta, 1 });
+				res->rows_text += r.rows;
+			}
 			res->hits.push_back(h);
 		}
 	}
 	if (!res->cs.empty()) res->cs.resize(res->hits.size(), mpa_result_s::CsRef{ 0, 0, 0 });
+	if (!res->rows.empty()) res->rows.resize(res->hits.size(), mpa_result_s::RowsRef{ 0, 0, 0, 0 });
 	res->hit_off[b->qs.size()] = (int64_t)res->hits.size();
 	parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t i) { b->qs[i] = QueryState(); });   // free per-query state in parallel
 	delete b;

@@ -12,6 +12,7 @@
 #include "chain_core.h"
 #include "aln_stats_core.h"
 #include "aln_cs_core.h"
+#include "aln_rows_core.h"
 #include "regions_core.h"
 #include "plans_core.h"
 
@@ -117,6 +118,11 @@ struct mpa_result_s {
 	struct CsRef { int64_t off; int32_t len, present; };
 	std::vector<CsRef> cs;
 	std::string cs_text;
+	// residue rows that came with the hits (MPA_GPU_ROWS), the same way: at off the four rows of `width` bytes each (none when the
+	// options print no --aln rows), then n_sta STA bytes (none without --trans)
+	struct RowsRef { int64_t off; int32_t width, n_sta, present; };
+	std::vector<RowsRef> rows;
+	std::string rows_text;
 };
 
 namespace mpa {
@@ -252,13 +258,18 @@ struct AlnStatsIO { AlnStatsJob *jobs = nullptr; uint32_t *cigar = nullptr; char
 int dev_aln_stats_stage(mpa_ctx_t *ctx, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat, AlnStatsIO &io);
 int dev_aln_stats(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const int8_t *mat, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat,
                   AlnStatsIO &io);
-// ---- cs:Z: difference strings on the device (MPA_GPU_CS=1; driver: stats_run.hip; code: aln_cs_core.h) ----
-// The same two steps with a slot per alignment: slot_bytes = the sum of aln_cs_bound() over the staged alignments, slot_off[n_jobs + 1]
-// is filled next to the jobs, and body + slot_off[j] holds out[j].len bytes afterwards (pinned, valid until the context's next call).
-// n_feat >= 0: the statistics run in the same call (io.out / io.feat as from dev_aln_stats); n_feat < 0: the cs strings alone.
+// ---- cs:Z: difference strings and --aln / --trans residue rows on the device (MPA_GPU_CS=1, MPA_GPU_ROWS=1; driver: stats_run.hip;
+// code: aln_cs_core.h, aln_rows_core.h) ----
+// The same two steps with a slot per alignment and walk.  slot_bytes = the sum of aln_cs_bound() over the staged alignments (< 0: no cs
+// strings in this call), rows_bytes = the sum of aln_rows_slot() (< 0: no rows); cs.slot_off[n_jobs + 1] / rows.slot_off[n_jobs + 1] are
+// filled next to the jobs.  Afterwards cs.body + cs.slot_off[j] holds cs.out[j].len bytes, and rows.body + rows.slot_off[j] the slot
+// aln_rows_core.h describes with rows.out[j] (pinned, valid until the context's next call).
+// n_feat >= 0: the statistics run in the same call (io.out / io.feat as from dev_aln_stats); n_feat < 0: without them.
 struct AlnCsIO { int64_t *slot_off = nullptr; const AlnCsOut *out = nullptr; const char *body = nullptr; };
-int dev_aln_cs_stage(mpa_ctx_t *ctx, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat, int64_t slot_bytes, AlnStatsIO &io, AlnCsIO &cs);
-int dev_aln_cs(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const int8_t *mat, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat,
-               int64_t slot_bytes, AlnStatsIO &io, AlnCsIO &cs);
+struct AlnRowsIO { int64_t *slot_off = nullptr; const AlnRowsOut *out = nullptr; const char *body = nullptr; };
+int dev_aln_walks_stage(mpa_ctx_t *ctx, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat, int64_t slot_bytes, int64_t rows_bytes, AlnStatsIO &io, AlnCsIO &cs,
+                        AlnRowsIO &rows);
+int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const AlnRowsParams &rp, const int8_t *mat, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes,
+                  int64_t n_feat, int64_t slot_bytes, int64_t rows_bytes, AlnStatsIO &io, AlnCsIO &cs, AlnRowsIO &rows);
 
 } // namespace mpa

@@ -4,6 +4,7 @@
 //   k_aln_stats   one wavefront per alignment, four alignments per workgroup: dist_stop / dist_start, the statistics of the CIGAR
 //                 walk and the exon / stop-codon features, written where the host's download finds them
 //   k_aln_cs      the same shape for the cs:Z: difference strings (MPA_GPU_CS=1; the code is aln_cs_core.h)
+//   k_aln_rows    the same shape for the residue rows of --aln / --trans (MPA_GPU_ROWS=1; the code is aln_rows_core.h)
 // The tables (codon table, aa20, substitution matrix: 804 bytes) are the workgroup's only LDS.  No capacity: the CIGAR is read 64
 // words at a time, runs of any length are strided over the lanes, features go straight to their slots in global memory.
 
@@ -74,6 +75,27 @@ __global__ __launch_bounds__(64 * STATS_WAVES) __attribute__((amdgpu_waves_per_e
 	const AlnStatsJob J = jobs[j];
 	const StatsGenome g{ seq, ctg_off[J.vid >> 1], ctg_len[J.vid >> 1], J.vid & 1 };
 	const AlnCsOut o = aln_cs_core<StatsWave>(J, tab, text, cig, g, slots + slot_off[j]);
+	if ((threadIdx.x & 63) == 0) out[j] = o;
+}
+
+// The residue rows of every alignment (aln_rows_core.h): the same jobs, tables, text and CIGAR pool, one
+// wavefront per alignment writing the four rows and the STA bytes into its own slot [slot_off[j], slot_off[j + 1]) of `slots` (sized
+// by aln_rows_slot() on the host, exactly) with plain byte stores, and its record to out[j].  Only the bases that are printed are
+// read from the resident genome.  The table block is the only LDS.
+__global__ __launch_bounds__(64 * STATS_WAVES) __attribute__((amdgpu_waves_per_eu(8))) void k_aln_rows(const AlnStatsJob *jobs, int32_t n_jobs, const uint8_t *tabs,
+                                                                                                      AlnRowsParams p, const uint8_t *text, const uint32_t *cig,
+                                                                                                      const uint8_t *seq, const int64_t *ctg_off, const int64_t *ctg_len,
+                                                                                                      const int64_t *slot_off, AlnRowsOut *out, char *slots)
+{
+	MPA_SHORT_KERNEL();
+	__shared__ uint8_t tab[(ALN_TAB_BYTES + 15) & ~15];
+	for (int i = (int)threadIdx.x; i < ALN_TAB_BYTES; i += 64 * STATS_WAVES) tab[i] = tabs[i];
+	__syncthreads();
+	const int32_t j = (int32_t)blockIdx.x * STATS_WAVES + __builtin_amdgcn_readfirstlane((int32_t)(threadIdx.x >> 6));
+	if (j >= n_jobs) return;
+	const AlnStatsJob J = jobs[j];
+	const StatsGenome g{ seq, ctg_off[J.vid >> 1], ctg_len[J.vid >> 1], J.vid & 1 };
+	const AlnRowsOut o = aln_rows_core<StatsWave>(J, p, tab, text, cig, g, slots + slot_off[j]);
 	if ((threadIdx.x & 63) == 0) out[j] = o;
 }
 
