@@ -1,0 +1,31 @@
+/* mpamd_dbg.h -- the test hook of MPA_GPU_SPANS.  It is not part of the C ABI of libmpamd.so (include/mpamd.h): it is built from
+ * miniprot_amd/csrc/spans_dbg.cpp into a library of its own, libmpamd_dbg.so, next to libmpamd.so and linked against it. */
+#ifndef MPAMD_DBG_H
+#define MPAMD_DBG_H
+#include "mpamd.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* The two steps of MPA_GPU_SPANS on hand-made inputs: the accepted spans between the DP rounds and the region CIGARs behind them, on
+ * the device (k_spans, k_spans_emit, k_assemble) or, with ctx == NULL, through the shared core on the host (spans_core.h).
+ * plans: n_plan records of 104 bytes -- int64 as, ae, vs0, vs1, mid_ve; int32 reg, as1, mid_qe, has_right, t_left, t_left2, t_right,
+ * t_right2, first gap segment (in segs), gap segments; int64 first residue of the query in q's text; int32 qid, qlen; uint32 vid; int32
+ * first round-1 result of the query (the t_* and the gap tasks count from it).  segs: n_seg records of 24 bytes -- int32 ne0, ne1, ae0,
+ * ae1, task (-1: the ungapped shortcut), score.  rst1 / pool1 and rst2 / pool2: the results of the two rounds and their CIGAR pools;
+ * rst2 is indexed by round-2 task number.  n_rst2 < 0: stop behind the first step.
+ * Out: span_rec[n_plan] (80 bytes: int64 vs; int32 qs, l_nt, l_aa, r_nt, r_aa, flags (1 / 2: the left / right span was
+ * made, 4 / 8: that side's terminal-exon repeat counted); the left and the right span as segment records),
+ * tasks[at most 2 n_plan] and *n_task; asm_rec[n_plan] (40 bytes: int64 ve, first word in cigar; int32 qe, dp_score, n_cigar, n_exon,
+ * bad, merged boundaries) and the words in cigar[cigar_cap] (a plan's slot is the sum of its segments' words).  Every index is checked first:
+ * MPA_ERR_ARG for inputs that point outside their arrays.
+ */
+int mpa_dbg_spans(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int32_t n_plan, const void *plans, int32_t n_seg, const void *segs,
+                  int64_t n_rst1, const mpa_dp_rst_t *rst1, const uint32_t *pool1, int64_t n_pool1, int64_t n_rst2, const mpa_dp_rst_t *rst2, const uint32_t *pool2,
+                  int64_t n_pool2, void *span_rec, mpa_dp_task_t *tasks, int32_t *n_task, void *asm_rec, uint32_t *cigar, int64_t cigar_cap);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

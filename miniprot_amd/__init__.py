@@ -488,6 +488,46 @@ def refine_chains(ctx, idx, mo, queries, wins):
 CLAIM_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p)
 
 
+DBG_LIB_PATH = os.path.join(_HERE, "libmpamd_dbg.so")   # the test hook of MPA_GPU_SPANS: a library of its own, linked against libmpamd.so
+_dbg_lib = None
+
+
+def dbg_lib():
+    """libmpamd_dbg.so (mpa_dbg_spans), loaded behind libmpamd.so"""
+    global _dbg_lib
+    if _dbg_lib is None:
+        lib()
+        if not os.path.exists(DBG_LIB_PATH):
+            raise ImportError("%s is missing: run `python -c 'import __graft_entry__ as g; g.build()'`" % DBG_LIB_PATH)
+        _dbg_lib = C.CDLL(DBG_LIB_PATH)
+    return _dbg_lib
+
+
+def dbg_spans(ctx, idx, mo, queries, plans, segs, rst1, pool1, rst2=None, pool2=None):
+    """mpa_dbg_spans(): the two steps of MPA_GPU_SPANS on hand-made inputs -- the accepted spans between the DP rounds and the region
+    CIGARs behind them -- on the device (ctx) or through the shared core on the host (ctx None).  plans (104-byte records), segs (24),
+    rst1 / rst2 (mpa_dp_rst_t) and the pools (uint32) are numpy arrays laid out as include/mpamd_dbg.h says.  Returns (span records as
+    bytes, round-2 tasks as bytes) for rst2 None, else (span records, tasks, assemble records, cigar words as a uint32 array)."""
+    import numpy as np
+    fn = dbg_lib().mpa_dbg_spans
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(MapOpt), C.POINTER(QBatch), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                   C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_int64]
+    n = len(plans)
+    rec, tasks, arec, n_task = np.zeros(80 * n, np.uint8), np.zeros(80 * n + 8, np.uint8), np.zeros(40 * n, np.uint8), C.c_int32(0)
+    cap = 2 * n + len(segs) + len(pool1) + (len(pool2) if pool2 is not None else 0) + 16
+    cig = np.zeros(cap, np.uint32)
+    keep = [np.ascontiguousarray(x) if x is not None else None for x in (plans, segs, rst1, pool1, rst2, pool2)]
+    ptr = [x.ctypes.data if x is not None and len(x) else None for x in keep]
+    _check(fn(ctx.h if ctx else None, idx.h, C.byref(mo), C.byref(queries.c), n, ptr[0], len(segs), ptr[1], len(rst1), ptr[2], ptr[3], len(pool1),
+              -1 if rst2 is None else len(rst2), ptr[4], ptr[5], 0 if pool2 is None else len(pool2), rec.ctypes.data, tasks.ctypes.data, C.byref(n_task), arec.ctypes.data,
+              cig.ctypes.data, cap))
+    tasks = tasks[:40 * n_task.value].tobytes()
+    if rst2 is None:
+        return rec.tobytes(), tasks
+    return rec.tobytes(), tasks, arec.tobytes(), cig
+
+
 def map_batches(ctx, idx, mo, batches, n_threads=1, keep_results=False, want_text=True, claim=None):
     """mpa_map_batches(): a stream of Queries batches through the pipelined mapper.  Returns the list of output texts
     (bytes, one per batch; the hit-id counter runs across the batches as in one output file); with keep_results the pair

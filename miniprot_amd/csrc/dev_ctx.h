@@ -164,6 +164,12 @@ struct mpa_ctx_s {
 	// ---- residue rows (stats_run.hip, MPA_GPU_ROWS=1): the same again
 	DevBuf rows_out;                          // records | slots
 	HostPinned h_rows_down;
+	// ---- accepted spans and region CIGARs (stats_run.hip, MPA_GPU_SPANS=1): grow-only, allocated by the first call that asks for them
+	DevBuf sp_in, sp_mid, sp_out;             // tables | plans | gap segments | round-1 results | text; k_spans' scratch; count | records | round-2 tasks
+	DevBuf sp_pool1;                          // the batch's round-1 CIGAR pool, kept across round 2 (which overwrites cigd)
+	DevBuf sp_in2, sp_asm, sp_cig;            // round-2 results | slot offsets (| a caller's round-2 pool); per-plan records; the assembled CIGARs
+	HostPinned h_sp_up, h_sp_down, h_sp_up2, h_sp_down2;
+	struct SpansKeep { size_t off_plan = 0, off_seg = 0, off_rst1 = 0; int64_t n_plan = -1, n_pool1 = 0; } sp_keep;   // what dev_spans_round1 left for dev_spans_assemble
 };
 
 namespace mpa {
@@ -179,7 +185,8 @@ template<typename F> static void ctx_each_devbuf(mpa_ctx_s *ctx, F f)
 	                  &B.c_a, &B.c_f, &B.c_pred, &B.c_mark, &B.c_flag, &B.c_first, &B.c_long,
 	                  &B.pf_qfirst2, &B.val64[0], &B.val64[1],
 	                  &B.s_meta, &B.s_cur, &B.s_cur2, &B.s_kept, &B.s_base, &B.s_out, &B.s_flag, &B.dkey, &B.x_all, &B.rx_all, &B.rx_keys,
-	                  &ctx->lite, &ctx->ckpt, &ctx->wlist, &B.k_in, &B.k_cnt, &B.k_bkt, &B.k_q, &B.r_gmap, &ctx->st_in, &ctx->st_out, &B.rg, &B.pl, &ctx->cs_out, &ctx->rows_out };
+	                  &ctx->lite, &ctx->ckpt, &ctx->wlist, &B.k_in, &B.k_cnt, &B.k_bkt, &B.k_q, &B.r_gmap, &ctx->st_in, &ctx->st_out, &B.rg, &B.pl, &ctx->cs_out, &ctx->rows_out,
+	                  &ctx->sp_in, &ctx->sp_mid, &ctx->sp_out, &ctx->sp_pool1, &ctx->sp_in2, &ctx->sp_asm, &ctx->sp_cig };
 	int k = 0;
 	for (DevBuf *b : all) f(*b, k++);
 }

@@ -48,6 +48,8 @@ struct AlignPlan {                   // the state of one mp_align() call
 	bool has_right = false;
 	Segment left_span, right_span;   // the spans accepted by the two extensions, re-aligned with traceback (round 3)
 	bool has_left_span = false, has_right_span = false;
+	bool l_rep = false, r_rep = false;   // the terminal-exon repeat of that side counted (MPA_SPANS_DUMP)
+	int32_t n_merged = 0;            // segment boundaries that merged two words into one (MPA_SPANS_DUMP)
 	std::vector<Segment> gaps;       // gaps between consecutive kept anchors: independent of the extensions (round 1)
 };
 
@@ -88,6 +90,16 @@ struct mpa_batch_s {
 	std::vector<int64_t> seed_qfirst;
 	bool dev_sketch = false;         // MPA_GPU_SKETCH: the sketch phase built the shell only, the seeder runs the sketch on the device first
 	mpa_ctx_t *dp_ctx = nullptr;     // the context that runs this batch's DP rounds (run_dp_rounds), null for a caller that drives the stage machine itself
+	int64_t dp_n_pool = 0;           // ... and the words of the CIGAR pool its last mpa_dp_run left there
+	// MPA_GPU_SPANS (1 or model) between the rounds: how round 1 was taken (0 host, 1 shared core, 2 device), the round-1 results and
+	// their CIGAR pool kept for the step behind round 2 (the pool is the executor's own block on the device path: run_dp_rounds hands
+	// it over instead of freeing it), and where k_assemble left every plan's words on the device (empty: not there)
+	int spans_src = 0;
+	bool spans_want_pool = false;
+	std::vector<mpa_dp_rst_t> sp_rst1;
+	uint32_t *sp_pool1 = nullptr;
+	std::vector<int64_t> sp_cig_off;
+	~mpa_batch_s() { free(sp_pool1); }
 };
 
 namespace mpa {
@@ -839,11 +851,11 @@ static void take_round1_emit_round2(mpa_batch_s *b, const mpa_dp_rst_t *rst, con
 			pl.l_nt = mine[pl.t_left].nt_len, pl.l_aa = mine[pl.t_left].aa_len;
 			// the terminal-exon repeat counts iff the reference would have made it AND it reaches the end of the protein (align.c:290-296)
 			if (pl.t_left2 >= 0 && pl.l_aa != pl.as1 && pl.l_nt < opt.max_ext && mine[pl.t_left2].aa_len == pl.as1)
-				pl.l_nt = mine[pl.t_left2].nt_len, pl.l_aa = mine[pl.t_left2].aa_len;
+				pl.l_nt = mine[pl.t_left2].nt_len, pl.l_aa = mine[pl.t_left2].aa_len, pl.l_rep = true;
 			if (pl.has_right) {
 				pl.r_nt = mine[pl.t_right].nt_len, pl.r_aa = mine[pl.t_right].aa_len;
 				if (pl.t_right2 >= 0 && pl.r_aa < qs.qlen - pl.mid_qe && pl.r_nt < opt.max_ext && mine[pl.t_right2].aa_len == qs.qlen - pl.mid_qe)
-					pl.r_nt = mine[pl.t_right2].nt_len, pl.r_aa = mine[pl.t_right2].aa_len;
+					pl.r_nt = mine[pl.t_right2].nt_len, pl.r_aa = mine[pl.t_right2].aa_len, pl.r_rep = true;
 			}
 		}
 	});
@@ -876,9 +888,10 @@ static void assemble_alignment(AlignPlan &pl, Region &r, const mpa_dp_rst_t *rst
 	r.cigar.clear();
 	if (pl.has_left_span) store_result(pl.left_span, rst, pool);
 	if (pl.has_right_span) store_result(pl.right_span, rst, pool);
+	int32_t words = 0;
 	auto add = [&](const Segment &s) {
 		for (uint32_t c : s.cigar) append_cigar(r.cigar, c & 0xf, (int32_t)(c >> 4));
-		score += s.score;
+		score += s.score, words += (int32_t)s.cigar.size();
 	};
 	if (pl.has_left_span) add(pl.left_span);
 	for (const Segment &g : pl.gaps) add(g);
@@ -887,6 +900,7 @@ static void assemble_alignment(AlignPlan &pl, Region &r, const mpa_dp_rst_t *rst
 	if (pl.has_right && pl.r_nt > 0 && pl.r_aa > 0) r.ve += pl.r_nt, r.qe += pl.r_aa;
 	r.aligned = true;
 	r.dp_score = score, r.dp_max2 = 0;
+	pl.n_merged = words - (int32_t)r.cigar.size();
 }
 
 // (b) on the host, as the reference walks it
@@ -993,7 +1007,10 @@ static int stats_on_device(mpa_batch_s *b, mpa_ctx_t *ctx, bool *ran)
 	if (n_jobs == 0) return MPA_OK;
 	const int64_t t0 = b->q.q_off[0], text_bytes = b->q.q_off[b->q.n_seq] - t0;
 	AlnStatsIO io;
-	int rc = dev_aln_stats_stage(ctx, n_jobs, n_cigar, text_bytes, n_feat, io);
+	// MPA_GPU_SPANS=1: k_assemble left the words on this context; they are neither staged nor uploaded
+	const bool dev_cig = (int64_t)b->sp_cig_off.size() == n_jobs;
+	const int64_t n_up = dev_cig ? 0 : n_cigar;
+	int rc = dev_aln_stats_stage(ctx, n_jobs, n_up, text_bytes, n_feat, io);
 	if (rc != MPA_OK) return rc;
 	if (text_bytes > 0) memcpy(io.text, b->q.seqs + t0, (size_t)text_bytes);
 	parallel_for(b->n_threads, (int64_t)nq, [&](int64_t qi) {
@@ -1001,13 +1018,15 @@ static int stats_on_device(mpa_batch_s *b, mpa_ctx_t *ctx, bool *ran)
 		int64_t j = job0[qi], c = cig0[qi], f = feat0[qi];
 		for (const AlignPlan &pl : qs.plans) {
 			const Region &r = qs.regs[pl.reg];
-			io.jobs[j++] = stats_job(qs, pl, r, (qs.seq - b->q.seqs) - t0, c, f);
-			if (!r.cigar.empty()) memcpy(io.cigar + c, r.cigar.data(), r.cigar.size() * 4);
+			io.jobs[j] = stats_job(qs, pl, r, (qs.seq - b->q.seqs) - t0, dev_cig ? b->sp_cig_off[(size_t)j] : c, f);
+			++j;
+			if (!dev_cig && !r.cigar.empty()) memcpy(io.cigar + c, r.cigar.data(), r.cigar.size() * 4);
 			c += (int64_t)r.cigar.size(), f += (int64_t)r.n_exon + 1;
 		}
 	});
-	rc = dev_aln_stats(ctx, const_cast<mpa_idx_s*>(b->mi), stats_params(b->opt), b->opt.mat, n_jobs, n_cigar, text_bytes, n_feat, io);
+	rc = dev_aln_stats(ctx, const_cast<mpa_idx_s*>(b->mi), stats_params(b->opt), b->opt.mat, n_jobs, n_up, text_bytes, n_feat, io, dev_cig);
 	if (rc != MPA_OK) return rc;
+	if (timing_on() && dev_cig) fprintf(stderr, "[mpa-timing]   walks upload: %lld alignments, %lld CIGAR words (the assembled pool is on the device)\n", (long long)n_jobs, (long long)n_up);
 	parallel_for(b->n_threads, (int64_t)nq, [&](int64_t qi) {
 		QueryState &qs = b->qs[qi];
 		int64_t j = job0[qi];
@@ -1153,7 +1172,10 @@ static int walks_on_device(mpa_batch_s *b, mpa_ctx_t *ctx, bool stats, bool cs_o
 	AlnStatsIO io;
 	AlnCsIO cs;
 	AlnRowsIO rows;
-	int rc = dev_aln_walks_stage(ctx, n_jobs, n_cigar, text_bytes, n_feat, slot_bytes, rows_bytes, io, cs, rows);
+	// MPA_GPU_SPANS=1: k_assemble left the words on this context; they are neither staged nor uploaded
+	const bool dev_cig = (int64_t)b->sp_cig_off.size() == n_jobs;
+	const int64_t n_up = dev_cig ? 0 : n_cigar;
+	int rc = dev_aln_walks_stage(ctx, n_jobs, n_up, text_bytes, n_feat, slot_bytes, rows_bytes, io, cs, rows);
 	if (rc != MPA_OK) return rc;
 	if (text_bytes > 0) memcpy(io.text, b->q.seqs + t0, (size_t)text_bytes);
 	if (cs_on) cs.slot_off[n_jobs] = slot_bytes;
@@ -1165,13 +1187,15 @@ static int walks_on_device(mpa_batch_s *b, mpa_ctx_t *ctx, bool stats, bool cs_o
 			const Region &r = qs.regs[pl.reg];
 			if (cs_on) cs.slot_off[j] = s, s += aln_cs_bound(r.cigar.data(), (int32_t)r.cigar.size());
 			if (rows_on) rows.slot_off[j] = rs, rs += aln_rows_slot(r.cigar.data(), (int32_t)r.cigar.size(), rp);
-			io.jobs[j++] = stats_job(qs, pl, r, (qs.seq - b->q.seqs) - t0, c, f);
-			if (!r.cigar.empty()) memcpy(io.cigar + c, r.cigar.data(), r.cigar.size() * 4);
+			io.jobs[j] = stats_job(qs, pl, r, (qs.seq - b->q.seqs) - t0, dev_cig ? b->sp_cig_off[(size_t)j] : c, f);
+			++j;
+			if (!dev_cig && !r.cigar.empty()) memcpy(io.cigar + c, r.cigar.data(), r.cigar.size() * 4);
 			c += (int64_t)r.cigar.size(), f += (int64_t)r.n_exon + 1;
 		}
 	});
-	rc = dev_aln_walks(ctx, const_cast<mpa_idx_s*>(b->mi), stats_params(b->opt), rp, b->opt.mat, n_jobs, n_cigar, text_bytes, n_feat, slot_bytes, rows_bytes, io, cs, rows);
+	rc = dev_aln_walks(ctx, const_cast<mpa_idx_s*>(b->mi), stats_params(b->opt), rp, b->opt.mat, n_jobs, n_up, text_bytes, n_feat, slot_bytes, rows_bytes, io, cs, rows, dev_cig);
 	if (rc != MPA_OK) return rc;
+	if (timing_on() && dev_cig) fprintf(stderr, "[mpa-timing]   walks upload: %lld alignments, %lld CIGAR words (the assembled pool is on the device)\n", (long long)n_jobs, (long long)n_up);
 	if (timing_on() && cs_on) {                          // what came down against what it held (the bounded slots: DESIGN.md section 4.8)
 		int64_t used = 0;
 		for (int64_t j = 0; j < n_jobs; ++j) used += cs.out[j].len;
@@ -1222,6 +1246,298 @@ static void cs_dump(const mpa_batch_s *b)
 	fclose(fp);
 }
 
+// ---- MPA_GPU_SPANS: the step between the DP rounds (take_round1_emit_round2) and step (a) behind them (assemble_alignment,
+// count_exons) through spans_core.h ----  0 / unset = the host functions above; 1 = on the device, on the
+// batch's DP context (k_spans, k_spans_emit, k_assemble: span_kernels.hip); model = the shared core on the host with a team of one
+static StatsMode spans_mode()
+{
+	const char *e = getenv("MPA_GPU_SPANS");            // (read per call: the tests flip it)
+	if (!e || !*e) return STATS_HOST;
+	if (!strcmp(e, "model")) return STATS_MODEL;
+	return atoi(e) != 0 ? STATS_DEVICE : STATS_HOST;
+}
+static bool spans_dump_on() { const char *fn = getenv("MPA_SPANS_DUMP"); return fn && *fn; }
+static SpansParams spans_params(const mpa_mapopt_t &opt) { return SpansParams{ opt.kmer2, opt.max_ext, opt.io, opt.asize }; }
+
+// the batch's plans and gap segments as the shared core reads them: query-major, plans in order (plan0[q]: the first plan of query q)
+static void spans_counts(const mpa_batch_s *b, std::vector<int64_t> &plan0, std::vector<int64_t> &seg0)
+{
+	const size_t nq = b->qs.size();
+	plan0.assign(nq + 1, 0), seg0.assign(nq + 1, 0);
+	for (size_t qi = 0; qi < nq; ++qi) {
+		int64_t ns = 0;
+		for (const AlignPlan &pl : b->qs[qi].plans) ns += (int64_t)pl.gaps.size();
+		plan0[qi + 1] = plan0[qi] + (int64_t)b->qs[qi].plans.size(), seg0[qi + 1] = seg0[qi] + ns;
+	}
+}
+static void spans_flatten(mpa_batch_s *b, const std::vector<int64_t> &plan0, const std::vector<int64_t> &seg0, SpansPlan *plan, SegRec *seg)
+{
+	const int64_t t0 = b->q.q_off[0];
+	parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
+		const QueryState &qs = b->qs[qi];
+		int64_t j = plan0[qi], g = seg0[qi];
+		for (const AlignPlan &pl : qs.plans) {
+			SpansPlan &P = plan[j++];
+			PlanRec &y = P.pl;
+			y.as = pl.as, y.ae = pl.ae, y.vs0 = pl.vs0, y.vs1 = pl.vs1, y.mid_ve = pl.mid_ve, y.reg = pl.reg, y.as1 = pl.as1, y.mid_qe = pl.mid_qe, y.has_right = pl.has_right ? 1 : 0;
+			y.t_left = pl.t_left, y.t_left2 = pl.t_left2, y.t_right = pl.t_right, y.t_right2 = pl.t_right2, y.gap0 = (int32_t)g, y.n_gap = (int32_t)pl.gaps.size();
+			P.q_off = (qs.seq - b->q.seqs) - t0, P.qid = qs.qid, P.qlen = qs.qlen, P.vid = qs.regs[pl.reg].vid, P.base1 = (int32_t)qs.base1;
+			for (const Segment &s : pl.gaps) seg[g++] = SegRec{ s.ne0, s.ne1, s.ae0, s.ae1, s.task, s.score };
+		}
+	});
+}
+static void span_segment_apply(Segment &s, const SegRec &z)
+{
+	s.ne0 = z.ne0, s.ne1 = z.ne1, s.ae0 = z.ae0, s.ae1 = z.ae1, s.task = z.task, s.score = z.score;
+	s.cigar.clear();
+	if (z.task < 0) s.cigar.assign(1, (uint32_t)(z.ae1 - z.ae0) << 4);
+}
+// what spans_accept left (on the host or on the device), into the plans, the regions and the batch's task list
+static void spans_apply_round1(mpa_batch_s *b, const std::vector<int64_t> &plan0, const SpanRec *rec, const mpa_dp_task_t *task, int64_t n_task)
+{
+	parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
+		QueryState &qs = b->qs[qi];
+		int64_t j = plan0[qi];
+		for (AlignPlan &pl : qs.plans) {
+			const SpanRec &R = rec[j++];
+			Region &r = qs.regs[pl.reg];
+			pl.l_nt = R.l_nt, pl.l_aa = R.l_aa, pl.r_nt = R.r_nt, pl.r_aa = R.r_aa;
+			r.vs = R.vs, r.qs = R.qs;
+			pl.has_left_span = true, span_segment_apply(pl.left_span, R.left);
+			pl.has_right_span = (R.flags & SPANS_RIGHT) != 0, pl.l_rep = (R.flags & SPANS_LREP) != 0, pl.r_rep = (R.flags & SPANS_RREP) != 0;
+			if (pl.has_right_span) span_segment_apply(pl.right_span, R.right);
+		}
+	});
+	b->tasks.assign(task, task + n_task);
+}
+// the record of a plan back from its state (behind round 2 the shared core reads what round 1 left)
+static SpanRec span_rec_of(const AlignPlan &pl, const Region &r)
+{
+	SpanRec R;
+	R.vs = r.vs, R.qs = r.qs, R.l_nt = pl.l_nt, R.l_aa = pl.l_aa, R.r_nt = pl.r_nt, R.r_aa = pl.r_aa, R.flags = SPANS_LEFT | (pl.has_right_span ? SPANS_RIGHT : 0) | (pl.l_rep ? SPANS_LREP : 0) | (pl.r_rep ? SPANS_RREP : 0);
+	R.left = SegRec{ pl.left_span.ne0, pl.left_span.ne1, pl.left_span.ae0, pl.left_span.ae1, pl.left_span.task, pl.left_span.score };
+	R.right = SegRec{ 0, 0, 0, 0, -1, 0 };
+	if (pl.has_right_span) R.right = SegRec{ pl.right_span.ne0, pl.right_span.ne1, pl.right_span.ae0, pl.right_span.ae1, pl.right_span.task, pl.right_span.score };
+	return R;
+}
+static void spans_keep_round1(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint32_t *pool, bool copy_pool)
+{
+	b->sp_rst1.assign(rst, rst + b->tasks.size());
+	free(b->sp_pool1), b->sp_pool1 = nullptr;
+	b->spans_want_pool = !copy_pool;                     // (the device path: run_dp_rounds hands the executor's block over)
+	if (copy_pool) {
+		int64_t n = 0;
+		for (const mpa_dp_rst_t &o : b->sp_rst1) n = std::max<int64_t>(n, o.cigar_off + o.n_cigar);
+		b->sp_pool1 = (uint32_t*)malloc((size_t)(n > 0 ? n : 1) * 4);
+		if (n > 0) memcpy(b->sp_pool1, pool, (size_t)n * 4);
+	}
+}
+
+// between the rounds through the shared core on the host: one lane per plan, the task numbers from a running count
+static void spans_round1_model(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint32_t *pool)
+{
+	std::vector<int64_t> plan0, seg0;
+	spans_counts(b, plan0, seg0);
+	const int64_t n_plan = plan0.back();
+	std::vector<SpansPlan> plan((size_t)n_plan);
+	std::vector<SegRec> seg((size_t)seg0.back() + 1);
+	spans_flatten(b, plan0, seg0, plan.data(), seg.data());
+	uint8_t tab[ALN_TAB_BYTES];
+	memcpy(tab + ALN_TAB_CODON, tab_codon(), 64), memcpy(tab + ALN_TAB_AA20, tab_aa20(), 256), memcpy(tab + ALN_TAB_MAT, b->opt.mat, 484);
+	const SpansParams p = spans_params(b->opt);
+	std::vector<SpanRec> rec((size_t)n_plan);
+	std::vector<mpa_dp_task_t> task;
+	const uint8_t *text = (const uint8_t*)b->q.seqs + b->q.q_off[0];
+	for (int64_t j = 0; j < n_plan; ++j) {
+		const Contig &c = b->mi->ctg[plan[j].vid >> 1];
+		const StatsGenomeHost g{ b->mi->seq.data(), c.off, c.len, (int)(plan[j].vid & 1) };
+		mpa_dp_task_t t[2];
+		const int32_t n = spans_accept(p, plan[j], rst, g, tab, text, rec[j], t), t0 = (int32_t)task.size();
+		if (rec[j].left.task >= 0) rec[j].left.task += t0;
+		if (rec[j].right.task >= 0) rec[j].right.task += t0;
+		task.insert(task.end(), t, t + n);
+	}
+	spans_keep_round1(b, rst, pool, true);
+	spans_apply_round1(b, plan0, rec.data(), task.data(), (int64_t)task.size());
+}
+
+// between the rounds on the device.  MPA_OK: done; MPA_ERR_UNSUPPORTED: the device declined and nothing was changed
+static int spans_round1_device(mpa_batch_s *b, mpa_ctx_t *ctx, const mpa_dp_rst_t *rst)
+{
+	std::vector<int64_t> plan0, seg0;
+	spans_counts(b, plan0, seg0);
+	const int64_t n_plan = plan0.back(), n_seg = seg0.back(), n_rst1 = (int64_t)b->tasks.size();
+	const int64_t t0 = b->q.q_off[0], text_bytes = b->q.q_off[b->q.n_seq] - t0;
+	SpansIO io;
+	int rc = dev_spans_stage(ctx, n_plan, n_seg, n_rst1, text_bytes, io);
+	if (rc != MPA_OK) return rc;
+	spans_flatten(b, plan0, seg0, io.plan, io.seg);
+	memcpy(io.rst1, rst, (size_t)n_rst1 * sizeof(mpa_dp_rst_t));
+	if (text_bytes > 0) memcpy(io.text, b->q.seqs + t0, (size_t)text_bytes);
+	rc = dev_spans_round1(ctx, const_cast<mpa_idx_s*>(b->mi), spans_params(b->opt), b->opt.mat, n_plan, n_seg, n_rst1, text_bytes, nullptr, b->dp_n_pool, io);
+	if (rc != MPA_OK) return rc;
+	spans_keep_round1(b, rst, nullptr, false);
+	spans_apply_round1(b, plan0, io.rec, io.task, io.n_task);
+	return MPA_OK;
+}
+
+// MPA_OK, or the error of a device call that failed (a call that merely declines leaves the batch to the host step)
+static int spans_take_round1(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint32_t *pool)
+{
+	StatsMode mode = spans_mode();
+	if (mode == STATS_DEVICE && !b->dp_ctx) mode = STATS_HOST;               // (the stage machine without a context: mpa_batch_begin)
+	b->spans_src = 0;
+	bool any_plan = false;
+	for (const QueryState &qs : b->qs) any_plan = any_plan || !qs.plans.empty();
+	if (mode != STATS_HOST && rst && any_plan) {
+		const double t0 = now_ms();
+		if (mode == STATS_MODEL) {
+			spans_round1_model(b, rst, pool);
+			b->spans_src = 1;
+			timing_note("spans: shared core", now_ms() - t0);
+			return MPA_OK;
+		}
+		const int rc = spans_round1_device(b, b->dp_ctx, rst);
+		if (rc == MPA_OK) {
+			b->spans_src = 2;
+			timing_note("spans on the GPU", now_ms() - t0);
+			return MPA_OK;
+		}
+		if (rc != MPA_ERR_UNSUPPORTED) return rc;
+		if (timing_on()) fprintf(stderr, "[mpa-timing]   device spans declined (%s): accepted spans on the host\n", mpa_last_error());
+	}
+	take_round1_emit_round2(b, rst, pool);
+	return MPA_OK;
+}
+
+// step (a) behind round 2 on the host for a batch whose round 1 went through the shared core: the gap segments' words come from the
+// kept round-1 results
+static void spans_assemble_host(mpa_batch_s *b, const mpa_dp_rst_t *rst2, const uint32_t *pool2)
+{
+	parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
+		QueryState &qs = b->qs[qi];
+		for (AlignPlan &pl : qs.plans) {
+			Region &r = qs.regs[pl.reg];
+			for (Segment &g : pl.gaps) store_result(g, b->sp_rst1.data() + qs.base1, b->sp_pool1);
+			assemble_alignment(pl, r, rst2, pool2);
+			r.n_exon = count_exons(r);
+		}
+	});
+}
+static void asm_apply(AlignPlan &pl, Region &r, const AsmRec &A, const uint32_t *words, const mpa_dp_rst_t *rst2)
+{
+	pl.n_merged = A.n_merged;
+	if (pl.left_span.task >= 0) pl.left_span.score = rst2[pl.left_span.task].score;       // (as store_result leaves the spans; their words stay in the pool)
+	if (pl.has_right_span && pl.right_span.task >= 0) pl.right_span.score = rst2[pl.right_span.task].score;
+	r.cigar.assign(words, words + A.n_cigar);
+	r.ve = A.ve, r.qe = A.qe, r.aligned = true, r.dp_score = A.dp_score, r.dp_max2 = 0, r.n_exon = A.n_exon;
+}
+// every plan's slot in words: the sum of its segments' words (merges only shorten it)
+static void spans_slots(mpa_batch_s *b, const std::vector<int64_t> &plan0, const mpa_dp_rst_t *rst2, int64_t *slot_off)
+{
+	parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
+		const QueryState &qs = b->qs[qi];
+		int64_t j = plan0[qi];
+		const mpa_dp_rst_t *mine = b->sp_rst1.data() + qs.base1;
+		for (const AlignPlan &pl : qs.plans) {
+			int64_t n = pl.left_span.task < 0 ? 1 : rst2[pl.left_span.task].n_cigar;
+			for (const Segment &g : pl.gaps) n += g.task < 0 ? 1 : mine[g.task].n_cigar;
+			if (pl.has_right_span) n += pl.right_span.task < 0 ? 1 : rst2[pl.right_span.task].n_cigar;
+			slot_off[j++ + 1] = n;
+		}
+	});
+	slot_off[0] = 0;
+	for (int64_t j = 0; j < plan0.back(); ++j) slot_off[j + 1] += slot_off[j];
+}
+
+// step (a) through the shared core on the host: a team of one per plan
+static void spans_assemble_model(mpa_batch_s *b, const mpa_dp_rst_t *rst2, const uint32_t *pool2)
+{
+	std::vector<int64_t> plan0, seg0;
+	spans_counts(b, plan0, seg0);
+	std::vector<SpansPlan> plan((size_t)plan0.back());
+	std::vector<SegRec> seg((size_t)seg0.back() + 1);
+	spans_flatten(b, plan0, seg0, plan.data(), seg.data());
+	std::vector<int64_t> slot((size_t)plan0.back() + 1);
+	spans_slots(b, plan0, rst2, slot.data());
+	std::atomic<bool> bad(false);
+	parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
+		QueryState &qs = b->qs[qi];
+		std::vector<uint32_t> out;
+		int64_t j = plan0[qi];
+		for (AlignPlan &pl : qs.plans) {
+			Region &r = qs.regs[pl.reg];
+			out.assign((size_t)(slot[j + 1] - slot[j]) + 1, 0);
+			const AsmRec A = spans_assemble<SpansSerial>(plan[j], span_rec_of(pl, r), seg.data(), b->sp_rst1.data(), b->sp_pool1, rst2, pool2, out.data());
+			if (A.bad) bad = true;
+			asm_apply(pl, r, A, out.data(), rst2);
+			++j;
+		}
+	});
+	if (bad) spans_assemble_host(b, rst2, pool2);        // (a DP call whose own words would merge: the host's word-by-word join)
+}
+
+// step (a) on the device.  MPA_OK: done; MPA_ERR_UNSUPPORTED: the device declined and nothing was changed
+static int spans_assemble_device(mpa_batch_s *b, mpa_ctx_t *ctx, const mpa_dp_rst_t *rst2)
+{
+	std::vector<int64_t> plan0, seg0;
+	spans_counts(b, plan0, seg0);
+	const int64_t n_plan = plan0.back(), n_rst2 = (int64_t)b->tasks.size();
+	SpansAsmIO io;
+	int rc = dev_spans_asm_stage(ctx, n_plan, n_rst2, io);
+	if (rc != MPA_OK) return rc;
+	if (n_rst2 > 0) memcpy(io.rst2, rst2, (size_t)n_rst2 * sizeof(mpa_dp_rst_t));
+	spans_slots(b, plan0, rst2, io.slot_off);
+	rc = dev_spans_assemble(ctx, n_plan, n_rst2, nullptr, rst2 ? b->dp_n_pool : 0, io);
+	if (rc != MPA_OK) return rc;
+	for (int64_t j = 0; j < n_plan; ++j)
+		if (io.rec[j].bad) { set_error("GPU spans: a DP call whose own CIGAR words would merge"); return MPA_ERR_UNSUPPORTED; }
+	b->sp_cig_off.resize((size_t)n_plan);
+	parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
+		QueryState &qs = b->qs[qi];
+		int64_t j = plan0[qi];
+		for (AlignPlan &pl : qs.plans) {
+			asm_apply(pl, qs.regs[pl.reg], io.rec[j], io.cigar + io.rec[j].cig_off, rst2);
+			b->sp_cig_off[(size_t)j] = io.rec[j].cig_off;
+			++j;
+		}
+	});
+	return MPA_OK;
+}
+
+// MPA_SPANS_DUMP=<file> (diagnostics; the tests' view of the two steps): what they left in every query's state, appended batch after
+// batch in query and plan order before stage_finish reorders the regions, whichever path produced it.  Per query: int32 qid, plans.
+// Per plan 184 bytes -- int32 l_nt, l_aa, r_nt, r_aa, flags (1 left span, 2 right span, 4 / 8 the left / right
+// terminal-exon repeat counted, 16 a segment boundary merged), qs, qe, dp_score, n_exon, n_cigar; int64 vs,
+// ve; the left and the right span segment (24 bytes each: int32 ne0, ne1, ae0, ae1, task, score; zeros with task -1 for a right span
+// that was not made); their round-2 task records (mpa_dp_task_t, 40 bytes each; zeros for a shortcut) -- then the n_cigar words.
+// Layout and parser: tests/spansdump.py
+static void spans_dump(const mpa_batch_s *b)
+{
+	if (!spans_dump_on()) return;
+	static std::mutex mu;                                // (batches of a stream finish side by side: one writer at a time)
+	std::lock_guard<std::mutex> g(mu);
+	FILE *fp = fopen(getenv("MPA_SPANS_DUMP"), "ab");
+	if (!fp) return;
+	for (const QueryState &qs : b->qs) {
+		const int32_t head[2] = { qs.qid, (int32_t)qs.plans.size() };
+		fwrite(head, 4, 2, fp);
+		for (const AlignPlan &pl : qs.plans) {
+			const Region &r = qs.regs[pl.reg];
+			const SpanRec R = span_rec_of(pl, r);
+			const int32_t w[10] = { R.l_nt, R.l_aa, R.r_nt, R.r_aa, R.flags | (pl.n_merged > 0 ? 16 : 0), r.qs, r.qe, r.dp_score, r.n_exon, (int32_t)r.cigar.size() };
+			const int64_t v[2] = { r.vs, r.ve };
+			mpa_dp_task_t t[2];
+			memset(t, 0, sizeof t);
+			if (R.left.task >= 0 && (size_t)R.left.task < b->tasks.size()) t[0] = b->tasks[(size_t)R.left.task];
+			if (R.right.task >= 0 && (size_t)R.right.task < b->tasks.size()) t[1] = b->tasks[(size_t)R.right.task];
+			fwrite(w, 4, 10, fp), fwrite(v, 8, 2, fp), fwrite(&R.left, sizeof(SegRec), 1, fp), fwrite(&R.right, sizeof(SegRec), 1, fp), fwrite(t, sizeof(mpa_dp_task_t), 2, fp);
+			if (!r.cigar.empty()) fwrite(r.cigar.data(), 4, r.cigar.size(), fp);
+		}
+	}
+	fclose(fp);
+}
+
 static int take_round3_steps(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint32_t *pool);
 // MPA_OK, or the error of a device call that failed (a call that merely declines leaves the batch to the host walk)
 static int take_round3(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint32_t *pool)
@@ -1239,7 +1555,7 @@ static int take_round3_steps(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint
 	if (cs == STATS_DEVICE && !b->dp_ctx) cs = STATS_HOST;
 	StatsMode rows = rows_printed(b->opt) ? aln_rows_mode() : STATS_HOST;
 	if (rows == STATS_DEVICE && !b->dp_ctx) rows = STATS_HOST;
-	if (mode == STATS_HOST && cs == STATS_HOST && rows == STATS_HOST) {   // the three steps in one pass over the queries
+	if (mode == STATS_HOST && cs == STATS_HOST && rows == STATS_HOST && b->spans_src == 0 && !spans_dump_on()) {   // the three steps in one pass over the queries
 		parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
 			QueryState &qs = b->qs[qi];
 			for (AlignPlan &pl : qs.plans) {
@@ -1251,7 +1567,10 @@ static int take_round3_steps(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint
 		});
 		return MPA_OK;
 	}
-	parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {      // (a)
+	b->sp_cig_off.clear();
+	bool any_plan = false;
+	for (const QueryState &qs : b->qs) any_plan = any_plan || !qs.plans.empty();
+	if (b->spans_src == 0 || !any_plan) parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {      // (a)
 		QueryState &qs = b->qs[qi];
 		for (AlignPlan &pl : qs.plans) {
 			Region &r = qs.regs[pl.reg];
@@ -1259,6 +1578,21 @@ static int take_round3_steps(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint
 			r.n_exon = count_exons(r);
 		}
 	});
+	else if (b->spans_src == 1) {                                          // (a) through the shared core: round 1 left no gap words in the plans
+		const double t1 = now_ms();
+		spans_assemble_model(b, rst, pool);
+		timing_note("spans: shared core", now_ms() - t1);
+	} else {                                                               // (a) on the device
+		const double t1 = now_ms();
+		const int rc = b->dp_ctx ? spans_assemble_device(b, b->dp_ctx, rst) : MPA_ERR_UNSUPPORTED;
+		if (rc == MPA_OK) timing_note("spans on the GPU", now_ms() - t1);
+		else if (rc != MPA_ERR_UNSUPPORTED) return rc;
+		else {
+			if (timing_on()) fprintf(stderr, "[mpa-timing]   device spans declined (%s): region CIGARs on the host\n", mpa_last_error());
+			b->sp_cig_off.clear();
+			spans_assemble_host(b, rst, pool);
+		}
+	}
 	const double t0 = now_ms();                                            // (b)
 	auto stats_host_all = [&]() {
 		parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
@@ -1316,6 +1650,7 @@ static int take_round3_steps(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint
 			if (rows_dev) fprintf(stderr, "[mpa-timing]   device residue rows declined (%s): the formatter builds them\n", mpa_last_error());
 		}
 	}
+	spans_dump(b);
 	parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) { stage_finish(b, b->qs[qi]); });   // (c)
 	return MPA_OK;
 }
@@ -2280,7 +2615,7 @@ int64_t mpa_batch_dp_tasks(mpa_batch_t *b, const mpa_dp_task_t **tasks, mpa_dpop
 static int mpa_batch_dp_results_impl(mpa_batch_t *b, const mpa_dp_rst_t *rst, const uint32_t *cigar_pool)
 {
 	double t0 = now_ms();
-	if (b->round == 1) { take_round1_emit_round2(b, rst, cigar_pool); b->round = 2; timing_note("take 1 / emit 2", now_ms() - t0); }
+	if (b->round == 1) { const int rc = spans_take_round1(b, rst, cigar_pool); if (rc != MPA_OK) return rc; b->round = 2; timing_note("take 1 / emit 2", now_ms() - t0); }
 	else if (b->round == 2) {
 		const int rc = take_round3(b, rst, cigar_pool);
 		if (rc != MPA_OK) return rc;
@@ -2374,7 +2709,9 @@ static int run_dp_rounds(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_qbatch_t
 		int rc = mpa_dp_run(ctx, mi, &dpopt, q, n, tasks, rst.data(), &pool, &n_pool);
 		timing_note("mpa_dp_run (total)", now_ms() - t0);
 		if (rc != MPA_OK) { free(pool); return rc; }
+		b->dp_n_pool = n_pool;           // (MPA_GPU_SPANS=1: the round's dense pool is still on the context)
 		rc = mpa_batch_dp_results(b, rst.data(), pool);
+		if (b->spans_want_pool) b->sp_pool1 = pool, pool = nullptr, b->spans_want_pool = false;   // (round 1's words stay with the batch: a declined step behind round 2 reads them)
 		free(pool);
 		if (rc != MPA_OK) return rc;
 	}

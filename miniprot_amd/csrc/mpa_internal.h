@@ -15,6 +15,7 @@
 #include "aln_rows_core.h"
 #include "regions_core.h"
 #include "plans_core.h"
+#include "spans_core.h"
 
 namespace mpa {
 
@@ -257,7 +258,7 @@ int dev_sketch_fetch(mpa_ctx_t *ctx, int64_t n_jobs, SeedJob *jobs, int32_t *buc
 struct AlnStatsIO { AlnStatsJob *jobs = nullptr; uint32_t *cigar = nullptr; char *text = nullptr; const AlnStatsOut *out = nullptr; const AlnFeat *feat = nullptr; };
 int dev_aln_stats_stage(mpa_ctx_t *ctx, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat, AlnStatsIO &io);
 int dev_aln_stats(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const int8_t *mat, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat,
-                  AlnStatsIO &io);
+                  AlnStatsIO &io, bool dev_cig = false);
 // ---- cs:Z: difference strings and --aln / --trans residue rows on the device (MPA_GPU_CS=1, MPA_GPU_ROWS=1; driver: stats_run.hip;
 // code: aln_cs_core.h, aln_rows_core.h) ----
 // The same two steps with a slot per alignment and walk.  slot_bytes = the sum of aln_cs_bound() over the staged alignments (< 0: no cs
@@ -270,6 +271,26 @@ struct AlnRowsIO { int64_t *slot_off = nullptr; const AlnRowsOut *out = nullptr;
 int dev_aln_walks_stage(mpa_ctx_t *ctx, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat, int64_t slot_bytes, int64_t rows_bytes, AlnStatsIO &io, AlnCsIO &cs,
                         AlnRowsIO &rows);
 int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const AlnRowsParams &rp, const int8_t *mat, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes,
-                  int64_t n_feat, int64_t slot_bytes, int64_t rows_bytes, AlnStatsIO &io, AlnCsIO &cs, AlnRowsIO &rows);
+                  int64_t n_feat, int64_t slot_bytes, int64_t rows_bytes, AlnStatsIO &io, AlnCsIO &cs, AlnRowsIO &rows, bool dev_cig = false);
+
+// ---- accepted spans and region CIGARs on the device (MPA_GPU_SPANS=1; driver: stats_run.hip; kernels: span_kernels.hip; code:
+// spans_core.h) ----
+// Between the rounds: dev_spans_stage sizes the context's pinned block and hands out where the caller writes the batch's plans, gap
+// segments, round-1 results and protein text; dev_spans_round1 runs k_spans / k_spans_emit and leaves rec[n_plan], the n_task round-2
+// tasks and keeps the round-1 CIGAR pool on the device -- pool1 == nullptr: a device-to-device copy of the n_pool1 words the last
+// mpa_dp_run on this context left (before the next one overwrites them); otherwise the caller's words go up.
+// Behind round 2: dev_spans_asm_stage hands out where the round-2 results and the slot offsets (slot_off[n_plan + 1], in words) go;
+// dev_spans_assemble runs k_assemble on what round 1 left and, for pool2 == nullptr, the pool of the last mpa_dp_run, and leaves
+// rec[n_plan] and the slots' words in pinned memory (valid until the context's next call); the words also stay on the device for
+// dev_aln_stats / dev_aln_walks (dev_cig).  MPA_ERR_UNSUPPORTED from any of them: a pool or pinned block could not grow -- the caller
+// keeps the host step.
+struct SpansIO { SpansPlan *plan = nullptr; SegRec *seg = nullptr; mpa_dp_rst_t *rst1 = nullptr; char *text = nullptr;
+                 const SpanRec *rec = nullptr; const mpa_dp_task_t *task = nullptr; int32_t n_task = 0; };
+int dev_spans_stage(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_seg, int64_t n_rst1, int64_t text_bytes, SpansIO &io);
+int dev_spans_round1(mpa_ctx_t *ctx, mpa_idx_s *mi, const SpansParams &p, const int8_t *mat, int64_t n_plan, int64_t n_seg, int64_t n_rst1, int64_t text_bytes,
+                     const uint32_t *pool1, int64_t n_pool1, SpansIO &io);
+struct SpansAsmIO { mpa_dp_rst_t *rst2 = nullptr; int64_t *slot_off = nullptr; const AsmRec *rec = nullptr; const uint32_t *cigar = nullptr; };
+int dev_spans_asm_stage(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, SpansAsmIO &io);
+int dev_spans_assemble(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, const uint32_t *pool2, int64_t n_pool2, SpansAsmIO &io);
 
 } // namespace mpa

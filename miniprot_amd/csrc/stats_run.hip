@@ -11,8 +11,14 @@
 // dev_aln_walks() take any of statistics, cs strings and residue rows in one call -- one upload (tables | jobs | cs slot offsets | rows
 // slot offsets | CIGAR words | protein text), up to three launches, one pinned block down each, one wait.  The rows' block (records |
 // slots: rows_out and its staging) is allocated by the first call that asks for rows.
+// MPA_GPU_SPANS=1 (kernels k_spans, k_spans_emit, k_assemble: span_kernels.hip; code: spans_core.h) puts the
+// host step between the DP rounds and the one behind them here: dev_spans_stage() / dev_spans_round1() and dev_spans_asm_stage() /
+// dev_spans_assemble().  The CIGAR pool k_assemble writes (sp_cig) stays on the device until the context's next call, and
+// dev_aln_stats() / dev_aln_walks() read it in place of an uploaded one when the caller says so (dev_cig).
 #include "dev_ctx.h"
+#include "spans_core.h"
 #include "stats_kernels.hip"
+#include "span_kernels.hip"
 
 namespace mpa {
 
@@ -56,8 +62,9 @@ int dev_aln_stats_stage(mpa_ctx_t *ctx, int64_t n_jobs, int64_t n_cigar, int64_t
 // What dev_aln_stats() and dev_aln_walks() share: the tables into the staged block, one upload, the launches asked for (stats:
 // k_aln_stats; cs: k_aln_cs; rows: k_aln_rows), their downloads and one wait.
 static int stats_walks_run(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const int8_t *mat, int64_t n_jobs, const StatsLayout &L, bool stats, AlnStatsIO &io, AlnCsIO *cs,
-                           const AlnRowsParams *rp = nullptr, AlnRowsIO *rows = nullptr)
+                           const AlnRowsParams *rp = nullptr, AlnRowsIO *rows = nullptr, bool dev_cig = false)
 {
+	if (dev_cig && !ctx->sp_cig.p) { set_error("dev_aln_stats: no assembled CIGAR pool on this context"); return MPA_ERR_ARG; }
 	if (p.asize < 1 || p.asize * p.asize > 484) { set_error("GPU alignment statistics: a substitution matrix of more than 22 x 22"); return MPA_ERR_UNSUPPORTED; }
 	HIP_TRY(hipSetDevice(ctx->device));
 	if (dev_upload_index(ctx, mi) != MPA_OK) return MPA_ERR_HIP;
@@ -79,11 +86,12 @@ static int stats_walks_run(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &
 	memcpy(hu + ALN_TAB_MAT, mat, (size_t)(p.asize * p.asize));
 	HIP_TRY(hipMemcpyAsync(ctx->st_in.p, hu, L.up_bytes - 16, hipMemcpyHostToDevice, s));
 	const char *din = ctx->st_in.as<char>();
+	const uint32_t *dcig = dev_cig ? ctx->sp_cig.as<uint32_t>() : (const uint32_t*)(din + L.off_cig);   // (MPA_GPU_SPANS=1: where k_assemble left the words)
 	const unsigned nwg = (unsigned)((n_jobs + STATS_WAVES - 1) / STATS_WAVES);
 	if (stats) {
 		char *dout = ctx->st_out.as<char>();
 		hipLaunchKernelGGL(k_aln_stats, dim3(nwg), dim3(64 * STATS_WAVES), 0, s, (const AlnStatsJob*)(din + L.off_jobs), (int32_t)n_jobs, (const uint8_t*)din, p,
-		                   (const uint8_t*)(din + L.off_text), (const uint32_t*)(din + L.off_cig), (const uint8_t*)d->seq, (const int64_t*)d->ctg_off, (const int64_t*)d->ctg_len,
+		                   (const uint8_t*)(din + L.off_text), dcig, (const uint8_t*)d->seq, (const int64_t*)d->ctg_off, (const int64_t*)d->ctg_len,
 		                   (AlnStatsOut*)dout, (AlnFeat*)(dout + L.off_feat));
 		HIP_TRY(hipGetLastError());
 		char *hd = ctx->h_stats_down.as<char>();
@@ -93,7 +101,7 @@ static int stats_walks_run(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &
 	if (cs) {
 		char *dout = ctx->cs_out.as<char>();
 		hipLaunchKernelGGL(k_aln_cs, dim3(nwg), dim3(64 * STATS_WAVES), 0, s, (const AlnStatsJob*)(din + L.off_jobs), (int32_t)n_jobs, (const uint8_t*)din,
-		                   (const uint8_t*)(din + L.off_text), (const uint32_t*)(din + L.off_cig), (const uint8_t*)d->seq, (const int64_t*)d->ctg_off, (const int64_t*)d->ctg_len,
+		                   (const uint8_t*)(din + L.off_text), dcig, (const uint8_t*)d->seq, (const int64_t*)d->ctg_off, (const int64_t*)d->ctg_len,
 		                   (const int64_t*)(din + L.off_slot), (AlnCsOut*)dout, dout + L.off_body);
 		HIP_TRY(hipGetLastError());
 		char *hd = ctx->h_cs_down.as<char>();
@@ -103,7 +111,7 @@ static int stats_walks_run(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &
 	if (rows) {
 		char *dout = ctx->rows_out.as<char>();
 		hipLaunchKernelGGL(k_aln_rows, dim3(nwg), dim3(64 * STATS_WAVES), 0, s, (const AlnStatsJob*)(din + L.off_jobs), (int32_t)n_jobs, (const uint8_t*)din, *rp,
-		                   (const uint8_t*)(din + L.off_text), (const uint32_t*)(din + L.off_cig), (const uint8_t*)d->seq, (const int64_t*)d->ctg_off, (const int64_t*)d->ctg_len,
+		                   (const uint8_t*)(din + L.off_text), dcig, (const uint8_t*)d->seq, (const int64_t*)d->ctg_off, (const int64_t*)d->ctg_len,
 		                   (const int64_t*)(din + L.off_rslot), (AlnRowsOut*)dout, dout + L.off_rbody);
 		HIP_TRY(hipGetLastError());
 		char *hd = ctx->h_rows_down.as<char>();
@@ -117,9 +125,9 @@ static int stats_walks_run(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &
 // The statistics and features of the n_jobs alignments staged in io, on ctx.  io.out / io.feat point into pinned memory of the
 // context afterwards, valid until its next call.  MPA_ERR_UNSUPPORTED: a pool could not grow -- the caller runs the host stage.
 int dev_aln_stats(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const int8_t *mat, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat,
-                  AlnStatsIO &io)
+                  AlnStatsIO &io, bool dev_cig)
 {
-	return stats_walks_run(ctx, mi, p, mat, n_jobs, StatsLayout(n_jobs, n_cigar, text_bytes, n_feat), true, io, nullptr);
+	return stats_walks_run(ctx, mi, p, mat, n_jobs, StatsLayout(n_jobs, n_cigar, text_bytes, n_feat), true, io, nullptr, nullptr, nullptr, dev_cig);
 }
 
 // The same for a call that writes cs strings, residue rows or both: slot_bytes = the sum of the alignments' aln_cs_bound() (< 0: no cs
@@ -148,10 +156,150 @@ int dev_aln_walks_stage(mpa_ctx_t *ctx, int64_t n_jobs, int64_t n_cigar, int64_t
 // statistics as dev_aln_stats() leaves them, behind one upload and one wait.  All of it is pinned memory of the context, valid until
 // its next call.  MPA_ERR_UNSUPPORTED: a pool could not grow -- the caller keeps the host's walks.
 int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const AlnRowsParams &rp, const int8_t *mat, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes,
-                  int64_t n_feat, int64_t slot_bytes, int64_t rows_bytes, AlnStatsIO &io, AlnCsIO &cs, AlnRowsIO &rows)
+                  int64_t n_feat, int64_t slot_bytes, int64_t rows_bytes, AlnStatsIO &io, AlnCsIO &cs, AlnRowsIO &rows, bool dev_cig)
 {
 	return stats_walks_run(ctx, mi, p, mat, n_jobs, StatsLayout(n_jobs, n_cigar, text_bytes, n_feat < 0 ? 0 : n_feat, slot_bytes, rows_bytes), n_feat >= 0, io,
-	                       slot_bytes >= 0 ? &cs : nullptr, &rp, rows_bytes >= 0 ? &rows : nullptr);
+	                       slot_bytes >= 0 ? &cs : nullptr, &rp, rows_bytes >= 0 ? &rows : nullptr, dev_cig);
+}
+
+// ---- MPA_GPU_SPANS=1 ------------------------------------------------------------------------------------------------------------
+namespace {
+struct SpansLayout {
+	size_t off_plan, off_seg, off_rst1, off_text, up_bytes;                  // sp_in / h_sp_up (the tables take the first KB)
+	size_t off_tmp, off_excl, off_bsum, mid_bytes;                            // sp_mid (records with local numbers at 0)
+	size_t off_rec, off_task, down_bytes;                                     // sp_out / h_sp_down (the task count at 0)
+	unsigned blocks;
+	SpansLayout(int64_t n_plan, int64_t n_seg, int64_t n_rst1, int64_t text_bytes)
+	{
+		auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+		blocks = (unsigned)((n_plan + SPANS_BLOCK - 1) / SPANS_BLOCK);
+		off_plan = 1024;
+		off_seg = off_plan + up16((size_t)n_plan * sizeof(SpansPlan));
+		off_rst1 = off_seg + up16((size_t)n_seg * sizeof(SegRec));
+		off_text = off_rst1 + up16((size_t)n_rst1 * sizeof(mpa_dp_rst_t));
+		up_bytes = off_text + up16((size_t)text_bytes) + 16;
+		off_tmp = up16((size_t)n_plan * sizeof(SpanRec));
+		off_excl = off_tmp + up16((size_t)n_plan * 2 * sizeof(mpa_dp_task_t));
+		off_bsum = off_excl + up16((size_t)n_plan * 4);
+		mid_bytes = off_bsum + up16((size_t)blocks * 4) + 16;
+		off_rec = 16;
+		off_task = off_rec + up16((size_t)n_plan * sizeof(SpanRec));
+		down_bytes = off_task + (size_t)n_plan * 2 * sizeof(mpa_dp_task_t) + 16;
+	}
+};
+struct AsmLayout {
+	size_t off_slot, off_pool2, up_bytes, rec_bytes;
+	AsmLayout(int64_t n_plan, int64_t n_rst2, int64_t n_pool2)
+	{
+		auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+		off_slot = up16((size_t)n_rst2 * sizeof(mpa_dp_rst_t));
+		off_pool2 = off_slot + up16((size_t)(n_plan + 1) * 8);
+		up_bytes = off_pool2 + up16((size_t)n_pool2 * 4) + 16;
+		rec_bytes = up16((size_t)n_plan * sizeof(AsmRec));
+	}
+};
+static_assert(sizeof(SpansPlan) % 8 == 0 && sizeof(SpanRec) % 8 == 0 && sizeof(AsmRec) % 8 == 0, "records in 16-byte aligned sections");
+}
+
+int dev_spans_stage(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_seg, int64_t n_rst1, int64_t text_bytes, SpansIO &io)
+{
+	io = SpansIO();
+	if (n_plan <= 0 || n_plan > (int64_t)1 << 28 || n_seg < 0 || n_rst1 <= 0) { set_error("GPU spans: no plans, or too many for one launch"); return MPA_ERR_UNSUPPORTED; }
+	if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return MPA_ERR_HIP; }
+	const SpansLayout L(n_plan, n_seg, n_rst1, text_bytes);
+	if (ctx->h_sp_up.ensure(L.up_bytes) != MPA_OK || ctx->h_sp_down.ensure(L.down_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
+	char *hu = ctx->h_sp_up.as<char>();
+	io.plan = (SpansPlan*)(hu + L.off_plan), io.seg = (SegRec*)(hu + L.off_seg), io.rst1 = (mpa_dp_rst_t*)(hu + L.off_rst1), io.text = hu + L.off_text;
+	return MPA_OK;
+}
+
+int dev_spans_round1(mpa_ctx_t *ctx, mpa_idx_s *mi, const SpansParams &p, const int8_t *mat, int64_t n_plan, int64_t n_seg, int64_t n_rst1, int64_t text_bytes,
+                     const uint32_t *pool1, int64_t n_pool1, SpansIO &io)
+{
+	ctx->sp_keep.n_plan = -1;
+	if (p.asize < 1 || p.asize * p.asize > 484) { set_error("GPU spans: a substitution matrix of more than 22 x 22"); return MPA_ERR_UNSUPPORTED; }
+	HIP_TRY(hipSetDevice(ctx->device));
+	if (dev_upload_index(ctx, mi) != MPA_OK) return MPA_ERR_HIP;
+	const DeviceIndex *d = mi->dev[ctx->device];
+	const SpansLayout L(n_plan, n_seg, n_rst1, text_bytes);
+	if (L.up_bytes > ctx->h_sp_up.cap || L.down_bytes > ctx->h_sp_down.cap) { set_error("dev_spans_round1: the staging block was not sized for this call"); return MPA_ERR_ARG; }
+	if (n_pool1 < 0 || (!pool1 && n_pool1 > 0 && (size_t)n_pool1 * 4 > ctx->cigd.cap)) { set_error("dev_spans_round1: no round-1 CIGAR pool of that size on this context"); return MPA_ERR_ARG; }
+	tl_alloc_failed = false;
+	if (ctx->sp_in.ensure(L.up_bytes) != MPA_OK || ctx->sp_mid.ensure(L.mid_bytes) != MPA_OK || ctx->sp_out.ensure(L.down_bytes) != MPA_OK ||
+	    ctx->sp_pool1.ensure((size_t)n_pool1 * 4 + 16) != MPA_OK)
+		return tl_alloc_failed ? MPA_ERR_UNSUPPORTED : MPA_ERR_HIP;
+	hipStream_t s = ctx->stream;
+	char *hu = ctx->h_sp_up.as<char>();
+	memcpy(hu + ALN_TAB_CODON, tab_codon(), 64);
+	memcpy(hu + ALN_TAB_AA20, tab_aa20(), 256);
+	memset(hu + ALN_TAB_MAT, 0, 484);
+	memcpy(hu + ALN_TAB_MAT, mat, (size_t)(p.asize * p.asize));
+	HIP_TRY(hipMemcpyAsync(ctx->sp_in.p, hu, L.up_bytes - 16, hipMemcpyHostToDevice, s));
+	// the round-1 pool stays: round 2 overwrites cigd
+	if (n_pool1 > 0) HIP_TRY(hipMemcpyAsync(ctx->sp_pool1.p, pool1 ? (const void*)pool1 : ctx->cigd.p, (size_t)n_pool1 * 4, pool1 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+	const char *din = ctx->sp_in.as<char>();
+	char *mid = ctx->sp_mid.as<char>(), *dout = ctx->sp_out.as<char>();
+	SpansArgs a;
+	a.plan = (const SpansPlan*)(din + L.off_plan), a.n_plan = (int32_t)n_plan, a.rst1 = (const mpa_dp_rst_t*)(din + L.off_rst1);
+	a.text = (const uint8_t*)(din + L.off_text), a.tabs = (const uint8_t*)din, a.seq = (const uint8_t*)d->seq, a.ctg_off = d->ctg_off, a.ctg_len = d->ctg_len;
+	a.p = p, a.rec = (SpanRec*)mid, a.tmp = (mpa_dp_task_t*)(mid + L.off_tmp), a.excl = (int32_t*)(mid + L.off_excl), a.bsum = (int32_t*)(mid + L.off_bsum);
+	hipLaunchKernelGGL(k_spans, dim3(L.blocks), dim3(SPANS_BLOCK), 0, s, a);
+	HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(k_spans_emit, dim3(L.blocks), dim3(SPANS_BLOCK), 0, s, a, (int32_t*)dout, (SpanRec*)(dout + L.off_rec), (mpa_dp_task_t*)(dout + L.off_task));
+	HIP_TRY(hipGetLastError());
+	char *hd = ctx->h_sp_down.as<char>();
+	HIP_TRY(hipMemcpyAsync(hd, dout, L.down_bytes - 16, hipMemcpyDeviceToHost, s));
+	HIP_TRY(wait_stream(ctx, s));
+	io.n_task = *(const int32_t*)hd, io.rec = (const SpanRec*)(hd + L.off_rec), io.task = (const mpa_dp_task_t*)(hd + L.off_task);
+	if (io.n_task < 0 || io.n_task > 2 * n_plan) { set_error("dev_spans_round1: an impossible task count"); return MPA_ERR_HIP; }
+	ctx->sp_keep.off_plan = L.off_plan, ctx->sp_keep.off_seg = L.off_seg, ctx->sp_keep.off_rst1 = L.off_rst1, ctx->sp_keep.n_plan = n_plan, ctx->sp_keep.n_pool1 = n_pool1;
+	return MPA_OK;
+}
+
+int dev_spans_asm_stage(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, SpansAsmIO &io)
+{
+	io = SpansAsmIO();
+	if (n_plan <= 0 || n_plan != ctx->sp_keep.n_plan || n_rst2 < 0) { set_error("GPU spans: the plans of this batch are not on the device"); return MPA_ERR_UNSUPPORTED; }
+	if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return MPA_ERR_HIP; }
+	const AsmLayout L(n_plan, n_rst2, 0);
+	if (ctx->h_sp_up2.ensure(L.up_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
+	char *hu = ctx->h_sp_up2.as<char>();
+	io.rst2 = (mpa_dp_rst_t*)hu, io.slot_off = (int64_t*)(hu + L.off_slot);
+	return MPA_OK;
+}
+
+int dev_spans_assemble(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, const uint32_t *pool2, int64_t n_pool2, SpansAsmIO &io)
+{
+	if (n_plan <= 0 || n_plan != ctx->sp_keep.n_plan) { set_error("dev_spans_assemble: the plans of this batch are not on the device"); return MPA_ERR_ARG; }
+	HIP_TRY(hipSetDevice(ctx->device));
+	const AsmLayout L0(n_plan, n_rst2, 0), L(n_plan, n_rst2, pool2 ? n_pool2 : 0);
+	if (L0.up_bytes > ctx->h_sp_up2.cap || !io.slot_off) { set_error("dev_spans_assemble: the staging block was not sized for this call"); return MPA_ERR_ARG; }
+	if (n_pool2 < 0 || (!pool2 && n_pool2 > 0 && (size_t)n_pool2 * 4 > ctx->cigd.cap)) { set_error("dev_spans_assemble: no round-2 CIGAR pool of that size on this context"); return MPA_ERR_ARG; }
+	const int64_t n_words = io.slot_off[n_plan];
+	if (n_words < 0) { set_error("dev_spans_assemble: negative slot offsets"); return MPA_ERR_ARG; }
+	const size_t down_bytes = L.rec_bytes + (size_t)n_words * 4 + 16;
+	if (ctx->h_sp_down2.ensure(down_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
+	tl_alloc_failed = false;
+	if (ctx->sp_in2.ensure(L.up_bytes) != MPA_OK || ctx->sp_asm.ensure(L.rec_bytes + 16) != MPA_OK || ctx->sp_cig.ensure((size_t)n_words * 4 + 16) != MPA_OK)
+		return tl_alloc_failed ? MPA_ERR_UNSUPPORTED : MPA_ERR_HIP;
+	hipStream_t s = ctx->stream;
+	HIP_TRY(hipMemcpyAsync(ctx->sp_in2.p, ctx->h_sp_up2.p, L0.up_bytes - 16, hipMemcpyHostToDevice, s));
+	char *din2 = ctx->sp_in2.as<char>();
+	if (pool2 && n_pool2 > 0) HIP_TRY(hipMemcpyAsync(din2 + L.off_pool2, pool2, (size_t)n_pool2 * 4, hipMemcpyHostToDevice, s));
+	const char *din = ctx->sp_in.as<char>();
+	AsmArgs a;
+	a.plan = (const SpansPlan*)(din + ctx->sp_keep.off_plan), a.rec = (const SpanRec*)(ctx->sp_out.as<char>() + 16), a.n_plan = (int32_t)n_plan;
+	a.gap = (const SegRec*)(din + ctx->sp_keep.off_seg), a.rst1 = (const mpa_dp_rst_t*)(din + ctx->sp_keep.off_rst1), a.rst2 = (const mpa_dp_rst_t*)din2;
+	a.pool1 = ctx->sp_pool1.as<uint32_t>(), a.pool2 = pool2 ? (const uint32_t*)(din2 + L.off_pool2) : ctx->cigd.as<uint32_t>();
+	a.slot_off = (const int64_t*)(din2 + L.off_slot), a.cig = ctx->sp_cig.as<uint32_t>(), a.out = ctx->sp_asm.as<AsmRec>();
+	hipLaunchKernelGGL(k_assemble, dim3((unsigned)((n_plan + STATS_WAVES - 1) / STATS_WAVES)), dim3(64 * STATS_WAVES), 0, s, a);
+	HIP_TRY(hipGetLastError());
+	char *hd = ctx->h_sp_down2.as<char>();
+	HIP_TRY(hipMemcpyAsync(hd, ctx->sp_asm.p, (size_t)n_plan * sizeof(AsmRec), hipMemcpyDeviceToHost, s));
+	if (n_words > 0) HIP_TRY(hipMemcpyAsync(hd + L.rec_bytes, ctx->sp_cig.p, (size_t)n_words * 4, hipMemcpyDeviceToHost, s));
+	HIP_TRY(wait_stream(ctx, s));
+	io.rec = (const AsmRec*)hd, io.cigar = (const uint32_t*)(hd + L.rec_bytes);
+	return MPA_OK;
 }
 
 } // namespace mpa
