@@ -198,7 +198,8 @@ void ensure_seed_stream(mpa_ctx_t *ctx);                                        
 hipError_t ensure_dynamic_lds(const void *fn, int device, size_t bytes);                 // hipFuncSetAttribute(MaxDynamicSharedMemorySize), once per (kernel, device)
 void ctx_pool_report(mpa_ctx_t *root);
 void pool_harvest(mpa_ctx_t *ctx, bool wait);                                            // (dp_exec.hip) the finished worker launches of a context's DP pool
-// (stats_run.hip: dev_aln_stats_stage / dev_aln_stats are declared in mpa_internal.h, where the host pipeline that calls them sees them)
+// (stats_run.hip: dev_aln_walks_stage / dev_aln_walks and the dev_spans_* calls are declared in mpa_internal.h, where the host pipeline that
+// calls them sees them)
 
 // ---- the chain tail (seed_run.hip): what the three device chaining routes -- behind the pre-chain (dev_chains_on_device), without one
 // (dev_seed_direct) and the refinement (dev_refine_chains) -- do alike, and the forward pass dev_chain_forward shares with them

@@ -30,7 +30,7 @@ static inline uint8_t codon_aa3(const uint8_t *nt)
 }
 
 // the cs:Z: difference string (format.c:102-187)
-// (the body alone: what follows "cs:Z:" -- also what MPA_CS_DUMP records for a region that carries none, host_map.cpp)
+// (the body alone: what follows "cs:Z:" -- also what MPA_CS_DUMP records for a region that carries none, host_align.cpp)
 void put_cs_body(std::string &s, const mpa_idx_s *mi, const char *aa, int32_t vid, int64_t vs, int64_t ve, const uint32_t *cig, int32_t n_cigar)
 {
 	static const char lc[] = "acgtn";

@@ -30,6 +30,16 @@ extern const uint8_t *tab_codon13(); // [64]  codon -> reduced alphabet
 extern const int8_t *blosum62();     // [484]
 int set_trans_code(int code);        // ns_make_tables (nasw-tab.c:85); returns <0 if undefined
 extern const char *const kAA;        // "ARNDCQEGHILKMFPSTWYV*X"
+// the tables the shared walks read (ALN_TAB_*, aln_stats_core.h) into dst[ALN_TAB_BYTES]: codon table, aa20 and the first mat_bytes of
+// the substitution matrix, zeros behind them.  The host's models pass all 484 bytes of opt.mat, as the host walks index it; the
+// device calls pass asize * asize
+static inline void aln_tables_fill(uint8_t *dst, const int8_t *mat, size_t mat_bytes)
+{
+	memcpy(dst + ALN_TAB_CODON, tab_codon(), 64);
+	memcpy(dst + ALN_TAB_AA20, tab_aa20(), 256);
+	memset(dst + ALN_TAB_MAT, 0, 484);
+	memcpy(dst + ALN_TAB_MAT, mat, mat_bytes);
+}
 
 void set_error(const std::string &msg);
 // no C++ exception may cross the C ABI: the extern "C" entry points run their bodies through this
@@ -251,27 +261,24 @@ struct SketchResult {
 int dev_sketch_jobs(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t max_occ, const mpa_qbatch_t *q, SketchResult &out);
 int dev_sketch_fetch(mpa_ctx_t *ctx, int64_t n_jobs, SeedJob *jobs, int32_t *bucket);   // test hook: the jobs the last sketch left, and their buckets
 
-// ---- alignment statistics on the device (driver: stats_run.hip; code: aln_stats_core.h) -----------
-// dev_aln_stats_stage sizes the context's pinned block for a call and hands out where the caller writes its jobs, CIGAR words and
-// protein text; dev_aln_stats runs them and leaves out[n_jobs] / feat[n_feat] in pinned memory of the context (valid until its next
-// call).  MPA_ERR_UNSUPPORTED from either: the device declines (a pool could not grow) and the caller keeps the host stage.
+// ---- the walks over the finished alignments on the device: statistics (MPA_GPU_STATS=1; aln_stats_core.h), cs:Z: difference strings
+// (MPA_GPU_CS=1; aln_cs_core.h) and --aln / --trans residue rows (MPA_GPU_ROWS=1; aln_rows_core.h).  Driver: stats_run.hip ----
+// One call takes any non-empty subset of the three.  Its sizes: n_cigar = the CIGAR words that go up (0 with dev_cig); n_feat = the
+// feature slots (< 0: no statistics in this call); slot_bytes = the sum of aln_cs_bound() over the alignments (< 0: no cs strings);
+// rows_bytes = the sum of aln_rows_slot() (< 0: no rows).
+// dev_aln_walks_stage sizes the context's pinned blocks for the call and hands out where the caller writes its jobs, CIGAR words,
+// protein text and, next to the jobs, cs.slot_off[n_jobs + 1] / rows.slot_off[n_jobs + 1]; dev_aln_walks sends them up, launches the
+// kernels asked for and waits once.  Afterwards io.out[n_jobs] / io.feat[n_feat] hold the statistics, cs.body + cs.slot_off[j] holds
+// cs.out[j].len bytes, and rows.body + rows.slot_off[j] the slot aln_rows_core.h describes with rows.out[j] (all pinned memory of the
+// context, valid until its next call).  MPA_ERR_UNSUPPORTED from either: the device declines (a pool or pinned block could not grow)
+// and the caller keeps the host's walks.
+struct AlnWalkSizes { int64_t n_jobs, n_cigar, text_bytes, n_feat, slot_bytes, rows_bytes; };
 struct AlnStatsIO { AlnStatsJob *jobs = nullptr; uint32_t *cigar = nullptr; char *text = nullptr; const AlnStatsOut *out = nullptr; const AlnFeat *feat = nullptr; };
-int dev_aln_stats_stage(mpa_ctx_t *ctx, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat, AlnStatsIO &io);
-int dev_aln_stats(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const int8_t *mat, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat,
-                  AlnStatsIO &io, bool dev_cig = false);
-// ---- cs:Z: difference strings and --aln / --trans residue rows on the device (MPA_GPU_CS=1, MPA_GPU_ROWS=1; driver: stats_run.hip;
-// code: aln_cs_core.h, aln_rows_core.h) ----
-// The same two steps with a slot per alignment and walk.  slot_bytes = the sum of aln_cs_bound() over the staged alignments (< 0: no cs
-// strings in this call), rows_bytes = the sum of aln_rows_slot() (< 0: no rows); cs.slot_off[n_jobs + 1] / rows.slot_off[n_jobs + 1] are
-// filled next to the jobs.  Afterwards cs.body + cs.slot_off[j] holds cs.out[j].len bytes, and rows.body + rows.slot_off[j] the slot
-// aln_rows_core.h describes with rows.out[j] (pinned, valid until the context's next call).
-// n_feat >= 0: the statistics run in the same call (io.out / io.feat as from dev_aln_stats); n_feat < 0: without them.
 struct AlnCsIO { int64_t *slot_off = nullptr; const AlnCsOut *out = nullptr; const char *body = nullptr; };
 struct AlnRowsIO { int64_t *slot_off = nullptr; const AlnRowsOut *out = nullptr; const char *body = nullptr; };
-int dev_aln_walks_stage(mpa_ctx_t *ctx, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes, int64_t n_feat, int64_t slot_bytes, int64_t rows_bytes, AlnStatsIO &io, AlnCsIO &cs,
-                        AlnRowsIO &rows);
-int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const AlnRowsParams &rp, const int8_t *mat, int64_t n_jobs, int64_t n_cigar, int64_t text_bytes,
-                  int64_t n_feat, int64_t slot_bytes, int64_t rows_bytes, AlnStatsIO &io, AlnCsIO &cs, AlnRowsIO &rows, bool dev_cig = false);
+int dev_aln_walks_stage(mpa_ctx_t *ctx, const AlnWalkSizes &z, AlnStatsIO &io, AlnCsIO &cs, AlnRowsIO &rows);
+int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const AlnRowsParams &rp, const int8_t *mat, const AlnWalkSizes &z, AlnStatsIO &io, AlnCsIO &cs,
+                  AlnRowsIO &rows, bool dev_cig = false);
 
 // ---- accepted spans and region CIGARs on the device (MPA_GPU_SPANS=1; driver: stats_run.hip; kernels: span_kernels.hip; code:
 // spans_core.h) ----
@@ -282,7 +289,7 @@ int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const 
 // Behind round 2: dev_spans_asm_stage hands out where the round-2 results and the slot offsets (slot_off[n_plan + 1], in words) go;
 // dev_spans_assemble runs k_assemble on what round 1 left and, for pool2 == nullptr, the pool of the last mpa_dp_run, and leaves
 // rec[n_plan] and the slots' words in pinned memory (valid until the context's next call); the words also stay on the device for
-// dev_aln_stats / dev_aln_walks (dev_cig).  MPA_ERR_UNSUPPORTED from any of them: a pool or pinned block could not grow -- the caller
+// dev_aln_walks (dev_cig).  MPA_ERR_UNSUPPORTED from any of them: a pool or pinned block could not grow -- the caller
 // keeps the host step.
 struct SpansIO { SpansPlan *plan = nullptr; SegRec *seg = nullptr; mpa_dp_rst_t *rst1 = nullptr; char *text = nullptr;
                  const SpanRec *rec = nullptr; const mpa_dp_task_t *task = nullptr; int32_t n_task = 0; };

@@ -1,6 +1,6 @@
 // spans_core.h -- the two host steps in the middle of the DP stage as ONE source for the host and the device,
 // like plans_core.h, whose records and pieces it is built from:
-//   spans_accept     between DP round 1 and round 2 (take_round1_emit_round2 of host_map.cpp; align.c:290-300, 324-331): which of an
+//   spans_accept     between DP round 1 and round 2 (take_round1_emit_round2 of host_align.cpp; align.c:290-300, 324-331): which of an
 //                    extension's two calls counts, where the region starts, the two accepted spans as segments -- the ungapped shortcut
 //                    or a round-2 DP task
 //   spans_assemble   behind DP round 2 (assemble_alignment + count_exons; align.c:302-338): the region's CIGAR joined from its

@@ -9,7 +9,7 @@
 using namespace mpa;
 
 namespace {
-// the packed genome as the shared core reads it on the host (StatsGenomeHost of host_map.cpp)
+// the packed genome as the shared core reads it on the host (StatsGenomeHost of host_batch.h)
 struct GenomeHost {
 	const uint8_t *seq;
 	int64_t off, len;

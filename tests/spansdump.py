@@ -1,5 +1,5 @@
 """MPA_SPANS_DUMP=<file>: what the step between the DP rounds (the accepted spans and the round-2 tasks) and step (a) behind them (the
-region CIGARs) left in every query's state, whichever path produced it -- the host functions of host_map.cpp (take_round1_emit_round2,
+region CIGARs) left in every query's state, whichever path produced it -- the host functions of host_align.cpp (take_round1_emit_round2,
 assemble_alignment, count_exons), the shared core on the host (MPA_GPU_SPANS=model) or k_spans / k_assemble on the device
 (MPA_GPU_SPANS=1).  Written before the final selection reorders the regions.
 

@@ -1,6 +1,6 @@
 """The cs:Z: difference strings through the code the device runs (miniprot_amd/csrc/aln_cs_core.h), on the CPU.
 
-MPA_GPU_CS=model makes take_round3() (host_map.cpp) build the body of every aligned region's cs string with the shared core and a
+MPA_GPU_CS=model makes take_round3() (host_align.cpp) build the body of every aligned region's cs string with the shared core and a
 team of one; the region carries it to the result and the formatter pastes it in where it otherwise walks the alignment itself
 (put_cs_body, host_format.cpp).  The stage machine with the oracle as DP executor must still print the reference's bytes, the format
 note must say that every string was carried and none built, and MPA_CS_DUMP must hold the same bodies as the run with the knob unset.

@@ -1,6 +1,6 @@
 """The residue rows of --aln / --trans through the code the device runs (miniprot_amd/csrc/aln_rows_core.h), on the CPU.
 
-MPA_GPU_ROWS=model makes take_round3() (host_map.cpp) build the four rows (##ATN, ##ATA, ##AAS, ##AQA) and the translated target (##STA)
+MPA_GPU_ROWS=model makes take_round3() (host_align.cpp) build the four rows (##ATN, ##ATA, ##AAS, ##AQA) and the translated target (##STA)
 of every aligned region with the shared core and a team of one; the region carries them to the result and the formatter pastes them
 in behind the five prefixes where it otherwise walks the alignment itself (put_residues, host_format.cpp).  The stage machine with the
 oracle as DP executor must still print the reference's bytes, and the format note must say that every row set was carried and none
@@ -160,6 +160,47 @@ def test_cases_cover_what_the_walk_distinguishes(oracle_built, tmp_path, monkeyp
             total[k] = total.get(k, 0) + v
     for k in ("abridged", "whole", "!", "$", "sta_stop", "sta_open", "N"):
         assert total[k] > 0, total
+
+
+WALK_KNOBS = (("MPA_GPU_STATS", "alignment statistics: shared core"), ("MPA_GPU_CS", "cs strings: shared core"), ("MPA_GPU_ROWS", MODEL_NOTE))
+
+
+def test_every_combination_of_the_three_walks_through_their_models(oracle_built, tmp_path, monkeypatch, capfd):
+    """take_round3() decides for each of the three walks behind the last DP round on its own.  syn_a's input with --aln --trans (its
+    options are -u: the row lines are all that --aln --trans add, so the text without them is the golden file) under all eight
+    settings of (MPA_GPU_STATS, MPA_GPU_CS, MPA_GPU_ROWS) in {unset, model}: the bytes of the all-unset run, each walk's note exactly
+    when its knob is `model`, and MPA_CS_DUMP records of source 1 exactly when MPA_GPU_CS=model (0 otherwise)"""
+    import csdump
+    idx, mo, q, ref = alnstats.case_inputs("syn_a", tmp_path)
+    mo.flag |= alnrows.ALN | alnrows.TRANS
+    ex = _memo(oracle_executor)
+    dump = str(tmp_path / "walks.cs")
+    monkeypatch.setenv("MPA_TIMING", "1")
+    monkeypatch.setenv("MPA_CS_DUMP", dump)
+    base = None
+    for k in range(8):
+        on = [bool(k >> i & 1) for i in range(3)]
+        for (knob, _), v in zip(WALK_KNOBS, on):
+            if v:
+                monkeypatch.setenv(knob, "model")
+            else:
+                monkeypatch.delenv(knob, raising=False)
+        if os.path.exists(dump):
+            os.remove(dump)
+        capfd.readouterr()
+        res = map_batch_result(idx, mo, q, ex, n_threads=4)
+        text = mpa.format_output(idx, mo, q, res)[0]
+        err = capfd.readouterr().err
+        recs = csdump.parse(csdump.read(dump))
+        if base is None:
+            base = text
+            assert alnrows.row_sets(text) > 0 and len(recs) > 0
+            assert b"".join(l + b"\n" for l in text.split(b"\n")[:-1] if not (l[:2] == b"##" and l[2:5] in alnrows.KINDS)) == ref
+        assert text == base, on
+        for (knob, note), v in zip(WALK_KNOBS, on):
+            assert (note in err) == v, (on, knob)
+        assert all(int(h["src"]) == (1 if on[1] else 0) for h, _ in recs), on
+    idx.close()
 
 
 def test_core_against_a_plain_walk_under_sanitizers(tmp_path):

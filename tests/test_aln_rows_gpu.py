@@ -108,6 +108,54 @@ def test_with_statistics_and_cs_strings_on_the_device_too(ctx, capfd, tmp_path_f
     assert "alignment statistics on the GPU" in host[1] and "cs strings on the GPU" in host[1]
 
 
+WALKS = (("MPA_GPU_STATS", "alignment statistics on the GPU", None), ("MPA_GPU_CS", "cs strings on the GPU", "cs slots:"), ("MPA_GPU_ROWS", GPU_NOTE, "rows slots:"))
+
+
+def test_every_combination_of_the_three_walks(ctx, capfd, tmp_path):
+    """The walks whose knob is 1 share one device call, whatever the others do.  syn_a's input with --aln --trans (its options are -u:
+    the row lines are all that --aln --trans add, so the text without them is the golden file) on one context under all eight
+    settings of (MPA_GPU_STATS, MPA_GPU_CS, MPA_GPU_ROWS) in {unset, 1} and two mixed ones (model, 1, 1) and (1, model, unset): the
+    bytes and the result arrays of the all-unset run, nothing declined, each walk's note once when its knob is 1 and never otherwise,
+    and its slot line with it"""
+    idx, mo, q, ref = alnstats.case_inputs("syn_a", tmp_path)
+    mo.flag |= alnrows.ALN | alnrows.TRANS
+    idx.to_device(ctx)
+    settings = [tuple("1" if k >> i & 1 else None for i in range(3)) for k in range(8)] + [("model", "1", "1"), ("1", "model", None)]
+    keep = {k: os.environ.get(k) for k in ("MPA_TIMING",) + tuple(w[0] for w in WALKS)}
+    base = None
+    try:
+        os.environ["MPA_TIMING"] = "1"
+        for setting in settings:
+            for (knob, _, _), v in zip(WALKS, setting):
+                if v is None:
+                    os.environ.pop(knob, None)
+                else:
+                    os.environ[knob] = v
+            capfd.readouterr()
+            res = mpa.map_batch(ctx, idx, mo, q, 4)
+            text = mpa.format_output(idx, mo, q, res)[0]
+            arrays = alnstats.result_arrays(res)
+            err = capfd.readouterr().err
+            if base is None:
+                base = (text, arrays)
+                assert alnrows.row_sets(text) > 0
+                assert b"".join(l + b"\n" for l in text.split(b"\n")[:-1] if not (l[:2] == b"##" and l[2:5] in alnrows.KINDS)) == ref
+            assert text == base[0], setting
+            assert alnstats.first_difference(arrays, base[1]) is None, (setting, alnstats.first_difference(arrays, base[1]))
+            assert "declined" not in err, (setting, [l for l in err.split("\n") if "declined" in l][:3])
+            for (knob, note, slots), v in zip(WALKS, setting):
+                assert err.count(note) == (1 if v == "1" else 0), (setting, knob)
+                if slots:
+                    assert err.count(slots) == (1 if v == "1" else 0), (setting, knob)
+    finally:
+        for k, v in keep.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+        idx.close()
+
+
 def test_with_every_device_knob(ctx, capfd, tmp_path_factory):
     _check(*_case(ctx, "syn_m", capfd, tmp_path_factory, ALL_KNOBS))
 

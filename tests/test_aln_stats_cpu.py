@@ -1,6 +1,6 @@
 """The alignment statistics through the code the device runs (miniprot_amd/csrc/aln_stats_core.h), on the CPU.
 
-MPA_GPU_STATS=model makes take_round3() (host_map.cpp) run the shared core with a team of one where it otherwise runs dist_to_stop /
+MPA_GPU_STATS=model makes take_round3() (host_align.cpp) run the shared core with a team of one where it otherwise runs dist_to_stop /
 dist_to_start / summarize_alignment: the stage machine with the oracle as DP executor must still print the reference's bytes, and every
 field of every hit, feature and CIGAR must equal the run with the knob unset.  A stand-alone program (tests/alnstats_check.cpp,
 compiled here with AddressSanitizer and UBSan) feeds the core hand-written CIGARs, with a team of one and a team of 64 threads, and

@@ -168,7 +168,7 @@ def test_edge_genome_reaches_the_edges(ctx, capfd, tmp_path_factory):
 
 # ---- the knob unset -----------------------------------------------------------------------------------
 def test_knob_unset_launches_nothing_and_holds_no_memory(capfd):
-    """k_aln_stats has one launch site, dev_aln_stats(), which sizes its two device pools first.  On a fresh context: runs with the knob
+    """k_aln_stats has one launch site, dev_aln_walks(), which sizes its two device pools first.  On a fresh context: runs with the knob
     unset (or 0) leave mpa_device_bytes() where it was and print no note; the first run with the knob set then grows it -- so the runs
     before it had allocated no pool, i.e. had not been there -- and going back to unset changes nothing again."""
     c = mpa.Context(0)

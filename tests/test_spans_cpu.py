@@ -1,7 +1,7 @@
 """The accepted spans between the DP rounds and the region CIGARs behind them through the code the device runs
 (miniprot_amd/csrc/spans_core.h), on the CPU.
 
-MPA_GPU_SPANS=model makes the stage machine (host_map.cpp) run the shared core with a team of one where it otherwise runs
+MPA_GPU_SPANS=model makes the stage machine (host_align.cpp) run the shared core with a team of one where it otherwise runs
 take_round1_emit_round2 / assemble_alignment / count_exons: with the oracle as DP executor it must still print the reference's bytes,
 and what the two steps leave -- MPA_SPANS_DUMP, tests/spansdump.py -- must equal the dump of the run with the knob unset, byte for
 byte.  A stand-alone program (tests/spans_check.cpp, compiled here with AddressSanitizer and UBSan) feeds the core hand-written and
