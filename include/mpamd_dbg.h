@@ -1,5 +1,6 @@
-/* mpamd_dbg.h -- the test hook of MPA_GPU_SPANS.  It is not part of the C ABI of libmpamd.so (include/mpamd.h): it is built from
- * miniprot_amd/csrc/spans_dbg.cpp into a library of its own, libmpamd_dbg.so, next to libmpamd.so and linked against it. */
+/* mpamd_dbg.h -- the test hooks of MPA_GPU_SPANS and MPA_GPU_DPPLAN.  They are not part of the C ABI of libmpamd.so (include/mpamd.h):
+ * they are built from miniprot_amd/csrc/spans_dbg.cpp and dpplan_dbg.cpp into a library of its own, libmpamd_dbg.so, next to libmpamd.so
+ * and linked against it. */
 #ifndef MPAMD_DBG_H
 #define MPAMD_DBG_H
 #include "mpamd.h"
@@ -24,6 +25,18 @@ extern "C" {
 int mpa_dbg_spans(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int32_t n_plan, const void *plans, int32_t n_seg, const void *segs,
                   int64_t n_rst1, const mpa_dp_rst_t *rst1, const uint32_t *pool1, int64_t n_pool1, int64_t n_rst2, const mpa_dp_rst_t *rst2, const uint32_t *pool2,
                   int64_t n_pool2, void *span_rec, mpa_dp_task_t *tasks, int32_t *n_task, void *asm_rec, uint32_t *cigar, int64_t cigar_cap);
+
+/* The planner of a DP round on the device (MPA_GPU_DPPLAN) for a task table: the arguments of mpa_dbg_dp_plan
+ * (mpamd.h) behind a context, and the same serialisation, assembled from what the device planner left in the context's pools and in
+ * its header.  ctx == NULL: the model -- the planner's stages run on the host with a team of one; no device is needed.  The contig
+ * lengths are uploaded by the hook: no index has to be resident.  Returns the bytes of the serialisation (written when they fit cap),
+ * a negative MPA_ERR_* code, or MPA_DBG_DP_PLAN_DECLINED (1; no serialisation is that short) when the device planner declines the table
+ * and mpa_dp_run would plan it on the host: penalties above 255, the worker pool, the anti-diagonal switch, a repeated round, more than
+ * 2^20 calls, a call of class X_HUGE, more than one traceback chunk, unit costs beyond the sort key, a pool that cannot grow, and every
+ * table or option the host planner refuses.  mpa_last_error() says which. */
+#define MPA_DBG_DP_PLAN_DECLINED 1
+int64_t mpa_dbg_dp_plan_device(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, int32_t n_seq, const int64_t *q_off, int64_t n,
+                               const mpa_dp_task_t *tasks, const int64_t *knobs, void *buf, int64_t cap);
 
 #ifdef __cplusplus
 }

@@ -528,6 +528,32 @@ def dbg_spans(ctx, idx, mo, queries, plans, segs, rst1, pool1, rst2=None, pool2=
     return rec.tobytes(), tasks, arec.tobytes(), cig
 
 
+DP_PLAN_DECLINED = 1   # MPA_DBG_DP_PLAN_DECLINED (include/mpamd_dbg.h)
+
+
+def dbg_dp_plan_device(ctx, dpopt, ctg_len, q_off, tasks, knobs):
+    """mpa_dbg_dp_plan_device(): the plan of dbg_dp_plan() from the device planner of MPA_GPU_DPPLAN on a context, or (ctx None) from its
+    model, the planner's stages on the host with a team of one.  Returns the serialised plan as bytes, (DP_PLAN_DECLINED, reason) when
+    the device planner leaves the table to the host planner, or (code, message) of an error."""
+    import numpy as np
+    tasks = np.ascontiguousarray(tasks, dtype=DP_TASK)
+    ctg_len = np.ascontiguousarray(ctg_len, dtype=np.int64)
+    q_off = np.ascontiguousarray(q_off, dtype=np.int64)
+    kn = np.array([knobs[k] for k in ("lite_min", "lite_wide", "no_split", "antidiag", "pool", "ext_dual", "unit_prio", "tb_budget")], dtype=np.int64)
+    f = dbg_lib().mpa_dbg_dp_plan_device
+    f.restype = C.c_int64
+    f.argtypes = [C.c_void_p, C.POINTER(DpOpt), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    args = (ctx.h if ctx else None, C.byref(dpopt), len(ctg_len), ctg_len.ctypes.data, len(q_off) - 1, q_off.ctypes.data, len(tasks), tasks.ctypes.data, kn.ctypes.data)
+    need = f(*args, None, 0)
+    if need < 0 or need == DP_PLAN_DECLINED:
+        return int(need), last_error()
+    buf = np.zeros(need, dtype=np.uint8)
+    got = f(*args, buf.ctypes.data, need)
+    if got != need:
+        return int(got), last_error()
+    return buf.tobytes()
+
+
 def map_batches(ctx, idx, mo, batches, n_threads=1, keep_results=False, want_text=True, claim=None):
     """mpa_map_batches(): a stream of Queries batches through the pipelined mapper.  Returns the list of output texts
     (bytes, one per batch; the hit-id counter runs across the batches as in one output file); with keep_results the pair

@@ -169,6 +169,9 @@ struct mpa_ctx_s {
 	DevBuf sp_pool1;                          // the batch's round-1 CIGAR pool, kept across round 2 (which overwrites cigd)
 	DevBuf sp_in2, sp_asm, sp_cig;            // round-2 results | slot offsets (| a caller's round-2 pool); per-plan records; the assembled CIGARs
 	HostPinned h_sp_up, h_sp_down, h_sp_up2, h_sp_down2;
+	// ---- the device planner of a DP round (dp_exec.hip, MPA_GPU_DPPLAN=1): grow-only, allocated by the first call that asks for them
+	DevBuf dpp;                               // raw tasks | query offsets | keys | block sums | units | the header and the sorted traceback calls | sort scratch
+	HostPinned h_dpp_up, h_dpp_down;          // ... its staging: one block up, one block down
 	struct SpansKeep { size_t off_plan = 0, off_seg = 0, off_rst1 = 0; int64_t n_plan = -1, n_pool1 = 0; } sp_keep;   // what dev_spans_round1 left for dev_spans_assemble
 };
 
@@ -186,7 +189,7 @@ template<typename F> static void ctx_each_devbuf(mpa_ctx_s *ctx, F f)
 	                  &B.pf_qfirst2, &B.val64[0], &B.val64[1],
 	                  &B.s_meta, &B.s_cur, &B.s_cur2, &B.s_kept, &B.s_base, &B.s_out, &B.s_flag, &B.dkey, &B.x_all, &B.rx_all, &B.rx_keys,
 	                  &ctx->lite, &ctx->ckpt, &ctx->wlist, &B.k_in, &B.k_cnt, &B.k_bkt, &B.k_q, &B.r_gmap, &ctx->st_in, &ctx->st_out, &B.rg, &B.pl, &ctx->cs_out, &ctx->rows_out,
-	                  &ctx->sp_in, &ctx->sp_mid, &ctx->sp_out, &ctx->sp_pool1, &ctx->sp_in2, &ctx->sp_asm, &ctx->sp_cig };
+	                  &ctx->sp_in, &ctx->sp_mid, &ctx->sp_out, &ctx->sp_pool1, &ctx->sp_in2, &ctx->sp_asm, &ctx->sp_cig, &ctx->dpp };
 	int k = 0;
 	for (DevBuf *b : all) f(*b, k++);
 }

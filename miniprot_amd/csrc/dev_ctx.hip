@@ -241,7 +241,7 @@ void mpa_ctx_destroy(mpa_ctx_t *ctx)
 	ctx->dp_trace.release();
 	SeedBufs &B = ctx->seed;
 	ctx_each_devbuf(ctx, [](DevBuf &b, int) { b.release(); });
-	for (HostPinned *h : { &B.h_jobs, &B.h_rhits, &B.hc_a, &B.hc_f, &B.hc_pred, &B.h_meta, &B.h_back, &B.h_xoff, &B.h_kin, &B.h_kout, &ctx->h_up, &ctx->h_down, &ctx->h_pool, &ctx->h_stats_up, &ctx->h_stats_down, &ctx->h_cs_down, &ctx->h_rows_down, &ctx->h_sp_up, &ctx->h_sp_down, &ctx->h_sp_up2, &ctx->h_sp_down2 }) h->release();
+	for (HostPinned *h : { &B.h_jobs, &B.h_rhits, &B.hc_a, &B.hc_f, &B.hc_pred, &B.h_meta, &B.h_back, &B.h_xoff, &B.h_kin, &B.h_kout, &ctx->h_up, &ctx->h_down, &ctx->h_pool, &ctx->h_stats_up, &ctx->h_stats_down, &ctx->h_cs_down, &ctx->h_rows_down, &ctx->h_sp_up, &ctx->h_sp_down, &ctx->h_sp_up2, &ctx->h_sp_down2, &ctx->h_dpp_up, &ctx->h_dpp_down }) h->release();
 	auto drop_hold = [](SeedHold &H) { for (HostPinned *h : { &H.h_pos, &H.h_f, &H.h_pred, &H.h_a, &H.h_U, &H.h_A, &H.h_R, &H.h_P }) h->release(); };
 	drop_hold(B.own);
 	for (SeedHold *H : ctx->holds) { drop_hold(*H); delete H; }

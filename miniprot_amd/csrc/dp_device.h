@@ -51,7 +51,7 @@ enum DpClass : int32_t {
 	T_LITE128,                   // 65..128 columns, one call per wave
 	T_LITE_W4                    // 129..256 columns, a four-wave group per pair of calls (k_lite_wide)
 };
-static inline bool is_checkpointed(int32_t tb_cls) { return tb_cls >= T_LITE16; }
+__host__ __device__ static inline bool is_checkpointed(int32_t tb_cls) { return tb_cls >= T_LITE16; }
 
 // Per-row record produced by the prep kernel, one uint32 per window row i:
 //   byte0 2*nas[i]      nas = amino acid (aa20 code) of the codon ending at row i, 21 when undefined; stored

@@ -1,7 +1,8 @@
 // dp_exec.hip -- host-side executor of the batched spliced DP: the implementation of mpa_dp_run().
 //
 // A batch of ns_global_gs16b() calls (nasw.h:135; call sites align.c:73,288,293,322,327) is planned on the host (dp_plan.cpp: classes,
-// order, pool layout, waves, traceback chunks, the round's unit list -- nothing of it needs the device) and then enqueued as
+// order, pool layout, waves, traceback chunks, the round's unit list -- nothing of it needs the device; with MPA_GPU_DPPLAN=1 the same
+// plan is made by the kernels of dp_plan_kernels.hip, dev_dp_plan() below, and the uploads of what they wrote are skipped) and then enqueued as
 //   1. one upload from a pinned staging block, k_prep_rows / k_prep_prof (per-row records + query profiles, written once to HBM),
 //   2. ONE k_dp_round launch for every DP unit of the round: the extension calls of every class up to 1024 columns, the packed
 //      sweeps of the checkpointed traceback and the plain traceback sweeps of the first traceback chunk, costliest unit first
@@ -13,9 +14,11 @@
 // bracketed by HIP events (mpa_dp_last_stats feeds bench.py's roofline record).  mpa_dp_run_impl is that list of phases.  There is no
 // CPU fallback here by design.  This unit holds the DP only (kernels: dp_kernels.hip, dp_antidiag.hip, gs32_exec.hip); the context
 // and its pools are dev_ctx.hip, the other stages seed_run.hip, refine_run.hip and index_run.hip.
+#include <rocprim/device/device_radix_sort.hpp>
 #include "dev_ctx.h"
 #include "dp_kernels.hip"
 #include "dp_antidiag.hip"
+#include "dp_plan_kernels.hip"
 
 namespace mpa {
 
@@ -236,6 +239,7 @@ struct DpRun {
 	hipStream_t s;
 	DpPlan &plan;
 	DpPlanKnobs kn;
+	const mpa_dp_task_t *in;                    // the caller's array
 	char *hup = nullptr, *hdn = nullptr;        // pinned staging: host -> device (plan.up), device -> host (plan.dn)
 	DpConst dc;
 	ExtArgs ea;
@@ -301,16 +305,17 @@ static int dp_upload_and_prep(DpRun &R, const mpa_idx_t *mi, const mpa_dpopt_t *
 	DpPlan &P = R.plan;
 	hipStream_t s = R.s;
 	char *hup = R.hup;
-	const size_t b_tasks = sizeof(DTask) * P.tasks.size(), b_chunks = sizeof(PrepChunk) * P.prep.size(), b_waves = sizeof(ExtWave) * P.ewaves.size();
-	memcpy(hup + P.up.tasks, P.tasks.data(), b_tasks);
-	memcpy(hup + P.up.chunks, P.prep.data(), b_chunks);
+	const size_t b_tasks = sizeof(DTask) * P.cnt.n, b_chunks = sizeof(PrepChunk) * P.cnt.n_prep, b_waves = sizeof(ExtWave) * P.cnt.n_ewaves;
+	const bool up = !P.on_device;                                         // (a plan made on the device: tasks, prep chunks and waves are in their pools)
+	if (up) memcpy(hup + P.up.tasks, P.tasks.data(), b_tasks);
+	if (up) memcpy(hup + P.up.chunks, P.prep.data(), b_chunks);
 	memcpy(hup + P.up.q, q->seqs + q->q_off[0], (size_t)P.q_bytes);
-	memcpy(hup + P.up.waves, P.ewaves.data(), b_waves);
+	if (up) memcpy(hup + P.up.waves, P.ewaves.data(), b_waves);
 	R.mark("    dp: buffers");
-	HIP_TRY(hipMemcpyAsync(ctx->tasks.p, hup + P.up.tasks, b_tasks, hipMemcpyHostToDevice, s));
-	HIP_TRY(hipMemcpyAsync(ctx->chunks.p, hup + P.up.chunks, b_chunks, hipMemcpyHostToDevice, s));
+	if (up) HIP_TRY(hipMemcpyAsync(ctx->tasks.p, hup + P.up.tasks, b_tasks, hipMemcpyHostToDevice, s));
+	if (up) HIP_TRY(hipMemcpyAsync(ctx->chunks.p, hup + P.up.chunks, b_chunks, hipMemcpyHostToDevice, s));
 	HIP_TRY(hipMemcpyAsync(ctx->qseq.p, hup + P.up.q, P.q_bytes, hipMemcpyHostToDevice, s));
-	if (!P.ewaves.empty()) HIP_TRY(hipMemcpyAsync(ctx->waves.p, hup + P.up.waves, b_waves, hipMemcpyHostToDevice, s));
+	if (up && b_waves) HIP_TRY(hipMemcpyAsync(ctx->waves.p, hup + P.up.waves, b_waves, hipMemcpyHostToDevice, s));
 	// (k_prep_rows writes every row of every call; only the padding the kernels prefetch behind the last call is cleared)
 	HIP_TRY(hipMemsetAsync((char*)ctx->rec.p + (size_t)(P.rec_total - P.rec_pad) * 4, 0, (size_t)P.rec_pad * 4, s));
 	if (P.n_wide_groups) HIP_TRY(hipMemsetAsync(ctx->rowkey.p, 0, (size_t)(P.n_wide_groups * 2 * P.key_stride * 4), s));
@@ -347,9 +352,9 @@ static int dp_upload_and_prep(DpRun &R, const mpa_idx_t *mi, const mpa_dpopt_t *
 	// queue, and with ten more queues in use the round kernels are time-sliced: 41 -> 72 ms per launch.  They stay in the lane's
 	// own queue; MPA_SHORT_KERNEL raises their wave priority instead.)
 	HIP_TRY(hipEventRecord(ctx->ev[0], s));
-	if (!P.prep.empty())
-		hipLaunchKernelGGL(k_prep_rows, dim3((unsigned)P.prep.size()), dim3(256), 0, s, dg, ctx->tasks.as<DTask>(), ctx->chunks.as<PrepChunk>(), ctx->rec.as<uint32_t>(), dc, tabs);
-	hipLaunchKernelGGL(k_prep_prof, dim3((unsigned)P.tasks.size()), dim3(256), 0, s, ctx->tasks.as<DTask>(), ctx->qseq.as<char>(), ctx->prof.as<int16_t>(), tabs);
+	if (P.cnt.n_prep)
+		hipLaunchKernelGGL(k_prep_rows, dim3((unsigned)P.cnt.n_prep), dim3(256), 0, s, dg, ctx->tasks.as<DTask>(), ctx->chunks.as<PrepChunk>(), ctx->rec.as<uint32_t>(), dc, tabs);
+	hipLaunchKernelGGL(k_prep_prof, dim3((unsigned)P.cnt.n), dim3(256), 0, s, ctx->tasks.as<DTask>(), ctx->qseq.as<char>(), ctx->prof.as<int16_t>(), tabs);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(ctx->ev[1], s));
 	R.mark("    dp: uploads + prep enqueued");
@@ -442,13 +447,13 @@ static int dp_launch_round(DpRun &R, GlobWave *d_gw)
 	hipStream_t s = R.s;
 	DpUnit *units = (DpUnit*)(R.hup + P.up.units);          // (pinned: the copy below needs no wait)
 	int rc;
-	if ((rc = dp_plan_units(P, R.kn, units))) { set_error(P.err); return rc; }
+	if (!P.on_device && (rc = dp_plan_units(P, R.kn, units))) { set_error(P.err); return rc; }   // (on the device: the list is in ctx->units, its length in the plan)
 	const size_t n_units = P.n_units;
 	if (n_units == 0) return MPA_OK;
 	static const bool show_top = [] { const char *e = getenv("MPA_DP_TOP"); return e && atoi(e) != 0; }();
-	if (show_top) fputs(dp_plan_top(P, R.kn).c_str(), stderr);
+	if (show_top && !P.on_device) fputs(dp_plan_top(P, R.kn).c_str(), stderr);
 	if ((rc = ctx->units.ensure(P.sz.units))) return rc;
-	HIP_TRY(hipMemcpyAsync(ctx->units.p, units, P.sz.units, hipMemcpyHostToDevice, s));
+	if (!P.on_device) HIP_TRY(hipMemcpyAsync(ctx->units.p, units, P.sz.units, hipMemcpyHostToDevice, s));
 	R.ga.waves = d_gw;
 	const size_t round_lds = dp_round_lds();
 	if (dp_pool_enabled()) {
@@ -509,7 +514,7 @@ static int dp_tb_chunks(DpRun &R)
 	char *hup = R.hup;
 	int rc;
 	for (size_t ri = 0; ri < P.chunks.size(); ++ri) {
-		dp_plan_chunk_waves(P, ri);
+		if (!P.on_device) dp_plan_chunk_waves(P, ri);
 		const DpTbChunk &r = P.chunks[ri];
 		if (ri > 0) {                                                    // later chunks reuse the traceback buffer (and its staging): join everything first
 			for (auto &l : R.launches) (void)hipStreamWaitEvent(s, ctx->lev[2 * l.side + 1], 0);
@@ -517,11 +522,13 @@ static int dp_tb_chunks(DpRun &R)
 			R.add_chunk_times();                                           // (the previous chunk's sweep and walk)
 		}
 		int32_t *d_list = ctx->list.as<int32_t>();
-		GlobWave *d_gw = (GlobWave*)((char*)ctx->list.p + ((P.tasks.size() * 4 + 63) & ~(size_t)63));
-		memcpy(hup + P.up.list, r.list.data(), r.list.size() * 4);
-		memcpy(hup + P.up.gw, r.waves.data(), r.waves.size() * sizeof(GlobWave));
-		HIP_TRY(hipMemcpyAsync(d_list, hup + P.up.list, r.list.size() * 4, hipMemcpyHostToDevice, s));
-		HIP_TRY(hipMemcpyAsync(d_gw, hup + P.up.gw, r.waves.size() * sizeof(GlobWave), hipMemcpyHostToDevice, s));
+		GlobWave *d_gw = (GlobWave*)((char*)ctx->list.p + ((P.cnt.n * 4 + 63) & ~(size_t)63));
+		if (!P.on_device) {
+			memcpy(hup + P.up.list, r.list.data(), r.n_list * 4);
+			memcpy(hup + P.up.gw, r.waves.data(), r.n_waves * sizeof(GlobWave));
+			HIP_TRY(hipMemcpyAsync(d_list, hup + P.up.list, r.n_list * 4, hipMemcpyHostToDevice, s));
+			HIP_TRY(hipMemcpyAsync(d_gw, hup + P.up.gw, r.n_waves * sizeof(GlobWave), hipMemcpyHostToDevice, s));
+		}
 		R.mark("    dp: traceback lists enqueued");
 		R.ga.tb = ctx->tb.as<uint16_t>();
 		HIP_TRY(hipEventRecord(ctx->ev[3], s));
@@ -548,7 +555,7 @@ static int dp_tb_chunks(DpRun &R)
 		}
 		for (size_t k = first_glob_launch; k < R.launches.size(); ++k) (void)hipStreamWaitEvent(s, ctx->lev[2 * R.launches[k].side + 1], 0);
 		HIP_TRY(hipEventRecord(ctx->ev[4], s));
-		hipLaunchKernelGGL(k_backtrack, dim3((unsigned)r.list.size()), dim3(64), 0, s, ctx->tasks.as<DTask>(), d_list, (int32_t)r.list.size(),
+		hipLaunchKernelGGL(k_backtrack, dim3((unsigned)r.n_list), dim3(64), 0, s, ctx->tasks.as<DTask>(), d_list, (int32_t)r.n_list,
 		                   ctx->tb.as<uint16_t>(), ctx->cig.as<uint32_t>(), ctx->ncig.as<int32_t>());
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipEventRecord(ctx->ev[5], s));
@@ -565,8 +572,10 @@ static int dp_walk(DpRun &R)
 	DpPlan &P = R.plan;
 	hipStream_t s = R.s;
 	if (!P.n_lite) return MPA_OK;
-	memcpy(R.hup + P.up.wl, P.glob_ids.data() + P.n_reg_glob, 4 * P.n_lite);
-	HIP_TRY(hipMemcpyAsync(ctx->wlist.p, R.hup + P.up.wl, 4 * P.n_lite, hipMemcpyHostToDevice, s));
+	if (!P.on_device) {
+		memcpy(R.hup + P.up.wl, P.glob_ids.data() + P.n_reg_glob, 4 * P.n_lite);
+		HIP_TRY(hipMemcpyAsync(ctx->wlist.p, R.hup + P.up.wl, 4 * P.n_lite, hipMemcpyHostToDevice, s));
+	}
 	WalkArgs wk;
 	wk.ga = R.ga, wk.ga.waves = nullptr, wk.list = ctx->wlist.as<int32_t>(), wk.n_list = (int32_t)P.n_lite;
 	wk.lite = ctx->lite.as<uint32_t>(), wk.ckpt = ctx->ckpt.as<uint32_t>(), wk.cig = ctx->cig.as<uint32_t>(), wk.n_cigar = ctx->ncig.as<int32_t>();
@@ -597,15 +606,15 @@ static int dp_join_and_download(DpRun &R)
 	mpa_ctx_t *ctx = R.ctx;
 	DpPlan &P = R.plan;
 	hipStream_t s = R.s;
-	const size_t n = P.tasks.size();
+	const size_t n = P.cnt.n;
 	for (auto &l : R.launches) (void)hipStreamWaitEvent(s, ctx->lev[2 * l.side + 1], 0);
 	HIP_TRY(hipEventRecord(ctx->ev[2], s));
 	int rc;
 	if ((rc = ctx->h_down.ensure(P.dn.end))) return rc;
 	char *hdn = R.hdn = ctx->h_down.as<char>();
 	*(int32_t*)(hdn + P.dn.err) = 0;
-	if (!P.ext_ids.empty()) HIP_TRY(hipMemcpyAsync(hdn + P.dn.eo, ctx->extout.p, sizeof(ExtOut) * n, hipMemcpyDeviceToHost, s));
-	if (!P.glob_ids.empty()) {
+	if (P.cnt.n_ext) HIP_TRY(hipMemcpyAsync(hdn + P.dn.eo, ctx->extout.p, sizeof(ExtOut) * n, hipMemcpyDeviceToHost, s));
+	if (P.cnt.n_glob) {
 		HIP_TRY(hipMemcpyAsync(hdn + P.dn.sc, ctx->score.p, n * 4, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipMemcpyAsync(hdn + P.dn.nc, ctx->ncig.p, n * 4, hipMemcpyDeviceToHost, s));
 	}
@@ -661,10 +670,10 @@ static int dp_assemble(DpRun &R, mpa_dp_rst_t *rst, uint32_t **cigar_pool, int64
 		HIP_TRY(wait_stream(ctx, s));
 		memcpy(pool, ctx->h_pool.p, (size_t)pool_n * 4);
 	}
-	std::vector<int64_t> off_of(P.tasks.size(), 0);
+	std::vector<int64_t> off_of(P.cnt.n, 0);
 	for (size_t k = 0; k < n_glob; ++k) off_of[P.glob_ids[k]] = dense_off[k];
-	for (size_t k = 0; k < P.tasks.size(); ++k) {
-		const DTask &t = P.tasks[k];
+	for (size_t k = 0; k < P.cnt.n; ++k) {
+		const mpa_dp_task_t &t = R.in[k];                                  // (mode and shape: the caller's own record)
 		mpa_dp_rst_t &o = rst[k];
 		if (t.flag & (MPA_F_EXT_LEFT | MPA_F_EXT_RIGHT)) {
 			o.nt_len = eo[k].nt_len, o.aa_len = eo[k].aa_len, o.score = eo[k].score, o.n_cigar = 0, o.cigar_off = 0;
@@ -682,7 +691,7 @@ static void dp_statistics(DpRun &R)
 {
 	mpa_ctx_t *ctx = R.ctx;
 	mpa_dp_stats_t &st = ctx->stats;
-	dp_plan_stats(R.plan);
+	if (!R.plan.on_device) dp_plan_stats(R.plan);                        // (on the device: sums of the classify stage, in the plan already)
 	const mpa_dp_stats_t &ps = R.plan.stats;
 	st.n_ext = ps.n_ext, st.n_glob = ps.n_glob, st.cells_ext = ps.cells_ext, st.cells_glob = ps.cells_glob, st.rows_prep = ps.rows_prep;
 	st.alg_bytes_ext = ps.alg_bytes_ext, st.alg_bytes_glob = ps.alg_bytes_glob + 4 * R.pool_n;   // (+ the CIGARs' own words)
@@ -717,6 +726,91 @@ static DpPlanKnobs dp_plan_knobs(const mpa_ctx_t *ctx)
 	return kn;
 }
 
+// ---- 1'. the plan of the round made on the device (MPA_GPU_DPPLAN=1)
+// Pools the planner writes are sized before its result is known, from n and one pass over the caller's array; one upload (raw tasks |
+// query offsets | contig lengths when the caller has them on the host only), the stages of dp_plan_core.h around two radix sorts, one
+// download (header | sorted traceback calls), one wait.  d_ctg_len: the resident index's contig lengths, or nullptr: h_ctg_len go up.
+// MPA_OK: *head and *gids point into the context's pinned block, tasks / chunks / waves / list (calls, then GlobWave[] at the
+// executor's offset) / units / wlist hold the plan.  MPA_ERR_UNSUPPORTED: declined (the last error says why), nothing the host planner
+// needs was touched.
+static int dev_dp_plan_run(mpa_ctx_t *ctx, hipStream_t s, const int64_t *d_ctg_len, const int64_t *h_ctg_len, int32_t n_ctg, const mpa_qbatch_t *q, const mpa_dpopt_t *opt,
+                           const DpPlanKnobs &kn, int64_t n, const mpa_dp_task_t *in, const DpDevHead **head, const int32_t **gids, size_t *bytes_up, size_t *bytes_down)
+{
+	if (const char *why = dp_plan_device_declines(opt, kn, n)) { set_error(std::string("device DP plan: ") + why); return MPA_ERR_UNSUPPORTED; }
+	if (q->n_seq < 0 || n_ctg < 0) { set_error("device DP plan: no queries or contigs"); return MPA_ERR_UNSUPPORTED; }
+	const size_t N = (size_t)n, U = (size_t)dp_units_bound(n), nb = (size_t)dp_blocks(n, TeamWG::W);
+	auto al256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+	// what goes up, in one block
+	const size_t up_raw = 0, up_qoff = up_raw + al256(sizeof(mpa_dp_task_t) * N), up_ctg = up_qoff + al256(8 * ((size_t)q->n_seq + 1));
+	const size_t up_end = up_ctg + (d_ctg_len ? 0 : al256(8 * (size_t)n_ctg));
+	tl_alloc_failed = false;
+	auto declined_alloc = [](int rc) { if (tl_alloc_failed) { tl_alloc_failed = false; return (int)MPA_ERR_UNSUPPORTED; } return rc; };
+	int rc;
+	if ((rc = ctx->h_dpp_up.ensure(up_end + 256))) return MPA_ERR_UNSUPPORTED;
+	char *hup = ctx->h_dpp_up.as<char>();
+	memcpy(hup + up_raw, in, sizeof(mpa_dp_task_t) * N);
+	int64_t max_nl = 0, max_al = 0;
+	const int64_t prep_bound = dp_plan_prep_bound((const mpa_dp_task_t*)(hup + up_raw), n, &max_nl, &max_al);
+	if (!dp_unit_costs_fit(max_nl, max_al)) { set_error("device DP plan: unit costs that do not fit the sort key"); return MPA_ERR_UNSUPPORTED; }
+	memcpy(hup + up_qoff, q->q_off, 8 * ((size_t)q->n_seq + 1));
+	if (!d_ctg_len && n_ctg > 0) memcpy(hup + up_ctg, h_ctg_len, 8 * (size_t)n_ctg);
+	// scratch: the upload block, keys, block sums, units, header | sorted traceback calls (one download), the sorts' own
+	size_t tmp_calls = 0, tmp_units = 0;
+	HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp_calls, (uint64_t*)nullptr, (uint64_t*)nullptr, N, 0u, (unsigned)MPA_DPPLAN_KEY_BITS, s));
+	HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp_units, (uint64_t*)nullptr, (uint64_t*)nullptr, U, 0u, 64u, s));
+	Carve carve;
+	const size_t o_up = carve(up_end), o_key = carve(8 * N), o_skey = carve(8 * N), o_bsum = carve(sizeof(DpSums) * nb), o_ubuf = carve(sizeof(DpUnit) * U);
+	const size_t o_ukey = carve(8 * U), o_uskey = carve(8 * U), o_head = carve(sizeof(DpDevHead)), o_gids = carve(4 * N), o_tmp = carve(std::max(tmp_calls, tmp_units) + 16);
+	const size_t down_bytes = o_gids + 4 * N - o_head;
+	// the executor's pools at their bounds (size_buffers() asks for no more once the plan is known: nothing the planner wrote moves)
+	if ((rc = ctx->dpp.ensure(carve.at)) || (rc = ctx->tasks.ensure(sizeof(DTask) * N)) || (rc = ctx->chunks.ensure(sizeof(PrepChunk) * ((size_t)prep_bound + 1))) ||
+	    (rc = ctx->waves.ensure(sizeof(ExtWave) * (N + 16))) || (rc = ctx->list.ensure(N * 4 + 128 + sizeof(GlobWave) * (N + 1))) ||
+	    (rc = ctx->units.ensure(sizeof(DpUnit) * U)) || (rc = ctx->wlist.ensure(N * 4 + 128)))
+		return declined_alloc(rc);
+	if ((rc = ctx->h_dpp_down.ensure(down_bytes + 256))) return MPA_ERR_UNSUPPORTED;
+	char *X = ctx->dpp.as<char>();
+	DpDevPlan D;
+	D.n = n, D.n_ubound = (int64_t)U, D.n_ctg = n_ctg, D.n_seq = q->n_seq, D.opt = dp_plan_opt(opt), D.kn = kn;
+	D.raw = (const mpa_dp_task_t*)(X + o_up + up_raw), D.q_off = (const int64_t*)(X + o_up + up_qoff), D.ctg_len = d_ctg_len ? d_ctg_len : (const int64_t*)(X + o_up + up_ctg);
+	D.tasks = ctx->tasks.as<DTask>(), D.chunks = ctx->chunks.as<PrepChunk>(), D.waves = ctx->waves.as<ExtWave>(), D.list = ctx->list.as<int32_t>();
+	D.gw = (GlobWave*)((char*)ctx->list.p + ((N * 4 + 63) & ~(size_t)63));                    // (where dp_tb_chunks puts a chunk's waves)
+	D.units = ctx->units.as<DpUnit>(), D.wlist = ctx->wlist.as<int32_t>();
+	D.key = (uint64_t*)(X + o_key), D.skey = (uint64_t*)(X + o_skey), D.bsum = (DpSums*)(X + o_bsum), D.ubuf = (DpUnit*)(X + o_ubuf);
+	D.ukey = (uint64_t*)(X + o_ukey), D.uskey = (uint64_t*)(X + o_uskey), D.head = (DpDevHead*)(X + o_head), D.gids = (int32_t*)(X + o_gids);
+	HIP_TRY(hipMemcpyAsync(X + o_up, hup, up_end, hipMemcpyHostToDevice, s));
+	HIP_TRY(hipMemsetAsync(D.head, 0, sizeof(DpDevHead), s));
+	const dim3 g_calls((unsigned)nb), g_units((unsigned)dp_blocks((int64_t)U, TeamWG::W)), wg(TeamWG::W);
+	hipLaunchKernelGGL(k_dpp_classify, g_calls, wg, 0, s, D);
+	HIP_TRY(rocprim::radix_sort_keys(X + o_tmp, tmp_calls, D.key, D.skey, N, 0u, (unsigned)MPA_DPPLAN_KEY_BITS, s));
+	hipLaunchKernelGGL(k_dpp_sums, g_calls, wg, 0, s, D);
+	hipLaunchKernelGGL(k_dpp_mid, dim3(1), wg, 0, s, D);
+	hipLaunchKernelGGL(k_dpp_layout, g_calls, wg, 0, s, D);
+	hipLaunchKernelGGL(k_dpp_units, g_units, wg, 0, s, D);
+	HIP_TRY(rocprim::radix_sort_keys(X + o_tmp, tmp_units, D.ukey, D.uskey, U, 0u, 64u, s));
+	hipLaunchKernelGGL(k_dpp_units_out, g_units, wg, 0, s, D);
+	HIP_TRY(hipGetLastError());
+	char *hdn = ctx->h_dpp_down.as<char>();
+	HIP_TRY(hipMemcpyAsync(hdn, X + o_head, down_bytes, hipMemcpyDeviceToHost, s));
+	HIP_TRY(wait_stream(ctx, s));
+	*head = (const DpDevHead*)hdn, *gids = (const int32_t*)(hdn + (o_gids - o_head));
+	*bytes_up = up_end, *bytes_down = down_bytes;
+	return MPA_OK;
+}
+
+// the round's plan from the device planner: MPA_OK (plan.on_device), MPA_ERR_UNSUPPORTED when it declines, else an error
+static int dev_dp_plan(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *opt, const mpa_qbatch_t *q, const DpPlanKnobs &kn, int64_t n, const mpa_dp_task_t *in, DpPlan &plan,
+                       size_t *bytes_up, size_t *bytes_down)
+{
+	const DpDevHead *head = nullptr;
+	const int32_t *gids = nullptr;
+	int rc = dev_dp_plan_run(ctx, ctx->stream, mi->dev[ctx->device]->ctg_len, nullptr, (int32_t)mi->ctg.size(), q, opt, kn, n, in, &head, &gids, bytes_up, bytes_down);
+	if (rc != MPA_OK) return rc;
+	if ((rc = dp_plan_from_head(*head, gids, q, opt, kn, sizeof(DpRoundArgs), plan))) set_error("device DP plan: " + plan.err);
+	return rc;
+}
+// MPA_GPU_DPPLAN, read per call
+static bool dp_plan_on_device() { const char *e = getenv("MPA_GPU_DPPLAN"); return e && atoi(e) != 0; }
+
 static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *opt, const mpa_qbatch_t *q,
                int64_t n, const mpa_dp_task_t *in, mpa_dp_rst_t *rst, uint32_t **cigar_pool, int64_t *n_pool)
 {
@@ -732,9 +826,22 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 	// 1. plan
 	DpPlan plan;
 	const DpPlanKnobs kn = dp_plan_knobs(ctx);
-	if ((rc = dp_plan(in, n, mi->ctg.empty() ? nullptr : &mi->ctg[0].len, sizeof(mi->ctg[0]), (int32_t)mi->ctg.size(), q, opt, kn, sizeof(DpRoundArgs), plan))) { set_error(plan.err); return rc; }
-	timing_note("  dp: classify/sort/layout", now_ms() - t_begin);
-	DpRun R{ ctx, ctx->stream, plan, kn };
+	bool planned = false;
+	if (dp_plan_on_device()) {                                  // (MPA_GPU_DPPLAN=1) the planner's stages on the device; declined: the host planner, as without the knob
+		size_t b_up = 0, b_down = 0;
+		rc = dev_dp_plan(ctx, mi, opt, q, kn, n, in, plan, &b_up, &b_down);
+		if (rc == MPA_OK) {
+			planned = true;
+			timing_note("  dp: plan on device", now_ms() - t_begin);
+			if (timing_on()) fprintf(stderr, "[mpa-timing]   dp: plan on device: %zu bytes up, %zu bytes down\n", b_up, b_down);
+		} else if (rc != MPA_ERR_UNSUPPORTED) return rc;
+		else if (timing_on()) fprintf(stderr, "[mpa-timing]   device DP plan declined (%s): planned on the host\n", mpa_last_error());
+	}
+	if (!planned) {
+		if ((rc = dp_plan(in, n, mi->ctg.empty() ? nullptr : &mi->ctg[0].len, sizeof(mi->ctg[0]), (int32_t)mi->ctg.size(), q, opt, kn, sizeof(DpRoundArgs), plan))) { set_error(plan.err); return rc; }
+		timing_note("  dp: classify/sort/layout", now_ms() - t_begin);
+	}
+	DpRun R{ ctx, ctx->stream, plan, kn, in };
 	R.t_mark = now_ms();
 	if ((rc = dp_size_pools(R)) ||                             // 2. pools and staging
 	    (rc = dp_upload_and_prep(R, mi, opt, q)) ||            // 3. uploads, memsets, prep
@@ -792,5 +899,43 @@ int64_t mpa_dbg_dp_plan(const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ct
 }
 
 } // extern "C"
+
+namespace mpa {
+size_t dp_round_args_bytes() { return sizeof(DpRoundArgs); }
+// mpa_dbg_dp_plan_device on a context (dpplan_dbg.cpp): the device planner on a task table, then every section it left in the pools
+// downloaded into a plan's vectors and serialised as mpa_dbg_dp_plan does.  1: declined (the last error says why).
+int64_t dev_dp_plan_dbg(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, const mpa_qbatch_t *q, int64_t n, const mpa_dp_task_t *in,
+                        const DpPlanKnobs &kn, void *buf, int64_t cap)
+{
+	HIP_TRY(hipSetDevice(ctx->device));
+	const DpDevHead *head = nullptr;
+	const int32_t *gids = nullptr;
+	size_t b_up = 0, b_down = 0;
+	int rc = dev_dp_plan_run(ctx, ctx->stream, nullptr, ctg_len, n_ctg, q, opt, kn, n, in, &head, &gids, &b_up, &b_down);
+	if (rc == MPA_ERR_UNSUPPORTED) return 1;
+	if (rc != MPA_OK) return rc;
+	DpPlan P;
+	if ((rc = dp_plan_from_head(*head, gids, q, opt, kn, sizeof(DpRoundArgs), P))) { set_error("device DP plan: " + P.err); return rc == MPA_ERR_UNSUPPORTED ? 1 : rc; }
+	const DpDevHead H = *head;
+	std::vector<DpUnit> units((size_t)H.n_units);
+	std::vector<int32_t> wl((size_t)H.n_lite);
+	P.tasks.resize((size_t)H.n), P.prep.resize((size_t)H.n_prep), P.ewaves.resize((size_t)H.n_ewaves);
+	auto down = [&](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
+	HIP_TRY(down(P.tasks.data(), ctx->tasks.p, sizeof(DTask) * P.tasks.size()));
+	HIP_TRY(down(P.prep.data(), ctx->chunks.p, sizeof(PrepChunk) * P.prep.size()));
+	HIP_TRY(down(P.ewaves.data(), ctx->waves.p, sizeof(ExtWave) * P.ewaves.size()));
+	HIP_TRY(down(units.data(), ctx->units.p, sizeof(DpUnit) * units.size()));
+	HIP_TRY(down(wl.data(), ctx->wlist.p, 4 * wl.size()));
+	if (!P.chunks.empty()) {
+		DpTbChunk &r = P.chunks[0];
+		r.list.resize(r.n_list), r.waves.resize(r.n_waves);
+		HIP_TRY(down(r.list.data(), ctx->list.p, 4 * r.n_list));
+		HIP_TRY(down(r.waves.data(), (char*)ctx->list.p + (((size_t)H.n * 4 + 63) & ~(size_t)63), sizeof(GlobWave) * r.n_waves));
+		for (size_t k = 0; k < r.n_list; ++k) if (r.list[k] != P.glob_ids[k]) { set_error("device DP plan: the chunk's call list is not the sorted order"); return MPA_ERR_HIP; }
+	}
+	for (size_t k = 0; k < wl.size(); ++k) if (wl[k] != P.glob_ids[P.n_reg_glob + k]) { set_error("device DP plan: the walk list is not the sorted order"); return MPA_ERR_HIP; }
+	return dp_plan_write(P, units, buf, cap);
+}
+} // namespace mpa
 
 #include "gs32_exec.hip"

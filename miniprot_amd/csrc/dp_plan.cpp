@@ -41,67 +41,24 @@ static int refuse(DpPlan &P, int rc, const std::string &msg) { P.rc = rc, P.err 
 // ---- classify: one DTask per call, its class and profile width; ext_ids / glob_ids unsorted
 static int classify(DpPlan &P, const mpa_dp_task_t *in, int64_t n, const int64_t *ctg_len, size_t ctg_stride, int32_t n_ctg, const mpa_qbatch_t *q, const mpa_dpopt_t *opt, const DpPlanKnobs &kn)
 {
-	// parameter guards: outside these the packed-int16 kernels would not be bit-exact
-	int32_t max_mat = 0;
-	for (int k = 0; k < 484; ++k) max_mat = std::max<int32_t>(max_mat, opt->mat[k]);
-	if (opt->go < 0 || opt->go > 32000 || opt->ge < 0 || opt->ge > 16000 || opt->fs < 0 || opt->fs > 16000 || opt->xdrop < 0 || opt->xdrop > 32000 ||
-	    opt->end_bonus < 0 || opt->end_bonus > 1000 || (opt->ge > 255 && opt->go + opt->ge > 32000))
+	const DpPlanOpt o = dp_plan_opt(opt);
+	if (!dp_opt_supported(o))
 		return refuse(P, MPA_ERR_UNSUPPORTED, "DP parameters outside the supported range (go <= 32000, ge, fs <= 16000, 0 <= xdrop <= 32000, 0 <= end_bonus <= 1000)");
-	// Gap-extension / frameshift penalties above 255 (-E / -F of the reference's command line, main.c:133,136) do not fit the byte
-	// the row records give them.  Such a run keeps the records' layout -- the byte then flags a stop codon -- and sweeps every call
-	// with the kernels that read it that way (glob_cands<K, true>): the stand-alone traceback kernels and, for extension calls,
-	// the block-major one-wave sweep (k_ext_huge); the packed round kernel is not used.  Slow, exact, and nobody's default.
-	P.wide_ge = opt->ge > 255 || opt->fs > 255;
+	P.wide_ge = dp_wide_ge(o);
 	const char *too_wide = ": too wide for this gap-extension penalty (columns x ge must stay below 2^19 in the int32 sweeps)";
 	P.tasks.assign((size_t)n, DTask{});
+	auto len_of = [ctg_len, ctg_stride](int32_t c) { return *(const int64_t*)((const char*)ctg_len + (size_t)c * ctg_stride); };
 	for (int64_t k = 0; k < n; ++k) {
-		const mpa_dp_task_t &x = in[k];
-		DTask &t = P.tasks[(size_t)k];
-		if (x.nl < 0 || x.al <= 0 || x.qid < 0 || x.qid >= q->n_seq || x.io < 0 || x.io > 32000) return refuse(P, MPA_ERR_ARG, "malformed DP task");
-		// the kernels address the resident genome and the query buffer with these: a window or a protein slice that leaves its
-		// contig / its query would read foreign memory (or fault the context), so it is refused here
-		if (x.vid < 0 || x.vid >= 2 * n_ctg || x.nt_off < 0 || x.nt_off + (int64_t)x.nl > *(const int64_t*)((const char*)ctg_len + (size_t)(x.vid >> 1) * ctg_stride) ||
-		    x.aa_off < 0 || (int64_t)x.aa_off + x.al > q->q_off[x.qid + 1] - q->q_off[x.qid])
-			return refuse(P, MPA_ERR_ARG, "DP task " + std::to_string(k) + " reaches outside its contig or its query");
-		t.nt_off = x.nt_off, t.vid = x.vid, t.nl = x.nl, t.al = x.al, t.flag = x.flag, t.io = x.io;
-		t.q_off = q->q_off[x.qid] + x.aa_off - q->q_off[0];     // relative to the slice the executor uploads
-		t.ncol = (x.al + 7) / 8 * 8;
-		t.out_idx = (int32_t)k;
-		// (the int32 sweeps keep the striped reference's lane segments apart by offsets of 2^20 in their scans: column * ge must stay
-		// below; checked where it matters: the traceback sweeps and the block-major extension sweep)
-		const bool seg_overflow = (int64_t)t.ncol * opt->ge >= (1 << 19);
-		// The packed int16 kernels run their gap scan on h + j*ge with saturating adds and hold go + j*ge in int16, which is only the
-		// reference's value while nothing can reach the int16 limits.  Calls that could -- with BLOSUM62 and ge = 1 more than ~2900
-		// columns, always of the huge class; with a large -E or -O already at a few dozen columns -- go to the int32 sweeps, which
-		// clamp every operation like the reference does: k_ext_huge for extension calls, the plain traceback sweep for the others.
-		const bool may_saturate = (int64_t)x.al * max_mat + (int64_t)t.ncol * opt->ge + std::max(0, opt->end_bonus) > 32000 || opt->go + (int64_t)t.ncol * opt->ge > 32000;
-		const bool packed_ok = !P.wide_ge && !may_saturate;
-		if (x.flag & (MPA_F_EXT_LEFT | MPA_F_EXT_RIGHT)) {
-			int cls = ext_class_of(t.ncol);
-			if (kn.no_split && cls >= X_SPLIT2) cls = X_HUGE;         // repeated round: no inter-workgroup hand-off (see mpa_dp_run)
-			if (!packed_ok) cls = X_HUGE;
-			if (cls == X_HUGE && seg_overflow) return refuse(P, MPA_ERR_UNSUPPORTED, "DP call " + std::to_string(k) + too_wide);
-			t.pw = cls == X_HUGE ? t.ncol : ext_columns(cls);
-			// 65..128 columns: one wave per call instead of a two-wave group per pair of calls (MPA_DP_EXT_DUAL=0: the two-wave groups)
-			if (cls == X_W2 && kn.ext_dual && !kn.antidiag) cls = X_128;
-			t.cls = cls;
-			P.ext_ids.push_back((int32_t)k);
-			P.max_nl_ext = std::max(P.max_nl_ext, x.nl);
-		} else {
-			if (!(x.flag & MPA_F_CIGAR)) return refuse(P, MPA_ERR_UNSUPPORTED, "global DP without CIGAR is not part of miniprot's path");
-			if (seg_overflow) return refuse(P, MPA_ERR_UNSUPPORTED, "DP call " + std::to_string(k) + too_wide);
-			t.pw = t.ncol;
-			t.cls = tb_class_of(t.ncol);
-			// Checkpointed traceback (dp_device.h): a call of up to 128 columns and many rows -- the gap fills across introns and the spans
-			// of accepted extensions, where nearly every row lies inside an intron -- is swept by the packed sweep and walked by k_walk.
-			// Short calls stay on the plain traceback sweep: the walk would recompute all of their rows anyway.  The packed sweep is an
-			// int16 one: calls that may saturate stay on the plain sweep too.  129..256 columns under the same predicate with lite_wide
-			// (MPA_DP_LITE_WIDE=1; the default keeps them on the plain sweep, and so does the worker pool, whose workers do not know the class).
-			const bool many_rows = kn.lite_min > 0 && packed_ok && x.nl >= kn.lite_min && x.nl >= 3;
-			if (many_rows && t.cls <= T_W2) t.cls += T_LITE16, t.pw = lite_columns(t.cls);
-			else if (many_rows && t.cls == T_W4 && kn.lite_wide && !kn.pool) t.cls = T_LITE_W4, t.pw = lite_columns(T_LITE_W4);
-			P.glob_ids.push_back((int32_t)k);
+		bool is_ext = false;
+		switch (dp_classify_call(in[k], (int32_t)k, n_ctg, len_of, q->n_seq, q->q_off, o, kn, P.tasks[(size_t)k], &is_ext)) {      // (the rules: dp_plan_core.h)
+		case DP_CALL_MALFORMED: return refuse(P, MPA_ERR_ARG, "malformed DP task");
+		case DP_CALL_OUTSIDE: return refuse(P, MPA_ERR_ARG, "DP task " + std::to_string(k) + " reaches outside its contig or its query");
+		case DP_CALL_EXT_TOO_WIDE: case DP_CALL_GLOB_TOO_WIDE: return refuse(P, MPA_ERR_UNSUPPORTED, "DP call " + std::to_string(k) + too_wide);
+		case DP_CALL_NO_CIGAR: return refuse(P, MPA_ERR_UNSUPPORTED, "global DP without CIGAR is not part of miniprot's path");
+		default: break;
 		}
+		if (is_ext) P.ext_ids.push_back((int32_t)k), P.max_nl_ext = std::max(P.max_nl_ext, in[k].nl);
+		else P.glob_ids.push_back((int32_t)k);
 	}
 	return MPA_OK;
 }
@@ -221,13 +178,12 @@ void dp_plan_chunk_waves(DpPlan &P, size_t ri)
 		}
 		r.cls[cls].cnt = (int)r.waves.size() - r.cls[cls].first;
 	}
+	r.n_list = r.list.size(), r.n_waves = r.waves.size();
 }
 
 // ---- the units of the round: the extension waves/groups of every class, the packed sweeps of the checkpointed calls and
 // (round_has_glob) the plain traceback waves of the first chunk; longest first
-// cost model: nanoseconds per row of a unit's longest call, by kind (measured: profiles/r06_dp_ns_per_row.txt, r06_wide_ns_per_row.txt)
-enum : int64_t { NS_EXT_NARROW = 160, NS_EXT_WIDE = 270, NS_EXT_SPLIT = 310, NS_EXT128 = 200, NS_LITE = 170, NS_LITE128 = 200, NS_LITE_W4 = 280, NS_GLOB = 430, NS_GLOB_WIDE = 510 };
-
+// cost model, kinds and how many neighbours share a unit: dp_plan_core.h
 struct Cost { int64_t cost; DpUnit u; };
 static bool costlier(const Cost &x, const Cost &y) { return x.cost > y.cost; }
 
@@ -242,34 +198,27 @@ static std::vector<Cost> unit_costs(const DpPlan &P, const DpPlanKnobs &kn)
 	auto add_range = [&](int kind, const WaveRange &r, int per, int64_t ns_per_row) {
 		for (int k = 0; k < r.cnt; k += per) add(kind, r.first + k, std::min(per, r.cnt - k), (int64_t)P.ewaves[r.first + k].max_nl * ns_per_row);
 	};
-	// (worker pool: the one-wave kinds are units of ONE wave descriptor each, taken by single waves; without the pool a
-	// workgroup's four waves take four neighbours of the sorted list)
-	const int per_narrow = kn.pool ? 1 : 4;
+	const bool pool = kn.pool != 0;
+	auto add_ext = [&](int cls, const WaveRange &r) { add_range(dp_ext_unit_kind(cls, pool), r, dp_ext_unit_per(cls, pool), dp_ext_unit_ns(cls)); };
 	for (int cls = X_16; cls <= X_64; ++cls)
-		if (!(cls == X_32 && kn.antidiag)) add_range(U_EXT16 + cls, P.ext[cls], per_narrow, NS_EXT_NARROW);
-	// (worker pool: a workgroup goes on to its next unit, so all four waves must leave a unit through the same barriers -- a
-	// 65..128-column group then takes a whole workgroup on the four-wave body, its waves 2 and 3 on dead columns)
-	if (kn.pool) add_range(U_EXT_W4, P.ext[X_W2], 1, NS_EXT_WIDE);
-	else add_range(U_EXT_W2, P.ext[X_W2], 2, NS_EXT_WIDE);
-	add_range(U_EXT_W4, P.ext[X_W4], 1, NS_EXT_WIDE);
+		if (!(cls == X_32 && kn.antidiag)) add_ext(cls, P.ext[cls]);
+	add_ext(X_W2, P.ext[X_W2]);
+	add_ext(X_W4, P.ext[X_W4]);
 	const int n4 = P.ext[X_SPLIT4].cnt;                           // split groups and their boundaries are numbered 1024-column groups first
 	for (int k = 0; k < n4; ++k)
-		for (int b = 0; b < 4; ++b) add(U_EXT_SPLIT, P.ext[X_SPLIT4].first + k, 1, (int64_t)P.ewaves[P.ext[X_SPLIT4].first + k].max_nl * NS_EXT_SPLIT, b, 4, k, 3 * k);
+		for (int b = 0; b < dp_ext_unit_blocks(X_SPLIT4); ++b) add(U_EXT_SPLIT, P.ext[X_SPLIT4].first + k, 1, (int64_t)P.ewaves[P.ext[X_SPLIT4].first + k].max_nl * dp_ext_unit_ns(X_SPLIT4), b, 4, k, 3 * k);
 	for (int k = 0; k < P.ext[X_SPLIT2].cnt; ++k)
-		for (int b = 0; b < 2; ++b) add(U_EXT_SPLIT, P.ext[X_SPLIT2].first + k, 1, (int64_t)P.ewaves[P.ext[X_SPLIT2].first + k].max_nl * NS_EXT_SPLIT, b, 2, n4 + k, 3 * n4 + k);
-	add_range(U_EXT128, P.ext128, per_narrow, NS_EXT128);
-	for (int c = 0; c < 4; ++c) add_range(U_LITE16 + c, P.lite[c], per_narrow, T_LITE16 + c == T_LITE128 ? NS_LITE128 : NS_LITE);
+		for (int b = 0; b < dp_ext_unit_blocks(X_SPLIT2); ++b) add(U_EXT_SPLIT, P.ext[X_SPLIT2].first + k, 1, (int64_t)P.ewaves[P.ext[X_SPLIT2].first + k].max_nl * dp_ext_unit_ns(X_SPLIT2), b, 2, n4 + k, 3 * n4 + k);
+	add_ext(X_128, P.ext128);
+	for (int c = 0; c < 4; ++c) add_range(dp_lite_unit_kind(T_LITE16 + c), P.lite[c], dp_per_narrow(pool), dp_lite_unit_ns(T_LITE16 + c));
 	if (P.round_has_glob) {
 		const DpTbChunk &r = P.chunks[0];
 		for (int cls = T_16; cls <= T_MB; ++cls) {
-			if (cls == T_W8 || cls == T_W16) continue;             // (the 512/1024-thread classes keep their own launch)
-			const int kind = cls <= T_64 ? U_GLOB16 + cls : cls == T_MB ? (int)U_GLOB_MB : cls == T_W4 || kn.pool ? (int)U_GLOB_W4 : (int)U_GLOB_W2;
-			const int per = cls == T_W2 ? (kn.pool ? 1 : 2) : cls == T_W4 ? 1 : per_narrow;
+			if (!dp_glob_in_round(cls)) continue;                    // (the 512/1024-thread classes keep their own launch)
+			const int kind = dp_glob_unit_kind(cls, pool), per = dp_glob_unit_per(cls, pool);
 			for (int k = 0; k < r.cls[cls].cnt; k += per) {
 				const GlobWave &g = r.waves[r.cls[cls].first + k];
-				int64_t cost = (int64_t)g.max_nl * (cls == T_W2 || cls == T_W4 ? NS_GLOB_WIDE : NS_GLOB);
-				if (cls == T_MB) cost *= (P.tasks[g.task[0]].ncol + 63) / 64;
-				add(kind, r.cls[cls].first + k, std::min(per, r.cls[cls].cnt - k), cost);
+				add(kind, r.cls[cls].first + k, std::min(per, r.cls[cls].cnt - k), dp_glob_unit_cost(cls, g.max_nl, P.tasks[g.task[0]].ncol));
 			}
 		}
 	}
@@ -290,10 +239,9 @@ int dp_plan_units(DpPlan &P, const DpPlanKnobs &kn, DpUnit *out)
 		P.n_group = (size_t)(std::stable_partition(cu.begin(), cu.end(), is_group) - cu.begin());
 	}
 	if (sizeof(DpUnit) * cu.size() > P.up.off - P.up.units) return refuse(P, MPA_ERR_HIP, "internal: more DP units than the staging buffer holds");
-	// the units that bound the round's duration issue ahead of the short ones they share a SIMD with (s_setprio in k_dp_round)
 	for (size_t k = 0; k < cu.size(); ++k) {
 		out[k] = cu[k].u;
-		if (kn.unit_prio) out[k].prio = cu[k].cost * 2 >= cost_max ? 3 : cu[k].cost * 4 >= cost_max ? 2 : cu[k].cost * 10 >= cost_max ? 1 : 0;   // (MPA_DP_PRIO=0: measurement)
+		if (kn.unit_prio) out[k].prio = dp_unit_prio(cu[k].cost, cost_max);   // (MPA_DP_PRIO=0: measurement)
 	}
 	P.n_units = cu.size(), P.sz.units = cu.size() * sizeof(DpUnit);
 	return MPA_OK;
@@ -322,18 +270,18 @@ std::string dp_plan_top(const DpPlan &P, const DpPlanKnobs &kn)
 // ---- bytes of every device pool; sections of the pinned staging block and of the download block
 static void size_buffers(DpPlan &P, int64_t n, size_t round_args_bytes)
 {
-	const size_t N = (size_t)n, n_glob = P.glob_ids.size(), n_ew = P.ewaves.size();
+	const size_t N = (size_t)n, n_glob = P.cnt.n_glob, n_ew = P.cnt.n_ewaves, n_prep = P.cnt.n_prep, n_huge = P.cnt.n_huge;
 	DpPlan::Pools &z = P.sz;
-	z.tasks = sizeof(DTask) * N, z.chunks = sizeof(PrepChunk) * (P.prep.size() + 1), z.qseq = (size_t)P.q_bytes + 16, z.rec = (size_t)P.rec_total * 4, z.prof = (size_t)P.prof_total * 2 + 16;
+	z.tasks = sizeof(DTask) * N, z.chunks = sizeof(PrepChunk) * (n_prep + 1), z.qseq = (size_t)P.q_bytes + 16, z.rec = (size_t)P.rec_total * 4, z.prof = (size_t)P.prof_total * 2 + 16;
 	z.waves = sizeof(ExtWave) * (n_ew + 1), z.extout = sizeof(ExtOut) * N, z.tb = (size_t)P.tb_max * 2 + 16, z.cig = (size_t)P.cig_total * 4 + 16, z.ncig = N * 4;
 	z.lite = (size_t)P.lite_total * 4 + 256, z.ckpt = (size_t)P.ck_total * 4 + 256, z.wlist = P.n_lite * 4 + 128, z.score = N * 4;
 	z.rowkey = (size_t)(P.n_wide_groups * 2 * P.key_stride * 4 + 64), z.bnd = (size_t)P.bnd_total * 16 + 16;
-	z.hkey = (size_t)P.hkey_total * 8 + 16 + (sizeof(GlobWave) + 4) * (P.huge_ids.size() + 1);         // keys, then one GlobWave and one list entry per call
+	z.hkey = (size_t)P.hkey_total * 8 + 16 + (sizeof(GlobWave) + 4) * (n_huge + 1);         // keys, then one GlobWave and one list entry per call
 	z.list = N * 4 + 128 + sizeof(GlobWave) * (n_glob + 1);                                            // a chunk's call list, then its waves
 	z.xg = P.n_split ? P.xg_bytes + P.xg_tail + 64 : 0;
 	auto al256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
 	DpPlan::Up &u = P.up;
-	u.tasks = 0, u.chunks = u.tasks + al256(sizeof(DTask) * N), u.q = u.chunks + al256(sizeof(PrepChunk) * P.prep.size());
+	u.tasks = 0, u.chunks = u.tasks + al256(sizeof(DTask) * N), u.q = u.chunks + al256(sizeof(PrepChunk) * n_prep);
 	u.waves = u.q + al256((size_t)P.q_bytes), u.list = u.waves + al256(sizeof(ExtWave) * n_ew);
 	u.gw = u.list + al256(4 * n_glob), u.units = u.gw + al256(sizeof(GlobWave) * (n_glob + 8));
 	u.off = u.units + al256(sizeof(DpUnit) * (4 * n_ew + n_glob + 64));
@@ -377,7 +325,7 @@ int dp_plan(const mpa_dp_task_t *in, int64_t n, const int64_t *ctg_len, size_t c
 	if (classify(P, in, n, ctg_len, ctg_stride, n_ctg, q, opt, kn)) return P.rc;
 	auto by_class_then_len = [&P](int32_t a, int32_t b) {
 		const DTask &x = P.tasks[a], &y = P.tasks[b];
-		return x.cls != y.cls ? x.cls < y.cls : x.nl != y.nl ? x.nl > y.nl : a < b;
+		return dp_call_before(x.cls, x.nl, a, y.cls, y.nl, b);
 	};
 	std::sort(P.ext_ids.begin(), P.ext_ids.end(), by_class_then_len);
 	std::sort(P.glob_ids.begin(), P.glob_ids.end(), by_class_then_len);
@@ -386,6 +334,7 @@ int dp_plan(const mpa_dp_task_t *in, int64_t n, const int64_t *ctg_len, size_t c
 	if (build_pen_table(opt->ie_coef, std::max(P.max_nl_ext, 2), &P.pen) < 0) return refuse(P, MPA_ERR_UNSUPPORTED, "ie_coef produces too many penalty steps");
 	plan_tb_chunks(P, kn);
 	P.q_bytes = q->q_off[q->n_seq] - q->q_off[0];
+	P.cnt = DpPlan::Counts{ (size_t)n, P.ext_ids.size(), P.glob_ids.size(), P.prep.size(), P.ewaves.size(), P.huge_ids.size() };
 	size_buffers(P, n, round_args_bytes);
 	P.round_has_glob = !P.chunks.empty() && !P.wide_ge;        // the first chunk's calls ride in the round's one launch
 	return MPA_OK;
@@ -399,9 +348,14 @@ int64_t dp_plan_serialize(DpPlan &P, const DpPlanKnobs &kn, void *buf, int64_t c
 	if (dp_plan_units(P, kn, units.data())) return P.rc;
 	units.resize(P.n_units);
 	dp_plan_stats(P);
+	return dp_plan_write(P, units, buf, cap);
+}
+
+int64_t dp_plan_write(const DpPlan &P, const std::vector<DpUnit> &units, void *buf, int64_t cap)
+{
 	std::vector<int64_t> h;
 	auto H = [&h](int64_t v) { h.push_back(v); };
-	H((int64_t)P.tasks.size()), H((int64_t)P.ext_ids.size()), H((int64_t)P.glob_ids.size()), H((int64_t)P.n_reg_glob), H((int64_t)P.n_lite), H((int64_t)P.prep.size()), H((int64_t)P.ewaves.size());
+	H((int64_t)P.tasks.size()), H((int64_t)P.cnt.n_ext), H((int64_t)P.glob_ids.size()), H((int64_t)P.n_reg_glob), H((int64_t)P.n_lite), H((int64_t)P.prep.size()), H((int64_t)P.ewaves.size());
 	H((int64_t)P.chunks.size()), H((int64_t)P.n_units), H((int64_t)P.n_group), H((int64_t)P.huge_ids.size()), H(P.wide_ge), H(P.round_has_glob);
 	H(P.max_nl), H(P.max_nl_ext), H(P.rec_total), H(P.rec_pad), H(P.prof_total), H(P.cig_total), H(P.bnd_total), H(P.hkey_total), H(P.lite_total), H(P.ck_total), H(P.tb_max);
 	H(P.key_stride), H(P.n_wide_groups), H(P.n_split), H(P.n_bound), H((int64_t)P.xg_bytes), H((int64_t)P.xg_tail), H(P.q_bytes);
@@ -446,6 +400,116 @@ int64_t dp_plan_serialize(DpPlan &P, const DpPlanKnobs &kn, void *buf, int64_t c
 		for (const Sec &s : secs) { if (s.bytes) memcpy((char*)buf + h[k], s.p, s.bytes); k += 2; }
 	}
 	return (int64_t)at;
+}
+
+// ---- the device planner's host side: what it declines, the plan from its header, the model
+const char *dp_plan_device_declines(const mpa_dpopt_t *opt, const DpPlanKnobs &kn, int64_t n)
+{
+	const DpPlanOpt o = dp_plan_opt(opt);
+	if (!dp_opt_supported(o)) return "options the planner refuses";
+	if (dp_wide_ge(o)) return "gap extension or frameshift above 255";
+	if (kn.pool) return "the worker pool";
+	if (kn.antidiag) return "the anti-diagonal measurement switch";
+	if (kn.no_split) return "a repeated round";
+	if (n <= 0 || n > MPA_DPPLAN_MAX_N) return "no calls, or more than 2^20";
+	return nullptr;
+}
+
+int64_t dp_plan_prep_bound(const mpa_dp_task_t *in, int64_t n, int64_t *max_nl, int64_t *max_al)
+{
+	int64_t chunks = 0, mnl = 0, mal = 0;
+	for (int64_t k = 0; k < n; ++k) {
+		const int64_t nl = in[k].nl > 0 ? in[k].nl : 0;
+		chunks += (nl + MPA_PREP_CHUNK_ROWS - 1) / MPA_PREP_CHUNK_ROWS, mnl = std::max(mnl, nl), mal = std::max<int64_t>(mal, in[k].al);
+	}
+	*max_nl = mnl, *max_al = mal;
+	return chunks;
+}
+
+int dp_plan_from_head(const DpDevHead &H, const int32_t *glob_ids, const mpa_qbatch_t *q, const mpa_dpopt_t *opt, const DpPlanKnobs &kn, size_t round_args_bytes, DpPlan &P)
+{
+	P = DpPlan();
+	memset(&P.pen, 0, sizeof(P.pen));
+	P.on_device = true;
+	if (H.status & DPP_REFUSED) return refuse(P, MPA_ERR_UNSUPPORTED, "a call the planner refuses");
+	if (H.status & DPP_HUGE) return refuse(P, MPA_ERR_UNSUPPORTED, "a call of the one-wave int32 extension class");
+	if (H.n_reg_glob > 1 && (size_t)H.tb_max * 2 > (size_t)kn.tb_budget) return refuse(P, MPA_ERR_UNSUPPORTED, "more than one traceback chunk");
+	P.cnt = DpPlan::Counts{ (size_t)H.n, (size_t)H.n_ext, (size_t)H.n_glob, (size_t)H.n_prep, (size_t)H.n_ewaves, 0 };
+	P.glob_ids.assign(glob_ids, glob_ids + H.n_glob);
+	P.n_reg_glob = (size_t)H.n_reg_glob, P.n_lite = (size_t)H.n_lite;
+	for (int c = 0; c < kNumExtPacked; ++c) P.ext[c] = WaveRange{ (int)H.ew_first[c], (int)H.ew_cnt[c] };
+	P.ext128 = WaveRange{ (int)H.ew_first[7], (int)H.ew_cnt[7] };
+	for (int c = 0; c < 4; ++c) P.lite[c] = WaveRange{ (int)H.ew_first[8 + c], (int)H.ew_cnt[8 + c] };
+	P.lite_w4 = WaveRange{ (int)H.ew_first[12], (int)H.ew_cnt[12] };
+	for (int c = 0; c < 5; ++c) P.walk_cnt[c] = (int32_t)H.walk_cnt[c];
+	P.max_nl = (int32_t)H.max_nl, P.max_nl_ext = (int32_t)H.max_nl_ext;
+	P.rec_total = H.rec_total, P.rec_pad = H.rec_pad, P.prof_total = H.prof_total, P.cig_total = H.cig_total, P.bnd_total = H.bnd_total, P.hkey_total = 0;
+	P.lite_total = H.lite_total, P.ck_total = H.ck_total, P.tb_max = H.tb_max;
+	P.key_stride = H.key_stride, P.n_wide_groups = H.n_wide_groups, P.n_split = H.n_split, P.n_bound = H.n_bound;
+	P.xg_bytes = (size_t)P.n_bound * P.key_stride * 16, P.xg_tail = (2 * (size_t)P.n_split + 1) * 4;
+	if (build_pen_table(opt->ie_coef, std::max(P.max_nl_ext, 2), &P.pen) < 0) { P.on_device = false; return refuse(P, MPA_ERR_UNSUPPORTED, "ie_coef produces too many penalty steps"); }
+	if (H.n_reg_glob > 0) {
+		DpTbChunk r;
+		r.first = 0, r.last = (size_t)H.n_reg_glob, r.tb_words = H.tb_max, r.n_list = (size_t)H.n_reg_glob, r.n_waves = (size_t)H.n_gw;
+		for (int c = 0; c < 8; ++c) r.cls[c] = WaveRange{ (int)H.gw_first[c], (int)H.gw_cnt[c] };
+		P.chunks.push_back(r);
+	}
+	P.q_bytes = q->q_off[q->n_seq] - q->q_off[0];
+	size_buffers(P, H.n, round_args_bytes);
+	P.round_has_glob = !P.chunks.empty();
+	P.n_units = (size_t)H.n_units, P.n_group = 0, P.sz.units = P.n_units * sizeof(DpUnit);
+	if (sizeof(DpUnit) * P.n_units > P.up.off - P.up.units) return refuse(P, MPA_ERR_HIP, "internal: more DP units than the staging buffer holds");
+	// the statistics (dp_plan_stats): sums of the classify stage
+	mpa_dp_stats_t &st = P.stats = mpa_dp_stats_t();
+	const bool round = P.n_units > 0;
+	st.n_ext = H.n_ext, st.n_glob = H.n_glob, st.cells_ext = H.st[DPP_ST_CELLS_EXT], st.cells_glob = H.st[DPP_ST_CELLS_GLOB];
+	st.alg_bytes_ext = H.st[DPP_ST_BYTES_EXT], st.alg_bytes_glob = H.st[DPP_ST_BYTES_GLOB], st.rows_prep = P.rec_total;
+	st.n_ckpt = H.st[DPP_ST_N_CKPT], st.cells_ckpt = H.st[DPP_ST_CELLS_CKPT], st.n_ckpt_wide = H.st[DPP_ST_N_WIDE], st.cells_ckpt_wide = H.st[DPP_ST_CELLS_WIDE];
+	st.cells_ext_round = round ? st.cells_ext : 0, st.cells_glob_round = round ? st.cells_glob - H.st[DPP_ST_CELLS_OWN] : 0;
+	return MPA_OK;
+}
+
+int dp_plan_model(const mpa_dp_task_t *in, int64_t n, const int64_t *ctg_len, int32_t n_ctg, const mpa_qbatch_t *q, const mpa_dpopt_t *opt, const DpPlanKnobs &kn,
+                  size_t round_args_bytes, DpPlan &P, std::vector<DpUnit> &units)
+{
+	P = DpPlan();
+	if (const char *why = dp_plan_device_declines(opt, kn, n)) return refuse(P, MPA_ERR_UNSUPPORTED, why);
+	int64_t max_nl = 0, max_al = 0;
+	const int64_t prep_bound = dp_plan_prep_bound(in, n, &max_nl, &max_al);
+	if (!dp_unit_costs_fit(max_nl, max_al)) return refuse(P, MPA_ERR_UNSUPPORTED, "unit costs that do not fit the sort key");
+	// the pools at the bounds the driver uses (dev_dp_plan), the scratch a team of one needs
+	const size_t N = (size_t)n, U = (size_t)dp_units_bound(n);
+	std::vector<DTask> tasks(N);
+	std::vector<PrepChunk> chunks((size_t)prep_bound + 1);
+	std::vector<ExtWave> waves(N + 16);
+	std::vector<int32_t> list(N), wlist(N), gids(N);
+	std::vector<GlobWave> gw(N);
+	std::vector<DpUnit> out(U), ubuf(U);
+	std::vector<uint64_t> key(N), skey, ukey(U), uskey;
+	std::vector<DpSums> bsum(N);
+	DpDevHead H;
+	memset(&H, 0, sizeof(H));
+	DpDevPlan D;
+	D.n = n, D.n_ubound = (int64_t)U, D.n_ctg = n_ctg, D.n_seq = q->n_seq, D.opt = dp_plan_opt(opt), D.kn = kn, D.raw = in, D.q_off = q->q_off, D.ctg_len = ctg_len;
+	D.tasks = tasks.data(), D.chunks = chunks.data(), D.waves = waves.data(), D.list = list.data(), D.gw = gw.data(), D.units = out.data(), D.wlist = wlist.data();
+	D.key = key.data(), D.bsum = bsum.data(), D.ubuf = ubuf.data(), D.ukey = ukey.data(), D.gids = gids.data(), D.head = &H;
+	const TeamOne one;
+	for (int64_t b = 0; b < n; ++b) dpp_classify(one, D, b);
+	skey = key, std::sort(skey.begin(), skey.end()), D.skey = skey.data();
+	for (int64_t b = 0; b < n; ++b) dpp_sums(one, D, b);
+	dpp_mid(one, D);
+	for (int64_t b = 0; b < n; ++b) dpp_layout(one, D, b);
+	for (int64_t b = 0; b < (int64_t)U; ++b) dpp_units(one, D, b);
+	uskey = ukey, std::sort(uskey.begin(), uskey.end()), D.uskey = uskey.data();
+	for (int64_t b = 0; b < H.n_units; ++b) dpp_units_out(one, D, b);
+	if (dp_plan_from_head(H, gids.data(), q, opt, kn, round_args_bytes, P)) return P.rc;
+	// what the device would have left in the pools
+	P.tasks = tasks, P.prep.assign(chunks.begin(), chunks.begin() + H.n_prep), P.ewaves.assign(waves.begin(), waves.begin() + H.n_ewaves);
+	if (!P.chunks.empty()) P.chunks[0].list.assign(list.begin(), list.begin() + H.n_reg_glob), P.chunks[0].waves.assign(gw.begin(), gw.begin() + H.n_gw);
+	P.ext_ids.resize((size_t)H.n_ext);
+	for (int64_t p = 0; p < H.n_ext; ++p) P.ext_ids[(size_t)p] = dp_key_call(skey[(size_t)p]);
+	units.assign(out.begin(), out.begin() + H.n_units);
+	return MPA_OK;
 }
 
 } // namespace mpa

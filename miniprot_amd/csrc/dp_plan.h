@@ -1,39 +1,16 @@
 // dp_plan.h -- the plan of one mpa_dp_run() call: everything the executor (dp_exec.hip) uploads, sizes and launches that follows
 // from the calls' shapes alone -- (nl, al, flag, io, vid, nt_off, aa_off, qid), contig and query lengths, the scoring options and
-// a few knobs.  Host only: no HIP, no context, no globals; an error comes back as (code, message) in the plan.
+// a few knobs.  Host only: no HIP, no context, no globals; an error comes back as (code, message) in the plan.  What the planner knows
+// about one call and one unit is dp_plan_core.h, which the device planner (MPA_GPU_DPPLAN, dp_plan_kernels.hip) compiles too.
 #pragma once
 #include <cstdint>
 #include <string>
 #include <vector>
 #include "../../include/mpamd.h"
 #include "dp_device.h"
+#include "dp_plan_core.h"       // the per-call and per-unit rules, the packing helpers, DpPlanKnobs; the stages of the device planner
 
 namespace mpa {
-
-// ---- what a class means for packing (DpClass, dp_device.h)
-static const int kNumExtPacked = 7;                                   // X_16 .. X_SPLIT4: the classes of the packed int16 sweeps, in ascending width
-inline int ext_lanes(int cls) { return cls == X_16 ? 16 : cls == X_32 ? 32 : 64; }                       // lanes per call
-inline int ext_waves(int cls) { return cls <= X_64 || cls == X_128 ? 1 : 1 << (cls - X_64); }            // waves per group: 1, 1, 1, 2, 4, 8, 16
-inline int ext_columns(int cls) { return cls == X_128 ? 128 : ext_lanes(cls) * ext_waves(cls); }         // columns the class covers (= profile row width)
-inline int ext_calls_per_wave(int cls) { return cls == X_128 ? 1 : 2 * (64 / ext_lanes(cls)); }          // ... per wave or group: two calls per lane
-inline int ext_class_of(int32_t ncol) { for (int c = X_16; c <= X_SPLIT4; ++c) if (ncol <= ext_columns(c)) return c; return X_HUGE; }
-inline int tb_class_of(int32_t ncol) { int c = T_16; while (c < T_MB && ncol > (16 << c)) ++c; return c; }   // 16, 32, ... 1024 columns, then block-major
-inline int tb_calls_per_wave(int cls) { return cls == T_16 ? 4 : cls == T_32 ? 2 : 1; }                  // the plain traceback sweep: one call per group of lanes
-inline int lite_columns(int cls) { return 16 << (cls - T_LITE16); }                                      // 16, 32, 64, 128, 256
-inline int lite_calls_per_wave(int cls) { return cls == T_LITE128 ? 1 : cls == T_LITE_W4 ? 2 : 2 * (64 / lite_columns(cls)); }
-// dwords of extension bits / checkpoints of one packed-sweep descriptor whose longest call has max_nl rows (layout: dp_device.h)
-inline int64_t lite_bits_dwords(int cls, int32_t max_nl) { return cls == T_LITE_W4 ? lite_wide_bits_dwords(max_nl) : ((int64_t)max_nl / 3 + 2) * 64; }
-inline int64_t lite_ckpt_dwords(int cls, int32_t max_nl) { return cls == T_LITE_W4 ? lite_wide_ckpt_dwords(max_nl) : (int64_t)(max_nl > 3 ? (max_nl - 3) / MPA_TB_BLOCK : 0) * 9 * 64; }
-
-// values the executor has when it plans (the environment is read by the executor: at context creation, or once per process)
-struct DpPlanKnobs {
-	int32_t lite_min = 384, lite_wide = 0;      // checkpointed traceback: from this many rows; 129..256 columns included
-	int32_t no_split = 0;                       // repeated round: no inter-workgroup hand-off
-	int32_t antidiag = 0;                       // (measurement) the 32-column extension class runs on k_ext_antidiag
-	int32_t pool = 0;                           // the worker pool takes the round's units (MPA_DP_POOL)
-	int32_t ext_dual = 1, unit_prio = 1;        // MPA_DP_EXT_DUAL, MPA_DP_PRIO
-	int64_t tb_budget = (int64_t)8 << 30;       // bytes of traceback matrix per chunk
-};
 
 struct WaveRange { int first = 0, cnt = 0; };                       // descriptors [first, first + cnt) of ExtWave[] / of a chunk's GlobWave[]
 
@@ -44,12 +21,17 @@ struct DpTbChunk {
 	// filled by dp_plan_chunk_waves():
 	std::vector<int32_t> list;                  // the calls in wave order: what k_backtrack walks
 	std::vector<GlobWave> waves;
+	size_t n_list = 0, n_waves = 0;             // ... their lengths (a plan made on the device has only these: the lists are in the pools)
 	WaveRange cls[8];                           // by DpClass T_16 .. T_MB
 };
 
 struct DpPlan {
 	int rc = MPA_OK;
 	std::string err;
+	// A plan made on the device (dev_dp_plan, dp_exec.hip): tasks, prep, ewaves, the chunk's list and waves, the units and the walk list are
+	// in the executor's pools already and the vectors below stay empty, except glob_ids.  The counts hold for both kinds of plan.
+	bool on_device = false;
+	struct Counts { size_t n = 0, n_ext = 0, n_glob = 0, n_prep = 0, n_ewaves = 0, n_huge = 0; } cnt;
 	bool wide_ge = false;                       // ge or fs above 255: the int32 sweeps take every call
 	std::vector<DTask> tasks;                   // indexed like the caller's array
 	std::vector<int32_t> ext_ids, glob_ids;     // sorted by (class, rows descending, index); glob_ids: plain sweep [0, n_reg_glob), then checkpointed
@@ -92,10 +74,31 @@ void dp_plan_chunk_waves(DpPlan &plan, size_t ri);
 int dp_plan_units(DpPlan &plan, const DpPlanKnobs &kn, DpUnit *out);
 // and the statistics (behind dp_plan_units: the *_round cells depend on whether the round has units).
 void dp_plan_stats(DpPlan &plan);
+// A plan from what the device planner left (DpDevHead): every count, total and range, the penalty table, pool sizes and staging
+// sections with size_buffers()'s arithmetic, the statistics.  glob_ids: the sorted traceback calls (n_glob of the head).  Returns
+// plan.rc; MPA_ERR_UNSUPPORTED (plan.err says why) when the plan is one the device planner declines: X_HUGE calls, a refused call, more
+// than one traceback chunk.
+int dp_plan_from_head(const DpDevHead &head, const int32_t *glob_ids, const mpa_qbatch_t *q, const mpa_dpopt_t *opt, const DpPlanKnobs &kn, size_t round_args_bytes, DpPlan &plan);
+// why the device planner does not take a round before looking at its calls (nullptr: it does)
+const char *dp_plan_device_declines(const mpa_dpopt_t *opt, const DpPlanKnobs &kn, int64_t n);
+// The model of the device planner: its stages (dp_plan_core.h) with a team of one on host memory, into a plan whose vectors hold what
+// the device would have left in the pools; units: the round's unit list.  Returns as dp_plan_from_head.
+int dp_plan_model(const mpa_dp_task_t *in, int64_t n, const int64_t *ctg_len, int32_t n_ctg, const mpa_qbatch_t *q, const mpa_dpopt_t *opt, const DpPlanKnobs &kn,
+                  size_t round_args_bytes, DpPlan &plan, std::vector<DpUnit> &units);
+// pool bounds of the device planner, which sizes before it knows the plan: prep chunks of the n calls of `in` at most
+int64_t dp_plan_prep_bound(const mpa_dp_task_t *in, int64_t n, int64_t *max_nl, int64_t *max_al);
 // (MPA_DP_TOP) one line naming the round's costliest units by kind
 std::string dp_plan_top(const DpPlan &plan, const DpPlanKnobs &kn);
 // the whole plan as mpa_dbg_dp_plan() hands it out (mpamd.h): runs the later stages, returns the bytes it takes (written when they fit cap)
 // or plan.rc
 int64_t dp_plan_serialize(DpPlan &plan, const DpPlanKnobs &kn, void *buf, int64_t cap);
+// ... the serialisation alone, of a plan whose later stages have run (dp_plan_serialize, or the device planner's vectors filled in)
+int64_t dp_plan_write(const DpPlan &plan, const std::vector<DpUnit> &units, void *buf, int64_t cap);
+
+// ---- dp_exec.hip, for the test hook mpa_dbg_dp_plan_device (dpplan_dbg.cpp)
+size_t dp_round_args_bytes();            // the size of the worker pool's argument block: the model's round_args_bytes
+// the device planner on a context, what it left serialised like dp_plan_serialize; 1: it declined (the last error says why)
+int64_t dev_dp_plan_dbg(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, const mpa_qbatch_t *q, int64_t n, const mpa_dp_task_t *in,
+                        const DpPlanKnobs &kn, void *buf, int64_t cap);
 
 } // namespace mpa

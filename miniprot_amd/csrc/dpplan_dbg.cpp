@@ -1,0 +1,28 @@
+// dpplan_dbg.cpp -- mpa_dbg_dp_plan_device (include/mpamd_dbg.h), the test hook of MPA_GPU_DPPLAN: a task table through the device planner
+// of a DP round (dev_dp_plan_dbg of dp_exec.hip) or, without a context, through its model -- the same stages with a team of one on the
+// host (dp_plan_model of dp_plan.cpp).  Built into libmpamd_dbg.so: the C ABI of libmpamd.so stays what it was.
+#include <vector>
+#include "mpa_internal.h"
+#include "dp_plan.h"
+#include "../../include/mpamd_dbg.h"
+
+using namespace mpa;
+
+extern "C" int64_t mpa_dbg_dp_plan_device(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, int32_t n_seq, const int64_t *q_off, int64_t n,
+                                          const mpa_dp_task_t *tasks, const int64_t *knobs, void *buf, int64_t cap)
+{
+	return mpa::guarded<int64_t>(MPA_ERR_HIP, [&]() -> int64_t {
+		if (!opt || !q_off || !knobs || n_seq < 0 || n_ctg < 0 || (n_ctg > 0 && !ctg_len) || (n > 0 && !tasks)) { set_error("mpa_dbg_dp_plan_device: missing arguments"); return MPA_ERR_ARG; }
+		DpPlanKnobs kn;
+		kn.lite_min = (int32_t)knobs[0], kn.lite_wide = (int32_t)knobs[1], kn.no_split = (int32_t)knobs[2], kn.antidiag = (int32_t)knobs[3], kn.pool = (int32_t)knobs[4];
+		kn.ext_dual = (int32_t)knobs[5], kn.unit_prio = (int32_t)knobs[6], kn.tb_budget = knobs[7];
+		const mpa_qbatch_t q{ n_seq, nullptr, q_off };
+		if (ctx) return dev_dp_plan_dbg(ctx, opt, n_ctg, ctg_len, &q, n, tasks, kn, buf, cap);
+		DpPlan plan;
+		std::vector<DpUnit> units;
+		const int rc = dp_plan_model(tasks, n, ctg_len, n_ctg, &q, opt, kn, dp_round_args_bytes(), plan, units);
+		if (rc == MPA_ERR_UNSUPPORTED) { set_error("device DP plan: " + plan.err); return MPA_DBG_DP_PLAN_DECLINED; }
+		if (rc != MPA_OK) { set_error(plan.err); return rc; }
+		return dp_plan_write(plan, units, buf, cap);
+	});
+}
