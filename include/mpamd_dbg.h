@@ -1,5 +1,5 @@
-/* mpamd_dbg.h -- the test hooks of MPA_GPU_SPANS and MPA_GPU_DPPLAN.  They are not part of the C ABI of libmpamd.so (include/mpamd.h):
- * they are built from miniprot_amd/csrc/spans_dbg.cpp and dpplan_dbg.cpp into a library of its own, libmpamd_dbg.so, next to libmpamd.so
+/* mpamd_dbg.h -- the test hooks of MPA_GPU_SPANS, MPA_GPU_DPPLAN and MPA_GPU_ROUND2.  They are not part of the C ABI of libmpamd.so (include/mpamd.h):
+ * they are built from miniprot_amd/csrc/spans_dbg.cpp, dpplan_dbg.cpp and round2_dbg.cpp into a library of its own, libmpamd_dbg.so, next to libmpamd.so
  * and linked against it. */
 #ifndef MPAMD_DBG_H
 #define MPAMD_DBG_H
@@ -37,6 +37,24 @@ int mpa_dbg_spans(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, 
 #define MPA_DBG_DP_PLAN_DECLINED 1
 int64_t mpa_dbg_dp_plan_device(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, int32_t n_seq, const int64_t *q_off, int64_t n,
                                const mpa_dp_task_t *tasks, const int64_t *knobs, void *buf, int64_t cap);
+
+/* A DP round from device-resident tasks (MPA_GPU_ROUND2): the arguments of mpa_dp_run.  On a context the hook
+ * puts the tasks into a device pool, has their bounds reduced there (k_task_bounds), plans the round from the tasks in place, runs it
+ * with the result records and the dense CIGAR pool assembled on the device in front of the round's one wait, and only then fetches the
+ * dense pool.  rst[n], *cigar_pool (mpa_free) and *n_pool are what mpa_dp_run returns for the same table.  rec[MPA_DBG_ROUND2_REC] says what
+ * the call did: [0] host waits of the planner, [1] host waits of the round behind it, [2] bytes uploaded by planner and round, [3] bytes
+ * of task records among them, [4] bytes downloaded by planner and round, [5] bytes of CIGAR pool among them, [6] bytes of the explicit
+ * pool fetch behind the round, [7] prep-chunk bound, [8] largest nl, [9] largest al of the tasks as reduced, [10] words of the dense pool.
+ * ctx == NULL: no DP runs; made_up holds what the kernels would have left -- ext_out (nt_len, aa_len, score, flags per call), score and
+ * n_cigar per call, gids[n_glob] the traceback calls in the planner's order -- and the stages of dp_results_core.h run on it with a
+ * team of one: rst[n], *n_pool, rec[7..10]; *cigar_pool stays NULL.  mi, opt and q may be NULL then.
+ * Returns MPA_OK, a negative MPA_ERR_* code, or MPA_DBG_ROUND2_DECLINED (1) when the round is one that falls back to mpa_dp_run: whatever the
+ * device planner declines (mpa_dbg_dp_plan_device above), a pool or pinned block that cannot grow, a repeated round. */
+#define MPA_DBG_ROUND2_DECLINED 1
+#define MPA_DBG_ROUND2_REC 12
+typedef struct { const int32_t *ext_out, *score, *n_cigar, *gids; int64_t n_glob; } mpa_dbg_dp_outputs_t;
+int mpa_dbg_dp_run_resident(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *opt, const mpa_qbatch_t *q, int64_t n, const mpa_dp_task_t *tasks,
+                            const mpa_dbg_dp_outputs_t *made_up, mpa_dp_rst_t *rst, uint32_t **cigar_pool, int64_t *n_pool, int64_t *rec);
 
 #ifdef __cplusplus
 }

@@ -488,7 +488,7 @@ def refine_chains(ctx, idx, mo, queries, wins):
 CLAIM_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p)
 
 
-DBG_LIB_PATH = os.path.join(_HERE, "libmpamd_dbg.so")   # the test hook of MPA_GPU_SPANS: a library of its own, linked against libmpamd.so
+DBG_LIB_PATH = os.path.join(_HERE, "libmpamd_dbg.so")   # the test hooks of the device steps: a library of its own, linked against libmpamd.so
 _dbg_lib = None
 
 
@@ -552,6 +552,43 @@ def dbg_dp_plan_device(ctx, dpopt, ctg_len, q_off, tasks, knobs):
     if got != need:
         return int(got), last_error()
     return buf.tobytes()
+
+
+ROUND2_DECLINED = 1   # MPA_DBG_ROUND2_DECLINED (include/mpamd_dbg.h)
+ROUND2_REC = ("plan_waits", "round_waits", "bytes_up", "task_bytes_up", "bytes_down", "pool_bytes_down", "pool_bytes_fetched", "prep_bound", "max_nl", "max_al", "n_pool", "reserved")
+
+
+class _DpOutputs(C.Structure):
+    _fields_ = [("ext_out", C.c_void_p), ("score", C.c_void_p), ("n_cigar", C.c_void_p), ("gids", C.c_void_p), ("n_glob", C.c_int64)]
+
+
+def dbg_dp_run_resident(ctx, idx, dpopt, queries, tasks, made_up=None):
+    """mpa_dbg_dp_run_resident(): a DP round from device-resident tasks (MPA_GPU_ROUND2) -- the arguments of dp_run().  On a context the
+    round is planned from the tasks in a device pool and its result records and dense CIGAR pool are assembled on the device; returns
+    (results, cigar_pool, record) with the record a dict of ROUND2_REC, (ROUND2_DECLINED, reason) for a round that falls back to
+    mpa_dp_run, or (code, message) of an error.  ctx None: no DP runs -- made_up = (ext_out int32 [n, 4], score int32 [n], n_cigar int32
+    [n], gids int32 [n_glob]) goes through the result stages with a team of one; idx, dpopt and queries may be None; the pool is empty."""
+    tasks = np.ascontiguousarray(tasks, dtype=DP_TASK)
+    rst = np.zeros(len(tasks), dtype=DP_RST)
+    pool = C.POINTER(C.c_uint32)()
+    n_pool = C.c_int64(0)
+    rec = np.zeros(len(ROUND2_REC), dtype=np.int64)
+    f = dbg_lib().mpa_dbg_dp_run_resident
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    mu, keep = None, None
+    if made_up is not None:
+        keep = [np.ascontiguousarray(x, dtype=np.int32) for x in made_up]
+        mu = _DpOutputs(keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data, keep[3].ctypes.data if len(keep[3]) else None, len(keep[3]))
+    rc = f(ctx.h if ctx else None, idx.h if idx else None, C.byref(dpopt) if dpopt is not None else None, C.byref(queries.c) if queries is not None else None,
+           len(tasks), tasks.ctypes.data, C.byref(mu) if mu is not None else None, rst.ctypes.data, C.byref(pool), C.byref(n_pool), rec.ctypes.data)
+    if rc != 0:
+        return int(rc), last_error()
+    words = n_pool.value if pool else 0
+    cig = np.ctypeslib.as_array(pool, (max(words, 1),))[:words].copy() if words else np.zeros(0, np.uint32)
+    if pool:
+        lib().mpa_free(pool)
+    return rst, cig, dict(zip(ROUND2_REC, (int(x) for x in rec)))
 
 
 def map_batches(ctx, idx, mo, batches, n_threads=1, keep_results=False, want_text=True, claim=None):

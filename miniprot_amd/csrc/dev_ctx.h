@@ -132,6 +132,7 @@ struct mpa_ctx_s {
 	hipStream_t seed_stream = nullptr;        // high-priority stream of the seeding kernels: short, and must not queue behind DP tails
 	bool no_split = false;                    // this mpa_dp_run() repeats a round whose workgroup hand-off timed out: 512/1024-column calls go to k_ext_huge
 	int64_t handoff_retries = 0;              // how often that has happened on this context (mpa_dp_handoff_retries)
+	std::atomic<int64_t> n_waits{0};          // host waits on this context's streams so far (wait_stream): a resident DP round reports its own
 	std::vector<SeedHold*> holds;             // result holders of the stream pipeline's batches (owned; ctx_seed_hold)
 	struct PoolHints { std::atomic<size_t> dev[3][96]; };
 	PoolHints *hints = nullptr;               // (root context only, owned) high-water marks per pipeline role and pool

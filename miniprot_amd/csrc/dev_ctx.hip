@@ -64,6 +64,7 @@ int DevBuf::ensure_exact(size_t bytes)
 // event and SLEEPS 100 us between polls after a short burst of immediate ones.
 hipError_t wait_stream(mpa_ctx_t *ctx, hipStream_t s)
 {
+	ctx->n_waits.fetch_add(1, std::memory_order_relaxed);
 	if (!ctx->wait_ev) return hipStreamSynchronize(s);
 	hipError_t e = hipEventRecord(ctx->wait_ev, s);
 	if (e != hipSuccess) return e;

@@ -10,7 +10,9 @@
 //   3. next to it on side streams: k_ext_huge + k_ext_replay (wider calls, and whatever the int16 sweeps may not take), k_lite_wide
 //      (129..256-column checkpointed calls), the 512/1024-thread traceback classes, the anti-diagonal prototype,
 //   4. k_backtrack per traceback chunk (chunks after the first: stand-alone k_glob_* launches, serial), k_walk for the
-//      checkpointed calls, one download, one host wait, k_cigar_gather,
+//      checkpointed calls, one download, one host wait, k_cigar_gather (MPA_GPU_ROUND2=1, a batch's round 2 from tasks that are on the
+//      device: the result records and the dense pool's offsets by the kernels of dp_results_kernels.hip and the gather in front of
+//      that one wait, the dense pool left on the device -- dp_run_resident() below),
 // bracketed by HIP events (mpa_dp_last_stats feeds bench.py's roofline record).  mpa_dp_run_impl is that list of phases.  There is no
 // CPU fallback here by design.  This unit holds the DP only (kernels: dp_kernels.hip, dp_antidiag.hip, gs32_exec.hip); the context
 // and its pools are dev_ctx.hip, the other stages seed_run.hip, refine_run.hip and index_run.hip.
@@ -19,6 +21,7 @@
 #include "dp_kernels.hip"
 #include "dp_antidiag.hip"
 #include "dp_plan_kernels.hip"
+#include "dp_results_kernels.hip"
 
 namespace mpa {
 
@@ -232,6 +235,14 @@ void mpa_dp_total_stats(mpa_ctx_t *ctx, mpa_dp_stats_t *st, int reset)
 
 #define MPA_RETRY_NO_SPLIT (-100)   /* internal: repeat the round without split extension calls */
 
+// A round from device-resident tasks: what goes in, what the phases count, where the device's result records are.
+struct Resident {
+	DpResidentIn in;
+	DpResidentRec rec;
+	const int32_t *d_gids = nullptr;            // the sorted traceback calls where the device planner left them
+	const mpa_dp_rst_t *d_rst = nullptr;
+};
+
 // What the phases of one mpa_dp_run() call share: the plan, the staging blocks, the kernels' argument structs, which side streams
 // carry what, and the event times collected so far.
 struct DpRun {
@@ -239,7 +250,9 @@ struct DpRun {
 	hipStream_t s;
 	DpPlan &plan;
 	DpPlanKnobs kn;
-	const mpa_dp_task_t *in;                    // the caller's array
+	const mpa_dp_task_t *in;                    // the caller's array (null for a resident round)
+	struct Resident *rz = nullptr;              // (MPA_GPU_ROUND2) a round from device-resident tasks: results assembled on the device
+	size_t dn_res = 0;                          // ... where its header and result records land in the download block
 	char *hup = nullptr, *hdn = nullptr;        // pinned staging: host -> device (plan.up), device -> host (plan.dn)
 	DpConst dc;
 	ExtArgs ea;
@@ -280,6 +293,18 @@ static hipStream_t begin_side(DpRun &R, bool is_ext)
 }
 static void end_side(DpRun &R) { const int k = R.launches.back().side; (void)hipEventRecord(R.ctx->lev[2 * k + 1], R.side_stream(k)); }
 
+// a resident round's results pool (ctx->cigoff): off[n_glob] | call_off[n] | bsum[blocks] | head | rst[n] (header and records: one download)
+struct ResLayout {
+	size_t off, call_off, bsum, head, rst, end, n;
+	ResLayout(size_t n_, size_t n_glob) : n(n_)
+	{
+		auto up64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
+		off = 0, call_off = up64(8 * n_glob), bsum = call_off + up64(8 * n), head = bsum + up64(8 * ((size_t)dp_blocks((int64_t)n_glob, TeamWG::W) + 1));
+		rst = head + 64, end = rst + up64(sizeof(mpa_dp_rst_t) * n) + 64;
+	}
+	size_t down_bytes() const { return 64 + sizeof(mpa_dp_rst_t) * n; }
+};
+
 // ---- 2. pools and staging at the sizes the plan asks for
 static int dp_size_pools(DpRun &R)
 {
@@ -295,6 +320,13 @@ static int dp_size_pools(DpRun &R)
 	// staged by the runtime and the host never waits for one: a DP round is enqueued in one go and waited for once.
 	if ((rc = ctx->h_up.ensure(R.plan.up.end + 256))) return rc;
 	R.hup = ctx->h_up.as<char>();
+	if (R.rz) {
+		// the dense pool at the plan's bound, the sum of cig_cap (its size is not known before the wait); offsets | offsets by call | block
+		// sums | header | result records in one pool; the download block with room for header and records
+		const ResLayout L((size_t)R.plan.cnt.n, R.plan.glob_ids.size());
+		R.dn_res = (R.plan.dn.end + 63) & ~(size_t)63;
+		if ((rc = ctx->cigd.ensure((size_t)R.plan.cig_total * 4 + 16)) || (rc = ctx->cigoff.ensure(L.end)) || (rc = ctx->h_down.ensure(R.dn_res + L.down_bytes()))) return rc;
+	}
 	return MPA_OK;
 }
 
@@ -599,6 +631,38 @@ static int dp_walk(DpRun &R)
 	return MPA_OK;
 }
 
+// ---- 6'. (a resident round) behind the round's last kernel and in front of its one wait: the dense pool's offsets scanned over the sorted
+// traceback calls, every call's result record, the CIGARs gathered from the device's own offsets, header and records into the download
+// block.  The dense pool stays in ctx->cigd.
+static int dp_results_enqueue(DpRun &R)
+{
+	mpa_ctx_t *ctx = R.ctx;
+	DpPlan &P = R.plan;
+	hipStream_t s = R.s;
+	const size_t n = P.cnt.n, n_glob = P.glob_ids.size();
+	const ResLayout L(n, n_glob);
+	static_assert(DPR_NHEAD * 8 <= 64, "the header has 64 bytes of the pool");
+	char *X = ctx->cigoff.as<char>();
+	DpResDev D;
+	D.n = (int64_t)n, D.n_glob = (int64_t)n_glob, D.tasks = ctx->tasks.as<DTask>(), D.gids = R.rz->d_gids;
+	D.eo = ctx->extout.as<ExtOut>(), D.sc = ctx->score.as<int32_t>(), D.nc = ctx->ncig.as<int32_t>();
+	D.off = (int64_t*)(X + L.off), D.call_off = (int64_t*)(X + L.call_off), D.bsum = (int64_t*)(X + L.bsum), D.head = (int64_t*)(X + L.head), D.rst = (mpa_dp_rst_t*)(X + L.rst);
+	HIP_TRY(hipMemsetAsync(D.head, 0, 64, s));
+	const dim3 wg(TeamWG::W), g_glob((unsigned)dp_blocks((int64_t)n_glob, TeamWG::W)), g_calls((unsigned)dp_blocks((int64_t)n, TeamWG::W));
+	if (n_glob) {
+		hipLaunchKernelGGL(k_dpr_sums, g_glob, wg, 0, s, D);
+		hipLaunchKernelGGL(k_dpr_mid, dim3(1), wg, 0, s, D);
+		hipLaunchKernelGGL(k_dpr_offsets, g_glob, wg, 0, s, D);
+	}
+	hipLaunchKernelGGL(k_dpr_records, g_calls, wg, 0, s, D);
+	if (n_glob) hipLaunchKernelGGL(k_cigar_gather, dim3((unsigned)n_glob), dim3(64), 0, s, ctx->tasks.as<DTask>(), D.gids, D.off, (int32_t)n_glob,
+	                               ctx->ncig.as<int32_t>(), ctx->cig.as<uint32_t>(), ctx->cigd.as<uint32_t>());
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(R.hdn + R.dn_res, X + L.head, L.down_bytes(), hipMemcpyDeviceToHost, s));
+	R.rz->d_rst = D.rst, R.rz->rec.bytes_down += (int64_t)L.down_bytes();
+	return MPA_OK;
+}
+
 // ---- 7. join the side streams; results into pinned memory behind the last kernel (extension outputs, traceback scores and
 // CIGAR lengths, hand-off error flag, the walk's block count); the one wait of the round; kernel times
 static int dp_join_and_download(DpRun &R)
@@ -613,13 +677,15 @@ static int dp_join_and_download(DpRun &R)
 	if ((rc = ctx->h_down.ensure(P.dn.end))) return rc;
 	char *hdn = R.hdn = ctx->h_down.as<char>();
 	*(int32_t*)(hdn + P.dn.err) = 0;
-	if (P.cnt.n_ext) HIP_TRY(hipMemcpyAsync(hdn + P.dn.eo, ctx->extout.p, sizeof(ExtOut) * n, hipMemcpyDeviceToHost, s));
-	if (P.cnt.n_glob) {
+	if (R.rz) { if ((rc = dp_results_enqueue(R))) return rc; }           // (resident: the records come down instead of what they are made from)
+	else if (P.cnt.n_ext) HIP_TRY(hipMemcpyAsync(hdn + P.dn.eo, ctx->extout.p, sizeof(ExtOut) * n, hipMemcpyDeviceToHost, s));
+	if (P.cnt.n_glob && !R.rz) {
 		HIP_TRY(hipMemcpyAsync(hdn + P.dn.sc, ctx->score.p, n * 4, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipMemcpyAsync(hdn + P.dn.nc, ctx->ncig.p, n * 4, hipMemcpyDeviceToHost, s));
 	}
 	if (P.n_split) HIP_TRY(hipMemcpyAsync(hdn + P.dn.err, R.wa.err, 4, hipMemcpyDeviceToHost, s));
 	*(unsigned long long*)(hdn + P.dn.wb) = 0;
+	if (R.rz) R.rz->rec.bytes_down += (P.n_split ? 4 : 0) + (P.n_lite ? 8 : 0);
 	if (P.n_lite) HIP_TRY(hipMemcpyAsync(hdn + P.dn.wb, (char*)ctx->wlist.p + ((P.n_lite * 4 + 63) & ~(size_t)63), 8, hipMemcpyDeviceToHost, s));
 	R.mark("    dp: round enqueued");
 	HIP_TRY(wait_stream(ctx, s));
@@ -673,13 +739,8 @@ static int dp_assemble(DpRun &R, mpa_dp_rst_t *rst, uint32_t **cigar_pool, int64
 	std::vector<int64_t> off_of(P.cnt.n, 0);
 	for (size_t k = 0; k < n_glob; ++k) off_of[P.glob_ids[k]] = dense_off[k];
 	for (size_t k = 0; k < P.cnt.n; ++k) {
-		const mpa_dp_task_t &t = R.in[k];                                  // (mode and shape: the caller's own record)
-		mpa_dp_rst_t &o = rst[k];
-		if (t.flag & (MPA_F_EXT_LEFT | MPA_F_EXT_RIGHT)) {
-			o.nt_len = eo[k].nt_len, o.aa_len = eo[k].aa_len, o.score = eo[k].score, o.n_cigar = 0, o.cigar_off = 0;
-		} else {
-			o.nt_len = t.nl, o.aa_len = t.al, o.score = sc[k], o.n_cigar = nc[k], o.cigar_off = off_of[k];
-		}
+		const mpa_dp_task_t &t = R.in[k];                                  // (mode and shape: the caller's own record; the rule: dp_results_core.h)
+		rst[k] = dp_result_of(t.flag, t.nl, t.al, (int64_t)k, eo, sc, nc, off_of[k]);
 	}
 	if (cigar_pool) *cigar_pool = pool; else free(pool);
 	if (n_pool) *n_pool = pool_n;
@@ -734,23 +795,25 @@ static DpPlanKnobs dp_plan_knobs(const mpa_ctx_t *ctx)
 // executor's offset) / units / wlist hold the plan.  MPA_ERR_UNSUPPORTED: declined (the last error says why), nothing the host planner
 // needs was touched.
 static int dev_dp_plan_run(mpa_ctx_t *ctx, hipStream_t s, const int64_t *d_ctg_len, const int64_t *h_ctg_len, int32_t n_ctg, const mpa_qbatch_t *q, const mpa_dpopt_t *opt,
-                           const DpPlanKnobs &kn, int64_t n, const mpa_dp_task_t *in, const DpDevHead **head, const int32_t **gids, size_t *bytes_up, size_t *bytes_down)
+                           const DpPlanKnobs &kn, int64_t n, const mpa_dp_task_t *in, const DpDevHead **head, const int32_t **gids, size_t *bytes_up, size_t *bytes_down,
+                           Resident *rz = nullptr)
 {
 	if (const char *why = dp_plan_device_declines(opt, kn, n)) { set_error(std::string("device DP plan: ") + why); return MPA_ERR_UNSUPPORTED; }
 	if (q->n_seq < 0 || n_ctg < 0) { set_error("device DP plan: no queries or contigs"); return MPA_ERR_UNSUPPORTED; }
 	const size_t N = (size_t)n, U = (size_t)dp_units_bound(n), nb = (size_t)dp_blocks(n, TeamWG::W);
 	auto al256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
-	// what goes up, in one block
-	const size_t up_raw = 0, up_qoff = up_raw + al256(sizeof(mpa_dp_task_t) * N), up_ctg = up_qoff + al256(8 * ((size_t)q->n_seq + 1));
+	// what goes up, in one block (rz: the tasks are read where they are -- no task bytes are staged or uploaded)
+	const size_t up_raw = 0, up_qoff = up_raw + (rz ? 0 : al256(sizeof(mpa_dp_task_t) * N)), up_ctg = up_qoff + al256(8 * ((size_t)q->n_seq + 1));
 	const size_t up_end = up_ctg + (d_ctg_len ? 0 : al256(8 * (size_t)n_ctg));
 	tl_alloc_failed = false;
 	auto declined_alloc = [](int rc) { if (tl_alloc_failed) { tl_alloc_failed = false; return (int)MPA_ERR_UNSUPPORTED; } return rc; };
 	int rc;
 	if ((rc = ctx->h_dpp_up.ensure(up_end + 256))) return MPA_ERR_UNSUPPORTED;
 	char *hup = ctx->h_dpp_up.as<char>();
-	memcpy(hup + up_raw, in, sizeof(mpa_dp_task_t) * N);
-	int64_t max_nl = 0, max_al = 0;
-	const int64_t prep_bound = dp_plan_prep_bound((const mpa_dp_task_t*)(hup + up_raw), n, &max_nl, &max_al);
+	if (!rz) memcpy(hup + up_raw, in, sizeof(mpa_dp_task_t) * N);
+	int64_t max_nl = rz ? rz->in.max_nl : 0, max_al = rz ? rz->in.max_al : 0;
+	const int64_t prep_bound = rz ? rz->in.prep_bound : dp_plan_prep_bound((const mpa_dp_task_t*)(hup + up_raw), n, &max_nl, &max_al);
+	if (prep_bound < 0 || prep_bound > (int64_t)N << 21) { set_error("device DP plan: impossible bounds of the task list"); return MPA_ERR_UNSUPPORTED; }
 	if (!dp_unit_costs_fit(max_nl, max_al)) { set_error("device DP plan: unit costs that do not fit the sort key"); return MPA_ERR_UNSUPPORTED; }
 	memcpy(hup + up_qoff, q->q_off, 8 * ((size_t)q->n_seq + 1));
 	if (!d_ctg_len && n_ctg > 0) memcpy(hup + up_ctg, h_ctg_len, 8 * (size_t)n_ctg);
@@ -771,7 +834,7 @@ static int dev_dp_plan_run(mpa_ctx_t *ctx, hipStream_t s, const int64_t *d_ctg_l
 	char *X = ctx->dpp.as<char>();
 	DpDevPlan D;
 	D.n = n, D.n_ubound = (int64_t)U, D.n_ctg = n_ctg, D.n_seq = q->n_seq, D.opt = dp_plan_opt(opt), D.kn = kn;
-	D.raw = (const mpa_dp_task_t*)(X + o_up + up_raw), D.q_off = (const int64_t*)(X + o_up + up_qoff), D.ctg_len = d_ctg_len ? d_ctg_len : (const int64_t*)(X + o_up + up_ctg);
+	D.raw = rz ? rz->in.d_tasks : (const mpa_dp_task_t*)(X + o_up + up_raw), D.q_off = (const int64_t*)(X + o_up + up_qoff), D.ctg_len = d_ctg_len ? d_ctg_len : (const int64_t*)(X + o_up + up_ctg);
 	D.tasks = ctx->tasks.as<DTask>(), D.chunks = ctx->chunks.as<PrepChunk>(), D.waves = ctx->waves.as<ExtWave>(), D.list = ctx->list.as<int32_t>();
 	D.gw = (GlobWave*)((char*)ctx->list.p + ((N * 4 + 63) & ~(size_t)63));                    // (where dp_tb_chunks puts a chunk's waves)
 	D.units = ctx->units.as<DpUnit>(), D.wlist = ctx->wlist.as<int32_t>();
@@ -794,16 +857,17 @@ static int dev_dp_plan_run(mpa_ctx_t *ctx, hipStream_t s, const int64_t *d_ctg_l
 	HIP_TRY(wait_stream(ctx, s));
 	*head = (const DpDevHead*)hdn, *gids = (const int32_t*)(hdn + (o_gids - o_head));
 	*bytes_up = up_end, *bytes_down = down_bytes;
+	if (rz) rz->d_gids = D.gids, rz->rec.task_bytes_up = (int64_t)(up_qoff - up_raw);
 	return MPA_OK;
 }
 
 // the round's plan from the device planner: MPA_OK (plan.on_device), MPA_ERR_UNSUPPORTED when it declines, else an error
 static int dev_dp_plan(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *opt, const mpa_qbatch_t *q, const DpPlanKnobs &kn, int64_t n, const mpa_dp_task_t *in, DpPlan &plan,
-                       size_t *bytes_up, size_t *bytes_down)
+                       size_t *bytes_up, size_t *bytes_down, Resident *rz = nullptr)
 {
 	const DpDevHead *head = nullptr;
 	const int32_t *gids = nullptr;
-	int rc = dev_dp_plan_run(ctx, ctx->stream, mi->dev[ctx->device]->ctg_len, nullptr, (int32_t)mi->ctg.size(), q, opt, kn, n, in, &head, &gids, bytes_up, bytes_down);
+	int rc = dev_dp_plan_run(ctx, ctx->stream, mi->dev[ctx->device]->ctg_len, nullptr, (int32_t)mi->ctg.size(), q, opt, kn, n, in, &head, &gids, bytes_up, bytes_down, rz);
 	if (rc != MPA_OK) return rc;
 	if ((rc = dp_plan_from_head(*head, gids, q, opt, kn, sizeof(DpRoundArgs), plan))) set_error("device DP plan: " + plan.err);
 	return rc;
@@ -812,7 +876,7 @@ static int dev_dp_plan(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *o
 static bool dp_plan_on_device() { const char *e = getenv("MPA_GPU_DPPLAN"); return e && atoi(e) != 0; }
 
 static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *opt, const mpa_qbatch_t *q,
-               int64_t n, const mpa_dp_task_t *in, mpa_dp_rst_t *rst, uint32_t **cigar_pool, int64_t *n_pool)
+               int64_t n, const mpa_dp_task_t *in, mpa_dp_rst_t *rst, uint32_t **cigar_pool, int64_t *n_pool, Resident *rz = nullptr)
 {
 	if (cigar_pool) *cigar_pool = nullptr;
 	if (n_pool) *n_pool = 0;
@@ -827,7 +891,16 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 	DpPlan plan;
 	const DpPlanKnobs kn = dp_plan_knobs(ctx);
 	bool planned = false;
-	if (dp_plan_on_device()) {                                  // (MPA_GPU_DPPLAN=1) the planner's stages on the device; declined: the host planner, as without the knob
+	const int64_t waits0 = ctx->n_waits;
+	if (rz) {                                                   // (MPA_GPU_ROUND2=1) planned from the tasks in place, or not run here at all
+		size_t b_up = 0, b_down = 0;
+		tl_alloc_failed = false;
+		if ((rc = dev_dp_plan(ctx, mi, opt, q, kn, n, nullptr, plan, &b_up, &b_down, rz)) != MPA_OK) return rc;
+		planned = true;
+		rz->rec.plan_waits = ctx->n_waits - waits0, rz->rec.bytes_up = (int64_t)b_up, rz->rec.bytes_down = (int64_t)b_down;
+		timing_note("  dp: plan on device", now_ms() - t_begin);
+		if (timing_on()) fprintf(stderr, "[mpa-timing]   dp: plan on device: %zu bytes up, %zu bytes down\n", b_up, b_down);
+	} else if (dp_plan_on_device()) {                                  // (MPA_GPU_DPPLAN=1) the planner's stages on the device; declined: the host planner, as without the knob
 		size_t b_up = 0, b_down = 0;
 		rc = dev_dp_plan(ctx, mi, opt, q, kn, n, in, plan, &b_up, &b_down);
 		if (rc == MPA_OK) {
@@ -843,7 +916,12 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 	}
 	DpRun R{ ctx, ctx->stream, plan, kn, in };
 	R.t_mark = now_ms();
-	if ((rc = dp_size_pools(R)) ||                             // 2. pools and staging
+	R.rz = rz;
+	const int64_t waits1 = ctx->n_waits;
+	rc = dp_size_pools(R);                                      // 2. pools and staging
+	if (rc && rz) { tl_alloc_failed = false; return MPA_ERR_UNSUPPORTED; }   // (resident: a pool or pinned block that cannot grow declines, before anything of the round is launched)
+	if (rz) rz->rec.bytes_up += plan.q_bytes;                   // (the queries' residues: the round's only upload)
+	if (rc ||
 	    (rc = dp_upload_and_prep(R, mi, opt, q)) ||            // 3. uploads, memsets, prep
 	    (rc = dp_side_launches(R)) ||                          // 4. next to the round: anti-diagonal, huge, T_LITE_W4 sweep
 	    (rc = dp_tb_chunks(R)) ||                              // 5. traceback chunks with the round's launch
@@ -855,11 +933,20 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 	// has been handed to the caller yet: mpa_dp_run() repeats it with those calls on the one-wave path (k_ext_huge, same bits).
 	static const bool test_fail = [] { const char *e = getenv("MPA_TEST_HANDOFF_FAIL"); return e && atoi(e) != 0; }();
 	if (*(const int32_t*)(R.hdn + plan.dn.err) || (test_fail && plan.n_split && !ctx->no_split)) {
+		if (rz) { set_error("round 2 resident: a column-block hand-off timed out, the round is repeated by mpa_dp_run"); return MPA_ERR_UNSUPPORTED; }
 		set_error("k_ext_wide_split: a column-block hand-off between workgroups timed out"); return MPA_RETRY_NO_SPLIT;
 	}
 	timing_note("  dp: upload+kernels (wall)", now_ms() - t_begin);
 	const double t_res = now_ms();
-	if ((rc = dp_assemble(R, rst, cigar_pool, n_pool))) return rc;   // 8. CIGAR gather, results
+	if (rz) {                                                   // 8'. the records are down already; the dense pool stays on the device
+		const int64_t *head = (const int64_t*)(R.hdn + R.dn_res);
+		if (head[DPR_H_BAD] || head[DPR_H_POOL] < 0 || head[DPR_H_POOL] > plan.cig_total) { set_error("round 2 resident: a traceback call's CIGAR length is outside its slot"); return MPA_ERR_HIP; }
+		R.pool_n = head[DPR_H_POOL];
+		memcpy(rst, R.hdn + R.dn_res + 64, sizeof(mpa_dp_rst_t) * (size_t)n);
+		if (n_pool) *n_pool = R.pool_n;
+		rz->rec.round_waits = ctx->n_waits - waits1;
+		if (timing_on()) fprintf(stderr, "[mpa-timing]   dp: round 2 resident: %lld up, %lld down, %lld wait\n", (long long)rz->rec.bytes_up, (long long)rz->rec.bytes_down, (long long)rz->rec.round_waits);
+	} else if ((rc = dp_assemble(R, rst, cigar_pool, n_pool))) return rc;   // 8. CIGAR gather, results
 	timing_note("  dp: download+assemble", now_ms() - t_res);
 	dp_statistics(R);                                           // 9.
 	return MPA_OK;
@@ -879,6 +966,42 @@ int mpa_dp_run(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *opt, cons
 		return rc;
 	});
 }
+
+} // extern "C"
+
+namespace mpa {
+int dp_run_resident(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *opt, const mpa_qbatch_t *q, int64_t n, const DpResidentIn &in, mpa_dp_rst_t *rst, int64_t *n_pool,
+                    const mpa_dp_rst_t **d_rst, DpResidentRec *rec)
+{
+	if (!in.d_tasks || n <= 0) { set_error("round 2 resident: no tasks on the device"); return MPA_ERR_UNSUPPORTED; }
+	Resident rz;
+	rz.in = in;
+	const int rc = mpa::guarded<int>(MPA_ERR_HIP, [&] { return mpa_dp_run_impl(ctx, mi, opt, q, n, nullptr, rst, nullptr, n_pool, &rz); });
+	if (d_rst) *d_rst = rc == MPA_OK ? rz.d_rst : nullptr;
+	if (rec) *rec = rz.rec;
+	return rc;
+}
+int dp_fetch_pool(mpa_ctx_t *ctx, int64_t n_pool, uint32_t **pool)
+{
+	*pool = nullptr;
+	if (n_pool < 0 || (size_t)n_pool * 4 > ctx->cigd.cap) { set_error("dp_fetch_pool: no dense CIGAR pool of that size on this context"); return MPA_ERR_ARG; }
+	HIP_TRY(hipSetDevice(ctx->device));
+	uint32_t *p = (uint32_t*)malloc((size_t)(n_pool > 0 ? n_pool : 1) * 4);
+	if (!p) { set_error("out of host memory"); return MPA_ERR_HIP; }
+	if (n_pool > 0) {
+		int rc;
+		if ((rc = ctx->h_pool.ensure((size_t)n_pool * 4))) { free(p); return rc; }
+		if (hipMemcpyAsync(ctx->h_pool.p, ctx->cigd.p, (size_t)n_pool * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || wait_stream(ctx, ctx->stream) != hipSuccess) {
+			free(p), set_error("dp_fetch_pool: the download failed"); return MPA_ERR_HIP;
+		}
+		memcpy(p, ctx->h_pool.p, (size_t)n_pool * 4);
+	}
+	*pool = p;
+	return MPA_OK;
+}
+} // namespace mpa
+
+extern "C" {
 
 int64_t mpa_dp_handoff_retries(const mpa_ctx_t *ctx) { return ctx ? ctx->handoff_retries : 0; }
 void mpa_dbg_antidiag(mpa_ctx_t *ctx, int on) { if (ctx) ctx->antidiag = on != 0; }
@@ -935,6 +1058,29 @@ int64_t dev_dp_plan_dbg(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int32_t n_ctg, c
 	}
 	for (size_t k = 0; k < wl.size(); ++k) if (wl[k] != P.glob_ids[P.n_reg_glob + k]) { set_error("device DP plan: the walk list is not the sorted order"); return MPA_ERR_HIP; }
 	return dp_plan_write(P, units, buf, cap);
+}
+// mpa_dbg_dp_run_resident on a context (round2_dbg.cpp): the tasks into a device pool, their bounds reduced there, the resident round, then
+// the explicit fetch of the dense pool.  rec: the hook's int64 record (mpamd_dbg.h).  1: declined (the last error says why).
+int dev_dp_run_resident_dbg(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *opt, const mpa_qbatch_t *q, int64_t n, const mpa_dp_task_t *in, mpa_dp_rst_t *rst,
+                            uint32_t **cigar_pool, int64_t *n_pool, int64_t *rec)
+{
+	HIP_TRY(hipSetDevice(ctx->device));
+	int rc;
+	if ((rc = ctx->sp_out.ensure(sizeof(mpa_dp_task_t) * (size_t)n + 64))) return rc;
+	HIP_TRY(hipMemcpy(ctx->sp_out.p, in, sizeof(mpa_dp_task_t) * (size_t)n, hipMemcpyHostToDevice));
+	DpResidentIn ri;
+	if ((rc = dev_task_bounds(ctx, ctx->sp_out.as<mpa_dp_task_t>(), n, ri))) return rc;
+	rec[7] = ri.prep_bound, rec[8] = ri.max_nl, rec[9] = ri.max_al;
+	DpResidentRec rr;
+	int64_t words = 0;
+	rc = dp_run_resident(ctx, mi, opt, q, n, ri, rst, &words, nullptr, &rr);
+	rec[0] = rr.plan_waits, rec[1] = rr.round_waits, rec[2] = rr.bytes_up, rec[3] = rr.task_bytes_up, rec[4] = rr.bytes_down, rec[5] = rr.pool_bytes_down;
+	if (rc == MPA_ERR_UNSUPPORTED) return 1;
+	if (rc != MPA_OK) return rc;
+	if ((rc = dp_fetch_pool(ctx, words, cigar_pool))) return rc;
+	rec[6] = 4 * words, rec[10] = words;
+	if (n_pool) *n_pool = words;
+	return MPA_OK;
 }
 } // namespace mpa
 

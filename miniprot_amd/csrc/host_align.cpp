@@ -594,6 +594,7 @@ static int spans_round1_device(mpa_batch_s *b, mpa_ctx_t *ctx, const mpa_dp_rst_
 	if (rc != MPA_OK) return rc;
 	spans_keep_round1(b, rst, nullptr, false);
 	spans_apply_round1(b, plan0, io.rec, io.task, io.n_task);
+	b->r2_in = io.r2;                                    // (MPA_GPU_ROUND2=1: the tasks in place and their bounds, for run_dp_rounds)
 	return MPA_OK;
 }
 
@@ -609,6 +610,7 @@ int spans_take_round1(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint32_t *p
 {
 	const StepMode mode = batch_step_mode(b, "MPA_GPU_SPANS");
 	b->spans_src = 0;
+	b->r2_in = DpResidentIn(), b->r2_resident = false, b->r2_rst_dev = nullptr;
 	bool any_plan = false;
 	for (const QueryState &qs : b->qs) any_plan = any_plan || !qs.plans.empty();
 	if (mode != STEP_HOST && rst && any_plan) {
@@ -706,11 +708,14 @@ static int spans_assemble_device(mpa_batch_s *b, mpa_ctx_t *ctx, const mpa_dp_rs
 	spans_counts(b, plan0, seg0);
 	const int64_t n_plan = plan0.back(), n_rst2 = (int64_t)b->tasks.size();
 	SpansAsmIO io;
+	// (tests) MPA_TEST_ROUND2_DECLINE=1: the step declines behind a resident round 2, so that the late fetch of its pool is taken
+	if (b->r2_resident) { const char *e = getenv("MPA_TEST_ROUND2_DECLINE"); if (e && atoi(e) != 0) { set_error("MPA_TEST_ROUND2_DECLINE"); return MPA_ERR_UNSUPPORTED; } }
 	int rc = dev_spans_asm_stage(ctx, n_plan, n_rst2, io);
 	if (rc != MPA_OK) return rc;
-	if (n_rst2 > 0) memcpy(io.rst2, rst2, (size_t)n_rst2 * sizeof(mpa_dp_rst_t));
+	const mpa_dp_rst_t *d_rst2 = b->r2_resident ? b->r2_rst_dev : nullptr;   // (a resident round 2: the records are read where its kernels wrote them)
+	if (n_rst2 > 0 && !d_rst2) memcpy(io.rst2, rst2, (size_t)n_rst2 * sizeof(mpa_dp_rst_t));
 	spans_slots(b, plan0, rst2, io.slot_off);
-	rc = dev_spans_assemble(ctx, n_plan, n_rst2, nullptr, rst2 ? b->dp_n_pool : 0, io);
+	rc = dev_spans_assemble(ctx, n_plan, n_rst2, nullptr, rst2 ? b->dp_n_pool : 0, io, d_rst2);
 	if (rc != MPA_OK) return rc;
 	for (int64_t j = 0; j < n_plan; ++j)
 		if (io.rec[j].bad) { set_error("GPU spans: a DP call whose own CIGAR words would merge"); return MPA_ERR_UNSUPPORTED; }
@@ -762,6 +767,7 @@ static void spans_dump(const mpa_batch_s *b)
 
 static int take_round3_steps(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint32_t *pool)
 {
+	struct Fetched { uint32_t *p = nullptr; ~Fetched() { free(p); } } fetched;   // (a resident round 2's pool, when a fallback needs its words)
 	const StepMode mode = batch_step_mode(b, "MPA_GPU_STATS");
 	const StepMode cs = cs_printed(b->opt) ? batch_step_mode(b, "MPA_GPU_CS") : STEP_HOST;
 	const StepMode rows = rows_printed(b->opt) ? batch_step_mode(b, "MPA_GPU_ROWS") : STEP_HOST;
@@ -800,6 +806,13 @@ static int take_round3_steps(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint
 		else {
 			if (timing_on()) fprintf(stderr, "[mpa-timing]   device spans declined (%s): region CIGARs on the host\n", mpa_last_error());
 			b->sp_cig_off.clear();
+			if (b->r2_resident && !pool) {                                     // the words of round 2 are still on the device: a second wait, their size is known by now
+				const double t2 = now_ms();
+				const int rc2 = dp_fetch_pool(b->dp_ctx, b->dp_n_pool, &fetched.p);
+				if (rc2 != MPA_OK) return rc2;
+				pool = fetched.p;
+				if (timing_on()) fprintf(stderr, "[mpa-timing]   dp: round 2 resident: pool fetched late, %lld bytes down, %.3f ms\n", (long long)(4 * b->dp_n_pool), now_ms() - t2);
+			}
 			spans_assemble_host(b, rst, pool);
 		}
 	}

@@ -75,6 +75,11 @@ struct mpa_batch_s {
 	std::vector<mpa_dp_rst_t> sp_rst1;
 	uint32_t *sp_pool1 = nullptr;
 	std::vector<int64_t> sp_cig_off;
+	// MPA_GPU_ROUND2: what the device step between the rounds left for a resident round 2 (d_tasks null: nothing);
+	// whether round 2 ran that way -- its dense pool is then on dp_ctx (dp_n_pool words) and not with the host -- and its records there
+	mpa::DpResidentIn r2_in;
+	bool r2_resident = false;
+	const mpa_dp_rst_t *r2_rst_dev = nullptr;
 	~mpa_batch_s() { free(sp_pool1); }
 };
 

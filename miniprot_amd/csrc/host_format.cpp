@@ -392,9 +392,10 @@ static int64_t format_batch(const mpa_idx_t *mi, const mpa_mapopt_t *opt, const 
 	for (const std::string &x : part) s += x;
 	// (the counts behind the time: tools/timing_agg.py still sees one label)
 	if (timing_on()) {
-		fprintf(stderr, "[mpa-timing] %-28s %9.3f ms  cs carried %lld, built %lld", "format output", now_ms() - t0, (long long)cs_carried.load(), (long long)cs_built.load());
-		if (opt->flag & (MPA_MF_SHOW_RESIDUE | MPA_MF_SHOW_TRANS)) fprintf(stderr, "; rows carried %lld, built %lld", (long long)rows_carried.load(), (long long)rows_built.load());
-		fputc('\n', stderr);
+		// (one write: the lanes of a stream print their notes side by side, and a note that lands inside this line hides its counts)
+		char rows[96] = "";
+		if (opt->flag & (MPA_MF_SHOW_RESIDUE | MPA_MF_SHOW_TRANS)) snprintf(rows, sizeof rows, "; rows carried %lld, built %lld", (long long)rows_carried.load(), (long long)rows_built.load());
+		fprintf(stderr, "[mpa-timing] %-28s %9.3f ms  cs carried %lld, built %lld%s\n", "format output", now_ms() - t0, (long long)cs_carried.load(), (long long)cs_built.load(), rows);
 	}
 	char *buf = (char*)malloc(s.size() + 1);
 	memcpy(buf, s.data(), s.size());

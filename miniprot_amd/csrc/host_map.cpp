@@ -1650,7 +1650,17 @@ static int run_dp_rounds(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_qbatch_t
 		int64_t n_pool = 0;
 		rst.resize((size_t)n);
 		double t0 = now_ms();
-		int rc = mpa_dp_run(ctx, mi, &dpopt, q, n, tasks, rst.data(), &pool, &n_pool);
+		int rc = MPA_ERR_UNSUPPORTED;
+		// (MPA_GPU_ROUND2=1) round 2 planned from the tasks the device step between the rounds left in place, its records and dense pool
+		// assembled on the device: no pool comes back.  Declined: the round runs through mpa_dp_run as always
+		if (b->round == 2 && round2_knob()) {
+			if (b->spans_src != 2 || !b->r2_in.d_tasks) set_error("the step between the rounds did not run on the device");
+			else rc = dp_run_resident(ctx, mi, &dpopt, q, n, b->r2_in, rst.data(), &n_pool, &b->r2_rst_dev, nullptr);
+			if (rc == MPA_OK) b->r2_resident = true;
+			else if (rc != MPA_ERR_UNSUPPORTED) return rc;
+			else if (timing_on()) fprintf(stderr, "[mpa-timing]   round 2 resident declined (%s): mpa_dp_run\n", mpa_last_error());
+		}
+		if (rc == MPA_ERR_UNSUPPORTED) rc = mpa_dp_run(ctx, mi, &dpopt, q, n, tasks, rst.data(), &pool, &n_pool);
 		timing_note("mpa_dp_run (total)", now_ms() - t0);
 		if (rc != MPA_OK) { free(pool); return rc; }
 		b->dp_n_pool = n_pool;           // (MPA_GPU_SPANS=1: the round's dense pool is still on the context)

@@ -8,6 +8,7 @@
 #include <exception>
 #include <vector>
 #include <cstring>
+#include <cstdlib>
 #include "../../include/mpamd.h"
 #include "chain_core.h"
 #include "aln_stats_core.h"
@@ -289,15 +290,36 @@ int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const 
 // Behind round 2: dev_spans_asm_stage hands out where the round-2 results and the slot offsets (slot_off[n_plan + 1], in words) go;
 // dev_spans_assemble runs k_assemble on what round 1 left and, for pool2 == nullptr, the pool of the last mpa_dp_run, and leaves
 // rec[n_plan] and the slots' words in pinned memory (valid until the context's next call); the words also stay on the device for
-// dev_aln_walks (dev_cig).  MPA_ERR_UNSUPPORTED from any of them: a pool or pinned block could not grow -- the caller
+// dev_aln_walks (dev_cig).  d_rst2 != nullptr (a resident round 2, MPA_GPU_ROUND2): the round-2 records are read from that device
+// pointer and only the slot offsets go up.  MPA_ERR_UNSUPPORTED from any of them: a pool or pinned block could not grow -- the caller
 // keeps the host step.
+// (r2, with MPA_GPU_ROUND2=1: the round-2 tasks in place on the device and their bounds; d_tasks == nullptr: not asked for)
+struct DpResidentIn { const mpa_dp_task_t *d_tasks = nullptr; int64_t prep_bound = 0, max_nl = 0, max_al = 0; };
 struct SpansIO { SpansPlan *plan = nullptr; SegRec *seg = nullptr; mpa_dp_rst_t *rst1 = nullptr; char *text = nullptr;
-                 const SpanRec *rec = nullptr; const mpa_dp_task_t *task = nullptr; int32_t n_task = 0; };
+                 const SpanRec *rec = nullptr; const mpa_dp_task_t *task = nullptr; int32_t n_task = 0; DpResidentIn r2; };
 int dev_spans_stage(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_seg, int64_t n_rst1, int64_t text_bytes, SpansIO &io);
 int dev_spans_round1(mpa_ctx_t *ctx, mpa_idx_s *mi, const SpansParams &p, const int8_t *mat, int64_t n_plan, int64_t n_seg, int64_t n_rst1, int64_t text_bytes,
                      const uint32_t *pool1, int64_t n_pool1, SpansIO &io);
 struct SpansAsmIO { mpa_dp_rst_t *rst2 = nullptr; int64_t *slot_off = nullptr; const AsmRec *rec = nullptr; const uint32_t *cigar = nullptr; };
 int dev_spans_asm_stage(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, SpansAsmIO &io);
-int dev_spans_assemble(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, const uint32_t *pool2, int64_t n_pool2, SpansAsmIO &io);
+int dev_spans_assemble(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, const uint32_t *pool2, int64_t n_pool2, SpansAsmIO &io, const mpa_dp_rst_t *d_rst2 = nullptr);
+
+// ---- DP round 2 from device-resident tasks (MPA_GPU_ROUND2=1; dp_exec.hip) ----
+// What dev_spans_round1 leaves for it: the round-2 tasks where k_spans_emit wrote them (a pool of the context) and the three bounds the
+// device planner sizes by (dp_results_core.h), reduced on the device and downloaded next to the task count (DpResidentIn, above).
+// ... and what a resident round says about itself: host waits of the planner and of the round behind it, bytes up and down (task records
+// among the bytes up, words of the dense CIGAR pool among the bytes down)
+struct DpResidentRec { int64_t plan_waits = 0, round_waits = 0, bytes_up = 0, task_bytes_up = 0, bytes_down = 0, pool_bytes_down = 0; };
+// The round of n calls planned from in.d_tasks in place, its result records written on the device and downloaded with the round's one
+// wait into rst[n]; *n_pool: words of the dense CIGAR pool, which stays in the context (dp_fetch_pool); *d_rst: the records on the
+// device, valid until the context's next round.  MPA_ERR_UNSUPPORTED: declined (the last error says why) -- the caller runs mpa_dp_run.
+int dp_run_resident(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *opt, const mpa_qbatch_t *q, int64_t n, const DpResidentIn &in, mpa_dp_rst_t *rst, int64_t *n_pool,
+                    const mpa_dp_rst_t **d_rst, DpResidentRec *rec);
+// the dense pool the context's last round left (n_pool words) into a malloc'ed block: a second wait, for the fallbacks that need the words
+int dp_fetch_pool(mpa_ctx_t *ctx, int64_t n_pool, uint32_t **pool);
+// MPA_GPU_ROUND2, read per batch
+static inline bool round2_knob() { const char *e = getenv("MPA_GPU_ROUND2"); return e && atoi(e) != 0; }
+// the bounds of the n tasks at d_tasks, reduced on the device (k_task_bounds, span_kernels.hip): for the hook mpa_dbg_dp_run_resident
+int dev_task_bounds(mpa_ctx_t *ctx, const mpa_dp_task_t *d_tasks, int64_t n, DpResidentIn &out);
 
 } // namespace mpa

@@ -7,6 +7,8 @@
 //   k_spans_emit   one lane per plan: the sums of the workgroups before its own added (the host's order: query-major, plans in
 //                  order, left before right), records and tasks written densely where one download finds them
 //   k_assemble     one wavefront per plan, four plans per workgroup: spans_assemble into the plan's slot of the CIGAR pool
+//   k_task_bounds  (MPA_GPU_ROUND2=1) one lane per round-2 task: the three bounds the device planner sizes by (dp_results_core.h), a
+//                  wave reduction and one vector atomic per wave and bound
 // The tables (804 bytes) and the workgroup scan's four wave totals are k_spans' only LDS.  No capacity.  Plain vector stores only.
 
 namespace mpa {
@@ -78,6 +80,24 @@ __global__ __launch_bounds__(SPANS_BLOCK) void k_spans_emit(SpansArgs x, int32_t
 		for (int32_t k = 0; k < n; ++k) task_dst[t0 + k] = x.tmp[2 * (int64_t)i + k];
 	}
 	if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) head[0] = base + x.bsum[blockIdx.x];
+}
+
+// out[3], zero before the launch: prep chunks, largest nl, largest al of task[0, *n_task); the grid covers the list's capacity
+__global__ __launch_bounds__(SPANS_BLOCK) void k_task_bounds(const mpa_dp_task_t *task, const int32_t *n_task, int64_t *out)
+{
+	MPA_SHORT_KERNEL();
+	const int64_t i = (int64_t)blockIdx.x * SPANS_BLOCK + threadIdx.x;
+	DpTaskBounds b{ 0, 0, 0 };
+	if (i < (int64_t)*n_task) b = dp_task_bounds_of(task[i].nl, task[i].al);
+	for (int d = 32; d > 0; d >>= 1) {
+		const DpTaskBounds o{ (int64_t)__shfl_xor((long long)b.prep, d, 64), (int64_t)__shfl_xor((long long)b.max_nl, d, 64), (int64_t)__shfl_xor((long long)b.max_al, d, 64) };
+		dp_task_bounds_join(b, o);
+	}
+	if ((threadIdx.x & 63) == 0 && (b.prep | b.max_nl | b.max_al)) {       // (all three are >= 0)
+		atomicAdd((unsigned long long*)out, (unsigned long long)b.prep);
+		atomicMax((unsigned long long*)out + 1, (unsigned long long)b.max_nl);
+		atomicMax((unsigned long long*)out + 2, (unsigned long long)b.max_al);
+	}
 }
 
 struct AsmArgs {

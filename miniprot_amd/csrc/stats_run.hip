@@ -13,6 +13,7 @@
 // dev_aln_walks() reads it in place of an uploaded one when the caller says so (dev_cig).
 #include "dev_ctx.h"
 #include "spans_core.h"
+#include "dp_results_core.h"
 #include "stats_kernels.hip"
 #include "span_kernels.hip"
 
@@ -131,10 +132,11 @@ int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const 
 
 // ---- MPA_GPU_SPANS=1 ------------------------------------------------------------------------------------------------------------
 namespace {
+static const size_t SPANS_HEAD_BYTES = 32;
 struct SpansLayout {
 	size_t off_plan, off_seg, off_rst1, off_text, up_bytes;                  // sp_in / h_sp_up (the tables take the first KB)
 	size_t off_tmp, off_excl, off_bsum, mid_bytes;                            // sp_mid (records with local numbers at 0)
-	size_t off_rec, off_task, down_bytes;                                     // sp_out / h_sp_down (the task count at 0)
+	size_t off_rec, off_task, down_bytes;                                     // sp_out / h_sp_down (the task count at 0, the tasks' three bounds as int64 at 8)
 	unsigned blocks;
 	SpansLayout(int64_t n_plan, int64_t n_seg, int64_t n_rst1, int64_t text_bytes)
 	{
@@ -149,7 +151,7 @@ struct SpansLayout {
 		off_excl = off_tmp + up16((size_t)n_plan * 2 * sizeof(mpa_dp_task_t));
 		off_bsum = off_excl + up16((size_t)n_plan * 4);
 		mid_bytes = off_bsum + up16((size_t)blocks * 4) + 16;
-		off_rec = 16;
+		off_rec = SPANS_HEAD_BYTES;
 		off_task = off_rec + up16((size_t)n_plan * sizeof(SpanRec));
 		down_bytes = off_task + (size_t)n_plan * 2 * sizeof(mpa_dp_task_t) + 16;
 	}
@@ -211,10 +213,19 @@ int dev_spans_round1(mpa_ctx_t *ctx, mpa_idx_s *mi, const SpansParams &p, const 
 	HIP_TRY(hipGetLastError());
 	hipLaunchKernelGGL(k_spans_emit, dim3(L.blocks), dim3(SPANS_BLOCK), 0, s, a, (int32_t*)dout, (SpanRec*)(dout + L.off_rec), (mpa_dp_task_t*)(dout + L.off_task));
 	HIP_TRY(hipGetLastError());
+	const bool want_r2 = round2_knob();                  // (MPA_GPU_ROUND2=1) the bounds of the tasks just written, for the planner of round 2
+	if (want_r2) {
+		HIP_TRY(hipMemsetAsync(dout + 8, 0, 24, s));
+		hipLaunchKernelGGL(k_task_bounds, dim3((unsigned)((2 * n_plan + SPANS_BLOCK - 1) / SPANS_BLOCK)), dim3(SPANS_BLOCK), 0, s, (const mpa_dp_task_t*)(dout + L.off_task), (const int32_t*)dout,
+		                   (int64_t*)(dout + 8));
+		HIP_TRY(hipGetLastError());
+	}
 	char *hd = ctx->h_sp_down.as<char>();
 	HIP_TRY(hipMemcpyAsync(hd, dout, L.down_bytes - 16, hipMemcpyDeviceToHost, s));
 	HIP_TRY(wait_stream(ctx, s));
 	io.n_task = *(const int32_t*)hd, io.rec = (const SpanRec*)(hd + L.off_rec), io.task = (const mpa_dp_task_t*)(hd + L.off_task);
+	io.r2 = DpResidentIn();
+	if (want_r2) { const int64_t *bd = (const int64_t*)(hd + 8); io.r2.d_tasks = (const mpa_dp_task_t*)(dout + L.off_task), io.r2.prep_bound = bd[0], io.r2.max_nl = bd[1], io.r2.max_al = bd[2]; }
 	if (io.n_task < 0 || io.n_task > 2 * n_plan) { set_error("dev_spans_round1: an impossible task count"); return MPA_ERR_HIP; }
 	ctx->sp_keep.off_plan = L.off_plan, ctx->sp_keep.off_seg = L.off_seg, ctx->sp_keep.off_rst1 = L.off_rst1, ctx->sp_keep.n_plan = n_plan, ctx->sp_keep.n_pool1 = n_pool1;
 	return MPA_OK;
@@ -232,7 +243,7 @@ int dev_spans_asm_stage(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, SpansAsm
 	return MPA_OK;
 }
 
-int dev_spans_assemble(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, const uint32_t *pool2, int64_t n_pool2, SpansAsmIO &io)
+int dev_spans_assemble(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, const uint32_t *pool2, int64_t n_pool2, SpansAsmIO &io, const mpa_dp_rst_t *d_rst2)
 {
 	if (n_plan <= 0 || n_plan != ctx->sp_keep.n_plan) { set_error("dev_spans_assemble: the plans of this batch are not on the device"); return MPA_ERR_ARG; }
 	HIP_TRY(hipSetDevice(ctx->device));
@@ -247,13 +258,15 @@ int dev_spans_assemble(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, const uin
 	if (ctx->sp_in2.ensure(L.up_bytes) != MPA_OK || ctx->sp_asm.ensure(L.rec_bytes + 16) != MPA_OK || ctx->sp_cig.ensure((size_t)n_words * 4 + 16) != MPA_OK)
 		return tl_alloc_failed ? MPA_ERR_UNSUPPORTED : MPA_ERR_HIP;
 	hipStream_t s = ctx->stream;
-	HIP_TRY(hipMemcpyAsync(ctx->sp_in2.p, ctx->h_sp_up2.p, L0.up_bytes - 16, hipMemcpyHostToDevice, s));
 	char *din2 = ctx->sp_in2.as<char>();
+	// (d_rst2: round 2's records are on the device already, where the round's own kernels wrote them -- only the slot offsets go up)
+	const size_t up_from = d_rst2 ? L0.off_slot : 0;
+	HIP_TRY(hipMemcpyAsync(din2 + up_from, ctx->h_sp_up2.as<char>() + up_from, L0.up_bytes - 16 - up_from, hipMemcpyHostToDevice, s));
 	if (pool2 && n_pool2 > 0) HIP_TRY(hipMemcpyAsync(din2 + L.off_pool2, pool2, (size_t)n_pool2 * 4, hipMemcpyHostToDevice, s));
 	const char *din = ctx->sp_in.as<char>();
 	AsmArgs a;
-	a.plan = (const SpansPlan*)(din + ctx->sp_keep.off_plan), a.rec = (const SpanRec*)(ctx->sp_out.as<char>() + 16), a.n_plan = (int32_t)n_plan;
-	a.gap = (const SegRec*)(din + ctx->sp_keep.off_seg), a.rst1 = (const mpa_dp_rst_t*)(din + ctx->sp_keep.off_rst1), a.rst2 = (const mpa_dp_rst_t*)din2;
+	a.plan = (const SpansPlan*)(din + ctx->sp_keep.off_plan), a.rec = (const SpanRec*)(ctx->sp_out.as<char>() + SPANS_HEAD_BYTES), a.n_plan = (int32_t)n_plan;
+	a.gap = (const SegRec*)(din + ctx->sp_keep.off_seg), a.rst1 = (const mpa_dp_rst_t*)(din + ctx->sp_keep.off_rst1), a.rst2 = d_rst2 ? d_rst2 : (const mpa_dp_rst_t*)din2;
 	a.pool1 = ctx->sp_pool1.as<uint32_t>(), a.pool2 = pool2 ? (const uint32_t*)(din2 + L.off_pool2) : ctx->cigd.as<uint32_t>();
 	a.slot_off = (const int64_t*)(din2 + L.off_slot), a.cig = ctx->sp_cig.as<uint32_t>(), a.out = ctx->sp_asm.as<AsmRec>();
 	hipLaunchKernelGGL(k_assemble, dim3((unsigned)((n_plan + STATS_WAVES - 1) / STATS_WAVES)), dim3(64 * STATS_WAVES), 0, s, a);
@@ -263,6 +276,25 @@ int dev_spans_assemble(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, const uin
 	if (n_words > 0) HIP_TRY(hipMemcpyAsync(hd + L.rec_bytes, ctx->sp_cig.p, (size_t)n_words * 4, hipMemcpyDeviceToHost, s));
 	HIP_TRY(wait_stream(ctx, s));
 	io.rec = (const AsmRec*)hd, io.cigar = (const uint32_t*)(hd + L.rec_bytes);
+	return MPA_OK;
+}
+
+// the bounds of a task list that is on the device, by the kernel dev_spans_round1 launches for MPA_GPU_ROUND2 (the hook's way to it)
+int dev_task_bounds(mpa_ctx_t *ctx, const mpa_dp_task_t *d_tasks, int64_t n, DpResidentIn &out)
+{
+	out = DpResidentIn();
+	if (n <= 0 || n > (int64_t)1 << 28) { set_error("dev_task_bounds: no tasks, or too many for one launch"); return MPA_ERR_ARG; }
+	HIP_TRY(hipSetDevice(ctx->device));
+	if (ctx->sp_mid.ensure(64) != MPA_OK) return MPA_ERR_HIP;
+	hipStream_t s = ctx->stream;
+	int64_t h[4] = { 0, 0, 0, 0 };                       // bounds[3] | the count
+	*(int32_t*)(h + 3) = (int32_t)n;
+	HIP_TRY(hipMemcpyAsync(ctx->sp_mid.p, h, sizeof h, hipMemcpyHostToDevice, s));
+	hipLaunchKernelGGL(k_task_bounds, dim3((unsigned)((n + SPANS_BLOCK - 1) / SPANS_BLOCK)), dim3(SPANS_BLOCK), 0, s, d_tasks, (const int32_t*)(ctx->sp_mid.as<int64_t>() + 3), ctx->sp_mid.as<int64_t>());
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(h, ctx->sp_mid.p, 24, hipMemcpyDeviceToHost, s));
+	HIP_TRY(wait_stream(ctx, s));
+	out.d_tasks = d_tasks, out.prep_bound = h[0], out.max_nl = h[1], out.max_al = h[2];
 	return MPA_OK;
 }
 
