@@ -1,5 +1,6 @@
-// host_batch.h -- the state of a batch in the stage machine (mpa_batch_*) and what its two host files share: host_map.cpp (seeding,
-// planning, the C ABI and the stream pipeline) and host_align.cpp (the steps between "DP results arrive" and "regions ranked").
+// host_batch.h -- the state of a batch in the stage machine (mpa_batch_*) and what its host files share: host_plan.cpp (stage A: seeding,
+// planning, round-1 tasks), host_align.cpp (the steps between "DP results arrive" and "regions ranked"), host_map.cpp (the stage
+// machine), host_pipeline.cpp (the stream), host_pool.cpp (the worker pools) and host_hooks.cpp (the test hooks of stage A).
 // Host-only: no device unit includes it.
 #pragma once
 #include <cstdlib>
@@ -83,18 +84,93 @@ struct mpa_batch_s {
 	~mpa_batch_s() { free(sp_pool1); }
 };
 
+// The query side of the device refinement: the query's k-mers (packed word, index of the last residue) grouped by word -- in
+// ascending hash order, positions ascending inside a group, as the pairing of map.c:53-79 meets them in the sorted list.
+// (Outside the namespace, where it was: the library's default visibility exports a few std::vector<QueryGroups> members under that name.)
+struct QueryGroups { std::vector<uint32_t> gword, gcount, qpos; };
+
 namespace mpa {
 
-// What crosses between the two files (internal to the library: hidden, so the dynamic symbol table does not grow):
+// What crosses between the files (internal to the library: hidden, so the dynamic symbol table does not grow):
 #define MPA_HOST_LOCAL __attribute__((visibility("hidden")))
 // host_map.cpp -> host_align.cpp: round 1 in / round 2 out, and the last round in (CIGARs, statistics, cs strings and rows, ranking)
 MPA_HOST_LOCAL int spans_take_round1(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint32_t *pool);
 MPA_HOST_LOCAL int take_round3(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint32_t *pool);
-// host_align.cpp -> host_map.cpp: plan_round1 makes the gap segments with it, take_round1_emit_round2 the accepted spans
+// host_align.cpp -> host_plan.cpp: plan_round1 makes the gap segments with it, take_round1_emit_round2 the accepted spans
 MPA_HOST_LOCAL void make_segment(mpa_batch_s *b, const QueryState &qs, const Region &r, const AlignPlan &pl, int32_t ne0, int32_t ne1, int32_t ae0, int32_t ae1,
                                  int32_t qi, int32_t pi, std::vector<mpa_dp_task_t> &tasks, Segment &s);
-// ... and the calling thread's worker pool (the pool, its lane and its share of the threads belong to the stream pipeline)
+// host_pipeline.cpp -> host_map.cpp: the DP rounds of a planned batch on a device context
+MPA_HOST_LOCAL int run_dp_rounds(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_qbatch_t *q, mpa_batch_s *b);
+
+// host_map.cpp, host_pipeline.cpp, host_hooks.cpp -> host_plan.cpp: the phases of stage A.  sketch (host: seeds of every query and the
+// seed jobs) -> device seed (anchors, pre-chain, main chain; false = error) -> plan (windows, refinement, plans, round-1 tasks)
+MPA_HOST_LOCAL mpa_batch_s *batch_shell(const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads);
+MPA_HOST_LOCAL mpa_batch_s *batch_sketch_phase(bool have_device, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads);
+MPA_HOST_LOCAL void batch_host_seeds(mpa_batch_s *b, bool have_device);
+MPA_HOST_LOCAL bool batch_device_seed_phase(mpa_ctx_t *seed_ctx, mpa_batch_s *b, bool want_chains, SeedHold *hold, double *sketch_ms = nullptr, bool for_planner = false);
+MPA_HOST_LOCAL mpa_batch_s *batch_seed_phase(mpa_ctx_t *seed_ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads, bool want_chains = true, SeedHold *hold = nullptr, bool for_planner = false);
+MPA_HOST_LOCAL void batch_plan_phase(mpa_batch_s *b, mpa_ctx_t *rctx);
+MPA_HOST_LOCAL mpa_batch_s *batch_begin_impl(mpa_ctx_t *seed_ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int n_threads);
+MPA_HOST_LOCAL void emit_round1(mpa_batch_s *b);
+struct MPA_HOST_LOCAL SeedModeScope { int keep; explicit SeedModeScope(int m); ~SeedModeScope(); };   // forces MPA_GPU_SEED for the calling thread over a scope (the mpa_dbg_* hooks, for their own call)
+// host_hooks.cpp -> host_plan.cpp: the per-query steps that the test hooks of stage A call one by one
+enum SeedRoute { SEED_ON_HOST = 0, SEED_PRECHAIN, SEED_DIRECT };
+MPA_HOST_LOCAL SeedRoute seed_route(const mpa_mapopt_t &opt, const mpa_idxopt_t &io);
+MPA_HOST_LOCAL void stage_seeds(mpa_batch_s *b, QueryState &qs);
+MPA_HOST_LOCAL void stage_anchors_host(mpa_batch_s *b, QueryState &qs, std::vector<uint64_t> &a);
+MPA_HOST_LOCAL void stage_anchors_from_device(mpa_batch_s *b, QueryState &qs, const PrechainSparse &ps, std::vector<uint64_t> &a);
+MPA_HOST_LOCAL void query_words(const char *aa, int32_t l_aa, int32_t k, std::vector<uint32_t> &w);
+MPA_HOST_LOCAL void query_groups(const char *aa, int32_t l_aa, int32_t k, QueryGroups &out);
+MPA_HOST_LOCAL void gather_query_groups(const QueryGroups *per, int64_t n_q, RefineGroupsHost &G);
+// mp_refine_reg (map.c:32-111): re-seed the region's window with all 5-mers at base resolution, re-chain
+// The query side of the refinement seeding, built once per query: its k-mers sorted by hash and a bitmap over the
+// hash space (2^(4k) bits; one per worker thread, reused) with the query's hashes set.
+struct RefineQuery {
+	std::vector<uint64_t> qk;
+	std::vector<uint64_t> *filter = nullptr;
+	int32_t kmer = 0;
+	static std::vector<uint64_t> &thread_filter(int32_t kmer) {
+		static thread_local std::vector<uint64_t> f;
+		const size_t words = ((size_t)1 << (4 * kmer)) / 64 + 1;
+		if (f.size() < words) f.assign(words, 0);
+		return f;
+	}
+	std::vector<uint32_t> words;                      // packed k-mer words of the query (bitmap keys)
+	RefineQuery(const char *aa, int32_t l_aa, int32_t k, bool want_filter = true) : kmer(k) {
+		sketch_protein(aa, l_aa, k, 0, qk);
+		sort_u64(qk.data(), qk.data() + qk.size());
+		if (k <= 6 && want_filter) {
+			filter = &thread_filter(k);
+			const uint8_t *aa13 = tab_aa13();
+			const uint32_t mask = (1U << 4 * k) - 1;
+			uint32_t w = 0;
+			for (int32_t i = 0, run = 0; i < l_aa; ++i) {
+				const uint32_t c = aa13[(uint8_t)aa[i]];
+				if (c >= 14) { run = 0, w = 0; continue; }
+				w = (w << 4 | c) & mask;
+				if (++run >= k) words.push_back(w), (*filter)[w >> 6] |= 1ULL << (w & 63);
+			}
+		}
+	}
+	~RefineQuery() { if (filter) for (uint32_t w : words) (*filter)[w >> 6] = 0; }
+};
+MPA_HOST_LOCAL void refine_region_pairs(const mpa_idx_s *mi, const mpa_mapopt_t &opt, const RefineQuery &rq, const Region &r, int32_t extl, int32_t extr, const uint64_t *dev_hits, int64_t n_dev_hits, std::vector<uint64_t> &a);
+static inline ChainParams refine_chain_params(const mpa_mapopt_t &opt)
+{
+	return ChainParams{ opt.max_intron, opt.max_gap, opt.bw, opt.max_chn_max_skip, opt.max_chn_iter, opt.min_chn_cnt, opt.min_chn_sc,
+	                    opt.chn_coef_log, !(opt.flag & MPA_MF_NO_SPLICE), opt.kmer2, 0 };
+}
+static inline ChainParams main_chain_params(const mpa_idx_s *mi, const mpa_mapopt_t &opt)
+{
+	return ChainParams{ opt.max_intron, opt.max_gap, opt.bw, opt.max_chn_max_skip, opt.max_chn_iter, opt.min_chn_cnt, opt.min_chn_sc,
+	                    opt.chn_coef_log, !(opt.flag & MPA_MF_NO_SPLICE), mi->opt.kmer, mi->opt.bbit };
+}
+
+// The calling thread's worker pool (host_pool.cpp); the pool, its lane and its share of the threads are set by the stream pipeline's
+// stage threads for themselves
 MPA_HOST_LOCAL void parallel_run(int n_threads, int64_t n, const std::function<void(int64_t)> &fn);
+MPA_HOST_LOCAL void pool_stage_enter(int lane, int thread_div, const char *label);
+MPA_HOST_LOCAL void pool_stage_leave();
 template<typename F> static void parallel_for(int n_threads, int64_t n, F fn)
 {
 	std::function<void(int64_t)> f = fn;

@@ -179,7 +179,7 @@ struct PrechainSparse {              // result for a mini-batch: the chained anc
 	const uint64_t *E = nullptr;
 	const int32_t *n_reg = nullptr;
 };
-// What the device refinement takes (k_refine_scan, k_refine_scan_map), stated once for the callers' gate (host_map.cpp) and the
+// What the device refinement takes (k_refine_scan, k_refine_scan_map), stated once for the callers' gate (host_plan.cpp) and the
 // guards of dev_refine_scan / dev_refine_chains: k-mers of 1..7 residues (4 bits each in a 32-bit word whose all-ones value marks
 // an empty slot of the LDS table) and a minimum ORF length that the walk into the chunk's halo can decide -- from a k-mer at the
 // chunk's first position the walk sees (halo - 3 k) / 3 whole codons before it: 37 codons in all for every k of 3..7.

@@ -1,6 +1,6 @@
 // plans_core.h -- from the refinement chains of a query to its regions, alignment plans, round-1 DP tasks and gap segments (the part of
 // rows a11 / a12 of DESIGN.md section 1 between the refinement and DP round 1; section 4.7): what mp_refine_reg() makes of a window's chains (map.c:89-111,
-// refine_region_from_chains of host_map.cpp), the second sort_regions / assign_parents / select_secondary, extension_limits in its
+// refine_region_from_chains of host_plan.cpp), the second sort_regions / assign_parents / select_secondary, extension_limits in its
 // genome-coordinate form (hit.c:252-287), mp_filter_seed (align.c:6-31, mark_reliable_anchors), the window and the extension
 // calls of mp_align() (align.c:239-301, plan_alignment / plan_round1) and the gaps between its kept anchors with their ungapped
 // shortcut (align.c:62-80, make_segment) as ONE source for the host and the device, like regions_core.h, whose pieces it is built
@@ -44,7 +44,7 @@ struct PlansParams {
 	float mask_level, pri_ratio;         // pri_ratio: what select_secondary takes (the option squared)
 };
 
-struct PlanRec {                         // AlignPlan (host_map.cpp) after plan_round1, as far as it is set there; 80 bytes
+struct PlanRec {                         // AlignPlan (host_plan.cpp) after plan_round1, as far as it is set there; 80 bytes
 	int64_t as, ae, vs0, vs1, mid_ve;
 	int32_t reg, as1, mid_qe, has_right, t_left, t_left2, t_right, t_right2;
 	int32_t gap0, n_gap;                 // its gap segments: seg[gap0 .. gap0 + n_gap)

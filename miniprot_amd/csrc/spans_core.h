@@ -54,7 +54,7 @@ struct AsmRec {                          // what spans_assemble leaves of a plan
 
 struct SpansSerial : StatsSerial {};     // a team of one: the host
 
-// make_segment (host_map.cpp; align.c:62-80): the shortcut's score, or the call that aligns the span.  Returns true for a DP task
+// make_segment (host_plan.cpp; align.c:62-80): the shortcut's score, or the call that aligns the span.  Returns true for a DP task
 template<class S> MPA_HD inline bool spans_segment(const SpansParams &p, const SpansPlan &P, const S &g, const uint8_t *tab, const uint8_t *text, int32_t ne0, int32_t ne1, int32_t ae0,
                                                    int32_t ae1, SegRec &s, mpa_dp_task_t &t)
 {

@@ -42,7 +42,7 @@ def aa13():
 
 
 def kmer_words(prot, k=KMER2, tab=None):
-    """the packed word of the k-mer ending at every residue that ends one (query_groups(), host_map.cpp: a residue with a code of 14
+    """the packed word of the k-mer ending at every residue that ends one (query_groups(), host_plan.cpp: a residue with a code of 14
     or more starts the run again), in query order"""
     tab = aa13() if tab is None else tab
     mask = (1 << 4 * k) - 1

@@ -2,7 +2,7 @@
 // -fsanitize=address,undefined and runs it).  Hand-written and random refinement chains over a small genome go through the shared
 // core twice -- with a team of one (PlansSerial, what MPA_GPU_PLANS=model runs) and with a team of 64 host threads that meet at a
 // barrier for every sync, sum and ballot (the device's wavefront in slow motion: same lane-strided loops, same lane-0 work) -- and
-// are compared, field by field, with plain restatements of the host functions on std::vector, written here after host_map.cpp
+// are compared, field by field, with plain restatements of the host functions on std::vector, written here after host_plan.cpp
 // (refine_region_from_chains, mark_reliable_anchors, plan_alignment, plan_round1, make_segment, ungapped_score) and
 // host_regions.cpp (chain_score_ungapped, sort_regions, assign_parents, select_secondary with its renumbering, extension_limits in
 // its genome-coordinate form).  The order of equal scores is the reference's unstable radix sort: both sides take it from

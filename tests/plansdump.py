@@ -1,5 +1,5 @@
 """MPA_PLANS_DUMP=<file>: what the step from the refinement chains of every window to the round-1 DP tasks left in every query's
-state, whichever path produced it -- the host functions of host_map.cpp (stage_refine_to_plan, plan_round1), the shared core on the
+state, whichever path produced it -- the host functions of host_plan.cpp (stage_refine_to_plan, plan_round1), the shared core on the
 host (MPA_GPU_PLANS=model) or k_plans on the device (MPA_GPU_PLANS=1).  This is how the tests see the step without an exported symbol.
 
 Layout (little endian, appended batch after batch, inside a batch in query order):

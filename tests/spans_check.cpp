@@ -2,7 +2,7 @@
 // -fsanitize=address,undefined and runs it).  Hand-written and random plans over a small genome go through the shared core twice --
 // with a team of one (SpansSerial, what MPA_GPU_SPANS=model runs) and with a team of 64 host threads that meet at a barrier for every
 // sync, sum, scan and broadcast (the device's wavefront in slow motion) -- and are compared, field by field and word by word, with
-// plain restatements of the host functions on std::vector, written here after host_align.cpp and host_map.cpp (take_round1_emit_round2,
+// plain restatements of the host functions on std::vector, written here after host_align.cpp and host_plan.cpp (take_round1_emit_round2,
 // store_result; make_segment, ungapped_score; assemble_alignment, append_cigar, count_exons).  Every output slot is a heap block of exactly the
 // plan's size, so a word written past it is AddressSanitizer's to report.
 #include <algorithm>

@@ -1,7 +1,7 @@
 """Refinement chains to regions, alignment plans, round-1 DP tasks and gap segments through the code the device runs
 (miniprot_amd/csrc/plans_core.h), on the CPU.
 
-MPA_GPU_PLANS=model makes batch_plan_phase() (host_map.cpp) collect the chains of every refinement window of a query and run the shared
+MPA_GPU_PLANS=model makes batch_plan_phase() (host_plan.cpp) collect the chains of every refinement window of a query and run the shared
 core with a team of one where it otherwise runs refine_region_from_chains / sort_regions / assign_parents / select_secondary /
 extension_limits / mark_reliable_anchors / plan_alignment / plan_round1: the stage machine with the oracle as DP executor must still
 print the reference's bytes, and the step's own result -- MPA_PLANS_DUMP, tests/plansdump.py -- must equal the dump of the run with the

@@ -1,6 +1,6 @@
 """Main chains to refinement windows through the code the device runs (miniprot_amd/csrc/regions_core.h), on the CPU.
 
-MPA_GPU_REGIONS=model makes stage_windows_from_chains() (host_map.cpp) run the shared core with a team of one where it otherwise runs
+MPA_GPU_REGIONS=model makes stage_windows_from_chains() (host_plan.cpp) run the shared core with a team of one where it otherwise runs
 regions_from_chains / sort_regions / assign_parents / select_secondary / extension_limits: the stage machine with the oracle as DP
 executor must still print the reference's bytes, and the stage's own result -- MPA_REGIONS_DUMP, tests/regionsdump.py -- must equal the
 dump of the run with the knob unset, byte for byte.  A stand-alone program (tests/regions_check.cpp, compiled here with

@@ -1,7 +1,7 @@
 """Whole-path parity at SCALE on the GPU, against the reference binary run live on the same box (oracle/_ref/miniprot travels
 with the repo).  These are the regimes the small golden cases never reach: `-I` at hundreds of Mbp with N runs and tandem
 paralogs, mini-batches big enough that the library switches GPU seeding and the GPU refinement scan on BY ITSELF (thresholds of
-host_map.cpp left at their defaults), `-G 500000` with 250 000-row extension windows, and the widest extension classes
+host_plan.cpp left at their defaults), `-G 500000` with 250 000-row extension windows, and the widest extension classes
 (k_ext_wide<8>, k_ext_wide<16>), and wide extensions under large penalties.  About two minutes in total."""
 import ctypes as C
 import os

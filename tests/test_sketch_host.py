@@ -1,4 +1,4 @@
-"""The host's sketch stage (host_map.cpp stage_seeds: protein sketch, bucket lookup, occurrence cut-off; map.c:126-170) pinned
+"""The host's sketch stage (host_plan.cpp stage_seeds: protein sketch, bucket lookup, occurrence cut-off; map.c:126-170) pinned
 directly: mpa_dbg_seed_jobs(ctx = NULL) against a numpy restatement built from the oracle's mpo_sketch_prot (pinned to the reference
 in tests/test_oracle.py) and mpa_idx_bucket_counts -- same kept seeds, same order, same cut-off per query.  This stage is the
 yardstick of tests/test_sketch_gpu.py; until now it was pinned only through whole-path goldens."""
