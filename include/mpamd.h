@@ -208,8 +208,8 @@ void mpa_dp_total_stats(mpa_ctx_t *ctx, mpa_dp_stats_t *st, int reset);
 int mpa_dp_run32(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *opt, const mpa_qbatch_t *q,
                  int64_t n, const mpa_dp_task_t *tasks, mpa_dp_rst_t *rst, uint32_t **cigar_pool, int64_t *n_pool);
 
-/* Extension calls of 257..1024 columns are swept by two or four workgroups that hand column-block boundaries to each other
- * through HBM.  Should a hand-off not arrive within seconds (a stalled hardware queue), mpa_dp_run() repeats the round with
+/* Extension calls of 257..1024 columns (with MPA_DP_SPLIT_WIDE=1: of up to 3072 columns) are swept by two or four (eight, twelve)
+ * workgroups that hand column-block boundaries to each other through HBM.  Should a hand-off not arrive within seconds (a stalled hardware queue), mpa_dp_run() repeats the round with
  * those calls on the one-wave path -- same results, no error.  How often that happened on this context: */
 int64_t mpa_dp_handoff_retries(const mpa_ctx_t *ctx);
 

@@ -38,6 +38,21 @@ int mpa_dbg_spans(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, 
 int64_t mpa_dbg_dp_plan_device(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, int32_t n_seq, const int64_t *q_off, int64_t n,
                                const mpa_dp_task_t *tasks, const int64_t *knobs, void *buf, int64_t cap);
 
+/* MPA_DP_SPLIT_WIDE (extension calls of 1025..3072 columns on the classes X_SPLIT8 / X_SPLIT12, 8 / 12 workgroups
+ * per pair of calls).  mpa_dbg_dp_plan_wide is mpa_dbg_dp_plan (mpamd.h) with knobs[9]: knobs[8] is split_wide, which the hook -- like
+ * the executor -- drops with the worker pool (knobs[4]) and in a repeated round (knobs[2]).  Its serialisation is mpa_dbg_dp_plan's,
+ * byte for byte, followed by five int64: first descriptor and number of descriptors of X_SPLIT8, the same of X_SPLIT12, and the number of
+ * boundaries n_bound (11 per X_SPLIT12 group, 7 per X_SPLIT8, 3 per X_SPLIT4, 1 per X_SPLIT2).  The descriptors of the two classes lie
+ * between X_SPLIT4's and X_128's in ExtWave[]; their calls carry DTask::cls 9 and 10.  mpa_dbg_dp_plan_device_wide is
+ * mpa_dbg_dp_plan_device with the same ninth knob and the same five words.
+ * mpa_dbg_dp_last_classes: the extension calls per DpClass (0 .. 15: X_16, X_32, X_64, X_W2, X_W4, X_SPLIT2, X_SPLIT4, X_HUGE, X_128,
+ * X_SPLIT8, X_SPLIT12) in the plan of the context's last mpa_dp_run -- of its repeat, when a hand-off timed out. */
+int64_t mpa_dbg_dp_plan_wide(const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, int32_t n_seq, const int64_t *q_off, int64_t n, const mpa_dp_task_t *tasks,
+                             const int64_t *knobs, void *buf, int64_t cap);
+int64_t mpa_dbg_dp_plan_device_wide(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, int32_t n_seq, const int64_t *q_off, int64_t n,
+                                    const mpa_dp_task_t *tasks, const int64_t *knobs, void *buf, int64_t cap);
+int mpa_dbg_dp_last_classes(const mpa_ctx_t *ctx, int64_t ext_calls[16]);
+
 /* A DP round from device-resident tasks (MPA_GPU_ROUND2): the arguments of mpa_dp_run.  On a context the hook
  * puts the tasks into a device pool, has their bounds reduced there (k_task_bounds), plans the round from the tasks in place, runs it
  * with the result records and the dense CIGAR pool assembled on the device in front of the round's one wait, and only then fetches the

@@ -554,6 +554,52 @@ def dbg_dp_plan_device(ctx, dpopt, ctg_len, q_off, tasks, knobs):
     return buf.tobytes()
 
 
+DP_PLAN_KNOBS_WIDE = ("lite_min", "lite_wide", "no_split", "antidiag", "pool", "ext_dual", "unit_prio", "tb_budget", "split_wide")
+DP_PLAN_WIDE_TAIL = 40   # bytes the *_wide serialisations add: int64 first, count of X_SPLIT8; first, count of X_SPLIT12; n_bound
+X_HUGE, X_SPLIT8, X_SPLIT12 = 7, 9, 10   # DpClass numbers (dp_device.h) in dbg_dp_last_classes()
+
+
+def _dp_plan_wide(f, head, dpopt, ctg_len, q_off, tasks, knobs, declines):
+    import numpy as np
+    tasks = np.ascontiguousarray(tasks, dtype=DP_TASK)
+    ctg_len = np.ascontiguousarray(ctg_len, dtype=np.int64)
+    q_off = np.ascontiguousarray(q_off, dtype=np.int64)
+    kn = np.array([knobs.get(k, 0) for k in DP_PLAN_KNOBS_WIDE], dtype=np.int64)
+    f.restype = C.c_int64
+    f.argtypes = [C.c_void_p] * len(head) + [C.POINTER(DpOpt), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    args = tuple(head) + (C.byref(dpopt), len(ctg_len), ctg_len.ctypes.data, len(q_off) - 1, q_off.ctypes.data, len(tasks), tasks.ctypes.data, kn.ctypes.data)
+    need = f(*args, None, 0)
+    if need < 0 or (declines and need == DP_PLAN_DECLINED):
+        return int(need), last_error()
+    buf = np.zeros(need, dtype=np.uint8)
+    got = f(*args, buf.ctypes.data, need)
+    if got != need:
+        return int(got), last_error()
+    return buf.tobytes()
+
+
+def dbg_dp_plan_wide(dpopt, ctg_len, q_off, tasks, knobs):
+    """mpa_dbg_dp_plan_wide(): dbg_dp_plan() with a ninth knob, split_wide (MPA_DP_SPLIT_WIDE; missing: 0).  The bytes are dbg_dp_plan()'s
+    followed by DP_PLAN_WIDE_TAIL more (include/mpamd_dbg.h); (code, message) when the planner refuses the table."""
+    return _dp_plan_wide(dbg_lib().mpa_dbg_dp_plan_wide, (), dpopt, ctg_len, q_off, tasks, knobs, False)
+
+
+def dbg_dp_plan_device_wide(ctx, dpopt, ctg_len, q_off, tasks, knobs):
+    """mpa_dbg_dp_plan_device_wide(): dbg_dp_plan_device() with the ninth knob and the tail of dbg_dp_plan_wide()."""
+    return _dp_plan_wide(dbg_lib().mpa_dbg_dp_plan_device_wide, (ctx.h if ctx else None,), dpopt, ctg_len, q_off, tasks, knobs, True)
+
+
+def dbg_dp_last_classes(ctx):
+    """mpa_dbg_dp_last_classes(): extension calls per DpClass (a list of 16) in the plan of the context's last dp_run()."""
+    import numpy as np
+    out = np.zeros(16, np.int64)
+    f = dbg_lib().mpa_dbg_dp_last_classes
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_void_p]
+    _check(f(ctx.h, out.ctypes.data))
+    return [int(x) for x in out]
+
+
 ROUND2_DECLINED = 1   # MPA_DBG_ROUND2_DECLINED (include/mpamd_dbg.h)
 ROUND2_REC = ("plan_waits", "round_waits", "bytes_up", "task_bytes_up", "bytes_down", "pool_bytes_down", "pool_bytes_fetched", "prep_bound", "max_nl", "max_al", "n_pool", "reserved")
 

@@ -223,6 +223,7 @@ mpa_ctx_t *mpa_ctx_create(int device)
 	if (const char *s = getenv("MPA_TB_BUDGET_MB")) ctx->tb_budget = (size_t)atoll(s) << 20;
 	if (const char *s = getenv("MPA_DP_LITE_MIN")) ctx->lite_min = atoi(s);
 	if (const char *s = getenv("MPA_DP_LITE_WIDE")) ctx->lite_wide = atoi(s) != 0;
+	if (const char *s = getenv("MPA_DP_SPLIT_WIDE")) ctx->split_wide = atoi(s) != 0;
 	return ctx;
 }
 
@@ -276,6 +277,7 @@ mpa_ctx_t *ctx_sibling(mpa_ctx_t *ctx, int k)
 		sb->tb_budget = ctx->tb_budget;
 		sb->lite_min = ctx->lite_min;
 		sb->lite_wide = ctx->lite_wide;
+		sb->split_wide = ctx->split_wide;
 		sb->root = ctx;
 		ctx->siblings.push_back(sb);
 	}

@@ -42,6 +42,8 @@ enum DpClass : int32_t {
 	X_SPLIT2, X_SPLIT4,          // up to 512 / 1024 columns: two / four workgroups of four waves per pair of calls, boundaries handed over in HBM
 	X_HUGE,                      // the block-major one-wave int32 sweep (k_ext_huge): wider calls, and whatever the packed int16 sweeps may not take
 	X_128,                       // 65..128 columns, one call per wave (column c + 64 in the high half of lane c)
+	X_SPLIT8, X_SPLIT12,         // up to 2048 / 3072 columns: eight / twelve workgroups per pair of calls (MPA_DP_SPLIT_WIDE=1; else such calls are X_HUGE).
+	                             // Numbered behind X_128 so that no earlier number moves; their ExtWave descriptors follow X_SPLIT4's
 	// traceback calls (CIGAR): the plain sweep that writes the traceback matrix ...
 	T_16 = 0, T_32, T_64,        // 4 / 2 / 1 call(s) per wave
 	T_W2, T_W4, T_W8, T_W16,     // one call per group of 2 / 4 / 8 / 16 waves: up to 128 / 256 / 512 / 1024 columns
@@ -143,7 +145,7 @@ enum DpUnitKind : int32_t {
 	U_EXT16 = 0, U_EXT32, U_EXT64,      // up to four independent extension waves (16 / 32 / 64 lanes per call), descriptors first .. first+count
 	U_EXT_W2,                           // up to two two-wave extension groups
 	U_EXT_W4,                           // one four-wave extension group
-	U_EXT_SPLIT,                        // a quarter (or half) of a 1024- (512-) column pair of calls: blk of n_blk
+	U_EXT_SPLIT,                        // a quarter (or half) of a 1024- (512-) column pair of calls: blk of n_blk (an eighth / a twelfth of a 2048- / 3072-column pair)
 	U_GLOB16, U_GLOB32, U_GLOB64,       // up to four independent traceback waves
 	U_GLOB_MB,                          // ... block-major ones (more than 1024 columns)
 	U_GLOB_W2, U_GLOB_W4,               // two two-wave / one four-wave traceback group(s)

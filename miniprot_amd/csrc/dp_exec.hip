@@ -783,6 +783,7 @@ static DpPlanKnobs dp_plan_knobs(const mpa_ctx_t *ctx)
 	static const bool unit_prio = [] { const char *e = getenv("MPA_DP_PRIO"); return !e || atoi(e) != 0; }();   // (MPA_DP_PRIO=0: measurement)
 	DpPlanKnobs kn;
 	kn.lite_min = ctx->lite_min, kn.lite_wide = ctx->lite_wide, kn.no_split = ctx->no_split, kn.antidiag = ctx->antidiag, kn.pool = dp_pool_enabled();
+	kn.split_wide = ctx->split_wide && !kn.pool && !kn.no_split;
 	kn.ext_dual = ext_dual, kn.unit_prio = unit_prio, kn.tb_budget = (int64_t)ctx->tb_budget;
 	return kn;
 }
@@ -800,7 +801,7 @@ static int dev_dp_plan_run(mpa_ctx_t *ctx, hipStream_t s, const int64_t *d_ctg_l
 {
 	if (const char *why = dp_plan_device_declines(opt, kn, n)) { set_error(std::string("device DP plan: ") + why); return MPA_ERR_UNSUPPORTED; }
 	if (q->n_seq < 0 || n_ctg < 0) { set_error("device DP plan: no queries or contigs"); return MPA_ERR_UNSUPPORTED; }
-	const size_t N = (size_t)n, U = (size_t)dp_units_bound(n), nb = (size_t)dp_blocks(n, TeamWG::W);
+	const size_t N = (size_t)n, U = (size_t)dp_units_bound(n, kn.split_wide != 0), nb = (size_t)dp_blocks(n, TeamWG::W);
 	auto al256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
 	// what goes up, in one block (rz: the tasks are read where they are -- no task bytes are staged or uploaded)
 	const size_t up_raw = 0, up_qoff = up_raw + (rz ? 0 : al256(sizeof(mpa_dp_task_t) * N)), up_ctg = up_qoff + al256(8 * ((size_t)q->n_seq + 1));
@@ -889,7 +890,7 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 	int rc;
 	// 1. plan
 	DpPlan plan;
-	const DpPlanKnobs kn = dp_plan_knobs(ctx);
+	DpPlanKnobs kn = dp_plan_knobs(ctx);
 	bool planned = false;
 	const int64_t waits0 = ctx->n_waits;
 	if (rz) {                                                   // (MPA_GPU_ROUND2=1) planned from the tasks in place, or not run here at all
@@ -914,6 +915,21 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 		if ((rc = dp_plan(in, n, mi->ctg.empty() ? nullptr : &mi->ctg[0].len, sizeof(mi->ctg[0]), (int32_t)mi->ctg.size(), q, opt, kn, sizeof(DpRoundArgs), plan))) { set_error(plan.err); return rc; }
 		timing_note("  dp: classify/sort/layout", now_ms() - t_begin);
 	}
+	// X_SPLIT8 / X_SPLIT12 groups need 7 / 11 boundaries of key_stride granules each: a granule pool that cannot grow that far declines
+	// them -- the round is planned again with those calls on k_ext_huge (same results), before anything of it is enqueued
+	if (kn.split_wide && plan.ext_wide[0].cnt + plan.ext_wide[1].cnt > 0) {
+		tl_alloc_failed = false;
+		if (ctx->xg.ensure(plan.sz.xg)) {
+			tl_alloc_failed = false;
+			if (rz) { set_error("round 2 resident: the boundary pool of the 2048/3072-column extension classes cannot grow"); return MPA_ERR_UNSUPPORTED; }
+			if (timing_on()) fprintf(stderr, "[mpa-timing]   2048/3072-column extension classes declined (%zu bytes of boundary granules): those calls on the one-wave int32 sweep\n", plan.sz.xg);
+			kn.split_wide = 0;
+			if ((rc = dp_plan(in, n, mi->ctg.empty() ? nullptr : &mi->ctg[0].len, sizeof(mi->ctg[0]), (int32_t)mi->ctg.size(), q, opt, kn, sizeof(DpRoundArgs), plan))) { set_error(plan.err); return rc; }
+		}
+	}
+	memcpy(ctx->last_ext_calls, plan.ext_calls, sizeof(ctx->last_ext_calls));
+	if (timing_on() && plan.ext_wide[0].cnt + plan.ext_wide[1].cnt > 0)
+		fprintf(stderr, "[mpa-timing]   dp: %d + %d groups of the 2048- / 3072-column extension classes (8 / 12 workgroups each), %lld boundaries\n", plan.ext_wide[0].cnt, plan.ext_wide[1].cnt, (long long)plan.n_bound);
 	DpRun R{ ctx, ctx->stream, plan, kn, in };
 	R.t_mark = now_ms();
 	R.rz = rz;
@@ -1025,10 +1041,11 @@ int64_t mpa_dbg_dp_plan(const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ct
 
 namespace mpa {
 size_t dp_round_args_bytes() { return sizeof(DpRoundArgs); }
+void dp_last_ext_calls(const mpa_ctx_t *ctx, int64_t ext_calls[16]) { memcpy(ext_calls, ctx->last_ext_calls, sizeof(ctx->last_ext_calls)); }
 // mpa_dbg_dp_plan_device on a context (dpplan_dbg.cpp): the device planner on a task table, then every section it left in the pools
 // downloaded into a plan's vectors and serialised as mpa_dbg_dp_plan does.  1: declined (the last error says why).
 int64_t dev_dp_plan_dbg(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, const mpa_qbatch_t *q, int64_t n, const mpa_dp_task_t *in,
-                        const DpPlanKnobs &kn, void *buf, int64_t cap)
+                        const DpPlanKnobs &kn, void *buf, int64_t cap, bool wide)
 {
 	HIP_TRY(hipSetDevice(ctx->device));
 	const DpDevHead *head = nullptr;
@@ -1057,7 +1074,7 @@ int64_t dev_dp_plan_dbg(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int32_t n_ctg, c
 		for (size_t k = 0; k < r.n_list; ++k) if (r.list[k] != P.glob_ids[k]) { set_error("device DP plan: the chunk's call list is not the sorted order"); return MPA_ERR_HIP; }
 	}
 	for (size_t k = 0; k < wl.size(); ++k) if (wl[k] != P.glob_ids[P.n_reg_glob + k]) { set_error("device DP plan: the walk list is not the sorted order"); return MPA_ERR_HIP; }
-	return dp_plan_write(P, units, buf, cap);
+	return dp_plan_write(P, units, buf, cap, wide);
 }
 // mpa_dbg_dp_run_resident on a context (round2_dbg.cpp): the tasks into a device pool, their bounds reduced there, the resident round, then
 // the explicit fetch of the dense pool.  rec: the hook's int64 record (mpamd_dbg.h).  1: declined (the last error says why).

@@ -1156,7 +1156,7 @@ struct ExtWideArgs {
 	int32_t *err;             // set to 1 if a hand-off never arrived (bounded spin)
 };
 
-// where a workgroup of the split kernel sits: group = pair of calls, blk = which quarter (or half) of its columns
+// where a workgroup of the split kernel sits: group = pair of calls, blk = which quarter (or half, eighth, twelfth) of its columns
 struct SplitPos { int32_t group, blk, n_blk, xg_first; };
 
 // One 8-byte granule {payload, tag} per value and row, written by ONE write-through store and polled with loads that bypass
@@ -1317,7 +1317,13 @@ __device__ __forceinline__ void ext_wide_body(const ExtWideArgs &a, const int gr
 		const uint4 q0 = ring[44], q1 = ring[45];
 		dn[1] = q0.x, dn[0] = q1.x, ac[1] = q0.y, ac[0] = q1.y, dn[2] = ac[2] = 0;
 	}
-	const int32_t max_nl = wvp->max_nl;
+	// SPLIT, dead block: a class covers a fixed number of columns (2048 or 3072 over 8 or 12 workgroups), so a workgroup's 256 columns
+	// may lie wholly at or beyond ncol of BOTH halves (a pair of 2100-column calls leaves three such workgroups of twelve).  It sweeps
+	// no row: its keys could never win a row (a dead column's key has value 0 and a larger column than block 0's), and nobody to its
+	// right has a live column either.  It has drawn its ticket and counts into `done` below like every other workgroup, and does the
+	// replay if it is the last to arrive; its left neighbour may keep writing granules nobody reads.
+	const bool dead_blk = SPLIT && blk * NWB * 64 >=(ncol[0] > ncol[1] ? ncol[0] : ncol[1]);
+	const int32_t max_nl = dead_blk ? 0 : wvp->max_nl;
 	uint4 rcur = ring[46], rnext = ring[47];                           // records of rows i and i + 1
 	uint32_t S = prof2s(pb0 + (rcur.w & 0xffff), pb1 + (rcur.w >> 16));   // profile scores of row i (generic rows)
 	bool have_hD = false;                                              // hD already holds row i's max(diagonal, D) (behind the asm rows)

@@ -57,7 +57,7 @@ static int classify(DpPlan &P, const mpa_dp_task_t *in, int64_t n, const int64_t
 		case DP_CALL_NO_CIGAR: return refuse(P, MPA_ERR_UNSUPPORTED, "global DP without CIGAR is not part of miniprot's path");
 		default: break;
 		}
-		if (is_ext) P.ext_ids.push_back((int32_t)k), P.max_nl_ext = std::max(P.max_nl_ext, in[k].nl);
+		if (is_ext) P.ext_ids.push_back((int32_t)k), P.max_nl_ext = std::max(P.max_nl_ext, in[k].nl), ++P.ext_calls[P.tasks[(size_t)k].cls];
 		else P.glob_ids.push_back((int32_t)k);
 	}
 	return MPA_OK;
@@ -122,11 +122,18 @@ static WaveRange pack_ext_class(DpPlan &P, const std::vector<int32_t> &ids, size
 	return r;
 }
 
+// the descriptors of an extension class
+static const WaveRange &ext_range(const DpPlan &P, int cls) { return cls == X_128 ? P.ext128 : cls >= X_SPLIT8 ? P.ext_wide[cls - X_SPLIT8] : P.ext[cls]; }
+
 static void pack_waves(DpPlan &P)
 {
 	const std::vector<DTask> &T = P.tasks;
 	size_t p = 0;
 	for (int cls = X_16; cls <= X_SPLIT4; ++cls) P.ext[cls] = pack_ext_class(P, P.ext_ids, p, cls, ext_calls_per_wave(cls), false);
+	// X_SPLIT8 / X_SPLIT12 sort behind X_HUGE and X_128; their descriptors follow X_SPLIT4's, so that the wide groups stay neighbours (row keys)
+	size_t pw = p + P.huge_ids.size();
+	while (pw < P.ext_ids.size() && T[P.ext_ids[pw]].cls == X_128) ++pw;
+	for (int cls = X_SPLIT8; cls <= X_SPLIT12; ++cls) P.ext_wide[cls - X_SPLIT8] = pack_ext_class(P, P.ext_ids, pw, cls, ext_calls_per_wave(cls), false);
 	for (size_t h = 0; h < P.huge_ids.size();) P.huge_waves.push_back(pack_wave<GlobWave>(T, P.huge_ids, h, P.huge_ids.size(), 1));
 	p += P.huge_ids.size();                                     // (X_HUGE sorts between X_SPLIT4 and X_128)
 	P.ext128 = pack_ext_class(P, P.ext_ids, p, X_128, ext_calls_per_wave(X_128), false);
@@ -138,12 +145,17 @@ static void pack_waves(DpPlan &P)
 	for (int c = 0; c < 5; ++c) P.walk_cnt[c] = 0;
 	for (size_t k = P.n_reg_glob; k < P.glob_ids.size(); ++k) ++P.walk_cnt[T[P.glob_ids[k]].cls - T_LITE16];
 	// per-row keys of the wide extension kernels: [group][2 halves][key_stride]
-	for (int cls = X_W2; cls <= X_SPLIT4; ++cls)
-		for (int k = 0; k < P.ext[cls].cnt; ++k) P.key_stride = std::max<int64_t>(P.key_stride, P.ewaves[P.ext[cls].first + k].max_nl), ++P.n_wide_groups;
+	for (int k = X_W2; k < kNumExtPacked + kNumExtWide; ++k) {
+		const WaveRange &r = ext_range(P, ext_class_at(k));
+		for (int j = 0; j < r.cnt; ++j) P.key_stride = std::max<int64_t>(P.key_stride, P.ewaves[r.first + j].max_nl), ++P.n_wide_groups;
+	}
 	P.key_stride = (P.key_stride + 64) & ~(int64_t)63;
-	// split classes: boundary granules (16 B per row and boundary: 3 boundaries per 1024-column group, 1 per 512-column group),
+	// split classes: boundary granules (16 B per row and boundary: n_blk - 1 boundaries per group -- 11, 7, 3, 1 for 3072, 2048, 1024, 512 columns),
 	// then the per-group completion counters and the error flag
-	P.n_split = P.ext[X_SPLIT2].cnt + P.ext[X_SPLIT4].cnt, P.n_bound = 3 * (int64_t)P.ext[X_SPLIT4].cnt + P.ext[X_SPLIT2].cnt;
+	for (int k = 0; k < kNumExtSplit; ++k) {
+		const int cls = ext_split_at(k);
+		P.n_split += ext_range(P, cls).cnt, P.n_bound += (int64_t)ext_range(P, cls).cnt * (dp_ext_unit_blocks(cls) - 1);
+	}
 	P.xg_bytes = (size_t)P.n_bound * P.key_stride * 16, P.xg_tail = (2 * (size_t)P.n_split + 1) * 4;   // + done[n_split], ticket[n_split], err
 }
 
@@ -204,11 +216,13 @@ static std::vector<Cost> unit_costs(const DpPlan &P, const DpPlanKnobs &kn)
 		if (!(cls == X_32 && kn.antidiag)) add_ext(cls, P.ext[cls]);
 	add_ext(X_W2, P.ext[X_W2]);
 	add_ext(X_W4, P.ext[X_W4]);
-	const int n4 = P.ext[X_SPLIT4].cnt;                           // split groups and their boundaries are numbered 1024-column groups first
-	for (int k = 0; k < n4; ++k)
-		for (int b = 0; b < dp_ext_unit_blocks(X_SPLIT4); ++b) add(U_EXT_SPLIT, P.ext[X_SPLIT4].first + k, 1, (int64_t)P.ewaves[P.ext[X_SPLIT4].first + k].max_nl * dp_ext_unit_ns(X_SPLIT4), b, 4, k, 3 * k);
-	for (int k = 0; k < P.ext[X_SPLIT2].cnt; ++k)
-		for (int b = 0; b < dp_ext_unit_blocks(X_SPLIT2); ++b) add(U_EXT_SPLIT, P.ext[X_SPLIT2].first + k, 1, (int64_t)P.ewaves[P.ext[X_SPLIT2].first + k].max_nl * dp_ext_unit_ns(X_SPLIT2), b, 2, n4 + k, 3 * n4 + k);
+	int sgroup = 0, xg = 0;                                       // split groups and their boundaries are numbered widest class first
+	for (int c = 0; c < kNumExtSplit; ++c) {
+		const int cls = ext_split_at(c), n_blk = dp_ext_unit_blocks(cls);
+		const WaveRange &r = ext_range(P, cls);
+		for (int k = 0; k < r.cnt; ++k, ++sgroup, xg += n_blk - 1)
+			for (int b = 0; b < n_blk; ++b) add(dp_ext_unit_kind(cls, pool), r.first + k, 1, (int64_t)P.ewaves[r.first + k].max_nl * dp_ext_unit_ns(cls), b, n_blk, sgroup, xg);
+	}
 	add_ext(X_128, P.ext128);
 	for (int c = 0; c < 4; ++c) add_range(dp_lite_unit_kind(T_LITE16 + c), P.lite[c], dp_per_narrow(pool), dp_lite_unit_ns(T_LITE16 + c));
 	if (P.round_has_glob) {
@@ -284,7 +298,7 @@ static void size_buffers(DpPlan &P, int64_t n, size_t round_args_bytes)
 	u.tasks = 0, u.chunks = u.tasks + al256(sizeof(DTask) * N), u.q = u.chunks + al256(sizeof(PrepChunk) * n_prep);
 	u.waves = u.q + al256((size_t)P.q_bytes), u.list = u.waves + al256(sizeof(ExtWave) * n_ew);
 	u.gw = u.list + al256(4 * n_glob), u.units = u.gw + al256(sizeof(GlobWave) * (n_glob + 8));
-	u.off = u.units + al256(sizeof(DpUnit) * (4 * n_ew + n_glob + 64));
+	u.off = u.units + al256(sizeof(DpUnit) * (4 * n_ew + n_glob + 64 + 4 * (size_t)P.ext_wide[0].cnt + 8 * (size_t)P.ext_wide[1].cnt));   // (8 / 12 units per X_SPLIT8 / X_SPLIT12 group)
 	u.ids = u.off + al256(8 * n_glob), u.args = u.ids + al256(4 * n_glob), u.wl = u.args + al256(round_args_bytes);
 	u.end = u.wl + al256(4 * P.n_lite);
 	DpPlan::Down &d = P.dn;
@@ -340,7 +354,7 @@ int dp_plan(const mpa_dp_task_t *in, int64_t n, const int64_t *ctg_len, size_t c
 	return MPA_OK;
 }
 
-int64_t dp_plan_serialize(DpPlan &P, const DpPlanKnobs &kn, void *buf, int64_t cap)
+int64_t dp_plan_serialize(DpPlan &P, const DpPlanKnobs &kn, void *buf, int64_t cap, bool wide)
 {
 	// the stages the executor runs behind its uploads
 	for (size_t ri = 0; ri < P.chunks.size(); ++ri) dp_plan_chunk_waves(P, ri);
@@ -348,10 +362,10 @@ int64_t dp_plan_serialize(DpPlan &P, const DpPlanKnobs &kn, void *buf, int64_t c
 	if (dp_plan_units(P, kn, units.data())) return P.rc;
 	units.resize(P.n_units);
 	dp_plan_stats(P);
-	return dp_plan_write(P, units, buf, cap);
+	return dp_plan_write(P, units, buf, cap, wide);
 }
 
-int64_t dp_plan_write(const DpPlan &P, const std::vector<DpUnit> &units, void *buf, int64_t cap)
+int64_t dp_plan_write(const DpPlan &P, const std::vector<DpUnit> &units, void *buf, int64_t cap, bool wide)
 {
 	std::vector<int64_t> h;
 	auto H = [&h](int64_t v) { h.push_back(v); };
@@ -393,13 +407,17 @@ int64_t dp_plan_write(const DpPlan &P, const std::vector<DpUnit> &units, void *b
 		{ P.huge_waves.data(), P.huge_waves.size() * sizeof(GlobWave) }, { P.huge_ids.data(), P.huge_ids.size() * 4 } };
 	size_t at = (h.size() + 2 * (sizeof(secs) / sizeof(secs[0]))) * 8;
 	for (const Sec &s : secs) H((int64_t)at), H((int64_t)s.bytes), at += (s.bytes + 7) & ~(size_t)7;
-	if (buf && (int64_t)at <= cap) {
-		memset(buf, 0, at);
+	// (mpa_dbg_dp_plan_wide) behind everything else: first and count of X_SPLIT8 and of X_SPLIT12, the boundary count
+	const int64_t tail[5] = { P.ext_wide[0].first, P.ext_wide[0].cnt, P.ext_wide[1].first, P.ext_wide[1].cnt, P.n_bound };
+	const size_t total = at + (wide ? sizeof(tail) : 0);
+	if (buf && (int64_t)total <= cap) {
+		memset(buf, 0, total);
 		memcpy(buf, h.data(), h.size() * 8);
 		size_t k = h.size() - 2 * (sizeof(secs) / sizeof(secs[0]));
 		for (const Sec &s : secs) { if (s.bytes) memcpy((char*)buf + h[k], s.p, s.bytes); k += 2; }
+		if (wide) memcpy((char*)buf + at, tail, sizeof(tail));
 	}
-	return (int64_t)at;
+	return (int64_t)total;
 }
 
 // ---- the device planner's host side: what it declines, the plan from its header, the model
@@ -438,10 +456,12 @@ int dp_plan_from_head(const DpDevHead &H, const int32_t *glob_ids, const mpa_qba
 	P.glob_ids.assign(glob_ids, glob_ids + H.n_glob);
 	P.n_reg_glob = (size_t)H.n_reg_glob, P.n_lite = (size_t)H.n_lite;
 	for (int c = 0; c < kNumExtPacked; ++c) P.ext[c] = WaveRange{ (int)H.ew_first[c], (int)H.ew_cnt[c] };
-	P.ext128 = WaveRange{ (int)H.ew_first[7], (int)H.ew_cnt[7] };
-	for (int c = 0; c < 4; ++c) P.lite[c] = WaveRange{ (int)H.ew_first[8 + c], (int)H.ew_cnt[8 + c] };
-	P.lite_w4 = WaveRange{ (int)H.ew_first[12], (int)H.ew_cnt[12] };
+	for (int c = 0; c < kNumExtWide; ++c) P.ext_wide[c] = WaveRange{ (int)H.ew_first[DPP_EW_SPLIT8 + c], (int)H.ew_cnt[DPP_EW_SPLIT8 + c] };
+	P.ext128 = WaveRange{ (int)H.ew_first[DPP_EW_128], (int)H.ew_cnt[DPP_EW_128] };
+	for (int c = 0; c < 4; ++c) P.lite[c] = WaveRange{ (int)H.ew_first[DPP_EW_LITE + c], (int)H.ew_cnt[DPP_EW_LITE + c] };
+	P.lite_w4 = WaveRange{ (int)H.ew_first[DPP_EW_LITE + 4], (int)H.ew_cnt[DPP_EW_LITE + 4] };
 	for (int c = 0; c < 5; ++c) P.walk_cnt[c] = (int32_t)H.walk_cnt[c];
+	for (int g = 0; g < 16; ++g) P.ext_calls[g] = H.run_cnt[g];
 	P.max_nl = (int32_t)H.max_nl, P.max_nl_ext = (int32_t)H.max_nl_ext;
 	P.rec_total = H.rec_total, P.rec_pad = H.rec_pad, P.prof_total = H.prof_total, P.cig_total = H.cig_total, P.bnd_total = H.bnd_total, P.hkey_total = 0;
 	P.lite_total = H.lite_total, P.ck_total = H.ck_total, P.tb_max = H.tb_max;
@@ -478,7 +498,7 @@ int dp_plan_model(const mpa_dp_task_t *in, int64_t n, const int64_t *ctg_len, in
 	const int64_t prep_bound = dp_plan_prep_bound(in, n, &max_nl, &max_al);
 	if (!dp_unit_costs_fit(max_nl, max_al)) return refuse(P, MPA_ERR_UNSUPPORTED, "unit costs that do not fit the sort key");
 	// the pools at the bounds the driver uses (dev_dp_plan), the scratch a team of one needs
-	const size_t N = (size_t)n, U = (size_t)dp_units_bound(n);
+	const size_t N = (size_t)n, U = (size_t)dp_units_bound(n, kn.split_wide != 0);
 	std::vector<DTask> tasks(N);
 	std::vector<PrepChunk> chunks((size_t)prep_bound + 1);
 	std::vector<ExtWave> waves(N + 16);

@@ -36,9 +36,11 @@ struct DpPlan {
 	std::vector<DTask> tasks;                   // indexed like the caller's array
 	std::vector<int32_t> ext_ids, glob_ids;     // sorted by (class, rows descending, index); glob_ids: plain sweep [0, n_reg_glob), then checkpointed
 	size_t n_reg_glob = 0, n_lite = 0;
+	int64_t ext_calls[16] = { 0 };              // extension calls per DpClass
 	std::vector<PrepChunk> prep;
 	std::vector<ExtWave> ewaves;
 	WaveRange ext[kNumExtPacked], ext128, lite[4], lite_w4;   // ... its parts: X_16 .. X_SPLIT4, X_128, T_LITE16 .. T_LITE128, T_LITE_W4
+	WaveRange ext_wide[kNumExtWide];            // ... and X_SPLIT8, X_SPLIT12 (split_wide), whose descriptors lie between X_SPLIT4's and X_128's
 	std::vector<int32_t> huge_ids;              // X_HUGE calls, with one GlobWave each
 	std::vector<GlobWave> huge_waves;
 	PenTable pen;
@@ -91,14 +93,17 @@ int64_t dp_plan_prep_bound(const mpa_dp_task_t *in, int64_t n, int64_t *max_nl, 
 std::string dp_plan_top(const DpPlan &plan, const DpPlanKnobs &kn);
 // the whole plan as mpa_dbg_dp_plan() hands it out (mpamd.h): runs the later stages, returns the bytes it takes (written when they fit cap)
 // or plan.rc
-int64_t dp_plan_serialize(DpPlan &plan, const DpPlanKnobs &kn, void *buf, int64_t cap);
+// (wide: as mpa_dbg_dp_plan_wide() does, mpamd_dbg.h: five more words behind everything else)
+int64_t dp_plan_serialize(DpPlan &plan, const DpPlanKnobs &kn, void *buf, int64_t cap, bool wide = false);
 // ... the serialisation alone, of a plan whose later stages have run (dp_plan_serialize, or the device planner's vectors filled in)
-int64_t dp_plan_write(const DpPlan &plan, const std::vector<DpUnit> &units, void *buf, int64_t cap);
+int64_t dp_plan_write(const DpPlan &plan, const std::vector<DpUnit> &units, void *buf, int64_t cap, bool wide = false);
 
 // ---- dp_exec.hip, for the test hook mpa_dbg_dp_plan_device (dpplan_dbg.cpp)
 size_t dp_round_args_bytes();            // the size of the worker pool's argument block: the model's round_args_bytes
+// ... and for mpa_dbg_dp_last_classes: extension calls per DpClass in the plan of the context's last mpa_dp_run
+void dp_last_ext_calls(const mpa_ctx_t *ctx, int64_t ext_calls[16]);
 // the device planner on a context, what it left serialised like dp_plan_serialize; 1: it declined (the last error says why)
 int64_t dev_dp_plan_dbg(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, const mpa_qbatch_t *q, int64_t n, const mpa_dp_task_t *in,
-                        const DpPlanKnobs &kn, void *buf, int64_t cap);
+                        const DpPlanKnobs &kn, void *buf, int64_t cap, bool wide = false);
 
 } // namespace mpa

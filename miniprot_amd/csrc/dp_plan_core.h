@@ -11,12 +11,25 @@
 namespace mpa {
 
 // ---- what a class means for packing (DpClass, dp_device.h)
-static const int kNumExtPacked = 7;                                   // X_16 .. X_SPLIT4: the classes of the packed int16 sweeps, in ascending width
+static const int kNumExtPacked = 7;                                   // X_16 .. X_SPLIT4: the classes of the packed int16 sweeps every plan may hold, in ascending width
+static const int kNumExtWide = 2;                                     // X_SPLIT8, X_SPLIT12: the same sweep over 8 / 12 workgroups (DpPlanKnobs::split_wide)
+// the packed classes in ascending width: X_16 .. X_SPLIT4, X_SPLIT8, X_SPLIT12 (k = 0 .. kNumExtPacked + kNumExtWide - 1); X_128 is X_W2's other shape
+MPA_DPP_HD int ext_class_at(int k) { return k < kNumExtPacked ? k : (int)X_SPLIT8 + (k - kNumExtPacked); }
+MPA_DPP_HD bool ext_is_split(int cls) { return cls == X_SPLIT2 || cls == X_SPLIT4 || cls == X_SPLIT8 || cls == X_SPLIT12; }   // workgroups hand column blocks over through HBM
+MPA_DPP_HD bool ext_is_wide_group(int cls) { return cls == X_W2 || cls == X_W4 || ext_is_split(cls); }        // a group of waves per pair of calls, with per-row keys
 MPA_DPP_HD int ext_lanes(int cls) { return cls == X_16 ? 16 : cls == X_32 ? 32 : 64; }                       // lanes per call
-MPA_DPP_HD int ext_waves(int cls) { return cls <= X_64 || cls == X_128 ? 1 : 1 << (cls - X_64); }            // waves per group: 1, 1, 1, 2, 4, 8, 16
+MPA_DPP_HD int ext_waves(int cls)                                                                            // waves per group: 1, 1, 1, 2, 4, 8, 16; 32, 48
+{
+	return cls == X_SPLIT8 ? 32 : cls == X_SPLIT12 ? 48 : cls <= X_64 || cls == X_128 ? 1 : 1 << (cls - X_64);
+}
 MPA_DPP_HD int ext_columns(int cls) { return cls == X_128 ? 128 : ext_lanes(cls) * ext_waves(cls); }         // columns the class covers (= profile row width)
 MPA_DPP_HD int ext_calls_per_wave(int cls) { return cls == X_128 ? 1 : 2 * (64 / ext_lanes(cls)); }          // ... per wave or group: two calls per lane
-MPA_DPP_HD int ext_class_of(int32_t ncol) { for (int c = X_16; c <= X_SPLIT4; ++c) if (ncol <= ext_columns(c)) return c; return X_HUGE; }
+// the narrowest class that covers ncol columns; split_wide: X_SPLIT8 / X_SPLIT12 beyond 1024 columns, else X_HUGE
+MPA_DPP_HD int ext_class_of(int32_t ncol, bool split_wide = false)
+{
+	for (int k = 0; k < kNumExtPacked + (split_wide ? kNumExtWide : 0); ++k) if (ncol <= ext_columns(ext_class_at(k))) return ext_class_at(k);
+	return X_HUGE;
+}
 MPA_DPP_HD int tb_class_of(int32_t ncol) { int c = T_16; while (c < T_MB && ncol > (16 << c)) ++c; return c; }   // 16, 32, ... 1024 columns, then block-major
 MPA_DPP_HD int tb_calls_per_wave(int cls) { return cls == T_16 ? 4 : cls == T_32 ? 2 : 1; }                  // the plain traceback sweep: one call per group of lanes
 MPA_DPP_HD int lite_columns(int cls) { return 16 << (cls - T_LITE16); }                                      // 16, 32, 64, 128, 256
@@ -29,6 +42,7 @@ MPA_DPP_HD int64_t lite_ckpt_dwords(int cls, int32_t max_nl) { return cls == T_L
 struct DpPlanKnobs {
 	int32_t lite_min = 384, lite_wide = 0;      // checkpointed traceback: from this many rows; 129..256 columns included
 	int32_t no_split = 0;                       // repeated round: no inter-workgroup hand-off
+	int32_t split_wide = 0;                     // MPA_DP_SPLIT_WIDE: 1025..3072-column extension calls on X_SPLIT8 / X_SPLIT12 (not with the pool, not in a repeated round)
 	int32_t antidiag = 0;                       // (measurement) the 32-column extension class runs on k_ext_antidiag
 	int32_t pool = 0;                           // the worker pool takes the round's units (MPA_DP_POOL)
 	int32_t ext_dual = 1, unit_prio = 1;        // MPA_DP_EXT_DUAL, MPA_DP_PRIO
@@ -87,8 +101,8 @@ MPA_DPP_HD int dp_classify_call(const mpa_dp_task_t &x, int32_t k, int32_t n_ctg
 	const bool may_saturate = (int64_t)x.al * o.max_mat + (int64_t)t.ncol * o.ge + (o.end_bonus > 0 ? o.end_bonus : 0) > 32000 || o.go + (int64_t)t.ncol * o.ge > 32000;
 	const bool packed_ok = !wide_ge && !may_saturate;
 	if (*is_ext) {
-		int cls = ext_class_of(t.ncol);
-		if (kn.no_split && cls >= X_SPLIT2) cls = X_HUGE;         // repeated round: no inter-workgroup hand-off (see mpa_dp_run)
+		int cls = ext_class_of(t.ncol, kn.split_wide && !kn.pool && !kn.no_split);
+		if (kn.no_split && ext_is_split(cls)) cls = X_HUGE;         // repeated round: no inter-workgroup hand-off (see mpa_dp_run)
 		if (!packed_ok) cls = X_HUGE;
 		if (cls == X_HUGE && seg_overflow) return DP_CALL_EXT_TOO_WIDE;
 		t.pw = cls == X_HUGE ? t.ncol : ext_columns(cls);
@@ -134,7 +148,7 @@ enum : int64_t { NS_EXT_NARROW = 160, NS_EXT_WIDE = 270, NS_EXT_SPLIT = 310, NS_
 // (worker pool: the one-wave kinds are units of ONE wave descriptor each, taken by single waves; without the pool a
 // workgroup's four waves take four neighbours of the sorted list)
 MPA_DPP_HD int dp_per_narrow(bool pool) { return pool ? 1 : 4; }
-// an extension class X_16 .. X_SPLIT4, X_128: the kind of its units, how many neighbouring descriptors share one, nanoseconds per row
+// an extension class X_16 .. X_SPLIT4, X_128, X_SPLIT8, X_SPLIT12: the kind of its units, how many neighbouring descriptors share one, nanoseconds per row
 // (worker pool: a workgroup goes on to its next unit, so all four waves must leave a unit through the same barriers -- a
 // 65..128-column group then takes a whole workgroup on the four-wave body, its waves 2 and 3 on dead columns)
 MPA_DPP_HD int dp_ext_unit_kind(int cls, bool pool)
@@ -142,8 +156,13 @@ MPA_DPP_HD int dp_ext_unit_kind(int cls, bool pool)
 	return cls <= X_64 ? U_EXT16 + cls : cls == X_W2 ? (pool ? (int)U_EXT_W4 : (int)U_EXT_W2) : cls == X_W4 ? (int)U_EXT_W4 : cls == X_128 ? (int)U_EXT128 : (int)U_EXT_SPLIT;
 }
 MPA_DPP_HD int dp_ext_unit_per(int cls, bool pool) { return cls <= X_64 || cls == X_128 ? dp_per_narrow(pool) : cls == X_W2 ? (pool ? 1 : 2) : 1; }
+// (X_SPLIT8 / X_SPLIT12 take NS_EXT_SPLIT: profiles/split_wide_ns_per_row.txt has 294-299 ns per row for a lone pair of them next to 293 for
+// the 1024-column groups in the same run, whose constant this is)
 MPA_DPP_HD int64_t dp_ext_unit_ns(int cls) { return cls <= X_64 ? NS_EXT_NARROW : cls <= X_W4 ? NS_EXT_WIDE : cls == X_128 ? NS_EXT128 : NS_EXT_SPLIT; }
-MPA_DPP_HD int dp_ext_unit_blocks(int cls) { return cls == X_SPLIT4 ? 4 : cls == X_SPLIT2 ? 2 : 1; }           // workgroups (units) per group
+MPA_DPP_HD int dp_ext_unit_blocks(int cls) { return ext_is_split(cls) ? ext_waves(cls) / 4 : 1; }              // workgroups (units) per group: 2, 4, 8, 12
+// the split classes in the order their groups and boundaries are numbered, widest first (k = 0 .. 3)
+static const int kNumExtSplit = 4;
+MPA_DPP_HD int ext_split_at(int k) { return k == 0 ? (int)X_SPLIT12 : k == 1 ? (int)X_SPLIT8 : k == 2 ? (int)X_SPLIT4 : (int)X_SPLIT2; }
 // the packed sweeps of the checkpointed classes T_LITE16 .. T_LITE128 (T_LITE_W4 has its own launch)
 MPA_DPP_HD int dp_lite_unit_kind(int cls) { return U_LITE16 + (cls - T_LITE16); }
 MPA_DPP_HD int64_t dp_lite_unit_ns(int cls) { return cls == T_LITE128 ? NS_LITE128 : NS_LITE; }
@@ -183,11 +202,15 @@ enum { DPP_S_REC = 0, DPP_S_PROF, DPP_S_PREP, DPP_S_CIG, DPP_S_BND, DPP_S_TB, DP
 enum { DPP_ST_CELLS_EXT = 0, DPP_ST_BYTES_EXT, DPP_ST_CELLS_GLOB, DPP_ST_BYTES_GLOB, DPP_ST_N_CKPT, DPP_ST_CELLS_CKPT, DPP_ST_N_WIDE, DPP_ST_CELLS_WIDE, DPP_ST_CELLS_OWN, DPP_NST };
 typedef DpVec<DPP_NSUM> DpSums;
 
-// wave descriptor classes in the order of ExtWave[]: X_16 .. X_SPLIT4, X_128, T_LITE16 .. T_LITE128, T_LITE_W4
-#define MPA_DPPLAN_EW 13
-MPA_DPP_HD int dp_ew_group(int e) { return e < 7 ? dp_key_group(true, e) : e == 7 ? dp_key_group(true, X_128) : dp_key_group(false, T_LITE16 + (e - 8)); }
-MPA_DPP_HD int dp_ew_of_group(int g) { return g < 7 ? g : g == X_128 ? 7 : g >= 16 + T_LITE16 && g <= 16 + T_LITE_W4 ? 8 + (g - 16 - T_LITE16) : -1; }   // -1: no ExtWave class
-MPA_DPP_HD int dp_ew_per(int e) { return e < 8 ? ext_calls_per_wave(e < 7 ? e : (int)X_128) : lite_calls_per_wave(T_LITE16 + (e - 8)); }
+// wave descriptor classes in the order of ExtWave[]: X_16 .. X_SPLIT4, X_SPLIT8, X_SPLIT12, X_128, T_LITE16 .. T_LITE128, T_LITE_W4
+// (the wide groups X_W2 .. X_SPLIT12 are neighbours: their row keys are indexed by descriptor, from the first X_W2 group)
+#define MPA_DPPLAN_EW 15
+enum { DPP_EW_SPLIT8 = 7, DPP_EW_SPLIT12 = 8, DPP_EW_128 = 9, DPP_EW_LITE = 10 };
+MPA_DPP_HD int dp_ew_ext_class(int e) { return e < 7 ? e : e == DPP_EW_SPLIT8 ? (int)X_SPLIT8 : e == DPP_EW_SPLIT12 ? (int)X_SPLIT12 : (int)X_128; }   // e < DPP_EW_LITE
+MPA_DPP_HD int dp_ew_of_ext_class(int cls) { return cls < 7 ? cls : cls == X_SPLIT8 ? (int)DPP_EW_SPLIT8 : cls == X_SPLIT12 ? (int)DPP_EW_SPLIT12 : cls == X_128 ? (int)DPP_EW_128 : -1; }
+MPA_DPP_HD int dp_ew_group(int e) { return e < DPP_EW_LITE ? dp_key_group(true, dp_ew_ext_class(e)) : dp_key_group(false, T_LITE16 + (e - DPP_EW_LITE)); }
+MPA_DPP_HD int dp_ew_of_group(int g) { return g < 16 ? dp_ew_of_ext_class(g) : g >= 16 + T_LITE16 && g <= 16 + T_LITE_W4 ? DPP_EW_LITE + (g - 16 - T_LITE16) : -1; }   // -1: no ExtWave class
+MPA_DPP_HD int dp_ew_per(int e) { return e < DPP_EW_LITE ? ext_calls_per_wave(dp_ew_ext_class(e)) : lite_calls_per_wave(T_LITE16 + (e - DPP_EW_LITE)); }
 
 // one run of units that are built alike (unit_costs() adds them in this order)
 struct DpUnitSeg {
@@ -197,7 +220,7 @@ struct DpUnitSeg {
 	int32_t cpw;                                // calls per descriptor
 	int64_t ns, pos0, ufirst;                   // nanoseconds per row; sorted position of the first descriptor's first call; first unit
 };
-#define MPA_DPPLAN_SEGS 20
+#define MPA_DPPLAN_SEGS 24
 
 // What the planner leaves besides the pools: counts, totals, ranges.  All int64 so that the block is one array for the download.
 struct DpDevHead {
@@ -227,8 +250,9 @@ MPA_DPP_HD bool dp_unit_costs_fit(int64_t max_nl, int64_t max_al)
 	const int64_t blocks = (max_al + 7 + 63) / 64 + 1;
 	return max_nl < ((int64_t)1 << 31) && max_nl * NS_GLOB_WIDE * blocks < ((int64_t)1 << MPA_DPPLAN_COST_BITS);
 }
-// units a round of n calls can have at most (the executor's staging section has the same bound: 4 n_ew + n_glob + 64)
-MPA_DPP_HD int64_t dp_units_bound(int64_t n) { return 4 * n + 64; }
+// units a round of n calls can have at most (the executor's staging section has the same bound: 4 n_ew + n_glob + 64, and with
+// split_wide 8 more for every X_SPLIT12 group, 4 more for every X_SPLIT8 group)
+MPA_DPP_HD int64_t dp_units_bound(int64_t n, bool split_wide = false) { return (split_wide ? 12 : 4) * n + 64; }
 
 // everything the stages read and write
 struct DpDevPlan {
@@ -350,15 +374,19 @@ template<typename Team> MPA_DPP_HD void dpp_mid(const Team &tm, const DpDevPlan 
 		for (int e = 0; e < MPA_DPPLAN_EW; ++e) {
 			const int g = dp_ew_group(e);
 			H.ew_first[e] = at, H.ew_cnt[e] = dp_blocks(H.run_cnt[g], dp_ew_per(e)), at += H.ew_cnt[e];
-			if (e >= X_W2 && e <= X_SPLIT4 && H.ew_cnt[e]) {
+			if (e < DPP_EW_LITE && ext_is_wide_group(dp_ew_ext_class(e)) && H.ew_cnt[e]) {
 				const int64_t nl = dpp_nl_at(D, H.run_first[g]);
 				H.key_stride = H.key_stride > nl ? H.key_stride : nl, H.n_wide_groups += H.ew_cnt[e];
 			}
 		}
 		H.n_ewaves = at;
 		H.key_stride = (H.key_stride + 64) & ~(int64_t)63;
-		// split classes: boundary granules (3 boundaries per 1024-column group, 1 per 512-column group)
-		H.n_split = H.ew_cnt[X_SPLIT2] + H.ew_cnt[X_SPLIT4], H.n_bound = 3 * H.ew_cnt[X_SPLIT4] + H.ew_cnt[X_SPLIT2];
+		// split classes: boundary granules (n_blk - 1 boundaries per group: 11, 7, 3, 1)
+		H.n_split = H.n_bound = 0;
+		for (int k = 0; k < kNumExtSplit; ++k) {
+			const int64_t cnt = H.ew_cnt[dp_ew_of_ext_class(ext_split_at(k))];
+			H.n_split += cnt, H.n_bound += cnt * (dp_ext_unit_blocks(ext_split_at(k)) - 1);
+		}
 		// the waves of the plain sweep's one chunk, by class
 		at = 0;
 		for (int c = T_16; c <= T_MB; ++c) H.gw_first[c] = at, H.gw_cnt[c] = dp_blocks(H.run_cnt[16 + c], tb_calls_per_wave(c)), at += H.gw_cnt[c];
@@ -378,16 +406,18 @@ template<typename Team> MPA_DPP_HD void dpp_mid(const Team &tm, const DpDevPlan 
 			if (!(cls == X_32 && D.kn.antidiag)) ext_seg(cls, dp_ext_unit_kind(cls, pool), dp_ext_unit_per(cls, pool), dp_ext_unit_ns(cls));
 		ext_seg(X_W2, dp_ext_unit_kind(X_W2, pool), dp_ext_unit_per(X_W2, pool), dp_ext_unit_ns(X_W2));
 		ext_seg(X_W4, dp_ext_unit_kind(X_W4, pool), dp_ext_unit_per(X_W4, pool), dp_ext_unit_ns(X_W4));
-		const int32_t n4 = (int32_t)H.ew_cnt[X_SPLIT4];               // split groups and their boundaries are numbered 1024-column groups first
-		for (int cls = X_SPLIT4; cls >= X_SPLIT2; --cls) {
-			if (!H.ew_cnt[cls]) continue;
-			ext_seg(cls, dp_ext_unit_kind(cls, pool), 1, dp_ext_unit_ns(cls));
+		int32_t sgroup = 0, xg = 0;                                   // split groups and their boundaries are numbered widest class first
+		for (int k = 0; k < kNumExtSplit; ++k) {
+			const int cls = ext_split_at(k), e = dp_ew_of_ext_class(cls);
+			if (!H.ew_cnt[e]) continue;
+			ext_seg(e, dp_ext_unit_kind(cls, pool), 1, dp_ext_unit_ns(cls));
 			DpUnitSeg &S = H.seg[ns - 1];
-			S.n_blk = dp_ext_unit_blocks(cls), S.sgroup0 = cls == X_SPLIT4 ? 0 : n4, S.xg0 = cls == X_SPLIT4 ? 0 : 3 * n4, S.xg_step = cls == X_SPLIT4 ? 3 : 1;
+			S.n_blk = dp_ext_unit_blocks(cls), S.sgroup0 = sgroup, S.xg0 = xg, S.xg_step = S.n_blk - 1;
 			u += (int64_t)S.cnt * (S.n_blk - 1);
+			sgroup += S.cnt, xg += S.cnt * S.xg_step;
 		}
-		ext_seg(7, dp_ext_unit_kind(X_128, pool), dp_ext_unit_per(X_128, pool), dp_ext_unit_ns(X_128));
-		for (int c = 0; c < 4; ++c) ext_seg(8 + c, dp_lite_unit_kind(T_LITE16 + c), dp_per_narrow(pool), dp_lite_unit_ns(T_LITE16 + c));
+		ext_seg(DPP_EW_128, dp_ext_unit_kind(X_128, pool), dp_ext_unit_per(X_128, pool), dp_ext_unit_ns(X_128));
+		for (int c = 0; c < 4; ++c) ext_seg(DPP_EW_LITE + c, dp_lite_unit_kind(T_LITE16 + c), dp_per_narrow(pool), dp_lite_unit_ns(T_LITE16 + c));
 		if (H.n_reg_glob > 0 && !dp_wide_ge(D.opt))                  // the first chunk's calls ride in the round's one launch
 			for (int cls = T_16; cls <= T_MB; ++cls) {
 				if (!dp_glob_in_round(cls) || !H.gw_cnt[cls]) continue;
@@ -400,7 +430,7 @@ template<typename Team> MPA_DPP_HD void dpp_mid(const Team &tm, const DpDevPlan 
 	}
 	tm.sync();
 	// checkpointed descriptors: a scan over their bit words and checkpoints, in descriptor order
-	const int64_t d0 = H.ew_first[8], nd = H.n_ewaves - d0;
+	const int64_t d0 = H.ew_first[DPP_EW_LITE], nd = H.n_ewaves - d0;
 	DpVec<2> run;
 	run.v[0] = run.v[1] = 0;
 	for (int64_t k0 = 0; k0 < nd; k0 += Team::W) {
@@ -408,9 +438,9 @@ template<typename Team> MPA_DPP_HD void dpp_mid(const Team &tm, const DpDevPlan 
 		DpVec<2> s, total;
 		s.v[0] = s.v[1] = 0;
 		if (d < H.n_ewaves) {
-			int e = 8;
+			int e = DPP_EW_LITE;
 			while (e + 1 < MPA_DPPLAN_EW && d >= H.ew_first[e + 1]) ++e;
-			const int cls = T_LITE16 + (e - 8);
+			const int cls = T_LITE16 + (e - DPP_EW_LITE);
 			const int32_t max_nl = dpp_nl_at(D, H.run_first[16 + cls] + (d - H.ew_first[e]) * dp_ew_per(e));
 			s.v[0] = lite_bits_dwords(cls, max_nl), s.v[1] = lite_ckpt_dwords(cls, max_nl);
 		}
@@ -472,10 +502,10 @@ template<typename Team> MPA_DPP_HD void dpp_layout(const Team &tm, const DpDevPl
 		w.task[slot] = id;
 		if (slot == 0) {
 			w.max_nl = t.nl, w.pad_[0] = w.pad_[1] = w.pad_[2] = 0, w.rec_base = t.rec_off;     // (sorted: the first call of a wave has the smallest offset)
-			if (e < 8) w.lite_off = w.ck_off = 0;
+			if (e < DPP_EW_LITE) w.lite_off = w.ck_off = 0;
 			for (int j = (int)(cnt - rel < per ? cnt - rel : per); j < 8; ++j) w.task[j] = -1;
 		}
-		if (e >= 8) t.flag |= slot << MPA_LITE_SLOT_SHIFT, t.tb_off = w.lite_off, t.bnd_off = w.ck_off;
+		if (e >= DPP_EW_LITE) t.flag |= slot << MPA_LITE_SLOT_SHIFT, t.tb_off = w.lite_off, t.bnd_off = w.ck_off;
 	}
 }
 

@@ -1,10 +1,49 @@
 """Kernel-time microbenchmark of the DP classes: n_tasks right-extension calls (flag 4) or traceback calls (flag 1) of `al` columns x
 `nl` rows (results are not checked here).  python tools/time_wide.py al nl n_tasks [flag] [antidiag]
-antidiag = 1: the 32-column extension class on the anti-diagonal prototype (dp_antidiag.hip) instead of the row sweep."""
+antidiag = 1: the 32-column extension class on the anti-diagonal prototype (dp_antidiag.hip) instead of the row sweep.
+python tools/time_wide.py split_wide [repeats]: the table of the 1 025..3 072-column extension classes (MPA_DP_SPLIT_WIDE) -- a pair of
+calls of 1 100, 1 500, 2 000 and 2 600 columns x 20 000 rows, first with the knob off (k_ext_huge, the one-wave int32 sweep), then with
+the knob on (X_SPLIT8 / X_SPLIT12), the pair of legs `repeats` times (default 3); 1 000 columns (X_SPLIT4 in both legs) for comparison."""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, ROOT)
 import numpy as np, miniprot_amd as mpa
+
+
+def split_wide_table(repeats, nl=20000, n=2):
+    rng = np.random.default_rng(1)
+    g = rng.integers(0, 4, nl * n + 1000).astype(np.uint8)
+    idx = mpa.Index.from_nt4([g], ["c"])
+    ctxs = {}
+    for knob in (0, 1):                                # the knob is read when a context is created
+        os.environ["MPA_DP_SPLIT_WIDE"] = str(knob)
+        ctxs[knob] = mpa.Context(0)
+        idx.to_device(ctxs[knob])
+    dp = mpa.dpopt_from(mpa.default_mapopt())
+    dp.xdrop = 32000                                   # never stop: time all rows
+    print("# ns per row of a pair of right-extension calls, %d rows each; knob off: ms_ext of the k_ext_huge + k_ext_replay launch, knob on: the round kernel" % nl)
+    print("%6s %4s %8s %14s %14s %8s" % ("al", "rep", "classes", "off ns/row", "on ns/row", "off/on"))
+    for al in (1000, 1100, 1500, 2000, 2600):
+        aa = bytes(rng.choice(list(b"ACDEFGHIKLMNPQRSTVWY"), al * n).tolist())
+        q = mpa.Queries([aa[i * al:(i + 1) * al] for i in range(n)])
+        tasks = np.zeros(n, mpa.DP_TASK)
+        for i in range(n):
+            tasks[i]["nt_off"] = i * nl; tasks[i]["nl"] = nl; tasks[i]["qid"] = i; tasks[i]["al"] = al; tasks[i]["flag"] = 4; tasks[i]["io"] = 29
+        for rep in range(repeats + 1):                 # (the first pair of legs warms both contexts up and is not printed)
+            ns, cls = {}, {}
+            for knob in (0, 1):
+                mpa.dp_run(ctxs[knob], idx, dp, q, tasks)
+                st = ctxs[knob].dp_stats()
+                ns[knob] = st["ms_ext"] * 1e6 / nl
+                c = mpa.dbg_dp_last_classes(ctxs[knob])
+                cls[knob] = "+".join("%d:%d" % (k, v) for k, v in enumerate(c) if v)
+            if rep:
+                print("%6d %4d %8s %14.1f %14.1f %8.2f" % (al, rep, cls[0] + "|" + cls[1], ns[0], ns[1], ns[0] / ns[1]))
+
+
+if sys.argv[1] == "split_wide":
+    split_wide_table(int(sys.argv[2]) if len(sys.argv) > 2 else 3)
+    sys.exit(0)
 al, nl, n = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])
 flag = int(sys.argv[4]) if len(sys.argv) > 4 else 4      # 4 = right extension (score only), 1 = global with traceback
 rng = np.random.default_rng(1)
