@@ -135,9 +135,29 @@ BOUND_CASES = [
 ]
 
 
+# The same bound for the 2 048- / 3 072-column extension classes (MPA_DP_SPLIT_WIDE, tests/splitwide.py): (al, parameters, the parameter
+# to raise by one, cap on the matrix entries or None).  With max_mat 11, or the cap where one is given (splitwide.capped_matrix), the
+# larger sum is exactly 32000.  The score sum decides the first six, go + ncol * ge the others.  al 1 032..2 048 is X_SPLIT8's, beyond it
+# X_SPLIT12's; with the uncapped matrix and ge = 1 the guard ends at 2 665 residues, so the last column block (2 816..3 071) is live in
+# the cases with a cap only: 2 904 reaches into it, 3 072 fills all twelve.  (al * 11 + ncol * ge = 32000 - end_bonus has no solution
+# with end_bonus <= 1000 at al = 2 048 or 3 072: 2 000, 2 128 and 2 904 stand in.)
+WIDE_BOUND_CASES = [
+    (1032, dict(ge=20, end_bonus=8), "end_bonus", None),
+    (1600, dict(ge=9, end_bonus=0), "end_bonus", None),
+    (2000, dict(ge=5, end_bonus=0), "end_bonus", None),
+    (2128, dict(ge=4, end_bonus=80), "end_bonus", None),
+    (2664, dict(ge=1, end_bonus=32), "end_bonus", None),
+    (2904, dict(ge=1, end_bonus=56), "end_bonus", 10),
+    (1032, dict(go=30968, ge=1), "go", None),
+    (2048, dict(go=29952, ge=1), "go", None),
+    (2600, dict(go=29400, ge=1), "go", None),
+    (3072, dict(go=28928, ge=1), "go", 4),
+]
+
+
 def bound_params(case, over):
-    """keyword arguments of BOUND_CASES[k] with the decisive sum at 32000 + over"""
-    al, kw, key = case
+    """keyword arguments of BOUND_CASES[k] / WIDE_BOUND_CASES[k] with the decisive sum at 32000 + over"""
+    al, kw, key = case[:3]
     kw = dict(kw)
     kw[key] += over
     return kw

@@ -8,10 +8,10 @@ from dpgen import make_task
 COMP = np.array([3, 2, 1, 0, 4], dtype=np.uint8)
 
 
-def build_workload(pairs, rng, modes=("cigar", "left", "right"), io=29, io_alt=19, n_ctg=3):
+def build_workload(pairs, rng, modes=("cigar", "left", "right"), io=29, io_alt=19, n_ctg=3, pair_modes=None):
     """pairs: list of (nt bytes, aa bytes).  Every pair is placed on a random contig and strand; for each
-    requested mode one task is emitted.  Returns (contigs, queries, tasks, meta) where meta[k] =
-    (pair index, flag, io)."""
+    requested mode one task is emitted (pair_modes: the modes of each pair, instead of `modes` for all).
+    Returns (contigs, queries, tasks, meta) where meta[k] = (pair index, flag, io)."""
     ctgs = [[] for _ in range(n_ctg)]
     pos = [0] * n_ctg
     place = []
@@ -33,7 +33,7 @@ def build_workload(pairs, rng, modes=("cigar", "left", "right"), io=29, io_alt=1
     flags = {"cigar": mpa.F_CIGAR, "left": mpa.F_EXT_LEFT, "right": mpa.F_EXT_RIGHT}
     for k, ((nt, aa), (c, rev, p, nl)) in enumerate(zip(pairs, place)):
         nt_off = lens[c] - (p + nl) if rev else p
-        for m in modes:
+        for m in (modes if pair_modes is None else pair_modes[k]):
             fl = flags[m]
             this_io = io if (fl == mpa.F_CIGAR or rng.random() < 0.7) else io_alt
             tasks.append((nt_off, c << 1 | rev, nl, k, 0, len(aa), fl, this_io, len(tasks)))

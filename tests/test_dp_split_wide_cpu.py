@@ -2,7 +2,9 @@
 pair of calls) by the host planner (mpa_dbg_dp_plan_wide) and by the model of the device planner (mpa_dbg_dp_plan_device_wide, ctx None),
 what the plan promises the executor (groups, boundaries, units, bytes of the granule pool), and the knob's absence: with split_wide = 0 the
 plan is mpa_dbg_dp_plan's, byte for byte.  A stand-alone program (tests/dpsplit_check.cpp, compiled here with AddressSanitizer and UBSan)
-runs random tables through both planners with every pool at exactly the executor's bound."""
+runs random tables through both planners with every pool at exactly the executor's bound.  And the batches of
+tests/test_dp_split_wide_range_gpu.py (capped matrix, penalty points, int16 bound): their sums, their routing by both planners, the
+classes their tests expect, the teeth of the class assertion, and oracle == reference on every call."""
 import os
 import subprocess
 import numpy as np
@@ -11,6 +13,8 @@ import miniprot_amd as mpa
 import dpplan
 import refbind
 import splitwide as sw
+from dpgen import WIDE_BOUND_CASES, PENALTY_POINTS, bound_params
+from dputil import dpopt_from_params
 from dpplan import EXT, GLOB
 
 
@@ -133,6 +137,169 @@ def test_device_planner_model_still_declines_the_one_wave_class():
     bad = sw.table(r, [(EXT, 1100, 300), (EXT, g + 1, 500), (EXT, 50, 90)])
     code, why = sw.device_plan(None, bad)
     assert code == mpa.DP_PLAN_DECLINED and "one-wave int32" in why
+
+
+# ---- the classes over the penalty range: the case lists and tables of tests/test_dp_split_wide_range_gpu.py, without a device
+BOUND_IDS = ["al%d-%s" % (c[0], c[2]) for c in WIDE_BOUND_CASES]
+TABLE_CLASS = {1032: sw.X_SPLIT8, 1600: sw.X_SPLIT8, 2000: sw.X_SPLIT8, 2048: sw.X_SPLIT8, 2128: sw.X_SPLIT12, 2600: sw.X_SPLIT12, 2664: sw.X_SPLIT12,
+               2904: sw.X_SPLIT12, 3072: sw.X_SPLIT12}                           # the class each bound case names at 32 000
+
+
+def test_capped_matrix():
+    full = refbind.mapping_matrix(23)
+    for cap in (4, 10):
+        m = sw.capped_matrix(cap)
+        assert m.dtype == np.int8 and m.shape == (22, 22) and int(m.max()) == cap
+        assert np.array_equal(m[full <= cap], full[full <= cap]) and np.all(m[full > cap] == cap)
+        assert list(dpplan.dpopt(**sw.opt_overrides(sw.wide_params(cap=cap))).mat) == list(dpplan.dpopt(**sw.low_matrix(cap)).mat)
+    assert int(full.max()) == 11 and np.array_equal(sw.capped_matrix(11), full)
+
+
+@pytest.mark.parametrize("over", [0, 1], ids=["at32000", "at32001"])
+@pytest.mark.parametrize("case", WIDE_BOUND_CASES, ids=BOUND_IDS)
+def test_wide_bound_sums_and_routing(case, over):
+    """the decisive sum of every dpgen.WIDE_BOUND_CASES entry is 32 000, and 32 001 with its key raised; both planners put the call in
+    the class the case names at 32 000 and on the one-wave sweep at 32 001 (the device planner's model by declining the table); the
+    capped cases need their cap: under the full matrix they are on the one-wave sweep on both sides"""
+    al, _, key, cap = case
+    P = sw.wide_params(bound_params(case, over), cap)
+    ncol = (al + 7) // 8 * 8
+    sums = (al * int(P.mat.max()) + ncol * P.ge + max(0, P.end_bonus), P.go + ncol * P.ge)
+    assert max(sums) == 32000 + over and (sums[0] > sums[1]) == (key == "end_bonus")
+    assert int(P.mat.max()) == (11 if cap is None else cap)
+    over_opt = sw.opt_overrides(P)
+    o = dpplan.dpopt(**over_opt)
+    assert bytes(o.mat) == bytes(dpopt_from_params(P).mat) and (o.go, o.ge, o.end_bonus) == (P.go, P.ge, P.end_bonus)      # what mpa.dp_run is given
+    assert sw.may_saturate(al, o) == (over == 1)
+    want = TABLE_CLASS[al] if over == 0 else sw.X_HUGE
+    assert sw.expected_class(al, o, sw.KNOBS) == want
+    r = np.random.default_rng(9330 + al)
+    tasks = sw.table(r, [(EXT, al, 900), (EXT, 40, 100), (GLOB, 30, 500)])
+    p = sw.plan(tasks, over_opt)
+    assert isinstance(p, sw.WidePlan), p
+    assert ext_classes(p)[al] == {want}
+    d = sw.device_plan(None, tasks, over_opt)
+    if over == 0:
+        assert isinstance(d, sw.WidePlan) and d.buf == p.buf
+    else:
+        assert d[0] == mpa.DP_PLAN_DECLINED and "one-wave int32" in d[1]
+    if cap is not None:
+        full = sw.plan(tasks, sw.opt_overrides(sw.wide_params(bound_params(case, over))))
+        assert ext_classes(full)[al] == {sw.X_HUGE}
+
+
+def test_wide_penalty_points_are_selected_by_the_guard():
+    pts = sw.wide_penalty_points()
+    assert [kw for kw, _ in pts] == [kw for kw in PENALTY_POINTS if sw.guard_limit(dpopt_from_params(sw.wide_params(kw))) > 1024]
+    lim = {repr(kw): l for kw, l in pts}
+    assert len(pts) == 16 and lim[repr(dict(ge=4))] == 2131 and lim[repr(dict(end_bonus=100))] == 2657 and lim[repr(dict(end_bonus=1000))] == 2583
+    assert sorted(set(lim.values())) == [2131, 2583, 2657, 2665]
+    assert all(any(k in kw for kw, _ in pts) for k in ("ge", "go", "io", "xdrop", "end_bonus", "fs", "sp"))
+
+
+def plan_counts(p):
+    """extension calls of X_SPLIT8, X_SPLIT12 and X_HUGE in a plan"""
+    T = p.sec["tasks"]
+    ext = (T["flag"] & (mpa.F_EXT_LEFT | mpa.F_EXT_RIGHT)) != 0
+    return {c: int(np.sum(ext & (T["cls"] == c))) for c in (sw.X_SPLIT8, sw.X_SPLIT12, sw.X_HUGE) if np.any(ext & (T["cls"] == c))}
+
+
+def check_table(tab, want):
+    """the host planner on the very table the GPU test runs: the calls the test expects per class, with the knob and without it; and
+    the assertion helper of the GPU tests has teeth -- the class vector of a context without the knob fails it, and so does one call
+    that took the one-wave sweep"""
+    on, off = tab.plan(1), tab.plan(0)
+    assert isinstance(on, sw.WidePlan) and isinstance(off, sw.WidePlan), (on, off)
+    assert plan_counts(on) == {c: n for c, n in want.items() if n} and plan_counts(off) == {sw.X_HUGE: tab.n_wide()}
+    assert want.get(sw.X_SPLIT8, 0) + want.get(sw.X_SPLIT12, 0) + want.get(sw.X_HUGE, 0) == tab.n_wide()
+    good = tab.class_counts(1)
+    sw.check_classes(good, tab, 1, want)
+    sw.check_classes(tab.class_counts(0), tab, 0, {sw.X_HUGE: tab.n_wide()})
+    if want.get(sw.X_SPLIT8, 0) + want.get(sw.X_SPLIT12, 0):
+        with pytest.raises(AssertionError, match="swept"):
+            sw.check_classes(tab.class_counts(0), tab, 1, want)                  # the knob-off context in the knob-on one's place
+        c = sw.X_SPLIT8 if want.get(sw.X_SPLIT8, 0) else sw.X_SPLIT12
+        one = list(good)
+        one[c] -= 1
+        one[sw.X_HUGE] += 1
+        with pytest.raises(AssertionError, match="swept"):
+            sw.check_classes(one, tab, 1, want)
+        with pytest.raises(AssertionError, match="rules of the classes"):
+            sw.check_classes(good, tab, 1, {sw.X_HUGE: tab.n_wide()})            # a test that expects the wrong classes
+    return on
+
+
+def ora_equals_ref(tab):
+    """the expected values are the reference's own, not only the restatement's"""
+    e, r = tab.expect("oracle"), tab.expect("reference")
+    assert len(e) == len(tab.tasks)
+    bad = [(k, tab.meta[k], e[k][:3], r[k][:3]) for k in range(len(e)) if e[k] != r[k]]
+    assert not bad, bad[:5]
+
+
+@pytest.mark.parametrize("name", ["twelve_blocks", "group_shapes", "short_windows", "xdrop_stops"])
+def test_range_tables(oracle_built, name):
+    tab, want = sw.range_tables()[name]
+    p = check_table(tab, want)
+    T, W = p.sec["tasks"], p.sec["ewaves"]
+    assert p.s8[1] == 0
+    groups = [[(int(T[i]["al"]), int(T[i]["nl"])) for i in W[d]["task"][:2] if i >= 0] for d in range(p.s12[0], p.s12[0] + p.s12[1])]
+    if name == "twelve_blocks":
+        assert sorted(al for g in groups for al, _ in g) == sorted(2 * sw.TWELVE_BLOCK_ALS) and all(len(g) == 2 for g in groups)
+        assert all(8000 < nl < 10600 for g in groups for _, nl in g)
+    if name == "group_shapes":                                                   # (3 072, 2 049) share a group, the second 3 072 call has an empty half
+        assert [[al for al, _ in g] for g in groups] == [[3072, 2049], [3072]] and groups[1][0][1] == 5000 and p.header["n_huge"] == 1
+    if name == "short_windows":
+        assert sorted(nl for g in groups for al, nl in g if al == 3072) == sorted(2 * sw.SHORT_ROWS_3072)
+    if name == "xdrop_stops":                                                    # the x-drop does stop: far from the end of the protein, on both sides
+        stop = {(len(tab.pairs[k][0]), fl): e[1] for (k, fl, _), e in zip(tab.meta, tab.expect("oracle"))}
+        assert all(n < 2900 for n in stop.values()) and sorted(stop.values())[-2] > 900, stop
+
+
+@pytest.mark.parametrize("point", sw.wide_penalty_points(), ids=lambda p: ",".join("%s=%s" % x for x in p[0].items()))
+def test_penalty_point_tables(oracle_built, point):
+    kw, lim = point
+    tab, want = sw.penalty_table(kw, lim)
+    als = sorted(set(a for a in tab.ext_als() if a > 1024))
+    assert als == sorted({1032, min(lim, 2048), lim, lim + 1}) and want[sw.X_HUGE] == 2
+    assert not sw.may_saturate(lim, tab.opt) and sw.may_saturate(lim + 1, tab.opt)
+    assert max(a for a in tab.ext_als() if a <= 1024) == 1000 and sum(fl == mpa.F_CIGAR for _, fl, _ in tab.meta) == len(sw.MIXED_ALS)
+    assert len({io for _, _, io in tab.meta}) == 2                               # io and io_alt, as build_workload deals them
+    p = check_table(tab, want)
+    assert p.header["n_huge"] == 2
+
+
+@pytest.mark.parametrize("over", [0, 1], ids=["at32000", "at32001"])
+@pytest.mark.parametrize("case", WIDE_BOUND_CASES, ids=BOUND_IDS)
+def test_bound_tables(oracle_built, case, over):
+    """the GPU test's batch of a bound case: the calls at al in the case's class at 32 000 and on the one-wave sweep at 32 001, the
+    hot pairs at the highest score the matrix gives, oracle == reference on every call"""
+    al, cap = case[0], case[3]
+    tab, want = sw.bound_table(case, over)
+    assert sorted(set(tab.ext_als())) == [al - 8, al, al + 8] and tab.ext_als().count(al) == 4
+    at = want.get(TABLE_CLASS[al], 0) if over == 0 else want.get(sw.X_HUGE, 0)
+    assert at >= 4 and (over == 0 or want.get(TABLE_CLASS[al], 0) <= 2)
+    if case[2] == "end_bonus" or al == 3072:
+        assert sw.expected_class(al + 8, tab.opt, sw.KNOBS) == sw.X_HUGE
+    check_table(tab, want)
+    hot = [e for (k, fl, _), e in zip(tab.meta, tab.expect("oracle")) if tab.pairs[k][1] == b"W" * al]
+    assert len(hot) == 2 and all(e[:3] == (3 * al, al, al * int(tab.P.mat.max()) + tab.P.end_bonus) for e in hot), hot
+
+
+def all_tables():
+    """(id, maker) of every table the GPU tests run"""
+    out = [("range-" + name, lambda name=name: sw.range_tables()[name][0]) for name in ("twelve_blocks", "group_shapes", "short_windows", "xdrop_stops")]
+    out += [("point-" + ",".join("%s=%s" % x for x in kw.items()), lambda kw=kw, lim=lim: sw.penalty_table(kw, lim)[0]) for kw, lim in sw.wide_penalty_points()]
+    out += [("bound-al%d-%s-%d" % (c[0], c[2], 32000 + over), lambda c=c, over=over: sw.bound_table(c, over)[0]) for c in WIDE_BOUND_CASES for over in (0, 1)]
+    return out
+
+
+@pytest.mark.skipif(not refbind.have_ref(), reason="the reference is not built")
+@pytest.mark.parametrize("make", [m for _, m in all_tables()], ids=[i for i, _ in all_tables()])
+def test_expected_values_are_the_references(oracle_built, make):
+    """oracle == reference (ns_global_gs16b) on every call of every table of the GPU tests: random and hot pairs on both sides of every
+    bound, full 3 072-column calls under the capped matrix, the penalty points"""
+    ora_equals_ref(make())
 
 
 def test_hooks_are_in_the_hooks_library():
