@@ -53,6 +53,14 @@ int64_t mpa_dbg_dp_plan_device_wide(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int3
                                     const mpa_dp_task_t *tasks, const int64_t *knobs, void *buf, int64_t cap);
 int mpa_dbg_dp_last_classes(const mpa_ctx_t *ctx, int64_t ext_calls[16]);
 
+/* MPA_DP_HUGE_WG (X_HUGE extension calls swept by k_ext_huge_wg, one wave per 64-column block, W waves in one
+ * workgroup).  mpa_dbg_dp_last_huge: of the context's last mpa_dp_run (of its repeat, when a hand-off timed out) out[0] the X_HUGE calls
+ * the one-wave kernel swept, out[1] those the workgroup kernel swept, out[2] the column blocks and out[3] the passes of the latter.
+ * mpa_dbg_dp_huge_wg_info: the schedule's constants (miniprot_amd/csrc/ext_huge_wg_core.h) -- out[0] W waves per workgroup, out[1] R rows
+ * per chunk, out[2] MIN_BLOCKS, the fewest column blocks at which a call takes the workgroup kernel. */
+int mpa_dbg_dp_last_huge(const mpa_ctx_t *ctx, int64_t out[4]);
+void mpa_dbg_dp_huge_wg_info(int32_t out[3]);
+
 /* A DP round from device-resident tasks (MPA_GPU_ROUND2): the arguments of mpa_dp_run.  On a context the hook
  * puts the tasks into a device pool, has their bounds reduced there (k_task_bounds), plans the round from the tasks in place, runs it
  * with the result records and the dense CIGAR pool assembled on the device in front of the round's one wait, and only then fetches the

@@ -600,7 +600,30 @@ def dbg_dp_last_classes(ctx):
     return [int(x) for x in out]
 
 
-ROUND2_DECLINED = 1   # MPA_DBG_ROUND2_DECLINED (include/mpamd_dbg.h)
+def dbg_dp_last_huge(ctx):
+    """mpa_dbg_dp_last_huge(): of the context's last dp_run(), (X_HUGE calls swept by the one-wave kernel, X_HUGE calls swept by the
+    workgroup kernel of MPA_DP_HUGE_WG, column blocks of the latter, passes of the latter)."""
+    import numpy as np
+    out = np.zeros(4, np.int64)
+    f = dbg_lib().mpa_dbg_dp_last_huge
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_void_p]
+    _check(f(ctx.h, out.ctypes.data))
+    return tuple(int(x) for x in out)
+
+
+def dbg_dp_huge_wg_info():
+    """mpa_dbg_dp_huge_wg_info(): (W waves per workgroup, R rows per chunk, MIN_BLOCKS) of the workgroup kernel's schedule."""
+    import numpy as np
+    out = np.zeros(3, np.int32)
+    f = dbg_lib().mpa_dbg_dp_huge_wg_info
+    f.restype = None
+    f.argtypes = [C.c_void_p]
+    f(out.ctypes.data)
+    return tuple(int(x) for x in out)
+
+
+ROUND2_DECLINED = 1  # MPA_DBG_ROUND2_DECLINED (include/mpamd_dbg.h)
 ROUND2_REC = ("plan_waits", "round_waits", "bytes_up", "task_bytes_up", "bytes_down", "pool_bytes_down", "pool_bytes_fetched", "prep_bound", "max_nl", "max_al", "n_pool", "reserved")
 
 

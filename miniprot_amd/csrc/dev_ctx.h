@@ -131,6 +131,8 @@ struct mpa_ctx_s {
 	int side_off = 0;                         // first side stream a round uses (lets the DP lanes of a stream of batches sit on different hardware queues)
 	hipStream_t seed_stream = nullptr;        // high-priority stream of the seeding kernels: short, and must not queue behind DP tails
 	int split_wide = 0;                       // 1025..3072-column extension calls on X_SPLIT8 / X_SPLIT12 instead of k_ext_huge (MPA_DP_SPLIT_WIDE; 0, the default until it has been measured)
+	int huge_wg = 0;                          // X_HUGE calls of hwg::MIN_BLOCKS column blocks or more on k_ext_huge_wg, one wave per block (MPA_DP_HUGE_WG; 0, the default until it has been measured)
+	int64_t last_huge[4] = { 0, 0, 0, 0 };    // the last mpa_dp_run's X_HUGE calls on the one-wave kernel, on the workgroup kernel, the latter's column blocks and passes (mpa_dbg_dp_last_huge)
 	int64_t last_ext_calls[16] = { 0 };       // extension calls per DpClass in the last mpa_dp_run (mpa_dbg_dp_last_classes)
 	bool no_split = false;                    // this mpa_dp_run() repeats a round whose workgroup hand-off timed out: 512/1024-column calls go to k_ext_huge
 	int64_t handoff_retries = 0;              // how often that has happened on this context (mpa_dp_handoff_retries)

@@ -224,6 +224,7 @@ mpa_ctx_t *mpa_ctx_create(int device)
 	if (const char *s = getenv("MPA_DP_LITE_MIN")) ctx->lite_min = atoi(s);
 	if (const char *s = getenv("MPA_DP_LITE_WIDE")) ctx->lite_wide = atoi(s) != 0;
 	if (const char *s = getenv("MPA_DP_SPLIT_WIDE")) ctx->split_wide = atoi(s) != 0;
+	if (const char *s = getenv("MPA_DP_HUGE_WG")) ctx->huge_wg = atoi(s) != 0;
 	return ctx;
 }
 
@@ -278,6 +279,7 @@ mpa_ctx_t *ctx_sibling(mpa_ctx_t *ctx, int k)
 		sb->lite_min = ctx->lite_min;
 		sb->lite_wide = ctx->lite_wide;
 		sb->split_wide = ctx->split_wide;
+		sb->huge_wg = ctx->huge_wg;
 		sb->root = ctx;
 		ctx->siblings.push_back(sb);
 	}

@@ -7,7 +7,8 @@
 //   2. ONE k_dp_round launch for every DP unit of the round: the extension calls of every class up to 1024 columns, the packed
 //      sweeps of the checkpointed traceback and the plain traceback sweeps of the first traceback chunk, costliest unit first
 //      (MPA_DP_POOL=1: the units go to the resident workers of the device's pool, k_dp_worker, instead),
-//   3. next to it on side streams: k_ext_huge + k_ext_replay (wider calls, and whatever the int16 sweeps may not take), k_lite_wide
+//   3. next to it on side streams: k_ext_huge (MPA_DP_HUGE_WG=1: and k_ext_huge_wg, one wave per column block, for the calls of four
+//      blocks or more) + k_ext_replay (wider calls, and whatever the int16 sweeps may not take), k_lite_wide
 //      (129..256-column checkpointed calls), the 512/1024-thread traceback classes, the anti-diagonal prototype,
 //   4. k_backtrack per traceback chunk (chunks after the first: stand-alone k_glob_* launches, serial), k_walk for the
 //      checkpointed calls, one download, one host wait, k_cigar_gather (MPA_GPU_ROUND2=1, a batch's round 2 from tasks that are on the
@@ -430,10 +431,28 @@ static int dp_side_launches(DpRun &R)
 		GlobArgs ha;
 		ha.tasks = ctx->tasks.as<DTask>(), ha.waves = R.d_hw, ha.rec = ctx->rec.as<uint32_t>(), ha.prof = ctx->prof.as<int16_t>();
 		ha.tb = nullptr, ha.bnd = ctx->bnd.as<int4>(), ha.score = nullptr, ha.c = R.dc, ha.rowkey64 = ctx->hkey.as<unsigned long long>();
+		// MPA_DP_HUGE_WG: calls of hwg::MIN_BLOCKS column blocks or more on k_ext_huge_wg (one wave per block, no hand-off between
+		// workgroups: a repeated round and the worker pool take it too); both kernels go over the same list and each returns at
+		// once for the other's calls.  A kernel without a call in the list is not launched.
+		int64_t *lh = ctx->last_huge;                                   // (zero: mpa_dp_run_impl)
+		for (int32_t id : P.huge_ids) {
+			const int32_t nblk = hwg::n_blocks(P.tasks[id].ncol);
+			if (ctx->huge_wg && hwg::takes_wg(P.tasks[id].ncol)) ++lh[1], lh[2] += nblk, lh[3] += hwg::n_pass(nblk);
+			else ++lh[0];
+		}
+		if (timing_on()) fprintf(stderr, "[mpa-timing]   dp: huge calls: %lld on one wave, %lld on workgroups (%lld blocks, %lld passes)\n", (long long)lh[0], (long long)lh[1], (long long)lh[2], (long long)lh[3]);
+		const int32_t wg_min = ctx->huge_wg ? hwg::MIN_BLOCKS : 0;
 		hipStream_t st = begin_side(R, true);
-		if (P.wide_ge) hipLaunchKernelGGL(k_ext_huge<true>, dim3(n_huge), dim3(64), (size_t)22 * 64 * 2 + 4 * 32 * 4, st, ha);
-		else hipLaunchKernelGGL(k_ext_huge<false>, dim3(n_huge), dim3(64), (size_t)22 * 64 * 2 + 4 * 32 * 4, st, ha);
-		HIP_TRY(hipGetLastError());
+		if (lh[0]) {
+			if (P.wide_ge) hipLaunchKernelGGL(k_ext_huge<true>, dim3(n_huge), dim3(64), (size_t)22 * 64 * 2 + 4 * 32 * 4, st, ha, wg_min);
+			else hipLaunchKernelGGL(k_ext_huge<false>, dim3(n_huge), dim3(64), (size_t)22 * 64 * 2 + 4 * 32 * 4, st, ha, wg_min);
+			HIP_TRY(hipGetLastError());
+		}
+		if (lh[1]) {
+			if (P.wide_ge) hipLaunchKernelGGL(k_ext_huge_wg<true>, dim3(n_huge), dim3(hwg::W * 64), 0, st, ha);
+			else hipLaunchKernelGGL(k_ext_huge_wg<false>, dim3(n_huge), dim3(hwg::W * 64), 0, st, ha);
+			HIP_TRY(hipGetLastError());
+		}
 		hipLaunchKernelGGL(k_ext_replay, dim3(n_huge), dim3(64), 0, st, ctx->tasks.as<DTask>(), R.d_hlist, (int32_t)n_huge,
 		                   ctx->hkey.as<unsigned long long>(), ctx->extout.as<ExtOut>(), R.dc, P.pen);
 		HIP_TRY(hipGetLastError());
@@ -928,6 +947,7 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 		}
 	}
 	memcpy(ctx->last_ext_calls, plan.ext_calls, sizeof(ctx->last_ext_calls));
+	memset(ctx->last_huge, 0, sizeof(ctx->last_huge));
 	if (timing_on() && plan.ext_wide[0].cnt + plan.ext_wide[1].cnt > 0)
 		fprintf(stderr, "[mpa-timing]   dp: %d + %d groups of the 2048- / 3072-column extension classes (8 / 12 workgroups each), %lld boundaries\n", plan.ext_wide[0].cnt, plan.ext_wide[1].cnt, (long long)plan.n_bound);
 	DpRun R{ ctx, ctx->stream, plan, kn, in };
@@ -1042,6 +1062,7 @@ int64_t mpa_dbg_dp_plan(const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ct
 namespace mpa {
 size_t dp_round_args_bytes() { return sizeof(DpRoundArgs); }
 void dp_last_ext_calls(const mpa_ctx_t *ctx, int64_t ext_calls[16]) { memcpy(ext_calls, ctx->last_ext_calls, sizeof(ctx->last_ext_calls)); }
+void dp_last_huge(const mpa_ctx_t *ctx, int64_t out[4]) { memcpy(out, ctx->last_huge, sizeof(ctx->last_huge)); }
 // mpa_dbg_dp_plan_device on a context (dpplan_dbg.cpp): the device planner on a task table, then every section it left in the pools
 // downloaded into a plan's vectors and serialised as mpa_dbg_dp_plan does.  1: declined (the last error says why).
 int64_t dev_dp_plan_dbg(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, const mpa_qbatch_t *q, int64_t n, const mpa_dp_task_t *in,

@@ -102,6 +102,8 @@ int64_t dp_plan_write(const DpPlan &plan, const std::vector<DpUnit> &units, void
 size_t dp_round_args_bytes();            // the size of the worker pool's argument block: the model's round_args_bytes
 // ... and for mpa_dbg_dp_last_classes: extension calls per DpClass in the plan of the context's last mpa_dp_run
 void dp_last_ext_calls(const mpa_ctx_t *ctx, int64_t ext_calls[16]);
+// ... and for mpa_dbg_dp_last_huge: the last mpa_dp_run's X_HUGE calls on the one-wave kernel, on the workgroup kernel, the latter's blocks and passes
+void dp_last_huge(const mpa_ctx_t *ctx, int64_t out[4]);
 // the device planner on a context, what it left serialised like dp_plan_serialize; 1: it declined (the last error says why)
 int64_t dev_dp_plan_dbg(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, const mpa_qbatch_t *q, int64_t n, const mpa_dp_task_t *in,
                         const DpPlanKnobs &kn, void *buf, int64_t cap, bool wide = false);

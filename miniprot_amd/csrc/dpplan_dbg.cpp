@@ -4,6 +4,7 @@
 #include <vector>
 #include "mpa_internal.h"
 #include "dp_plan.h"
+#include "ext_huge_wg_core.h"
 #include "../../include/mpamd_dbg.h"
 
 using namespace mpa;
@@ -67,4 +68,16 @@ extern "C" int mpa_dbg_dp_last_classes(const mpa_ctx_t *ctx, int64_t ext_calls[1
 	if (!ctx || !ext_calls) { set_error("mpa_dbg_dp_last_classes: missing arguments"); return MPA_ERR_ARG; }
 	dp_last_ext_calls(ctx, ext_calls);
 	return MPA_OK;
+}
+
+extern "C" int mpa_dbg_dp_last_huge(const mpa_ctx_t *ctx, int64_t out[4])
+{
+	if (!ctx || !out) { set_error("mpa_dbg_dp_last_huge: missing arguments"); return MPA_ERR_ARG; }
+	dp_last_huge(ctx, out);
+	return MPA_OK;
+}
+
+extern "C" void mpa_dbg_dp_huge_wg_info(int32_t out[3])
+{
+	if (out) out[0] = hwg::W, out[1] = hwg::R, out[2] = hwg::MIN_BLOCKS;
 }

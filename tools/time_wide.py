@@ -3,7 +3,11 @@
 antidiag = 1: the 32-column extension class on the anti-diagonal prototype (dp_antidiag.hip) instead of the row sweep.
 python tools/time_wide.py split_wide [repeats]: the table of the 1 025..3 072-column extension classes (MPA_DP_SPLIT_WIDE) -- a pair of
 calls of 1 100, 1 500, 2 000 and 2 600 columns x 20 000 rows, first with the knob off (k_ext_huge, the one-wave int32 sweep), then with
-the knob on (X_SPLIT8 / X_SPLIT12), the pair of legs `repeats` times (default 3); 1 000 columns (X_SPLIT4 in both legs) for comparison."""
+the knob on (X_SPLIT8 / X_SPLIT12), the pair of legs `repeats` times (default 3); 1 000 columns (X_SPLIT4 in both legs) for comparison.
+python tools/time_wide.py huge_wg [repeats]: the table of MPA_DP_HUGE_WG -- a pair of right-extension calls of 20 000 rows at 1 100, 1 500,
+2 000, 2 600, 3 300 and 6 800 columns with MPA_DP_SPLIT_WIDE unset (all X_HUGE), knob off (k_ext_huge, one wave per call) and knob on
+(k_ext_huge_wg, one wave per column block), interleaved; then ms_total of the mixed batch of the tests (tests/hugewg.py, mixed_table:
+X_HUGE calls of 4, W + 1 and 2 W + 1 blocks next to a round of 40 ordinary pairs), the same way."""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, ROOT)
@@ -41,6 +45,58 @@ def split_wide_table(repeats, nl=20000, n=2):
                 print("%6d %4d %8s %14.1f %14.1f %8.2f" % (al, rep, cls[0] + "|" + cls[1], ns[0], ns[1], ns[0] / ns[1]))
 
 
+def huge_wg_table(repeats, nl=20000, n=2):
+    rng = np.random.default_rng(1)
+    g = rng.integers(0, 4, nl * n + 1000).astype(np.uint8)
+    idx = mpa.Index.from_nt4([g], ["c"])
+    os.environ.pop("MPA_DP_SPLIT_WIDE", None)
+    ctxs = {}
+    for knob in (0, 1):                                # the knob is read when a context is created
+        os.environ["MPA_DP_HUGE_WG"] = str(knob)
+        ctxs[knob] = mpa.Context(0)
+        idx.to_device(ctxs[knob])
+    dp = mpa.dpopt_from(mpa.default_mapopt())
+    dp.xdrop = 32000                                   # never stop: time all rows
+    print("# (W, R, MIN_BLOCKS) = %s" % (mpa.dbg_dp_huge_wg_info(),))
+    print("# ns per row of a pair of right-extension calls, %d rows each: ms_ext of the huge calls' launches + k_ext_replay; huge: mpa_dbg_dp_last_huge off|on" % nl)
+    print("%6s %4s %28s %14s %14s %8s" % ("al", "rep", "huge", "off ns/row", "on ns/row", "off/on"))
+    for al in (1100, 1500, 2000, 2600, 3300, 6800):
+        aa = bytes(rng.choice(list(b"ACDEFGHIKLMNPQRSTVWY"), al * n).tolist())
+        q = mpa.Queries([aa[i * al:(i + 1) * al] for i in range(n)])
+        tasks = np.zeros(n, mpa.DP_TASK)
+        for i in range(n):
+            tasks[i]["nt_off"] = i * nl; tasks[i]["nl"] = nl; tasks[i]["qid"] = i; tasks[i]["al"] = al; tasks[i]["flag"] = 4; tasks[i]["io"] = 29
+        for rep in range(repeats + 1):                 # (the first pair of legs warms both contexts up and is not printed)
+            ns, huge, rst = {}, {}, {}
+            for knob in (0, 1):
+                rst[knob], _ = mpa.dp_run(ctxs[knob], idx, dp, q, tasks)
+                ns[knob] = ctxs[knob].dp_stats()["ms_ext"] * 1e6 / nl
+                huge[knob] = ",".join(str(x) for x in mpa.dbg_dp_last_huge(ctxs[knob]))
+            assert [tuple(r) for r in rst[0]] == [tuple(r) for r in rst[1]], "the two kernels disagree at %d columns" % al
+            if rep:
+                print("%6d %4d %28s %14.1f %14.1f %8.2f" % (al, rep, huge[0] + "|" + huge[1], ns[0], ns[1], ns[0] / ns[1]))
+    idx.close()
+    # the mixed batch: does the 64 KB workgroup wait for the round's workgroups to leave a CU?
+    import hugewg as hw
+    tab, want = hw.mixed_table()
+    idx = mpa.Index.from_nt4(tab.contigs)
+    for knob in (0, 1):
+        idx.to_device(ctxs[knob])
+    print("# the mixed batch (X_HUGE calls of %s blocks, %d calls in all): ms of the batch on the device, of the extension launches, of the round" % (sorted(set(want)), len(tab.tasks)))
+    print("%4s %28s %12s %12s %12s %12s" % ("rep", "huge", "off ms_total", "on ms_total", "off ms_ext", "on ms_ext"))
+    for rep in range(repeats + 1):
+        st, huge = {}, {}
+        for knob in (0, 1):
+            mpa.dp_run(ctxs[knob], idx, tab.opt, tab.queries, tab.tasks)
+            st[knob] = ctxs[knob].dp_stats()
+            huge[knob] = ",".join(str(x) for x in mpa.dbg_dp_last_huge(ctxs[knob]))
+        if rep:
+            print("%4d %28s %12.3f %12.3f %12.3f %12.3f" % (rep, huge[0] + "|" + huge[1], st[0]["ms_total"], st[1]["ms_total"], st[0]["ms_ext"], st[1]["ms_ext"]))
+
+
+if sys.argv[1] == "huge_wg":
+    huge_wg_table(int(sys.argv[2]) if len(sys.argv) > 2 else 3)
+    sys.exit(0)
 if sys.argv[1] == "split_wide":
     split_wide_table(int(sys.argv[2]) if len(sys.argv) > 2 else 3)
     sys.exit(0)
