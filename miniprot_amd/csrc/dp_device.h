@@ -1,4 +1,5 @@
-// dp_device.h -- device-side data layout shared by the DP kernels (dp_kernels.hip) and the executor.
+// dp_device.h -- device-side data layout shared by the DP kernels (dp_kernels.hip and the four files of stand-alone launches its header
+// lists: dp_prep_kernels.hip, dp_lite_wide.hip, dp_huge_kernels.hip, dp_traceback_kernels.hip) and the executor.
 #pragma once
 #include <cstdint>
 #ifndef __HIPCC__

@@ -15,11 +15,17 @@
 //      device: the result records and the dense pool's offsets by the kernels of dp_results_kernels.hip and the gather in front of
 //      that one wait, the dense pool left on the device -- dp_run_resident() below),
 // bracketed by HIP events (mpa_dp_last_stats feeds bench.py's roofline record).  mpa_dp_run_impl is that list of phases.  There is no
-// CPU fallback here by design.  This unit holds the DP only (kernels: dp_kernels.hip, dp_antidiag.hip, gs32_exec.hip); the context
-// and its pools are dev_ctx.hip, the other stages seed_run.hip, refine_run.hip and index_run.hip.
+// CPU fallback here by design.  This unit holds the DP only (kernels: dp_kernels.hip -- what k_dp_round and k_dp_worker execute -- and,
+// behind it, the launches of phases 1, 3 and 4 in dp_prep_kernels.hip, dp_lite_wide.hip, dp_huge_kernels.hip and
+// dp_traceback_kernels.hip; dp_antidiag.hip, gs32_exec.hip); the context and its pools are dev_ctx.hip, the other stages seed_run.hip,
+// refine_run.hip and index_run.hip.
 #include <rocprim/device/device_radix_sort.hpp>
 #include "dev_ctx.h"
 #include "dp_kernels.hip"
+#include "dp_prep_kernels.hip"
+#include "dp_lite_wide.hip"
+#include "dp_huge_kernels.hip"
+#include "dp_traceback_kernels.hip"
 #include "dp_antidiag.hip"
 #include "dp_plan_kernels.hip"
 #include "dp_results_kernels.hip"
@@ -28,7 +34,7 @@ namespace mpa {
 
 template<int NW> static hipError_t launch_glob_wide(const GlobArgs &a, int n_groups, hipStream_t s, bool wide_ge = false)
 {
-	const size_t lds = (size_t)NW * 22 * 64 * 2 + 2 * NW * 16 + 64 * 4;
+	const size_t lds = GLOB_WIDE_LDS(NW);
 	if (wide_ge) hipLaunchKernelGGL((k_glob_wide<NW, true>), dim3(n_groups), dim3(NW * 64), lds, s, a);
 	else hipLaunchKernelGGL((k_glob_wide<NW, false>), dim3(n_groups), dim3(NW * 64), lds, s, a);
 	return hipGetLastError();
@@ -38,7 +44,7 @@ template<int NW> static hipError_t launch_glob_wide(const GlobArgs &a, int n_gro
 // (the traceback chunks after the first, which do not ride in the round's launch)
 static hipError_t launch_glob_narrow(const GlobArgs &a, const int *first, const int *cnt, hipStream_t s, bool wide_ge = false)
 {
-	const size_t lds = (size_t)22 * 64 * 2 + (size_t)4 * 32 * 4;
+	const size_t lds = GLOB_NARROW_LDS;
 	NarrowMap m{};
 	const int cls[4] = { T_16, T_32, T_64, T_MB };
 	int total = 0;
@@ -444,8 +450,8 @@ static int dp_side_launches(DpRun &R)
 		const int32_t wg_min = ctx->huge_wg ? hwg::MIN_BLOCKS : 0;
 		hipStream_t st = begin_side(R, true);
 		if (lh[0]) {
-			if (P.wide_ge) hipLaunchKernelGGL(k_ext_huge<true>, dim3(n_huge), dim3(64), (size_t)22 * 64 * 2 + 4 * 32 * 4, st, ha, wg_min);
-			else hipLaunchKernelGGL(k_ext_huge<false>, dim3(n_huge), dim3(64), (size_t)22 * 64 * 2 + 4 * 32 * 4, st, ha, wg_min);
+			if (P.wide_ge) hipLaunchKernelGGL(k_ext_huge<true>, dim3(n_huge), dim3(64), GLOB_NARROW_LDS, st, ha, wg_min);
+			else hipLaunchKernelGGL(k_ext_huge<false>, dim3(n_huge), dim3(64), GLOB_NARROW_LDS, st, ha, wg_min);
 			HIP_TRY(hipGetLastError());
 		}
 		if (lh[1]) {

@@ -1,10 +1,26 @@
 // dp_kernels.hip -- hand-written CDNA4 (gfx950) kernels for miniprot's spliced protein-to-genome DP.
 //
-// What they replace in the reference (lh3/miniprot v0.18-r281):
-//   k_prep_rows / k_prep_prof  ns_prep_seq, ns_prep_seq_left, ns_prep_nas, ns_gen_prof   nasw-sse.c:91-224
-//   k_ext_narrow / k_ext_wide  ns_global_gs16b score-only / extension loop               nasw-sse.c:349-443
-//   k_glob_narrow / _wide      ns_global_gs16b traceback loop                             nasw-sse.c:444-542
-//   k_backtrack                ns_backtrack + ns_fix_tiny_UV                              nasw-sse.c:30-89
+// The DP kernel source is five files, one translation unit (dp_exec.hip includes them in this order).  THIS file holds exactly what
+// k_dp_round and k_dp_worker execute, and the definitions the other four build on; each of the others holds launches of its own,
+// none of whose code runs inside the round kernel or the pool:
+//   dp_kernels.hip            the round: sections below
+//   dp_prep_kernels.hip       k_prep_rows, k_prep_prof (per-row records, query profiles; DevTables)
+//   dp_lite_wide.hip          k_lite_wide / lite_wide_body (packed sweep of the checkpointed traceback, 129..256 columns)
+//   dp_huge_kernels.hip       k_ext_huge, k_ext_huge_wg, k_ext_replay (extension calls wider than 1024 columns, int32)
+//   dp_traceback_kernels.hip  k_glob_narrow / k_glob_wide (the bodies below as launches), k_backtrack, k_walk, k_cigar_gather
+// Sections of this file, in order:
+//   helpers          WavePos, packed int16 and DPP primitives, scans, votes
+//   K1               ExtArgs, profile and record-ring layout (ring_entry), the asm rows (every row macro of the five files), ext_narrow
+//   K1-wide          ExtWideArgs, granules, ext_wide_body
+//   K2, K2-wide      GlobArgs, GlobState, glob_cands, GlobResume, glob_narrow, glob_wide_body (int32 traceback sweeps)
+//   k_dp_round       dp_run_unit, k_dp_round
+//   worker pool      DpPool, k_dp_arm, k_l2_writeback, k_dp_worker
+//
+// What the kernels replace in the reference (lh3/miniprot v0.18-r281):
+//   k_prep_rows / k_prep_prof  ns_prep_seq, ns_prep_seq_left, ns_prep_nas, ns_gen_prof   nasw-sse.c:91-224   (dp_prep_kernels.hip)
+//   ext_narrow / ext_wide_body ns_global_gs16b score-only / extension loop               nasw-sse.c:349-443
+//   glob_narrow / _wide_body   ns_global_gs16b traceback loop                             nasw-sse.c:444-542
+//   k_backtrack                ns_backtrack + ns_fix_tiny_UV                              nasw-sse.c:30-89    (dp_traceback_kernels.hip)
 //
 // Mapping to the hardware (DESIGN.md has the full argument):
 //   * The DP matrix is tall and thin (rows = genomic window up to ~1e5, columns = the unaligned protein
@@ -27,16 +43,14 @@
 //     in column blocks with a per-row boundary record.
 //
 // No MFMA: this is integer max-plus DP, not a contraction.
+#pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
 #include "dp_device.h"
 #include "dev_common.h"
-#include "ext_huge_wg_core.h"
 
 namespace mpa {
-
-struct DevTables { uint8_t aa20[256]; uint8_t codon[64]; int8_t mat[484]; };
 
 // Where a wavefront sits: every DP body below is written for "a group of NW waves working on one unit" and is told its LDS
 // region, its lane, its wave index inside the group (scalar) and its thread index inside the group.  The stand-alone kernels
@@ -203,166 +217,6 @@ __device__ __forceinline__ int32_t s_sub(int32_t a, int32_t b) { return sat16(a 
 __device__ __forceinline__ int32_t s_add(int32_t a, int32_t b) { return sat16(a + b); }
 
 // ------------------------------------------------------------------------------------------------
-// K3: per-row records and query profiles
-// ------------------------------------------------------------------------------------------------
-#define PROF_AA_STRIDE_REC 2   /* byte0 of a record = amino acid * 2 = byte offset into an int16 profile column (k_ext) */
-
-// donor/acceptor/nas of window row i (the window fetch, ntseq.c:89-114 -- 4-bit unpack, reverse complement -- is folded into the
-// addressing).  Forward: ns_prep_seq (nasw-sse.c:106-155); left extension:
-// ns_prep_seq_left (nasw-sse.c:157-210).  int8 wrap-around of the reference's arrays is preserved.
-// Four rows per thread (rows i, i + 256, i + 512, i + 768 of a 1 024-row chunk): the kernel is bound by the chain of dependent loads
-// chunk -> task -> contig -> genome words and by how many waves the chip holds at once, not by bandwidth or arithmetic (round 4:
-// 1.8 ms alone for 200 M rows = 0.5 TB/s, and 2-6 x that next to the other kernels of the stream, on every round's critical
-// path) -- a thread that fetches the words of four rows together pays the chain once for four records.
-#define MPA_PREP_ROWS (MPA_PREP_CHUNK_ROWS / 256)
-__global__ __launch_bounds__(256) void k_prep_rows(DevGenome g, const DTask *tasks, const PrepChunk *chunks, uint32_t *rec, DpConst c, DevTables tb)
-{
-	MPA_SHORT_KERNEL();
-	const PrepChunk ch = chunks[blockIdx.x];
-	const DTask t = tasks[ch.task];
-	const int32_t nl = t.nl;
-	const int cid = t.vid >> 1, rev = t.vid & 1, left = (t.flag & 2) != 0;
-	const int64_t off = g.ctg_off[cid], len = g.ctg_len[cid];
-	// w[j] = b[i-6+j], j=0..15, where b[] is the (possibly reversed) window; 15 = outside the window.
-	// The sixteen bases are consecutive in the packed genome (ascending, or descending for a reversed window / the minus strand):
-	// three aligned words cover them, and the sixteen nibbles are shifted out of those -- instead of sixteen dependent byte loads
-	// with 64-bit address arithmetic each.  The genome buffer is padded by 16 bytes; what lies outside the
-	// window is masked to 15 whatever was read for it.
-	uint64_t nibs[MPA_PREP_ROWS];
-	const int64_t x0 = t.nt_off + (left ? nl - 1 : 0);             // strand position of window position 0
-	const int64_t p0 = rev ? off + len - 1 - x0 : off + x0;        // ... its position in the packed genome
-	const int dir = (left != (rev != 0)) ? -1 : 1;
-#pragma unroll
-	for (int r = 0; r < MPA_PREP_ROWS; ++r) {
-		const int32_t i = ch.row0 + (int32_t)threadIdx.x + 256 * r;
-		nibs[r] = i < nl ? packed_window16(g.seq, g.l_seq, p0 + (int64_t)dir * (i - 6), dir, rev) : 0;
-	}
-#pragma unroll
-	for (int r = 0; r < MPA_PREP_ROWS; ++r) {
-	const int32_t i = ch.row0 + (int32_t)threadIdx.x + 256 * r;
-	if (i >= nl) continue;
-	uint64_t nib = nibs[r];
-	{
-		const int32_t jlo = 6 - i > 0 ? (6 - i > 16 ? 16 : 6 - i) : 0;                        // w[j], j < jlo: before the window
-		const int32_t jhi = nl - i + 6 < 16 ? (nl - i + 6 < 0 ? 0 : nl - i + 6) : 16;       // w[j], j >= jhi: behind it
-		uint64_t valid = jhi >= 16 ? ~0ULL : ((1ULL << (4 * jhi)) - 1);
-		valid &= jlo >= 16 ? 0ULL : ~((1ULL << (4 * jlo)) - 1);
-		nib = (nib & valid) | ~valid;
-	}
-	uint32_t w[16];
-#pragma unroll
-	for (int j = 0; j < 16; ++j) w[j] = (uint32_t)(nib >> (4 * j)) & 15u;
-#define B_(d) w[6 + (d)]   /* b[i+d] */
-	uint32_t nas = 21;
-	int32_t don, acc;
-	const int32_t sp3 = (int8_t)c.sp[3];
-	if (!left) {
-		if (i >= 2 && B_(0) < 4 && B_(-1) < 4 && B_(-2) < 4) nas = tb.codon[B_(-2) << 4 | B_(-1) << 2 | B_(0)];
-		{ // donor[k], k = i+1
-			const int32_t k = i + 1;
-			don = sp3;
-			if (k < nl - 3) {
-				int tt = 3;
-				if (B_(2) == 2 && B_(3) == 3) tt = (B_(4) == 0 || B_(4) == 2) ? (B_(1) == 2 ? -1 : 4) : 0;
-				else if (B_(2) == 2 && B_(3) == 1 && B_(1) == 2) tt = 1;
-				else if (B_(2) == 0 && B_(3) == 3) tt = 2;
-				don = tt < 0 ? 0 : (int8_t)c.sp[tt];
-			}
-		}
-		{ // acceptor[i]
-			acc = sp3;
-			if (i >= 1) {
-				int tt = 3, pen_y = 0;
-				if (B_(-1) == 0 && B_(0) == 2) {
-					tt = (i >= 2 && (B_(-2) == 1 || B_(-2) == 3)) ? -1 : 0;
-#pragma unroll
-					for (int d = 4; d <= 6; ++d)
-						if (i - d >= 0 && B_(-d) != 1 && B_(-d) != 3) pen_y += c.sp[5];
-				} else if (B_(-1) == 0 && B_(0) == 1) tt = 2;
-				acc = tt < 0 ? 0 : (int8_t)c.sp[tt];
-				if (tt == -1 || tt == 0) acc = (int8_t)(acc + pen_y);
-			}
-		}
-	} else {
-		if (i >= 2 && B_(0) < 4 && B_(-1) < 4 && B_(-2) < 4) nas = tb.codon[B_(0) << 4 | B_(-1) << 2 | B_(-2)];
-		{ // "donor"[k] of the reversed string, k = i+1 (really the acceptor signal read backwards)
-			const int32_t k = i + 1;
-			don = sp3;
-			if (k < nl - 3) {
-				int tt = 3, pen_y = 0;
-				if (B_(2) == 2 && B_(3) == 0) {
-					tt = (B_(4) == 1 || B_(4) == 3) ? -1 : 0;
-#pragma unroll
-					for (int d = 6; d <= 8; ++d)       // j = k+5 .. k+7  ->  b[i+6 .. i+8]
-						if (i + d < nl && B_(d) != 1 && B_(d) != 3) pen_y += c.sp[5];
-				} else if (B_(2) == 1 && B_(3) == 0) tt = 2;
-				don = tt < 0 ? 0 : (int8_t)c.sp[tt];
-				if (tt == -1 || tt == 0) don = (int8_t)(don + pen_y);
-			}
-		}
-		{ // "acceptor"[i] of the reversed string (really the donor signal read backwards)
-			acc = sp3;
-			if (i >= 1) {
-				int tt = 3;
-				if (B_(-1) == 3 && B_(0) == 2)
-					tt = (i >= 2 && (B_(-2) == 0 || B_(-2) == 2)) ? ((i + 1 < nl && B_(1) == 2) ? -1 : 4) : 0;
-				else if (B_(-1) == 1 && B_(0) == 2 && i + 1 < nl && B_(1) == 1) tt = 1;
-				else if (B_(-1) == 3 && B_(0) == 0) tt = 2;
-				acc = tt < 0 ? 0 : (int8_t)c.sp[tt];
-			}
-		}
-	}
-#undef B_
-	if (g.spsc) {
-		// --spsc: the score track adjusts the penalties (nasw-sse.c:138-152, left: 189-203).  ss[p] belongs to window position p
-		// (forward); forward calls shift it onto donor/acceptor[p-1], the reversed left extension onto [nl-1-p] with the two
-		// roles swapped.  int8 wrap-around as in the reference's arrays.
-		const uint8_t *track = g.spsc + (rev ? g.l_seq : 0) + off;
-		const int32_t max_spsc = (t.io + 1) / 2 - 1;
-		auto ss_at = [&](int32_t p) -> int32_t {             // -1: outside what the reference reads
-			if (p < (left ? 0 : 1) || p >= nl) return -1;
-			if (p == 0 && (t.flag & 8)) return 0xff;           // MPA_F_SS_SKIP0
-			return track[t.nt_off + p];
-		};
-		auto adjust = [&](int32_t v, int32_t ss, bool for_acceptor_entry) -> int32_t {
-			if (ss < 0) return v;
-			if (ss == 0xff) return (int8_t)(v - c.sp_null_bonus);
-			if (((ss & 1) != 0) != for_acceptor_entry) return v;
-			int32_t spsc = (int8_t)(ss >> 1) - 64;
-			if (spsc > max_spsc) spsc = max_spsc;
-			return (int8_t)(v - spsc);
-		};
-		if (!left) {
-			don = adjust(don, ss_at(i + 2), false);          // donor[i+1] <- ss[i+2] (donor entries)
-			acc = adjust(acc, ss_at(i + 1), true);           // acceptor[i] <- ss[i+1] (acceptor entries)
-		} else {
-			don = adjust(don, ss_at(nl - 2 - i), true);      // "donor"[i+1] of the reversed string <- acceptor entries at nl-1-(i+1)
-			acc = adjust(acc, ss_at(nl - 1 - i), false);     // "acceptor"[i] <- donor entries at nl-1-i
-		}
-	}
-	// (byte 2: the row's gap extension -- fs on a stop codon, nasw-sse.c:263,370 -- or, when the penalties do not fit a byte, just the stop flag)
-	rec[t.rec_off + i] = make_rec(nas * PROF_AA_STRIDE_REC, don, c.wide_ge ? (uint32_t)(nas == 20) : nas == 20 ? (uint32_t)c.fs : (uint32_t)c.ge, acc);
-	}
-}
-
-// query profile prof[a][col] = mat[a][aa(col)] (ns_gen_prof nasw-sse.c:212-224); columns >= al score -32768
-__global__ __launch_bounds__(256) void k_prep_prof(const DTask *tasks, const char *qseq, int16_t *prof, DevTables tb)
-{
-	MPA_SHORT_KERNEL();
-	const DTask t = tasks[blockIdx.x];
-	const int left = (t.flag & 2) != 0;
-	for (int idx = threadIdx.x; idx < 22 * t.pw; idx += blockDim.x) {
-		int a = idx / t.pw, col = idx - a * t.pw;
-		int16_t v = NEG16;
-		if (col < t.al) {
-			uint8_t ch = (uint8_t)qseq[t.q_off + (left ? t.al - 1 - col : col)];
-			v = tb.mat[a * 22 + tb.aa20[ch]];
-		}
-		prof[t.prof_off + idx] = v;
-	}
-}
-
-// ------------------------------------------------------------------------------------------------
 // K1: extension (score only).  See file header.
 //
 // What one row costs (round 6, tools/ubench/valu_rate.hip on the MI355X): every packed-int16 instruction, DPP move, v_perm,
@@ -436,15 +290,27 @@ __device__ __forceinline__ uint32_t prof2s(const uint32_t lo, const uint32_t hi)
 	return as_u(r);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The asm rows.  Every instruction sequence and every operand list below is written once; the rows of the sweeps -- score rows
+// (ext_narrow<G>, its DUAL form, ext_wide_body) and LITE rows (ext_narrow<G, true>, its DUAL form, lite_wide_body in
+// dp_lite_wide.hip) -- are instantiations.  A macro parameter that stands for asm text or for a piece of an operand list may be
+// empty (MPA_NONE); a piece of an operand list ends with its comma.  tools/kernel_identity.py is the check after any change here.
+// ------------------------------------------------------------------------------------------------
+#define MPA_NONE
+#define MPA_NOP0 "s_nop 0\n\t"
+#define MPA_NOP1 "s_nop 1\n\t"
+
 // The first asm block of a row: the three intron states, the frameshift moves and the choice among everything but the
 // horizontal gap.  hD = max(H(i-3,j-1) + s(i,j), D(i,j)) was made during the row before.  x = h + j*ge feeds the scan.
-#define MPA_ROW_HEAD(Hr1, Hs1, dn1, dn2, dn3, ac1, ac2, ac3, M1, M2) \
+// DIFFS / DOUTS: what a LITE row puts between the fresh intron states and their maxima (MPA_HEAD_DIFFS below).
+#define MPA_ROW_HEAD_X(DIFFS, DOUTS, Hr1, Hs1, dn1, dn2, dn3, ac1, ac2, ac3, M1, M2) \
 	asm volatile( \
 		"v_pk_sub_i16 %[uA], %[hr1], %[io] clamp\n\t" \
 		"v_pk_sub_i16 %[uB], %[hs1], %[io] clamp\n\t" \
 		"v_pk_sub_i16 %[uA], %[uA], %[d2] clamp\n\t" \
 		"v_pk_sub_i16 %[t1], %[uB], %[d1] clamp\n\t" \
 		"v_pk_sub_i16 %[uB], %[uB], %[d3] clamp\n\t" \
+		DIFFS \
 		"v_pk_max_i16 %[A], %[uA], %[A]\n\t" \
 		"v_pk_max_i16 %[B], %[t1], %[B]\n\t" \
 		"v_pk_max_i16 %[C], %[uB], %[C]\n\t" \
@@ -458,14 +324,28 @@ __device__ __forceinline__ uint32_t prof2s(const uint32_t lo, const uint32_t hi)
 		"v_pk_max_i16 %[h], %[hD], %[uA]\n\t" \
 		"v_pk_max_i16 %[h], %[h], %[uB]\n\t" \
 		"v_pk_add_i16 %[x], %[h], %[jge] clamp" \
-		: [uA] "=&v"(tA_), [uB] "=&v"(tB_), [t1] "=&v"(tC_), [h] "=&v"(h), [x] "=&v"(x), [A] "+v"(A), [B] "+v"(B), [C] "+v"(C) \
+		: [uA] "=&v"(tA_), [uB] "=&v"(tB_), [t1] "=&v"(tC_), [h] "=&v"(h), [x] "=&v"(x), DOUTS [A] "+v"(A), [B] "+v"(B), [C] "+v"(C) \
 		: [hr1] "v"(Hr1), [hs1] "v"(Hs1), [io] "v"(ioP), [d1] "v"(dn1), [d2] "v"(dn2), [d3] "v"(dn3), [a1] "v"(ac1), [a2] "v"(ac2), [a3] "v"(ac3), \
 		  [m1] "v"(M1), [m2] "v"(M2), [hD] "v"(hD), [jge] "v"(jge), [fs] "s"(fsP))
+// The rows of the checkpointed traceback's sweep (LITE: ext_narrow<G, true>, lite_wide_body) are the same two blocks without the
+// vote, with the four "fresh value minus carried value" differences whose signs are the extension bits of the reference's traceback
+// word (bit 5: D(i-3,j) > H(i-3,j) - q, nasw-sse.c:455; bits 6..8: A, B, C carried rather than opened, :462-485), and with the new
+// D state in a register of its own (the old one is what a checkpoint stores).  dA, dB, dC come from the head; dD from the tail's
+// scan (MPA_SCAN4_L) and belongs to the NEXT row, like the D state it comes with.
+#define MPA_HEAD_DIFFS \
+		"v_pk_sub_i16 %[dA], %[uA], %[A] clamp\n\t" \
+		"v_pk_sub_i16 %[dB], %[t1], %[B] clamp\n\t" \
+		"v_pk_sub_i16 %[dC], %[uB], %[C] clamp\n\t"
+#define MPA_HEAD_DOUTS [dA] "=&v"(dA), [dB] "=&v"(dB), [dC] "=&v"(dC),
+#define MPA_ROW_HEAD(...)   MPA_ROW_HEAD_X(MPA_NONE, MPA_NONE, __VA_ARGS__)
+#define MPA_ROW_HEAD_L(...) MPA_ROW_HEAD_X(MPA_HEAD_DIFFS, MPA_HEAD_DOUTS, __VA_ARGS__)
 
 // The second asm block: the gap scan with the next row's independent part in its wait states (D state from H(i-2), Dr(i-2) and the
 // next record's gap extension; the diagonal term from Hs(i-2) and the two profile scores fetched a row ago; the LDS addresses of
 // the scores of the row after from the record fetched at the top of this row), the final H, the vote clamp, H shifted by one
 // column, and M.  Wait states: a DPP move needs two instructions between it and the VALU write of its source.
+// MPA_SCAN4_L is the LITE rows' scan (dD, and the new D state in drn); the two are not one macro with insertion points: their
+// instruction orders differ on purpose (MPA_SCAN4_L ends with an instruction that does not write x).
 #define MPA_SCAN4 \
 		"v_pk_sub_i16 %[t2], %[hr2], %[go] clamp\n\t" \
 		"v_pk_max_i16 %[t2], %[t2], %[dr2]\n\t" \
@@ -483,105 +363,6 @@ __device__ __forceinline__ uint32_t prof2s(const uint32_t lo, const uint32_t hi)
 		"v_add_u32_sdwa %[a1], %[pb1], %[aw] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1\n\t" \
 		"v_mov_b32_dpp %[k3], %[x] row_shr:8 row_mask:0xf bank_mask:0xf\n\t" \
 		"v_pk_max_i16 %[x], %[x], %[k3]\n\t"
-#define MPA_EX16 \
-		"s_nop 1\n\t" \
-		"v_mov_b32_dpp %[ke], %[x] row_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
-		"v_pk_sub_i16 %[t2], %[ke], %[gojge] clamp\n\t"
-#define MPA_EX32 \
-		"s_nop 1\n\t" \
-		"v_mov_b32_dpp %[ke], %[x] row_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
-		"v_mov_b32_dpp %[kc], %[x] row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
-		"v_pk_max_i16 %[t2], %[ke], %[kc]\n\t" \
-		"v_pk_sub_i16 %[t2], %[t2], %[gojge] clamp\n\t"
-#define MPA_EX64 \
-		"v_mov_b32 %[t2], 0x80008000\n\t" \
-		"s_nop 0\n\t" \
-		"v_mov_b32_dpp %[t2], %[x] row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
-		"v_pk_max_i16 %[x], %[x], %[t2]\n\t" \
-		"v_mov_b32 %[t2], 0x80008000\n\t" \
-		"s_nop 0\n\t" \
-		"v_mov_b32_dpp %[t2], %[x] row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" \
-		"v_pk_max_i16 %[x], %[x], %[t2]\n\t" \
-		"s_nop 1\n\t" \
-		"v_mov_b32_dpp %[ke], %[x] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
-		"v_pk_sub_i16 %[t2], %[ke], %[gojge] clamp\n\t"
-#define MPA_FIN \
-		"v_pk_max_i16 %[h], %[h], %[t2]\n\t" \
-		"v_pk_min_i16 %[vt], %[h], %[gl]\n\t" \
-		"v_pk_max_i16 %[vt], %[vt], %[tl]\n\t"
-#define MPA_HS16 "v_mov_b32_dpp %[hs3], %[h] row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-#define MPA_HS32 "v_mov_b32_dpp %[hs3], %[h] wave_shr:1 row_mask:0xb bank_mask:0xf\n\tv_mov_b32_dpp %[hs3], %[h] row_shr:1 row_mask:0x4 bank_mask:0xf\n\t"
-#define MPA_HS64 "v_mov_b32_dpp %[hs3], %[h] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-#define MPA_ROW_TAIL(EX, HS, Hr2, Hs2, Dr2, Hs3, M3) \
-	asm volatile(MPA_SCAN4 EX MPA_FIN HS "v_pk_max_i16 %[m3], %[h], %[hs3]" \
-		: [x] "+v"(x), [h] "+v"(h), [k0] "+v"(k0), [k1] "+v"(k1), [k2] "+v"(k2), [k3] "+v"(k3), [ke] "+v"(ke), [kc] "+v"(kc), [dr2] "+v"(Dr2), [hs3] "+v"(Hs3), \
-		  [t2] "=&v"(tA_), [hDn] "=&v"(hDn), [a0] "=&v"(a0), [a1] "=&v"(a1), [vt] "=&v"(vt), [m3] "=&v"(M3) \
-		: [hr2] "v"(Hr2), [gei] "v"(rnext.z), [s0] "v"(sraw0), [s1] "v"(sraw1), [hs2] "v"(Hs2), [pb0] "v"(pb0), [pb1] "v"(pb1), [aw] "v"(rnn.w), \
-		  [gojge] "v"(gojge), [gl] "v"(GvL), [tl] "v"(TvL), [go] "s"(goP), [sel] "s"(sel_lo))
-
-// DUAL extension rows (one call of 65..128 columns per wave, see MPA_EX64_LD below): the tail with the vote and the two carries
-#define MPA_ROW_TAIL_D(Hr2, Hs2, Dr2, Hs3, M3) \
-	asm volatile(MPA_SCAN4 \
-		"v_mov_b32 %[t2], 0x80008000\n\t" \
-		"s_nop 0\n\t" \
-		"v_mov_b32_dpp %[t2], %[x] row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
-		"v_pk_max_i16 %[x], %[x], %[t2]\n\t" \
-		"v_mov_b32 %[t2], 0x80008000\n\t" \
-		"s_nop 0\n\t" \
-		"v_mov_b32_dpp %[t2], %[x] row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" \
-		"v_pk_max_i16 %[x], %[x], %[t2]\n\t" \
-		"s_nop 0\n\t" \
-		"v_readlane_b32 %[st], %[x], 63\n\t" \
-		"s_lshl_b32 %[st], %[st], 16\n\t" \
-		"s_or_b32 %[st], %[st], 0x8000\n\t" \
-		"v_mov_b32_dpp %[ke], %[x] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
-		"v_pk_max_i16 %[t2], %[ke], %[st]\n\t" \
-		"v_pk_sub_i16 %[t2], %[t2], %[gojge] clamp\n\t" \
-		"v_pk_max_i16 %[h], %[h], %[t2]\n\t" \
-		"v_pk_min_i16 %[vt], %[h], %[gl]\n\t" \
-		"v_pk_max_i16 %[vt], %[vt], %[tl]\n\t" \
-		"v_readlane_b32 %[st], %[h], 63\n\t" \
-		"s_lshl_b32 %[st], %[st], 16\n\t" \
-		"s_or_b32 %[st], %[st], 0x8000\n\t" \
-		"v_mov_b32_dpp %[hs3], %[h] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
-		"v_writelane_b32 %[hs3], %[st], 0\n\t" \
-		"v_pk_max_i16 %[m3], %[h], %[hs3]" \
-		: [x] "+v"(x), [h] "+v"(h), [k0] "+v"(k0), [k1] "+v"(k1), [k2] "+v"(k2), [k3] "+v"(k3), [ke] "+v"(ke), [dr2] "+v"(Dr2), [hs3] "+v"(Hs3), \
-		  [t2] "=&v"(tA_), [hDn] "=&v"(hDn), [a0] "=&v"(a0), [a1] "=&v"(a1), [vt] "=&v"(vt), [m3] "=&v"(M3), [st] "=&s"(stmp) \
-		: [hr2] "v"(Hr2), [gei] "v"(rnext.z), [s0] "v"(sraw0), [s1] "v"(sraw1), [hs2] "v"(Hs2), [pb0] "v"(pb0), [pb1] "v"(pb1), [aw] "v"(rnn.w), \
-		  [gojge] "v"(gojge), [gl] "v"(GvL), [tl] "v"(TvL), [go] "s"(goP), [sel] "s"(sel_lo) \
-		: "scc")
-// The rows of the checkpointed traceback's sweep (ext_narrow<G, true>): the same two blocks without the vote, with the four
-// "fresh value minus carried value" differences whose signs are the extension bits of the reference's traceback word (bit 5: D(i-3,j)
-// > H(i-3,j) - q, nasw-sse.c:455; bits 6..8: A, B, C carried rather than opened, :462-485), and with the new D state in a register
-// of its own (the old one is what a checkpoint stores).  dD belongs to the NEXT row, like the D state it comes with.
-#define MPA_ROW_HEAD_L(Hr1, Hs1, dn1, dn2, dn3, ac1, ac2, ac3, M1, M2) \
-	asm volatile( \
-		"v_pk_sub_i16 %[uA], %[hr1], %[io] clamp\n\t" \
-		"v_pk_sub_i16 %[uB], %[hs1], %[io] clamp\n\t" \
-		"v_pk_sub_i16 %[uA], %[uA], %[d2] clamp\n\t" \
-		"v_pk_sub_i16 %[t1], %[uB], %[d1] clamp\n\t" \
-		"v_pk_sub_i16 %[uB], %[uB], %[d3] clamp\n\t" \
-		"v_pk_sub_i16 %[dA], %[uA], %[A] clamp\n\t" \
-		"v_pk_sub_i16 %[dB], %[t1], %[B] clamp\n\t" \
-		"v_pk_sub_i16 %[dC], %[uB], %[C] clamp\n\t" \
-		"v_pk_max_i16 %[A], %[uA], %[A]\n\t" \
-		"v_pk_max_i16 %[B], %[t1], %[B]\n\t" \
-		"v_pk_max_i16 %[C], %[uB], %[C]\n\t" \
-		"v_pk_sub_i16 %[uA], %[A], %[a3] clamp\n\t" \
-		"v_pk_sub_i16 %[t1], %[B], %[a2] clamp\n\t" \
-		"v_pk_sub_i16 %[uB], %[C], %[a1] clamp\n\t" \
-		"v_pk_max_i16 %[uA], %[uA], %[t1]\n\t" \
-		"v_pk_max_i16 %[t1], %[m1], %[m2]\n\t" \
-		"v_pk_sub_i16 %[t1], %[t1], %[fs] clamp\n\t" \
-		"v_pk_max_i16 %[uB], %[uB], %[t1]\n\t" \
-		"v_pk_max_i16 %[h], %[hD], %[uA]\n\t" \
-		"v_pk_max_i16 %[h], %[h], %[uB]\n\t" \
-		"v_pk_add_i16 %[x], %[h], %[jge] clamp" \
-		: [uA] "=&v"(tA_), [uB] "=&v"(tB_), [t1] "=&v"(tC_), [h] "=&v"(h), [x] "=&v"(x), [dA] "=&v"(dA), [dB] "=&v"(dB), [dC] "=&v"(dC), \
-		  [A] "+v"(A), [B] "+v"(B), [C] "+v"(C) \
-		: [hr1] "v"(Hr1), [hs1] "v"(Hs1), [io] "v"(ioP), [d1] "v"(dn1), [d2] "v"(dn2), [d3] "v"(dn3), [a1] "v"(ac1), [a2] "v"(ac2), [a3] "v"(ac3), \
-		  [m1] "v"(M1), [m2] "v"(M2), [hD] "v"(hD), [jge] "v"(jge), [fs] "s"(fsP))
 #define MPA_SCAN4_L \
 		"v_pk_sub_i16 %[t2], %[hr2], %[go] clamp\n\t" \
 		"v_pk_sub_i16 %[dDn], %[t2], %[dr2] clamp\n\t" \
@@ -600,67 +381,116 @@ __device__ __forceinline__ uint32_t prof2s(const uint32_t lo, const uint32_t hi)
 		"v_mov_b32_dpp %[k3], %[x] row_shr:8 row_mask:0xf bank_mask:0xf\n\t" \
 		"v_pk_max_i16 %[x], %[x], %[k3]\n\t" \
 		"v_add_u32_sdwa %[a1], %[pb1], %[aw] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1\n\t"
-#define MPA_EX16_L \
-		"s_nop 0\n\t" \
+// The exclusive step behind the scan inside rows of 16 lanes, t2 = the horizontal gap's candidate, per group width.  NOP: the wait
+// states in front of the first DPP read of x -- s_nop 1 behind MPA_SCAN4, s_nop 0 behind MPA_SCAN4_L (one instruction further on).
+#define MPA_EX16_N(NOP) \
+		NOP \
 		"v_mov_b32_dpp %[ke], %[x] row_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
 		"v_pk_sub_i16 %[t2], %[ke], %[gojge] clamp\n\t"
-#define MPA_EX32_L \
-		"s_nop 0\n\t" \
+#define MPA_EX32_N(NOP) \
+		NOP \
 		"v_mov_b32_dpp %[ke], %[x] row_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
 		"v_mov_b32_dpp %[kc], %[x] row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
 		"v_pk_max_i16 %[t2], %[ke], %[kc]\n\t" \
 		"v_pk_sub_i16 %[t2], %[t2], %[gojge] clamp\n\t"
-#define MPA_EX64_L \
+#define MPA_EX16   MPA_EX16_N(MPA_NOP1)
+#define MPA_EX16_L MPA_EX16_N(MPA_NOP0)
+#define MPA_EX32   MPA_EX32_N(MPA_NOP1)
+#define MPA_EX32_L MPA_EX32_N(MPA_NOP0)
+// 64 lanes: the scan goes on across the rows of 16 lanes.  F15, F31: what fills the slot between each fill of t2 and the DPP move
+// that reads x behind it -- s_nop 0; nothing in front of the first move behind MPA_SCAN4_L; or, in the wide rows, the preset of
+// lane 0 of the two registers that the wave_shr:1 moves leave untouched there (the left neighbour's carry and H).
+#define MPA_XROW(F15, F31) \
 		"v_mov_b32 %[t2], 0x80008000\n\t" \
+		F15 \
 		"v_mov_b32_dpp %[t2], %[x] row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
 		"v_pk_max_i16 %[x], %[x], %[t2]\n\t" \
 		"v_mov_b32 %[t2], 0x80008000\n\t" \
-		"s_nop 0\n\t" \
+		F31 \
 		"v_mov_b32_dpp %[t2], %[x] row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" \
-		"v_pk_max_i16 %[x], %[x], %[t2]\n\t" \
-		"s_nop 1\n\t" \
+		"v_pk_max_i16 %[x], %[x], %[t2]\n\t"
+#define MPA_EX64_F(F15, F31) \
+		MPA_XROW(F15, F31) \
+		MPA_NOP1 \
 		"v_mov_b32_dpp %[ke], %[x] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
 		"v_pk_sub_i16 %[t2], %[ke], %[gojge] clamp\n\t"
+#define MPA_EX64   MPA_EX64_F(MPA_NOP0, MPA_NOP0)
+#define MPA_EX64_L MPA_EX64_F(MPA_NONE, MPA_NOP0)
 // DUAL (one call of 65..128 columns in a wave: column c in the low half of lane c, column c + 64 in the high half of the same lane):
 // the gap scan's total over the low halves (lane 63) is the carry into every high half, and H of column 63 is the left neighbour
 // of column 64 (lane 0, high half); one v_readlane each (one wait state behind the VALU write of what it reads: gfx940 family),
 // the two scalar instructions that move the value into the high half sit in the DPP move's wait states.
-#define MPA_EX64_LD \
-		"v_mov_b32 %[t2], 0x80008000\n\t" \
-		"v_mov_b32_dpp %[t2], %[x] row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
-		"v_pk_max_i16 %[x], %[x], %[t2]\n\t" \
-		"v_mov_b32 %[t2], 0x80008000\n\t" \
-		"s_nop 0\n\t" \
-		"v_mov_b32_dpp %[t2], %[x] row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" \
-		"v_pk_max_i16 %[x], %[x], %[t2]\n\t" \
-		"s_nop 0\n\t" \
-		"v_readlane_b32 %[st], %[x], 63\n\t" \
+#define MPA_CARRY63(V) \
+		"v_readlane_b32 %[st], " V ", 63\n\t" \
 		"s_lshl_b32 %[st], %[st], 16\n\t" \
-		"s_or_b32 %[st], %[st], 0x8000\n\t" \
+		"s_or_b32 %[st], %[st], 0x8000\n\t"
+#define MPA_EX64_DUAL(F15) \
+		MPA_XROW(F15, MPA_NOP0) \
+		MPA_NOP0 \
+		MPA_CARRY63("%[x]") \
 		"v_mov_b32_dpp %[ke], %[x] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
 		"v_pk_max_i16 %[t2], %[ke], %[st]\n\t" \
 		"v_pk_sub_i16 %[t2], %[t2], %[gojge] clamp\n\t"
-#define MPA_FIN_HS64_LD \
-		"v_pk_max_i16 %[h], %[h], %[t2]\n\t" \
-		"s_nop 0\n\t" \
-		"v_readlane_b32 %[st], %[h], 63\n\t" \
-		"s_lshl_b32 %[st], %[st], 16\n\t" \
-		"s_or_b32 %[st], %[st], 0x8000\n\t" \
-		"v_mov_b32_dpp %[hs3], %[h] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
-		"v_writelane_b32 %[hs3], %[st], 0\n\t"
-#define MPA_ROW_TAIL_LD(Hr2, Hs2, Dr2, Hs3, M3) \
-	asm volatile(MPA_SCAN4_L MPA_EX64_LD MPA_FIN_HS64_LD "v_pk_max_i16 %[m3], %[h], %[hs3]" \
-		: [x] "+v"(x), [h] "+v"(h), [k0] "+v"(k0), [k1] "+v"(k1), [k2] "+v"(k2), [k3] "+v"(k3), [ke] "+v"(ke), [hs3] "+v"(Hs3), \
-		  [t2] "=&v"(tA_), [hDn] "=&v"(hDn), [a0] "=&v"(a0), [a1] "=&v"(a1), [m3] "=&v"(M3), [drn] "=&v"(drn), [dDn] "=&v"(dDn), [st] "=&s"(stmp) \
-		: [hr2] "v"(Hr2), [dr2] "v"(Dr2), [gei] "v"(rnext.z), [s0] "v"(sraw0), [s1] "v"(sraw1), [hs2] "v"(Hs2), [pb0] "v"(pb0), [pb1] "v"(pb1), [aw] "v"(rnn.w), \
-		  [gojge] "v"(gojge), [go] "s"(goP), [sel] "s"(sel_lo) \
-		: "scc")
+// the final H; in a score row the vote clamp behind it (which is also the wait state of what reads h next)
+#define MPA_HMAX "v_pk_max_i16 %[h], %[h], %[t2]\n\t"
+#define MPA_FIN \
+		MPA_HMAX \
+		"v_pk_min_i16 %[vt], %[h], %[gl]\n\t" \
+		"v_pk_max_i16 %[vt], %[vt], %[tl]\n\t"
+// H shifted by one column, per group width, and M
+#define MPA_HS16 "v_mov_b32_dpp %[hs3], %[h] row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+#define MPA_HS32 "v_mov_b32_dpp %[hs3], %[h] wave_shr:1 row_mask:0xb bank_mask:0xf\n\tv_mov_b32_dpp %[hs3], %[h] row_shr:1 row_mask:0x4 bank_mask:0xf\n\t"
+#define MPA_HS64 "v_mov_b32_dpp %[hs3], %[h] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+#define MPA_HS64_DUAL MPA_CARRY63("%[h]") MPA_HS64 "v_writelane_b32 %[hs3], %[st], 0\n\t"
+#define MPA_M3 "v_pk_max_i16 %[m3], %[h], %[hs3]"
+
+// The tails' operands.  The order of a constraint list is part of what the compiler sees, so a tail's own operands go where they
+// always stood (KC, VT, MORE), not at the end.  What every tail has:
+#define MPA_OPS_SCAN_RW [x] "+v"(x), [h] "+v"(h), [k0] "+v"(k0), [k1] "+v"(k1), [k2] "+v"(k2), [k3] "+v"(k3), [ke] "+v"(ke),
+#define MPA_OPS_SCAN_W [t2] "=&v"(tA_), [hDn] "=&v"(hDn), [a0] "=&v"(a0), [a1] "=&v"(a1),
+#define MPA_OPS_SCAN_R(Hs2) [gei] "v"(rnext.z), [s0] "v"(sraw0), [s1] "v"(sraw1), [hs2] "v"(Hs2), [pb0] "v"(pb0), [pb1] "v"(pb1), [aw] "v"(rnn.w), [gojge] "v"(gojge),
+// the score rows' set (the D state updated in place) and the LITE rows' set (dr2 read only; drn, dDn out):
+#define MPA_SCORE_OUTS(Dr2, Hs3, M3, KC, VT) \
+		MPA_OPS_SCAN_RW KC [dr2] "+v"(Dr2), [hs3] "+v"(Hs3), MPA_OPS_SCAN_W VT [m3] "=&v"(M3)
+#define MPA_SCORE_INS(Hr2, Hs2, MORE) \
+		[hr2] "v"(Hr2), MPA_OPS_SCAN_R(Hs2) MORE [go] "s"(goP), [sel] "s"(sel_lo)
+#define MPA_LITE_OUTS(Hs3, M3, KC) \
+		MPA_OPS_SCAN_RW KC [hs3] "+v"(Hs3), MPA_OPS_SCAN_W [m3] "=&v"(M3), [drn] "=&v"(drn), [dDn] "=&v"(dDn)
+#define MPA_LITE_INS(Hr2, Hs2, Dr2, MORE) \
+		[hr2] "v"(Hr2), [dr2] "v"(Dr2), MPA_OPS_SCAN_R(Hs2) MORE [go] "s"(goP), [sel] "s"(sel_lo)
+// and what only some tails have: the fill register of MPA_EX32's row_bcast:15 (kept, so declared by every tail that takes an
+// EX parameter), the vote, the wide rows' carry and H from the left.  DUAL tails append the scalar temporary and clobber scc.
+#define MPA_OPS_KC [kc] "+v"(kc),
+#define MPA_OPS_VT [vt] "=&v"(vt),
+#define MPA_OPS_VOTE [gl] "v"(GvL), [tl] "v"(TvL),
+#define MPA_OPS_LEFT(CX, CH) [cx] "v"(CX), [ch] "v"(CH),
+#define MPA_OPS_ST [st] "=&s"(stmp)
+
+// score rows: G = 16, 32, 64 (EX, HS of that width), and DUAL with the vote and the two carries
+#define MPA_ROW_TAIL(EX, HS, Hr2, Hs2, Dr2, Hs3, M3) \
+	asm volatile(MPA_SCAN4 EX MPA_FIN HS MPA_M3 \
+		: MPA_SCORE_OUTS(Dr2, Hs3, M3, MPA_OPS_KC, MPA_OPS_VT) : MPA_SCORE_INS(Hr2, Hs2, MPA_OPS_VOTE))
+#define MPA_ROW_TAIL_D(Hr2, Hs2, Dr2, Hs3, M3) \
+	asm volatile(MPA_SCAN4 MPA_EX64_DUAL(MPA_NOP0) MPA_FIN MPA_HS64_DUAL MPA_M3 \
+		: MPA_SCORE_OUTS(Dr2, Hs3, M3, MPA_NONE, MPA_OPS_VT), MPA_OPS_ST : MPA_SCORE_INS(Hr2, Hs2, MPA_OPS_VOTE) : "scc")
+// LITE rows: no vote, so the wait states in front of HS are idle
 #define MPA_ROW_TAIL_L(EX, HS, Hr2, Hs2, Dr2, Hs3, M3) \
-	asm volatile(MPA_SCAN4_L EX "v_pk_max_i16 %[h], %[h], %[t2]\n\ts_nop 1\n\t" HS "v_pk_max_i16 %[m3], %[h], %[hs3]" \
-		: [x] "+v"(x), [h] "+v"(h), [k0] "+v"(k0), [k1] "+v"(k1), [k2] "+v"(k2), [k3] "+v"(k3), [ke] "+v"(ke), [kc] "+v"(kc), [hs3] "+v"(Hs3), \
-		  [t2] "=&v"(tA_), [hDn] "=&v"(hDn), [a0] "=&v"(a0), [a1] "=&v"(a1), [m3] "=&v"(M3), [drn] "=&v"(drn), [dDn] "=&v"(dDn) \
-		: [hr2] "v"(Hr2), [dr2] "v"(Dr2), [gei] "v"(rnext.z), [s0] "v"(sraw0), [s1] "v"(sraw1), [hs2] "v"(Hs2), [pb0] "v"(pb0), [pb1] "v"(pb1), [aw] "v"(rnn.w), \
-		  [gojge] "v"(gojge), [go] "s"(goP), [sel] "s"(sel_lo))
+	asm volatile(MPA_SCAN4_L EX MPA_HMAX MPA_NOP1 HS MPA_M3 \
+		: MPA_LITE_OUTS(Hs3, M3, MPA_OPS_KC) : MPA_LITE_INS(Hr2, Hs2, Dr2, MPA_NONE))
+#define MPA_ROW_TAIL_LD(Hr2, Hs2, Dr2, Hs3, M3) \
+	asm volatile(MPA_SCAN4_L MPA_EX64_DUAL(MPA_NONE) MPA_HMAX MPA_NOP0 MPA_HS64_DUAL MPA_M3 \
+		: MPA_LITE_OUTS(Hs3, M3, MPA_NONE), MPA_OPS_ST : MPA_LITE_INS(Hr2, Hs2, Dr2, MPA_NONE) : "scc")
+// Wide rows (ext_wide_body; lite_wide_body in dp_lite_wide.hip): one column per lane, a wave's left neighbour is another wave.
+// Its carry of the gap scan CX and its H of the column before this wave's first, CH, enter through LANE 0 only: CX folded into
+// the scan input, and both preset in the registers that the wave_shr:1 moves leave untouched in lane 0 (see ext_wide_body).
+#define MPA_ROW_TAIL_WX(SCAN, OUTS, INS) \
+	asm volatile("v_pk_max_i16 %[x], %[x], %[cx]\n\t" \
+		SCAN MPA_EX64_F("v_mov_b32 %[ke], %[cx]\n\t", "v_mov_b32 %[hs3], %[ch]\n\t") MPA_HMAX MPA_NOP1 MPA_HS64 MPA_M3 \
+		: OUTS : INS)
+#define MPA_ROW_TAIL_W(Hr2, Hs2, Dr2, Hs3, M3, CX, CH) \
+	MPA_ROW_TAIL_WX(MPA_SCAN4, MPA_SCORE_OUTS(Dr2, Hs3, M3, MPA_NONE, MPA_NONE), MPA_SCORE_INS(Hr2, Hs2, MPA_OPS_LEFT(CX, CH)))
+#define MPA_ROW_TAIL_WL(Hr2, Hs2, Dr2, Hs3, M3, CX, CH) \
+	MPA_ROW_TAIL_WX(MPA_SCAN4_L, MPA_LITE_OUTS(Hs3, M3, MPA_NONE), MPA_LITE_INS(Hr2, Hs2, Dr2, MPA_OPS_LEFT(CX, CH)))
 // the row's nibble (D | A << 1 | B << 2 | C << 3 in bits 0..3 of each half) from the signs of the four differences, pushed into the
 // three-row accumulator (FIRST: the row opens a new word)
 #define MPA_NIBBLE(LAST_OP) \
@@ -1121,13 +951,6 @@ __device__ __forceinline__ void ext_narrow(const ExtArgs &a, const ExtWave *wvp,
 	}
 }
 
-// One launch for the three narrow shapes (16 / 32 / 64 lanes per call): wave b of the launch belongs to the class whose
-// range of wave descriptors contains it.  Fewer, larger launches matter because every concurrently running kernel
-// occupies a hardware queue and a stream of batches keeps several rounds in flight (dp_exec.hip).
-struct NarrowMap { int32_t first[4], cnt[4]; };
-
-
-
 // ------------------------------------------------------------------------------------------------
 // K1-wide: extension calls wider than 64 columns.  One workgroup of NW waves per pair of calls (the two
 // int16 halves); wave w owns columns [64w, 64w+64) and runs ONE ROW BEHIND wave w-1 (a wavefront over
@@ -1193,29 +1016,6 @@ static_assert(EXT_WIDE_LDS(2) % 16 == 0 && EXT_WIDE_LDS(4) % 16 == 0 && (2 * 64 
 static_assert(EXT_WIDE_RING % 12 == 0 && EXT_WIDE_XIN % 48 == 0 && EXT_WIDE_KROWS % 12 == 0 && EXT_WIDE_KROWS >= 64 + 12 + 12 + 3, "rings in whole 12-row blocks; the key ring holds a flush of 64 rows, a block, and the first wave's lead");
 typedef uint32_t v2u __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) v2u *lds_u2p;
-#define MPA_ROW_TAIL_W(Hr2, Hs2, Dr2, Hs3, M3, CX, CH) \
-	asm volatile( \
-		"v_pk_max_i16 %[x], %[x], %[cx]\n\t" \
-		MPA_SCAN4 \
-		"v_mov_b32 %[t2], 0x80008000\n\t" \
-		"v_mov_b32 %[ke], %[cx]\n\t" \
-		"v_mov_b32_dpp %[t2], %[x] row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
-		"v_pk_max_i16 %[x], %[x], %[t2]\n\t" \
-		"v_mov_b32 %[t2], 0x80008000\n\t" \
-		"v_mov_b32 %[hs3], %[ch]\n\t" \
-		"v_mov_b32_dpp %[t2], %[x] row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" \
-		"v_pk_max_i16 %[x], %[x], %[t2]\n\t" \
-		"s_nop 1\n\t" \
-		"v_mov_b32_dpp %[ke], %[x] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
-		"v_pk_sub_i16 %[t2], %[ke], %[gojge] clamp\n\t" \
-		"v_pk_max_i16 %[h], %[h], %[t2]\n\t" \
-		"s_nop 1\n\t" \
-		"v_mov_b32_dpp %[hs3], %[h] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
-		"v_pk_max_i16 %[m3], %[h], %[hs3]" \
-		: [x] "+v"(x), [h] "+v"(h), [k0] "+v"(k0), [k1] "+v"(k1), [k2] "+v"(k2), [k3] "+v"(k3), [ke] "+v"(ke), [dr2] "+v"(Dr2), [hs3] "+v"(Hs3), \
-		  [t2] "=&v"(tA_), [hDn] "=&v"(hDn), [a0] "=&v"(a0), [a1] "=&v"(a1), [m3] "=&v"(M3) \
-		: [hr2] "v"(Hr2), [gei] "v"(rnext.z), [s0] "v"(sraw0), [s1] "v"(sraw1), [hs2] "v"(Hs2), [pb0] "v"(pb0), [pb1] "v"(pb1), [aw] "v"(rnn.w), \
-		  [gojge] "v"(gojge), [cx] "v"(CX), [ch] "v"(CH), [go] "s"(goP), [sel] "s"(sel_lo))
 template<int NWB, bool SPLIT>
 __device__ __forceinline__ void ext_wide_body(const ExtWideArgs &a, const int group_idx, const SplitPos pos, const WavePos wp)
 {
@@ -1264,6 +1064,8 @@ __device__ __forceinline__ void ext_wide_body(const ExtWideArgs &a, const int gr
 		} else nl[h] = 0, al[h] = 1, ncol[h] = 0, roff[h] = 0;
 	}
 	// profile columns of this wave: global [22][pw] int16 -> LDS [column][amino acid]
+	// (Same text in lite_wide_body, dp_lite_wide.hip, as is the ring prefill below; a shared inline function changes the code of
+	// k_dp_round, k_dp_worker and k_lite_wide -- tried: DESIGN.md section 5, file layout of the DP kernels.)
 	for (int h = 0; h < 2; ++h) {
 		char *dst = lds_prof + (size_t)(w * 2 + h) * 64 * PROF_COL_STRIDE;
 		if (tid[h] < 0) {   // (an empty half scores zero everywhere; its keys are never read)
@@ -1593,275 +1395,6 @@ __device__ __forceinline__ void ext_wide_body(const ExtWideArgs &a, const int gr
 		}
 	}
 }
-
-
-
-
-
-// ------------------------------------------------------------------------------------------------
-// The packed sweep of the checkpointed traceback for calls of 129..256 columns (class 12, dp_device.h): one workgroup of four
-// waves per PAIR of calls (the two int16 halves), one column per lane, wave w three rows behind wave w - 1 and the hand-over of
-// {scan carry, H of the wave's last column} through lane 0 and the LDS exchange slots, one barrier per step of three rows --
-// ext_wide_body<4, false> without the per-row keys and the x-drop replay (a global alignment sweeps every row), with the rows
-// of ext_narrow<G, true>: the four differences whose signs are the extension bits, the three-row nibble word and the checkpoints.
-// The two calls may differ in rows: the group iterates max_nl, a call past its end only produces bits and checkpoints nobody
-// reads; its score H(nl - 1, al - 1) is taken from the wave and lane that own column al - 1 behind the step that holds row nl - 1.
-// ------------------------------------------------------------------------------------------------
-#define LITE_WIDE_LDS ((size_t)MPA_LITE_WIDE_WAVES * 2 * 64 * PROF_COL_STRIDE + (EXT_WIDE_RING + 1) * 16 + 256 + 32 + (64 * 8 + 32))   /* bytes per group; a multiple of 16 */
-#define MPA_ROW_TAIL_WL(Hr2, Hs2, Dr2, Hs3, M3, CX, CH) \
-	asm volatile( \
-		"v_pk_max_i16 %[x], %[x], %[cx]\n\t" \
-		MPA_SCAN4_L \
-		"v_mov_b32 %[t2], 0x80008000\n\t" \
-		"v_mov_b32 %[ke], %[cx]\n\t" \
-		"v_mov_b32_dpp %[t2], %[x] row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
-		"v_pk_max_i16 %[x], %[x], %[t2]\n\t" \
-		"v_mov_b32 %[t2], 0x80008000\n\t" \
-		"v_mov_b32 %[hs3], %[ch]\n\t" \
-		"v_mov_b32_dpp %[t2], %[x] row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" \
-		"v_pk_max_i16 %[x], %[x], %[t2]\n\t" \
-		"s_nop 1\n\t" \
-		"v_mov_b32_dpp %[ke], %[x] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
-		"v_pk_sub_i16 %[t2], %[ke], %[gojge] clamp\n\t" \
-		"v_pk_max_i16 %[h], %[h], %[t2]\n\t" \
-		"s_nop 1\n\t" \
-		"v_mov_b32_dpp %[hs3], %[h] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
-		"v_pk_max_i16 %[m3], %[h], %[hs3]" \
-		: [x] "+v"(x), [h] "+v"(h), [k0] "+v"(k0), [k1] "+v"(k1), [k2] "+v"(k2), [k3] "+v"(k3), [ke] "+v"(ke), [hs3] "+v"(Hs3), \
-		  [t2] "=&v"(tA_), [hDn] "=&v"(hDn), [a0] "=&v"(a0), [a1] "=&v"(a1), [m3] "=&v"(M3), [drn] "=&v"(drn), [dDn] "=&v"(dDn) \
-		: [hr2] "v"(Hr2), [dr2] "v"(Dr2), [gei] "v"(rnext.z), [s0] "v"(sraw0), [s1] "v"(sraw1), [hs2] "v"(Hs2), [pb0] "v"(pb0), [pb1] "v"(pb1), [aw] "v"(rnn.w), \
-		  [gojge] "v"(gojge), [cx] "v"(CX), [ch] "v"(CH), [go] "s"(goP), [sel] "s"(sel_lo))
-__device__ __forceinline__ void lite_wide_body(const ExtArgs &a, const int group_idx, const WavePos wp)
-{
-	constexpr int NW = MPA_LITE_WIDE_WAVES, RING = EXT_WIDE_RING;
-	// per wave: profile of its 64 columns for both halves [2][64 columns][23] int16; then the record ring, the exchange slots
-	// [2 step parities][NW waves][3 rows] of {scan, H of the wave's last column}, 32 bytes of -inf and the dump area
-	char *lds_prof = wp.lds;
-	uint4 *ring = (uint4*)(lds_prof + NW * 2 * 64 * PROF_COL_STRIDE);  // [RING + 1] decoded records of both halves
-	uint2 *xch = (uint2*)(ring + RING + 1);                          // [2][16] slots: parity * 16 + 3 w + k
-	uint2 *xneg = xch + 32;                                          // [4] {-inf, -inf}
-	uint2 *xdump = xneg + 4;                                         // [64 + 4]
-	const int lane = wp.lane, w = wp.w;                              // w: wave index inside the group, scalar
-	const ExtWave *wvp = &a.waves[group_idx];
-	const DpConst c = a.c;
-	const uint32_t *recbase = a.rec + wvp->rec_base;
-
-	int32_t tid[2], end_row[2], al[2];
-	uint32_t roff[2];
-#pragma unroll
-	for (int h = 0; h < 2; ++h) {
-		tid[h] = __builtin_amdgcn_readfirstlane(wvp->task[h]);
-		if (tid[h] >= 0) {
-			const DTask *t = &a.tasks[tid[h]];
-			end_row[h] = __builtin_amdgcn_readfirstlane(t->nl) - 1, al[h] = t->al, roff[h] = (uint32_t)(t->rec_off - wvp->rec_base);
-		} else end_row[h] = -1, al[h] = 1, roff[h] = 0;
-	}
-	// profile columns of this wave: global [22][pw] int16 -> LDS [column][amino acid]
-	for (int h = 0; h < 2; ++h) {
-		char *dst = lds_prof + (size_t)(w * 2 + h) * 64 * PROF_COL_STRIDE;
-		if (tid[h] < 0) {   // (an empty half scores zero everywhere; nobody reads what it produces)
-			for (int k = lane; k < 64 * PROF_COL_STRIDE / 2; k += 64) ((uint16_t*)dst)[k] = 0;
-			continue;
-		}
-		const DTask *t = &a.tasks[tid[h]];
-		const int16_t *src = a.prof + t->prof_off;
-		for (int k = lane; k < 22 * 64; k += 64) {
-			const int aidx = k >> 6, cc = k & 63, gcc = w * 64 + cc;
-			*(int16_t*)(dst + cc * PROF_COL_STRIDE + aidx * PROF_AA_STRIDE) = gcc < t->pw ? src[aidx * t->pw + gcc] : (int16_t)NEG16;
-		}
-	}
-	if (wp.tg < 36) xch[wp.tg] = make_uint2(NEGP, NEGP);           // the exchange slots and, behind them, the slots of -inf
-	// record ring, filled by the leading wave (ext_wide_body's scheme): row r in slot (r + 44) % 48
-	const bool loader = w == 0 && lane < 12;
-	uint2 pf = make_uint2(0, 0);
-	if (w == 0 && lane < 16) {
-		const uint4 e = ring_entry(recbase[roff[0] + lane], recbase[roff[1] + lane]);
-		ring[lane < 4 ? lane + 44 : lane - 4] = e;
-		if (lane == 4) ring[RING] = e;
-	}
-	if (loader) pf = make_uint2(recbase[roff[0] + 16 + lane], recbase[roff[1] + 16 + lane]);
-	__syncthreads();
-
-	const int gc = w * 64 + lane;
-	const uint32_t jge = splat16(gc * c.ge), gojge = splat16(c.go + gc * c.ge);
-	const uint32_t goP = __builtin_amdgcn_readfirstlane(splat16(c.go)), fsP = __builtin_amdgcn_readfirstlane(splat16(c.fs));
-	const uint32_t ioP = pack16(tid[0] >= 0 ? a.tasks[tid[0]].io : 0, tid[1] >= 0 ? a.tasks[tid[1]].io : 0);
-	const uint32_t sel_lo = __builtin_amdgcn_readfirstlane(0x05040100u);
-	const uint32_t nb1 = __builtin_amdgcn_readfirstlane(0x00010001u), nb2 = __builtin_amdgcn_readfirstlane(0x00020002u),
-	               nb4 = __builtin_amdgcn_readfirstlane(0x00040004u), nb8 = __builtin_amdgcn_readfirstlane(0x00080008u);
-	// absolute LDS addresses: this lane's two profile columns; the exchange slot it reads / writes in a step of parity 0
-	const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)wp.lds;
-	const uint32_t pb0 = lds0 + (uint32_t)(((w * 2 + 0) * 64 + lane) * PROF_COL_STRIDE), pb1 = pb0 + 64 * PROF_COL_STRIDE;
-	const uint32_t xch0 = lds0 + (uint32_t)((char*)xch - wp.lds), xneg0 = lds0 + (uint32_t)((char*)xneg - wp.lds), xdump0 = lds0 + (uint32_t)((char*)xdump - wp.lds);
-	const uint32_t xwr_even = lane == 63 ? xch0 + (uint32_t)(3 * w) * 8 : xdump0 + (uint32_t)lane * 8;
-	const uint32_t xwr_flip = lane == 63 ? 128u : 0u;              // (the other parity's slots: + 16 slots)
-	const bool takes_left = lane == 0 && w > 0;
-
-	uint32_t Hr[3], Hs[3], Dr[3], dn[3], ac[3], M[3], A = NEGP, B = NEGP, C = NEGP;
-#pragma unroll
-	for (int k = 0; k < 3; ++k) Hr[k] = Hs[k] = Dr[k] = M[k] = NEGP;
-	uint32_t k0 = NEGP, k1 = NEGP, k2 = NEGP, k3 = NEGP, ke = NEGP;    // fill registers of the asm rows' scan: only ever written by DPP moves
-	if (gc == 0) Hs[2] = 0u, Hs[1] = splat16(-c.fs), Hs[0] = splat16(-c.fs);
-	{
-		const uint4 q0 = ring[44], q1 = ring[45];
-		dn[1] = q0.x, dn[0] = q1.x, ac[1] = q0.y, ac[0] = q1.y, dn[2] = ac[2] = 0;
-	}
-	const int32_t max_nl = __builtin_amdgcn_readfirstlane(wvp->max_nl);
-	uint4 rcur = ring[46], rnext = ring[47];                           // records of rows i and i + 1
-	uint32_t S = prof2s(pb0 + (rcur.w & 0xffff), pb1 + (rcur.w >> 16));   // profile scores of row i (generic rows)
-	bool have_hD = false;                                              // hD already holds row i's max(diagonal, D) (behind the asm rows)
-	uint32_t hD = NEGP;
-	// the three-row accumulator of nibbles, the difference that holds row i's D bit, the D state the precomputation for row i replaced
-	// (what a checkpoint wants), this wave's slice of the group's bit words and checkpoints (dp_device.h)
-	uint32_t acc = 0, dDc = 0, Dold = NEGP;
-	int32_t sh_;
-	uint32_t *lite_p = a.lite + wvp->lite_off + lite_wide_bit_at(2, gc, 0, &sh_);
-	const int64_t lite_step = lite_wide_bit_at(5, gc, 0, &sh_) - lite_wide_bit_at(2, gc, 0, &sh_);
-	auto checkpoint = [&](const int32_t i, const uint32_t d3) {        // top of row i = 2 + k * MPA_TB_BLOCK: slots 0, 1, 2 hold rows i-1, i-2, i-3
-		uint32_t *p = a.ckpt + wvp->ck_off + lite_wide_ckpt_at((i - 2) / MPA_TB_BLOCK, gc, 0, &sh_);
-		p[0] = Hr[0], p[64] = Hr[1], p[128] = Hr[2], p[192] = Dr[0], p[256] = Dr[1], p[320] = d3, p[384] = A, p[448] = B, p[512] = C;
-	};
-	// the score of a call whose last row is among the rows [i, i + 3) just swept: h0, h1, h2 = their H rows (slots 2, 1, 0; passed by
-	// value: a choice among the elements of Hr[] by a run-time index would move the array out of the registers)
-	auto scores = [&](const int32_t i, const uint32_t h0, const uint32_t h1, const uint32_t h2) {
-#pragma unroll
-		for (int h = 0; h < 2; ++h) {
-			const int32_t k = end_row[h] - i;
-			uint32_t v = h2;
-			v = k == 1 ? h1 : v, v = k == 0 ? h0 : v;
-			if (tid[h] >= 0 && (uint32_t)k < 3u && gc == al[h] - 1) a.score[tid[h]] = half16(v, h);
-		}
-	};
-	auto refill = [&](const int32_t i, const int rs) {                 // the leading wave, every twelfth row
-		if (loader) {
-			const uint4 e = ring_entry(pf.x, pf.y);
-			const int at = (rs + 12) % RING + lane;
-			ring[at] = e;
-			if (at == 0) ring[RING] = e;                                       // slot 0 again behind slot 47
-			pf = make_uint2(recbase[roff[0] + (uint32_t)i + 26 + lane], recbase[roff[1] + (uint32_t)i + 26 + lane]);
-		}
-	};
-	v2u cv[3];
-	uint32_t xwr = 0;
-	auto step_begin = [&](const int par) {                             // what the wave to the left produced for the step's three rows, in the previous step
-		uint32_t at = xneg0;
-		if (takes_left) at = xch0 + (uint32_t)(((par ^ 1) * 16 + 3 * (w - 1)) * 8);
-#pragma unroll
-		for (int k = 0; k < 3; ++k) cv[k] = *(lds_u2p)(uintptr_t)(at + 8 * k);
-		xwr = xwr_even + (par ? xwr_flip : 0u);
-	};
-	// the generic row (plain C++): the first twelve rows and what the blocks of asm rows leave over
-	auto row = [&](auto kc, const int32_t i, const int rs) {
-		constexpr int K = decltype(kc)::value;
-		constexpr int R1 = (3 - K) % 3, R2 = (4 - K) % 3, R3 = (5 - K) % 3;
-		if (K == 0 && i > 2 && (uint32_t)(i - 2) % MPA_TB_BLOCK == 0) checkpoint(i, have_hD ? Dold : Dr[R3]);
-		const uint32_t Snext = prof2s(pb0 + (rnext.w & 0xffff), pb1 + (rnext.w >> 16));
-		const uint4 rnn = ring[rs + K];                                    // record of row i + 2
-		dn[R3] = rcur.x, ac[R3] = rcur.y;                                  // donor[i+1], acceptor[i]
-		uint32_t h, t, u, dA, dB, dC;
-		if (have_hD) h = hD;
-		else {
-			h = p_adds(Hs[R3], S);
-			u = p_subs(Hr[R3], goP); dDc = p_subs(u, Dr[R3]); t = p_max(u, Dr[R3]);
-			t = p_subs(t, rcur.z); Dr[R3] = t; h = p_max(h, t);
-		}
-		u = p_subs(Hr[R1], ioP); t = p_subs(u, dn[R2]); dA = p_subs(t, A);
-		t = p_max(t, A); A = t; h = p_max(h, p_subs(t, ac[R3]));
-		u = p_subs(Hs[R1], ioP); t = p_subs(u, dn[R1]); dB = p_subs(t, B);
-		t = p_max(t, B); B = t; h = p_max(h, p_subs(t, ac[R2]));
-		t = p_subs(u, dn[R3]); dC = p_subs(t, C);
-		t = p_max(t, C); C = t; h = p_max(h, p_subs(t, ac[R1]));
-		{
-			const uint32_t nib = (dDc >> 15 & 0x00010001u) | (dA >> 14 & 0x00020002u) | (dB >> 13 & 0x00040004u) | (dC >> 12 & 0x00080008u);
-			acc = K == 0 ? nib : (acc << 4 | nib);
-			if (K == 2) *lite_p = acc, lite_p += lite_step;
-		}
-		t = p_max(p_max(Hr[R1], Hr[R2]), p_max(Hs[R1], Hs[R2]));
-		h = p_max(h, p_subs(t, fsP));
-		const uint32_t y = scan_max_pk<64>(p_max(p_adds(h, jge), cv[K].x));   // (the incoming carry through lane 0)
-		const uint32_t ex = shift1<64>(y, cv[K].x, lane);
-		h = p_max(h, p_subs(ex, gojge));
-		Hr[R3] = h, Hs[R3] = shift1<64>(h, cv[K].y, lane);
-		*(lds_u2p)(uintptr_t)(xwr + 8 * K) = v2u{ y, h };
-		if (i == 2 && gc == 0) Hs[R1] = NEGP, Hs[R2] = NEGP;
-		S = Snext;
-		rcur = rnext, rnext = rnn, have_hD = false;
-	};
-
-	// Wave w runs 3 w rows behind wave 0: one barrier per step of three rows, w barriers of delay first and NW-1-w at the end so
-	// that every wave passes the same number.  Step parity = (step + w) & 1.
-	for (int k = 0; k < w; ++k) lds_barrier();
-	{
-		int par = w & 1;
-		int32_t i = 2;
-		int rs = 0, rs12 = 0;                                              // (i - 2) % 48, % 12 at the top of a step
-		auto generic_step = [&](const int n_rows) {
-			if (w == 0 && rs12 == 0) refill(i, rs);
-			step_begin(par);
-			row(std::integral_constant<int, 0>(), i, rs);
-			if (n_rows > 1) row(std::integral_constant<int, 1>(), i + 1, rs);
-			if (n_rows > 2) row(std::integral_constant<int, 2>(), i + 2, rs);
-			if (n_rows < 3) *lite_p = acc << (4 * (3 - n_rows));               // (the sweep ends inside a word)
-			if ((uint32_t)(end_row[0] - i) < 3u || (uint32_t)(end_row[1] - i) < 3u) scores(i, Hr[2], Hr[1], Hr[0]);
-			lds_barrier();
-			i += 3, par ^= 1, rs = rs == RING - 3 ? 0 : rs + 3, rs12 = rs12 == 9 ? 0 : rs12 + 3;
-		};
-		while (i < 14 && i + 3 <= max_nl) generic_step(3);
-		// ---- the asm rows, in blocks of four steps (i = 2 + 12 k: the record ring is refilled and checkpoints are written at block starts only)
-		if (i + 12 <= max_nl) {
-			uint32_t tA_, tB_, tC_, h, x, hDn, a0, a1, dA, dB, dC, drn, dDn;
-			v2s sraw0, sraw1;                                              // (.x = a profile score; .y is never set: v_perm_b32 takes the low halves)
-			M[0] = p_max(Hr[0], Hs[0]), M[1] = p_max(Hr[1], Hs[1]);
-			{                                                              // row i's diagonal term and D state (slot R3 = 2)
-				const uint32_t u = p_subs(Hr[2], goP), t = p_max(u, Dr[2]);
-				dDc = p_subs(u, Dr[2]), Dold = Dr[2];
-				Dr[2] = p_subs(t, rcur.z);
-				hD = p_max(p_adds(Hs[2], S), Dr[2]);
-			}
-			sraw0.x = *(lds_s16p)(uintptr_t)(pb0 + (rnext.w & 0xffff)), sraw1.x = *(lds_s16p)(uintptr_t)(pb1 + (rnext.w >> 16));
-			uint4 rnn = ring[rs];                                          // record of row i + 2; from here on fetched a row before it is needed
-			do {
-				if (w == 0) refill(i, rs);
-				if ((uint32_t)(i - 2) % MPA_TB_BLOCK == 0) checkpoint(i, Dold);
-				const uint4 *rb = ring + rs;
-#pragma unroll 1
-				for (int st = 0; st < 4; ++st, rb += 3) {
-					step_begin(par);
-#define MPA_LW_ROW(K, R1, R2, R3, NIB) { \
-					MPA_ROW_HEAD_L(Hr[R1], Hs[R1], dn[R1], dn[R2], rcur.x, ac[R1], ac[R2], rcur.y, M[R1], M[R2]); \
-					dn[R3] = rcur.x, ac[R3] = rcur.y; \
-					MPA_ROW_TAIL_WL(Hr[R2], Hs[R2], Dr[R2], Hs[R3], M[R3], cv[K].x, cv[K].y); \
-					MPA_NIBBLE(NIB); \
-					Dold = Dr[R2], Dr[R2] = drn, dDc = dDn; \
-					if (K == 2) *lite_p = acc, lite_p += lite_step; \
-					{ v2s f0, f1; f0.x = *(lds_s16p)(uintptr_t)a0, f1.x = *(lds_s16p)(uintptr_t)a1; sraw0 = f0, sraw1 = f1; } \
-					rcur = rnext, rnext = rnn, rnn = rb[K + 1]; \
-					Hr[R3] = h, hD = hDn; \
-					*(lds_u2p)(uintptr_t)(xwr + 8 * K) = v2u{ x, h }; }
-					MPA_LW_ROW(0, 0, 1, 2, MPA_NIB_FIRST)
-					MPA_LW_ROW(1, 2, 0, 1, MPA_NIB_NEXT)
-					MPA_LW_ROW(2, 1, 2, 0, MPA_NIB_NEXT)
-#undef MPA_LW_ROW
-					if ((uint32_t)(end_row[0] - i) < 3u || (uint32_t)(end_row[1] - i) < 3u) scores(i, Hr[2], Hr[1], Hr[0]);
-					lds_barrier();
-					i += 3, par ^= 1;
-				}
-				rs = rs == RING - 12 ? 0 : rs + 12;
-			} while (i + 12 <= max_nl);
-			have_hD = true;
-		}
-		while (i + 3 <= max_nl) generic_step(3);
-		if (i < max_nl) generic_step(max_nl - i);
-	}
-	for (int k = w; k < NW - 1; ++k) lds_barrier();
-}
-// (a launch of its own on a side stream of the round, like the 512/1024-thread traceback classes: k_dp_round stays what it is)
-__global__ __launch_bounds__(MPA_LITE_WIDE_WAVES * 64) void k_lite_wide(ExtArgs a, int first_group)
-{
-	__shared__ __attribute__((aligned(16))) char lds[LITE_WIDE_LDS];
-	lite_wide_body(a, first_group + (int)blockIdx.x, whole_block(lds));
-}
-
 // ------------------------------------------------------------------------------------------------
 // K2: global alignment with traceback.  int32 arithmetic, one column per lane, one call per group of
 // G lanes; matrices wider than 64 columns are swept in column blocks (block-major), each block leaving
@@ -2112,238 +1645,6 @@ __device__ __forceinline__ void glob_narrow(const GlobArgs &a, const GlobWave &w
 	if (!EXT && !rz && tid >= 0 && nl < 3 && col == 0) a.score[tid] = NEG16;
 }
 
-// one launch for the narrow traceback shapes (classes 16 / 32 / 64 lanes and the block-major one), see k_ext_narrow
-template<bool WIDE>
-__global__ __launch_bounds__(64) void k_glob_narrow(GlobArgs a, NarrowMap m)
-{
-	int b = blockIdx.x;
-	extern __shared__ __attribute__((aligned(16))) uint32_t lds_raw[];
-	const WavePos wp = whole_block((char*)lds_raw);
-	if (b < m.cnt[0]) { glob_narrow<16, false, false, WIDE>(a, a.waves[m.first[0] + b], wp); return; }
-	b -= m.cnt[0];
-	if (b < m.cnt[1]) { glob_narrow<32, false, false, WIDE>(a, a.waves[m.first[1] + b], wp); return; }
-	b -= m.cnt[1];
-	if (b < m.cnt[2]) { glob_narrow<64, false, false, WIDE>(a, a.waves[m.first[2] + b], wp); return; }
-	b -= m.cnt[2];
-	glob_narrow<64, true, false, WIDE>(a, a.waves[m.first[3] + b], wp);
-}
-
-// Extension calls wider than 1024 columns: one wave per call, 64-column blocks swept one after the other (each all rows),
-// boundary records through HBM, per-row keys combined across blocks with 64-bit atomic maxima.
-// wg_min_blocks > 0 (MPA_DP_HUGE_WG): calls of that many column blocks or more are k_ext_huge_wg's, launched over the same list.
-template<bool WIDE>
-__global__ __launch_bounds__(64) void k_ext_huge(GlobArgs a, int32_t wg_min_blocks)
-{
-	extern __shared__ __attribute__((aligned(16))) uint32_t lds_raw[];
-	if (wg_min_blocks > 0) {
-		const int32_t tid = a.waves[blockIdx.x].task[0];
-		if (tid >= 0 && hwg::n_blocks(a.tasks[tid].ncol) >= wg_min_blocks) return;
-	}
-	glob_narrow<64, true, true, WIDE>(a, a.waves[blockIdx.x], whole_block((char*)lds_raw));
-}
-
-// The same sweep with one wave per column block (MPA_DP_HUGE_WG; schedule and LDS layout: ext_huge_wg_core.h).  W waves of one
-// workgroup own W neighbouring blocks of a pass; wave w runs one chunk of R rows behind wave w - 1, takes the boundary records of
-// that chunk from its neighbour's LDS ring and leaves its own in its ring, at the parity of the step; one workgroup barrier per
-// step, the same number for every wave, and nothing that polls or spins.  Only the two ends of a pass go through the call's
-// bnd[] rows in HBM, as every block of the one-wave kernel does.  Per row the arithmetic is glob_narrow<64, true, true, WIDE>'s,
-// operation for operation: the per-row keys, and so k_ext_replay's results, are the same bits.
-static_assert(hwg::WAVE_LDS == GLOB_NARROW_LDS, "ext_huge_wg_core.h: a wave's LDS area is the one-wave kernel's");
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4i *lds_v4p;
-template<bool WIDE>
-__device__ __forceinline__ void ext_huge_wg_body(const GlobArgs &a, const DTask &t, char *lds, const int lane, const int w)
-{
-	constexpr int G = 64;
-	int16_t *lds_prof = (int16_t*)(lds + hwg::wave_area(w));    // [22][64] for the wave's column block
-	const int col = lane;
-	const DpConst c = a.c;
-	const int32_t nl = t.nl, ncol = t.ncol, slen = ncol >> 3;
-	const int32_t nblk = hwg::n_blocks(ncol), npass = hwg::n_pass(nblk), nstep = hwg::n_step(nl);
-	const int32_t go = c.go, ge = c.ge, goe = (int16_t)(c.go + c.ge), io = t.io, fs = c.fs;
-	const uint32_t *rec = a.rec + t.rec_off;
-	unsigned long long *rowkey = a.rowkey64 + t.tb_off;
-	int4 *bnd = a.bnd + t.bnd_off;
-	const uint32_t go_s = splat16(go), io_s = splat16(io), fs_s = splat16(fs), ge_s = splat16(ge);
-	const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
-
-	for (int32_t p = 0; p < npass; ++p) {
-		// bnd[] rows of this pass's right end overwrite the ones its left end read: the stores of the pass before are drained, every
-		// wave has passed, and the CU's L1 (which may still hold lines of the earlier reads) is dropped before the first read
-		if (p > 0) {
-			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-			lds_barrier();
-			__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
-		}
-		const int32_t blk = hwg::block_of(p, w);
-		const bool have = blk < nblk;                               // (uniform over the wave; a wave without a block only passes the barriers)
-		const int32_t gc = blk * G + col;                           // global column of this lane
-		const bool live = have && gc < ncol;
-		const int ledge = hwg::left_edge(blk, w), redge = have ? hwg::right_edge(blk, w, nblk) : (int)hwg::EDGE_NONE;
-		const bool first_blk = blk == 0;
-		uint32_t *ring = (uint32_t*)(lds_prof + 22 * G);
-		const bool loader = col < 16;
-		uint32_t pf = 0;
-		if (have) {
-			// stage this block's profile columns
-			wave_sync();
-			const int16_t *src = a.prof + t.prof_off;
-			for (int k = lane; k < 22 * G; k += 64) {
-				int aidx = k / G, cc = k - aidx * G, gcc = blk * G + cc;
-				lds_prof[k] = gcc < t.pw ? src[aidx * t.pw + gcc] : (int16_t)NEG16;
-			}
-			wave_sync();
-			// record ring (see k_ext): rows [0,16) now, rows [16,32) wait in pf, then 16 rows per refill
-			if (loader) ring[col] = rec[col], pf = rec[16 + col];
-			wave_sync();
-		}
-		const int32_t seg = slen > 0 ? gc / slen : 0;
-		const bool seg_start = slen > 0 && gc % slen == 0;
-		const int32_t cge = gc * ge, yoff = seg * SEG_BIG + cge;
-		GlobState gs;
-		glob_state_init(gs, have ? ring[0] : 0u, have ? ring[1] : 0u, first_blk && col == 0, fs);
-		const char *profb = (const char*)(lds_prof + col);      // + byte0(record) * G = this lane's score for the row's amino acid
-		uint32_t r[3];                                          // records of rows i, i+1 (and, once fetched, i+2) at slot row mod 3
-		r[2] = have ? ring[2] : 0u, r[0] = have ? ring[3] : 0u, r[1] = 0;
-		const bool carry_src = seg_start && gc >= slen;         // lanes that feed the carry scan
-
-		// LDS addresses (explicit address space: ds_read_b128 / ds_write_b128, never a flat access that would have to pick its path
-		// at run time) of the chunk's records in the left neighbour's ring, for the chunk's first row, and of this wave's own
-		uint32_t rd = lds0, wr = lds0;
-		int32_t i0 = 0;
-		auto row = [&](auto kc, const int32_t i) {
-			constexpr int K = decltype(kc)::value;
-			if ((i & 15) == 12) { if (loader) ring[((i + 4) & 31) + col] = pf, pf = rec[i + 20 + col]; }   // rows [i+4, i+20) published, the next 16 requested
-			r[(K + 2) % 3] = ring[(i + 2) & 31];                           // two rows ahead: LDS latency is off the critical path
-			const uint32_t rcur = r[K];
-			const char *sp = profb + (rcur & 0xff) * G;
-			const uint32_t S = prof2(sp, sp);
-			// boundary record of the block to the left
-			int4 bin = make_int4(NEG32, NEG32, (int)NEGP, NEG16);
-			if (ledge == hwg::EDGE_LDS) { const v4i b = *(lds_v4p)(uintptr_t)(rd + (uint32_t)(i - i0) * hwg::BND_BYTES); bin = make_int4(b.x, b.y, b.z, b.w); }
-			else if (ledge == hwg::EDGE_HBM) bin = bnd[i];
-			const int32_t Hb = lo16((uint32_t)bin.z), h1b = hi16((uint32_t)bin.z), I1b = bin.w;
-
-			uint32_t dD, dA, dB, dC;
-			const int32_t knon = glob_cands<K, WIDE>(gs, rcur, S, go_s, io_s, fs_s, dD, dA, dB, dC, ge_s);
-			const int32_t nonI = knon >> 16;
-			const int32_t py = scan_max_i32<G>(nonI + yoff);
-			int32_t pex = shift1_i32<G>(py, NEG32, lane);
-			pex = imax(pex, bin.x);
-			const int32_t py_tot = imax(bin.x, __shfl(py, G - 1));
-			const int32_t I1 = imax(pex - yoff - go, NEG16);
-			const int32_t kbest = imax(knon, st_key((uint32_t)I1, 1));
-			const int32_t h1 = kbest >> 16;
-			const int32_t hl_raw = shift1_i32<G>(h1, first_blk ? NEG16 : h1b, lane);
-			const int32_t il_raw = shift1_i32<G>(I1, first_blk ? NEG16 : I1b, lane);
-			const int32_t dI = seg_start ? 0 : s_sub(hl_raw, go) - il_raw;
-			(void)dI;
-			const int32_t E = imax(s_sub(hl_raw, goe), s_sub(il_raw, ge));
-			const int32_t z = carry_src ? E + cge : NEG32;
-			int32_t pz = scan_max_i32<G>(z);
-			pz = imax(pz, bin.y);
-			const int32_t Gc = imax(pz - cge, NEG16);
-			const int32_t h = imax(h1, Gc);
-			// key of this block's row: best (H + end bonus) among the live columns, ties to the smallest column
-			const int32_t hb = h + (gc == t.al - 1 ? c.end_bonus : 0);
-			const uint32_t kk = reduce_max_u32(live ? ((uint32_t)(imax(hb, NEG16) + 32768) << 6) | (63u - (uint32_t)lane) : 0u);
-			if (lane == 63 && kk != 0)
-				atomicMax(&rowkey[i], (unsigned long long)(kk >> 6) << 32 | (0xffffffffu - (uint32_t)(blk * 64 + 63 - (int32_t)(kk & 63))));
-			// boundary record for the block to the right
-			if (col == G - 1) {
-				const int4 out = make_int4(py_tot, pz, (int)pack16(h, h1), I1);
-				if (redge == hwg::EDGE_LDS) *(lds_v4p)(uintptr_t)(wr + (uint32_t)(i - i0) * hwg::BND_BYTES) = v4i{ out.x, out.y, out.z, out.w };
-				else if (redge == hwg::EDGE_HBM) bnd[i] = out;
-			}
-			const uint32_t hsp = spl(h);
-			gs.H[K] = hsp;
-			gs.Hs[K] = shift1<G>(hsp, first_blk ? NEGP : splat16(Hb), lane);
-			if (K == 2) { if (i == 2 && first_blk && col == 0) gs.Hs[0] = NEGP, gs.Hs[1] = NEGP; }
-		};
-		for (int32_t s = 0; s < nstep; ++s) {
-			const int32_t ch = have ? hwg::chunk_at(s, w, nl) : -1;
-			if (ch >= 0) {
-				i0 = hwg::chunk_first_row(ch);
-				const int32_t i1 = hwg::chunk_end_row(ch, nl);
-				if (ledge == hwg::EDGE_LDS) rd = lds0 + (uint32_t)hwg::ring_read(w, s, i0);
-				wr = lds0 + (uint32_t)hwg::ring_write(w, s, i0);
-				for (int32_t i = i0; i < i1; i += 3) {
-					row(std::integral_constant<int, 2>(), i);
-					if (i + 1 < i1) row(std::integral_constant<int, 0>(), i + 1);
-					if (i + 2 < i1) row(std::integral_constant<int, 1>(), i + 2);
-				}
-			}
-			lds_barrier();
-		}
-	}
-}
-template<bool WIDE>
-__global__ __launch_bounds__(hwg::W * 64) void k_ext_huge_wg(GlobArgs a)
-{
-	__shared__ __attribute__((aligned(16))) char lds[hwg::LDS_BYTES];
-	const int32_t tid = a.waves[blockIdx.x].task[0];
-	if (tid < 0) return;
-	const DTask t = a.tasks[tid];
-	if (!hwg::takes_wg(t.ncol)) return;                             // (uniform over the workgroup, before its first barrier)
-	ext_huge_wg_body<WIDE>(a, t, lds, (int)(threadIdx.x & 63), __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)));
-}
-
-// nasw-sse.c:423-443 replayed over per-row keys ((row max + 32768) << 32 | ~column): best row under the length penalty,
-// x-drop stop.  One wave per call.
-__global__ __launch_bounds__(64) void k_ext_replay(const DTask *tasks, const int32_t *list, int32_t n_list, const unsigned long long *rowkey64,
-                                                   ExtOut *out, DpConst c, PenTable pen)
-{
-	MPA_SHORT_KERNEL();
-	if ((int32_t)blockIdx.x >= n_list) return;
-	const int32_t tid = list[blockIdx.x];
-	const DTask t = tasks[tid];
-	const int lane = threadIdx.x;
-	const unsigned long long *key = rowkey64 + t.tb_off;
-	const int64_t pen_len = 3 * (int64_t)t.al;
-	int32_t G = INT32_MIN, best_i = -1, best_sc = INT32_MIN, best_col = -1;
-	bool stopped = false;
-	for (int32_t base = 2; base < t.nl && !stopped; base += 64) {
-		const int32_t i = base + lane;
-		const bool ok = i < t.nl;
-		const unsigned long long kv = ok ? key[i] : 0ULL;
-		int32_t pv = 0;
-		{
-			const int64_t x = (int64_t)i - pen_len;
-			int k = 0;
-			while (k + 1 < MPA_PEN_MAX && x >= (int64_t)pen.x[k + 1]) ++k;
-			pv = pen.val[k];
-		}
-		const int32_t sc = (int32_t)(kv >> 32) - 32768;
-		const int32_t v = ok ? sc - pv : INT32_MIN;
-		int32_t m = v;
-#pragma unroll
-		for (int off = 1; off < 64; off <<= 1) { const int32_t o = __shfl_up(m, off); if (lane >= off) m = imax(m, o); }
-		m = imax(m, G);
-		const int32_t up = __shfl_up(m, 1);
-		const bool imp = ok && v > (lane == 0 ? G : up);
-		const bool brk = ok && (int64_t)m - (int64_t)v > c.xdrop;
-		const uint64_t bm = __ballot(brk);
-		const int first_brk = bm ? __ffsll((unsigned long long)bm) - 1 : 64;
-		const uint64_t im = __ballot(imp) & (first_brk >= 63 ? ~0ULL : ((2ULL << first_brk) - 1));
-		if (im) {
-			const int last = 63 - __clzll((long long)im);
-			best_i = base + last;
-			G = __shfl(v, last);
-			best_sc = __shfl(sc, last);
-			best_col = (int32_t)(0xffffffffu - (uint32_t)__shfl((int)(uint32_t)kv, last));
-		}
-		if (bm) stopped = true;
-	}
-	if (lane == 0) {
-		ExtOut o;
-		o.nt_len = best_i + 1;
-		o.aa_len = best_i < 0 ? 0 : best_col + 1;
-		o.score = best_sc;
-		o.flags = (best_i >= 0 && best_col >= t.al) ? 1 : 0;
-		out[tid] = o;
-	}
-}
-
 // ------------------------------------------------------------------------------------------------
 // K2-wide: the same traceback DP for matrices of 65..64*NW columns with one wave per 64-column block, the
 // waves skewed by one row (see k_ext_wide); the boundary record travels through LDS instead of HBM and
@@ -2450,13 +1751,6 @@ __device__ __forceinline__ void glob_wide_body(const GlobArgs &a, const GlobWave
 	for (int k = w; k < NW - 1; ++k) lds_barrier();
 	if (nl >= 3 && gc == t.al - 1) { const int k = (nl - 1) % 3; a.score[tid] = lo16(k == 0 ? gs.H[0] : k == 1 ? gs.H[1] : gs.H[2]); }
 	if (nl < 3 && wp.tg == 0) a.score[tid] = NEG16;
-}
-
-template<int NW, bool WIDE>
-__global__ __launch_bounds__(NW * 64) void k_glob_wide(GlobArgs a)
-{
-	extern __shared__ __attribute__((aligned(16))) uint32_t lds_raw[];
-	glob_wide_body<NW, WIDE>(a, a.waves[blockIdx.x], whole_block((char*)lds_raw));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2738,252 +2032,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 		}
 	}
 	if ((tid & 63) == 0 && atomicAdd(&seen[3], 1) == 3) atomicSub(&pool->ctl.alive, 1);   // the last wave to leave takes the workgroup off the count
-}
-
-// ------------------------------------------------------------------------------------------------
-// traceback walk (ns_backtrack nasw-sse.c:40-89), one WAVE per call.
-//
-// The reference follows one cell per step.  The path is made of runs that move in a fixed direction while
-// a bit of the traceback word stays set (match runs on the diagonal, gap/intron extensions along a column
-// or a row), so the 64 lanes fetch the next 64 cells of the current direction at once, a ballot finds where
-// the run ends, and the whole run is emitted as one CIGAR operation.  A 50 kb intron costs ~800 dependent
-// memory round trips instead of 50 000.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_backtrack(const DTask *tasks, const int32_t *list, int32_t n_list, const uint16_t *tbpool, uint32_t *cigpool, int32_t *n_cigar)
-{
-	MPA_SHORT_KERNEL();
-	if ((int32_t)blockIdx.x >= n_list) return;
-	const int32_t tid = list[blockIdx.x];
-	const DTask t = tasks[tid];
-	const uint16_t *tb = tbpool + t.tb_off;
-	uint32_t *cig = cigpool + t.cig_off;
-	const int32_t ncol = t.ncol, cap = t.cig_cap, lane = threadIdx.x;
-	int32_t i = t.nl - 1, j = t.al - 1, carry = 0, n = 0;
-	// the CIGAR operation being accumulated (ns_push_cigar merges equal neighbours except F/G, nasw.h:141-152)
-	int32_t cur_op = -1, cur_len = 0;
-	auto push = [&](int32_t op, int32_t len) {
-		if (cur_op == op && op != 10 && op != 11) { cur_len += len; return; }
-		if (cur_op >= 0) { if (lane == 0 && n < cap) cig[n] = (uint32_t)cur_len << 4 | (uint32_t)cur_op; ++n; }
-		cur_op = op, cur_len = len;
-	};
-	auto state_of = [](int32_t w) { return (w >> 9 & 1) ? 1 : (w & 0xf); };   // a cell raised by the cross-lane I counts as I
-	while (i >= 2 && j >= 0) {
-		int32_t st = carry;
-		if (st == 0) {                                           // fresh cell: its own state decides the direction
-			const int32_t w0 = tb[(int64_t)i * ncol + j];
-			st = state_of(w0);
-		}
-		if (st == 0) {                                           // run of matches on the diagonal (i-3l, j-l)
-			const int32_t ii = i - 3 * lane, jj = j - lane;
-			const bool ok = ii >= 2 && jj >= 0;
-			const int32_t w = ok ? tb[(int64_t)ii * ncol + jj] : 0xf;
-			const uint64_t stop = __ballot(!ok || state_of(w) != 0);
-			const int32_t run = stop ? __ffsll((unsigned long long)stop) - 1 : 64;
-			push(0, run), i -= 3 * run, j -= run, carry = 0;
-		} else if (st <= 5) {                                    // extension runs: I along the row, D/N/U/V along the column
-			const int32_t di = st == 1 ? 0 : st == 2 ? 3 : 1, dj = st == 1 ? 1 : 0;
-			const int32_t ii = i - di * lane, jj = j - dj * lane;
-			const bool ok = ii >= 2 && jj >= 0;
-			const int32_t w = ok ? tb[(int64_t)ii * ncol + jj] : 0;
-			const bool ext = ok && (w >> (st + 3) & 1);
-			const uint64_t inval = __ballot(!ok), noext = __ballot(!ext);
-			// cells are consumed up to and including the first one whose extension bit is clear; a cell outside
-			// the matrix ends the walk before it is consumed
-			const int32_t first_noext = noext ? __ffsll((unsigned long long)noext) - 1 : 64;
-			const int32_t first_inval = inval ? __ffsll((unsigned long long)inval) - 1 : 64;
-			int32_t run;
-			bool closed;                                          // did the run meet a cell with the extension bit clear?
-			if (first_noext < first_inval) run = first_noext + 1, closed = true;
-			else run = first_inval, closed = false;
-			static const int32_t op_of[6] = { 0, 1, 2, 3, 12, 13 };
-			push(op_of[st], run);
-			i -= di * run, j -= dj * run;
-			if (closed && (st == 4 || st == 5)) --j;               // the intron of phase 1/2 ends inside a codon
-			carry = closed ? 0 : st;
-			if (run == 0) break;                                  // cannot happen (the loop condition holds for lane 0)
-		} else {                                                 // frameshifts: one cell
-			if (st == 6) push(10, 1), i -= 1;
-			else if (st == 7) push(10, 2), i -= 2;
-			else if (st == 8) push(11, 1), i -= 1, j -= 1;
-			else push(11, 2), i -= 2, j -= 1;
-			carry = 0;
-		}
-	}
-	if (j > 0) push(1, j);
-	if (i >= 0) {
-		const int32_t l = (i + 1) / 3 * 3, r = (i + 1) % 3;
-		if (l > 0) push(2, l);
-		if (r != 0) push(10, r);
-	}
-	push(-2, 0);                                                 // flush
-	if (n > cap) n = cap;
-	__syncthreads();
-	for (int32_t x = lane; x < n >> 1; x += 64) { uint32_t tmp = cig[x]; cig[x] = cig[n - 1 - x], cig[n - 1 - x] = tmp; }
-	__syncthreads();
-	for (int32_t x = lane; x < n; x += 64) {                      // ns_fix_tiny_UV
-		const uint32_t op = cig[x] & 0xf;
-		if ((op == 12 || op == 13) && cig[x] >> 4 < 3) cig[x] = cig[x] >> 4 << 4 | 11;
-	}
-	if (lane == 0) n_cigar[tid] = n;
-}
-
-// ------------------------------------------------------------------------------------------------
-// The walk of the checkpointed traceback (dp_device.h): ns_backtrack (nasw-sse.c:40-89) over a call whose sweep kept only the four
-// extension bits per cell and a checkpoint per block of MPA_TB_BLOCK rows.  One wave per call.  Deletion and intron runs (states 2..5)
-// are followed on the bits, 64 cells at a time; in any other state the wave first recomputes the traceback words of the block it
-// stands in (glob_narrow restarted from the block's checkpoint, words into LDS) and walks those, exactly like k_backtrack -- a run
-// that leaves the block is simply continued in the next iteration.  A call is swept twice only where its path is not in a run.
-// ------------------------------------------------------------------------------------------------
-struct WalkArgs {
-	GlobArgs ga;                 // tasks, records, profiles, scoring
-	const int32_t *list;         // the calls
-	int32_t n_list;
-	const uint32_t *lite, *ckpt; // extension-bit words and checkpoints of the packed sweeps
-	uint32_t *cig;
-	int32_t *n_cigar;
-	unsigned long long *n_blocks; // (statistics) blocks recomputed
-};
-// (per class of the packed sweep -- 16 / 32 / 64 / 128 / 256 columns at most: 8 / 11 / 17 / 29 / 53 KB; one launch per class, so that the narrow
-// calls' walks, most of them, take LDS for their own block of direction words and not for a 256-column one)
-#define WALK_LDS(NC) (GLOB_NARROW_LDS + (size_t)MPA_TB_BLOCK * (NC) * 2 + (size_t)(MPA_TB_BLOCK + 2) * 16)
-// DUAL: a call of 65..128 columns, swept with column c + 64 in the high half of lane c (ext_narrow<64, true, true>) and recomputed
-// by the block-major traceback sweep (two blocks of 64 columns, boundary records in LDS)
-// WIDE4: a call of 129..256 columns, swept by a four-wave group (lite_wide_body; the call is int16 half `slot` of every lane) and
-// recomputed by the same block-major sweep over up to four blocks of 64 columns, each from the checkpoint of the wave that swept it
-template<int G, bool DUAL = false, bool WIDE4 = false>
-__device__ __forceinline__ void walk_call(const WalkArgs &wa, const DTask &t, const int32_t tid, char *lds, const int lane)
-{
-	static_assert(!(DUAL || WIDE4) || G == 64, "the block-major classes are swept in blocks of 64 columns");
-	constexpr int NG = 64 / G;
-	const int slot = DUAL ? 0 : (t.flag >> MPA_LITE_SLOT_SHIFT) & 15, half = WIDE4 ? slot : slot / NG, lane0 = WIDE4 ? 0 : (slot % NG) * G;
-	const uint32_t *lite = wa.lite + t.tb_off + lane0;
-	uint16_t *tbs = (uint16_t*)(lds + GLOB_NARROW_LDS);            // [MPA_TB_BLOCK][ncol] words of the block that is materialised
-	int4 *bnds = (int4*)(lds + GLOB_NARROW_LDS + (size_t)MPA_TB_BLOCK * (WIDE4 ? 256 : DUAL ? 128 : G) * 2);
-	uint32_t *cig = wa.cig + t.cig_off;
-	const int32_t ncol = t.ncol, cap = t.cig_cap;
-	int32_t blk = -1, blk_lo = 0, blk_hi = 0;                      // the materialised block and its rows [blk_lo, blk_hi)
-	auto ensure = [&](const int32_t row) {
-		if (blk >= 0 && row >= blk_lo && row < blk_hi) return;
-		const int32_t b = (row - 2) / MPA_TB_BLOCK;
-		constexpr int NCB = WIDE4 ? 4 : DUAL ? 2 : 1;
-		GlobResume<NCB> rz;
-		rz.row_off = b * MPA_TB_BLOCK, rz.n_rows = t.nl - 2 - rz.row_off < MPA_TB_BLOCK ? t.nl - 2 - rz.row_off : MPA_TB_BLOCK;
-#pragma unroll
-		for (int cb = 0; cb < NCB; ++cb) {
-			rz.ck[cb] = nullptr, rz.sh[cb] = 0;
-			if (b == 0) continue;
-			if (WIDE4) rz.ck[cb] = wa.ckpt + t.bnd_off + lite_wide_ckpt_at(b, 64 * cb, half, &rz.sh[cb]);
-			else rz.ck[cb] = wa.ckpt + t.bnd_off + (int64_t)(b - 1) * 9 * 64 + lane0, rz.sh[cb] = 16 * (DUAL ? cb : half);
-		}
-		rz.tb = tbs, rz.bnd = bnds;
-		GlobWave gw;
-		gw.task[0] = tid, gw.task[1] = gw.task[2] = gw.task[3] = -1, gw.max_nl = rz.n_rows + 2;
-		wave_sync();
-		glob_narrow<G, DUAL || WIDE4, false, false, NCB>(wa.ga, gw, WavePos{ lds, lane, 0, lane }, &rz);
-		wave_sync();
-		blk = b, blk_lo = 2 + rz.row_off, blk_hi = blk_lo + rz.n_rows;
-		if (lane == 0) atomicAdd(wa.n_blocks, 1ULL);
-	};
-	auto full = [&](const int32_t ii, const int32_t jj) -> int32_t { return tbs[(ii - blk_lo) * ncol + jj]; };
-	auto nibble = [&](const int32_t ii, const int32_t jj) -> int32_t {
-		if (WIDE4) {
-			int32_t sh;
-			const int64_t at = lite_wide_bit_at(ii, jj, half, &sh);
-			return (int32_t)(lite[at] >> sh) & 0xf;
-		}
-		const uint32_t r = (uint32_t)(ii - 2);
-		return (int32_t)(lite[(int64_t)(r / 3) * 64 + (DUAL ? jj & 63 : jj)] >> (16 * (DUAL ? jj >> 6 : half) + 4 * (2 - r % 3))) & 0xf;
-	};
-	int32_t i = t.nl - 1, j = t.al - 1, carry = 0, n = 0;
-	int32_t cur_op = -1, cur_len = 0;                              // (ns_push_cigar merges equal neighbours except F/G, nasw.h:141-152)
-	auto push = [&](int32_t op, int32_t len) {
-		if (cur_op == op && op != 10 && op != 11) { cur_len += len; return; }
-		if (cur_op >= 0) { if (lane == 0 && n < cap) cig[n] = (uint32_t)cur_len << 4 | (uint32_t)cur_op; ++n; }
-		cur_op = op, cur_len = len;
-	};
-	auto state_of = [](int32_t w) { return (w >> 9 & 1) ? 1 : (w & 0xf); };
-	while (i >= 2 && j >= 0) {
-		int32_t st = carry;
-		if (st == 0) { ensure(i); st = state_of(full(i, j)); }          // fresh cell: its own state decides the direction
-		if (st == 0) {                                               // run of matches on the diagonal (i-3l, j-l), inside the block
-			const int32_t ii = i - 3 * lane, jj = j - lane;
-			const bool ok = ii >= blk_lo && jj >= 0;
-			const int32_t w = ok ? full(ii, jj) : 0xf;
-			const uint64_t stop = __ballot(!ok || state_of(w) != 0);
-			const int32_t run = stop ? __ffsll((unsigned long long)stop) - 1 : 64;
-			push(0, run), i -= 3 * run, j -= run, carry = 0;
-		} else if (st <= 5) {                                        // extension runs: I along the row (words), D/N/U/V along the column (bits)
-			const int32_t di = st == 1 ? 0 : st == 2 ? 3 : 1, dj = st == 1 ? 1 : 0;
-			if (st == 1) ensure(i);
-			const int32_t ii = i - di * lane, jj = j - dj * lane;
-			const bool ok = ii >= 2 && jj >= 0;
-			bool ext = false;
-			if (ok) ext = st == 1 ? (full(ii, jj) >> 4 & 1) != 0 : (nibble(ii, jj) >> (st - 2) & 1) != 0;
-			const uint64_t inval = __ballot(!ok), noext = __ballot(!ext);
-			const int32_t first_noext = noext ? __ffsll((unsigned long long)noext) - 1 : 64;
-			const int32_t first_inval = inval ? __ffsll((unsigned long long)inval) - 1 : 64;
-			int32_t run;
-			bool closed;
-			if (first_noext < first_inval) run = first_noext + 1, closed = true;
-			else run = first_inval, closed = false;
-			static const int32_t op_of[6] = { 0, 1, 2, 3, 12, 13 };
-			push(op_of[st], run);
-			i -= di * run, j -= dj * run;
-			if (closed && (st == 4 || st == 5)) --j;
-			carry = closed ? 0 : st;
-			if (run == 0) break;
-		} else {                                                     // frameshifts: one cell
-			if (st == 6) push(10, 1), i -= 1;
-			else if (st == 7) push(10, 2), i -= 2;
-			else if (st == 8) push(11, 1), i -= 1, j -= 1;
-			else push(11, 2), i -= 2, j -= 1;
-			carry = 0;
-		}
-	}
-	if (j > 0) push(1, j);
-	if (i >= 0) {
-		const int32_t l = (i + 1) / 3 * 3, r = (i + 1) % 3;
-		if (l > 0) push(2, l);
-		if (r != 0) push(10, r);
-	}
-	push(-2, 0);                                                 // flush
-	if (n > cap) n = cap;
-	__syncthreads();
-	for (int32_t x = lane; x < n >> 1; x += 64) { uint32_t tmp = cig[x]; cig[x] = cig[n - 1 - x], cig[n - 1 - x] = tmp; }
-	__syncthreads();
-	for (int32_t x = lane; x < n; x += 64) {                      // ns_fix_tiny_UV
-		const uint32_t op = cig[x] & 0xf;
-		if ((op == 12 || op == 13) && cig[x] >> 4 < 3) cig[x] = cig[x] >> 4 << 4 | 11;
-	}
-	if (lane == 0) wa.n_cigar[tid] = n;
-}
-__global__ __launch_bounds__(64) void k_walk(WalkArgs wa)
-{
-	extern __shared__ __attribute__((aligned(16))) uint32_t lds_raw[];
-	if ((int32_t)blockIdx.x >= wa.n_list) return;
-	const int32_t tid = wa.list[blockIdx.x];
-	const DTask t = wa.ga.tasks[tid];
-	const int lane = (int)threadIdx.x;
-	switch (t.cls) {                                             // (class of the call's packed sweep)
-	case T_LITE16: walk_call<16>(wa, t, tid, (char*)lds_raw, lane); break;
-	case T_LITE32: walk_call<32>(wa, t, tid, (char*)lds_raw, lane); break;
-	case T_LITE64: walk_call<64>(wa, t, tid, (char*)lds_raw, lane); break;
-	case T_LITE128: walk_call<64, true>(wa, t, tid, (char*)lds_raw, lane); break;   // 65..128 columns, one call per wave
-	case T_LITE_W4: walk_call<64, false, true>(wa, t, tid, (char*)lds_raw, lane); break;   // 129..256 columns, a four-wave group per pair of calls
-	default: break;
-	}
-}
-
-// dense copy of the CIGARs: every call's slot was sized for the worst case, only n_cigar words are real
-__global__ __launch_bounds__(64) void k_cigar_gather(const DTask *tasks, const int32_t *list, const int64_t *dst_off, int32_t n_list,
-                                                     const int32_t *n_cigar, const uint32_t *src, uint32_t *dst)
-{
-	MPA_SHORT_KERNEL();
-	if ((int32_t)blockIdx.x >= n_list) return;
-	const int32_t tid = list[blockIdx.x], n = n_cigar[tid];
-	const uint32_t *from = src + tasks[tid].cig_off;
-	uint32_t *to = dst + dst_off[blockIdx.x];
-	for (int32_t k = threadIdx.x; k < n; k += 64) to[k] = from[k];
 }
 
 } // namespace mpa

@@ -1,4 +1,4 @@
-// ext_huge_wg_core.h -- the schedule of k_ext_huge_wg (dp_kernels.hip): the block-major int32 sweep of an X_HUGE
+// ext_huge_wg_core.h -- the schedule of k_ext_huge_wg (dp_huge_kernels.hip): the block-major int32 sweep of an X_HUGE
 // extension call with one wave per 64-column block, W waves in one workgroup, boundary records handed from a block to its right
 // neighbour through LDS.  Host and device compile the same text: the kernel takes every loop bound, ring slot and LDS offset from
 // here, and tests/hugewg_check.cpp walks the same functions step by step without a device.  No HIP, no std::, no globals.
@@ -21,7 +21,7 @@ static const int FIRST_ROW = 2;                 // rows 0 and 1 are the start st
 
 // LDS: W wave areas as the one-wave kernel has one (profile columns of the wave's block, record ring), then W boundary rings of two
 // parities x R records of 16 bytes.  16 x 3328 + 16 x 768 = 65536 bytes: what a launch may ask for without an attribute.
-static const int WAVE_LDS = 22 * 64 * 2 + 4 * 32 * 4;           // GLOB_NARROW_LDS (dp_kernels.hip asserts the two equal)
+static const int WAVE_LDS = 22 * 64 * 2 + 4 * 32 * 4;           // GLOB_NARROW_LDS of dp_kernels.hip (dp_huge_kernels.hip asserts the two equal)
 static const int BND_BYTES = 16;
 static const int RING_BYTES = 2 * R * BND_BYTES;
 static const int LDS_BYTES = W * (WAVE_LDS + RING_BYTES);
