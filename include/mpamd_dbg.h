@@ -1,5 +1,5 @@
-/* mpamd_dbg.h -- the test hooks of MPA_GPU_SPANS, MPA_GPU_DPPLAN and MPA_GPU_ROUND2.  They are not part of the C ABI of libmpamd.so (include/mpamd.h):
- * they are built from miniprot_amd/csrc/spans_dbg.cpp, dpplan_dbg.cpp and round2_dbg.cpp into a library of its own, libmpamd_dbg.so, next to libmpamd.so
+/* mpamd_dbg.h -- the test hooks of MPA_GPU_SPANS, MPA_GPU_DPPLAN, MPA_GPU_ROUND2 and the stream plan.  They are not part of the C ABI of libmpamd.so (include/mpamd.h):
+ * they are built from miniprot_amd/csrc/spans_dbg.cpp, dpplan_dbg.cpp, round2_dbg.cpp and stream_dbg.cpp into a library of its own, libmpamd_dbg.so, next to libmpamd.so
  * and linked against it. */
 #ifndef MPAMD_DBG_H
 #define MPAMD_DBG_H
@@ -78,6 +78,18 @@ void mpa_dbg_dp_huge_wg_info(int32_t out[3]);
 typedef struct { const int32_t *ext_out, *score, *n_cigar, *gids; int64_t n_glob; } mpa_dbg_dp_outputs_t;
 int mpa_dbg_dp_run_resident(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *opt, const mpa_qbatch_t *q, int64_t n, const mpa_dp_task_t *tasks,
                             const mpa_dbg_dp_outputs_t *made_up, mpa_dp_rst_t *rst, uint32_t **cigar_pool, int64_t *n_pool, int64_t *rec);
+
+/* The stream plan (miniprot_amd/csrc/stream_plan.h): which streams mpa_map_batches creates for its DP lanes,
+ * seeders and planners, in which priority class (0 normal, 1 high, 2 low) and in which order, for the hardware queues of the process.
+ * As int32 words: q, lanes, seeders, planners, layout (0 legacy, 1 A, 2 B, 3 C), streams created up front; per lane class, rank in
+ * creation order, side streams it may create, their class; per seeder and then per planner main class, main rank, seeding class, seeding
+ * rank (the same stream twice unless the layout is the legacy one).  Both return the words the plan takes, written when they fit cap.
+ * mpa_dbg_stream_plan: the plan in force on a context, that is the one its last mpa_map_batches* call created its sibling contexts by
+ * (0 words before the first).  mpa_dbg_stream_plan_for: the module's plan for q hardware queues (q <= 0: GPU_MAX_HW_QUEUES as the
+ * process saw it when its first context was created, or as it sees it now if there is none yet) and a value of MPA_STREAM_PLAN
+ * (NULL: unset). */
+int64_t mpa_dbg_stream_plan(const mpa_ctx_t *ctx, int32_t *out, int64_t cap);
+int64_t mpa_dbg_stream_plan_for(int32_t q, int32_t n_lanes, int32_t n_seed, int32_t n_plan, const char *layout, int32_t *out, int64_t cap);
 
 #ifdef __cplusplus
 }

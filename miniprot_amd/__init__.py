@@ -623,6 +623,52 @@ def dbg_dp_huge_wg_info():
     return tuple(int(x) for x in out)
 
 
+STREAM_CLASSES = ("normal", "high", "low")
+STREAM_LAYOUTS = ("legacy", "A", "B", "C")
+
+
+def _stream_plan_of(words):
+    w = [int(x) for x in words]
+    q, lanes, seeders, planners, layout, n_streams = w[:6]
+    at = 6
+    plan = {"q": q, "layout": STREAM_LAYOUTS[layout], "n_streams": n_streams, "lanes": [], "seeders": [], "planners": []}
+    for _ in range(lanes):
+        plan["lanes"].append({"cls": STREAM_CLASSES[w[at]], "rank": w[at + 1], "side_cap": w[at + 2], "side_cls": STREAM_CLASSES[w[at + 3]]})
+        at += 4
+    for role, n in (("seeders", seeders), ("planners", planners)):
+        for _ in range(n):
+            plan[role].append({"cls": STREAM_CLASSES[w[at]], "rank": w[at + 1], "seed_cls": STREAM_CLASSES[w[at + 2]], "seed_rank": w[at + 3]})
+            at += 4
+    assert at == len(w)
+    return plan
+
+
+def dbg_stream_plan(ctx):
+    """mpa_dbg_stream_plan(): the stream plan in force on a context -- the one its last map_batches() created its sibling contexts by --
+    as a dict (q, layout, n_streams, lanes / seeders / planners: class and rank in creation order of every stream, a lane's side-stream
+    cap and class); None before the first stream of batches."""
+    import numpy as np
+    out = np.zeros(6 + 4 * 18, np.int32)
+    f = dbg_lib().mpa_dbg_stream_plan
+    f.restype = C.c_int64
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    n = f(ctx.h, out.ctypes.data, len(out))
+    _check(min(n, 0))
+    return _stream_plan_of(out[:n]) if n else None
+
+
+def dbg_stream_plan_for(q, lanes=5, seeders=3, planners=4, layout=None):
+    """mpa_dbg_stream_plan_for(): the plan of the module (stream_plan.cpp; no device needed) for q hardware queues (0: GPU_MAX_HW_QUEUES
+    as the process sees it) and a value of MPA_STREAM_PLAN (None: unset)."""
+    import numpy as np
+    out = np.zeros(6 + 4 * 18, np.int32)
+    f = dbg_lib().mpa_dbg_stream_plan_for
+    f.restype = C.c_int64
+    f.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_void_p, C.c_int64]
+    n = f(q, lanes, seeders, planners, None if layout is None else str(layout).encode(), out.ctypes.data, len(out))
+    return _stream_plan_of(out[:n])
+
+
 ROUND2_DECLINED = 1  # MPA_DBG_ROUND2_DECLINED (include/mpamd_dbg.h)
 ROUND2_REC = ("plan_waits", "round_waits", "bytes_up", "task_bytes_up", "bytes_down", "pool_bytes_down", "pool_bytes_fetched", "prep_bound", "max_nl", "max_al", "n_pool", "reserved")
 

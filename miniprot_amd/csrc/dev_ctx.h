@@ -18,6 +18,7 @@
 #include "host_core.h"
 #include "dp_device.h"
 #include "dp_plan.h"
+#include "stream_plan.h"
 #include "chain_core.h"
 #include "dev_common.h"
 
@@ -130,6 +131,11 @@ struct mpa_ctx_s {
 	hipEvent_t wait_ev = nullptr;             // blocking-sync event: a host thread that waits for the device SLEEPS (wait_stream)
 	int side_off = 0;                         // first side stream a round uses (lets the DP lanes of a stream of batches sit on different hardware queues)
 	hipStream_t seed_stream = nullptr;        // high-priority stream of the seeding kernels: short, and must not queue behind DP tails
+	// ---- what the stream plan (stream_plan.h) says about this context; the defaults are a context outside a stream of batches
+	bool one_stream = false;                  // a seeder or planner of a planned layout: its seeding stream IS its main stream
+	int side_cap = kSide;                     // side streams a DP round may create (0: its side launches take the main stream) ...
+	int side_cls = 0;                         // ... and their priority class (StreamClass)
+	mpa::StreamPlan *splan = nullptr;         // (root context only, owned) the plan its siblings were created by (mpa_dbg_stream_plan)
 	int split_wide = 0;                       // 1025..3072-column extension calls on X_SPLIT8 / X_SPLIT12 instead of k_ext_huge (MPA_DP_SPLIT_WIDE; 0, the default until it has been measured)
 	int huge_wg = 0;                          // X_HUGE calls of hwg::MIN_BLOCKS column blocks or more on k_ext_huge_wg, one wave per block (MPA_DP_HUGE_WG; 0, the default until it has been measured)
 	int64_t last_huge[4] = { 0, 0, 0, 0 };    // the last mpa_dp_run's X_HUGE calls on the one-wave kernel, on the workgroup kernel, the latter's column blocks and passes (mpa_dbg_dp_last_huge)
@@ -203,6 +209,7 @@ template<typename F> static void ctx_each_devbuf(mpa_ctx_s *ctx, F f)
 hipError_t wait_stream(mpa_ctx_t *ctx, hipStream_t s);                                   // wait for a stream, asleep
 hipError_t upload_large(void *dst, const void *src, size_t bytes, hipStream_t s);       // a large host array into device memory through pinned slices
 void ensure_seed_stream(mpa_ctx_t *ctx);                                                 // ctx->seed_stream, created on first use
+hipError_t create_stream_in_class(hipStream_t *s, int cls);                              // a non-blocking stream of a StreamClass (stream_plan.h)
 hipError_t ensure_dynamic_lds(const void *fn, int device, size_t bytes);                 // hipFuncSetAttribute(MaxDynamicSharedMemorySize), once per (kernel, device)
 void ctx_pool_report(mpa_ctx_t *root);
 void pool_harvest(mpa_ctx_t *ctx, bool wait);                                            // (dp_exec.hip) the finished worker launches of a context's DP pool

@@ -117,13 +117,31 @@ hipError_t upload_large(void *dst, const void *src, size_t bytes, hipStream_t s)
 // The seeding / refinement kernels of a context run on a stream of their own, created with the device's highest priority: they are
 // short and a pipeline stage waits for each of them (MPA_PRIO_SEED=0: normal priority; MPA_PRIO_MAIN=1: the contexts' main streams
 // -- the DP lanes' prep kernels, walks and copies -- get the high priority too).
+// (a seeder or planner of a planned layout has one stream, created in the plan's class: stream_plan.h)
 void ensure_seed_stream(mpa_ctx_t *ctx)
 {
 	if (ctx->seed_stream) return;
+	if (ctx->one_stream) { ctx->seed_stream = ctx->stream; return; }
 	static const bool high = [] { const char *e = getenv("MPA_PRIO_SEED"); return !e || atoi(e) != 0; }();
 	int least = 0, greatest = 0;
 	(void)hipDeviceGetStreamPriorityRange(&least, &greatest);
 	if (hipStreamCreateWithPriority(&ctx->seed_stream, hipStreamNonBlocking, high ? greatest : least) != hipSuccess) ctx->seed_stream = ctx->stream;
+}
+
+hipError_t create_stream_in_class(hipStream_t *s, int cls)
+{
+	if (cls == SC_NORMAL) return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+	int least = 0, greatest = 0;
+	(void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+	return hipStreamCreateWithPriority(s, hipStreamNonBlocking, cls == SC_HIGH ? greatest : least);
+}
+
+// GPU_MAX_HW_QUEUES as the process sees it when its first context is created (the library's constructor sets 16 where the variable is
+// unset: tables.cpp); the runtime reads it when it initialises, which is not later than that
+int ctx_hw_queues(void)
+{
+	static const int q = [] { const char *e = getenv("GPU_MAX_HW_QUEUES"); const int v = e && *e ? atoi(e) : 4; return v < 1 ? 4 : v; }();
+	return q;
 }
 
 int dev_upload_index(mpa_ctx_t *ctx, mpa_idx_s *mi)
@@ -197,7 +215,9 @@ int mpa_device_count(void)
 	return n;
 }
 
-mpa_ctx_t *mpa_ctx_create(int device)
+// cls < 0: a context of its own (mpa_ctx_create) -- a normal main stream, or a high one with MPA_PRIO_MAIN=1; otherwise the class
+// the stream plan gives this context's main stream
+static mpa_ctx_t *ctx_create_in_class(int device, int cls)
 {
 	int n = mpa_device_count();
 	if (n <= 0 || device < 0 || device >= n) {
@@ -208,9 +228,8 @@ mpa_ctx_t *mpa_ctx_create(int device)
 	mpa_ctx_s *ctx = new mpa_ctx_s();
 	ctx->device = device;
 	static const bool main_high = [] { const char *e = getenv("MPA_PRIO_MAIN"); return e && atoi(e) != 0; }();
-	int least = 0, greatest = 0;
-	(void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-	bool ok = (main_high ? hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, greatest) : hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) == hipSuccess;
+	(void)ctx_hw_queues();
+	bool ok = create_stream_in_class(&ctx->stream, cls >= 0 ? cls : main_high ? SC_HIGH : SC_NORMAL) == hipSuccess;
 	for (auto &e : ctx->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
 	for (auto &e : ctx->lev) ok = ok && hipEventCreate(&e) == hipSuccess;
 	ok = ok && hipEventCreate(&ctx->fork_ev) == hipSuccess;
@@ -227,6 +246,8 @@ mpa_ctx_t *mpa_ctx_create(int device)
 	if (const char *s = getenv("MPA_DP_HUGE_WG")) ctx->huge_wg = atoi(s) != 0;
 	return ctx;
 }
+
+mpa_ctx_t *mpa_ctx_create(int device) { return ctx_create_in_class(device, -1); }
 
 void mpa_ctx_destroy(mpa_ctx_t *ctx)
 {
@@ -250,6 +271,7 @@ void mpa_ctx_destroy(mpa_ctx_t *ctx)
 	for (SeedHold *H : ctx->holds) { drop_hold(*H); delete H; }
 	ctx->holds.clear();
 	delete ctx->hints, ctx->hints = nullptr;
+	delete ctx->splan, ctx->splan = nullptr;
 	for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
 	for (auto &e : ctx->lev) if (e) (void)hipEventDestroy(e);
 	if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
@@ -286,6 +308,42 @@ mpa_ctx_t *ctx_sibling(mpa_ctx_t *ctx, int k)
 	return ctx->siblings[k - 1];
 }
 void ctx_set_side_offset(mpa_ctx_t *ctx, int off) { ctx->side_off = off; }
+
+const StreamPlan *ctx_stream_plan(const mpa_ctx_t *root) { return root ? root->splan : nullptr; }
+
+// Siblings 1 .. lanes - 1 are the DP lanes behind the root (lane 0, whose normal main stream exists), then the seeders, then the
+// planners: the plan's creation order.  Between two streams of batches nothing is in flight on a sibling, so a plan that differs from
+// the one they were made by (another layout, other stage counts) replaces them, pools included.
+int ctx_apply_stream_plan(mpa_ctx_t *root, int n_lanes, int n_seed, int n_plan, int layout)
+{
+	const StreamPlan p = stream_plan(ctx_hw_queues(), n_lanes, n_seed, n_plan, layout);
+	const int n_sib = p.n_lanes - 1 + p.n_seed + p.n_plan;
+	if (!root->splan || memcmp(root->splan, &p, sizeof p) != 0) {
+		for (mpa_ctx_s *sb : root->siblings) mpa_ctx_destroy(sb);
+		root->siblings.clear();
+		for (auto &st : root->side) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); st = nullptr; }   // (the root's own, of the old plan's class)
+		if (!root->splan) root->splan = new StreamPlan();
+		*root->splan = p;
+	}
+	auto entry = [&](int k, const StreamSlot *&main, bool &lane) {       // sibling k (>= 1) of the plan
+		lane = k < p.n_lanes;
+		main = lane ? &p.lane[k] : k < p.n_lanes + p.n_seed ? &p.seed_main[k - p.n_lanes] : &p.plan_main[k - p.n_lanes - p.n_seed];
+	};
+	root->side_cap = p.side_cap[0], root->side_cls = p.side_cls[0];
+	while ((int)root->siblings.size() < n_sib) {
+		const int k = (int)root->siblings.size() + 1;
+		const StreamSlot *main; bool lane;
+		entry(k, main, lane);
+		mpa_ctx_t *sb = ctx_create_in_class(root->device, p.layout == SL_LEGACY ? -1 : main->cls);
+		if (!sb) return MPA_ERR_HIP;
+		sb->tb_budget = root->tb_budget, sb->lite_min = root->lite_min, sb->lite_wide = root->lite_wide, sb->split_wide = root->split_wide, sb->huge_wg = root->huge_wg;
+		sb->root = root;
+		sb->one_stream = !lane && p.layout != SL_LEGACY;
+		if (lane) sb->side_cap = p.side_cap[k], sb->side_cls = p.side_cls[k];
+		root->siblings.push_back(sb);
+	}
+	return MPA_OK;
+}
 // `ctx` (the root itself or one of its siblings) plays part `role` of the root's stream pipeline: 0 DP lane, 1 seeder, 2 planner
 void ctx_set_role(mpa_ctx_t *root, mpa_ctx_t *ctx, int role)
 {

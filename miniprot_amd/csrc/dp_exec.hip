@@ -279,7 +279,8 @@ struct DpRun {
 	double t_mark = 0;
 	void mark(const char *what) { const double t = now_ms(); timing_note(what, t - t_mark); t_mark = t; }   // (MPA_TIMING: wall clock between marks)
 	hipEvent_t ev_round(int k) const { return ctx->lev[2 * (mpa_ctx_s::kSide - 1) + k]; }                    // the last event pair times the round's launch
-	hipStream_t side_stream(int k) const { hipStream_t st = ctx->side[(k + ctx->side_off) % mpa_ctx_s::kSide]; return st ? st : s; }
+	int side_slot(int k) const { return (k + ctx->side_off) % ctx->side_cap; }                               // (side_cap > 0) the stream plan caps a lane's side streams: launches beyond the cap share them in turn
+	hipStream_t side_stream(int k) const { hipStream_t st = ctx->side_cap > 0 ? ctx->side[side_slot(k)] : nullptr; return st ? st : s; }
 	void add_chunk_times() { float a = 0, b = 0; (void)hipEventElapsedTime(&a, ctx->ev[3], ctx->ev[4]); (void)hipEventElapsedTime(&b, ctx->ev[4], ctx->ev[5]); ms_glob += a, ms_bt += b; }
 };
 
@@ -290,8 +291,11 @@ static hipStream_t begin_side(DpRun &R, bool is_ext)
 	const int k = (int)R.launches.size();
 	// (side streams are created when first used: HIP deals hardware queues to streams in creation order, and sixteen idle side
 	// streams per context pushed the main streams of later contexts onto queues that other contexts' long kernels were using)
-	hipStream_t &slot = ctx->side[(k + ctx->side_off) % mpa_ctx_s::kSide];
-	if (!slot && hipStreamCreateWithFlags(&slot, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); slot = nullptr; }
+	// (how many a lane may have and in which priority class is the stream plan's: stream_plan.h; none: the lane's own stream)
+	if (ctx->side_cap > 0) {
+		hipStream_t &slot = ctx->side[R.side_slot(k)];
+		if (!slot && create_stream_in_class(&slot, ctx->side_cls) != hipSuccess) { (void)hipGetLastError(); slot = nullptr; }
+	}
 	hipStream_t st = R.side_stream(k);
 	(void)hipStreamWaitEvent(st, ctx->fork_ev, 0);
 	(void)hipEventRecord(ctx->lev[2 * k], st);

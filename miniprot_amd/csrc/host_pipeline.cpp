@@ -6,6 +6,7 @@
 #include <cstring>
 #include <thread>
 #include "host_batch.h"
+#include "stream_plan.h"
 #pragma GCC visibility push(hidden)   // (the scheduler is internal to the library: the dynamic symbol table does not grow)
 #include "host_pipeline.h"
 #pragma GCC visibility pop
@@ -66,6 +67,14 @@ static int mpa_map_batches_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_m
 	// round 3 (both chaining rounds on the device, sleeping waits: the host stages no longer bound the stream): 5 lanes 93.5 ms per
 	// 4 000-protein step, 4 lanes 99.8, 6 lanes 100-112 (config 3, 20 steps)
 	const int n_lanes = stream_knob("MPA_DP_LANES", 5, 1, 8);
+	const int n_plan = stream_knob("MPA_PLANNERS", 4, 1, 6), n_seed = stream_knob("MPA_SEEDERS", 3, 1, 4);   // (what they are: below)
+	// The streams of all these contexts share the process's hardware queues (GPU_MAX_HW_QUEUES per priority class): which context's
+	// stream is created when and in which class is stream_plan.h.  MPA_STREAM_PLAN=0 (and the legacy layout's own knobs MPA_PRIO_MAIN,
+	// MPA_PRIO_SEED): every context a normal main stream, seeders and planners a high one on top, sixteen side streams per lane.
+	{
+		const int layout = getenv("MPA_PRIO_MAIN") || getenv("MPA_PRIO_SEED") ? (int)SL_LEGACY : stream_layout_of(getenv("MPA_STREAM_PLAN"));
+		if (const int rc = ctx_apply_stream_plan(ctx, n_lanes, n_seed, n_plan, layout)) return rc;
+	}
 	std::vector<mpa_ctx_t*> lane_ctx((size_t)n_lanes, ctx);
 	for (int d = 1; d < n_lanes; ++d) if (!(lane_ctx[d] = ctx_sibling(ctx, d))) return MPA_ERR_HIP;
 	for (int d = 0; d < n_lanes; ++d) ctx_set_role(ctx, lane_ctx[d], 0);
@@ -78,10 +87,8 @@ static int mpa_map_batches_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_m
 	// the end of planning: the result of batch k is consumed while batches k+1 .. are on the device.
 	// (round 3: with the whole refinement on the device a planner mostly waits for it -- three of them, a third of the threads each)
 	// (round 5, once the contexts' idle side streams no longer took hardware queues away: four planners and three seeders, +5 %)
-	const int n_plan = stream_knob("MPA_PLANNERS", 4, 1, 6);
 	// Seeders: the device-seeding stage of a batch is mostly waiting for its kernels, which share the GPU with the DP rounds in
 	// flight; two batches are seeded side by side (MPA_SEEDERS, default 2)
-	const int n_seed = stream_knob("MPA_SEEDERS", 3, 1, 4);
 	// Depth of the pipeline.  A seeding context is busy from the start of a batch's seeding to the end of its planning, and a
 	// planned batch waits for a DP lane: seeding of batch k waits for the plan of batch k - n_seed_ctx, the plan of batch k for
 	// the end of the DP of batch k - (lanes + planners).  Deeper coupling was measured to change nothing (rounds 2-3).

@@ -153,6 +153,14 @@ int dev_index_build(mpa_ctx_t *ctx, mpa_idx_s *mi);           // k-mer table of 
 int32_t idx_plan_passes(const int64_t *hist, int32_t n_bins, int64_t budget_keys, int32_t *first_bin);   // bucket ranges of a multi-pass build (index.cpp; mpa_dbg_idx_plan_passes)
 void dev_free_index(mpa_idx_s *mi);
 mpa_ctx_t *ctx_sibling(mpa_ctx_t *ctx, int k);   // extra context on the same device (k >= 1), owned by ctx
+// the sibling contexts of a stream of batches, created in the order and the priority classes of a stream plan (stream_plan.h) for the
+// process's hardware queues and the layout asked for (StreamLayout); siblings made by another plan are destroyed first.  The plan in
+// force stays with the root (ctx_stream_plan; nullptr before the first stream).  ctx_hw_queues(): GPU_MAX_HW_QUEUES as the process saw
+// it when its first context was created.
+struct StreamPlan;
+int ctx_apply_stream_plan(mpa_ctx_t *root, int n_lanes, int n_seed, int n_plan, int layout);
+const StreamPlan *ctx_stream_plan(const mpa_ctx_t *root);
+int ctx_hw_queues(void);
 void ctx_absorb_sibling_stats(mpa_ctx_t *ctx);
 void ctx_set_side_offset(mpa_ctx_t *ctx, int off);   // which of its side streams a DP round starts with
 void ctx_set_role(mpa_ctx_t *root, mpa_ctx_t *ctx, int role);   // ctx's pools share their high-water marks with the root's other contexts of that role (0 DP lane, 1 seeder, 2 planner)
