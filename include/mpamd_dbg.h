@@ -1,5 +1,5 @@
-/* mpamd_dbg.h -- the test hooks of MPA_GPU_SPANS, MPA_GPU_DPPLAN, MPA_GPU_ROUND2 and the stream plan.  They are not part of the C ABI of libmpamd.so (include/mpamd.h):
- * they are built from miniprot_amd/csrc/spans_dbg.cpp, dpplan_dbg.cpp, round2_dbg.cpp and stream_dbg.cpp into a library of its own, libmpamd_dbg.so, next to libmpamd.so
+/* mpamd_dbg.h -- the test hooks of MPA_GPU_SPANS, MPA_GPU_DPPLAN, MPA_GPU_ROUND2, the stream plan and the contexts' pool registry.  They are not part of the C ABI of libmpamd.so (include/mpamd.h):
+ * they are built from miniprot_amd/csrc/spans_dbg.cpp, dpplan_dbg.cpp, round2_dbg.cpp, stream_dbg.cpp and ctx_pools_dbg.cpp into a library of its own, libmpamd_dbg.so, next to libmpamd.so
  * and linked against it. */
 #ifndef MPAMD_DBG_H
 #define MPAMD_DBG_H
@@ -90,6 +90,13 @@ int mpa_dbg_dp_run_resident(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt
  * (NULL: unset). */
 int64_t mpa_dbg_stream_plan(const mpa_ctx_t *ctx, int32_t *out, int64_t cap);
 int64_t mpa_dbg_stream_plan_for(int32_t q, int32_t n_lanes, int32_t n_seed, int32_t n_plan, const char *layout, int32_t *out, int64_t cap);
+
+/* The device pools of a context (miniprot_amd/csrc/dev_ctx.h): every pool registers with its context under its
+ * name when the context is created, in the same order in every context of a process.  sibling 0: ctx itself; k >= 1: the k-th sibling
+ * context it owns (the DP lanes, seeders and planners of its last stream of batches).  Returns the number of registered pools and
+ * writes the name (a string the library owns) and the capacity in bytes (0: not allocated yet) of the first cap of them; names and
+ * caps may be NULL with cap 0.  MPA_ERR_ARG: no context, or no sibling of that number. */
+int32_t mpa_dbg_ctx_pools(const mpa_ctx_t *ctx, int32_t sibling, const char **names, int64_t *caps, int32_t cap);
 
 #ifdef __cplusplus
 }

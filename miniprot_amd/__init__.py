@@ -669,6 +669,21 @@ def dbg_stream_plan_for(q, lanes=5, seeders=3, planners=4, layout=None):
     return _stream_plan_of(out[:n])
 
 
+def dbg_ctx_pools(ctx, sibling=0):
+    """mpa_dbg_ctx_pools(): the device pools a context (sibling 0) or its sibling number `sibling` has registered, in registration
+    order, as a list of (name, capacity in bytes); None when the context has no sibling of that number."""
+    f = dbg_lib().mpa_dbg_ctx_pools
+    f.restype = C.c_int32
+    f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
+    n = f(ctx.h, sibling, None, None, 0)
+    if n < 0:
+        return None
+    names = (C.c_char_p * n)()
+    caps = (C.c_int64 * n)()
+    _check(min(f(ctx.h, sibling, names, caps, n), 0))
+    return [(names[k].decode(), int(caps[k])) for k in range(n)]
+
+
 ROUND2_DECLINED = 1  # MPA_DBG_ROUND2_DECLINED (include/mpamd_dbg.h)
 ROUND2_REC = ("plan_waits", "round_waits", "bytes_up", "task_bytes_up", "bytes_down", "pool_bytes_down", "pool_bytes_fetched", "prep_bound", "max_nl", "max_al", "n_pool", "reserved")
 

@@ -4,9 +4,12 @@
 // defines it, everything across units goes through the host functions declared here and in mpa_internal.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
 #include <time.h>
 #include <algorithm>
-#include <functional>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <atomic>
@@ -34,6 +37,8 @@ struct DpPool;                            // the DP worker pool's block of devic
 extern std::atomic<long long> g_dev_bytes, g_pool_growths;
 extern thread_local bool tl_alloc_failed;                 // the last pool request of this thread could not be met (device seeding then declines instead of failing)
 
+// A block of device memory and its owner: freed when the owner goes, counted in g_dev_bytes while it is held.  take() and release()
+// are the only places that count.  Movable, so that a block built in a local can be handed over; not copyable.
 struct DevBuf {
 	void *p = nullptr;
 	size_t cap = 0;
@@ -42,35 +47,56 @@ struct DevBuf {
 	// (re)allocate sizes the pool for the largest request any of them has seen, and the first batches of a stream do the growing
 	// once for everybody instead of once per context (a growth is a hipFree: it waits for the whole device)
 	std::atomic<size_t> *hint = nullptr;
+	DevBuf() = default;
+	DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+	DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { release(); cap = o.cap, p = o.p; o.p = nullptr, o.cap = 0; } return *this; }   // (p last: a table is tested by its pointer)
+	~DevBuf() { release(); }
 	int ensure(size_t bytes);                // (dev_ctx.hip) at least `bytes`, with slack and the siblings' hint
 	int ensure_exact(size_t bytes);          // exactly `bytes` (the caller has added its own slack)
+	hipError_t take(size_t bytes);           // (dev_ctx.hip) what it holds goes, then a block of exactly `bytes`: no slack, no hint, no growth counted, tl_alloc_failed untouched
 	void release() { if (p) { (void)hipFree(p); g_dev_bytes -= (long long)cap; } p = nullptr, cap = 0; }
 	template<typename T> T *as() { return (T*)p; }
 };
 
+// a pool of a device context: it can only be declared with the registry of its owner and its name, so a context has no pool that
+// its report, its hints and mpa_dbg_ctx_pools do not know.  The registry lists the pools in declaration order, which is the same
+// in every context of a process: the position is the pool's identity across contexts (the siblings' hints).
+struct CtxPool;
+struct PoolRegistry { std::vector<CtxPool*> all; };
+struct CtxPool : DevBuf {
+	const char *const name;
+	CtxPool(PoolRegistry &reg, const char *name_) : name(name_) { reg.all.push_back(this); }
+	CtxPool(CtxPool &&) = delete;             // (the registry holds its address)
+};
+
+// a table of the resident index: exactly as large as it was asked for, read as a pointer to its elements
+template<typename T> struct DevTable : DevBuf {
+	operator T*() const { return (T*)p; }
+};
+
 struct DeviceIndex {
 	int device = -1;
-	uint8_t *seq = nullptr;
-	int64_t *ctg_off = nullptr, *ctg_len = nullptr;
-	uint32_t *kb = nullptr;                   // k-mer occurrence lists (block ids), uploaded on first GPU seeding call
-	size_t kb_bytes = 0;
-	int64_t *ki = nullptr;                    // bucket offsets of the k-mer table, uploaded on the first device sketch (dev_sketch_jobs)
-	size_t ki_bytes = 0;
-	uint32_t *bo = nullptr;                   // block offset of every (contig, strand), uploaded on the first device regions call (k_regions)
-	size_t bo_bytes = 0;
-	uint8_t *spsc = nullptr;                  // splice-score track (--spsc), uploaded with the genome when the index has one
-	size_t seq_bytes = 0, spsc_bytes = 0;     // bytes counted into g_dev_bytes for the genome and the track
+	DevTable<uint8_t> seq;
+	DevTable<int64_t> ctg_off, ctg_len;
+	DevTable<uint8_t> spsc;                   // splice-score track (--spsc), uploaded with the genome when the index has one
+	// uploaded on first use (dev_index_table):
+	DevTable<uint32_t> kb;                    // k-mer occurrence lists (block ids): the first GPU seeding call
+	DevTable<int64_t> ki;                     // bucket offsets of the k-mer table: the first device sketch (dev_sketch_jobs)
+	DevTable<uint32_t> bo;                    // block offset of every (contig, strand): the first device regions call (k_regions)
 };
 
 struct HostPinned {
 	void *p = nullptr;
 	size_t cap = 0;
+	HostPinned() = default;
+	HostPinned(const HostPinned &) = delete;
+	HostPinned &operator=(const HostPinned &) = delete;
+	~HostPinned() { release(); }
 	int ensure(size_t bytes) {
 		if (bytes <= cap) return MPA_OK;
-		if (p) (void)hipHostFree(p);
-		p = nullptr, cap = 0;
+		release();
 		const size_t want = bytes * 3 / 2 + 4096;   // (re-pinning host memory is slow: grow in big steps)
-		if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc failed"); return MPA_ERR_HIP; }
+		if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { p = nullptr; set_error("hipHostMalloc failed"); return MPA_ERR_HIP; }
 		cap = want;
 		return MPA_OK;
 	}
@@ -84,74 +110,45 @@ struct HostPinned {
 struct SeedHold { HostPinned h_pos, h_f, h_pred, h_a, h_U, h_A, h_R, h_P; };   // h_R (MPA_GPU_REGIONS=1): region records | refinement limits | regions per query
                                                                                 // h_P (MPA_GPU_PLANS=1): regions | plans | round-1 tasks | gap segments | counts per query
 
+// The groups of a context's memory, one per stage.  Each starts with the registry of its context, which the context hands it
+// (`SeedBufs seed{ pools }`); a pool is `CtxPool name{ reg, "name" }`, a pinned block a plain HostPinned member.
 struct SeedBufs {
-	DevBuf jobs, f, pred, mark, flag, idx, tmp, cfirst;
+	PoolRegistry &reg;
+	CtxPool jobs{ reg, "jobs" }, f{ reg, "f" }, pred{ reg, "pred" }, mark{ reg, "mark" }, flag{ reg, "flag" }, idx{ reg, "idx" }, tmp{ reg, "tmp" }, cfirst{ reg, "cfirst" };
 	HostPinned h_jobs;
 	SeedHold own;                                                          // results of a call without a holder of its own (blocking path, refinement)
-	DevBuf r_win, r_chunk, r_words, r_hits, r_count;      // refinement scan
-	DevBuf r_gmap;                                        // ... the k-mer tables of long queries (k_refine_gmap_build), grow-only
+	CtxPool r_win{ reg, "r_win" }, r_chunk{ reg, "r_chunk" }, r_words{ reg, "r_words" }, r_hits{ reg, "r_hits" }, r_count{ reg, "r_count" };   // refinement scan
+	CtxPool r_gmap{ reg, "r_gmap" };                                     // ... the k-mer tables of long queries (k_refine_gmap_build), grow-only
 	HostPinned h_rhits;
-	DevBuf pf_qfirst2, val64[2];                                            // first kept anchor of every query; the kept anchors' values
-	DevBuf s_meta, s_cur, s_cur2, s_kept, s_base, s_out, s_flag, dkey;      // k_seed_sift: segments + per-query tables, list cursors, per-segment results, dense keys
+	CtxPool pf_qfirst2{ reg, "pf_qfirst2" }, val64[2]{ { reg, "val64_0" }, { reg, "val64_1" } };   // first kept anchor of every query; the kept anchors' values
+	// k_seed_sift: segments + per-query tables, list cursors, per-segment results, dense keys
+	CtxPool s_meta{ reg, "s_meta" }, s_cur{ reg, "s_cur" }, s_cur2{ reg, "s_cur2" }, s_kept{ reg, "s_kept" }, s_base{ reg, "s_base" }, s_out{ reg, "s_out" }, s_flag{ reg, "s_flag" }, dkey{ reg, "dkey" };
 	HostPinned h_meta, h_back;                                             // ... their staging (up) and qfirst2 / flags / cfirst (down)
-	DevBuf k_in, k_cnt, k_bkt, k_q;                                         // device sketch (sketch_exec.hip): residue table + q_off + protein text; count and bucket per position; per-query counts, prefixes, cut-offs, flags
+	// device sketch (sketch_exec.hip): residue table + q_off + protein text; count and bucket per position; per-query counts, prefixes, cut-offs, flags
+	CtxPool k_in{ reg, "k_in" }, k_cnt{ reg, "k_cnt" }, k_bkt{ reg, "k_bkt" }, k_q{ reg, "k_q" };
 	HostPinned h_kin, h_kout;                                              // ... its staging (up) and qfirst / jfirst / cut-offs / flags (down)
-	DevBuf rg;                                                             // device regions (k_regions): records, limits and per-query scratch, carved up per call
-	DevBuf pl;                                                             // device plans (k_plans): records and per-query scratch, carved up per call
-	DevBuf x_all;                                                          // device chaining: views, extraction scratch, survivors, main-chain state, chains (carved up per call)
-	DevBuf rx_all, rx_keys;                                                // device refinement: pairing tables, pair keys (two buffers), chain state (carved up per call)
+	CtxPool rg{ reg, "rg" };                                             // device regions (k_regions): records, limits and per-query scratch, carved up per call
+	CtxPool pl{ reg, "pl" };                                             // device plans (k_plans): records and per-query scratch, carved up per call
+	CtxPool x_all{ reg, "x_all" };                                       // device chaining: views, extraction scratch, survivors, main-chain state, chains (carved up per call)
+	CtxPool rx_all{ reg, "rx_all" }, rx_keys{ reg, "rx_keys" };        // device refinement: pairing tables, pair keys (two buffers), chain state (carved up per call)
 	HostPinned h_xoff;                                                     // ... offsets of the chains of every query (down)
-	DevBuf c_a, c_f, c_pred, c_mark, c_flag, c_first, c_long;        // chain forward pass (k_chain_fwd, k_chain_fwd_wave: list of long runs + its counter)
+	// chain forward pass (k_chain_fwd, k_chain_fwd_wave: list of long runs + its counter)
+	CtxPool c_a{ reg, "c_a" }, c_f{ reg, "c_f" }, c_pred{ reg, "c_pred" }, c_mark{ reg, "c_mark" }, c_flag{ reg, "c_flag" }, c_first{ reg, "c_first" }, c_long{ reg, "c_long" };
 	HostPinned hc_a, hc_f, hc_pred;
 };
 
-
-} // namespace mpa
-
-using namespace mpa;
-
-struct mpa_ctx_s {
-	int device = 0;
-	hipStream_t stream = nullptr;
-	static const int kSide = 16;              // side streams: every kernel class of a batch runs concurrently
-	hipStream_t side[kSide] = {};
-	hipEvent_t ev[6] = {};
-	hipEvent_t fork_ev = nullptr;
-	hipEvent_t lev[2 * kSide] = {};           // start/stop pair per side-stream launch
-	DevBuf tasks, waves, chunks, qseq, rec, prof, tb, cig, ncig, score, extout, bnd, list, rowkey, cigd, cigoff, hkey, xg, units;
-	DevBuf lite, ckpt, wlist;                 // checkpointed traceback (dp_device.h): extension-bit words, checkpoints, the calls the walk takes
+// a DP round (dp_exec.hip, gs32_exec.hip)
+struct RoundBufs {
+	PoolRegistry &reg;
+	CtxPool tasks{ reg, "tasks" }, waves{ reg, "waves" }, chunks{ reg, "chunks" }, qseq{ reg, "qseq" }, rec{ reg, "rec" }, prof{ reg, "prof" }, tb{ reg, "tb" }, cig{ reg, "cig" }, ncig{ reg, "ncig" }, score{ reg, "score" };
+	CtxPool extout{ reg, "extout" }, bnd{ reg, "bnd" }, list{ reg, "list" }, rowkey{ reg, "rowkey" }, cigd{ reg, "cigd" }, cigoff{ reg, "cigoff" }, hkey{ reg, "hkey" }, xg{ reg, "xg" }, units{ reg, "units" };
+	CtxPool lite{ reg, "lite" }, ckpt{ reg, "ckpt" }, wlist{ reg, "wlist" };   // checkpointed traceback (dp_device.h): extension-bit words, checkpoints, the calls the walk takes
 	HostPinned h_up, h_down, h_pool;          // staging of a DP round's descriptors (host -> device) and of its results: no pageable copies, one wait
-	mpa_dp_stats_t stats = {};
-	mpa_dp_stats_t total = {};
-	size_t tb_budget = (size_t)8 << 30;       // bytes of traceback matrix per k_glob launch
-	int lite_min = 384;                       // rows from which a traceback call of <= 256 columns is checkpointed (MPA_DP_LITE_MIN; 0: never)
-	int lite_wide = 0;                        // ... 129..256 columns included (MPA_DP_LITE_WIDE; 0, the default until it has been measured: those keep the plain sweep)
-	std::vector<mpa_ctx_s*> siblings;         // extra contexts on the same device for concurrent sub-batches (owned)
-	SeedBufs seed;                            // buffers of the GPU seeding stage (seed_exec.hip)
-	hipEvent_t wait_ev = nullptr;             // blocking-sync event: a host thread that waits for the device SLEEPS (wait_stream)
-	int side_off = 0;                         // first side stream a round uses (lets the DP lanes of a stream of batches sit on different hardware queues)
-	hipStream_t seed_stream = nullptr;        // high-priority stream of the seeding kernels: short, and must not queue behind DP tails
-	// ---- what the stream plan (stream_plan.h) says about this context; the defaults are a context outside a stream of batches
-	bool one_stream = false;                  // a seeder or planner of a planned layout: its seeding stream IS its main stream
-	int side_cap = kSide;                     // side streams a DP round may create (0: its side launches take the main stream) ...
-	int side_cls = 0;                         // ... and their priority class (StreamClass)
-	mpa::StreamPlan *splan = nullptr;         // (root context only, owned) the plan its siblings were created by (mpa_dbg_stream_plan)
-	int split_wide = 0;                       // 1025..3072-column extension calls on X_SPLIT8 / X_SPLIT12 instead of k_ext_huge (MPA_DP_SPLIT_WIDE; 0, the default until it has been measured)
-	int huge_wg = 0;                          // X_HUGE calls of hwg::MIN_BLOCKS column blocks or more on k_ext_huge_wg, one wave per block (MPA_DP_HUGE_WG; 0, the default until it has been measured)
-	int64_t last_huge[4] = { 0, 0, 0, 0 };    // the last mpa_dp_run's X_HUGE calls on the one-wave kernel, on the workgroup kernel, the latter's column blocks and passes (mpa_dbg_dp_last_huge)
-	int64_t last_ext_calls[16] = { 0 };       // extension calls per DpClass in the last mpa_dp_run (mpa_dbg_dp_last_classes)
-	bool no_split = false;                    // this mpa_dp_run() repeats a round whose workgroup hand-off timed out: 512/1024-column calls go to k_ext_huge
-	int64_t handoff_retries = 0;              // how often that has happened on this context (mpa_dp_handoff_retries)
-	std::atomic<int64_t> n_waits{0};          // host waits on this context's streams so far (wait_stream): a resident DP round reports its own
-	std::vector<SeedHold*> holds;             // result holders of the stream pipeline's batches (owned; ctx_seed_hold)
-	struct PoolHints { std::atomic<size_t> dev[3][96]; };
-	PoolHints *hints = nullptr;               // (root context only, owned) high-water marks per pipeline role and pool
-	mpa_idx_build_stats_t idx_stats = {};     // what the last device index build on this context did (mpa_idx_build_last_stats)
-	std::vector<int64_t> idx_hist;            // ... and the histogram it planned its passes from (empty: one pass)
-	int64_t idx_budget_dbg = 0;               // (tests) exact key budget of the device index build in bytes, 0 = the default (mpa_dbg_idx_build_budget)
-	bool antidiag = false;                    // (measurement) the 32-column extension class runs on the anti-diagonal prototype, k_ext_antidiag (mpa_dbg_antidiag)
-	// ---- DP worker pool (dp_kernels.hip, k_dp_worker).  The pool itself belongs to the ROOT context of a device ...
-	mpa_ctx_s *root = nullptr;                // the context this one is a sibling of (nullptr: a root)
+};
+
+// the DP worker pool (dp_kernels.hip, k_dp_worker).  The pool itself belongs to the ROOT context of a device ...
+struct WorkerBufs {
+	PoolRegistry &reg;
 	DpPool *dp_pool = nullptr;                // (root) slots + arguments of every lane, one block of device memory
 	std::mutex pool_mu;                       // (root) guards pool creation, slot numbers and the interval list
 	int pool_slots = 0;                       // (root) slots handed out
@@ -165,49 +162,127 @@ struct mpa_ctx_s {
 	hipEvent_t arm_ev = nullptr;
 	struct WorkerLaunch { hipEvent_t e0, e1; };
 	std::vector<WorkerLaunch> wl_busy, wl_free;   // event pairs of worker launches not yet harvested / free for reuse
-	DevBuf dp_trace;                          // (MPA_DP_TRACE) per-unit start/end ticks of the current round
-	// ---- alignment statistics (stats_run.hip, MPA_GPU_STATS=1): grow-only, allocated by the first call that asks for them
-	DevBuf st_in, st_out;                     // tables | jobs | CIGAR words | protein text; per-alignment records | features
+	CtxPool dp_trace{ reg, "dp_trace" };      // (MPA_DP_TRACE) per-unit start/end ticks of the current round
+};
+
+// the walks over finished alignments (stats_run.hip): grow-only, allocated by the first call that asks for them
+struct WalkBufs {
+	PoolRegistry &reg;
+	// alignment statistics (MPA_GPU_STATS=1)
+	CtxPool st_in{ reg, "st_in" }, st_out{ reg, "st_out" };   // tables | jobs | CIGAR words | protein text; per-alignment records | features
 	HostPinned h_stats_up, h_stats_down;      // ... their staging: one block up, one block down
-	// ---- cs strings (stats_run.hip, MPA_GPU_CS=1): what goes up shares st_in / h_stats_up; grow-only, allocated by the first call
-	DevBuf cs_out;                            // lengths | slots
+	// cs strings (MPA_GPU_CS=1): what goes up shares st_in / h_stats_up
+	CtxPool cs_out{ reg, "cs_out" };          // lengths | slots
 	HostPinned h_cs_down;
-	// ---- residue rows (stats_run.hip, MPA_GPU_ROWS=1): the same again
-	DevBuf rows_out;                          // records | slots
+	// residue rows (MPA_GPU_ROWS=1): the same again
+	CtxPool rows_out{ reg, "rows_out" };      // records | slots
 	HostPinned h_rows_down;
-	// ---- accepted spans and region CIGARs (stats_run.hip, MPA_GPU_SPANS=1): grow-only, allocated by the first call that asks for them
-	DevBuf sp_in, sp_mid, sp_out;             // tables | plans | gap segments | round-1 results | text; k_spans' scratch; count | records | round-2 tasks
-	DevBuf sp_pool1;                          // the batch's round-1 CIGAR pool, kept across round 2 (which overwrites cigd)
-	DevBuf sp_in2, sp_asm, sp_cig;            // round-2 results | slot offsets (| a caller's round-2 pool); per-plan records; the assembled CIGARs
+};
+
+// accepted spans and region CIGARs (stats_run.hip, MPA_GPU_SPANS=1): grow-only, allocated by the first call that asks for them
+struct SpanBufs {
+	PoolRegistry &reg;
+	CtxPool sp_in{ reg, "sp_in" }, sp_mid{ reg, "sp_mid" }, sp_out{ reg, "sp_out" };   // tables | plans | gap segments | round-1 results | text; k_spans' scratch; count | records | round-2 tasks
+	CtxPool sp_pool1{ reg, "sp_pool1" };      // the batch's round-1 CIGAR pool, kept across round 2 (which overwrites cigd)
+	CtxPool sp_in2{ reg, "sp_in2" }, sp_asm{ reg, "sp_asm" }, sp_cig{ reg, "sp_cig" };   // round-2 results | slot offsets (| a caller's round-2 pool); per-plan records; the assembled CIGARs
 	HostPinned h_sp_up, h_sp_down, h_sp_up2, h_sp_down2;
-	// ---- the device planner of a DP round (dp_exec.hip, MPA_GPU_DPPLAN=1): grow-only, allocated by the first call that asks for them
-	DevBuf dpp;                               // raw tasks | query offsets | keys | block sums | units | the header and the sorted traceback calls | sort scratch
-	HostPinned h_dpp_up, h_dpp_down;          // ... its staging: one block up, one block down
 	struct SpansKeep { size_t off_plan = 0, off_seg = 0, off_rst1 = 0; int64_t n_plan = -1, n_pool1 = 0; } sp_keep;   // what dev_spans_round1 left for dev_spans_assemble
+};
+
+// the device planner of a DP round (dp_exec.hip, MPA_GPU_DPPLAN=1): grow-only, allocated by the first call that asks for them
+struct PlannerBufs {
+	PoolRegistry &reg;
+	CtxPool dpp{ reg, "dpp" };                // raw tasks | query offsets | keys | block sums | units | the header and the sorted traceback calls | sort scratch
+	HostPinned h_dpp_up, h_dpp_down;          // ... its staging: one block up, one block down
+};
+
+// What the environment says about every context of a pipeline: filled once for a root (ctx_knobs_from_env), handed to a sibling by
+// one assignment, read by dp_plan_knobs().  A new knob is a field here and a line there.
+struct CtxKnobs {
+	size_t tb_budget = (size_t)8 << 30;       // bytes of traceback matrix per k_glob launch (MPA_TB_BUDGET_MB)
+	int lite_min = 384;                       // rows from which a traceback call of <= 256 columns is checkpointed (MPA_DP_LITE_MIN; 0: never)
+	int lite_wide = 0;                        // ... 129..256 columns included (MPA_DP_LITE_WIDE; 0, the default until it has been measured: those keep the plain sweep)
+	int split_wide = 0;                       // 1025..3072-column extension calls on X_SPLIT8 / X_SPLIT12 instead of k_ext_huge (MPA_DP_SPLIT_WIDE; 0, the default until it has been measured)
+	int huge_wg = 0;                          // X_HUGE calls of hwg::MIN_BLOCKS column blocks or more on k_ext_huge_wg, one wave per block (MPA_DP_HUGE_WG; 0, the default until it has been measured)
+};
+
+} // namespace mpa
+
+using namespace mpa;
+
+struct mpa_ctx_s {
+	int device = 0;
+	hipStream_t stream = nullptr;
+	static const int kSide = 16;              // side streams: every kernel class of a batch runs concurrently
+	hipStream_t side[kSide] = {};
+	hipEvent_t ev[6] = {};
+	hipEvent_t fork_ev = nullptr;
+	hipEvent_t lev[2 * kSide] = {};           // start/stop pair per side-stream launch
+	hipEvent_t wait_ev = nullptr;             // blocking-sync event: a host thread that waits for the device SLEEPS (wait_stream)
+	int side_off = 0;                         // first side stream a round uses (lets the DP lanes of a stream of batches sit on different hardware queues)
+	hipStream_t seed_stream = nullptr;        // high-priority stream of the seeding kernels: short, and must not queue behind DP tails
+	CtxKnobs knobs;
+	// ---- the contexts of a device: a root and the siblings it owns
+	mpa_ctx_s *root = nullptr;                // the context this one is a sibling of (nullptr: a root)
+	std::vector<mpa_ctx_s*> siblings;         // extra contexts on the same device for concurrent sub-batches (owned)
+	// ---- what the stream plan (stream_plan.h) says about this context; the defaults are a context outside a stream of batches
+	bool one_stream = false;                  // a seeder or planner of a planned layout: its seeding stream IS its main stream
+	int side_cap = kSide;                     // side streams a DP round may create (0: its side launches take the main stream) ...
+	int side_cls = 0;                         // ... and their priority class (StreamClass)
+	std::unique_ptr<mpa::StreamPlan> splan;   // (root context only) the plan its siblings were created by (mpa_dbg_stream_plan)
+	// ---- device memory: every pool registers here when it is declared, in the order of the groups below
+	PoolRegistry pools;
+	std::unique_ptr<std::atomic<size_t>[]> hints;   // (root context only) high-water marks: [role][pool], 3 x pools.all.size() (ctx_set_role)
+	SeedBufs seed{ pools };                   // the seeding, chaining and refinement stages (seed_run.hip, refine_run.hip)
+	std::vector<std::unique_ptr<SeedHold>> holds;   // result holders of the stream pipeline's batches (ctx_seed_hold)
+	RoundBufs round{ pools };
+	WorkerBufs worker{ pools };
+	WalkBufs walks{ pools };
+	SpanBufs spans{ pools };
+	PlannerBufs planner{ pools };
+	// ---- what the DP rounds of this context did
+	mpa_dp_stats_t stats = {};
+	mpa_dp_stats_t total = {};
+	int64_t last_huge[4] = { 0, 0, 0, 0 };    // the last mpa_dp_run's X_HUGE calls on the one-wave kernel, on the workgroup kernel, the latter's column blocks and passes (mpa_dbg_dp_last_huge)
+	int64_t last_ext_calls[16] = { 0 };       // extension calls per DpClass in the last mpa_dp_run (mpa_dbg_dp_last_classes)
+	bool no_split = false;                    // this mpa_dp_run() repeats a round whose workgroup hand-off timed out: 512/1024-column calls go to k_ext_huge
+	int64_t handoff_retries = 0;              // how often that has happened on this context (mpa_dp_handoff_retries)
+	std::atomic<int64_t> n_waits{0};          // host waits on this context's streams so far (wait_stream): a resident DP round reports its own
+	bool antidiag = false;                    // (measurement) the 32-column extension class runs on the anti-diagonal prototype, k_ext_antidiag (mpa_dbg_antidiag)
+	// ---- the device index build (index_run.hip)
+	mpa_idx_build_stats_t idx_stats = {};     // what the last device index build on this context did (mpa_idx_build_last_stats)
+	std::vector<int64_t> idx_hist;            // ... and the histogram it planned its passes from (empty: one pass)
+	int64_t idx_budget_dbg = 0;               // (tests) exact key budget of the device index build in bytes, 0 = the default (mpa_dbg_idx_build_budget)
 };
 
 namespace mpa {
 
-// every device pool of a context, in a fixed order (the index is the pool's identity across contexts)
-template<typename F> static void ctx_each_devbuf(mpa_ctx_s *ctx, F f)
+// ---- rocPRIM through a scratch pool: ask for the scratch size, grow the pool, call.  `exact`: the pool grows to the size asked for
+// and no further (the index build in passes budgets its memory to the byte); otherwise with the pools' slack.
+// (Not for scratch that is no pool of its own: the device planner's two sorts work in a piece of `dpp` carved before either runs,
+// dp_exec.hip, and ask rocPRIM themselves; nor for calls that share one sizing -- the refinement's two scans, the pass build's first sort.)
+template<typename In, typename Out, typename T> static int dev_exclusive_scan(DevBuf &scratch, bool exact, In in, Out out, T init, size_t n, hipStream_t s)
 {
-	SeedBufs &B = ctx->seed;
-	DevBuf *all[] = { &ctx->tasks, &ctx->waves, &ctx->chunks, &ctx->qseq, &ctx->rec, &ctx->prof, &ctx->tb, &ctx->cig, &ctx->ncig,
-	                  &ctx->score, &ctx->extout, &ctx->bnd, &ctx->list, &ctx->rowkey, &ctx->cigd, &ctx->cigoff, &ctx->hkey, &ctx->xg, &ctx->units,
-	                  &B.jobs, &B.f, &B.pred, &B.mark, &B.flag, &B.idx, &B.tmp, &B.cfirst,
-	                  &B.r_win, &B.r_chunk, &B.r_words, &B.r_hits, &B.r_count,
-	                  &B.c_a, &B.c_f, &B.c_pred, &B.c_mark, &B.c_flag, &B.c_first, &B.c_long,
-	                  &B.pf_qfirst2, &B.val64[0], &B.val64[1],
-	                  &B.s_meta, &B.s_cur, &B.s_cur2, &B.s_kept, &B.s_base, &B.s_out, &B.s_flag, &B.dkey, &B.x_all, &B.rx_all, &B.rx_keys,
-	                  &ctx->lite, &ctx->ckpt, &ctx->wlist, &B.k_in, &B.k_cnt, &B.k_bkt, &B.k_q, &B.r_gmap, &ctx->st_in, &ctx->st_out, &B.rg, &B.pl, &ctx->cs_out, &ctx->rows_out,
-	                  &ctx->sp_in, &ctx->sp_mid, &ctx->sp_out, &ctx->sp_pool1, &ctx->sp_in2, &ctx->sp_asm, &ctx->sp_cig, &ctx->dpp };
-	int k = 0;
-	for (DevBuf *b : all) f(*b, k++);
+	size_t bytes = 0;
+	HIP_TRY(rocprim::exclusive_scan(nullptr, bytes, in, out, init, n, rocprim::plus<T>(), s));
+	if (int rc = exact ? scratch.ensure_exact(bytes + 256) : scratch.ensure(bytes + 256)) return rc;
+	HIP_TRY(rocprim::exclusive_scan(scratch.p, bytes, in, out, init, n, rocprim::plus<T>(), s));
+	return MPA_OK;
+}
+// keys_in[n] sorted by bits [bit0, bit1) into keys_out[n]
+template<typename K> static int dev_sort_keys(DevBuf &scratch, bool exact, K *keys_in, K *keys_out, size_t n, unsigned bit0, unsigned bit1, hipStream_t s)
+{
+	size_t bytes = 0;
+	HIP_TRY(rocprim::radix_sort_keys(nullptr, bytes, keys_in, keys_out, n, bit0, bit1, s));
+	if (int rc = exact ? scratch.ensure_exact(bytes + 256) : scratch.ensure(bytes + 256)) return rc;
+	HIP_TRY(rocprim::radix_sort_keys(scratch.p, bytes, keys_in, keys_out, n, bit0, bit1, s));
+	return MPA_OK;
 }
 
 // ---- dev_ctx.hip, for the stage drivers
 hipError_t wait_stream(mpa_ctx_t *ctx, hipStream_t s);                                   // wait for a stream, asleep
 hipError_t upload_large(void *dst, const void *src, size_t bytes, hipStream_t s);       // a large host array into device memory through pinned slices
+hipError_t dev_index_table(mpa_ctx_t *ctx, DevBuf &t, const void *src, size_t bytes, const char *note);   // a table of the resident index, uploaded on first use
 void ensure_seed_stream(mpa_ctx_t *ctx);                                                 // ctx->seed_stream, created on first use
 hipError_t create_stream_in_class(hipStream_t *s, int cls);                              // a non-blocking stream of a StreamClass (stream_plan.h)
 hipError_t ensure_dynamic_lds(const void *fn, int device, size_t bytes);                 // hipFuncSetAttribute(MaxDynamicSharedMemorySize), once per (kernel, device)

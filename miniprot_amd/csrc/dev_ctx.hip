@@ -24,8 +24,8 @@ int DevBuf::ensure(size_t bytes)
 	// (free, then allocate: measured -- round 3, call 18 -- a pool that keeps its old block until the stream is over and only
 	// hipMalloc()s pays 25 ms per growth instead of 6: the allocator hands the block just freed straight back, a fresh one is
 	// mapped)
-	if (p) { (void)hipFree(p); g_dev_bytes -= (long long)cap; ++g_pool_growths; }
-	p = nullptr, cap = 0;
+	if (p) ++g_pool_growths;
+	release();
 	// (round 5 tried an arena -- a few 8-GB chunks carved up on the host instead of ~180 hipMallocs in a cold run's first second:
 	// no gain, the cost of a cold start is the VOLUME of device memory the driver maps, ~100 GB in ~2.5 s, however it is asked for:
 	// profiles/r05_cli_cold_start.txt)
@@ -36,11 +36,9 @@ int DevBuf::ensure(size_t bytes)
 	want += std::max<size_t>(want / 8, std::min<size_t>(want / 3, (size_t)256 << 20)) + 4096;   // a third of slack up to 256 MB, an eighth beyond (round 4: every pool carried a third: 100 GB per rank)
 	size_t free_b = 0, total_b = 0;
 	if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && want > free_b - (free_b >> 4)) want = asked + 4096;
-	hipError_t e = hipMalloc(&p, want);
-	if (e != hipSuccess && want > asked + 4096) { (void)hipGetLastError(); want = asked + 4096; e = hipMalloc(&p, want); }
-	if (e != hipSuccess) { (void)hipGetLastError(); p = nullptr, tl_alloc_failed = true; set_error(std::string("hipMalloc(") + std::to_string(want) + "): " + hipGetErrorString(e)); return MPA_ERR_HIP; }
-	cap = want;
-	g_dev_bytes += (long long)cap;
+	hipError_t e = take(want);
+	if (e != hipSuccess && want > asked + 4096) { want = asked + 4096; e = take(want); }
+	if (e != hipSuccess) { tl_alloc_failed = true; set_error(std::string("hipMalloc(") + std::to_string(want) + "): " + hipGetErrorString(e)); return MPA_ERR_HIP; }
 	timing_note("    pool growth (device)", now_ms() - t0);
 	return MPA_OK;
 }
@@ -48,12 +46,19 @@ int DevBuf::ensure(size_t bytes)
 int DevBuf::ensure_exact(size_t bytes)
 {
 	if (bytes <= cap) return MPA_OK;
-	if (p) { (void)hipFree(p); g_dev_bytes -= (long long)cap; ++g_pool_growths; }
-	p = nullptr, cap = 0;
-	if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); p = nullptr, tl_alloc_failed = true; set_error("hipMalloc(" + std::to_string(bytes) + ") failed"); return MPA_ERR_HIP; }
+	if (p) ++g_pool_growths;
+	if (take(bytes) != hipSuccess) { tl_alloc_failed = true; set_error("hipMalloc(" + std::to_string(bytes) + ") failed"); return MPA_ERR_HIP; }
+	return MPA_OK;
+}
+
+hipError_t DevBuf::take(size_t bytes)
+{
+	release();
+	const hipError_t e = hipMalloc(&p, bytes);
+	if (e != hipSuccess) { (void)hipGetLastError(); p = nullptr; return e; }
 	cap = bytes;
 	g_dev_bytes += (long long)cap;
-	return MPA_OK;
+	return hipSuccess;
 }
 
 // Wait for everything enqueued on a stream -- asleep.  hipStreamSynchronize() spins on the completion signal by default; a
@@ -151,28 +156,43 @@ int dev_upload_index(mpa_ctx_t *ctx, mpa_idx_s *mi)
 	std::lock_guard<std::mutex> g(mu[ctx->device]);
 	if (mi->dev[ctx->device]) return MPA_OK;
 	HIP_TRY(hipSetDevice(ctx->device));
-	DeviceIndex *d = new DeviceIndex();
+	// (an upload that fails half-way gives everything back with the record: the caller may retry, e.g. on the host path, and must not leak HBM)
+	std::unique_ptr<DeviceIndex> d(new DeviceIndex());
 	d->device = ctx->device;
-	// (an upload that fails half-way gives everything back: the caller may retry, e.g. on the host path, and must not leak HBM)
-	struct Undo { DeviceIndex *d; ~Undo() { if (!d) return; (void)hipFree(d->seq); (void)hipFree(d->ctg_off); (void)hipFree(d->ctg_len); (void)hipFree(d->spsc); delete d; } } undo{ d };
 	const size_t n = mi->ctg.size();
 	std::vector<int64_t> off(n), len(n);
 	for (size_t i = 0; i < n; ++i) off[i] = mi->ctg[i].off, len[i] = mi->ctg[i].len;
-	HIP_TRY(hipMalloc((void**)&d->seq, mi->seq.size() + 16));
-	HIP_TRY(hipMalloc((void**)&d->ctg_off, n * 8 + 8));
-	HIP_TRY(hipMalloc((void**)&d->ctg_len, n * 8 + 8));
+	HIP_TRY(d->seq.take(mi->seq.size() + 16));
+	HIP_TRY(d->ctg_off.take(n * 8 + 8));
+	HIP_TRY(d->ctg_len.take(n * 8 + 8));
 	{ const double t0 = now_ms(); HIP_TRY(upload_large(d->seq, mi->seq.data(), mi->seq.size(), ctx->stream)); timing_note("index upload: packed genome", now_ms() - t0); }
 	HIP_TRY(hipMemcpy(d->ctg_off, off.data(), n * 8, hipMemcpyHostToDevice));
 	HIP_TRY(hipMemcpy(d->ctg_len, len.data(), n * 8, hipMemcpyHostToDevice));
 	if (!mi->spsc.empty()) {
-		HIP_TRY(hipMalloc((void**)&d->spsc, mi->spsc.size() + 16));
+		HIP_TRY(d->spsc.take(mi->spsc.size() + 16));
 		HIP_TRY(hipMemcpy(d->spsc, mi->spsc.data(), mi->spsc.size(), hipMemcpyHostToDevice));
 	}
-	d->seq_bytes = mi->seq.size() + 16, d->spsc_bytes = mi->spsc.empty() ? 0 : mi->spsc.size() + 16;   // (what was added is what dev_free_index takes off again)
-	mi->dev[ctx->device] = d;
-	undo.d = nullptr;
-	g_dev_bytes += (long long)(d->seq_bytes + d->spsc_bytes);
+	mi->dev[ctx->device] = d.release();
 	return MPA_OK;
+}
+
+// Table `t` of this device's resident index (kb, ki, bo), uploaded on first use: `bytes` of `src` into an allocation 16 bytes longer.
+// Several seeders get here at once: one of them uploads, under the device's lock, and the table shows only when it is complete.
+// hipErrorOutOfMemory: no device memory for it; another error: the copy's.  What the caller makes of either is its own business.
+hipError_t dev_index_table(mpa_ctx_t *ctx, DevBuf &t, const void *src, size_t bytes, const char *note)
+{
+	if (t.p) return hipSuccess;
+	static std::mutex mu[mpa_idx_s::kMaxDevices];             // (per device, like dev_upload_index)
+	std::lock_guard<std::mutex> g(mu[ctx->device]);
+	if (t.p) return hipSuccess;
+	DevBuf up;
+	if (up.take(bytes + 16) != hipSuccess) return hipErrorOutOfMemory;
+	const double t0 = now_ms();
+	const hipError_t e = upload_large(up.p, src, bytes, ctx->stream);
+	if (e != hipSuccess) { (void)hipGetLastError(); return e; }
+	timing_note(note, now_ms() - t0);
+	t = std::move(up);
+	return hipSuccess;
 }
 
 void dev_free_index(mpa_idx_s *mi)
@@ -180,12 +200,6 @@ void dev_free_index(mpa_idx_s *mi)
 	for (DeviceIndex *&d : mi->dev) {
 		if (!d) continue;
 		(void)hipSetDevice(d->device);
-		(void)hipFree(d->seq); (void)hipFree(d->ctg_off); (void)hipFree(d->ctg_len);
-		g_dev_bytes -= (long long)(d->seq_bytes + d->spsc_bytes);
-		if (d->kb) { (void)hipFree(d->kb); g_dev_bytes -= (long long)d->kb_bytes; }
-		if (d->ki) { (void)hipFree(d->ki); g_dev_bytes -= (long long)d->ki_bytes; }
-		if (d->bo) { (void)hipFree(d->bo); g_dev_bytes -= (long long)d->bo_bytes; }
-		if (d->spsc) (void)hipFree(d->spsc);
 		delete d;
 		d = nullptr;
 	}
@@ -215,6 +229,18 @@ int mpa_device_count(void)
 	return n;
 }
 
+// the context knobs as the environment sets them (read for every context that is created for itself; a sibling takes its root's)
+static CtxKnobs ctx_knobs_from_env(void)
+{
+	CtxKnobs k;
+	if (const char *s = getenv("MPA_TB_BUDGET_MB")) k.tb_budget = (size_t)atoll(s) << 20;
+	if (const char *s = getenv("MPA_DP_LITE_MIN")) k.lite_min = atoi(s);
+	if (const char *s = getenv("MPA_DP_LITE_WIDE")) k.lite_wide = atoi(s) != 0;
+	if (const char *s = getenv("MPA_DP_SPLIT_WIDE")) k.split_wide = atoi(s) != 0;
+	if (const char *s = getenv("MPA_DP_HUGE_WG")) k.huge_wg = atoi(s) != 0;
+	return k;
+}
+
 // cls < 0: a context of its own (mpa_ctx_create) -- a normal main stream, or a high one with MPA_PRIO_MAIN=1; otherwise the class
 // the stream plan gives this context's main stream
 static mpa_ctx_t *ctx_create_in_class(int device, int cls)
@@ -239,11 +265,7 @@ static mpa_ctx_t *ctx_create_in_class(int device, int cls)
 		mpa_ctx_destroy(ctx);
 		return nullptr;
 	}
-	if (const char *s = getenv("MPA_TB_BUDGET_MB")) ctx->tb_budget = (size_t)atoll(s) << 20;
-	if (const char *s = getenv("MPA_DP_LITE_MIN")) ctx->lite_min = atoi(s);
-	if (const char *s = getenv("MPA_DP_LITE_WIDE")) ctx->lite_wide = atoi(s) != 0;
-	if (const char *s = getenv("MPA_DP_SPLIT_WIDE")) ctx->split_wide = atoi(s) != 0;
-	if (const char *s = getenv("MPA_DP_HUGE_WG")) ctx->huge_wg = atoi(s) != 0;
+	ctx->knobs = ctx_knobs_from_env();
 	return ctx;
 }
 
@@ -256,22 +278,13 @@ void mpa_ctx_destroy(mpa_ctx_t *ctx)
 	ctx->siblings.clear();
 	(void)hipSetDevice(ctx->device);
 	if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-	if (ctx->worker_stream) { (void)hipStreamSynchronize(ctx->worker_stream); (void)hipStreamDestroy(ctx->worker_stream); }   // (workers exit by themselves once no slot has a unit left)
-	for (auto *v : { &ctx->wl_busy, &ctx->wl_free }) { for (auto &w : *v) { (void)hipEventDestroy(w.e0); (void)hipEventDestroy(w.e1); } v->clear(); }
-	if (ctx->arm_ev) (void)hipEventDestroy(ctx->arm_ev);
-	if (ctx->dp_done) (void)hipHostFree(ctx->dp_done);
-	if (ctx->pool_base) (void)hipEventDestroy(ctx->pool_base);
-	if (ctx->dp_pool) (void)hipFree(ctx->dp_pool);
-	ctx->dp_trace.release();
-	SeedBufs &B = ctx->seed;
-	ctx_each_devbuf(ctx, [](DevBuf &b, int) { b.release(); });
-	for (HostPinned *h : { &B.h_jobs, &B.h_rhits, &B.hc_a, &B.hc_f, &B.hc_pred, &B.h_meta, &B.h_back, &B.h_xoff, &B.h_kin, &B.h_kout, &ctx->h_up, &ctx->h_down, &ctx->h_pool, &ctx->h_stats_up, &ctx->h_stats_down, &ctx->h_cs_down, &ctx->h_rows_down, &ctx->h_sp_up, &ctx->h_sp_down, &ctx->h_sp_up2, &ctx->h_sp_down2, &ctx->h_dpp_up, &ctx->h_dpp_down }) h->release();
-	auto drop_hold = [](SeedHold &H) { for (HostPinned *h : { &H.h_pos, &H.h_f, &H.h_pred, &H.h_a, &H.h_U, &H.h_A, &H.h_R, &H.h_P }) h->release(); };
-	drop_hold(B.own);
-	for (SeedHold *H : ctx->holds) { drop_hold(*H); delete H; }
-	ctx->holds.clear();
-	delete ctx->hints, ctx->hints = nullptr;
-	delete ctx->splan, ctx->splan = nullptr;
+	WorkerBufs &W = ctx->worker;
+	if (W.worker_stream) { (void)hipStreamSynchronize(W.worker_stream); (void)hipStreamDestroy(W.worker_stream); }   // (workers exit by themselves once no slot has a unit left)
+	for (auto *v : { &W.wl_busy, &W.wl_free }) { for (auto &w : *v) { (void)hipEventDestroy(w.e0); (void)hipEventDestroy(w.e1); } v->clear(); }
+	if (W.arm_ev) (void)hipEventDestroy(W.arm_ev);
+	if (W.dp_done) (void)hipHostFree(W.dp_done);
+	if (W.pool_base) (void)hipEventDestroy(W.pool_base);
+	if (W.dp_pool) (void)hipFree(W.dp_pool);
 	for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
 	for (auto &e : ctx->lev) if (e) (void)hipEventDestroy(e);
 	if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
@@ -279,7 +292,7 @@ void mpa_ctx_destroy(mpa_ctx_t *ctx)
 	for (auto &st : ctx->side) if (st) (void)hipStreamDestroy(st);
 	if (ctx->seed_stream && ctx->seed_stream != ctx->stream) (void)hipStreamDestroy(ctx->seed_stream);
 	if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-	delete ctx;
+	delete ctx;                                            // (its pools, pinned blocks and result holders go with their members)
 }
 
 int mpa_idx_to_device(mpa_ctx_t *ctx, mpa_idx_t *mi) { return dev_upload_index(ctx, mi); }
@@ -290,26 +303,26 @@ int64_t mpa_pool_growths(void) { return (int64_t)g_pool_growths.load(); }
 } // extern "C"
 
 namespace mpa {
-// k-th sibling of a context: same device, own streams and buffers, created on first use
+// one more sibling of a root: same device, own streams and pools, the root's knobs (cls: as ctx_create_in_class takes it)
+static mpa_ctx_t *ctx_add_sibling(mpa_ctx_t *root, int cls)
+{
+	mpa_ctx_t *sb = ctx_create_in_class(root->device, cls);
+	if (!sb) return nullptr;
+	sb->root = root;
+	sb->knobs = root->knobs;
+	root->siblings.push_back(sb);
+	return sb;
+}
+// k-th sibling of a context, created on first use
 mpa_ctx_t *ctx_sibling(mpa_ctx_t *ctx, int k)
 {
 	if (k <= 0) return ctx;
-	while ((int)ctx->siblings.size() < k) {
-		mpa_ctx_t *sb = mpa_ctx_create(ctx->device);
-		if (!sb) return nullptr;
-		sb->tb_budget = ctx->tb_budget;
-		sb->lite_min = ctx->lite_min;
-		sb->lite_wide = ctx->lite_wide;
-		sb->split_wide = ctx->split_wide;
-		sb->huge_wg = ctx->huge_wg;
-		sb->root = ctx;
-		ctx->siblings.push_back(sb);
-	}
+	while ((int)ctx->siblings.size() < k) if (!ctx_add_sibling(ctx, -1)) return nullptr;
 	return ctx->siblings[k - 1];
 }
 void ctx_set_side_offset(mpa_ctx_t *ctx, int off) { ctx->side_off = off; }
 
-const StreamPlan *ctx_stream_plan(const mpa_ctx_t *root) { return root ? root->splan : nullptr; }
+const StreamPlan *ctx_stream_plan(const mpa_ctx_t *root) { return root ? root->splan.get() : nullptr; }
 
 // Siblings 1 .. lanes - 1 are the DP lanes behind the root (lane 0, whose normal main stream exists), then the seeders, then the
 // planners: the plan's creation order.  Between two streams of batches nothing is in flight on a sibling, so a plan that differs from
@@ -318,11 +331,11 @@ int ctx_apply_stream_plan(mpa_ctx_t *root, int n_lanes, int n_seed, int n_plan, 
 {
 	const StreamPlan p = stream_plan(ctx_hw_queues(), n_lanes, n_seed, n_plan, layout);
 	const int n_sib = p.n_lanes - 1 + p.n_seed + p.n_plan;
-	if (!root->splan || memcmp(root->splan, &p, sizeof p) != 0) {
+	if (!root->splan || memcmp(root->splan.get(), &p, sizeof p) != 0) {
 		for (mpa_ctx_s *sb : root->siblings) mpa_ctx_destroy(sb);
 		root->siblings.clear();
 		for (auto &st : root->side) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); st = nullptr; }   // (the root's own, of the old plan's class)
-		if (!root->splan) root->splan = new StreamPlan();
+		if (!root->splan) root->splan.reset(new StreamPlan());
 		*root->splan = p;
 	}
 	auto entry = [&](int k, const StreamSlot *&main, bool &lane) {       // sibling k (>= 1) of the plan
@@ -334,49 +347,50 @@ int ctx_apply_stream_plan(mpa_ctx_t *root, int n_lanes, int n_seed, int n_plan, 
 		const int k = (int)root->siblings.size() + 1;
 		const StreamSlot *main; bool lane;
 		entry(k, main, lane);
-		mpa_ctx_t *sb = ctx_create_in_class(root->device, p.layout == SL_LEGACY ? -1 : main->cls);
+		mpa_ctx_t *sb = ctx_add_sibling(root, p.layout == SL_LEGACY ? -1 : main->cls);
 		if (!sb) return MPA_ERR_HIP;
-		sb->tb_budget = root->tb_budget, sb->lite_min = root->lite_min, sb->lite_wide = root->lite_wide, sb->split_wide = root->split_wide, sb->huge_wg = root->huge_wg;
-		sb->root = root;
 		sb->one_stream = !lane && p.layout != SL_LEGACY;
 		if (lane) sb->side_cap = p.side_cap[k], sb->side_cls = p.side_cls[k];
-		root->siblings.push_back(sb);
 	}
 	return MPA_OK;
 }
-// `ctx` (the root itself or one of its siblings) plays part `role` of the root's stream pipeline: 0 DP lane, 1 seeder, 2 planner
+// `ctx` (the root itself or one of its siblings) plays part `role` of the root's stream pipeline: 0 DP lane, 1 seeder, 2 planner.
+// The hint table has a slot per role and registered pool: every context registers the same pools in the same order.
 void ctx_set_role(mpa_ctx_t *root, mpa_ctx_t *ctx, int role)
 {
-	if (!root->hints) {
-		root->hints = new mpa_ctx_s::PoolHints();
-		for (auto &r : root->hints->dev) for (auto &h : r) h.store(0);
-	}
-	mpa_ctx_s::PoolHints *H = root->hints;
-	ctx_each_devbuf(ctx, [&](DevBuf &b, int k) { b.hint = k < 96 ? &H->dev[role][k] : nullptr; });
+	const size_t n = ctx->pools.all.size();
+	if (!root->hints) root->hints.reset(new std::atomic<size_t>[3 * n]());
+	for (size_t k = 0; k < n; ++k) ctx->pools.all[k]->hint = &root->hints[(size_t)role * n + k];
 }
 SeedHold *ctx_seed_hold(mpa_ctx_t *ctx, int k)
 {
-	while ((int)ctx->holds.size() <= k) ctx->holds.push_back(new SeedHold());
-	return ctx->holds[(size_t)k];
+	while ((int)ctx->holds.size() <= k) ctx->holds.emplace_back(new SeedHold());
+	return ctx->holds[(size_t)k].get();
+}
+
+// the registered device pools of a root context (sibling 0) or of its sibling number `sibling`: their names and capacities in
+// registration order, as many as fit `cap`; returns their number, or -1 without such a context (mpa_dbg_ctx_pools)
+int32_t ctx_pool_list(const mpa_ctx_t *ctx, int32_t sibling, const char **names, int64_t *caps, int32_t cap)
+{
+	if (!ctx || sibling < 0 || sibling > (int32_t)ctx->siblings.size()) return -1;
+	const PoolRegistry &R = (sibling ? ctx->siblings[(size_t)sibling - 1] : ctx)->pools;
+	for (size_t k = 0; k < R.all.size() && (int32_t)k < cap; ++k) names[k] = R.all[k]->name, caps[k] = (int64_t)R.all[k]->cap;
+	return (int32_t)R.all.size();
 }
 
 // (MPA_TIMING) the device pools of a root context and its siblings, largest first: where the HBM of a pipeline goes
 void ctx_pool_report(mpa_ctx_t *root)
 {
-	static const char *const kName[] = { "tasks", "waves", "chunks", "qseq", "rec", "prof", "tb", "cig", "ncig", "score", "extout", "bnd", "list", "rowkey", "cigd", "cigoff", "hkey", "xg", "units",
-		"s.jobs", "s.f", "s.pred", "s.mark", "s.flag", "s.idx", "s.tmp", "s.cfirst", "s.r_win", "s.r_chunk", "s.r_words", "s.r_hits", "s.r_count",
-		"s.c_a", "s.c_f", "s.c_pred", "s.c_mark", "s.c_flag", "s.c_first", "s.c_long", "s.pf_qfirst2", "s.val64_0", "s.val64_1",
-		"s.s_meta", "s.s_cur", "s.s_cur2", "s.s_kept", "s.s_base", "s.s_out", "s.s_flag", "s.dkey", "s.x_all", "s.rx_all", "s.rx_keys", "lite", "ckpt", "wlist", "s.k_in", "s.k_cnt", "s.k_bkt", "s.k_q", "s.r_gmap", "st_in", "st_out" };
 	std::vector<mpa_ctx_t*> all{ root };
 	for (mpa_ctx_t *sb : root->siblings) all.push_back(sb);
 	size_t grand = 0;
 	for (size_t c = 0; c < all.size(); ++c) {
 		size_t tot = 0;
-		std::vector<std::pair<size_t, int>> big;
-		ctx_each_devbuf(all[c], [&](DevBuf &b, int k) { tot += b.cap; if (b.cap >= ((size_t)64 << 20)) big.push_back({ b.cap, k }); });
-		std::sort(big.rbegin(), big.rend());
+		std::vector<std::pair<size_t, const char*>> big;
+		for (const CtxPool *b : all[c]->pools.all) { tot += b->cap; if (b->cap >= ((size_t)64 << 20)) big.push_back({ b->cap, b->name }); }
+		std::stable_sort(big.begin(), big.end(), [](auto &x, auto &y) { return x.first > y.first; });
 		fprintf(stderr, "[mpa-pools] context %zu: %.2f GB;", c, tot / 1e9);
-		for (auto &x : big) fprintf(stderr, " %s %.2f", x.second < (int)(sizeof(kName) / sizeof(kName[0])) ? kName[x.second] : "?", x.first / 1e9);
+		for (auto &x : big) fprintf(stderr, " %s %.2f", x.second, x.first / 1e9);
 		fprintf(stderr, "\n");
 		grand += tot;
 	}

@@ -89,8 +89,8 @@ static const char *dp_trace_path()
 static int pool_attach(mpa_ctx_t *ctx)
 {
 	mpa_ctx_s *root = ctx->root ? ctx->root : ctx;
-	std::lock_guard<std::mutex> g(root->pool_mu);
-	if (!root->dp_pool) {
+	std::lock_guard<std::mutex> g(root->worker.pool_mu);
+	if (!root->worker.dp_pool) {
 		DpPool *p = nullptr;
 		HIP_TRY(hipMalloc((void**)&p, sizeof(DpPool)));
 		HIP_TRY(hipMemset(p, 0, sizeof(DpPool)));
@@ -98,17 +98,17 @@ static int pool_attach(mpa_ctx_t *ctx)
 		HIP_TRY(hipMemcpy(&p->ctl.budget, &budget, 4, hipMemcpyHostToDevice));
 		const int32_t acq = [] { const char *e = getenv("MPA_DP_ACQUIRE"); return e ? atoi(e) : 2; }();
 		HIP_TRY(hipMemcpy(&p->ctl.acquire_mode, &acq, 4, hipMemcpyHostToDevice));
-		HIP_TRY(hipEventCreate(&root->pool_base));
-		HIP_TRY(hipEventRecord(root->pool_base, root->stream));
-		root->dp_pool = p;
+		HIP_TRY(hipEventCreate(&root->worker.pool_base));
+		HIP_TRY(hipEventRecord(root->worker.pool_base, root->stream));
+		root->worker.dp_pool = p;
 	}
-	if (ctx->dp_slot < 0) {
-		if (root->pool_slots >= MPA_DP_SLOTS) { set_error("more than " + std::to_string(MPA_DP_SLOTS) + " contexts of one device run DP rounds"); return MPA_ERR_UNSUPPORTED; }
-		HIP_TRY(hipHostMalloc((void**)&ctx->dp_done, 64, hipHostMallocDefault));
-		*(volatile int32_t*)ctx->dp_done = 0;
-		HIP_TRY(hipStreamCreateWithFlags(&ctx->worker_stream, hipStreamNonBlocking));
-		HIP_TRY(hipEventCreateWithFlags(&ctx->arm_ev, hipEventDisableTiming));
-		ctx->dp_slot = root->pool_slots++;
+	if (ctx->worker.dp_slot < 0) {
+		if (root->worker.pool_slots >= MPA_DP_SLOTS) { set_error("more than " + std::to_string(MPA_DP_SLOTS) + " contexts of one device run DP rounds"); return MPA_ERR_UNSUPPORTED; }
+		HIP_TRY(hipHostMalloc((void**)&ctx->worker.dp_done, 64, hipHostMallocDefault));
+		*(volatile int32_t*)ctx->worker.dp_done = 0;
+		HIP_TRY(hipStreamCreateWithFlags(&ctx->worker.worker_stream, hipStreamNonBlocking));
+		HIP_TRY(hipEventCreateWithFlags(&ctx->worker.arm_ev, hipEventDisableTiming));
+		ctx->worker.dp_slot = root->worker.pool_slots++;
 	}
 	return MPA_OK;
 }
@@ -116,46 +116,46 @@ static int pool_attach(mpa_ctx_t *ctx)
 // workers then leave within microseconds) into the context's totals and the device's interval list
 void pool_harvest(mpa_ctx_t *ctx, bool wait)
 {
-	if (ctx->wl_busy.empty()) return;
+	if (ctx->worker.wl_busy.empty()) return;
 	mpa_ctx_s *root = ctx->root ? ctx->root : ctx;
 	(void)hipSetDevice(ctx->device);
-	if (wait) (void)wait_stream(ctx, ctx->worker_stream);
+	if (wait) (void)wait_stream(ctx, ctx->worker.worker_stream);
 	size_t keep = 0;
-	for (size_t k = 0; k < ctx->wl_busy.size(); ++k) {
-		mpa_ctx_s::WorkerLaunch w = ctx->wl_busy[k];
+	for (size_t k = 0; k < ctx->worker.wl_busy.size(); ++k) {
+		WorkerBufs::WorkerLaunch w = ctx->worker.wl_busy[k];
 		float a = 0, b = 0;
-		if (hipEventQuery(w.e1) == hipSuccess && hipEventElapsedTime(&a, root->pool_base, w.e0) == hipSuccess && hipEventElapsedTime(&b, root->pool_base, w.e1) == hipSuccess) {
+		if (hipEventQuery(w.e1) == hipSuccess && hipEventElapsedTime(&a, root->worker.pool_base, w.e0) == hipSuccess && hipEventElapsedTime(&b, root->worker.pool_base, w.e1) == hipSuccess) {
 			ctx->total.ms_round += (double)(b - a), ctx->total.launches_round++;
-			{ std::lock_guard<std::mutex> g(root->pool_mu); root->pool_iv.emplace_back(a, b); }
-			ctx->wl_free.push_back(w);
-		} else ctx->wl_busy[keep++] = w;
+			{ std::lock_guard<std::mutex> g(root->worker.pool_mu); root->worker.pool_iv.emplace_back(a, b); }
+			ctx->worker.wl_free.push_back(w);
+		} else ctx->worker.wl_busy[keep++] = w;
 	}
 	(void)hipGetLastError();
-	ctx->wl_busy.resize(keep);
+	ctx->worker.wl_busy.resize(keep);
 }
 // A round for the pool: the round's arguments (ha: pinned) and units into the lane's slot of the device's pool, the slot armed in
 // stream order behind everything the round reads, the lane's workers launched (a worker takes any lane's units: their stream is
 // never waited for by a round -- a round is complete when its last unit says so in pinned memory).  The unit list is in
-// ctx->units already: whole-workgroup units [0, n_group), then the one-wave units.  *gen: what pool_wait_round waits for.
+// ctx->round.units already: whole-workgroup units [0, n_group), then the one-wave units.  *gen: what pool_wait_round waits for.
 static int pool_launch_round(mpa_ctx_t *ctx, hipStream_t s, const ExtArgs &ea, const ExtWideArgs &wa, const GlobArgs &ga, DpRoundArgs *ha,
                              size_t n_units, size_t n_group, size_t round_lds, unsigned int *gen)
 {
 	int rc;
 	if ((rc = pool_attach(ctx))) return rc;
 	mpa_ctx_s *root = ctx->root ? ctx->root : ctx;
-	DpPool *pool = root->dp_pool;
+	DpPool *pool = root->worker.dp_pool;
 	int n_slots;
-	{ std::lock_guard<std::mutex> g(root->pool_mu); n_slots = root->pool_slots; }
-	ha->ea = ea, ha->wa = wa, ha->ga = ga, ha->units = ctx->units.as<DpUnit>(), ha->n_group = (int32_t)n_group, ha->pad_ = 0;
-	HIP_TRY(hipMemcpyAsync(&pool->args[ctx->dp_slot], ha, sizeof(DpRoundArgs), hipMemcpyHostToDevice, s));
+	{ std::lock_guard<std::mutex> g(root->worker.pool_mu); n_slots = root->worker.pool_slots; }
+	ha->ea = ea, ha->wa = wa, ha->ga = ga, ha->units = ctx->round.units.as<DpUnit>(), ha->n_group = (int32_t)n_group, ha->pad_ = 0;
+	HIP_TRY(hipMemcpyAsync(&pool->args[ctx->worker.dp_slot], ha, sizeof(DpRoundArgs), hipMemcpyHostToDevice, s));
 	long long *d_trace = nullptr;
 	if (dp_trace_path()) {
-		if ((rc = ctx->dp_trace.ensure(n_units * 16))) return rc;
-		HIP_TRY(hipMemsetAsync(ctx->dp_trace.p, 0, n_units * 16, s));
-		d_trace = ctx->dp_trace.as<long long>();
+		if ((rc = ctx->worker.dp_trace.ensure(n_units * 16))) return rc;
+		HIP_TRY(hipMemsetAsync(ctx->worker.dp_trace.p, 0, n_units * 16, s));
+		d_trace = ctx->worker.dp_trace.as<long long>();
 	}
-	*gen = ++ctx->dp_gen;
-	hipLaunchKernelGGL(k_dp_arm, dim3(1), dim3(1), 0, s, pool, ctx->dp_slot, (int)n_group, (int)(n_units - n_group), *gen, ctx->dp_done, d_trace);
+	*gen = ++ctx->worker.dp_gen;
+	hipLaunchKernelGGL(k_dp_arm, dim3(1), dim3(1), 0, s, pool, ctx->worker.dp_slot, (int)n_group, (int)(n_units - n_group), *gen, ctx->worker.dp_done, d_trace);
 	HIP_TRY(hipGetLastError());
 	// The workers go out on the lane's own stream (what follows the round on that stream then also waits for this launch's
 	// workers to run out of units of ANY lane; measured level with a stream of their own, 19.6 against 19.7 M residues/s).
@@ -163,29 +163,29 @@ static int pool_launch_round(mpa_ctx_t *ctx, hipStream_t s, const ExtArgs &ea, c
 	// when that stream lands on a queue another context's long kernels use, every round waits for them (the evidence run of
 	// round 5 measured 6.5 M residues/s that way: profiles/r05_experiments.txt).
 	static const bool own_stream = [] { const char *e = getenv("MPA_DP_WORKER_STREAM"); return e && atoi(e) != 0; }();
-	hipStream_t ws = own_stream ? ctx->worker_stream : s;
+	hipStream_t ws = own_stream ? ctx->worker.worker_stream : s;
 	if (own_stream) {
-		HIP_TRY(hipEventRecord(ctx->arm_ev, s));
-		HIP_TRY(hipStreamWaitEvent(ws, ctx->arm_ev, 0));
+		HIP_TRY(hipEventRecord(ctx->worker.arm_ev, s));
+		HIP_TRY(hipStreamWaitEvent(ws, ctx->worker.arm_ev, 0));
 	}
-	mpa_ctx_s::WorkerLaunch wl;
-	if (!ctx->wl_free.empty()) wl = ctx->wl_free.back(), ctx->wl_free.pop_back();
+	WorkerBufs::WorkerLaunch wl;
+	if (!ctx->worker.wl_free.empty()) wl = ctx->worker.wl_free.back(), ctx->worker.wl_free.pop_back();
 	else { HIP_TRY(hipEventCreate(&wl.e0)); HIP_TRY(hipEventCreate(&wl.e1)); }
 	HIP_TRY(ensure_dynamic_lds((const void*)k_dp_worker, ctx->device, round_lds));
 	static const int launch_cap = [] { const char *e = getenv("MPA_DP_LAUNCH_WORKERS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : dp_pool_budget(); }();
 	// a workgroup serves one workgroup unit at a time, or four one-wave units side by side
 	const unsigned grid = (unsigned)std::min<size_t>(n_group + (n_units - n_group + 3) / 4, (size_t)launch_cap);
 	HIP_TRY(hipEventRecord(wl.e0, ws));
-	hipLaunchKernelGGL(k_dp_worker, dim3(grid), dim3(256), round_lds, ws, pool, ctx->dp_slot, n_slots);
+	hipLaunchKernelGGL(k_dp_worker, dim3(grid), dim3(256), round_lds, ws, pool, ctx->worker.dp_slot, n_slots);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(wl.e1, ws));
-	ctx->wl_busy.push_back(wl);
+	ctx->worker.wl_busy.push_back(wl);
 	return MPA_OK;
 }
 // the round is complete when the last of its units has stored the round's generation into the lane's pinned word
 static int pool_wait_round(mpa_ctx_t *ctx, hipStream_t s, unsigned int gen, const DpUnit *units, size_t n_units)
 {
-	volatile int32_t *d = ctx->dp_done;
+	volatile int32_t *d = ctx->worker.dp_done;
 	const double t0 = now_ms();
 	for (int polls = 0; (unsigned int)*d != gen; ++polls) {
 		if (polls >= 8) { struct timespec ts = { 0, 100000L }; nanosleep(&ts, nullptr); }
@@ -199,12 +199,12 @@ static int pool_wait_round(mpa_ctx_t *ctx, hipStream_t s, unsigned int gen, cons
 	HIP_TRY(hipGetLastError());
 	if (const char *path = dp_trace_path()) {                             // (debug) one line per unit: who ran when
 		std::vector<long long> tr(2 * n_units);
-		HIP_TRY(hipMemcpy(tr.data(), ctx->dp_trace.p, n_units * 16, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(tr.data(), ctx->worker.dp_trace.p, n_units * 16, hipMemcpyDeviceToHost));
 		static std::mutex tmu;
 		std::lock_guard<std::mutex> g(tmu);
 		if (FILE *f = fopen(path, "a")) {
 			for (size_t k = 0; k < n_units; ++k)
-				fprintf(f, "%d\t%u\t%zu\t%d\t%d\t%lld\t%lld\n", ctx->dp_slot, gen, k, units[k].kind, units[k].prio, tr[2 * k], tr[2 * k + 1]);
+				fprintf(f, "%d\t%u\t%zu\t%d\t%d\t%lld\t%lld\n", ctx->worker.dp_slot, gen, k, units[k].kind, units[k].prio, tr[2 * k], tr[2 * k + 1]);
 			fclose(f);
 		}
 	}
@@ -213,9 +213,9 @@ static int pool_wait_round(mpa_ctx_t *ctx, hipStream_t s, unsigned int gen, cons
 // time during which at least one worker launch of the device was running
 static double pool_union_ms(mpa_ctx_s *root, bool reset)
 {
-	std::lock_guard<std::mutex> g(root->pool_mu);
-	std::vector<std::pair<float, float>> iv = root->pool_iv;
-	if (reset) root->pool_iv.clear();
+	std::lock_guard<std::mutex> g(root->worker.pool_mu);
+	std::vector<std::pair<float, float>> iv = root->worker.pool_iv;
+	if (reset) root->worker.pool_iv.clear();
 	std::sort(iv.begin(), iv.end());
 	double sum = 0, lo = 0, hi = -1;
 	for (auto &x : iv) {
@@ -304,7 +304,7 @@ static hipStream_t begin_side(DpRun &R, bool is_ext)
 }
 static void end_side(DpRun &R) { const int k = R.launches.back().side; (void)hipEventRecord(R.ctx->lev[2 * k + 1], R.side_stream(k)); }
 
-// a resident round's results pool (ctx->cigoff): off[n_glob] | call_off[n] | bsum[blocks] | head | rst[n] (header and records: one download)
+// a resident round's results pool (ctx->round.cigoff): off[n_glob] | call_off[n] | bsum[blocks] | head | rst[n] (header and records: one download)
 struct ResLayout {
 	size_t off, call_off, bsum, head, rst, end, n;
 	ResLayout(size_t n_, size_t n_glob) : n(n_)
@@ -322,21 +322,21 @@ static int dp_size_pools(DpRun &R)
 	mpa_ctx_t *ctx = R.ctx;
 	const DpPlan::Pools &z = R.plan.sz;
 	int rc;
-	if ((rc = ctx->tasks.ensure(z.tasks)) || (rc = ctx->chunks.ensure(z.chunks)) || (rc = ctx->qseq.ensure(z.qseq)) || (rc = ctx->rec.ensure(z.rec)) || (rc = ctx->prof.ensure(z.prof)) ||
-	    (rc = ctx->waves.ensure(z.waves)) || (rc = ctx->extout.ensure(z.extout)) || (rc = ctx->tb.ensure(z.tb)) || (rc = ctx->cig.ensure(z.cig)) || (rc = ctx->ncig.ensure(z.ncig)) ||
-	    (rc = ctx->lite.ensure(z.lite)) || (rc = ctx->ckpt.ensure(z.ckpt)) || (rc = ctx->wlist.ensure(z.wlist)) || (rc = ctx->score.ensure(z.score)) || (rc = ctx->rowkey.ensure(z.rowkey)) ||
-	    (rc = ctx->bnd.ensure(z.bnd)) || (rc = ctx->hkey.ensure(z.hkey)) || (rc = ctx->list.ensure(z.list)))
+	if ((rc = ctx->round.tasks.ensure(z.tasks)) || (rc = ctx->round.chunks.ensure(z.chunks)) || (rc = ctx->round.qseq.ensure(z.qseq)) || (rc = ctx->round.rec.ensure(z.rec)) || (rc = ctx->round.prof.ensure(z.prof)) ||
+	    (rc = ctx->round.waves.ensure(z.waves)) || (rc = ctx->round.extout.ensure(z.extout)) || (rc = ctx->round.tb.ensure(z.tb)) || (rc = ctx->round.cig.ensure(z.cig)) || (rc = ctx->round.ncig.ensure(z.ncig)) ||
+	    (rc = ctx->round.lite.ensure(z.lite)) || (rc = ctx->round.ckpt.ensure(z.ckpt)) || (rc = ctx->round.wlist.ensure(z.wlist)) || (rc = ctx->round.score.ensure(z.score)) || (rc = ctx->round.rowkey.ensure(z.rowkey)) ||
+	    (rc = ctx->round.bnd.ensure(z.bnd)) || (rc = ctx->round.hkey.ensure(z.hkey)) || (rc = ctx->round.list.ensure(z.list)))
 		return rc;
 	// Everything the device needs from the host goes through ONE pinned staging buffer (plan.up), so that no copy is
 	// staged by the runtime and the host never waits for one: a DP round is enqueued in one go and waited for once.
-	if ((rc = ctx->h_up.ensure(R.plan.up.end + 256))) return rc;
-	R.hup = ctx->h_up.as<char>();
+	if ((rc = ctx->round.h_up.ensure(R.plan.up.end + 256))) return rc;
+	R.hup = ctx->round.h_up.as<char>();
 	if (R.rz) {
 		// the dense pool at the plan's bound, the sum of cig_cap (its size is not known before the wait); offsets | offsets by call | block
 		// sums | header | result records in one pool; the download block with room for header and records
 		const ResLayout L((size_t)R.plan.cnt.n, R.plan.glob_ids.size());
 		R.dn_res = (R.plan.dn.end + 63) & ~(size_t)63;
-		if ((rc = ctx->cigd.ensure((size_t)R.plan.cig_total * 4 + 16)) || (rc = ctx->cigoff.ensure(L.end)) || (rc = ctx->h_down.ensure(R.dn_res + L.down_bytes()))) return rc;
+		if ((rc = ctx->round.cigd.ensure((size_t)R.plan.cig_total * 4 + 16)) || (rc = ctx->round.cigoff.ensure(L.end)) || (rc = ctx->round.h_down.ensure(R.dn_res + L.down_bytes()))) return rc;
 	}
 	return MPA_OK;
 }
@@ -355,24 +355,24 @@ static int dp_upload_and_prep(DpRun &R, const mpa_idx_t *mi, const mpa_dpopt_t *
 	memcpy(hup + P.up.q, q->seqs + q->q_off[0], (size_t)P.q_bytes);
 	if (up) memcpy(hup + P.up.waves, P.ewaves.data(), b_waves);
 	R.mark("    dp: buffers");
-	if (up) HIP_TRY(hipMemcpyAsync(ctx->tasks.p, hup + P.up.tasks, b_tasks, hipMemcpyHostToDevice, s));
-	if (up) HIP_TRY(hipMemcpyAsync(ctx->chunks.p, hup + P.up.chunks, b_chunks, hipMemcpyHostToDevice, s));
-	HIP_TRY(hipMemcpyAsync(ctx->qseq.p, hup + P.up.q, P.q_bytes, hipMemcpyHostToDevice, s));
-	if (up && b_waves) HIP_TRY(hipMemcpyAsync(ctx->waves.p, hup + P.up.waves, b_waves, hipMemcpyHostToDevice, s));
+	if (up) HIP_TRY(hipMemcpyAsync(ctx->round.tasks.p, hup + P.up.tasks, b_tasks, hipMemcpyHostToDevice, s));
+	if (up) HIP_TRY(hipMemcpyAsync(ctx->round.chunks.p, hup + P.up.chunks, b_chunks, hipMemcpyHostToDevice, s));
+	HIP_TRY(hipMemcpyAsync(ctx->round.qseq.p, hup + P.up.q, P.q_bytes, hipMemcpyHostToDevice, s));
+	if (up && b_waves) HIP_TRY(hipMemcpyAsync(ctx->round.waves.p, hup + P.up.waves, b_waves, hipMemcpyHostToDevice, s));
 	// (k_prep_rows writes every row of every call; only the padding the kernels prefetch behind the last call is cleared)
-	HIP_TRY(hipMemsetAsync((char*)ctx->rec.p + (size_t)(P.rec_total - P.rec_pad) * 4, 0, (size_t)P.rec_pad * 4, s));
-	if (P.n_wide_groups) HIP_TRY(hipMemsetAsync(ctx->rowkey.p, 0, (size_t)(P.n_wide_groups * 2 * P.key_stride * 4), s));
+	HIP_TRY(hipMemsetAsync((char*)ctx->round.rec.p + (size_t)(P.rec_total - P.rec_pad) * 4, 0, (size_t)P.rec_pad * 4, s));
+	if (P.n_wide_groups) HIP_TRY(hipMemsetAsync(ctx->round.rowkey.p, 0, (size_t)(P.n_wide_groups * 2 * P.key_stride * 4), s));
 	// split classes: boundary granules, then the per-group completion counters and the error flag; all zero before the launch (a granule's tag is row + 1)
 	if (P.n_split) {
 		int rc;
-		if ((rc = ctx->xg.ensure(P.sz.xg))) return rc;
-		HIP_TRY(hipMemsetAsync(ctx->xg.p, 0, P.xg_bytes + P.xg_tail, s));
+		if ((rc = ctx->round.xg.ensure(P.sz.xg))) return rc;
+		HIP_TRY(hipMemsetAsync(ctx->round.xg.p, 0, P.xg_bytes + P.xg_tail, s));
 	}
 	// extension calls wider than 1024 columns: keys (zeroed), then one GlobWave and one list entry per call
 	if (!P.huge_ids.empty()) {
 		const size_t n_huge = P.huge_ids.size();
-		HIP_TRY(hipMemsetAsync(ctx->hkey.p, 0, (size_t)P.hkey_total * 8, s));
-		R.d_hw = (GlobWave*)((char*)ctx->hkey.p + (((size_t)P.hkey_total * 8 + 15) & ~(size_t)15));
+		HIP_TRY(hipMemsetAsync(ctx->round.hkey.p, 0, (size_t)P.hkey_total * 8, s));
+		R.d_hw = (GlobWave*)((char*)ctx->round.hkey.p + (((size_t)P.hkey_total * 8 + 15) & ~(size_t)15));
 		R.d_hlist = (int32_t*)(R.d_hw + n_huge);
 		HIP_TRY(hipMemcpyAsync(R.d_hw, P.huge_waves.data(), sizeof(GlobWave) * n_huge, hipMemcpyHostToDevice, s));
 		HIP_TRY(hipMemcpyAsync(R.d_hlist, P.huge_ids.data(), 4 * n_huge, hipMemcpyHostToDevice, s));
@@ -396,29 +396,29 @@ static int dp_upload_and_prep(DpRun &R, const mpa_idx_t *mi, const mpa_dpopt_t *
 	// own queue; MPA_SHORT_KERNEL raises their wave priority instead.)
 	HIP_TRY(hipEventRecord(ctx->ev[0], s));
 	if (P.cnt.n_prep)
-		hipLaunchKernelGGL(k_prep_rows, dim3((unsigned)P.cnt.n_prep), dim3(256), 0, s, dg, ctx->tasks.as<DTask>(), ctx->chunks.as<PrepChunk>(), ctx->rec.as<uint32_t>(), dc, tabs);
-	hipLaunchKernelGGL(k_prep_prof, dim3((unsigned)P.cnt.n), dim3(256), 0, s, ctx->tasks.as<DTask>(), ctx->qseq.as<char>(), ctx->prof.as<int16_t>(), tabs);
+		hipLaunchKernelGGL(k_prep_rows, dim3((unsigned)P.cnt.n_prep), dim3(256), 0, s, dg, ctx->round.tasks.as<DTask>(), ctx->round.chunks.as<PrepChunk>(), ctx->round.rec.as<uint32_t>(), dc, tabs);
+	hipLaunchKernelGGL(k_prep_prof, dim3((unsigned)P.cnt.n), dim3(256), 0, s, ctx->round.tasks.as<DTask>(), ctx->round.qseq.as<char>(), ctx->round.prof.as<int16_t>(), tabs);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(ctx->ev[1], s));
 	R.mark("    dp: uploads + prep enqueued");
 
 	// the kernels' arguments
 	ExtArgs &ea = R.ea;
-	ea.tasks = ctx->tasks.as<DTask>(), ea.rec = ctx->rec.as<uint32_t>(), ea.prof = ctx->prof.as<int16_t>(), ea.out = ctx->extout.as<ExtOut>();
+	ea.tasks = ctx->round.tasks.as<DTask>(), ea.rec = ctx->round.rec.as<uint32_t>(), ea.prof = ctx->round.prof.as<int16_t>(), ea.out = ctx->round.extout.as<ExtOut>();
 	ea.c = dc, ea.pen = P.pen;
-	ea.lite = ctx->lite.as<uint32_t>(), ea.ckpt = ctx->ckpt.as<uint32_t>(), ea.score = ctx->score.as<int32_t>();
-	ea.waves = ctx->waves.as<ExtWave>();
+	ea.lite = ctx->round.lite.as<uint32_t>(), ea.ckpt = ctx->round.ckpt.as<uint32_t>(), ea.score = ctx->round.score.as<int32_t>();
+	ea.waves = ctx->round.waves.as<ExtWave>();
 	ExtWideArgs &wa = R.wa;
 	wa.tasks = ea.tasks, wa.rec = ea.rec, wa.prof = ea.prof, wa.out = ea.out, wa.c = dc, wa.pen = P.pen, wa.key_stride = P.key_stride;
-	wa.xg = P.n_split ? ctx->xg.as<unsigned long long>() : nullptr;
-	wa.done = P.n_split ? (int32_t*)((char*)ctx->xg.p + P.xg_bytes) : nullptr;
+	wa.xg = P.n_split ? ctx->round.xg.as<unsigned long long>() : nullptr;
+	wa.done = P.n_split ? (int32_t*)((char*)ctx->round.xg.p + P.xg_bytes) : nullptr;
 	wa.ticket = P.n_split ? wa.done + P.n_split : nullptr;
 	wa.err = P.n_split ? wa.ticket + P.n_split : nullptr;
-	wa.waves = ctx->waves.as<ExtWave>();                // absolute descriptor indices: the rowkey slot of group g is g - first wide group
-	wa.rowkey = ctx->rowkey.as<uint32_t>() - (int64_t)P.ext[X_W2].first * 2 * P.key_stride;
+	wa.waves = ctx->round.waves.as<ExtWave>();                // absolute descriptor indices: the rowkey slot of group g is g - first wide group
+	wa.rowkey = ctx->round.rowkey.as<uint32_t>() - (int64_t)P.ext[X_W2].first * 2 * P.key_stride;
 	GlobArgs &ga = R.ga;
-	ga.tasks = ctx->tasks.as<DTask>(), ga.rec = ctx->rec.as<uint32_t>(), ga.prof = ctx->prof.as<int16_t>();
-	ga.tb = ctx->tb.as<uint16_t>(), ga.bnd = ctx->bnd.as<int4>(), ga.score = ctx->score.as<int32_t>(), ga.c = dc, ga.rowkey64 = nullptr, ga.waves = nullptr;
+	ga.tasks = ctx->round.tasks.as<DTask>(), ga.rec = ctx->round.rec.as<uint32_t>(), ga.prof = ctx->round.prof.as<int16_t>();
+	ga.tb = ctx->round.tb.as<uint16_t>(), ga.bnd = ctx->round.bnd.as<int4>(), ga.score = ctx->round.score.as<int32_t>(), ga.c = dc, ga.rowkey64 = nullptr, ga.waves = nullptr;
 	return MPA_OK;
 }
 
@@ -439,19 +439,19 @@ static int dp_side_launches(DpRun &R)
 	if (!P.huge_ids.empty()) {                                         // block-major sweep with the traceback kernel's arithmetic, then the replay
 		const unsigned n_huge = (unsigned)P.huge_ids.size();
 		GlobArgs ha;
-		ha.tasks = ctx->tasks.as<DTask>(), ha.waves = R.d_hw, ha.rec = ctx->rec.as<uint32_t>(), ha.prof = ctx->prof.as<int16_t>();
-		ha.tb = nullptr, ha.bnd = ctx->bnd.as<int4>(), ha.score = nullptr, ha.c = R.dc, ha.rowkey64 = ctx->hkey.as<unsigned long long>();
+		ha.tasks = ctx->round.tasks.as<DTask>(), ha.waves = R.d_hw, ha.rec = ctx->round.rec.as<uint32_t>(), ha.prof = ctx->round.prof.as<int16_t>();
+		ha.tb = nullptr, ha.bnd = ctx->round.bnd.as<int4>(), ha.score = nullptr, ha.c = R.dc, ha.rowkey64 = ctx->round.hkey.as<unsigned long long>();
 		// MPA_DP_HUGE_WG: calls of hwg::MIN_BLOCKS column blocks or more on k_ext_huge_wg (one wave per block, no hand-off between
 		// workgroups: a repeated round and the worker pool take it too); both kernels go over the same list and each returns at
 		// once for the other's calls.  A kernel without a call in the list is not launched.
 		int64_t *lh = ctx->last_huge;                                   // (zero: mpa_dp_run_impl)
 		for (int32_t id : P.huge_ids) {
 			const int32_t nblk = hwg::n_blocks(P.tasks[id].ncol);
-			if (ctx->huge_wg && hwg::takes_wg(P.tasks[id].ncol)) ++lh[1], lh[2] += nblk, lh[3] += hwg::n_pass(nblk);
+			if (ctx->knobs.huge_wg && hwg::takes_wg(P.tasks[id].ncol)) ++lh[1], lh[2] += nblk, lh[3] += hwg::n_pass(nblk);
 			else ++lh[0];
 		}
 		if (timing_on()) fprintf(stderr, "[mpa-timing]   dp: huge calls: %lld on one wave, %lld on workgroups (%lld blocks, %lld passes)\n", (long long)lh[0], (long long)lh[1], (long long)lh[2], (long long)lh[3]);
-		const int32_t wg_min = ctx->huge_wg ? hwg::MIN_BLOCKS : 0;
+		const int32_t wg_min = ctx->knobs.huge_wg ? hwg::MIN_BLOCKS : 0;
 		hipStream_t st = begin_side(R, true);
 		if (lh[0]) {
 			if (P.wide_ge) hipLaunchKernelGGL(k_ext_huge<true>, dim3(n_huge), dim3(64), GLOB_NARROW_LDS, st, ha, wg_min);
@@ -463,8 +463,8 @@ static int dp_side_launches(DpRun &R)
 			else hipLaunchKernelGGL(k_ext_huge_wg<false>, dim3(n_huge), dim3(hwg::W * 64), 0, st, ha);
 			HIP_TRY(hipGetLastError());
 		}
-		hipLaunchKernelGGL(k_ext_replay, dim3(n_huge), dim3(64), 0, st, ctx->tasks.as<DTask>(), R.d_hlist, (int32_t)n_huge,
-		                   ctx->hkey.as<unsigned long long>(), ctx->extout.as<ExtOut>(), R.dc, P.pen);
+		hipLaunchKernelGGL(k_ext_replay, dim3(n_huge), dim3(64), 0, st, ctx->round.tasks.as<DTask>(), R.d_hlist, (int32_t)n_huge,
+		                   ctx->round.hkey.as<unsigned long long>(), ctx->round.extout.as<ExtOut>(), R.dc, P.pen);
 		HIP_TRY(hipGetLastError());
 		end_side(R);
 		ctx->stats.launches_ext++;
@@ -508,13 +508,13 @@ static int dp_launch_round(DpRun &R, GlobWave *d_gw)
 	hipStream_t s = R.s;
 	DpUnit *units = (DpUnit*)(R.hup + P.up.units);          // (pinned: the copy below needs no wait)
 	int rc;
-	if (!P.on_device && (rc = dp_plan_units(P, R.kn, units))) { set_error(P.err); return rc; }   // (on the device: the list is in ctx->units, its length in the plan)
+	if (!P.on_device && (rc = dp_plan_units(P, R.kn, units))) { set_error(P.err); return rc; }   // (on the device: the list is in ctx->round.units, its length in the plan)
 	const size_t n_units = P.n_units;
 	if (n_units == 0) return MPA_OK;
 	static const bool show_top = [] { const char *e = getenv("MPA_DP_TOP"); return e && atoi(e) != 0; }();
 	if (show_top && !P.on_device) fputs(dp_plan_top(P, R.kn).c_str(), stderr);
-	if ((rc = ctx->units.ensure(P.sz.units))) return rc;
-	if (!P.on_device) HIP_TRY(hipMemcpyAsync(ctx->units.p, units, P.sz.units, hipMemcpyHostToDevice, s));
+	if ((rc = ctx->round.units.ensure(P.sz.units))) return rc;
+	if (!P.on_device) HIP_TRY(hipMemcpyAsync(ctx->round.units.p, units, P.sz.units, hipMemcpyHostToDevice, s));
 	R.ga.waves = d_gw;
 	const size_t round_lds = dp_round_lds();
 	if (dp_pool_enabled()) {
@@ -523,7 +523,7 @@ static int dp_launch_round(DpRun &R, GlobWave *d_gw)
 	} else {
 		if (round_lds > 48 * 1024) HIP_TRY(ensure_dynamic_lds((const void*)k_dp_round, ctx->device, round_lds));
 		HIP_TRY(hipEventRecord(R.ev_round(0), s));
-		hipLaunchKernelGGL(k_dp_round, dim3((unsigned)n_units), dim3(256), round_lds, s, R.ea, R.wa, R.ga, ctx->units.as<DpUnit>());
+		hipLaunchKernelGGL(k_dp_round, dim3((unsigned)n_units), dim3(256), round_lds, s, R.ea, R.wa, R.ga, ctx->round.units.as<DpUnit>());
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipEventRecord(R.ev_round(1), s));
 	}
@@ -582,8 +582,8 @@ static int dp_tb_chunks(DpRun &R)
 			HIP_TRY(wait_stream(ctx, s));
 			R.add_chunk_times();                                           // (the previous chunk's sweep and walk)
 		}
-		int32_t *d_list = ctx->list.as<int32_t>();
-		GlobWave *d_gw = (GlobWave*)((char*)ctx->list.p + ((P.cnt.n * 4 + 63) & ~(size_t)63));
+		int32_t *d_list = ctx->round.list.as<int32_t>();
+		GlobWave *d_gw = (GlobWave*)((char*)ctx->round.list.p + ((P.cnt.n * 4 + 63) & ~(size_t)63));
 		if (!P.on_device) {
 			memcpy(hup + P.up.list, r.list.data(), r.n_list * 4);
 			memcpy(hup + P.up.gw, r.waves.data(), r.n_waves * sizeof(GlobWave));
@@ -591,7 +591,7 @@ static int dp_tb_chunks(DpRun &R)
 			HIP_TRY(hipMemcpyAsync(d_gw, hup + P.up.gw, r.n_waves * sizeof(GlobWave), hipMemcpyHostToDevice, s));
 		}
 		R.mark("    dp: traceback lists enqueued");
-		R.ga.tb = ctx->tb.as<uint16_t>();
+		R.ga.tb = ctx->round.tb.as<uint16_t>();
 		HIP_TRY(hipEventRecord(ctx->ev[3], s));
 		// every launch on its own stream (next to the extension classes in the first chunk); the walk needs them all
 		HIP_TRY(hipEventRecord(ctx->fork_ev, s));
@@ -616,8 +616,8 @@ static int dp_tb_chunks(DpRun &R)
 		}
 		for (size_t k = first_glob_launch; k < R.launches.size(); ++k) (void)hipStreamWaitEvent(s, ctx->lev[2 * R.launches[k].side + 1], 0);
 		HIP_TRY(hipEventRecord(ctx->ev[4], s));
-		hipLaunchKernelGGL(k_backtrack, dim3((unsigned)r.n_list), dim3(64), 0, s, ctx->tasks.as<DTask>(), d_list, (int32_t)r.n_list,
-		                   ctx->tb.as<uint16_t>(), ctx->cig.as<uint32_t>(), ctx->ncig.as<int32_t>());
+		hipLaunchKernelGGL(k_backtrack, dim3((unsigned)r.n_list), dim3(64), 0, s, ctx->round.tasks.as<DTask>(), d_list, (int32_t)r.n_list,
+		                   ctx->round.tb.as<uint16_t>(), ctx->round.cig.as<uint32_t>(), ctx->round.ncig.as<int32_t>());
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipEventRecord(ctx->ev[5], s));
 		R.glob_timed = true;                                              // (ev[3..5] are read after the next wait)
@@ -635,19 +635,19 @@ static int dp_walk(DpRun &R)
 	if (!P.n_lite) return MPA_OK;
 	if (!P.on_device) {
 		memcpy(R.hup + P.up.wl, P.glob_ids.data() + P.n_reg_glob, 4 * P.n_lite);
-		HIP_TRY(hipMemcpyAsync(ctx->wlist.p, R.hup + P.up.wl, 4 * P.n_lite, hipMemcpyHostToDevice, s));
+		HIP_TRY(hipMemcpyAsync(ctx->round.wlist.p, R.hup + P.up.wl, 4 * P.n_lite, hipMemcpyHostToDevice, s));
 	}
 	WalkArgs wk;
-	wk.ga = R.ga, wk.ga.waves = nullptr, wk.list = ctx->wlist.as<int32_t>(), wk.n_list = (int32_t)P.n_lite;
-	wk.lite = ctx->lite.as<uint32_t>(), wk.ckpt = ctx->ckpt.as<uint32_t>(), wk.cig = ctx->cig.as<uint32_t>(), wk.n_cigar = ctx->ncig.as<int32_t>();
-	wk.n_blocks = (unsigned long long*)((char*)ctx->wlist.p + ((P.n_lite * 4 + 63) & ~(size_t)63));
+	wk.ga = R.ga, wk.ga.waves = nullptr, wk.list = ctx->round.wlist.as<int32_t>(), wk.n_list = (int32_t)P.n_lite;
+	wk.lite = ctx->round.lite.as<uint32_t>(), wk.ckpt = ctx->round.ckpt.as<uint32_t>(), wk.cig = ctx->round.cig.as<uint32_t>(), wk.n_cigar = ctx->round.ncig.as<int32_t>();
+	wk.n_blocks = (unsigned long long*)((char*)ctx->round.wlist.p + ((P.n_lite * 4 + 63) & ~(size_t)63));
 	HIP_TRY(hipMemsetAsync(wk.n_blocks, 0, 8, s));
 	// (the list is sorted by class: one launch per class, with the LDS that class's block of direction words needs)
 	size_t at = 0;
 	for (int cls = T_LITE16; cls <= T_LITE_W4; ++cls) {
 		const size_t n_c = (size_t)P.walk_cnt[cls - T_LITE16];
 		if (n_c == 0) continue;
-		wk.list = ctx->wlist.as<int32_t>() + at, wk.n_list = (int32_t)n_c;
+		wk.list = ctx->round.wlist.as<int32_t>() + at, wk.n_list = (int32_t)n_c;
 		if (cls == T_LITE_W4) {                                            // behind their own sweep; more LDS than a launch gets unasked
 			if (R.l12_side >= 0) (void)hipStreamWaitEvent(s, ctx->lev[2 * R.l12_side + 1], 0);
 			HIP_TRY(ensure_dynamic_lds((const void*)k_walk, ctx->device, WALK_LDS(256)));
@@ -662,7 +662,7 @@ static int dp_walk(DpRun &R)
 
 // ---- 6'. (a resident round) behind the round's last kernel and in front of its one wait: the dense pool's offsets scanned over the sorted
 // traceback calls, every call's result record, the CIGARs gathered from the device's own offsets, header and records into the download
-// block.  The dense pool stays in ctx->cigd.
+// block.  The dense pool stays in ctx->round.cigd.
 static int dp_results_enqueue(DpRun &R)
 {
 	mpa_ctx_t *ctx = R.ctx;
@@ -671,10 +671,10 @@ static int dp_results_enqueue(DpRun &R)
 	const size_t n = P.cnt.n, n_glob = P.glob_ids.size();
 	const ResLayout L(n, n_glob);
 	static_assert(DPR_NHEAD * 8 <= 64, "the header has 64 bytes of the pool");
-	char *X = ctx->cigoff.as<char>();
+	char *X = ctx->round.cigoff.as<char>();
 	DpResDev D;
-	D.n = (int64_t)n, D.n_glob = (int64_t)n_glob, D.tasks = ctx->tasks.as<DTask>(), D.gids = R.rz->d_gids;
-	D.eo = ctx->extout.as<ExtOut>(), D.sc = ctx->score.as<int32_t>(), D.nc = ctx->ncig.as<int32_t>();
+	D.n = (int64_t)n, D.n_glob = (int64_t)n_glob, D.tasks = ctx->round.tasks.as<DTask>(), D.gids = R.rz->d_gids;
+	D.eo = ctx->round.extout.as<ExtOut>(), D.sc = ctx->round.score.as<int32_t>(), D.nc = ctx->round.ncig.as<int32_t>();
 	D.off = (int64_t*)(X + L.off), D.call_off = (int64_t*)(X + L.call_off), D.bsum = (int64_t*)(X + L.bsum), D.head = (int64_t*)(X + L.head), D.rst = (mpa_dp_rst_t*)(X + L.rst);
 	HIP_TRY(hipMemsetAsync(D.head, 0, 64, s));
 	const dim3 wg(TeamWG::W), g_glob((unsigned)dp_blocks((int64_t)n_glob, TeamWG::W)), g_calls((unsigned)dp_blocks((int64_t)n, TeamWG::W));
@@ -684,8 +684,8 @@ static int dp_results_enqueue(DpRun &R)
 		hipLaunchKernelGGL(k_dpr_offsets, g_glob, wg, 0, s, D);
 	}
 	hipLaunchKernelGGL(k_dpr_records, g_calls, wg, 0, s, D);
-	if (n_glob) hipLaunchKernelGGL(k_cigar_gather, dim3((unsigned)n_glob), dim3(64), 0, s, ctx->tasks.as<DTask>(), D.gids, D.off, (int32_t)n_glob,
-	                               ctx->ncig.as<int32_t>(), ctx->cig.as<uint32_t>(), ctx->cigd.as<uint32_t>());
+	if (n_glob) hipLaunchKernelGGL(k_cigar_gather, dim3((unsigned)n_glob), dim3(64), 0, s, ctx->round.tasks.as<DTask>(), D.gids, D.off, (int32_t)n_glob,
+	                               ctx->round.ncig.as<int32_t>(), ctx->round.cig.as<uint32_t>(), ctx->round.cigd.as<uint32_t>());
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(R.hdn + R.dn_res, X + L.head, L.down_bytes(), hipMemcpyDeviceToHost, s));
 	R.rz->d_rst = D.rst, R.rz->rec.bytes_down += (int64_t)L.down_bytes();
@@ -703,19 +703,19 @@ static int dp_join_and_download(DpRun &R)
 	for (auto &l : R.launches) (void)hipStreamWaitEvent(s, ctx->lev[2 * l.side + 1], 0);
 	HIP_TRY(hipEventRecord(ctx->ev[2], s));
 	int rc;
-	if ((rc = ctx->h_down.ensure(P.dn.end))) return rc;
-	char *hdn = R.hdn = ctx->h_down.as<char>();
+	if ((rc = ctx->round.h_down.ensure(P.dn.end))) return rc;
+	char *hdn = R.hdn = ctx->round.h_down.as<char>();
 	*(int32_t*)(hdn + P.dn.err) = 0;
 	if (R.rz) { if ((rc = dp_results_enqueue(R))) return rc; }           // (resident: the records come down instead of what they are made from)
-	else if (P.cnt.n_ext) HIP_TRY(hipMemcpyAsync(hdn + P.dn.eo, ctx->extout.p, sizeof(ExtOut) * n, hipMemcpyDeviceToHost, s));
+	else if (P.cnt.n_ext) HIP_TRY(hipMemcpyAsync(hdn + P.dn.eo, ctx->round.extout.p, sizeof(ExtOut) * n, hipMemcpyDeviceToHost, s));
 	if (P.cnt.n_glob && !R.rz) {
-		HIP_TRY(hipMemcpyAsync(hdn + P.dn.sc, ctx->score.p, n * 4, hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipMemcpyAsync(hdn + P.dn.nc, ctx->ncig.p, n * 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(hdn + P.dn.sc, ctx->round.score.p, n * 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(hdn + P.dn.nc, ctx->round.ncig.p, n * 4, hipMemcpyDeviceToHost, s));
 	}
 	if (P.n_split) HIP_TRY(hipMemcpyAsync(hdn + P.dn.err, R.wa.err, 4, hipMemcpyDeviceToHost, s));
 	*(unsigned long long*)(hdn + P.dn.wb) = 0;
 	if (R.rz) R.rz->rec.bytes_down += (P.n_split ? 4 : 0) + (P.n_lite ? 8 : 0);
-	if (P.n_lite) HIP_TRY(hipMemcpyAsync(hdn + P.dn.wb, (char*)ctx->wlist.p + ((P.n_lite * 4 + 63) & ~(size_t)63), 8, hipMemcpyDeviceToHost, s));
+	if (P.n_lite) HIP_TRY(hipMemcpyAsync(hdn + P.dn.wb, (char*)ctx->round.wlist.p + ((P.n_lite * 4 + 63) & ~(size_t)63), 8, hipMemcpyDeviceToHost, s));
 	R.mark("    dp: round enqueued");
 	HIP_TRY(wait_stream(ctx, s));
 	R.mark("    dp: round (wait)");
@@ -752,18 +752,18 @@ static int dp_assemble(DpRun &R, mpa_dp_rst_t *rst, uint32_t **cigar_pool, int64
 	uint32_t *pool = (uint32_t*)malloc((size_t)(pool_n > 0 ? pool_n : 1) * 4);
 	if (pool_n > 0) {
 		int rc;
-		if ((rc = ctx->cigd.ensure((size_t)pool_n * 4)) || (rc = ctx->cigoff.ensure(n_glob * 12 + 64)) || (rc = ctx->h_pool.ensure((size_t)pool_n * 4))) { free(pool); return rc; }
-		int64_t *d_off = ctx->cigoff.as<int64_t>();
+		if ((rc = ctx->round.cigd.ensure((size_t)pool_n * 4)) || (rc = ctx->round.cigoff.ensure(n_glob * 12 + 64)) || (rc = ctx->round.h_pool.ensure((size_t)pool_n * 4))) { free(pool); return rc; }
+		int64_t *d_off = ctx->round.cigoff.as<int64_t>();
 		int32_t *d_ids = (int32_t*)(d_off + n_glob);
 		memcpy(R.hup + P.up.ids, P.glob_ids.data(), n_glob * 4);
 		HIP_TRY(hipMemcpyAsync(d_off, dense_off, n_glob * 8, hipMemcpyHostToDevice, s));
 		HIP_TRY(hipMemcpyAsync(d_ids, R.hup + P.up.ids, n_glob * 4, hipMemcpyHostToDevice, s));
-		hipLaunchKernelGGL(k_cigar_gather, dim3((unsigned)n_glob), dim3(64), 0, s, ctx->tasks.as<DTask>(), d_ids, d_off, (int32_t)n_glob,
-		                   ctx->ncig.as<int32_t>(), ctx->cig.as<uint32_t>(), ctx->cigd.as<uint32_t>());
+		hipLaunchKernelGGL(k_cigar_gather, dim3((unsigned)n_glob), dim3(64), 0, s, ctx->round.tasks.as<DTask>(), d_ids, d_off, (int32_t)n_glob,
+		                   ctx->round.ncig.as<int32_t>(), ctx->round.cig.as<uint32_t>(), ctx->round.cigd.as<uint32_t>());
 		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(ctx->h_pool.p, ctx->cigd.p, (size_t)pool_n * 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(ctx->round.h_pool.p, ctx->round.cigd.p, (size_t)pool_n * 4, hipMemcpyDeviceToHost, s));
 		HIP_TRY(wait_stream(ctx, s));
-		memcpy(pool, ctx->h_pool.p, (size_t)pool_n * 4);
+		memcpy(pool, ctx->round.h_pool.p, (size_t)pool_n * 4);
 	}
 	std::vector<int64_t> off_of(P.cnt.n, 0);
 	for (size_t k = 0; k < n_glob; ++k) off_of[P.glob_ids[k]] = dense_off[k];
@@ -811,9 +811,9 @@ static DpPlanKnobs dp_plan_knobs(const mpa_ctx_t *ctx)
 	static const bool ext_dual = [] { const char *e = getenv("MPA_DP_EXT_DUAL"); return !e || atoi(e) != 0; }();
 	static const bool unit_prio = [] { const char *e = getenv("MPA_DP_PRIO"); return !e || atoi(e) != 0; }();   // (MPA_DP_PRIO=0: measurement)
 	DpPlanKnobs kn;
-	kn.lite_min = ctx->lite_min, kn.lite_wide = ctx->lite_wide, kn.no_split = ctx->no_split, kn.antidiag = ctx->antidiag, kn.pool = dp_pool_enabled();
-	kn.split_wide = ctx->split_wide && !kn.pool && !kn.no_split;
-	kn.ext_dual = ext_dual, kn.unit_prio = unit_prio, kn.tb_budget = (int64_t)ctx->tb_budget;
+	kn.lite_min = ctx->knobs.lite_min, kn.lite_wide = ctx->knobs.lite_wide, kn.no_split = ctx->no_split, kn.antidiag = ctx->antidiag, kn.pool = dp_pool_enabled();
+	kn.split_wide = ctx->knobs.split_wide && !kn.pool && !kn.no_split;
+	kn.ext_dual = ext_dual, kn.unit_prio = unit_prio, kn.tb_budget = (int64_t)ctx->knobs.tb_budget;
 	return kn;
 }
 
@@ -838,8 +838,8 @@ static int dev_dp_plan_run(mpa_ctx_t *ctx, hipStream_t s, const int64_t *d_ctg_l
 	tl_alloc_failed = false;
 	auto declined_alloc = [](int rc) { if (tl_alloc_failed) { tl_alloc_failed = false; return (int)MPA_ERR_UNSUPPORTED; } return rc; };
 	int rc;
-	if ((rc = ctx->h_dpp_up.ensure(up_end + 256))) return MPA_ERR_UNSUPPORTED;
-	char *hup = ctx->h_dpp_up.as<char>();
+	if ((rc = ctx->planner.h_dpp_up.ensure(up_end + 256))) return MPA_ERR_UNSUPPORTED;
+	char *hup = ctx->planner.h_dpp_up.as<char>();
 	if (!rz) memcpy(hup + up_raw, in, sizeof(mpa_dp_task_t) * N);
 	int64_t max_nl = rz ? rz->in.max_nl : 0, max_al = rz ? rz->in.max_al : 0;
 	const int64_t prep_bound = rz ? rz->in.prep_bound : dp_plan_prep_bound((const mpa_dp_task_t*)(hup + up_raw), n, &max_nl, &max_al);
@@ -856,18 +856,18 @@ static int dev_dp_plan_run(mpa_ctx_t *ctx, hipStream_t s, const int64_t *d_ctg_l
 	const size_t o_ukey = carve(8 * U), o_uskey = carve(8 * U), o_head = carve(sizeof(DpDevHead)), o_gids = carve(4 * N), o_tmp = carve(std::max(tmp_calls, tmp_units) + 16);
 	const size_t down_bytes = o_gids + 4 * N - o_head;
 	// the executor's pools at their bounds (size_buffers() asks for no more once the plan is known: nothing the planner wrote moves)
-	if ((rc = ctx->dpp.ensure(carve.at)) || (rc = ctx->tasks.ensure(sizeof(DTask) * N)) || (rc = ctx->chunks.ensure(sizeof(PrepChunk) * ((size_t)prep_bound + 1))) ||
-	    (rc = ctx->waves.ensure(sizeof(ExtWave) * (N + 16))) || (rc = ctx->list.ensure(N * 4 + 128 + sizeof(GlobWave) * (N + 1))) ||
-	    (rc = ctx->units.ensure(sizeof(DpUnit) * U)) || (rc = ctx->wlist.ensure(N * 4 + 128)))
+	if ((rc = ctx->planner.dpp.ensure(carve.at)) || (rc = ctx->round.tasks.ensure(sizeof(DTask) * N)) || (rc = ctx->round.chunks.ensure(sizeof(PrepChunk) * ((size_t)prep_bound + 1))) ||
+	    (rc = ctx->round.waves.ensure(sizeof(ExtWave) * (N + 16))) || (rc = ctx->round.list.ensure(N * 4 + 128 + sizeof(GlobWave) * (N + 1))) ||
+	    (rc = ctx->round.units.ensure(sizeof(DpUnit) * U)) || (rc = ctx->round.wlist.ensure(N * 4 + 128)))
 		return declined_alloc(rc);
-	if ((rc = ctx->h_dpp_down.ensure(down_bytes + 256))) return MPA_ERR_UNSUPPORTED;
-	char *X = ctx->dpp.as<char>();
+	if ((rc = ctx->planner.h_dpp_down.ensure(down_bytes + 256))) return MPA_ERR_UNSUPPORTED;
+	char *X = ctx->planner.dpp.as<char>();
 	DpDevPlan D;
 	D.n = n, D.n_ubound = (int64_t)U, D.n_ctg = n_ctg, D.n_seq = q->n_seq, D.opt = dp_plan_opt(opt), D.kn = kn;
 	D.raw = rz ? rz->in.d_tasks : (const mpa_dp_task_t*)(X + o_up + up_raw), D.q_off = (const int64_t*)(X + o_up + up_qoff), D.ctg_len = d_ctg_len ? d_ctg_len : (const int64_t*)(X + o_up + up_ctg);
-	D.tasks = ctx->tasks.as<DTask>(), D.chunks = ctx->chunks.as<PrepChunk>(), D.waves = ctx->waves.as<ExtWave>(), D.list = ctx->list.as<int32_t>();
-	D.gw = (GlobWave*)((char*)ctx->list.p + ((N * 4 + 63) & ~(size_t)63));                    // (where dp_tb_chunks puts a chunk's waves)
-	D.units = ctx->units.as<DpUnit>(), D.wlist = ctx->wlist.as<int32_t>();
+	D.tasks = ctx->round.tasks.as<DTask>(), D.chunks = ctx->round.chunks.as<PrepChunk>(), D.waves = ctx->round.waves.as<ExtWave>(), D.list = ctx->round.list.as<int32_t>();
+	D.gw = (GlobWave*)((char*)ctx->round.list.p + ((N * 4 + 63) & ~(size_t)63));                    // (where dp_tb_chunks puts a chunk's waves)
+	D.units = ctx->round.units.as<DpUnit>(), D.wlist = ctx->round.wlist.as<int32_t>();
 	D.key = (uint64_t*)(X + o_key), D.skey = (uint64_t*)(X + o_skey), D.bsum = (DpSums*)(X + o_bsum), D.ubuf = (DpUnit*)(X + o_ubuf);
 	D.ukey = (uint64_t*)(X + o_ukey), D.uskey = (uint64_t*)(X + o_uskey), D.head = (DpDevHead*)(X + o_head), D.gids = (int32_t*)(X + o_gids);
 	HIP_TRY(hipMemcpyAsync(X + o_up, hup, up_end, hipMemcpyHostToDevice, s));
@@ -882,7 +882,7 @@ static int dev_dp_plan_run(mpa_ctx_t *ctx, hipStream_t s, const int64_t *d_ctg_l
 	HIP_TRY(rocprim::radix_sort_keys(X + o_tmp, tmp_units, D.ukey, D.uskey, U, 0u, 64u, s));
 	hipLaunchKernelGGL(k_dpp_units_out, g_units, wg, 0, s, D);
 	HIP_TRY(hipGetLastError());
-	char *hdn = ctx->h_dpp_down.as<char>();
+	char *hdn = ctx->planner.h_dpp_down.as<char>();
 	HIP_TRY(hipMemcpyAsync(hdn, X + o_head, down_bytes, hipMemcpyDeviceToHost, s));
 	HIP_TRY(wait_stream(ctx, s));
 	*head = (const DpDevHead*)hdn, *gids = (const int32_t*)(hdn + (o_gids - o_head));
@@ -948,7 +948,7 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 	// them -- the round is planned again with those calls on k_ext_huge (same results), before anything of it is enqueued
 	if (kn.split_wide && plan.ext_wide[0].cnt + plan.ext_wide[1].cnt > 0) {
 		tl_alloc_failed = false;
-		if (ctx->xg.ensure(plan.sz.xg)) {
+		if (ctx->round.xg.ensure(plan.sz.xg)) {
 			tl_alloc_failed = false;
 			if (rz) { set_error("round 2 resident: the boundary pool of the 2048/3072-column extension classes cannot grow"); return MPA_ERR_UNSUPPORTED; }
 			if (timing_on()) fprintf(stderr, "[mpa-timing]   2048/3072-column extension classes declined (%zu bytes of boundary granules): those calls on the one-wave int32 sweep\n", plan.sz.xg);
@@ -1030,17 +1030,17 @@ int dp_run_resident(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *opt,
 int dp_fetch_pool(mpa_ctx_t *ctx, int64_t n_pool, uint32_t **pool)
 {
 	*pool = nullptr;
-	if (n_pool < 0 || (size_t)n_pool * 4 > ctx->cigd.cap) { set_error("dp_fetch_pool: no dense CIGAR pool of that size on this context"); return MPA_ERR_ARG; }
+	if (n_pool < 0 || (size_t)n_pool * 4 > ctx->round.cigd.cap) { set_error("dp_fetch_pool: no dense CIGAR pool of that size on this context"); return MPA_ERR_ARG; }
 	HIP_TRY(hipSetDevice(ctx->device));
 	uint32_t *p = (uint32_t*)malloc((size_t)(n_pool > 0 ? n_pool : 1) * 4);
 	if (!p) { set_error("out of host memory"); return MPA_ERR_HIP; }
 	if (n_pool > 0) {
 		int rc;
-		if ((rc = ctx->h_pool.ensure((size_t)n_pool * 4))) { free(p); return rc; }
-		if (hipMemcpyAsync(ctx->h_pool.p, ctx->cigd.p, (size_t)n_pool * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || wait_stream(ctx, ctx->stream) != hipSuccess) {
+		if ((rc = ctx->round.h_pool.ensure((size_t)n_pool * 4))) { free(p); return rc; }
+		if (hipMemcpyAsync(ctx->round.h_pool.p, ctx->round.cigd.p, (size_t)n_pool * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || wait_stream(ctx, ctx->stream) != hipSuccess) {
 			free(p), set_error("dp_fetch_pool: the download failed"); return MPA_ERR_HIP;
 		}
-		memcpy(p, ctx->h_pool.p, (size_t)n_pool * 4);
+		memcpy(p, ctx->round.h_pool.p, (size_t)n_pool * 4);
 	}
 	*pool = p;
 	return MPA_OK;
@@ -1092,16 +1092,16 @@ int64_t dev_dp_plan_dbg(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int32_t n_ctg, c
 	std::vector<int32_t> wl((size_t)H.n_lite);
 	P.tasks.resize((size_t)H.n), P.prep.resize((size_t)H.n_prep), P.ewaves.resize((size_t)H.n_ewaves);
 	auto down = [&](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
-	HIP_TRY(down(P.tasks.data(), ctx->tasks.p, sizeof(DTask) * P.tasks.size()));
-	HIP_TRY(down(P.prep.data(), ctx->chunks.p, sizeof(PrepChunk) * P.prep.size()));
-	HIP_TRY(down(P.ewaves.data(), ctx->waves.p, sizeof(ExtWave) * P.ewaves.size()));
-	HIP_TRY(down(units.data(), ctx->units.p, sizeof(DpUnit) * units.size()));
-	HIP_TRY(down(wl.data(), ctx->wlist.p, 4 * wl.size()));
+	HIP_TRY(down(P.tasks.data(), ctx->round.tasks.p, sizeof(DTask) * P.tasks.size()));
+	HIP_TRY(down(P.prep.data(), ctx->round.chunks.p, sizeof(PrepChunk) * P.prep.size()));
+	HIP_TRY(down(P.ewaves.data(), ctx->round.waves.p, sizeof(ExtWave) * P.ewaves.size()));
+	HIP_TRY(down(units.data(), ctx->round.units.p, sizeof(DpUnit) * units.size()));
+	HIP_TRY(down(wl.data(), ctx->round.wlist.p, 4 * wl.size()));
 	if (!P.chunks.empty()) {
 		DpTbChunk &r = P.chunks[0];
 		r.list.resize(r.n_list), r.waves.resize(r.n_waves);
-		HIP_TRY(down(r.list.data(), ctx->list.p, 4 * r.n_list));
-		HIP_TRY(down(r.waves.data(), (char*)ctx->list.p + (((size_t)H.n * 4 + 63) & ~(size_t)63), sizeof(GlobWave) * r.n_waves));
+		HIP_TRY(down(r.list.data(), ctx->round.list.p, 4 * r.n_list));
+		HIP_TRY(down(r.waves.data(), (char*)ctx->round.list.p + (((size_t)H.n * 4 + 63) & ~(size_t)63), sizeof(GlobWave) * r.n_waves));
 		for (size_t k = 0; k < r.n_list; ++k) if (r.list[k] != P.glob_ids[k]) { set_error("device DP plan: the chunk's call list is not the sorted order"); return MPA_ERR_HIP; }
 	}
 	for (size_t k = 0; k < wl.size(); ++k) if (wl[k] != P.glob_ids[P.n_reg_glob + k]) { set_error("device DP plan: the walk list is not the sorted order"); return MPA_ERR_HIP; }
@@ -1114,10 +1114,10 @@ int dev_dp_run_resident_dbg(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt
 {
 	HIP_TRY(hipSetDevice(ctx->device));
 	int rc;
-	if ((rc = ctx->sp_out.ensure(sizeof(mpa_dp_task_t) * (size_t)n + 64))) return rc;
-	HIP_TRY(hipMemcpy(ctx->sp_out.p, in, sizeof(mpa_dp_task_t) * (size_t)n, hipMemcpyHostToDevice));
+	if ((rc = ctx->spans.sp_out.ensure(sizeof(mpa_dp_task_t) * (size_t)n + 64))) return rc;
+	HIP_TRY(hipMemcpy(ctx->spans.sp_out.p, in, sizeof(mpa_dp_task_t) * (size_t)n, hipMemcpyHostToDevice));
 	DpResidentIn ri;
-	if ((rc = dev_task_bounds(ctx, ctx->sp_out.as<mpa_dp_task_t>(), n, ri))) return rc;
+	if ((rc = dev_task_bounds(ctx, ctx->spans.sp_out.as<mpa_dp_task_t>(), n, ri))) return rc;
 	rec[7] = ri.prep_bound, rec[8] = ri.max_nl, rec[9] = ri.max_al;
 	DpResidentRec rr;
 	int64_t words = 0;

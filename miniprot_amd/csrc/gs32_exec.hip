@@ -68,20 +68,20 @@ extern "C" int mpa_dp_run32(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt
 				walk.push_back((int32_t)k);
 			}
 		}
-		if ((uint64_t)tb_total * 2 > ctx->tb_budget) { set_error("mpa_dp_run32: traceback matrices of this batch exceed the context's traceback budget; pass fewer calls"); return MPA_ERR_UNSUPPORTED; }
+		if ((uint64_t)tb_total * 2 > ctx->knobs.tb_budget) { set_error("mpa_dp_run32: traceback matrices of this batch exceed the context's traceback budget; pass fewer calls"); return MPA_ERR_UNSUPPORTED; }
 		rec_total += max_nl + 96;
 		const int64_t q_bytes = q->q_off[q->n_seq] - q->q_off[0];
 		int rc;
-		if ((rc = ctx->tasks.ensure(sizeof(DTask) * (size_t)n)) || (rc = ctx->chunks.ensure(sizeof(PrepChunk) * chunks.size() + 16)) ||
-		    (rc = ctx->qseq.ensure((size_t)q_bytes + 16)) || (rc = ctx->rec.ensure((size_t)rec_total * 4)) || (rc = ctx->prof.ensure((size_t)prof_total * 2 + 16)) ||
-		    (rc = ctx->bnd.ensure((size_t)scr_total * 4 + 16)) || (rc = ctx->tb.ensure((size_t)tb_total * 2 + 16)) || (rc = ctx->cig.ensure((size_t)cig_total * 4 + 16)) ||
-		    (rc = ctx->ncig.ensure((size_t)n * 4)) || (rc = ctx->score.ensure((size_t)n * 4)) || (rc = ctx->list.ensure(walk.size() * 4 + 16)))
+		if ((rc = ctx->round.tasks.ensure(sizeof(DTask) * (size_t)n)) || (rc = ctx->round.chunks.ensure(sizeof(PrepChunk) * chunks.size() + 16)) ||
+		    (rc = ctx->round.qseq.ensure((size_t)q_bytes + 16)) || (rc = ctx->round.rec.ensure((size_t)rec_total * 4)) || (rc = ctx->round.prof.ensure((size_t)prof_total * 2 + 16)) ||
+		    (rc = ctx->round.bnd.ensure((size_t)scr_total * 4 + 16)) || (rc = ctx->round.tb.ensure((size_t)tb_total * 2 + 16)) || (rc = ctx->round.cig.ensure((size_t)cig_total * 4 + 16)) ||
+		    (rc = ctx->round.ncig.ensure((size_t)n * 4)) || (rc = ctx->round.score.ensure((size_t)n * 4)) || (rc = ctx->round.list.ensure(walk.size() * 4 + 16)))
 			return rc;
-		HIP_TRY(hipMemcpyAsync(ctx->tasks.p, T.data(), sizeof(DTask) * (size_t)n, hipMemcpyHostToDevice, s));
-		if (!chunks.empty()) HIP_TRY(hipMemcpyAsync(ctx->chunks.p, chunks.data(), sizeof(PrepChunk) * chunks.size(), hipMemcpyHostToDevice, s));
-		HIP_TRY(hipMemcpyAsync(ctx->qseq.p, q->seqs + q->q_off[0], (size_t)q_bytes, hipMemcpyHostToDevice, s));
-		if (!walk.empty()) HIP_TRY(hipMemcpyAsync(ctx->list.p, walk.data(), walk.size() * 4, hipMemcpyHostToDevice, s));
-		HIP_TRY(hipMemsetAsync(ctx->ncig.p, 0, (size_t)n * 4, s));
+		HIP_TRY(hipMemcpyAsync(ctx->round.tasks.p, T.data(), sizeof(DTask) * (size_t)n, hipMemcpyHostToDevice, s));
+		if (!chunks.empty()) HIP_TRY(hipMemcpyAsync(ctx->round.chunks.p, chunks.data(), sizeof(PrepChunk) * chunks.size(), hipMemcpyHostToDevice, s));
+		HIP_TRY(hipMemcpyAsync(ctx->round.qseq.p, q->seqs + q->q_off[0], (size_t)q_bytes, hipMemcpyHostToDevice, s));
+		if (!walk.empty()) HIP_TRY(hipMemcpyAsync(ctx->round.list.p, walk.data(), walk.size() * 4, hipMemcpyHostToDevice, s));
+		HIP_TRY(hipMemsetAsync(ctx->round.ncig.p, 0, (size_t)n * 4, s));
 		HIP_TRY(hipStreamSynchronize(s));                                      // (the sources above are pageable vectors of this call)
 		DevTables tabs;
 		memcpy(tabs.aa20, tab_aa20(), 256);
@@ -94,19 +94,19 @@ extern "C" int mpa_dp_run32(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt
 		dc.wide_ge = wide_ge;
 		DevGenome dg{ mi->dev[ctx->device]->seq, mi->dev[ctx->device]->ctg_off, mi->dev[ctx->device]->ctg_len, mi->dev[ctx->device]->spsc, mi->l_seq };
 		if (!chunks.empty())
-			hipLaunchKernelGGL(k_prep_rows, dim3((unsigned)chunks.size()), dim3(256), 0, s, dg, ctx->tasks.as<DTask>(), ctx->chunks.as<PrepChunk>(), ctx->rec.as<uint32_t>(), dc, tabs);
-		hipLaunchKernelGGL(k_prep_prof, dim3((unsigned)n), dim3(256), 0, s, ctx->tasks.as<DTask>(), ctx->qseq.as<char>(), ctx->prof.as<int16_t>(), tabs);
-		hipLaunchKernelGGL(k_gs32, dim3((unsigned)n), dim3(64), 0, s, ctx->tasks.as<DTask>(), (int32_t)n, ctx->rec.as<uint32_t>(), ctx->prof.as<int16_t>(),
-		                   ctx->bnd.as<int32_t>(), ctx->tb.as<uint16_t>(), ctx->score.as<int32_t>(), Gs32Params{ opt->go, opt->ge, 0, opt->fs, wide_ge });
+			hipLaunchKernelGGL(k_prep_rows, dim3((unsigned)chunks.size()), dim3(256), 0, s, dg, ctx->round.tasks.as<DTask>(), ctx->round.chunks.as<PrepChunk>(), ctx->round.rec.as<uint32_t>(), dc, tabs);
+		hipLaunchKernelGGL(k_prep_prof, dim3((unsigned)n), dim3(256), 0, s, ctx->round.tasks.as<DTask>(), ctx->round.qseq.as<char>(), ctx->round.prof.as<int16_t>(), tabs);
+		hipLaunchKernelGGL(k_gs32, dim3((unsigned)n), dim3(64), 0, s, ctx->round.tasks.as<DTask>(), (int32_t)n, ctx->round.rec.as<uint32_t>(), ctx->round.prof.as<int16_t>(),
+		                   ctx->round.bnd.as<int32_t>(), ctx->round.tb.as<uint16_t>(), ctx->round.score.as<int32_t>(), Gs32Params{ opt->go, opt->ge, 0, opt->fs, wide_ge });
 		if (!walk.empty())
-			hipLaunchKernelGGL(k_backtrack, dim3((unsigned)walk.size()), dim3(64), 0, s, ctx->tasks.as<DTask>(), ctx->list.as<int32_t>(), (int32_t)walk.size(),
-			                   ctx->tb.as<uint16_t>(), ctx->cig.as<uint32_t>(), ctx->ncig.as<int32_t>());
+			hipLaunchKernelGGL(k_backtrack, dim3((unsigned)walk.size()), dim3(64), 0, s, ctx->round.tasks.as<DTask>(), ctx->round.list.as<int32_t>(), (int32_t)walk.size(),
+			                   ctx->round.tb.as<uint16_t>(), ctx->round.cig.as<uint32_t>(), ctx->round.ncig.as<int32_t>());
 		HIP_TRY(hipGetLastError());
 		std::vector<int32_t> sc((size_t)n), nc((size_t)n);
 		std::vector<uint32_t> cig((size_t)cig_total + 1);
-		HIP_TRY(hipMemcpyAsync(sc.data(), ctx->score.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipMemcpyAsync(nc.data(), ctx->ncig.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-		if (cig_total) HIP_TRY(hipMemcpyAsync(cig.data(), ctx->cig.p, (size_t)cig_total * 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(sc.data(), ctx->round.score.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(nc.data(), ctx->round.ncig.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+		if (cig_total) HIP_TRY(hipMemcpyAsync(cig.data(), ctx->round.cig.p, (size_t)cig_total * 4, hipMemcpyDeviceToHost, s));
 		HIP_TRY(wait_stream(ctx, s));
 		int64_t pool_n = 0;
 		for (int32_t k : walk) pool_n += nc[k];

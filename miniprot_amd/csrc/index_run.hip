@@ -1,8 +1,5 @@
 // index_run.hip -- host driver of the index build on the device (dev_index_build, in one pass or in passes over bucket ranges) and
 // its entry points of the C ABI.  The unit of the index-build kernels (index_kernels.hip).
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
 #include "dev_ctx.h"
 #include "index_kernels.hip"
 
@@ -25,6 +22,26 @@ struct IndexPassEnv {
 	double t0;
 };
 
+// the total of an exclusive scan of n 32-bit elements into 64-bit offsets: the last offset plus the last element (one wait on s)
+static int scan_total(mpa_ctx_t *ctx, hipStream_t s, const uint64_t *off, const uint32_t *elem, int64_t n, int64_t *total)
+{
+	uint64_t last_off = 0;
+	uint32_t last_elem = 0;
+	HIP_TRY(hipMemcpyAsync(&last_off, off + (n - 1), 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(&last_elem, elem + (n - 1), 4, hipMemcpyDeviceToHost, s));
+	HIP_TRY(wait_stream(ctx, s));
+	*total = (int64_t)(last_off + last_elem);
+	return MPA_OK;
+}
+
+// the finished kb[] of a build takes the place of the resident one; the old table's bucket offsets go with it (the new table's go up
+// with the first device sketch)
+static void install_kb(DeviceIndex *d, DevTable<uint32_t> &kb)
+{
+	d->kb = std::move(kb);
+	d->ki.release();
+}
+
 static int dev_index_build_passes(const IndexPassEnv &E)
 {
 	mpa_ctx_t *ctx = E.ctx;
@@ -36,11 +53,9 @@ static int dev_index_build_passes(const IndexPassEnv &E)
 	const bool timed = timing_on();
 	double ms_scan = 0;
 	auto scan_clock = [&](double t) -> int { if (timed) { HIP_TRY(hipStreamSynchronize(s)); ms_scan += now_ms() - t; } return MPA_OK; };
-	DevBuf b_hist, b_keys, b_keys2, b_flag, b_idx, b_kbp, b_cnt, b_ki;
-	auto release_all = [&]() { for (DevBuf *b : { &b_hist, &b_keys, &b_keys2, &b_flag, &b_idx, &b_kbp, &b_cnt, &b_ki }) b->release(); };
-	struct Guard { std::function<void()> f; ~Guard() { f(); } } guard{ release_all };
 	int rc;
 	// 1. the histogram
+	DevBuf b_hist;
 	if ((rc = b_hist.ensure_exact((size_t)n_bin * 8))) return rc;
 	HIP_TRY(hipMemsetAsync(b_hist.p, 0, (size_t)n_bin * 8, s));
 	double tc = timed ? now_ms() : 0;
@@ -75,10 +90,11 @@ static int dev_index_build_passes(const IndexPassEnv &E)
 		max_pass = std::max(max_pass, pass_keys[p]);
 	}
 	// 3. the passes, over buffers sized once for the fullest of them
+	DevBuf b_keys, b_keys2, b_flag, b_idx, b_kbp, b_cnt, b_ki;
 	if ((rc = b_keys.ensure_exact((size_t)max_pass * 8 + 16)) || (rc = b_keys2.ensure_exact((size_t)max_pass * 8 + 16)) || (rc = b_flag.ensure_exact((size_t)max_pass * 4 + 16)) ||
 	    (rc = b_idx.ensure_exact((size_t)max_pass * 8 + 16)) || (rc = b_kbp.ensure_exact((size_t)max_pass * 4 + 16)) || (rc = b_cnt.ensure_exact(n_bucket * 8)) ||
 	    (rc = b_ki.ensure_exact(n_bucket * 8))) return rc;
-	{
+	{	// (the sort's scratch for the fullest pass, before the first pass: what does not fit fails here)
 		size_t tmp_bytes = 0;
 		HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp_bytes, b_keys.as<uint64_t>(), b_keys2.as<uint64_t>(), (size_t)max_pass, 0u, 32u + (unsigned)E.bucket_bits, s));
 		if ((rc = E.b_tmp->ensure_exact(tmp_bytes + 256))) return rc;
@@ -95,46 +111,22 @@ static int dev_index_build_passes(const IndexPassEnv &E)
 		hipLaunchKernelGGL((k_index_scan<INDEX_COUNT, true>), dim3((unsigned)n_chunk), dim3(256), E.lds, s, E.a, E.b_count->as<uint32_t>(), (const uint64_t*)nullptr, (uint64_t*)nullptr, r);
 		HIP_TRY(hipGetLastError());
 		if ((rc = scan_clock(tc))) return rc;
-		{
-			size_t tmp_bytes = 0;
-			auto in = rocprim::make_transform_iterator(E.b_count->as<uint32_t>(), U32ToU64());
-			HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes, in, E.b_off->as<uint64_t>(), (uint64_t)0, (size_t)n_chunk, rocprim::plus<uint64_t>(), s));
-			if ((rc = E.b_tmp->ensure_exact(tmp_bytes + 256))) return rc;
-			HIP_TRY(rocprim::exclusive_scan(E.b_tmp->p, tmp_bytes, in, E.b_off->as<uint64_t>(), (uint64_t)0, (size_t)n_chunk, rocprim::plus<uint64_t>(), s));
-		}
+		if ((rc = dev_exclusive_scan(*E.b_tmp, true, rocprim::make_transform_iterator(E.b_count->as<uint32_t>(), U32ToU64()), E.b_off->as<uint64_t>(), (uint64_t)0, (size_t)n_chunk, s))) return rc;
 		// (the emit pass writes at these offsets: they must add up to what the buffers were sized for)
-		uint64_t last_off = 0;
-		uint32_t last_cnt = 0;
-		HIP_TRY(hipMemcpyAsync(&last_off, E.b_off->as<uint64_t>() + (n_chunk - 1), 8, hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipMemcpyAsync(&last_cnt, E.b_count->as<uint32_t>() + (n_chunk - 1), 4, hipMemcpyDeviceToHost, s));
-		HIP_TRY(wait_stream(ctx, s));
-		if ((int64_t)(last_off + last_cnt) != nk) { set_error("index build: a pass counts other keys than the histogram gave it"); return MPA_ERR_HIP; }
+		int64_t n_emit = 0;
+		if ((rc = scan_total(ctx, s, E.b_off->as<uint64_t>(), E.b_count->as<uint32_t>(), n_chunk, &n_emit))) return rc;
+		if (n_emit != nk) { set_error("index build: a pass counts other keys than the histogram gave it"); return MPA_ERR_HIP; }
 		tc = timed ? now_ms() : 0;
 		hipLaunchKernelGGL((k_index_scan<INDEX_EMIT, true>), dim3((unsigned)n_chunk), dim3(256), E.lds, s, E.a, (uint32_t*)nullptr, E.b_off->as<uint64_t>(), b_keys.as<uint64_t>(), r);
 		HIP_TRY(hipGetLastError());
 		if ((rc = scan_clock(tc))) return rc;
-		{
-			size_t tmp_bytes = 0;
-			HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp_bytes, b_keys.as<uint64_t>(), b_keys2.as<uint64_t>(), (size_t)nk, 0u, 32u + (unsigned)E.bucket_bits, s));
-			if ((rc = E.b_tmp->ensure_exact(tmp_bytes + 256))) return rc;
-			HIP_TRY(rocprim::radix_sort_keys(E.b_tmp->p, tmp_bytes, b_keys.as<uint64_t>(), b_keys2.as<uint64_t>(), (size_t)nk, 0u, 32u + (unsigned)E.bucket_bits, s));
-		}
+		if ((rc = dev_sort_keys(*E.b_tmp, true, b_keys.as<uint64_t>(), b_keys2.as<uint64_t>(), (size_t)nk, 0u, 32u + (unsigned)E.bucket_bits, s))) return rc;
 		const uint64_t *sorted = b_keys2.as<uint64_t>();
 		const unsigned nblk = (unsigned)((nk + 255) / 256);
 		hipLaunchKernelGGL(k_index_flag, dim3(nblk), dim3(256), 0, s, sorted, nk, b_flag.as<uint32_t>());
-		{
-			size_t tmp_bytes = 0;
-			auto in = rocprim::make_transform_iterator(b_flag.as<uint32_t>(), U32ToU64());
-			HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes, in, b_idx.as<uint64_t>(), (uint64_t)0, (size_t)nk, rocprim::plus<uint64_t>(), s));
-			if ((rc = E.b_tmp->ensure_exact(tmp_bytes + 256))) return rc;
-			HIP_TRY(rocprim::exclusive_scan(E.b_tmp->p, tmp_bytes, in, b_idx.as<uint64_t>(), (uint64_t)0, (size_t)nk, rocprim::plus<uint64_t>(), s));
-		}
-		uint64_t last_idx = 0;
-		uint32_t last_flag = 0;
-		HIP_TRY(hipMemcpyAsync(&last_idx, b_idx.as<uint64_t>() + (nk - 1), 8, hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipMemcpyAsync(&last_flag, b_flag.as<uint32_t>() + (nk - 1), 4, hipMemcpyDeviceToHost, s));
-		HIP_TRY(wait_stream(ctx, s));
-		const int64_t n_kb_pass = (int64_t)(last_idx + last_flag);
+		if ((rc = dev_exclusive_scan(*E.b_tmp, true, rocprim::make_transform_iterator(b_flag.as<uint32_t>(), U32ToU64()), b_idx.as<uint64_t>(), (uint64_t)0, (size_t)nk, s))) return rc;
+		int64_t n_kb_pass = 0;
+		if ((rc = scan_total(ctx, s, b_idx.as<uint64_t>(), b_flag.as<uint32_t>(), nk, &n_kb_pass))) return rc;
 		if (n_kb_pass < 1 || n_kb_pass > nk) { set_error("index build: a pass has more distinct keys than keys"); return MPA_ERR_HIP; }
 		hipLaunchKernelGGL(k_index_compact, dim3(nblk), dim3(256), 0, s, sorted, nk, b_flag.as<uint32_t>(), b_idx.as<uint64_t>(), b_kbp.as<uint32_t>(), b_cnt.as<unsigned long long>());
 		HIP_TRY(hipGetLastError());
@@ -144,28 +136,17 @@ static int dev_index_build_passes(const IndexPassEnv &E)
 		n_kb += n_kb_pass;
 	}
 	// 4. bucket boundaries from the counts of all passes; the pass buffers go before the whole kb[] comes up
-	{
-		size_t tmp_bytes = 0;
-		HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes, b_cnt.as<uint64_t>(), b_ki.as<uint64_t>(), (uint64_t)0, n_bucket, rocprim::plus<uint64_t>(), s));
-		if ((rc = E.b_tmp->ensure_exact(tmp_bytes + 256))) return rc;
-		HIP_TRY(rocprim::exclusive_scan(E.b_tmp->p, tmp_bytes, b_cnt.as<uint64_t>(), b_ki.as<uint64_t>(), (uint64_t)0, n_bucket, rocprim::plus<uint64_t>(), s));
-	}
+	if ((rc = dev_exclusive_scan(*E.b_tmp, true, b_cnt.as<uint64_t>(), b_ki.as<uint64_t>(), (uint64_t)0, n_bucket, s))) return rc;
 	std::vector<int64_t> ki_new(n_bucket);
 	HIP_TRY(hipMemcpyAsync(ki_new.data(), b_ki.p, n_bucket * 8, hipMemcpyDeviceToHost, s));
 	HIP_TRY(wait_stream(ctx, s));
-	release_all();
-	uint32_t *d_kb = nullptr;
-	HIP_TRY(hipMalloc((void**)&d_kb, (size_t)n_kb * 4 + 16));
-	struct KbGuard { uint32_t *&p; hipStream_t s; ~KbGuard() { if (p) { (void)hipStreamSynchronize(s); (void)hipFree(p); } } } kb_guard{ d_kb, s };
+	b_keys.release(), b_keys2.release(), b_flag.release(), b_idx.release(), b_kbp.release(), b_cnt.release(), b_ki.release();
+	DevTable<uint32_t> d_kb;
+	HIP_TRY(d_kb.take((size_t)n_kb * 4 + 16));
 	HIP_TRY(hipMemcpyAsync(d_kb, kb_new.data(), (size_t)n_kb * 4, hipMemcpyHostToDevice, s));
 	HIP_TRY(wait_stream(ctx, s));
-	DeviceIndex *d = E.d;
 	mi->ki.swap(ki_new), mi->kb.swap(kb_new), mi->n_kb = n_kb;
-	if (d->kb) { (void)hipFree(d->kb); g_dev_bytes -= (long long)d->kb_bytes; }
-	if (d->ki) { (void)hipFree(d->ki); g_dev_bytes -= (long long)d->ki_bytes; d->ki = nullptr, d->ki_bytes = 0; }
-	d->kb = d_kb, d->kb_bytes = (size_t)n_kb * 4 + 16;
-	g_dev_bytes += (long long)d->kb_bytes;
-	d_kb = nullptr;
+	install_kb(E.d, d_kb);
 	ctx->idx_stats.n_pass = n_pass, ctx->idx_stats.max_pass_keys = max_pass;
 	if (timed) {
 		char note[64];
@@ -192,9 +173,7 @@ int dev_index_build(mpa_ctx_t *ctx, mpa_idx_s *mi)
 	const int64_t n_chunk = chunk_first[n_strand];
 	if (n_chunk == 0 || n_chunk > 0x7fffffff) { set_error("index build: genome too small or too large for one launch"); return MPA_ERR_UNSUPPORTED; }
 	const size_t n_bucket = (size_t)1 << bucket_bits;
-	DevBuf b_first, b_bo, b_count, b_off, b_keys, b_keys2, b_flag, b_idx, b_tmp, b_cnt, b_ki;
-	auto release_all = [&]() { for (DevBuf *b : { &b_first, &b_bo, &b_count, &b_off, &b_keys, &b_keys2, &b_flag, &b_idx, &b_tmp, &b_cnt, &b_ki }) b->release(); };
-	struct Guard { std::function<void()> f; ~Guard() { f(); } } guard{ release_all };
+	DevBuf b_first, b_bo, b_count, b_off, b_keys, b_keys2, b_flag, b_idx, b_tmp, b_cnt, b_ki;   // (gone with the call, however it ends)
 	int rc;
 	if ((rc = b_first.ensure(((size_t)n_strand + 1) * 8)) || (rc = b_bo.ensure((size_t)n_strand * 4 + 4)) || (rc = b_count.ensure((size_t)n_chunk * 4 + 4)) ||
 	    (rc = b_off.ensure(((size_t)n_chunk + 1) * 8))) return rc;
@@ -212,19 +191,9 @@ int dev_index_build(mpa_ctx_t *ctx, mpa_idx_s *mi)
 	hipLaunchKernelGGL((k_index_scan<INDEX_COUNT, false>), dim3((unsigned)n_chunk), dim3(256), lds, s, a, b_count.as<uint32_t>(), (const uint64_t*)nullptr, (uint64_t*)nullptr, IndexPassArgs{});
 	HIP_TRY(hipGetLastError());
 	// exclusive scan of the per-chunk counts (as 64-bit offsets)
-	{
-		size_t tmp_bytes = 0;
-		auto in = rocprim::make_transform_iterator(b_count.as<uint32_t>(), U32ToU64());
-		HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes, in, b_off.as<uint64_t>(), (uint64_t)0, (size_t)n_chunk, rocprim::plus<uint64_t>(), s));
-		if ((rc = b_tmp.ensure(tmp_bytes + 256))) return rc;
-		HIP_TRY(rocprim::exclusive_scan(b_tmp.p, tmp_bytes, in, b_off.as<uint64_t>(), (uint64_t)0, (size_t)n_chunk, rocprim::plus<uint64_t>(), s));
-	}
-	uint64_t last_off = 0;
-	uint32_t last_cnt = 0;
-	HIP_TRY(hipMemcpyAsync(&last_off, b_off.as<uint64_t>() + (n_chunk - 1), 8, hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipMemcpyAsync(&last_cnt, b_count.as<uint32_t>() + (n_chunk - 1), 4, hipMemcpyDeviceToHost, s));
-	HIP_TRY(wait_stream(ctx, s));
-	const int64_t n_keys = (int64_t)(last_off + last_cnt);
+	if ((rc = dev_exclusive_scan(b_tmp, false, rocprim::make_transform_iterator(b_count.as<uint32_t>(), U32ToU64()), b_off.as<uint64_t>(), (uint64_t)0, (size_t)n_chunk, s))) return rc;
+	int64_t n_keys = 0;
+	if ((rc = scan_total(ctx, s, b_off.as<uint64_t>(), b_count.as<uint32_t>(), n_chunk, &n_keys))) return rc;
 	if (n_keys == 0) { mi->ki.assign(n_bucket, 0), mi->kb.clear(), mi->n_kb = 0; return MPA_OK; }
 	{	// two key buffers, flags, scan, kb: ~40 bytes per key.  The budget for them is 7/8 of the free memory less the two bucket
 		// tables, which every build needs; MPA_IDX_BUILD_MB (read on every call: for users who share a device) and the tests' hook cap it
@@ -246,57 +215,29 @@ int dev_index_build(mpa_ctx_t *ctx, mpa_idx_s *mi)
 	if ((rc = b_keys.ensure((size_t)n_keys * 8)) || (rc = b_keys2.ensure((size_t)n_keys * 8))) return rc;
 	hipLaunchKernelGGL((k_index_scan<INDEX_EMIT, false>), dim3((unsigned)n_chunk), dim3(256), lds, s, a, (uint32_t*)nullptr, b_off.as<uint64_t>(), b_keys.as<uint64_t>(), IndexPassArgs{});
 	HIP_TRY(hipGetLastError());
-	int nb = 1;
-	while ((1ULL << nb) < (uint64_t)mi->n_block + 1) ++nb;
-	{
-		size_t tmp_bytes = 0;
-		HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp_bytes, b_keys.as<uint64_t>(), b_keys2.as<uint64_t>(), (size_t)n_keys, 0u, 32u + (unsigned)bucket_bits, s));
-		if ((rc = b_tmp.ensure(tmp_bytes + 256))) return rc;
-		HIP_TRY(rocprim::radix_sort_keys(b_tmp.p, tmp_bytes, b_keys.as<uint64_t>(), b_keys2.as<uint64_t>(), (size_t)n_keys, 0u, 32u + (unsigned)bucket_bits, s));
-	}
-	(void)nb;
+	if ((rc = dev_sort_keys(b_tmp, false, b_keys.as<uint64_t>(), b_keys2.as<uint64_t>(), (size_t)n_keys, 0u, 32u + (unsigned)bucket_bits, s))) return rc;
 	b_keys.release();
 	const uint64_t *sorted = b_keys2.as<uint64_t>();
 	if ((rc = b_flag.ensure((size_t)n_keys * 4)) || (rc = b_idx.ensure((size_t)n_keys * 8)) || (rc = b_cnt.ensure(n_bucket * 8)) || (rc = b_ki.ensure(n_bucket * 8))) return rc;
 	const unsigned nblk = (unsigned)((n_keys + 255) / 256);
 	hipLaunchKernelGGL(k_index_flag, dim3(nblk), dim3(256), 0, s, sorted, n_keys, b_flag.as<uint32_t>());
-	{
-		size_t tmp_bytes = 0;
-		auto in = rocprim::make_transform_iterator(b_flag.as<uint32_t>(), U32ToU64());
-		HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes, in, b_idx.as<uint64_t>(), (uint64_t)0, (size_t)n_keys, rocprim::plus<uint64_t>(), s));
-		if ((rc = b_tmp.ensure(tmp_bytes + 256))) return rc;
-		HIP_TRY(rocprim::exclusive_scan(b_tmp.p, tmp_bytes, in, b_idx.as<uint64_t>(), (uint64_t)0, (size_t)n_keys, rocprim::plus<uint64_t>(), s));
-	}
-	uint64_t last_idx = 0;
-	uint32_t last_flag = 0;
-	HIP_TRY(hipMemcpyAsync(&last_idx, b_idx.as<uint64_t>() + (n_keys - 1), 8, hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipMemcpyAsync(&last_flag, b_flag.as<uint32_t>() + (n_keys - 1), 4, hipMemcpyDeviceToHost, s));
-	HIP_TRY(wait_stream(ctx, s));
-	const int64_t n_kb = (int64_t)(last_idx + last_flag);
-	uint32_t *d_kb = nullptr;
-	HIP_TRY(hipMalloc((void**)&d_kb, (size_t)n_kb * 4 + 16));
-	struct KbGuard { uint32_t *&p; hipStream_t s; ~KbGuard() { if (p) { (void)hipStreamSynchronize(s); (void)hipFree(p); } } } kb_guard{ d_kb, s };   // freed on every error path below
+	if ((rc = dev_exclusive_scan(b_tmp, false, rocprim::make_transform_iterator(b_flag.as<uint32_t>(), U32ToU64()), b_idx.as<uint64_t>(), (uint64_t)0, (size_t)n_keys, s))) return rc;
+	int64_t n_kb = 0;
+	if ((rc = scan_total(ctx, s, b_idx.as<uint64_t>(), b_flag.as<uint32_t>(), n_keys, &n_kb))) return rc;
+	DevTable<uint32_t> d_kb;                               // (a local until the table is whole: an error below gives it back)
+	HIP_TRY(d_kb.take((size_t)n_kb * 4 + 16));
 	HIP_TRY(hipMemsetAsync(b_cnt.p, 0, n_bucket * 8, s));
-	hipLaunchKernelGGL(k_index_compact, dim3(nblk), dim3(256), 0, s, sorted, n_keys, b_flag.as<uint32_t>(), b_idx.as<uint64_t>(), d_kb, b_cnt.as<unsigned long long>());
-	{
-		size_t tmp_bytes = 0;
-		HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes, b_cnt.as<uint64_t>(), b_ki.as<uint64_t>(), (uint64_t)0, n_bucket, rocprim::plus<uint64_t>(), s));
-		if ((rc = b_tmp.ensure(tmp_bytes + 256))) return rc;
-		HIP_TRY(rocprim::exclusive_scan(b_tmp.p, tmp_bytes, b_cnt.as<uint64_t>(), b_ki.as<uint64_t>(), (uint64_t)0, n_bucket, rocprim::plus<uint64_t>(), s));
-	}
+	hipLaunchKernelGGL(k_index_compact, dim3(nblk), dim3(256), 0, s, sorted, n_keys, b_flag.as<uint32_t>(), b_idx.as<uint64_t>(), (uint32_t*)d_kb, b_cnt.as<unsigned long long>());
+	if ((rc = dev_exclusive_scan(b_tmp, false, b_cnt.as<uint64_t>(), b_ki.as<uint64_t>(), (uint64_t)0, n_bucket, s))) return rc;
 	HIP_TRY(hipGetLastError());
 	// (into temporaries: a copy that fails must not leave the index with a half-filled table)
 	std::vector<int64_t> ki_new(n_bucket);
 	std::vector<uint32_t> kb_new((size_t)n_kb);
 	HIP_TRY(hipMemcpyAsync(ki_new.data(), b_ki.p, n_bucket * 8, hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipMemcpyAsync(kb_new.data(), d_kb, (size_t)n_kb * 4, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(kb_new.data(), (const uint32_t*)d_kb, (size_t)n_kb * 4, hipMemcpyDeviceToHost, s));
 	HIP_TRY(wait_stream(ctx, s));
 	mi->ki.swap(ki_new), mi->kb.swap(kb_new), mi->n_kb = n_kb;
-	if (d->kb) { (void)hipFree(d->kb); g_dev_bytes -= (long long)d->kb_bytes; }
-	if (d->ki) { (void)hipFree(d->ki); g_dev_bytes -= (long long)d->ki_bytes; d->ki = nullptr, d->ki_bytes = 0; }   // (the new table's offsets go up with the first device sketch)
-	d->kb = d_kb, d->kb_bytes = (size_t)n_kb * 4 + 16;     // stays resident for the seeding kernels
-	g_dev_bytes += (long long)d->kb_bytes;
-	d_kb = nullptr;                                        // (ownership moved: the guard lets go)
+	install_kb(d, d_kb);                                   // stays resident for the seeding kernels
 	timing_note("index build on the GPU", now_ms() - t0);
 	return MPA_OK;
 }

@@ -160,6 +160,7 @@ mpa_ctx_t *ctx_sibling(mpa_ctx_t *ctx, int k);   // extra context on the same de
 struct StreamPlan;
 int ctx_apply_stream_plan(mpa_ctx_t *root, int n_lanes, int n_seed, int n_plan, int layout);
 const StreamPlan *ctx_stream_plan(const mpa_ctx_t *root);
+int32_t ctx_pool_list(const mpa_ctx_t *ctx, int32_t sibling, const char **names, int64_t *caps, int32_t cap);   // the registered device pools of a context or one of its siblings (mpa_dbg_ctx_pools)
 int ctx_hw_queues(void);
 void ctx_absorb_sibling_stats(mpa_ctx_t *ctx);
 void ctx_set_side_offset(mpa_ctx_t *ctx, int off);   // which of its side streams a DP round starts with

@@ -1,9 +1,6 @@
 // refine_run.hip -- host drivers of the refinement stage on the device (mp_refine_reg, map.c:32-111): the window scan for the host's
 // pairing (dev_refine_scan) and the whole refinement -- scan, pairing, sort, chains -- of a mini-batch (dev_refine_chains).  The unit
 // of the refinement kernels (refine_kernels.hip); the chains of the pairs come from the seeding unit's chain tail (dev_ctx.h).
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
 #include "dev_ctx.h"
 #include "refine_kernels.hip"
 
@@ -310,9 +307,10 @@ int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_a
 	hipLaunchKernelGGL(k_refine_pair_count, dim3(nbh), dim3(256), 0, s, B.r_hits.as<uint4>(), n_hits, d_wg, d_wcnt, gr.gcount, max_ava, d_pc, d_wpairs);
 	HIP_TRY(hipGetLastError());
 	{
-		size_t tb = 0, tb2 = 0;
 		auto in = rocprim::make_transform_iterator((const uint32_t*)d_pc, U32ToU64());
 		auto inw = rocprim::make_transform_iterator((const uint32_t*)d_wpairs, U32ToU64());
+		// (two scans behind one another share one sizing of the scratch, the larger one's: dev_exclusive_scan twice could grow the pool twice)
+		size_t tb = 0, tb2 = 0;
 		HIP_TRY(rocprim::exclusive_scan(nullptr, tb, in, d_po, (uint64_t)0, (size_t)n_hits, rocprim::plus<uint64_t>(), s));
 		HIP_TRY(rocprim::exclusive_scan(nullptr, tb2, inw, (uint64_t*)d_first, (uint64_t)0, NW + 1, rocprim::plus<uint64_t>(), s));
 		if ((rc = B.tmp.ensure(std::max(tb, tb2) + 256))) return rc;
@@ -331,10 +329,7 @@ int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_a
 	{
 		int wbits = 1;
 		while ((1LL << wbits) < n_win) ++wbits;
-		size_t tb = 0;
-		HIP_TRY(rocprim::radix_sort_keys(nullptr, tb, keys0, keys1, (size_t)np, 0u, (unsigned)(44 + wbits), s));
-		if ((rc = B.tmp.ensure(tb + 256))) return rc;
-		HIP_TRY(rocprim::radix_sort_keys(B.tmp.p, tb, keys0, keys1, (size_t)np, 0u, (unsigned)(44 + wbits), s));
+		if ((rc = dev_sort_keys(B.tmp, false, keys0, keys1, (size_t)np, 0u, (unsigned)(44 + wbits), s))) return rc;
 	}
 	const unsigned nbp = (unsigned)((np + 255) / 256);
 	hipLaunchKernelGGL(k_refine_pair_decode, dim3(nbp), dim3(256), 0, s, (const uint64_t*)keys1, np, d_a);

@@ -275,29 +275,16 @@ static void seed_mark_on_host(PrechainSparse &out, int32_t n_query, const int32_
 	}
 }
 
-// bo[] next to kb[] in HBM, on the first device regions call of a device (like ki[] for the device sketch).  No device memory for it:
-// nullptr, and the caller keeps the chains' route.
-static const uint32_t *ensure_dev_bo(mpa_ctx_t *ctx, mpa_idx_s *mi)
-{
-	DeviceIndex *d = mi->dev[ctx->device];
-	if (d->bo) return d->bo;
-	static std::mutex mu[mpa_idx_s::kMaxDevices];            // (per device, like dev_upload_index)
-	std::lock_guard<std::mutex> g(mu[ctx->device]);
-	if (d->bo) return d->bo;
-	uint32_t *p = nullptr;
-	const size_t bytes = mi->bo.size() * 4;
-	if (hipMalloc((void**)&p, bytes + 16) != hipSuccess) { (void)hipGetLastError(); set_error("device regions: no device memory for the block offsets"); return nullptr; }
-	if (hipMemcpy(p, mi->bo.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(p); set_error("device regions: uploading the block offsets"); return nullptr; }
-	d->bo_bytes = bytes + 16, g_dev_bytes += (long long)d->bo_bytes;
-	d->bo = p;
-	return d->bo;
-}
 // what a seeding route hands the chain tail for MPA_GPU_REGIONS=1 (nullptr: the chains), and what it takes from it afterwards
 static RegionsTail *regions_tail_begin(mpa_ctx_t *ctx, mpa_idx_s *mi, const RegionsParams *rp, RegionsTail &rt)
 {
 	if (!rp) return nullptr;
-	const uint32_t *d_bo = ensure_dev_bo(ctx, mi);
-	if (!d_bo) {
+	// bo[] next to kb[] in HBM, on the first device regions call of a device.  No device memory for it: the chains' route
+	DeviceIndex *d = mi->dev[ctx->device];
+	const hipError_t e = dev_index_table(ctx, d->bo, mi->bo.data(), mi->bo.size() * 4, "index upload: block offsets");
+	const uint32_t *d_bo = d->bo;
+	if (e != hipSuccess) {
+		set_error(e == hipErrorOutOfMemory ? "device regions: no device memory for the block offsets" : "device regions: uploading the block offsets");
 		if (timing_on()) fprintf(stderr, "[mpa-timing]   device regions declined (%s): chains to the host\n", mpa_last_error());
 		return nullptr;
 	}
@@ -460,10 +447,7 @@ static int dev_prechain_forward_sift(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_
 	hipLaunchKernelGGL(k_prechain_fwd<uint64_t>, dim3(nblk), dim3(256), 0, s, key, val, n2, nb, B.pf_qfirst2.as<int64_t>(), pp, B.f.as<int32_t>(), B.pred.as<int32_t>(),
 	                   B.mark.as<int32_t>(), B.flag.as<uint32_t>());
 	HIP_TRY(hipGetLastError());
-	size_t scan_bytes = 0;
-	HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, B.flag.as<uint32_t>(), B.idx.as<uint32_t>(), 0u, (size_t)n2, rocprim::plus<uint32_t>(), s));
-	if ((rc = B.tmp.ensure(scan_bytes + 256))) return rc;
-	HIP_TRY(rocprim::exclusive_scan(B.tmp.p, scan_bytes, B.flag.as<uint32_t>(), B.idx.as<uint32_t>(), 0u, (size_t)n2, rocprim::plus<uint32_t>(), s));
+	if ((rc = dev_exclusive_scan(B.tmp, false, B.flag.as<uint32_t>(), B.idx.as<uint32_t>(), 0u, (size_t)n2, s))) return rc;
 	hipLaunchKernelGGL(k_seed_bounds, dim3((unsigned)(n_query / 256 + 1)), dim3(256), 0, s, B.pf_qfirst2.as<int64_t>(), n_query, n2, B.idx.as<uint32_t>(), B.flag.as<uint32_t>(),
 	                   B.cfirst.as<int64_t>());
 	HIP_TRY(hipGetLastError());
@@ -634,17 +618,7 @@ static int dev_seed_entry(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams *pre_
 	HIP_TRY(hipSetDevice(ctx->device));
 	if (dev_upload_index(ctx, mi) != MPA_OK) return MPA_ERR_HIP;
 	DeviceIndex *d = mi->dev[ctx->device];
-	if (!d->kb) {
-		static std::mutex mu[mpa_idx_s::kMaxDevices];            // (per device, like dev_upload_index)
-		std::lock_guard<std::mutex> g(mu[ctx->device]);
-		if (!d->kb) {
-			uint32_t *p = nullptr;
-			HIP_TRY(hipMalloc((void**)&p, mi->kb.size() * 4 + 16));
-			{ const double t0 = now_ms(); HIP_TRY(upload_large(p, mi->kb.data(), mi->kb.size() * 4, ctx->stream)); timing_note("index upload: occurrence lists", now_ms() - t0); }
-			d->kb = p, d->kb_bytes = mi->kb.size() * 4 + 16;
-			g_dev_bytes += (long long)d->kb_bytes;
-		}
-	}
+	HIP_TRY(dev_index_table(ctx, d->kb, mi->kb.data(), mi->kb.size() * 4, "index upload: occurrence lists"));
 	const PreParams pp = pre_params(pre);                      // (direct route: the main chain's parameters, as dev_chains_on_device derives them)
 	int nb = 1, qb = 1;
 	while ((1ULL << nb) < (uint64_t)mi->n_block + (uint64_t)pp.max_dblock + 2) ++nb;
@@ -697,26 +671,6 @@ int dev_seed_direct(mpa_ctx_t *ctx, mpa_idx_s *mi, const ChainParams &mainp, int
                     PrechainSparse &out, SeedHold *hold, const int64_t *jfirst_dev, SiftKept *kept, const RegionsParams *regions)
 {
 	return dev_seed_entry(ctx, mi, nullptr, n_query, qfirst, jobs, n_jobs, out, &mainp, hold, jfirst_dev, kept, regions);
-}
-
-// ki[] next to kb[] in HBM, on the first device sketch of a device.  The host array may be a misaligned view into a mapped .mpi:
-// it is only ever copied byte-wise.  No device memory for it: the caller sketches on the host.
-static int ensure_dev_ki(mpa_ctx_t *ctx, mpa_idx_s *mi, DeviceIndex *d)
-{
-	if (d->ki) return MPA_OK;
-	static std::mutex mu[mpa_idx_s::kMaxDevices];            // (per device, like dev_upload_index)
-	std::lock_guard<std::mutex> g(mu[ctx->device]);
-	if (d->ki) return MPA_OK;
-	int64_t *p = nullptr;
-	const size_t bytes = mi->ki.size() * 8;
-	if (hipMalloc((void**)&p, bytes + 16) != hipSuccess) { (void)hipGetLastError(); set_error("GPU sketch: no device memory for the bucket offsets"); return MPA_ERR_UNSUPPORTED; }
-	const double t0 = now_ms();
-	const hipError_t e = upload_large(p, (const void*)mi->ki.data(), bytes, ctx->stream);
-	if (e != hipSuccess) { (void)hipFree(p); set_error(std::string("GPU sketch: uploading the bucket offsets: ") + hipGetErrorString(e)); return MPA_ERR_HIP; }
-	timing_note("index upload: bucket offsets", now_ms() - t0);
-	d->ki = p, d->ki_bytes = bytes + 16;
-	g_dev_bytes += (long long)d->ki_bytes;
-	return MPA_OK;
 }
 
 static int dev_sketch_jobs_impl(mpa_ctx_t *ctx, mpa_idx_s *mi, DeviceIndex *d, int32_t max_occ, const mpa_qbatch_t *q, SketchResult &out)
@@ -773,11 +727,14 @@ int dev_sketch_jobs(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t max_occ, const mpa_qb
 	HIP_TRY(hipSetDevice(ctx->device));
 	if (dev_upload_index(ctx, mi) != MPA_OK) return MPA_ERR_HIP;
 	DeviceIndex *d = mi->dev[ctx->device];
-	int rc = ensure_dev_ki(ctx, mi, d);
-	if (rc != MPA_OK) return rc;
+	// ki[] next to kb[] in HBM, on the first device sketch of a device.  The host array may be a misaligned view into a mapped .mpi:
+	// it is only ever copied byte-wise.  No device memory for it: the caller sketches on the host.
+	const hipError_t e = dev_index_table(ctx, d->ki, (const void*)mi->ki.data(), mi->ki.size() * 8, "index upload: bucket offsets");
+	if (e == hipErrorOutOfMemory) { set_error("GPU sketch: no device memory for the bucket offsets"); return MPA_ERR_UNSUPPORTED; }
+	if (e != hipSuccess) { set_error(std::string("GPU sketch: uploading the bucket offsets: ") + hipGetErrorString(e)); return MPA_ERR_HIP; }
 	ensure_seed_stream(ctx);
 	tl_alloc_failed = false;
-	rc = dev_sketch_jobs_impl(ctx, mi, d, max_occ, q, out);
+	const int rc = dev_sketch_jobs_impl(ctx, mi, d, max_occ, q, out);
 	if (rc == MPA_ERR_HIP && tl_alloc_failed) { (void)hipStreamSynchronize(ctx->seed_stream); out = SketchResult(); return MPA_ERR_UNSUPPORTED; }   // (a pool could not grow: host stage)
 	return rc;
 }

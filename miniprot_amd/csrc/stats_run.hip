@@ -53,11 +53,11 @@ int dev_aln_walks_stage(mpa_ctx_t *ctx, const AlnWalkSizes &z, AlnStatsIO &io, A
 	if (z.n_jobs <= 0 || z.n_jobs > (int64_t)1 << 28) { set_error("GPU alignment statistics / cs strings / residue rows: no alignments, or too many for one launch"); return MPA_ERR_UNSUPPORTED; }
 	if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return MPA_ERR_HIP; }
 	const StatsLayout L(z);
-	if (ctx->h_stats_up.ensure(L.up_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
-	if (z.slot_bytes >= 0 && ctx->h_cs_down.ensure(L.cs_down_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
-	if (z.rows_bytes >= 0 && ctx->h_rows_down.ensure(L.rows_down_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
-	if (z.n_feat >= 0 && ctx->h_stats_down.ensure(L.down_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
-	char *hu = ctx->h_stats_up.as<char>();
+	if (ctx->walks.h_stats_up.ensure(L.up_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
+	if (z.slot_bytes >= 0 && ctx->walks.h_cs_down.ensure(L.cs_down_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
+	if (z.rows_bytes >= 0 && ctx->walks.h_rows_down.ensure(L.rows_down_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
+	if (z.n_feat >= 0 && ctx->walks.h_stats_down.ensure(L.down_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
+	char *hu = ctx->walks.h_stats_up.as<char>();
 	io.jobs = (AlnStatsJob*)(hu + L.off_jobs), io.cigar = (uint32_t*)(hu + L.off_cig), io.text = hu + L.off_text;
 	if (z.slot_bytes >= 0) cs.slot_off = (int64_t*)(hu + L.off_slot);
 	if (z.rows_bytes >= 0) rows.slot_off = (int64_t*)(hu + L.off_rslot);
@@ -75,54 +75,54 @@ int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const 
 	const StatsLayout L(z);
 	const int64_t n_jobs = z.n_jobs;
 	const bool stats = z.n_feat >= 0, cs_on = z.slot_bytes >= 0, rows_on = z.rows_bytes >= 0;
-	if (dev_cig && !ctx->sp_cig.p) { set_error("dev_aln_walks: no assembled CIGAR pool on this context"); return MPA_ERR_ARG; }
+	if (dev_cig && !ctx->spans.sp_cig.p) { set_error("dev_aln_walks: no assembled CIGAR pool on this context"); return MPA_ERR_ARG; }
 	if (p.asize < 1 || p.asize * p.asize > 484) { set_error("GPU alignment statistics: a substitution matrix of more than 22 x 22"); return MPA_ERR_UNSUPPORTED; }
 	HIP_TRY(hipSetDevice(ctx->device));
 	if (dev_upload_index(ctx, mi) != MPA_OK) return MPA_ERR_HIP;
 	const DeviceIndex *d = mi->dev[ctx->device];
-	if (L.up_bytes > ctx->h_stats_up.cap || (stats && L.down_bytes > ctx->h_stats_down.cap) || (cs_on && L.cs_down_bytes > ctx->h_cs_down.cap) ||
-	    (rows_on && L.rows_down_bytes > ctx->h_rows_down.cap)) {
+	if (L.up_bytes > ctx->walks.h_stats_up.cap || (stats && L.down_bytes > ctx->walks.h_stats_down.cap) || (cs_on && L.cs_down_bytes > ctx->walks.h_cs_down.cap) ||
+	    (rows_on && L.rows_down_bytes > ctx->walks.h_rows_down.cap)) {
 		set_error("dev_aln_walks: the staging block was not sized for this call");
 		return MPA_ERR_ARG;
 	}
 	tl_alloc_failed = false;
-	if (ctx->st_in.ensure(L.up_bytes) != MPA_OK || (stats && ctx->st_out.ensure(L.down_bytes) != MPA_OK) || (cs_on && ctx->cs_out.ensure(L.cs_down_bytes) != MPA_OK) ||
-	    (rows_on && ctx->rows_out.ensure(L.rows_down_bytes) != MPA_OK))
+	if (ctx->walks.st_in.ensure(L.up_bytes) != MPA_OK || (stats && ctx->walks.st_out.ensure(L.down_bytes) != MPA_OK) || (cs_on && ctx->walks.cs_out.ensure(L.cs_down_bytes) != MPA_OK) ||
+	    (rows_on && ctx->walks.rows_out.ensure(L.rows_down_bytes) != MPA_OK))
 		return tl_alloc_failed ? MPA_ERR_UNSUPPORTED : MPA_ERR_HIP;
 	hipStream_t s = ctx->stream;
-	char *hu = ctx->h_stats_up.as<char>();
+	char *hu = ctx->walks.h_stats_up.as<char>();
 	aln_tables_fill((uint8_t*)hu, mat, (size_t)(p.asize * p.asize));
-	HIP_TRY(hipMemcpyAsync(ctx->st_in.p, hu, L.up_bytes - 16, hipMemcpyHostToDevice, s));
-	const char *din = ctx->st_in.as<char>();
-	const uint32_t *dcig = dev_cig ? ctx->sp_cig.as<uint32_t>() : (const uint32_t*)(din + L.off_cig);   // (MPA_GPU_SPANS=1: where k_assemble left the words)
+	HIP_TRY(hipMemcpyAsync(ctx->walks.st_in.p, hu, L.up_bytes - 16, hipMemcpyHostToDevice, s));
+	const char *din = ctx->walks.st_in.as<char>();
+	const uint32_t *dcig = dev_cig ? ctx->spans.sp_cig.as<uint32_t>() : (const uint32_t*)(din + L.off_cig);   // (MPA_GPU_SPANS=1: where k_assemble left the words)
 	const unsigned nwg = (unsigned)((n_jobs + STATS_WAVES - 1) / STATS_WAVES);
 	if (stats) {
-		char *dout = ctx->st_out.as<char>();
+		char *dout = ctx->walks.st_out.as<char>();
 		hipLaunchKernelGGL(k_aln_stats, dim3(nwg), dim3(64 * STATS_WAVES), 0, s, (const AlnStatsJob*)(din + L.off_jobs), (int32_t)n_jobs, (const uint8_t*)din, p,
 		                   (const uint8_t*)(din + L.off_text), dcig, (const uint8_t*)d->seq, (const int64_t*)d->ctg_off, (const int64_t*)d->ctg_len,
 		                   (AlnStatsOut*)dout, (AlnFeat*)(dout + L.off_feat));
 		HIP_TRY(hipGetLastError());
-		char *hd = ctx->h_stats_down.as<char>();
+		char *hd = ctx->walks.h_stats_down.as<char>();
 		HIP_TRY(hipMemcpyAsync(hd, dout, L.down_bytes - 16, hipMemcpyDeviceToHost, s));
 		io.out = (const AlnStatsOut*)hd, io.feat = (const AlnFeat*)(hd + L.off_feat);
 	}
 	if (cs_on) {
-		char *dout = ctx->cs_out.as<char>();
+		char *dout = ctx->walks.cs_out.as<char>();
 		hipLaunchKernelGGL(k_aln_cs, dim3(nwg), dim3(64 * STATS_WAVES), 0, s, (const AlnStatsJob*)(din + L.off_jobs), (int32_t)n_jobs, (const uint8_t*)din,
 		                   (const uint8_t*)(din + L.off_text), dcig, (const uint8_t*)d->seq, (const int64_t*)d->ctg_off, (const int64_t*)d->ctg_len,
 		                   (const int64_t*)(din + L.off_slot), (AlnCsOut*)dout, dout + L.off_body);
 		HIP_TRY(hipGetLastError());
-		char *hd = ctx->h_cs_down.as<char>();
+		char *hd = ctx->walks.h_cs_down.as<char>();
 		HIP_TRY(hipMemcpyAsync(hd, dout, L.cs_down_bytes - 16, hipMemcpyDeviceToHost, s));
 		cs.out = (const AlnCsOut*)hd, cs.body = hd + L.off_body;
 	}
 	if (rows_on) {
-		char *dout = ctx->rows_out.as<char>();
+		char *dout = ctx->walks.rows_out.as<char>();
 		hipLaunchKernelGGL(k_aln_rows, dim3(nwg), dim3(64 * STATS_WAVES), 0, s, (const AlnStatsJob*)(din + L.off_jobs), (int32_t)n_jobs, (const uint8_t*)din, rp,
 		                   (const uint8_t*)(din + L.off_text), dcig, (const uint8_t*)d->seq, (const int64_t*)d->ctg_off, (const int64_t*)d->ctg_len,
 		                   (const int64_t*)(din + L.off_rslot), (AlnRowsOut*)dout, dout + L.off_rbody);
 		HIP_TRY(hipGetLastError());
-		char *hd = ctx->h_rows_down.as<char>();
+		char *hd = ctx->walks.h_rows_down.as<char>();
 		HIP_TRY(hipMemcpyAsync(hd, dout, L.rows_down_bytes - 16, hipMemcpyDeviceToHost, s));
 		rows.out = (const AlnRowsOut*)hd, rows.body = hd + L.off_rbody;
 	}
@@ -176,8 +176,8 @@ int dev_spans_stage(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_seg, int64_t n_rst
 	if (n_plan <= 0 || n_plan > (int64_t)1 << 28 || n_seg < 0 || n_rst1 <= 0) { set_error("GPU spans: no plans, or too many for one launch"); return MPA_ERR_UNSUPPORTED; }
 	if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return MPA_ERR_HIP; }
 	const SpansLayout L(n_plan, n_seg, n_rst1, text_bytes);
-	if (ctx->h_sp_up.ensure(L.up_bytes) != MPA_OK || ctx->h_sp_down.ensure(L.down_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
-	char *hu = ctx->h_sp_up.as<char>();
+	if (ctx->spans.h_sp_up.ensure(L.up_bytes) != MPA_OK || ctx->spans.h_sp_down.ensure(L.down_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
+	char *hu = ctx->spans.h_sp_up.as<char>();
 	io.plan = (SpansPlan*)(hu + L.off_plan), io.seg = (SegRec*)(hu + L.off_seg), io.rst1 = (mpa_dp_rst_t*)(hu + L.off_rst1), io.text = hu + L.off_text;
 	return MPA_OK;
 }
@@ -185,26 +185,26 @@ int dev_spans_stage(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_seg, int64_t n_rst
 int dev_spans_round1(mpa_ctx_t *ctx, mpa_idx_s *mi, const SpansParams &p, const int8_t *mat, int64_t n_plan, int64_t n_seg, int64_t n_rst1, int64_t text_bytes,
                      const uint32_t *pool1, int64_t n_pool1, SpansIO &io)
 {
-	ctx->sp_keep.n_plan = -1;
+	ctx->spans.sp_keep.n_plan = -1;
 	if (p.asize < 1 || p.asize * p.asize > 484) { set_error("GPU spans: a substitution matrix of more than 22 x 22"); return MPA_ERR_UNSUPPORTED; }
 	HIP_TRY(hipSetDevice(ctx->device));
 	if (dev_upload_index(ctx, mi) != MPA_OK) return MPA_ERR_HIP;
 	const DeviceIndex *d = mi->dev[ctx->device];
 	const SpansLayout L(n_plan, n_seg, n_rst1, text_bytes);
-	if (L.up_bytes > ctx->h_sp_up.cap || L.down_bytes > ctx->h_sp_down.cap) { set_error("dev_spans_round1: the staging block was not sized for this call"); return MPA_ERR_ARG; }
-	if (n_pool1 < 0 || (!pool1 && n_pool1 > 0 && (size_t)n_pool1 * 4 > ctx->cigd.cap)) { set_error("dev_spans_round1: no round-1 CIGAR pool of that size on this context"); return MPA_ERR_ARG; }
+	if (L.up_bytes > ctx->spans.h_sp_up.cap || L.down_bytes > ctx->spans.h_sp_down.cap) { set_error("dev_spans_round1: the staging block was not sized for this call"); return MPA_ERR_ARG; }
+	if (n_pool1 < 0 || (!pool1 && n_pool1 > 0 && (size_t)n_pool1 * 4 > ctx->round.cigd.cap)) { set_error("dev_spans_round1: no round-1 CIGAR pool of that size on this context"); return MPA_ERR_ARG; }
 	tl_alloc_failed = false;
-	if (ctx->sp_in.ensure(L.up_bytes) != MPA_OK || ctx->sp_mid.ensure(L.mid_bytes) != MPA_OK || ctx->sp_out.ensure(L.down_bytes) != MPA_OK ||
-	    ctx->sp_pool1.ensure((size_t)n_pool1 * 4 + 16) != MPA_OK)
+	if (ctx->spans.sp_in.ensure(L.up_bytes) != MPA_OK || ctx->spans.sp_mid.ensure(L.mid_bytes) != MPA_OK || ctx->spans.sp_out.ensure(L.down_bytes) != MPA_OK ||
+	    ctx->spans.sp_pool1.ensure((size_t)n_pool1 * 4 + 16) != MPA_OK)
 		return tl_alloc_failed ? MPA_ERR_UNSUPPORTED : MPA_ERR_HIP;
 	hipStream_t s = ctx->stream;
-	char *hu = ctx->h_sp_up.as<char>();
+	char *hu = ctx->spans.h_sp_up.as<char>();
 	aln_tables_fill((uint8_t*)hu, mat, (size_t)(p.asize * p.asize));
-	HIP_TRY(hipMemcpyAsync(ctx->sp_in.p, hu, L.up_bytes - 16, hipMemcpyHostToDevice, s));
+	HIP_TRY(hipMemcpyAsync(ctx->spans.sp_in.p, hu, L.up_bytes - 16, hipMemcpyHostToDevice, s));
 	// the round-1 pool stays: round 2 overwrites cigd
-	if (n_pool1 > 0) HIP_TRY(hipMemcpyAsync(ctx->sp_pool1.p, pool1 ? (const void*)pool1 : ctx->cigd.p, (size_t)n_pool1 * 4, pool1 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
-	const char *din = ctx->sp_in.as<char>();
-	char *mid = ctx->sp_mid.as<char>(), *dout = ctx->sp_out.as<char>();
+	if (n_pool1 > 0) HIP_TRY(hipMemcpyAsync(ctx->spans.sp_pool1.p, pool1 ? (const void*)pool1 : ctx->round.cigd.p, (size_t)n_pool1 * 4, pool1 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+	const char *din = ctx->spans.sp_in.as<char>();
+	char *mid = ctx->spans.sp_mid.as<char>(), *dout = ctx->spans.sp_out.as<char>();
 	SpansArgs a;
 	a.plan = (const SpansPlan*)(din + L.off_plan), a.n_plan = (int32_t)n_plan, a.rst1 = (const mpa_dp_rst_t*)(din + L.off_rst1);
 	a.text = (const uint8_t*)(din + L.off_text), a.tabs = (const uint8_t*)din, a.seq = (const uint8_t*)d->seq, a.ctg_off = d->ctg_off, a.ctg_len = d->ctg_len;
@@ -220,60 +220,60 @@ int dev_spans_round1(mpa_ctx_t *ctx, mpa_idx_s *mi, const SpansParams &p, const 
 		                   (int64_t*)(dout + 8));
 		HIP_TRY(hipGetLastError());
 	}
-	char *hd = ctx->h_sp_down.as<char>();
+	char *hd = ctx->spans.h_sp_down.as<char>();
 	HIP_TRY(hipMemcpyAsync(hd, dout, L.down_bytes - 16, hipMemcpyDeviceToHost, s));
 	HIP_TRY(wait_stream(ctx, s));
 	io.n_task = *(const int32_t*)hd, io.rec = (const SpanRec*)(hd + L.off_rec), io.task = (const mpa_dp_task_t*)(hd + L.off_task);
 	io.r2 = DpResidentIn();
 	if (want_r2) { const int64_t *bd = (const int64_t*)(hd + 8); io.r2.d_tasks = (const mpa_dp_task_t*)(dout + L.off_task), io.r2.prep_bound = bd[0], io.r2.max_nl = bd[1], io.r2.max_al = bd[2]; }
 	if (io.n_task < 0 || io.n_task > 2 * n_plan) { set_error("dev_spans_round1: an impossible task count"); return MPA_ERR_HIP; }
-	ctx->sp_keep.off_plan = L.off_plan, ctx->sp_keep.off_seg = L.off_seg, ctx->sp_keep.off_rst1 = L.off_rst1, ctx->sp_keep.n_plan = n_plan, ctx->sp_keep.n_pool1 = n_pool1;
+	ctx->spans.sp_keep.off_plan = L.off_plan, ctx->spans.sp_keep.off_seg = L.off_seg, ctx->spans.sp_keep.off_rst1 = L.off_rst1, ctx->spans.sp_keep.n_plan = n_plan, ctx->spans.sp_keep.n_pool1 = n_pool1;
 	return MPA_OK;
 }
 
 int dev_spans_asm_stage(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, SpansAsmIO &io)
 {
 	io = SpansAsmIO();
-	if (n_plan <= 0 || n_plan != ctx->sp_keep.n_plan || n_rst2 < 0) { set_error("GPU spans: the plans of this batch are not on the device"); return MPA_ERR_UNSUPPORTED; }
+	if (n_plan <= 0 || n_plan != ctx->spans.sp_keep.n_plan || n_rst2 < 0) { set_error("GPU spans: the plans of this batch are not on the device"); return MPA_ERR_UNSUPPORTED; }
 	if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return MPA_ERR_HIP; }
 	const AsmLayout L(n_plan, n_rst2, 0);
-	if (ctx->h_sp_up2.ensure(L.up_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
-	char *hu = ctx->h_sp_up2.as<char>();
+	if (ctx->spans.h_sp_up2.ensure(L.up_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
+	char *hu = ctx->spans.h_sp_up2.as<char>();
 	io.rst2 = (mpa_dp_rst_t*)hu, io.slot_off = (int64_t*)(hu + L.off_slot);
 	return MPA_OK;
 }
 
 int dev_spans_assemble(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, const uint32_t *pool2, int64_t n_pool2, SpansAsmIO &io, const mpa_dp_rst_t *d_rst2)
 {
-	if (n_plan <= 0 || n_plan != ctx->sp_keep.n_plan) { set_error("dev_spans_assemble: the plans of this batch are not on the device"); return MPA_ERR_ARG; }
+	if (n_plan <= 0 || n_plan != ctx->spans.sp_keep.n_plan) { set_error("dev_spans_assemble: the plans of this batch are not on the device"); return MPA_ERR_ARG; }
 	HIP_TRY(hipSetDevice(ctx->device));
 	const AsmLayout L0(n_plan, n_rst2, 0), L(n_plan, n_rst2, pool2 ? n_pool2 : 0);
-	if (L0.up_bytes > ctx->h_sp_up2.cap || !io.slot_off) { set_error("dev_spans_assemble: the staging block was not sized for this call"); return MPA_ERR_ARG; }
-	if (n_pool2 < 0 || (!pool2 && n_pool2 > 0 && (size_t)n_pool2 * 4 > ctx->cigd.cap)) { set_error("dev_spans_assemble: no round-2 CIGAR pool of that size on this context"); return MPA_ERR_ARG; }
+	if (L0.up_bytes > ctx->spans.h_sp_up2.cap || !io.slot_off) { set_error("dev_spans_assemble: the staging block was not sized for this call"); return MPA_ERR_ARG; }
+	if (n_pool2 < 0 || (!pool2 && n_pool2 > 0 && (size_t)n_pool2 * 4 > ctx->round.cigd.cap)) { set_error("dev_spans_assemble: no round-2 CIGAR pool of that size on this context"); return MPA_ERR_ARG; }
 	const int64_t n_words = io.slot_off[n_plan];
 	if (n_words < 0) { set_error("dev_spans_assemble: negative slot offsets"); return MPA_ERR_ARG; }
 	const size_t down_bytes = L.rec_bytes + (size_t)n_words * 4 + 16;
-	if (ctx->h_sp_down2.ensure(down_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
+	if (ctx->spans.h_sp_down2.ensure(down_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
 	tl_alloc_failed = false;
-	if (ctx->sp_in2.ensure(L.up_bytes) != MPA_OK || ctx->sp_asm.ensure(L.rec_bytes + 16) != MPA_OK || ctx->sp_cig.ensure((size_t)n_words * 4 + 16) != MPA_OK)
+	if (ctx->spans.sp_in2.ensure(L.up_bytes) != MPA_OK || ctx->spans.sp_asm.ensure(L.rec_bytes + 16) != MPA_OK || ctx->spans.sp_cig.ensure((size_t)n_words * 4 + 16) != MPA_OK)
 		return tl_alloc_failed ? MPA_ERR_UNSUPPORTED : MPA_ERR_HIP;
 	hipStream_t s = ctx->stream;
-	char *din2 = ctx->sp_in2.as<char>();
+	char *din2 = ctx->spans.sp_in2.as<char>();
 	// (d_rst2: round 2's records are on the device already, where the round's own kernels wrote them -- only the slot offsets go up)
 	const size_t up_from = d_rst2 ? L0.off_slot : 0;
-	HIP_TRY(hipMemcpyAsync(din2 + up_from, ctx->h_sp_up2.as<char>() + up_from, L0.up_bytes - 16 - up_from, hipMemcpyHostToDevice, s));
+	HIP_TRY(hipMemcpyAsync(din2 + up_from, ctx->spans.h_sp_up2.as<char>() + up_from, L0.up_bytes - 16 - up_from, hipMemcpyHostToDevice, s));
 	if (pool2 && n_pool2 > 0) HIP_TRY(hipMemcpyAsync(din2 + L.off_pool2, pool2, (size_t)n_pool2 * 4, hipMemcpyHostToDevice, s));
-	const char *din = ctx->sp_in.as<char>();
+	const char *din = ctx->spans.sp_in.as<char>();
 	AsmArgs a;
-	a.plan = (const SpansPlan*)(din + ctx->sp_keep.off_plan), a.rec = (const SpanRec*)(ctx->sp_out.as<char>() + SPANS_HEAD_BYTES), a.n_plan = (int32_t)n_plan;
-	a.gap = (const SegRec*)(din + ctx->sp_keep.off_seg), a.rst1 = (const mpa_dp_rst_t*)(din + ctx->sp_keep.off_rst1), a.rst2 = d_rst2 ? d_rst2 : (const mpa_dp_rst_t*)din2;
-	a.pool1 = ctx->sp_pool1.as<uint32_t>(), a.pool2 = pool2 ? (const uint32_t*)(din2 + L.off_pool2) : ctx->cigd.as<uint32_t>();
-	a.slot_off = (const int64_t*)(din2 + L.off_slot), a.cig = ctx->sp_cig.as<uint32_t>(), a.out = ctx->sp_asm.as<AsmRec>();
+	a.plan = (const SpansPlan*)(din + ctx->spans.sp_keep.off_plan), a.rec = (const SpanRec*)(ctx->spans.sp_out.as<char>() + SPANS_HEAD_BYTES), a.n_plan = (int32_t)n_plan;
+	a.gap = (const SegRec*)(din + ctx->spans.sp_keep.off_seg), a.rst1 = (const mpa_dp_rst_t*)(din + ctx->spans.sp_keep.off_rst1), a.rst2 = d_rst2 ? d_rst2 : (const mpa_dp_rst_t*)din2;
+	a.pool1 = ctx->spans.sp_pool1.as<uint32_t>(), a.pool2 = pool2 ? (const uint32_t*)(din2 + L.off_pool2) : ctx->round.cigd.as<uint32_t>();
+	a.slot_off = (const int64_t*)(din2 + L.off_slot), a.cig = ctx->spans.sp_cig.as<uint32_t>(), a.out = ctx->spans.sp_asm.as<AsmRec>();
 	hipLaunchKernelGGL(k_assemble, dim3((unsigned)((n_plan + STATS_WAVES - 1) / STATS_WAVES)), dim3(64 * STATS_WAVES), 0, s, a);
 	HIP_TRY(hipGetLastError());
-	char *hd = ctx->h_sp_down2.as<char>();
-	HIP_TRY(hipMemcpyAsync(hd, ctx->sp_asm.p, (size_t)n_plan * sizeof(AsmRec), hipMemcpyDeviceToHost, s));
-	if (n_words > 0) HIP_TRY(hipMemcpyAsync(hd + L.rec_bytes, ctx->sp_cig.p, (size_t)n_words * 4, hipMemcpyDeviceToHost, s));
+	char *hd = ctx->spans.h_sp_down2.as<char>();
+	HIP_TRY(hipMemcpyAsync(hd, ctx->spans.sp_asm.p, (size_t)n_plan * sizeof(AsmRec), hipMemcpyDeviceToHost, s));
+	if (n_words > 0) HIP_TRY(hipMemcpyAsync(hd + L.rec_bytes, ctx->spans.sp_cig.p, (size_t)n_words * 4, hipMemcpyDeviceToHost, s));
 	HIP_TRY(wait_stream(ctx, s));
 	io.rec = (const AsmRec*)hd, io.cigar = (const uint32_t*)(hd + L.rec_bytes);
 	return MPA_OK;
@@ -285,14 +285,14 @@ int dev_task_bounds(mpa_ctx_t *ctx, const mpa_dp_task_t *d_tasks, int64_t n, DpR
 	out = DpResidentIn();
 	if (n <= 0 || n > (int64_t)1 << 28) { set_error("dev_task_bounds: no tasks, or too many for one launch"); return MPA_ERR_ARG; }
 	HIP_TRY(hipSetDevice(ctx->device));
-	if (ctx->sp_mid.ensure(64) != MPA_OK) return MPA_ERR_HIP;
+	if (ctx->spans.sp_mid.ensure(64) != MPA_OK) return MPA_ERR_HIP;
 	hipStream_t s = ctx->stream;
 	int64_t h[4] = { 0, 0, 0, 0 };                       // bounds[3] | the count
 	*(int32_t*)(h + 3) = (int32_t)n;
-	HIP_TRY(hipMemcpyAsync(ctx->sp_mid.p, h, sizeof h, hipMemcpyHostToDevice, s));
-	hipLaunchKernelGGL(k_task_bounds, dim3((unsigned)((n + SPANS_BLOCK - 1) / SPANS_BLOCK)), dim3(SPANS_BLOCK), 0, s, d_tasks, (const int32_t*)(ctx->sp_mid.as<int64_t>() + 3), ctx->sp_mid.as<int64_t>());
+	HIP_TRY(hipMemcpyAsync(ctx->spans.sp_mid.p, h, sizeof h, hipMemcpyHostToDevice, s));
+	hipLaunchKernelGGL(k_task_bounds, dim3((unsigned)((n + SPANS_BLOCK - 1) / SPANS_BLOCK)), dim3(SPANS_BLOCK), 0, s, d_tasks, (const int32_t*)(ctx->spans.sp_mid.as<int64_t>() + 3), ctx->spans.sp_mid.as<int64_t>());
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(h, ctx->sp_mid.p, 24, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h, ctx->spans.sp_mid.p, 24, hipMemcpyDeviceToHost, s));
 	HIP_TRY(wait_stream(ctx, s));
 	out.d_tasks = d_tasks, out.prep_bound = h[0], out.max_nl = h[1], out.max_al = h[2];
 	return MPA_OK;
