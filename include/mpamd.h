@@ -170,7 +170,16 @@ typedef struct {
 } mpa_qbatch_t;
 
 /* Run n DP calls on the GPU.  rst[n] is filled; *cigar_pool receives a malloc'd pool (caller frees with
- * mpa_free) holding every CIGAR as len<<4|op words (nasw.h:33-44).  The index must be on the device. */
+ * mpa_free) holding every CIGAR as len<<4|op words (nasw.h:33-44).  The index must be on the device.
+ *
+ * Windows of fewer than three rows (nl = 0, 1, 2; the first row the DP sweeps is row 2) are accepted in every mode:
+ *   - a traceback call (MPA_F_CIGAR) returns what ns_global_gs16b() returns: nt_len = nl, aa_len = al, score -32768 and the CIGAR of
+ *     the empty walk (nl F, then (al - 1) I; no word where a length is 0);
+ *   - an extension call (MPA_F_EXT_LEFT / MPA_F_EXT_RIGHT) returns nt_len = 0, aa_len = al + 1, score = INT32_MIN, whatever its width
+ *     and whatever the options.  ns_global_gs16b() fails its own assertion on such a call (nasw-sse.c:441); the triple is what it
+ *     computes with assertions compiled out.  No kernel sweeps the call: the planner gives it no unit and the result rule writes the
+ *     triple (dp_plan_core.h, dp_results_core.h).  A caller must read nt_len = 0 as "nothing was extended" and ignore aa_len then,
+ *     as mpa_map_batch() does. */
 int mpa_dp_run(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *opt, const mpa_qbatch_t *q,
                int64_t n, const mpa_dp_task_t *tasks, mpa_dp_rst_t *rst, uint32_t **cigar_pool, int64_t *n_pool);
 void mpa_free(void *p);

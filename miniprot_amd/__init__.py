@@ -556,7 +556,7 @@ def dbg_dp_plan_device(ctx, dpopt, ctg_len, q_off, tasks, knobs):
 
 DP_PLAN_KNOBS_WIDE = ("lite_min", "lite_wide", "no_split", "antidiag", "pool", "ext_dual", "unit_prio", "tb_budget", "split_wide")
 DP_PLAN_WIDE_TAIL = 40   # bytes the *_wide serialisations add: int64 first, count of X_SPLIT8; first, count of X_SPLIT12; n_bound
-X_HUGE, X_SPLIT8, X_SPLIT12 = 7, 9, 10   # DpClass numbers (dp_device.h) in dbg_dp_last_classes()
+X_HUGE, X_SPLIT8, X_SPLIT12, X_NONE = 7, 9, 10, 11   # DpClass numbers (dp_device.h) in dbg_dp_last_classes(); X_NONE: extension calls of fewer than three rows, swept by nobody
 
 
 def _dp_plan_wide(f, head, dpopt, ctg_len, q_off, tasks, knobs, declines):

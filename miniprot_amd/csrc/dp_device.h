@@ -45,6 +45,7 @@ enum DpClass : int32_t {
 	X_128,                       // 65..128 columns, one call per wave (column c + 64 in the high half of lane c)
 	X_SPLIT8, X_SPLIT12,         // up to 2048 / 3072 columns: eight / twelve workgroups per pair of calls (MPA_DP_SPLIT_WIDE=1; else such calls are X_HUGE).
 	                             // Numbered behind X_128 so that no earlier number moves; their ExtWave descriptors follow X_SPLIT4's
+	X_NONE,                      // fewer than three rows: nothing to sweep.  No descriptor, no unit; the result rule (dp_results_core.h) answers the call
 	// traceback calls (CIGAR): the plain sweep that writes the traceback matrix ...
 	T_16 = 0, T_32, T_64,        // 4 / 2 / 1 call(s) per wave
 	T_W2, T_W4, T_W8, T_W16,     // one call per group of 2 / 4 / 8 / 16 waves: up to 128 / 256 / 512 / 1024 columns

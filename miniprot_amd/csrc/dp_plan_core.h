@@ -50,6 +50,11 @@ struct DpPlanKnobs {
 };
 
 // ---- the per-call rules of classify()
+// An extension call of fewer than three rows has no row to sweep (the first swept row is row 2): the reference fails its own assertion
+// there (nasw-sse.c:441), and with assertions compiled out it returns (nt_len 0, aa_len al + 1, score INT32_MIN).  That triple is this
+// operator's contract (include/mpamd.h).  The planner gives such a call the class X_NONE -- no wave descriptor, no unit, no kernel ever
+// sees it -- and dp_result_of() (dp_results_core.h) writes the triple, on the host and on the device.
+MPA_DPP_HD bool dp_ext_unswept(int32_t flag, int32_t nl) { return (flag & (MPA_F_EXT_LEFT | MPA_F_EXT_RIGHT)) != 0 && nl < 3; }
 // the scalar options a call's class depends on; max_mat: the largest entry of the scoring matrix
 struct DpPlanOpt { int32_t go, ge, fs, xdrop, end_bonus, max_mat; };
 MPA_DPP_HD DpPlanOpt dp_plan_opt(const mpa_dpopt_t *opt)
@@ -108,6 +113,7 @@ MPA_DPP_HD int dp_classify_call(const mpa_dp_task_t &x, int32_t k, int32_t n_ctg
 		t.pw = cls == X_HUGE ? t.ncol : ext_columns(cls);
 		// 65..128 columns: one wave per call instead of a two-wave group per pair of calls (MPA_DP_EXT_DUAL=0: the two-wave groups)
 		if (cls == X_W2 && kn.ext_dual && !kn.antidiag) cls = X_128;
+		if (dp_ext_unswept(x.flag, x.nl)) cls = X_NONE;             // nothing to sweep: answered by the result rule (the refusals above stay)
 		t.cls = cls;
 	} else {
 		if (!(x.flag & MPA_F_CIGAR)) return DP_CALL_NO_CIGAR;

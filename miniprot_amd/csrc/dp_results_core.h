@@ -29,11 +29,13 @@ MPA_DPP_HD DpTaskBounds dp_task_bounds(const mpa_dp_task_t *in, int64_t n)
 
 // ---- the rule: call k's record from its mode and shape and from what the kernels left.  An extension call takes its lengths and score
 // from its ExtOut and has no CIGAR; a traceback call covers its whole window and slice, its score and word count are the sweep's and the
-// walk's, its words start at dense_off in the dense pool.  Only what the call's mode needs is read.
+// walk's, its words start at dense_off in the dense pool.  Only what the call's mode needs is read.  An extension call of fewer than three
+// rows (class X_NONE: no kernel swept it, its ExtOut was never written) is (0, al + 1, INT32_MIN), the contract of include/mpamd.h.
 MPA_DPP_HD mpa_dp_rst_t dp_result_of(int32_t flag, int32_t nl, int32_t al, int64_t k, const ExtOut *eo, const int32_t *sc, const int32_t *nc, int64_t dense_off)
 {
 	mpa_dp_rst_t o;
-	if (flag & (MPA_F_EXT_LEFT | MPA_F_EXT_RIGHT)) o.nt_len = eo[k].nt_len, o.aa_len = eo[k].aa_len, o.score = eo[k].score, o.n_cigar = 0, o.cigar_off = 0;
+	if (dp_ext_unswept(flag, nl)) o.nt_len = 0, o.aa_len = al + 1, o.score = INT32_MIN, o.n_cigar = 0, o.cigar_off = 0;
+	else if (flag & (MPA_F_EXT_LEFT | MPA_F_EXT_RIGHT)) o.nt_len = eo[k].nt_len, o.aa_len = eo[k].aa_len, o.score = eo[k].score, o.n_cigar = 0, o.cigar_off = 0;
 	else o.nt_len = nl, o.aa_len = al, o.score = sc[k], o.n_cigar = nc[k], o.cigar_off = dense_off;
 	return o;
 }

@@ -162,13 +162,14 @@ static void take_round1_emit_round2(mpa_batch_s *b, const mpa_dp_rst_t *rst, con
 			AlignPlan &pl = qs.plans[pi];
 			const mpa_dp_rst_t *mine = rst + qs.base1;                 // this query's slice of the round-1 results
 			for (Segment &g : pl.gaps) store_result(g, mine, pool);
-			pl.l_nt = mine[pl.t_left].nt_len, pl.l_aa = mine[pl.t_left].aa_len;
+			// (spans_ext_aa, spans_core.h: a call that consumed no row extended nothing -- the (0, al + 1, INT32_MIN) of a window of fewer than three rows)
+			pl.l_nt = mine[pl.t_left].nt_len, pl.l_aa = spans_ext_aa(mine[pl.t_left]);
 			// the terminal-exon repeat counts iff the reference would have made it AND it reaches the end of the protein (align.c:290-296)
-			if (pl.t_left2 >= 0 && pl.l_aa != pl.as1 && pl.l_nt < opt.max_ext && mine[pl.t_left2].aa_len == pl.as1)
+			if (pl.t_left2 >= 0 && pl.l_aa != pl.as1 && pl.l_nt < opt.max_ext && spans_ext_aa(mine[pl.t_left2]) == pl.as1)
 				pl.l_nt = mine[pl.t_left2].nt_len, pl.l_aa = mine[pl.t_left2].aa_len, pl.l_rep = true;
 			if (pl.has_right) {
-				pl.r_nt = mine[pl.t_right].nt_len, pl.r_aa = mine[pl.t_right].aa_len;
-				if (pl.t_right2 >= 0 && pl.r_aa < qs.qlen - pl.mid_qe && pl.r_nt < opt.max_ext && mine[pl.t_right2].aa_len == qs.qlen - pl.mid_qe)
+				pl.r_nt = mine[pl.t_right].nt_len, pl.r_aa = spans_ext_aa(mine[pl.t_right]);
+				if (pl.t_right2 >= 0 && pl.r_aa < qs.qlen - pl.mid_qe && pl.r_nt < opt.max_ext && spans_ext_aa(mine[pl.t_right2]) == qs.qlen - pl.mid_qe)
 					pl.r_nt = mine[pl.t_right2].nt_len, pl.r_aa = mine[pl.t_right2].aa_len, pl.r_rep = true;
 			}
 		}

@@ -69,6 +69,12 @@ template<class S> MPA_HD inline bool spans_segment(const SpansParams &p, const S
 	return true;
 }
 
+// Residues an extension call consumed, as the accept rules read them.  A call that consumed no row of its window extended nothing,
+// whatever its aa_len says: mpa_dp_run() answers an extension call of fewer than three rows with (0, al + 1, INT32_MIN) (include/mpamd.h;
+// the reference fails an assertion there), and al + 1 residues must neither move a region's start or end nor pass for "reached the end
+// of the protein".  Every swept call that finds no best row returns (0, 0) already.
+MPA_HD inline int32_t spans_ext_aa(const mpa_dp_rst_t &r) { return r.nt_len > 0 ? r.aa_len : 0; }
+
 // One plan between the rounds.  rst1: the round-1 results of the batch; g: the strand of P.vid; text: the batch's protein text.
 // Returns the number of round-2 tasks (0 .. 2) written to t[]; R.left.task / R.right.task number them from 0 (the caller adds the
 // tasks of the plans before this one)
@@ -77,13 +83,15 @@ template<class S> MPA_HD inline int32_t spans_accept(const SpansParams &p, const
 {
 	const PlanRec &pl = P.pl;
 	const mpa_dp_rst_t *mine = rst1 + P.base1;
-	int32_t l_nt = mine[pl.t_left].nt_len, l_aa = mine[pl.t_left].aa_len, r_nt = 0, r_aa = 0, flags = SPANS_LEFT;
+	// (an extension that consumed no row is no extension: spans_ext_aa() makes the (0, al + 1, INT32_MIN) of a window of fewer than
+	// three rows the (0, 0) every swept call that finds no best row returns)
+	int32_t l_nt = mine[pl.t_left].nt_len, l_aa = spans_ext_aa(mine[pl.t_left]), r_nt = 0, r_aa = 0, flags = SPANS_LEFT;
 	// the terminal-exon repeat counts iff the reference would have made it AND it reaches the end of the protein (align.c:290-296)
-	if (pl.t_left2 >= 0 && l_aa != pl.as1 && l_nt < p.max_ext && mine[pl.t_left2].aa_len == pl.as1)
+	if (pl.t_left2 >= 0 && l_aa != pl.as1 && l_nt < p.max_ext && spans_ext_aa(mine[pl.t_left2]) == pl.as1)
 		l_nt = mine[pl.t_left2].nt_len, l_aa = mine[pl.t_left2].aa_len, flags |= SPANS_LREP;
 	if (pl.has_right) {
-		r_nt = mine[pl.t_right].nt_len, r_aa = mine[pl.t_right].aa_len;
-		if (pl.t_right2 >= 0 && r_aa < P.qlen - pl.mid_qe && r_nt < p.max_ext && mine[pl.t_right2].aa_len == P.qlen - pl.mid_qe)
+		r_nt = mine[pl.t_right].nt_len, r_aa = spans_ext_aa(mine[pl.t_right]);
+		if (pl.t_right2 >= 0 && r_aa < P.qlen - pl.mid_qe && r_nt < p.max_ext && spans_ext_aa(mine[pl.t_right2]) == P.qlen - pl.mid_qe)
 			r_nt = mine[pl.t_right2].nt_len, r_aa = mine[pl.t_right2].aa_len, flags |= SPANS_RREP;
 	}
 	R.l_nt = l_nt, R.l_aa = l_aa, R.r_nt = r_nt, R.r_aa = r_aa;

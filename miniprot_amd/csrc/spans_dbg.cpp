@@ -48,8 +48,8 @@ static int mpa_dbg_spans_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_map
 		    (int64_t)pl.gap0 + pl.n_gap > n_seg || (P.vid >> 1) >= mi->ctg.size() || P.qlen < 0 || P.q_off < 0 || P.q_off + P.qlen > text_bytes || pl.as1 < 0 || pl.as1 > P.qlen ||
 		    pl.mid_qe < 0 || pl.mid_qe > P.qlen) { set_error("mpa_dbg_spans: a plan that points outside its inputs"); return MPA_ERR_ARG; }
 		const mpa_dp_rst_t *mine = rst1 + P.base1;
-		for (int32_t t : { pl.t_left, pl.t_left2 }) if (t >= 0 && (mine[t].aa_len < 0 || mine[t].aa_len > pl.as1 || mine[t].nt_len < 0)) { set_error("mpa_dbg_spans: a left extension longer than its protein slice"); return MPA_ERR_ARG; }
-		for (int32_t t : { pl.t_right, pl.t_right2 }) if (t >= 0 && (mine[t].aa_len < 0 || mine[t].aa_len > P.qlen - pl.mid_qe || mine[t].nt_len < 0)) { set_error("mpa_dbg_spans: a right extension longer than its protein slice"); return MPA_ERR_ARG; }
+		for (int32_t t : { pl.t_left, pl.t_left2 }) if (t >= 0 && (mine[t].aa_len < 0 || spans_ext_aa(mine[t]) > pl.as1 || mine[t].nt_len < 0)) { set_error("mpa_dbg_spans: a left extension longer than its protein slice"); return MPA_ERR_ARG; }
+		for (int32_t t : { pl.t_right, pl.t_right2 }) if (t >= 0 && (mine[t].aa_len < 0 || spans_ext_aa(mine[t]) > P.qlen - pl.mid_qe || mine[t].nt_len < 0)) { set_error("mpa_dbg_spans: a right extension longer than its protein slice"); return MPA_ERR_ARG; }
 		for (int32_t g = 0; g < pl.n_gap; ++g) {
 			const SegRec &x = seg[pl.gap0 + g];
 			if (x.task < -1 || (x.task >= 0 && (int64_t)P.base1 + x.task >= n_rst1)) { set_error("mpa_dbg_spans: a gap segment without a result"); return MPA_ERR_ARG; }

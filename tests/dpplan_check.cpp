@@ -94,6 +94,16 @@ int main()
 		std::vector<mpa_dp_task_t> tasks = { call(rng, true, 30, 100), call(rng, false, 30, 100), call(rng, true, 500, 300) };
 		DpPlanKnobs kn;
 		check("three calls", tasks, opt, kn, false);
+		// extension calls of fewer than three rows are swept by nobody (class X_NONE): planned alike at every width, 1 100 columns included
+		{
+			std::vector<mpa_dp_task_t> t3 = tasks;
+			for (int32_t nl = 0; nl < 3; ++nl)
+				for (int32_t al : { 1, 16, 17, 64, 65, 128, 129, 256, 257, 512, 1024, 1025, 1100 }) t3.push_back(call(rng, true, al, nl)), t3.push_back(call(rng, false, al > 300 ? 300 : al, nl));
+			for (int k = 0; k < 40; ++k) t3.push_back(call(rng, (rng() & 1) != 0, 1 + (int32_t)(rng() % 1000), 3 + (int32_t)(rng() % 900)));
+			check("extension calls of fewer than three rows", t3, opt, kn, false);
+			DpPlanKnobs k3 = kn; k3.lite_min = 3, k3.lite_wide = 1; check("... with the checkpointed classes from three rows", t3, opt, k3, false);
+			check("only such calls", std::vector<mpa_dp_task_t>(t3.begin() + 3, t3.begin() + 3 + 2), opt, kn, false);
+		}
 		DpPlanKnobs k2 = kn; k2.pool = 1; check("pool", tasks, opt, k2, true);
 		k2 = kn, k2.antidiag = 1; check("antidiag", tasks, opt, k2, true);
 		k2 = kn, k2.no_split = 1; check("no_split", tasks, opt, k2, true);

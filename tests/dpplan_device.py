@@ -41,6 +41,12 @@ def planned():
     c = dpplan.cases()
     for name in ("b_glob", "c_wide", "k_no_dual_no_prio"):
         t["cases_" + name] = c[name]
+    # extension calls of fewer than three rows (class X_NONE: no descriptor, no unit) of every width -- 1 100 columns too, which with more
+    # rows is the class the device planner declines -- between ordinary calls and traceback calls of as few rows
+    r = np.random.default_rng(9244)
+    spec = [(EXT, al, nl) for nl in (0, 1, 2) for al in (1, 8, 24, 50, 100, 200, 400, 800, 1025, 1100)] + [(GLOB, al, nl) for nl in (0, 1, 2) for al in (1, 40, 300, 1100)]
+    spec += _spread(r, EXT, 20, al_max=1024) + _spread(r, GLOB, 20, al_max=300)
+    t["tiny_ext"] = (_table(r, [spec[k] for k in r.permutation(len(spec))]), {}, {})
     return t
 
 

@@ -29,14 +29,16 @@ def made_up(tasks, rng, nc=None, zero_every=0):
 
 def host_loop(tasks, eo, sc, nc, gids):
     """dp_assemble()'s offsets and its last loop as they were before the shared rule: dense offsets in sorted-call order, then one record
-    per call from the caller's own task"""
+    per call from the caller's own task (an extension call of fewer than three rows: (0, al + 1, INT32_MIN), which no kernel computes)"""
     off_of, pool_n = {}, 0
     for g in gids.tolist():
         off_of[g] = pool_n
         pool_n += int(nc[g])
     rst = np.zeros(len(tasks), dtype=mpa.DP_RST)
     for k in range(len(tasks)):
-        if int(tasks["flag"][k]) & EXT_BITS:
+        if int(tasks["flag"][k]) & EXT_BITS and int(tasks["nl"][k]) < 3:   # no row to sweep: the contract of include/mpamd.h, whatever the outputs hold
+            rst[k] = (0, int(tasks["al"][k]) + 1, -2 ** 31, 0, 0)
+        elif int(tasks["flag"][k]) & EXT_BITS:
             rst[k] = (eo[k, 0], eo[k, 1], eo[k, 2], 0, 0)
         else:
             rst[k] = (tasks["nl"][k], tasks["al"][k], sc[k], nc[k], off_of[k])

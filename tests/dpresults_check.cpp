@@ -90,7 +90,8 @@ static void check(const char *what, std::mt19937_64 &rng, size_t n, int ext_of_1
 	for (size_t k = 0; k < n; ++k) {
 		const mpa_dp_task_t &t = tasks[k];
 		mpa_dp_rst_t &o = want[k];
-		if (t.flag & (MPA_F_EXT_LEFT | MPA_F_EXT_RIGHT)) o.nt_len = eo[k].nt_len, o.aa_len = eo[k].aa_len, o.score = eo[k].score, o.n_cigar = 0, o.cigar_off = 0;
+		if ((t.flag & (MPA_F_EXT_LEFT | MPA_F_EXT_RIGHT)) && t.nl < 3) o.nt_len = 0, o.aa_len = t.al + 1, o.score = INT32_MIN, o.n_cigar = 0, o.cigar_off = 0;   // (no row to sweep: mpamd.h)
+		else if (t.flag & (MPA_F_EXT_LEFT | MPA_F_EXT_RIGHT)) o.nt_len = eo[k].nt_len, o.aa_len = eo[k].aa_len, o.score = eo[k].score, o.n_cigar = 0, o.cigar_off = 0;
 		else o.nt_len = t.nl, o.aa_len = t.al, o.score = sc[k], o.n_cigar = nc[k], o.cigar_off = off_of[k];
 	}
 	// the stages, every output in a block of exactly its bound

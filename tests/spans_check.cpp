@@ -190,11 +190,14 @@ static void plain_accept(const SpansParams &p, const Built &b, const std::string
 	const PlanRec &pl = b.P.pl;
 	const mpa_dp_rst_t *mine = b.rst1.data() + b.P.base1;
 	o.tasks.assign((size_t)task0, mpa_dp_task_t());                              // (the tasks of the plans before this one)
-	o.l_nt = mine[pl.t_left].nt_len, o.l_aa = mine[pl.t_left].aa_len;
-	if (pl.t_left2 >= 0 && o.l_aa != pl.as1 && o.l_nt < p.max_ext && mine[pl.t_left2].aa_len == pl.as1) o.l_nt = mine[pl.t_left2].nt_len, o.l_aa = mine[pl.t_left2].aa_len, o.l_rep = true;
+	// (a call that consumed no row extended nothing, whatever its aa_len says: an extension call of fewer than three rows returns
+	// (0, al + 1, INT32_MIN), include/mpamd.h)
+	auto aa_of = [](const mpa_dp_rst_t &x) { return x.nt_len > 0 ? x.aa_len : 0; };
+	o.l_nt = mine[pl.t_left].nt_len, o.l_aa = aa_of(mine[pl.t_left]);
+	if (pl.t_left2 >= 0 && o.l_aa != pl.as1 && o.l_nt < p.max_ext && aa_of(mine[pl.t_left2]) == pl.as1) o.l_nt = mine[pl.t_left2].nt_len, o.l_aa = mine[pl.t_left2].aa_len, o.l_rep = true;
 	if (pl.has_right) {
-		o.r_nt = mine[pl.t_right].nt_len, o.r_aa = mine[pl.t_right].aa_len;
-		if (pl.t_right2 >= 0 && o.r_aa < b.P.qlen - pl.mid_qe && o.r_nt < p.max_ext && mine[pl.t_right2].aa_len == b.P.qlen - pl.mid_qe)
+		o.r_nt = mine[pl.t_right].nt_len, o.r_aa = aa_of(mine[pl.t_right]);
+		if (pl.t_right2 >= 0 && o.r_aa < b.P.qlen - pl.mid_qe && o.r_nt < p.max_ext && aa_of(mine[pl.t_right2]) == b.P.qlen - pl.mid_qe)
 			o.r_nt = mine[pl.t_right2].nt_len, o.r_aa = mine[pl.t_right2].aa_len, o.r_rep = true;
 	}
 	o.vs = pl.vs1 - o.l_nt, o.qs = pl.as1 - o.l_aa;
@@ -374,6 +377,16 @@ int main()
 		c.has_right = 0;
 		w = run_case("right span: has_right == 0", P, c);
 		EXPECT(!w.has_right_span);
+		// windows of fewer than three rows: mpa_dp_run() answers (0, al + 1, INT32_MIN); neither side moves, no repeat counts
+		c.has_right = 1, c.retry = 1;
+		const int32_t rest = c.qlen - (c.as1 + 9);
+		c.r[0][0] = 0, c.r[0][1] = rest + 1, c.r[1][0] = 0, c.r[1][1] = rest + 1;
+		c.l[0][0] = 0, c.l[0][1] = c.as1 + 1, c.l[1][0] = 0, c.l[1][1] = c.as1 + 1;
+		w = run_case("both extensions on windows of fewer than three rows", P, c);
+		EXPECT(!w.has_right_span && !w.r_rep && !w.l_rep && w.r_aa == 0 && w.l_aa == 0 && w.qs == c.as1 && w.l_nt == 0);
+		c = Case();
+		c.gaps.push_back(dp_gap({ W(0, 9) }));
+		c.retry = 0;
 		c.has_right = 1, c.r[0][0] = 12, c.r[0][1] = 4;
 		w = run_case("right span: made", P, c);
 		EXPECT(w.has_right_span && w.right.task < 0 && w.ve == 3000 + 600 + 40 + 12);

@@ -85,7 +85,7 @@ def world(ctx):
     idx.close()
 
 
-@pytest.mark.parametrize("name", ["spread_default", "prep_chunk_edge"])
+@pytest.mark.parametrize("name", ["spread_default", "prep_chunk_edge", "tiny_ext"])     # (tiny_ext: extension calls of fewer than three rows, answered without a unit)
 def test_dp_run_with_the_device_plan(ctx, world, oracle_built, name, monkeypatch, capfd):
     """the executor's knobs are the context's (lite_min 384, lite_wide 0): the tables' calls, not their knob sets"""
     idx, q = world

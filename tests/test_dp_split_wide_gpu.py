@@ -138,22 +138,23 @@ def test_short_windows(ctx_on, oracle_built, al):
 
 def test_two_row_windows(ctx_on, ctx_off, oracle_built):
     """A window of two rows has no DP row at all.  The reference does not define the result: its search for the best column runs over a
-    row it never filled and ends in assert(j < al) (nasw-sse.c:436-441); the oracle, a restatement without the assert, reports aa_len =
-    al + 1 there, every extension kernel of this project reports 0 (measured on the MI355X, knob on and knob off: (0, 0, INT32_MIN)
-    against the oracle's (0, al + 1, INT32_MIN) for al = 1 500 and 2 100).  So nt_len and score are compared with the oracle, and all
-    three fields with what the one-wave sweep gives without the knob."""
+    row it never filled and ends in assert(j < al) (nasw-sse.c:436-441); the oracle, a restatement without the assert, reports
+    (0, al + 1, INT32_MIN), and that is the contract of mpa_dp_run() (include/mpamd.h).  Every extension kernel of this project would
+    report aa_len 0 (measured on the MI355X before the contract was set), so the planner gives such a call no unit -- class X_NONE with
+    the knob on and off, no X_SPLIT8 / X_SPLIT12 group, no X_HUGE call -- and the result rule writes the triple."""
     P = params()
     rng = np.random.default_rng(9450)
     w = Workload([sw.wide_pair(rng, al, rows=2, **WIDE_KW) for al in (1500, 2100)], P, 9451, modes=("right",))
     on, _ = w.results(ctx_on)
     cls = mpa.dbg_dp_last_classes(ctx_on)
-    assert (cls[sw.X_SPLIT8], cls[sw.X_SPLIT12], cls[sw.X_HUGE]) == (1, 1, 0)
+    assert (cls[sw.X_SPLIT8], cls[sw.X_SPLIT12], cls[sw.X_HUGE], cls[mpa.X_NONE]) == (0, 0, 0, 2)
     off, _ = w.results(ctx_off)
-    assert mpa.dbg_dp_last_classes(ctx_off)[sw.X_HUGE] == 2
+    cls = mpa.dbg_dp_last_classes(ctx_off)
+    assert (cls[sw.X_HUGE], cls[mpa.X_NONE]) == (0, 2)
     for k, e in enumerate(w.expect):
-        print("two-row window, al %d: knob on %s, knob off %s, oracle %s" % (len(w.pairs[k][1]), on[k], off[k], e[:3]))
-        assert (int(on[k]["nt_len"]), int(on[k]["score"])) == (e[0], e[2])
-        assert [int(on[k][f]) for f in ("nt_len", "aa_len", "score")] == [int(off[k][f]) for f in ("nt_len", "aa_len", "score")]
+        assert e[:3] == (0, len(w.pairs[k][1]) + 1, -2 ** 31)
+        for r in (on[k], off[k]):
+            assert (int(r["nt_len"]), int(r["aa_len"]), int(r["score"])) == e[:3], (k, r, e[:3])
 
 
 # ---- 2. knob off: the same tables as X_HUGE; knob on at the guard

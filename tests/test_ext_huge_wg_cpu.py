@@ -55,6 +55,12 @@ def test_tables_are_huge_calls_of_the_named_blocks(name, make, knobs):
     p = tab.plan(knobs)
     assert not isinstance(p, tuple), p
     T = p.sec["tasks"]
+    if name.startswith("two-rows-"):
+        # a window of two rows has no row to sweep: whatever its columns, the call is of class X_NONE (11), in no descriptor and behind no
+        # unit, and the result rule answers it (include/mpamd.h); with three rows it is the X_HUGE call of `want` blocks ("rows-" tables)
+        assert len(T) == 1 and int(T["nl"][0]) == 2 and (int(T["ncol"][0]) + 63) // 64 == want[0] and int(T["flag"][0]) & (mpa.F_EXT_LEFT | mpa.F_EXT_RIGHT)
+        assert int(T["cls"][0]) == 11 and p.header["n_huge"] == p.header["n_units"] == p.header["n_ewaves"] == 0
+        return
     huge = T[(T["cls"] == sw.X_HUGE) & ((T["flag"] & (mpa.F_EXT_LEFT | mpa.F_EXT_RIGHT)) != 0)]
     assert p.header["n_huge"] == len(huge) == len(want) > 0
     assert sorted((int(c) + 63) // 64 for c in huge["ncol"]) == sorted(want) == sorted(tab.huge_blocks(knobs))
@@ -81,16 +87,14 @@ def test_tables_are_huge_calls_of_the_named_blocks(name, make, knobs):
     if name.startswith("rows-"):
         assert sorted(int(x) for x in huge["nl"]) == sorted(hw.row_counts())
         assert set(hw.row_counts()) == {3, 4, R + 1, R + 2, R + 3, 2 * R + 2, (W - 1) * R + 1, W * R + 3}
-    if name.startswith("two-rows-"):
-        assert [int(x) for x in huge["nl"]] == [2]
     assert hw.expected_last_huge(want, True)[1] == sum(b >= MIN_BLOCKS for b in want)
 
 
 @pytest.mark.skipif(not refbind.have_ref(), reason="the reference is not built")
 @pytest.mark.parametrize("name,make,knobs", [t for t in TABLES if not t[0].startswith("two-rows-")], ids=[t[0] for t in TABLES if not t[0].startswith("two-rows-")])
 def test_expected_values_are_the_references(oracle_built, name, make, knobs):
-    """oracle == reference (ns_global_gs16b) on every call of every table of the GPU tests (not the two-row windows, where the
-    reference leaves the result undefined: tests/test_dp_split_wide_gpu.py, test_two_row_windows)"""
+    """oracle == reference (ns_global_gs16b) on every call of every table of the GPU tests (not the two-row windows, on which the
+    reference fails its own assertion: tests/test_dp_edges_cpu.py)"""
     tab, _ = make()
     e, r = tab.expect("oracle"), tab.expect("reference")
     assert len(e) == len(tab.tasks)
