@@ -1,5 +1,5 @@
-/* mpamd_dbg.h -- the test hooks of MPA_GPU_SPANS, MPA_GPU_DPPLAN, MPA_GPU_ROUND2, the stream plan and the contexts' pool registry.  They are not part of the C ABI of libmpamd.so (include/mpamd.h):
- * they are built from miniprot_amd/csrc/spans_dbg.cpp, dpplan_dbg.cpp, round2_dbg.cpp, stream_dbg.cpp and ctx_pools_dbg.cpp into a library of its own, libmpamd_dbg.so, next to libmpamd.so
+/* mpamd_dbg.h -- the test hooks of MPA_GPU_SPANS, MPA_GPU_DPPLAN, MPA_GPU_ROUND2, the stream plan, the contexts' pool registry and the chain extraction.  They are not part of the C ABI of libmpamd.so (include/mpamd.h):
+ * they are built from miniprot_amd/csrc/spans_dbg.cpp, dpplan_dbg.cpp, round2_dbg.cpp, stream_dbg.cpp, ctx_pools_dbg.cpp and chain_dbg.cpp into a library of its own, libmpamd_dbg.so, next to libmpamd.so
  * and linked against it. */
 #ifndef MPAMD_DBG_H
 #define MPAMD_DBG_H
@@ -97,6 +97,43 @@ int64_t mpa_dbg_stream_plan_for(int32_t q, int32_t n_lanes, int32_t n_seed, int3
  * writes the name (a string the library owns) and the capacity in bytes (0: not allocated yet) of the first cap of them; names and
  * caps may be NULL with cap 0.  MPA_ERR_ARG: no context, or no sibling of that number. */
 int32_t mpa_dbg_ctx_pools(const mpa_ctx_t *ctx, int32_t sibling, const char **names, int64_t *caps, int32_t cap);
+
+/* The chain extraction (k_chain_extract = chain_extract_core of miniprot_amd/csrc/chain_core.h) on raw anchors: the eleven parameters of
+ * mp_chain in the order mpa_dbg_chain takes them, then n_prob chaining problems whose sorted anchors lie back to back in a[]
+ * (first[n_prob + 1], first[0] = 0), as for mpa_dbg_chain_forward.  mode says which view of a problem the extraction gets:
+ *   MPA_DBG_CHAIN_DENSE          every anchor, set_only 0: the main chain behind the pre-chain, the refinement chains
+ *   MPA_DBG_CHAIN_SPARSE_SET     sparse, set_only 1: the pre-chain (a_out: the anchors of the kept chains, ascending; no u)
+ *   MPA_DBG_CHAIN_SPARSE_CHAINS  sparse, set_only 0: the direct route (-S, --no-pre-chain)
+ * The sparse view is mpa_dbg_prechain_sparse's: the anchors of runs of two or more whose consecutive blocks differ by at most
+ * max(max_dist_x, bw) >> bbit, pred re-indexed into the view, n_total the full count.  It is exact when min_cnt rejects one-anchor
+ * chains or the view leaves nothing out; the hook does not check that.
+ * ctx != NULL: forward pass on the device, views built on the host from its f / pred and uploaded, then the product's own carving of
+ * the extraction scratch, status memset and launch (chain_extract_launch for the set, chain_extract_pack for chains), on the context's
+ * chaining pool as it is -- never zeroed between calls.  ctx == NULL: the host forward pass and chain_extract_core with a team of one,
+ * in work space of the kernel's sizes (room for m + 64 chain ends), so that it declines what the kernel declines.
+ * Out, per problem q: u[off_u[q] .. off_u[q + 1]) (score << 32 | anchors per chain) and a_out[off_a[q] .. off_a[q + 1]); u and a_out
+ * have room for first[n_prob] words each; status[q] = 1: the extraction declined the problem (it needs the full list of chain ends and
+ * n_total > m + 64), nothing written for it; rec[8 q ..]: the path the problem takes, computed on the host from f / pred and the view by
+ * the preconditions of chain_core.h -- [0] anchors in the view m, [1] n_total, [2] non-roots (chained anchors) in the view, [3] their
+ * largest score max_f, [4] the class, [5] c0 = n_total minus the non-roots scoring 256 or more (the region of level 1's bucket 0),
+ * [6] the largest level-1 bucket (non-roots of 256 or more sharing bits 8-15 of their score), [7] why the full list is needed (bits).
+ * Classes: FULL_LIST -- sorted_chain_ends_sparse returns -1 and the list fits; ONE_LEVEL -- max_f < 256; TWO_LEVEL; DECLINED. */
+#define MPA_DBG_CHAIN_DENSE 0
+#define MPA_DBG_CHAIN_SPARSE_SET 1
+#define MPA_DBG_CHAIN_SPARSE_CHAINS 2
+#define MPA_DBG_CHAIN_REC 8
+#define MPA_DBG_CHAIN_FULL_LIST 0
+#define MPA_DBG_CHAIN_ONE_LEVEL 1
+#define MPA_DBG_CHAIN_TWO_LEVEL 2
+#define MPA_DBG_CHAIN_DECLINED 3
+#define MPA_DBG_CHAIN_WHY_MIN_CNT 1   /* min_cnt <= 1 */
+#define MPA_DBG_CHAIN_WHY_MIN_SC 2    /* min_sc > kmer */
+#define MPA_DBG_CHAIN_WHY_SMALL 4     /* n_total <= 64 */
+#define MPA_DBG_CHAIN_WHY_MAX_F 8     /* max_f >= 65536, and nothing above */
+#define MPA_DBG_CHAIN_WHY_OTHER 16    /* kmer outside 0..255, or a chained anchor that scores no more than a lone one */
+int mpa_dbg_chain_extract(mpa_ctx_t *ctx, int32_t max_dist_x, int32_t max_dist_y, int32_t bw, int32_t max_skip, int32_t max_iter, int32_t min_cnt, int32_t min_sc,
+                          float coef_log, int32_t is_spliced, int32_t kmer, int32_t bbit, int32_t n_prob, const int64_t *first, const uint64_t *a, int32_t mode,
+                          int64_t *off_u, uint64_t *u, int64_t *off_a, uint64_t *a_out, int32_t *status, int64_t *rec);
 
 #ifdef __cplusplus
 }

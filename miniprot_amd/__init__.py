@@ -721,6 +721,40 @@ def dbg_dp_run_resident(ctx, idx, dpopt, queries, tasks, made_up=None):
     return rst, cig, dict(zip(ROUND2_REC, (int(x) for x in rec)))
 
 
+# mpa_dbg_chain_extract (include/mpamd_dbg.h): modes, the columns of a path record, path classes and the reasons for the full list
+CHAIN_DENSE, CHAIN_SPARSE_SET, CHAIN_SPARSE_CHAINS = 0, 1, 2
+CHAIN_REC = ("m", "n_total", "non_roots", "max_f", "path", "c0", "big_bucket", "why")
+CHAIN_FULL_LIST, CHAIN_ONE_LEVEL, CHAIN_TWO_LEVEL, CHAIN_DECLINED = 0, 1, 2, 3
+CHAIN_WHY_MIN_CNT, CHAIN_WHY_MIN_SC, CHAIN_WHY_SMALL, CHAIN_WHY_MAX_F, CHAIN_WHY_OTHER = 1, 2, 4, 8, 16
+
+
+def dbg_chain_extract(ctx, args, probs, mode):
+    """mpa_dbg_chain_extract(): the chain extraction on raw anchors.  args: the eleven parameters of mp_chain (max_dist_x, max_dist_y, bw,
+    max_skip, max_iter, min_cnt, min_sc, coef_log, is_spliced, kmer, bbit); probs: a list of sorted uint64 anchor arrays, the problems of
+    ONE launch; mode: CHAIN_DENSE / CHAIN_SPARSE_SET / CHAIN_SPARSE_CHAINS.  On a context the forward pass and k_chain_extract run on the
+    device, through the chaining routes' own carving and launch; ctx None: chain_extract_core with a team of one in work space of the
+    kernel's sizes.  Returns (u, a, status, rec): per problem the chains (score << 32 | anchors) and their anchors as lists of arrays,
+    status int32 [n_prob] (1: declined), rec int64 [n_prob, 8] with the columns CHAIN_REC."""
+    n_prob = len(probs)
+    first = np.zeros(n_prob + 1, np.int64)
+    np.cumsum([len(p) for p in probs], out=first[1:])
+    a = np.ascontiguousarray(np.concatenate(list(probs) + [np.zeros(0, np.uint64)]), dtype=np.uint64)
+    n = len(a)
+    off_u, off_a = np.zeros(n_prob + 1, np.int64), np.zeros(n_prob + 1, np.int64)
+    u, ao = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+    status, rec = np.zeros(n_prob + 1, np.int32), np.zeros((n_prob + 1, len(CHAIN_REC)), np.int64)
+    f = dbg_lib().mpa_dbg_chain_extract
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p] + [C.c_int32] * 7 + [C.c_float] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 6
+    rc = f(ctx.h if ctx else None, *args, n_prob, first.ctypes.data, a.ctypes.data, int(mode), off_u.ctypes.data, u.ctypes.data, off_a.ctypes.data, ao.ctypes.data,
+           status.ctypes.data, rec.ctypes.data)
+    if rc != 0:
+        raise MpaError("mpa_dbg_chain_extract: %d: %s" % (rc, last_error()))
+    us = [u[off_u[q]:off_u[q + 1]].copy() for q in range(n_prob)]
+    as_ = [ao[off_a[q]:off_a[q + 1]].copy() for q in range(n_prob)]
+    return us, as_, status[:n_prob].copy(), rec[:n_prob].copy()
+
+
 def map_batches(ctx, idx, mo, batches, n_threads=1, keep_results=False, want_text=True, claim=None):
     """mpa_map_batches(): a stream of Queries batches through the pipelined mapper.  Returns the list of output texts
     (bytes, one per batch; the hit-id counter runs across the batches as in one output file); with keep_results the pair

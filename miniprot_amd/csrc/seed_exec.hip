@@ -222,11 +222,18 @@ __global__ __launch_bounds__(256) void k_chain_fwd(const uint64_t *a, int64_t n,
 // chain scores in; it is therefore not re-derived here but COMPILED from the host's own source (chain_core.h:
 // chain_extract_core), which tests/test_host_core.py pins to the oracle.  A problem is the pre-chain of a query (sparse view
 // of the anchors that k_prechain_fwd linked, set_only: the survivors as an ascending set), its main chain (dense view over
-// those survivors: chains laid out and sorted by first target position) or a refinement chain.  The code runs on lane 0 of the
-// wave (it is serial and latency-bound; what the device buys is that 4 000 problems run side by side and that no anchor has
-// to travel to the host and back between the two chaining rounds).  Layout: the view of problem q sits at first[q] in every
-// view / scratch / output array; status[q] = 1 when the problem needs the full list of chain ends and has no room for it
-// (tiny or degenerate problems: the host takes the query over).
+// those survivors: chains laid out and sorted by first target position), the main chain of the direct route (sparse view,
+// chains) or a refinement chain.  All 64 lanes run the code as the team CoopWave (dev_common.h) of chain_core.h: the parts that
+// are sequential by nature -- the cycle-leader walks of the sort replay, a chain's walk back -- are executed by every lane alike
+// on identical state, and everything else is shared out.  Fills, counts, scatters and compactions are strided over the lanes
+// (ballots give the ranks); the sort replay places 64 displaced chain ends per round side by side as long as their displacements
+// do not carry on (place_in_order), steps over 64 slots that are in place at once (walk_buckets), merges the moved and the low
+// list by binary search per element, and walks a level-1 bucket of up to EXTRACT_STAGE_WORDS ends in LDS (team_digit_level0); the
+// greedy extraction takes 64 chain ends at a time, one per lane, and only lanes whose ends sit in one predecessor tree (roots by
+// pointer jumping) take turns, the lowest lane first (atomic_min on owner[root]).  The digit tables (hist) live in LDS as well.
+// tests/test_chain_extract_gpu.py drives each of these branches on synthetic anchors (mpa_dbg_chain_extract).
+// Layout: the view of problem q sits at first[q] in every view / scratch / output array; status[q] = 1 when the problem needs
+// the full list of chain ends and has no room for it (n_total > m + 64: tiny or degenerate problems, the host takes the query over).
 // ------------------------------------------------------------------------------------------------
 struct ExtractArgs {
 	const int64_t *first;            // [n_prob + 1] offset of every problem's view

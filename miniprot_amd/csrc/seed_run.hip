@@ -801,4 +801,67 @@ int dev_chain_forward(mpa_ctx_t *ctx, const ChainParams &cp, int32_t n_prob, con
 	HIP_TRY(wait_stream(ctx, s));                       // (first[] may be pageable memory of the caller: it is consumed by now)
 	return MPA_OK;
 }
+
+// Test hook (mpa_dbg_chain_extract, chain_dbg.cpp): k_chain_extract over views the caller has made on the host -- vfirst[n_prob + 1] their
+// offsets; sparse views with v_pos and ntot_first, dense ones with both null -- through what every chaining route goes through: the
+// carving of the scratch in the context's chaining pool (which keeps whatever the last call left in it), the status memset, and
+// chain_extract_launch (set_only: the kept anchors as a set) or chain_extract_pack (the chains, packed by k_offsets2 + k_chain_pack).
+// u / a_out: room for vfirst[n_prob] words; off_u / off_a [n_prob + 1]; status[n_prob].
+int dev_chain_extract_dbg(mpa_ctx_t *ctx, const ChainParams &p, int32_t n_prob, const int64_t *vfirst, const int64_t *ntot_first, const int32_t *v_pos, const int32_t *v_f,
+                          const int32_t *v_pred, const uint64_t *v_a, int32_t set_only, int64_t *off_u, uint64_t *u, int64_t *off_a, uint64_t *a_out, int32_t *status)
+{
+	for (int32_t q = 0; q <= n_prob; ++q) off_u[q] = off_a[q] = 0;
+	for (int32_t q = 0; q < n_prob; ++q) status[q] = 0;
+	const int64_t m = vfirst[n_prob];
+	if (n_prob == 0 || m == 0) return MPA_OK;                  // (no view, no launch: as in every route)
+	HIP_TRY(hipSetDevice(ctx->device));
+	SeedBufs &B = ctx->seed;
+	ensure_seed_stream(ctx);
+	hipStream_t s = ctx->seed_stream;
+	const size_t M = (size_t)m, NP = (size_t)n_prob;
+	Carve carve;
+	const size_t o_first = carve((NP + 1) * 8), o_ntot = carve((NP + 1) * 8), o_vpos = carve(M * 4), o_vf = carve(M * 4), o_vpred = carve(M * 4), o_va = carve(M * 8);
+	ExtractCarve xc = carve_extract_scratch(carve, M, NP);
+	xc.out_a = carve(M * 8), xc.out_u = carve(M * 8);
+	carve_extract_counts(carve, NP, xc);
+	int rc;
+	if ((rc = B.x_all.ensure(carve.at))) return rc;
+	char *X = B.x_all.as<char>();
+	HIP_TRY(hipMemsetAsync(X + xc.status, 0, NP * 4 + 16, s));
+	HIP_TRY(hipMemcpyAsync(X + o_first, vfirst, (NP + 1) * 8, hipMemcpyHostToDevice, s));
+	if (ntot_first) HIP_TRY(hipMemcpyAsync(X + o_ntot, ntot_first, (NP + 1) * 8, hipMemcpyHostToDevice, s));
+	if (v_pos) HIP_TRY(hipMemcpyAsync(X + o_vpos, v_pos, M * 4, hipMemcpyHostToDevice, s));
+	HIP_TRY(hipMemcpyAsync(X + o_vf, v_f, M * 4, hipMemcpyHostToDevice, s));
+	HIP_TRY(hipMemcpyAsync(X + o_vpred, v_pred, M * 4, hipMemcpyHostToDevice, s));
+	HIP_TRY(hipMemcpyAsync(X + o_va, v_a, M * 8, hipMemcpyHostToDevice, s));
+	const ChainViewDev view{ (const int64_t*)(X + o_first), nullptr, ntot_first ? (const int64_t*)(X + o_ntot) : nullptr, v_pos ? (const int32_t*)(X + o_vpos) : nullptr,
+	                         (const int32_t*)(X + o_vf), (const int32_t*)(X + o_vpred), (const uint64_t*)(X + o_va) };
+	if (set_only) {
+		if ((rc = chain_extract_launch(ctx, s, X, xc, view, p, n_prob, 1, nullptr))) return rc;
+		std::vector<int64_t> na(NP);
+		std::vector<int32_t> st(NP);
+		std::vector<uint64_t> all(M);
+		HIP_TRY(hipMemcpyAsync(na.data(), X + xc.na, NP * 8, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(st.data(), X + xc.status, NP * 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(all.data(), X + xc.out_a, M * 8, hipMemcpyDeviceToHost, s));
+		HIP_TRY(wait_stream(ctx, s));
+		for (size_t q = 0; q < NP; ++q) {
+			const int64_t room = vfirst[q + 1] - vfirst[q];
+			if (na[q] < 0 || na[q] > room) { set_error("dev_chain_extract_dbg: a problem reports more anchors than its view holds"); return MPA_ERR_HIP; }
+			if (na[q] > 0) memcpy(a_out + off_a[q], all.data() + vfirst[q], (size_t)na[q] * 8);
+			off_a[q + 1] = off_a[q] + na[q], status[q] = st[q];
+		}
+		return MPA_OK;
+	}
+	std::vector<int64_t> a_first, u_first;
+	const uint64_t *A = nullptr, *U = nullptr;
+	const int32_t *h_status = nullptr;
+	if ((rc = chain_extract_pack(ctx, s, X, xc, view, p, n_prob, B.own, nullptr, nullptr, ChainTailOut{ a_first, u_first, A, U }, &h_status))) return rc;
+	if (a_first[NP] < 0 || a_first[NP] > m || u_first[NP] < 0 || u_first[NP] > m) { set_error("dev_chain_extract_dbg: more chains than the views hold anchors"); return MPA_ERR_HIP; }
+	for (size_t q = 0; q <= NP; ++q) off_a[q] = a_first[q], off_u[q] = u_first[q];
+	for (size_t q = 0; q < NP; ++q) status[q] = h_status[q];
+	if (a_first[NP] > 0) memcpy(a_out, A, (size_t)a_first[NP] * 8);
+	if (u_first[NP] > 0) memcpy(u, U, (size_t)u_first[NP] * 8);
+	return MPA_OK;
+}
 } // namespace mpa

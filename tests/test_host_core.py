@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import miniprot_amd as mpa
 import refbind
+from chaincases import _anchors, _long_chains   # (the generators live with the other chaining cases)
 
 CHAIN_ARGS = [C.c_int32] * 7 + [C.c_float] + [C.c_int32] * 3 + [C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
 
@@ -17,35 +18,6 @@ def _chain(fn, a, args):
     no = C.c_int64(0)
     nu = fn(*args, len(a), a.ctypes.data, u.ctypes.data, C.byref(no))
     return u[:nu].copy(), a[:no.value].copy()
-
-
-def _anchors(rng, n, n_block, qlen, n_planted):
-    """random background + planted collinear runs + duplicated fragments (equal scores on purpose)"""
-    blk = rng.integers(0, n_block, n)
-    q = rng.integers(5, qlen, n)
-    xs, ys = [blk], [q]
-    for _ in range(n_planted):
-        b0, q0, m = int(rng.integers(0, n_block)), int(rng.integers(5, qlen // 2)), int(rng.integers(2, 12))
-        dq = np.cumsum(rng.integers(1, 9, m))
-        for rep in range(int(rng.integers(1, 4))):           # the same fragment again a few blocks away / shifted by one residue
-            xs.append(b0 + (dq * 3) // 256 + rep * int(rng.integers(0, 3)))
-            ys.append(q0 + dq + (rep if rng.random() < 0.5 else 0))
-    a = (np.concatenate(xs).astype(np.uint64) << np.uint64(32)) | (np.concatenate(ys).astype(np.uint64) & np.uint64(0x7fffffff))
-    return np.unique(a)
-
-
-def _long_chains(rng, n_block, n_copies, where):
-    """the same long collinear fragment (chain score well above 255) planted several times: equal high scores, placed at
-    the start / end / anywhere of the block range so that they fall inside and behind the first bucket's region"""
-    m = int(rng.choice([50, 90, 160]))
-    dq = np.cumsum(rng.integers(1, 4, m))
-    out = []
-    for c in range(n_copies):
-        b0 = {"start": 3 + 40 * c, "end": n_block - 400 + 40 * c, "any": int(rng.integers(0, n_block - 100))}[where]
-        jitter = 0 if rng.random() < 0.6 else int(rng.integers(0, 2))
-        x = (b0 + (dq * 3) // 256).astype(np.uint64)
-        out.append((x << np.uint64(32)) | (10 + jitter + dq).astype(np.uint64))
-    return np.concatenate(out)
 
 
 def test_chain_anchors_matches_oracle(oracle_built):

@@ -244,7 +244,7 @@ def test_device_chain_forward_equals_host_forward(serial_run, monkeypatch):
     # serial_run: runs longer than this are walked by a wavefront (k_chain_fwd_wave: 64 candidates at a time, the max_skip counter
     # replayed over ballots) instead of one thread; 4 sends almost every run there
     monkeypatch.setenv("MPA_CHAIN_SERIAL_RUN", serial_run)
-    from test_host_core import _anchors, _long_chains
+    from chaincases import _anchors, _long_chains
     L = mpa.lib()
     L.mpa_dbg_chain_forward.argtypes = [C.c_void_p] + [C.c_int32] * 5 + [C.c_float] + [C.c_int32] * 4 + [C.c_void_p] * 4
     rng = np.random.default_rng(17)

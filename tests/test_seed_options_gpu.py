@@ -159,7 +159,7 @@ def test_device_chain_forward_equals_host_forward_off_defaults(serial_run, monke
     coefficient and the query-side reach drawn away from the defaults: (kcur - kprev) << bbit, max_dist_x >> bbit and the block
     bonus at bbit 4, 6, 10, 12; kmer 4, 5, 7; coef_log 0.2, 0.75, 2.0; max_dist_y 200, 1000"""
     monkeypatch.setenv("MPA_CHAIN_SERIAL_RUN", serial_run)
-    from test_host_core import _anchors, _long_chains
+    from chaincases import _anchors, _long_chains
     L = mpa.lib()
     L.mpa_dbg_chain_forward.argtypes = [C.c_void_p] + [C.c_int32] * 5 + [C.c_float] + [C.c_int32] * 4 + [C.c_void_p] * 4
     rng = np.random.default_rng(23)
