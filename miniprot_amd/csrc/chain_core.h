@@ -44,6 +44,10 @@ struct ChainView {
 
 struct SparseItem { int64_t pos; Pair64 e; };        // an element that is not a root, and the slot it occupies
 struct SortRange { int64_t beg, end; int32_t shift, pad; };
+// the forward pass on the device (k_chain_fwd): a run of anchors longer than the serial limit gets a wavefront (k_chain_fwd_wave)
+// through a list of these; the limit every device chaining route uses (MPA_CHAIN_SERIAL_RUN overrides it for dev_chain_forward)
+struct LongRun { int64_t s, e, q0; };
+static const int32_t kChainSerialRun = 48;
 
 // Work space of chain_extract_core() for a view of m anchors (every array [m] unless noted).
 struct ExtractScratch {

@@ -4,15 +4,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "chain_core.h"
 
 namespace mpa {
 
 struct U32ToU64 { __host__ __device__ uint64_t operator()(uint32_t x) const { return (uint64_t)x; } };   // scan inputs of 32-bit counts as 64-bit sums
 
 // the chain forward pass (k_chain_fwd, k_chain_fwd_wave: seed_exec.hip) as its host entry takes it (chain_fwd_launch, dev_ctx.h): the
-// parameters, and an entry of the list of long runs
+// parameters (an entry of the list of long runs: LongRun, chain_core.h)
 struct PreParams { int32_t max_dist_x, max_dist_y, bw, max_skip, max_iter, kmer, bbit, is_spliced, max_dblock; float coef_log; };
-struct LongRun { int64_t s, e, q0; };
 
 // base of the strand-oriented contig at strand-local position x (ntseq.c:89-106 folded into addressing; the scans of refine_kernels.hip and index_kernels.hip)
 __device__ __forceinline__ uint32_t strand_base(const uint8_t *seq, int64_t off, int64_t len, int rev, int64_t x)

@@ -23,6 +23,7 @@
 #include "dp_plan.h"
 #include "stream_plan.h"
 #include "chain_core.h"
+#include "dev_layout.h"
 #include "dev_common.h"
 
 namespace mpa {
@@ -186,7 +187,7 @@ struct SpanBufs {
 	CtxPool sp_pool1{ reg, "sp_pool1" };      // the batch's round-1 CIGAR pool, kept across round 2 (which overwrites cigd)
 	CtxPool sp_in2{ reg, "sp_in2" }, sp_asm{ reg, "sp_asm" }, sp_cig{ reg, "sp_cig" };   // round-2 results | slot offsets (| a caller's round-2 pool); per-plan records; the assembled CIGARs
 	HostPinned h_sp_up, h_sp_down, h_sp_up2, h_sp_down2;
-	struct SpansKeep { size_t off_plan = 0, off_seg = 0, off_rst1 = 0; int64_t n_plan = -1, n_pool1 = 0; } sp_keep;   // what dev_spans_round1 left for dev_spans_assemble
+	struct SpansKeep { Piece<SpansPlan> plan; Piece<SegRec> seg; Piece<mpa_dp_rst_t> rst1; Piece<SpanRec> rec; int64_t n_plan = -1, n_pool1 = 0; } sp_keep;   // what dev_spans_round1 left for dev_spans_assemble
 };
 
 // the device planner of a DP round (dp_exec.hip, MPA_GPU_DPPLAN=1): grow-only, allocated by the first call that asks for them
@@ -294,22 +295,15 @@ void pool_harvest(mpa_ctx_t *ctx, bool wait);                                   
 // ---- the chain tail (seed_run.hip): what the three device chaining routes -- behind the pre-chain (dev_chains_on_device), without one
 // (dev_seed_direct) and the refinement (dev_refine_chains) -- do alike, and the forward pass dev_chain_forward shares with them
 PreParams pre_params(const ChainParams &cp);              // mp_chain's parameters as the forward-pass kernels take them
-// one allocation (x_all), carved up: every piece starts on a 256-byte boundary
-struct Carve {
-	size_t at = 0;
-	size_t operator()(size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; }
-};
+// One allocation (x_all) per call, cut into typed pieces by a Carve (carve.h) of 256-byte alignment.  What one extraction works
+// in and leaves is an ExtractCarve (dev_layout.h: carve_extract_scratch for mark .. status, carve_extract_counts for the counts and
+// their prefixes; out_a / out_u are pieces the route places, the deliberate aliases of the pre-chain's dead view included), the
+// forward pass's arrays a ChainFwdCarve (carve_chain_fwd, carve_chain_runs); a kernel gets piece.in(X).
 // k_seed_fill -> k_chain_fwd -> k_chain_fwd_wave on stream s over the n anchors `a` of n_prob problems (first / cnt as k_chain_fwd
 // takes them).  Runs longer than serial_run get a wavefront each, through the list `runs` (long_cap entries) and its counter n_runs,
 // which the caller has zeroed on s; flag is only initialised.
-struct ChainFwdBufs { int32_t *f, *pred, *mark; uint32_t *flag; LongRun *runs; unsigned int *n_runs; size_t long_cap; };
 int chain_fwd_launch(hipStream_t s, const uint64_t *a, int64_t n, const int64_t *first, const int64_t *cnt, int32_t n_prob, const PreParams &pp, int32_t serial_run,
                      const ChainFwdBufs &b);
-// Offsets into x_all of what one extraction works in and leaves: scratch indexed like the views (m entries; `ends` and `stack` have
-// extras per problem), the per-problem status, the chains (out_a, out_u: m words each), their counts and the counts' prefixes.
-struct ExtractCarve { size_t mark, order, ends, tail8, items, moved, merged, kept, stack, status, out_a, out_u, na, nu, offa, offu; };
-ExtractCarve carve_extract_scratch(Carve &carve, size_t m, size_t n_prob);                // mark .. status; the caller zeroes status
-void carve_extract_counts(Carve &carve, size_t n_prob, ExtractCarve &c);                  // na, nu, offa, offu
 // the views of all problems on the device (ExtractArgs, seed_exec.hip): sparse (v_pos, ntot_first) or dense (both null)
 struct ChainViewDev { const int64_t *first, *cnt, *ntot_first; const int32_t *v_pos, *v_f, *v_pred; const uint64_t *v_a; };
 // k_chain_extract for n_prob problems on stream s, X = x_all.  prof_label != nullptr: with MPA_TIMING=2 the launch is profiled per phase

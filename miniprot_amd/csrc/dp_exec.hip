@@ -304,17 +304,12 @@ static hipStream_t begin_side(DpRun &R, bool is_ext)
 }
 static void end_side(DpRun &R) { const int k = R.launches.back().side; (void)hipEventRecord(R.ctx->lev[2 * k + 1], R.side_stream(k)); }
 
-// a resident round's results pool (ctx->round.cigoff): off[n_glob] | call_off[n] | bsum[blocks] | head | rst[n] (header and records: one download)
-struct ResLayout {
-	size_t off, call_off, bsum, head, rst, end, n;
-	ResLayout(size_t n_, size_t n_glob) : n(n_)
-	{
-		auto up64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
-		off = 0, call_off = up64(8 * n_glob), bsum = call_off + up64(8 * n), head = bsum + up64(8 * ((size_t)dp_blocks((int64_t)n_glob, TeamWG::W) + 1));
-		rst = head + 64, end = rst + up64(sizeof(mpa_dp_rst_t) * n) + 64;
-	}
-	size_t down_bytes() const { return 64 + sizeof(mpa_dp_rst_t) * n; }
-};
+// a resident round's results pool (ctx->round.cigoff): ResLayout, dev_layout.h
+static ResLayout res_layout(size_t n, size_t n_glob) { return ResLayout(n, n_glob, (size_t)dp_blocks((int64_t)n_glob, TeamWG::W)); }
+// round.list: the calls of a traceback chunk, then its GlobWave[] in the next 64-byte section (dp_tb_chunks and the device planner put
+// them there); round.wlist: the calls the walk takes, then the walk's block counter
+static GlobWave *round_list_waves(mpa_ctx_t *ctx, size_t n_calls) { Carve c(64); c.take<int32_t>(n_calls); return Piece<GlobWave>{ c.at, 0 }.in(ctx->round.list.p); }
+static unsigned long long *round_wlist_blocks(mpa_ctx_t *ctx, size_t n_lite) { Carve c(64); c.take<int32_t>(n_lite); return Piece<unsigned long long>{ c.at, 1 }.in(ctx->round.wlist.p); }
 
 // ---- 2. pools and staging at the sizes the plan asks for
 static int dp_size_pools(DpRun &R)
@@ -334,8 +329,8 @@ static int dp_size_pools(DpRun &R)
 	if (R.rz) {
 		// the dense pool at the plan's bound, the sum of cig_cap (its size is not known before the wait); offsets | offsets by call | block
 		// sums | header | result records in one pool; the download block with room for header and records
-		const ResLayout L((size_t)R.plan.cnt.n, R.plan.glob_ids.size());
-		R.dn_res = (R.plan.dn.end + 63) & ~(size_t)63;
+		const ResLayout L = res_layout((size_t)R.plan.cnt.n, R.plan.glob_ids.size());
+		Carve dc(64); dc.take<char>(R.plan.dn.end), R.dn_res = dc.at;        // (behind the plan's own sections, in a 64-byte section of its own)
 		if ((rc = ctx->round.cigd.ensure((size_t)R.plan.cig_total * 4 + 16)) || (rc = ctx->round.cigoff.ensure(L.end)) || (rc = ctx->round.h_down.ensure(R.dn_res + L.down_bytes()))) return rc;
 	}
 	return MPA_OK;
@@ -372,8 +367,9 @@ static int dp_upload_and_prep(DpRun &R, const mpa_idx_t *mi, const mpa_dpopt_t *
 	if (!P.huge_ids.empty()) {
 		const size_t n_huge = P.huge_ids.size();
 		HIP_TRY(hipMemsetAsync(ctx->round.hkey.p, 0, (size_t)P.hkey_total * 8, s));
-		R.d_hw = (GlobWave*)((char*)ctx->round.hkey.p + (((size_t)P.hkey_total * 8 + 15) & ~(size_t)15));
-		R.d_hlist = (int32_t*)(R.d_hw + n_huge);
+		Carve kc(16), tail(1);                                             // hkey: the keys in a 16-byte section | waves | list, packed
+		kc.take<uint64_t>((size_t)P.hkey_total), tail.skip(kc.at);
+		R.d_hw = tail.take<GlobWave>(n_huge).in(ctx->round.hkey.p), R.d_hlist = tail.take<int32_t>(n_huge).in(ctx->round.hkey.p);
 		HIP_TRY(hipMemcpyAsync(R.d_hw, P.huge_waves.data(), sizeof(GlobWave) * n_huge, hipMemcpyHostToDevice, s));
 		HIP_TRY(hipMemcpyAsync(R.d_hlist, P.huge_ids.data(), 4 * n_huge, hipMemcpyHostToDevice, s));
 		HIP_TRY(wait_stream(ctx, s));                  // (pageable sources; the calls are rare)
@@ -583,7 +579,7 @@ static int dp_tb_chunks(DpRun &R)
 			R.add_chunk_times();                                           // (the previous chunk's sweep and walk)
 		}
 		int32_t *d_list = ctx->round.list.as<int32_t>();
-		GlobWave *d_gw = (GlobWave*)((char*)ctx->round.list.p + ((P.cnt.n * 4 + 63) & ~(size_t)63));
+		GlobWave *d_gw = round_list_waves(ctx, P.cnt.n);
 		if (!P.on_device) {
 			memcpy(hup + P.up.list, r.list.data(), r.n_list * 4);
 			memcpy(hup + P.up.gw, r.waves.data(), r.n_waves * sizeof(GlobWave));
@@ -640,7 +636,7 @@ static int dp_walk(DpRun &R)
 	WalkArgs wk;
 	wk.ga = R.ga, wk.ga.waves = nullptr, wk.list = ctx->round.wlist.as<int32_t>(), wk.n_list = (int32_t)P.n_lite;
 	wk.lite = ctx->round.lite.as<uint32_t>(), wk.ckpt = ctx->round.ckpt.as<uint32_t>(), wk.cig = ctx->round.cig.as<uint32_t>(), wk.n_cigar = ctx->round.ncig.as<int32_t>();
-	wk.n_blocks = (unsigned long long*)((char*)ctx->round.wlist.p + ((P.n_lite * 4 + 63) & ~(size_t)63));
+	wk.n_blocks = round_wlist_blocks(ctx, P.n_lite);
 	HIP_TRY(hipMemsetAsync(wk.n_blocks, 0, 8, s));
 	// (the list is sorted by class: one launch per class, with the LDS that class's block of direction words needs)
 	size_t at = 0;
@@ -669,14 +665,14 @@ static int dp_results_enqueue(DpRun &R)
 	DpPlan &P = R.plan;
 	hipStream_t s = R.s;
 	const size_t n = P.cnt.n, n_glob = P.glob_ids.size();
-	const ResLayout L(n, n_glob);
+	const ResLayout L = res_layout(n, n_glob);
 	static_assert(DPR_NHEAD * 8 <= 64, "the header has 64 bytes of the pool");
 	char *X = ctx->round.cigoff.as<char>();
 	DpResDev D;
 	D.n = (int64_t)n, D.n_glob = (int64_t)n_glob, D.tasks = ctx->round.tasks.as<DTask>(), D.gids = R.rz->d_gids;
 	D.eo = ctx->round.extout.as<ExtOut>(), D.sc = ctx->round.score.as<int32_t>(), D.nc = ctx->round.ncig.as<int32_t>();
-	D.off = (int64_t*)(X + L.off), D.call_off = (int64_t*)(X + L.call_off), D.bsum = (int64_t*)(X + L.bsum), D.head = (int64_t*)(X + L.head), D.rst = (mpa_dp_rst_t*)(X + L.rst);
-	HIP_TRY(hipMemsetAsync(D.head, 0, 64, s));
+	D.off = L.off.in(X), D.call_off = L.call_off.in(X), D.bsum = L.bsum.in(X), D.head = L.head.in(X), D.rst = L.rst.in(X);
+	HIP_TRY(hipMemsetAsync(D.head, 0, L.head.bytes(), s));
 	const dim3 wg(TeamWG::W), g_glob((unsigned)dp_blocks((int64_t)n_glob, TeamWG::W)), g_calls((unsigned)dp_blocks((int64_t)n, TeamWG::W));
 	if (n_glob) {
 		hipLaunchKernelGGL(k_dpr_sums, g_glob, wg, 0, s, D);
@@ -687,7 +683,7 @@ static int dp_results_enqueue(DpRun &R)
 	if (n_glob) hipLaunchKernelGGL(k_cigar_gather, dim3((unsigned)n_glob), dim3(64), 0, s, ctx->round.tasks.as<DTask>(), D.gids, D.off, (int32_t)n_glob,
 	                               ctx->round.ncig.as<int32_t>(), ctx->round.cig.as<uint32_t>(), ctx->round.cigd.as<uint32_t>());
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(R.hdn + R.dn_res, X + L.head, L.down_bytes(), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(R.hdn + R.dn_res, L.head.in(X), L.down_bytes(), hipMemcpyDeviceToHost, s));
 	R.rz->d_rst = D.rst, R.rz->rec.bytes_down += (int64_t)L.down_bytes();
 	return MPA_OK;
 }
@@ -715,7 +711,7 @@ static int dp_join_and_download(DpRun &R)
 	if (P.n_split) HIP_TRY(hipMemcpyAsync(hdn + P.dn.err, R.wa.err, 4, hipMemcpyDeviceToHost, s));
 	*(unsigned long long*)(hdn + P.dn.wb) = 0;
 	if (R.rz) R.rz->rec.bytes_down += (P.n_split ? 4 : 0) + (P.n_lite ? 8 : 0);
-	if (P.n_lite) HIP_TRY(hipMemcpyAsync(hdn + P.dn.wb, (char*)ctx->round.wlist.p + ((P.n_lite * 4 + 63) & ~(size_t)63), 8, hipMemcpyDeviceToHost, s));
+	if (P.n_lite) HIP_TRY(hipMemcpyAsync(hdn + P.dn.wb, round_wlist_blocks(ctx, P.n_lite), 8, hipMemcpyDeviceToHost, s));
 	R.mark("    dp: round enqueued");
 	HIP_TRY(wait_stream(ctx, s));
 	R.mark("    dp: round (wait)");
@@ -752,9 +748,10 @@ static int dp_assemble(DpRun &R, mpa_dp_rst_t *rst, uint32_t **cigar_pool, int64
 	uint32_t *pool = (uint32_t*)malloc((size_t)(pool_n > 0 ? pool_n : 1) * 4);
 	if (pool_n > 0) {
 		int rc;
-		if ((rc = ctx->round.cigd.ensure((size_t)pool_n * 4)) || (rc = ctx->round.cigoff.ensure(n_glob * 12 + 64)) || (rc = ctx->round.h_pool.ensure((size_t)pool_n * 4))) { free(pool); return rc; }
-		int64_t *d_off = ctx->round.cigoff.as<int64_t>();
-		int32_t *d_ids = (int32_t*)(d_off + n_glob);
+		Carve oc(1);                                                       // cigoff, packed: every call's offset into the dense pool | the calls
+		const auto c_off = oc.take<int64_t>(n_glob); const auto c_ids = oc.take<int32_t>(n_glob);
+		if ((rc = ctx->round.cigd.ensure((size_t)pool_n * 4)) || (rc = ctx->round.cigoff.ensure(oc.at + 64)) || (rc = ctx->round.h_pool.ensure((size_t)pool_n * 4))) { free(pool); return rc; }
+		int64_t *d_off = c_off.in(ctx->round.cigoff.p); int32_t *d_ids = c_ids.in(ctx->round.cigoff.p);
 		memcpy(R.hup + P.up.ids, P.glob_ids.data(), n_glob * 4);
 		HIP_TRY(hipMemcpyAsync(d_off, dense_off, n_glob * 8, hipMemcpyHostToDevice, s));
 		HIP_TRY(hipMemcpyAsync(d_ids, R.hup + P.up.ids, n_glob * 4, hipMemcpyHostToDevice, s));
@@ -831,30 +828,31 @@ static int dev_dp_plan_run(mpa_ctx_t *ctx, hipStream_t s, const int64_t *d_ctg_l
 	if (const char *why = dp_plan_device_declines(opt, kn, n)) { set_error(std::string("device DP plan: ") + why); return MPA_ERR_UNSUPPORTED; }
 	if (q->n_seq < 0 || n_ctg < 0) { set_error("device DP plan: no queries or contigs"); return MPA_ERR_UNSUPPORTED; }
 	const size_t N = (size_t)n, U = (size_t)dp_units_bound(n, kn.split_wide != 0), nb = (size_t)dp_blocks(n, TeamWG::W);
-	auto al256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
 	// what goes up, in one block (rz: the tasks are read where they are -- no task bytes are staged or uploaded)
-	const size_t up_raw = 0, up_qoff = up_raw + (rz ? 0 : al256(sizeof(mpa_dp_task_t) * N)), up_ctg = up_qoff + al256(8 * ((size_t)q->n_seq + 1));
-	const size_t up_end = up_ctg + (d_ctg_len ? 0 : al256(8 * (size_t)n_ctg));
+	Carve up;
+	const auto u_raw = up.take_if<mpa_dp_task_t>(!rz, N); const auto u_qoff = up.take<int64_t>((size_t)q->n_seq + 1), u_ctg = up.take_if<int64_t>(!d_ctg_len, (size_t)n_ctg);
+	const size_t up_end = up.at;
 	tl_alloc_failed = false;
 	auto declined_alloc = [](int rc) { if (tl_alloc_failed) { tl_alloc_failed = false; return (int)MPA_ERR_UNSUPPORTED; } return rc; };
 	int rc;
 	if ((rc = ctx->planner.h_dpp_up.ensure(up_end + 256))) return MPA_ERR_UNSUPPORTED;
 	char *hup = ctx->planner.h_dpp_up.as<char>();
-	if (!rz) memcpy(hup + up_raw, in, sizeof(mpa_dp_task_t) * N);
+	if (!rz) memcpy(u_raw.in(hup), in, u_raw.bytes());
 	int64_t max_nl = rz ? rz->in.max_nl : 0, max_al = rz ? rz->in.max_al : 0;
-	const int64_t prep_bound = rz ? rz->in.prep_bound : dp_plan_prep_bound((const mpa_dp_task_t*)(hup + up_raw), n, &max_nl, &max_al);
+	const int64_t prep_bound = rz ? rz->in.prep_bound : dp_plan_prep_bound(u_raw.in((const char*)hup), n, &max_nl, &max_al);
 	if (prep_bound < 0 || prep_bound > (int64_t)N << 21) { set_error("device DP plan: impossible bounds of the task list"); return MPA_ERR_UNSUPPORTED; }
 	if (!dp_unit_costs_fit(max_nl, max_al)) { set_error("device DP plan: unit costs that do not fit the sort key"); return MPA_ERR_UNSUPPORTED; }
-	memcpy(hup + up_qoff, q->q_off, 8 * ((size_t)q->n_seq + 1));
-	if (!d_ctg_len && n_ctg > 0) memcpy(hup + up_ctg, h_ctg_len, 8 * (size_t)n_ctg);
+	memcpy(u_qoff.in(hup), q->q_off, u_qoff.bytes());
+	if (!d_ctg_len && n_ctg > 0) memcpy(u_ctg.in(hup), h_ctg_len, u_ctg.bytes());
 	// scratch: the upload block, keys, block sums, units, header | sorted traceback calls (one download), the sorts' own
 	size_t tmp_calls = 0, tmp_units = 0;
 	HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp_calls, (uint64_t*)nullptr, (uint64_t*)nullptr, N, 0u, (unsigned)MPA_DPPLAN_KEY_BITS, s));
 	HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp_units, (uint64_t*)nullptr, (uint64_t*)nullptr, U, 0u, 64u, s));
 	Carve carve;
-	const size_t o_up = carve(up_end), o_key = carve(8 * N), o_skey = carve(8 * N), o_bsum = carve(sizeof(DpSums) * nb), o_ubuf = carve(sizeof(DpUnit) * U);
-	const size_t o_ukey = carve(8 * U), o_uskey = carve(8 * U), o_head = carve(sizeof(DpDevHead)), o_gids = carve(4 * N), o_tmp = carve(std::max(tmp_calls, tmp_units) + 16);
-	const size_t down_bytes = o_gids + 4 * N - o_head;
+	const auto x_up = carve.take<char>(up_end); const auto x_key = carve.take<uint64_t>(N), x_skey = carve.take<uint64_t>(N); const auto x_bsum = carve.take<DpSums>(nb); const auto x_ubuf = carve.take<DpUnit>(U);
+	const auto x_ukey = carve.take<uint64_t>(U), x_uskey = carve.take<uint64_t>(U); const auto x_head = carve.take<DpDevHead>(1); const auto x_gids = carve.take<int32_t>(N); const auto x_tmp = carve.take<char>(std::max(tmp_calls, tmp_units), 16);
+	const Piece<int32_t> h_gids{ x_gids.off - x_head.off, N };          // header | sorted traceback calls: one download, the header at 0
+	const size_t down_bytes = h_gids.end();
 	// the executor's pools at their bounds (size_buffers() asks for no more once the plan is known: nothing the planner wrote moves)
 	if ((rc = ctx->planner.dpp.ensure(carve.at)) || (rc = ctx->round.tasks.ensure(sizeof(DTask) * N)) || (rc = ctx->round.chunks.ensure(sizeof(PrepChunk) * ((size_t)prep_bound + 1))) ||
 	    (rc = ctx->round.waves.ensure(sizeof(ExtWave) * (N + 16))) || (rc = ctx->round.list.ensure(N * 4 + 128 + sizeof(GlobWave) * (N + 1))) ||
@@ -864,30 +862,31 @@ static int dev_dp_plan_run(mpa_ctx_t *ctx, hipStream_t s, const int64_t *d_ctg_l
 	char *X = ctx->planner.dpp.as<char>();
 	DpDevPlan D;
 	D.n = n, D.n_ubound = (int64_t)U, D.n_ctg = n_ctg, D.n_seq = q->n_seq, D.opt = dp_plan_opt(opt), D.kn = kn;
-	D.raw = rz ? rz->in.d_tasks : (const mpa_dp_task_t*)(X + o_up + up_raw), D.q_off = (const int64_t*)(X + o_up + up_qoff), D.ctg_len = d_ctg_len ? d_ctg_len : (const int64_t*)(X + o_up + up_ctg);
+	const char *dup = x_up.in(X);
+	D.raw = rz ? rz->in.d_tasks : u_raw.in(dup), D.q_off = u_qoff.in(dup), D.ctg_len = d_ctg_len ? d_ctg_len : u_ctg.in(dup);
 	D.tasks = ctx->round.tasks.as<DTask>(), D.chunks = ctx->round.chunks.as<PrepChunk>(), D.waves = ctx->round.waves.as<ExtWave>(), D.list = ctx->round.list.as<int32_t>();
-	D.gw = (GlobWave*)((char*)ctx->round.list.p + ((N * 4 + 63) & ~(size_t)63));                    // (where dp_tb_chunks puts a chunk's waves)
+	D.gw = round_list_waves(ctx, N);
 	D.units = ctx->round.units.as<DpUnit>(), D.wlist = ctx->round.wlist.as<int32_t>();
-	D.key = (uint64_t*)(X + o_key), D.skey = (uint64_t*)(X + o_skey), D.bsum = (DpSums*)(X + o_bsum), D.ubuf = (DpUnit*)(X + o_ubuf);
-	D.ukey = (uint64_t*)(X + o_ukey), D.uskey = (uint64_t*)(X + o_uskey), D.head = (DpDevHead*)(X + o_head), D.gids = (int32_t*)(X + o_gids);
-	HIP_TRY(hipMemcpyAsync(X + o_up, hup, up_end, hipMemcpyHostToDevice, s));
+	D.key = x_key.in(X), D.skey = x_skey.in(X), D.bsum = x_bsum.in(X), D.ubuf = x_ubuf.in(X);
+	D.ukey = x_ukey.in(X), D.uskey = x_uskey.in(X), D.head = x_head.in(X), D.gids = x_gids.in(X);
+	HIP_TRY(hipMemcpyAsync(x_up.in(X), hup, up_end, hipMemcpyHostToDevice, s));
 	HIP_TRY(hipMemsetAsync(D.head, 0, sizeof(DpDevHead), s));
 	const dim3 g_calls((unsigned)nb), g_units((unsigned)dp_blocks((int64_t)U, TeamWG::W)), wg(TeamWG::W);
 	hipLaunchKernelGGL(k_dpp_classify, g_calls, wg, 0, s, D);
-	HIP_TRY(rocprim::radix_sort_keys(X + o_tmp, tmp_calls, D.key, D.skey, N, 0u, (unsigned)MPA_DPPLAN_KEY_BITS, s));
+	HIP_TRY(rocprim::radix_sort_keys(x_tmp.in(X), tmp_calls, D.key, D.skey, N, 0u, (unsigned)MPA_DPPLAN_KEY_BITS, s));
 	hipLaunchKernelGGL(k_dpp_sums, g_calls, wg, 0, s, D);
 	hipLaunchKernelGGL(k_dpp_mid, dim3(1), wg, 0, s, D);
 	hipLaunchKernelGGL(k_dpp_layout, g_calls, wg, 0, s, D);
 	hipLaunchKernelGGL(k_dpp_units, g_units, wg, 0, s, D);
-	HIP_TRY(rocprim::radix_sort_keys(X + o_tmp, tmp_units, D.ukey, D.uskey, U, 0u, 64u, s));
+	HIP_TRY(rocprim::radix_sort_keys(x_tmp.in(X), tmp_units, D.ukey, D.uskey, U, 0u, 64u, s));
 	hipLaunchKernelGGL(k_dpp_units_out, g_units, wg, 0, s, D);
 	HIP_TRY(hipGetLastError());
 	char *hdn = ctx->planner.h_dpp_down.as<char>();
-	HIP_TRY(hipMemcpyAsync(hdn, X + o_head, down_bytes, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(hdn, x_head.in(X), down_bytes, hipMemcpyDeviceToHost, s));
 	HIP_TRY(wait_stream(ctx, s));
-	*head = (const DpDevHead*)hdn, *gids = (const int32_t*)(hdn + (o_gids - o_head));
+	*head = (const DpDevHead*)hdn, *gids = h_gids.in((const char*)hdn);
 	*bytes_up = up_end, *bytes_down = down_bytes;
-	if (rz) rz->d_gids = D.gids, rz->rec.task_bytes_up = (int64_t)(up_qoff - up_raw);
+	if (rz) rz->d_gids = D.gids, rz->rec.task_bytes_up = (int64_t)(u_qoff.off - u_raw.off);
 	return MPA_OK;
 }
 
@@ -1101,7 +1100,7 @@ int64_t dev_dp_plan_dbg(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int32_t n_ctg, c
 		DpTbChunk &r = P.chunks[0];
 		r.list.resize(r.n_list), r.waves.resize(r.n_waves);
 		HIP_TRY(down(r.list.data(), ctx->round.list.p, 4 * r.n_list));
-		HIP_TRY(down(r.waves.data(), (char*)ctx->round.list.p + (((size_t)H.n * 4 + 63) & ~(size_t)63), sizeof(GlobWave) * r.n_waves));
+		HIP_TRY(down(r.waves.data(), round_list_waves(ctx, (size_t)H.n), sizeof(GlobWave) * r.n_waves));
 		for (size_t k = 0; k < r.n_list; ++k) if (r.list[k] != P.glob_ids[k]) { set_error("device DP plan: the chunk's call list is not the sorted order"); return MPA_ERR_HIP; }
 	}
 	for (size_t k = 0; k < wl.size(); ++k) if (wl[k] != P.glob_ids[P.n_reg_glob + k]) { set_error("device DP plan: the walk list is not the sorted order"); return MPA_ERR_HIP; }

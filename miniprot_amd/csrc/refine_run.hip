@@ -79,18 +79,18 @@ int dev_refine_scan(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_aa_
 	if (n_chunk == 0) return MPA_OK;
 	const unsigned long long cap = (unsigned long long)(n_pos / 64 + (1 << 20));   // ~0.04 % of the positions hit on random sequence
 	const int64_t n_words = qw_first[n_query];
-	auto al64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
-	const size_t o_win = 0, o_chunk = al64((size_t)n_win * sizeof(RefineWindowDev)), o_qf = o_chunk + al64((size_t)n_chunk * sizeof(RefineChunk)),
-	             o_words = o_qf + al64(((size_t)n_query + 1) * 8), o_gd = o_words + al64((size_t)n_words * 4 + 16), o_lq = o_gd + al64((size_t)n_query * 8 + 8),
-	             up_bytes = o_lq + al64(n_long * 4 + 4);
+	Carve up(64);
+	const auto u_win = up.take<RefineWindowDev>((size_t)n_win); const auto u_chunk = up.take<RefineChunk>((size_t)n_chunk); const auto u_qf = up.take<int64_t>((size_t)n_query + 1);
+	const auto u_words = up.take<uint32_t>((size_t)n_words, 16); const auto u_gd = up.take<int64_t>((size_t)n_query + 1); const auto u_lq = up.take<int32_t>(n_long + 1);
+	const size_t up_bytes = up.at;
 	int rc;
 	if ((rc = B.h_meta.ensure(up_bytes + 64)) || (rc = B.r_win.ensure(up_bytes)) || (rc = B.r_hits.ensure((size_t)cap * 16)) || (rc = B.r_count.ensure(16)) ||
 	    (rc = B.h_back.ensure(64)) || (n_long && (rc = B.r_gmap.ensure((size_t)gp.n_slots * 8)))) return rc;
 	char *hm = B.h_meta.as<char>();
 	int64_t c_lds = 0;                                         // the chunks of the LDS launch come first, then those of the long queries' windows
 	{
-		RefineWindowDev *dw = (RefineWindowDev*)(hm + o_win);
-		RefineChunk *ch = (RefineChunk*)(hm + o_chunk);
+		RefineWindowDev *dw = u_win.in(hm);
+		RefineChunk *ch = u_chunk.in(hm);
 		int64_t c = 0;
 		for (int pass = 0; pass < 2; ++pass) {
 			for (int64_t k = 0; k < n_win; ++k) {
@@ -100,10 +100,10 @@ int dev_refine_scan(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_aa_
 			}
 			if (pass == 0) c_lds = c;
 		}
-		memcpy(hm + o_qf, qw_first, ((size_t)n_query + 1) * 8);
-		memcpy(hm + o_words, qwords, (size_t)n_words * 4);
-		memcpy(hm + o_gd, gp.desc.data(), (size_t)n_query * 8);
-		if (n_long) memcpy(hm + o_lq, gp.long_q.data(), n_long * 4);
+		memcpy(u_qf.in(hm), qw_first, u_qf.bytes());
+		memcpy(u_words.in(hm), qwords, u_words.bytes());
+		memcpy(u_gd.in(hm), gp.desc.data(), (size_t)n_query * 8);
+		if (n_long) memcpy(u_lq.in(hm), gp.long_q.data(), n_long * 4);
 	}
 	HIP_TRY(hipMemcpyAsync(B.r_win.p, hm, up_bytes, hipMemcpyHostToDevice, s));
 	HIP_TRY(hipMemsetAsync(B.r_count.p, 0, 16, s));
@@ -113,13 +113,12 @@ int dev_refine_scan(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_aa_
 	const size_t lds = ((size_t)4 << hs_log2) + REFINE_CHUNK + 2 * REFINE_HALO;
 	const char *dm = B.r_win.as<char>();
 	if (c_lds > 0)
-		hipLaunchKernelGGL(k_refine_scan, dim3((unsigned)c_lds), dim3(256), lds, s, dg, (const RefineWindowDev*)(dm + o_win), (const RefineChunk*)(dm + o_chunk),
-		                   (const int64_t*)(dm + o_qf), (const uint32_t*)(dm + o_words), rt, kmer, min_aa_len, hs_log2, B.r_hits.as<uint4>(), B.r_count.as<unsigned long long>(), cap);
+		hipLaunchKernelGGL(k_refine_scan, dim3((unsigned)c_lds), dim3(256), lds, s, dg, u_win.in(dm), u_chunk.in(dm), u_qf.in(dm), u_words.in(dm), rt, kmer, min_aa_len, hs_log2, B.r_hits.as<uint4>(), B.r_count.as<unsigned long long>(), cap);
 	if (n_chunk > c_lds) {
-		if ((rc = gmap_build(B, s, gp, (const int64_t*)(dm + o_qf), (const uint32_t*)(dm + o_words), (const int32_t*)(dm + o_lq), (const int64_t*)(dm + o_gd)))) return rc;
-		hipLaunchKernelGGL(k_refine_scan_gset, dim3((unsigned)(n_chunk - c_lds)), dim3(256), REFINE_CHUNK + 2 * REFINE_HALO, s, dg, (const RefineWindowDev*)(dm + o_win),
-		                   (const RefineChunk*)(dm + o_chunk) + c_lds, rt, kmer, min_aa_len, B.r_hits.as<uint4>(), B.r_count.as<unsigned long long>(), cap,
-		                   RefineGmap{ B.r_gmap.as<uint2>(), (const int64_t*)(dm + o_gd) });
+		if ((rc = gmap_build(B, s, gp, u_qf.in(dm), u_words.in(dm), u_lq.in(dm), u_gd.in(dm)))) return rc;
+		hipLaunchKernelGGL(k_refine_scan_gset, dim3((unsigned)(n_chunk - c_lds)), dim3(256), REFINE_CHUNK + 2 * REFINE_HALO, s, dg, u_win.in(dm),
+		                   u_chunk.in(dm) + c_lds, rt, kmer, min_aa_len, B.r_hits.as<uint4>(), B.r_count.as<unsigned long long>(), cap,
+		                   RefineGmap{ B.r_gmap.as<uint2>(), u_gd.in(dm) });
 		if (timing_on()) fprintf(stderr, "[mpa-timing]     refine scan: global-set launch (%zu queries, %lld chunks)\n", n_long, (long long)(n_chunk - c_lds));
 	}
 	HIP_TRY(hipGetLastError());
@@ -208,22 +207,22 @@ int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_a
 	if (n_chunk == 0) return MPA_OK;
 	const unsigned long long cap = (unsigned long long)(n_pos / 64 + (1 << 20));
 	const size_t n_group = G.gword.size(), n_qpos = G.qpos.size(), NW = (size_t)n_win, NQ = (size_t)n_query;
-	auto al64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
-	const size_t o_win = 0, o_chunk = al64(NW * sizeof(RefineWindowDev)), o_wg = o_chunk + al64((size_t)n_chunk * sizeof(RefineChunk)), o_qg = o_wg + al64((NW + 1) * 8),
-	             o_gw = o_qg + al64((NQ + 1) * 8), o_gf = o_gw + al64(n_group * 4 + 4), o_gc = o_gf + al64(n_group * 4 + 4), o_qp = o_gc + al64(n_group * 4 + 4),
-	             o_gd = o_qp + al64(n_qpos * 4 + 4), o_lq = o_gd + al64(NQ * 8 + 8), o_pw = o_lq + al64(n_long * 4 + 4);
 	const int64_t text0 = plans ? plans->q_off[0] : 0, text_bytes = plans ? plans->q_off[n_query] - text0 : 0;
-	const size_t o_w0 = o_pw + (plans ? al64(NW * sizeof(PlansWindow)) : 0), o_qo = o_w0 + (plans ? al64((NQ + 1) * 8) : 0), o_tab = o_qo + (plans ? al64((NQ + 1) * 8) : 0),
-	             o_txt = o_tab + (plans ? al64(ALN_TAB_BYTES) : 0), up_bytes = o_txt + (plans ? al64((size_t)text_bytes + 16) : 0);
+	Carve up(64);
+	const auto u_win = up.take<RefineWindowDev>(NW); const auto u_chunk = up.take<RefineChunk>((size_t)n_chunk); const auto u_wg = up.take<int64_t>(NW + 1), u_qg = up.take<int64_t>(NQ + 1);
+	const auto u_gw = up.take<uint32_t>(n_group + 1), u_gf = up.take<uint32_t>(n_group + 1), u_gc = up.take<uint32_t>(n_group + 1), u_qp = up.take<uint32_t>(n_qpos + 1);
+	const auto u_gd = up.take<int64_t>(NQ + 1); const auto u_lq = up.take<int32_t>(n_long + 1); const auto u_pw = up.take_if<PlansWindow>(plans, NW);
+	const auto u_w0 = up.take_if<int64_t>(plans, NQ + 1), u_qo = up.take_if<int64_t>(plans, NQ + 1); const auto u_tab = up.take_if<uint8_t>(plans, ALN_TAB_BYTES), u_txt = up.take_if<uint8_t>(plans, (size_t)text_bytes, 16);
+	const size_t up_bytes = up.at;
 	int rc;
 	int64_t cls_end[4] = { 0, 0, 0, 0 };                       // chunks of the windows whose query's map has 1 024 / 2 048 / 4 096 LDS slots, or lives in device memory, end here
 	if ((rc = B.h_meta.ensure(up_bytes + 64)) || (rc = B.r_win.ensure(up_bytes)) || (rc = B.r_hits.ensure((size_t)cap * 16)) || (rc = B.r_count.ensure(16)) ||
 	    (rc = B.h_back.ensure(256)) || (n_long && (rc = B.r_gmap.ensure((size_t)gp.n_slots * 8)))) return rc;
 	char *hm = B.h_meta.as<char>();
 	{
-		RefineWindowDev *dw = (RefineWindowDev*)(hm + o_win);
-		RefineChunk *ch = (RefineChunk*)(hm + o_chunk);
-		int64_t *wg = (int64_t*)(hm + o_wg);
+		RefineWindowDev *dw = u_win.in(hm);
+		RefineChunk *ch = u_chunk.in(hm);
+		int64_t *wg = u_wg.in(hm);
 		for (int64_t k = 0; k < n_win; ++k) {
 			dw[k] = RefineWindowDev{ wins[k].as, wins[k].qid, wins[k].vid, wins[k].len, 0 };
 			wg[k] = wg_total;
@@ -241,27 +240,26 @@ int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_a
 			}
 			cls_end[cls] = c;
 		}
-		memcpy(hm + o_qg, G.qg_first.data(), (NQ + 1) * 8);
-		if (n_group) memcpy(hm + o_gw, G.gword.data(), n_group * 4), memcpy(hm + o_gf, G.gfirst.data(), n_group * 4), memcpy(hm + o_gc, G.gcount.data(), n_group * 4);
-		if (n_qpos) memcpy(hm + o_qp, G.qpos.data(), n_qpos * 4);
-		memcpy(hm + o_gd, gp.desc.data(), NQ * 8);
-		if (n_long) memcpy(hm + o_lq, gp.long_q.data(), n_long * 4);
+		memcpy(u_qg.in(hm), G.qg_first.data(), u_qg.bytes());
+		if (n_group) memcpy(u_gw.in(hm), G.gword.data(), n_group * 4), memcpy(u_gf.in(hm), G.gfirst.data(), n_group * 4), memcpy(u_gc.in(hm), G.gcount.data(), n_group * 4);
+		if (n_qpos) memcpy(u_qp.in(hm), G.qpos.data(), n_qpos * 4);
+		memcpy(u_gd.in(hm), gp.desc.data(), NQ * 8);
+		if (n_long) memcpy(u_lq.in(hm), gp.long_q.data(), n_long * 4);
 		if (plans) {
-			memcpy(hm + o_pw, plans->win, NW * sizeof(PlansWindow));
-			memcpy(hm + o_w0, plans->win0, (NQ + 1) * 8);
-			int64_t *qo = (int64_t*)(hm + o_qo);
+			memcpy(u_pw.in(hm), plans->win, u_pw.bytes());
+			memcpy(u_w0.in(hm), plans->win0, u_w0.bytes());
+			int64_t *qo = u_qo.in(hm);
 			for (size_t q = 0; q <= NQ; ++q) qo[q] = plans->q_off[q] - text0;
-			char *tab = hm + o_tab;
+			uint8_t *tab = u_tab.in(hm);
 			memcpy(tab + ALN_TAB_CODON, tab_codon(), 64), memcpy(tab + ALN_TAB_AA20, tab_aa20(), 256), memcpy(tab + ALN_TAB_MAT, plans->mat, 484);
-			if (text_bytes > 0) memcpy(hm + o_txt, plans->text + text0, (size_t)text_bytes);
+			if (text_bytes > 0) memcpy(u_txt.in(hm), plans->text + text0, (size_t)text_bytes);
 		}
 	}
 	// device tables: per (window, group) hit counts and per-window pair counts, zeroed
-	size_t at = 0;
-	auto carve = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; };
-	const size_t o_wcnt = carve(((size_t)wg_total + 1) * 4), o_wpairs = carve((NW + 2) * 4), o_first = carve((NW + 2) * 8);
-	const size_t zero_bytes = at;
-	if ((rc = B.rx_all.ensure(at))) return rc;
+	Carve rc_tab;
+	const auto r_wcnt = rc_tab.take<uint32_t>((size_t)wg_total + 1), r_wpairs = rc_tab.take<uint32_t>(NW + 2); const auto r_first = rc_tab.take<int64_t>(NW + 2);
+	const size_t zero_bytes = rc_tab.at;
+	if ((rc = B.rx_all.ensure(zero_bytes))) return rc;
 	HIP_TRY(hipMemcpyAsync(B.r_win.p, hm, up_bytes, hipMemcpyHostToDevice, s));
 	HIP_TRY(hipMemsetAsync(B.r_count.p, 0, 16, s));
 	HIP_TRY(hipMemsetAsync(B.rx_all.p, 0, zero_bytes, s));
@@ -269,25 +267,24 @@ int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_a
 	for (int c = 0; c < 64; ++c) rt.t[c] = tab_codon()[c] >= 20 ? 0xff : tab_codon13()[c];
 	DevGenome dg{ mi->dev[ctx->device]->seq, mi->dev[ctx->device]->ctg_off, mi->dev[ctx->device]->ctg_len, nullptr, mi->l_seq };
 	const char *dm = B.r_win.as<char>();
-	RefineGroups gr{ (const int64_t*)(dm + o_qg), (const uint32_t*)(dm + o_gw), (const uint32_t*)(dm + o_gf), (const uint32_t*)(dm + o_gc), (const uint32_t*)(dm + o_qp) };
-	const int64_t *d_wg = (const int64_t*)(dm + o_wg);
+	RefineGroups gr{ u_qg.in(dm), u_gw.in(dm), u_gf.in(dm), u_gc.in(dm), u_qp.in(dm) };
+	const int64_t *d_wg = u_wg.in(dm);
 	char *R = B.rx_all.as<char>();
-	uint32_t *d_wcnt = (uint32_t*)(R + o_wcnt), *d_wpairs = (uint32_t*)(R + o_wpairs);
-	int64_t *d_first = (int64_t*)(R + o_first);
+	uint32_t *d_wcnt = r_wcnt.in(R), *d_wpairs = r_wpairs.in(R); int64_t *d_first = r_first.in(R);
 	HIP_TRY(ensure_dynamic_lds((const void*)k_refine_scan_map, ctx->device, 48 * 1024));
 	for (int cls = 0; cls < 3; ++cls) {
 		const int64_t c_first = cls ? cls_end[cls - 1] : 0, c_n = cls_end[cls] - c_first;
 		if (c_n == 0) continue;
 		const int hs = 10 + cls;
 		const size_t lds = ((size_t)8 << hs) + 2 * (REFINE_CHUNK + 2 * REFINE_HALO);   // k-mer map, bases, codons
-		hipLaunchKernelGGL(k_refine_scan_map, dim3((unsigned)c_n), dim3(256), lds, s, dg, (const RefineWindowDev*)(dm + o_win), (const RefineChunk*)(dm + o_chunk) + c_first, gr, d_wg, rt,
+		hipLaunchKernelGGL(k_refine_scan_map, dim3((unsigned)c_n), dim3(256), lds, s, dg, u_win.in(dm), u_chunk.in(dm) + c_first, gr, d_wg, rt,
 		                   kmer, min_aa_len, hs, B.r_hits.as<uint4>(), B.r_count.as<unsigned long long>(), cap, d_wcnt, (int32_t)n_super);
 	}
 	if (cls_end[3] > cls_end[2]) {                             // the long queries: their tables once per batch, then the scan that probes them (LDS: bases + codons)
-		if ((rc = gmap_build(B, s, gp, gr.qg_first, gr.gword, (const int32_t*)(dm + o_lq), (const int64_t*)(dm + o_gd)))) return rc;
-		hipLaunchKernelGGL(k_refine_scan_gmap, dim3((unsigned)(cls_end[3] - cls_end[2])), dim3(256), 2 * (REFINE_CHUNK + 2 * REFINE_HALO), s, dg, (const RefineWindowDev*)(dm + o_win),
-		                   (const RefineChunk*)(dm + o_chunk) + cls_end[2], gr, d_wg, rt, kmer, min_aa_len, B.r_hits.as<uint4>(), B.r_count.as<unsigned long long>(), cap, d_wcnt, (int32_t)n_super,
-		                   RefineGmap{ B.r_gmap.as<uint2>(), (const int64_t*)(dm + o_gd) });
+		if ((rc = gmap_build(B, s, gp, gr.qg_first, gr.gword, u_lq.in(dm), u_gd.in(dm)))) return rc;
+		hipLaunchKernelGGL(k_refine_scan_gmap, dim3((unsigned)(cls_end[3] - cls_end[2])), dim3(256), 2 * (REFINE_CHUNK + 2 * REFINE_HALO), s, dg, u_win.in(dm),
+		                   u_chunk.in(dm) + cls_end[2], gr, d_wg, rt, kmer, min_aa_len, B.r_hits.as<uint4>(), B.r_count.as<unsigned long long>(), cap, d_wcnt, (int32_t)n_super,
+		                   RefineGmap{ B.r_gmap.as<uint2>(), u_gd.in(dm) });
 		if (timing_on()) fprintf(stderr, "[mpa-timing]     refine: global-map class (%zu queries, %lld windows)\n", n_long, (long long)n_long_win);
 	}
 	HIP_TRY(hipGetLastError());
@@ -317,13 +314,15 @@ int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_a
 		HIP_TRY(rocprim::exclusive_scan(B.tmp.p, tb, in, d_po, (uint64_t)0, (size_t)n_hits, rocprim::plus<uint64_t>(), s));
 		HIP_TRY(rocprim::exclusive_scan(B.tmp.p, tb2, inw, (uint64_t*)d_first, (uint64_t)0, NW + 1, rocprim::plus<uint64_t>(), s));
 	}
-	int64_t *h_np = (int64_t*)(h_n + 1);
+	int64_t *h_np = B.h_back.as<int64_t>() + 1;               // (h_back: the hit count | the pair count)
 	HIP_TRY(hipMemcpyAsync(h_np, d_first + n_win, 8, hipMemcpyDeviceToHost, s));
 	HIP_TRY(wait_stream(ctx, s));
 	const int64_t np = *h_np;
 	if (np == 0) return MPA_OK;
-	if ((rc = B.rx_keys.ensure((size_t)np * 24 + 64))) return rc;
-	uint64_t *keys0 = B.rx_keys.as<uint64_t>(), *keys1 = keys0 + np, *d_a = keys1 + np;
+	Carve kc(1);                                             // rx_keys, packed: the pair keys (two buffers of the sort) | the pairs as anchors
+	const auto k_keys0 = kc.take<uint64_t>((size_t)np), k_keys1 = kc.take<uint64_t>((size_t)np), k_a = kc.take<uint64_t>((size_t)np);
+	if ((rc = B.rx_keys.ensure(kc.at + 64))) return rc;
+	uint64_t *keys0 = k_keys0.in(B.rx_keys.p), *keys1 = k_keys1.in(B.rx_keys.p), *d_a = k_a.in(B.rx_keys.p);
 	hipLaunchKernelGGL(k_refine_pair_emit, dim3(nbh), dim3(256), 0, s, B.r_hits.as<uint4>(), n_hits, (const uint32_t*)d_pc, (const uint64_t*)d_po, gr, keys0);
 	HIP_TRY(hipGetLastError());
 	{
@@ -339,23 +338,21 @@ int dev_refine_chains(mpa_ctx_t *ctx, mpa_idx_s *mi, int32_t kmer, int32_t min_a
 	const size_t M = (size_t)np;
 	Carve xcarve;
 	ExtractCarve xc = carve_extract_scratch(xcarve, M, NW);
-	const size_t x_f = xcarve(M * 4), x_pred = xcarve(M * 4), x_fm = xcarve(M * 4);
-	xc.out_a = xcarve(M * 8), xc.out_u = xcarve(M * 8);
+	ChainFwdCarve fw{};
+	fw.f = xcarve.take<int32_t>(M), fw.pred = xcarve.take<int32_t>(M), fw.mark = xcarve.take<int32_t>(M);
+	xc.out_a = xcarve.take<uint64_t>(M), xc.out_u = xcarve.take<uint64_t>(M);
 	carve_extract_counts(xcarve, NW, xc);
-	const int32_t kSerialRun = 48;
-	const size_t long_cap = M / (size_t)(kSerialRun + 1) + 16, x_long = xcarve(long_cap * sizeof(LongRun)), x_nlong = xcarve(64);
+	carve_chain_runs(xcarve, M, kChainSerialRun, fw);
 	if ((rc = B.x_all.ensure(xcarve.at))) return rc;
 	char *X = B.x_all.as<char>();
-	HIP_TRY(hipMemsetAsync(X + xc.status, 0, NW * 4 + 16, s));
-	HIP_TRY(hipMemsetAsync(X + x_nlong, 0, 64, s));
-	if ((rc = chain_fwd_launch(s, (const uint64_t*)d_a, np, (const int64_t*)d_first, nullptr, (int32_t)n_win, pm, kSerialRun,
-	                           ChainFwdBufs{ (int32_t*)(X + x_f), (int32_t*)(X + x_pred), (int32_t*)(X + x_fm), (uint32_t*)(X + xc.mark), (LongRun*)(X + x_long), (unsigned int*)(X + x_nlong), long_cap }))) return rc;
-	const ChainViewDev view{ d_first, nullptr, nullptr, nullptr, (const int32_t*)(X + x_f), (const int32_t*)(X + x_pred), (const uint64_t*)d_a };
+	HIP_TRY(hipMemsetAsync(xc.status.in(X), 0, xc.status.bytes() + 16, s));
+	HIP_TRY(hipMemsetAsync(fw.n_runs.in(X), 0, fw.n_runs.bytes(), s));
+	if ((rc = chain_fwd_launch(s, (const uint64_t*)d_a, np, (const int64_t*)d_first, nullptr, (int32_t)n_win, pm, kChainSerialRun, fw.in(X, xc)))) return rc;
+	const ChainViewDev view{ d_first, nullptr, nullptr, nullptr, fw.f.in(X), fw.pred.in(X), (const uint64_t*)d_a };
 	PlansTail ptail;
 	if (plans) {
 		const DeviceIndex *d = mi->dev[ctx->device];
-		ptail = PlansTail{ plans->p, n_query, (const PlansWindow*)(dm + o_pw), (const int64_t*)(dm + o_w0), (const int64_t*)(dm + o_qo), (const uint8_t*)(dm + o_txt),
-		                   (const uint8_t*)(dm + o_tab), (const uint8_t*)d->seq, (const int64_t*)d->ctg_off, (const int64_t*)d->ctg_len, false, nullptr, nullptr, nullptr, nullptr, nullptr };
+		ptail = PlansTail{ plans->p, n_query, u_pw.in(dm), u_w0.in(dm), u_qo.in(dm), u_txt.in(dm), u_tab.in(dm), (const uint8_t*)d->seq, (const int64_t*)d->ctg_off, (const int64_t*)d->ctg_len, false, nullptr, nullptr, nullptr, nullptr, nullptr };
 	}
 	if ((rc = chain_extract_pack(ctx, s, X, xc, view, cp, (int32_t)n_win, B.own, nullptr, "device refinement: a chain extraction needs the host",   // (dense views never do)
 	                             ChainTailOut{ out.a_first, out.u_first, out.A, out.U }, nullptr, nullptr, plans ? &ptail : nullptr))) return rc;

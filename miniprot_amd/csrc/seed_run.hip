@@ -33,21 +33,6 @@ int chain_fwd_launch(hipStream_t s, const uint64_t *a, int64_t n, const int64_t 
 	return MPA_OK;
 }
 
-ExtractCarve carve_extract_scratch(Carve &carve, size_t m, size_t n_prob)
-{
-	ExtractCarve c{};
-	c.mark = carve(m * 4), c.order = carve(m * 4), c.ends = carve((m + 64 * n_prob + 64) * sizeof(Pair64)), c.tail8 = carve(m * sizeof(Pair64));
-	// (the chain layout's scratch -- packed anchors, sorted u, first positions -- is only live after the sort replay and the
-	// extraction: k_chain_extract puts it into the problem's own `moved` and `merged` lists)
-	c.items = carve(m * sizeof(SparseItem)), c.moved = carve(m * sizeof(SparseItem)), c.merged = carve(m * sizeof(SparseItem));
-	c.kept = carve(m), c.stack = carve((m / 64 + 6 * n_prob + 16) * sizeof(SortRange)), c.status = carve(n_prob * 4 + 16);
-	return c;
-}
-void carve_extract_counts(Carve &carve, size_t n_prob, ExtractCarve &c)
-{
-	c.na = carve(n_prob * 8 + 8), c.nu = carve(n_prob * 8 + 8), c.offa = carve(n_prob * 8 + 16), c.offu = carve(n_prob * 8 + 16);
-}
-
 // MPA_TIMING=2 (debug): per-phase wall clock of the extraction kernel, averaged over the problems of the launch
 static bool extract_prof_on()
 {
@@ -115,11 +100,11 @@ int chain_extract_launch(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCa
 	ExtractArgs xa;
 	xa.first = v.first, xa.cnt = v.cnt, xa.ntot_first = v.ntot_first;
 	xa.v_pos = v.v_pos, xa.v_f = v.v_f, xa.v_pred = v.v_pred, xa.v_a = v.v_a;
-	xa.mark = (int32_t*)(X + c.mark), xa.order = (int32_t*)(X + c.order), xa.ends = (Pair64*)(X + c.ends), xa.tail8 = (Pair64*)(X + c.tail8);
-	xa.items = (SparseItem*)(X + c.items), xa.moved = (SparseItem*)(X + c.moved), xa.merged = (SparseItem*)(X + c.merged);
-	xa.kept = (uint8_t*)(X + c.kept), xa.stack = (SortRange*)(X + c.stack);
-	xa.a_out = (uint64_t*)(X + c.out_a), xa.u_out = (uint64_t*)(X + c.out_u), xa.n_a = (int64_t*)(X + c.na), xa.n_u = (int64_t*)(X + c.nu);
-	xa.status = (int32_t*)(X + c.status), xa.p = p, xa.set_only = set_only;
+	xa.mark = c.mark.in(X), xa.order = c.order.in(X), xa.ends = c.ends.in(X), xa.tail8 = c.tail8.in(X);
+	xa.items = c.items.in(X), xa.moved = c.moved.in(X), xa.merged = c.merged.in(X);
+	xa.kept = c.kept.in(X), xa.stack = c.stack.in(X);
+	xa.a_out = c.out_a.in(X), xa.u_out = c.out_u.in(X), xa.n_a = c.na.in(X), xa.n_u = c.nu.in(X);
+	xa.status = c.status.in(X), xa.p = p, xa.set_only = set_only;
 	const bool prof = prof_label && extract_prof_on();
 	long long *d_prof = nullptr;
 	int rc;
@@ -139,26 +124,23 @@ static int regions_tail(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCar
 	SeedBufs &B = ctx->seed;
 	const size_t T = (size_t)tot_u, NP = (size_t)n_prob;
 	const double t0 = now_ms();
-	Carve cv;
-	const size_t o_tmp = cv(T * sizeof(RegionRec)), o_out = cv(T * sizeof(RegionRec)), o_ext = cv(T * 8), o_cov = cv(T * 8), o_key = cv(T * sizeof(Pair64));
-	const size_t o_stack = cv((T / 64 + 5 * NP + 8) * sizeof(SortRange)), o_hist = cv(NP * 768 * 4), o_prim = cv(T * 4), o_ctl = cv(NP * 8), o_nreg = cv(NP * 4);
-	const size_t h_ext = T * sizeof(RegionRec), h_nreg = h_ext + T * 8;
-	if (B.rg.ensure(cv.at + 256) != MPA_OK || H.h_R.ensure(h_nreg + NP * 4 + 64) != MPA_OK) {
+	const RegionsLayout L(T, NP);
+	if (B.rg.ensure(L.dev_bytes) != MPA_OK || H.h_R.ensure(L.pinned_bytes) != MPA_OK) {
 		tl_alloc_failed = false;
 		if (timing_on()) fprintf(stderr, "[mpa-timing]   device regions declined (%s): chains to the host\n", mpa_last_error());
 		return MPA_ERR_UNSUPPORTED;
 	}
 	char *G = B.rg.as<char>(), *P = H.h_R.as<char>();
-	rt.R = (const RegionRec*)P, rt.E = (const uint64_t*)(P + h_ext), rt.n_reg = (const int32_t*)(P + h_nreg);
-	if (tot_u == 0) { memset(P + h_nreg, 0, NP * 4); rt.done = true; return MPA_OK; }
+	rt.R = L.h_rec.in(P), rt.E = L.h_ext.in(P), rt.n_reg = L.h_nreg.in(P);
+	if (tot_u == 0) { memset(L.h_nreg.in(P), 0, L.h_nreg.bytes()); rt.done = true; return MPA_OK; }
 	RegionsArgs ra;
-	ra.first = v.first, ra.a = (const uint64_t*)(X + c.out_a), ra.u = (const uint64_t*)(X + c.out_u), ra.nu = (const int64_t*)(X + c.nu), ra.offu = (const int64_t*)(X + c.offu);
+	ra.first = v.first, ra.a = c.out_a.in(X), ra.u = c.out_u.in(X), ra.nu = c.nu.in(X), ra.offu = c.offu.in(X);
 	ra.bo = rt.d_bo, ra.p = rt.p;
-	ra.tmp = (RegionRec*)(G + o_tmp), ra.out = (RegionRec*)(G + o_out), ra.ext = (uint64_t*)(G + o_ext), ra.cov = (uint64_t*)(G + o_cov), ra.key = (Pair64*)(G + o_key);
-	ra.stack = (SortRange*)(G + o_stack), ra.hist = (uint32_t*)(G + o_hist), ra.prim = (int32_t*)(G + o_prim), ra.ctl = (int32_t*)(G + o_ctl), ra.n_reg = (int32_t*)(G + o_nreg);
+	ra.tmp = L.tmp.in(G), ra.out = L.out.in(G), ra.ext = L.ext.in(G), ra.cov = L.cov.in(G), ra.key = L.key.in(G);
+	ra.stack = L.stack.in(G), ra.hist = L.hist.in(G), ra.prim = L.prim.in(G), ra.ctl = L.ctl.in(G), ra.n_reg = L.n_reg.in(G);
 	hipLaunchKernelGGL(k_regions, dim3((unsigned)((n_prob + REGIONS_WAVES - 1) / REGIONS_WAVES)), dim3(64 * REGIONS_WAVES), 0, s, ra, n_prob);
 	hipLaunchKernelGGL(k_region_pack, dim3((unsigned)n_prob), dim3(256), 0, s, ra.offu, (const int32_t*)ra.n_reg, (const RegionRec*)ra.out, (const uint64_t*)ra.ext,
-	                   (RegionRec*)P, (uint64_t*)(P + h_ext), (int32_t*)(P + h_nreg));
+	                   L.h_rec.in(P), L.h_ext.in(P), L.h_nreg.in(P));
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(wait_stream(ctx, s));
 	rt.done = true;
@@ -176,30 +158,25 @@ static int plans_tail(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCarve
 	SeedBufs &B = ctx->seed;
 	const size_t T = (size_t)tot_a, NW = (size_t)n_prob, NQ = (size_t)pt.n_query;
 	const double t0 = now_ms();
-	Carve cv;
-	const size_t o_tmp = cv(NW * sizeof(RegionRec)), o_key = cv(NW * sizeof(Pair64)), o_stack = cv((NW / 64 + 5 * NQ + 8) * sizeof(SortRange)), o_hist = cv(NQ * 768 * 4);
-	const size_t o_prim = cv(NW * 4), o_cov = cv(NW * 8), o_ext = cv(NW * 8), o_aoff = cv(NW * 8), o_flag = cv(T * 4 + 4), o_list = cv(T * 4 + 4), o_ctl = cv(NQ * 8);
-	const size_t o_reg = cv(NW * sizeof(RegionRec)), o_plan = cv(NW * sizeof(PlanRec)), o_task = cv((4 * NW + T) * sizeof(mpa_dp_task_t)), o_seg = cv(T * sizeof(SegRec) + 8);
-	const size_t o_cnt = cv(NQ * sizeof(PlansCounts));
-	const size_t h_plan = NW * sizeof(RegionRec), h_task = h_plan + NW * sizeof(PlanRec), h_seg = h_task + (4 * NW + T) * sizeof(mpa_dp_task_t), h_cnt = h_seg + T * sizeof(SegRec);
-	if (B.pl.ensure(cv.at + 256) != MPA_OK || H.h_P.ensure(h_cnt + NQ * sizeof(PlansCounts) + 64) != MPA_OK) {
+	const PlansLayout L(T, NW, NQ);
+	if (B.pl.ensure(L.dev_bytes) != MPA_OK || H.h_P.ensure(L.pinned_bytes) != MPA_OK) {
 		tl_alloc_failed = false;
 		if (timing_on()) fprintf(stderr, "[mpa-timing]   device plans declined (%s): chains to the host\n", mpa_last_error());
 		return MPA_ERR_UNSUPPORTED;
 	}
 	char *G = B.pl.as<char>(), *P = H.h_P.as<char>();
-	pt.R = (const RegionRec*)P, pt.P = (const PlanRec*)(P + h_plan), pt.T = (const mpa_dp_task_t*)(P + h_task), pt.S = (const SegRec*)(P + h_seg), pt.N = (const PlansCounts*)(P + h_cnt);
+	pt.R = L.h_reg.in(P), pt.P = L.h_plan.in(P), pt.T = L.h_task.in(P), pt.S = L.h_seg.in(P), pt.N = L.h_cnt.in(P);
 	PlansArgs pa{};
-	pa.first = v.first, pa.nu = (const int64_t*)(X + c.nu), pa.offa = (const int64_t*)(X + c.offa), pa.u = (const uint64_t*)(X + c.out_u), pa.a = (uint64_t*)(X + c.out_a);
+	pa.first = v.first, pa.nu = c.nu.in(X), pa.offa = c.offa.in(X), pa.u = c.out_u.in(X), pa.a = c.out_a.in(X);
 	pa.win = pt.d_win, pa.win0 = pt.d_win0, pa.q_off = pt.d_qoff, pa.text = pt.d_text, pa.tabs = pt.d_tabs;
 	pa.g = PlansGenome{ pt.d_seq, pt.d_ctg_off, pt.d_ctg_len }, pa.p = pt.p;
-	pa.tmp = (RegionRec*)(G + o_tmp), pa.key = (Pair64*)(G + o_key), pa.stack = (SortRange*)(G + o_stack), pa.hist = (uint32_t*)(G + o_hist), pa.prim = (int32_t*)(G + o_prim);
-	pa.flag = (int32_t*)(G + o_flag), pa.list = (int32_t*)(G + o_list), pa.ctl = (int32_t*)(G + o_ctl), pa.cov = (uint64_t*)(G + o_cov), pa.ext = (uint64_t*)(G + o_ext);
-	pa.aoff = (int64_t*)(G + o_aoff), pa.reg = (RegionRec*)(G + o_reg), pa.plan = (PlanRec*)(G + o_plan), pa.task = (mpa_dp_task_t*)(G + o_task), pa.seg = (SegRec*)(G + o_seg);
-	pa.cnt = (PlansCounts*)(G + o_cnt);
+	pa.tmp = L.tmp.in(G), pa.key = L.key.in(G), pa.stack = L.stack.in(G), pa.hist = L.hist.in(G), pa.prim = L.prim.in(G);
+	pa.flag = L.flag.in(G), pa.list = L.list.in(G), pa.ctl = L.ctl.in(G), pa.cov = L.cov.in(G), pa.ext = L.ext.in(G);
+	pa.aoff = L.aoff.in(G), pa.reg = L.reg.in(G), pa.plan = L.plan.in(G), pa.task = L.task.in(G), pa.seg = L.seg.in(G);
+	pa.cnt = L.cnt.in(G);
 	hipLaunchKernelGGL(k_plans, dim3((unsigned)((pt.n_query + PLANS_WAVES - 1) / PLANS_WAVES)), dim3(64 * PLANS_WAVES), 0, s, pa, pt.n_query);
 	hipLaunchKernelGGL(k_plan_pack, dim3((unsigned)pt.n_query), dim3(256), 0, s, pa.win0, pa.offa, (const PlansCounts*)pa.cnt, (const RegionRec*)pa.reg, (const PlanRec*)pa.plan,
-	                   (const mpa_dp_task_t*)pa.task, (const SegRec*)pa.seg, (RegionRec*)P, (PlanRec*)(P + h_plan), (mpa_dp_task_t*)(P + h_task), (SegRec*)(P + h_seg), (PlansCounts*)(P + h_cnt));
+	                   (const mpa_dp_task_t*)pa.task, (const SegRec*)pa.seg, L.h_reg.in(P), L.h_plan.in(P), L.h_task.in(P), L.h_seg.in(P), L.h_cnt.in(P));
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(wait_stream(ctx, s));
 	pt.done = true;
@@ -214,52 +191,44 @@ int chain_extract_pack(mpa_ctx_t *ctx, hipStream_t s, char *X, const ExtractCarv
 	const size_t NP = (size_t)n_prob;
 	int rc;
 	if ((rc = chain_extract_launch(ctx, s, X, c, v, p, n_prob, 0, prof_label))) return rc;
-	hipLaunchKernelGGL(k_offsets2, dim3(1), dim3(256), 0, s, (const int64_t*)(X + c.na), (const int64_t*)(X + c.nu), n_prob, (int64_t*)(X + c.offa), (int64_t*)(X + c.offu));
+	hipLaunchKernelGGL(k_offsets2, dim3(1), dim3(256), 0, s, c.na.in(X), c.nu.in(X), n_prob, c.offa.in(X), c.offu.in(X));
 	HIP_TRY(hipGetLastError());
-	// offsets + status down, then the chains themselves straight into pinned memory
-	const size_t offb = (NP + 1) * 8;
-	if ((rc = B.h_xoff.ensure(2 * offb + NP * 4 + 64))) return rc;
-	int64_t *h_offa = B.h_xoff.as<int64_t>(), *h_offu = h_offa + (NP + 1);
-	int32_t *h_status = (int32_t*)(h_offu + (NP + 1));
-	HIP_TRY(hipMemcpyAsync(h_offa, X + c.offa, offb, hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipMemcpyAsync(h_offu, X + c.offu, offb, hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipMemcpyAsync(h_status, X + c.status, NP * 4, hipMemcpyDeviceToHost, s));
+	// offsets + status down (one pinned block, packed: offa | offu | status), then the chains themselves straight into pinned memory
+	Carve hc(1);
+	const auto p_offa = hc.take<int64_t>(NP + 1), p_offu = hc.take<int64_t>(NP + 1); const auto p_status = hc.take<int32_t>(NP);
+	if ((rc = B.h_xoff.ensure(hc.at + 64))) return rc;
+	int64_t *h_offa = p_offa.in(B.h_xoff.p), *h_offu = p_offu.in(B.h_xoff.p); int32_t *h_status = p_status.in(B.h_xoff.p);
+	HIP_TRY(hipMemcpyAsync(h_offa, c.offa.in(X), p_offa.bytes(), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h_offu, c.offu.in(X), p_offu.bytes(), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h_status, c.status.in(X), p_status.bytes(), hipMemcpyDeviceToHost, s));
 	HIP_TRY(wait_stream(ctx, s));
 	if (status_error)
 		for (size_t w = 0; w < NP; ++w) if (h_status[w]) { set_error(status_error); return MPA_ERR_UNSUPPORTED; }
 	const int64_t tot_a = h_offa[n_prob], tot_u = h_offu[n_prob];
-	if (regions) {                                            // the regions instead of the chains; declined: the chains, as without it
+	bool chains = true;                                      // the regions or the plans instead of the chains; declined: the chains, as without them
+	if (regions) {
 		regions->done = false;
 		rc = regions_tail(ctx, s, X, c, v, n_prob, H, tot_u, *regions);
-		if (rc == MPA_OK) {
-			out.a_first.assign(h_offa, h_offa + n_prob + 1), out.u_first.assign(h_offu, h_offu + n_prob + 1);
-			out.A = out.U = nullptr;
-			if (h_status_out) *h_status_out = h_status;
-			return MPA_OK;
-		}
-		if (rc != MPA_ERR_UNSUPPORTED) return rc;
+		if (rc != MPA_OK && rc != MPA_ERR_UNSUPPORTED) return rc;
+		chains = rc != MPA_OK;
 	}
-	if (plans) {                                              // the plans instead of the chains; declined: the chains, as without it
+	if (plans && chains) {
 		plans->done = false;
 		rc = plans_tail(ctx, s, X, c, v, n_prob, H, tot_a, *plans);
-		if (rc == MPA_OK) {
-			out.a_first.assign(h_offa, h_offa + n_prob + 1), out.u_first.assign(h_offu, h_offu + n_prob + 1);
-			out.A = out.U = nullptr;
-			if (h_status_out) *h_status_out = h_status;
-			return MPA_OK;
-		}
-		if (rc != MPA_ERR_UNSUPPORTED) return rc;
+		if (rc != MPA_OK && rc != MPA_ERR_UNSUPPORTED) return rc;
+		chains = rc != MPA_OK;
 	}
-	if ((rc = H.h_A.ensure((size_t)tot_a * 8 + 64)) || (rc = H.h_U.ensure((size_t)tot_u * 8 + 64))) return rc;
-	if (tot_a > 0 || tot_u > 0) {
-		hipLaunchKernelGGL(k_chain_pack, dim3((unsigned)n_prob), dim3(256), 0, s, v.first, (const int64_t*)(X + c.na), (const int64_t*)(X + c.nu),
-		                   (const int64_t*)(X + c.offa), (const int64_t*)(X + c.offu), (const uint64_t*)(X + c.out_a), (const uint64_t*)(X + c.out_u),
-		                   H.h_A.as<uint64_t>(), H.h_U.as<uint64_t>());
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(wait_stream(ctx, s));
+	if (chains) {
+		if ((rc = H.h_A.ensure((size_t)tot_a * 8 + 64)) || (rc = H.h_U.ensure((size_t)tot_u * 8 + 64))) return rc;
+		if (tot_a > 0 || tot_u > 0) {
+			hipLaunchKernelGGL(k_chain_pack, dim3((unsigned)n_prob), dim3(256), 0, s, v.first, c.na.in(X), c.nu.in(X), c.offa.in(X), c.offu.in(X), c.out_a.in(X), c.out_u.in(X),
+			                   H.h_A.as<uint64_t>(), H.h_U.as<uint64_t>());
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(wait_stream(ctx, s));
+		}
 	}
 	out.a_first.assign(h_offa, h_offa + n_prob + 1), out.u_first.assign(h_offu, h_offu + n_prob + 1);
-	out.A = H.h_A.as<uint64_t>(), out.U = H.h_U.as<uint64_t>();
+	out.A = chains ? H.h_A.as<uint64_t>() : nullptr, out.U = chains ? H.h_U.as<uint64_t>() : nullptr;
 	if (h_status_out) *h_status_out = h_status;
 	return MPA_OK;
 }
@@ -361,49 +330,45 @@ static int dev_sift_front(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_block, int 
 	qseg[(size_t)n_query] = (int32_t)segs.size();
 	const int32_t n_seg = (int32_t)segs.size();
 	if (n_seg == 0) return MPA_OK;                             // (F.n_seg stays 0)
-	// one pinned block up: qfirst | jfirst | sfirst | segments | qseg
-	const size_t meta_q = ((size_t)n_query + 1) * 8, seg_bytes = (size_t)n_seg * sizeof(SiftSeg);
-	const size_t off_jf = meta_q, off_sf = 2 * meta_q, off_seg = 3 * meta_q, off_qs = off_seg + seg_bytes, meta_bytes = off_qs + ((size_t)n_query + 1) * 4;
+	// one pinned block up, packed: qfirst | jfirst | sfirst | segments | qseg; one down: qfirst2 | cfirst (room for one more prefix array) | flag
+	const size_t NQ1 = (size_t)n_query + 1;
+	Carve mc(1), bc(1), xc;
+	const auto m_qf = mc.take<int64_t>(NQ1), m_jf = mc.take<int64_t>(NQ1), m_sf = mc.take<int64_t>(NQ1); const auto m_seg = mc.take<SiftSeg>((size_t)n_seg); const auto m_qs = mc.take<int32_t>(NQ1);
+	const auto b_qfirst2 = bc.take<int64_t>(NQ1), b_cfirst = bc.take<int64_t>(NQ1); const auto b_flag = bc.take<int32_t>((size_t)n_query);
+	const size_t meta_q = m_qf.bytes(), meta_bytes = mc.at;
 	int rc;
 	// (round 6: the two staging arrays of the sift -- 8 B per staging slot each, dead once k_sift_copy has packed the kept anchors --
 	// live at the front of the chaining block, which is carved up only behind that copy: 4.4 GB less per seeder at genome scale)
-	const size_t stage_bytes = ((size_t)n_stage * 8 + 64 + 255) & ~(size_t)255;
+	const auto x_stage0 = xc.take<uint64_t>((size_t)n_stage, 64), x_stage1 = xc.take<uint64_t>((size_t)n_stage, 64);
 	if ((rc = B.h_meta.ensure(meta_bytes))) return rc;
 	char *hm = B.h_meta.as<char>();
-	memcpy(hm, qfirst, meta_q), memcpy(hm + off_jf, jfirst.data(), meta_q), memcpy(hm + off_sf, sfirst.data(), meta_q), memcpy(hm + off_seg, segs.data(), seg_bytes), memcpy(hm + off_qs, qseg.data(), ((size_t)n_query + 1) * 4);
+	memcpy(m_qf.in(hm), qfirst, meta_q), memcpy(m_jf.in(hm), jfirst.data(), meta_q), memcpy(m_sf.in(hm), sfirst.data(), meta_q), memcpy(m_seg.in(hm), segs.data(), m_seg.bytes()), memcpy(m_qs.in(hm), qseg.data(), m_qs.bytes());
 	if ((rc = B.s_meta.ensure(meta_bytes)) || (rc = B.s_cur.ensure((size_t)n_cur * 4 + 16)) || (rc = B.s_cur2.ensure((size_t)n_cur * 4 + 16)) ||
 	    (rc = B.s_kept.ensure((size_t)n_seg * 4)) || (rc = B.s_base.ensure((size_t)n_seg * 8)) || (rc = B.s_out.ensure(((size_t)n_seg + 1) * 8)) ||
 	    (rc = B.s_flag.ensure((size_t)n_query * 4 + 16)) || (rc = B.pf_qfirst2.ensure(meta_q)) || (rc = B.cfirst.ensure(meta_q)) ||
-	    (rc = B.x_all.ensure(2 * stage_bytes)) || (rc = B.h_back.ensure(2 * meta_q + (size_t)n_query * 4 + 64))) return rc;
-	uint64_t *const stage0 = B.x_all.as<uint64_t>(), *const stage1 = (uint64_t*)(B.x_all.as<char>() + stage_bytes);
+	    (rc = B.x_all.ensure(xc.at)) || (rc = B.h_back.ensure(bc.at + 64))) return rc;
+	uint64_t *const stage0 = x_stage0.in(B.x_all.p), *const stage1 = x_stage1.in(B.x_all.p);
 	HIP_TRY(hipMemcpyAsync(B.s_meta.p, hm, meta_bytes, hipMemcpyHostToDevice, s));
 	HIP_TRY(hipMemsetAsync(B.s_flag.p, 0, (size_t)n_query * 4 + 16, s));
 	const char *dm = B.s_meta.as<char>();
-	const int64_t *d_qfirst = (const int64_t*)dm, *d_jfirst = (const int64_t*)(dm + off_jf), *d_sfirst = (const int64_t*)(dm + off_sf);
-	const SiftSeg *d_segs = (const SiftSeg*)(dm + off_seg);
-	const int32_t *d_qseg = (const int32_t*)(dm + off_qs);
+	const int64_t *d_qfirst = m_qf.in(dm), *d_jfirst = m_jf.in(dm), *d_sfirst = m_sf.in(dm);
+	const SiftSeg *d_segs = m_seg.in(dm); const int32_t *d_qseg = m_qs.in(dm);
 	// (MPA_SIFT_CAP=2048, measurement: ranges of half the size need 18 KB of LDS instead of 37 KB -- a workgroup then fits next to
 	// four DP workgroups on a CU -- and touch the lists twice as often)
 	static const int sift_cap = [] { const char *e = getenv("MPA_SIFT_CAP"); return e ? atoi(e) : 4096; }();
-	if (reach >= 0)
-		hipLaunchKernelGGL((k_seed_sift<4096, true, uint32_t>), dim3((unsigned)n_seg), dim3(SIFT_THREADS), 0, s, d_segs, B.jobs.as<SeedJobDev>(), d_jfirst, d_qfirst, d_sfirst, d->kb, n_block, nb,
-		                   B.s_cur.as<int32_t>(), B.s_cur2.as<int32_t>(), stage0, stage1, B.s_kept.as<uint32_t>(), B.s_base.as<int64_t>(),
-		                   B.s_flag.as<int32_t>(), (uint32_t)reach);
-	else if (sift_cap == 2048)
-		hipLaunchKernelGGL(k_seed_sift<2048>, dim3((unsigned)n_seg), dim3(SIFT_THREADS), 0, s, d_segs, B.jobs.as<SeedJobDev>(), d_jfirst, d_qfirst, d_sfirst, d->kb, n_block, nb,
-		                   B.s_cur.as<int32_t>(), B.s_cur2.as<int32_t>(), stage0, stage1, B.s_kept.as<uint32_t>(), B.s_base.as<int64_t>(),
-		                   B.s_flag.as<int32_t>());
-	else
-	hipLaunchKernelGGL(k_seed_sift<4096>, dim3((unsigned)n_seg), dim3(SIFT_THREADS), 0, s, d_segs, B.jobs.as<SeedJobDev>(), d_jfirst, d_qfirst, d_sfirst, d->kb, n_block, nb,
-	                   B.s_cur.as<int32_t>(), B.s_cur2.as<int32_t>(), stage0, stage1, B.s_kept.as<uint32_t>(), B.s_base.as<int64_t>(),
-	                   B.s_flag.as<int32_t>());
+	auto sift = [&](auto kernel, auto... reach_arg) {           // the three instantiations differ in the template arguments and the trailing reach alone
+		hipLaunchKernelGGL(kernel, dim3((unsigned)n_seg), dim3(SIFT_THREADS), 0, s, d_segs, B.jobs.as<SeedJobDev>(), d_jfirst, d_qfirst, d_sfirst, d->kb, n_block, nb,
+		                   B.s_cur.as<int32_t>(), B.s_cur2.as<int32_t>(), stage0, stage1, B.s_kept.as<uint32_t>(), B.s_base.as<int64_t>(), B.s_flag.as<int32_t>(), reach_arg...);
+	};
+	if (reach >= 0) sift(k_seed_sift<4096, true, uint32_t>, (uint32_t)reach);
+	else if (sift_cap == 2048) sift(k_seed_sift<2048>);
+	else sift(k_seed_sift<4096>);
 	hipLaunchKernelGGL(k_sift_offsets, dim3(1), dim3(256), 0, s, d_segs, n_seg, n_query, d_qseg, B.s_flag.as<int32_t>(), B.s_kept.as<uint32_t>(), B.s_out.as<int64_t>(),
 	                   B.pf_qfirst2.as<int64_t>());
 	HIP_TRY(hipGetLastError());
-	int64_t *h_qfirst2 = B.h_back.as<int64_t>(), *h_cfirst = h_qfirst2 + (n_query + 1);
-	int32_t *h_flag = (int32_t*)(h_cfirst + (n_query + 1));
+	int64_t *h_qfirst2 = b_qfirst2.in(B.h_back.p), *h_cfirst = b_cfirst.in(B.h_back.p); int32_t *h_flag = b_flag.in(B.h_back.p);
 	HIP_TRY(hipMemcpyAsync(h_qfirst2, B.pf_qfirst2.p, meta_q, hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipMemcpyAsync(h_flag, B.s_flag.p, (size_t)n_query * 4, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h_flag, B.s_flag.p, b_flag.bytes(), hipMemcpyDeviceToHost, s));
 	HIP_TRY(wait_stream(ctx, s));
 	const double t_sift = now_ms();
 	timing_note("    seed: segments + sift (wait)", t_sift - t_begin);
@@ -494,35 +459,33 @@ static int dev_chains_on_device(mpa_ctx_t *ctx, int32_t n_query, int64_t m, int6
 	// ---- one allocation, carved up: everything is indexed like the view (m entries), `ends` and `stack` have extras per problem
 	const size_t M = (size_t)m, NQ = (size_t)n_query;
 	Carve carve;
-	const size_t o_vpos = carve(M * 8), o_vf = o_vpos + M * 4, o_vpred = carve(M * 4), o_va = carve(M * 8);
+	// (the view's positions and scores share one piece: the main chains' u words land there once the pre-chain has been extracted)
+	const auto v_posf = carve.take<int32_t>(2 * M), v_pos = v_posf.sub<int32_t>(0, M), v_f = v_posf.sub<int32_t>(M * 4, M), v_pred = carve.take<int32_t>(M); const auto v_a = carve.take<uint64_t>(M);
 	ExtractCarve xc = carve_extract_scratch(carve, M, NQ);
-	const size_t o_pre_a = carve(M * 8), o_pre_u = carve(M * 8), o_pre_na = carve(NQ * 8 + 8), o_pre_nu = carve(NQ * 8 + 8);
-	const size_t o_mf = carve(M * 4), o_mpred = carve(M * 4), o_mmark = carve(M * 4);
-	const int32_t kSerialRun = 48;                          // longer runs of the main chain get a wavefront each (k_chain_fwd_wave)
-	const size_t long_cap = M / (size_t)(kSerialRun + 1) + 16, o_long = carve(long_cap * sizeof(LongRun)), o_nlong = carve(64);
+	const auto pre_a = carve.take<uint64_t>(M), pre_u = carve.take<uint64_t>(M); const auto pre_na = carve.take<int64_t>(NQ + 1), pre_nu = carve.take<int64_t>(NQ + 1);
+	const ChainFwdCarve fw = carve_chain_fwd(carve, M, kChainSerialRun);   // longer runs of the main chain get a wavefront each (k_chain_fwd_wave)
 	// (the main chains go where the pre-chain's view was: it is dead once the pre-chain has been extracted)
-	xc.out_a = o_va, xc.out_u = o_vpos;
+	xc.out_a = v_a, xc.out_u = v_posf.sub<uint64_t>(0, M);
 	carve_extract_counts(carve, NQ, xc);
 	int rc;
 	if ((rc = B.x_all.ensure(carve.at))) return rc;         // (ensure() adds a third of slack: a re-allocation is a hipFree, which waits for the whole device)
 	char *X = B.x_all.as<char>();
-	HIP_TRY(hipMemsetAsync(X + xc.status, 0, NQ * 4 + 16, s));
+	HIP_TRY(hipMemsetAsync(xc.status.in(X), 0, xc.status.bytes() + 16, s));
 	const unsigned nblk2 = (unsigned)((n2 + 255) / 256);
 	// the sparse view of the pre-chain's forward pass
 	hipLaunchKernelGGL((k_seed_compact<uint64_t, true>), dim3(nblk2), dim3(256), 0, s, key, val, n2, nb, B.pf_qfirst2.as<int64_t>(), B.flag.as<uint32_t>(), B.idx.as<uint32_t>(),
-	                   B.f.as<int32_t>(), B.pred.as<int32_t>(), (int32_t*)(X + o_vpos), (int32_t*)(X + o_vf), (int32_t*)(X + o_vpred), (uint64_t*)(X + o_va));
+	                   B.f.as<int32_t>(), B.pred.as<int32_t>(), v_pos.in(X), v_f.in(X), v_pred.in(X), v_a.in(X));
 	// pre-chain extraction (the survivors as a set): into the pre_* arrays, over the scratch the main chain's extraction uses again
 	ExtractCarve pc = xc;
-	pc.out_a = o_pre_a, pc.out_u = o_pre_u, pc.na = o_pre_na, pc.nu = o_pre_nu;
-	const ChainViewDev pre_view{ B.cfirst.as<int64_t>(), nullptr, d_qfirst, (const int32_t*)(X + o_vpos), (const int32_t*)(X + o_vf), (const int32_t*)(X + o_vpred), (const uint64_t*)(X + o_va) };
+	pc.out_a = pre_a, pc.out_u = pre_u, pc.na = pre_na, pc.nu = pre_nu;
+	const ChainViewDev pre_view{ B.cfirst.as<int64_t>(), nullptr, d_qfirst, v_pos.in(X), v_f.in(X), v_pred.in(X), v_a.in(X) };
 	if ((rc = chain_extract_launch(ctx, s, X, pc, pre_view, pre, n_query, 1, "pre-chain"))) return rc;
 	// the main chain over the survivors: forward pass ...
 	const PreParams pm = pre_params(mainp);
-	HIP_TRY(hipMemsetAsync(X + o_nlong, 0, 64, s));
-	if ((rc = chain_fwd_launch(s, (const uint64_t*)(X + o_pre_a), m, B.cfirst.as<int64_t>(), (const int64_t*)(X + o_pre_na), n_query, pm, kSerialRun,
-	                           ChainFwdBufs{ (int32_t*)(X + o_mf), (int32_t*)(X + o_mpred), (int32_t*)(X + o_mmark), (uint32_t*)(X + xc.mark), (LongRun*)(X + o_long), (unsigned int*)(X + o_nlong), long_cap }))) return rc;
+	HIP_TRY(hipMemsetAsync(fw.n_runs.in(X), 0, fw.n_runs.bytes(), s));
+	if ((rc = chain_fwd_launch(s, pre_a.in(X), m, B.cfirst.as<int64_t>(), pre_na.in(X), n_query, pm, kChainSerialRun, fw.in(X, xc)))) return rc;
 	// ... and extraction: dense views over the survivors; the chains of all queries into pinned memory
-	const ChainViewDev main_view{ B.cfirst.as<int64_t>(), (const int64_t*)(X + o_pre_na), nullptr, nullptr, (const int32_t*)(X + o_mf), (const int32_t*)(X + o_mpred), (const uint64_t*)(X + o_pre_a) };
+	const ChainViewDev main_view{ B.cfirst.as<int64_t>(), pre_na.in(X), nullptr, nullptr, fw.f.in(X), fw.pred.in(X), pre_a.in(X) };
 	const int32_t *h_status = nullptr;
 	if ((rc = chain_extract_pack(ctx, s, X, xc, main_view, mainp, n_query, H, "main chain", nullptr, ChainTailOut{ out.a_first, out.u_first, out.A, out.U }, &h_status, regions))) return rc;
 	out.has_chains = true;
@@ -568,11 +531,12 @@ static int dev_seed_direct_impl(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_block
 	}
 	// ---- one allocation, carved up, as in dev_chains_on_device: the view (= the forward pass's own arrays), the extraction's scratch, the chains
 	Carve carve;
-	const size_t o_vpos = carve(M * 4), o_vf = carve(M * 4), o_vpred = carve(M * 4), o_va = carve(M * 8), o_fmark = carve(M * 4);
+	ChainFwdCarve fw{};                                      // (the view's f / pred ARE the forward pass's)
+	const auto v_pos = carve.take<int32_t>(M), v_f = fw.f = carve.take<int32_t>(M), v_pred = fw.pred = carve.take<int32_t>(M); const auto v_a = carve.take<uint64_t>(M);
+	fw.mark = carve.take<int32_t>(M);
 	ExtractCarve xc = carve_extract_scratch(carve, M, NQ);
-	const int32_t kSerialRun = 48;                          // longer runs get a wavefront each (k_chain_fwd_wave)
-	const size_t long_cap = M / (size_t)(kSerialRun + 1) + 16, o_long = carve(long_cap * sizeof(LongRun)), o_nlong = carve(64);
-	xc.out_a = carve(M * 8), xc.out_u = carve(M * 8);
+	carve_chain_runs(carve, M, kChainSerialRun, fw);         // longer runs get a wavefront each (k_chain_fwd_wave)
+	xc.out_a = carve.take<uint64_t>(M), xc.out_u = carve.take<uint64_t>(M);
 	carve_extract_counts(carve, NQ, xc);
 	// (the sift's staging sits at the front of this block: if the block has to move, k_sift_copy must have read it first)
 	if (carve.at > B.x_all.cap) HIP_TRY(wait_stream(ctx, s));
@@ -580,12 +544,11 @@ static int dev_seed_direct_impl(mpa_ctx_t *ctx, DeviceIndex *d, uint32_t n_block
 	char *X = B.x_all.as<char>();
 	const unsigned nblk = (unsigned)((n2 + 255) / 256);
 	const int64_t *d_first = B.pf_qfirst2.as<int64_t>();       // first kept anchor of every query (k_sift_offsets)
-	HIP_TRY(hipMemsetAsync(X + xc.status, 0, NQ * 4 + 16, s));
-	HIP_TRY(hipMemsetAsync(X + o_nlong, 0, 64, s));
-	hipLaunchKernelGGL(k_sift_anchors, dim3(nblk), dim3(256), 0, s, B.dkey.as<uint64_t>(), B.val64[0].as<uint64_t>(), n2, nb, (uint64_t*)(X + o_va), (int32_t*)(X + o_vpos));
-	if ((rc = chain_fwd_launch(s, (const uint64_t*)(X + o_va), n2, d_first, nullptr, n_query, pm, kSerialRun,
-	                           ChainFwdBufs{ (int32_t*)(X + o_vf), (int32_t*)(X + o_vpred), (int32_t*)(X + o_fmark), (uint32_t*)(X + xc.mark), (LongRun*)(X + o_long), (unsigned int*)(X + o_nlong), long_cap }))) return rc;
-	const ChainViewDev view{ d_first, nullptr, F.d_qfirst, (const int32_t*)(X + o_vpos), (const int32_t*)(X + o_vf), (const int32_t*)(X + o_vpred), (const uint64_t*)(X + o_va) };
+	HIP_TRY(hipMemsetAsync(xc.status.in(X), 0, xc.status.bytes() + 16, s));
+	HIP_TRY(hipMemsetAsync(fw.n_runs.in(X), 0, fw.n_runs.bytes(), s));
+	hipLaunchKernelGGL(k_sift_anchors, dim3(nblk), dim3(256), 0, s, B.dkey.as<uint64_t>(), B.val64[0].as<uint64_t>(), n2, nb, v_a.in(X), v_pos.in(X));
+	if ((rc = chain_fwd_launch(s, v_a.in(X), n2, d_first, nullptr, n_query, pm, kChainSerialRun, fw.in(X, xc)))) return rc;
+	const ChainViewDev view{ d_first, nullptr, F.d_qfirst, v_pos.in(X), v_f.in(X), v_pred.in(X), v_a.in(X) };
 	const int32_t *h_status = nullptr;
 	if ((rc = chain_extract_pack(ctx, s, X, xc, view, mainp, n_query, H, nullptr, nullptr, ChainTailOut{ out.a_first, out.u_first, out.A, out.U }, &h_status, regions))) return rc;
 	out.has_chains = true;
@@ -679,35 +642,41 @@ static int dev_sketch_jobs_impl(mpa_ctx_t *ctx, mpa_idx_s *mi, DeviceIndex *d, i
 	hipStream_t s = ctx->seed_stream;
 	const int32_t n_query = q->n_seq;
 	const int64_t base = q->q_off[0], L = q->q_off[n_query] - base;
-	const size_t NQ = (size_t)n_query, mq = (NQ + 1) * 8, fq = (NQ * 4 + 15) & ~(size_t)15;
-	// one pinned block up: residue table | q_off (from 0) | protein text
-	const size_t off_qo = 256, off_tx = off_qo + mq, up_bytes = off_tx + (size_t)L + 16;
+	const size_t NQ = (size_t)n_query;
+	// one pinned block up, packed: residue table | q_off (from 0) | protein text
+	Carve up(1), cnt(1), res8(1), res(16);
+	const auto u_tab = up.take<uint8_t>(256); const auto u_qo = up.take<int64_t>(NQ + 1); const auto u_tx = up.take<uint8_t>((size_t)L);
+	const size_t up_bytes = up.at + 16;
+	// k_q: anchors and seeds per query | the results, as they come down: qfirst | jfirst | cut-offs | flags (the last two in 16-byte sections)
+	const auto q_na = cnt.take<int64_t>(NQ + 1), q_nk = cnt.take<int64_t>(NQ + 1), r_qfirst = res8.take<int64_t>(NQ + 1), r_jfirst = res8.take<int64_t>(NQ + 1);
+	res.skip(res8.at);
+	const auto r_mo = res.take<int32_t>(NQ), r_flag = res.take<int32_t>(NQ);
 	int rc;
 	if ((rc = B.h_kin.ensure(up_bytes)) || (rc = B.k_in.ensure(up_bytes)) || (rc = B.k_cnt.ensure((size_t)L * 4 + 16)) || (rc = B.k_bkt.ensure((size_t)L * 4 + 16)) ||
-	    (rc = B.k_q.ensure(4 * mq + 2 * fq)) || (rc = B.h_kout.ensure(2 * mq + 2 * fq)) || (rc = B.jobs.ensure(((size_t)L + 1) * sizeof(SeedJobDev)))) return rc;   // (a position ends at most one seed)
+	    (rc = B.k_q.ensure(cnt.at + res.at)) || (rc = B.h_kout.ensure(res.at)) || (rc = B.jobs.ensure(((size_t)L + 1) * sizeof(SeedJobDev)))) return rc;   // (a position ends at most one seed)
 	char *hu = B.h_kin.as<char>();
-	memcpy(hu, tab_aa13(), 256);
-	{ int64_t *qo = (int64_t*)(hu + off_qo); for (int32_t i = 0; i <= n_query; ++i) qo[i] = q->q_off[i] - base; }
-	if (L > 0) memcpy(hu + off_tx, q->seqs + base, (size_t)L);
-	HIP_TRY(hipMemcpyAsync(B.k_in.p, hu, off_tx + (size_t)L, hipMemcpyHostToDevice, s));
+	memcpy(u_tab.in(hu), tab_aa13(), 256);
+	{ int64_t *qo = u_qo.in(hu); for (int32_t i = 0; i <= n_query; ++i) qo[i] = q->q_off[i] - base; }
+	if (L > 0) memcpy(u_tx.in(hu), q->seqs + base, (size_t)L);
+	HIP_TRY(hipMemcpyAsync(B.k_in.p, hu, up.at, hipMemcpyHostToDevice, s));
 	const char *din = B.k_in.as<char>();
-	char *dq = B.k_q.as<char>();
-	int64_t *d_na = (int64_t*)dq, *d_nk = (int64_t*)(dq + mq), *d_qfirst = (int64_t*)(dq + 2 * mq), *d_jfirst = (int64_t*)(dq + 3 * mq);
-	int32_t *d_mo = (int32_t*)(dq + 4 * mq), *d_flag = (int32_t*)(dq + 4 * mq + fq);
+	char *dq = B.k_q.as<char>(), *dres = dq + cnt.at;
+	int64_t *d_na = q_na.in(dq), *d_nk = q_nk.in(dq), *d_qfirst = r_qfirst.in(dres), *d_jfirst = r_jfirst.in(dres);
+	int32_t *d_mo = r_mo.in(dres), *d_flag = r_flag.in(dres);
 	SketchParams sp;
 	sp.n_bucket = (int64_t)mi->ki.size(), sp.n_kb = mi->n_kb, sp.kmer = mi->opt.kmer, sp.mod_bit = mi->opt.mod_bit, sp.max_occ = max_occ, sp.pad = 0;
 	const unsigned nwg = (unsigned)((n_query + SKETCH_WAVES - 1) / SKETCH_WAVES);
-	hipLaunchKernelGGL(k_sketch_count, dim3(nwg), dim3(64 * SKETCH_WAVES), 0, s, (const uint8_t*)(din + off_tx), (const int64_t*)(din + off_qo), n_query, (const uint8_t*)din,
+	hipLaunchKernelGGL(k_sketch_count, dim3(nwg), dim3(64 * SKETCH_WAVES), 0, s, u_tx.in(din), u_qo.in(din), n_query, u_tab.in(din),
 	                   (const int64_t*)d->ki, sp, B.k_cnt.as<int32_t>(), B.k_bkt.as<uint32_t>(), d_na, d_nk, d_mo, d_flag);
 	hipLaunchKernelGGL(k_offsets2, dim3(1), dim3(256), 0, s, (const int64_t*)d_na, (const int64_t*)d_nk, n_query, d_qfirst, d_jfirst);
-	hipLaunchKernelGGL(k_sketch_emit, dim3(nwg), dim3(64 * SKETCH_WAVES), 0, s, (const int64_t*)(din + off_qo), n_query, (const int64_t*)d->ki, B.k_cnt.as<int32_t>(),
+	hipLaunchKernelGGL(k_sketch_emit, dim3(nwg), dim3(64 * SKETCH_WAVES), 0, s, u_qo.in(din), n_query, (const int64_t*)d->ki, B.k_cnt.as<int32_t>(),
 	                   B.k_bkt.as<uint32_t>(), (const int64_t*)d_qfirst, (const int64_t*)d_jfirst, (const int32_t*)d_mo, (const int32_t*)d_flag, B.jobs.as<SeedJobDev>());
 	HIP_TRY(hipGetLastError());
-	// qfirst | jfirst | cut-offs | flags: contiguous on the device, one copy, one wait
-	char *hd = B.h_kout.as<char>();
-	HIP_TRY(hipMemcpyAsync(hd, dq + 2 * mq, 2 * mq + 2 * fq, hipMemcpyDeviceToHost, s));
+	// the results: contiguous on the device, one copy, one wait
+	const char *hd = B.h_kout.as<char>();
+	HIP_TRY(hipMemcpyAsync(B.h_kout.p, dres, res.at, hipMemcpyDeviceToHost, s));
 	HIP_TRY(wait_stream(ctx, s));
-	out.qfirst = (const int64_t*)hd, out.jfirst = (const int64_t*)(hd + mq), out.max_occ = (const int32_t*)(hd + 2 * mq), out.flag = (const int32_t*)(hd + 2 * mq + fq);
+	out.qfirst = r_qfirst.in(hd), out.jfirst = r_jfirst.in(hd), out.max_occ = r_mo.in(hd), out.flag = r_flag.in(hd);
 	out.n_anchor = out.qfirst[n_query], out.n_jobs = out.jfirst[n_query];
 	for (int32_t i = 0; i < n_query; ++i) out.n_flagged += out.flag[i] != 0;
 	return MPA_OK;
@@ -786,12 +755,13 @@ int dev_chain_forward(mpa_ctx_t *ctx, const ChainParams &cp, int32_t n_prob, con
 	if ((rc = B.c_a.ensure((size_t)n * 8)) || (rc = B.c_f.ensure((size_t)n * 4)) || (rc = B.c_pred.ensure((size_t)n * 4)) || (rc = B.c_mark.ensure((size_t)n * 4)) ||
 	    (rc = B.c_flag.ensure((size_t)n * 4)) || (rc = B.c_first.ensure(((size_t)n_prob + 1) * 8))) return rc;
 	// runs longer than this get a wavefront each (k_chain_fwd_wave); MPA_CHAIN_SERIAL_RUN overrides (tests: 4 = almost every run)
-	const int32_t serial_run = [] { const char *e = getenv("MPA_CHAIN_SERIAL_RUN"); return e ? std::max(1, atoi(e)) : 48; }();
-	const size_t long_cap = (size_t)n / (size_t)(serial_run + 1) + 16;
-	if ((rc = B.c_long.ensure(64 + long_cap * sizeof(LongRun)))) return rc;
-	unsigned int *d_nlong = B.c_long.as<unsigned int>();
-	LongRun *d_long = (LongRun*)(B.c_long.as<char>() + 64);
-	HIP_TRY(hipMemsetAsync(d_nlong, 0, 64, s));
+	const int32_t serial_run = [] { const char *e = getenv("MPA_CHAIN_SERIAL_RUN"); return e ? std::max(1, atoi(e)) : kChainSerialRun; }();
+	Carve lc(1);                                             // c_long, packed: the counter's 64 bytes | the list
+	const auto p_nlong = lc.take<unsigned int>(16); const auto p_long = lc.take<LongRun>((size_t)n / (size_t)(serial_run + 1) + 16);
+	const size_t long_cap = p_long.n;
+	if ((rc = B.c_long.ensure(lc.at))) return rc;
+	unsigned int *d_nlong = p_nlong.in(B.c_long.p); LongRun *d_long = p_long.in(B.c_long.p);
+	HIP_TRY(hipMemsetAsync(d_nlong, 0, p_nlong.bytes(), s));
 	HIP_TRY(hipMemcpyAsync(B.c_a.p, io.a, (size_t)n * 8, hipMemcpyHostToDevice, s));
 	HIP_TRY(hipMemcpyAsync(B.c_first.p, first, ((size_t)n_prob + 1) * 8, hipMemcpyHostToDevice, s));
 	if ((rc = chain_fwd_launch(s, B.c_a.as<uint64_t>(), n, B.c_first.as<int64_t>(), nullptr, n_prob, pp, serial_run,
@@ -820,30 +790,30 @@ int dev_chain_extract_dbg(mpa_ctx_t *ctx, const ChainParams &p, int32_t n_prob, 
 	hipStream_t s = ctx->seed_stream;
 	const size_t M = (size_t)m, NP = (size_t)n_prob;
 	Carve carve;
-	const size_t o_first = carve((NP + 1) * 8), o_ntot = carve((NP + 1) * 8), o_vpos = carve(M * 4), o_vf = carve(M * 4), o_vpred = carve(M * 4), o_va = carve(M * 8);
+	const auto x_first = carve.take<int64_t>(NP + 1), x_ntot = carve.take<int64_t>(NP + 1); const auto x_pos = carve.take<int32_t>(M), x_f = carve.take<int32_t>(M), x_pred = carve.take<int32_t>(M);
+	const auto x_a = carve.take<uint64_t>(M);
 	ExtractCarve xc = carve_extract_scratch(carve, M, NP);
-	xc.out_a = carve(M * 8), xc.out_u = carve(M * 8);
+	xc.out_a = carve.take<uint64_t>(M), xc.out_u = carve.take<uint64_t>(M);
 	carve_extract_counts(carve, NP, xc);
 	int rc;
 	if ((rc = B.x_all.ensure(carve.at))) return rc;
 	char *X = B.x_all.as<char>();
-	HIP_TRY(hipMemsetAsync(X + xc.status, 0, NP * 4 + 16, s));
-	HIP_TRY(hipMemcpyAsync(X + o_first, vfirst, (NP + 1) * 8, hipMemcpyHostToDevice, s));
-	if (ntot_first) HIP_TRY(hipMemcpyAsync(X + o_ntot, ntot_first, (NP + 1) * 8, hipMemcpyHostToDevice, s));
-	if (v_pos) HIP_TRY(hipMemcpyAsync(X + o_vpos, v_pos, M * 4, hipMemcpyHostToDevice, s));
-	HIP_TRY(hipMemcpyAsync(X + o_vf, v_f, M * 4, hipMemcpyHostToDevice, s));
-	HIP_TRY(hipMemcpyAsync(X + o_vpred, v_pred, M * 4, hipMemcpyHostToDevice, s));
-	HIP_TRY(hipMemcpyAsync(X + o_va, v_a, M * 8, hipMemcpyHostToDevice, s));
-	const ChainViewDev view{ (const int64_t*)(X + o_first), nullptr, ntot_first ? (const int64_t*)(X + o_ntot) : nullptr, v_pos ? (const int32_t*)(X + o_vpos) : nullptr,
-	                         (const int32_t*)(X + o_vf), (const int32_t*)(X + o_vpred), (const uint64_t*)(X + o_va) };
+	HIP_TRY(hipMemsetAsync(xc.status.in(X), 0, xc.status.bytes() + 16, s));
+	HIP_TRY(hipMemcpyAsync(x_first.in(X), vfirst, x_first.bytes(), hipMemcpyHostToDevice, s));
+	if (ntot_first) HIP_TRY(hipMemcpyAsync(x_ntot.in(X), ntot_first, x_ntot.bytes(), hipMemcpyHostToDevice, s));
+	if (v_pos) HIP_TRY(hipMemcpyAsync(x_pos.in(X), v_pos, x_pos.bytes(), hipMemcpyHostToDevice, s));
+	HIP_TRY(hipMemcpyAsync(x_f.in(X), v_f, x_f.bytes(), hipMemcpyHostToDevice, s));
+	HIP_TRY(hipMemcpyAsync(x_pred.in(X), v_pred, x_pred.bytes(), hipMemcpyHostToDevice, s));
+	HIP_TRY(hipMemcpyAsync(x_a.in(X), v_a, x_a.bytes(), hipMemcpyHostToDevice, s));
+	const ChainViewDev view{ x_first.in(X), nullptr, ntot_first ? x_ntot.in(X) : nullptr, v_pos ? x_pos.in(X) : nullptr, x_f.in(X), x_pred.in(X), x_a.in(X) };
 	if (set_only) {
 		if ((rc = chain_extract_launch(ctx, s, X, xc, view, p, n_prob, 1, nullptr))) return rc;
 		std::vector<int64_t> na(NP);
 		std::vector<int32_t> st(NP);
 		std::vector<uint64_t> all(M);
-		HIP_TRY(hipMemcpyAsync(na.data(), X + xc.na, NP * 8, hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipMemcpyAsync(st.data(), X + xc.status, NP * 4, hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipMemcpyAsync(all.data(), X + xc.out_a, M * 8, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(na.data(), xc.na.in(X), NP * 8, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(st.data(), xc.status.in(X), NP * 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(all.data(), xc.out_a.in(X), M * 8, hipMemcpyDeviceToHost, s));
 		HIP_TRY(wait_stream(ctx, s));
 		for (size_t q = 0; q < NP; ++q) {
 			const int64_t room = vfirst[q + 1] - vfirst[q];

@@ -19,29 +19,7 @@
 
 namespace mpa {
 
-namespace {
-struct StatsLayout {
-	size_t off_jobs, off_slot, off_rslot, off_cig, off_text, up_bytes, off_feat, down_bytes, off_body, cs_down_bytes, off_rbody, rows_down_bytes;
-	// slot_bytes < 0: no cs strings; rows_bytes < 0: no residue rows (the block that goes up is then what it was without them)
-	explicit StatsLayout(const AlnWalkSizes &z)
-	{
-		auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-		off_jobs = 1024;                                                   // (the tables take ALN_TAB_BYTES of the first KB)
-		off_slot = off_jobs + up16((size_t)z.n_jobs * sizeof(AlnStatsJob));
-		off_rslot = off_slot + (z.slot_bytes >= 0 ? up16((size_t)(z.n_jobs + 1) * 8) : 0);
-		off_cig = off_rslot + (z.rows_bytes >= 0 ? up16((size_t)(z.n_jobs + 1) * 8) : 0);
-		off_text = off_cig + up16((size_t)z.n_cigar * 4);
-		up_bytes = off_text + up16((size_t)z.text_bytes) + 16;
-		off_feat = up16((size_t)z.n_jobs * sizeof(AlnStatsOut));
-		down_bytes = off_feat + (size_t)(z.n_feat > 0 ? z.n_feat : 0) * sizeof(AlnFeat) + 16;
-		off_body = up16((size_t)z.n_jobs * sizeof(AlnCsOut));
-		cs_down_bytes = off_body + (size_t)(z.slot_bytes > 0 ? z.slot_bytes : 0) + 16;
-		off_rbody = up16((size_t)z.n_jobs * sizeof(AlnRowsOut));
-		rows_down_bytes = off_rbody + (size_t)(z.rows_bytes > 0 ? z.rows_bytes : 0) + 16;
-	}
-};
-static_assert(ALN_TAB_BYTES <= 1024, "the tables share the first KB of the staging block");
-}
+// (the layouts of the blocks: StatsLayout, SpansLayout, AsmLayout in dev_layout.h)
 
 // The pinned blocks of a call for any non-empty subset of the walks, the one that goes up for the caller to fill: jobs, CIGAR words,
 // text and, next to the jobs, cs.slot_off[n_jobs + 1] / rows.slot_off[n_jobs + 1].  z.n_feat < 0: no statistics (the statistics stay
@@ -58,9 +36,9 @@ int dev_aln_walks_stage(mpa_ctx_t *ctx, const AlnWalkSizes &z, AlnStatsIO &io, A
 	if (z.rows_bytes >= 0 && ctx->walks.h_rows_down.ensure(L.rows_down_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
 	if (z.n_feat >= 0 && ctx->walks.h_stats_down.ensure(L.down_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
 	char *hu = ctx->walks.h_stats_up.as<char>();
-	io.jobs = (AlnStatsJob*)(hu + L.off_jobs), io.cigar = (uint32_t*)(hu + L.off_cig), io.text = hu + L.off_text;
-	if (z.slot_bytes >= 0) cs.slot_off = (int64_t*)(hu + L.off_slot);
-	if (z.rows_bytes >= 0) rows.slot_off = (int64_t*)(hu + L.off_rslot);
+	io.jobs = L.jobs.in(hu), io.cigar = L.cig.in(hu), io.text = L.text.in(hu);
+	if (z.slot_bytes >= 0) cs.slot_off = L.slot.in(hu);
+	if (z.rows_bytes >= 0) rows.slot_off = L.rslot.in(hu);
 	return MPA_OK;
 }
 
@@ -91,94 +69,58 @@ int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const 
 		return tl_alloc_failed ? MPA_ERR_UNSUPPORTED : MPA_ERR_HIP;
 	hipStream_t s = ctx->stream;
 	char *hu = ctx->walks.h_stats_up.as<char>();
-	aln_tables_fill((uint8_t*)hu, mat, (size_t)(p.asize * p.asize));
+	aln_tables_fill(L.tabs.in(hu), mat, (size_t)(p.asize * p.asize));
 	HIP_TRY(hipMemcpyAsync(ctx->walks.st_in.p, hu, L.up_bytes - 16, hipMemcpyHostToDevice, s));
 	const char *din = ctx->walks.st_in.as<char>();
-	const uint32_t *dcig = dev_cig ? ctx->spans.sp_cig.as<uint32_t>() : (const uint32_t*)(din + L.off_cig);   // (MPA_GPU_SPANS=1: where k_assemble left the words)
+	const uint8_t *dtext = (const uint8_t*)L.text.in(din);
+	const uint32_t *dcig = dev_cig ? ctx->spans.sp_cig.as<uint32_t>() : L.cig.in(din);   // (MPA_GPU_SPANS=1: where k_assemble left the words)
 	const unsigned nwg = (unsigned)((n_jobs + STATS_WAVES - 1) / STATS_WAVES);
 	if (stats) {
 		char *dout = ctx->walks.st_out.as<char>();
-		hipLaunchKernelGGL(k_aln_stats, dim3(nwg), dim3(64 * STATS_WAVES), 0, s, (const AlnStatsJob*)(din + L.off_jobs), (int32_t)n_jobs, (const uint8_t*)din, p,
-		                   (const uint8_t*)(din + L.off_text), dcig, (const uint8_t*)d->seq, (const int64_t*)d->ctg_off, (const int64_t*)d->ctg_len,
-		                   (AlnStatsOut*)dout, (AlnFeat*)(dout + L.off_feat));
+		hipLaunchKernelGGL(k_aln_stats, dim3(nwg), dim3(64 * STATS_WAVES), 0, s, L.jobs.in(din), (int32_t)n_jobs, L.tabs.in(din), p,
+		                   dtext, dcig, (const uint8_t*)d->seq, (const int64_t*)d->ctg_off, (const int64_t*)d->ctg_len,
+		                   L.out.in(dout), L.feat.in(dout));
 		HIP_TRY(hipGetLastError());
-		char *hd = ctx->walks.h_stats_down.as<char>();
-		HIP_TRY(hipMemcpyAsync(hd, dout, L.down_bytes - 16, hipMemcpyDeviceToHost, s));
-		io.out = (const AlnStatsOut*)hd, io.feat = (const AlnFeat*)(hd + L.off_feat);
+		const char *hd = ctx->walks.h_stats_down.as<char>();
+		HIP_TRY(hipMemcpyAsync(ctx->walks.h_stats_down.p, dout, L.down_bytes - 16, hipMemcpyDeviceToHost, s));
+		io.out = L.out.in(hd), io.feat = L.feat.in(hd);
 	}
 	if (cs_on) {
 		char *dout = ctx->walks.cs_out.as<char>();
-		hipLaunchKernelGGL(k_aln_cs, dim3(nwg), dim3(64 * STATS_WAVES), 0, s, (const AlnStatsJob*)(din + L.off_jobs), (int32_t)n_jobs, (const uint8_t*)din,
-		                   (const uint8_t*)(din + L.off_text), dcig, (const uint8_t*)d->seq, (const int64_t*)d->ctg_off, (const int64_t*)d->ctg_len,
-		                   (const int64_t*)(din + L.off_slot), (AlnCsOut*)dout, dout + L.off_body);
+		hipLaunchKernelGGL(k_aln_cs, dim3(nwg), dim3(64 * STATS_WAVES), 0, s, L.jobs.in(din), (int32_t)n_jobs, L.tabs.in(din),
+		                   dtext, dcig, (const uint8_t*)d->seq, (const int64_t*)d->ctg_off, (const int64_t*)d->ctg_len,
+		                   L.slot.in(din), L.cs_out.in(dout), L.body.in(dout));
 		HIP_TRY(hipGetLastError());
-		char *hd = ctx->walks.h_cs_down.as<char>();
-		HIP_TRY(hipMemcpyAsync(hd, dout, L.cs_down_bytes - 16, hipMemcpyDeviceToHost, s));
-		cs.out = (const AlnCsOut*)hd, cs.body = hd + L.off_body;
+		const char *hd = ctx->walks.h_cs_down.as<char>();
+		HIP_TRY(hipMemcpyAsync(ctx->walks.h_cs_down.p, dout, L.cs_down_bytes - 16, hipMemcpyDeviceToHost, s));
+		cs.out = L.cs_out.in(hd), cs.body = L.body.in(hd);
 	}
 	if (rows_on) {
 		char *dout = ctx->walks.rows_out.as<char>();
-		hipLaunchKernelGGL(k_aln_rows, dim3(nwg), dim3(64 * STATS_WAVES), 0, s, (const AlnStatsJob*)(din + L.off_jobs), (int32_t)n_jobs, (const uint8_t*)din, rp,
-		                   (const uint8_t*)(din + L.off_text), dcig, (const uint8_t*)d->seq, (const int64_t*)d->ctg_off, (const int64_t*)d->ctg_len,
-		                   (const int64_t*)(din + L.off_rslot), (AlnRowsOut*)dout, dout + L.off_rbody);
+		hipLaunchKernelGGL(k_aln_rows, dim3(nwg), dim3(64 * STATS_WAVES), 0, s, L.jobs.in(din), (int32_t)n_jobs, L.tabs.in(din), rp,
+		                   dtext, dcig, (const uint8_t*)d->seq, (const int64_t*)d->ctg_off, (const int64_t*)d->ctg_len,
+		                   L.rslot.in(din), L.rows_out.in(dout), L.rbody.in(dout));
 		HIP_TRY(hipGetLastError());
-		char *hd = ctx->walks.h_rows_down.as<char>();
-		HIP_TRY(hipMemcpyAsync(hd, dout, L.rows_down_bytes - 16, hipMemcpyDeviceToHost, s));
-		rows.out = (const AlnRowsOut*)hd, rows.body = hd + L.off_rbody;
+		const char *hd = ctx->walks.h_rows_down.as<char>();
+		HIP_TRY(hipMemcpyAsync(ctx->walks.h_rows_down.p, dout, L.rows_down_bytes - 16, hipMemcpyDeviceToHost, s));
+		rows.out = L.rows_out.in(hd), rows.body = L.rbody.in(hd);
 	}
 	HIP_TRY(wait_stream(ctx, s));
 	return MPA_OK;
 }
 
 // ---- MPA_GPU_SPANS=1 ------------------------------------------------------------------------------------------------------------
-namespace {
-static const size_t SPANS_HEAD_BYTES = 32;
-struct SpansLayout {
-	size_t off_plan, off_seg, off_rst1, off_text, up_bytes;                  // sp_in / h_sp_up (the tables take the first KB)
-	size_t off_tmp, off_excl, off_bsum, mid_bytes;                            // sp_mid (records with local numbers at 0)
-	size_t off_rec, off_task, down_bytes;                                     // sp_out / h_sp_down (the task count at 0, the tasks' three bounds as int64 at 8)
-	unsigned blocks;
-	SpansLayout(int64_t n_plan, int64_t n_seg, int64_t n_rst1, int64_t text_bytes)
-	{
-		auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-		blocks = (unsigned)((n_plan + SPANS_BLOCK - 1) / SPANS_BLOCK);
-		off_plan = 1024;
-		off_seg = off_plan + up16((size_t)n_plan * sizeof(SpansPlan));
-		off_rst1 = off_seg + up16((size_t)n_seg * sizeof(SegRec));
-		off_text = off_rst1 + up16((size_t)n_rst1 * sizeof(mpa_dp_rst_t));
-		up_bytes = off_text + up16((size_t)text_bytes) + 16;
-		off_tmp = up16((size_t)n_plan * sizeof(SpanRec));
-		off_excl = off_tmp + up16((size_t)n_plan * 2 * sizeof(mpa_dp_task_t));
-		off_bsum = off_excl + up16((size_t)n_plan * 4);
-		mid_bytes = off_bsum + up16((size_t)blocks * 4) + 16;
-		off_rec = SPANS_HEAD_BYTES;
-		off_task = off_rec + up16((size_t)n_plan * sizeof(SpanRec));
-		down_bytes = off_task + (size_t)n_plan * 2 * sizeof(mpa_dp_task_t) + 16;
-	}
-};
-struct AsmLayout {
-	size_t off_slot, off_pool2, up_bytes, rec_bytes;
-	AsmLayout(int64_t n_plan, int64_t n_rst2, int64_t n_pool2)
-	{
-		auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-		off_slot = up16((size_t)n_rst2 * sizeof(mpa_dp_rst_t));
-		off_pool2 = off_slot + up16((size_t)(n_plan + 1) * 8);
-		up_bytes = off_pool2 + up16((size_t)n_pool2 * 4) + 16;
-		rec_bytes = up16((size_t)n_plan * sizeof(AsmRec));
-	}
-};
-static_assert(sizeof(SpansPlan) % 8 == 0 && sizeof(SpanRec) % 8 == 0 && sizeof(AsmRec) % 8 == 0, "records in 16-byte aligned sections");
-}
+static size_t spans_blocks(int64_t n_plan) { return (size_t)((n_plan + SPANS_BLOCK - 1) / SPANS_BLOCK); }   // workgroups of k_spans / k_spans_emit
 
 int dev_spans_stage(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_seg, int64_t n_rst1, int64_t text_bytes, SpansIO &io)
 {
 	io = SpansIO();
 	if (n_plan <= 0 || n_plan > (int64_t)1 << 28 || n_seg < 0 || n_rst1 <= 0) { set_error("GPU spans: no plans, or too many for one launch"); return MPA_ERR_UNSUPPORTED; }
 	if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return MPA_ERR_HIP; }
-	const SpansLayout L(n_plan, n_seg, n_rst1, text_bytes);
+	const SpansLayout L(n_plan, n_seg, n_rst1, text_bytes, spans_blocks(n_plan));
 	if (ctx->spans.h_sp_up.ensure(L.up_bytes) != MPA_OK || ctx->spans.h_sp_down.ensure(L.down_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
 	char *hu = ctx->spans.h_sp_up.as<char>();
-	io.plan = (SpansPlan*)(hu + L.off_plan), io.seg = (SegRec*)(hu + L.off_seg), io.rst1 = (mpa_dp_rst_t*)(hu + L.off_rst1), io.text = hu + L.off_text;
+	io.plan = L.plan.in(hu), io.seg = L.seg.in(hu), io.rst1 = L.rst1.in(hu), io.text = L.text.in(hu);
 	return MPA_OK;
 }
 
@@ -190,7 +132,7 @@ int dev_spans_round1(mpa_ctx_t *ctx, mpa_idx_s *mi, const SpansParams &p, const 
 	HIP_TRY(hipSetDevice(ctx->device));
 	if (dev_upload_index(ctx, mi) != MPA_OK) return MPA_ERR_HIP;
 	const DeviceIndex *d = mi->dev[ctx->device];
-	const SpansLayout L(n_plan, n_seg, n_rst1, text_bytes);
+	const SpansLayout L(n_plan, n_seg, n_rst1, text_bytes, spans_blocks(n_plan));
 	if (L.up_bytes > ctx->spans.h_sp_up.cap || L.down_bytes > ctx->spans.h_sp_down.cap) { set_error("dev_spans_round1: the staging block was not sized for this call"); return MPA_ERR_ARG; }
 	if (n_pool1 < 0 || (!pool1 && n_pool1 > 0 && (size_t)n_pool1 * 4 > ctx->round.cigd.cap)) { set_error("dev_spans_round1: no round-1 CIGAR pool of that size on this context"); return MPA_ERR_ARG; }
 	tl_alloc_failed = false;
@@ -199,35 +141,36 @@ int dev_spans_round1(mpa_ctx_t *ctx, mpa_idx_s *mi, const SpansParams &p, const 
 		return tl_alloc_failed ? MPA_ERR_UNSUPPORTED : MPA_ERR_HIP;
 	hipStream_t s = ctx->stream;
 	char *hu = ctx->spans.h_sp_up.as<char>();
-	aln_tables_fill((uint8_t*)hu, mat, (size_t)(p.asize * p.asize));
+	aln_tables_fill(L.tabs.in(hu), mat, (size_t)(p.asize * p.asize));
 	HIP_TRY(hipMemcpyAsync(ctx->spans.sp_in.p, hu, L.up_bytes - 16, hipMemcpyHostToDevice, s));
 	// the round-1 pool stays: round 2 overwrites cigd
 	if (n_pool1 > 0) HIP_TRY(hipMemcpyAsync(ctx->spans.sp_pool1.p, pool1 ? (const void*)pool1 : ctx->round.cigd.p, (size_t)n_pool1 * 4, pool1 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
 	const char *din = ctx->spans.sp_in.as<char>();
 	char *mid = ctx->spans.sp_mid.as<char>(), *dout = ctx->spans.sp_out.as<char>();
 	SpansArgs a;
-	a.plan = (const SpansPlan*)(din + L.off_plan), a.n_plan = (int32_t)n_plan, a.rst1 = (const mpa_dp_rst_t*)(din + L.off_rst1);
-	a.text = (const uint8_t*)(din + L.off_text), a.tabs = (const uint8_t*)din, a.seq = (const uint8_t*)d->seq, a.ctg_off = d->ctg_off, a.ctg_len = d->ctg_len;
-	a.p = p, a.rec = (SpanRec*)mid, a.tmp = (mpa_dp_task_t*)(mid + L.off_tmp), a.excl = (int32_t*)(mid + L.off_excl), a.bsum = (int32_t*)(mid + L.off_bsum);
-	hipLaunchKernelGGL(k_spans, dim3(L.blocks), dim3(SPANS_BLOCK), 0, s, a);
+	a.plan = L.plan.in(din), a.n_plan = (int32_t)n_plan, a.rst1 = L.rst1.in(din);
+	a.text = (const uint8_t*)L.text.in(din), a.tabs = L.tabs.in(din), a.seq = (const uint8_t*)d->seq, a.ctg_off = d->ctg_off, a.ctg_len = d->ctg_len;
+	a.p = p, a.rec = L.mid_rec.in(mid), a.tmp = L.tmp.in(mid), a.excl = L.excl.in(mid), a.bsum = L.bsum.in(mid);
+	const dim3 grid((unsigned)L.bsum.n);
+	hipLaunchKernelGGL(k_spans, grid, dim3(SPANS_BLOCK), 0, s, a);
 	HIP_TRY(hipGetLastError());
-	hipLaunchKernelGGL(k_spans_emit, dim3(L.blocks), dim3(SPANS_BLOCK), 0, s, a, (int32_t*)dout, (SpanRec*)(dout + L.off_rec), (mpa_dp_task_t*)(dout + L.off_task));
+	hipLaunchKernelGGL(k_spans_emit, grid, dim3(SPANS_BLOCK), 0, s, a, L.n_task.in(dout), L.rec.in(dout), L.task.in(dout));
 	HIP_TRY(hipGetLastError());
 	const bool want_r2 = round2_knob();                  // (MPA_GPU_ROUND2=1) the bounds of the tasks just written, for the planner of round 2
 	if (want_r2) {
-		HIP_TRY(hipMemsetAsync(dout + 8, 0, 24, s));
-		hipLaunchKernelGGL(k_task_bounds, dim3((unsigned)((2 * n_plan + SPANS_BLOCK - 1) / SPANS_BLOCK)), dim3(SPANS_BLOCK), 0, s, (const mpa_dp_task_t*)(dout + L.off_task), (const int32_t*)dout,
-		                   (int64_t*)(dout + 8));
+		HIP_TRY(hipMemsetAsync(L.bounds.in(dout), 0, L.bounds.bytes(), s));
+		hipLaunchKernelGGL(k_task_bounds, dim3((unsigned)((2 * n_plan + SPANS_BLOCK - 1) / SPANS_BLOCK)), dim3(SPANS_BLOCK), 0, s, (const mpa_dp_task_t*)L.task.in(dout), (const int32_t*)L.n_task.in(dout),
+		                   L.bounds.in(dout));
 		HIP_TRY(hipGetLastError());
 	}
-	char *hd = ctx->spans.h_sp_down.as<char>();
-	HIP_TRY(hipMemcpyAsync(hd, dout, L.down_bytes - 16, hipMemcpyDeviceToHost, s));
+	const char *hd = ctx->spans.h_sp_down.as<char>();
+	HIP_TRY(hipMemcpyAsync(ctx->spans.h_sp_down.p, dout, L.down_bytes - 16, hipMemcpyDeviceToHost, s));
 	HIP_TRY(wait_stream(ctx, s));
-	io.n_task = *(const int32_t*)hd, io.rec = (const SpanRec*)(hd + L.off_rec), io.task = (const mpa_dp_task_t*)(hd + L.off_task);
+	io.n_task = *L.n_task.in(hd), io.rec = L.rec.in(hd), io.task = L.task.in(hd);
 	io.r2 = DpResidentIn();
-	if (want_r2) { const int64_t *bd = (const int64_t*)(hd + 8); io.r2.d_tasks = (const mpa_dp_task_t*)(dout + L.off_task), io.r2.prep_bound = bd[0], io.r2.max_nl = bd[1], io.r2.max_al = bd[2]; }
+	if (want_r2) { const int64_t *bd = L.bounds.in(hd); io.r2.d_tasks = L.task.in(dout), io.r2.prep_bound = bd[0], io.r2.max_nl = bd[1], io.r2.max_al = bd[2]; }
 	if (io.n_task < 0 || io.n_task > 2 * n_plan) { set_error("dev_spans_round1: an impossible task count"); return MPA_ERR_HIP; }
-	ctx->spans.sp_keep.off_plan = L.off_plan, ctx->spans.sp_keep.off_seg = L.off_seg, ctx->spans.sp_keep.off_rst1 = L.off_rst1, ctx->spans.sp_keep.n_plan = n_plan, ctx->spans.sp_keep.n_pool1 = n_pool1;
+	ctx->spans.sp_keep = SpanBufs::SpansKeep{ L.plan, L.seg, L.rst1, L.rec, n_plan, n_pool1 };
 	return MPA_OK;
 }
 
@@ -239,7 +182,7 @@ int dev_spans_asm_stage(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, SpansAsm
 	const AsmLayout L(n_plan, n_rst2, 0);
 	if (ctx->spans.h_sp_up2.ensure(L.up_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
 	char *hu = ctx->spans.h_sp_up2.as<char>();
-	io.rst2 = (mpa_dp_rst_t*)hu, io.slot_off = (int64_t*)(hu + L.off_slot);
+	io.rst2 = L.rst2.in(hu), io.slot_off = L.slot.in(hu);
 	return MPA_OK;
 }
 
@@ -252,7 +195,8 @@ int dev_spans_assemble(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, const uin
 	if (n_pool2 < 0 || (!pool2 && n_pool2 > 0 && (size_t)n_pool2 * 4 > ctx->round.cigd.cap)) { set_error("dev_spans_assemble: no round-2 CIGAR pool of that size on this context"); return MPA_ERR_ARG; }
 	const int64_t n_words = io.slot_off[n_plan];
 	if (n_words < 0) { set_error("dev_spans_assemble: negative slot offsets"); return MPA_ERR_ARG; }
-	const size_t down_bytes = L.rec_bytes + (size_t)n_words * 4 + 16;
+	const Piece<uint32_t> h_cig = L.cigar((size_t)n_words);
+	const size_t down_bytes = h_cig.end() + 16;
 	if (ctx->spans.h_sp_down2.ensure(down_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
 	tl_alloc_failed = false;
 	if (ctx->spans.sp_in2.ensure(L.up_bytes) != MPA_OK || ctx->spans.sp_asm.ensure(L.rec_bytes + 16) != MPA_OK || ctx->spans.sp_cig.ensure((size_t)n_words * 4 + 16) != MPA_OK)
@@ -260,22 +204,23 @@ int dev_spans_assemble(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, const uin
 	hipStream_t s = ctx->stream;
 	char *din2 = ctx->spans.sp_in2.as<char>();
 	// (d_rst2: round 2's records are on the device already, where the round's own kernels wrote them -- only the slot offsets go up)
-	const size_t up_from = d_rst2 ? L0.off_slot : 0;
+	const size_t up_from = d_rst2 ? L0.slot.off : 0;
 	HIP_TRY(hipMemcpyAsync(din2 + up_from, ctx->spans.h_sp_up2.as<char>() + up_from, L0.up_bytes - 16 - up_from, hipMemcpyHostToDevice, s));
-	if (pool2 && n_pool2 > 0) HIP_TRY(hipMemcpyAsync(din2 + L.off_pool2, pool2, (size_t)n_pool2 * 4, hipMemcpyHostToDevice, s));
-	const char *din = ctx->spans.sp_in.as<char>();
+	if (pool2 && n_pool2 > 0) HIP_TRY(hipMemcpyAsync(L.pool2.in(din2), pool2, (size_t)n_pool2 * 4, hipMemcpyHostToDevice, s));
+	const char *din = ctx->spans.sp_in.as<char>(), *in2 = din2, *dout1 = ctx->spans.sp_out.as<char>();
 	AsmArgs a;
-	a.plan = (const SpansPlan*)(din + ctx->spans.sp_keep.off_plan), a.rec = (const SpanRec*)(ctx->spans.sp_out.as<char>() + SPANS_HEAD_BYTES), a.n_plan = (int32_t)n_plan;
-	a.gap = (const SegRec*)(din + ctx->spans.sp_keep.off_seg), a.rst1 = (const mpa_dp_rst_t*)(din + ctx->spans.sp_keep.off_rst1), a.rst2 = d_rst2 ? d_rst2 : (const mpa_dp_rst_t*)din2;
-	a.pool1 = ctx->spans.sp_pool1.as<uint32_t>(), a.pool2 = pool2 ? (const uint32_t*)(din2 + L.off_pool2) : ctx->round.cigd.as<uint32_t>();
-	a.slot_off = (const int64_t*)(din2 + L.off_slot), a.cig = ctx->spans.sp_cig.as<uint32_t>(), a.out = ctx->spans.sp_asm.as<AsmRec>();
+	const SpanBufs::SpansKeep &K = ctx->spans.sp_keep;       // (what dev_spans_round1 left in sp_in and sp_out)
+	a.plan = K.plan.in(din), a.rec = K.rec.in(dout1), a.n_plan = (int32_t)n_plan;
+	a.gap = K.seg.in(din), a.rst1 = K.rst1.in(din), a.rst2 = d_rst2 ? d_rst2 : L.rst2.in(in2);
+	a.pool1 = ctx->spans.sp_pool1.as<uint32_t>(), a.pool2 = pool2 ? L.pool2.in(in2) : ctx->round.cigd.as<uint32_t>();
+	a.slot_off = L.slot.in(in2), a.cig = ctx->spans.sp_cig.as<uint32_t>(), a.out = ctx->spans.sp_asm.as<AsmRec>();
 	hipLaunchKernelGGL(k_assemble, dim3((unsigned)((n_plan + STATS_WAVES - 1) / STATS_WAVES)), dim3(64 * STATS_WAVES), 0, s, a);
 	HIP_TRY(hipGetLastError());
 	char *hd = ctx->spans.h_sp_down2.as<char>();
-	HIP_TRY(hipMemcpyAsync(hd, ctx->spans.sp_asm.p, (size_t)n_plan * sizeof(AsmRec), hipMemcpyDeviceToHost, s));
-	if (n_words > 0) HIP_TRY(hipMemcpyAsync(hd + L.rec_bytes, ctx->spans.sp_cig.p, (size_t)n_words * 4, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(L.rec.in(hd), ctx->spans.sp_asm.p, L.rec.bytes(), hipMemcpyDeviceToHost, s));
+	if (n_words > 0) HIP_TRY(hipMemcpyAsync(h_cig.in(hd), ctx->spans.sp_cig.p, h_cig.bytes(), hipMemcpyDeviceToHost, s));
 	HIP_TRY(wait_stream(ctx, s));
-	io.rec = (const AsmRec*)hd, io.cigar = (const uint32_t*)(hd + L.rec_bytes);
+	io.rec = L.rec.in(hd), io.cigar = h_cig.in(hd);
 	return MPA_OK;
 }
 
@@ -287,12 +232,14 @@ int dev_task_bounds(mpa_ctx_t *ctx, const mpa_dp_task_t *d_tasks, int64_t n, DpR
 	HIP_TRY(hipSetDevice(ctx->device));
 	if (ctx->spans.sp_mid.ensure(64) != MPA_OK) return MPA_ERR_HIP;
 	hipStream_t s = ctx->stream;
-	int64_t h[4] = { 0, 0, 0, 0 };                       // bounds[3] | the count
-	*(int32_t*)(h + 3) = (int32_t)n;
+	Carve hc(8);                                         // bounds[3] | the count
+	const auto p_bounds = hc.take<int64_t>(3); const auto p_n = hc.take<int32_t>(1);
+	int64_t h[4] = { 0, 0, 0, 0 };
+	*p_n.in(h) = (int32_t)n;
 	HIP_TRY(hipMemcpyAsync(ctx->spans.sp_mid.p, h, sizeof h, hipMemcpyHostToDevice, s));
-	hipLaunchKernelGGL(k_task_bounds, dim3((unsigned)((n + SPANS_BLOCK - 1) / SPANS_BLOCK)), dim3(SPANS_BLOCK), 0, s, d_tasks, (const int32_t*)(ctx->spans.sp_mid.as<int64_t>() + 3), ctx->spans.sp_mid.as<int64_t>());
+	hipLaunchKernelGGL(k_task_bounds, dim3((unsigned)((n + SPANS_BLOCK - 1) / SPANS_BLOCK)), dim3(SPANS_BLOCK), 0, s, d_tasks, (const int32_t*)p_n.in(ctx->spans.sp_mid.p), p_bounds.in(ctx->spans.sp_mid.p));
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(h, ctx->spans.sp_mid.p, 24, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h, ctx->spans.sp_mid.p, p_bounds.bytes(), hipMemcpyDeviceToHost, s));
 	HIP_TRY(wait_stream(ctx, s));
 	out.d_tasks = d_tasks, out.prep_bound = h[0], out.max_nl = h[1], out.max_al = h[2];
 	return MPA_OK;
