@@ -61,6 +61,12 @@ int mpa_dbg_dp_last_classes(const mpa_ctx_t *ctx, int64_t ext_calls[16]);
 int mpa_dbg_dp_last_huge(const mpa_ctx_t *ctx, int64_t out[4]);
 void mpa_dbg_dp_huge_wg_info(int32_t out[3]);
 
+/* MPA_DP_MB_WG (traceback calls of more than 1 024 columns, class T_MB, swept by k_glob_mb_wg on the same schedule,
+ * whose constants are mpa_dbg_dp_huge_wg_info's).  mpa_dbg_dp_last_mb: of the context's last mpa_dp_run, over all its traceback chunks,
+ * out[0] the T_MB calls swept on one wave (in the round kernel or by k_glob_narrow), out[1] those swept on workgroups, out[2] the column
+ * blocks and out[3] the passes of the latter. */
+int mpa_dbg_dp_last_mb(const mpa_ctx_t *ctx, int64_t out[4]);
+
 /* A DP round from device-resident tasks (MPA_GPU_ROUND2): the arguments of mpa_dp_run.  On a context the hook
  * puts the tasks into a device pool, has their bounds reduced there (k_task_bounds), plans the round from the tasks in place, runs it
  * with the result records and the dense CIGAR pool assembled on the device in front of the round's one wait, and only then fetches the

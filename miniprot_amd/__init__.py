@@ -612,6 +612,18 @@ def dbg_dp_last_huge(ctx):
     return tuple(int(x) for x in out)
 
 
+def dbg_dp_last_mb(ctx):
+    """mpa_dbg_dp_last_mb(): of the context's last dp_run(), (T_MB traceback calls swept on one wave, T_MB calls swept by the workgroup
+    kernel of MPA_DP_MB_WG, column blocks of the latter, passes of the latter)."""
+    import numpy as np
+    out = np.zeros(4, np.int64)
+    f = dbg_lib().mpa_dbg_dp_last_mb
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_void_p]
+    _check(f(ctx.h, out.ctypes.data))
+    return tuple(int(x) for x in out)
+
+
 def dbg_dp_huge_wg_info():
     """mpa_dbg_dp_huge_wg_info(): (W waves per workgroup, R rows per chunk, MIN_BLOCKS) of the workgroup kernel's schedule."""
     import numpy as np

@@ -9,7 +9,8 @@
 //      (MPA_DP_POOL=1: the units go to the resident workers of the device's pool, k_dp_worker, instead),
 //   3. next to it on side streams: k_ext_huge (MPA_DP_HUGE_WG=1: and k_ext_huge_wg, one wave per column block, for the calls of four
 //      blocks or more) + k_ext_replay (wider calls, and whatever the int16 sweeps may not take), k_lite_wide
-//      (129..256-column checkpointed calls), the 512/1024-thread traceback classes, the anti-diagonal prototype,
+//      (129..256-column checkpointed calls), the 512/1024-thread traceback classes, the anti-diagonal prototype, and (MPA_DP_MB_WG=1)
+//      k_glob_mb_wg, one wave per column block, over the T_MB traceback calls, whose units in the round then find no call,
 //   4. k_backtrack per traceback chunk (chunks after the first: stand-alone k_glob_* launches, serial), k_walk for the
 //      checkpointed calls, one download, one host wait, k_cigar_gather (MPA_GPU_ROUND2=1, a batch's round 2 from tasks that are on the
 //      device: the result records and the dense pool's offsets by the kernels of dp_results_kernels.hip and the gather in front of
@@ -274,6 +275,7 @@ struct DpRun {
 	bool pool_pending = false;                  // (worker pool) a round is armed and not yet known to be complete ...
 	unsigned int pool_gen = 0;                  // ... its generation
 	int64_t pool_n = 0;                         // words of the dense CIGAR pool
+	bool mb_wg = false;                         // (MPA_DP_MB_WG, not with the worker pool) the T_MB traceback calls on k_glob_mb_wg, next to the round
 	float ms_glob = 0, ms_bt = 0;
 	bool glob_timed = false;                    // ev[3..5] hold a chunk's sweep and walk not yet added to ms_glob / ms_bt
 	double t_mark = 0;
@@ -543,13 +545,22 @@ static int dp_round(DpRun &R, GlobWave *d_gw, const char *what)
 }
 
 // one stand-alone launch of a chunk's plain traceback sweep: T_16, T_32, T_64 and T_MB share one ("narrow", cls < 0), every wide class has its own
-static hipError_t launch_glob_class(DpRun &R, const DpTbChunk &r, GlobWave *d_gw, int cls, hipStream_t st)
+// (MPA_DP_MB_WG: T_MB leaves the narrow launch and, cls == T_MB, has k_glob_mb_wg over the tail of the chunk's call list d_list)
+static hipError_t launch_glob_class(DpRun &R, const DpTbChunk &r, GlobWave *d_gw, const int32_t *d_list, int cls, hipStream_t st)
 {
 	GlobArgs &ga = R.ga;
 	const bool wide_ge = R.plan.wide_ge;
+	if (cls == T_MB) {
+		const unsigned n_mb = (unsigned)r.cls[T_MB].cnt;
+		const int32_t *mbl = d_list + (r.n_list - n_mb);
+		if (wide_ge) hipLaunchKernelGGL(k_glob_mb_wg<true>, dim3(n_mb), dim3(hwg::W * 64), 0, st, ga, mbl);
+		else hipLaunchKernelGGL(k_glob_mb_wg<false>, dim3(n_mb), dim3(hwg::W * 64), 0, st, ga, mbl);
+		return hipGetLastError();
+	}
 	if (cls < 0) {
 		int first[8], cnt[8];
 		for (int c = 0; c < 8; ++c) first[c] = r.cls[c].first, cnt[c] = r.cls[c].cnt;
+		if (R.mb_wg) cnt[T_MB] = 0;                                        // (k_glob_mb_wg's, above)
 		ga.waves = d_gw;
 		return launch_glob_narrow(ga, first, cnt, st, wide_ge);
 	}
@@ -580,9 +591,22 @@ static int dp_tb_chunks(DpRun &R)
 		}
 		int32_t *d_list = ctx->round.list.as<int32_t>();
 		GlobWave *d_gw = round_list_waves(ctx, P.cnt.n);
+		const bool in_round = ri == 0 && P.round_has_glob;
+		// the chunk's T_MB calls: one per wave, the last class of the chunk's waves and so the tail of its call list.  MPA_DP_MB_WG: they are
+		// k_glob_mb_wg's (a device plan with such a call was declined: dev_dp_plan)
+		const int n_mb = r.cls[T_MB].cnt, n_mb_wg = R.mb_wg ? n_mb : 0;
+		ctx->last_mb[0] += n_mb - n_mb_wg, ctx->last_mb[1] += n_mb_wg;
+		for (int k = 0; k < n_mb_wg; ++k) {
+			const int32_t nblk = hwg::n_blocks(P.tasks[r.list[r.n_list - n_mb_wg + k]].ncol);
+			ctx->last_mb[2] += nblk, ctx->last_mb[3] += hwg::n_pass(nblk);
+		}
 		if (!P.on_device) {
 			memcpy(hup + P.up.list, r.list.data(), r.n_list * 4);
 			memcpy(hup + P.up.gw, r.waves.data(), r.n_waves * sizeof(GlobWave));
+			// in the round their U_GLOB_MB units stay (the plan and k_dp_round are what they are without the knob) and find no call:
+			// glob_narrow returns at once for an empty wave of no rows, having written nothing
+			if (in_round)
+				for (int k = 0; k < n_mb_wg; ++k) { GlobWave &g = ((GlobWave*)(hup + P.up.gw))[r.cls[T_MB].first + k]; g.task[0] = -1, g.max_nl = 0; }
 			HIP_TRY(hipMemcpyAsync(d_list, hup + P.up.list, r.n_list * 4, hipMemcpyHostToDevice, s));
 			HIP_TRY(hipMemcpyAsync(d_gw, hup + P.up.gw, r.n_waves * sizeof(GlobWave), hipMemcpyHostToDevice, s));
 		}
@@ -592,16 +616,16 @@ static int dp_tb_chunks(DpRun &R)
 		// every launch on its own stream (next to the extension classes in the first chunk); the walk needs them all
 		HIP_TRY(hipEventRecord(ctx->fork_ev, s));
 		const size_t first_glob_launch = R.launches.size();
-		const bool in_round = ri == 0 && P.round_has_glob;
-		const int order[5] = { T_W16, T_W8, T_W4, T_W2, -1 };
+		const int order[6] = { T_MB, T_W16, T_W8, T_W4, T_W2, -1 };      // (T_MB: k_glob_mb_wg over the chunk's T_MB calls, the longest of these launches)
 		for (int cls : order) {
-			if (in_round && cls < T_W8) continue;                            // (only the 512/1024-thread traceback classes keep their own launch)
-			if (cls >= 0 ? !r.cls[cls].cnt : !(r.cls[T_16].cnt + r.cls[T_32].cnt + r.cls[T_64].cnt + r.cls[T_MB].cnt)) continue;
+			if (in_round && cls < T_W8) continue;                            // (only the 512/1024-thread traceback classes and k_glob_mb_wg keep their own launch)
+			const int cnt = cls == T_MB ? n_mb_wg : cls >= 0 ? r.cls[cls].cnt : r.cls[T_16].cnt + r.cls[T_32].cnt + r.cls[T_64].cnt + n_mb - n_mb_wg;
+			if (!cnt) continue;
 			if ((int)R.launches.size() >= mpa_ctx_s::kSide - 1) {            // out of side streams (the last event pair times the round's launch): main stream
-				HIP_TRY(launch_glob_class(R, r, d_gw, cls, s));
+				HIP_TRY(launch_glob_class(R, r, d_gw, d_list, cls, s));
 			} else {
 				hipStream_t st = begin_side(R, false);
-				HIP_TRY(launch_glob_class(R, r, d_gw, cls, st));
+				HIP_TRY(launch_glob_class(R, r, d_gw, d_list, cls, st));
 				end_side(R);
 			}
 			ctx->stats.launches_glob++;
@@ -619,6 +643,9 @@ static int dp_tb_chunks(DpRun &R)
 		R.glob_timed = true;                                              // (ev[3..5] are read after the next wait)
 	}
 	if (!R.round_launched && (rc = dp_round(R, nullptr, "    dp: (round without traceback launched)")) != MPA_OK) return rc;
+	const int64_t *lm = ctx->last_mb;                                   // (zero: mpa_dp_run_impl)
+	if (timing_on() && lm[0] + lm[1] > 0)
+		fprintf(stderr, "[mpa-timing]   dp: block-major traceback calls: %lld on one wave, %lld on workgroups (%lld blocks, %lld passes)\n", (long long)lm[0], (long long)lm[1], (long long)lm[2], (long long)lm[3]);
 	return MPA_OK;
 }
 
@@ -802,6 +829,9 @@ static void dp_statistics(DpRun &R)
 	t.cells_ext_round += st.cells_ext_round, t.cells_glob_round += st.cells_glob_round, t.ms_round += st.ms_round, t.launches_round += st.launches_round;
 }
 
+// MPA_DP_MB_WG as the executor applies it: off with the worker pool, like MPA_DP_LITE_WIDE and MPA_DP_SPLIT_WIDE
+static bool dp_mb_wg(const mpa_ctx_t *ctx) { return ctx->knobs.mb_wg && !dp_pool_enabled(); }
+
 // the executor's knobs as the planner takes them (the environment: read when the context was created, or once per process)
 static DpPlanKnobs dp_plan_knobs(const mpa_ctx_t *ctx)
 {
@@ -899,6 +929,12 @@ static int dev_dp_plan(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *o
 	int rc = dev_dp_plan_run(ctx, ctx->stream, mi->dev[ctx->device]->ctg_len, nullptr, (int32_t)mi->ctg.size(), q, opt, kn, n, in, &head, &gids, bytes_up, bytes_down, rz);
 	if (rc != MPA_OK) return rc;
 	if ((rc = dp_plan_from_head(*head, gids, q, opt, kn, sizeof(DpRoundArgs), plan))) set_error("device DP plan: " + plan.err);
+	// MPA_DP_MB_WG: k_glob_mb_wg's calls leave the round through the host's copy of the chunk's descriptors, which a device plan does not have
+	else if (dp_mb_wg(ctx) && !plan.chunks.empty() && plan.chunks[0].cls[T_MB].cnt > 0) {
+		plan = DpPlan();
+		set_error("device DP plan: a block-major traceback call (T_MB) with MPA_DP_MB_WG");
+		rc = MPA_ERR_UNSUPPORTED;
+	}
 	return rc;
 }
 // MPA_GPU_DPPLAN, read per call
@@ -957,11 +993,13 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 	}
 	memcpy(ctx->last_ext_calls, plan.ext_calls, sizeof(ctx->last_ext_calls));
 	memset(ctx->last_huge, 0, sizeof(ctx->last_huge));
+	memset(ctx->last_mb, 0, sizeof(ctx->last_mb));
 	if (timing_on() && plan.ext_wide[0].cnt + plan.ext_wide[1].cnt > 0)
 		fprintf(stderr, "[mpa-timing]   dp: %d + %d groups of the 2048- / 3072-column extension classes (8 / 12 workgroups each), %lld boundaries\n", plan.ext_wide[0].cnt, plan.ext_wide[1].cnt, (long long)plan.n_bound);
 	DpRun R{ ctx, ctx->stream, plan, kn, in };
 	R.t_mark = now_ms();
 	R.rz = rz;
+	R.mb_wg = dp_mb_wg(ctx) && !plan.on_device;                 // (a device plan with a T_MB call was declined under the knob: dev_dp_plan)
 	const int64_t waits1 = ctx->n_waits;
 	rc = dp_size_pools(R);                                      // 2. pools and staging
 	if (rc && rz) { tl_alloc_failed = false; return MPA_ERR_UNSUPPORTED; }   // (resident: a pool or pinned block that cannot grow declines, before anything of the round is launched)
@@ -1072,6 +1110,7 @@ namespace mpa {
 size_t dp_round_args_bytes() { return sizeof(DpRoundArgs); }
 void dp_last_ext_calls(const mpa_ctx_t *ctx, int64_t ext_calls[16]) { memcpy(ext_calls, ctx->last_ext_calls, sizeof(ctx->last_ext_calls)); }
 void dp_last_huge(const mpa_ctx_t *ctx, int64_t out[4]) { memcpy(out, ctx->last_huge, sizeof(ctx->last_huge)); }
+void dp_last_mb(const mpa_ctx_t *ctx, int64_t out[4]) { memcpy(out, ctx->last_mb, sizeof(ctx->last_mb)); }
 // mpa_dbg_dp_plan_device on a context (dpplan_dbg.cpp): the device planner on a task table, then every section it left in the pools
 // downloaded into a plan's vectors and serialised as mpa_dbg_dp_plan does.  1: declined (the last error says why).
 int64_t dev_dp_plan_dbg(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, const mpa_qbatch_t *q, int64_t n, const mpa_dp_task_t *in,

@@ -1,8 +1,8 @@
 // dp_huge_kernels.hip -- the X_HUGE extension calls (wider than 1024 columns, and whatever the int16 sweeps may not take), swept in
 // int32 in 64-column blocks: k_ext_huge (one wave per call, the blocks one after the other), k_ext_huge_wg / ext_huge_wg_body (one
 // wave per column block, MPA_DP_HUGE_WG=1; schedule and LDS layout in ext_huge_wg_core.h) and k_ext_replay (best row and x-drop
-// replayed over the per-row keys either sweep leaves).  Launched by dp_exec.hip on a side stream of the round; none of this code runs
-// inside k_dp_round or k_dp_worker.
+// replayed over the per-row keys either sweep leaves); and k_glob_mb_wg, the workgroup schedule under the row of a traceback call of class T_MB
+// (MPA_DP_MB_WG=1).  Launched by dp_exec.hip on a side stream of the round; none of this code runs inside k_dp_round or k_dp_worker.
 // Included by dp_exec.hip behind dp_kernels.hip.  Relies on dp_kernels.hip for: WavePos / whole_block, wave_sync, lds_barrier, GlobArgs,
 // GlobState / glob_state_init / glob_cands, glob_narrow<64, true, true, WIDE> (k_ext_huge IS that body as a launch; ext_huge_wg_body
 // repeats its row operation for operation), GLOB_NARROW_LDS, SEG_BIG, the int32 scans and imax.
@@ -35,8 +35,11 @@ __global__ __launch_bounds__(64) void k_ext_huge(GlobArgs a, int32_t wg_min_bloc
 static_assert(hwg::WAVE_LDS == GLOB_NARROW_LDS, "ext_huge_wg_core.h: a wave's LDS area is the one-wave kernel's");
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) v4i *lds_v4p;
-template<bool WIDE>
-__device__ __forceinline__ void ext_huge_wg_body(const GlobArgs &a, const DTask &t, char *lds, const int lane, const int w)
+// EXT = false (MPA_DP_MB_WG, k_glob_mb_wg below): the same schedule under the row of a traceback call of class T_MB, which is
+// glob_narrow<64, true, false, WIDE>'s: no per-row key; one direction word per live cell at tb[i * ncol + column], where k_backtrack
+// reads it, and H of the last row at column al - 1 as the call's score (tid: the call, for that store).
+template<bool WIDE, bool EXT = true>
+__device__ __forceinline__ void ext_huge_wg_body(const GlobArgs &a, const DTask &t, char *lds, const int lane, const int w, const int32_t tid = -1)
 {
 	constexpr int G = 64;
 	int16_t *lds_prof = (int16_t*)(lds + hwg::wave_area(w));    // [22][64] for the wave's column block
@@ -46,7 +49,8 @@ __device__ __forceinline__ void ext_huge_wg_body(const GlobArgs &a, const DTask 
 	const int32_t nblk = hwg::n_blocks(ncol), npass = hwg::n_pass(nblk), nstep = hwg::n_step(nl);
 	const int32_t go = c.go, ge = c.ge, goe = (int16_t)(c.go + c.ge), io = t.io, fs = c.fs;
 	const uint32_t *rec = a.rec + t.rec_off;
-	unsigned long long *rowkey = a.rowkey64 + t.tb_off;
+	unsigned long long *rowkey = EXT ? a.rowkey64 + t.tb_off : nullptr;
+	uint16_t *tb = EXT ? nullptr : a.tb + t.tb_off;
 	int4 *bnd = a.bnd + t.bnd_off;
 	const uint32_t go_s = splat16(go), io_s = splat16(io), fs_s = splat16(fs), ge_s = splat16(ge);
 	const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
@@ -90,6 +94,7 @@ __device__ __forceinline__ void ext_huge_wg_body(const GlobArgs &a, const DTask 
 		uint32_t r[3];                                          // records of rows i, i+1 (and, once fetched, i+2) at slot row mod 3
 		r[2] = have ? ring[2] : 0u, r[0] = have ? ring[3] : 0u, r[1] = 0;
 		const bool carry_src = seg_start && gc >= slen;         // lanes that feed the carry scan
+		int32_t hfin = NEG16;                                   // (!EXT) H of the last row
 
 		// LDS addresses (explicit address space: ds_read_b128 / ds_write_b128, never a flat access that would have to pick its path
 		// at run time) of the chunk's records in the left neighbour's ring, for the chunk's first row, and of this wave's own
@@ -121,18 +126,27 @@ __device__ __forceinline__ void ext_huge_wg_body(const GlobArgs &a, const DTask 
 			const int32_t hl_raw = shift1_i32<G>(h1, first_blk ? NEG16 : h1b, lane);
 			const int32_t il_raw = shift1_i32<G>(I1, first_blk ? NEG16 : I1b, lane);
 			const int32_t dI = seg_start ? 0 : s_sub(hl_raw, go) - il_raw;
-			(void)dI;
 			const int32_t E = imax(s_sub(hl_raw, goe), s_sub(il_raw, ge));
 			const int32_t z = carry_src ? E + cge : NEG32;
 			int32_t pz = scan_max_i32<G>(z);
 			pz = imax(pz, bin.y);
 			const int32_t Gc = imax(pz - cge, NEG16);
 			const int32_t h = imax(h1, Gc);
-			// key of this block's row: best (H + end bonus) among the live columns, ties to the smallest column
-			const int32_t hb = h + (gc == t.al - 1 ? c.end_bonus : 0);
-			const uint32_t kk = reduce_max_u32(live ? ((uint32_t)(imax(hb, NEG16) + 32768) << 6) | (63u - (uint32_t)lane) : 0u);
-			if (lane == 63 && kk != 0)
-				atomicMax(&rowkey[i], (unsigned long long)(kk >> 6) << 32 | (0xffffffffu - (uint32_t)(blk * 64 + 63 - (int32_t)(kk & 63))));
+			if (!EXT) {
+				// bits 9..4 of the direction word: Gc > h1 | C | B | A | D | il > hl - go; bits 3..0: the state
+				if (live) {
+					const uint32_t dw = push_neg(push_neg(push_neg(push_neg(push_neg((uint32_t)(h1 - Gc) >> 31, dC), dB), dA), dD), (uint32_t)dI);
+					tb[(int64_t)i * ncol + gc] = (uint16_t)((dw << 4) | (uint32_t)(15 - (kbest & 15)));
+				}
+				hfin = h;
+			} else {
+				(void)dI;
+				// key of this block's row: best (H + end bonus) among the live columns, ties to the smallest column
+				const int32_t hb = h + (gc == t.al - 1 ? c.end_bonus : 0);
+				const uint32_t kk = reduce_max_u32(live ? ((uint32_t)(imax(hb, NEG16) + 32768) << 6) | (63u - (uint32_t)lane) : 0u);
+				if (lane == 63 && kk != 0)
+					atomicMax(&rowkey[i], (unsigned long long)(kk >> 6) << 32 | (0xffffffffu - (uint32_t)(blk * 64 + 63 - (int32_t)(kk & 63))));
+			}
 			// boundary record for the block to the right
 			if (col == G - 1) {
 				const int4 out = make_int4(py_tot, pz, (int)pack16(h, h1), I1);
@@ -159,6 +173,7 @@ __device__ __forceinline__ void ext_huge_wg_body(const GlobArgs &a, const DTask 
 			}
 			lds_barrier();
 		}
+		if (!EXT && have && nl >= 3 && gc == t.al - 1) a.score[tid] = hfin;
 	}
 }
 template<bool WIDE>
@@ -170,6 +185,20 @@ __global__ __launch_bounds__(hwg::W * 64) void k_ext_huge_wg(GlobArgs a)
 	const DTask t = a.tasks[tid];
 	if (!hwg::takes_wg(t.ncol)) return;                             // (uniform over the workgroup, before its first barrier)
 	ext_huge_wg_body<WIDE>(a, t, lds, (int)(threadIdx.x & 63), __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)));
+}
+
+// MPA_DP_MB_WG: the traceback calls of class T_MB (more than 1024 columns, so 17 column blocks or more: hwg::takes_wg holds for every
+// one) swept like that instead of by glob_narrow<64, true> on one wave: one workgroup per call of list[0, gridDim.x), the T_MB calls of
+// a traceback chunk (the tail of the chunk's call list, which k_backtrack walks).  Launched by dp_exec.hip next to the round or, for
+// later chunks, next to k_glob_narrow.
+template<bool WIDE>
+__global__ __launch_bounds__(hwg::W * 64) void k_glob_mb_wg(GlobArgs a, const int32_t *list)
+{
+	__shared__ __attribute__((aligned(16))) char lds[hwg::LDS_BYTES];
+	const int32_t tid = list[blockIdx.x];
+	const DTask t = a.tasks[tid];
+	if (t.nl < 3) { if (threadIdx.x == 0) a.score[tid] = NEG16; return; }   // no row to sweep: no step, no barrier (uniform over the workgroup); as glob_narrow writes it
+	ext_huge_wg_body<WIDE, false>(a, t, lds, (int)(threadIdx.x & 63), __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), tid);
 }
 
 // nasw-sse.c:423-443 replayed over per-row keys ((row max + 32768) << 32 | ~column): best row under the length penalty,

@@ -6,7 +6,7 @@
 //   dp_kernels.hip            the round: sections below
 //   dp_prep_kernels.hip       k_prep_rows, k_prep_prof (per-row records, query profiles; DevTables)
 //   dp_lite_wide.hip          k_lite_wide / lite_wide_body (packed sweep of the checkpointed traceback, 129..256 columns)
-//   dp_huge_kernels.hip       k_ext_huge, k_ext_huge_wg, k_ext_replay (extension calls wider than 1024 columns, int32)
+//   dp_huge_kernels.hip       k_ext_huge, k_ext_huge_wg, k_ext_replay (extension calls wider than 1024 columns, int32), k_glob_mb_wg (traceback calls wider than that)
 //   dp_traceback_kernels.hip  k_glob_narrow / k_glob_wide (the bodies below as launches), k_backtrack, k_walk, k_cigar_gather
 // Sections of this file, in order:
 //   helpers          WavePos, packed int16 and DPP primitives, scans, votes

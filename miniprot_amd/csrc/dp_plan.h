@@ -104,6 +104,8 @@ size_t dp_round_args_bytes();            // the size of the worker pool's argume
 void dp_last_ext_calls(const mpa_ctx_t *ctx, int64_t ext_calls[16]);
 // ... and for mpa_dbg_dp_last_huge: the last mpa_dp_run's X_HUGE calls on the one-wave kernel, on the workgroup kernel, the latter's blocks and passes
 void dp_last_huge(const mpa_ctx_t *ctx, int64_t out[4]);
+// ... and for mpa_dbg_dp_last_mb: the last mpa_dp_run's T_MB traceback calls swept on one wave, on workgroups, the latter's blocks and passes
+void dp_last_mb(const mpa_ctx_t *ctx, int64_t out[4]);
 // the device planner on a context, what it left serialised like dp_plan_serialize; 1: it declined (the last error says why)
 int64_t dev_dp_plan_dbg(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, const mpa_qbatch_t *q, int64_t n, const mpa_dp_task_t *in,
                         const DpPlanKnobs &kn, void *buf, int64_t cap, bool wide = false);

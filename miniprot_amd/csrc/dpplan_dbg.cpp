@@ -77,6 +77,13 @@ extern "C" int mpa_dbg_dp_last_huge(const mpa_ctx_t *ctx, int64_t out[4])
 	return MPA_OK;
 }
 
+extern "C" int mpa_dbg_dp_last_mb(const mpa_ctx_t *ctx, int64_t out[4])
+{
+	if (!ctx || !out) { set_error("mpa_dbg_dp_last_mb: missing arguments"); return MPA_ERR_ARG; }
+	dp_last_mb(ctx, out);
+	return MPA_OK;
+}
+
 extern "C" void mpa_dbg_dp_huge_wg_info(int32_t out[3])
 {
 	if (out) out[0] = hwg::W, out[1] = hwg::R, out[2] = hwg::MIN_BLOCKS;

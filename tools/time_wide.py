@@ -7,7 +7,12 @@ the knob on (X_SPLIT8 / X_SPLIT12), the pair of legs `repeats` times (default 3)
 python tools/time_wide.py huge_wg [repeats]: the table of MPA_DP_HUGE_WG -- a pair of right-extension calls of 20 000 rows at 1 100, 1 500,
 2 000, 2 600, 3 300 and 6 800 columns with MPA_DP_SPLIT_WIDE unset (all X_HUGE), knob off (k_ext_huge, one wave per call) and knob on
 (k_ext_huge_wg, one wave per column block), interleaved; then ms_total of the mixed batch of the tests (tests/hugewg.py, mixed_table:
-X_HUGE calls of 4, W + 1 and 2 W + 1 blocks next to a round of 40 ordinary pairs), the same way."""
+X_HUGE calls of 4, W + 1 and 2 W + 1 blocks next to a round of 40 ordinary pairs), the same way.
+python tools/time_wide.py mb_wg [repeats]: the table of MPA_DP_MB_WG -- a pair of traceback calls (flag 1) of 20 000 rows at 1 100, 1 500,
+2 000, 2 600 and 3 300 columns (class T_MB), knob off (one wave per call, in the round kernel) and knob on (k_glob_mb_wg, one wave per
+column block), interleaved; the clock is ms_glob, the traceback sweeps of the batch; the two legs' records and CIGAR pools must agree.
+Then ms_total of the mixed batch of the tests (tests/mbwg.py, mixed_table: T_MB calls of 17, 33 and 49 blocks next to 40 ordinary
+pairs), the same way."""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, ROOT)
@@ -94,6 +99,64 @@ def huge_wg_table(repeats, nl=20000, n=2):
             print("%4d %28s %12.3f %12.3f %12.3f %12.3f" % (rep, huge[0] + "|" + huge[1], st[0]["ms_total"], st[1]["ms_total"], st[0]["ms_ext"], st[1]["ms_ext"]))
 
 
+def mb_wg_table(repeats, nl=20000, n=2):
+    rng = np.random.default_rng(1)
+    g = rng.integers(0, 4, nl * n + 1000).astype(np.uint8)
+    idx = mpa.Index.from_nt4([g], ["c"])
+    ctxs = {}
+    for knob in (0, 1):                                # the knob is read when a context is created
+        os.environ["MPA_DP_MB_WG"] = str(knob)
+        ctxs[knob] = mpa.Context(0)
+        idx.to_device(ctxs[knob])
+    dp = mpa.dpopt_from(mpa.default_mapopt())
+    W, R, _ = mpa.dbg_dp_huge_wg_info()
+    print("# (W, R) = (%d, %d)" % (W, R))
+    print("# ns per row of a pair of traceback calls, %d rows each: ms_glob, the batch's traceback sweeps (knob off: the round kernel with its two U_GLOB_MB waves;" % nl)
+    print("# knob on: the round kernel without them next to k_glob_mb_wg); per block / per pass: ns per row divided by the call's column blocks / passes; mb: mpa_dbg_dp_last_mb off|on")
+    print("%6s %4s %24s %12s %12s %8s %14s %14s" % ("al", "rep", "mb", "off ns/row", "on ns/row", "off/on", "off per block", "on per pass"))
+    for al in (1100, 1500, 2000, 2600, 3300):
+        aa = bytes(rng.choice(list(b"ACDEFGHIKLMNPQRSTVWY"), al * n).tolist())
+        q = mpa.Queries([aa[i * al:(i + 1) * al] for i in range(n)])
+        tasks = np.zeros(n, mpa.DP_TASK)
+        for i in range(n):
+            tasks[i]["nt_off"] = i * nl; tasks[i]["nl"] = nl; tasks[i]["qid"] = i; tasks[i]["al"] = al; tasks[i]["flag"] = 1; tasks[i]["io"] = 29
+        nblk = ((al + 7) // 8 * 8 + 63) // 64
+        for rep in range(repeats + 1):                 # (the first pair of legs warms both contexts up and is not printed)
+            ns, mb, out = {}, {}, {}
+            for knob in (0, 1):
+                rst, cig = mpa.dp_run(ctxs[knob], idx, dp, q, tasks)
+                out[knob] = ([tuple(r) for r in rst], np.asarray(cig).tobytes())
+                ns[knob] = ctxs[knob].dp_stats()["ms_glob"] * 1e6 / nl
+                mb[knob] = ",".join(str(x) for x in mpa.dbg_dp_last_mb(ctxs[knob]))
+            if out[0] != out[1]:
+                sys.exit("the two legs' records or CIGAR pools differ at %d columns" % al)
+            if rep:
+                print("%6d %4d %24s %12.1f %12.1f %8.2f %14.1f %14.1f" % (al, rep, mb[0] + "|" + mb[1], ns[0], ns[1], ns[0] / ns[1], ns[0] / nblk, ns[1] / ((nblk + W - 1) // W)))
+    idx.close()
+    # the mixed batch: does the 64 KB workgroup wait for the round's workgroups to leave a CU?
+    import mbwg
+    tab, want = mbwg.mixed_table()
+    idx = mpa.Index.from_nt4(tab.contigs)
+    for knob in (0, 1):
+        idx.to_device(ctxs[knob])
+    print("# the mixed batch (T_MB calls of %s blocks, %d calls in all): ms of the batch on the device, of its traceback sweeps, of the round" % (sorted(want), len(tab.tasks)))
+    print("%4s %24s %12s %12s %12s %12s %12s %12s" % ("rep", "mb", "off ms_total", "on ms_total", "off ms_glob", "on ms_glob", "off ms_round", "on ms_round"))
+    for rep in range(repeats + 1):
+        st, mb, out = {}, {}, {}
+        for knob in (0, 1):
+            rst, cig = mpa.dp_run(ctxs[knob], idx, tab.opt, tab.queries, tab.tasks)
+            out[knob] = ([tuple(r) for r in rst], np.asarray(cig).tobytes())
+            st[knob] = ctxs[knob].dp_stats()
+            mb[knob] = ",".join(str(x) for x in mpa.dbg_dp_last_mb(ctxs[knob]))
+        if out[0] != out[1]:
+            sys.exit("the two legs' records or CIGAR pools differ on the mixed batch")
+        if rep:
+            print("%4d %24s %12.3f %12.3f %12.3f %12.3f %12.3f %12.3f" % (rep, mb[0] + "|" + mb[1], st[0]["ms_total"], st[1]["ms_total"], st[0]["ms_glob"], st[1]["ms_glob"], st[0]["ms_round"], st[1]["ms_round"]))
+
+
+if sys.argv[1] == "mb_wg":
+    mb_wg_table(int(sys.argv[2]) if len(sys.argv) > 2 else 3)
+    sys.exit(0)
 if sys.argv[1] == "huge_wg":
     huge_wg_table(int(sys.argv[2]) if len(sys.argv) > 2 else 3)
     sys.exit(0)
