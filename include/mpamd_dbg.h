@@ -141,6 +141,37 @@ int mpa_dbg_chain_extract(mpa_ctx_t *ctx, int32_t max_dist_x, int32_t max_dist_y
                           float coef_log, int32_t is_spliced, int32_t kmer, int32_t bbit, int32_t n_prob, const int64_t *first, const uint64_t *a, int32_t mode,
                           int64_t *off_u, uint64_t *u, int64_t *off_a, uint64_t *a_out, int32_t *status, int64_t *rec);
 
+/* Ranking and flat result of a batch (MPA_GPU_FINISH; miniprot_amd/csrc/finish_core.h) on hand-made tables: the tail
+ * of mp_map() behind mp_align() -- mp_sort_reg, mp_select_multi_exon(opt->io), mp_set_parent(opt->mask_level, opt->mask_len, sub_diff = kmer)
+ * and mp_select_sub(opt->pri_ratio, 2 kmer, opt->best_n) -- per query, the exclusive prefix of the queries' counts, and the gather of every
+ * kept hit into the arrays of a result, laid out as mpa_batch_finish() lays them out.  On a context: k_finish_rank, k_finish_scan and
+ * k_finish_gather; ctx == NULL: the shared core on the host with a team of one.
+ * Query q's aligned regions are recs[first[q] .. first[q + 1]), first[0] = 0.  A record is 160 bytes: int64 vs, ve, first CIGAR word (in
+ * words), first feature (in feats), first byte of its cs body (in cs_text), first byte of its rows slot (in rows_text); uint32 vid, hash;
+ * int32 qs, qe, cnt, n_exon, chn_sc, chn_sc_ungap; parent, n_sub, subsc, dp_max2 (carried in); dp_score, dp_max, blen, n_fs, n_stop,
+ * dist_stop, dist_start, n_iden, n_plus; n_cigar, n_feat; cs_len (< 0: no cs body carried); rows width, STA bytes, stride (the slot holds
+ * four rows of `width` bytes `stride` apart and the STA bytes behind 4 stride; stride < 0: no rows carried); one word the hook ignores.
+ * Every index is checked first: MPA_ERR_ARG for records that point outside their arrays.  *out: the result (mpa_result_destroy), hits
+ * with qid = q; read its arrays with the accessors of mpamd.h or, as bytes, with mpa_dbg_result_flat.
+ * mpa_dbg_finish_last: of the context's last device call, the hook's or a batch's inside its walks' call -- [0] queries, [1] hits in, [2] hits kept, [3] bytes the kernels wrote into pinned host memory (the result at its real size), [4] queries of
+ * more than 64 regions (ranked in HBM scratch, not in LDS), [5] host waits of the call (a batch's: walks and finish together).
+ * mpa_dbg_result_flat: array `which` of any result as bytes into buf[cap]; returns its size in bytes (written when it fits).  The cs and
+ * rows references come field by field -- 16 bytes (int64 off; int32 len, present) and 24 bytes (int64 off; int32 width, n_sta, present,
+ * zero) per hit, or none at all when no hit carries one -- every other array as it lies in the result. */
+#define MPA_DBG_FINISH_REC 6
+#define MPA_DBG_FLAT_HITS 0
+#define MPA_DBG_FLAT_HIT_OFF 1
+#define MPA_DBG_FLAT_CIGARS 2
+#define MPA_DBG_FLAT_FEATS 3
+#define MPA_DBG_FLAT_CS 4
+#define MPA_DBG_FLAT_CS_TEXT 5
+#define MPA_DBG_FLAT_ROWS 6
+#define MPA_DBG_FLAT_ROWS_TEXT 7
+int mpa_dbg_finish(mpa_ctx_t *ctx, const mpa_mapopt_t *opt, int32_t kmer, int32_t n_query, const int64_t *first, const void *recs, const uint32_t *words, int64_t n_words,
+                   const mpa_feat_t *feats, int64_t n_feat, const char *cs_text, int64_t cs_bytes, const char *rows_text, int64_t rows_bytes, mpa_result_t **out);
+int mpa_dbg_finish_last(const mpa_ctx_t *ctx, int64_t out[MPA_DBG_FINISH_REC]);
+int64_t mpa_dbg_result_flat(const mpa_result_t *r, int32_t which, void *buf, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

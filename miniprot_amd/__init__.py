@@ -528,6 +528,59 @@ def dbg_spans(ctx, idx, mo, queries, plans, segs, rst1, pool1, rst2=None, pool2=
     return rec.tobytes(), tasks, arec.tobytes(), cig
 
 
+FLAT_ARRAYS = ("hits", "hit_off", "cigars", "feats", "cs", "cs_text", "rows", "rows_text")   # MPA_DBG_FLAT_* (include/mpamd_dbg.h), in order
+
+
+def result_flat(handle):
+    """mpa_dbg_result_flat(): the flat arrays of a result (a Result or a raw mpa_result_t handle) as a dict of bytes, keyed by FLAT_ARRAYS."""
+    f = dbg_lib().mpa_dbg_result_flat
+    f.restype = C.c_int64
+    f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
+    h = getattr(handle, "h", handle)
+    out = {}
+    for which, name in enumerate(FLAT_ARRAYS):
+        n = f(h, which, None, 0)
+        if n < 0:
+            raise MpaError("mpa_dbg_result_flat: %d: %s" % (n, last_error()))
+        buf = C.create_string_buffer(max(int(n), 1))
+        f(h, which, buf, n)
+        out[name] = buf.raw[:n]
+    return out
+
+
+def dbg_finish(ctx, mo, kmer, first, recs, words, feats, cs_text, rows_text):
+    """mpa_dbg_finish(): ranking and flat result (MPA_GPU_FINISH) of hand-made tables, on the device (ctx) or through the shared core on
+    the host (ctx None).  first (int64, n_query + 1), recs (160-byte records as a uint8 array), words (uint32), feats (56-byte records
+    as a uint8 array) are numpy arrays, cs_text / rows_text bytes, laid out as include/mpamd_dbg.h says.  Returns result_flat()'s dict."""
+    import numpy as np
+    f = dbg_lib().mpa_dbg_finish
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.POINTER(MapOpt), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_char_p, C.c_int64,
+                  C.c_char_p, C.c_int64, C.POINTER(C.c_void_p)]
+    first = np.ascontiguousarray(first, np.int64)
+    recs, words, feats = np.ascontiguousarray(recs, np.uint8), np.ascontiguousarray(words, np.uint32), np.ascontiguousarray(feats, np.uint8)
+    assert len(recs) == 160 * int(first[-1]) and len(feats) % 56 == 0
+    out = C.c_void_p(None)
+    _check(f(ctx.h if ctx else None, C.byref(mo), int(kmer), len(first) - 1, first.ctypes.data, recs.ctypes.data if len(recs) else None, words.ctypes.data if len(words) else None,
+             len(words), feats.ctypes.data if len(feats) else None, len(feats) // 56, cs_text if cs_text else None, len(cs_text), rows_text if rows_text else None, len(rows_text),
+             C.byref(out)))
+    try:
+        return result_flat(out.value)
+    finally:
+        lib().mpa_result_destroy(C.c_void_p(out.value))
+
+
+def dbg_finish_last(ctx):
+    """mpa_dbg_finish_last(): of the context's last device finish call, (queries, hits in, hits kept, bytes down, queries ranked in HBM
+    scratch, host waits)."""
+    f = dbg_lib().mpa_dbg_finish_last
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.POINTER(C.c_int64 * 6)]
+    out = (C.c_int64 * 6)()
+    _check(f(ctx.h, C.byref(out)))
+    return tuple(int(x) for x in out)
+
+
 DP_PLAN_DECLINED = 1   # MPA_DBG_DP_PLAN_DECLINED (include/mpamd_dbg.h)
 
 

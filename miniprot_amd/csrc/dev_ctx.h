@@ -197,6 +197,14 @@ struct PlannerBufs {
 	HostPinned h_dpp_up, h_dpp_down;          // ... its staging: one block up, one block down
 };
 
+// ranking and flat result of a batch (stats_run.hip, MPA_GPU_FINISH=1; FinishLayout): grow-only, allocated by the first call that asks for them
+struct FinishBufs {
+	PoolRegistry &reg;
+	CtxPool fin_in{ reg, "fin_in" }, fin_mid{ reg, "fin_mid" };   // what goes up; ranks, counts, their prefix and the large queries' scratch
+	HostPinned h_fin_up, h_fin_down;          // the block that goes up; the flat result, which k_finish_scan and k_finish_gather write directly
+	int64_t last[6] = { 0, 0, 0, 0, 0, 0 };   // of the last call: queries, hits in, hits kept, bytes down, queries ranked in HBM scratch, host waits (mpa_dbg_finish_last)
+};
+
 // What the environment says about every context of a pipeline: filled once for a root (ctx_knobs_from_env), handed to a sibling by
 // one assignment, read by dp_plan_knobs().  A new knob is a field here and a line there.
 struct CtxKnobs {
@@ -242,6 +250,7 @@ struct mpa_ctx_s {
 	WalkBufs walks{ pools };
 	SpanBufs spans{ pools };
 	PlannerBufs planner{ pools };
+	FinishBufs finish{ pools };
 	// ---- what the DP rounds of this context did
 	mpa_dp_stats_t stats = {};
 	mpa_dp_stats_t total = {};

@@ -126,6 +126,30 @@ struct AsmLayout {
 };
 static_assert(sizeof(SpansPlan) % 8 == 0 && sizeof(SpanRec) % 8 == 0 && sizeof(AsmRec) % 8 == 0, "records in 16-byte aligned sections");
 
+// ---- ranking and flat result of a batch (stats_run.hip, MPA_GPU_FINISH; 16-byte sections)
+// fin_in / h_fin_up: the queries' first records | the large queries' numbers | records | CIGAR words | features | cs text | rows text;
+// (behind the walks only the first three go up: the rest is read where the walks left it);
+// fin_mid: kept hits by rank | counts | their prefix | the scratch of the queries of more than FINISH_LDS_REGS regions (none: empty
+// pieces); h_fin_down: the prefix | hits | cs refs | rows refs | CIGAR words | features | cs text | rows text, every array dense from
+// its piece's start and with room for a batch that keeps every hit -- the kernels write it directly, so only what is kept travels
+struct FinishLayout {
+	Piece<int64_t> first; Piece<int32_t> big; Piece<FinRec> rec; Piece<uint32_t> words, cigars; Piece<mpa_feat_t> in_feat, feats; Piece<char> in_cs, in_rows, cs_text, rows_text;
+	Piece<FinOut> out; Piece<FinCounts> cnt, off, h_off; Piece<FinRank> tmp, r; Piece<Pair64> key; Piece<SortRange> stack; Piece<uint32_t> hist; Piece<int32_t> prim, ctl; Piece<uint64_t> cov;
+	Piece<mpa_hit_t> hits; Piece<FinCsRef> cs; Piece<FinRowsRef> rows;
+	size_t up_bytes, mid_bytes, down_bytes;
+	explicit FinishLayout(const FinishSizes &z) {
+		const size_t nq = (size_t)z.n_query, nr = (size_t)z.n_rec, nb = (size_t)z.n_big, sr = nb ? nr : 0;
+		Carve up(16), mid(16), dn(16);
+		first = up.take<int64_t>(nq + 1), big = up.take<int32_t>(nq), rec = up.take<FinRec>(nr), words = up.take<uint32_t>((size_t)z.in_words), in_feat = up.take<mpa_feat_t>((size_t)z.in_feat);
+		in_cs = up.take<char>((size_t)z.in_cs), in_rows = up.take<char>((size_t)z.in_rows), up_bytes = up.at + 16;
+		out = mid.take<FinOut>(nr), cnt = mid.take<FinCounts>(nq), off = mid.take<FinCounts>(nq + 1);
+		tmp = mid.take<FinRank>(sr), r = mid.take<FinRank>(sr), key = mid.take<Pair64>(sr), stack = mid.take<SortRange>(nb ? sr / 64 + 8 * nb + 8 : 0), hist = mid.take<uint32_t>(768 * nb);
+		prim = mid.take<int32_t>(sr), ctl = mid.take<int32_t>(2 * nb), cov = mid.take<uint64_t>(sr), mid_bytes = mid.at + 16;
+		h_off = dn.take<FinCounts>(nq + 1), hits = dn.take<mpa_hit_t>(nr), cs = dn.take<FinCsRef>(nr), rows = dn.take<FinRowsRef>(nr), cigars = dn.take<uint32_t>((size_t)z.out_words);
+		feats = dn.take<mpa_feat_t>((size_t)z.out_feat), cs_text = dn.take<char>((size_t)z.out_cs), rows_text = dn.take<char>((size_t)z.out_rows), down_bytes = dn.at + 16;
+	}
+};
+
 // ---- a resident round's results pool (dp_exec.hip; round.cigoff, 64-byte sections): off[n_glob] | call_off[n] | bsum[blocks + 1] |
 // head (64 bytes) | rst[n]; header and records come down in one copy
 struct ResLayout {

@@ -6,12 +6,14 @@
 //                         statistics, and with their knobs the cs strings and residue rows the formatter would otherwise build -- and
 //                         (c) the final ranking (stage_finish)
 // Steps (a) and (b) have a device twin and a model of it behind a knob each (MPA_GPU_SPANS, _STATS, _CS, _ROWS: StepMode of host_batch.h);
-// the walks that run on the device share one call (walks_on_device).  Everything but the two entry points is local to this file.
+// the walks that run on the device share one call (walks_on_device).  Step (c) and the flatten loop of mpa_batch_finish() have one behind
+// MPA_GPU_FINISH (host_finish.cpp, finish_core.h).  Everything but the two entry points is local to this file.
 #include <algorithm>
 #include <atomic>
 #include <cassert>
 #include <cstring>
 #include <mutex>
+#include <string>
 #include "host_batch.h"
 
 using namespace mpa;
@@ -367,8 +369,12 @@ static void rows_model(mpa_batch_s *b)
 // The walks over the finished alignments on the device in one call, for any of the statistics (`stats`), the cs strings (`cs_on`) and
 // the residue rows (`rows_on`): one upload, a launch each, one wait.  MPA_OK: done (*ran: there was something to do);
 // MPA_ERR_UNSUPPORTED: the device declined (the last error says why) and nothing was changed; anything else is an error of the call
-static int walks_on_device(mpa_batch_s *b, mpa_ctx_t *ctx, bool stats, bool cs_on, bool rows_on, bool *ran)
+// want_fin (MPA_GPU_FINISH=1, with stats): the ranking and the flat result run in the same call behind the walks' kernels (DESIGN.md section
+// 4.13): only the records' host-side fields go up next to the jobs, the walks' output is neither downloaded nor applied to the regions, and
+// b->flat is the batch's result.  *fin_why: why that part declined (the walks then ran as without it)
+static int walks_on_device(mpa_batch_s *b, mpa_ctx_t *ctx, bool stats, bool cs_on, bool rows_on, bool *ran, bool want_fin = false, std::string *fin_why = nullptr)
 {
+	const double t_call = now_ms();
 	const size_t nq = b->qs.size();
 	const AlnRowsParams rp = rows_params(b->opt);
 	std::vector<int64_t> job0(nq + 1, 0), cig0(nq + 1, 0), feat0(nq + 1, 0), slot0(nq + 1, 0), rslot0(nq + 1, 0);
@@ -407,6 +413,24 @@ static int walks_on_device(mpa_batch_s *b, mpa_ctx_t *ctx, bool stats, bool cs_o
 	if (text_bytes > 0) memcpy(io.text, b->q.seqs + t0, (size_t)text_bytes);
 	if (cs_on) cs.slot_off[n_jobs] = slot_bytes;
 	if (rows_on) rows.slot_off[n_jobs] = rows_bytes;
+	FinishResident fr;
+	FinishTables ft;
+	if (want_fin) {
+		// (a record per aligned region in the order of the query's regions, as stage_finish meets them; every one of them has a plan)
+		for (size_t qi = 0; qi < nq && want_fin; ++qi) {
+			int64_t n_aln = 0;
+			for (const Region &r : b->qs[qi].regs) n_aln += r.aligned;
+			if (n_aln != (int64_t)b->qs[qi].plans.size()) want_fin = false, *fin_why = "an aligned region without a plan";
+		}
+		fr.p = FinParams{ b->mi->opt.kmer, b->opt.mask_len, b->opt.best_n, b->opt.io, b->opt.mask_level, b->opt.pri_ratio };
+		fr.z = FinishSizes{ (int64_t)nq, n_jobs, finish_count_big(job0.data(), (int64_t)nq), 0, 0, 0, 0, n_cigar, feat0[nq], cs_on ? slot_bytes : 0, rows_on ? rows_bytes : 0 };
+		if (want_fin) {
+			rc = dev_finish_stage(ctx, fr.z, ft);
+			if (rc == MPA_ERR_UNSUPPORTED) want_fin = false, *fin_why = mpa_last_error();
+			else if (rc != MPA_OK) return rc;
+		}
+		if (want_fin) memcpy(ft.first, job0.data(), (nq + 1) * 8);
+	}
 	parallel_for(b->n_threads, (int64_t)nq, [&](int64_t qi) {
 		const QueryState &qs = b->qs[qi];
 		int64_t j = job0[qi], c = cig0[qi], f = feat0[qi], s = slot0[qi], rs = rslot0[qi];
@@ -415,14 +439,33 @@ static int walks_on_device(mpa_batch_s *b, mpa_ctx_t *ctx, bool stats, bool cs_o
 			if (cs_on) cs.slot_off[j] = s, s += aln_cs_bound(r.cigar.data(), (int32_t)r.cigar.size());
 			if (rows_on) rows.slot_off[j] = rs, rs += aln_rows_slot(r.cigar.data(), (int32_t)r.cigar.size(), rp);
 			io.jobs[j] = stats_job(qs, pl, r, (qs.seq - b->q.seqs) - t0, dev_cig ? b->sp_cig_off[(size_t)j] : c, f);
+			if (want_fin) {
+				int64_t at = job0[qi];                                  // (its place among the query's records: plans with a smaller region number)
+				for (const AlignPlan &o : qs.plans) at += o.reg < pl.reg;
+				FinRec &x = ft.rec[at];
+				memset(&x, 0, sizeof x);
+				x.vs = r.vs, x.ve = r.ve, x.cig_off = io.jobs[j].cig_off, x.feat_off = f, x.vid = r.vid, x.hash = r.hash, x.qs = r.qs, x.qe = r.qe, x.cnt = r.cnt, x.n_exon = r.n_exon;
+				x.chn_sc = r.chn_sc, x.chn_sc_ungap = r.chn_sc_ungap, x.parent = r.parent, x.n_sub = r.n_sub, x.subsc = r.subsc, x.dp_max2 = r.dp_max2, x.dp_score = r.dp_score;
+				x.n_cigar = (int32_t)r.cigar.size(), x.job = (int32_t)j, x.cs_len = -1, x.rows_stride = -1;      // (k_finish_fill: the statistics, cs_len, the rows' width)
+				if (cs_on) x.cs_off = cs.slot_off[j];
+				if (rows_on) x.rows_off = rows.slot_off[j], x.rows_stride = rp.show_aln ? (int32_t)(aln_rows_cols(r.cigar.data(), (int32_t)r.cigar.size(), rp.flank) + 3) : 0;
+			}
 			++j;
 			if (!dev_cig && !r.cigar.empty()) memcpy(io.cigar + c, r.cigar.data(), r.cigar.size() * 4);
 			c += (int64_t)r.cigar.size(), f += (int64_t)r.n_exon + 1;
 		}
 	});
-	rc = dev_aln_walks(ctx, const_cast<mpa_idx_s*>(b->mi), stats_params(b->opt), rp, b->opt.mat, z, io, cs, rows, dev_cig);
+	rc = dev_aln_walks(ctx, const_cast<mpa_idx_s*>(b->mi), stats_params(b->opt), rp, b->opt.mat, z, io, cs, rows, dev_cig, want_fin ? &fr : nullptr);
 	if (rc != MPA_OK) return rc;
 	if (timing_on() && dev_cig) fprintf(stderr, "[mpa-timing]   walks upload: %lld alignments, %lld CIGAR words (the assembled pool is on the device)\n", (long long)n_jobs, (long long)n_up);
+	if (want_fin) {                                      // the result is laid out: nothing to apply to the regions
+		std::unique_ptr<mpa_result_s> res(new mpa_result_s());
+		finish_flat_to_result(fr.flat, (int64_t)nq, res.get());
+		if (timing_on()) fprintf(stderr, "[mpa-timing]   finish on the GPU: %lld queries, %lld hits in, %lld kept, %lld bytes down, %.3f ms\n", (long long)nq, (long long)n_jobs,
+		                         (long long)res->hits.size(), (long long)fr.flat.bytes_down, now_ms() - t_call);
+		b->flat = std::move(res), b->flat_cs_src = cs_on ? 2 : 0;
+		return MPA_OK;
+	}
 	if (timing_on() && cs_on) {                          // what came down against what it held (the bounded slots: DESIGN.md section 4.8)
 		int64_t used = 0;
 		for (int64_t j = 0; j < n_jobs; ++j) used += cs.out[j].len;
@@ -459,6 +502,23 @@ static void cs_dump(const mpa_batch_s *b)
 	FILE *fp = fopen(fn, "ab");
 	if (!fp) return;
 	std::string body;
+	if (b->flat) {                                       // (MPA_GPU_FINISH ran: the ranked hits are the flat result's, the regions were left unranked)
+		const mpa_result_s &R = *b->flat;
+		for (size_t h = 0; h < R.hits.size(); ++h) {
+			const mpa_hit_t &x = R.hits[h];
+			const bool carried = !R.cs.empty() && R.cs[h].present;
+			const char *s = carried ? R.cs_text.data() + R.cs[h].off : nullptr;
+			int32_t len = carried ? R.cs[h].len : 0;
+			if (!carried) body.clear(), put_cs_body(body, b->mi, b->qs[(size_t)x.qid].seq + x.qs, (int32_t)x.vid, x.vs, x.ve, R.cigars.data() + x.cigar_off, x.n_cigar), s = body.data(), len = (int32_t)body.size();
+			const int32_t a[2] = { x.qid, (int32_t)x.vid };
+			const int64_t v[2] = { x.vs, x.ve };
+			const int32_t w[4] = { x.qs, x.qe, carried ? b->flat_cs_src : 0, len };
+			fwrite(a, 4, 2, fp), fwrite(v, 8, 2, fp), fwrite(w, 4, 4, fp);
+			if (len > 0) fwrite(s, 1, (size_t)len, fp);
+		}
+		fclose(fp);
+		return;
+	}
 	for (const QueryState &qs : b->qs)
 		for (const Region &r : qs.regs) {
 			if (!r.aligned) continue;
@@ -772,7 +832,9 @@ static int take_round3_steps(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint
 	const StepMode mode = batch_step_mode(b, "MPA_GPU_STATS");
 	const StepMode cs = cs_printed(b->opt) ? batch_step_mode(b, "MPA_GPU_CS") : STEP_HOST;
 	const StepMode rows = rows_printed(b->opt) ? batch_step_mode(b, "MPA_GPU_ROWS") : STEP_HOST;
-	if (mode == STEP_HOST && cs == STEP_HOST && rows == STEP_HOST && b->spans_src == 0 && !spans_dump_on()) {   // the three steps in one pass over the queries
+	const StepMode fin = (b->opt.flag & MPA_MF_NO_ALIGN) ? STEP_HOST : batch_step_mode(b, "MPA_GPU_FINISH");
+	b->flat.reset(), b->flat_cs_src = 0;
+	if (mode == STEP_HOST && cs == STEP_HOST && rows == STEP_HOST && fin == STEP_HOST && b->spans_src == 0 && !spans_dump_on()) {   // the three steps in one pass over the queries
 		parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
 			QueryState &qs = b->qs[qi];
 			for (AlignPlan &pl : qs.plans) {
@@ -826,18 +888,19 @@ static int take_round3_steps(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint
 		{ "cs strings", "cs strings on the GPU", "the formatter builds them" },
 		{ "residue rows", "residue rows on the GPU", "the formatter builds them" } };
 	const bool on_dev[3] = { mode == STEP_DEVICE, cs == STEP_DEVICE, rows == STEP_DEVICE };
-	bool stats_host = mode == STEP_HOST;
+	bool stats_host = mode == STEP_HOST, stats_dev_ok = on_dev[0];
+	std::string fin_why;
 	if (on_dev[0] || on_dev[1] || on_dev[2]) {
 		const double t0 = now_ms();
 		bool ran = false;
-		const int rc = walks_on_device(b, b->dp_ctx, on_dev[0], on_dev[1], on_dev[2], &ran);
+		const int rc = walks_on_device(b, b->dp_ctx, on_dev[0], on_dev[1], on_dev[2], &ran, fin == STEP_DEVICE && on_dev[0] && cs != STEP_MODEL && rows != STEP_MODEL, &fin_why);
 		if (rc != MPA_OK && rc != MPA_ERR_UNSUPPORTED) return rc;
 		for (int k = 0; k < 3; ++k) {
 			if (!on_dev[k]) continue;
 			if (rc == MPA_OK && ran) timing_note(kWalk[k].note, now_ms() - t0);      // (one call: the same span)
 			if (rc != MPA_OK && timing_on()) fprintf(stderr, "[mpa-timing]   device %s declined (%s): %s\n", kWalk[k].name, mpa_last_error(), kWalk[k].left);
 		}
-		if (rc != MPA_OK && on_dev[0]) stats_host = true;
+		if (rc != MPA_OK && on_dev[0]) stats_host = true, stats_dev_ok = false;
 	}
 	if (stats_host) parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
 		QueryState &qs = b->qs[qi];
@@ -853,6 +916,20 @@ static int take_round3_steps(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint
 	through_model(cs, cs_model, "cs strings: shared core");                // (b')
 	through_model(rows, rows_model, "residue rows: shared core");          // (b'')
 	spans_dump(b);
+	// (c) MPA_GPU_FINISH.  1: the step ran inside walks_on_device, behind the walks' kernels and in front of their
+	// one wait, and left b->flat -- it needs the statistics on the device in that call (dp_max is theirs, and so are the records it
+	// reads); declined, the ranking is stage_finish's, with the same result.  model: the shared core on the host (host_finish.cpp).
+	// (flat_cs_src is one value per batch: a batch's walks all take one path, so its carried cs bodies have one source)
+	if (b->flat) return MPA_OK;
+	if (fin == STEP_DEVICE) {
+		bool any = false;
+		for (const QueryState &qs : b->qs) any = any || !qs.plans.empty();
+		const char *why = mode != STEP_DEVICE ? "MPA_GPU_STATS is not 1" : !stats_dev_ok ? "the device statistics declined" : cs == STEP_MODEL || rows == STEP_MODEL ? "a walk runs through its model" : !fin_why.empty() ? fin_why.c_str() : nullptr;
+		if (any && why && timing_on()) fprintf(stderr, "[mpa-timing]   finish declined (%s): ranking and flatten on the host\n", why);
+	} else if (fin == STEP_MODEL && batch_finish_model(b)) {
+		for (const QueryState &qs : b->qs) for (const Region &r : qs.regs) if (r.aligned && r.cs_src) b->flat_cs_src = r.cs_src;
+		return MPA_OK;
+	}
 	parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) { stage_finish(b, b->qs[qi]); });   // (c)
 	return MPA_OK;
 }

@@ -5,6 +5,7 @@
 #pragma once
 #include <cstdlib>
 #include <functional>
+#include <memory>
 #include "host_core.h"
 
 namespace mpa {
@@ -81,6 +82,10 @@ struct mpa_batch_s {
 	mpa::DpResidentIn r2_in;
 	bool r2_resident = false;
 	const mpa_dp_rst_t *r2_rst_dev = nullptr;
+	// MPA_GPU_FINISH (1 or model): the batch's flat result when the step behind the walks ranked and laid it out
+	// (null: stage_finish ranked the regions and mpa_batch_finish flattens them), and where its cs bodies came from (Region::cs_src)
+	std::unique_ptr<mpa_result_s> flat;
+	int flat_cs_src = 0;
 	~mpa_batch_s() { free(sp_pool1); }
 };
 
@@ -187,6 +192,9 @@ static inline StepMode step_mode(const char *env_name)
 	if (!strcmp(e, "model")) return STEP_MODEL;
 	return atoi(e) != 0 ? STEP_DEVICE : STEP_HOST;
 }
+
+// host_align.cpp -> host_finish.cpp (MPA_GPU_FINISH=model): ranking and flat result of the batch through finish_core.h on the host, into b->flat
+MPA_HOST_LOCAL bool batch_finish_model(mpa_batch_s *b);
 
 static inline uint8_t codon_aa(const uint8_t *nt)
 {

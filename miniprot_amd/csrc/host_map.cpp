@@ -83,6 +83,14 @@ int mpa_batch_dp_results(mpa_batch_t *b, const mpa_dp_rst_t *rst, const uint32_t
 static mpa_result_t *mpa_batch_finish_impl(mpa_batch_t *b)
 {
 	double t_fin = now_ms();
+	if (b->flat) {                                           // (MPA_GPU_FINISH: the step behind the walks laid the result out already)
+		mpa_result_s *res = b->flat.release();
+		res->n_seq = (int32_t)b->qs.size();
+		parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t i) { b->qs[i] = QueryState(); });
+		delete b;
+		timing_note("batch_finish (flatten)", now_ms() - t_fin);
+		return res;
+	}
 	mpa_result_s *res = new mpa_result_s();
 	res->n_seq = (int32_t)b->qs.size();
 	res->hit_off.assign(b->qs.size() + 1, 0);

@@ -17,6 +17,7 @@
 #include "regions_core.h"
 #include "plans_core.h"
 #include "spans_core.h"
+#include "finish_core.h"
 
 namespace mpa {
 
@@ -286,9 +287,14 @@ struct AlnWalkSizes { int64_t n_jobs, n_cigar, text_bytes, n_feat, slot_bytes, r
 struct AlnStatsIO { AlnStatsJob *jobs = nullptr; uint32_t *cigar = nullptr; char *text = nullptr; const AlnStatsOut *out = nullptr; const AlnFeat *feat = nullptr; };
 struct AlnCsIO { int64_t *slot_off = nullptr; const AlnCsOut *out = nullptr; const char *body = nullptr; };
 struct AlnRowsIO { int64_t *slot_off = nullptr; const AlnRowsOut *out = nullptr; const char *body = nullptr; };
+// fin != nullptr (MPA_GPU_FINISH=1, with the statistics in the call; the records staged through dev_finish_stage): the ranking and the
+// flat result run behind the walks' kernels on the same stream and in front of the call's one wait, reading the out records, features,
+// slots and CIGAR words where they lie; nothing of the walks' own output is downloaded then (io.out, cs.out, rows.out stay null) and
+// fin->flat is the result.
+struct FinishResident;
 int dev_aln_walks_stage(mpa_ctx_t *ctx, const AlnWalkSizes &z, AlnStatsIO &io, AlnCsIO &cs, AlnRowsIO &rows);
 int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const AlnRowsParams &rp, const int8_t *mat, const AlnWalkSizes &z, AlnStatsIO &io, AlnCsIO &cs,
-                  AlnRowsIO &rows, bool dev_cig = false);
+                  AlnRowsIO &rows, bool dev_cig = false, FinishResident *fin = nullptr);
 
 // ---- accepted spans and region CIGARs on the device (MPA_GPU_SPANS=1; driver: stats_run.hip; kernels: span_kernels.hip; code:
 // spans_core.h) ----
@@ -312,6 +318,37 @@ int dev_spans_round1(mpa_ctx_t *ctx, mpa_idx_s *mi, const SpansParams &p, const 
 struct SpansAsmIO { mpa_dp_rst_t *rst2 = nullptr; int64_t *slot_off = nullptr; const AsmRec *rec = nullptr; const uint32_t *cigar = nullptr; };
 int dev_spans_asm_stage(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, SpansAsmIO &io);
 int dev_spans_assemble(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, const uint32_t *pool2, int64_t n_pool2, SpansAsmIO &io, const mpa_dp_rst_t *d_rst2 = nullptr);
+
+// ---- ranking and flat result of a batch (MPA_GPU_FINISH; code: finish_core.h; kernels: finish_kernels.hip;
+// driver: stats_run.hip; the host side and the model: host_finish.cpp) ----
+// The tables of a call: the queries' aligned regions as records (query q: rec[first[q] .. first[q + 1])), and the CIGAR words, features,
+// cs text and rows text their offsets point into.  in_*: the sizes of those arrays; out_*: the sums of the records' n_cigar, n_feat,
+// cs_len and row bytes (a result that keeps every hit); n_big: queries of more than FINISH_LDS_REGS regions (finish_count_big).
+// dev_finish_stage sizes the context's pinned blocks and hands out where the caller writes the tables; dev_finish sends them up, runs
+// k_finish_rank, k_finish_scan and k_finish_gather on the context's stream, whose stores put the flat result into a pinned block at its
+// real size, and waits once: flat points into that pinned memory of the context, valid until its next call.  (The hook's way; a batch
+// takes the step inside dev_aln_walks, where only first[] and the records go up and the rest is read where the walks left it.)  MPA_ERR_UNSUPPORTED from either: a pool or pinned block could
+// not grow -- the caller keeps the host's ranking.
+struct FinishSizes { int64_t n_query, n_rec, n_big, in_words, in_feat, in_cs, in_rows, out_words, out_feat, out_cs, out_rows; };
+struct FinishTables { int64_t *first = nullptr; FinRec *rec = nullptr; uint32_t *words = nullptr; mpa_feat_t *feats = nullptr; char *cs_text = nullptr, *rows_text = nullptr; };
+struct FinishFlat { const FinCounts *off = nullptr; const mpa_hit_t *hits = nullptr; const FinCsRef *cs = nullptr; const FinRowsRef *rows = nullptr; const uint32_t *cigars = nullptr;
+                    const mpa_feat_t *feats = nullptr; const char *cs_text = nullptr, *rows_text = nullptr; int64_t bytes_down = 0; };
+struct FinishResident { FinParams p; FinishSizes z; FinishFlat flat; };   // the step inside dev_aln_walks: in p and z, out flat
+static inline int64_t finish_count_big(const int64_t *first, int64_t n_query)
+{
+	int64_t n = 0;
+	for (int64_t q = 0; q < n_query; ++q) n += first[q + 1] - first[q] > FINISH_LDS_REGS;
+	return n;
+}
+int dev_finish_stage(mpa_ctx_t *ctx, const FinishSizes &z, FinishTables &t);
+int dev_finish(mpa_ctx_t *ctx, const FinParams &p, const FinishSizes &z, FinishFlat &flat);
+int dev_finish_last(const mpa_ctx_t *ctx, int64_t out[6]);
+// the same through the shared core on the host with a team of one, into a result (host_finish.cpp); and a device call's flat arrays
+// into a result, one copy each
+void finish_model(const FinParams &p, const FinishSizes &z, const FinishTables &t, mpa_result_s *res);
+void finish_flat_to_result(const FinishFlat &f, int64_t n_query, mpa_result_s *res);
+// every index the step follows, checked once for both paths (the test hook; the batch's own tables are made right)
+bool finish_tables_ok(const FinishSizes &z, const FinishTables &t);
 
 // ---- DP round 2 from device-resident tasks (MPA_GPU_ROUND2=1; dp_exec.hip) ----
 // What dev_spans_round1 leaves for it: the round-2 tasks where k_spans_emit wrote them (a pool of the context) and the three bounds the

@@ -11,15 +11,24 @@
 // host step between the DP rounds and the one behind them here: dev_spans_stage() / dev_spans_round1() and dev_spans_asm_stage() /
 // dev_spans_assemble().  The CIGAR pool k_assemble writes (sp_cig) stays on the device until the context's next call, and
 // dev_aln_walks() reads it in place of an uploaded one when the caller says so (dev_cig).
+// MPA_GPU_FINISH=1 (kernels k_finish_rank, k_finish_scan, k_finish_gather: finish_kernels.hip; code: finish_core.h; DESIGN.md section
+// 4.13) puts the final ranking of the batch's aligned regions and the layout of its flat result here: dev_finish_stage() / dev_finish().
 #include "dev_ctx.h"
 #include "spans_core.h"
 #include "dp_results_core.h"
 #include "stats_kernels.hip"
 #include "span_kernels.hip"
+#include "finish_kernels.hip"
 
 namespace mpa {
 
-// (the layouts of the blocks: StatsLayout, SpansLayout, AsmLayout in dev_layout.h)
+// (the layouts of the blocks: StatsLayout, SpansLayout, AsmLayout, FinishLayout in dev_layout.h)
+
+// the finish step's parts (below), which dev_aln_walks runs behind its own kernels
+struct FinishSrc { const uint32_t *words; const void *feats; const char *cs_text, *rows_text; const AlnStatsOut *st; const AlnCsOut *cs; const AlnRowsOut *rows; int32_t show_trans; };
+static int finish_prepare(mpa_ctx_t *ctx, const FinishSizes &z);
+static int finish_launch(mpa_ctx_t *ctx, const FinParams &p, const FinishSizes &z, const FinishSrc *src);
+static int finish_collect(mpa_ctx_t *ctx, const FinishSizes &z, int64_t waits, FinishFlat &flat);
 
 // The pinned blocks of a call for any non-empty subset of the walks, the one that goes up for the caller to fill: jobs, CIGAR words,
 // text and, next to the jobs, cs.slot_off[n_jobs + 1] / rows.slot_off[n_jobs + 1].  z.n_feat < 0: no statistics (the statistics stay
@@ -48,7 +57,7 @@ int dev_aln_walks_stage(mpa_ctx_t *ctx, const AlnWalkSizes &z, AlnStatsIO &io, A
 // rows.slot_off[j] as aln_rows_core.h lays it out -- all of it pinned memory of the context, valid until its next call.
 // MPA_ERR_UNSUPPORTED: a pool could not grow -- the caller keeps the host's walks.
 int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const AlnRowsParams &rp, const int8_t *mat, const AlnWalkSizes &z, AlnStatsIO &io, AlnCsIO &cs,
-                  AlnRowsIO &rows, bool dev_cig)
+                  AlnRowsIO &rows, bool dev_cig, FinishResident *fin)
 {
 	const StatsLayout L(z);
 	const int64_t n_jobs = z.n_jobs;
@@ -67,6 +76,11 @@ int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const 
 	if (ctx->walks.st_in.ensure(L.up_bytes) != MPA_OK || (stats && ctx->walks.st_out.ensure(L.down_bytes) != MPA_OK) || (cs_on && ctx->walks.cs_out.ensure(L.cs_down_bytes) != MPA_OK) ||
 	    (rows_on && ctx->walks.rows_out.ensure(L.rows_down_bytes) != MPA_OK))
 		return tl_alloc_failed ? MPA_ERR_UNSUPPORTED : MPA_ERR_HIP;
+	// (MPA_GPU_FINISH=1) ranking and flat result behind the walks' kernels, in front of the call's one wait: what the walks leave is
+	// read where it lies and is not downloaded.  Whatever can decline does so here, before anything is launched
+	if (fin && !stats) { set_error("dev_aln_walks: the finish step needs the statistics in the same call"); return MPA_ERR_ARG; }
+	if (fin) { const int rc = finish_prepare(ctx, fin->z); if (rc != MPA_OK) return rc; }
+	const int64_t waits0 = ctx->n_waits.load();
 	hipStream_t s = ctx->stream;
 	char *hu = ctx->walks.h_stats_up.as<char>();
 	aln_tables_fill(L.tabs.in(hu), mat, (size_t)(p.asize * p.asize));
@@ -82,7 +96,7 @@ int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const 
 		                   L.out.in(dout), L.feat.in(dout));
 		HIP_TRY(hipGetLastError());
 		const char *hd = ctx->walks.h_stats_down.as<char>();
-		HIP_TRY(hipMemcpyAsync(ctx->walks.h_stats_down.p, dout, L.down_bytes - 16, hipMemcpyDeviceToHost, s));
+		if (!fin) HIP_TRY(hipMemcpyAsync(ctx->walks.h_stats_down.p, dout, L.down_bytes - 16, hipMemcpyDeviceToHost, s));
 		io.out = L.out.in(hd), io.feat = L.feat.in(hd);
 	}
 	if (cs_on) {
@@ -92,7 +106,7 @@ int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const 
 		                   L.slot.in(din), L.cs_out.in(dout), L.body.in(dout));
 		HIP_TRY(hipGetLastError());
 		const char *hd = ctx->walks.h_cs_down.as<char>();
-		HIP_TRY(hipMemcpyAsync(ctx->walks.h_cs_down.p, dout, L.cs_down_bytes - 16, hipMemcpyDeviceToHost, s));
+		if (!fin) HIP_TRY(hipMemcpyAsync(ctx->walks.h_cs_down.p, dout, L.cs_down_bytes - 16, hipMemcpyDeviceToHost, s));
 		cs.out = L.cs_out.in(hd), cs.body = L.body.in(hd);
 	}
 	if (rows_on) {
@@ -102,10 +116,19 @@ int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const 
 		                   L.rslot.in(din), L.rows_out.in(dout), L.rbody.in(dout));
 		HIP_TRY(hipGetLastError());
 		const char *hd = ctx->walks.h_rows_down.as<char>();
-		HIP_TRY(hipMemcpyAsync(ctx->walks.h_rows_down.p, dout, L.rows_down_bytes - 16, hipMemcpyDeviceToHost, s));
+		if (!fin) HIP_TRY(hipMemcpyAsync(ctx->walks.h_rows_down.p, dout, L.rows_down_bytes - 16, hipMemcpyDeviceToHost, s));
 		rows.out = L.rows_out.in(hd), rows.body = L.rbody.in(hd);
 	}
+	if (fin) {
+		const char *d_st = ctx->walks.st_out.as<char>(), *d_cs = cs_on ? ctx->walks.cs_out.as<char>() : nullptr, *d_rows = rows_on ? ctx->walks.rows_out.as<char>() : nullptr;
+		const FinishSrc src{ dcig, (const void*)L.feat.in(d_st), cs_on ? L.body.in(d_cs) : nullptr, rows_on ? L.rbody.in(d_rows) : nullptr, L.out.in(d_st),
+		                     cs_on ? L.cs_out.in(d_cs) : nullptr, rows_on ? L.rows_out.in(d_rows) : nullptr, rp.show_trans };
+		const int rc = finish_launch(ctx, fin->p, fin->z, &src);
+		if (rc != MPA_OK) return rc;
+		io.out = nullptr, io.feat = nullptr, cs.out = nullptr, cs.body = nullptr, rows.out = nullptr, rows.body = nullptr;   // (not downloaded)
+	}
 	HIP_TRY(wait_stream(ctx, s));
+	if (fin) return finish_collect(ctx, fin->z, ctx->n_waits.load() - waits0, fin->flat);
 	return MPA_OK;
 }
 
@@ -221,6 +244,116 @@ int dev_spans_assemble(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, const uin
 	if (n_words > 0) HIP_TRY(hipMemcpyAsync(h_cig.in(hd), ctx->spans.sp_cig.p, h_cig.bytes(), hipMemcpyDeviceToHost, s));
 	HIP_TRY(wait_stream(ctx, s));
 	io.rec = L.rec.in(hd), io.cigar = h_cig.in(hd);
+	return MPA_OK;
+}
+
+// ---- MPA_GPU_FINISH=1 -----------------------------------------------------------------------------------------------------------
+static bool finish_sizes_ok(const FinishSizes &z)
+{
+	const int64_t lim = (int64_t)1 << 40;
+	return z.n_query > 0 && z.n_query < INT32_MAX && z.n_rec > 0 && z.n_rec <= (int64_t)1 << 28 && z.n_big >= 0 && z.n_big <= z.n_query && z.in_words >= 0 && z.in_words < lim && z.in_feat >= 0 &&
+	       z.in_feat < lim && z.in_cs >= 0 && z.in_cs < lim && z.in_rows >= 0 && z.in_rows < lim && z.out_words >= 0 && z.out_words < lim && z.out_feat >= 0 && z.out_feat < lim && z.out_cs >= 0 &&
+	       z.out_cs < lim && z.out_rows >= 0 && z.out_rows < lim;
+}
+
+int dev_finish_stage(mpa_ctx_t *ctx, const FinishSizes &z, FinishTables &t)
+{
+	t = FinishTables();
+	if (!finish_sizes_ok(z)) { set_error("GPU finish: no aligned regions, or too many for one launch"); return MPA_ERR_UNSUPPORTED; }
+	if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return MPA_ERR_HIP; }
+	const FinishLayout L(z);
+	if (ctx->finish.h_fin_up.ensure(L.up_bytes) != MPA_OK || ctx->finish.h_fin_down.ensure(L.down_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
+	char *hu = ctx->finish.h_fin_up.as<char>();
+	t.first = L.first.in(hu), t.rec = L.rec.in(hu), t.words = L.words.in(hu), t.feats = L.in_feat.in(hu), t.cs_text = L.in_cs.in(hu), t.rows_text = L.in_rows.in(hu);
+	return MPA_OK;
+}
+
+// The three parts of a call.  finish_prepare: the staged first[] checked, the large queries numbered, the pools sized -- everything that
+// can decline, before anything is launched.  finish_launch: the staged block up (behind the walks only first | big | records: `src` says
+// where the walks left the rest, and k_finish_fill completes the records from their out records), then rank, scan and gather on the
+// context's stream; scan and gather write the pinned block directly.  finish_collect, behind the caller's wait: the flat arrays.
+
+static int finish_prepare(mpa_ctx_t *ctx, const FinishSizes &z)
+{
+	if (!finish_sizes_ok(z)) { set_error("dev_finish: no aligned regions, or too many for one launch"); return MPA_ERR_ARG; }
+	const FinishLayout L(z);
+	if (L.up_bytes > ctx->finish.h_fin_up.cap || L.down_bytes > ctx->finish.h_fin_down.cap) { set_error("dev_finish: the staging block was not sized for this call"); return MPA_ERR_ARG; }
+	char *hu = ctx->finish.h_fin_up.as<char>();
+	const int64_t *first = L.first.in(hu);
+	int32_t *big = L.big.in(hu);
+	int64_t nb = 0;
+	if (first[0] != 0 || first[z.n_query] != z.n_rec) { set_error("dev_finish: first[] does not span the records"); return MPA_ERR_ARG; }
+	for (int64_t q = 0; q < z.n_query; ++q) {
+		const int64_t n = first[q + 1] - first[q];
+		if (n < 0 || n > INT32_MAX) { set_error("dev_finish: first[] is not ascending"); return MPA_ERR_ARG; }
+		big[q] = n > FINISH_LDS_REGS ? (int32_t)nb++ : -1;
+	}
+	if (nb != z.n_big) { set_error("dev_finish: n_big is not the number of large queries"); return MPA_ERR_ARG; }
+	tl_alloc_failed = false;
+	if (ctx->finish.fin_in.ensure(L.up_bytes) != MPA_OK || ctx->finish.fin_mid.ensure(L.mid_bytes) != MPA_OK) return tl_alloc_failed ? MPA_ERR_UNSUPPORTED : MPA_ERR_HIP;
+	return MPA_OK;
+}
+
+static int finish_launch(mpa_ctx_t *ctx, const FinParams &p, const FinishSizes &z, const FinishSrc *src)
+{
+	const FinishLayout L(z);
+	hipStream_t s = ctx->stream;
+	char *din = ctx->finish.fin_in.as<char>(), *mid = ctx->finish.fin_mid.as<char>(), *hd = ctx->finish.h_fin_down.as<char>();
+	HIP_TRY(hipMemcpyAsync(din, ctx->finish.h_fin_up.p, src ? L.rec.end() : L.up_bytes - 16, hipMemcpyHostToDevice, s));
+	if (src) {
+		hipLaunchKernelGGL(k_finish_fill, dim3((unsigned)((z.n_rec + 255) / 256)), dim3(256), 0, s, L.rec.in(din), z.n_rec, src->st, src->cs, src->rows, src->show_trans);
+		HIP_TRY(hipGetLastError());
+	}
+	FinishArgs a;
+	a.first = L.first.in(din), a.rec = L.rec.in(din), a.big = L.big.in(din), a.p = p, a.out = L.out.in(mid), a.cnt = L.cnt.in(mid), a.off = L.off.in(mid);
+	a.tmp = L.tmp.in(mid), a.r = L.r.in(mid), a.key = L.key.in(mid), a.stack = L.stack.in(mid), a.hist = L.hist.in(mid), a.prim = L.prim.in(mid), a.ctl = L.ctl.in(mid), a.cov = L.cov.in(mid);
+	// (pinned host memory, written by the kernels: what the result holds is what crosses the bus)
+	const FinDst dst{ L.hits.in(hd), L.cigars.in(hd), L.feats.in(hd), L.cs.in(hd), L.cs_text.in(hd), L.rows.in(hd), L.rows_text.in(hd) };
+	const int32_t nq = (int32_t)z.n_query;
+	hipLaunchKernelGGL(k_finish_rank, dim3((unsigned)nq), dim3(64), 0, s, a, nq);
+	HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(k_finish_scan, dim3(1), dim3(FINISH_SCAN), 0, s, (const FinCounts*)a.cnt, nq, a.off, L.h_off.in(hd));
+	HIP_TRY(hipGetLastError());
+	if (src) hipLaunchKernelGGL(k_finish_gather, dim3((unsigned)nq), dim3(64 * FINISH_GATHER_WAVES), 0, s, a, nq, src->words, src->feats, src->cs_text, src->rows_text, dst);
+	else hipLaunchKernelGGL(k_finish_gather, dim3((unsigned)nq), dim3(64 * FINISH_GATHER_WAVES), 0, s, a, nq, (const uint32_t*)L.words.in(din), (const void*)L.in_feat.in(din), (const char*)L.in_cs.in(din), (const char*)L.in_rows.in(din), dst);
+	HIP_TRY(hipGetLastError());
+	return MPA_OK;
+}
+
+static int finish_collect(mpa_ctx_t *ctx, const FinishSizes &z, int64_t waits, FinishFlat &flat)
+{
+	const FinishLayout L(z);
+	const char *hd = ctx->finish.h_fin_down.as<char>();
+	flat.off = L.h_off.in(hd), flat.hits = L.hits.in(hd), flat.cs = L.cs.in(hd), flat.rows = L.rows.in(hd), flat.cigars = L.cigars.in(hd), flat.feats = L.feats.in(hd);
+	flat.cs_text = L.cs_text.in(hd), flat.rows_text = L.rows_text.in(hd);
+	const FinCounts &tot = flat.off[z.n_query];
+	if (tot.hit < 0 || tot.hit > z.n_rec || tot.cigar < 0 || tot.cigar > z.out_words || tot.feat < 0 || tot.feat > z.out_feat || tot.cs < 0 || tot.cs > z.out_cs || tot.rows < 0 || tot.rows > z.out_rows) {
+		set_error("dev_finish: impossible counts");
+		return MPA_ERR_HIP;
+	}
+	// what the kernels wrote into the pinned block: the prefix, a hit record and two references per hit, and the dense arrays at their real length
+	flat.bytes_down = (int64_t)L.h_off.bytes() + tot.hit * (int64_t)(sizeof(mpa_hit_t) + sizeof(FinCsRef) + sizeof(FinRowsRef)) + 4 * tot.cigar + (int64_t)sizeof(mpa_feat_t) * tot.feat + tot.cs + tot.rows;
+	int64_t *last = ctx->finish.last;
+	last[0] = z.n_query, last[1] = z.n_rec, last[2] = tot.hit, last[3] = flat.bytes_down, last[4] = z.n_big, last[5] = waits;
+	return MPA_OK;
+}
+
+int dev_finish(mpa_ctx_t *ctx, const FinParams &p, const FinishSizes &z, FinishFlat &flat)
+{
+	flat = FinishFlat();
+	HIP_TRY(hipSetDevice(ctx->device));
+	int rc = finish_prepare(ctx, z);
+	if (rc != MPA_OK) return rc;
+	const int64_t waits0 = ctx->n_waits.load();
+	if ((rc = finish_launch(ctx, p, z, nullptr)) != MPA_OK) return rc;
+	HIP_TRY(wait_stream(ctx, ctx->stream));
+	return finish_collect(ctx, z, ctx->n_waits.load() - waits0, flat);
+}
+
+int dev_finish_last(const mpa_ctx_t *ctx, int64_t out[6])
+{
+	if (!ctx || !out) { set_error("dev_finish_last: missing arguments"); return MPA_ERR_ARG; }
+	for (int k = 0; k < 6; ++k) out[k] = ctx->finish.last[k];
 	return MPA_OK;
 }
 
