@@ -172,6 +172,31 @@ int mpa_dbg_finish(mpa_ctx_t *ctx, const mpa_mapopt_t *opt, int32_t kmer, int32_
 int mpa_dbg_finish_last(const mpa_ctx_t *ctx, int64_t out[MPA_DBG_FINISH_REC]);
 int64_t mpa_dbg_result_flat(const mpa_result_t *r, int32_t which, void *buf, int64_t cap);
 
+/* The output text of a batch (MPA_GPU_FORMAT; miniprot_amd/csrc/format_core.h): what mpa_format_output() prints
+ * for result r -- PAF, the carried --aln / --trans rows, GFF3 or GTF according to opt->flag, behind the output filters -- through select
+ * and size, scan and write.  On a context: the result's arrays, the query names and the contigs' names and lengths go up and
+ * k_format_size, k_format_scan and k_format_write put the text, with ids relative to the batch, and the places of its id fields into
+ * pinned memory; ctx == NULL: the shared core on the host with a team of one (which builds the cs bodies and rows of hits that carry
+ * none with the host's walks; on a context such a hit declines).  Then the patch with id0: every six-digit id field becomes field + id0.
+ * *text (mpa_free): the text, *len its bytes, *n_out the printed hits (= how far the running id advances).  Returns MPA_OK, or
+ * MPA_DBG_FORMAT_DECLINED when the step declined -- a blen of 0, something not carried, a gff_prefix longer than 64 bytes, ids reaching
+ * seven digits, more text than the block's bound -- and *text is mpa_format_output()'s; negative: an error.  Every index of the result is
+ * checked first.
+ * mpa_dbg_format_last: of the context's last device call -- [0] queries, [1] hits printed, [2] bytes of text the kernels wrote, [3] id
+ * fields, [4] host waits of the call, [5] 1 when it declined.
+ * mpa_dbg_result_make: a result (mpa_result_destroy) from flat arrays laid out as mpa_dbg_result_flat gives them; cs / rows: the 16- /
+ * 24-byte references of every hit, or NULL when no hit carries one.
+ * mpa_dbg_idx_names: an index (mpa_idx_destroy) that holds contig names and lengths and nothing else -- all the formatter reads when
+ * every aligned hit carries what the options print.  Contigs longer than any test could hold as sequence. */
+#define MPA_DBG_FORMAT_REC 6
+#define MPA_DBG_FORMAT_DECLINED 1
+int mpa_dbg_format(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, const char *const *names, const mpa_result_t *r, int64_t id0, char **text,
+                   int64_t *len, int64_t *n_out);
+int mpa_dbg_format_last(const mpa_ctx_t *ctx, int64_t out[MPA_DBG_FORMAT_REC]);
+int mpa_dbg_result_make(int32_t n_seq, const int64_t *hit_off, const mpa_hit_t *hits, const uint32_t *cigars, int64_t n_words, const mpa_feat_t *feats, int64_t n_feat, const void *cs,
+                        const char *cs_text, int64_t cs_bytes, const void *rows, const char *rows_text, int64_t rows_bytes, mpa_result_t **out);
+mpa_idx_t *mpa_dbg_idx_names(int32_t n_ctg, const char *const *names, const int64_t *lens);
+
 #ifdef __cplusplus
 }
 #endif

@@ -581,6 +581,69 @@ def dbg_finish_last(ctx):
     return tuple(int(x) for x in out)
 
 
+FORMAT_DECLINED = 1   # MPA_DBG_FORMAT_DECLINED (include/mpamd_dbg.h)
+
+
+def dbg_idx_names(names, lens):
+    """mpa_dbg_idx_names(): an Index of contig names and lengths alone (no sequence): what the formatter reads of an index when every
+    aligned hit carries what the options print."""
+    f = dbg_lib().mpa_dbg_idx_names
+    f.restype = C.c_void_p
+    f.argtypes = [C.c_int32, C.c_void_p, C.c_void_p]
+    arr = (C.c_char_p * len(names))(*[s.encode() for s in names])
+    ln = np.ascontiguousarray(lens, np.int64)
+    return Index(f(len(names), arr, ln.ctypes.data))
+
+
+def dbg_result_make(hit_off, hits, cigars, feats, cs=None, cs_text=b"", rows=None, rows_text=b""):
+    """mpa_dbg_result_make(): a Result from flat arrays -- hit_off (int64, n_seq + 1), hits (HIT records), cigars (uint32), feats (56-byte
+    records as a uint8 array), and the cs / rows references of every hit (16- / 24-byte records as uint8 arrays, or None) with their texts."""
+    f = dbg_lib().mpa_dbg_result_make
+    f.restype = C.c_int
+    f.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_char_p, C.c_int64,
+                  C.POINTER(C.c_void_p)]
+    hit_off = np.ascontiguousarray(hit_off, np.int64)
+    hits = np.ascontiguousarray(hits)
+    cigars, feats = np.ascontiguousarray(cigars, np.uint32), np.ascontiguousarray(feats, np.uint8)
+    assert hits.nbytes == 136 * int(hit_off[-1]) and len(feats) % 56 == 0
+    cs = None if cs is None else np.ascontiguousarray(cs).view(np.uint8)
+    rows = None if rows is None else np.ascontiguousarray(rows).view(np.uint8)
+    assert cs is None or len(cs) == 16 * int(hit_off[-1])
+    assert rows is None or len(rows) == 24 * int(hit_off[-1])
+    out = C.c_void_p(None)
+    _check(f(len(hit_off) - 1, hit_off.ctypes.data, hits.ctypes.data if hits.nbytes else None, cigars.ctypes.data if len(cigars) else None, len(cigars),
+             feats.ctypes.data if len(feats) else None, len(feats) // 56, None if cs is None else cs.ctypes.data, cs_text, len(cs_text),
+             None if rows is None else rows.ctypes.data, rows_text, len(rows_text), C.byref(out)))
+    return Result(out.value)
+
+
+def dbg_format(ctx, idx, mo, queries, result, id0=0):
+    """mpa_dbg_format(): the output text of a result through the three stages of MPA_GPU_FORMAT, on the device (ctx) or through the shared
+    core on the host (ctx None), patched with id0.  Returns (text, printed hits, declined): declined = the step declined and the text is
+    mpa_format_output()'s."""
+    f = dbg_lib().mpa_dbg_format
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(MapOpt), C.POINTER(QBatch), C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    names = (C.c_char_p * len(queries.names))(*[n.encode() for n in queries.names])
+    out, n, n_out = C.c_void_p(None), C.c_int64(0), C.c_int64(0)
+    rc = f(ctx.h if ctx else None, idx.h, C.byref(mo), C.byref(queries.c), names, result.h, int(id0), C.byref(out), C.byref(n), C.byref(n_out))
+    if rc < 0:
+        _check(rc)
+    txt = C.string_at(out.value, n.value)
+    lib().mpa_free(out)
+    return txt, int(n_out.value), rc == FORMAT_DECLINED
+
+
+def dbg_format_last(ctx):
+    """mpa_dbg_format_last(): of the context's last device format call, (queries, hits printed, text bytes, id fields, host waits, declined)."""
+    f = dbg_lib().mpa_dbg_format_last
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.POINTER(C.c_int64 * 6)]
+    out = (C.c_int64 * 6)()
+    _check(f(ctx.h, C.byref(out)))
+    return tuple(int(x) for x in out)
+
+
 DP_PLAN_DECLINED = 1   # MPA_DBG_DP_PLAN_DECLINED (include/mpamd_dbg.h)
 
 
@@ -820,9 +883,10 @@ def dbg_chain_extract(ctx, args, probs, mode):
     return us, as_, status[:n_prob].copy(), rec[:n_prob].copy()
 
 
-def map_batches(ctx, idx, mo, batches, n_threads=1, keep_results=False, want_text=True, claim=None):
+def map_batches(ctx, idx, mo, batches, n_threads=1, keep_results=False, want_text=True, claim=None, id0=0):
     """mpa_map_batches(): a stream of Queries batches through the pipelined mapper.  Returns the list of output texts
-    (bytes, one per batch; the hit-id counter runs across the batches as in one output file); with keep_results the pair
+    (bytes, one per batch; the hit-id counter runs across the batches as in one output file, its first printed hit
+    getting id0 + 1); with keep_results the pair
     (texts, [Result]); with want_text=False no text is produced (texts are None).
     claim: mpa_map_batches_claim() -- `batches` is a whole job shared with other processes and claim() returns the index of
     the next batch this process should map (-1: none left); the return value is then (order, texts[, results]) for the
@@ -832,7 +896,7 @@ def map_batches(ctx, idx, mo, batches, n_threads=1, keep_results=False, want_tex
         return (([], [], []) if keep_results else ([], [])) if claim else (([], []) if keep_results else [])
     qb = (QBatch * n)(*[b.c for b in batches])
     res = (C.c_void_p * n)()
-    idc = C.c_int64(0)
+    idc = C.c_int64(int(id0))
     names = text = tlen = None
     if want_text:
         name_arrays = [(C.c_char_p * len(b.names))(*[x.encode() for x in b.names]) for b in batches]

@@ -205,6 +205,14 @@ struct FinishBufs {
 	int64_t last[6] = { 0, 0, 0, 0, 0, 0 };   // of the last call: queries, hits in, hits kept, bytes down, queries ranked in HBM scratch, host waits (mpa_dbg_finish_last)
 };
 
+// the output text of a batch (stats_run.hip, MPA_GPU_FORMAT; FormatLayout): grow-only, allocated by the first call that asks for them
+struct FormatBufs {
+	PoolRegistry &reg;
+	CtxPool fmt_in{ reg, "fmt_in" }, fmt_mid{ reg, "fmt_mid" };   // what goes up; a place per hit, the queries' sums and their prefix
+	HostPinned h_fmt_up, h_fmt_down;          // the block that goes up; totals, id places and text, which k_format_scan and k_format_write write directly
+	int64_t last[6] = { 0, 0, 0, 0, 0, 0 };   // of the last call: queries, hits printed, text bytes, id fields, host waits, declined while sizing (mpa_dbg_format_last)
+};
+
 // What the environment says about every context of a pipeline: filled once for a root (ctx_knobs_from_env), handed to a sibling by
 // one assignment, read by dp_plan_knobs().  A new knob is a field here and a line there.
 struct CtxKnobs {
@@ -251,6 +259,7 @@ struct mpa_ctx_s {
 	SpanBufs spans{ pools };
 	PlannerBufs planner{ pools };
 	FinishBufs finish{ pools };
+	FormatBufs format{ pools };
 	// ---- what the DP rounds of this context did
 	mpa_dp_stats_t stats = {};
 	mpa_dp_stats_t total = {};

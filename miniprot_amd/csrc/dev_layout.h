@@ -150,6 +150,27 @@ struct FinishLayout {
 	}
 };
 
+// ---- the output text of a batch (stats_run.hip, MPA_GPU_FORMAT; 16-byte sections)
+// fmt_in / h_fmt_up: the hits' prefix | query offsets | query name offsets | contig name offsets | contig lengths | hits | cs refs | rows
+// refs | features | CIGAR words | cs text | rows text | query names | contig names (refs and texts only when the result carries them);
+// fmt_mid: a place per hit | the queries' sums | their prefix; h_fmt_down: the totals (the head) | where the id fields lie | the text --
+// sized from bounds, written by the kernels at their real size
+struct FormatLayout {
+	Piece<int64_t> hit_off, q_off, qname_off, cname_off, clen, id_at; Piece<mpa_hit_t> hits; Piece<FinCsRef> cs; Piece<FinRowsRef> rows; Piece<mpa_feat_t> feats; Piece<uint32_t> cigars;
+	Piece<char> cs_text, rows_text, qname, cname, text; Piece<FmtAt> at; Piece<FmtCounts> cnt, off, head;
+	size_t up_bytes, mid_bytes, down_bytes;
+	explicit FormatLayout(const FormatSizes &z) {
+		const size_t nq = (size_t)z.n_query, nh = (size_t)z.n_hit, nc = (size_t)z.n_ctg;
+		Carve up(16), mid(16), dn(16);
+		hit_off = up.take<int64_t>(nq + 1), q_off = up.take<int64_t>(nq + 1), qname_off = up.take<int64_t>(nq + 1), cname_off = up.take<int64_t>(nc + 1), clen = up.take<int64_t>(nc);
+		hits = up.take<mpa_hit_t>(nh), cs = up.take_if<FinCsRef>(z.has_cs != 0, nh), rows = up.take_if<FinRowsRef>(z.has_rows != 0, nh);
+		feats = up.take<mpa_feat_t>((size_t)z.n_feat), cigars = up.take<uint32_t>((size_t)z.n_words), cs_text = up.take<char>((size_t)z.cs_bytes), rows_text = up.take<char>((size_t)z.rows_bytes);
+		qname = up.take<char>((size_t)z.qname_bytes), cname = up.take<char>((size_t)z.cname_bytes), up_bytes = up.at + 16;
+		at = mid.take<FmtAt>((size_t)z.n_place), cnt = mid.take<FmtCounts>(nq), off = mid.take<FmtCounts>(nq + 1), mid_bytes = mid.at + 16;
+		head = dn.take<FmtCounts>(1), id_at = dn.take<int64_t>((size_t)z.id_cap), text = dn.take<char>((size_t)z.text_cap), down_bytes = dn.at + 16;
+	}
+};
+
 // ---- a resident round's results pool (dp_exec.hip; round.cigoff, 64-byte sections): off[n_glob] | call_off[n] | bsum[blocks + 1] |
 // head (64 bytes) | rst[n]; header and records come down in one copy
 struct ResLayout {

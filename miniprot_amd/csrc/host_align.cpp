@@ -372,7 +372,10 @@ static void rows_model(mpa_batch_s *b)
 // want_fin (MPA_GPU_FINISH=1, with stats): the ranking and the flat result run in the same call behind the walks' kernels (DESIGN.md section
 // 4.13): only the records' host-side fields go up next to the jobs, the walks' output is neither downloaded nor applied to the regions, and
 // b->flat is the batch's result.  *fin_why: why that part declined (the walks then ran as without it)
-static int walks_on_device(mpa_batch_s *b, mpa_ctx_t *ctx, bool stats, bool cs_on, bool rows_on, bool *ran, bool want_fin = false, std::string *fin_why = nullptr)
+// want_fmt (MPA_GPU_FORMAT=1, with want_fin and the batch's names): the batch's output text is written behind the
+// gather of the same call and stays with b->flat.  *fmt_why: why that part declined (the rest ran as without it)
+static int walks_on_device(mpa_batch_s *b, mpa_ctx_t *ctx, bool stats, bool cs_on, bool rows_on, bool *ran, bool want_fin = false, std::string *fin_why = nullptr, bool want_fmt = false,
+                           std::string *fmt_why = nullptr)
 {
 	const double t_call = now_ms();
 	const size_t nq = b->qs.size();
@@ -431,6 +434,50 @@ static int walks_on_device(mpa_batch_s *b, mpa_ctx_t *ctx, bool stats, bool cs_o
 		}
 		if (want_fin) memcpy(ft.first, job0.data(), (nq + 1) * 8);
 	}
+	// (MPA_GPU_FORMAT=1) the names and lengths the text needs, and room for it from bounds: a fixed allowance for a line's fields, 11 bytes
+	// per CIGAR word, the cs and rows slots, a line per feature slot, the names wherever a line repeats them (format_bounds' figures)
+	FormatResident fmr;
+	want_fmt = want_fmt && want_fin;
+	if (want_fmt && !format_opt_from(b->opt, fmr.o)) want_fmt = false, *fmt_why = "a gff_prefix longer than 64 bytes";
+	if (want_fmt) {
+		const std::vector<Contig> &ctg = b->mi->ctg;
+		FormatSizes &fz = fmr.z;
+		fz = FormatSizes{};
+		fz.n_query = (int64_t)nq, fz.n_place = n_jobs, fz.n_ctg = (int64_t)ctg.size();
+		for (const Contig &c : ctg) fz.cname_bytes += (int64_t)c.name.size();
+		const bool annot = (b->opt.flag & (MPA_MF_GFF | MPA_MF_GTF)) != 0;
+		int64_t text = 11 * n_cigar + (cs_on ? slot_bytes : 0) + (rows_on ? rows_bytes + 35 * n_jobs : 0), ids = 0;
+		for (size_t qi = 0; qi < nq; ++qi) {
+			const QueryState &qs = b->qs[qi];
+			const int64_t qn = (int64_t)strlen(b->fmt_names[qi]);
+			fz.qname_bytes += qn, text += qn + 128;
+			for (const AlignPlan &pl : qs.plans) {
+				const Region &r = qs.regs[pl.reg];
+				const int64_t cn = (int64_t)ctg[r.vid >> 1].name.size(), nf = (int64_t)r.n_exon + 1;
+				text += 640 + qn + cn;
+				if (annot) text += (2 + 2 * nf) * (400 + cn + 2 * qn + 2 * fmr.o.prefix_len), ids += 3 + 4 * nf;
+			}
+		}
+		fz.text_cap = text, fz.id_cap = ids;
+		FormatTables up;
+		rc = dev_format_stage(ctx, fz, up);
+		if (rc == MPA_ERR_UNSUPPORTED) want_fmt = false, *fmt_why = mpa_last_error();
+		else if (rc != MPA_OK) return rc;
+		if (want_fmt) {
+			up.qname_off[0] = 0, up.cname_off[0] = 0, up.hit_off[0] = 0;
+			for (size_t qi = 0; qi < nq; ++qi) {
+				const size_t n = strlen(b->fmt_names[qi]);
+				memcpy(up.qname + up.qname_off[qi], b->fmt_names[qi], n);
+				up.qname_off[qi + 1] = up.qname_off[qi] + (int64_t)n, up.hit_off[qi + 1] = 0;
+				up.q_off[qi] = b->q.q_off[qi];
+			}
+			up.q_off[nq] = b->q.q_off[nq];
+			for (size_t c = 0; c < ctg.size(); ++c) {
+				memcpy(up.cname + up.cname_off[c], ctg[c].name.data(), ctg[c].name.size());
+				up.cname_off[c + 1] = up.cname_off[c] + (int64_t)ctg[c].name.size(), up.clen[c] = ctg[c].len;
+			}
+		}
+	}
 	parallel_for(b->n_threads, (int64_t)nq, [&](int64_t qi) {
 		const QueryState &qs = b->qs[qi];
 		int64_t j = job0[qi], c = cig0[qi], f = feat0[qi], s = slot0[qi], rs = rslot0[qi];
@@ -455,7 +502,7 @@ static int walks_on_device(mpa_batch_s *b, mpa_ctx_t *ctx, bool stats, bool cs_o
 			c += (int64_t)r.cigar.size(), f += (int64_t)r.n_exon + 1;
 		}
 	});
-	rc = dev_aln_walks(ctx, const_cast<mpa_idx_s*>(b->mi), stats_params(b->opt), rp, b->opt.mat, z, io, cs, rows, dev_cig, want_fin ? &fr : nullptr);
+	rc = dev_aln_walks(ctx, const_cast<mpa_idx_s*>(b->mi), stats_params(b->opt), rp, b->opt.mat, z, io, cs, rows, dev_cig, want_fin ? &fr : nullptr, want_fmt ? &fmr : nullptr);
 	if (rc != MPA_OK) return rc;
 	if (timing_on() && dev_cig) fprintf(stderr, "[mpa-timing]   walks upload: %lld alignments, %lld CIGAR words (the assembled pool is on the device)\n", (long long)n_jobs, (long long)n_up);
 	if (want_fin) {                                      // the result is laid out: nothing to apply to the regions
@@ -463,6 +510,10 @@ static int walks_on_device(mpa_batch_s *b, mpa_ctx_t *ctx, bool stats, bool cs_o
 		finish_flat_to_result(fr.flat, (int64_t)nq, res.get());
 		if (timing_on()) fprintf(stderr, "[mpa-timing]   finish on the GPU: %lld queries, %lld hits in, %lld kept, %lld bytes down, %.3f ms\n", (long long)nq, (long long)n_jobs,
 		                         (long long)res->hits.size(), (long long)fr.flat.bytes_down, now_ms() - t_call);
+		if (want_fmt && fmr.out.declined) *fmt_why = format_decline_reason(fmr.out.tot, fmr.z.text_cap, fmr.z.id_cap);
+		else if (want_fmt) {                                 // (out of the pinned block: the context's next call reuses it)
+			res->fmt_text.assign(fmr.out.text, (size_t)fmr.out.tot.bytes), res->fmt_id_at.assign(fmr.out.id_at, fmr.out.id_at + fmr.out.tot.ids), res->fmt_n_out = fmr.out.tot.n_out;
+		}
 		b->flat = std::move(res), b->flat_cs_src = cs_on ? 2 : 0;
 		return MPA_OK;
 	}
@@ -834,7 +885,11 @@ static int take_round3_steps(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint
 	const StepMode rows = rows_printed(b->opt) ? batch_step_mode(b, "MPA_GPU_ROWS") : STEP_HOST;
 	const StepMode fin = (b->opt.flag & MPA_MF_NO_ALIGN) ? STEP_HOST : batch_step_mode(b, "MPA_GPU_FINISH");
 	b->flat.reset(), b->flat_cs_src = 0;
+	// MPA_GPU_FORMAT=1: the text behind the finish step of the same device call, for a batch whose names the stream
+	// pipeline handed over.  It needs the finish step on the device, and the cs strings and rows the options print from their device walks
+	const bool fmt_asked = b->fmt_names && !(b->opt.flag & MPA_MF_NO_ALIGN) && format_knob() == 1;
 	if (mode == STEP_HOST && cs == STEP_HOST && rows == STEP_HOST && fin == STEP_HOST && b->spans_src == 0 && !spans_dump_on()) {   // the three steps in one pass over the queries
+		if (fmt_asked && timing_on()) fprintf(stderr, "[mpa-timing] format declined (the finish step does not run on the device)\n");
 		parallel_for(b->n_threads, (int64_t)b->qs.size(), [&](int64_t qi) {
 			QueryState &qs = b->qs[qi];
 			for (AlignPlan &pl : qs.plans) {
@@ -889,11 +944,14 @@ static int take_round3_steps(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint
 		{ "residue rows", "residue rows on the GPU", "the formatter builds them" } };
 	const bool on_dev[3] = { mode == STEP_DEVICE, cs == STEP_DEVICE, rows == STEP_DEVICE };
 	bool stats_host = mode == STEP_HOST, stats_dev_ok = on_dev[0];
-	std::string fin_why;
+	std::string fin_why, fmt_why;
+	const bool fin_possible = fin == STEP_DEVICE && on_dev[0] && cs != STEP_MODEL && rows != STEP_MODEL;
+	const char *fmt_pre = !fmt_asked ? nullptr : !fin_possible ? "the finish step does not run on the device" : cs_printed(b->opt) && cs != STEP_DEVICE ? "cs strings are printed and MPA_GPU_CS is not 1" :
+	                      rows_printed(b->opt) && rows != STEP_DEVICE ? "residue rows are printed and MPA_GPU_ROWS is not 1" : nullptr;
 	if (on_dev[0] || on_dev[1] || on_dev[2]) {
 		const double t0 = now_ms();
 		bool ran = false;
-		const int rc = walks_on_device(b, b->dp_ctx, on_dev[0], on_dev[1], on_dev[2], &ran, fin == STEP_DEVICE && on_dev[0] && cs != STEP_MODEL && rows != STEP_MODEL, &fin_why);
+		const int rc = walks_on_device(b, b->dp_ctx, on_dev[0], on_dev[1], on_dev[2], &ran, fin_possible, &fin_why, fmt_asked && !fmt_pre, &fmt_why);
 		if (rc != MPA_OK && rc != MPA_ERR_UNSUPPORTED) return rc;
 		for (int k = 0; k < 3; ++k) {
 			if (!on_dev[k]) continue;
@@ -920,6 +978,12 @@ static int take_round3_steps(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint
 	// one wait, and left b->flat -- it needs the statistics on the device in that call (dp_max is theirs, and so are the records it
 	// reads); declined, the ranking is stage_finish's, with the same result.  model: the shared core on the host (host_finish.cpp).
 	// (flat_cs_src is one value per batch: a batch's walks all take one path, so its carried cs bodies have one source)
+	if (fmt_asked && !(b->flat && b->flat->fmt_n_out >= 0) && timing_on()) {
+		bool any = false;
+		for (const QueryState &qs : b->qs) any = any || !qs.plans.empty();
+		const char *why = fmt_pre ? fmt_pre : !fmt_why.empty() ? fmt_why.c_str() : !b->flat ? (any ? "the finish step did not run on the device" : "no aligned region in the batch") : "the device call declined";
+		fprintf(stderr, "[mpa-timing] format declined (%s)\n", why);
+	}
 	if (b->flat) return MPA_OK;
 	if (fin == STEP_DEVICE) {
 		bool any = false;

@@ -86,6 +86,9 @@ struct mpa_batch_s {
 	// (null: stage_finish ranked the regions and mpa_batch_finish flattens them), and where its cs bodies came from (Region::cs_src)
 	std::unique_ptr<mpa_result_s> flat;
 	int flat_cs_src = 0;
+	// MPA_GPU_FORMAT=1: the batch's query names, handed over by the stream pipeline before the DP stage when it
+	// will want the batch's text (null: nobody formats this batch, or not on the device)
+	const char *const *fmt_names = nullptr;
 	~mpa_batch_s() { free(sp_pool1); }
 };
 

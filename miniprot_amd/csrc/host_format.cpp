@@ -300,9 +300,222 @@ static void put_gtf(std::string &s, const mpa_idx_s *mi, const mpa_mapopt_t &opt
 	}
 }
 
+// ---- MPA_GPU_FORMAT: the host side of the shared core (format_core.h) ---------------------------------------
+int format_knob()
+{
+	const char *e = getenv("MPA_GPU_FORMAT");
+	if (!e || !*e) return 0;
+	return !strcmp(e, "model") ? 2 : atoi(e) != 0 ? 1 : 0;
+}
+
+bool format_opt_from(const mpa_mapopt_t &opt, FmtOpt &o)
+{
+	memset(&o, 0, sizeof o);
+	o.flag = opt.flag, o.out_n = opt.out_n, o.out_sim = opt.out_sim, o.out_cov = opt.out_cov, o.gff_delim = opt.gff_delim;
+	const char *prefix = opt.gff_prefix ? opt.gff_prefix : "MP";
+	const size_t n = strlen(prefix);
+	if (n > FORMAT_PREFIX_MAX) return false;
+	memcpy(o.prefix, prefix, n), o.prefix_len = (int32_t)n;
+	return true;
+}
+
+// does the text of this hit hold a PAF line (and so a cs string) / residue rows?
+static inline bool prints_paf(uint32_t flag)
+{
+	const bool residues = (flag & (MPA_MF_SHOW_RESIDUE | MPA_MF_SHOW_TRANS)) != 0;
+	return flag & MPA_MF_GTF ? residues : !(flag & MPA_MF_NO_PAF);
+}
+
+void format_input(const mpa_idx_s *mi, const mpa_mapopt_t &opt, const mpa_qbatch_t *q, const char *const *names, const mpa_result_s *r, bool build, FormatInput &in)
+{
+	const int32_t n_seq = q->n_seq;
+	const size_t nh = r->hits.size();
+	in.qname_off.assign((size_t)n_seq + 1, 0), in.qname.clear();
+	for (int32_t i = 0; i < n_seq; ++i) in.qname += names[i], in.qname_off[(size_t)i + 1] = (int64_t)in.qname.size();
+	const size_t nc = mi->ctg.size();
+	in.cname_off.assign(nc + 1, 0), in.clen.assign(nc, 0), in.cname.clear();
+	for (size_t c = 0; c < nc; ++c) in.cname += mi->ctg[c].name, in.cname_off[c + 1] = (int64_t)in.cname.size(), in.clen[c] = mi->ctg[c].len;
+	in.cs.clear(), in.rows.clear(), in.cs_text.clear(), in.rows_text.clear();
+	const bool want_cs = prints_paf(opt.flag) && !(opt.flag & MPA_MF_NO_CS), want_rows = (opt.flag & (MPA_MF_SHOW_RESIDUE | MPA_MF_SHOW_TRANS)) != 0;
+	bool cs_missing = false, rows_missing = false;
+	for (size_t h = 0; h < nh; ++h) {
+		if (!r->hits[h].has_aln) continue;
+		cs_missing |= want_cs && (r->cs.empty() || !r->cs[h].present);
+		rows_missing |= want_rows && (r->rows.empty() || !r->rows[h].present);
+	}
+	const char *cs_text = r->cs_text.data(), *rows_text = r->rows_text.data();
+	size_t cs_bytes = r->cs_text.size(), rows_bytes = r->rows_text.size();
+	for (size_t h = 0; h < r->cs.size(); ++h) in.cs.push_back(FinCsRef{ r->cs[h].off, r->cs[h].len, r->cs[h].present });
+	for (size_t h = 0; h < r->rows.size(); ++h) in.rows.push_back(FinRowsRef{ r->rows[h].off, r->rows[h].width, r->rows[h].n_sta, r->rows[h].present, 0 });
+	if (build && (cs_missing || rows_missing)) {                 // the host's walks for what no device walk brought along
+		mpa_mapopt_t both = opt;
+		both.flag |= MPA_MF_SHOW_RESIDUE | MPA_MF_SHOW_TRANS;
+		if (cs_missing) in.cs.resize(nh, FinCsRef{ 0, 0, 0 }), in.cs_text = r->cs_text;
+		if (rows_missing) in.rows.resize(nh, FinRowsRef{ 0, 0, 0, 0, 0 }), in.rows_text = r->rows_text;
+		for (int32_t i = 0; i < n_seq; ++i)
+			for (int64_t h = r->hit_off[(size_t)i]; h < r->hit_off[(size_t)i + 1]; ++h) {
+				const mpa_hit_t &x = r->hits[(size_t)h];
+				if (!x.has_aln) continue;
+				const char *seq = q->seqs + q->q_off[i];
+				const uint32_t *cig = r->cigars.data() + x.cigar_off;
+				if (cs_missing && !in.cs[(size_t)h].present) {
+					std::string body;
+					put_cs_body(body, mi, seq + x.qs, (int32_t)x.vid, x.vs, x.ve, cig, x.n_cigar);
+					in.cs[(size_t)h] = FinCsRef{ (int64_t)in.cs_text.size(), (int32_t)body.size(), 1 };
+					in.cs_text += body;
+				}
+				if (rows_missing && !in.rows[(size_t)h].present) {   // five lines behind their six-byte prefixes: four rows of one width, the STA bytes
+					std::string t;
+					put_residues(t, mi, both, seq, x, cig);
+					const size_t w = t.find('\n') - 6, sta0 = 4 * (w + 7) + 6, n_sta = t.size() - sta0 - 1;
+					in.rows[(size_t)h] = FinRowsRef{ (int64_t)in.rows_text.size(), (int32_t)w, (int32_t)n_sta, 1, 0 };
+					for (size_t k = 0; k < 4; ++k) in.rows_text.append(t, k * (w + 7) + 6, w);
+					in.rows_text.append(t, sta0, n_sta);
+				}
+			}
+		if (cs_missing) cs_text = in.cs_text.data(), cs_bytes = in.cs_text.size();
+		if (rows_missing) rows_text = in.rows_text.data(), rows_bytes = in.rows_text.size();
+	}
+	FormatSizes &z = in.z;
+	z = FormatSizes{};
+	z.n_query = n_seq, z.n_hit = z.n_place = (int64_t)nh, z.n_words = (int64_t)r->cigars.size(), z.n_feat = (int64_t)r->feats.size(), z.cs_bytes = (int64_t)cs_bytes, z.rows_bytes = (int64_t)rows_bytes;
+	z.qname_bytes = (int64_t)in.qname.size(), z.n_ctg = (int64_t)nc, z.cname_bytes = (int64_t)in.cname.size(), z.has_cs = !in.cs.empty(), z.has_rows = !in.rows.empty();
+	FmtSrc &S = in.S;
+	S.hits = r->hits.data(), S.hit_off = r->hit_off.data(), S.cigars = r->cigars.data(), S.feats = r->feats.data();
+	S.cs = in.cs.empty() ? nullptr : in.cs.data(), S.cs_text = cs_text, S.rows = in.rows.empty() ? nullptr : in.rows.data(), S.rows_text = rows_text;
+	S.q_off = q->q_off, S.qname = in.qname.data(), S.qname_off = in.qname_off.data(), S.cname = in.cname.data(), S.cname_off = in.cname_off.data(), S.clen = in.clen.data();
+}
+
+bool format_tables_ok(const FormatInput &in)
+{
+	const FormatSizes &z = in.z;
+	const FmtSrc &S = in.S;
+	if (z.n_query <= 0 || S.hit_off[0] != 0 || S.hit_off[z.n_query] != z.n_hit) return false;
+	if ((S.cs && (int64_t)in.cs.size() != z.n_hit) || (S.rows && (int64_t)in.rows.size() != z.n_hit)) return false;
+	for (int64_t i = 0; i < z.n_query; ++i) {
+		const int64_t ql = S.q_off[i + 1] - S.q_off[i];
+		if (S.hit_off[i + 1] < S.hit_off[i] || S.hit_off[i + 1] > z.n_hit || ql < 0 || ql > INT32_MAX) return false;
+	}
+	for (int64_t h = 0; h < z.n_hit; ++h) {
+		const mpa_hit_t &x = S.hits[h];
+		if ((int64_t)(x.vid >> 1) >= z.n_ctg) return false;
+		if (!x.has_aln) continue;
+		if (x.n_cigar < 0 || x.cigar_off < 0 || x.cigar_off + x.n_cigar > z.n_words || x.n_feat < 0 || x.feat_off < 0 || x.feat_off + x.n_feat > z.n_feat) return false;
+		if (S.cs && S.cs[h].present && (S.cs[h].len < 0 || S.cs[h].off < 0 || S.cs[h].off + S.cs[h].len > z.cs_bytes)) return false;
+		if (S.rows && S.rows[h].present) {
+			const FinRowsRef &w = S.rows[h];
+			if (w.width < 0 || w.n_sta < 0 || w.off < 0 || w.off + 4 * (int64_t)w.width + w.n_sta > z.rows_bytes) return false;
+		}
+	}
+	return true;
+}
+
+// Room for the text and the id places from what the host has without looking at a hit's numbers: a fixed allowance for the fields of
+// a line (an integer prints in at most 20 bytes), 11 bytes per CIGAR word, the carried bytes, the names wherever a line repeats them
+void format_bounds(const FmtOpt &o, FormatInput &in)
+{
+	FormatSizes &z = in.z;
+	const FmtSrc &S = in.S;
+	int64_t text = 0, ids = 0;
+	for (int64_t i = 0; i < z.n_query; ++i) {
+		const int64_t qn = S.qname_off[i + 1] - S.qname_off[i];
+		text += qn + 128;                                        // the -u line
+		for (int64_t h = S.hit_off[i]; h < S.hit_off[i + 1]; ++h) {
+			const mpa_hit_t &x = S.hits[h];
+			const int64_t c = x.vid >> 1, cn = S.cname_off[c + 1] - S.cname_off[c];
+			const int64_t line = 400 + cn + 2 * qn + 2 * o.prefix_len;   // a GFF3 / GTF line: up to ten numbers, its keywords, the names, two ids
+			text += 640 + qn + cn;                                   // the PAF line's fields and tags
+			if (!x.has_aln) continue;
+			text += 11 * (int64_t)x.n_cigar;
+			if (S.cs && S.cs[h].present) text += S.cs[h].len;
+			if (S.rows && S.rows[h].present) text += 4 * ((int64_t)S.rows[h].width + 7) + S.rows[h].n_sta + 7;
+			if (o.flag & (MPA_MF_GFF | MPA_MF_GTF)) text += (2 + 2 * (int64_t)x.n_feat) * line, ids += 3 + 4 * (int64_t)x.n_feat;
+		}
+	}
+	z.text_cap = text, z.id_cap = ids;
+}
+
+const char *format_decline_reason(const FmtCounts &tot, int64_t text_cap, int64_t id_cap)
+{
+	if (tot.bad != 0) return "a blen of 0, or a cs string or rows that a hit does not carry";
+	if (tot.bytes > text_cap || tot.ids > id_cap) return "more text than the block was sized for";
+	if (tot.n_out > FORMAT_ID_LIMIT) return "ids reach seven digits";
+	return nullptr;
+}
+
+const char *format_host(const FmtOpt &o, const FormatInput &in, FormatText &t)
+{
+	const int64_t nq = in.z.n_query;
+	std::vector<FmtAt> at((size_t)in.z.n_hit);
+	std::vector<FmtCounts> cnt((size_t)nq), off((size_t)nq + 1);
+	for (int64_t i = 0; i < nq; ++i) format_size_core<FormatSerial>(o, in.S, (int32_t)i, at.data(), &cnt[(size_t)i]);
+	format_scan_serial(cnt.data(), nq, off.data());
+	t.tot = off[(size_t)nq];
+	if (const char *why = format_decline_reason(t.tot, INT64_MAX, INT64_MAX)) return why;
+	t.text.assign((size_t)t.tot.bytes, '\0'), t.id_at.assign((size_t)t.tot.ids, 0);
+	for (int64_t i = 0; i < nq; ++i) {
+		const int64_t h0 = in.S.hit_off[i], n_reg = in.S.hit_off[i + 1] - h0;
+		for (int64_t j = 0; j < n_reg; ++j)
+			if (at[(size_t)(h0 + j)].rank >= 0) format_write_core<FormatSerial>(o, in.S, (int32_t)i, j, at[(size_t)(h0 + j)], off[(size_t)i], &t.text[0], t.id_at.data());
+		if (off[(size_t)i + 1].n_out == off[(size_t)i].n_out && (o.flag & MPA_MF_SHOW_UNMAP)) format_unmap_core<FormatSerial>(o, in.S, (int32_t)i, off[(size_t)i], &t.text[0]);
+	}
+	return nullptr;
+}
+
+int64_t format_take_text(mpa_result_s *r, int32_t n_query, int64_t *id_io, char **out)
+{
+	if (!r || r->fmt_n_out < 0) return -1;
+	std::string text;
+	std::vector<int64_t> id_at;
+	text.swap(r->fmt_text), id_at.swap(r->fmt_id_at);
+	const int64_t n_out = r->fmt_n_out;
+	r->fmt_n_out = -1;
+	if (!format_patch_ids(&text[0], id_at.data(), (int64_t)id_at.size(), n_out, *id_io)) {
+		if (timing_on()) fprintf(stderr, "[mpa-timing] format declined (ids reach seven digits)\n");
+		return -1;
+	}
+	*id_io += n_out;
+	if (timing_on()) fprintf(stderr, "[mpa-timing] format on the GPU: %d queries, %lld hits printed, %lld bytes down, %lld id fields\n", (int)n_query, (long long)n_out, (long long)text.size(), (long long)id_at.size());
+	char *buf = (char*)malloc(text.size() + 1);
+	memcpy(buf, text.data(), text.size());
+	buf[text.size()] = 0;
+	*out = buf;
+	return (int64_t)text.size();
+}
+
 } // namespace mpa
 
 using namespace mpa;
+
+// MPA_GPU_FORMAT=model: the batch's text through the shared core with a team of one.  -1: declined (said so under MPA_TIMING=1)
+static int64_t format_batch_model(const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, const char *const *names, const mpa_result_t *r, int64_t *id_io, char **out)
+{
+	const double t0 = now_ms();
+	const char *why = nullptr;
+	FmtOpt o;
+	FormatInput in;
+	FormatText t;
+	if (q->n_seq <= 0) why = "no queries";
+	else if (!format_opt_from(*opt, o)) why = "a gff_prefix longer than 64 bytes";
+	else {
+		format_input(mi, *opt, q, names, r, true, in);
+		why = format_host(o, in, t);
+		if (!why && !format_patch_ids(&t.text[0], t.id_at.data(), t.tot.ids, t.tot.n_out, id_io ? *id_io : 0)) why = "ids reach seven digits";
+	}
+	if (why) {
+		if (timing_on()) fprintf(stderr, "[mpa-timing] format declined (%s)\n", why);
+		return -1;
+	}
+	if (id_io) *id_io += t.tot.n_out;
+	if (timing_on())
+		fprintf(stderr, "[mpa-timing] %-28s %9.3f ms  %d queries, %lld hits printed, %lld bytes, %lld id fields\n", "format: shared core", now_ms() - t0, (int)q->n_seq, (long long)t.tot.n_out,
+		        (long long)t.tot.bytes, (long long)t.tot.ids);
+	char *buf = (char*)malloc(t.text.size() + 1);
+	memcpy(buf, t.text.data(), t.text.size());
+	buf[t.text.size()] = 0;
+	*out = buf;
+	return (int64_t)t.text.size();
+}
 
 // mp_write_output (format.c:453-473) applied to a whole batch, with the output filters and the running hit id of
 // worker_pipeline step 2 (map.c:298-311).
@@ -431,12 +644,16 @@ extern "C" int64_t mpa_format_paf(const mpa_idx_t *mi, const mpa_mapopt_t *opt, 
 {
 	mpa_mapopt_t o = *opt;
 	o.flag &= ~(uint32_t)(MPA_MF_GFF | MPA_MF_GTF | MPA_MF_NO_PAF);
-	return format_batch(mi, &o, q, names, r, nullptr, out);
+	return mpa::guarded<int64_t>((int64_t)MPA_ERR_HIP, [&] {
+		if (format_knob() == 2) { const int64_t n = format_batch_model(mi, &o, q, names, r, nullptr, out); if (n >= 0) return n; }
+		return format_batch(mi, &o, q, names, r, nullptr, out);
+	});
 }
 
 static int64_t mpa_format_output_impl(const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, const char *const *names,
                                      const mpa_result_t *r, int64_t *id_io, char **out)
 {
+	if (format_knob() == 2) { const int64_t n = format_batch_model(mi, opt, q, names, r, id_io, out); if (n >= 0) return n; }
 	return format_batch(mi, opt, q, names, r, id_io, out);
 }
 

@@ -127,6 +127,7 @@ static int mpa_map_batches_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_m
 		work[k].q = batches[g];
 		trace("sketch", k, "begin");
 		{ StageClock sc(4); work[k].b = batch_sketch_phase(true, mi, opt, &work[k].q, n_threads); }
+		if (work[k].b && names && format_knob() == 1) work[k].b->fmt_names = names[g];   // (MPA_GPU_FORMAT=1: the DP lane's last call writes the text)
 		trace("sketch", k, "end");
 		return work[k].b ? MPA_OK : MPA_ERR_ARG;
 	};
@@ -161,7 +162,9 @@ static int mpa_map_batches_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_m
 		work[k].b = nullptr;
 		char *t = nullptr;
 		int64_t tl = 0;
-		if (names) tl = mpa_format_output(mi, opt, &work[k].q, names[g], r, id_io, &t);   // (batches finish in input order: the hit ids run on)
+		// (batches finish in input order: the hit ids run on.  MPA_GPU_FORMAT=1: the text came down with the result and is patched with the id)
+		if (names && (tl = format_take_text(r, work[k].q.n_seq, id_io, &t)) < 0) tl = mpa_format_output(mi, opt, &work[k].q, names[g], r, id_io, &t);
+		if (r) r->fmt_n_out = -1, std::string().swap(r->fmt_text), std::vector<int64_t>().swap(r->fmt_id_at);
 		results[j] = r;
 		if (names) text[j] = t, text_len[j] = tl;
 		trace("finish", k, "end");

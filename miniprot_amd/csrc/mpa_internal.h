@@ -18,6 +18,7 @@
 #include "plans_core.h"
 #include "spans_core.h"
 #include "finish_core.h"
+#include "format_core.h"
 
 namespace mpa {
 
@@ -136,6 +137,12 @@ struct mpa_result_s {
 	struct RowsRef { int64_t off; int32_t width, n_sta, present; };
 	std::vector<RowsRef> rows;
 	std::string rows_text;
+	// (MPA_GPU_FORMAT=1, inside the stream pipeline only) the batch's output text as the device wrote it behind the finish step, with ids
+	// relative to the batch, where its id fields lie and how many hits it prints (fmt_n_out < 0: none).  The pipeline takes it out before
+	// the result reaches the caller (format_take_text); no accessor and no formatter looks at it
+	std::string fmt_text;
+	std::vector<int64_t> fmt_id_at;
+	int64_t fmt_n_out = -1;
 };
 
 namespace mpa {
@@ -292,9 +299,10 @@ struct AlnRowsIO { int64_t *slot_off = nullptr; const AlnRowsOut *out = nullptr;
 // slots and CIGAR words where they lie; nothing of the walks' own output is downloaded then (io.out, cs.out, rows.out stay null) and
 // fin->flat is the result.
 struct FinishResident;
+struct FormatResident;
 int dev_aln_walks_stage(mpa_ctx_t *ctx, const AlnWalkSizes &z, AlnStatsIO &io, AlnCsIO &cs, AlnRowsIO &rows);
 int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const AlnRowsParams &rp, const int8_t *mat, const AlnWalkSizes &z, AlnStatsIO &io, AlnCsIO &cs,
-                  AlnRowsIO &rows, bool dev_cig = false, FinishResident *fin = nullptr);
+                  AlnRowsIO &rows, bool dev_cig = false, FinishResident *fin = nullptr, FormatResident *fmt = nullptr);
 
 // ---- accepted spans and region CIGARs on the device (MPA_GPU_SPANS=1; driver: stats_run.hip; kernels: span_kernels.hip; code:
 // spans_core.h) ----
@@ -349,6 +357,51 @@ void finish_model(const FinParams &p, const FinishSizes &z, const FinishTables &
 void finish_flat_to_result(const FinishFlat &f, int64_t n_query, mpa_result_s *res);
 // every index the step follows, checked once for both paths (the test hook; the batch's own tables are made right)
 bool finish_tables_ok(const FinishSizes &z, const FinishTables &t);
+
+// ---- the output text of a batch (MPA_GPU_FORMAT; code: format_core.h; kernels: format_kernels.hip; driver:
+// stats_run.hip; the host side and the model: host_format.cpp) ----
+// The sizes of a call: the flat result's arrays (has_cs / has_rows: it carries cs bodies / rows), the name pools, and the room for the text
+// and the id places (bounds: format_bounds).  dev_format_stage sizes the context's pinned blocks and hands out where the caller writes
+// the tables; dev_format sends them up, runs k_format_size, k_format_scan and k_format_write on the context's stream, whose stores put
+// totals, id places and text into a pinned block, and waits once: out points into that pinned memory of the context, valid until its
+// next call.  out.declined: the kernels wrote no text (a blen of 0, something not carried, or more than the room given) -- the caller
+// formats on the host.  MPA_ERR_UNSUPPORTED from either: a pool or pinned block could not grow.
+struct FormatSizes { int64_t n_query, n_hit, n_words, n_feat, cs_bytes, rows_bytes, qname_bytes, n_ctg, cname_bytes, text_cap, id_cap, n_place; int32_t has_cs, has_rows; };   // n_place: entries of at[] (the hits that may be printed)
+struct FormatTables { int64_t *hit_off = nullptr, *q_off = nullptr, *qname_off = nullptr, *cname_off = nullptr, *clen = nullptr; mpa_hit_t *hits = nullptr; FinCsRef *cs = nullptr;
+                      FinRowsRef *rows = nullptr; mpa_feat_t *feats = nullptr; uint32_t *cigars = nullptr; char *cs_text = nullptr, *rows_text = nullptr, *qname = nullptr, *cname = nullptr; };
+struct FormatOut { const char *text = nullptr; const int64_t *id_at = nullptr; FmtCounts tot = { 0, 0, 0, 0 }; bool declined = false; };
+int dev_format_stage(mpa_ctx_t *ctx, const FormatSizes &z, FormatTables &t);
+int dev_format(mpa_ctx_t *ctx, const FmtOpt &o, const FormatSizes &z, FormatOut &out);
+int dev_format_last(const mpa_ctx_t *ctx, int64_t out[6]);
+// The same three kernels inside dev_aln_walks (MPA_GPU_FORMAT=1, behind the finish step of the same call: `fmt` next to `fin`), on the
+// call's stream behind k_finish_gather and in front of its one wait.  They read the hits where the finish step left them (FmtSrc::rec):
+// nothing of the result goes up again, only the names and lengths staged through dev_format_stage with z.n_hit = 0 and z.n_place = the
+// aligned regions.  In: o, z (staged); out: what dev_format gives.  A pool that cannot grow declines the whole call, as for the finish step
+struct FormatResident { FmtOpt o; FormatSizes z; FormatOut out; };
+// The host side (host_format.cpp).  format_knob: MPA_GPU_FORMAT, read per call -- 0 unset, 2 model.  format_opt_from: the options the
+// step reads (false: a gff_prefix longer than FORMAT_PREFIX_MAX).  FormatInput: a result and its names as the tables of a call, owning
+// what it had to build (names pools; with `build`, the cs bodies and rows of hits that carry none, by the host's walks).
+// format_tables_ok: every index the step follows.  format_bounds: text_cap / id_cap from what the host already has.  format_host:
+// the three stages with a team of one; nullptr, or why it declined.  format_finish_text: the patch with id0 into a malloc'ed string.
+int format_knob();                                        // 0 unset, 1 the device stage inside a batch's call, 2 model
+bool format_opt_from(const mpa_mapopt_t &opt, FmtOpt &o);
+struct FormatInput {
+	FormatSizes z = {};
+	FmtSrc S = {};
+	std::vector<int64_t> qname_off, cname_off, clen;
+	std::string qname, cname, cs_text, rows_text;
+	std::vector<FinCsRef> cs;
+	std::vector<FinRowsRef> rows;
+};
+void format_input(const mpa_idx_s *mi, const mpa_mapopt_t &opt, const mpa_qbatch_t *q, const char *const *names, const mpa_result_s *r, bool build, FormatInput &in);
+bool format_tables_ok(const FormatInput &in);
+void format_bounds(const FmtOpt &o, FormatInput &in);
+struct FormatText { std::string text; std::vector<int64_t> id_at; FmtCounts tot = { 0, 0, 0, 0 }; };
+const char *format_host(const FmtOpt &o, const FormatInput &in, FormatText &t);
+const char *format_decline_reason(const FmtCounts &tot, int64_t text_cap, int64_t id_cap);
+// the pipeline's output stage: the text a batch's device call left in its result (fmt_n_out >= 0) patched with *id_io, which advances, into
+// a malloc'ed string; -1: there is none, or ids reach seven digits (said under MPA_TIMING=1) -- the caller formats.  The result never keeps it
+int64_t format_take_text(mpa_result_s *r, int32_t n_query, int64_t *id_io, char **out);
 
 // ---- DP round 2 from device-resident tasks (MPA_GPU_ROUND2=1; dp_exec.hip) ----
 // What dev_spans_round1 leaves for it: the round-2 tasks where k_spans_emit wrote them (a pool of the context) and the three bounds the

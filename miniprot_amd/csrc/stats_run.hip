@@ -13,22 +13,29 @@
 // dev_aln_walks() reads it in place of an uploaded one when the caller says so (dev_cig).
 // MPA_GPU_FINISH=1 (kernels k_finish_rank, k_finish_scan, k_finish_gather: finish_kernels.hip; code: finish_core.h; DESIGN.md section
 // 4.13) puts the final ranking of the batch's aligned regions and the layout of its flat result here: dev_finish_stage() / dev_finish().
+// MPA_GPU_FORMAT (kernels k_format_size, k_format_scan, k_format_write: format_kernels.hip; code: format_core.h)
+// writes the output text of a flat result: dev_format_stage() / dev_format().
 #include "dev_ctx.h"
 #include "spans_core.h"
 #include "dp_results_core.h"
 #include "stats_kernels.hip"
 #include "span_kernels.hip"
 #include "finish_kernels.hip"
+#include "format_kernels.hip"
 
 namespace mpa {
 
-// (the layouts of the blocks: StatsLayout, SpansLayout, AsmLayout, FinishLayout in dev_layout.h)
+// (the layouts of the blocks: StatsLayout, SpansLayout, AsmLayout, FinishLayout, FormatLayout in dev_layout.h)
 
 // the finish step's parts (below), which dev_aln_walks runs behind its own kernels
 struct FinishSrc { const uint32_t *words; const void *feats; const char *cs_text, *rows_text; const AlnStatsOut *st; const AlnCsOut *cs; const AlnRowsOut *rows; int32_t show_trans; };
 static int finish_prepare(mpa_ctx_t *ctx, const FinishSizes &z);
 static int finish_launch(mpa_ctx_t *ctx, const FinParams &p, const FinishSizes &z, const FinishSrc *src);
 static int finish_collect(mpa_ctx_t *ctx, const FinishSizes &z, int64_t waits, FinishFlat &flat);
+// ... and the format step's (further below), behind the finish step's in the same call
+static int format_prepare(mpa_ctx_t *ctx, const FormatSizes &z);
+static int format_launch(mpa_ctx_t *ctx, const FmtOpt &o, const FormatSizes &z, const FinishSizes *fin, const FinishSrc *src);
+static int format_collect(mpa_ctx_t *ctx, const FormatSizes &z, int64_t waits, FormatOut &out);
 
 // The pinned blocks of a call for any non-empty subset of the walks, the one that goes up for the caller to fill: jobs, CIGAR words,
 // text and, next to the jobs, cs.slot_off[n_jobs + 1] / rows.slot_off[n_jobs + 1].  z.n_feat < 0: no statistics (the statistics stay
@@ -57,7 +64,7 @@ int dev_aln_walks_stage(mpa_ctx_t *ctx, const AlnWalkSizes &z, AlnStatsIO &io, A
 // rows.slot_off[j] as aln_rows_core.h lays it out -- all of it pinned memory of the context, valid until its next call.
 // MPA_ERR_UNSUPPORTED: a pool could not grow -- the caller keeps the host's walks.
 int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const AlnRowsParams &rp, const int8_t *mat, const AlnWalkSizes &z, AlnStatsIO &io, AlnCsIO &cs,
-                  AlnRowsIO &rows, bool dev_cig, FinishResident *fin)
+                  AlnRowsIO &rows, bool dev_cig, FinishResident *fin, FormatResident *fmt)
 {
 	const StatsLayout L(z);
 	const int64_t n_jobs = z.n_jobs;
@@ -80,6 +87,8 @@ int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const 
 	// read where it lies and is not downloaded.  Whatever can decline does so here, before anything is launched
 	if (fin && !stats) { set_error("dev_aln_walks: the finish step needs the statistics in the same call"); return MPA_ERR_ARG; }
 	if (fin) { const int rc = finish_prepare(ctx, fin->z); if (rc != MPA_OK) return rc; }
+	if (fmt && !fin) { set_error("dev_aln_walks: the format step needs the finish step in the same call"); return MPA_ERR_ARG; }
+	if (fmt) { const int rc = format_prepare(ctx, fmt->z); if (rc != MPA_OK) return rc; }
 	const int64_t waits0 = ctx->n_waits.load();
 	hipStream_t s = ctx->stream;
 	char *hu = ctx->walks.h_stats_up.as<char>();
@@ -123,11 +132,13 @@ int dev_aln_walks(mpa_ctx_t *ctx, mpa_idx_s *mi, const AlnStatsParams &p, const 
 		const char *d_st = ctx->walks.st_out.as<char>(), *d_cs = cs_on ? ctx->walks.cs_out.as<char>() : nullptr, *d_rows = rows_on ? ctx->walks.rows_out.as<char>() : nullptr;
 		const FinishSrc src{ dcig, (const void*)L.feat.in(d_st), cs_on ? L.body.in(d_cs) : nullptr, rows_on ? L.rbody.in(d_rows) : nullptr, L.out.in(d_st),
 		                     cs_on ? L.cs_out.in(d_cs) : nullptr, rows_on ? L.rows_out.in(d_rows) : nullptr, rp.show_trans };
-		const int rc = finish_launch(ctx, fin->p, fin->z, &src);
+		int rc = finish_launch(ctx, fin->p, fin->z, &src);
 		if (rc != MPA_OK) return rc;
+		if (fmt && (rc = format_launch(ctx, fmt->o, fmt->z, &fin->z, &src)) != MPA_OK) return rc;   // (MPA_GPU_FORMAT=1) the text, behind the gather
 		io.out = nullptr, io.feat = nullptr, cs.out = nullptr, cs.body = nullptr, rows.out = nullptr, rows.body = nullptr;   // (not downloaded)
 	}
 	HIP_TRY(wait_stream(ctx, s));
+	if (fmt) { fmt->out = FormatOut(); const int rc = format_collect(ctx, fmt->z, ctx->n_waits.load() - waits0, fmt->out); if (rc != MPA_OK) return rc; }
 	if (fin) return finish_collect(ctx, fin->z, ctx->n_waits.load() - waits0, fin->flat);
 	return MPA_OK;
 }
@@ -354,6 +365,104 @@ int dev_finish_last(const mpa_ctx_t *ctx, int64_t out[6])
 {
 	if (!ctx || !out) { set_error("dev_finish_last: missing arguments"); return MPA_ERR_ARG; }
 	for (int k = 0; k < 6; ++k) out[k] = ctx->finish.last[k];
+	return MPA_OK;
+}
+
+// ---- MPA_GPU_FORMAT -------------------------------------------------------------------------------------------------------------
+static bool format_sizes_ok(const FormatSizes &z)
+{
+	const int64_t lim = (int64_t)1 << 40;
+	return z.n_query > 0 && z.n_query < INT32_MAX && z.n_hit >= 0 && z.n_hit <= (int64_t)1 << 28 && z.n_words >= 0 && z.n_words < lim && z.n_feat >= 0 && z.n_feat < lim && z.cs_bytes >= 0 &&
+	       z.cs_bytes < lim && z.rows_bytes >= 0 && z.rows_bytes < lim && z.qname_bytes >= 0 && z.qname_bytes < lim && z.n_ctg > 0 && z.n_ctg < INT32_MAX && z.cname_bytes >= 0 &&
+	       z.cname_bytes < lim && z.text_cap >= 0 && z.text_cap < lim && z.id_cap >= 0 && z.id_cap < lim && z.n_place >= 0 && z.n_place <= (int64_t)1 << 28;
+}
+
+int dev_format_stage(mpa_ctx_t *ctx, const FormatSizes &z, FormatTables &t)
+{
+	t = FormatTables();
+	if (!format_sizes_ok(z)) { set_error("GPU format: no queries, or too many hits for one launch"); return MPA_ERR_UNSUPPORTED; }
+	if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed"); return MPA_ERR_HIP; }
+	const FormatLayout L(z);
+	if (ctx->format.h_fmt_up.ensure(L.up_bytes) != MPA_OK || ctx->format.h_fmt_down.ensure(L.down_bytes) != MPA_OK) return MPA_ERR_UNSUPPORTED;
+	char *hu = ctx->format.h_fmt_up.as<char>();
+	t.hit_off = L.hit_off.in(hu), t.q_off = L.q_off.in(hu), t.qname_off = L.qname_off.in(hu), t.cname_off = L.cname_off.in(hu), t.clen = L.clen.in(hu), t.hits = L.hits.in(hu);
+	t.cs = z.has_cs ? L.cs.in(hu) : nullptr, t.rows = z.has_rows ? L.rows.in(hu) : nullptr, t.feats = L.feats.in(hu), t.cigars = L.cigars.in(hu);
+	t.cs_text = L.cs_text.in(hu), t.rows_text = L.rows_text.in(hu), t.qname = L.qname.in(hu), t.cname = L.cname.in(hu);
+	return MPA_OK;
+}
+
+// The three parts of a call, as for the finish step.  format_prepare: the pools sized -- what can decline, before anything is launched.
+// format_launch: the staged block up, then size, scan and write on the context's stream; scan and write store into the pinned block.
+// `fin` (inside dev_aln_walks): the hits are read where the finish step of the same call left them, and only the names went up.
+// format_collect, behind the caller's wait: the totals, and whether the kernels wrote the text.
+static int format_prepare(mpa_ctx_t *ctx, const FormatSizes &z)
+{
+	if (!format_sizes_ok(z)) { set_error("dev_format: no queries, or too many hits for one launch"); return MPA_ERR_ARG; }
+	const FormatLayout L(z);
+	if (L.up_bytes > ctx->format.h_fmt_up.cap || L.down_bytes > ctx->format.h_fmt_down.cap) { set_error("dev_format: the staging block was not sized for this call"); return MPA_ERR_ARG; }
+	tl_alloc_failed = false;
+	if (ctx->format.fmt_in.ensure(L.up_bytes) != MPA_OK || ctx->format.fmt_mid.ensure(L.mid_bytes) != MPA_OK) return tl_alloc_failed ? MPA_ERR_UNSUPPORTED : MPA_ERR_HIP;
+	return MPA_OK;
+}
+
+static int format_launch(mpa_ctx_t *ctx, const FmtOpt &o, const FormatSizes &z, const FinishSizes *fin, const FinishSrc *src)
+{
+	const FormatLayout L(z);
+	hipStream_t s = ctx->stream;
+	char *din = ctx->format.fmt_in.as<char>(), *mid = ctx->format.fmt_mid.as<char>(), *hd = ctx->format.h_fmt_down.as<char>();
+	*L.head.in(hd) = FmtCounts{ 0, 0, 0, -1 };           // (what the host reads if the scan never ran)
+	HIP_TRY(hipMemcpyAsync(din, ctx->format.h_fmt_up.p, L.up_bytes - 16, hipMemcpyHostToDevice, s));
+	FmtSrc S;
+	S.hits = L.hits.in(din), S.hit_off = L.hit_off.in(din), S.cigars = L.cigars.in(din), S.feats = L.feats.in(din);
+	S.cs = z.has_cs ? L.cs.in(din) : nullptr, S.cs_text = L.cs_text.in(din), S.rows = z.has_rows ? L.rows.in(din) : nullptr, S.rows_text = L.rows_text.in(din);
+	S.q_off = L.q_off.in(din), S.qname = L.qname.in(din), S.qname_off = L.qname_off.in(din), S.cname = L.cname.in(din), S.cname_off = L.cname_off.in(din), S.clen = L.clen.in(din);
+	if (fin) {                                           // (what finish_launch set up in fin_in / fin_mid, and what the walks left)
+		const FinishLayout F(*fin);
+		const char *fin_in = ctx->finish.fin_in.as<char>(), *fin_mid = ctx->finish.fin_mid.as<char>();
+		S.hits = nullptr, S.hit_off = nullptr, S.cs = nullptr, S.rows = nullptr;
+		S.rec = F.rec.in(fin_in), S.first = F.first.in(fin_in), S.out = F.out.in(fin_mid), S.fin_off = F.off.in(fin_mid);
+		S.cigars = src->words, S.feats = (const mpa_feat_t*)src->feats, S.cs_text = src->cs_text, S.rows_text = src->rows_text;
+	}
+	const int32_t nq = (int32_t)z.n_query;
+	hipLaunchKernelGGL(k_format_size, dim3((unsigned)nq), dim3(64), 0, s, o, S, nq, L.at.in(mid), L.cnt.in(mid));
+	HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(k_format_scan, dim3(1), dim3(FORMAT_SCAN), 0, s, (const FmtCounts*)L.cnt.in(mid), nq, L.off.in(mid), L.head.in(hd));
+	HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(k_format_write, dim3((unsigned)nq), dim3(64 * FORMAT_WRITE_WAVES), 0, s, o, S, nq, (const FmtAt*)L.at.in(mid), (const FmtCounts*)L.off.in(mid), L.text.in(hd), z.text_cap,
+	                   L.id_at.in(hd), z.id_cap);
+	HIP_TRY(hipGetLastError());
+	return MPA_OK;
+}
+
+static int format_collect(mpa_ctx_t *ctx, const FormatSizes &z, int64_t waits, FormatOut &out)
+{
+	const FormatLayout L(z);
+	const char *hd = ctx->format.h_fmt_down.as<char>();
+	out.tot = *L.head.in(hd);
+	if (out.tot.bad < 0 || out.tot.bytes < 0 || out.tot.ids < 0 || out.tot.n_out < 0 || out.tot.n_out > z.n_place) { set_error("dev_format: impossible counts"); return MPA_ERR_HIP; }
+	out.declined = format_decline_reason(out.tot, z.text_cap, z.id_cap) != nullptr;
+	out.text = L.text.in(hd), out.id_at = L.id_at.in(hd);
+	int64_t *last = ctx->format.last;
+	last[0] = z.n_query, last[1] = out.tot.n_out, last[2] = out.tot.bytes, last[3] = out.tot.ids, last[4] = waits, last[5] = out.declined;
+	return MPA_OK;
+}
+
+int dev_format(mpa_ctx_t *ctx, const FmtOpt &o, const FormatSizes &z, FormatOut &out)
+{
+	out = FormatOut();
+	HIP_TRY(hipSetDevice(ctx->device));
+	int rc = format_prepare(ctx, z);
+	if (rc != MPA_OK) return rc;
+	const int64_t waits0 = ctx->n_waits.load();
+	if ((rc = format_launch(ctx, o, z, nullptr, nullptr)) != MPA_OK) return rc;
+	HIP_TRY(wait_stream(ctx, ctx->stream));
+	return format_collect(ctx, z, ctx->n_waits.load() - waits0, out);
+}
+
+int dev_format_last(const mpa_ctx_t *ctx, int64_t out[6])
+{
+	if (!ctx || !out) { set_error("dev_format_last: missing arguments"); return MPA_ERR_ARG; }
+	for (int k = 0; k < 6; ++k) out[k] = ctx->format.last[k];
 	return MPA_OK;
 }
 
