@@ -85,6 +85,35 @@ typedef struct { const int32_t *ext_out, *score, *n_cigar, *gids; int64_t n_glob
 int mpa_dbg_dp_run_resident(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *opt, const mpa_qbatch_t *q, int64_t n, const mpa_dp_task_t *tasks,
                             const mpa_dbg_dp_outputs_t *made_up, mpa_dp_rst_t *rst, uint32_t **cigar_pool, int64_t *n_pool, int64_t *rec);
 
+/* DP round 1 and the step behind it in one submission (MPA_GPU_ROUND1), on a context: what mpa_dbg_spans takes for
+ * its round-1 half -- options, queries, plans[n_plan] (SpansPlan, 104 bytes) and segs[n_seg] (SegRec, 24 bytes) -- and, in place of round-1
+ * results, the round-1 task table tasks[n] the plans' task numbers point into (base1 + t_left ...), with the DP options.  The hook stages
+ * the step's block and sends it up without its record section, plans the round on the device from the table, runs it with records and
+ * dense pool assembled on the device, the records copied into the block's record section, k_spans / k_spans_emit / k_task_bounds chained
+ * behind them inside the round's one wait, and only then fetches the dense pool from the spans step's pool.  Out: rst[n] and *cigar_pool
+ * (mpa_free) / *n_pool as mpa_dp_run returns them for the table; span_rec[n_plan] (SpanRec, 80 bytes), tasks2[up to 2 n_plan] / *n_task as
+ * mpa_dbg_spans returns them for those results; bounds[3] (prep chunks, largest nl, largest al of tasks2).  rec[MPA_DBG_ROUND1_REC]: [0] host
+ * waits of the planner, [1] host waits of the round behind it, [2] bytes uploaded by planner, round and step, [3] bytes of task records among
+ * them, [4] bytes downloaded, [5] bytes of CIGAR pool among them, [6] kernels of the step launched inside the round's wait, [7] the
+ * planner's upload, [8] the queries' residues, [9] the step's block as it went up, [10] bytes of its record section, which did not, [11]
+ * bytes of the explicit pool fetch: [2] = [7] + [8] + [9].  Every index the step follows that does not depend on the round's results is
+ * checked first (MPA_ERR_ARG; also without a context: the round has no host model).  Returns MPA_OK, a negative MPA_ERR_* code, or
+ * MPA_DBG_ROUND1_DECLINED (1) for a round that falls back to mpa_dp_run: whatever the device planner declines, a pool or pinned block
+ * that cannot grow, a repeated round; the last error says why. */
+#define MPA_DBG_ROUND1_DECLINED 1
+#define MPA_DBG_ROUND1_REC 12
+int mpa_dbg_round1_chain(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_dpopt_t *dpopt, const mpa_qbatch_t *q, int32_t n_plan, const void *plans,
+                         int32_t n_seg, const void *segs, int64_t n, const mpa_dp_task_t *tasks, mpa_dp_rst_t *rst, void *span_rec, mpa_dp_task_t *tasks2, int32_t *n_task,
+                         int64_t *bounds, uint32_t **cigar_pool, int64_t *n_pool, int64_t *rec);
+
+/* The device guard of the chained step: k_spans, k_spans_emit and k_task_bounds on a context, on plans, segments
+ * and round-1 records as mpa_dbg_spans takes them, with the two words a chained step is guarded by set by the caller on the device -- err,
+ * the round's hand-off error word, and bad, the bad-call word of its results header; at least one must be non-zero (MPA_ERR_ARG otherwise:
+ * with both zero the step is mpa_dbg_spans).  The kernels then read no record of rst1[] and no genome byte: *n_task and bounds[3] come
+ * back 0 whatever rst1[] holds. */
+int mpa_dbg_spans_guard(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_mapopt_t *opt, const mpa_qbatch_t *q, int32_t n_plan, const void *plans, int32_t n_seg, const void *segs,
+                        int64_t n_rst1, const mpa_dp_rst_t *rst1, int32_t err, int64_t bad, int32_t *n_task, int64_t *bounds);
+
 /* The stream plan (miniprot_amd/csrc/stream_plan.h): which streams mpa_map_batches creates for its DP lanes,
  * seeders and planners, in which priority class (0 normal, 1 high, 2 low) and in which order, for the hardware queues of the process.
  * As int32 words: q, lanes, seeders, planners, layout (0 legacy, 1 A, 2 B, 3 C), streams created up front; per lane class, rank in

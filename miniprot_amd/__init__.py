@@ -849,6 +849,56 @@ def dbg_dp_run_resident(ctx, idx, dpopt, queries, tasks, made_up=None):
     return rst, cig, dict(zip(ROUND2_REC, (int(x) for x in rec)))
 
 
+ROUND1_DECLINED = 1  # MPA_DBG_ROUND1_DECLINED (include/mpamd_dbg.h)
+ROUND1_REC = ("plan_waits", "round_waits", "bytes_up", "task_bytes_up", "bytes_down", "pool_bytes_down", "chained_launches", "plan_bytes_up", "residue_bytes", "spans_bytes_up",
+              "rst1_bytes_skipped", "pool_bytes_fetched")
+
+
+def dbg_round1_chain(ctx, idx, mo, dpopt, queries, plans, segs, tasks):
+    """mpa_dbg_round1_chain(): DP round 1 and the step behind it in one submission (MPA_GPU_ROUND1) -- plans (104-byte records) and segs (24)
+    as dbg_spans() takes them and the round-1 task table they point into.  Returns (results, cigar_pool, span records as bytes, round-2
+    tasks as bytes, (prep_bound, max_nl, max_al), record) with the record a dict of ROUND1_REC, (ROUND1_DECLINED, reason) for a round that
+    falls back to mpa_dp_run, or (code, message) of an error (ctx None: the argument error)."""
+    tasks = np.ascontiguousarray(tasks, dtype=DP_TASK)
+    n, n_plan = len(tasks), len(plans)
+    rst = np.zeros(n, dtype=DP_RST)
+    srec, tasks2, n_task = np.zeros(80 * n_plan + 8, np.uint8), np.zeros(80 * n_plan + 8, np.uint8), C.c_int32(0)
+    bounds, rec = np.zeros(3, np.int64), np.zeros(len(ROUND1_REC), dtype=np.int64)
+    pool, n_pool = C.POINTER(C.c_uint32)(), C.c_int64(0)
+    f = dbg_lib().mpa_dbg_round1_chain
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(MapOpt), C.c_void_p, C.POINTER(QBatch), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    keep = [np.ascontiguousarray(x) for x in (plans, segs)]
+    ptr = [x.ctypes.data if len(x) else None for x in keep]
+    rc = f(ctx.h if ctx else None, idx.h, C.byref(mo), C.addressof(dpopt), C.byref(queries.c), n_plan, ptr[0], len(segs), ptr[1], n, tasks.ctypes.data, rst.ctypes.data,
+           srec.ctypes.data, tasks2.ctypes.data, C.byref(n_task), bounds.ctypes.data, C.addressof(pool), C.addressof(n_pool), rec.ctypes.data)
+    if rc != 0:
+        return int(rc), last_error()
+    words = n_pool.value if pool else 0
+    cig = np.ctypeslib.as_array(pool, (max(words, 1),))[:words].copy() if words else np.zeros(0, np.uint32)
+    if pool:
+        lib().mpa_free(pool)
+    return rst, cig, srec[:80 * n_plan].tobytes(), tasks2[:40 * n_task.value].tobytes(), tuple(int(x) for x in bounds), dict(zip(ROUND1_REC, (int(x) for x in rec)))
+
+
+def dbg_spans_guard(ctx, idx, mo, queries, plans, segs, rst1, err, bad):
+    """mpa_dbg_spans_guard(): the step between the rounds on the device under the guard words of a round that failed (err, bad; one of
+    them non-zero).  Returns (n_task, (prep_bound, max_nl, max_al)) -- zeros, whatever rst1 holds -- or (code, message) of an error."""
+    f = dbg_lib().mpa_dbg_spans_guard
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(MapOpt), C.POINTER(QBatch), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64,
+                  C.POINTER(C.c_int32), C.c_void_p]
+    keep = [np.ascontiguousarray(x) for x in (plans, segs, rst1)]
+    ptr = [x.ctypes.data if len(x) else None for x in keep]
+    n_task, bounds = C.c_int32(-1), np.full(3, -1, np.int64)
+    rc = f(ctx.h if ctx else None, idx.h, C.byref(mo), C.byref(queries.c), len(plans), ptr[0], len(segs), ptr[1], len(rst1), ptr[2], int(err), int(bad), C.byref(n_task),
+           bounds.ctypes.data)
+    if rc != 0:
+        return int(rc), last_error()
+    return n_task.value, tuple(int(x) for x in bounds)
+
+
 # mpa_dbg_chain_extract (include/mpamd_dbg.h): modes, the columns of a path record, path classes and the reasons for the full list
 CHAIN_DENSE, CHAIN_SPARSE_SET, CHAIN_SPARSE_CHAINS = 0, 1, 2
 CHAIN_REC = ("m", "n_total", "non_roots", "max_f", "path", "c0", "big_bucket", "why")

@@ -249,6 +249,14 @@ struct Resident {
 	DpResidentRec rec;
 	const int32_t *d_gids = nullptr;            // the sorted traceback calls where the device planner left them
 	const mpa_dp_rst_t *d_rst = nullptr;
+	const int64_t *d_head = nullptr;            // ... and their header
+	// (MPA_GPU_ROUND1, section 4.15) round 1: in.d_tasks is null and the tasks go up with the planner's upload; the step between the rounds
+	// is chained behind the results kernels (chain: what the caller staged for it; cdev: where it wants records and dense pool)
+	const SpansChain *chain = nullptr;
+	mpa_idx_s *chain_mi = nullptr;
+	SpansChainDev cdev;
+	int64_t plan_up = 0;                        // the planner's upload, for the record's parts
+	const char *who() const { return chain ? "round 1 resident" : "round 2 resident"; }
 };
 
 // What the phases of one mpa_dp_run() call share: the plan, the staging blocks, the kernels' argument structs, which side streams
@@ -333,7 +341,8 @@ static int dp_size_pools(DpRun &R)
 		// sums | header | result records in one pool; the download block with room for header and records
 		const ResLayout L = res_layout((size_t)R.plan.cnt.n, R.plan.glob_ids.size());
 		Carve dc(64); dc.take<char>(R.plan.dn.end), R.dn_res = dc.at;        // (behind the plan's own sections, in a 64-byte section of its own)
-		if ((rc = ctx->round.cigd.ensure((size_t)R.plan.cig_total * 4 + 16)) || (rc = ctx->round.cigoff.ensure(L.end)) || (rc = ctx->round.h_down.ensure(R.dn_res + L.down_bytes()))) return rc;
+		// (round 1: the dense pool is the spans step's sp_pool1, sized by dev_spans_chain_prepare -- round 2 overwrites cigd)
+		if ((!R.rz->chain && (rc = ctx->round.cigd.ensure((size_t)R.plan.cig_total * 4 + 16))) || (rc = ctx->round.cigoff.ensure(L.end)) || (rc = ctx->round.h_down.ensure(R.dn_res + L.down_bytes()))) return rc;
 	}
 	return MPA_OK;
 }
@@ -707,11 +716,15 @@ static int dp_results_enqueue(DpRun &R)
 		hipLaunchKernelGGL(k_dpr_offsets, g_glob, wg, 0, s, D);
 	}
 	hipLaunchKernelGGL(k_dpr_records, g_calls, wg, 0, s, D);
+	// (round 1, section 4.15: the words go straight into the spans step's pool, which outlives round 2, and the records into the rst1 section
+	// of its block, where k_spans reads them now and k_assemble behind round 2)
+	uint32_t *dense = R.rz->chain ? R.rz->cdev.d_pool1 : ctx->round.cigd.as<uint32_t>();
 	if (n_glob) hipLaunchKernelGGL(k_cigar_gather, dim3((unsigned)n_glob), dim3(64), 0, s, ctx->round.tasks.as<DTask>(), D.gids, D.off, (int32_t)n_glob,
-	                               ctx->round.ncig.as<int32_t>(), ctx->round.cig.as<uint32_t>(), ctx->round.cigd.as<uint32_t>());
+	                               ctx->round.ncig.as<int32_t>(), ctx->round.cig.as<uint32_t>(), dense);
 	HIP_TRY(hipGetLastError());
+	if (R.rz->chain) HIP_TRY(hipMemcpyAsync(R.rz->cdev.d_rst1, D.rst, sizeof(mpa_dp_rst_t) * n, hipMemcpyDeviceToDevice, s));
 	HIP_TRY(hipMemcpyAsync(R.hdn + R.dn_res, L.head.in(X), L.down_bytes(), hipMemcpyDeviceToHost, s));
-	R.rz->d_rst = D.rst, R.rz->rec.bytes_down += (int64_t)L.down_bytes();
+	R.rz->d_rst = D.rst, R.rz->d_head = D.head, R.rz->rec.bytes_down += (int64_t)L.down_bytes();
 	return MPA_OK;
 }
 
@@ -739,6 +752,13 @@ static int dp_join_and_download(DpRun &R)
 	*(unsigned long long*)(hdn + P.dn.wb) = 0;
 	if (R.rz) R.rz->rec.bytes_down += (P.n_split ? 4 : 0) + (P.n_lite ? 8 : 0);
 	if (P.n_lite) HIP_TRY(hipMemcpyAsync(hdn + P.dn.wb, round_wlist_blocks(ctx, P.n_lite), 8, hipMemcpyDeviceToHost, s));
+	// (MPA_GPU_ROUND1, section 4.15) the step between the rounds, by its own unit's enqueue function: its kernels read the records in place
+	// and are guarded by the words the host checks behind the wait -- a hand-off that timed out, a call outside its slot
+	if (R.rz && R.rz->chain) {
+		int64_t down = 0;
+		if ((rc = dev_spans_chain_enqueue(ctx, R.rz->chain_mi, *R.rz->chain, P.n_split ? R.wa.err : nullptr, R.rz->d_head + DPR_H_BAD, &R.rz->rec.chained_launches, &down))) return rc;
+		R.rz->rec.bytes_down += down;
+	}
 	R.mark("    dp: round enqueued");
 	HIP_TRY(wait_stream(ctx, s));
 	R.mark("    dp: round (wait)");
@@ -858,18 +878,20 @@ static int dev_dp_plan_run(mpa_ctx_t *ctx, hipStream_t s, const int64_t *d_ctg_l
 	if (const char *why = dp_plan_device_declines(opt, kn, n)) { set_error(std::string("device DP plan: ") + why); return MPA_ERR_UNSUPPORTED; }
 	if (q->n_seq < 0 || n_ctg < 0) { set_error("device DP plan: no queries or contigs"); return MPA_ERR_UNSUPPORTED; }
 	const size_t N = (size_t)n, U = (size_t)dp_units_bound(n, kn.split_wide != 0), nb = (size_t)dp_blocks(n, TeamWG::W);
-	// what goes up, in one block (rz: the tasks are read where they are -- no task bytes are staged or uploaded)
+	// what goes up, in one block (rz: the tasks are read where they are -- no task bytes are staged or uploaded; a resident round 1 has
+	// them on the host, and they go up here as with MPA_GPU_DPPLAN=1)
+	const bool tasks_up = !rz || !rz->in.d_tasks;
 	Carve up;
-	const auto u_raw = up.take_if<mpa_dp_task_t>(!rz, N); const auto u_qoff = up.take<int64_t>((size_t)q->n_seq + 1), u_ctg = up.take_if<int64_t>(!d_ctg_len, (size_t)n_ctg);
+	const auto u_raw = up.take_if<mpa_dp_task_t>(tasks_up, N); const auto u_qoff = up.take<int64_t>((size_t)q->n_seq + 1), u_ctg = up.take_if<int64_t>(!d_ctg_len, (size_t)n_ctg);
 	const size_t up_end = up.at;
 	tl_alloc_failed = false;
 	auto declined_alloc = [](int rc) { if (tl_alloc_failed) { tl_alloc_failed = false; return (int)MPA_ERR_UNSUPPORTED; } return rc; };
 	int rc;
 	if ((rc = ctx->planner.h_dpp_up.ensure(up_end + 256))) return MPA_ERR_UNSUPPORTED;
 	char *hup = ctx->planner.h_dpp_up.as<char>();
-	if (!rz) memcpy(u_raw.in(hup), in, u_raw.bytes());
-	int64_t max_nl = rz ? rz->in.max_nl : 0, max_al = rz ? rz->in.max_al : 0;
-	const int64_t prep_bound = rz ? rz->in.prep_bound : dp_plan_prep_bound(u_raw.in((const char*)hup), n, &max_nl, &max_al);
+	if (tasks_up) memcpy(u_raw.in(hup), in, u_raw.bytes());
+	int64_t max_nl = tasks_up ? 0 : rz->in.max_nl, max_al = tasks_up ? 0 : rz->in.max_al;
+	const int64_t prep_bound = tasks_up ? dp_plan_prep_bound(u_raw.in((const char*)hup), n, &max_nl, &max_al) : rz->in.prep_bound;
 	if (prep_bound < 0 || prep_bound > (int64_t)N << 21) { set_error("device DP plan: impossible bounds of the task list"); return MPA_ERR_UNSUPPORTED; }
 	if (!dp_unit_costs_fit(max_nl, max_al)) { set_error("device DP plan: unit costs that do not fit the sort key"); return MPA_ERR_UNSUPPORTED; }
 	memcpy(u_qoff.in(hup), q->q_off, u_qoff.bytes());
@@ -893,7 +915,7 @@ static int dev_dp_plan_run(mpa_ctx_t *ctx, hipStream_t s, const int64_t *d_ctg_l
 	DpDevPlan D;
 	D.n = n, D.n_ubound = (int64_t)U, D.n_ctg = n_ctg, D.n_seq = q->n_seq, D.opt = dp_plan_opt(opt), D.kn = kn;
 	const char *dup = x_up.in(X);
-	D.raw = rz ? rz->in.d_tasks : u_raw.in(dup), D.q_off = u_qoff.in(dup), D.ctg_len = d_ctg_len ? d_ctg_len : u_ctg.in(dup);
+	D.raw = tasks_up ? u_raw.in(dup) : rz->in.d_tasks, D.q_off = u_qoff.in(dup), D.ctg_len = d_ctg_len ? d_ctg_len : u_ctg.in(dup);
 	D.tasks = ctx->round.tasks.as<DTask>(), D.chunks = ctx->round.chunks.as<PrepChunk>(), D.waves = ctx->round.waves.as<ExtWave>(), D.list = ctx->round.list.as<int32_t>();
 	D.gw = round_list_waves(ctx, N);
 	D.units = ctx->round.units.as<DpUnit>(), D.wlist = ctx->round.wlist.as<int32_t>();
@@ -960,9 +982,9 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 	if (rz) {                                                   // (MPA_GPU_ROUND2=1) planned from the tasks in place, or not run here at all
 		size_t b_up = 0, b_down = 0;
 		tl_alloc_failed = false;
-		if ((rc = dev_dp_plan(ctx, mi, opt, q, kn, n, nullptr, plan, &b_up, &b_down, rz)) != MPA_OK) return rc;
+		if ((rc = dev_dp_plan(ctx, mi, opt, q, kn, n, in, plan, &b_up, &b_down, rz)) != MPA_OK) return rc;   // (in: null for round 2, whose tasks are in place)
 		planned = true;
-		rz->rec.plan_waits = ctx->n_waits - waits0, rz->rec.bytes_up = (int64_t)b_up, rz->rec.bytes_down = (int64_t)b_down;
+		rz->rec.plan_waits = ctx->n_waits - waits0, rz->rec.bytes_up = (int64_t)b_up, rz->rec.bytes_down = (int64_t)b_down, rz->plan_up = (int64_t)b_up;
 		timing_note("  dp: plan on device", now_ms() - t_begin);
 		if (timing_on()) fprintf(stderr, "[mpa-timing]   dp: plan on device: %zu bytes up, %zu bytes down\n", b_up, b_down);
 	} else if (dp_plan_on_device()) {                                  // (MPA_GPU_DPPLAN=1) the planner's stages on the device; declined: the host planner, as without the knob
@@ -985,7 +1007,7 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 		tl_alloc_failed = false;
 		if (ctx->round.xg.ensure(plan.sz.xg)) {
 			tl_alloc_failed = false;
-			if (rz) { set_error("round 2 resident: the boundary pool of the 2048/3072-column extension classes cannot grow"); return MPA_ERR_UNSUPPORTED; }
+			if (rz) { set_error(std::string(rz->who()) + ": the boundary pool of the 2048/3072-column extension classes cannot grow"); return MPA_ERR_UNSUPPORTED; }
 			if (timing_on()) fprintf(stderr, "[mpa-timing]   2048/3072-column extension classes declined (%zu bytes of boundary granules): those calls on the one-wave int32 sweep\n", plan.sz.xg);
 			kn.split_wide = 0;
 			if ((rc = dp_plan(in, n, mi->ctg.empty() ? nullptr : &mi->ctg[0].len, sizeof(mi->ctg[0]), (int32_t)mi->ctg.size(), q, opt, kn, sizeof(DpRoundArgs), plan))) { set_error(plan.err); return rc; }
@@ -1004,6 +1026,13 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 	rc = dp_size_pools(R);                                      // 2. pools and staging
 	if (rc && rz) { tl_alloc_failed = false; return MPA_ERR_UNSUPPORTED; }   // (resident: a pool or pinned block that cannot grow declines, before anything of the round is launched)
 	if (rz) rz->rec.bytes_up += plan.q_bytes;                   // (the queries' residues: the round's only upload)
+	// (MPA_GPU_ROUND1, section 4.15) the step between the rounds staged before round 1 is launched: its block up without the record section,
+	// its pools sized -- sp_pool1 at the plan's bound of the dense pool, whose real size is not known before the wait
+	if (!rc && rz && rz->chain) {
+		tl_alloc_failed = false;
+		if ((rc = dev_spans_chain_prepare(ctx, rz->chain_mi, *rz->chain, plan.cig_total, rz->cdev)) != MPA_OK) { tl_alloc_failed = false; return rc; }
+		rz->rec.bytes_up += rz->cdev.bytes_up;
+	}
 	if (rc ||
 	    (rc = dp_upload_and_prep(R, mi, opt, q)) ||            // 3. uploads, memsets, prep
 	    (rc = dp_side_launches(R)) ||                          // 4. next to the round: anti-diagonal, huge, T_LITE_W4 sweep
@@ -1016,19 +1045,19 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 	// has been handed to the caller yet: mpa_dp_run() repeats it with those calls on the one-wave path (k_ext_huge, same bits).
 	static const bool test_fail = [] { const char *e = getenv("MPA_TEST_HANDOFF_FAIL"); return e && atoi(e) != 0; }();
 	if (*(const int32_t*)(R.hdn + plan.dn.err) || (test_fail && plan.n_split && !ctx->no_split)) {
-		if (rz) { set_error("round 2 resident: a column-block hand-off timed out, the round is repeated by mpa_dp_run"); return MPA_ERR_UNSUPPORTED; }
+		if (rz) { set_error(std::string(rz->who()) + ": a column-block hand-off timed out, the round is repeated by mpa_dp_run"); return MPA_ERR_UNSUPPORTED; }
 		set_error("k_ext_wide_split: a column-block hand-off between workgroups timed out"); return MPA_RETRY_NO_SPLIT;
 	}
 	timing_note("  dp: upload+kernels (wall)", now_ms() - t_begin);
 	const double t_res = now_ms();
 	if (rz) {                                                   // 8'. the records are down already; the dense pool stays on the device
 		const int64_t *head = (const int64_t*)(R.hdn + R.dn_res);
-		if (head[DPR_H_BAD] || head[DPR_H_POOL] < 0 || head[DPR_H_POOL] > plan.cig_total) { set_error("round 2 resident: a traceback call's CIGAR length is outside its slot"); return MPA_ERR_HIP; }
+		if (head[DPR_H_BAD] || head[DPR_H_POOL] < 0 || head[DPR_H_POOL] > plan.cig_total) { set_error(std::string(rz->who()) + ": a traceback call's CIGAR length is outside its slot"); return MPA_ERR_HIP; }
 		R.pool_n = head[DPR_H_POOL];
 		memcpy(rst, R.hdn + R.dn_res + 64, sizeof(mpa_dp_rst_t) * (size_t)n);
 		if (n_pool) *n_pool = R.pool_n;
 		rz->rec.round_waits = ctx->n_waits - waits1;
-		if (timing_on()) fprintf(stderr, "[mpa-timing]   dp: round 2 resident: %lld up, %lld down, %lld wait\n", (long long)rz->rec.bytes_up, (long long)rz->rec.bytes_down, (long long)rz->rec.round_waits);
+		if (timing_on()) fprintf(stderr, "[mpa-timing]   dp: %s: %lld up, %lld down, %lld wait\n", rz->who(), (long long)rz->rec.bytes_up, (long long)rz->rec.bytes_down, (long long)rz->rec.round_waits);
 	} else if ((rc = dp_assemble(R, rst, cigar_pool, n_pool))) return rc;   // 8. CIGAR gather, results
 	timing_note("  dp: download+assemble", now_ms() - t_res);
 	dp_statistics(R);                                           // 9.
@@ -1064,23 +1093,43 @@ int dp_run_resident(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *opt,
 	if (rec) *rec = rz.rec;
 	return rc;
 }
-int dp_fetch_pool(mpa_ctx_t *ctx, int64_t n_pool, uint32_t **pool)
+// n_pool words of a dense pool of the context (src: cigd, or the spans step's sp_pool1) into a malloc'ed block, in a wait of its own
+static int dp_fetch_pool_from(mpa_ctx_t *ctx, const CtxPool &src, int64_t n_pool, uint32_t **pool)
 {
 	*pool = nullptr;
-	if (n_pool < 0 || (size_t)n_pool * 4 > ctx->round.cigd.cap) { set_error("dp_fetch_pool: no dense CIGAR pool of that size on this context"); return MPA_ERR_ARG; }
+	if (n_pool < 0 || (size_t)n_pool * 4 > src.cap) { set_error("dp_fetch_pool: no dense CIGAR pool of that size on this context"); return MPA_ERR_ARG; }
 	HIP_TRY(hipSetDevice(ctx->device));
 	uint32_t *p = (uint32_t*)malloc((size_t)(n_pool > 0 ? n_pool : 1) * 4);
 	if (!p) { set_error("out of host memory"); return MPA_ERR_HIP; }
 	if (n_pool > 0) {
 		int rc;
 		if ((rc = ctx->round.h_pool.ensure((size_t)n_pool * 4))) { free(p); return rc; }
-		if (hipMemcpyAsync(ctx->round.h_pool.p, ctx->round.cigd.p, (size_t)n_pool * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || wait_stream(ctx, ctx->stream) != hipSuccess) {
+		if (hipMemcpyAsync(ctx->round.h_pool.p, src.p, (size_t)n_pool * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || wait_stream(ctx, ctx->stream) != hipSuccess) {
 			free(p), set_error("dp_fetch_pool: the download failed"); return MPA_ERR_HIP;
 		}
 		memcpy(p, ctx->round.h_pool.p, (size_t)n_pool * 4);
 	}
 	*pool = p;
 	return MPA_OK;
+}
+int dp_fetch_pool(mpa_ctx_t *ctx, int64_t n_pool, uint32_t **pool) { return dp_fetch_pool_from(ctx, ctx->round.cigd, n_pool, pool); }
+int dp_fetch_pool1(mpa_ctx_t *ctx, int64_t n_pool, uint32_t **pool) { return dp_fetch_pool_from(ctx, ctx->spans.sp_pool1, n_pool, pool); }
+
+// (MPA_GPU_ROUND1=1) round 1 from the caller's table with the step between the rounds chained into its submission
+int dp_run_round1_chained(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *opt, const mpa_qbatch_t *q, int64_t n, const mpa_dp_task_t *tasks, const SpansChain &c,
+                          mpa_dp_rst_t *rst, int64_t *n_pool, SpansIO &io, DpResidentRec *rec, int64_t *parts)
+{
+	if (n_pool) *n_pool = 0;
+	if (!ctx || !tasks || n <= 0 || c.n_rst1 != n) { set_error("round 1 resident: no context, no tasks, or a staged block of another size"); return MPA_ERR_UNSUPPORTED; }
+	Resident rz;
+	rz.chain = &c, rz.chain_mi = const_cast<mpa_idx_s*>(mi);
+	int64_t words = 0;
+	int rc = mpa::guarded<int>(MPA_ERR_HIP, [&] { return mpa_dp_run_impl(ctx, mi, opt, q, n, tasks, rst, nullptr, &words, &rz); });
+	if (rc == MPA_OK) rc = dev_spans_chain_collect(ctx, c, words, io);    // (behind the round's wait and its checks: nothing is enqueued)
+	if (n_pool && rc == MPA_OK) *n_pool = words;
+	if (rec) *rec = rz.rec;
+	if (parts) parts[0] = rz.plan_up, parts[1] = q->q_off[q->n_seq] - q->q_off[0], parts[2] = rz.cdev.bytes_up, parts[3] = rz.cdev.rst1_bytes;
+	return rc;
 }
 } // namespace mpa
 

@@ -717,12 +717,50 @@ static StepMode batch_step_mode(const mpa_batch_s *b, const char *env_name)
 	return m == STEP_DEVICE && !b->dp_ctx ? STEP_HOST : m;
 }
 
+// MPA_GPU_ROUND1=1: round 1 of the batch with the step between the rounds chained into its submission.  The step's
+// block is staged here -- counts, plans, gap segments, text; no result record -- and dp_run_round1_chained sends it up before the round is
+// launched, runs the round from `tasks`, the step's kernels behind its results kernels, and waits once.  MPA_OK: rst[n] and *n_pool as
+// from a resident round, and the step's outputs wait in b->r1_io for spans_take_round1.  MPA_ERR_UNSUPPORTED: declined, *why says what
+// held it back before the device was asked (null: the last error says it) -- the batch is untouched and takes mpa_dp_run
+int spans_round1_resident(mpa_batch_s *b, mpa_ctx_t *ctx, const mpa_dpopt_t *dpopt, int64_t n, const mpa_dp_task_t *tasks, mpa_dp_rst_t *rst, int64_t *n_pool, const char **why)
+{
+	*why = nullptr;
+	b->r1_prefetched = false, b->r1_resident = false, b->r1_io = SpansIO(), b->r1_n_pool = 0;
+	if (!ctx || !b->dp_ctx) { *why = "the batch has no DP context"; return MPA_ERR_UNSUPPORTED; }
+	if (batch_step_mode(b, "MPA_GPU_SPANS") != STEP_DEVICE) { *why = "MPA_GPU_SPANS is not 1"; return MPA_ERR_UNSUPPORTED; }
+	std::vector<int64_t> plan0, seg0;
+	spans_counts(b, plan0, seg0);
+	const int64_t n_plan = plan0.back(), n_seg = seg0.back();
+	if (n_plan <= 0) { *why = "no plan in the batch"; return MPA_ERR_UNSUPPORTED; }
+	const int64_t t0 = b->q.q_off[0], text_bytes = b->q.q_off[b->q.n_seq] - t0;
+	SpansIO io;
+	int rc = dev_spans_stage(ctx, n_plan, n_seg, n, text_bytes, io);
+	if (rc != MPA_OK) return rc;
+	spans_flatten(b, plan0, seg0, io.plan, io.seg);
+	if (text_bytes > 0) memcpy(io.text, b->q.seqs + t0, (size_t)text_bytes);
+	const SpansChain c{ spans_params(b->opt), b->opt.mat, n_plan, n_seg, n, text_bytes, round2_knob() };
+	if ((rc = dp_run_round1_chained(ctx, b->mi, dpopt, &b->q, n, tasks, c, rst, n_pool, io, nullptr)) != MPA_OK) return rc;
+	b->r1_io = io, b->r1_prefetched = true, b->r1_n_pool = *n_pool;
+	return MPA_OK;
+}
+
 // MPA_OK, or the error of a device call that failed (a call that merely declines leaves the batch to the host step)
 int spans_take_round1(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint32_t *pool)
 {
 	const StepMode mode = batch_step_mode(b, "MPA_GPU_SPANS");
 	b->spans_src = 0;
 	b->r2_in = DpResidentIn(), b->r2_resident = false, b->r2_rst_dev = nullptr;
+	const bool prefetched = b->r1_prefetched;
+	b->r1_prefetched = false, b->r1_resident = false;
+	if (prefetched && rst) {                             // (MPA_GPU_ROUND1=1) the step ran inside round 1's wait: its outputs are here already
+		std::vector<int64_t> plan0, seg0;
+		spans_counts(b, plan0, seg0);
+		spans_keep_round1(b, rst, nullptr, false);
+		spans_apply_round1(b, plan0, b->r1_io.rec, b->r1_io.task, b->r1_io.n_task);
+		b->r2_in = b->r1_io.r2, b->r1_io = SpansIO();
+		b->spans_src = 2, b->r1_resident = true;
+		return MPA_OK;
+	}
 	bool any_plan = false;
 	for (const QueryState &qs : b->qs) any_plan = any_plan || !qs.plans.empty();
 	if (mode != STEP_HOST && rst && any_plan) {
@@ -924,6 +962,12 @@ static int take_round3_steps(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint
 		else {
 			if (timing_on()) fprintf(stderr, "[mpa-timing]   device spans declined (%s): region CIGARs on the host\n", mpa_last_error());
 			b->sp_cig_off.clear();
+			if (b->r1_resident && !b->sp_pool1) {                              // (MPA_GPU_ROUND1=1) round 1's words never came down: they are in the spans step's pool, a wait of its own
+				const double t2 = now_ms();
+				const int rc1 = dp_fetch_pool1(b->dp_ctx, b->r1_n_pool, &b->sp_pool1);
+				if (rc1 != MPA_OK) return rc1;
+				if (timing_on()) fprintf(stderr, "[mpa-timing]   dp: round 1 resident: pool fetched late, %lld bytes down, %.3f ms\n", (long long)(4 * b->r1_n_pool), now_ms() - t2);
+			}
 			if (b->r2_resident && !pool) {                                     // the words of round 2 are still on the device: a second wait, their size is known by now
 				const double t2 = now_ms();
 				const int rc2 = dp_fetch_pool(b->dp_ctx, b->dp_n_pool, &fetched.p);

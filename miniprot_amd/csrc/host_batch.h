@@ -82,6 +82,12 @@ struct mpa_batch_s {
 	mpa::DpResidentIn r2_in;
 	bool r2_resident = false;
 	const mpa_dp_rst_t *r2_rst_dev = nullptr;
+	// MPA_GPU_ROUND1: round 1 ran with the step between the rounds chained into its submission -- r1_io is what the
+	// step left (taken by spans_take_round1 in place of a device call, then cleared), and round 1's dense pool (r1_n_pool words) is on dp_ctx
+	// in the spans step's pool and not with the host: sp_pool1 stays null until a fallback fetches the words
+	bool r1_prefetched = false, r1_resident = false;
+	mpa::SpansIO r1_io;
+	int64_t r1_n_pool = 0;
 	// MPA_GPU_FINISH (1 or model): the batch's flat result when the step behind the walks ranked and laid it out
 	// (null: stage_finish ranked the regions and mpa_batch_finish flattens them), and where its cs bodies came from (Region::cs_src)
 	std::unique_ptr<mpa_result_s> flat;
@@ -104,6 +110,8 @@ namespace mpa {
 // host_map.cpp -> host_align.cpp: round 1 in / round 2 out, and the last round in (CIGARs, statistics, cs strings and rows, ranking)
 MPA_HOST_LOCAL int spans_take_round1(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint32_t *pool);
 MPA_HOST_LOCAL int take_round3(mpa_batch_s *b, const mpa_dp_rst_t *rst, const uint32_t *pool);
+// ... and (MPA_GPU_ROUND1=1) round 1 itself with the step behind it in one submission; declined: *why, or the last error
+MPA_HOST_LOCAL int spans_round1_resident(mpa_batch_s *b, mpa_ctx_t *ctx, const mpa_dpopt_t *dpopt, int64_t n, const mpa_dp_task_t *tasks, mpa_dp_rst_t *rst, int64_t *n_pool, const char **why);
 // host_align.cpp -> host_plan.cpp: plan_round1 makes the gap segments with it, take_round1_emit_round2 the accepted spans
 MPA_HOST_LOCAL void make_segment(mpa_batch_s *b, const QueryState &qs, const Region &r, const AlignPlan &pl, int32_t ne0, int32_t ne1, int32_t ae0, int32_t ae1,
                                  int32_t qi, int32_t pi, std::vector<mpa_dp_task_t> &tasks, Segment &s);

@@ -176,6 +176,15 @@ int mpa::run_dp_rounds(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_qbatch_t *
 			else if (rc != MPA_ERR_UNSUPPORTED) return rc;
 			else if (timing_on()) fprintf(stderr, "[mpa-timing]   round 2 resident declined (%s): mpa_dp_run\n", mpa_last_error());
 		}
+		// (MPA_GPU_ROUND1=1) round 1 planned on the device from the batch's tasks, its records and dense pool assembled there and the step
+		// between the rounds chained behind them, inside the round's one wait: no pool comes back, and spans_take_round1 finds the step's
+		// outputs with the batch.  Declined: mpa_dp_run and the step as always
+		if (b->round == 1 && round1_knob()) {
+			const char *why = nullptr;
+			rc = spans_round1_resident(b, ctx, &dpopt, n, tasks, rst.data(), &n_pool, &why);
+			if (rc != MPA_OK && rc != MPA_ERR_UNSUPPORTED) return rc;
+			if (rc != MPA_OK && timing_on()) fprintf(stderr, "[mpa-timing]   round 1 resident declined (%s): mpa_dp_run\n", why ? why : mpa_last_error());
+		}
 		if (rc == MPA_ERR_UNSUPPORTED) rc = mpa_dp_run(ctx, mi, &dpopt, q, n, tasks, rst.data(), &pool, &n_pool);
 		timing_note("mpa_dp_run (total)", now_ms() - t0);
 		if (rc != MPA_OK) { free(pool); return rc; }

@@ -408,7 +408,8 @@ int64_t format_take_text(mpa_result_s *r, int32_t n_query, int64_t *id_io, char 
 // device planner sizes by (dp_results_core.h), reduced on the device and downloaded next to the task count (DpResidentIn, above).
 // ... and what a resident round says about itself: host waits of the planner and of the round behind it, bytes up and down (task records
 // among the bytes up, words of the dense CIGAR pool among the bytes down)
-struct DpResidentRec { int64_t plan_waits = 0, round_waits = 0, bytes_up = 0, task_bytes_up = 0, bytes_down = 0, pool_bytes_down = 0; };
+// (chained_launches: kernels of the step between the rounds launched inside the round's wait -- MPA_GPU_ROUND1, below; 0 for round 2)
+struct DpResidentRec { int64_t plan_waits = 0, round_waits = 0, bytes_up = 0, task_bytes_up = 0, bytes_down = 0, pool_bytes_down = 0, chained_launches = 0; };
 // The round of n calls planned from in.d_tasks in place, its result records written on the device and downloaded with the round's one
 // wait into rst[n]; *n_pool: words of the dense CIGAR pool, which stays in the context (dp_fetch_pool); *d_rst: the records on the
 // device, valid until the context's next round.  MPA_ERR_UNSUPPORTED: declined (the last error says why) -- the caller runs mpa_dp_run.
@@ -420,5 +421,33 @@ int dp_fetch_pool(mpa_ctx_t *ctx, int64_t n_pool, uint32_t **pool);
 static inline bool round2_knob() { const char *e = getenv("MPA_GPU_ROUND2"); return e && atoi(e) != 0; }
 // the bounds of the n tasks at d_tasks, reduced on the device (k_task_bounds, span_kernels.hip): for the hook mpa_dbg_dp_run_resident
 int dev_task_bounds(mpa_ctx_t *ctx, const mpa_dp_task_t *d_tasks, int64_t n, DpResidentIn &out);
+
+// ---- DP round 1 and the step behind it in one submission (MPA_GPU_ROUND1=1; dp_exec.hip, stats_run.hip) ----
+// The step between the rounds as the round sees it: c says what the caller staged through dev_spans_stage (plans, gap segments, text;
+// the record section of the block is left alone -- the round's own kernels write it on the device).
+// dev_spans_chain_prepare (before the round is launched; whatever can decline does so here): the block up without its record section,
+// sp_pool1 sized at pool_words; dev: where records and dense pool go, and what went up (block_bytes / rst1_bytes: the whole block and its
+// record section, for the record).  dev_spans_chain_enqueue (behind the round's results kernels, in front of its one wait): k_spans,
+// k_spans_emit and, with MPA_GPU_ROUND2=1, k_task_bounds under the guard of g_err / g_bad (the round's hand-off error word and the bad-call
+// word of its results header: either non-zero and the kernels read no record and write a task count of 0), then the step's download; no
+// wait.  dev_spans_chain_collect (behind the wait, for a round that passed its checks): what dev_spans_round1 leaves in io.
+struct SpansChain { SpansParams p; const int8_t *mat; int64_t n_plan, n_seg, n_rst1, text_bytes; bool want_r2; };   // want_r2: k_task_bounds too (MPA_GPU_ROUND2=1; the hook: always)
+struct SpansChainDev { mpa_dp_rst_t *d_rst1 = nullptr; uint32_t *d_pool1 = nullptr; int64_t bytes_up = 0, block_bytes = 0, rst1_bytes = 0; };
+int dev_spans_chain_prepare(mpa_ctx_t *ctx, mpa_idx_s *mi, const SpansChain &c, int64_t pool_words, SpansChainDev &dev);
+int dev_spans_chain_enqueue(mpa_ctx_t *ctx, mpa_idx_s *mi, const SpansChain &c, const int32_t *g_err, const int64_t *g_bad, int64_t *launches, int64_t *bytes_down);
+int dev_spans_chain_collect(mpa_ctx_t *ctx, const SpansChain &c, int64_t n_pool1, SpansIO &io);
+// (the hook mpa_dbg_spans_guard) the step alone on a staged block that holds its records, with guard words of the caller's on the device
+int dev_spans_round1_guarded(mpa_ctx_t *ctx, mpa_idx_s *mi, const SpansChain &c, int32_t err, int64_t bad, SpansIO &io);
+// The round of n calls from the caller's task table, planned on the device (or declined), with the chained step: rst[n] and *n_pool as
+// for dp_run_resident, io what dev_spans_round1 would have left (rec, task, n_task, r2), the dense pool in the context's sp_pool1
+// (dp_fetch_pool1).  rec->bytes_up holds planner upload + query residues + the staged block without its record section; parts[4]
+// (nullable): those three and the bytes of the record section that stayed down.  MPA_ERR_UNSUPPORTED: declined (the last error says why),
+// io untouched -- the caller runs mpa_dp_run and the step as always.
+int dp_run_round1_chained(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_t *opt, const mpa_qbatch_t *q, int64_t n, const mpa_dp_task_t *tasks, const SpansChain &c,
+                          mpa_dp_rst_t *rst, int64_t *n_pool, SpansIO &io, DpResidentRec *rec, int64_t *parts = nullptr);
+// the round-1 words a chained round left in the context's sp_pool1 (n_pool words) into a malloc'ed block: a wait of its own
+int dp_fetch_pool1(mpa_ctx_t *ctx, int64_t n_pool, uint32_t **pool);
+// MPA_GPU_ROUND1, read per batch
+static inline bool round1_knob() { const char *e = getenv("MPA_GPU_ROUND1"); return e && atoi(e) != 0; }
 
 } // namespace mpa

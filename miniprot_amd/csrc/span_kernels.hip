@@ -9,6 +9,8 @@
 //   k_assemble     one wavefront per plan, four plans per workgroup: spans_assemble into the plan's slot of the CIGAR pool
 //   k_task_bounds  (MPA_GPU_ROUND2=1) one lane per round-2 task: the three bounds the device planner sizes by (dp_results_core.h), a
 //                  wave reduction and one vector atomic per wave and bound
+// (MPA_GPU_ROUND1=1) the three kernels chained behind a DP round inside its one wait take a guard: the round's
+// hand-off error word and its results header.  Either one non-zero: no result record and no genome byte is read, and the task count is 0.
 // The tables (804 bytes) and the workgroup scan's four wave totals are k_spans' only LDS.  No capacity.  Plain vector stores only.
 
 namespace mpa {
@@ -28,7 +30,15 @@ struct SpansArgs {
 	mpa_dp_task_t *tmp;                  // [2 n_plan] plan i's tasks at 2 i
 	int32_t *excl;                       // [n_plan] tasks of the plans before it in its workgroup
 	int32_t *bsum;                       // [workgroups] tasks of the workgroup
+	const int32_t *g_err = nullptr;      // (nullable) the round's hand-off error word and the bad-call word of its results header: when
+	const int64_t *g_bad = nullptr;      // either is non-zero nobody wrote the records at rst1
 };
+
+// the guard of a chained step: plain loads, stream-ordered behind the round that wrote the words
+__device__ __forceinline__ bool spans_guarded(const int32_t *g_err, const int64_t *g_bad)
+{
+	return (g_err && *g_err != 0) || (g_bad && *g_bad != 0);
+}
 
 __global__ __launch_bounds__(SPANS_BLOCK) void k_spans(SpansArgs x)
 {
@@ -39,7 +49,7 @@ __global__ __launch_bounds__(SPANS_BLOCK) void k_spans(SpansArgs x)
 	__syncthreads();
 	const int32_t i = (int32_t)(blockIdx.x * SPANS_BLOCK + threadIdx.x);
 	int32_t n = 0;
-	if (i < x.n_plan) {
+	if (i < x.n_plan && !spans_guarded(x.g_err, x.g_bad)) {
 		const SpansPlan P = x.plan[i];
 		const StatsGenome g{ x.seq, x.ctg_off[P.vid >> 1], x.ctg_len[P.vid >> 1], (int)(P.vid & 1) };
 		n = spans_accept(x.p, P, x.rst1, g, tab, x.text, x.rec[i], x.tmp + 2 * (int64_t)i);   // (straight into global memory: no private copy)
@@ -67,6 +77,10 @@ __global__ __launch_bounds__(SPANS_BLOCK) void k_spans_emit(SpansArgs x, int32_t
 	int32_t base = 0;
 	for (int w = 0; w < SPANS_BLOCK / 64; ++w) base += wsum[w];
 	const int32_t i = (int32_t)(blockIdx.x * SPANS_BLOCK + threadIdx.x);
+	if (spans_guarded(x.g_err, x.g_bad)) {                                 // (uniform: k_spans wrote no record and counted no task)
+		if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) head[0] = 0;
+		return;
+	}
 	if (i < x.n_plan) {
 		// (the record as ten 8-byte words, then the two task numbers over it: no private copy of the record)
 		const int32_t t0 = base + x.excl[i], lt = x.rec[i].left.task, rt = x.rec[i].right.task;
@@ -83,9 +97,10 @@ __global__ __launch_bounds__(SPANS_BLOCK) void k_spans_emit(SpansArgs x, int32_t
 }
 
 // out[3], zero before the launch: prep chunks, largest nl, largest al of task[0, *n_task); the grid covers the list's capacity
-__global__ __launch_bounds__(SPANS_BLOCK) void k_task_bounds(const mpa_dp_task_t *task, const int32_t *n_task, int64_t *out)
+__global__ __launch_bounds__(SPANS_BLOCK) void k_task_bounds(const mpa_dp_task_t *task, const int32_t *n_task, int64_t *out, const int32_t *g_err, const int64_t *g_bad)
 {
 	MPA_SHORT_KERNEL();
+	if (spans_guarded(g_err, g_bad)) return;                               // (a chained step behind a round that failed: out stays zero)
 	const int64_t i = (int64_t)blockIdx.x * SPANS_BLOCK + threadIdx.x;
 	DpTaskBounds b{ 0, 0, 0 };
 	if (i < (int64_t)*n_task) b = dp_task_bounds_of(task[i].nl, task[i].al);

@@ -8,7 +8,8 @@
 // features; cs: lengths | slots; rows: records | slots) and waits once.  The pools (st_in, st_out, cs_out, rows_out and their staging)
 // are grow-only and allocated by the first call that asks for them: a run that never sets a knob holds none of them.
 // MPA_GPU_SPANS=1 (kernels k_spans, k_spans_emit, k_assemble: span_kernels.hip; code: spans_core.h) puts the
-// host step between the DP rounds and the one behind them here: dev_spans_stage() / dev_spans_round1() and dev_spans_asm_stage() /
+// host step between the DP rounds and the one behind them here: dev_spans_stage() / dev_spans_round1() (MPA_GPU_ROUND1=1, section 4.15: the
+// dev_spans_chain_*() parts of it, behind a resident round 1 inside that round's wait) and dev_spans_asm_stage() /
 // dev_spans_assemble().  The CIGAR pool k_assemble writes (sp_cig) stays on the device until the context's next call, and
 // dev_aln_walks() reads it in place of an uploaded one when the caller says so (dev_cig).
 // MPA_GPU_FINISH=1 (kernels k_finish_rank, k_finish_scan, k_finish_gather: finish_kernels.hip; code: finish_core.h; DESIGN.md section
@@ -158,54 +159,141 @@ int dev_spans_stage(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_seg, int64_t n_rst
 	return MPA_OK;
 }
 
-int dev_spans_round1(mpa_ctx_t *ctx, mpa_idx_s *mi, const SpansParams &p, const int8_t *mat, int64_t n_plan, int64_t n_seg, int64_t n_rst1, int64_t text_bytes,
-                     const uint32_t *pool1, int64_t n_pool1, SpansIO &io)
+// The three parts of the step between the rounds, as for the finish step.  spans_prepare: the pools sized, the tables filled and the staged
+// block sent up -- everything that can decline, before anything is launched (with_rst1 false: the round-1 records are written on the
+// device behind it, so their section of the block stays out of the upload, which is then the two pieces around it).  spans_launch: k_spans,
+// k_spans_emit and, with MPA_GPU_ROUND2=1, k_task_bounds on the context's stream, then the step's download; it does not wait.
+// spans_collect, behind the caller's wait: the task count checked, io filled, what dev_spans_assemble reads kept.
+static SpansLayout spans_layout(const SpansChain &c) { return SpansLayout(c.n_plan, c.n_seg, c.n_rst1, c.text_bytes, spans_blocks(c.n_plan)); }
+
+static int spans_prepare(mpa_ctx_t *ctx, mpa_idx_s *mi, const SpansChain &c, int64_t pool_words, bool with_rst1, int64_t *bytes_up)
 {
 	ctx->spans.sp_keep.n_plan = -1;
-	if (p.asize < 1 || p.asize * p.asize > 484) { set_error("GPU spans: a substitution matrix of more than 22 x 22"); return MPA_ERR_UNSUPPORTED; }
+	if (c.p.asize < 1 || c.p.asize * c.p.asize > 484) { set_error("GPU spans: a substitution matrix of more than 22 x 22"); return MPA_ERR_UNSUPPORTED; }
 	HIP_TRY(hipSetDevice(ctx->device));
 	if (dev_upload_index(ctx, mi) != MPA_OK) return MPA_ERR_HIP;
-	const DeviceIndex *d = mi->dev[ctx->device];
-	const SpansLayout L(n_plan, n_seg, n_rst1, text_bytes, spans_blocks(n_plan));
+	const SpansLayout L = spans_layout(c);
 	if (L.up_bytes > ctx->spans.h_sp_up.cap || L.down_bytes > ctx->spans.h_sp_down.cap) { set_error("dev_spans_round1: the staging block was not sized for this call"); return MPA_ERR_ARG; }
-	if (n_pool1 < 0 || (!pool1 && n_pool1 > 0 && (size_t)n_pool1 * 4 > ctx->round.cigd.cap)) { set_error("dev_spans_round1: no round-1 CIGAR pool of that size on this context"); return MPA_ERR_ARG; }
 	tl_alloc_failed = false;
 	if (ctx->spans.sp_in.ensure(L.up_bytes) != MPA_OK || ctx->spans.sp_mid.ensure(L.mid_bytes) != MPA_OK || ctx->spans.sp_out.ensure(L.down_bytes) != MPA_OK ||
-	    ctx->spans.sp_pool1.ensure((size_t)n_pool1 * 4 + 16) != MPA_OK)
+	    ctx->spans.sp_pool1.ensure((size_t)pool_words * 4 + 16) != MPA_OK)
 		return tl_alloc_failed ? MPA_ERR_UNSUPPORTED : MPA_ERR_HIP;
 	hipStream_t s = ctx->stream;
-	char *hu = ctx->spans.h_sp_up.as<char>();
-	aln_tables_fill(L.tabs.in(hu), mat, (size_t)(p.asize * p.asize));
-	HIP_TRY(hipMemcpyAsync(ctx->spans.sp_in.p, hu, L.up_bytes - 16, hipMemcpyHostToDevice, s));
-	// the round-1 pool stays: round 2 overwrites cigd
-	if (n_pool1 > 0) HIP_TRY(hipMemcpyAsync(ctx->spans.sp_pool1.p, pool1 ? (const void*)pool1 : ctx->round.cigd.p, (size_t)n_pool1 * 4, pool1 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+	char *hu = ctx->spans.h_sp_up.as<char>(), *din = ctx->spans.sp_in.as<char>();
+	aln_tables_fill(L.tabs.in(hu), c.mat, (size_t)(c.p.asize * c.p.asize));
+	if (with_rst1) {
+		HIP_TRY(hipMemcpyAsync(din, hu, L.up_bytes - 16, hipMemcpyHostToDevice, s));
+		if (bytes_up) *bytes_up = (int64_t)(L.up_bytes - 16);
+	} else {                                             // tables | plans | gap segments, then the text: the records' section is the device's
+		const size_t head = L.seg.end(), tail = L.text.bytes();
+		HIP_TRY(hipMemcpyAsync(din, hu, head, hipMemcpyHostToDevice, s));
+		if (tail) HIP_TRY(hipMemcpyAsync(din + L.text.off, hu + L.text.off, tail, hipMemcpyHostToDevice, s));
+		if (bytes_up) *bytes_up = (int64_t)(head + tail);
+	}
+	return MPA_OK;
+}
+
+static int spans_launch(mpa_ctx_t *ctx, mpa_idx_s *mi, const SpansChain &c, const int32_t *g_err, const int64_t *g_bad, int64_t *launches, int64_t *bytes_down)
+{
+	const DeviceIndex *d = mi->dev[ctx->device];
+	const SpansLayout L = spans_layout(c);
+	hipStream_t s = ctx->stream;
 	const char *din = ctx->spans.sp_in.as<char>();
 	char *mid = ctx->spans.sp_mid.as<char>(), *dout = ctx->spans.sp_out.as<char>();
 	SpansArgs a;
-	a.plan = L.plan.in(din), a.n_plan = (int32_t)n_plan, a.rst1 = L.rst1.in(din);
+	a.plan = L.plan.in(din), a.n_plan = (int32_t)c.n_plan, a.rst1 = L.rst1.in(din);
 	a.text = (const uint8_t*)L.text.in(din), a.tabs = L.tabs.in(din), a.seq = (const uint8_t*)d->seq, a.ctg_off = d->ctg_off, a.ctg_len = d->ctg_len;
-	a.p = p, a.rec = L.mid_rec.in(mid), a.tmp = L.tmp.in(mid), a.excl = L.excl.in(mid), a.bsum = L.bsum.in(mid);
+	a.p = c.p, a.rec = L.mid_rec.in(mid), a.tmp = L.tmp.in(mid), a.excl = L.excl.in(mid), a.bsum = L.bsum.in(mid);
+	a.g_err = g_err, a.g_bad = g_bad;
 	const dim3 grid((unsigned)L.bsum.n);
 	hipLaunchKernelGGL(k_spans, grid, dim3(SPANS_BLOCK), 0, s, a);
 	HIP_TRY(hipGetLastError());
 	hipLaunchKernelGGL(k_spans_emit, grid, dim3(SPANS_BLOCK), 0, s, a, L.n_task.in(dout), L.rec.in(dout), L.task.in(dout));
 	HIP_TRY(hipGetLastError());
-	const bool want_r2 = round2_knob();                  // (MPA_GPU_ROUND2=1) the bounds of the tasks just written, for the planner of round 2
-	if (want_r2) {
+	int64_t n_launch = 2;
+	if (c.want_r2) {                                     // (MPA_GPU_ROUND2=1) the bounds of the tasks just written, for the planner of round 2
 		HIP_TRY(hipMemsetAsync(L.bounds.in(dout), 0, L.bounds.bytes(), s));
-		hipLaunchKernelGGL(k_task_bounds, dim3((unsigned)((2 * n_plan + SPANS_BLOCK - 1) / SPANS_BLOCK)), dim3(SPANS_BLOCK), 0, s, (const mpa_dp_task_t*)L.task.in(dout), (const int32_t*)L.n_task.in(dout),
-		                   L.bounds.in(dout));
+		hipLaunchKernelGGL(k_task_bounds, dim3((unsigned)((2 * c.n_plan + SPANS_BLOCK - 1) / SPANS_BLOCK)), dim3(SPANS_BLOCK), 0, s, (const mpa_dp_task_t*)L.task.in(dout), (const int32_t*)L.n_task.in(dout),
+		                   L.bounds.in(dout), g_err, g_bad);
 		HIP_TRY(hipGetLastError());
+		++n_launch;
 	}
-	const char *hd = ctx->spans.h_sp_down.as<char>();
 	HIP_TRY(hipMemcpyAsync(ctx->spans.h_sp_down.p, dout, L.down_bytes - 16, hipMemcpyDeviceToHost, s));
-	HIP_TRY(wait_stream(ctx, s));
+	if (launches) *launches = n_launch;
+	if (bytes_down) *bytes_down = (int64_t)(L.down_bytes - 16);
+	return MPA_OK;
+}
+
+static int spans_collect(mpa_ctx_t *ctx, const SpansChain &c, int64_t n_pool1, SpansIO &io)
+{
+	const SpansLayout L = spans_layout(c);
+	const char *hd = ctx->spans.h_sp_down.as<char>();
+	char *dout = ctx->spans.sp_out.as<char>();
 	io.n_task = *L.n_task.in(hd), io.rec = L.rec.in(hd), io.task = L.task.in(hd);
 	io.r2 = DpResidentIn();
-	if (want_r2) { const int64_t *bd = L.bounds.in(hd); io.r2.d_tasks = L.task.in(dout), io.r2.prep_bound = bd[0], io.r2.max_nl = bd[1], io.r2.max_al = bd[2]; }
-	if (io.n_task < 0 || io.n_task > 2 * n_plan) { set_error("dev_spans_round1: an impossible task count"); return MPA_ERR_HIP; }
-	ctx->spans.sp_keep = SpanBufs::SpansKeep{ L.plan, L.seg, L.rst1, L.rec, n_plan, n_pool1 };
+	if (c.want_r2) { const int64_t *bd = L.bounds.in(hd); io.r2.d_tasks = L.task.in(dout), io.r2.prep_bound = bd[0], io.r2.max_nl = bd[1], io.r2.max_al = bd[2]; }
+	if (io.n_task < 0 || io.n_task > 2 * c.n_plan) { set_error("dev_spans_round1: an impossible task count"); return MPA_ERR_HIP; }
+	ctx->spans.sp_keep = SpanBufs::SpansKeep{ L.plan, L.seg, L.rst1, L.rec, c.n_plan, n_pool1 };
 	return MPA_OK;
+}
+
+int dev_spans_round1(mpa_ctx_t *ctx, mpa_idx_s *mi, const SpansParams &p, const int8_t *mat, int64_t n_plan, int64_t n_seg, int64_t n_rst1, int64_t text_bytes,
+                     const uint32_t *pool1, int64_t n_pool1, SpansIO &io)
+{
+	const SpansChain c{ p, mat, n_plan, n_seg, n_rst1, text_bytes, round2_knob() };
+	ctx->spans.sp_keep.n_plan = -1;
+	if (n_pool1 < 0 || (!pool1 && n_pool1 > 0 && (size_t)n_pool1 * 4 > ctx->round.cigd.cap)) { set_error("dev_spans_round1: no round-1 CIGAR pool of that size on this context"); return MPA_ERR_ARG; }
+	int rc = spans_prepare(ctx, mi, c, n_pool1, true, nullptr);
+	if (rc != MPA_OK) return rc;
+	hipStream_t s = ctx->stream;
+	// the round-1 pool stays: round 2 overwrites cigd
+	if (n_pool1 > 0) HIP_TRY(hipMemcpyAsync(ctx->spans.sp_pool1.p, pool1 ? (const void*)pool1 : ctx->round.cigd.p, (size_t)n_pool1 * 4, pool1 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+	if ((rc = spans_launch(ctx, mi, c, nullptr, nullptr, nullptr, nullptr)) != MPA_OK) return rc;
+	HIP_TRY(wait_stream(ctx, s));
+	return spans_collect(ctx, c, n_pool1, io);
+}
+
+// ---- MPA_GPU_ROUND1=1: the same step chained behind a resident round 1 (dp_exec.hip), inside the round's one wait.
+// dev_spans_chain_prepare, before the round is launched: the block staged through dev_spans_stage goes up without its record section and
+// sp_pool1 is sized at pool_words, the plan's bound of the dense pool; dev says where the round's kernels put records and words.
+// dev_spans_chain_enqueue, behind the round's results kernels: the step's kernels under the guard (g_err, g_bad: the round's hand-off
+// error word and the bad-call word of its results header) and its download.  dev_spans_chain_collect, behind the wait.
+int dev_spans_chain_prepare(mpa_ctx_t *ctx, mpa_idx_s *mi, const SpansChain &c, int64_t pool_words, SpansChainDev &dev)
+{
+	dev = SpansChainDev();
+	if (c.n_plan <= 0 || c.n_rst1 <= 0 || pool_words < 0) { set_error("dev_spans_chain_prepare: no plans, no calls or a negative pool"); return MPA_ERR_ARG; }
+	const int rc = spans_prepare(ctx, mi, c, pool_words, false, &dev.bytes_up);
+	if (rc != MPA_OK) return rc;
+	const SpansLayout L = spans_layout(c);
+	dev.d_rst1 = L.rst1.in(ctx->spans.sp_in.as<char>()), dev.d_pool1 = ctx->spans.sp_pool1.as<uint32_t>();
+	dev.block_bytes = (int64_t)(L.up_bytes - 16), dev.rst1_bytes = (int64_t)(L.text.off - L.seg.end());
+	return MPA_OK;
+}
+int dev_spans_chain_enqueue(mpa_ctx_t *ctx, mpa_idx_s *mi, const SpansChain &c, const int32_t *g_err, const int64_t *g_bad, int64_t *launches, int64_t *bytes_down)
+{
+	return spans_launch(ctx, mi, c, g_err, g_bad, launches, bytes_down);
+}
+int dev_spans_chain_collect(mpa_ctx_t *ctx, const SpansChain &c, int64_t n_pool1, SpansIO &io)
+{
+	if (n_pool1 < 0 || (size_t)n_pool1 * 4 > ctx->spans.sp_pool1.cap) { set_error("dev_spans_chain_collect: no round-1 CIGAR pool of that size on this context"); return MPA_ERR_ARG; }
+	return spans_collect(ctx, c, n_pool1, io);
+}
+// (the hook mpa_dbg_spans_guard) the step on a staged block that holds its records, under guard words the caller chooses: err and bad go
+// into a pool of the context and the kernels get pointers to them, as a chained step gets the round's.  No CIGAR pool is kept
+int dev_spans_round1_guarded(mpa_ctx_t *ctx, mpa_idx_s *mi, const SpansChain &c, int32_t err, int64_t bad, SpansIO &io)
+{
+	int rc = spans_prepare(ctx, mi, c, 0, true, nullptr);
+	if (rc != MPA_OK) return rc;
+	if (ctx->spans.sp_in2.ensure(64) != MPA_OK) return MPA_ERR_HIP;
+	hipStream_t s = ctx->stream;
+	Carve gc(8);                                         // the error word | the bad-call word
+	const auto p_err = gc.take<int32_t>(1); const auto p_bad = gc.take<int64_t>(1);
+	int64_t h[2] = { 0, 0 };
+	*p_err.in(h) = err, *p_bad.in(h) = bad;
+	HIP_TRY(hipMemcpyAsync(ctx->spans.sp_in2.p, h, sizeof h, hipMemcpyHostToDevice, s));
+	if ((rc = spans_launch(ctx, mi, c, p_err.in((const void*)ctx->spans.sp_in2.p), p_bad.in((const void*)ctx->spans.sp_in2.p), nullptr, nullptr)) != MPA_OK) return rc;
+	HIP_TRY(wait_stream(ctx, s));
+	return spans_collect(ctx, c, 0, io);
 }
 
 int dev_spans_asm_stage(mpa_ctx_t *ctx, int64_t n_plan, int64_t n_rst2, SpansAsmIO &io)
@@ -479,7 +567,7 @@ int dev_task_bounds(mpa_ctx_t *ctx, const mpa_dp_task_t *d_tasks, int64_t n, DpR
 	int64_t h[4] = { 0, 0, 0, 0 };
 	*p_n.in(h) = (int32_t)n;
 	HIP_TRY(hipMemcpyAsync(ctx->spans.sp_mid.p, h, sizeof h, hipMemcpyHostToDevice, s));
-	hipLaunchKernelGGL(k_task_bounds, dim3((unsigned)((n + SPANS_BLOCK - 1) / SPANS_BLOCK)), dim3(SPANS_BLOCK), 0, s, d_tasks, (const int32_t*)p_n.in(ctx->spans.sp_mid.p), p_bounds.in(ctx->spans.sp_mid.p));
+	hipLaunchKernelGGL(k_task_bounds, dim3((unsigned)((n + SPANS_BLOCK - 1) / SPANS_BLOCK)), dim3(SPANS_BLOCK), 0, s, d_tasks, (const int32_t*)p_n.in(ctx->spans.sp_mid.p), p_bounds.in(ctx->spans.sp_mid.p), (const int32_t*)nullptr, (const int64_t*)nullptr);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(h, ctx->spans.sp_mid.p, p_bounds.bytes(), hipMemcpyDeviceToHost, s));
 	HIP_TRY(wait_stream(ctx, s));
