@@ -204,7 +204,8 @@ typedef struct {
 	/* checkpointed traceback (traceback calls of <= 128 columns and >= MPA_DP_LITE_MIN rows): calls and padded cells swept by the
 	 * packed sweep, and the blocks of 96 rows whose traceback words the walk recomputed (walk_blocks: of every checkpointed class) */
 	int64_t n_ckpt, cells_ckpt, walk_blocks;
-	/* ... the same for calls of 129..256 columns (MPA_DP_LITE_WIDE=1, four waves per pair of calls); not part of n_ckpt / cells_ckpt */
+	/* ... the same for the classes swept by a group of waves per pair of calls: 129..256 columns (MPA_DP_LITE_WIDE=1, four waves) and
+	 * 257..512 columns (MPA_DP_LITE_W8=1, eight waves; counted alone by mpa_dbg_dp_last_w8, mpamd_dbg.h); not part of n_ckpt / cells_ckpt */
 	int64_t n_ckpt_wide, cells_ckpt_wide;
 } mpa_dp_stats_t;
 void mpa_dp_last_stats(const mpa_ctx_t *ctx, mpa_dp_stats_t *st);

@@ -67,6 +67,17 @@ void mpa_dbg_dp_huge_wg_info(int32_t out[3]);
  * blocks and out[3] the passes of the latter. */
 int mpa_dbg_dp_last_mb(const mpa_ctx_t *ctx, int64_t out[4]);
 
+/* MPA_DP_LITE_W8 (traceback calls of 257..512 columns on the checkpointed class T_LITE_W8, DTask::cls 13 -- an
+ * eight-wave group per pair of calls swept by k_lite_w8, walked by k_walk_w8).  mpa_dbg_dp_last_w8: of the context's last mpa_dp_run
+ * out[0] the calls of the class, out[1] their padded cells ((nl - 2) * 8 * ceil(al / 8) each), out[2] the groups k_lite_w8 was launched
+ * over, out[3] the blocks of MPA_TB_BLOCK rows k_walk_w8 recomputed.  mpa_dbg_dp_plan_w8 is mpa_dbg_dp_plan_wide with knobs[10]: knobs[9]
+ * is lite_w8, which the hook -- like the executor -- drops with the worker pool (knobs[4]).  Its serialisation is mpa_dbg_dp_plan_wide's,
+ * byte for byte, followed by three int64: first descriptor and number of descriptors of T_LITE_W8 in ExtWave[] (behind T_LITE_W4's) and
+ * the calls of its walk list, the sixth (behind T_LITE_W4's in the section of walk calls). */
+int mpa_dbg_dp_last_w8(const mpa_ctx_t *ctx, int64_t out[4]);
+int64_t mpa_dbg_dp_plan_w8(const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, int32_t n_seq, const int64_t *q_off, int64_t n, const mpa_dp_task_t *tasks,
+                           const int64_t *knobs, void *buf, int64_t cap);
+
 /* A DP round from device-resident tasks (MPA_GPU_ROUND2): the arguments of mpa_dp_run.  On a context the hook
  * puts the tasks into a device pool, has their bounds reduced there (k_task_bounds), plans the round from the tasks in place, runs it
  * with the result records and the dense CIGAR pool assembled on the device in front of the round's one wait, and only then fetches the

@@ -740,6 +740,45 @@ def dbg_dp_last_mb(ctx):
     return tuple(int(x) for x in out)
 
 
+DP_PLAN_KNOBS_W8 = DP_PLAN_KNOBS_WIDE + ("lite_w8",)
+DP_PLAN_W8_TAIL = 24   # bytes dbg_dp_plan_w8() adds behind the *_wide tail: int64 first, count of T_LITE_W8's descriptors; calls of its walk list
+T_LITE_W8 = 13         # DpClass number (dp_device.h) of the 257..512-column checkpointed traceback class
+
+
+def dbg_dp_plan_w8(dpopt, ctg_len, q_off, tasks, knobs):
+    """mpa_dbg_dp_plan_w8(): dbg_dp_plan_wide() with a tenth knob, lite_w8 (MPA_DP_LITE_W8; missing: 0).  The bytes are dbg_dp_plan_wide()'s
+    followed by DP_PLAN_W8_TAIL more (include/mpamd_dbg.h); (code, message) when the planner refuses the table."""
+    import numpy as np
+    tasks = np.ascontiguousarray(tasks, dtype=DP_TASK)
+    ctg_len = np.ascontiguousarray(ctg_len, dtype=np.int64)
+    q_off = np.ascontiguousarray(q_off, dtype=np.int64)
+    kn = np.array([knobs.get(k, 0) for k in DP_PLAN_KNOBS_W8], dtype=np.int64)
+    f = dbg_lib().mpa_dbg_dp_plan_w8
+    f.restype = C.c_int64
+    f.argtypes = [C.POINTER(DpOpt), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    args = (C.byref(dpopt), len(ctg_len), ctg_len.ctypes.data, len(q_off) - 1, q_off.ctypes.data, len(tasks), tasks.ctypes.data, kn.ctypes.data)
+    need = f(*args, None, 0)
+    if need < 0:
+        return int(need), last_error()
+    buf = np.zeros(need, dtype=np.uint8)
+    got = f(*args, buf.ctypes.data, need)
+    if got != need:
+        return int(got), last_error()
+    return buf.tobytes()
+
+
+def dbg_dp_last_w8(ctx):
+    """mpa_dbg_dp_last_w8(): of the context's last dp_run(), (traceback calls of the class T_LITE_W8 -- 257..512 columns, MPA_DP_LITE_W8 --,
+    their padded cells, the eight-wave groups k_lite_w8 swept, the blocks of 96 rows k_walk_w8 recomputed)."""
+    import numpy as np
+    out = np.zeros(4, np.int64)
+    f = dbg_lib().mpa_dbg_dp_last_w8
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_void_p]
+    _check(f(ctx.h, out.ctypes.data))
+    return tuple(int(x) for x in out)
+
+
 def dbg_dp_huge_wg_info():
     """mpa_dbg_dp_huge_wg_info(): (W waves per workgroup, R rows per chunk, MIN_BLOCKS) of the workgroup kernel's schedule."""
     import numpy as np

@@ -221,6 +221,7 @@ struct CtxKnobs {
 	int lite_wide = 0;                        // ... 129..256 columns included (MPA_DP_LITE_WIDE; 0, the default until it has been measured: those keep the plain sweep)
 	int split_wide = 0;                       // 1025..3072-column extension calls on X_SPLIT8 / X_SPLIT12 instead of k_ext_huge (MPA_DP_SPLIT_WIDE; 0, the default until it has been measured)
 	int huge_wg = 0;                          // X_HUGE calls of hwg::MIN_BLOCKS column blocks or more on k_ext_huge_wg, one wave per block (MPA_DP_HUGE_WG; 0, the default until it has been measured)
+	int lite_w8 = 0;                          // ... 257..512 columns included, on eight-wave groups (MPA_DP_LITE_W8; 0 until measured; independent of lite_wide; off with the worker pool)
 	int mb_wg = 0;                            // traceback calls of class T_MB on k_glob_mb_wg, one wave per block, instead of one wave per call (MPA_DP_MB_WG; 0; off with the worker pool)
 };
 
@@ -264,6 +265,7 @@ struct mpa_ctx_s {
 	mpa_dp_stats_t stats = {};
 	mpa_dp_stats_t total = {};
 	int64_t last_huge[4] = { 0, 0, 0, 0 };    // the last mpa_dp_run's X_HUGE calls on the one-wave kernel, on the workgroup kernel, the latter's column blocks and passes (mpa_dbg_dp_last_huge)
+	int64_t last_w8[4] = { 0, 0, 0, 0 };      // the last mpa_dp_run's T_LITE_W8 calls, their padded cells, the groups k_lite_w8 swept, the blocks k_walk_w8 recomputed (mpa_dbg_dp_last_w8)
 	int64_t last_mb[4] = { 0, 0, 0, 0 };      // the last mpa_dp_run's T_MB traceback calls swept on one wave, on workgroups (k_glob_mb_wg), the latter's column blocks and passes (mpa_dbg_dp_last_mb)
 	int64_t last_ext_calls[16] = { 0 };       // extension calls per DpClass in the last mpa_dp_run (mpa_dbg_dp_last_classes)
 	bool no_split = false;                    // this mpa_dp_run() repeats a round whose workgroup hand-off timed out: 512/1024-column calls go to k_ext_huge

@@ -236,6 +236,7 @@ static CtxKnobs ctx_knobs_from_env(void)
 	if (const char *s = getenv("MPA_TB_BUDGET_MB")) k.tb_budget = (size_t)atoll(s) << 20;
 	if (const char *s = getenv("MPA_DP_LITE_MIN")) k.lite_min = atoi(s);
 	if (const char *s = getenv("MPA_DP_LITE_WIDE")) k.lite_wide = atoi(s) != 0;
+	if (const char *s = getenv("MPA_DP_LITE_W8")) k.lite_w8 = atoi(s) != 0;
 	if (const char *s = getenv("MPA_DP_SPLIT_WIDE")) k.split_wide = atoi(s) != 0;
 	if (const char *s = getenv("MPA_DP_HUGE_WG")) k.huge_wg = atoi(s) != 0;
 	if (const char *s = getenv("MPA_DP_MB_WG")) k.mb_wg = atoi(s) != 0;

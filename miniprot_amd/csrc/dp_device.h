@@ -53,7 +53,8 @@ enum DpClass : int32_t {
 	// ... and the checkpointed traceback (below): packed sweep + walk
 	T_LITE16 = 8, T_LITE32, T_LITE64,   // 8 / 4 / 2 calls per wave
 	T_LITE128,                   // 65..128 columns, one call per wave
-	T_LITE_W4                    // 129..256 columns, a four-wave group per pair of calls (k_lite_wide)
+	T_LITE_W4,                   // 129..256 columns, a four-wave group per pair of calls (k_lite_wide)
+	T_LITE_W8                    // 257..512 columns, an eight-wave group per pair of calls (k_lite_w8; MPA_DP_LITE_W8=1, else such calls are T_W8)
 };
 __host__ __device__ static inline bool is_checkpointed(int32_t tb_cls) { return tb_cls >= T_LITE16; }
 
@@ -99,35 +100,46 @@ struct ExtWave {
 // 129..256 columns (class 12: a group of four waves per PAIR of calls, lite_wide_body; call slot s = int16 half s of every lane, wave w
 // owns the columns [64 w, 64 w + 64)): the same words with the wave index added -- see the lite_wide_* functions below, which the
 // sweep, the walk and the executor's pool sizing all call.
+// 257..512 columns (class 13: a group of eight waves per pair of calls, the same body and the same words with eight waves): the
+// lite_group_* functions below with nw = 8, of which the lite_wide_* functions are the four-wave instance.
 #define MPA_TB_BLOCK 96
 #define MPA_LITE_SLOT_SHIFT 8        /* DTask::flag bits 8..11: the call's slot in its wave */
 #define MPA_LITE_WIDE_WAVES 4        /* waves of a class-12 group: 256 columns */
+#define MPA_LITE_W8_WAVES 8          /* waves of a class-13 group: 512 columns */
 
-// ---- class 12: the one definition of where a group's extension bits and checkpoints lie (dword offsets from the group's lite_off / ck_off)
+// ---- classes 12 and 13: the one definition of where a group's extension bits and checkpoints lie (dword offsets from the group's
+// lite_off / ck_off), by the waves nw of a group (4 or 8: 64 nw columns)
 // bits: one dword per lane, wave and three rows
-__host__ __device__ static inline int64_t lite_wide_bits_dwords(int32_t max_nl)       // reserved per group whose longest call has max_nl rows
+__host__ __device__ static inline int64_t lite_group_bits_dwords(int32_t nw, int32_t max_nl)   // reserved per group whose longest call has max_nl rows
 {
-	return ((int64_t)max_nl / 3 + 2) * (MPA_LITE_WIDE_WAVES * 64);
+	return ((int64_t)max_nl / 3 + 2) * (nw * 64);
 }
-// (row 2 <= i, column 0 <= j < 256, call slot 0 / 1) -> dword offset; *shift = position of the cell's nibble in that dword
-__host__ __device__ static inline int64_t lite_wide_bit_at(int32_t i, int32_t j, int32_t slot, int32_t *shift)
+// (row 2 <= i, column 0 <= j < 64 nw, call slot 0 / 1) -> dword offset; *shift = position of the cell's nibble in that dword
+__host__ __device__ static inline int64_t lite_group_bit_at(int32_t nw, int32_t i, int32_t j, int32_t slot, int32_t *shift)
 {
 	const uint32_t r = (uint32_t)(i - 2);
 	*shift = 16 * slot + 4 * (2 - (int32_t)(r % 3));
-	return (int64_t)(r / 3) * (MPA_LITE_WIDE_WAVES * 64) + j;                        // (j = 64 * wave + lane)
+	return (int64_t)(r / 3) * (nw * 64) + j;                                         // (j = 64 * wave + lane)
 }
-// checkpoints: nine dwords (64 apart) per lane and wave at the top of every block k >= 1, the four waves of a block one after the other
-__host__ __device__ static inline int64_t lite_wide_ckpt_dwords(int32_t max_nl)
+// checkpoints: nine dwords (64 apart) per lane and wave at the top of every block k >= 1, the nw waves of a block one after the other
+__host__ __device__ static inline int64_t lite_group_ckpt_dwords(int32_t nw, int32_t max_nl)
 {
 	const int32_t nb = max_nl > 3 ? (max_nl - 3) / MPA_TB_BLOCK : 0;                 // blocks with a first row 2 + k * MPA_TB_BLOCK <= max_nl - 1, k >= 1
-	return (int64_t)nb * 9 * (MPA_LITE_WIDE_WAVES * 64);
+	return (int64_t)nb * 9 * (nw * 64);
 }
 // (block k >= 1, column, call slot) -> dword offset of the first of the nine values (value q at + 64 q); *shift = 16 * slot
-__host__ __device__ static inline int64_t lite_wide_ckpt_at(int32_t k, int32_t j, int32_t slot, int32_t *shift)
+// (the next wave's values of the same block lie MPA_LITE_CKPT_WAVE_STEP dwords further)
+#define MPA_LITE_CKPT_WAVE_STEP (9 * 64)
+__host__ __device__ static inline int64_t lite_group_ckpt_at(int32_t nw, int32_t k, int32_t j, int32_t slot, int32_t *shift)
 {
 	*shift = 16 * slot;
-	return ((int64_t)(k - 1) * MPA_LITE_WIDE_WAVES + (j >> 6)) * (9 * 64) + (j & 63);
+	return ((int64_t)(k - 1) * nw + (j >> 6)) * MPA_LITE_CKPT_WAVE_STEP + (j & 63);
 }
+// ---- class 12: the four-wave instance
+__host__ __device__ static inline int64_t lite_wide_bits_dwords(int32_t max_nl) { return lite_group_bits_dwords(MPA_LITE_WIDE_WAVES, max_nl); }
+__host__ __device__ static inline int64_t lite_wide_bit_at(int32_t i, int32_t j, int32_t slot, int32_t *shift) { return lite_group_bit_at(MPA_LITE_WIDE_WAVES, i, j, slot, shift); }
+__host__ __device__ static inline int64_t lite_wide_ckpt_dwords(int32_t max_nl) { return lite_group_ckpt_dwords(MPA_LITE_WIDE_WAVES, max_nl); }
+__host__ __device__ static inline int64_t lite_wide_ckpt_at(int32_t k, int32_t j, int32_t slot, int32_t *shift) { return lite_group_ckpt_at(MPA_LITE_WIDE_WAVES, k, j, slot, shift); }
 
 struct ExtOut { int32_t nt_len, aa_len, score, flags; };
 
@@ -156,6 +168,7 @@ enum DpUnitKind : int32_t {
 	U_EXT128,                           // up to four independent extension waves of one 65..128-column call each (same layout)
 	U_LITE_W4,                          // one four-wave group of the checkpointed traceback's packed sweep for a pair of 129..256-column calls: swept by
 	                                    // k_lite_wide next to the round (k_dp_round and k_dp_worker do not take it); the kind names it in the MPA_DP_TOP listing
+	U_LITE_W8,                          // ... one eight-wave group for a pair of 257..512-column calls, swept by k_lite_w8 next to the round: the listing only
 	U_KIND_COUNT
 };
 struct DpUnit { int32_t kind, first, count, blk, n_blk, sgroup, xg_first, prio; };   // prio: issue priority 0..3 by expected duration (dp_plan.cpp, plan_units)

@@ -8,7 +8,7 @@
 //      sweeps of the checkpointed traceback and the plain traceback sweeps of the first traceback chunk, costliest unit first
 //      (MPA_DP_POOL=1: the units go to the resident workers of the device's pool, k_dp_worker, instead),
 //   3. next to it on side streams: k_ext_huge (MPA_DP_HUGE_WG=1: and k_ext_huge_wg, one wave per column block, for the calls of four
-//      blocks or more) + k_ext_replay (wider calls, and whatever the int16 sweeps may not take), k_lite_wide
+//      blocks or more) + k_ext_replay (wider calls, and whatever the int16 sweeps may not take), k_lite_wide, k_lite_w8
 //      (129..256-column checkpointed calls), the 512/1024-thread traceback classes, the anti-diagonal prototype, and (MPA_DP_MB_WG=1)
 //      k_glob_mb_wg, one wave per column block, over the T_MB traceback calls, whose units in the round then find no call,
 //   4. k_backtrack per traceback chunk (chunks after the first: stand-alone k_glob_* launches, serial), k_walk for the
@@ -279,6 +279,7 @@ struct DpRun {
 	struct Launch { int side; bool is_ext; };
 	std::vector<Launch> launches;               // side-stream launches so far (side = index of the stream and of its event pair)
 	int l12_side = -1;                          // ... the one of the T_LITE_W4 sweep
+	int l13_side = -1;                          // ... and of the T_LITE_W8 sweep
 	bool round_launched = false;
 	bool pool_pending = false;                  // (worker pool) a round is armed and not yet known to be complete ...
 	unsigned int pool_gen = 0;                  // ... its generation
@@ -320,6 +321,7 @@ static ResLayout res_layout(size_t n, size_t n_glob) { return ResLayout(n, n_glo
 // them there); round.wlist: the calls the walk takes, then the walk's block counter
 static GlobWave *round_list_waves(mpa_ctx_t *ctx, size_t n_calls) { Carve c(64); c.take<int32_t>(n_calls); return Piece<GlobWave>{ c.at, 0 }.in(ctx->round.list.p); }
 static unsigned long long *round_wlist_blocks(mpa_ctx_t *ctx, size_t n_lite) { Carve c(64); c.take<int32_t>(n_lite); return Piece<unsigned long long>{ c.at, 1 }.in(ctx->round.wlist.p); }
+// (the word behind it counts the blocks of k_walk_w8 alone: the pool's 128 bytes of slack hold both)
 
 // ---- 2. pools and staging at the sizes the plan asks for
 static int dp_size_pools(DpRun &R)
@@ -484,6 +486,15 @@ static int dp_side_launches(DpRun &R)
 		HIP_TRY(hipGetLastError());
 		end_side(R), R.l12_side = R.launches.back().side;
 		ctx->stats.launches_glob++;
+	}
+	// ... and of the 257..512-column checkpointed class (U_LITE_W8): a 512-thread launch on a side stream of its own, next to k_lite_wide
+	if (P.lite_w8.cnt > 0) {
+		hipStream_t st = begin_side(R, false);
+		hipLaunchKernelGGL(k_lite_w8, dim3((unsigned)P.lite_w8.cnt), dim3(MPA_LITE_W8_WAVES * 64), 0, st, R.ea, P.lite_w8.first);
+		HIP_TRY(hipGetLastError());
+		end_side(R), R.l13_side = R.launches.back().side;
+		ctx->stats.launches_glob++;
+		ctx->last_w8[2] += P.lite_w8.cnt;
 	}
 	return MPA_OK;
 }
@@ -673,7 +684,7 @@ static int dp_walk(DpRun &R)
 	wk.ga = R.ga, wk.ga.waves = nullptr, wk.list = ctx->round.wlist.as<int32_t>(), wk.n_list = (int32_t)P.n_lite;
 	wk.lite = ctx->round.lite.as<uint32_t>(), wk.ckpt = ctx->round.ckpt.as<uint32_t>(), wk.cig = ctx->round.cig.as<uint32_t>(), wk.n_cigar = ctx->round.ncig.as<int32_t>();
 	wk.n_blocks = round_wlist_blocks(ctx, P.n_lite);
-	HIP_TRY(hipMemsetAsync(wk.n_blocks, 0, 8, s));
+	HIP_TRY(hipMemsetAsync(wk.n_blocks, 0, 16, s));                     // (and the word of k_walk_w8's blocks behind it)
 	// (the list is sorted by class: one launch per class, with the LDS that class's block of direction words needs)
 	size_t at = 0;
 	for (int cls = T_LITE16; cls <= T_LITE_W4; ++cls) {
@@ -686,6 +697,13 @@ static int dp_walk(DpRun &R)
 		}
 		hipLaunchKernelGGL(k_walk, dim3((unsigned)n_c), dim3(64), WALK_LDS(lite_columns(cls)), s, wk);
 		at += n_c;
+	}
+	if (P.walk_cnt_w8 > 0) {                                             // the sixth list: T_LITE_W8, behind its own sweep, on a kernel of its own
+		HIP_TRY(hipGetLastError());
+		wk.list = ctx->round.wlist.as<int32_t>() + at, wk.n_list = P.walk_cnt_w8, wk.n_blocks += 1;
+		if (R.l13_side >= 0) (void)hipStreamWaitEvent(s, ctx->lev[2 * R.l13_side + 1], 0);
+		HIP_TRY(ensure_dynamic_lds((const void*)k_walk_w8, ctx->device, WALK_LDS(lite_columns(T_LITE_W8))));
+		hipLaunchKernelGGL(k_walk_w8, dim3((unsigned)P.walk_cnt_w8), dim3(64), WALK_LDS(lite_columns(T_LITE_W8)), s, wk);
 	}
 	HIP_TRY(hipGetLastError());
 	ctx->stats.launches_glob++;
@@ -749,9 +767,9 @@ static int dp_join_and_download(DpRun &R)
 		HIP_TRY(hipMemcpyAsync(hdn + P.dn.nc, ctx->round.ncig.p, n * 4, hipMemcpyDeviceToHost, s));
 	}
 	if (P.n_split) HIP_TRY(hipMemcpyAsync(hdn + P.dn.err, R.wa.err, 4, hipMemcpyDeviceToHost, s));
-	*(unsigned long long*)(hdn + P.dn.wb) = 0;
+	((unsigned long long*)(hdn + P.dn.wb))[0] = 0, ((unsigned long long*)(hdn + P.dn.wb))[1] = 0;
 	if (R.rz) R.rz->rec.bytes_down += (P.n_split ? 4 : 0) + (P.n_lite ? 8 : 0);
-	if (P.n_lite) HIP_TRY(hipMemcpyAsync(hdn + P.dn.wb, round_wlist_blocks(ctx, P.n_lite), 8, hipMemcpyDeviceToHost, s));
+	if (P.n_lite) HIP_TRY(hipMemcpyAsync(hdn + P.dn.wb, round_wlist_blocks(ctx, P.n_lite), P.walk_cnt_w8 > 0 ? 16 : 8, hipMemcpyDeviceToHost, s));
 	// (MPA_GPU_ROUND1, section 4.15) the step between the rounds, by its own unit's enqueue function: its kernels read the records in place
 	// and are guarded by the words the host checks behind the wait -- a hand-off that timed out, a call outside its slot
 	if (R.rz && R.rz->chain) {
@@ -773,7 +791,7 @@ static int dp_join_and_download(DpRun &R)
 		float ms = 0;
 		(void)hipEventElapsedTime(&ms, ctx->lev[2 * l.side], ctx->lev[2 * l.side + 1]);
 		if (l.is_ext) ms_ext_sum += ms;
-		else if (l.side == R.l12_side) R.ms_glob += ms;                  // (the 129..256-column packed sweep: a traceback sweep like the chunks')
+		else if (l.side == R.l12_side || l.side == R.l13_side) R.ms_glob += ms;   // (the 129..256- and 257..512-column packed sweeps: traceback sweeps like the chunks')
 	}
 	ctx->stats.ms_ext = ms_ext_sum;
 	return MPA_OK;
@@ -831,7 +849,9 @@ static void dp_statistics(DpRun &R)
 	st.alg_bytes_ext = ps.alg_bytes_ext, st.alg_bytes_glob = ps.alg_bytes_glob + 4 * R.pool_n;   // (+ the CIGARs' own words)
 	st.n_ckpt = ps.n_ckpt, st.cells_ckpt = ps.cells_ckpt, st.n_ckpt_wide = ps.n_ckpt_wide, st.cells_ckpt_wide = ps.cells_ckpt_wide;
 	st.cells_ext_round = ps.cells_ext_round, st.cells_glob_round = ps.cells_glob_round;
-	st.walk_blocks = (int64_t)*(const unsigned long long*)(R.hdn + R.plan.dn.wb);
+	// (k_walk's blocks and, counted apart for mpa_dbg_dp_last_w8, k_walk_w8's)
+	ctx->last_w8[3] = (int64_t)((const unsigned long long*)(R.hdn + R.plan.dn.wb))[1];
+	st.walk_blocks = (int64_t)((const unsigned long long*)(R.hdn + R.plan.dn.wb))[0] + ctx->last_w8[3];
 	float ms = 0;
 	(void)hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); st.ms_prep = ms;
 	st.ms_glob = R.ms_glob, st.ms_backtrack = R.ms_bt;
@@ -849,7 +869,7 @@ static void dp_statistics(DpRun &R)
 	t.cells_ext_round += st.cells_ext_round, t.cells_glob_round += st.cells_glob_round, t.ms_round += st.ms_round, t.launches_round += st.launches_round;
 }
 
-// MPA_DP_MB_WG as the executor applies it: off with the worker pool, like MPA_DP_LITE_WIDE and MPA_DP_SPLIT_WIDE
+// MPA_DP_MB_WG as the executor applies it: off with the worker pool, like MPA_DP_LITE_WIDE, MPA_DP_LITE_W8 and MPA_DP_SPLIT_WIDE
 static bool dp_mb_wg(const mpa_ctx_t *ctx) { return ctx->knobs.mb_wg && !dp_pool_enabled(); }
 
 // the executor's knobs as the planner takes them (the environment: read when the context was created, or once per process)
@@ -860,6 +880,7 @@ static DpPlanKnobs dp_plan_knobs(const mpa_ctx_t *ctx)
 	DpPlanKnobs kn;
 	kn.lite_min = ctx->knobs.lite_min, kn.lite_wide = ctx->knobs.lite_wide, kn.no_split = ctx->no_split, kn.antidiag = ctx->antidiag, kn.pool = dp_pool_enabled();
 	kn.split_wide = ctx->knobs.split_wide && !kn.pool && !kn.no_split;
+	kn.lite_w8 = ctx->knobs.lite_w8 && !kn.pool;
 	kn.ext_dual = ext_dual, kn.unit_prio = unit_prio, kn.tb_budget = (int64_t)ctx->knobs.tb_budget;
 	return kn;
 }
@@ -1016,6 +1037,13 @@ static int mpa_dp_run_impl(mpa_ctx_t *ctx, const mpa_idx_t *mi, const mpa_dpopt_
 	memcpy(ctx->last_ext_calls, plan.ext_calls, sizeof(ctx->last_ext_calls));
 	memset(ctx->last_huge, 0, sizeof(ctx->last_huge));
 	memset(ctx->last_mb, 0, sizeof(ctx->last_mb));
+	memset(ctx->last_w8, 0, sizeof(ctx->last_w8));
+	for (size_t k = plan.n_reg_glob; k < plan.glob_ids.size() && !plan.on_device; ++k) {      // (a plan made on the device holds no call of the class)
+		const DTask &t = plan.tasks[plan.glob_ids[k]];
+		if (t.cls == T_LITE_W8) ++ctx->last_w8[0], ctx->last_w8[1] += (int64_t)(t.nl > 2 ? t.nl - 2 : 0) * t.ncol;
+	}
+	if (timing_on() && ctx->last_w8[0] > 0)
+		fprintf(stderr, "[mpa-timing]   dp: %lld traceback calls of 257..512 columns checkpointed, in %d eight-wave groups\n", (long long)ctx->last_w8[0], plan.lite_w8.cnt);
 	if (timing_on() && plan.ext_wide[0].cnt + plan.ext_wide[1].cnt > 0)
 		fprintf(stderr, "[mpa-timing]   dp: %d + %d groups of the 2048- / 3072-column extension classes (8 / 12 workgroups each), %lld boundaries\n", plan.ext_wide[0].cnt, plan.ext_wide[1].cnt, (long long)plan.n_bound);
 	DpRun R{ ctx, ctx->stream, plan, kn, in };
@@ -1160,6 +1188,7 @@ size_t dp_round_args_bytes() { return sizeof(DpRoundArgs); }
 void dp_last_ext_calls(const mpa_ctx_t *ctx, int64_t ext_calls[16]) { memcpy(ext_calls, ctx->last_ext_calls, sizeof(ctx->last_ext_calls)); }
 void dp_last_huge(const mpa_ctx_t *ctx, int64_t out[4]) { memcpy(out, ctx->last_huge, sizeof(ctx->last_huge)); }
 void dp_last_mb(const mpa_ctx_t *ctx, int64_t out[4]) { memcpy(out, ctx->last_mb, sizeof(ctx->last_mb)); }
+void dp_last_w8(const mpa_ctx_t *ctx, int64_t out[4]) { memcpy(out, ctx->last_w8, sizeof(ctx->last_w8)); }
 // mpa_dbg_dp_plan_device on a context (dpplan_dbg.cpp): the device planner on a task table, then every section it left in the pools
 // downloaded into a plan's vectors and serialised as mpa_dbg_dp_plan does.  1: declined (the last error says why).
 int64_t dev_dp_plan_dbg(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, const mpa_qbatch_t *q, int64_t n, const mpa_dp_task_t *in,

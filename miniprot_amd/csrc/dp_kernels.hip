@@ -1492,9 +1492,12 @@ struct GlobResume {
 	uint16_t *tb;
 	int4 *bnd;                   // block-major sweep: the boundary records of the block's rows, [n_rows + 2]
 };
-template<int G, bool MB, bool EXT = false, bool WIDE = false, int NCB = 1>
+// CKSTEP > 0 (with NCB = 1; the 257..512-column walk, k_walk_w8): the checkpoint of column block cb lies CKSTEP dwords behind that of
+// block cb - 1, in the same half -- the pair is worked out per column block from ck[0] / sh[0], not carried for every block
+template<int G, bool MB, bool EXT = false, bool WIDE = false, int NCB = 1, int CKSTEP = 0>
 __device__ __forceinline__ void glob_narrow(const GlobArgs &a, const GlobWave &wv, const WavePos wp, const GlobResume<NCB> *rz = nullptr)
 {
+	static_assert(CKSTEP == 0 || (NCB == 1 && MB), "checkpoints at a fixed step: one pair, block-major");
 	constexpr int NG = 64 / G;
 	int16_t *lds_prof = (int16_t*)wp.lds;            // [NG][22][G] for the current column block
 	const int lane = wp.lane, grp = lane / G, col = lane % G;
@@ -1556,6 +1559,7 @@ __device__ __forceinline__ void glob_narrow(const GlobArgs &a, const GlobWave &w
 				if (cb == k) p = rz->ck[k], sh = rz->sh[k];
 				if (lb == k) pl = rz->ck[k], shl = rz->sh[k];
 			}
+			if (CKSTEP > 0) p += (int64_t)cb * CKSTEP, pl += (int64_t)lb * CKSTEP;
 			p += gc < ncol ? col : 0;
 			auto half_splat = [&](const uint32_t x) { return spl((int32_t)(x >> sh)); };
 			gs.H[1] = half_splat(p[0]), gs.H[0] = half_splat(p[64]), gs.H[2] = half_splat(p[128]);

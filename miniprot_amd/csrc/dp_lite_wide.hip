@@ -1,6 +1,7 @@
-// dp_lite_wide.hip -- k_lite_wide and its body lite_wide_body: the packed int16 sweep of the checkpointed traceback for calls of
-// 129..256 columns (class 12, dp_device.h).  A launch of its own on a side stream of the round (dp_exec.hip, next to k_dp_round, like
-// the 512/1024-thread traceback classes); none of this code runs inside k_dp_round or k_dp_worker.
+// dp_lite_wide.hip -- k_lite_wide, k_lite_w8 and their body lite_wide_body<NW>: the packed int16 sweep of the checkpointed traceback for
+// calls of 129..256 columns (class 12, dp_device.h; four waves) and of 257..512 columns (class 13; eight waves).  Launches of their own
+// on side streams of the round (dp_exec.hip, next to k_dp_round, like the 512/1024-thread traceback classes); none of this code runs
+// inside k_dp_round or k_dp_worker.
 // Included by dp_exec.hip behind dp_kernels.hip.  Relies on dp_kernels.hip for: WavePos / whole_block, lds_barrier, the packed int16
 // helpers, ExtArgs, the profile and record-ring layout (PROF_*, EXT_WIDE_RING, ring_entry, prof2s, lds_s16p, v2u / lds_u2p) and the
 // row macros MPA_ROW_HEAD_L, MPA_ROW_TAIL_WL and MPA_NIBBLE -- the rows are defined there, next to the ones they are variants of.
@@ -17,17 +18,29 @@ namespace mpa {
 // of ext_narrow<G, true>: the four differences whose signs are the extension bits, the three-row nibble word and the checkpoints.
 // The two calls may differ in rows: the group iterates max_nl, a call past its end only produces bits and checkpoints nobody
 // reads; its score H(nl - 1, al - 1) is taken from the wave and lane that own column al - 1 behind the step that holds row nl - 1.
+// NW waves (4: class 12, k_lite_wide; 8: class 13, 257..512 columns, k_lite_w8): what depends on the count is the profile area, the
+// exchange slots (3 NW per step parity, in a stride of 16 or 32), where the bits and checkpoints lie (lite_group_*, dp_device.h) and
+// how far the last wave runs behind the first -- 3 (NW - 1) rows, which the record ring must still hold (below).
+// Barriers: a wave passes w of them before its first step, one per step, and NW - 1 - w behind its last; the steps are counted by the
+// one loop nest below from max_nl alone (the group's longer call: a scalar every wave reads from the same descriptor), never from the
+// wave index, a call's own rows or an empty half -- so every wave of a group passes NW - 1 + steps(max_nl) barriers, whatever max_nl.
 // ------------------------------------------------------------------------------------------------
-#define LITE_WIDE_LDS ((size_t)MPA_LITE_WIDE_WAVES * 2 * 64 * PROF_COL_STRIDE + (EXT_WIDE_RING + 1) * 16 + 256 + 32 + (64 * 8 + 32))   /* bytes per group; a multiple of 16 */
+#define LITE_GROUP_XSLOTS(NW) ((NW) <= 4 ? 16 : 32)        /* exchange slots per step parity: 3 NW of them are used */
+#define LITE_GROUP_LDS(NW) ((size_t)(NW) * 2 * 64 * PROF_COL_STRIDE + (EXT_WIDE_RING + 1) * 16 + 2 * LITE_GROUP_XSLOTS(NW) * 8 + 32 + (64 * 8 + 32))   /* bytes per group; a multiple of 16 */
+#define LITE_WIDE_LDS LITE_GROUP_LDS(MPA_LITE_WIDE_WAVES)
+template<int NW>
 __device__ __forceinline__ void lite_wide_body(const ExtArgs &a, const int group_idx, const WavePos wp)
 {
-	constexpr int NW = MPA_LITE_WIDE_WAVES, RING = EXT_WIDE_RING;
+	constexpr int RING = EXT_WIDE_RING, XS = LITE_GROUP_XSLOTS(NW);
+	static_assert(3 * NW <= XS, "a step's exchange slots: three per wave");
+	// the leading wave's refill at row i overwrites the ring slots of rows i - 34 .. i - 23; the last wave is then at row i - 3 (NW - 1) and reads rows from there on
+	static_assert(RING == 48 && 3 * (NW - 1) < 23, "the record ring must still hold the last wave's rows");
 	// per wave: profile of its 64 columns for both halves [2][64 columns][23] int16; then the record ring, the exchange slots
 	// [2 step parities][NW waves][3 rows] of {scan, H of the wave's last column}, 32 bytes of -inf and the dump area
 	char *lds_prof = wp.lds;
 	uint4 *ring = (uint4*)(lds_prof + NW * 2 * 64 * PROF_COL_STRIDE);  // [RING + 1] decoded records of both halves
-	uint2 *xch = (uint2*)(ring + RING + 1);                          // [2][16] slots: parity * 16 + 3 w + k
-	uint2 *xneg = xch + 32;                                          // [4] {-inf, -inf}
+	uint2 *xch = (uint2*)(ring + RING + 1);                          // [2][XS] slots: parity * XS + 3 w + k
+	uint2 *xneg = xch + 2 * XS;                                      // [4] {-inf, -inf}
 	uint2 *xdump = xneg + 4;                                         // [64 + 4]
 	const int lane = wp.lane, w = wp.w;                              // w: wave index inside the group, scalar
 	const ExtWave *wvp = &a.waves[group_idx];
@@ -60,7 +73,7 @@ __device__ __forceinline__ void lite_wide_body(const ExtArgs &a, const int group
 			*(int16_t*)(dst + cc * PROF_COL_STRIDE + aidx * PROF_AA_STRIDE) = gcc < t->pw ? src[aidx * t->pw + gcc] : (int16_t)NEG16;
 		}
 	}
-	if (wp.tg < 36) xch[wp.tg] = make_uint2(NEGP, NEGP);           // the exchange slots and, behind them, the slots of -inf
+	if (wp.tg < 2 * XS + 4) xch[wp.tg] = make_uint2(NEGP, NEGP);   // the exchange slots and, behind them, the slots of -inf
 	// record ring, filled by the leading wave (ext_wide_body's scheme): row r in slot (r + 44) % 48
 	const bool loader = w == 0 && lane < 12;
 	uint2 pf = make_uint2(0, 0);
@@ -84,7 +97,7 @@ __device__ __forceinline__ void lite_wide_body(const ExtArgs &a, const int group
 	const uint32_t pb0 = lds0 + (uint32_t)(((w * 2 + 0) * 64 + lane) * PROF_COL_STRIDE), pb1 = pb0 + 64 * PROF_COL_STRIDE;
 	const uint32_t xch0 = lds0 + (uint32_t)((char*)xch - wp.lds), xneg0 = lds0 + (uint32_t)((char*)xneg - wp.lds), xdump0 = lds0 + (uint32_t)((char*)xdump - wp.lds);
 	const uint32_t xwr_even = lane == 63 ? xch0 + (uint32_t)(3 * w) * 8 : xdump0 + (uint32_t)lane * 8;
-	const uint32_t xwr_flip = lane == 63 ? 128u : 0u;              // (the other parity's slots: + 16 slots)
+	const uint32_t xwr_flip = lane == 63 ? (uint32_t)(XS * 8) : 0u; // (the other parity's slots: + XS slots)
 	const bool takes_left = lane == 0 && w > 0;
 
 	uint32_t Hr[3], Hs[3], Dr[3], dn[3], ac[3], M[3], A = NEGP, B = NEGP, C = NEGP;
@@ -105,10 +118,10 @@ __device__ __forceinline__ void lite_wide_body(const ExtArgs &a, const int group
 	// (what a checkpoint wants), this wave's slice of the group's bit words and checkpoints (dp_device.h)
 	uint32_t acc = 0, dDc = 0, Dold = NEGP;
 	int32_t sh_;
-	uint32_t *lite_p = a.lite + wvp->lite_off + lite_wide_bit_at(2, gc, 0, &sh_);
-	const int64_t lite_step = lite_wide_bit_at(5, gc, 0, &sh_) - lite_wide_bit_at(2, gc, 0, &sh_);
+	uint32_t *lite_p = a.lite + wvp->lite_off + lite_group_bit_at(NW, 2, gc, 0, &sh_);
+	const int64_t lite_step = lite_group_bit_at(NW, 5, gc, 0, &sh_) - lite_group_bit_at(NW, 2, gc, 0, &sh_);
 	auto checkpoint = [&](const int32_t i, const uint32_t d3) {        // top of row i = 2 + k * MPA_TB_BLOCK: slots 0, 1, 2 hold rows i-1, i-2, i-3
-		uint32_t *p = a.ckpt + wvp->ck_off + lite_wide_ckpt_at((i - 2) / MPA_TB_BLOCK, gc, 0, &sh_);
+		uint32_t *p = a.ckpt + wvp->ck_off + lite_group_ckpt_at(NW, (i - 2) / MPA_TB_BLOCK, gc, 0, &sh_);
 		p[0] = Hr[0], p[64] = Hr[1], p[128] = Hr[2], p[192] = Dr[0], p[256] = Dr[1], p[320] = d3, p[384] = A, p[448] = B, p[512] = C;
 	};
 	// the score of a call whose last row is among the rows [i, i + 3) just swept: h0, h1, h2 = their H rows (slots 2, 1, 0; passed by
@@ -135,7 +148,7 @@ __device__ __forceinline__ void lite_wide_body(const ExtArgs &a, const int group
 	uint32_t xwr = 0;
 	auto step_begin = [&](const int par) {                             // what the wave to the left produced for the step's three rows, in the previous step
 		uint32_t at = xneg0;
-		if (takes_left) at = xch0 + (uint32_t)(((par ^ 1) * 16 + 3 * (w - 1)) * 8);
+		if (takes_left) at = xch0 + (uint32_t)(((par ^ 1) * XS + 3 * (w - 1)) * 8);
 #pragma unroll
 		for (int k = 0; k < 3; ++k) cv[k] = *(lds_u2p)(uintptr_t)(at + 8 * k);
 		xwr = xwr_even + (par ? xwr_flip : 0u);
@@ -249,7 +262,13 @@ __device__ __forceinline__ void lite_wide_body(const ExtArgs &a, const int group
 __global__ __launch_bounds__(MPA_LITE_WIDE_WAVES * 64) void k_lite_wide(ExtArgs a, int first_group)
 {
 	__shared__ __attribute__((aligned(16))) char lds[LITE_WIDE_LDS];
-	lite_wide_body(a, first_group + (int)blockIdx.x, whole_block(lds));
+	lite_wide_body<MPA_LITE_WIDE_WAVES>(a, first_group + (int)blockIdx.x, whole_block(lds));
+}
+// (257..512 columns, class 13: the same body on eight waves, on a side stream of its own; about 51 KB of LDS)
+__global__ __launch_bounds__(MPA_LITE_W8_WAVES * 64) void k_lite_w8(ExtArgs a, int first_group)
+{
+	__shared__ __attribute__((aligned(16))) char lds[LITE_GROUP_LDS(MPA_LITE_W8_WAVES)];
+	lite_wide_body<MPA_LITE_W8_WAVES>(a, first_group + (int)blockIdx.x, whole_block(lds));
 }
 
 } // namespace mpa

@@ -142,8 +142,14 @@ static void pack_waves(DpPlan &P)
 	p = P.n_reg_glob;
 	for (int cls = T_LITE16; cls <= T_LITE128; ++cls) P.lite[cls - T_LITE16] = pack_ext_class(P, P.glob_ids, p, cls, lite_calls_per_wave(cls), true);
 	P.lite_w4 = pack_ext_class(P, P.glob_ids, p, T_LITE_W4, lite_calls_per_wave(T_LITE_W4), true);   // pools sized by the group's longest call
+	P.lite_w8 = pack_ext_class(P, P.glob_ids, p, T_LITE_W8, lite_calls_per_wave(T_LITE_W8), true);
 	for (int c = 0; c < 5; ++c) P.walk_cnt[c] = 0;
-	for (size_t k = P.n_reg_glob; k < P.glob_ids.size(); ++k) ++P.walk_cnt[T[P.glob_ids[k]].cls - T_LITE16];
+	P.walk_cnt_w8 = 0;
+	for (size_t k = P.n_reg_glob; k < P.glob_ids.size(); ++k) {
+		const int cls = T[P.glob_ids[k]].cls;
+		if (cls == T_LITE_W8) ++P.walk_cnt_w8;
+		else ++P.walk_cnt[cls - T_LITE16];
+	}
 	// per-row keys of the wide extension kernels: [group][2 halves][key_stride]
 	for (int k = X_W2; k < kNumExtPacked + kNumExtWide; ++k) {
 		const WaveRange &r = ext_range(P, ext_class_at(k));
@@ -269,6 +275,8 @@ std::string dp_plan_top(const DpPlan &P, const DpPlanKnobs &kn)
 	std::vector<Cost> shown = unit_costs(P, kn);
 	if (shown.empty()) return "";
 	for (int k = 0; k < P.lite_w4.cnt; ++k) shown.push_back(Cost{ (int64_t)P.ewaves[P.lite_w4.first + k].max_nl * NS_LITE_W4, DpUnit{ U_LITE_W4, P.lite_w4.first + k, 1, 0, 1, 0, 0, 0 } });
+	// (k_lite_w8's groups likewise; their rows have not been measured: the four-wave groups' constant stands in)
+	for (int k = 0; k < P.lite_w8.cnt; ++k) shown.push_back(Cost{ (int64_t)P.ewaves[P.lite_w8.first + k].max_nl * NS_LITE_W4, DpUnit{ U_LITE_W8, P.lite_w8.first + k, 1, 0, 1, 0, 0, 0 } });
 	std::stable_sort(shown.begin(), shown.end(), costlier);
 	int64_t by_kind[U_KIND_COUNT] = { 0 }, n_kind[U_KIND_COUNT] = { 0 };
 	for (const Cost &c : shown) by_kind[c.u.kind] += c.cost, ++n_kind[c.u.kind];
@@ -323,7 +331,7 @@ void dp_plan_stats(DpPlan &P)
 		// (the first traceback chunk rides in the round's launch, except the 512/1024-thread classes)
 		if (round && ((!P.chunks.empty() && gi < P.chunks[0].last && t.cls != T_W8 && t.cls != T_W16) || gi >= P.n_reg_glob)) st.cells_glob_round += cells;
 		st.n_glob++, st.cells_glob += cells;
-		if (t.cls == T_LITE_W4) st.n_ckpt_wide++, st.cells_ckpt_wide += cells;
+		if (t.cls == T_LITE_W4 || t.cls == T_LITE_W8) st.n_ckpt_wide++, st.cells_ckpt_wide += cells;   // (the classes of a group of waves per pair of calls)
 		else if (is_checkpointed(t.cls)) st.n_ckpt++, st.cells_ckpt += cells;
 		st.alg_bytes_glob += (t.nl + 1) / 2 + t.al + 12 + 2 * cells + 2 * ((int64_t)t.nl + t.al);   // (+ 4 B per CIGAR word: the executor adds them)
 	}
@@ -354,7 +362,7 @@ int dp_plan(const mpa_dp_task_t *in, int64_t n, const int64_t *ctg_len, size_t c
 	return MPA_OK;
 }
 
-int64_t dp_plan_serialize(DpPlan &P, const DpPlanKnobs &kn, void *buf, int64_t cap, bool wide)
+int64_t dp_plan_serialize(DpPlan &P, const DpPlanKnobs &kn, void *buf, int64_t cap, bool wide, bool w8)
 {
 	// the stages the executor runs behind its uploads
 	for (size_t ri = 0; ri < P.chunks.size(); ++ri) dp_plan_chunk_waves(P, ri);
@@ -362,10 +370,10 @@ int64_t dp_plan_serialize(DpPlan &P, const DpPlanKnobs &kn, void *buf, int64_t c
 	if (dp_plan_units(P, kn, units.data())) return P.rc;
 	units.resize(P.n_units);
 	dp_plan_stats(P);
-	return dp_plan_write(P, units, buf, cap, wide);
+	return dp_plan_write(P, units, buf, cap, wide, w8);
 }
 
-int64_t dp_plan_write(const DpPlan &P, const std::vector<DpUnit> &units, void *buf, int64_t cap, bool wide)
+int64_t dp_plan_write(const DpPlan &P, const std::vector<DpUnit> &units, void *buf, int64_t cap, bool wide, bool w8)
 {
 	std::vector<int64_t> h;
 	auto H = [&h](int64_t v) { h.push_back(v); };
@@ -409,13 +417,16 @@ int64_t dp_plan_write(const DpPlan &P, const std::vector<DpUnit> &units, void *b
 	for (const Sec &s : secs) H((int64_t)at), H((int64_t)s.bytes), at += (s.bytes + 7) & ~(size_t)7;
 	// (mpa_dbg_dp_plan_wide) behind everything else: first and count of X_SPLIT8 and of X_SPLIT12, the boundary count
 	const int64_t tail[5] = { P.ext_wide[0].first, P.ext_wide[0].cnt, P.ext_wide[1].first, P.ext_wide[1].cnt, P.n_bound };
-	const size_t total = at + (wide ? sizeof(tail) : 0);
+	// (mpa_dbg_dp_plan_w8) behind those: first and count of T_LITE_W8's descriptors, the calls of its walk list
+	const int64_t tail_w8[3] = { P.lite_w8.first, P.lite_w8.cnt, P.walk_cnt_w8 };
+	const size_t total = at + (wide ? sizeof(tail) : 0) + (w8 ? sizeof(tail_w8) : 0);
 	if (buf && (int64_t)total <= cap) {
 		memset(buf, 0, total);
 		memcpy(buf, h.data(), h.size() * 8);
 		size_t k = h.size() - 2 * (sizeof(secs) / sizeof(secs[0]));
 		for (const Sec &s : secs) { if (s.bytes) memcpy((char*)buf + h[k], s.p, s.bytes); k += 2; }
 		if (wide) memcpy((char*)buf + at, tail, sizeof(tail));
+		if (w8) memcpy((char*)buf + at + (wide ? sizeof(tail) : 0), tail_w8, sizeof(tail_w8));
 	}
 	return (int64_t)total;
 }
@@ -451,6 +462,7 @@ int dp_plan_from_head(const DpDevHead &H, const int32_t *glob_ids, const mpa_qba
 	P.on_device = true;
 	if (H.status & DPP_REFUSED) return refuse(P, MPA_ERR_UNSUPPORTED, "a call the planner refuses");
 	if (H.status & DPP_HUGE) return refuse(P, MPA_ERR_UNSUPPORTED, "a call of the one-wave int32 extension class");
+	if (H.status & DPP_LITE_W8) return refuse(P, MPA_ERR_UNSUPPORTED, "a call of the eight-wave checkpointed traceback class");
 	if (H.n_reg_glob > 1 && (size_t)H.tb_max * 2 > (size_t)kn.tb_budget) return refuse(P, MPA_ERR_UNSUPPORTED, "more than one traceback chunk");
 	P.cnt = DpPlan::Counts{ (size_t)H.n, (size_t)H.n_ext, (size_t)H.n_glob, (size_t)H.n_prep, (size_t)H.n_ewaves, 0 };
 	P.glob_ids.assign(glob_ids, glob_ids + H.n_glob);

@@ -41,6 +41,7 @@ struct DpPlan {
 	std::vector<ExtWave> ewaves;
 	WaveRange ext[kNumExtPacked], ext128, lite[4], lite_w4;   // ... its parts: X_16 .. X_SPLIT4, X_128, T_LITE16 .. T_LITE128, T_LITE_W4
 	WaveRange ext_wide[kNumExtWide];            // ... and X_SPLIT8, X_SPLIT12 (split_wide), whose descriptors lie between X_SPLIT4's and X_128's
+	WaveRange lite_w8;                          // ... and T_LITE_W8 (lite_w8), behind T_LITE_W4's
 	std::vector<int32_t> huge_ids;              // X_HUGE calls, with one GlobWave each
 	std::vector<GlobWave> huge_waves;
 	PenTable pen;
@@ -49,6 +50,7 @@ struct DpPlan {
 	bool round_has_glob = false;
 	size_t n_units = 0, n_group = 0;            // (dp_plan_units) costliest first; with the pool: whole-workgroup units [0, n_group), then the one-wave units
 	int32_t walk_cnt[5] = { 0, 0, 0, 0, 0 };    // walk launches: calls per class T_LITE16 .. T_LITE_W4, consecutive in glob_ids behind n_reg_glob
+	int32_t walk_cnt_w8 = 0;                    // ... and of T_LITE_W8, the sixth list behind them (k_walk_w8)
 	// totals (units as in DTask) and what follows from them
 	int32_t max_nl = 0, max_nl_ext = 0;
 	int64_t rec_total = 0, rec_pad = 0, prof_total = 0, cig_total = 0, bnd_total = 0, hkey_total = 0, lite_total = 0, ck_total = 0, tb_max = 0;
@@ -93,10 +95,11 @@ int64_t dp_plan_prep_bound(const mpa_dp_task_t *in, int64_t n, int64_t *max_nl, 
 std::string dp_plan_top(const DpPlan &plan, const DpPlanKnobs &kn);
 // the whole plan as mpa_dbg_dp_plan() hands it out (mpamd.h): runs the later stages, returns the bytes it takes (written when they fit cap)
 // or plan.rc
-// (wide: as mpa_dbg_dp_plan_wide() does, mpamd_dbg.h: five more words behind everything else)
-int64_t dp_plan_serialize(DpPlan &plan, const DpPlanKnobs &kn, void *buf, int64_t cap, bool wide = false);
+// (wide: as mpa_dbg_dp_plan_wide() does, mpamd_dbg.h: five more words behind everything else; w8: as mpa_dbg_dp_plan_w8() does: three
+// more behind those -- first and count of T_LITE_W8's descriptors, the calls of its walk list)
+int64_t dp_plan_serialize(DpPlan &plan, const DpPlanKnobs &kn, void *buf, int64_t cap, bool wide = false, bool w8 = false);
 // ... the serialisation alone, of a plan whose later stages have run (dp_plan_serialize, or the device planner's vectors filled in)
-int64_t dp_plan_write(const DpPlan &plan, const std::vector<DpUnit> &units, void *buf, int64_t cap, bool wide = false);
+int64_t dp_plan_write(const DpPlan &plan, const std::vector<DpUnit> &units, void *buf, int64_t cap, bool wide = false, bool w8 = false);
 
 // ---- dp_exec.hip, for the test hook mpa_dbg_dp_plan_device (dpplan_dbg.cpp)
 size_t dp_round_args_bytes();            // the size of the worker pool's argument block: the model's round_args_bytes
@@ -106,6 +109,8 @@ void dp_last_ext_calls(const mpa_ctx_t *ctx, int64_t ext_calls[16]);
 void dp_last_huge(const mpa_ctx_t *ctx, int64_t out[4]);
 // ... and for mpa_dbg_dp_last_mb: the last mpa_dp_run's T_MB traceback calls swept on one wave, on workgroups, the latter's blocks and passes
 void dp_last_mb(const mpa_ctx_t *ctx, int64_t out[4]);
+// ... and for mpa_dbg_dp_last_w8: the last mpa_dp_run's T_LITE_W8 calls, their padded cells, the groups k_lite_w8 swept, the blocks k_walk_w8 recomputed
+void dp_last_w8(const mpa_ctx_t *ctx, int64_t out[4]);
 // the device planner on a context, what it left serialised like dp_plan_serialize; 1: it declined (the last error says why)
 int64_t dev_dp_plan_dbg(mpa_ctx_t *ctx, const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, const mpa_qbatch_t *q, int64_t n, const mpa_dp_task_t *in,
                         const DpPlanKnobs &kn, void *buf, int64_t cap, bool wide = false);

@@ -32,15 +32,22 @@ MPA_DPP_HD int ext_class_of(int32_t ncol, bool split_wide = false)
 }
 MPA_DPP_HD int tb_class_of(int32_t ncol) { int c = T_16; while (c < T_MB && ncol > (16 << c)) ++c; return c; }   // 16, 32, ... 1024 columns, then block-major
 MPA_DPP_HD int tb_calls_per_wave(int cls) { return cls == T_16 ? 4 : cls == T_32 ? 2 : 1; }                  // the plain traceback sweep: one call per group of lanes
-MPA_DPP_HD int lite_columns(int cls) { return 16 << (cls - T_LITE16); }                                      // 16, 32, 64, 128, 256
-MPA_DPP_HD int lite_calls_per_wave(int cls) { return cls == T_LITE128 ? 1 : cls == T_LITE_W4 ? 2 : 2 * (64 / lite_columns(cls)); }
+MPA_DPP_HD int lite_columns(int cls) { return 16 << (cls - T_LITE16); }                                      // 16, 32, 64, 128, 256, 512
+MPA_DPP_HD int lite_calls_per_wave(int cls) { return cls == T_LITE128 ? 1 : cls == T_LITE_W4 || cls == T_LITE_W8 ? 2 : 2 * (64 / lite_columns(cls)); }
 // dwords of extension bits / checkpoints of one packed-sweep descriptor whose longest call has max_nl rows (layout: dp_device.h)
-MPA_DPP_HD int64_t lite_bits_dwords(int cls, int32_t max_nl) { return cls == T_LITE_W4 ? lite_wide_bits_dwords(max_nl) : ((int64_t)max_nl / 3 + 2) * 64; }
-MPA_DPP_HD int64_t lite_ckpt_dwords(int cls, int32_t max_nl) { return cls == T_LITE_W4 ? lite_wide_ckpt_dwords(max_nl) : (int64_t)(max_nl > 3 ? (max_nl - 3) / MPA_TB_BLOCK : 0) * 9 * 64; }
+MPA_DPP_HD int64_t lite_bits_dwords(int cls, int32_t max_nl)
+{
+	return cls == T_LITE_W8 ? lite_group_bits_dwords(MPA_LITE_W8_WAVES, max_nl) : cls == T_LITE_W4 ? lite_wide_bits_dwords(max_nl) : ((int64_t)max_nl / 3 + 2) * 64;
+}
+MPA_DPP_HD int64_t lite_ckpt_dwords(int cls, int32_t max_nl)
+{
+	return cls == T_LITE_W8 ? lite_group_ckpt_dwords(MPA_LITE_W8_WAVES, max_nl) : cls == T_LITE_W4 ? lite_wide_ckpt_dwords(max_nl) : (int64_t)(max_nl > 3 ? (max_nl - 3) / MPA_TB_BLOCK : 0) * 9 * 64;
+}
 
 // values the executor has when it plans (the environment is read by the executor: at context creation, or once per process)
 struct DpPlanKnobs {
 	int32_t lite_min = 384, lite_wide = 0;      // checkpointed traceback: from this many rows; 129..256 columns included
+	int32_t lite_w8 = 0;                        // ... 257..512 columns included (MPA_DP_LITE_W8; independent of lite_wide; not with the pool)
 	int32_t no_split = 0;                       // repeated round: no inter-workgroup hand-off
 	int32_t split_wide = 0;                     // MPA_DP_SPLIT_WIDE: 1025..3072-column extension calls on X_SPLIT8 / X_SPLIT12 (not with the pool, not in a repeated round)
 	int32_t antidiag = 0;                       // (measurement) the 32-column extension class runs on k_ext_antidiag
@@ -128,6 +135,8 @@ MPA_DPP_HD int dp_classify_call(const mpa_dp_task_t &x, int32_t k, int32_t n_ctg
 		const bool many_rows = kn.lite_min > 0 && packed_ok && x.nl >= kn.lite_min && x.nl >= 3;
 		if (many_rows && t.cls <= T_W2) t.cls += T_LITE16, t.pw = lite_columns(t.cls);
 		else if (many_rows && t.cls == T_W4 && kn.lite_wide && !kn.pool) t.cls = T_LITE_W4, t.pw = lite_columns(T_LITE_W4);
+		// 257..512 columns under the same predicate with lite_w8 (MPA_DP_LITE_W8=1, a knob of its own): an eight-wave group per pair of calls
+		else if (many_rows && t.cls == T_W8 && kn.lite_w8 && !kn.pool) t.cls = T_LITE_W8, t.pw = lite_columns(T_LITE_W8);
 	}
 	return DP_CALL_OK;
 }
@@ -203,7 +212,7 @@ struct TeamOne {
 	void flag(int64_t *dst, int64_t bits) const { *dst |= bits; }
 };
 
-enum : int64_t { DPP_REFUSED = 1, DPP_HUGE = 2 };      // DpDevHead::status: a call the host planner refuses; a call of class X_HUGE
+enum : int64_t { DPP_REFUSED = 1, DPP_HUGE = 2, DPP_LITE_W8 = 4 };   // DpDevHead::status: a call the host planner refuses; a call of class X_HUGE; of class T_LITE_W8
 enum { DPP_S_REC = 0, DPP_S_PROF, DPP_S_PREP, DPP_S_CIG, DPP_S_BND, DPP_S_TB, DPP_NSUM };                 // what the layout scans, in sorted order
 enum { DPP_ST_CELLS_EXT = 0, DPP_ST_BYTES_EXT, DPP_ST_CELLS_GLOB, DPP_ST_BYTES_GLOB, DPP_ST_N_CKPT, DPP_ST_CELLS_CKPT, DPP_ST_N_WIDE, DPP_ST_CELLS_WIDE, DPP_ST_CELLS_OWN, DPP_NST };
 typedef DpVec<DPP_NSUM> DpSums;
@@ -293,6 +302,9 @@ template<typename Team> MPA_DPP_HD void dpp_classify(const Team &tm, const DpDev
 			t = DTask(), t.al = 1, t.ncol = 8, t.pw = 16, t.cls = X_16, t.out_idx = (int32_t)k, is_ext = true;
 		}
 		if (is_ext && t.cls == X_HUGE) tm.flag(&D.head->status, DPP_HUGE);
+		// (the later stages do not know the eight-wave checkpointed class: the round goes to the host planner, and until the host has
+		// seen the flag the call stands in the stages as the plain T_W8 call it would be without the knob)
+		if (!is_ext && t.cls == T_LITE_W8) tm.flag(&D.head->status, DPP_LITE_W8), t.cls = T_W8, t.pw = t.ncol;
 		D.tasks[k] = t;
 		D.key[k] = dp_call_key(is_ext, t.cls, t.nl, (int32_t)k);
 		// the statistics that follow from the plan (cells = (nl-2) * 8*ceil(al/8); algorithmic bytes per call)

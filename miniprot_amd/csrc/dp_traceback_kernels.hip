@@ -1,8 +1,8 @@
 // dp_traceback_kernels.hip -- the traceback launches outside the round kernel: k_glob_narrow / k_glob_wide (the int32 traceback sweeps
 // glob_narrow / glob_wide_body of dp_kernels.hip as launches of their own: the traceback chunks after a round's first, the 512/1024-
 // thread classes, and every traceback of a run whose penalties do not fit a record's byte), k_backtrack (the walk over traceback
-// words), k_walk / walk_call (the walk of the checkpointed traceback, which sweeps a block of rows again where the path is not in a
-// run) and k_cigar_gather (the dense copy of the CIGARs).  Launched by dp_exec.hip behind the round's sweeps (phase 4); none of this
+// words), k_walk / k_walk_w8 / walk_call (the walk of the checkpointed traceback, which sweeps a block of rows again where the path is
+// not in a run) and k_cigar_gather (the dense copy of the CIGARs).  Launched by dp_exec.hip behind the round's sweeps (phase 4); none of this
 // code runs inside k_dp_round or k_dp_worker.
 // Included by dp_exec.hip behind dp_kernels.hip.  Relies on dp_kernels.hip for: WavePos / whole_block, wave_sync, GlobArgs, GlobResume,
 // glob_narrow, glob_wide_body and GLOB_NARROW_LDS; on dp_device.h for the layout of the extension-bit words and checkpoints.
@@ -142,43 +142,48 @@ struct WalkArgs {
 	int32_t *n_cigar;
 	unsigned long long *n_blocks; // (statistics) blocks recomputed
 };
-// (per class of the packed sweep -- 16 / 32 / 64 / 128 / 256 columns at most: 8 / 11 / 17 / 29 / 53 KB; one launch per class, so that the narrow
-// calls' walks, most of them, take LDS for their own block of direction words and not for a 256-column one)
+// (per class of the packed sweep -- 16 / 32 / 64 / 128 / 256 / 512 columns at most: 8 / 11 / 17 / 29 / 53 / 101 KB; one launch per class, so that the
+// narrow calls' walks, most of them, take LDS for their own block of direction words and not for a 256- or 512-column one)
 #define WALK_LDS(NC) (GLOB_NARROW_LDS + (size_t)MPA_TB_BLOCK * (NC) * 2 + (size_t)(MPA_TB_BLOCK + 2) * 16)
 // DUAL: a call of 65..128 columns, swept with column c + 64 in the high half of lane c (ext_narrow<64, true, true>) and recomputed
 // by the block-major traceback sweep (two blocks of 64 columns, boundary records in LDS)
 // WIDE4: a call of 129..256 columns, swept by a four-wave group (lite_wide_body; the call is int16 half `slot` of every lane) and
 // recomputed by the same block-major sweep over up to four blocks of 64 columns, each from the checkpoint of the wave that swept it
+// DUAL and WIDE4 together: a call of 257..512 columns, swept by an EIGHT-wave group (k_walk_w8; the same template parameters, so that the
+// instances k_walk is made of keep their names and k_walk its code object): everything of WIDE4 with GW = 8 waves, up to eight blocks of
+// 64 columns whose (checkpoint, shift) pairs are worked out per column block from the first (glob_narrow's CKSTEP), not held for all eight
 template<int G, bool DUAL = false, bool WIDE4 = false>
 __device__ __forceinline__ void walk_call(const WalkArgs &wa, const DTask &t, const int32_t tid, char *lds, const int lane)
 {
+	constexpr int GW = WIDE4 ? (DUAL ? MPA_LITE_W8_WAVES : MPA_LITE_WIDE_WAVES) : 0;   // the waves of the group that swept the call (its int16 half is its slot)
+	constexpr bool DUAL2 = DUAL && !WIDE4;                         // the 65..128-column class proper
 	static_assert(!(DUAL || WIDE4) || G == 64, "the block-major classes are swept in blocks of 64 columns");
 	constexpr int NG = 64 / G;
-	const int slot = DUAL ? 0 : (t.flag >> MPA_LITE_SLOT_SHIFT) & 15, half = WIDE4 ? slot : slot / NG, lane0 = WIDE4 ? 0 : (slot % NG) * G;
+	const int slot = DUAL2 ? 0 : (t.flag >> MPA_LITE_SLOT_SHIFT) & 15, half = WIDE4 ? slot : slot / NG, lane0 = WIDE4 ? 0 : (slot % NG) * G;
 	const uint32_t *lite = wa.lite + t.tb_off + lane0;
 	uint16_t *tbs = (uint16_t*)(lds + GLOB_NARROW_LDS);            // [MPA_TB_BLOCK][ncol] words of the block that is materialised
-	int4 *bnds = (int4*)(lds + GLOB_NARROW_LDS + (size_t)MPA_TB_BLOCK * (WIDE4 ? 256 : DUAL ? 128 : G) * 2);
+	int4 *bnds = (int4*)(lds + GLOB_NARROW_LDS + (size_t)MPA_TB_BLOCK * (WIDE4 ? GW * 64 : DUAL ? 128 : G) * 2);
 	uint32_t *cig = wa.cig + t.cig_off;
 	const int32_t ncol = t.ncol, cap = t.cig_cap;
 	int32_t blk = -1, blk_lo = 0, blk_hi = 0;                      // the materialised block and its rows [blk_lo, blk_hi)
 	auto ensure = [&](const int32_t row) {
 		if (blk >= 0 && row >= blk_lo && row < blk_hi) return;
 		const int32_t b = (row - 2) / MPA_TB_BLOCK;
-		constexpr int NCB = WIDE4 ? 4 : DUAL ? 2 : 1;
+		constexpr int NCB = GW == 4 ? 4 : DUAL2 ? 2 : 1, CKSTEP = GW == 8 ? MPA_LITE_CKPT_WAVE_STEP : 0;
 		GlobResume<NCB> rz;
 		rz.row_off = b * MPA_TB_BLOCK, rz.n_rows = t.nl - 2 - rz.row_off < MPA_TB_BLOCK ? t.nl - 2 - rz.row_off : MPA_TB_BLOCK;
 #pragma unroll
 		for (int cb = 0; cb < NCB; ++cb) {
 			rz.ck[cb] = nullptr, rz.sh[cb] = 0;
 			if (b == 0) continue;
-			if (WIDE4) rz.ck[cb] = wa.ckpt + t.bnd_off + lite_wide_ckpt_at(b, 64 * cb, half, &rz.sh[cb]);
+			if (WIDE4) rz.ck[cb] = wa.ckpt + t.bnd_off + lite_group_ckpt_at(GW, b, 64 * cb, half, &rz.sh[cb]);
 			else rz.ck[cb] = wa.ckpt + t.bnd_off + (int64_t)(b - 1) * 9 * 64 + lane0, rz.sh[cb] = 16 * (DUAL ? cb : half);
 		}
 		rz.tb = tbs, rz.bnd = bnds;
 		GlobWave gw;
 		gw.task[0] = tid, gw.task[1] = gw.task[2] = gw.task[3] = -1, gw.max_nl = rz.n_rows + 2;
 		wave_sync();
-		glob_narrow<G, DUAL || WIDE4, false, false, NCB>(wa.ga, gw, WavePos{ lds, lane, 0, lane }, &rz);
+		glob_narrow<G, DUAL || WIDE4, false, false, NCB, CKSTEP>(wa.ga, gw, WavePos{ lds, lane, 0, lane }, &rz);
 		wave_sync();
 		blk = b, blk_lo = 2 + rz.row_off, blk_hi = blk_lo + rz.n_rows;
 		if (lane == 0) atomicAdd(wa.n_blocks, 1ULL);
@@ -187,7 +192,7 @@ __device__ __forceinline__ void walk_call(const WalkArgs &wa, const DTask &t, co
 	auto nibble = [&](const int32_t ii, const int32_t jj) -> int32_t {
 		if (WIDE4) {
 			int32_t sh;
-			const int64_t at = lite_wide_bit_at(ii, jj, half, &sh);
+			const int64_t at = lite_group_bit_at(GW, ii, jj, half, &sh);
 			return (int32_t)(lite[at] >> sh) & 0xf;
 		}
 		const uint32_t r = (uint32_t)(ii - 2);
@@ -271,6 +276,16 @@ __global__ __launch_bounds__(64) void k_walk(WalkArgs wa)
 	case T_LITE_W4: walk_call<64, false, true>(wa, t, tid, (char*)lds_raw, lane); break;   // 129..256 columns, a four-wave group per pair of calls
 	default: break;
 	}
+}
+// the walk of the 257..512-column class (T_LITE_W8), a kernel of its own: its block of direction words takes WALK_LDS(512) and its
+// recomputation goes over up to eight column blocks -- inside k_walk it would set that kernel's registers and LDS for every class
+__global__ __launch_bounds__(64) void k_walk_w8(WalkArgs wa)
+{
+	extern __shared__ __attribute__((aligned(16))) uint32_t lds_raw[];
+	if ((int32_t)blockIdx.x >= wa.n_list) return;
+	const int32_t tid = wa.list[blockIdx.x];
+	const DTask t = wa.ga.tasks[tid];
+	if (t.cls == T_LITE_W8) walk_call<64, true, true>(wa, t, tid, (char*)lds_raw, (int)threadIdx.x);   // (DUAL and WIDE4: the eight-wave class)
 }
 
 // dense copy of the CIGARs: every call's slot was sized for the worst case, only n_cigar words are real

@@ -63,6 +63,23 @@ extern "C" int64_t mpa_dbg_dp_plan_wide(const mpa_dpopt_t *opt, int32_t n_ctg, c
 	});
 }
 
+// (knobs[10]: the nine of mpa_dbg_dp_plan_wide, then lite_w8 as the executor passes it -- off with the pool)
+extern "C" int64_t mpa_dbg_dp_plan_w8(const mpa_dpopt_t *opt, int32_t n_ctg, const int64_t *ctg_len, int32_t n_seq, const int64_t *q_off, int64_t n, const mpa_dp_task_t *tasks,
+                                      const int64_t *knobs, void *buf, int64_t cap)
+{
+	return mpa::guarded<int64_t>(MPA_ERR_HIP, [&]() -> int64_t {
+		if (!opt || !q_off || !knobs || n_seq < 0 || n_ctg < 0 || (n_ctg > 0 && !ctg_len) || (n > 0 && !tasks)) { set_error("mpa_dbg_dp_plan_w8: missing arguments"); return MPA_ERR_ARG; }
+		DpPlanKnobs kn = knobs_of(knobs, true);
+		kn.lite_w8 = knobs[9] && !kn.pool;
+		const mpa_qbatch_t q{ n_seq, nullptr, q_off };
+		DpPlan plan;
+		int64_t r = dp_plan(tasks, n, ctg_len, sizeof(int64_t), n_ctg, &q, opt, kn, dp_round_args_bytes(), plan);
+		if (r == MPA_OK) r = dp_plan_serialize(plan, kn, buf, cap, true, true);
+		if (r < 0) set_error(plan.err);
+		return r;
+	});
+}
+
 extern "C" int mpa_dbg_dp_last_classes(const mpa_ctx_t *ctx, int64_t ext_calls[16])
 {
 	if (!ctx || !ext_calls) { set_error("mpa_dbg_dp_last_classes: missing arguments"); return MPA_ERR_ARG; }
@@ -81,6 +98,13 @@ extern "C" int mpa_dbg_dp_last_mb(const mpa_ctx_t *ctx, int64_t out[4])
 {
 	if (!ctx || !out) { set_error("mpa_dbg_dp_last_mb: missing arguments"); return MPA_ERR_ARG; }
 	dp_last_mb(ctx, out);
+	return MPA_OK;
+}
+
+extern "C" int mpa_dbg_dp_last_w8(const mpa_ctx_t *ctx, int64_t out[4])
+{
+	if (!ctx || !out) { set_error("mpa_dbg_dp_last_w8: missing arguments"); return MPA_ERR_ARG; }
+	dp_last_w8(ctx, out);
 	return MPA_OK;
 }
 

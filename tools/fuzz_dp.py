@@ -1,6 +1,7 @@
 """Randomised parity of mpa_dp_run() against the oracle: python tools/fuzz_dp.py [seconds] [first seed].  Every call class of the
 round kernel (asm extension rows, the 128-column one-call-per-wave classes, the checkpointed traceback at several row thresholds, its 129..256-column class included;
-third argument "wide": the multi-wave extension classes of 129..1024 columns)."""
+third argument "wide": the multi-wave extension classes of 129..1024 columns -- and, among its traceback calls, the 257..512-column
+checkpointed class, MPA_DP_LITE_W8, which the run sets like MPA_DP_LITE_WIDE unless the environment says otherwise)."""
 import sys, os, time
 sys.path.insert(0, "tests"); sys.path.insert(0, ".")
 import numpy as np, miniprot_amd as mpa, refbind
@@ -10,6 +11,7 @@ budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
 wide = len(sys.argv) > 3 and sys.argv[3] == "wide"     # the multi-wave extension classes: 129..1024 columns, pairs of calls, split groups
 os.environ.setdefault("MPA_DP_LITE_WIDE", "1")            # the 129..256-column checkpointed class is off by default: the fuzz run covers it
+os.environ.setdefault("MPA_DP_LITE_W8", "1")              # ... and so does the 257..512-column one (calls of that width: the "wide" run)
 t0 = time.time()
 n_calls = n_bad = 0
 while time.time() - t0 < budget:
@@ -30,10 +32,11 @@ while time.time() - t0 < budget:
     ctx = mpa.Context(0); idx = mpa.Index.from_nt4(contigs); idx.to_device(ctx)
     rst, cig = mpa.dp_run(ctx, idx, dpopt_from_params(P), queries, tasks)
     st = ctx.dp_stats()
+    w8 = mpa.dbg_dp_last_w8(ctx)
     bad, msg = compare(rst, cig, oracle_eval(pairs, meta, P), meta, pairs)
     idx.close(); ctx.close()
     n_calls += len(tasks); n_bad += len(bad)
-    print("seed %d lite_min %s go %d ge %d io %d fs %d xdrop %d: %d calls (%d + %d wide checkpointed, %d blocks recomputed), %d differ" % (seed, os.environ["MPA_DP_LITE_MIN"], P.go, P.ge, P.io, P.fs, P.xdrop, len(tasks), st["n_ckpt"], st["n_ckpt_wide"], st["walk_blocks"], len(bad)), flush=True)
+    print("seed %d lite_min %s go %d ge %d io %d fs %d xdrop %d: %d calls (%d + %d wide checkpointed, %d of them in %d eight-wave groups, %d blocks recomputed), %d differ" % (seed, os.environ["MPA_DP_LITE_MIN"], P.go, P.ge, P.io, P.fs, P.xdrop, len(tasks), st["n_ckpt"], st["n_ckpt_wide"], w8[0], w8[2], st["walk_blocks"], len(bad)), flush=True)
     if bad:
         print(msg[:2000])
     seed += 1

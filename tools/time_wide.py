@@ -12,7 +12,13 @@ python tools/time_wide.py mb_wg [repeats]: the table of MPA_DP_MB_WG -- a pair o
 2 000, 2 600 and 3 300 columns (class T_MB), knob off (one wave per call, in the round kernel) and knob on (k_glob_mb_wg, one wave per
 column block), interleaved; the clock is ms_glob, the traceback sweeps of the batch; the two legs' records and CIGAR pools must agree.
 Then ms_total of the mixed batch of the tests (tests/mbwg.py, mixed_table: T_MB calls of 17, 33 and 49 blocks next to 40 ordinary
-pairs), the same way."""
+pairs), the same way.
+python tools/time_wide.py lite_w8 [repeats]: the table of MPA_DP_LITE_W8 -- 1, 2 and 64 traceback calls (flag 1) of 20 000 rows at 264, 384
+and 512 columns, knob off (the plain int32 sweep k_glob_wide<8> + k_backtrack) and knob on (k_lite_w8 + k_walk_w8), interleaved on one
+device; per leg the sweep (ms_glob) as ns per row, ms_backtrack (k_backtrack; the checkpointed walk is not timed apart), the batch on the
+device (ms_total) and what is left of it behind prep and sweep -- with the knob on: the walk and the downloads --, the blocks walked, and
+the bytes of traceback memory the leg asks for (off: the matrix of direction words; on: bit words and checkpoints).  The two legs'
+records and CIGAR pools must agree."""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, ROOT)
@@ -154,6 +160,56 @@ def mb_wg_table(repeats, nl=20000, n=2):
             print("%4d %24s %12.3f %12.3f %12.3f %12.3f %12.3f %12.3f" % (rep, mb[0] + "|" + mb[1], st[0]["ms_total"], st[1]["ms_total"], st[0]["ms_glob"], st[1]["ms_glob"], st[0]["ms_round"], st[1]["ms_round"]))
 
 
+def lite_w8_table(repeats, nl=20000):
+    rng = np.random.default_rng(1)
+    n_max = 64
+    g = rng.integers(0, 4, nl * n_max + 1000).astype(np.uint8)
+    idx = mpa.Index.from_nt4([g], ["c"])
+    os.environ["MPA_DP_LITE_WIDE"] = "0"
+    ctxs = {}
+    for knob in (0, 1):                                # the knob is read when a context is created
+        os.environ["MPA_DP_LITE_W8"] = str(knob)
+        ctxs[knob] = mpa.Context(0)
+        idx.to_device(ctxs[knob])
+    dp = mpa.dpopt_from(mpa.default_mapopt())
+    print("# traceback calls of %d rows; sweep: ms_glob as ns per row (off: k_glob_wide<8>, one call per 512-thread group; on: k_lite_w8, two calls per group);" % nl)
+    print("# bt: ms_backtrack (off: k_backtrack); total: ms_total, the batch on the device; rest: ms_total - ms_prep - ms_glob (on: k_walk_w8 and the downloads) and its share of total;")
+    print("# tb bytes: off 2 B per cell of nl x ncol, on 4 B per bit word and checkpoint dword of the eight-wave groups; w8: mpa_dbg_dp_last_w8 of the on leg")
+    print("%4s %3s %4s %11s %11s %7s %8s %8s %9s %9s %9s %9s %6s %13s %12s %s" % ("al", "n", "rep", "off ns/row", "on ns/row", "off/on", "off bt", "on bt", "off total", "on total", "off rest", "on rest", "share", "off tb bytes", "on tb bytes", "w8"))
+    for al in (264, 384, 512):
+        ncol = (al + 7) // 8 * 8
+        for n in (1, 2, 64):
+            aa = bytes(rng.choice(list(b"ACDEFGHIKLMNPQRSTVWY"), al * n).tolist())
+            q = mpa.Queries([aa[i * al:(i + 1) * al] for i in range(n)])
+            tasks = np.zeros(n, mpa.DP_TASK)
+            for i in range(n):
+                tasks[i]["nt_off"] = i * nl; tasks[i]["nl"] = nl; tasks[i]["qid"] = i; tasks[i]["al"] = al; tasks[i]["flag"] = 1; tasks[i]["io"] = 29
+            groups = (n + 1) // 2
+            tb_off = 2 * n * nl * ncol
+            tb_on = 4 * groups * ((nl // 3 + 2) * 512 + (nl - 3) // 96 * 9 * 512)
+            for rep in range(repeats + 1):             # (the first pair of legs warms both contexts up and is not printed)
+                st, out, w8 = {}, {}, None
+                for knob in (0, 1):
+                    rst, cig = mpa.dp_run(ctxs[knob], idx, dp, q, tasks)
+                    out[knob] = ([tuple(r) for r in rst], np.asarray(cig).tobytes())
+                    st[knob] = ctxs[knob].dp_stats()
+                    if knob:
+                        w8 = mpa.dbg_dp_last_w8(ctxs[knob])
+                if out[0] != out[1]:
+                    sys.exit("the two legs' records or CIGAR pools differ at %d columns, %d calls" % (al, n))
+                if w8[0] != n or mpa.dbg_dp_last_w8(ctxs[0])[0] != 0:
+                    sys.exit("routing: %s calls of the class with the knob on" % (w8,))
+                if rep:
+                    ns = [st[k]["ms_glob"] * 1e6 / nl for k in (0, 1)]
+                    rest = [st[k]["ms_total"] - st[k]["ms_prep"] - st[k]["ms_glob"] for k in (0, 1)]
+                    print("%4d %3d %4d %11.1f %11.1f %7.2f %8.3f %8.3f %9.3f %9.3f %9.3f %9.3f %6.2f %13d %12d %s" % (al, n, rep, ns[0], ns[1], ns[0] / ns[1], st[0]["ms_backtrack"], st[1]["ms_backtrack"],
+                          st[0]["ms_total"], st[1]["ms_total"], rest[0], rest[1], rest[1] / st[1]["ms_total"], tb_off, tb_on, ",".join(str(x) for x in w8)))
+    idx.close()
+
+
+if sys.argv[1] == "lite_w8":
+    lite_w8_table(int(sys.argv[2]) if len(sys.argv) > 2 else 3)
+    sys.exit(0)
 if sys.argv[1] == "mb_wg":
     mb_wg_table(int(sys.argv[2]) if len(sys.argv) > 2 else 3)
     sys.exit(0)
